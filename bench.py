@@ -16,6 +16,10 @@ Multi-GPU: one process per GPU (torchrun), instances sharded with no data-path c
 recorded trajectories of all ranks are collected on rank 0 in time chunks (--chunks launches per rollout through the k0
 continuation of cclqr_rollout_dev; chunk c travels over RCCL on a second stream while chunk c+1 is computed) and the final
 states with one more gather ("scaling": "weak").  RCCL is mandatory for --gpus > 1: gloo has to be asked for (--allow-gloo).
+
+A plain run does only what the headline line needs: set-up, warm-up, the --steps timed steps, --dump-outputs if asked, the JSON line.
+Everything else it can measure (warm LQR construction, fp64 roofline by counted flops, CPU baseline, the other BASELINE configs, the
+newton_mode 1 line) runs with --full only.
 """
 import argparse
 import hashlib
@@ -96,6 +100,32 @@ def build_workload(pkg, n_links, n_inst, seed, rank):
     return ex, mech, zd, z0
 
 
+DUMP_BYTES = {"final_states": 24_000_000, "trajectory": 36_000_000, "status": 2_000_000}     # 62 MB at most in all
+
+
+def _rows_within(torch, x, budget, seed):
+    """x [rows][...] on the device -> float64 numpy array: all of it when it fits `budget` bytes, else a fixed seeded sample of its rows (sorted)"""
+    row_bytes = 8 * max(1, x[0].numel()) if x.shape[0] else 8
+    if x.shape[0] * row_bytes <= budget:
+        return x.double().cpu().numpy()
+    rows = np.sort(np.random.default_rng(seed).choice(x.shape[0], max(1, budget // row_bytes), replace=False))
+    return x.index_select(0, torch.from_numpy(rows).to(x.device)).double().cpu().numpy()
+
+
+def dump_outputs(out_dir, torch, zT, traj, status):
+    """--dump-outputs: final states, Newton status and (with record) the trajectory of the last timed step as DIR/<name>.npy, float64"""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"final_states": _rows_within(torch, zT, DUMP_BYTES["final_states"], 1),
+              "status": _rows_within(torch, status, DUMP_BYTES["status"], 2)}
+    if traj is not None:
+        flat = traj.reshape((-1,) + tuple(traj.shape[2:]))          # (instance, step) rows
+        a = _rows_within(torch, flat, DUMP_BYTES["trajectory"], 3)
+        arrays["trajectory"] = a.reshape(traj.shape) if a.shape[0] == flat.shape[0] else a
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    print("[bench] outputs of the last timed step in %s: %s" % (out_dir, ", ".join("%s %s" % (k, list(v.shape)) for k, v in arrays.items())), file=sys.stderr)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -119,6 +149,15 @@ def main():
     ap.add_argument("--rehearse-shared-gpu", action="store_true",
                     help="rehearsal of the N>1 path on a 1-GPU box: every rank uses cuda:0 and the collective runs over gloo "
                          "(RCCL refuses two ranks on one device); the JSON line is marked and is not a scaling measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need (off by default): the warm LQR construction, the fp64 roofline from "
+                         "flops counted by the instrumented oracle, the CPU baseline, the other BASELINE configs and the newton_mode 1 line "
+                         "(--no-cpu-baseline / --no-extra leave parts of it out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step handed back to DIR/<name>.npy as float64 (64 MB at most in "
+                         "all): final_states [n][nb][13], status [n] (Newton status per instance, rank 0's shard) and, with record, "
+                         "trajectory [n][T][nb][13]; an array larger than its share is a fixed seeded sample of its rows (instances, or "
+                         "(instance, step) pairs of the trajectory), so runs with the same arguments compare output for output")
     args = ap.parse_args()
     if args.gpus > 1 and "RANK" not in os.environ and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(sys.argv[1:], args.gpus))
@@ -151,10 +190,12 @@ def main():
     lqr = pkg.LQR(mech, [pkg.getid(b) for b in ex["bodies"]], [pkg.getid(ex["ctrl"][0])], ex["Q"], ex["R"], T * t.dt,
                   xd=[zd[i, 0:3] for i in range(nb)], qd=[zd[i, 3:7] for i in range(nb)])
     setup_s = time.time() - t0
-    t0 = time.time()            # the same construction again: without the first call's code-object load and workspace allocation
-    pkg.LQR(mech, [pkg.getid(b) for b in ex["bodies"]], [pkg.getid(ex["ctrl"][0])], ex["Q"], ex["R"], T * t.dt,
-            xd=[zd[i, 0:3] for i in range(nb)], qd=[zd[i, 3:7] for i in range(nb)])
-    setup_warm_s = time.time() - t0
+    setup_warm_s = None
+    if args.full:
+        t0 = time.time()            # the same construction again: without the first call's code-object load and workspace allocation
+        pkg.LQR(mech, [pkg.getid(b) for b in ex["bodies"]], [pkg.getid(ex["ctrl"][0])], ex["Q"], ex["R"], T * t.dt,
+                xd=[zd[i, 0:3] for i in range(nb)], qd=[zd[i, 3:7] for i in range(nb)])
+        setup_warm_s = time.time() - t0
     mh = mech._cclqr_handle
     ctrl = lqr._ctrl_handle(mh)
     lanes, lds_bytes = mh.geometry()
@@ -230,13 +271,17 @@ def main():
     if world > 1:
         dist.barrier()
     t0 = time.perf_counter()
+    zT_out = None
     for i in range(args.steps):
-        one_rollout(True)
+        zT_out = one_rollout(True)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
     elapsed = pkg.dist.max_over_ranks(elapsed, dev)
+    if args.dump_outputs and rank == 0:
+        # what the caller of the timed path holds after its last step: rank 0's final states of all ranks, the collected (or the rank's own) trajectory
+        dump_outputs(args.dump_outputs, torch, zT_out if zT_out is not None else zT_d, tg.out if tg is not None else traj_d, st_d)
     kern_ms_launch = float(np.mean([a.elapsed_time(b) for a, b in kern_ev])) if kern_ev else float("nan")   # average launch
     kern_ms = kern_ms_launch * chunks                                                                      # kernel time of one rollout
     status = st_d.cpu().numpy()
@@ -283,9 +328,12 @@ def main():
                        "rank0_allocation_plan_gb": round(plan["total"] / 1e9, 3),
                        "exposed_ms_per_rollout": 1e3 * elapsed / max(1, args.steps) - kern_ms},
         "newton": {"max_iters_mean": float(status.mean()), "max_iters_max": int(status.max()), "failed_instances": n_bad},
-        "setup": {"lqr_construct_s": setup_s, "lqr_construct_warm_s": setup_warm_s, "riccati_kbreak": int(lqr.kbreak)},
+        "setup": {"lqr_construct_s": setup_s, "riccati_kbreak": int(lqr.kbreak)}, "full": bool(args.full),
     }
-    if not args.no_cpu_baseline:
+    if setup_warm_s is not None:
+        out["setup"]["lqr_construct_warm_s"] = setup_warm_s
+    # everything below takes work of its own beyond the headline figure: --full only
+    if args.full and not args.no_cpu_baseline:
         # The kernel is bound by the fp64 vector ALU, not by HBM: with the flops of one instance-step counted by the
         # instrumented oracle on this workload, `roofline` carries THAT bound and keeps the HBM figures beside it.
         f_step = count_flops(pkg, t, lqr, z0, T)
@@ -297,9 +345,9 @@ def main():
                            **{k: hbm[k] for k in ("kernel", "kernel_ms", "launches_per_rollout", "algorithmic_bytes_per_instance_step", "kernel_source_sha")},
                            "note": "fp64 vector ALU is the binding unit (256 CU x 4 SIMD x 16 fp64 lanes x 2 flop x 2.4 GHz = 78.6 TFLOP/s); "
                                    "HBM carries only the recorded trajectory (traffic < algorithmic bytes: state never leaves the chip)"}
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         out.update(cpu_baseline(pkg, t, lqr, z0, T))
-    if world == 1 and not args.no_extra:
+    if args.full and world == 1 and not args.no_extra:
         out["extra"] = extra_workloads(pkg, capi, torch, dev, setup_s, lqr, mx, mu, ml, T, args)
         if record and chunks == 1:
             try:

@@ -695,14 +695,14 @@ def test_riccati_bf16_split_mode_error_is_measured(cclqr, orc):
 
 
 def test_bench_line_contract(tmp_path):
-    """`python bench.py` prints ONE JSON line with the fields the driver reads: metric/value/unit, n_gpus, steps, warmup, ms_per_step,
+    """`python bench.py --full` prints ONE JSON line with the fields the driver reads: metric/value/unit, n_gpus, steps, warmup, ms_per_step,
     scaling, dtype, config.workload, roofline {bound, achieved, peak, unit, frac, traffic}, cpu_baseline {value, unit, cores, kind, sample}"""
     import json
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "1", "--warmup", "1", "--instances", "512", "--sim-steps", "40",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", "1", "--warmup", "1", "--instances", "512", "--sim-steps", "40",
                         "--cpu-sample", "64"], capture_output=True, text=True, timeout=600, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [x for x in r.stdout.splitlines() if x.strip()]
@@ -717,6 +717,47 @@ def test_bench_line_contract(tmp_path):
     assert abs(d["roofline"]["frac"] - d["roofline"]["achieved"] / d["roofline"]["peak"]) < 1e-12
     assert set(("value", "unit", "cores", "kind", "sample")) <= set(d["cpu_baseline"]) and d["cpu_baseline"]["kind"] in ("port", "reference")
     assert abs(d["value"] - 512 * 40 / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+    assert d["roofline"]["bound"] == "fp64_valu" and "extra" in d and "lqr_construct_warm_s" in d["setup"]
+
+
+def test_bench_plain_run_and_dumped_outputs(cclqr, orc, tmp_path):
+    """a plain `python bench.py` (no --full) prints the headline line only -- no CPU baseline, no extra configs -- and --dump-outputs DIR writes what the
+    last timed step computed as float64 .npy files: the same for every run with the same workload arguments, whatever --steps / --warmup say, and equal
+    to the oracle's rollout of the same starts (bench.build_workload, seed 0) under the same LQR"""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    n, T = 64, 40
+    dumps = []
+    for steps, warmup in ((2, 1), (1, 0)):
+        d_out = tmp_path / ("dump_%d_%d" % (steps, warmup))
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", str(steps), "--warmup", str(warmup), "--instances", str(n),
+                            "--sim-steps", str(T), "--dump-outputs", str(d_out)], capture_output=True, text=True, timeout=300, cwd=root)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [x for x in r.stdout.splitlines() if x.strip()]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        assert d["steps"] == steps and d["warmup"] == warmup and d["full"] is False and d["value"] > 0
+        assert abs(d["value"] - n * T / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+        assert "cpu_baseline" not in d and "extra" not in d and d["roofline"]["bound"] == "hbm"
+        files = sorted(os.listdir(d_out))
+        assert files == ["final_states.npy", "status.npy", "trajectory.npy"], files
+        arrs = {f[:-4]: np.load(os.path.join(d_out, f)) for f in files}
+        assert all(a.dtype == np.float64 for a in arrs.values()) and sum(a.nbytes for a in arrs.values()) <= 64 << 20
+        assert arrs["final_states"].shape == (n, 17, 13) and arrs["trajectory"].shape == (n, T, 17, 13) and arrs["status"].shape == (n,)
+        dumps.append(arrs)
+    for k in dumps[0]:
+        assert np.array_equal(dumps[0][k], dumps[1][k]), k
+    import bench
+    ex, mech, zd, z0 = bench.build_workload(cclqr, 16, n, 0, 0)
+    t = mech.tables()
+    lqr = cclqr.LQR(mech, [cclqr.getid(b) for b in ex["bodies"]], [cclqr.getid(ex["ctrl"][0])], ex["Q"], ex["R"], T * t.dt,
+                    xd=[zd[i, 0:3] for i in range(t.nb)], qd=[zd[i, 3:7] for i in range(t.nb)])
+    zT, traj, st = orc.rollout(t, orc.ctrl_desc(t.nb, lqr.ctrl_joints, K=lqr.K, N=lqr.N, zd=lqr.zd), z0, T, record=True)
+    assert (st > 0).all() and (dumps[0]["status"] > 0).all()
+    assert np.abs(dumps[0]["final_states"] - zT).max() < 1e-8 and np.abs(dumps[0]["trajectory"] - traj).max() < 1e-8
 
 
 def test_riccati_bf16_mode_on_the_batched_resident_kernel(cclqr, orc):

@@ -158,6 +158,35 @@ def test_bench_self_launch_starts_the_ranks_before_touching_the_gpu(tmp_path):
     assert not [x for x in r.stdout.splitlines() if x.strip().startswith("{")]
 
 
+def test_bench_dump_outputs_sample_within_budget(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: an array within its share is written whole, a larger one as the same seeded sample of its rows every time (trajectory rows
+    = (instance, step) pairs), float64 throughout; and --full is an option of the plain argument parser (a plain run leaves the extras out)"""
+    import torch
+    import bench
+    src = open(os.path.join(ROOT, "bench.py")).read()
+    assert '"--full"' in src and '"--dump-outputs"' in src
+    assert sum(bench.DUMP_BYTES.values()) <= 64 << 20
+    n, T, nb = 40, 30, 3
+    g = torch.Generator().manual_seed(0)
+    zT, traj = torch.randn(n, nb, 13, generator=g, dtype=torch.float64), torch.randn(n, T, nb, 13, generator=g, dtype=torch.float64)
+    st = torch.arange(1, n + 1, dtype=torch.int32)
+    bench.dump_outputs(str(tmp_path / "whole"), torch, zT, traj, st)
+    a = {k: np.load(str(tmp_path / "whole" / (k + ".npy"))) for k in ("final_states", "trajectory", "status")}
+    assert all(v.dtype == np.float64 for v in a.values())
+    assert np.array_equal(a["final_states"], zT.numpy()) and np.array_equal(a["trajectory"], traj.numpy()) and np.array_equal(a["status"], st.numpy())
+    row = nb * 13 * 8
+    monkeypatch.setattr(bench, "DUMP_BYTES", {"final_states": 10 * row, "trajectory": 100 * row, "status": 1 << 20})
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), torch, zT, traj, st)
+    s = [{k: np.load(str(tmp_path / d / (k + ".npy"))) for k in ("final_states", "trajectory")} for d in ("s1", "s2")]
+    assert s[0]["final_states"].shape == (10, nb, 13) and s[0]["trajectory"].shape == (100, nb, 13)
+    for k in s[0]:
+        assert np.array_equal(s[0][k], s[1][k]), k
+    flat = traj.reshape(n * T, nb, 13).numpy()
+    assert all((flat == r).all(axis=(1, 2)).any() for r in s[0]["trajectory"])          # every sampled row is a row of the trajectory
+    assert all((zT.numpy() == r).all(axis=(1, 2)).any() for r in s[0]["final_states"])
+
+
 def test_no_silent_gloo_fallback():
     """dist.init_from_env never replaces RCCL by gloo on its own: the only way to gloo is to ask for it by name"""
     src = open(os.path.join(ROOT, "constrainedcontrol.jl_amd", "dist.py")).read()
@@ -282,9 +311,8 @@ def test_sawyer_fixture_matches_reference_urdf_when_present(cclqr):
     import json
     tab = json.load(open(os.path.join(ROOT, "tests", "golden", "sawyer_arm_tables.json")))
     assert len(tab["joints"]) == 7 and len(tab["links"]) == 8
-    ref = "/root/reference/examples/examples_files/sawyer_arm.urdf"
-    if os.path.exists(ref):
-        assert cclqr.parse_urdf(ref) == tab
+    # the reference's examples_files/sawyer_arm.urdf, stored as a fixture
+    assert cclqr.parse_urdf(os.path.join(ROOT, "tests", "golden", "sawyer_arm.urdf")) == tab
     ex = cclqr.examples.sawyer(tab)
     assert len(ex["mech"].bodies) == 7 and ex["mech"].tables().ml == 35      # Nb = 7, mλ = 35
 
@@ -340,9 +368,8 @@ def test_sawyer_full_fixture_is_a_branching_robot(cclqr, orc):
     import json
     tab = json.load(open(os.path.join(ROOT, "tests", "golden", "sawyer_full_tables.json")))
     assert len(tab["links"]) == 24 and sum(j["type"] == "fixed" for j in tab["joints"]) == 15
-    ref = "/root/reference/examples/examples_files/sawyer.urdf"
-    if os.path.exists(ref):
-        assert cclqr.parse_urdf(ref, keep_fixed=True) == tab
+    # the reference's examples_files/sawyer.urdf, stored as a fixture
+    assert cclqr.parse_urdf(os.path.join(ROOT, "tests", "golden", "sawyer.urdf"), keep_fixed=True) == tab
     mech = cclqr.mechanism_from_urdf_tables(tab, g=0.0)
     t = mech.tables()
     assert t.nb == 8 and t.ne == 8 and sorted(e.name for e in mech.eqconstraints) == sorted(["head_pan"] + ["right_j%d" % i for i in range(7)])
