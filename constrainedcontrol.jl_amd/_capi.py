@@ -344,9 +344,10 @@ def riccati(A, Bu, Bl, G, Q, R, N, tol=1e-5, path=0, bf16_terms=0, keep_last=Fal
     mx = A.shape[-1]
     A = A.reshape(-1, mx, mx)
     nprob = A.shape[0]
-    Bu = f64(Bu).reshape(nprob, mx, -1)
+    Bu, Bl = f64(Bu), f64(Bl)
+    Bu = Bu.reshape(nprob, mx, Bu.shape[-1] if Bu.ndim > 1 else -1)      # (the trailing size stated: mu = 0 / ml = 0 leave nothing to infer -1 from)
     mu = Bu.shape[2]
-    Bl = f64(Bl).reshape(nprob, mx, -1)
+    Bl = Bl.reshape(nprob, mx, Bl.shape[-1] if Bl.ndim > 1 else -1)
     ml = Bl.shape[2]
     G = f64(G).reshape(nprob, ml, mx)
     Q, R = f64(Q).reshape(mx, mx), f64(R).reshape(mu, mu)
@@ -363,9 +364,10 @@ def riccati_tv(A, Bu, Bl, G, Q, R, N, tol=1e-5):
     A = f64(A)
     nk, mx = A.shape[0], A.shape[1]
     assert nk == N - 1
-    Bu = f64(Bu).reshape(nk, mx, -1)
+    Bu, Bl = f64(Bu), f64(Bl)
+    Bu = Bu.reshape(nk, mx, Bu.shape[-1] if Bu.ndim > 1 else -1)
     mu = Bu.shape[2]
-    Bl = f64(Bl).reshape(nk, mx, -1)
+    Bl = Bl.reshape(nk, mx, Bl.shape[-1] if Bl.ndim > 1 else -1)
     ml = Bl.shape[2]
     G = f64(G).reshape(nk, ml, mx)
     K = np.zeros((nk, mu, mx))

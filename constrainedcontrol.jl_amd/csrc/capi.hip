@@ -277,6 +277,7 @@ extern "C" int cclqr_ctrl_create_lqr_batch(const cclqr_mech* m, int32_t n_ctrl, 
     // dlqr for every setpoint (lqr.jl:141-184), gains written straight into the controller's table
     RicArgs ra;
     ra.nprob = n_ctrl; ra.mx = (int)mx; ra.mu = mu; ra.ml = (int)ml; ra.N = N; ra.time_varying = 0; ra.tol = tol; ra.path = 0; ra.bf16_terms = 0; ra.keep_last = inf ? 1 : 0; ra.kpad = (long long)padi;
+    ra.p_rows = (ric_symmetric(Q, (int)mx) && ric_symmetric(R, mu)) ? 0 : 1;
     const size_t wd = ric_total_work_doubles(ra);
     if (e == hipSuccess) e = ws_get((void**)&dQ, mx * mx * sizeof(double));
     if (e == hipSuccess) e = ws_get((void**)&dR, (size_t)(mu * mu + 1) * sizeof(double));
@@ -731,6 +732,7 @@ static int run_riccati(int nprob, int mx, int mu, int ml, int N, int time_varyin
     a.path = opts ? opts->path : 0;
     a.bf16_terms = opts ? opts->bf16_terms : 0;
     a.keep_last = keep_last;
+    a.p_rows = (ric_symmetric(Q, mx) && (mu == 0 || ric_symmetric(R, mu))) ? 0 : 1;
     if (a.path < 0 || a.path > 2 || a.bf16_terms < 0 || a.bf16_terms > 3) return fail(CCLQR_EINVAL, "riccati options: path in 0..2, bf16_terms in 0..3");
     const size_t wd = ric_total_work_doubles(a);
     hipError_t e = ws_get((void**)&dQ, (size_t)mx * mx * sizeof(double));

@@ -80,7 +80,15 @@ struct RicArgs {
     int bf16_terms;          // 0: fp64 MFMA; 1..3: split-bf16 products with fp32 accumulation (tiled path)
     int keep_last;           // 1: K is [nprob][mu][mx], the gain of the last executed backward step (= Ku[1] after the back-fill)
     long long kpad = 0;      // doubles left free between the tables of consecutive problems in K (0: contiguous)
+    int p_rows = 0;          // 1: Q or R is not symmetric (ric_symmetric on the host arrays): the kernels that assume a symmetric Pk are not used
 };
+// is the n x n row-major host matrix exactly symmetric?
+inline bool ric_symmetric(const double* X, int n) {
+    for (int i = 0; i < n; i++)
+        for (int j = i + 1; j < n; j++)
+            if (!(X[(size_t)i * n + j] == X[(size_t)j * n + i])) return false;
+    return true;
+}
 size_t ric_total_work_doubles(const RicArgs& a);
 hipError_t launch_riccati(const RicArgs& a, hipStream_t stream);
 

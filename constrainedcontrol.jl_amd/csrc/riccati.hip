@@ -212,9 +212,22 @@ struct RicGrid {
                        // lqr.jl:179-181 = the one gain LQR{T,Inf} keeps, lqr.jl:40-43); 0: the whole table K [nprob][N-1][mu][mx]
     int bf16_terms;    // 0: fp64 MFMA (parity mode); 1..3: the two mx^3 products of a backward step on bf16 MFMA with fp32 accumulation,
                        // every fp64 operand split into that many bf16 terms (measured-error mode, BASELINE configs[3]; tiled path only)
+    int p_rows;        // 1: Q or R is not symmetric, so neither is Pk: W = Pk [A'|D] reads Pk by rows (the reference's D'*Pk, lqr.jl:152-158);
+                       // 0: by columns (= rows of a symmetric Pk: the layout the MFMA A operand wants)
     unsigned char pp_mask[8];   // resident kernel, register-fragment form: bit ct of pp_mask[w] = wavefront w computes the 16x16 tile (its own
                                 // row strip, column tile ct) of the SYMMETRIC Pkp1 and mirrors it (ric_pp_assign)
 };
+
+// per knot: the pivots of its G Bλ LU, then [ml] = 1 if G Bλ is singular (set by ric_project_kernel, read when a backward step reaches the knot)
+__device__ inline int* ric_knot_piv(const RicGrid& a, size_t lin) {
+    const size_t sc = ((size_t)a.ml * a.ml + (size_t)a.ml * a.na + 3) & ~(size_t)1;
+    return (int*)(a.scratch + (size_t)a.nprob * a.nlin * sc) + lin * (a.ml + 2);
+}
+// is G Bλ of the model of backward step k singular?  The reference factors it inside the step (lqr.jl:151, lqr_tracking.jl:89), so a knot the
+// sweep never reaches -- below the break, or any knot with N = 1 -- is no error
+__device__ inline bool ric_knot_singular(const RicGrid& a, int prob, int k) {
+    return ric_knot_piv(a, (size_t)prob * a.nlin + (a.nlin > 1 ? k - 1 : 0))[a.ml] != 0;
+}
 
 template <bool LDSM>
 __global__ __launch_bounds__(RIC_THREADS) void ric_project_kernel(RicGrid a, int lds_cols) {
@@ -229,7 +242,7 @@ __global__ __launch_bounds__(RIC_THREADS) void ric_project_kernel(RicGrid a, int
     double* sc = a.scratch + lin * (((size_t)ml * ml + (size_t)ml * na + 3) & ~(size_t)1);
     double* GBlg = sc;
     double* X = sc + (((size_t)ml * ml + 1) & ~(size_t)1);
-    int* piv = (int*)(a.scratch + (size_t)a.nprob * a.nlin * (((size_t)ml * ml + (size_t)ml * na + 3) & ~(size_t)1)) + lin * (ml + 2);
+    int* piv = ric_knot_piv(a, lin);
     MP GBl = LDSM ? (MP)lds_M : (MP)GBlg;
     MP Xs = LDSM ? (MP)lds_M + (size_t)ml * ml : (MP) nullptr;
     if (tid == 0) sing = 0;
@@ -245,7 +258,9 @@ __global__ __launch_bounds__(RIC_THREADS) void ric_project_kernel(RicGrid a, int
         wg_gemm<false>(ml, na, mx, 1.0, G, mx, AD, na, 0.0, X, na);                      // [G*A | G*Bu]                 lqr.jl:158,154
         if (LDSM) { for (int e = tid; e < ml * ml; e += RIC_THREADS) GBl[e] = GBlg[e]; __syncthreads(); }
         wg_lu<MP>(ml, GBl, ml, piv, &sing);
-        if (sing) { if (tid == 0) { a.status[prob] = CCLQR_ESINGULAR_; a.stop[prob] = 1; a.kbreak[prob] = knot + 1; } return; }
+    }
+    if (tid == 0) piv[ml] = sing;      // the step that reaches this knot fails (ric_knot_singular); one that never does is no error
+    if (ml > 0 && !sing) {
         wg_lu_solve<MP>(ml, GBl, ml, piv, X, na, na, Xs, LDSM ? lds_cols : 0);           // X = (G Bλ)^-1 G [A | Bu]
         wg_gemm<false>(mx, na, ml, -1.0, Bl, ml, X, na, 1.0, AD, na);                    // [A' | D]                     lqr.jl:151
     }
@@ -376,6 +391,7 @@ __device__ inline bool ric_stopped(const RicGrid& a, int prob, int k, int ntile_
             for (int o = 32; o > 0; o >>= 1) tot += __shfl_xor(tot, o, 64);
             if (sqrt(tot) < a.tol) st = 2;                                            // if norm(Pk-Pkp1) < 1e-5  break   lqr.jl:172-174
         }
+        if (!st && ric_knot_singular(a, prob, k)) st = 3;                             // the step reaches a singular G Bλ      lqr.jl:151
         if (threadIdx.x == 0) *flag = st;
     }
     __syncthreads();
@@ -396,8 +412,9 @@ __global__ __launch_bounds__(TILE_THREADS) void ric_pa_kernel(RicGrid a, int k) 
     const bool iok[2] = {i0 + li < mx, i0 + 16 + li < mx}, jok[2] = {j0 + li < na, j0 + 16 + li < na};
     const int mu = a.mu, ti = blockIdx.x / a.tn;
     for (int t = tid; t < 32 * mu; t += TILE_THREADS) { const int r = t / mu, q = t % mu; Dl[t] = (i0 + r < mx) ? AD[(size_t)(i0 + r) * na + mx + q] : 0.0; }
+    const size_t sk = a.p_rows ? 1 : mx, si = a.p_rows ? mx : 1;       // A operand Pk[i][kk]: by rows, or by columns when Pk is symmetric
     tile_product(a.bf16_terms, mx,
-        [&](int kk, int h) { return iok[h] ? P[(size_t)kk * mx + i0 + 16 * h + li] : 0.0; },      // Pk symmetric
+        [&](int kk, int h) { return iok[h] ? P[kk * sk + (size_t)(i0 + 16 * h + li) * si] : 0.0; },
         [&](int kk, int h) { return jok[h] ? AD[(size_t)kk * na + j0 + 16 * h + li] : 0.0; }, red);
     for (int e = tid; e < 1024; e += TILE_THREADS) {
         const int i = i0 + (e >> 5), j = j0 + (e & 31);
@@ -430,6 +447,7 @@ __global__ __launch_bounds__(TILE_THREADS) void ric_gain_update_kernel(RicGrid a
     const bool lead = blockIdx.x == 0;
     if (ric_stopped(a, prob, k, a.tm * a.tm, &flag)) {
         if (lead && tid == 0 && flag == 2) { a.stop[prob] = 1; a.kbreak[prob] = k + 1; }
+        if (lead && tid == 0 && flag == 3) { a.status[prob] = CCLQR_ESINGULAR_; a.stop[prob] = 1; a.kbreak[prob] = k; }
         return;
     }
     double* TS = gl;
@@ -773,7 +791,6 @@ __global__ __launch_bounds__(RIC_THREADS) void riccati_resident_kernel(RicGrid a
     __shared__ int sing;
     const int prob = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = lane & 15, lk = lane >> 4;
     const int mx = NGT > 0 ? 4 * NGT : a.mx, mu = MUT > 0 ? MUT : a.mu, na = mx + mu, N = a.N;
-    if (a.stop[prob]) return;            // G Bλ was singular in the projection (status already set)
     lds_double* P = (lds_double*)rl;
     lds_double* W = P + (size_t)mx * mx;
     lds_double* Dl = W + (size_t)mx * na;
@@ -836,6 +853,7 @@ __global__ __launch_bounds__(RIC_THREADS) void riccati_resident_kernel(RicGrid a
     };
     if (N - 1 >= 1 && BF == 0) fetch_operands(N - 1);
     for (k = N - 1; k >= 1; k--) {                                        // for outer k=N-1:-1:1                    lqr.jl:150
+        if (ric_knot_singular(a, prob, k)) { status = CCLQR_ESINGULAR_; break; }       // G Bλ of this step singular   lqr.jl:151
         const double* AD = a.AD + ((size_t)prob * a.nlin + (a.nlin > 1 ? k - 1 : 0)) * mx * na;
         if (BF > 0) {                    // (the bf16 measured-error modes fetch at the top of the step: no registers to carry the fragment across the norm)
             fetch_operands(k);
@@ -863,12 +881,13 @@ __global__ __launch_bounds__(RIC_THREADS) void riccati_resident_kernel(RicGrid a
             }
             RWAVE(RP_WAVE_W, rw0);
         } else {
-            // W = Pk [A' | D]   (Pk symmetric)
+            // W = Pk [A' | D]; A operand Pk[i][k] by rows, or by columns when Pk is symmetric (p_rows)
+            const int sk = a.p_rows ? 1 : mx, si = a.p_rows ? mx : 1;
             for (int tile = wave; tile < t16m * t16n; tile += RIC_WAVES) {
                 const int i0 = (tile / t16n) << 4, j0 = (tile % t16n) << 4;
                 const bool iok = i0 + li < mx, jok = j0 + li < na;
                 const int ic = iok ? i0 + li : mx - 1, jc = jok ? j0 + li : na - 1;
-                const v4d acc = wave_tile16_db(mx >> 2, P + lk * mx + ic, 4 * mx, AD + (size_t)lk * na + jc, 4 * na);
+                const v4d acc = wave_tile16_db(mx >> 2, P + lk * sk + ic * si, 4 * sk, AD + (size_t)lk * na + jc, 4 * na);
                 if (jok) {
 #pragma unroll
                     for (int r = 0; r < 4; r++) { const int row = i0 + lk + 4 * r; if (row < mx) W[row * na + j0 + li] = acc[r]; }
@@ -922,7 +941,7 @@ __global__ __launch_bounds__(RIC_THREADS) void riccati_resident_kernel(RicGrid a
         if (in_regs) {
             __syncthreads();
         } else {
-            if (wave == 0) {                                     // LU with partial pivoting (mu <= 32) by ONE wavefront: LDS is in order per
+            if (wave == 0) {                                     // LU with partial pivoting (mu <= 64) by ONE wavefront: LDS is in order per
                 for (int c = 0; c < mu; c++) {                   // wavefront, so fences replace the workgroup barriers
                     int bi = c;
                     {
@@ -1186,16 +1205,17 @@ size_t ric_grid_work_doubles(int nprob, int mx, int mu, int ml, int N, int time_
     return (size_t)nprob * (nlin * mx * na + mx * na + 3 * (size_t)mx * mx + 2 * (size_t)mu * mx + 2 * tm * tm + tm * mu * na + nlin * sc + nlin * (ml + 2) + 8) + 64;
 }
 
-// P and W in one CU's LDS, and whole k-groups of four for the double-buffered tiles (mx = 12 nb always is a multiple of 4)
+// P and W in one CU's LDS, whole k-groups of four for the double-buffered tiles (mx = 12 nb always is a multiple of 4), and an S the
+// one-wavefront pivoted LU covers (its lanes are S's columns: mu <= 64)
 static bool ric_resident_fits(const RicArgs& a) {
-    return ric_resident_lds_bytes(a.mx, a.mu) <= 158 * 1024 && (a.mx & 3) == 0 && (a.mx + a.mu + 15) / 16 <= RIC_WAVES;
+    return ric_resident_lds_bytes(a.mx, a.mu) <= 158 * 1024 && (a.mx & 3) == 0 && (a.mx + a.mu + 15) / 16 <= RIC_WAVES && a.mu <= 64;
 }
 // resident (one workgroup per problem, P and W in LDS) whenever it fits; otherwise the tiled three-launch step
 // shapes for which the bf16 measured-error mode exists on the resident kernel (the register-fragment specialisations)
 static bool ric_resident_has_bf16(const RicArgs& a) { return (a.mu == 7 && a.mx == 84) || (a.mu == 1 && a.mx == 24); }
 static bool ric_use_tiled(const RicArgs& a) {
     if (!ric_resident_fits(a)) return true;
-    if (a.bf16_terms > 0 && !ric_resident_has_bf16(a)) return true;   // elsewhere the measured-error mode exists on the tiled path only
+    if (a.bf16_terms > 0 && (!ric_resident_has_bf16(a) || a.p_rows)) return true;   // elsewhere the measured-error mode exists on the tiled path only
     const int path = a.path;      // 0 auto, 1 LDS-resident workgroup per problem, 2 tiled
     if (path != 0) return path == 2;
     // measured crossover: a single 84..96-state problem is faster spread over the device (41 vs 59 us per step), small problems
@@ -1247,6 +1267,7 @@ hipError_t launch_riccati(const RicArgs& a, hipStream_t stream) {
     ric_pp_assign((a.mx + 15) / 16, (a.mx + a.mu + 15) / 16, g.pp_mask);
     g.nprob = a.nprob; g.mx = a.mx; g.mu = a.mu; g.ml = a.ml; g.N = a.N; g.nlin = a.time_varying ? (a.N > 1 ? a.N - 1 : 1) : 1;
     g.na = a.mx + a.mu; g.tm = (a.mx + 31) / 32; g.tn = (g.na + 31) / 32; g.tol = a.tol; g.bf16_terms = a.bf16_terms; g.keep_last = a.keep_last; g.kpad = a.kpad;
+    g.p_rows = a.p_rows;
     g.A = a.A; g.Bu = a.Bu; g.Bl = a.Bl; g.G = a.G; g.Q = a.Q; g.R = a.R; g.K = a.K; g.kbreak = a.kbreak; g.status = a.status; g.stop = a.stop;
     const size_t np = a.nprob, nlin = g.nlin, mx = a.mx, na = g.na, mu = a.mu, ml = a.ml;
     double* o = a.work;
@@ -1287,7 +1308,7 @@ hipError_t launch_riccati(const RicArgs& a, hipStream_t stream) {
         static const ResKernel by_mu[RIC_MU_REG + 1] = {riccati_resident_kernel<0, 0>, riccati_resident_kernel<1, 0>, riccati_resident_kernel<2, 0>, riccati_resident_kernel<3, 0>,
                                                         riccati_resident_kernel<4, 0>, riccati_resident_kernel<5, 0>, riccati_resident_kernel<6, 0>, riccati_resident_kernel<7, 0>};
         ResKernel kern = by_mu[(a.mu >= 1 && a.mu <= RIC_MU_REG) ? a.mu : 0];
-        const int ng4 = a.mx >> 2;
+        const int ng4 = a.p_rows ? -1 : a.mx >> 2;     // (the register-fragment forms compute half of a symmetric Pkp1 and mirror it)
         if (a.mu == 1 && ng4 == 3) kern = riccati_resident_kernel<1, 3>;          // pendulum (mx 12)
         else if (a.mu == 1 && ng4 == 6) kern = riccati_resident_kernel<1, 6>;     // cartpole, acrobot (mx 24)
         else if (a.mu == 1 && ng4 == 12) kern = riccati_resident_kernel<1, 12>;   // triple cartpole (mx 48)

@@ -155,7 +155,11 @@ int cclqr_linearize_projected(const cclqr_mech *m, int32_t nk, const double *zd,
 /* dlqr(A, Bu, Bλ, G, Q, R, N) -- lqr.jl:141-184, batched over nprob independent problems (nprob = 1 in the reference).
  * Q [mx][mx] and R [mu][mu] are the already Δt-scaled block-diagonal weights (lqr.jl:18-19).
  * K [nprob][N-1][mu][mx] ([nprob][mu][mx] with cclqr_riccati_opts.keep_last); kbreak [nprob] = value of the loop index k after the loop
- * (lqr.jl:172-181). Host pointers. */
+ * (lqr.jl:172-181). Host pointers.
+ * Q and R are used as written, symmetric or not (lqr.jl:152-170 never symmetrises them); the kernels that assume a symmetric Pk are used only
+ * when both are EXACTLY symmetric.  G*Bλ is factored for the backward steps that reach it, as in the reference: CCLQR_ESINGULAR (kbreak = the
+ * step that met it) only when a step that runs meets a singular G*Bλ or M; with N = 1 nothing is factored.  Any mu >= 0 is served (mu > 64
+ * on the tiled path). */
 int cclqr_riccati(int32_t nprob, int32_t mx, int32_t mu, int32_t ml, const double *A, const double *Bu, const double *Bl, const double *G,
                   const double *Q, const double *R, int32_t N, double tol, double *K, int32_t *kbreak);
 
@@ -192,7 +196,8 @@ int cclqr_release_workspaces(void);
 
 /* The recursion of lqr_tracking.jl:73-122 on per-knot linear models the caller brings: A [N-1][mx][mx], Bu [N-1][mx][mu], Bl [N-1][mx][ml],
  * G [N-1][ml][mx] (knot k = 1 .. N-1 at index k-1, as cclqr_riccati_tracking linearises them itself); ml = 0 with the projected pairs of
- * cclqr_linearize_projected gives the TrackingLQR of a closed-loop mechanism.  K [N-1][mu][mx], kbreak [1]. Host pointers. */
+ * cclqr_linearize_projected gives the TrackingLQR of a closed-loop mechanism.  K [N-1][mu][mx], kbreak [1]. Host pointers.
+ * A singular G*Bλ at a knot the sweep never reaches (below the break) is no error, as in lqr_tracking.jl:87-116. */
 int cclqr_riccati_tv(int32_t mx, int32_t mu, int32_t ml, const double *A, const double *Bu, const double *Bl, const double *G,
                      const double *Q, const double *R, int32_t N, double tol, double *K, int32_t *kbreak);
 
