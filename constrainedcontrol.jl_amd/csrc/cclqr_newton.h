@@ -32,6 +32,18 @@ struct Prof {
 #define NEWTON_MAXIT 100
 #define LINE_MAXIT 10
 
+// Status word of an instance after a launch (cclqr.h cclqr_rollout_opts.status), written by every rollout kernel: the largest Newton iteration
+// count of its steps, negated if a step did not converge ("bad").  An instance is "dead" once a step stopped early on a non-finite residual: it is
+// frozen at its last pose from then on.  With CCLQR_ROLLOUT_CARRY_STATUS the word comes back into the next launch, where a negative count above
+// -NEWTON_MAXIT means dead; so a dead instance that had also hit NEWTON_MAXIT in an earlier step reports NEWTON_MAXIT - 1 when carrying.
+struct NewtonStatus { int worst; bool bad, dead; };
+__device__ __forceinline__ NewtonStatus status_decode(int carried) {
+    return {carried < 0 ? -carried : carried, carried < 0, carried < 0 && carried > -NEWTON_MAXIT};
+}
+__device__ __forceinline__ int status_encode(int worst, bool bad, bool dead, int carry) {
+    return bad ? -((carry && dead && worst >= NEWTON_MAXIT) ? NEWTON_MAXIT - 1 : worst) : worst;
+}
+
 // 16-lane row rotation through the DPP crossbar (no LDS round trip)
 template <int N>
 __device__ __forceinline__ double dpp_row_ror(double v) {

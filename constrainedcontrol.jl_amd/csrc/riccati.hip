@@ -632,14 +632,10 @@ __device__ __forceinline__ bool gain_in_registers(int j, bool owner, int mx, int
 #pragma unroll
     for (int c = 0; c < MU; c++) {
         ok = ok && (Sr[c][c] > 0.0);
-#ifdef RIC_IEEE_DIV
-        const double pinv = 1.0 / Sr[c][c];
-#else
         // the pivot's reciprocal (v_rcp_f64 + two Newton steps, ~1 ulp: cclqr_dev.h fast_rcp) is kept in the pivot's place and MULTIPLIES in the back
         // substitution: 14 IEEE division sequences (~ 100 dependent cycles each) sat on the critical path of every backward step between two barriers
         const double pinv = fast_rcp(Sr[c][c]);
         Sr[c][c] = pinv;
-#endif
 #pragma unroll
         for (int r = c + 1; r < MU; r++) Sr[r][c] *= pinv;
 #pragma unroll
@@ -658,11 +654,7 @@ __device__ __forceinline__ bool gain_in_registers(int j, bool owner, int mx, int
     for (int i = MU - 1; i >= 0; i--) {
 #pragma unroll
         for (int r = i + 1; r < MU; r++) x[i] -= Sr[i][r] * x[r];
-#ifdef RIC_IEEE_DIV
-        x[i] = x[i] / Sr[i][i];
-#else
         x[i] = x[i] * Sr[i][i];
-#endif
     }
 #pragma unroll
     for (int q = 0; q < MU; q++) { Ku[q * mx + j] = x[q]; Kdst[(size_t)q * mx + j] = x[q]; }   // Ku[k][i] = Kk[i:i,:]  lqr.jl:162-164
@@ -910,9 +902,7 @@ __global__ __launch_bounds__(RIC_THREADS) void riccati_resident_kernel(RicGrid a
                         const int row = lk + 4 * r;
                         if (row < mu) {
                             TS[row * na + j] = acc[r];
-#ifndef RIC_S_SEPARATE
                             if (j >= mx) S[row * mu + (j - mx)] = Rl[row * mu + (j - mx)] + acc[r];      // S = R + D'PkD (lqr.jl:152-153) leaves with the tile that holds D'W_D: no pass, no barrier of its own
-#endif
                         }
                     }
                 }
@@ -926,10 +916,7 @@ __global__ __launch_bounds__(RIC_THREADS) void riccati_resident_kernel(RicGrid a
             }
         }
         __syncthreads();
-#ifndef RIC_S_SEPARATE
-        if (mu > 16)
-#endif
-        {
+        if (mu > 16) {
             for (int e = tid; e < mu * mu; e += RIC_THREADS) S[e] = Rl[e] + TS[(e / mu) * na + mx + e % mu];       // S = R + D'PkD   lqr.jl:152-153
             __syncthreads();
         }

@@ -9,6 +9,7 @@
 #include "cclqr_chain.h"
 #include "cclqr_internal.h"
 #include "cclqr_newton.h"
+#include "cclqr_rollout_step.h"
 
 namespace cclqr {
 
@@ -35,13 +36,6 @@ __device__ __forceinline__ void from_next(const double* in, double* out) {
 #pragma unroll
     for (int i = 0; i < N; i++) out[i] = wave_from_next(in[i]);
 }
-
-// dynamic per-lane data of the owned link.  The velocity part of the state is s itself: the solution (v+, w+) of one step is
-// the state's (v, w) at the next knot and the Newton start of the next step.
-struct LinkS {
-    double z[7], s[6];
-    double ds[6], cd[6], d[6];
-};
 
 // residual (+ Jacobians when JAC) at the point s - alpha ds with constraint forces C - alpha cd; returns the group's ||f||_2.
 // With JAC the Schur complement rows of the point go straight to LDS: W = G_v D^-1 only lives inside this function.
@@ -120,13 +114,7 @@ __device__ __forceinline__ double chain_eval(LinkC& c, LinkS& S, int t, const La
     return nrm;
 }
 
-// ---- line search of the 32-lane instantiations (two instances per wavefront): TWO step lengths per pass in a group's own lanes, and when
-// only ONE of the wavefront's two instances is still searching the other group's idle lanes evaluate two more for it.  The noise-floor
-// searches of the exact stopping rule are heavy-tailed (9 % of them run to the 10th halving), and a wavefront pays the longer of its two:
-// the accept sequence -- first level that does not grow, level LINE_MAXIT at the latest -- and every bit of the result are unchanged.
-struct TrialIn { double z[7], s[6], ds[6], cd[6]; };
-__device__ __forceinline__ double other_half(double v) { return __shfl_xor(v, 32, 64); }
-// ||f|| of the owning group at the trial points s - a ds (constraint forces C - a cd) for a = a1 and a = a2; Lc = LDS image of the instance
+// line search of the 32-lane instantiations (cclqr_rollout_step.h TrialIn): ||f|| of the owning group at the trial points s - a ds (constraint forces C - a cd) for a = a1 and a = a2; Lc = LDS image of the instance
 template <int G, int KL = 1>
 __device__ __forceinline__ void chain_eval2(LinkC& c, const TrialIn& T, const double* Lc, int t, const Lay& Y, double a1, double a2, bool active, double dt,
                                             double& n1, double& n2) {
@@ -241,9 +229,6 @@ template <int G, int NBP, int EXTRA, bool RELAX = false, int KL = 1, int NL = G>
 __global__ __launch_bounds__(64) void rollout_chain_kernel(RolloutArgs a) {
     extern __shared__ double lds[];
     static_assert(KL >= 1 && KL <= 3 && KL * NL <= G && (KL > 1 || NL == G) && (KL == 1 || NL <= NBP), "lane group too small for KL lanes per link");
-#if defined(CHAIN_DIAG_EXIT) && CHAIN_DIAG_EXIT == 1
-    if (a.steps == 0) return;                                // (diagnostic build, tools/gpu_launch_overhead.py: what a launch costs with NO kernel body)
-#endif
     const int lane = threadIdx.x, t = lane % G, grp = lane / G;
     const int w = KL > 1 ? t / NL : 0;                      // sub-lane of the lane's link
     const int tl = KL > 1 ? t - NL * w : t;                 // the link the lane works for (LDS slots, tables)
@@ -264,9 +249,6 @@ __global__ __launch_bounds__(64) void rollout_chain_kernel(RolloutArgs a) {
     if (KL > 1) sub_setup<KL>(c, w < KL ? w : 0, Q);
     if (EXTRA && C->has_fric && c.on()) { c.fric = C->fric[tl]; if (c.fric != 0.0) c.flags |= LinkC::FRIC; }
     c.set_valid(grp < a.ipw && inst < a.n_inst);
-#if defined(CHAIN_DIAG_EXIT) && CHAIN_DIAG_EXIT == 3
-    if (a.steps == 0) { if (t == 0 && c.valid()) a.status[inst] = (int)(c.m + c.J[8] + c.sxa + c.qoc[3] + c.V12[5] + c.p1[2] + c.p2[2] + c.axis[2]); return; }      // (diagnostic: link constants only)
-#endif
     const long long ginst = a.inst0 + inst;     // global instance index: selects the controller table when there is one per instance
     const int ut = c.on() ? M->perm[tl] : 0;      // user body index of the owned link
 
@@ -279,13 +261,6 @@ __global__ __launch_bounds__(64) void rollout_chain_kernel(RolloutArgs a) {
     if (EXTRA == 2 && a.pid_state && a.k0 > 1 && c.live()) { pid_int = a.pid_state[(inst * nb + tl) * 2]; pid_last = a.pid_state[(inst * nb + tl) * 2 + 1]; }
 #pragma unroll
     for (int i = 0; i < 6; i++) { S.cd[i] = 0.0; S.d[i] = 0.0; S.ds[i] = 0.0; }
-#if defined(CHAIN_DIAG_EXIT) && CHAIN_DIAG_EXIT == 4
-    if (a.steps == 0) { if (t == 0 && c.valid()) a.status[inst] = (int)(S.z[0] + S.s[5] + c.m); return; }      // (diagnostic: constants + state)
-#endif
-#ifdef CHAIN_LDS_ZERO_FILL
-    for (int e = t; e < Y.total; e += G) L[e] = 0.0;
-    __syncthreads();
-#endif
     // What the Newton phases read before they have written it is the multiplier block only (tests/emu/emu_chain.cpp runs every phase function on an
     // LDS image poisoned with signalling NaNs but for LAM): zero, or the caller's warm start.  Everything else in the image is discarded by a
     // select wherever a phase reads past what was produced (ck_tri_back / cr_back), so it is not cleared: at one step per launch (configs[4]'s
@@ -297,9 +272,6 @@ __global__ __launch_bounds__(64) void rollout_chain_kernel(RolloutArgs a) {
     }
     __syncthreads();
 
-#if defined(CHAIN_DIAG_EXIT) && CHAIN_DIAG_EXIT == 2
-    if (a.steps == 0) { if (t == 0 && c.valid()) a.status[inst] = (int)(S.z[0] + L[Y.LAM + 5 * tl]); return; }      // (diagnostic: prologue only)
-#endif
 #ifdef CCLQR_PROFILE
     Prof prof;
     prof.start();
@@ -308,10 +280,10 @@ __global__ __launch_bounds__(64) void rollout_chain_kernel(RolloutArgs a) {
     // "bad" (a step did not converge) and "dead" (a step produced a non-finite residual; the instance is frozen from then on) are
     // bits of the lane flags, not 64-bit lane masks held in scalar registers through the launch
     if (a.carry && a.status && c.valid()) {      // CCLQR_ROLLOUT_CARRY_STATUS: the launches before this one count (step-per-launch chains)
-        const int carried = a.status[inst];
-        worst = carried < 0 ? -carried : carried;
-        if (carried < 0) c.flags |= LinkC::BAD;
-        if (carried < 0 && carried > -NEWTON_MAXIT) c.flags |= LinkC::DEAD;      // lost in an earlier launch (stopped before NEWTON_MAXIT): it stays frozen
+        const NewtonStatus st = status_decode(a.status[inst]);
+        worst = st.worst;
+        if (st.bad) c.flags |= LinkC::BAD;
+        if (st.dead) c.flags |= LinkC::DEAD;      // lost in an earlier launch: it stays frozen
     }
     // Launch arguments that are only needed once per step or at the end are read from the kernel-argument segment where they are
     // used, through a pointer the optimiser cannot see through, instead of sitting in scalar registers for the whole launch.
@@ -530,14 +502,6 @@ __global__ __launch_bounds__(64) void rollout_chain_kernel(RolloutArgs a) {
             }
             double nd;
             LINK_FLAGS_FRESH(c);
-#ifdef CHAIN_RELOAD_CONSTS
-            {   // experiment: the link constants (33 doubles per lane) re-read behind the linear solve through a pointer the optimiser cannot see
-                // through, so that they are dead -- 66 registers free -- while the solve runs
-                const MechDev* Mq = ap->M;
-                asm volatile("" : "+s"(Mq));
-                link_reload_consts(c, Mq, tl, nb, dt);
-            }
-#endif
             {   // multiplier step from LDS, body solve
                 double own[6], par[6], cpar[6], dl[5], pdn = 0.0;
 #pragma unroll
@@ -716,22 +680,6 @@ __global__ __launch_bounds__(64) void rollout_chain_kernel(RolloutArgs a) {
     prof.flush();
 #endif
     // ---------------- final state, multipliers, status
-#ifdef CHAIN_DIRECT_FINAL_STORE      // (rejected variant, kept buildable for A/B: 13 one-double stores per lane straight from registers; 0-step launch 4.75 -> 5.23 us)
-    asm volatile("" : "+s"(ap));
-    LINK_FLAGS_FRESH(c);
-    if (c.live() && (KL == 1 || c.prim())) {
-        double* zT = ap->zT;
-#pragma unroll
-        for (int i = 0; i < 7; i++) zT[inst * nz + 13 * ut + i] = S.z[i];
-#pragma unroll
-        for (int i = 0; i < 6; i++) zT[inst * nz + 13 * ut + 7 + i] = S.s[i];
-    }
-    if (c.valid()) {
-        int* status = ap->status;
-        // (carried statuses mark a lost instance by a count below NEWTON_MAXIT: one that had also failed to converge earlier reports NEWTON_MAXIT - 1)
-        if (status && t == 0) status[inst] = c.bad() ? -((ap->carry && c.dead() && worst >= NEWTON_MAXIT) ? NEWTON_MAXIT - 1 : worst) : worst;
-    }
-#else
     __syncthreads();
     if (c.live() && (KL == 1 || c.prim())) {
 #pragma unroll
@@ -746,10 +694,8 @@ __global__ __launch_bounds__(64) void rollout_chain_kernel(RolloutArgs a) {
         double* zT = ap->zT;
         int* status = ap->status;
         for (int e = t; e < nz; e += G) zT[inst * nz + e] = L[Y.Z + e];
-        // (carried statuses mark a lost instance by a count below NEWTON_MAXIT: one that had also failed to converge earlier reports NEWTON_MAXIT - 1)
-        if (status && t == 0) status[inst] = c.bad() ? -((ap->carry && c.dead() && worst >= NEWTON_MAXIT) ? NEWTON_MAXIT - 1 : worst) : worst;
+        if (status && t == 0) status[inst] = status_encode(worst, c.bad(), c.dead(), ap->carry);
     }
-#endif
     if (c.live() && (KL == 1 || c.prim())) {
         const int nbT = ap->M->nb;      // read again here rather than kept in a scalar register through the launch
         double* lam = ap->lam;
@@ -828,17 +774,7 @@ static hipError_t launch_chain_one(const RolloutArgs& a, int extra, int newton_m
 // shipped: the joint rows get cheaper (11.0 k -> 9.6 k cycles per step on the tracking triple cartpole) but the Schur rows do not (25.7 k -> 25.5 k) -- that phase is
 // bound by its ~180 LDS instructions per evaluation, which every lane issues whatever rows it keeps, not by its multiply-adds -- and the whole step moves by
 // < 0.5 % while the order of summation (hence noise-floor decisions of the stopping rule) changes (profiles/r05/lanes_per_link_*).
-// -DCHAIN_ONE_LANE_PER_LINK: one lane per link everywhere, -DCHAIN_TWO_LANES_PER_LINK: the measured-and-rejected shapes, both for A/B timing
-int chain_lanes_per_link(int nb) {
-#if defined(CHAIN_ONE_LANE_PER_LINK)
-    (void)nb;
-    return 1;
-#elif defined(CHAIN_TWO_LANES_PER_LINK)
-    return nb <= 2 ? 3 : (nb <= 16 ? 2 : 1);
-#else
-    return nb <= 2 ? 3 : 1;
-#endif
-}
+int chain_lanes_per_link(int nb) { return nb <= 2 ? 3 : 1; }
 
 hipError_t launch_rollout_chain(const RolloutArgs& a_in, int nb, int extra, int newton_mode, hipStream_t stream) {
     const int per_wg = chain_instances_per_wavefront(nb, a_in.n_inst, a_in.steps, a_in.ipw != 0);
@@ -855,22 +791,12 @@ hipError_t launch_rollout_chain(const RolloutArgs& a_in, int nb, int extra, int 
     }
     const int kl = chain_lanes_per_link(nb);
     switch (chain_layout_links(nb)) {
-#if defined(CHAIN_TWO_LANES_PER_LINK)
-        case 4: return nb <= 2 ? launch_chain_one<8, 4, 3, 2>(a, extra, newton_mode, grid, lds, stream) : launch_chain_one<8, 4, 2, 4>(a, extra, newton_mode, grid, lds, stream);
-        case 8: return launch_chain_one<16, 8, 2, 8>(a, extra, newton_mode, grid, lds, stream);
-        case 16: return launch_chain_one<32, 16, 2, 16>(a, extra, newton_mode, grid, lds, stream);
-#elif defined(CHAIN_ONE_LANE_PER_LINK)
-        case 4: return launch_chain_one<8, 4>(a, extra, newton_mode, grid, lds, stream);
+        case 4: return kl == 3 ? launch_chain_one<8, 4, 3, 2>(a, extra, newton_mode, grid, lds, stream) : launch_chain_one<8, 4>(a, extra, newton_mode, grid, lds, stream);
         case 8: return launch_chain_one<16, 8>(a, extra, newton_mode, grid, lds, stream);
         case 16: return launch_chain_one<32, 16>(a, extra, newton_mode, grid, lds, stream);
-#else
-        case 4: return nb <= 2 ? launch_chain_one<8, 4, 3, 2>(a, extra, newton_mode, grid, lds, stream) : launch_chain_one<8, 4>(a, extra, newton_mode, grid, lds, stream);
-        case 8: return launch_chain_one<16, 8>(a, extra, newton_mode, grid, lds, stream);
-        case 16: return launch_chain_one<32, 16>(a, extra, newton_mode, grid, lds, stream);
-#endif
         case 17: return launch_chain_one<32, 17>(a, extra, newton_mode, grid, lds, stream);
         case 32: return launch_chain_one<32, 32>(a, extra, newton_mode, grid, lds, stream);
-        default: (void)kl; return launch_chain_one<64, 64>(a, extra, newton_mode, grid, lds, stream);
+        default: return launch_chain_one<64, 64>(a, extra, newton_mode, grid, lds, stream);
     }
 }
 

@@ -10,6 +10,7 @@
 #include "cclqr_treereg.h"
 #include "cclqr_internal.h"
 #include "cclqr_newton.h"
+#include "cclqr_rollout_step.h"
 
 namespace cclqr {
 
@@ -41,11 +42,6 @@ __device__ __forceinline__ void child_sum(const TreeL& T, int gb4, int maxchild,
     }
 }
 
-struct TLinkS {
-    double z[7], s[6];
-    double ds[6], cd[6], d[6];
-};
-
 __device__ __forceinline__ void load_rec(TrRec& K, const TrRec* p) {
     const int4* q = (const int4*)p;
     const int4 a = q[0], b = q[1], c = q[2];
@@ -57,7 +53,7 @@ __device__ __forceinline__ void load_rec(TrRec& K, const TrRec* p) {
 // residual (+ Jacobians when JAC) at the point s - alpha ds with constraint forces C - alpha cd; returns the group's ||f||_2.
 // With JAC the Schur complement rows of the point go straight to LDS (tr_schur_rows).
 template <int G, bool JAC>
-__device__ __forceinline__ double tree_eval(LinkC& c, const TreeL& T, TLinkS& S, int t, int pa4, int maxchild, int maxsib, const Lay& Y, double* L, double alpha,
+__device__ __forceinline__ double tree_eval(LinkC& c, const TreeL& T, LinkS& S, int t, int pa4, int maxchild, int maxsib, const Lay& Y, double* L, double alpha,
                                             bool active, double dt PROF_ARG) {
     double part = 0.0;
     double NB[9], g[5], xq[7];
@@ -104,12 +100,9 @@ __device__ __forceinline__ double tree_eval(LinkC& c, const TreeL& T, TLinkS& S,
     return nrm;
 }
 
-// line search of the 32-lane instantiations: two step lengths per pass in a group's own lanes, and the wavefront's other group helps when
-// it has nothing to search itself (rollout_chain.hip chain_eval2 / the accept sequence there: unchanged)
-struct TTrialIn { double z[7], s[6], ds[6], cd[6]; };
-__device__ __forceinline__ double tr_other_half(double v) { return __shfl_xor(v, 32, 64); }
+// line search of the 32-lane instantiations (cclqr_rollout_step.h TrialIn; rollout_chain.hip chain_eval2 / the accept sequence there: unchanged)
 template <int G>
-__device__ __forceinline__ void tree_eval2(LinkC& c, const TTrialIn& T, const double* Lc, int t, int pa4, const Lay& Y, double a1, double a2, bool active, double dt,
+__device__ __forceinline__ void tree_eval2(LinkC& c, const TrialIn& T, const double* Lc, int t, int pa4, const Lay& Y, double a1, double a2, bool active, double dt,
                                            double& n1, double& n2) {
     double part1 = 0.0, part2 = 0.0, xq1[7], xq2[7];
     LINK_FLAGS_FRESH(c);
@@ -176,7 +169,7 @@ __global__ __launch_bounds__(64) void rollout_treereg_kernel(RolloutArgs a) {
     const long long ginst = a.inst0 + inst;
     const int ut = c.on() ? M->perm[t] : 0;
 
-    TLinkS S;
+    LinkS S;
     double pid_int = 0.0, pid_last = 0.0;
 #pragma unroll
     for (int i = 0; i < 7; i++) S.z[i] = c.live() ? a.z0[inst * nz + ut * 13 + i] : ((i == 3) ? 1.0 : 0.0);
@@ -199,10 +192,10 @@ __global__ __launch_bounds__(64) void rollout_treereg_kernel(RolloutArgs a) {
 #endif
     int worst = 0;
     if (a.carry && a.status && c.valid()) {      // CCLQR_ROLLOUT_CARRY_STATUS (rollout_chain.hip)
-        const int carried = a.status[inst];
-        worst = carried < 0 ? -carried : carried;
-        if (carried < 0) c.flags |= LinkC::BAD;
-        if (carried < 0 && carried > -NEWTON_MAXIT) c.flags |= LinkC::DEAD;
+        const NewtonStatus st = status_decode(a.status[inst]);
+        worst = st.worst;
+        if (st.bad) c.flags |= LinkC::BAD;
+        if (st.dead) c.flags |= LinkC::DEAD;
     }
     typedef const __attribute__((address_space(4))) RolloutArgs* KernArgs;
     KernArgs ap = (KernArgs)__builtin_amdgcn_kernarg_segment_ptr();
@@ -423,17 +416,17 @@ __global__ __launch_bounds__(64) void rollout_treereg_kernel(RolloutArgs a) {
                     const bool mine = !ls_done;
                     const bool other = __shfl_xor(mine ? 1 : 0, 32, 64) != 0;
                     const bool helping = !mine && other;
-                    TTrialIn Tr;
+                    TrialIn Tr;
 #pragma unroll
                     for (int i = 0; i < 7; i++) Tr.z[i] = S.z[i];
 #pragma unroll
                     for (int i = 0; i < 6; i++) { Tr.s[i] = S.s[i]; Tr.ds[i] = S.ds[i]; Tr.cd[i] = S.cd[i]; }
                     if (mine != other) {
 #pragma unroll
-                        for (int i = 0; i < 7; i++) { const double o = tr_other_half(S.z[i]); Tr.z[i] = helping ? o : Tr.z[i]; }
+                        for (int i = 0; i < 7; i++) { const double o = other_half(S.z[i]); Tr.z[i] = helping ? o : Tr.z[i]; }
 #pragma unroll
                         for (int i = 0; i < 6; i++) {
-                            const double o1 = tr_other_half(S.s[i]), o2 = tr_other_half(S.ds[i]), o3 = tr_other_half(S.cd[i]);
+                            const double o1 = other_half(S.s[i]), o2 = other_half(S.ds[i]), o3 = other_half(S.cd[i]);
                             Tr.s[i] = helping ? o1 : Tr.s[i]; Tr.ds[i] = helping ? o2 : Tr.ds[i]; Tr.cd[i] = helping ? o3 : Tr.cd[i];
                         }
                     }
@@ -442,7 +435,7 @@ __global__ __launch_bounds__(64) void rollout_treereg_kernel(RolloutArgs a) {
                     double n1, n2;
                     tree_eval2<G>(c, Tr, Lc, t, pa4, Y, ldexp(1.0, -l0), ldexp(1.0, -(l0 + 1)), c.on() && (mine || helping) && l0 <= LINE_MAXIT, dt, n1, n2);
                     PCOUNT(PF_EVALS);
-                    const double h1 = tr_other_half(n1), h2 = tr_other_half(n2);
+                    const double h1 = other_half(n1), h2 = other_half(n2);
                     if (mine) {
                         const double cand[4] = {n1, n2, h1, h2};
 #pragma unroll
@@ -523,7 +516,7 @@ __global__ __launch_bounds__(64) void rollout_treereg_kernel(RolloutArgs a) {
         double* zT = ap->zT;
         int* status = ap->status;
         for (int e = t; e < nz; e += G) zT[inst * nz + e] = L[Y.Z + e];
-        if (status && t == 0) status[inst] = c.bad() ? -((ap->carry && c.dead() && worst >= NEWTON_MAXIT) ? NEWTON_MAXIT - 1 : worst) : worst;
+        if (status && t == 0) status[inst] = status_encode(worst, c.bad(), c.dead(), ap->carry);
     }
     if (c.live()) {
         const int nbT = ap->M->nb;
