@@ -127,7 +127,12 @@ extern "C" int cclqr_mech_create(const cclqr_mech_desc* d, cclqr_mech** out) {
     if (e == hipSuccess) e = hipMalloc((void**)&m->dev, image.size());
     if (e == hipSuccess) e = hipMemcpy(m->dev, image.data(), image.size(), hipMemcpyHostToDevice);
     if (e != hipSuccess) { delete m; return fail(CCLQR_EHIP, std::string("mechanism upload: ") + hipGetErrorString(e)); }
-    (void)spread_instances_per_wavefront(2, 1, 8, false);      // (reads the device's compute-unit count once, here: never inside a caller's hipGraph capture)
+    // the kernels this mechanism runs on, and the SIMDs of ITS device that a small batch is spread over (spread_instances_per_wavefront): both
+    // fixed here, so that no launch queries the runtime (never inside a caller's hipGraph capture)
+    m->shape = rollout_shape_of(m->host, m->nb, m->nj);
+    int cus = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, m->device) != hipSuccess || cus <= 0) cus = 256;
+    m->simds = 4 * cus;
     *out = m;
     return CCLQR_OK;
 }
@@ -141,11 +146,13 @@ extern "C" int cclqr_mech_destroy(cclqr_mech* m) {
 
 // doubles the rollout kernels' control phase fetches past the end of a gain row: they read ceil(12 NBP / G) G entries of a row (G lanes per instance,
 // the LDS image laid out for NBP >= nb links) and let the surplus meet a zero factor.  Closed-loop kernel: exact row length.
+// one knot of the mechanism's linearisation kernel (launch_linearize) within a CU's 160 KB of LDS
+static bool linearize_fits_lds(const cclqr_mech* m) { return m->shape.lin_lds <= 160 * 1024; }
+
 static size_t gain_row_overrun(const cclqr_mech* m) {
-    if (m->host.loop) return 0;
-    const int G = m->host.tree ? treereg_lanes(m->nb, m->host.tree) : chain_lanes_per_instance(m->nb);
-    const int nbp = m->host.tree ? treereg_layout_links(m->nb, m->host.tree) : chain_layout_links(m->nb);
-    const long long over = (long long)((12 * nbp + G - 1) / G) * G - 12LL * m->nb;
+    const RolloutShape& s = m->shape;
+    if (s.family == RolloutFamily::Loop) return 0;
+    const long long over = (long long)((12 * s.NBP + s.G - 1) / s.G) * s.G - 12LL * m->nb;
     return over > 0 ? (size_t)((over + 1) & ~1LL) : 0;
 }
 
@@ -225,7 +232,7 @@ extern "C" int cclqr_ctrl_create_lqr_batch(const cclqr_mech* m, int32_t n_ctrl, 
     if (n_ctrl < 1 || N < 2 || mu < 1 || mu > m->nb) return fail(CCLQR_EINVAL, "bad sizes");
     const int nb = m->nb;
     const size_t nz = 13 * (size_t)nb, mx = 12 * (size_t)nb, ml = 5 * (size_t)nb, np = (size_t)n_ctrl;
-    if (linearize_lds_bytes(nb, m->host.tree, m->host.npairs) > 160 * 1024) return fail(CCLQR_EUNSUPPORTED, "instance does not fit LDS");
+    if (!linearize_fits_lds(m)) return fail(CCLQR_EUNSUPPORTED, "instance does not fit LDS");
     LinArgs la;
     memset(&la, 0, sizeof(la));
     la.M = m->dev; la.nk = n_ctrl; la.mu = mu;
@@ -273,7 +280,7 @@ extern "C" int cclqr_ctrl_create_lqr_batch(const cclqr_mech* m, int32_t n_ctrl, 
     if (e == hipSuccess) e = hipMemcpy(dzd, zd, np * nz * sizeof(double), hipMemcpyHostToDevice);
     // linearsystem at every setpoint (lqr.jl:63), one launch; the matrices stay on the device
     la.zd = dzd; la.Fd = c->Fd_dev; la.A = dA; la.Bu = dBu; la.Bl = dBl; la.G = dG; la.status = dlst;
-    if (e == hipSuccess) e = launch_linearize(la, nb, m->host.tree, m->host.npairs, nullptr);
+    if (e == hipSuccess) e = launch_linearize(la, m->shape, nullptr);
     // dlqr for every setpoint (lqr.jl:141-184), gains written straight into the controller's table
     RicArgs ra;
     ra.nprob = n_ctrl; ra.mx = (int)mx; ra.mu = mu; ra.ml = (int)ml; ra.N = N; ra.time_varying = 0; ra.tol = tol; ra.path = 0; ra.bf16_terms = 0; ra.keep_last = inf ? 1 : 0; ra.kpad = (long long)padi;
@@ -292,8 +299,7 @@ extern "C" int cclqr_ctrl_create_lqr_batch(const cclqr_mech* m, int32_t n_ctrl, 
     if (e == hipSuccess) e = launch_riccati(ra, nullptr);
     if (e == hipSuccess) {
         const long long nrows = (long long)np * (long long)nKtab * mu;
-        hipLaunchKernelGGL(k_rows_to_link_order_kernel, dim3((unsigned)nrows), dim3(128), mx * sizeof(double), nullptr, c->K_dev, nrows, (long long)nKtab * mu, tab_stride, nb, m->dev);
-        e = hipGetLastError();
+        e = launch_lds<false>(k_rows_to_link_order_kernel, dim3((unsigned)nrows), dim3(128), mx * sizeof(double), nullptr, c->K_dev, nrows, (long long)nKtab * mu, tab_stride, nb, m->dev);
     }
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e == hipSuccess) e = hipMemcpy(lst.data(), dlst, np * sizeof(int), hipMemcpyDeviceToHost);
@@ -323,46 +329,96 @@ extern "C" int cclqr_ctrl_destroy(cclqr_ctrl* c) {
     return CCLQR_OK;
 }
 
+// the four geometry queries read the mechanism's RolloutShape: what they report is what the launchers launch
 extern "C" int cclqr_rollout_layout_links(const cclqr_mech* m, int32_t* links) {
     if (!m || !links) return fail(CCLQR_EINVAL, "null argument");
     // links the rollout kernel's LDS image is laid out for (it names the instantiation): chains rollout_chain_kernel, branching trees
     // rollout_treereg_kernel; 0 for closed-loop mechanisms (one kernel, runtime layout)
-    *links = m->host.loop ? 0 : (m->host.tree ? treereg_layout_links(m->nb, m->host.tree) : chain_layout_links(m->nb));
+    *links = m->shape.NBP;
     return CCLQR_OK;
 }
 
 extern "C" int cclqr_rollout_lanes_per_link(const cclqr_mech* m, int32_t* lanes_per_link, int32_t* links_per_group) {
     if (!m) return fail(CCLQR_EINVAL, "null argument");
-    int kl = 1, nl = 64;
-    if (m->host.loop) nl = 64;
-    else if (m->host.tree) nl = treereg_lanes(m->nb, m->host.tree);
-    else {
-        kl = chain_lanes_per_link(m->nb);
-        nl = kl == 1 ? chain_lanes_per_instance(m->nb) : (m->nb <= 2 ? 2 : chain_layout_links(m->nb));
-    }
-    if (lanes_per_link) *lanes_per_link = kl;
-    if (links_per_group) *links_per_group = nl;
+    if (lanes_per_link) *lanes_per_link = m->shape.KL;
+    if (links_per_group) *links_per_group = m->shape.NL;
     return CCLQR_OK;
 }
 
 extern "C" int cclqr_rollout_instances_per_wavefront(const cclqr_mech* m, int64_t n_inst, int32_t steps, int32_t flags, int32_t* instances) {
     if (!m || !instances) return fail(CCLQR_EINVAL, "null argument");
-    if (m->host.loop) *instances = 1;
-    else if (m->host.tree) *instances = spread_instances_per_wavefront(64 / treereg_lanes(m->nb, m->host.tree), n_inst, steps, (flags & CCLQR_ROLLOUT_PACK_WAVEFRONTS) != 0);
-    else *instances = chain_instances_per_wavefront(m->nb, n_inst, steps, (flags & CCLQR_ROLLOUT_PACK_WAVEFRONTS) != 0);
+    *instances = spread_instances_per_wavefront(m->shape.full, n_inst, steps, (flags & CCLQR_ROLLOUT_PACK_WAVEFRONTS) != 0, m->simds);
     return CCLQR_OK;
 }
 
 extern "C" int cclqr_rollout_geometry(const cclqr_mech* m, int32_t* lanes, int32_t* lds_bytes) {
     if (!m) return fail(CCLQR_EINVAL, "null argument");
-    if (m->host.loop) { if (lanes) *lanes = 64; if (lds_bytes) *lds_bytes = (int32_t)loop_lds_bytes(m->nb, m->nj); return CCLQR_OK; }
-    if (m->host.tree) {       // branching trees: rollout_treereg.hip
-        if (lanes) *lanes = treereg_lanes(m->nb, m->host.tree);
-        if (lds_bytes) *lds_bytes = (int32_t)treereg_lds_bytes(m->nb, m->host.tree, m->host.npairs);
-        return CCLQR_OK;
+    if (lanes) *lanes = m->shape.G;
+    if (lds_bytes) *lds_bytes = (int32_t)m->shape.lds;
+    return CCLQR_OK;
+}
+
+// cclqr_rollout_ex, first part: the arguments as the caller gave them
+static int rollout_check_args(const cclqr_mech* m, const cclqr_ctrl* c, int64_t n_inst, int32_t steps, int32_t k0, const double* z0, const double* zT,
+                              const int32_t* status, const cclqr_rollout_opts* opts) {
+    if (!m || !c || !z0 || !zT) return fail(CCLQR_EINVAL, "null argument");
+    if (n_inst < 0 || steps < 0 || k0 < 1) return fail(CCLQR_EINVAL, "bad sizes");
+    if (c->nb != m->nb) return fail(CCLQR_EINVAL, "controller was built for another mechanism");
+    { int rc = check_device(m); if (rc != CCLQR_OK) return rc; }
+    if (m->shape.lds > 160 * 1024) return fail(CCLQR_EUNSUPPORTED, "instance does not fit LDS");
+    const int64_t first = opts ? opts->first_instance : 0;
+    if (first < 0) return fail(CCLQR_EINVAL, "negative first_instance");
+    if (c->host.n_ctrl > 1 && first + n_inst > c->host.n_ctrl) return fail(CCLQR_EINVAL, "more instances than per-instance controller tables");
+    // one (integrated, last) pair per joint; never looked at for a controller without a PID law
+    if (opts && c->host.has_pid && opts->pid_state_dev && opts->pid_state_len != n_inst * (int64_t)m->shape.pid_slots * 2)
+        return fail(CCLQR_EINVAL, "pid_state_len must be n_inst * nb * 2 (closed loops: n_inst * joints * 2)");
+    if (opts && (opts->flags & ~(CCLQR_ROLLOUT_NO_ALLOC | CCLQR_ROLLOUT_PACK_WAVEFRONTS | CCLQR_ROLLOUT_CARRY_STATUS))) return fail(CCLQR_EINVAL, "unknown bit in cclqr_rollout_opts.flags");
+    if (opts && (opts->flags & CCLQR_ROLLOUT_CARRY_STATUS) && !status) return fail(CCLQR_EINVAL, "CCLQR_ROLLOUT_CARRY_STATUS needs the status array (it is read and written)");
+    return CCLQR_OK;
+}
+
+// cclqr_rollout_ex, second part: where the noise of this launch comes from.  On return *noise is the array the kernel reads (the caller's, or a
+// workspace filled here on `stream`; null: none) or *in_kernel says that the kernel draws the samples itself.
+// Counter-based noise is generated for this launch into a workspace, read by the rollout like an injected array.  The workspace is the
+// caller's (opts->noise_ws_dev: required for launches that share one controller on different streams or threads) or the handle's,
+// which only ever grows OUTSIDE stream capture: hipMalloc / hipFree are illegal while a stream is being captured, so a captured
+// launch needs the workspace sized beforehand (cclqr_ctrl_reserve_noise) or passed in.
+static int rollout_resolve_noise(const cclqr_mech* m, const cclqr_ctrl* c, int64_t n_inst, int32_t steps, int32_t k0, const cclqr_rollout_opts* opts, void* stream,
+                                 const double** noise, int64_t* noise_stride, bool* in_kernel) {
+    const CtrlDev& H = c->host;
+    *in_kernel = false;
+    if (!(H.noise_scale != 0.0 && H.mu > 0)) { *noise = nullptr; return CCLQR_OK; }
+    if (*noise || !H.noise_philox || steps <= 0) return CCLQR_OK;
+    // launches of a few steps on forests of chains (the step-per-launch form a hipGraph replays, BASELINE configs[4]) generate their samples inside the
+    // rollout kernel (rollout_chain_kernel<.., 3>): one kernel per step instead of two, and no workspace that could have to grow
+    if (m->shape.family == RolloutFamily::Chain && !H.has_pid && steps <= CCLQR_PHILOX_INKERNEL_STEPS && !(opts && opts->noise_ws_dev)) { *in_kernel = true; return CCLQR_OK; }
+    const size_t need = (size_t)n_inst * steps;
+    const int64_t first = opts ? opts->first_instance : 0;
+    double* ws = nullptr;
+    if (opts && opts->noise_ws_dev) {
+        if (opts->noise_ws_len < (int64_t)need) return fail(CCLQR_EINVAL, "noise_ws_len must be at least n_inst * steps");
+        ws = opts->noise_ws_dev;
+    } else {
+        cclqr_ctrl* cm = const_cast<cclqr_ctrl*>(c);
+        if (cm->noise_ws_cap < need) {
+            // growing = a device synchronisation + an allocation.  A caller who has said CCLQR_ROLLOUT_NO_ALLOC (anybody with a capture open on
+            // this device, on whichever stream) is refused outright; without the flag the library can only see a capture of `stream` itself
+            if (opts && (opts->flags & CCLQR_ROLLOUT_NO_ALLOC))
+                return fail(CCLQR_EINVAL, "CCLQR_ROLLOUT_NO_ALLOC: the Philox noise workspace of this controller holds " + std::to_string(cm->noise_ws_cap) + " samples, the launch needs " +
+                                          std::to_string(need) + ": call cclqr_ctrl_reserve_noise(ctrl, n_inst, steps) beforehand or pass cclqr_rollout_opts.noise_ws_dev");
+            hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+            if (stream) HIPCHK(hipStreamIsCapturing((hipStream_t)stream, &cap));
+            if (cap != hipStreamCaptureStatusNone)
+                return fail(CCLQR_EINVAL, "the Philox noise workspace cannot grow during stream capture: call cclqr_ctrl_reserve_noise(ctrl, n_inst, steps) "
+                                          "before the capture or pass cclqr_rollout_opts.noise_ws_dev");
+            int rc = cclqr_ctrl_reserve_noise(cm, n_inst, steps);
+            if (rc != CCLQR_OK) return rc;
+        }
+        ws = cm->noise_ws;
     }
-    if (lanes) *lanes = chain_lanes_per_instance(m->nb);
-    if (lds_bytes) *lds_bytes = (int32_t)chain_lds_bytes(m->nb);
+    HIPCHK(launch_philox_fill(ws, H.noise_key0, first, n_inst, k0, steps, (hipStream_t)stream));
+    *noise = ws - (k0 - 1);      // indexed by the absolute step k-1
+    *noise_stride = steps;
     return CCLQR_OK;
 }
 
@@ -370,78 +426,29 @@ extern "C" int cclqr_rollout_ex(const cclqr_mech* m, const cclqr_ctrl* c, int64_
                                 double* lam, const double* noise, int64_t noise_stride, double* traj, double* zT, int32_t* status,
                                 const cclqr_rollout_opts* opts, void* stream) {
     if (m && c && n_inst == 0) return CCLQR_OK;   // empty batch
-    if (!m || !c || !z0 || !zT) return fail(CCLQR_EINVAL, "null argument");
-    if (n_inst < 0 || steps < 0 || k0 < 1) return fail(CCLQR_EINVAL, "bad sizes");
-    if (c->nb != m->nb) return fail(CCLQR_EINVAL, "controller was built for another mechanism");
-    { int rc = check_device(m); if (rc != CCLQR_OK) return rc; }
-    if (!m->host.loop && (m->host.tree ? treereg_lds_bytes(m->nb, m->host.tree, m->host.npairs) : chain_lds_bytes(m->nb)) > 160 * 1024)
-        return fail(CCLQR_EUNSUPPORTED, "instance does not fit LDS");
-    const int64_t first = opts ? opts->first_instance : 0;
-    if (first < 0) return fail(CCLQR_EINVAL, "negative first_instance");
-    if (c->host.n_ctrl > 1 && first + n_inst > c->host.n_ctrl) return fail(CCLQR_EINVAL, "more instances than per-instance controller tables");
-    const CtrlDev& H = c->host;
-    double* pid_state = (opts && H.has_pid) ? opts->pid_state_dev : nullptr;      // never forwarded to a controller without a PID law
-    const int pid_slots = m->host.loop ? m->nj : m->nb;           // one (integrated, last) pair per joint; a tree has as many joints as bodies
-    if (pid_state && opts->pid_state_len != n_inst * (int64_t)pid_slots * 2) return fail(CCLQR_EINVAL, "pid_state_len must be n_inst * nb * 2 (closed loops: n_inst * joints * 2)");
-    // counter-based noise: generated for this launch into a workspace, read by the rollout like an injected array.  The workspace is the
-    // caller's (opts->noise_ws_dev: required for launches that share one controller on different streams or threads) or the handle's,
-    // which only ever grows OUTSIDE stream capture: hipMalloc / hipFree are illegal while a stream is being captured, so a captured
-    // launch needs the workspace sized beforehand (cclqr_ctrl_reserve_noise) or passed in.
-    const bool use_noise = H.noise_scale != 0.0 && H.mu > 0;
-    if (opts && (opts->flags & ~(CCLQR_ROLLOUT_NO_ALLOC | CCLQR_ROLLOUT_PACK_WAVEFRONTS | CCLQR_ROLLOUT_CARRY_STATUS))) return fail(CCLQR_EINVAL, "unknown bit in cclqr_rollout_opts.flags");
-    if (opts && (opts->flags & CCLQR_ROLLOUT_CARRY_STATUS) && !status) return fail(CCLQR_EINVAL, "CCLQR_ROLLOUT_CARRY_STATUS needs the status array (it is read and written)");
-    const bool no_alloc = opts && (opts->flags & CCLQR_ROLLOUT_NO_ALLOC);
-    // launches of a few steps on forests of chains (the step-per-launch form a hipGraph replays, BASELINE configs[4]) generate their samples inside the
-    // rollout kernel (rollout_chain_kernel<.., 3>): one kernel per step instead of two, and no workspace that could have to grow
+    { int rc = rollout_check_args(m, c, n_inst, steps, k0, z0, zT, status, opts); if (rc != CCLQR_OK) return rc; }
     bool philox_in_kernel = false;
-    if (use_noise && !noise && H.noise_philox && steps > 0) {
-        if (!m->host.loop && !m->host.tree && !H.has_pid && steps <= CCLQR_PHILOX_INKERNEL_STEPS && !(opts && opts->noise_ws_dev)) philox_in_kernel = true;
-    }
-    if (use_noise && !noise && H.noise_philox && steps > 0 && !philox_in_kernel) {
-        const size_t need = (size_t)n_inst * steps;
-        double* ws = nullptr;
-        if (opts && opts->noise_ws_dev) {
-            if (opts->noise_ws_len < (int64_t)need) return fail(CCLQR_EINVAL, "noise_ws_len must be at least n_inst * steps");
-            ws = opts->noise_ws_dev;
-        } else {
-            cclqr_ctrl* cm = const_cast<cclqr_ctrl*>(c);
-            if (cm->noise_ws_cap < need) {
-                // growing = a device synchronisation + an allocation.  A caller who has said CCLQR_ROLLOUT_NO_ALLOC (anybody with a capture open on
-                // this device, on whichever stream) is refused outright; without the flag the library can only see a capture of `stream` itself
-                if (no_alloc)
-                    return fail(CCLQR_EINVAL, "CCLQR_ROLLOUT_NO_ALLOC: the Philox noise workspace of this controller holds " + std::to_string(cm->noise_ws_cap) + " samples, the launch needs " +
-                                              std::to_string(need) + ": call cclqr_ctrl_reserve_noise(ctrl, n_inst, steps) beforehand or pass cclqr_rollout_opts.noise_ws_dev");
-                hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-                if (stream) HIPCHK(hipStreamIsCapturing((hipStream_t)stream, &cap));
-                if (cap != hipStreamCaptureStatusNone)
-                    return fail(CCLQR_EINVAL, "the Philox noise workspace cannot grow during stream capture: call cclqr_ctrl_reserve_noise(ctrl, n_inst, steps) "
-                                              "before the capture or pass cclqr_rollout_opts.noise_ws_dev");
-                int rc = cclqr_ctrl_reserve_noise(cm, n_inst, steps);
-                if (rc != CCLQR_OK) return rc;
-            }
-            ws = cm->noise_ws;
-        }
-        HIPCHK(launch_philox_fill(ws, H.noise_key0, first, n_inst, k0, steps, (hipStream_t)stream));
-        noise = ws - (k0 - 1);      // indexed by the absolute step k-1
-        noise_stride = steps;
-    }
-    const int extra = H.has_pid ? 2 : (philox_in_kernel ? 3 : ((H.has_fric || (use_noise && noise)) ? 1 : 0));
+    { int rc = rollout_resolve_noise(m, c, n_inst, steps, k0, opts, stream, &noise, &noise_stride, &philox_in_kernel); if (rc != CCLQR_OK) return rc; }
+    const CtrlDev& H = c->host;
+    // the one place a controller's tables become a kernel's law
+    const ControlLaw law = H.has_pid ? ControlLaw::Pid : (philox_in_kernel ? ControlLaw::PhiloxInKernel : ((H.has_fric || noise) ? ControlLaw::FricNoise : ControlLaw::Lqr));
     RolloutArgs a;
-    a.M = m->dev; a.C = c->dev; a.n_inst = n_inst; a.steps = steps; a.k0 = k0; a.z0 = z0; a.lam = lam; a.noise = use_noise ? noise : nullptr;
-    a.noise_stride = noise_stride; a.traj = traj; a.zT = zT; a.status = status; a.inst0 = first; a.pid_state = pid_state;
+    a.M = m->dev; a.C = c->dev; a.n_inst = n_inst; a.steps = steps; a.k0 = k0; a.z0 = z0; a.lam = lam; a.noise = noise;
+    a.noise_stride = noise_stride; a.traj = traj; a.zT = zT; a.status = status; a.inst0 = opts ? opts->first_instance : 0;
+    a.pid_state = (opts && H.has_pid) ? opts->pid_state_dev : nullptr;      // never forwarded to a controller without a PID law
     a.ipw = (opts && (opts->flags & CCLQR_ROLLOUT_PACK_WAVEFRONTS)) ? 1 : 0;
     a.carry = (opts && (opts->flags & CCLQR_ROLLOUT_CARRY_STATUS)) ? 1 : 0;
     const int newton_mode = opts ? opts->newton_mode : 0;
     a.eps_alone = (opts && opts->newton_eps_alone > 0.0) ? opts->newton_eps_alone : 1e-10;
     if (newton_mode != 0 && newton_mode != 1) return fail(CCLQR_EINVAL, "newton_mode must be 0 (exact rule) or 1 (residual-only stop)");
-    if (m->host.loop) {      // closed loops: one kernel, every law at run time (LQR / TrackingLQR, friction, noise, PID); newton_mode 1 under any of them
-        HIPCHK(launch_rollout_loop(a, m->nb, m->nj, newton_mode, (hipStream_t)stream));
+    if (m->shape.family == RolloutFamily::Loop) {      // one kernel, every law at run time (LQR / TrackingLQR, friction, noise, PID); newton_mode 1 under any of them
+        HIPCHK(launch_rollout_loop(a, m->shape, newton_mode, (hipStream_t)stream));
         return CCLQR_OK;
     }
-    if (newton_mode != 0 && extra != 0)
+    if (newton_mode != 0 && law != ControlLaw::Lqr)
         return fail(CCLQR_EUNSUPPORTED, "newton_mode 1 exists under the plain LQR / TrackingLQR law only on chains and branching trees (closed-loop mechanisms: every law)");
-    if (m->host.tree) HIPCHK(launch_rollout_treereg(a, m->nb, m->host.tree, m->host.npairs, extra, newton_mode, (hipStream_t)stream));
-    else HIPCHK(launch_rollout_chain(a, m->nb, extra, newton_mode, (hipStream_t)stream));
+    if (m->shape.family == RolloutFamily::Tree) HIPCHK(launch_rollout_treereg(a, m->shape, m->simds, law, newton_mode, (hipStream_t)stream));
+    else HIPCHK(launch_rollout_chain(a, m->shape, m->simds, law, newton_mode, (hipStream_t)stream));
     return CCLQR_OK;
 }
 
@@ -517,7 +524,7 @@ extern "C" int cclqr_linearize(const cclqr_mech* m, int32_t nk, const double* zd
     if (nk < 0 || mu < 0 || mu > nj) return fail(CCLQR_EINVAL, "Missmatched length for constraints");
     if (nk == 0) return CCLQR_OK;
     const size_t nz = 13 * (size_t)nb, mx = 12 * (size_t)nb, ml = 5 * (size_t)nj;
-    if (!loop && linearize_lds_bytes(nb, m->host.tree, m->host.npairs) > 160 * 1024) return fail(CCLQR_EUNSUPPORTED, "instance does not fit LDS");
+    if (!linearize_fits_lds(m)) return fail(CCLQR_EUNSUPPORTED, "instance does not fit LDS");
     LinArgs a;
     memset(&a, 0, sizeof(a));
     a.M = m->dev; a.nk = nk; a.mu = mu;
@@ -539,7 +546,7 @@ extern "C" int cclqr_linearize(const cclqr_mech* m, int32_t nk, const double* zd
     if (e == hipSuccess) e = hipMemcpy(dzd, zd, nk * nz * sizeof(double), hipMemcpyHostToDevice);
     if (e == hipSuccess && dFd) e = hipMemcpy(dFd, Fd, (size_t)nk * mu * sizeof(double), hipMemcpyHostToDevice);
     a.zd = dzd; a.Fd = dFd; a.A = dA; a.Bu = dBu; a.Bl = dBl; a.G = dG; a.status = dst;
-    if (e == hipSuccess) e = loop ? launch_linearize_loop(a, nb, nj, nullptr) : launch_linearize(a, nb, m->host.tree, m->host.npairs, nullptr);
+    if (e == hipSuccess) e = launch_linearize(a, m->shape, nullptr);
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e == hipSuccess) e = hipMemcpy(A, dA, nk * mx * mx * sizeof(double), hipMemcpyDeviceToHost);
     if (e == hipSuccess && mu > 0) e = hipMemcpy(Bu, dBu, nk * mx * mu * sizeof(double), hipMemcpyDeviceToHost);
@@ -591,7 +598,7 @@ static int linearize_projected_analytic(const cclqr_mech* m, int32_t nk, const d
                                         double* Ap, double* D) {
     const int nb = m->nb, nj = m->host.loop ? m->nj : nb, mx = 12 * nb, ml = 5 * nj;
     const size_t nz = 13 * (size_t)nb;
-    if (!m->host.loop && linearize_lds_bytes(nb, m->host.tree, m->host.npairs) > 160 * 1024) return fail(CCLQR_EUNSUPPORTED, "instance does not fit LDS");
+    if (!linearize_fits_lds(m)) return fail(CCLQR_EUNSUPPORTED, "instance does not fit LDS");
     if (!project_model_fits(mx, mu, ml)) return fail(CCLQR_EUNSUPPORTED, "the projection of this model does not fit LDS (use h > 0)");
     LinArgs a;
     memset(&a, 0, sizeof(a));
@@ -620,7 +627,7 @@ static int linearize_projected_analytic(const cclqr_mech* m, int32_t nk, const d
     if (e == hipSuccess) e = hipMemcpy(dzd, zd, nk * nz * sizeof(double), hipMemcpyHostToDevice);
     if (e == hipSuccess && dFd) e = hipMemcpy(dFd, Fd, (size_t)nk * mu * sizeof(double), hipMemcpyHostToDevice);
     a.zd = dzd; a.Fd = dFd; a.A = dA; a.Bu = dBu; a.Bl = dBl; a.G = dG; a.status = dst;
-    if (e == hipSuccess) e = m->host.loop ? launch_linearize_loop(a, nb, nj, nullptr) : launch_linearize(a, nb, m->host.tree, m->host.npairs, nullptr);
+    if (e == hipSuccess) e = launch_linearize(a, m->shape, nullptr);
     if (e == hipSuccess) e = launch_project_model(nk, mx, mu, ml, dA, dBu, dBl, dG, dAp, dD, dres, drank, nullptr);
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e == hipSuccess) e = hipMemcpy(Ap, dAp, (size_t)nk * mx * mx * sizeof(double), hipMemcpyDeviceToHost);
@@ -647,7 +654,7 @@ extern "C" int cclqr_linearize_projected(const cclqr_mech* m, int32_t nk, const 
         // the 17-body headline chain.  What does not fit is differenced instead (the h > 0 form with its documented step), so that the default
         // call is defined for every mechanism cclqr_mech_create takes
         const int nj = m->host.loop ? m->nj : nb;
-        const bool fits = project_model_fits(mx, mu, 5 * nj) && (m->host.loop || linearize_lds_bytes(nb, m->host.tree, m->host.npairs) <= 160 * 1024);
+        const bool fits = project_model_fits(mx, mu, 5 * nj) && linearize_fits_lds(m);
         if (fits) return linearize_projected_analytic(m, nk, zd, mu, ctrl_joint, Fd, Ap, D);
         h = 1e-6;
     }
@@ -703,8 +710,7 @@ extern "C" int cclqr_linearize_projected(const cclqr_mech* m, int32_t nk, const 
     }
     if (rc == CCLQR_OK && e == hipSuccess) {
         const long long work = (long long)nk * (mx + mu) * nb;
-        hipLaunchKernelGGL(fd_quotient_kernel, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, nullptr, dzT, nk, per, nb, mu, h, dAp, dD);
-        e = hipGetLastError();
+        e = launch_lds<false>(fd_quotient_kernel, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, nullptr, dzT, nk, per, nb, mu, h, dAp, dD);
     }
     if (rc == CCLQR_OK && e == hipSuccess) e = hipDeviceSynchronize();
     if (rc == CCLQR_OK && e == hipSuccess) e = hipMemcpy(st.data(), dst, n * sizeof(int32_t), hipMemcpyDeviceToHost);
@@ -843,7 +849,7 @@ extern "C" int cclqr_riccati_tracking_ex(const cclqr_mech* m, int32_t mu, const 
     if (e == hipSuccess) e = hipMemcpy(dzd, zd, nk * nz * sizeof(double), hipMemcpyHostToDevice);
     if (e == hipSuccess && dFd) e = hipMemcpy(dFd, Fd, (size_t)nk * mu * sizeof(double), hipMemcpyHostToDevice);
     a.zd = dzd; a.Fd = dFd; a.A = dA; a.Bu = dBu; a.Bl = dBl; a.G = dG; a.status = dst;
-    if (e == hipSuccess) e = launch_linearize(a, nb, m->host.tree, m->host.npairs, nullptr);
+    if (e == hipSuccess) e = launch_linearize(a, m->shape, nullptr);
     if (e == hipSuccess) e = hipMemcpy(st.data(), dst, nk * sizeof(int), hipMemcpyDeviceToHost);
     int rc = CCLQR_OK;
     if (e == hipSuccess) {

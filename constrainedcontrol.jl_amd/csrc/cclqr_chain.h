@@ -966,4 +966,21 @@ HD Lay make_chain_layout(int nb) {
     return L;
 }
 
+// ---- which instantiation of rollout_chain_kernel a chain of nb links runs on (host side: RolloutShape, cclqr_tables.h rollout_shape_of)
+// 8 lanes per instance up to 4 links (one elimination front of 6 lanes; eight instances per wavefront: the cartpole and triple-cartpole
+// configs), 16 up to 8 links (the two fronts need 14), 32 up to 32 links: with 16 lanes a 9..16-link instance would fill LDS with two
+// wavefronts per CU; 33..64 links: the whole wavefront is one instance (76.8 KB of LDS: two workgroups per CU)
+inline int chain_lanes_per_instance(int nb) { return nb <= 4 ? 8 : (nb <= 8 ? 16 : (nb <= 32 ? 32 : 64)); }
+// links the LDS image is laid out for: the instantiations of rollout_chain.hip (17 = the headline mechanism: exactly four workgroups per CU)
+inline int chain_layout_links(int nb) { return nb <= 4 ? 4 : (nb <= 8 ? 8 : (nb <= 16 ? 16 : (nb == 17 ? 17 : (nb <= 32 ? 32 : 64)))); }
+// lanes per link of the instantiation a mechanism of nb links runs on.  Only the 1- and 2-link mechanisms (pendulum, cartpole, acrobot: 2 of 8 lanes own a link)
+// get several -- three.  TWO lanes per link were built for every group with lanes to spare (3-4 links in 8 lanes, 5-8 in 16, 9-16 in 32), measured and NOT
+// shipped: the joint rows get cheaper (11.0 k -> 9.6 k cycles per step on the tracking triple cartpole) but the Schur rows do not (25.7 k -> 25.5 k) -- that phase is
+// bound by its ~180 LDS instructions per evaluation, which every lane issues whatever rows it keeps, not by its multiply-adds -- and the whole step moves by
+// < 0.5 % while the order of summation (hence noise-floor decisions of the stopping rule) changes (profiles/r05/lanes_per_link_*).
+inline int chain_lanes_per_link(int nb) { return nb <= 2 ? 3 : 1; }
+// links per lane group: with one lane per link the whole group, with three the two links of the <8, 4, 3, 2> instantiation
+inline int chain_links_per_group(int nb) { return chain_lanes_per_link(nb) == 1 ? chain_lanes_per_instance(nb) : 2; }
+inline size_t chain_lds_bytes(int nb) { return (size_t)(64 / chain_lanes_per_instance(nb)) * make_chain_layout(chain_layout_links(nb)).total * sizeof(double); }
+
 }  // namespace cclqr

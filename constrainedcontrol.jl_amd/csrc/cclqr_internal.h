@@ -27,25 +27,73 @@ struct RolloutArgs {
     int carry;            // CCLQR_ROLLOUT_CARRY_STATUS: `status` comes in with the instance's status of the launches before (0: none): an instance that was lost stays
                           // frozen and keeps its status, the others merge this launch's Newton count / failure into it
     int ipw;              // chain and tree kernels: instances per wavefront, 1 .. 64 / lanes per instance (lane groups beyond it hold no instance).  The caller of
-                          // launch_rollout_chain / launch_rollout_treereg passes 0 (the launch chooses: chain_instances_per_wavefront) or nonzero = pack every wavefront full
+                          // launch_rollout_chain / launch_rollout_treereg passes 0 (the launch chooses: spread_instances_per_wavefront) or nonzero = pack every wavefront full
 };
 
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (device, kernel) instead of once per launch: remembers the largest size set so
 // far and only calls the runtime when a launch needs more (capi.hip)
 hipError_t set_max_dynamic_lds_once(const void* fn, size_t lds);
+// The one way a kernel is launched: raise the kernel's dynamic-LDS limit (set_max_dynamic_lds_once), launch through the pointer, report the
+// launch error.  The pointer is selected once by the caller, so the kernel whose limit is raised is the kernel that runs.  RAISE_LDS = false
+// for the launches that stay under the 48 KB every kernel has: they make no runtime call besides the launch (nothing that a stream capture
+// could object to).  The arguments are converted to the kernel's parameter types as a direct call would.
+template <bool RAISE_LDS = true, class... P, class... A>
+inline hipError_t launch_lds(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t stream, const A&... args) {
+    if (RAISE_LDS) {
+        const hipError_t e = set_max_dynamic_lds_once((const void*)kernel, lds);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(kernel, grid, block, lds, stream, static_cast<P>(args)...);
+    return hipGetLastError();
+}
+
+// The control law a rollout kernel is instantiated for.  The values are the kernels' template parameter EXTRA (rollout_chain_kernel,
+// rollout_treereg_kernel); the closed-loop kernel has every law at run time.
+enum class ControlLaw : int {
+    Lqr = 0,           // LQR / TrackingLQR alone
+    FricNoise = 1,     // + joint friction and / or noise read from an array (the caller's, or a Philox workspace filled before the launch)
+    Pid = 2,           // + PID joints (and everything above)
+    PhiloxInKernel = 3 // LQR + noise whose samples the kernel generates itself (forests of chains only)
+};
+
+// Which kernel a mechanism's rollout runs on and how it is launched.  Filled once per mechanism (cclqr_tables.h rollout_shape_of, kept in
+// cclqr_mech); the entry points, the geometry queries and the launchers all read this one copy.
+enum class RolloutFamily : int { Chain, Tree, Loop };     // rollout_chain.hip / rollout_treereg.hip / rollout_loop.hip
+struct RolloutShape {
+    RolloutFamily family;
+    int G;             // lanes per instance (loops: the whole wavefront)
+    int NBP;           // links the LDS image is laid out for: with G it names the instantiation (loops: 0, one kernel with a run-time layout)
+    int KL, NL;        // lanes per link, links per lane group (KL * NL <= G)
+    int full;          // instances per full wavefront: 64 / G (loops: 1)
+    int NCB;           // loops: column blocks of eight the instantiation holds (loop_col_blocks), else 0
+    int pid_slots;     // (integrated, last) PID pairs per instance: one per joint
+    size_t lds;        // dynamic LDS per workgroup of the rollout kernel, `full` instances
+    size_t lin_lds;    // dynamic LDS per workgroup (one knot) of the mechanism's linearisation kernel
+};
+
+// Instances per wavefront of a launch.  A wavefront's step is latency -- a chain of dependent 5 x 5 stages -- not lanes, and a lane group without an
+// instance is not idle: it evaluates further step lengths of its neighbours' line searches (group_assist / the partner group).  So a batch that would
+// leave SIMDs without a wavefront when packed 64 / G to a wavefront is spread: the fewest instances per wavefront that still fit the batch into
+// `slots` wavefronts -- slots = every SIMD of the device for a persistent launch (steps >= 8: it has the device to itself), a quarter of them for
+// short launches (step-per-launch chains run several to a device, bench.py::_graph_captured_steps: spreading each over the whole device would
+// queue them behind one another).  Measured (tools/gpu_batch_density.py, ms per 1000 steps, packed -> spread): 256 tracking triple cartpoles
+// 43.7 -> 34.7, 256 cartpoles 24.6 -> 21.5, 256 17-body chains (300 steps) 22.0 -> 20.2, 4096 cartpoles (configs[1]) 24.9 -> 24.0; a batch that
+// fills the device is packed as before.  Same arithmetic in the same order either way: results are bitwise those of the packed launch
+// (tests/test_gpu_rollout.py::test_spread_and_packed_launches_agree_bitwise).  packed: CCLQR_ROLLOUT_PACK_WAVEFRONTS.  `full` = 64 / lanes per
+// instance (RolloutShape::full); simds = SIMDs of the mechanism's device (cclqr_mech::simds).  Chains and branching trees spread by this one rule.
+inline int spread_instances_per_wavefront(int full, int64_t n_inst, int steps, bool packed, int simds) {
+    if (packed || full == 1) return full;
+    const int64_t slots = steps >= 8 ? simds : simds / 4;
+    const int64_t ipw = (n_inst + slots - 1) / slots;
+    return ipw < 1 ? 1 : (ipw > full ? full : (int)ipw);
+}
 
 hipError_t launch_philox_fill(double* out, unsigned key0, long long inst0, long long n_inst, int k0, int steps, hipStream_t stream);
-// forests of chains (rollout_chain.hip)
-int chain_lanes_per_instance(int nb);
-int chain_layout_links(int nb);
-int chain_lanes_per_link(int nb);
-size_t chain_lds_bytes(int nb);
-int chain_instances_per_wavefront(int nb, int64_t n_inst, int steps, bool packed);
-int spread_instances_per_wavefront(int full, int64_t n_inst, int steps, bool packed);      // the rule itself (rollout_chain.hip); full = 64 / lanes per instance
-hipError_t launch_rollout_chain(const RolloutArgs& a, int nb, int extra, int newton_mode, hipStream_t stream);
-// closed-loop mechanisms (rollout_loop.hip)
-size_t loop_lds_bytes(int nb, int nj);
-hipError_t launch_rollout_loop(const RolloutArgs& a, int nb, int nj, int newton_mode, hipStream_t stream);
+// the three rollout launchers: forests of chains (rollout_chain.hip), branching trees (rollout_treereg.hip; a.M must point at the device image
+// [MechDev | TreeRegDev], treereg_of) and closed-loop mechanisms (rollout_loop.hip: every law at run time).  s = the mechanism's shape
+hipError_t launch_rollout_chain(const RolloutArgs& a, const RolloutShape& s, int simds, ControlLaw law, int newton_mode, hipStream_t stream);
+hipError_t launch_rollout_treereg(const RolloutArgs& a, const RolloutShape& s, int simds, ControlLaw law, int newton_mode, hipStream_t stream);
+hipError_t launch_rollout_loop(const RolloutArgs& a, const RolloutShape& s, int newton_mode, hipStream_t stream);
 
 struct LinArgs {
     const MechDev* M;
@@ -56,15 +104,15 @@ struct LinArgs {
     double *A, *Bu, *Bl, *G; // [nk][...] internal link order
     int* status;             // [nk]
 };
-size_t linearize_lds_bytes(int nb, int tree, int npairs);
-// closed-loop mechanisms (rollout_loop.hip): the model with the multipliers exogenous, and the rank-revealing projection onto (A', D)
-size_t linearize_loop_lds_bytes(int nb, int nj);
-hipError_t launch_linearize_loop(const LinArgs& a, int nb, int nj, hipStream_t stream);
+// the model with the multipliers exogenous at the knots a.zd, for any mechanism (linearize.hip): linearize_kernel for chains and trees; closed
+// loops are handed on to launch_linearize_loop (rollout_loop.hip, linearize_loop_kernel)
+hipError_t launch_linearize(const LinArgs& a, const RolloutShape& s, hipStream_t stream);
+hipError_t launch_linearize_loop(const LinArgs& a, const RolloutShape& s, hipStream_t stream);
+// the rank-revealing projection onto (A', D) (rollout_loop.hip)
 size_t project_model_lds_bytes(int mx, int mu, int ml);
 bool project_model_fits(int mx, int mu, int ml);      // dynamic + static LDS of project_model_kernel within one CU's 160 KB
 hipError_t launch_project_model(int nk, int mx, int mu, int ml, const double* A, const double* Bu, const double* Bl, const double* G, double* Ap, double* D,
                                 double* res, int* rank, hipStream_t stream);
-hipError_t launch_linearize(const LinArgs& a, int nb, int tree, int npairs, hipStream_t stream);
 
 struct RicArgs {
     int nprob, mx, mu, ml, N;
@@ -103,6 +151,8 @@ struct cclqr_mech {
     int link_of_body[CCLQR_MAXL];   // user body  -> internal link
     int link_of_joint[CCLQR_MAXL];  // user joint -> internal link (= link of its child body)
     int device;
+    int simds;                 // SIMDs of `device` (4 per compute unit): what spread_instances_per_wavefront spreads a small batch over
+    cclqr::RolloutShape shape; // the kernel this mechanism's rollouts and linearisations run on
 };
 // zero doubles behind a controller's gain table: the control phase fetches ceil(12 NBP / G) G entries of a row whatever the mechanism's own
 // 12 nb, i.e. up to 12 x 64 - 12 past the end of the LAST row when a short chain runs on a long image.  With one table per instance (n_ctrl > 1)

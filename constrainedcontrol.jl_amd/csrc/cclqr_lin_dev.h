@@ -13,6 +13,8 @@
 namespace cclqr {
 
 #define LJB 64   // doubles of per-joint scratch: 7 blocks of 9
+// dynamic LDS of linearize_kernel (one knot per workgroup): the instance image + the per-joint scratch
+inline size_t linearize_lds_bytes(int nb, int tree, int npairs) { return (size_t)(make_layout(nb, tree ? 2 * npairs : 0).total + LJB * nb) * sizeof(double); }
 // block offsets inside a joint's scratch
 #define J_TQA 0    // d(F+cT)_b / d qa
 #define J_RQA 9    // d(2tau+cR)_b / d qa

@@ -18,6 +18,9 @@
 
 namespace cclqr {
 
+// dynamic LDS of linearize_loop_kernel (one knot per workgroup): the instance image + the per-joint scratch
+inline size_t linearize_loop_lds_bytes(int nb, int nj) { return (size_t)(make_loop_layout(nb, nj).total + LJB * nj) * sizeof(double); }
+
 // L1: joint t (lane t < nj)
 HD void lp_lin_joint(int t, const Lay& Y, int JB, double* L, const LaneRegs& r, const MechDev* M) {
     if (t >= M->nj) return;

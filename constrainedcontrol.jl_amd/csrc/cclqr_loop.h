@@ -303,6 +303,8 @@ HD void lpr_solution(const LoopRowR<NCB>& R, int row, int mr, const Lay& Y, doub
 }
 // columns the instantiation must hold for nj joints
 HD int loop_col_blocks(int nj) { return (5 * nj + 7) / 8; }
+// dynamic LDS of rollout_loop_kernel (one instance per workgroup)
+inline size_t loop_lds_bytes(int nb, int nj) { return (size_t)make_loop_layout(nb, nj).total * sizeof(double); }
 
 // body solve: cd = sum G_k' dl ; ds = D^-1 (d + cd)
 HD void lp_body_solve(int t, const Lay& Y, double* L, const MechDev* M) {

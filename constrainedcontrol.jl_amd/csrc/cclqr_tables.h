@@ -3,13 +3,37 @@
 #pragma once
 #include "../../include/cclqr.h"
 #include "cclqr_internal.h"
-#include "cclqr_loop.h"
+#include "cclqr_treereg.h"
+#include "cclqr_lin_loop.h"
 #include <math.h>
 #include <string.h>
 #include <string>
 #include <vector>
 
 namespace cclqr {
+
+// The kernels of the mechanism H (build_mech_tables) of nb bodies and nj joints, and how they are launched.  Every rule is stated once, next to
+// the layout it sizes: chain_* (cclqr_chain.h), treereg_* (cclqr_treereg.h), loop_* (cclqr_loop.h), linearize_*lds_bytes (cclqr_lin_dev.h, cclqr_lin_loop.h).
+static inline RolloutShape rollout_shape_of(const MechDev& H, int nb, int nj) {
+    RolloutShape s;
+    memset(&s, 0, sizeof(s));
+    s.KL = 1;
+    if (H.loop) {
+        s.family = RolloutFamily::Loop;
+        s.G = s.NL = 64; s.NBP = 0; s.NCB = loop_col_blocks(nj); s.pid_slots = nj;
+        s.lds = loop_lds_bytes(nb, nj); s.lin_lds = linearize_loop_lds_bytes(nb, nj);
+    } else if (H.tree) {
+        s.family = RolloutFamily::Tree;
+        s.G = s.NL = treereg_lanes(nb, H.tree); s.NBP = treereg_layout_links(nb, H.tree); s.pid_slots = nb;      // a tree has as many joints as bodies
+        s.lds = treereg_lds_bytes(nb, H.tree, H.npairs); s.lin_lds = linearize_lds_bytes(nb, H.tree, H.npairs);
+    } else {
+        s.family = RolloutFamily::Chain;
+        s.G = chain_lanes_per_instance(nb); s.NBP = chain_layout_links(nb); s.KL = chain_lanes_per_link(nb); s.NL = chain_links_per_group(nb); s.pid_slots = nb;
+        s.lds = chain_lds_bytes(nb); s.lin_lds = linearize_lds_bytes(nb, H.tree, H.npairs);
+    }
+    s.full = 64 / s.G;
+    return s;
+}
 
 // two unit rows orthogonal to the unit axis (same deterministic choice as the oracle; any basis gives the same trajectory)
 static inline void orth_rows(const double* a, double* V12) {

@@ -10,10 +10,6 @@
 
 namespace cclqr {
 
-// rollout_treereg.hip; a.M must point at the device image [MechDev | TreeRegDev] (treereg_of)
-size_t treereg_lds_bytes(int nb, int tree8, int npairs);
-hipError_t launch_rollout_treereg(const RolloutArgs& a, int nb, int tree8, int npairs, int extra, int newton_mode, hipStream_t stream);
-
 // R for the mechanism H (H.tree != 0: build_mech_tables, cclqr_tables.h).  Returns false with `err` set when the mechanism does not fit
 // the kernel (more than TR_LANES links).
 static inline bool build_treereg_tables(const MechDev& H, TreeRegDev& R, std::string& err) {

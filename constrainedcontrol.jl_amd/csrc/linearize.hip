@@ -62,17 +62,10 @@ __global__ __launch_bounds__(64) void linearize_kernel(LinArgs a) {
     if (t == 0 && a.status) a.status[knot] = done ? its : -its;
 }
 
-size_t linearize_lds_bytes(int nb, int tree, int npairs) { return (size_t)(make_layout(nb, tree ? 2 * npairs : 0).total + LJB * nb) * sizeof(double); }
-
-hipError_t launch_linearize(const LinArgs& a, int nb, int tree, int npairs, hipStream_t stream) {
+hipError_t launch_linearize(const LinArgs& a, const RolloutShape& s, hipStream_t stream) {
+    if (s.family == RolloutFamily::Loop) return launch_linearize_loop(a, s, stream);
     if (a.nk <= 0) return hipSuccess;
-    const size_t lds = linearize_lds_bytes(nb, tree, npairs);
-    const void* fn = tree ? (const void*)linearize_kernel<true> : (const void*)linearize_kernel<false>;
-    hipError_t e = set_max_dynamic_lds_once(fn, lds);
-    if (e != hipSuccess) return e;
-    if (tree) hipLaunchKernelGGL(linearize_kernel<true>, dim3(a.nk), dim3(64), lds, stream, a);
-    else hipLaunchKernelGGL(linearize_kernel<false>, dim3(a.nk), dim3(64), lds, stream, a);
-    return hipGetLastError();
+    return launch_lds(s.family == RolloutFamily::Tree ? linearize_kernel<true> : linearize_kernel<false>, dim3(a.nk), dim3(64), s.lin_lds, stream, a);
 }
 
 }  // namespace cclqr

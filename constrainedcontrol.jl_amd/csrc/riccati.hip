@@ -1186,10 +1186,27 @@ __global__ void ric_backfill_kernel(RicGrid a) {
 }
 
 
-size_t ric_grid_work_doubles(int nprob, int mx, int mu, int ml, int N, int time_varying) {
-    const size_t nlin = time_varying ? (size_t)(N > 1 ? N - 1 : 1) : 1, na = (size_t)mx + mu, tm = (mx + 31) / 32;
-    const size_t sc = (((size_t)ml * ml + (size_t)ml * na + 3) & ~(size_t)1);
-    return (size_t)nprob * (nlin * mx * na + mx * na + 3 * (size_t)mx * mx + 2 * (size_t)mu * mx + 2 * tm * tm + tm * mu * na + nlin * sc + nlin * (ml + 2) + 8) + 64;
+// The sizes of g from a, and the workspace of one launch_riccati walked once: g's arrays are placed one behind the other from `base` (null: nowhere);
+// returns the doubles of the whole.  launch_riccati places them in a.work, which ric_total_work_doubles has sized by the same walk.  Behind
+// g.scratch ([nprob][nlin] blocks of sc doubles) sit the per-knot pivots that ric_knot_piv finds there.
+static size_t ric_lay_out(RicGrid& g, const RicArgs& a, double* base) {
+    g.nprob = a.nprob; g.mx = a.mx; g.mu = a.mu; g.ml = a.ml; g.N = a.N; g.nlin = a.time_varying ? (a.N > 1 ? a.N - 1 : 1) : 1;
+    g.na = a.mx + a.mu; g.tm = (a.mx + 31) / 32; g.tn = (g.na + 31) / 32;
+    const size_t np = g.nprob, nlin = g.nlin, mx = g.mx, na = g.na, mu = g.mu, ml = g.ml, tm = g.tm;
+    const size_t sc = (ml * ml + ml * na + 3) & ~(size_t)1;      // = ric_knot_piv
+    size_t o = 0;
+    auto take = [&](double*& p, size_t n) { p = base ? base + o : nullptr; o += n; };
+    take(g.AD, np * nlin * mx * na);
+    take(g.W, np * mx * na);
+    take(g.Abar, np * mx * mx);
+    take(g.P, 2 * np * mx * mx);
+    take(g.Ku, np * mu * mx);
+    take(g.KRK, np * mu * mx);
+    take(g.part, 2 * np * tm * tm);
+    take(g.TSp, np * tm * mu * na);
+    take(g.scratch, np * nlin * sc);
+    o += np * nlin * (ml + 2);      // pivots and the singular flag of every knot: ints, a double's room each
+    return o + 8 * np + 64;         // tail
 }
 
 // P and W in one CU's LDS, whole k-groups of four for the double-buffered tiles (mx = 12 nb always is a multiple of 4), and an S the
@@ -1210,7 +1227,7 @@ static bool ric_use_tiled(const RicArgs& a) {
     return a.mx >= 64 && a.nprob < 128;
 }
 
-size_t ric_total_work_doubles(const RicArgs& a) { return ric_grid_work_doubles(a.nprob, a.mx, a.mu, a.ml, a.N, a.time_varying); }
+size_t ric_total_work_doubles(const RicArgs& a) { RicGrid g; return ric_lay_out(g, a, nullptr); }
 
 // Pkp1 = Q + Ku'RKu + Abar'(Pk Abar) is symmetric, so of its T x T tiles of 16 x 16 only the T (T + 1) / 2 with column tile >= row tile are
 // computed (and mirrored): 21 instead of 36 for the Sawyer's 84 states.  A tile's A operand is the Abar fragment of the wavefront that owns the
@@ -1252,21 +1269,11 @@ hipError_t launch_riccati(const RicArgs& a, hipStream_t stream) {
     if (a.nprob <= 0) return hipSuccess;
     RicGrid g;
     ric_pp_assign((a.mx + 15) / 16, (a.mx + a.mu + 15) / 16, g.pp_mask);
-    g.nprob = a.nprob; g.mx = a.mx; g.mu = a.mu; g.ml = a.ml; g.N = a.N; g.nlin = a.time_varying ? (a.N > 1 ? a.N - 1 : 1) : 1;
-    g.na = a.mx + a.mu; g.tm = (a.mx + 31) / 32; g.tn = (g.na + 31) / 32; g.tol = a.tol; g.bf16_terms = a.bf16_terms; g.keep_last = a.keep_last; g.kpad = a.kpad;
+    (void)ric_lay_out(g, a, a.work);
+    g.tol = a.tol; g.bf16_terms = a.bf16_terms; g.keep_last = a.keep_last; g.kpad = a.kpad;
     g.p_rows = a.p_rows;
     g.A = a.A; g.Bu = a.Bu; g.Bl = a.Bl; g.G = a.G; g.Q = a.Q; g.R = a.R; g.K = a.K; g.kbreak = a.kbreak; g.status = a.status; g.stop = a.stop;
-    const size_t np = a.nprob, nlin = g.nlin, mx = a.mx, na = g.na, mu = a.mu, ml = a.ml;
-    double* o = a.work;
-    g.AD = o; o += np * nlin * mx * na;
-    g.W = o; o += np * mx * na;
-    g.Abar = o; o += np * mx * mx;
-    g.P = o; o += 2 * np * mx * mx;
-    g.Ku = o; o += np * mu * mx;
-    g.KRK = o; o += np * mu * mx;
-    g.part = o; o += 2 * np * g.tm * g.tm;
-    g.TSp = o; o += np * g.tm * mu * na;
-    g.scratch = o;
+    const size_t np = a.nprob, na = g.na, mu = a.mu, ml = a.ml;
     hipError_t e = hipMemsetAsync(a.stop, 0, np * sizeof(int), stream);
     if (e == hipSuccess) e = hipMemsetAsync(a.status, 0, np * sizeof(int), stream);
     if (e == hipSuccess) e = hipMemsetAsync(a.kbreak, 0, np * sizeof(int), stream);
@@ -1281,13 +1288,9 @@ hipError_t launch_riccati(const RicArgs& a, hipStream_t stream) {
         cols = (int)c;
         lds = (ml * ml + ml * c) * sizeof(double);        // G Bλ for the pivoted LU + one batch of right-hand-side columns
     }
-    if (lds > 0) {
-        e = set_max_dynamic_lds_once((const void*)ric_project_kernel<true>, lds);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(ric_project_kernel<true>, dim3(g.nlin, a.nprob), dim3(RIC_THREADS), lds, stream, g, cols);
-    } else {
-        hipLaunchKernelGGL(ric_project_kernel<false>, dim3(g.nlin, a.nprob), dim3(RIC_THREADS), 0, stream, g, 0);
-    }
+    e = lds > 0 ? launch_lds(ric_project_kernel<true>, dim3(g.nlin, a.nprob), dim3(RIC_THREADS), lds, stream, g, cols)
+                : launch_lds<false>(ric_project_kernel<false>, dim3(g.nlin, a.nprob), dim3(RIC_THREADS), 0, stream, g, 0);
+    if (e != hipSuccess) return e;
     if (!ric_use_tiled(a)) {
         const size_t rl = ric_resident_lds_bytes(a.mx, a.mu);
         typedef void (*ResKernel)(RicGrid);
@@ -1304,23 +1307,21 @@ hipError_t launch_riccati(const RicArgs& a, hipStream_t stream) {
             if (a.mu == 7) kern = a.bf16_terms == 1 ? riccati_resident_kernel<7, 21, 1> : (a.bf16_terms == 2 ? riccati_resident_kernel<7, 21, 2> : riccati_resident_kernel<7, 21, 3>);
             else kern = a.bf16_terms == 1 ? riccati_resident_kernel<1, 6, 1> : (a.bf16_terms == 2 ? riccati_resident_kernel<1, 6, 2> : riccati_resident_kernel<1, 6, 3>);
         }
-        e = set_max_dynamic_lds_once((const void*)kern, rl);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(kern, dim3(a.nprob), dim3(RIC_THREADS), rl, stream, g);
-        return hipGetLastError();
+        return launch_lds(kern, dim3(a.nprob), dim3(RIC_THREADS), rl, stream, g);
     }
     const size_t lds_gain = (mu * na + mu * mu + 2 * RU * mu) * sizeof(double) + (mu + 2) * sizeof(int), lds_pn = 2 * mu * 32 * sizeof(double);
+    void (*const gain_update)(RicGrid, int) = ric_gain_update_kernel;      // (one name for the limit raised here, once per call, and the launches below)
     if (lds_gain > 48 * 1024) {
-        e = set_max_dynamic_lds_once((const void*)ric_gain_update_kernel, lds_gain);
+        e = set_max_dynamic_lds_once((const void*)gain_update, lds_gain);
         if (e != hipSuccess) return e;
     }
     for (int k = a.N - 1; k >= 1; k--) {                                 // for outer k=N-1:-1:1                    lqr.jl:150
-        hipLaunchKernelGGL(ric_pa_kernel, dim3(g.tm * g.tn, a.nprob), dim3(TILE_THREADS), 32 * mu * sizeof(double), stream, g, k);
-        hipLaunchKernelGGL(ric_gain_update_kernel, dim3((a.mx + RU - 1) / RU, a.nprob), dim3(TILE_THREADS), lds_gain, stream, g, k);
-        hipLaunchKernelGGL(ric_pn_kernel, dim3(g.tm * g.tm, a.nprob), dim3(TILE_THREADS), lds_pn, stream, g, k);
+        e = launch_lds<false>(ric_pa_kernel, dim3(g.tm * g.tn, a.nprob), dim3(TILE_THREADS), 32 * mu * sizeof(double), stream, g, k);
+        if (e == hipSuccess) e = launch_lds<false>(gain_update, dim3((a.mx + RU - 1) / RU, a.nprob), dim3(TILE_THREADS), lds_gain, stream, g, k);
+        if (e == hipSuccess) e = launch_lds<false>(ric_pn_kernel, dim3(g.tm * g.tm, a.nprob), dim3(TILE_THREADS), lds_pn, stream, g, k);
+        if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(ric_backfill_kernel, dim3(a.nprob), dim3(TILE_THREADS), 0, stream, g);
-    return hipGetLastError();
+    return launch_lds<false>(ric_backfill_kernel, dim3(a.nprob), dim3(TILE_THREADS), 0, stream, g);
 }
 
 #ifdef CCLQR_PROFILE

@@ -211,8 +211,7 @@ __global__ __launch_bounds__(256) void philox_fill_kernel(double* out, unsigned 
 hipError_t launch_philox_fill(double* out, unsigned key0, long long inst0, long long n_inst, int k0, int steps, hipStream_t stream) {
     const long long total = n_inst * steps;
     if (total <= 0) return hipSuccess;
-    hipLaunchKernelGGL(philox_fill_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, out, key0, inst0, n_inst, k0, steps);
-    return hipGetLastError();
+    return launch_lds<false>(philox_fill_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, out, key0, inst0, n_inst, k0, steps);
 }
 
 // NBP: links the LDS image is laid out for (>= nb): a compile-time layout turns every LDS offset into an immediate instead
@@ -718,85 +717,37 @@ extern "C" int cclqr_prof_read_chain(unsigned long long* out, int reset) {
 }
 #endif
 
-// 8 lanes per instance up to 4 links (one elimination front of 6 lanes; eight instances per wavefront: the cartpole and triple-cartpole
-// configs), 16 up to 8 links (the two fronts need 14), 32 up to 32 links: with 16 lanes a 9..16-link instance would fill LDS with two
-// wavefronts per CU; 33..64 links: the whole wavefront is one instance (76.8 KB of LDS: two workgroups per CU)
-int chain_lanes_per_instance(int nb) { return nb <= 4 ? 8 : (nb <= 8 ? 16 : (nb <= 32 ? 32 : 64)); }
-// links the LDS image is laid out for: the instantiations below (17 = the headline mechanism: exactly four workgroups per CU)
-int chain_layout_links(int nb) { return nb <= 4 ? 4 : (nb <= 8 ? 8 : (nb <= 16 ? 16 : (nb == 17 ? 17 : (nb <= 32 ? 32 : 64)))); }
-
-// Instances per wavefront of a launch.  A wavefront's step is latency -- a chain of dependent 5 x 5 stages -- not lanes, and a lane group without an
-// instance is not idle: it evaluates further step lengths of its neighbours' line searches (group_assist / the partner group).  So a batch that would
-// leave SIMDs without a wavefront when packed 64 / G to a wavefront is spread: the fewest instances per wavefront that still fit the batch into
-// `slots` wavefronts -- slots = every SIMD of the device for a persistent launch (steps >= 8: it has the device to itself), a quarter of them for
-// short launches (step-per-launch chains run several to a device, bench.py::_graph_captured_steps: spreading each over the whole device would
-// queue them behind one another).  Measured (tools/gpu_batch_density.py, ms per 1000 steps, packed -> spread): 256 tracking triple cartpoles
-// 43.7 -> 34.7, 256 cartpoles 24.6 -> 21.5, 256 17-body chains (300 steps) 22.0 -> 20.2, 4096 cartpoles (configs[1]) 24.9 -> 24.0; a batch that
-// fills the device is packed as before.  Same arithmetic in the same order either way: results are bitwise those of the packed launch
-// (tests/test_gpu_rollout.py::test_spread_and_packed_launches_agree_bitwise).  packed: CCLQR_ROLLOUT_PACK_WAVEFRONTS.  `full` = 64 / lanes per
-// instance; the branching-tree kernel (rollout_treereg.hip) spreads by the same rule.
-int spread_instances_per_wavefront(int full, int64_t n_inst, int steps, bool packed) {
-    if (packed || full == 1) return full;
-    static int simds = 0;
-    if (simds == 0) {
-        int dev = 0, cus = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-        simds = 4 * cus;
-    }
-    const int64_t slots = steps >= 8 ? simds : simds / 4;
-    const int64_t ipw = (n_inst + slots - 1) / slots;
-    return ipw < 1 ? 1 : (ipw > full ? full : (int)ipw);
-}
-int chain_instances_per_wavefront(int nb, int64_t n_inst, int steps, bool packed) {
-    return spread_instances_per_wavefront(64 / chain_lanes_per_instance(nb), n_inst, steps, packed);
-}
-
-size_t chain_lds_bytes(int nb) { return (size_t)(64 / chain_lanes_per_instance(nb)) * make_chain_layout(chain_layout_links(nb)).total * sizeof(double); }
-
 template <int G, int NBP, int KL = 1, int NL = G>
-static hipError_t launch_chain_one(const RolloutArgs& a, int extra, int newton_mode, unsigned grid, size_t lds, hipStream_t stream) {
-    const bool relax = newton_mode != 0 && extra == 0;
-    const void* f = relax ? (const void*)rollout_chain_kernel<G, NBP, 0, true, KL, NL>
-                          : (extra == 0 ? (const void*)rollout_chain_kernel<G, NBP, 0, false, KL, NL> : (extra == 1 ? (const void*)rollout_chain_kernel<G, NBP, 1, false, KL, NL>
-                          : (extra == 2 ? (const void*)rollout_chain_kernel<G, NBP, 2, false, KL, NL> : (const void*)rollout_chain_kernel<G, NBP, 3, false, KL, NL>)));
-    hipError_t e = set_max_dynamic_lds_once(f, lds);
-    if (e != hipSuccess) return e;
-    if (relax) hipLaunchKernelGGL((rollout_chain_kernel<G, NBP, 0, true, KL, NL>), dim3(grid), dim3(64), lds, stream, a);
-    else if (extra == 0) hipLaunchKernelGGL((rollout_chain_kernel<G, NBP, 0, false, KL, NL>), dim3(grid), dim3(64), lds, stream, a);
-    else if (extra == 1) hipLaunchKernelGGL((rollout_chain_kernel<G, NBP, 1, false, KL, NL>), dim3(grid), dim3(64), lds, stream, a);
-    else if (extra == 2) hipLaunchKernelGGL((rollout_chain_kernel<G, NBP, 2, false, KL, NL>), dim3(grid), dim3(64), lds, stream, a);
-    else hipLaunchKernelGGL((rollout_chain_kernel<G, NBP, 3, false, KL, NL>), dim3(grid), dim3(64), lds, stream, a);
-    return hipGetLastError();
+static hipError_t launch_chain_one(const RolloutArgs& a, ControlLaw law, bool relax, unsigned grid, size_t lds, hipStream_t stream) {
+    void (*kern)(RolloutArgs) = nullptr;
+    switch (law) {
+        case ControlLaw::Lqr: kern = relax ? rollout_chain_kernel<G, NBP, 0, true, KL, NL> : rollout_chain_kernel<G, NBP, 0, false, KL, NL>; break;
+        case ControlLaw::FricNoise: kern = rollout_chain_kernel<G, NBP, 1, false, KL, NL>; break;
+        case ControlLaw::Pid: kern = rollout_chain_kernel<G, NBP, 2, false, KL, NL>; break;
+        case ControlLaw::PhiloxInKernel: kern = rollout_chain_kernel<G, NBP, 3, false, KL, NL>; break;
+    }
+    if (!kern) return hipErrorInvalidValue;
+    return launch_lds(kern, dim3(grid), dim3(64), lds, stream, a);
 }
 
-// lanes per link of the instantiation a mechanism of nb links runs on.  Only the 1- and 2-link mechanisms (pendulum, cartpole, acrobot: 2 of 8 lanes own a link)
-// get several -- three.  TWO lanes per link were built for every group with lanes to spare (3-4 links in 8 lanes, 5-8 in 16, 9-16 in 32), measured and NOT
-// shipped: the joint rows get cheaper (11.0 k -> 9.6 k cycles per step on the tracking triple cartpole) but the Schur rows do not (25.7 k -> 25.5 k) -- that phase is
-// bound by its ~180 LDS instructions per evaluation, which every lane issues whatever rows it keeps, not by its multiply-adds -- and the whole step moves by
-// < 0.5 % while the order of summation (hence noise-floor decisions of the stopping rule) changes (profiles/r05/lanes_per_link_*).
-int chain_lanes_per_link(int nb) { return nb <= 2 ? 3 : 1; }
-
-hipError_t launch_rollout_chain(const RolloutArgs& a_in, int nb, int extra, int newton_mode, hipStream_t stream) {
-    const int per_wg = chain_instances_per_wavefront(nb, a_in.n_inst, a_in.steps, a_in.ipw != 0);
-    const size_t lds = chain_lds_bytes(nb);
+hipError_t launch_rollout_chain(const RolloutArgs& a_in, const RolloutShape& s, int simds, ControlLaw law, int newton_mode, hipStream_t stream) {
     RolloutArgs a = a_in;
-    a.ipw = per_wg;
-    const unsigned grid = (unsigned)((a.n_inst + per_wg - 1) / per_wg);
+    a.ipw = spread_instances_per_wavefront(s.full, a.n_inst, a.steps, a_in.ipw != 0, simds);
+    const unsigned grid = (unsigned)((a.n_inst + a.ipw - 1) / a.ipw);
     if (grid == 0) return hipSuccess;
     {   // the reduction level's back substitution reads DL / R of one link past the chain and selects the value away (cclqr_chain.h cr_back): that
         // read must stay inside the instance's image whatever order a later re-cut of the layout puts the arrays in
-        const int nbp = chain_layout_links(nb);
-        const Lay Y = make_chain_layout(nbp);
-        if (Y.DL + 5 * (nbp + 1) > Y.total || Y.R + 5 * (nbp + 1) > Y.total) return hipErrorInvalidValue;
+        const Lay Y = make_chain_layout(s.NBP);
+        if (Y.DL + 5 * (s.NBP + 1) > Y.total || Y.R + 5 * (s.NBP + 1) > Y.total) return hipErrorInvalidValue;
     }
-    const int kl = chain_lanes_per_link(nb);
-    switch (chain_layout_links(nb)) {
-        case 4: return kl == 3 ? launch_chain_one<8, 4, 3, 2>(a, extra, newton_mode, grid, lds, stream) : launch_chain_one<8, 4>(a, extra, newton_mode, grid, lds, stream);
-        case 8: return launch_chain_one<16, 8>(a, extra, newton_mode, grid, lds, stream);
-        case 16: return launch_chain_one<32, 16>(a, extra, newton_mode, grid, lds, stream);
-        case 17: return launch_chain_one<32, 17>(a, extra, newton_mode, grid, lds, stream);
-        case 32: return launch_chain_one<32, 32>(a, extra, newton_mode, grid, lds, stream);
-        default: return launch_chain_one<64, 64>(a, extra, newton_mode, grid, lds, stream);
+    const bool relax = newton_mode != 0;      // (the residual-only stop exists under the plain law only: launch_chain_one)
+    switch (s.NBP) {
+        case 4: return s.KL == 3 ? launch_chain_one<8, 4, 3, 2>(a, law, relax, grid, s.lds, stream) : launch_chain_one<8, 4>(a, law, relax, grid, s.lds, stream);
+        case 8: return launch_chain_one<16, 8>(a, law, relax, grid, s.lds, stream);
+        case 16: return launch_chain_one<32, 16>(a, law, relax, grid, s.lds, stream);
+        case 17: return launch_chain_one<32, 17>(a, law, relax, grid, s.lds, stream);
+        case 32: return launch_chain_one<32, 32>(a, law, relax, grid, s.lds, stream);
+        default: return launch_chain_one<64, 64>(a, law, relax, grid, s.lds, stream);
     }
 }
 

@@ -385,28 +385,13 @@ __global__ __launch_bounds__(PROJ_THREADS) void project_model_kernel(int mx, int
     }
 }
 
-size_t linearize_loop_lds_bytes(int nb, int nj) { return (size_t)(make_loop_layout(nb, nj).total + LJB * nj) * sizeof(double); }
-template <int NCB>
-static hipError_t launch_linearize_loop_t(const LinArgs& a, size_t lds, hipStream_t stream) {
-    hipError_t e = set_max_dynamic_lds_once((const void*)linearize_loop_kernel<NCB>, lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(linearize_loop_kernel<NCB>, dim3(a.nk), dim3(64), lds, stream, a);
-    return hipGetLastError();
-}
-hipError_t launch_linearize_loop(const LinArgs& a, int nb, int nj, hipStream_t stream) {
+hipError_t launch_linearize_loop(const LinArgs& a, const RolloutShape& s, hipStream_t stream) {
     if (a.nk <= 0) return hipSuccess;
-    const size_t lds = linearize_loop_lds_bytes(nb, nj);
-    switch (loop_col_blocks(nj)) {
-        case 1: return launch_linearize_loop_t<1>(a, lds, stream);
-        case 2: return launch_linearize_loop_t<2>(a, lds, stream);
-        case 3: return launch_linearize_loop_t<3>(a, lds, stream);
-        case 4: return launch_linearize_loop_t<4>(a, lds, stream);
-        case 5: return launch_linearize_loop_t<5>(a, lds, stream);
-        case 6: return launch_linearize_loop_t<6>(a, lds, stream);
-        case 7: return launch_linearize_loop_t<7>(a, lds, stream);
-        case 8: return launch_linearize_loop_t<8>(a, lds, stream);
-        default: return hipErrorInvalidValue;
-    }
+    // 5 nj <= 60 columns (CCLQR_LOOP_MAXJ) in blocks of eight
+    static void (*const by_ncb[9])(LinArgs) = {nullptr, linearize_loop_kernel<1>, linearize_loop_kernel<2>, linearize_loop_kernel<3>, linearize_loop_kernel<4>,
+                                               linearize_loop_kernel<5>, linearize_loop_kernel<6>, linearize_loop_kernel<7>, linearize_loop_kernel<8>};
+    if (s.NCB < 1 || s.NCB > 8) return hipErrorInvalidValue;
+    return launch_lds(by_ncb[s.NCB], dim3(a.nk), dim3(64), s.lin_lds, stream, a);
 }
 // dynamic LDS of project_model_kernel; project_model_fits adds the kernel's static LDS (red_v, red_i, four scalars) before comparing with a CU's 160 KB
 size_t project_model_lds_bytes(int mx, int mu, int ml) { return ((size_t)ml * (ml + mx + mu) + ml) * sizeof(double) + 2 * (size_t)ml * sizeof(int) + 16; }
@@ -418,35 +403,15 @@ hipError_t launch_project_model(int nk, int mx, int mu, int ml, const double* A,
                                 double* res, int* rank, hipStream_t stream) {
     if (nk <= 0) return hipSuccess;
     const size_t lds = project_model_lds_bytes(mx, mu, ml);
-    hipError_t e = set_max_dynamic_lds_once((const void*)project_model_kernel, lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(project_model_kernel, dim3(nk), dim3(PROJ_THREADS), lds, stream, mx, mu, ml, A, Bu, Bl, G, Ap, D, res, rank);
-    return hipGetLastError();
+    return launch_lds(project_model_kernel, dim3(nk), dim3(PROJ_THREADS), lds, stream, mx, mu, ml, A, Bu, Bl, G, Ap, D, res, rank);
 }
 
-size_t loop_lds_bytes(int nb, int nj) { return (size_t)make_loop_layout(nb, nj).total * sizeof(double); }
-
-template <int NCB>
-static hipError_t launch_rollout_loop_t(const RolloutArgs& a, size_t lds, int newton_mode, hipStream_t stream) {
-    hipError_t e = set_max_dynamic_lds_once((const void*)rollout_loop_kernel<NCB>, lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(rollout_loop_kernel<NCB>, dim3((unsigned)a.n_inst), dim3(64), lds, stream, a, newton_mode != 0 ? 1 : 0);
-    return hipGetLastError();
-}
-hipError_t launch_rollout_loop(const RolloutArgs& a, int nb, int nj, int newton_mode, hipStream_t stream) {
+hipError_t launch_rollout_loop(const RolloutArgs& a, const RolloutShape& s, int newton_mode, hipStream_t stream) {
     if (a.n_inst <= 0) return hipSuccess;
-    const size_t lds = loop_lds_bytes(nb, nj);
-    switch (loop_col_blocks(nj)) {       // 5 nj <= 60 columns (CCLQR_LOOP_MAXJ) in blocks of eight
-        case 1: return launch_rollout_loop_t<1>(a, lds, newton_mode, stream);
-        case 2: return launch_rollout_loop_t<2>(a, lds, newton_mode, stream);
-        case 3: return launch_rollout_loop_t<3>(a, lds, newton_mode, stream);
-        case 4: return launch_rollout_loop_t<4>(a, lds, newton_mode, stream);
-        case 5: return launch_rollout_loop_t<5>(a, lds, newton_mode, stream);
-        case 6: return launch_rollout_loop_t<6>(a, lds, newton_mode, stream);
-        case 7: return launch_rollout_loop_t<7>(a, lds, newton_mode, stream);
-        case 8: return launch_rollout_loop_t<8>(a, lds, newton_mode, stream);
-        default: return hipErrorInvalidValue;
-    }
+    static void (*const by_ncb[9])(RolloutArgs, int) = {nullptr, rollout_loop_kernel<1>, rollout_loop_kernel<2>, rollout_loop_kernel<3>, rollout_loop_kernel<4>,
+                                                        rollout_loop_kernel<5>, rollout_loop_kernel<6>, rollout_loop_kernel<7>, rollout_loop_kernel<8>};
+    if (s.NCB < 1 || s.NCB > 8) return hipErrorInvalidValue;
+    return launch_lds(by_ncb[s.NCB], dim3((unsigned)a.n_inst), dim3(64), s.lds, stream, a, newton_mode != 0 ? 1 : 0);
 }
 
 }  // namespace cclqr

@@ -540,50 +540,37 @@ extern "C" int cclqr_prof_read_treereg(unsigned long long* out, int reset) {
 }
 #endif
 
-size_t treereg_lds_bytes(int nb, int tree8, int npairs) {
-    return (size_t)(64 / treereg_lanes(nb, tree8)) * make_treereg_layout(treereg_layout_links(nb, tree8), 2 * npairs).total * sizeof(double);
-}
-
 template <int G, int NBP>
-static hipError_t launch_treereg_one(const RolloutArgs& a, int extra, int newton_mode, unsigned grid, size_t lds, hipStream_t stream) {
-    const bool relax = newton_mode != 0 && extra == 0;
-    const void* f = relax ? (const void*)rollout_treereg_kernel<G, NBP, 0, true>
-                          : (extra == 0 ? (const void*)rollout_treereg_kernel<G, NBP, 0> : (extra == 1 ? (const void*)rollout_treereg_kernel<G, NBP, 1> : (const void*)rollout_treereg_kernel<G, NBP, 2>));
-    hipError_t e = set_max_dynamic_lds_once(f, lds);
-    if (e != hipSuccess) return e;
-    if (relax) hipLaunchKernelGGL((rollout_treereg_kernel<G, NBP, 0, true>), dim3(grid), dim3(64), lds, stream, a);
-    else if (extra == 0) hipLaunchKernelGGL((rollout_treereg_kernel<G, NBP, 0>), dim3(grid), dim3(64), lds, stream, a);
-    else if (extra == 1) hipLaunchKernelGGL((rollout_treereg_kernel<G, NBP, 1>), dim3(grid), dim3(64), lds, stream, a);
-    else hipLaunchKernelGGL((rollout_treereg_kernel<G, NBP, 2>), dim3(grid), dim3(64), lds, stream, a);
-    return hipGetLastError();
+static hipError_t launch_treereg_one(const RolloutArgs& a, ControlLaw law, bool relax, unsigned grid, size_t lds, hipStream_t stream) {
+    void (*kern)(RolloutArgs) = nullptr;
+    switch (law) {
+        case ControlLaw::Lqr: kern = relax ? rollout_treereg_kernel<G, NBP, 0, true> : rollout_treereg_kernel<G, NBP, 0>; break;
+        case ControlLaw::FricNoise: kern = rollout_treereg_kernel<G, NBP, 1>; break;
+        case ControlLaw::Pid: kern = rollout_treereg_kernel<G, NBP, 2>; break;
+        case ControlLaw::PhiloxInKernel: break;      // chains only: a tree's Philox noise is filled into a workspace before the launch (capi.hip)
+    }
+    if (!kern) return hipErrorInvalidValue;
+    return launch_lds(kern, dim3(grid), dim3(64), lds, stream, a);
 }
 
 // a.M must be the device image [MechDev | TreeRegDev] of capi.hip (treereg_of)
-hipError_t launch_rollout_treereg(const RolloutArgs& a_in, int nb, int tree8, int npairs, int extra, int newton_mode, hipStream_t stream) {
-    const int G = treereg_lanes(nb, tree8), nbp = treereg_layout_links(nb, tree8);
-    const int per_wg = spread_instances_per_wavefront(64 / G, a_in.n_inst, a_in.steps, a_in.ipw != 0);
+hipError_t launch_rollout_treereg(const RolloutArgs& a_in, const RolloutShape& s, int simds, ControlLaw law, int newton_mode, hipStream_t stream) {
     RolloutArgs a = a_in;
-    a.ipw = per_wg;
-    const size_t lds = treereg_lds_bytes(nb, tree8, npairs);
-    const unsigned grid = (unsigned)((a.n_inst + per_wg - 1) / per_wg);
+    a.ipw = spread_instances_per_wavefront(s.full, a.n_inst, a.steps, a_in.ipw != 0, simds);
+    const unsigned grid = (unsigned)((a.n_inst + a.ipw - 1) / a.ipw);
     if (grid == 0) return hipSuccess;
-    if (nb > G || nb > nbp) return hipErrorInvalidValue;
-    if (G == 16) {
-#if TR_G16_MAXLINKS > 8
-        if (nbp == 14) return launch_treereg_one<16, 14>(a, extra, newton_mode, grid, lds, stream);
-        if (nbp > 8) return hipErrorInvalidValue;
-#endif
-        return nbp == 4 ? launch_treereg_one<16, 4>(a, extra, newton_mode, grid, lds, stream) : launch_treereg_one<16, 8>(a, extra, newton_mode, grid, lds, stream);
-    }
-    if (G == 64) return nbp == 48 ? launch_treereg_one<64, 48>(a, extra, newton_mode, grid, lds, stream) : launch_treereg_one<64, 64>(a, extra, newton_mode, grid, lds, stream);
-    switch (nbp) {
-        case 8: return launch_treereg_one<32, 8>(a, extra, newton_mode, grid, lds, stream);
-        case 10: return launch_treereg_one<32, 10>(a, extra, newton_mode, grid, lds, stream);
-        case 12: return launch_treereg_one<32, 12>(a, extra, newton_mode, grid, lds, stream);
-        case 14: return launch_treereg_one<32, 14>(a, extra, newton_mode, grid, lds, stream);
-        case 16: return launch_treereg_one<32, 16>(a, extra, newton_mode, grid, lds, stream);
-        case 24: return launch_treereg_one<32, 24>(a, extra, newton_mode, grid, lds, stream);
-        default: return launch_treereg_one<32, 32>(a, extra, newton_mode, grid, lds, stream);
+    if (s.pid_slots > s.G || s.pid_slots > s.NBP) return hipErrorInvalidValue;      // (a tree has a joint, hence a PID slot, per link)
+    const bool relax = newton_mode != 0;      // (the residual-only stop exists under the plain law only: launch_treereg_one)
+    if (s.G == 16) return s.NBP == 4 ? launch_treereg_one<16, 4>(a, law, relax, grid, s.lds, stream) : launch_treereg_one<16, 8>(a, law, relax, grid, s.lds, stream);
+    if (s.G == 64) return s.NBP == 48 ? launch_treereg_one<64, 48>(a, law, relax, grid, s.lds, stream) : launch_treereg_one<64, 64>(a, law, relax, grid, s.lds, stream);
+    switch (s.NBP) {
+        case 8: return launch_treereg_one<32, 8>(a, law, relax, grid, s.lds, stream);
+        case 10: return launch_treereg_one<32, 10>(a, law, relax, grid, s.lds, stream);
+        case 12: return launch_treereg_one<32, 12>(a, law, relax, grid, s.lds, stream);
+        case 14: return launch_treereg_one<32, 14>(a, law, relax, grid, s.lds, stream);
+        case 16: return launch_treereg_one<32, 16>(a, law, relax, grid, s.lds, stream);
+        case 24: return launch_treereg_one<32, 24>(a, law, relax, grid, s.lds, stream);
+        default: return launch_treereg_one<32, 32>(a, law, relax, grid, s.lds, stream);
     }
 }
 

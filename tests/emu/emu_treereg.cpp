@@ -268,3 +268,19 @@ extern "C" int emu_treereg_schedule(const cclqr_mech_desc* md, int* ne_steps, in
     *ne_steps = Rt.ne_steps; *nb_steps = Rt.nb_steps; *lanes = Rt.lanes;
     return 0;
 }
+
+// the launch shape libcclqr.so keeps for a mechanism (cclqr_tables.h rollout_shape_of), as numbers: family (0 chain, 1 tree, 2 loop), lanes per
+// instance, layout links, lanes per link, links per lane group, instances per full wavefront, LDS bytes, PID slots, LDS bytes of the linearisation
+extern "C" int emu_rollout_shape(const cclqr_mech_desc* md, long long* out9) {
+    static cclqr_mech m;
+    std::string err;
+    int rc = build_mech_tables(md, &m, err);
+    if (rc) return rc;
+    const RolloutShape s = rollout_shape_of(m.host, m.nb, m.nj);
+    const long long v[9] = {(long long)s.family, s.G, s.NBP, s.KL, s.NL, s.full, (long long)s.lds, s.pid_slots, (long long)s.lin_lds};
+    for (int i = 0; i < 9; i++) out9[i] = v[i];
+    return 0;
+}
+extern "C" int emu_spread_instances_per_wavefront(int full, long long n_inst, int steps, int packed, int simds) {
+    return spread_instances_per_wavefront(full, n_inst, steps, packed != 0, simds);
+}

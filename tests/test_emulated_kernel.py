@@ -551,3 +551,44 @@ def test_emulated_loop_linearisation(cclqr, orc, emu):
     assert np.abs(G @ Ap).max() < 1e-8 and np.abs(G @ D).max() < 1e-8
     Apo, Do = loops.projected_linear_model(lm, z, u, cjd)
     assert np.abs(Ap - Apo).max() < 2e-6 * max(1.0, np.abs(Apo).max()) and np.abs(D - Do).max() < 2e-6 * max(1.0, np.abs(Do).max())
+
+
+def test_launch_shape_rules_without_a_gpu(cclqr, orc, emu):
+    """The one launch shape per mechanism (csrc/cclqr_tables.h rollout_shape_of: what the geometry queries report and the launchers launch), tabulated
+    for chains of 1..64 links and for the trees of the GPU suite, against the values the GPU tests state (test_lanes_per_link_of_the_chain_instantiations,
+    test_tree_launch_geometry, test_trees_of_33_to_64_links, the spread tests)."""
+    from test_tree import _random_parents, build
+
+    def shape(t):
+        out = (C.c_longlong * 9)()
+        assert emu.emu_rollout_shape(C.byref(orc.mech_desc(t).desc), out) == 0
+        return dict(zip(("family", "G", "NBP", "KL", "NL", "full", "lds", "pid_slots", "lin_lds"), out))
+
+    chains = {1: cclqr.examples.pendulum()["mech"].tables()}
+    for nb in range(2, 65):
+        chains[nb] = cclqr.examples.cartpole_n(nb - 1)["mech"].tables()
+    for nb, t in chains.items():
+        s = shape(t)
+        assert t.nb == nb and s["family"] == 0 and s["pid_slots"] == nb
+        assert s["G"] == (8 if nb <= 4 else 16 if nb <= 8 else 32 if nb <= 32 else 64) and s["full"] == 64 // s["G"]
+        assert s["NBP"] == (4 if nb <= 4 else 8 if nb <= 8 else 16 if nb <= 16 else 17 if nb == 17 else 32 if nb <= 32 else 64)
+        assert (s["KL"], s["NL"]) == ((3, 2) if nb <= 2 else (1, s["G"]))
+        assert s["KL"] * s["NL"] <= s["G"] and nb <= s["NBP"] and nb <= s["G"] and s["lds"] <= 160 * 1024
+    for n_links, want in ((1, (3, 2)), (3, (1, 8)), (7, (1, 16)), (15, (1, 32)), (16, (1, 32)), (40, (1, 64))):      # test_lanes_per_link_of_the_chain_instantiations
+        s = shape(chains[n_links + 1])
+        assert (s["KL"], s["NL"]) == want
+    assert 4 * shape(chains[17])["lds"] <= 160 * 1024       # the headline mechanism: four workgroups per compute unit
+    s = shape(build(cclqr, "deep")["mech"].tables())        # test_tree_launch_geometry
+    assert s["family"] == 1 and s["G"] == 32 and 4 * s["lds"] <= 160 * 1024
+    assert shape(build(cclqr, "dual_cartpole")["mech"].tables())["G"] == 16
+    for nb, seed in ((33, 1), (41, 2), (48, 3), (57, 4), (64, 5)):      # test_trees_of_33_to_64_links
+        parents = _random_parents(np.random.default_rng(6000 + seed), nb)
+        if not any(parents.count(a) > 1 for a in set(parents) if a >= 0):
+            parents[-1] = parents[-2] if parents[-2] >= 0 else 0
+        s = shape(cclqr.examples.tree_mechanism(parents, seed=seed)["mech"].tables())
+        assert s["family"] == 1 and s["G"] == 64 and s["full"] == 1 and s["lds"] <= 160 * 1024 and s["NBP"] == (48 if nb <= 48 else 64)
+        assert emu.emu_spread_instances_per_wavefront(s["full"], 10 ** 6, 10, 0, 1024) == 1
+    for full in (1, 2, 4, 8):      # the spread tests, on the 1024 SIMDs of an MI355X; short launches spread over a quarter of them
+        spread = lambda n, steps, packed=0: emu.emu_spread_instances_per_wavefront(full, n, steps, packed, 1024)
+        assert spread(37, 120) == 1 and spread(37, 120, 1) == full
+        assert spread(4096, 1000) == min(4, full) and spread(4096, 1) == full

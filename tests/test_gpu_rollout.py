@@ -688,7 +688,7 @@ def test_graph_captured_steps_with_friction_and_philox_noise(cclqr, orc):
 
 @pytest.mark.parametrize("n_links,ninst,steps,extra", [(1, 37, 120, False), (3, 21, 100, True), (7, 9, 80, False), (16, 5, 60, False), (22, 3, 40, False)])
 def test_spread_and_packed_launches_agree_bitwise(cclqr, n_links, ninst, steps, extra):
-    """A batch too small to give every SIMD a wavefront is spread over more wavefronts (rollout_chain.hip::chain_instances_per_wavefront: the lane
+    """A batch too small to give every SIMD a wavefront is spread over more wavefronts (cclqr_internal.h::spread_instances_per_wavefront: the lane
     groups without an instance work on their neighbours' line searches); CCLQR_ROLLOUT_PACK_WAVEFRONTS packs 64 / lanes-per-instance instances
     into every wavefront as a device-filling batch is.  Same arithmetic in the same order: trajectories, final states and Newton counts are
     bitwise equal -- so every small parity test of this suite, which runs spread, also stands for the packed layout of the full-size ones.

@@ -228,7 +228,7 @@ def test_whole_sawyer_robot_lqr_pipeline(cclqr, orc):
 
 @pytest.mark.parametrize("name", ["dual_cartpole", "deep"])
 def test_tree_spread_and_packed_launches_agree_bitwise(cclqr, name):
-    """the tree kernel spreads a small batch over more wavefronts by the chain kernels' rule (rollout_chain.hip::spread_instances_per_wavefront);
+    """the tree kernel spreads a small batch over more wavefronts by the chain kernels' rule (cclqr_internal.h::spread_instances_per_wavefront);
     CCLQR_ROLLOUT_PACK_WAVEFRONTS packs them as a device-filling batch is: bitwise the same trajectories and Newton counts"""
     capi = cclqr._capi
     ex = build(cclqr, name)

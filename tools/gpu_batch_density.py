@@ -1,5 +1,5 @@
 """diagnostic (not a test): instances per wavefront against the batch size -- the chain kernels at batches that leave SIMDs without a wavefront when every
-wavefront is packed full (64 / lanes-per-instance instances): the launch as shipped (spread by rollout_chain.hip::spread_instances_per_wavefront) against
+wavefront is packed full (64 / lanes-per-instance instances): the launch as shipped (spread by cclqr_internal.h::spread_instances_per_wavefront) against
 CCLQR_ROLLOUT_PACK_WAVEFRONTS.  (profiles/r05/batch_density.txt came from an experiment build whose density an environment variable forced: every density per batch size.)
 python tools/gpu_batch_density.py"""
 import json, os, sys
