@@ -190,6 +190,7 @@ extern "C" int cclqr_ctrl_create(const cclqr_mech* m, const cclqr_ctrl_desc* d, 
     c->host.K = c->K_dev; c->host.zd = c->zd_dev; c->host.Fd = c->Fd_dev;
     if (!c->Fd_dev) c->host.Fd_stride = 0;
     if (!c->K_dev) c->host.K_stride = 0;
+    ctrl_hot_build(c->host);      // the record the rollout steps read: after the tables' addresses and strides are final
     if (e == hipSuccess) e = hipMalloc((void**)&c->dev, sizeof(CtrlDev));
     if (e == hipSuccess) e = hipMemcpy(c->dev, &c->host, sizeof(CtrlDev), hipMemcpyHostToDevice);
     if (e != hipSuccess) { cclqr_ctrl_destroy(c); return fail(CCLQR_EHIP, std::string("controller upload: ") + hipGetErrorString(e)); }
@@ -306,6 +307,7 @@ extern "C" int cclqr_ctrl_create_lqr_batch(const cclqr_mech* m, int32_t n_ctrl, 
     if (e == hipSuccess) e = hipMemcpy(kb.data(), dkb, np * sizeof(int), hipMemcpyDeviceToHost);
     if (e == hipSuccess) e = hipMemcpy(st.data(), dst, np * sizeof(int), hipMemcpyDeviceToHost);
     H.K = c->K_dev; H.zd = c->zd_dev; H.Fd = c->Fd_dev;
+    ctrl_hot_build(c->host);      // the record the rollout steps read: after the tables' addresses and strides are final
     if (e == hipSuccess) e = hipMalloc((void**)&c->dev, sizeof(CtrlDev));
     if (e == hipSuccess) e = hipMemcpy(c->dev, &c->host, sizeof(CtrlDev), hipMemcpyHostToDevice);
     if (e != hipSuccess) { cclqr_ctrl_destroy(c); return fail(CCLQR_EHIP, std::string("batched LQR construction: ") + hipGetErrorString(e)); }

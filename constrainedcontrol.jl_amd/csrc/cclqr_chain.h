@@ -966,6 +966,13 @@ HD Lay make_chain_layout(int nb) {
     return L;
 }
 
+// ---- the chain plan of a launch: the forest's chains as ONE 32-bit word per lane of the wavefront.  Lane ci < nchains carries chain ci's first
+// link (bits 0-7) and length (bits 8-15; <= CCLQR_MAXL = 64 links, so <= 64 chains: a lane each), every lane the number of chains (bits 16-23).
+HD int chain_plan_pack(int nchains, int start, int len) { return (nchains << 16) | (len << 8) | start; }
+HD int chain_plan_count(int w) { return (w >> 16) & 0xff; }
+HD int chain_plan_start(int w) { return w & 0xff; }
+HD int chain_plan_len(int w) { return (w >> 8) & 0xff; }
+
 // ---- which instantiation of rollout_chain_kernel a chain of nb links runs on (host side: RolloutShape, cclqr_tables.h rollout_shape_of)
 // 8 lanes per instance up to 4 links (one elimination front of 6 lanes; eight instances per wavefront: the cartpole and triple-cartpole
 // configs), 16 up to 8 links (the two fronts need 14), 32 up to 32 links: with 16 lanes a 9..16-link instance would fill LDS with two

@@ -61,6 +61,21 @@ struct MechDev {
     int inc_n[8], inc_j[8][CCLQR_MAXI], inc_side[8][CCLQR_MAXI];   // joints around body b; side 0: b is the child, 1: the parent
 };
 
+// ---- the launch-invariant record of a controller that a rollout step reads (CtrlDev::hot): ONE contiguous, aligned block, so that a step fetches
+// it with one wide uniform load (a scalar load through the constant address space: cclqr_rollout_step.h) and forms every row address from it
+// without another load.  The tables' bases are kept as integers: the kernels turn them into GLOBAL-address-space pointers, which a pointer read
+// from memory is not known to be (the gain row came through flat loads).
+struct alignas(64) CtrlHot {
+    unsigned long long K, zd, Fd;                 // device addresses of the tables (0: none)
+    long long K_stride, zd_stride, Fd_stride;     // per-instance strides in doubles (0: one table for all)
+    int nK, N, nsp, mu;
+    double noise_scale;
+    unsigned noise_key0, flags;                   // the law's flags: FRIC | PID | NOISE
+    unsigned cj4[CCLQR_MAXL / 4];                 // controlled links, a byte each
+    static const unsigned FRIC = 1u, PID = 2u, NOISE = 4u;
+};
+HD int ctrl_hot_cj(unsigned word, int i) { return (int)((word >> (8 * (i & 3))) & 0xffu); }      // word = cj4[i >> 2]
+
 // ---- controller tables in device memory ----
 struct CtrlDev {
     int mu, nK, N, nsp;       // N <= 0: infinite horizon
@@ -80,7 +95,41 @@ struct CtrlDev {
     // (strides in doubles; all 0 when one table is shared, the reference's case)
     long long K_stride, zd_stride, Fd_stride;
     int n_ctrl;
+    // what a rollout step reads of all this, gathered (ctrl_hot_build, at create time: none of it changes while the handle lives)
+    CtrlHot hot;
 };
+
+// the record of a controller: every field a copy of the CtrlDev field of the same name (the law's switches are bits of `flags`, cj is packed to bytes)
+HD void ctrl_hot_build(CtrlDev& C) {
+    CtrlHot& H = C.hot;
+    H.K = (unsigned long long)(uintptr_t)C.K; H.zd = (unsigned long long)(uintptr_t)C.zd; H.Fd = (unsigned long long)(uintptr_t)C.Fd;
+    H.K_stride = C.K_stride; H.zd_stride = C.zd_stride; H.Fd_stride = C.Fd_stride;
+    H.nK = C.nK; H.N = C.N; H.nsp = C.nsp; H.mu = C.mu;
+    H.flags = (C.has_fric ? CtrlHot::FRIC : 0u) | (C.has_pid ? CtrlHot::PID : 0u) | (C.noise_scale != 0.0 ? CtrlHot::NOISE : 0u);
+    H.noise_scale = C.noise_scale; H.noise_key0 = C.noise_key0;
+    for (int w = 0; w < CCLQR_MAXL / 4; w++) H.cj4[w] = 0;
+    for (int i = 0; i < C.mu && i < CCLQR_MAXL; i++) H.cj4[i >> 2] |= (unsigned)(C.cj[i] & 0xff) << (8 * (i & 3));
+}
+
+// The rows of the tables that step k of the instance with global index gi reads, as offsets in doubles from the tables' bases -- the indexing of
+// lqr.jl:89-139 / lqr_tracking.jl:46-71: the feedback acts while k < N (always, N <= 0), setpoint and feed-forward row min(k, nsp) - 1, gain
+// table min(k, nK) - 1 (the first, N <= 0).  Computed from the record alone: no further load stands between the record and the rows.
+struct CtrlRows {
+    bool gate;
+    long long zd, K, Fd;      // zd: + 13 link; K: + input * ne + entry; Fd: + input
+};
+template <class HotPtr>      // (const CtrlHot*, or the kernels' pointer to it in the constant address space)
+HD CtrlRows ctrl_step_rows(HotPtr H, int k, long long gi, int nz, int ne) {
+    CtrlRows R;
+    const int N = H->N, nsp = H->nsp, nK = H->nK, mu = H->mu;
+    R.gate = (N <= 0) || (k < N);
+    const int ksp = (nsp > 1) ? ((k - 1 < nsp) ? k - 1 : nsp - 1) : 0;
+    const int kidx = (N <= 0) ? 0 : ((k - 1 < nK) ? k - 1 : nK - 1);
+    R.zd = gi * H->zd_stride + (long long)((size_t)ksp * nz);
+    R.K = gi * H->K_stride + (long long)((size_t)kidx * mu * ne);
+    R.Fd = gi * H->Fd_stride + (long long)((size_t)ksp * mu);
+    return R;
+}
 
 // ---- LDS layout of one instance (offsets in doubles) ----
 // NB holds N(w+) D_R^-1 (so that the joint evaluation emits W = G_v D^-1 directly)

@@ -234,7 +234,7 @@ __global__ __launch_bounds__(64) void rollout_chain_kernel(RolloutArgs a) {
     const int tc = KL > 1 ? (w < KL ? tl : -2) : t;         // ... for comparisons with a link number (no match on a lane without a link)
     const int64_t inst = (int64_t)blockIdx.x * a.ipw + grp;
     const MechDev* M = a.M;
-    const CtrlDev* C = a.C;
+    const CtrlDev* CT = a.C;       // the controller's tables; what a step reads of them is the record C below
     const int nb = M->nb;
     const double dt = M->dt;
     const Lay Y = make_chain_layout(NBP);
@@ -246,10 +246,20 @@ __global__ __launch_bounds__(64) void rollout_chain_kernel(RolloutArgs a) {
     if (KL == 1 || w == 0) c.flags |= LinkC::PRIM;
     SubSel Q;
     if (KL > 1) sub_setup<KL>(c, w < KL ? w : 0, Q);
-    if (EXTRA && C->has_fric && c.on()) { c.fric = C->fric[tl]; if (c.fric != 0.0) c.flags |= LinkC::FRIC; }
+    if (EXTRA && CT->has_fric && c.on()) { c.fric = CT->fric[tl]; if (c.fric != 0.0) c.flags |= LinkC::FRIC; }
     c.set_valid(grp < a.ipw && inst < a.n_inst);
     const long long ginst = a.inst0 + inst;     // global instance index: selects the controller table when there is one per instance
     const int ut = c.on() ? M->perm[tl] : 0;      // user body index of the owned link
+    // The chains of the forest, fetched once: lane ci of the wavefront keeps (start, length) of chain ci, every lane the number of chains
+    // (chain_plan_pack, cclqr_chain.h), and the Newton loop reads them with v_readlane instead of going to M->chain_start / M->chain_len (two
+    // dependent memory round trips per iteration).  No scalar register holds any of it, and no new vector register: the word shares the register
+    // of the lane's user body index (bits 24-29), which the launch keeps anyway.
+    int plan;
+    {
+        const int nch = M->nchains;
+        const int cs = M->chain_start[lane], cn = M->chain_len[lane];      // (64 lanes, CCLQR_MAXL = 64 entries: every lane's read is inside the table)
+        plan = chain_plan_pack(nch, lane < nch ? cs : 0, lane < nch ? cn : 0) | (ut << 24);
+    }
 
     LinkS S;
     double pid_int = 0.0, pid_last = 0.0;
@@ -294,30 +304,35 @@ __global__ __launch_bounds__(64) void rollout_chain_kernel(RolloutArgs a) {
         const int k = k0 + kk;
         asm volatile("" : "+s"(ap));
         LINK_FLAGS_FRESH(c);
+        // ---------------- the launch-invariant data of the step comes first: the controller's record (CtrlDev::hot: one scalar load; the rows of this
+        // step's tables follow from it without another load) and gravity.  The setpoint row and the gain rows are read where the feedback law uses
+        // them, and the trajectory row is stored BEHIND the law: the memory counter runs over loads and stores in one order, so a load requested
+        // behind the stores would wait for their acknowledgement too.
+        CtrlHotK C = ctrl_hot_of(CT);
+        asm volatile("" : "+s"(C));
+        const long long gi = c.valid() ? ginst : a.inst0;      // (a lane of an instance that does not exist reads the first instance's tables; its result is never used)
+        const int ne = 12 * nb;
+        const int mu = C->mu;
+        const CtrlRows rows = ctrl_step_rows(C, k, gi, nz, ne);
+        const bool gate = rows.gate;
+        const GlobalD Kp = global_table(C->K) + rows.K + t;      // the lane's first entry of the step's first gain row
+        const GlobalD Fp = C->Fd ? global_table(C->Fd) + rows.Fd : (GlobalD)0;
+        double grav = M->g;
+        unsigned long long zd_base = C->zd;
+        asm volatile("" : "+s"(zd_base));      // (read with the rest of the record, not on its own where the setpoint row is formed)
         double* const traj_out = ap->traj;
         if (traj_out) {     // Storage row of this step, staged through LDS in user body order so that the HBM stores coalesce
             if (c.live() && (KL == 1 || c.prim())) {
+                LANE_INT_FRESH(plan);
+                const int ub = plan >> 24;      // user body index of the owned link
 #pragma unroll
-                for (int i = 0; i < 7; i++) L[Y.Z + 13 * ut + i] = S.z[i];
+                for (int i = 0; i < 7; i++) L[Y.Z + 13 * ub + i] = S.z[i];
 #pragma unroll
-                for (int i = 0; i < 6; i++) L[Y.Z + 13 * ut + 7 + i] = S.s[i];
+                for (int i = 0; i < 6; i++) L[Y.Z + 13 * ub + 7 + i] = S.s[i];
             }
-            __syncthreads();
-            if (c.valid()) {
-                int kr = kk, nzr = nz;
-                asm volatile("" : "+s"(kr), "+s"(nzr));   // keeps the row address a product computed here (not a running pointer + a 64-bit stride kept in registers)
-                double* dst = traj_out + ((size_t)inst * ap->steps + kr) * nzr;
-                int e0 = t;
-                asm volatile("" : "+v"(e0));      // the loop's entry test is made here, not once per launch and kept as a lane mask
-                for (int e = e0; e < nz; e += G) dst[e] = L[Y.Z + e];
-            }
-            __syncthreads();
         }
         STAMP(PF_IO);
         // ---------------- feedback law (lqr.jl:89-139 / lqr_tracking.jl:46-71)
-        const bool gate = (C->N <= 0) || (k < C->N);
-        const int ksp = (C->nsp > 1) ? ((k - 1 < C->nsp) ? k - 1 : C->nsp - 1) : 0;
-        const int kidx = (C->N <= 0) ? 0 : ((k - 1 < C->nK) ? k - 1 : C->nK - 1);
         double uj = 0.0;
         double zf[13], za[13];
 #pragma unroll
@@ -332,78 +347,52 @@ __global__ __launch_bounds__(64) void rollout_chain_kernel(RolloutArgs a) {
         }
         if (gate) {
             if (c.live()) {
-                double dz[12];
-                ck_control_error(zf, C->zd + ginst * C->zd_stride + (size_t)ksp * nz + 13 * tl, dz);
+                double dz[12], zdv[13];
+                const GlobalD zp = global_table(zd_base) + rows.zd + 13 * tl;
+#pragma unroll
+                for (int i = 0; i < 13; i++) zdv[i] = zp[i];
+                ck_control_error(zf, zdv, dz);
                 if (KL == 1 || c.prim()) {
 #pragma unroll
                     for (int i = 0; i < 12; i++) L[Y.DZ + 12 * tl + i] = dz[i];
                 }
-                if (EXTRA && C->has_fric && c.has_fric()) uj = ck_friction(c, zf, za);
+                if (EXTRA && (C->flags & CtrlHot::FRIC) && c.has_fric()) uj = ck_friction(c, zf, za);
             }
-            __syncthreads();
-            {
-                // u_i = Fd_i - K_i . dz for the mu inputs.  The gain entries of a lane -- NE per input, read from HBM / L2 -- are ALL requested
-                // before the first one is used, CH inputs at a time, together with the inputs' feed-forward values and joint numbers: as a loop
-                // "load, multiply-add, next entry" every entry paid its own memory round trip (6 round trips per input and lane; 25 % of a
-                // step of the seven-input Sawyer arm, 2.4 % of the headline's).  Same products, same order of summation.
-                constexpr int NE = (12 * NBP + G - 1) / G;
-                constexpr int CH = (G == 16) ? 8 : 1;       // (16 lanes = 5 .. 8 links: the multi-input arms, all their inputs at once; the others usually have one input)
-                // No predicate lives across the loads (each would be a 64-bit lane mask in scalar registers): an entry past the end of a row is
-                // fetched all the same -- it is the next row's, or the zero padding behind the table (CCLQR_K_PAD) -- and meets a zero in dz;
-                // a lane of an instance that does not exist reads the first instance's tables, and its result is never used.
-                const long long gi = c.valid() ? ginst : a.inst0;
-                const int ne = 12 * nb;
-                double unoise = 0.0;                    // noise: injected by the caller, or generated for this launch by philox_fill_kernel
-                if (EXTRA == 3) {
-                    if (C->noise_scale != 0.0) unoise = C->noise_scale * philox_normal_dev(C->noise_key0, (unsigned long long)gi, k);
-                } else if (EXTRA) {
-                    const double* noise = ap->noise;
-                    if (C->noise_scale != 0.0 && c.valid() && noise) unoise = C->noise_scale * noise[(size_t)inst * ap->noise_stride + (k - 1)];
-                }
-                double dzv[NE];
-                int tf = t;
-                asm volatile("" : "+v"(tf));            // the entries' range tests are made here, every step -- not once per launch and kept as NE lane masks
-#pragma unroll
-                for (int q = 0; q < NE; q++) { const int e = tf + q * G; dzv[q] = (c.valid() && e < ne) ? L[Y.DZ + e] : 0.0; }
-                const int mu = C->mu;
-                const double* Fp = C->Fd ? C->Fd + gi * C->Fd_stride + (size_t)ksp * mu : nullptr;
-                if (C->K) {                                  // (uniform) LQR / TrackingLQR
-                    const double* Kp = C->K + gi * C->K_stride + (size_t)kidx * mu * ne + t;      // the lane's first entry of the step's first row
-                    for (int i0 = 0; i0 < mu; i0 += CH) {
-                        double kv[CH][NE], fd[CH];
-                        int cjv[CH];
-#pragma unroll
-                        for (int j = 0; j < CH; j++) {
-                            const bool ok = i0 + j < mu;         // (uniform)
-                            const int ij = ok ? i0 + j : i0;
-#pragma unroll
-                            for (int q = 0; q < NE; q++) kv[j][q] = Kp[(size_t)ij * ne + q * G];
-                            fd[j] = Fp ? Fp[ij] : 0.0;
-                            cjv[j] = ok ? C->cj[ij] : -1;
-                        }
-#pragma unroll
-                        for (int j = 0; j < CH; j++) {
-                            double part = 0.0;
-#pragma unroll
-                            for (int q = 0; q < NE; q++) part += kv[j][q] * dzv[q];
-                            const double s = group_sum<G>(part);
-                            double u = fd[j] - s;
-                            if (EXTRA) u += unoise;
-                            if (tc == cjv[j]) uj += u;
-                        }
-                    }
-                } else {                                     // feed-forward only (OpenLoop, a host closure's inputs)
-                    for (int i = 0; i < mu; i++) {
-                        double u = Fp ? Fp[i] : 0.0;
-                        if (EXTRA) u += unoise;
-                        if (tc == C->cj[i]) uj += u;
-                    }
-                }
-            }
-            __syncthreads();
         }
-        if (EXTRA == 2 && C->has_pid) {
-            if (c.live() && C->pid_on[tl]) uj += ck_pid(c, zf, za, C->pid_P[tl], C->pid_I[tl], C->pid_D[tl], C->pid_goal[tl], dt, k == 1, pid_int, pid_last);
+        // ONE barrier for the staged row and the control error: they lie side by side in the image (Y.Z, Y.DZ), which nothing writes again before the
+        // barrier in front of the Newton solve -- the forces phase writes GKA / D / C only
+        __syncthreads();
+        if (gate) {     // u_i = Fd_i - K_i . dz for the mu inputs (feedback_inputs, cclqr_rollout_step.h)
+            constexpr int NE = GainRows<G, NBP>::NE;
+            double unoise = 0.0;                    // noise: injected by the caller, or generated for this launch by philox_fill_kernel
+            if (EXTRA == 3) {
+                if (C->flags & CtrlHot::NOISE) unoise = C->noise_scale * philox_normal_dev(C->noise_key0, (unsigned long long)gi, k);
+            } else if (EXTRA) {
+                const double* noise = ap->noise;
+                if ((C->flags & CtrlHot::NOISE) && c.valid() && noise) unoise = C->noise_scale * noise[(size_t)inst * ap->noise_stride + (k - 1)];
+            }
+            double dzv[NE];
+            int tf = t;
+            asm volatile("" : "+v"(tf));            // the entries' range tests are made here, every step -- not once per launch and kept as NE lane masks
+#pragma unroll
+            for (int q = 0; q < NE; q++) { const int e = tf + q * G; dzv[q] = (c.valid() && e < ne) ? L[Y.DZ + e] : 0.0; }
+            feedback_inputs<G, NBP, EXTRA>(C, Kp, Fp, mu, ne, dzv, unoise, tc, uj);
+        }
+        STAMP(PF_CONTROL);
+        asm volatile("" : "+v"(grav));      // the last of the step's loads is waited for HERE, in front of the stores (behind them the wait would be for the stores too)
+        if (traj_out) {     // the row leaves behind everything the step had to read: no load waits for the acknowledgement of these stores
+            if (c.valid()) {
+                int kr = kk, nzr = nz;
+                asm volatile("" : "+s"(kr), "+s"(nzr));   // keeps the row address a product computed here (not a running pointer + a 64-bit stride kept in registers)
+                double* dst = traj_out + ((size_t)inst * ap->steps + kr) * nzr;
+                int e0 = t;
+                asm volatile("" : "+v"(e0));      // the loop's entry test is made here, not once per launch and kept as a lane mask
+                for (int e = e0; e < nz; e += G) dst[e] = L[Y.Z + e];
+            }
+        }
+        STAMP(PF_IO);
+        if (EXTRA == 2 && (C->flags & CtrlHot::PID)) {
+            if (c.live() && CT->pid_on[tl]) uj += ck_pid(c, zf, za, CT->pid_P[tl], CT->pid_I[tl], CT->pid_D[tl], CT->pid_goal[tl], dt, k == 1, pid_int, pid_last);
         }
         STAMP(PF_CONTROL);
         LINK_FLAGS_FRESH(c);
@@ -417,7 +406,7 @@ __global__ __launch_bounds__(64) void rollout_chain_kernel(RolloutArgs a) {
                 for (int i = 0; i < 3; i++) { F[i] += cW6[i]; tau[i] += cW6[3 + i]; }
             }
             double cTR[6];
-            ck_step_invariants(c, zf, F, tau, dt, M->g, cTR, cTR + 3);
+            ck_step_invariants(c, zf, F, tau, dt, grav, cTR, cTR + 3);
             double gk[5], kXT[3][3], kPB[5][3], kPA[5][3], lam[5];
             joint_eval_sparse<true>(c, za, za + 3, zf, zf + 3, nullptr, nullptr, gk, kXT, kPB, kPA);
 #pragma unroll
@@ -447,14 +436,16 @@ __global__ __launch_bounds__(64) void rollout_chain_kernel(RolloutArgs a) {
         int its = 0;
         double normf0 = chain_eval<G, true, KL>(c, S, tl, Y, L, 0.0, c.live() && !done, dt, Q PROF_PASS);
         __syncthreads();
-        const int nchains = M->nchains;
+        LANE_INT_FRESH(plan);      // (read here, every step: not once per launch and kept in a scalar register)
+        const int nchains = chain_plan_count(__builtin_amdgcn_readfirstlane(plan));
         for (int iter = 1; iter <= NEWTON_MAXIT; iter++) {
             if (!__any(!done)) break;
             PCOUNT(PF_NEWTON_ITERS);
             const bool active = c.live() && !done;
             // block-tridiagonal solve along each chain, swept from both ends (cclqr_chain.h)
             for (int ci = 0; ci < nchains; ci++) {
-                const int cs = M->chain_start[ci], cn = M->chain_len[ci];
+                const int pw = __builtin_amdgcn_readlane(plan, ci);
+                const int cs = chain_plan_start(pw), cn = chain_plan_len(pw);
                 // long chains: every second link is eliminated first, all at once (cr_level, cclqr_chain.h), and the two-front sweep
                 // runs over the half that is left
                 constexpr int CRW = 4;
@@ -681,10 +672,11 @@ __global__ __launch_bounds__(64) void rollout_chain_kernel(RolloutArgs a) {
     // ---------------- final state, multipliers, status
     __syncthreads();
     if (c.live() && (KL == 1 || c.prim())) {
+        const int ub = plan >> 24;
 #pragma unroll
-        for (int i = 0; i < 7; i++) L[Y.Z + 13 * ut + i] = S.z[i];
+        for (int i = 0; i < 7; i++) L[Y.Z + 13 * ub + i] = S.z[i];
 #pragma unroll
-        for (int i = 0; i < 6; i++) L[Y.Z + 13 * ut + 7 + i] = S.s[i];
+        for (int i = 0; i < 6; i++) L[Y.Z + 13 * ub + 7 + i] = S.s[i];
     }
     __syncthreads();
     asm volatile("" : "+s"(ap));

@@ -147,7 +147,7 @@ __global__ __launch_bounds__(64) void rollout_treereg_kernel(RolloutArgs a) {
     const int64_t inst = (int64_t)blockIdx.x * a.ipw + grp;      // (a.ipw instances per wavefront: cclqr_internal.h)
     const MechDev* M = a.M;
     const TreeRegDev* R = treereg_of(M);
-    const CtrlDev* C = a.C;
+    const CtrlDev* CT = a.C;       // the controller's tables; what a step reads of them is the record C below
     const int nb = M->nb;
     const double dt = M->dt;
     const int nss = R->nss;
@@ -164,7 +164,7 @@ __global__ __launch_bounds__(64) void rollout_treereg_kernel(RolloutArgs a) {
     tree_load(T, M, R, t, nb);
     const int pa4 = gb4 + 4 * T.par;
     if (T.nchild > 0) c.flags |= 4;          // "has a child link" (link_load_consts reads the chains' single-child table)
-    if (EXTRA && C->has_fric && c.on()) { c.fric = C->fric[t]; if (c.fric != 0.0) c.flags |= LinkC::FRIC; }
+    if (EXTRA && CT->has_fric && c.on()) { c.fric = CT->fric[t]; if (c.fric != 0.0) c.flags |= LinkC::FRIC; }
     c.set_valid(grp < a.ipw && inst < a.n_inst);
     const long long ginst = a.inst0 + inst;
     const int ut = c.on() ? M->perm[t] : 0;
@@ -205,6 +205,22 @@ __global__ __launch_bounds__(64) void rollout_treereg_kernel(RolloutArgs a) {
         const int k = k0 + kk;
         asm volatile("" : "+s"(ap));
         LINK_FLAGS_FRESH(c);
+        // ---------------- the launch-invariant data of the step comes first: the controller's record (CtrlDev::hot: one scalar load; the rows of this
+        // step's tables follow from it without another load) and gravity.  The setpoint row and the gain rows are read where the feedback law uses
+        // them, and the trajectory row is stored BEHIND the law: the memory counter runs over loads and stores in one order, so a load requested
+        // behind the stores would wait for their acknowledgement too.
+        CtrlHotK C = ctrl_hot_of(CT);
+        asm volatile("" : "+s"(C));
+        const long long gi = c.valid() ? ginst : a.inst0;      // (a lane of an instance that does not exist reads the first instance's tables; its result is never used)
+        const int ne = 12 * nb;
+        const int mu = C->mu;
+        const CtrlRows rows = ctrl_step_rows(C, k, gi, nz, ne);
+        const bool gate = rows.gate;
+        const GlobalD Kp = global_table(C->K) + rows.K + t;      // the lane's first entry of the step's first gain row
+        const GlobalD Fp = C->Fd ? global_table(C->Fd) + rows.Fd : (GlobalD)0;
+        double grav = M->g;
+        unsigned long long zd_base = C->zd;
+        asm volatile("" : "+s"(zd_base));      // (read with the rest of the record, not on its own where the setpoint row is formed)
         double* const traj_out = ap->traj;
         if (traj_out) {     // Storage row of this step, staged through LDS in user body order so that the HBM stores coalesce
             if (c.live()) {
@@ -213,22 +229,9 @@ __global__ __launch_bounds__(64) void rollout_treereg_kernel(RolloutArgs a) {
 #pragma unroll
                 for (int i = 0; i < 6; i++) L[Y.Z + 13 * ut + 7 + i] = S.s[i];
             }
-            __syncthreads();
-            if (c.valid()) {
-                int kr = kk, nzr = nz;
-                asm volatile("" : "+s"(kr), "+s"(nzr));
-                double* dst = traj_out + ((size_t)inst * ap->steps + kr) * nzr;
-                int e0 = t;
-                asm volatile("" : "+v"(e0));
-                for (int e = e0; e < nz; e += G) dst[e] = L[Y.Z + e];
-            }
-            __syncthreads();
         }
         STAMP(PF_IO);
         // ---------------- feedback law (lqr.jl:89-139 / lqr_tracking.jl:46-71)
-        const bool gate = (C->N <= 0) || (k < C->N);
-        const int ksp = (C->nsp > 1) ? ((k - 1 < C->nsp) ? k - 1 : C->nsp - 1) : 0;
-        const int kidx = (C->N <= 0) ? 0 : ((k - 1 < C->nK) ? k - 1 : C->nK - 1);
         double uj = 0.0;
         double zf[13], za[13];
 #pragma unroll
@@ -243,70 +246,48 @@ __global__ __launch_bounds__(64) void rollout_treereg_kernel(RolloutArgs a) {
         }
         if (gate) {
             if (c.live()) {
-                double dz[12];
-                ck_control_error(zf, C->zd + ginst * C->zd_stride + (size_t)ksp * nz + 13 * t, dz);
+                double dz[12], zdv[13];
+                const GlobalD zp = global_table(zd_base) + rows.zd + 13 * t;
+#pragma unroll
+                for (int i = 0; i < 13; i++) zdv[i] = zp[i];
+                ck_control_error(zf, zdv, dz);
 #pragma unroll
                 for (int i = 0; i < 12; i++) L[Y.DZ + 12 * t + i] = dz[i];
-                if (EXTRA && C->has_fric && c.has_fric()) uj = ck_friction(c, zf, za);
+                if (EXTRA && (C->flags & CtrlHot::FRIC) && c.has_fric()) uj = ck_friction(c, zf, za);
             }
-            __syncthreads();
-            {
-                // u_i = Fd_i - K_i . dz: the gain entries of a lane are all requested before the first is used, CH inputs at a time (the whole
-                // arm's on the 16-lane kernels), entries past a row's end meet a zero in dz (the tables are padded: CCLQR_K_PAD) -- the control
-                // phase of rollout_chain.hip, where the measurement and the reasons are
-                constexpr int NE = (12 * NBP + G - 1) / G;
-                constexpr int CH = (G == 16) ? 8 : 1;
-                const long long gi = c.valid() ? ginst : a.inst0;
-                const int ne = 12 * nb;
-                double unoise = 0.0;
-                if (EXTRA) {
-                    const double* noise = ap->noise;
-                    if (C->noise_scale != 0.0 && c.valid() && noise) unoise = C->noise_scale * noise[(size_t)inst * ap->noise_stride + (k - 1)];
-                }
-                double dzv[NE];
-                int tf = t;
-                asm volatile("" : "+v"(tf));            // the entries' range tests are made here, every step -- not once per launch and kept as NE lane masks
-#pragma unroll
-                for (int q = 0; q < NE; q++) { const int e = tf + q * G; dzv[q] = (c.valid() && e < ne) ? L[Y.DZ + e] : 0.0; }
-                const int mu = C->mu;
-                const double* Fp = C->Fd ? C->Fd + gi * C->Fd_stride + (size_t)ksp * mu : nullptr;
-                if (C->K) {                                  // (uniform) LQR / TrackingLQR
-                    const double* Kp = C->K + gi * C->K_stride + (size_t)kidx * mu * ne + t;
-                    for (int i0 = 0; i0 < mu; i0 += CH) {
-                        double kv[CH][NE], fd[CH];
-                        int cjv[CH];
-#pragma unroll
-                        for (int j = 0; j < CH; j++) {
-                            const bool ok = i0 + j < mu;         // (uniform)
-                            const int ij = ok ? i0 + j : i0;
-#pragma unroll
-                            for (int q = 0; q < NE; q++) kv[j][q] = Kp[(size_t)ij * ne + q * G];
-                            fd[j] = Fp ? Fp[ij] : 0.0;
-                            cjv[j] = ok ? C->cj[ij] : -1;
-                        }
-#pragma unroll
-                        for (int j = 0; j < CH; j++) {
-                            double part = 0.0;
-#pragma unroll
-                            for (int q = 0; q < NE; q++) part += kv[j][q] * dzv[q];
-                            const double s = group_sum<G>(part);
-                            double u = fd[j] - s;
-                            if (EXTRA) u += unoise;
-                            if (t == cjv[j]) uj += u;
-                        }
-                    }
-                } else {                                     // feed-forward only (OpenLoop, a host closure's inputs)
-                    for (int i = 0; i < mu; i++) {
-                        double u = Fp ? Fp[i] : 0.0;
-                        if (EXTRA) u += unoise;
-                        if (t == C->cj[i]) uj += u;
-                    }
-                }
-            }
-            __syncthreads();
         }
-        if (EXTRA >= 2 && C->has_pid) {
-            if (c.live() && C->pid_on[t]) uj += ck_pid(c, zf, za, C->pid_P[t], C->pid_I[t], C->pid_D[t], C->pid_goal[t], dt, k == 1, pid_int, pid_last);
+        // ONE barrier for the staged row and the control error: they lie side by side in the image (Y.Z, Y.DZ), which nothing writes again before the
+        // barrier in front of the Newton solve -- the forces phase writes GKA / D / C only
+        __syncthreads();
+        if (gate) {     // u_i = Fd_i - K_i . dz for the mu inputs (feedback_inputs, cclqr_rollout_step.h)
+            constexpr int NE = GainRows<G, NBP>::NE;
+            double unoise = 0.0;                    // noise: injected by the caller, or generated for this launch by philox_fill_kernel (rollout_chain.hip)
+            if (EXTRA) {
+                const double* noise = ap->noise;
+                if ((C->flags & CtrlHot::NOISE) && c.valid() && noise) unoise = C->noise_scale * noise[(size_t)inst * ap->noise_stride + (k - 1)];
+            }
+            double dzv[NE];
+            int tf = t;
+            asm volatile("" : "+v"(tf));            // the entries' range tests are made here, every step -- not once per launch and kept as NE lane masks
+#pragma unroll
+            for (int q = 0; q < NE; q++) { const int e = tf + q * G; dzv[q] = (c.valid() && e < ne) ? L[Y.DZ + e] : 0.0; }
+            feedback_inputs<G, NBP, EXTRA>(C, Kp, Fp, mu, ne, dzv, unoise, t, uj);
+        }
+        STAMP(PF_CONTROL);
+        asm volatile("" : "+v"(grav));      // the last of the step's loads is waited for HERE, in front of the stores (behind them the wait would be for the stores too)
+        if (traj_out) {     // the row leaves behind everything the step had to read: no load waits for the acknowledgement of these stores
+            if (c.valid()) {
+                int kr = kk, nzr = nz;
+                asm volatile("" : "+s"(kr), "+s"(nzr));   // keeps the row address a product computed here (not a running pointer + a 64-bit stride kept in registers)
+                double* dst = traj_out + ((size_t)inst * ap->steps + kr) * nzr;
+                int e0 = t;
+                asm volatile("" : "+v"(e0));      // the loop's entry test is made here, not once per launch and kept as a lane mask
+                for (int e = e0; e < nz; e += G) dst[e] = L[Y.Z + e];
+            }
+        }
+        STAMP(PF_IO);
+        if (EXTRA >= 2 && (C->flags & CtrlHot::PID)) {
+            if (c.live() && CT->pid_on[t]) uj += ck_pid(c, zf, za, CT->pid_P[t], CT->pid_I[t], CT->pid_D[t], CT->pid_goal[t], dt, k == 1, pid_int, pid_last);
         }
         STAMP(PF_CONTROL);
         LINK_FLAGS_FRESH(c);
@@ -318,7 +299,7 @@ __global__ __launch_bounds__(64) void rollout_treereg_kernel(RolloutArgs a) {
 #pragma unroll
             for (int i = 0; i < 3; i++) { F[i] += cW6[i]; tau[i] += cW6[3 + i]; }
             double cTR[6];
-            ck_step_invariants(c, zf, F, tau, dt, M->g, cTR, cTR + 3);
+            ck_step_invariants(c, zf, F, tau, dt, grav, cTR, cTR + 3);
             double gk[5], kXT[3][3], kPB[5][3], kPA[5][3], lam[5];
             joint_eval_sparse<true>(c, za, za + 3, zf, zf + 3, nullptr, nullptr, gk, kXT, kPB, kPA);
 #pragma unroll
