@@ -16,8 +16,9 @@ _ERRNAME = {EINVAL: "CCLQR_EINVAL", ESINGULAR: "CCLQR_ESINGULAR", ENOCONV: "CCLQ
 EXPORTS = ["cclqr_last_error", "cclqr_version", "cclqr_device_count", "cclqr_set_device", "cclqr_mech_create", "cclqr_mech_destroy",
            "cclqr_ctrl_create", "cclqr_ctrl_create_lqr_batch", "cclqr_ctrl_destroy", "cclqr_linearize", "cclqr_linearize_projected", "cclqr_riccati", "cclqr_riccati_tv", "cclqr_riccati_tracking", "cclqr_rollout",
            "cclqr_rollout_dev", "cclqr_rollout_ex", "cclqr_rollout_host_ex", "cclqr_ctrl_reserve_noise", "cclqr_riccati_ex", "cclqr_riccati_tracking_ex",
-           "cclqr_release_workspaces", "cclqr_rollout_geometry", "cclqr_rollout_layout_links", "cclqr_ctrl_set_feedforward", "cclqr_abi_layout", "cclqr_rollout_lanes_per_link", "cclqr_rollout_instances_per_wavefront"]
-ABI_VERSION = 201     # include/cclqr.h CCLQR_ABI_VERSION: the structs below mirror that header (verified field by field against cclqr_abi_layout at load time)
+           "cclqr_release_workspaces", "cclqr_rollout_geometry", "cclqr_rollout_layout_links", "cclqr_ctrl_set_feedforward", "cclqr_abi_layout", "cclqr_rollout_lanes_per_link", "cclqr_rollout_instances_per_wavefront",
+           "cclqr_plants_create", "cclqr_plants_destroy", "cclqr_rollout_plants"]
+ABI_VERSION = 202     # include/cclqr.h CCLQR_ABI_VERSION: the structs below mirror that header (verified field by field against cclqr_abi_layout at load time)
 ROLLOUT_NO_ALLOC = 1  # cclqr_rollout_opts.flags: the call may neither allocate nor synchronise (a hipGraph capture is open on the device)
 ROLLOUT_CARRY_STATUS = 4  # ... `status` is read and written: an instance lost in an earlier launch stays frozen, the others merge this launch's result into it
 ROLLOUT_PACK_WAVEFRONTS = 2  # ... every wavefront of a chain launch full, whatever the batch size (many launches sharing the device at once)
@@ -274,11 +275,71 @@ class BatchLqrHandle:
             pass
 
 
-def rollout(mech, ctrl, z0, steps, k0=1, noise=None, record=False, first_instance=0, newton_mode=0, newton_eps_alone=0.0, flags=0):
-    """host-pointer rollout: returns (zT, traj or None, status)"""
+class PlantsHandle:
+    """cclqr_plants*: device-resident per-instance plants of a tree mechanism.  mass [n][nb], inertia [n][nb][9], p1 / p2 [n][ne][3] in the mechanism's
+    body / joint order, None = the mechanism's own value; host arrays, or (on_device=True) raw device addresses read on `stream`; n_plant must be given
+    with device addresses.  first_index: global instance index of row 0."""
+
+    def __init__(self, mech, mass=None, inertia=None, p1=None, p2=None, first_index=0, n_plant=None, on_device=False, stream=0):
+        nb, ne = mech.tables.nb, mech.tables.ne
+        self.mech = mech      # (the handle must not outlive the mechanism's)
+        if on_device:
+            args = [C.c_void_p(int(a)) if a else None for a in (mass, inertia, p1, p2)]
+        else:
+            arrs = [None if a is None else f64(a).reshape((-1,) + sh) for a, sh in ((mass, (nb,)), (inertia, (nb, 9)), (p1, (ne, 3)), (p2, (ne, 3)))]
+            sizes = {a.shape[0] for a in arrs if a is not None}
+            if len(sizes) > 1:
+                raise ValueError("the plant arrays have different leading sizes: %s" % sorted(sizes))
+            if n_plant is None:
+                n_plant = sizes.pop() if sizes else 0
+            elif sizes and sizes.pop() != n_plant:
+                raise ValueError("the plant arrays do not have n_plant rows")
+            self._arrs = arrs
+            args = [_d(a) for a in arrs]
+        self.n_plant, self.first_index = int(n_plant or 0), int(first_index)
+        self.ptr = C.c_void_p()
+        check(lib().cclqr_plants_create(mech.ptr, C.c_int64(self.n_plant), C.c_int64(self.first_index), args[0], args[1], args[2], args[3],
+                                        C.c_int32(1 if on_device else 0), C.c_void_p(int(stream)) if stream else None, C.byref(self.ptr)))
+
+    def close(self):
+        if self.ptr:
+            lib().cclqr_plants_destroy(self.ptr)
+            self.ptr = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _rollout_plants(mech, ctrl, plants, z0, steps, k0, noise, record, first_instance, newton_mode, newton_eps_alone, flags):
+    """rollout(..., plants=): cclqr_rollout_plants takes device pointers, so the batch is staged in torch tensors on the current device"""
+    import torch
+    n, nb = z0.shape[0], mech.tables.nb
+    td = torch.device("cuda", torch.cuda.current_device())
+    dz0 = torch.from_numpy(z0).to(td)
+    dzT = torch.empty_like(dz0)
+    dst = torch.zeros(n, dtype=torch.int32, device=td)
+    dtraj = torch.empty((n, steps, nb, 13), dtype=torch.float64, device=td) if record else None
+    dnoise = None if noise is None else torch.from_numpy(noise).to(td)
+    stream = torch.cuda.current_stream().cuda_stream
+    # noise is indexed by the absolute step k-1: the base is shifted so that k0 maps to column 0 of the caller's array
+    rollout_dev(mech, ctrl, n, steps, k0, dz0.data_ptr(), 0, 0 if dnoise is None else dnoise.data_ptr() - 8 * (k0 - 1), steps, 0 if dtraj is None else dtraj.data_ptr(),
+                dzT.data_ptr(), dst.data_ptr(), stream, first_instance=first_instance, newton_mode=newton_mode, newton_eps_alone=newton_eps_alone, flags=flags,
+                plants=plants)
+    torch.cuda.current_stream().synchronize()
+    return dzT.cpu().numpy(), (dtraj.cpu().numpy() if record else None), dst.cpu().numpy()
+
+
+def rollout(mech, ctrl, z0, steps, k0=1, noise=None, record=False, first_instance=0, newton_mode=0, newton_eps_alone=0.0, flags=0, plants=None):
+    """host-pointer rollout: returns (zT, traj or None, status).  plants: a PlantsHandle -- instance i runs plant first_instance + i - plants.first_index"""
     nb = mech.tables.nb
     z0 = f64(z0).reshape(-1, nb, 13)
     n = z0.shape[0]
+    if plants is not None:
+        return _rollout_plants(mech, ctrl, plants, z0, steps, k0, None if noise is None else f64(noise).reshape(n, steps), record, first_instance,
+                               newton_mode, newton_eps_alone, flags)
     traj = np.zeros((n, steps, nb, 13)) if record else None
     zT = np.zeros_like(z0)
     status = np.zeros(n, dtype=np.int32)
@@ -290,18 +351,22 @@ def rollout(mech, ctrl, z0, steps, k0=1, noise=None, record=False, first_instanc
 
 
 def rollout_dev(mech, ctrl, n_inst, steps, k0, z0_ptr, lam_ptr, noise_ptr, noise_stride, traj_ptr, zT_ptr, status_ptr, stream=0,
-                first_instance=None, pid_state=None, noise_ws=None, noise_ws_len=0, newton_mode=0, newton_eps_alone=0.0, flags=0):
+                first_instance=None, pid_state=None, noise_ws=None, noise_ws_len=0, newton_mode=0, newton_eps_alone=0.0, flags=0, plants=None):
     """device-pointer rollout (integers are raw device addresses, e.g. torch.Tensor.data_ptr()); asynchronous.
     Options (cclqr_rollout_opts): first_instance, pid_state = device address of [n_inst][joints][2] doubles, noise_ws / noise_ws_len = caller's
     Philox workspace, newton_mode, flags (ROLLOUT_NO_ALLOC: what a caller with a hipGraph capture open passes; ROLLOUT_PACK_WAVEFRONTS); none given: cclqr_rollout_dev
-    (= NULL options)"""
+    (= NULL options).  plants: a PlantsHandle (cclqr_rollout_plants) -- instance i runs plant first_instance + i - plants.first_index"""
     vp = lambda p: C.c_void_p(int(p)) if p else None
-    if first_instance is None and pid_state is None and noise_ws is None and not newton_mode and not flags:
+    if plants is None and first_instance is None and pid_state is None and noise_ws is None and not newton_mode and not flags:
         check(lib().cclqr_rollout_dev(mech.ptr, ctrl.ptr, C.c_int64(n_inst), C.c_int32(steps), C.c_int32(k0), vp(z0_ptr), vp(lam_ptr),
                                       vp(noise_ptr), C.c_int64(noise_stride), vp(traj_ptr), vp(zT_ptr), vp(status_ptr), vp(stream)))
         return
     o = RolloutOpts(int(first_instance or 0), int(pid_state) if pid_state else None, n_inst * mech.tables.ne * 2 if pid_state else 0,       # one pair per joint (a tree has nb joints, a loop mechanism more)
                     int(noise_ws) if noise_ws else None, int(noise_ws_len) if noise_ws else 0, int(newton_mode), int(flags), float(newton_eps_alone))
+    if plants is not None:
+        check(lib().cclqr_rollout_plants(mech.ptr, plants.ptr, ctrl.ptr, C.c_int64(n_inst), C.c_int32(steps), C.c_int32(k0), vp(z0_ptr), vp(lam_ptr),
+                                         vp(noise_ptr), C.c_int64(noise_stride), vp(traj_ptr), vp(zT_ptr), vp(status_ptr), C.byref(o), vp(stream)))
+        return
     check(lib().cclqr_rollout_ex(mech.ptr, ctrl.ptr, C.c_int64(n_inst), C.c_int32(steps), C.c_int32(k0), vp(z0_ptr), vp(lam_ptr),
                                  vp(noise_ptr), C.c_int64(noise_stride), vp(traj_ptr), vp(zT_ptr), vp(status_ptr), C.byref(o), vp(stream)))
 

@@ -424,11 +424,19 @@ static int rollout_resolve_noise(const cclqr_mech* m, const cclqr_ctrl* c, int64
     return CCLQR_OK;
 }
 
-extern "C" int cclqr_rollout_ex(const cclqr_mech* m, const cclqr_ctrl* c, int64_t n_inst, int32_t steps, int32_t k0, const double* z0,
-                                double* lam, const double* noise, int64_t noise_stride, double* traj, double* zT, int32_t* status,
-                                const cclqr_rollout_opts* opts, void* stream) {
+extern "C" int cclqr_rollout_plants(const cclqr_mech* m, const cclqr_plants* plants, const cclqr_ctrl* c, int64_t n_inst, int32_t steps, int32_t k0,
+                                    const double* z0, double* lam, const double* noise, int64_t noise_stride, double* traj, double* zT, int32_t* status,
+                                    const cclqr_rollout_opts* opts, void* stream) {
     if (m && c && n_inst == 0) return CCLQR_OK;   // empty batch
     { int rc = rollout_check_args(m, c, n_inst, steps, k0, z0, zT, status, opts); if (rc != CCLQR_OK) return rc; }
+    const int64_t first_instance = opts ? opts->first_instance : 0;
+    if (plants) {      // every instance of the launch must find its plant: refused before anything is launched (the Philox fill included)
+        if (plants->mech != m) return fail(CCLQR_EINVAL, "the plants were created for another mechanism");
+        const int64_t lo = first_instance - plants->first_index;
+        if (lo < 0 || lo + n_inst > plants->n_plant)
+            return fail(CCLQR_EINVAL, "instances " + std::to_string(first_instance) + " .. " + std::to_string(first_instance + n_inst - 1) + " of the launch are not all among the plants " +
+                                      std::to_string(plants->first_index) + " .. " + std::to_string(plants->first_index + plants->n_plant - 1));
+    }
     bool philox_in_kernel = false;
     { int rc = rollout_resolve_noise(m, c, n_inst, steps, k0, opts, stream, &noise, &noise_stride, &philox_in_kernel); if (rc != CCLQR_OK) return rc; }
     const CtrlDev& H = c->host;
@@ -442,6 +450,8 @@ extern "C" int cclqr_rollout_ex(const cclqr_mech* m, const cclqr_ctrl* c, int64_
     a.carry = (opts && (opts->flags & CCLQR_ROLLOUT_CARRY_STATUS)) ? 1 : 0;
     const int newton_mode = opts ? opts->newton_mode : 0;
     a.eps_alone = (opts && opts->newton_eps_alone > 0.0) ? opts->newton_eps_alone : 1e-10;
+    a.plants = plants ? plants->dev : nullptr;
+    a.plant_off = plants ? first_instance - plants->first_index : 0;
     if (newton_mode != 0 && newton_mode != 1) return fail(CCLQR_EINVAL, "newton_mode must be 0 (exact rule) or 1 (residual-only stop)");
     if (m->shape.family == RolloutFamily::Loop) {      // one kernel, every law at run time (LQR / TrackingLQR, friction, noise, PID); newton_mode 1 under any of them
         HIPCHK(launch_rollout_loop(a, m->shape, newton_mode, (hipStream_t)stream));
@@ -451,6 +461,63 @@ extern "C" int cclqr_rollout_ex(const cclqr_mech* m, const cclqr_ctrl* c, int64_
         return fail(CCLQR_EUNSUPPORTED, "newton_mode 1 exists under the plain LQR / TrackingLQR law only on chains and branching trees (closed-loop mechanisms: every law)");
     if (m->shape.family == RolloutFamily::Tree) HIPCHK(launch_rollout_treereg(a, m->shape, m->simds, law, newton_mode, (hipStream_t)stream));
     else HIPCHK(launch_rollout_chain(a, m->shape, m->simds, law, newton_mode, (hipStream_t)stream));
+    return CCLQR_OK;
+}
+
+extern "C" int cclqr_rollout_ex(const cclqr_mech* m, const cclqr_ctrl* c, int64_t n_inst, int32_t steps, int32_t k0, const double* z0,
+                                double* lam, const double* noise, int64_t noise_stride, double* traj, double* zT, int32_t* status,
+                                const cclqr_rollout_opts* opts, void* stream) {
+    return cclqr_rollout_plants(m, nullptr, c, n_inst, steps, k0, z0, lam, noise, noise_stride, traj, zT, status, opts, stream);
+}
+
+// Per-instance plants: upload (host pointers) or read in place (device pointers) the caller-order arrays, pack and validate them on the device
+// (plants.hip), read the first-error word back once.
+extern "C" int cclqr_plants_create(const cclqr_mech* m, int64_t n_plant, int64_t first_index, const double* mass, const double* inertia, const double* p1,
+                                   const double* p2, int32_t on_device, void* stream, cclqr_plants** out) {
+    if (!m || !out) return fail(CCLQR_EINVAL, "null argument");
+    if (n_plant < 1 || first_index < 0) return fail(CCLQR_EINVAL, "need n_plant >= 1 and first_index >= 0");
+    if (n_plant * (int64_t)(m ? m->nb : 1) >= (int64_t)1 << 31) return fail(CCLQR_EUNSUPPORTED, "a plant table holds fewer than 2^31 (plant, link) records (256 GB)");
+    { int rc = check_device(m); if (rc != CCLQR_OK) return rc; }
+    if (m->host.loop) return fail(CCLQR_EUNSUPPORTED, "per-instance plants are for forests of chains and branching trees (closed-loop mechanisms run their own plant)");
+    const size_t nb = (size_t)m->nb, np = (size_t)n_plant;
+    hipStream_t st = (hipStream_t)stream;
+    const double* src[4] = {mass, inertia, p1, p2};
+    const size_t per[4] = {nb, 9 * nb, 3 * nb, 3 * nb};
+    unsigned long long* derr = nullptr;
+    WsScope scope;
+    hipError_t e = ws_get((void**)&derr, sizeof(unsigned long long));
+    if (!on_device) {
+        for (int k = 0; k < 4 && e == hipSuccess; k++) {
+            if (!src[k]) continue;
+            double* d = nullptr;
+            e = ws_get((void**)&d, np * per[k] * sizeof(double));
+            if (e == hipSuccess) e = hipMemcpyAsync(d, src[k], np * per[k] * sizeof(double), hipMemcpyHostToDevice, st);
+            src[k] = d;
+        }
+    }
+    cclqr_plants* P = new cclqr_plants();
+    P->dev = nullptr; P->n_plant = n_plant; P->first_index = first_index; P->mech = m; P->nb = m->nb; P->device = m->device;
+    unsigned long long herr = ~0ull;
+    if (e == hipSuccess) e = hipMalloc((void**)&P->dev, np * nb * sizeof(PlantRec));
+    if (e == hipSuccess) e = hipMemcpyAsync(derr, &herr, sizeof(herr), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = launch_plants_pack(m->dev, m->nb, n_plant, src[0], src[1], src[2], src[3], P->dev, derr, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(&herr, derr, sizeof(herr), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) { cclqr_plants_destroy(P); return fail(CCLQR_EHIP, std::string("plants upload: ") + hipGetErrorString(e)); }
+    if (herr != ~0ull) {
+        cclqr_plants_destroy(P);
+        const unsigned long long pb = herr / 4;
+        static const char* what[3] = {"a non-finite value", "mass must be positive", "inertia must be symmetric positive definite"};
+        return fail(CCLQR_EINVAL, "plant " + std::to_string(pb / nb) + ", body " + std::to_string(pb % nb) + ": " + what[herr % 4 < 3 ? herr % 4 : 0]);
+    }
+    *out = P;
+    return CCLQR_OK;
+}
+
+extern "C" int cclqr_plants_destroy(cclqr_plants* p) {
+    if (!p) return CCLQR_OK;
+    if (p->dev) (void)hipFree(p->dev);
+    delete p;
     return CCLQR_OK;
 }
 

@@ -65,15 +65,20 @@ struct LinkC {
 #define LANE_INT_FRESH(x) ((void)0)
 #endif
 
-HD void link_load_consts(LinkC& c, const MechDev* M, int t, int nb, double dt) {
+// P: the records of the plant the lane's instance runs on, [nb] in link order -- the mechanism's own (M->rec) or a row of a per-instance plant table
+// (cclqr_plants_create): m, J, p1, p2 and the parent's mass come from there, everything else (the topology) from the mechanism.  ONE code path for both,
+// so a plant table that repeats the mechanism's numbers gives the same bits.  The parent's mass is read from the parent link's record, indexed by the
+// mechanism's parent table: no load of a record waits for another one.
+HD void link_load_consts_rec(LinkC& c, const MechDev* M, const PlantRec* P, int t, int nb, double dt) {
     const bool on = t < nb;
     const int l = on ? t : 0;
+    const PlantRec* r = P + l;
 
-    c.m = M->m[l];
+    c.m = r->m;
 #pragma unroll
-    for (int i = 0; i < 9; i++) c.J[i] = M->J[l][i];
+    for (int i = 0; i < 9; i++) c.J[i] = r->J[i];
 #pragma unroll
-    for (int i = 0; i < 3; i++) { c.p1[i] = M->p1[l][i]; c.p2[i] = M->p2[l][i]; c.axis[i] = M->axis[l][i]; }
+    for (int i = 0; i < 3; i++) { c.p1[i] = r->p1[i]; c.p2[i] = r->p2[i]; c.axis[i] = M->axis[l][i]; }
 #pragma unroll
     for (int i = 0; i < 4; i++) c.qoc[i] = M->qoc[l][i];
     const int type = M->type[l];              // 0 revolute, 1 prismatic
@@ -85,9 +90,11 @@ HD void link_load_consts(LinkC& c, const MechDev* M, int t, int nb, double dt) {
     c.flags = (on ? 1 : 0) | (has_a ? 2 : 0) | ((on && M->childl[l] >= 0) ? 4 : 0) | (type == 0 ? 8 : 0);
     c.dtm = dt / c.m;
     c.sxb = dt * c.dtm;
-    c.sxa = has_a ? dt * dt / M->m[pa >= 0 ? pa : 0] : 0.0;
+    c.sxa = has_a ? dt * dt / P[pa >= 0 ? pa : 0].m : 0.0;
     c.fric = 0.0;
 }
+// the mechanism's own plant
+HD void link_load_consts(LinkC& c, const MechDev* M, int t, int nb, double dt) { link_load_consts_rec(c, M, M->rec, t, nb, dt); }
 // selector of constraint row `row` (compile-time row index)
 HD void row_sel(const LinkC& c, int row, double* s) {
     const bool rev = c.rev();

@@ -25,6 +25,14 @@
 
 namespace cclqr {
 
+// ---- what a PLANT fixes of one link, in link order: the body's mass and inertia and the two vertices of the link's own joint, as ONE aligned record of
+// 16 doubles.  The mechanism carries the records of its own plant (MechDev::rec, filled with the tables); per-instance plants (cclqr_plants_create) are
+// [n_plant][nb] of them, packed and validated on the device by plants.hip.  The rollout kernels' prologue reads a link's constants from a record
+// either way (cclqr_chain.h link_load_consts_rec): one code path, the same bits.  The topology (joint types, axes, qoffset, dt, g) is the mechanism's.
+struct alignas(128) PlantRec {
+    double m, J[9], p1[3], p2[3];
+};
+
 // ---- mechanism tables in device memory (internal link order = chain by chain, root to leaf) ----
 struct MechDev {
     int nb;
@@ -59,7 +67,16 @@ struct MechDev {
     int loop, nj;
     int jchild[CCLQR_MAXL];
     int inc_n[8], inc_j[8][CCLQR_MAXI], inc_side[8][CCLQR_MAXI];   // joints around body b; side 0: b is the child, 1: the parent
+    // ---- m, J, p1, p2 of every link once more as records (chains and trees; mech_fill_records): what the register-resident kernels' prologue loads
+    PlantRec rec[CCLQR_MAXL];
 };
+HD void mech_fill_records(MechDev& H) {
+    for (int l = 0; l < CCLQR_MAXL; l++) {
+        H.rec[l].m = H.m[l];
+        for (int i = 0; i < 9; i++) H.rec[l].J[i] = H.J[l][i];
+        for (int i = 0; i < 3; i++) { H.rec[l].p1[i] = H.p1[l][i]; H.rec[l].p2[i] = H.p2[l][i]; }
+    }
+}
 
 // ---- the launch-invariant record of a controller that a rollout step reads (CtrlDev::hot): ONE contiguous, aligned block, so that a step fetches
 // it with one wide uniform load (a scalar load through the constant address space: cclqr_rollout_step.h) and forms every row address from it

@@ -28,6 +28,8 @@ struct RolloutArgs {
                           // frozen and keeps its status, the others merge this launch's Newton count / failure into it
     int ipw;              // chain and tree kernels: instances per wavefront, 1 .. 64 / lanes per instance (lane groups beyond it hold no instance).  The caller of
                           // launch_rollout_chain / launch_rollout_treereg passes 0 (the launch chooses: spread_instances_per_wavefront) or nonzero = pack every wavefront full
+    const PlantRec* plants;   // per-instance plants (cclqr_rollout_plants): records [n_plant][nb] in link order, or nullptr = every instance runs the mechanism's own plant
+    int64_t plant_off;        // instance n of this launch runs plant plant_off + n (= first_instance - the table's first_index; checked against [0, n_plant) on the host)
 };
 
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (device, kernel) instead of once per launch: remembers the largest size set so
@@ -95,6 +97,12 @@ hipError_t launch_rollout_chain(const RolloutArgs& a, const RolloutShape& s, int
 hipError_t launch_rollout_treereg(const RolloutArgs& a, const RolloutShape& s, int simds, ControlLaw law, int newton_mode, hipStream_t stream);
 hipError_t launch_rollout_loop(const RolloutArgs& a, const RolloutShape& s, int newton_mode, hipStream_t stream);
 
+// per-instance plants (plants.hip): pack the caller-order arrays (device pointers; null = the mechanism's own value) into link-order records and
+// validate them; *first_err (set to ~0 by the caller) receives the smallest (plant * nb + body) * 4 + kind among the offending entries
+enum { PLANT_ERR_NONFINITE = 0, PLANT_ERR_MASS = 1, PLANT_ERR_INERTIA = 2 };
+hipError_t launch_plants_pack(const MechDev* M, int nb, long long n_plant, const double* mass, const double* inertia, const double* p1, const double* p2,
+                              PlantRec* out, unsigned long long* first_err, hipStream_t stream);
+
 struct LinArgs {
     const MechDev* M;
     int nk, mu;
@@ -153,6 +161,12 @@ struct cclqr_mech {
     int device;
     int simds;                 // SIMDs of `device` (4 per compute unit): what spread_instances_per_wavefront spreads a small batch over
     cclqr::RolloutShape shape; // the kernel this mechanism's rollouts and linearisations run on
+};
+struct cclqr_plants {
+    cclqr::PlantRec* dev;      // [n_plant][nb] records in the mechanism's link order
+    int64_t n_plant, first_index;
+    const cclqr_mech* mech;    // the mechanism whose link order and default values the records were packed with
+    int nb, device;
 };
 // zero doubles behind a controller's gain table: the control phase fetches ceil(12 NBP / G) G entries of a row whatever the mechanism's own
 // 12 nb, i.e. up to 12 x 64 - 12 past the end of the LAST row when a short chain runs on a long image.  With one table per instance (n_ctrl > 1)

@@ -205,6 +205,7 @@ static inline int build_mech_tables(const cclqr_mech_desc* d, cclqr_mech* m, std
             for (int i = 0; i < 3; i++) H.sel[l][r][i] = (nrows == 3) ? (i == q ? 1.0 : 0.0) : V12[3 * q + i];
         }
     }
+    mech_fill_records(H);
     for (int l = 0; l < nb; l++)
         if (H.parent[l] >= 0) {
             const int a = H.parent[l];

@@ -242,12 +242,17 @@ __global__ __launch_bounds__(64) void rollout_chain_kernel(RolloutArgs a) {
     const int nz = 13 * nb;
 
     LinkC c;
-    link_load_consts(c, M, (KL > 1 && w >= KL) ? CCLQR_MAXL : tl, nb, dt);
+    // the lane's link constants, from the records of the plant its instance runs on: the mechanism's own, or -- per-instance plants, a wavefront-uniform
+    // branch -- the row of the launch's table (a lane group without an instance reads the first instance's, as it does with controller tables)
+    const PlantRec* plant = M->rec;
+    const bool have = grp < a.ipw && inst < a.n_inst;      // the lane's instance exists
+    if (a.plants) plant = a.plants + ((unsigned)a.plant_off + (have ? (unsigned)inst : 0u)) * (unsigned)nb;      // (a table holds fewer than 2^31 records: cclqr_plants_create)
+    link_load_consts_rec(c, M, plant, (KL > 1 && w >= KL) ? CCLQR_MAXL : tl, nb, dt);
     if (KL == 1 || w == 0) c.flags |= LinkC::PRIM;
     SubSel Q;
     if (KL > 1) sub_setup<KL>(c, w < KL ? w : 0, Q);
     if (EXTRA && CT->has_fric && c.on()) { c.fric = CT->fric[tl]; if (c.fric != 0.0) c.flags |= LinkC::FRIC; }
-    c.set_valid(grp < a.ipw && inst < a.n_inst);
+    c.set_valid(have);
     const long long ginst = a.inst0 + inst;     // global instance index: selects the controller table when there is one per instance
     const int ut = c.on() ? M->perm[tl] : 0;      // user body index of the owned link
     // The chains of the forest, fetched once: lane ci of the wavefront keeps (start, length) of chain ci, every lane the number of chains
@@ -532,7 +537,10 @@ __global__ __launch_bounds__(64) void rollout_chain_kernel(RolloutArgs a) {
                     if (!__any(!ls_done)) break;
                     const bool mine = !ls_done;                                   // uniform over the group
                     const bool other = __shfl_xor(mine ? 1 : 0, 32, 64) != 0;     // the wavefront's other instance is searching too
-                    const bool helping = !mine && other;                          // this group's lanes evaluate two more levels of the other's search
+                    // per-instance plants: a group holds the constants of its own instance's plant only, so it evaluates no trial of the other instance --
+                    // nobody helps, and a searcher advances its own two levels per pass.  Read from the kernel arguments here, not kept through the launch
+                    const bool solo = ap->plants != nullptr;
+                    const bool helping = !mine && other && !solo;                 // this group's lanes evaluate two more levels of the other's search
                     TrialIn T;
 #pragma unroll
                     for (int i = 0; i < 7; i++) T.z[i] = S.z[i];
@@ -558,13 +566,13 @@ __global__ __launch_bounds__(64) void rollout_chain_kernel(RolloutArgs a) {
 #pragma unroll
                         for (int i = 0; i < 4; i++) {
                             const int l = lv + i;
-                            if (!ls_done && l <= LINE_MAXIT && (i < 2 || !other)) {
+                            if (!ls_done && l <= LINE_MAXIT && (i < 2 || !(other || solo))) {
                                 normf1 = cand[i]; alpha = ldexp(1.0, -l); jac_ok = false;
                                 if (!(cand[i] > normf0) || l == LINE_MAXIT) ls_done = true;
                             }
                         }
                     }
-                    lv += (mine && other) ? 2 : 4;
+                    lv += (solo || (mine && other)) ? 2 : 4;
                 }
             } else {
                 // group assist: the NG = 64 / G groups of the wavefront are dealt to the `count` instances that are still searching -- group g
@@ -576,12 +584,14 @@ __global__ __launch_bounds__(64) void rollout_chain_kernel(RolloutArgs a) {
                     if (!__any(!ls_done)) break;
                     const bool mine = !ls_done;                                                   // uniform over the group
                     const unsigned long long heads = __ballot(mine && t == 0);                    // bit g G: group g is searching
-                    const int count = __builtin_popcountll(heads);                                // >= 1 behind the vote above
+                    // per-instance plants: a group holds its own instance's plant only, so every group works for itself -- the count == NG form below
+                    const bool solo = ap->plants != nullptr;
+                    const int count = solo ? NG : __builtin_popcountll(heads);                    // >= 1 behind the vote above
                     const int per = NG / count;                                                   // levels of every search this pass (>= 1)
                     const int kq = grp % count, off = grp / count;                                // this group works for the kq-th searcher, level lv + off
                     unsigned long long hm = heads;
                     for (int i = 0; i < kq; i++) hm &= hm - 1;                                    // (kq < count: the kq-th set bit exists)
-                    const int src = __builtin_ctzll(hm) / G;                                      // that searcher's group
+                    const int src = solo ? grp : __builtin_ctzll(hm) / G;                         // that searcher's group
                     int myrank = 0;                                                               // rank of this group among the searchers
                     for (int g2 = 0; g2 < NG; g2++) myrank += (g2 < grp && ((heads >> (g2 * G)) & 1ull)) ? 1 : 0;
                     const int l0 = lv + off;

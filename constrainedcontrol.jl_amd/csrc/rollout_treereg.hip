@@ -159,13 +159,18 @@ __global__ __launch_bounds__(64) void rollout_treereg_kernel(RolloutArgs a) {
     const int maxchild = R->maxchild, maxsib = R->maxsib;
 
     LinkC c;
-    link_load_consts(c, M, t, nb, dt);
+    // the lane's link constants, from the records of the plant its instance runs on: the mechanism's own, or -- per-instance plants, a wavefront-uniform
+    // branch -- the row of the launch's table (a lane group without an instance reads the first instance's, as it does with controller tables)
+    const PlantRec* plant = M->rec;
+    const bool have = grp < a.ipw && inst < a.n_inst;      // the lane's instance exists
+    if (a.plants) plant = a.plants + ((unsigned)a.plant_off + (have ? (unsigned)inst : 0u)) * (unsigned)nb;      // (a table holds fewer than 2^31 records: cclqr_plants_create)
+    link_load_consts_rec(c, M, plant, t, nb, dt);
     TreeL T;
     tree_load(T, M, R, t, nb);
     const int pa4 = gb4 + 4 * T.par;
     if (T.nchild > 0) c.flags |= 4;          // "has a child link" (link_load_consts reads the chains' single-child table)
     if (EXTRA && CT->has_fric && c.on()) { c.fric = CT->fric[t]; if (c.fric != 0.0) c.flags |= LinkC::FRIC; }
-    c.set_valid(grp < a.ipw && inst < a.n_inst);
+    c.set_valid(have);
     const long long ginst = a.inst0 + inst;
     const int ut = c.on() ? M->perm[t] : 0;
 
@@ -396,7 +401,8 @@ __global__ __launch_bounds__(64) void rollout_treereg_kernel(RolloutArgs a) {
                     if (!__any(!ls_done)) break;
                     const bool mine = !ls_done;
                     const bool other = __shfl_xor(mine ? 1 : 0, 32, 64) != 0;
-                    const bool helping = !mine && other;
+                    const bool solo = ap->plants != nullptr;      // per-instance plants: no group evaluates the other instance's trial (rollout_chain.hip)
+                    const bool helping = !mine && other && !solo;
                     TrialIn Tr;
 #pragma unroll
                     for (int i = 0; i < 7; i++) Tr.z[i] = S.z[i];
@@ -422,13 +428,13 @@ __global__ __launch_bounds__(64) void rollout_treereg_kernel(RolloutArgs a) {
 #pragma unroll
                         for (int i = 0; i < 4; i++) {
                             const int l = lv + i;
-                            if (!ls_done && l <= LINE_MAXIT && (i < 2 || !other)) {
+                            if (!ls_done && l <= LINE_MAXIT && (i < 2 || !(other || solo))) {
                                 normf1 = cand[i]; alpha = ldexp(1.0, -l); jac_ok = false;
                                 if (!(cand[i] > normf0) || l == LINE_MAXIT) ls_done = true;
                             }
                         }
                     }
-                    lv += (mine && other) ? 2 : 4;
+                    lv += (solo || (mine && other)) ? 2 : 4;
                 }
             } else {
                 for (int lv = 1; lv <= LINE_MAXIT; lv++) {

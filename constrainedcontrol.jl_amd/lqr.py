@@ -571,13 +571,16 @@ def _simulate_device_closure(mechanism, steps, controller, record, z0):
 
 
 def simulate(mechanism, tend_or_storage, controller, record=True, z0=None, fric=None, noise=None, noise_scale=None, noise_seed=None,
-             first_instance=0):
+             first_instance=0, plants=None):
     """simulate!(mechanism, tend::Real | storage::Storage, controller; record)  -> Storage
 
     z0 [n_inst][nb][13]: batch of initial states (default: the mechanism's current body states, one instance).
     fric [ne], noise [n_inst][steps] (injected samples) or noise_seed (device-side Philox-4x32 stream per instance), noise_scale:
     the friction/noise law of examples/trackingLQR_triple_cartpole.jl:93-111.  first_instance: global index of z0[0] when z0 is one
     rank's shard of a larger batch (the Philox stream of an instance is keyed by its global index).
+    plants: a PlantBatch -- instance i runs with the masses, inertias and joint vertices of plant first_instance + i (the controller's gains stay the
+    ones it was built with: the Monte-Carlo robustness run).  z0[i] must lie on plant i's constraint manifold (joint_position_states(..., plants=)).  For the
+    fused laws (LQR, TrackingLQR with friction / noise, OpenLoop, PID).
     After the call the mechanism's bodies hold instance 0's final state (simulate! mutates the mechanism)."""
     if isinstance(tend_or_storage, Storage):
         steps = tend_or_storage.steps
@@ -585,9 +588,16 @@ def simulate(mechanism, tend_or_storage, controller, record=True, z0=None, fric=
         steps = int(math.ceil(tend_or_storage / mechanism.Δt))     # steps = 1:ceil(tend/Δt)
     nb = len(mechanism.bodies)
     z0 = mechanism.state()[None] if z0 is None else np.asarray(z0, dtype=np.float64).reshape(-1, nb, 13)
+    if plants is not None:
+        if getattr(controller, "controlfunction", None) is not None:
+            raise ValueError("plants= with a custom controlfunction is not supported yet: per-instance plants run under the fused laws (LQR, TrackingLQR, OpenLoop, PID)")
+        if plants.mechanism is not mechanism:
+            raise ValueError("the PlantBatch was made for another mechanism")
+        plants.rows_for(first_instance, z0.shape[0])      # every instance must find its plant
     dev = _device_mech(mechanism)
     if (noise is not None or noise_seed is not None) and noise_scale is None:
         noise_scale = 1.0
+    ph = None if plants is None else plants.handle(dev)
     if getattr(controller, "controlfunction", None) is not None:
         # a custom controlfunction (lqr.jl:14): the closure owns the whole law, as in the reference -- the built-in extras do not apply on top of it
         if fric is not None or noise is not None or noise_seed is not None:
@@ -597,7 +607,7 @@ def simulate(mechanism, tend_or_storage, controller, record=True, z0=None, fric=
     else:
         ctrl = controller._ctrl_handle(dev, fric=fric, noise_scale=0.0 if noise_scale is None else noise_scale, noise_seed=noise_seed)
         try:
-            zT, traj, status = _capi.rollout(dev, ctrl, z0, steps, k0=1, noise=noise, record=record, first_instance=first_instance)
+            zT, traj, status = _capi.rollout(dev, ctrl, z0, steps, k0=1, noise=noise, record=record, first_instance=first_instance, plants=ph)
         finally:
             ctrl.close()
     mechanism.set_state(zT[0])

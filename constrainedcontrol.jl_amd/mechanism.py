@@ -279,12 +279,135 @@ def setJointPosition(mech, eqc, θ):
         setPosition(j.body1, j.body2, p1=j.p1, p2=j.p2, Δx=θ * a, Δq=j.qoffset)
 
 
-def joint_position_states(mech, θ):
+def link_order(tables):
+    """(perm, jperm): the caller's body and joint index of every link in the kernels' link order of a TREE mechanism -- depth first from the origin,
+    children in the caller's joint order, the first child of a body continuing its chain (the order cclqr_mech_create numbers links in)"""
+    nb = tables.nb
+    parent, child = [int(x) for x in tables.parent], [int(x) for x in tables.child]
+    if tables.ne != nb or sorted(child) != list(range(nb)):
+        raise ValueError("link_order: a tree mechanism has one joint per body")
+    pj = {child[j]: j for j in range(nb)}
+    stack = [child[j] for j in range(nb - 1, -1, -1) if parent[j] == -1]
+    perm = []
+    while stack:
+        b = stack.pop()
+        perm.append(b)
+        if len(perm) > nb:
+            break
+        stack += [child[k] for k in range(nb - 1, -1, -1) if parent[k] == b]
+    if len(perm) != nb:
+        raise ValueError("link_order: the mechanism is not a tree rooted at the origin")
+    return np.array(perm, dtype=np.int32), np.array([pj[b] for b in perm], dtype=np.int32)
+
+
+class PlantBatch:
+    """Per-instance plants of one tree mechanism: instance i of a batch runs with its own masses, inertias and joint vertices -- the numbers
+    `Box(x, y, z, m)` and `Revolute(a, b, axis; p1, p2)` fix for the single plant of a reference run (examples/lqr_cartpole.jl:21-26) -- while the
+    topology (joint types, axes, qoffset, Δt, g) stays the mechanism's.  mass [n][nb], inertia [n][nb][3][3], p1 / p2 [n][ne][3] in the order of
+    mechanism.bodies / mechanism.eqconstraints; None = the mechanism's own value for every plant.  first_index: global instance index of row 0
+    (a rank of a sharded batch holds its slice only).  Pass it to joint_position_states(..., plants=) and simulate(..., plants=)."""
+
+    def __init__(self, mechanism, mass=None, inertia=None, p1=None, p2=None, first_index=0):
+        t = self._tables(mechanism)
+        if t.ne != t.nb or sorted(int(c) for c in t.child) != list(range(t.nb)) or any(int(k) == FIXED_ORIENTATION for k in t.type):
+            raise ValueError("PlantBatch: per-instance plants exist for tree mechanisms (forests of chains, branching trees), not for closed loops")
+        nb, ne = t.nb, t.ne
+        arr = lambda a, sh: None if a is None else np.ascontiguousarray(a, dtype=np.float64).reshape((-1,) + sh)
+        self.mass, self.inertia, self.p1, self.p2 = arr(mass, (nb,)), arr(inertia, (nb, 9)), arr(p1, (ne, 3)), arr(p2, (ne, 3))
+        sizes = {a.shape[0] for a in (self.mass, self.inertia, self.p1, self.p2) if a is not None}
+        if len(sizes) != 1:
+            raise ValueError("PlantBatch: give at least one of mass, inertia, p1, p2, all with the same number of plants (got %s)" % sorted(sizes))
+        self.mechanism, self.n_plant, self.first_index = mechanism, sizes.pop(), int(first_index)
+        if self.first_index < 0:
+            raise ValueError("PlantBatch: first_index must not be negative")
+        self._validate()
+        self._handle = None
+
+    @staticmethod
+    def _tables(mechanism):          # a Mechanism, or its flat MechTables
+        return mechanism if isinstance(mechanism, MechTables) else mechanism.tables()
+
+    def _validate(self):
+        """the refusals of cclqr_plants_create, stated on the host before anything is uploaded: the first offending (plant, body)"""
+        def first(bad):          # bad [n][nb] -> (plant, body) of the first True in row-major order, or None
+            k = np.flatnonzero(bad.reshape(-1))
+            return None if k.size == 0 else divmod(int(k[0]), bad.shape[1])
+        t = self._tables(self.mechanism)
+        ch = np.asarray(t.child)
+        for name, a in (("mass", self.mass), ("inertia", self.inertia), ("p1", self.p1), ("p2", self.p2)):
+            if a is None:
+                continue
+            hit = first(~np.isfinite(a).reshape(a.shape[0], a.shape[1], -1).all(axis=2))
+            if hit:
+                raise ValueError("PlantBatch: plant %d, body %d: a non-finite value in %s" % (hit[0], ch[hit[1]] if name in ("p1", "p2") else hit[1], name))
+        if self.mass is not None:
+            hit = first(~(self.mass > 0))
+            if hit:
+                raise ValueError("PlantBatch: plant %d, body %d: mass must be positive" % hit)
+        if self.inertia is not None:
+            J = self.inertia.reshape(-1, t.nb, 3, 3)
+            big = np.abs(J).max(axis=(2, 3))
+            sym = np.abs(J - J.transpose(0, 1, 3, 2)).max(axis=(2, 3)) <= 1e-12 * big
+            pd = (J[..., 0, 0] > 0) & (np.linalg.det(J[..., :2, :2]) > 0) & (np.linalg.det(J) > 0)
+            hit = first(~(sym & pd))
+            if hit:
+                raise ValueError("PlantBatch: plant %d, body %d: inertia must be symmetric positive definite" % hit)
+
+    @classmethod
+    def scaled(cls, mechanism, n, mass=(1.0, 1.0), length=(1.0, 1.0), seed=0, first_index=0):
+        """n randomised plants: every body's mass times U(mass) with its inertia scaled alike, every joint's p1 and p2 times U(length) (one factor
+        per joint).  The draws of plant i depend on (seed, first_index + i) only, so a shard holds the rows the whole batch would."""
+        t = cls._tables(mechanism)
+        fm, fl = np.empty((n, t.nb)), np.empty((n, t.ne))
+        for i in range(n):
+            rng = np.random.default_rng([int(seed), int(first_index) + i])
+            fm[i], fl[i] = rng.uniform(mass[0], mass[1], t.nb), rng.uniform(length[0], length[1], t.ne)
+        return cls(mechanism, mass=t.mass[None] * fm, inertia=t.inertia[None] * fm[:, :, None], p1=t.p1[None] * fl[:, :, None], p2=t.p2[None] * fl[:, :, None],
+                   first_index=first_index)
+
+    def tables(self, i):
+        """MechTables of plant i (row i of the arrays): the mechanism's tables with that plant's numbers"""
+        t = self._tables(self.mechanism)
+        pick = lambda a, own: own if a is None else a[i]
+        return MechTables(t.nb, t.ne, t.dt, t.g, pick(self.mass, t.mass), pick(self.inertia, t.inertia), t.parent, t.child, t.type, pick(self.p1, t.p1),
+                          pick(self.p2, t.p2), t.axis, t.qoff)
+
+    def link_records(self):
+        """[n_plant][nb][16] = (m, J[9], p1[3], p2[3]) of every link in the kernels' link order: what cclqr_plants_create packs on the device"""
+        t = self._tables(self.mechanism)
+        perm, jperm = link_order(t)
+        full = lambda a, own: np.broadcast_to(own[None], (self.n_plant,) + own.shape) if a is None else a
+        rec = np.empty((self.n_plant, t.nb, 16))
+        rec[:, :, 0] = full(self.mass, t.mass)[:, perm]
+        rec[:, :, 1:10] = full(self.inertia, t.inertia)[:, perm]
+        rec[:, :, 10:13] = full(self.p1, t.p1)[:, jperm]
+        rec[:, :, 13:16] = full(self.p2, t.p2)[:, jperm]
+        return rec
+
+    def rows_for(self, first_instance, n_inst):
+        """rows of the arrays that instances first_instance .. first_instance + n_inst - 1 run on; ValueError when they are not all here"""
+        lo = int(first_instance) - self.first_index
+        if lo < 0 or lo + n_inst > self.n_plant:
+            raise ValueError("PlantBatch: instances %d .. %d are not all among the plants %d .. %d" % (first_instance, first_instance + n_inst - 1, self.first_index,
+                                                                                                  self.first_index + self.n_plant - 1))
+        return range(lo, lo + n_inst)
+
+    def handle(self, dev):
+        """the device-resident copy (a _capi.PlantsHandle on the mechanism handle dev), created on first use"""
+        from . import _capi
+        if self._handle is None or not self._handle.ptr or self._handle.mech is not dev:
+            self._handle = _capi.PlantsHandle(dev, self.mass, self.inertia, self.p1, self.p2, first_index=self.first_index)
+        return self._handle
+
+
+def joint_position_states(mech, θ, plants=None, first_instance=0):
     """batch form of `setPosition!(mech, eqc, [θ])` applied to every joint of a TREE mechanism in root-to-leaf order (the loop of
     examples/lqr_sawyer.jl:11-14 for n poses at once): θ [n][ne] joint coordinates in the order of mech.eqconstraints -> z [n][nb][13]
-    at rest.  Same arithmetic as setJointPosition / setPosition, vectorised over the batch (workload generator of bench.py)."""
+    at rest.  Same arithmetic as setJointPosition / setPosition, vectorised over the batch (workload generator of bench.py).
+    plants: a PlantBatch -- pose i is placed with the joint vertices of plant first_instance + i, so that it lies on its own plant's constraint manifold."""
     θ = np.asarray(θ, dtype=np.float64).reshape(-1, len(mech.eqconstraints))
     n, nb = θ.shape[0], len(mech.bodies)
+    rows = None if plants is None else list(plants.rows_for(first_instance, n))
     index = {id(b): i for i, b in enumerate(mech.bodies)}
     z = np.zeros((n, nb, 13))
     z[:, :, 3] = 1.0
@@ -324,7 +447,9 @@ def joint_position_states(mech, θ):
                 dx = θ[:, k:k + 1] * a[None]
             q2 = bq(q1, dq)
             z[:, ch, 3:7] = q2
-            z[:, ch, 0:3] = x1 + brot(j.p1 + dx, q1) - brot(j.p2, q2)
+            jp1 = j.p1 if rows is None or plants.p1 is None else plants.p1[rows, k]
+            jp2 = j.p2 if rows is None or plants.p2 is None else plants.p2[rows, k]
+            z[:, ch, 0:3] = x1 + brot(jp1 + dx, q1) - brot(jp2, q2)
             done.add(ch)
         if len(rest) == len(pending):
             raise ValueError("joint_position_states: the mechanism is not a tree hung off the origin")

@@ -34,8 +34,10 @@ extern "C" {
  * the thread-local setters (cclqr_set_instance_offset, cclqr_set_pid_state, cclqr_riccati_path) removed.
  * 201 (additive over 200: same struct sizes and offsets): cclqr_rollout_opts.reserved became `flags` (CCLQR_ROLLOUT_NO_ALLOC), new entry points
  * cclqr_ctrl_set_feedforward and cclqr_abi_layout.  A shim checks cclqr_version() == the version it was written against AND, through
- * cclqr_abi_layout(), the sizeof / offsetof of every struct it mirrors. */
-#define CCLQR_ABI_VERSION 201
+ * cclqr_abi_layout(), the sizeof / offsetof of every struct it mirrors.
+ * 202 (additive over 201: no struct changed): per-instance plants -- the opaque cclqr_plants with cclqr_plants_create / cclqr_plants_destroy, and the
+ * launch on them, cclqr_rollout_plants. */
+#define CCLQR_ABI_VERSION 202
 
 #define CCLQR_REVOLUTE 0      /* EqualityConstraint(Revolute(a, b, axis; p1, p2, qoffset)),  examples/lqr_cartpole.jl:26 */
 #define CCLQR_PRISMATIC 1     /* EqualityConstraint(Prismatic(a, b, axis; p1, p2, qoffset)), examples/lqr_cartpole.jl:25 */
@@ -94,6 +96,7 @@ typedef struct {
 
 typedef struct cclqr_mech cclqr_mech; /* opaque: device-resident mechanism tables */
 typedef struct cclqr_ctrl cclqr_ctrl; /* opaque: device-resident controller tables */
+typedef struct cclqr_plants cclqr_plants; /* opaque: device-resident per-instance plants (masses, inertias, joint vertices) */
 
 const char *cclqr_last_error(void);
 int cclqr_version(void);     /* CCLQR_ABI_VERSION of the library that was loaded */
@@ -283,6 +286,29 @@ typedef struct {
 int cclqr_rollout_ex(const cclqr_mech *m, const cclqr_ctrl *c, int64_t n_inst, int32_t steps, int32_t k0, const double *z0_dev,
                      double *lam_dev, const double *noise_dev, int64_t noise_stride, double *traj_dev, double *zT_dev,
                      int32_t *status_dev, const cclqr_rollout_opts *opts, void *stream);
+
+/* Per-instance plants: the numbers that `Box(width, depth, length1, length1)` (examples/lqr_cartpole.jl:21-22: mass, inertia), `Prismatic(origin, cart, ey)` /
+ * `Revolute(cart, pole, ex; p2=-p2)` (:25-26: the joint vertices p1, p2) and `Mechanism(origin, links, constraints; g, Δt)` (:32) fix for the ONE plant of a reference
+ * run, here one set for every instance of a batch -- the Monte-Carlo robustness run "do these gains survive a plant that is 20 % heavier or 5 % longer" as one
+ * launch.  The topology stays the mechanism's: joint types, axes, qoffset, Δt, g.
+ *   mass [n_plant][nb], inertia [n_plant][nb][9] (body frame), p1, p2 [n_plant][ne][3], in the caller's body / joint order as in cclqr_mech_desc; any of them
+ *   may be NULL = the mechanism's own value for every plant.  on_device = 0: HOST pointers; 1: DEVICE pointers, read on `stream` (a hipStream_t).  Either way the
+ *   arrays are packed into link-order records and validated on the device, and the call returns when that is done (the arrays may be released then).
+ *   first_index = global instance index of row 0: rank r of a sharded batch uploads its slice only (cclqr_rollout_opts.first_instance).
+ * CCLQR_EUNSUPPORTED for a closed-loop mechanism; CCLQR_EINVAL naming the first offending (plant = row of the arrays, body) for a non-finite value, a mass <= 0 or
+ * an inertia that is not symmetric positive definite.  The handle must not outlive the mechanism it was created for. */
+int cclqr_plants_create(const cclqr_mech *m, int64_t n_plant, int64_t first_index, const double *mass, const double *inertia, const double *p1,
+                        const double *p2, int32_t on_device, void *stream, cclqr_plants **out);
+int cclqr_plants_destroy(cclqr_plants *p);
+
+/* cclqr_rollout_ex on per-instance plants -- simulate!(mechanism_n, steps, controller) (examples/lqr_cartpole.jl:44) where mechanism_n is the `Mechanism(...)` of
+ * examples/lqr_cartpole.jl:32 rebuilt with instance n's `Box(...)` / `Revolute(...; p1, p2)` numbers (:21-26).  Instance n of the launch runs plant
+ * first_instance + n - first_index; a launch whose instances are not all inside the table is refused with CCLQR_EINVAL before anything is launched.  The plant set
+ * is an argument of the launch: nothing of it is kept in the mechanism or controller handle.  plants == NULL: exactly cclqr_rollout_ex.  The states z0 must lie on
+ * each instance's OWN plant's constraint manifold (its own joint vertices).  Forests of chains and branching trees, every control law. */
+int cclqr_rollout_plants(const cclqr_mech *m, const cclqr_plants *plants, const cclqr_ctrl *c, int64_t n_inst, int32_t steps, int32_t k0, const double *z0_dev,
+                         double *lam_dev, const double *noise_dev, int64_t noise_stride, double *traj_dev, double *zT_dev, int32_t *status_dev,
+                         const cclqr_rollout_opts *opts, void *stream);
 
 /* cclqr_rollout (HOST pointers) with options: first_instance and newton_mode apply, the device-buffer fields must be NULL. */
 int cclqr_rollout_host_ex(const cclqr_mech *m, const cclqr_ctrl *c, int64_t n_inst, int32_t steps, int32_t k0, const double *z0,

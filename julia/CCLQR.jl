@@ -56,7 +56,7 @@ struct RiccatiOpts         # cclqr_riccati_opts
     reserved::Int32
 end
 
-const ABI_VERSION = 201    # include/cclqr.h CCLQR_ABI_VERSION: the structs above mirror THAT header field by field
+const ABI_VERSION = 202    # include/cclqr.h CCLQR_ABI_VERSION: the structs above mirror THAT header field by field
 "sizeof / fieldoffset of the four mirrors above in the order cclqr_abi_layout reports the library's own (include/cclqr.h)"
 mirrored_layout() = Int32[x for S in (MechDesc, CtrlDesc, RiccatiOpts, RolloutOpts) for x in (sizeof(S), (fieldoffset(S, i) for i in 1:fieldcount(S))...)]
 "call once after loading: a library built from another header would read these structs past their end (ADVICE r2).  The version number says which
@@ -296,6 +296,38 @@ function rollout_dev!(h::MechHandle, c::CtrlHandle, n::Integer, steps::Integer, 
                 (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Int32},
                  Ref{RolloutOpts}, Ptr{Cvoid}),
                 h.ptr, c.ptr, n, steps, k0, z0, lam, noise, noise_stride, traj, zT, status, o, stream))
+end
+
+"Per-instance plants (cclqr_plants_create): what `Box(...)`, `Revolute(...; p1, p2)` and `Mechanism(...)` (examples/lqr_cartpole.jl:21-32) fix for one plant, one set
+ per instance.  mass Nb x n, inertia 9 x Nb x n (each 3 x 3 block column-major = row-major, it is symmetric), p1 / p2 3 x Ne x n in the order of mech_tables; `nothing` =
+ the mechanism's own value.  first_index = global index (0-based) of the first plant.  Host arrays."
+mutable struct PlantsHandle
+    ptr::Ptr{Cvoid}
+    n::Int
+    mech::MechHandle      # keeps the mechanism alive: the plants were packed in its link order
+end
+function PlantsHandle(h::MechHandle, n::Integer; mass = nothing, inertia = nothing, p1 = nothing, p2 = nothing, first_index = 0)
+    arg(a) = a === nothing ? Ptr{Float64}(C_NULL) : pointer(a)
+    out = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve mass inertia p1 p2 check(ccall((:cclqr_plants_create, lib), Cint,
+                (Ptr{Cvoid}, Int64, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int32, Ptr{Cvoid}, Ref{Ptr{Cvoid}}),
+                h.ptr, n, first_index, arg(mass), arg(inertia), arg(p1), arg(p2), 0, C_NULL, out))
+    obj = PlantsHandle(out[], n, h)
+    finalizer(o -> ccall((:cclqr_plants_destroy, lib), Cint, (Ptr{Cvoid},), o.ptr), obj)
+    obj
+end
+
+"rollout_dev! on per-instance plants (cclqr_rollout_plants): instance i of the launch runs plant first_instance + i - first_index of `p`; the states must lie on each
+ instance's own plant's constraint manifold.  Everything else as rollout_dev!."
+function rollout_plants_dev!(h::MechHandle, p::PlantsHandle, c::CtrlHandle, n::Integer, steps::Integer, k0::Integer, z0::Ptr{Float64}, lam::Ptr{Float64},
+                             traj::Ptr{Float64}, zT::Ptr{Float64}, status::Ptr{Int32}; noise::Ptr{Float64} = Ptr{Float64}(C_NULL), noise_stride = 0,
+                             first_instance = 0, pid_state::Ptr{Float64} = Ptr{Float64}(C_NULL), noise_ws::Ptr{Float64} = Ptr{Float64}(C_NULL),
+                             newton_mode = 0, newton_eps_alone = 0.0, flags = Int32(0), stream::Ptr{Cvoid} = C_NULL)
+    o = RolloutOpts(first_instance, pid_state, pid_state == C_NULL ? 0 : n * h.nb * 2, noise_ws, noise_ws == C_NULL ? 0 : n * steps, newton_mode, Int32(flags), newton_eps_alone)
+    check(ccall((:cclqr_rollout_plants, lib), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Int32},
+                 Ref{RolloutOpts}, Ptr{Cvoid}),
+                h.ptr, p.ptr, c.ptr, n, steps, k0, z0, lam, noise, noise_stride, traj, zT, status, o, stream))
 end
 
 "Size the controller handle's Philox workspace before step-per-launch rollouts are captured into a hipGraph (cclqr_ctrl_reserve_noise)."
