@@ -26,6 +26,18 @@
 #else
 #define SCHED_FENCE() ((void)0)
 #endif
+// One double of the LDS image, read on its own.  The compiler pairs neighbouring 8-byte LDS reads into ds_read2_b64, which CDNA4 executes at half the
+// rate of two ds_read_b64 (128 against 256 bytes per clock); a volatile read through a pointer typed to the LDS address space stays a single
+// ds_read_b64 with a counted wait (volatile on a generic pointer would become a flat load).  Loads only, and only where it was measured to pay on the
+// headline kernel, phase by phase: the sweep (tri_step), the reduction level (cr_phase_a, cr_phase_b, cr_back) and the G_k operands
+// of the Schur rows (schur_col_load); ck_tri_mid, ck_tri_back and gk_t_apply gained less than the bar and keep the paired reads.  The
+// 8- and 16-lane kernels run tri_step and schur_col_load too: for them only head against parent as a whole was measured (+ 9.6 to + 11 %), not each phase.  Plain
+// indexing on the host (tests/emu).
+#if defined(__HIP_DEVICE_COMPILE__)
+#define LDS_RD(L, i) (*(const volatile __attribute__((address_space(3))) double*)(const __attribute__((address_space(3))) double*)((L) + (i)))
+#else
+#define LDS_RD(L, i) ((L)[i])
+#endif
 
 namespace cclqr {
 
@@ -369,10 +381,10 @@ HD void schur_col_load(SchurCol& K, int q, int j, int jp, int jc, const Lay& Y, 
     const int o = gk_row(q), ob = q < 3 ? 3 : 0;   // offset of PB inside the row
 #pragma unroll
     for (int i = 0; i < 3; i++) {
-        if (q < 3) { K.kx[i] = L[Y.GKA + GKSZ * j + o + i]; K.kpx[i] = L[Y.GKA + GKSZ * jp + o + i]; K.kcx[i] = L[Y.GKA + GKSZ * jc + o + i]; }
+        if (q < 3) { K.kx[i] = LDS_RD(L, Y.GKA + GKSZ * j + o + i); K.kpx[i] = LDS_RD(L, Y.GKA + GKSZ * jp + o + i); K.kcx[i] = LDS_RD(L, Y.GKA + GKSZ * jc + o + i); }
         else { K.kx[i] = 0.0; K.kpx[i] = 0.0; K.kcx[i] = 0.0; }
-        K.kb[i] = L[Y.GKA + GKSZ * j + o + ob + i]; K.ka[i] = L[Y.GKA + GKSZ * j + o + ob + 3 + i];
-        K.kpb[i] = L[Y.GKA + GKSZ * jp + o + ob + i]; K.kca[i] = L[Y.GKA + GKSZ * jc + o + ob + 3 + i];
+        K.kb[i] = LDS_RD(L, Y.GKA + GKSZ * j + o + ob + i); K.ka[i] = LDS_RD(L, Y.GKA + GKSZ * j + o + ob + 3 + i);
+        K.kpb[i] = LDS_RD(L, Y.GKA + GKSZ * jp + o + ob + i); K.kca[i] = LDS_RD(L, Y.GKA + GKSZ * jc + o + ob + 3 + i);
     }
 }
 // PF: the operands of column q + 1 are requested before column q is computed (two operand sets live: + 42 registers, which the 8- and 16-lane instantiations
@@ -735,18 +747,18 @@ HD bool tri_step(TriCur& K, int i, const double* L, double* tg, double* zy, int*
 #pragma unroll
     for (int cI = 0; cI < 5; cI++)
 #pragma unroll
-        for (int r = 0; r < 5; r++) lu[r * 5 + cI] = L[K.oLL + 5 * cI + r];
+        for (int r = 0; r < 5; r++) lu[r * 5 + cI] = LDS_RD(L, K.oLL + 5 * cI + r);
 #pragma unroll
-    for (int r = 0; r < 5; r++) zy[r] = L[K.oRhs + r];
+    for (int r = 0; r < 5; r++) zy[r] = LDS_RD(L, K.oRhs + r);
     const bool mstep = i == K.imerge;          // both fronts fold into the middle link now: this one's share goes to the scratch block
     // (loaded unconditionally and then selected: a load inside the conditional becomes five separately EXEC-masked reads)
     double tl[5];
 #pragma unroll
-    for (int r = 0; r < 5; r++) tl[r] = L[K.oTgt + r];
+    for (int r = 0; r < 5; r++) tl[r] = LDS_RD(L, K.oTgt + r);
 #pragma unroll
     for (int r = 0; r < 5; r++) tg[r] = mstep ? 0.0 : tl[r];
 #pragma unroll
-    for (int e = 0; e < 25; e++) sql[e] = L[K.oQL + e];
+    for (int e = 0; e < 25; e++) sql[e] = LDS_RD(L, K.oQL + e);
     lu5_factor(lu);
     lu5_solve(lu, zy);
 #pragma unroll
@@ -857,22 +869,22 @@ HD void cr_phase_a(CrLane<W>& K, const double* L, double (*tA)[5]) {
 #pragma unroll
     for (int cI = 0; cI < 5; cI++)
 #pragma unroll
-        for (int r = 0; r < 5; r++) lu[r * 5 + cI] = L[K.oLL + 5 * cI + r];
+        for (int r = 0; r < 5; r++) lu[r * 5 + cI] = LDS_RD(L, K.oLL + 5 * cI + r);
 #pragma unroll
     for (int s = 0; s < CrLane<W>::NS; s++)
 #pragma unroll
-        for (int r = 0; r < 5; r++) K.z[s][r] = L[K.oRhs[s] + r];
+        for (int r = 0; r < 5; r++) K.z[s][r] = LDS_RD(L, K.oRhs[s] + r);
     lu5_factor(lu);
 #pragma unroll
     for (int s = 0; s < CrLane<W>::NS; s++) lu5_solve(lu, K.z[s]);
     SCHED_FENCE();      // the factorisation is dead here: the neighbour block and the targets take its registers (fetching them
                         // ahead of the pivot chain costs ~80 registers more than the kernel has)
 #pragma unroll
-    for (int e = 0; e < 25; e++) blk[e] = L[K.oPL + e];
+    for (int e = 0; e < 25; e++) blk[e] = LDS_RD(L, K.oPL + e);
 #pragma unroll
     for (int s = 0; s < CrLane<W>::NS; s++)
 #pragma unroll
-        for (int r = 0; r < 5; r++) tA[s][r] = L[K.oA[s] + r];
+        for (int r = 0; r < 5; r++) tA[s][r] = LDS_RD(L, K.oA[s] + r);
 #pragma unroll
     for (int s = 0; s < CrLane<W>::NS; s++) {
         const double* z = K.z[s];
@@ -897,9 +909,9 @@ HD void cr_phase_b(const CrLane<W>& K, const double* L, double (*tB)[5]) {
 #pragma unroll
     for (int s = 0; s < CrLane<W>::NS; s++)
 #pragma unroll
-        for (int r = 0; r < 5; r++) tB[s][r] = L[K.oB[s] + r];
+        for (int r = 0; r < 5; r++) tB[s][r] = LDS_RD(L, K.oB[s] + r);
 #pragma unroll
-    for (int e = 0; e < 25; e++) blk[e] = L[K.oNL + e];
+    for (int e = 0; e < 25; e++) blk[e] = LDS_RD(L, K.oNL + e);
 #pragma unroll
     for (int s = 0; s < CrLane<W>::NS; s++) {
         const double* z = K.z[s];
@@ -927,15 +939,15 @@ HD void cr_back(int t, int cs, int n, int st, const Lay& Y, double* L, bool skip
     const bool has_n = idx + 1 < n;
     double dp[5], dn[5];
 #pragma unroll
-    for (int cI = 0; cI < 5; cI++) { dp[cI] = L[Y.DL + 5 * p + cI]; const double dnx = L[Y.DL + 5 * nx + cI]; dn[cI] = has_n ? dnx : 0.0; }   // nx <= one link past the chain: inside the image
+    for (int cI = 0; cI < 5; cI++) { dp[cI] = LDS_RD(L, Y.DL + 5 * p + cI); const double dnx = LDS_RD(L, Y.DL + 5 * nx + cI); dn[cI] = has_n ? dnx : 0.0; }   // nx <= one link past the chain: inside the image
     const int oZm = Y.SJP + 25 * l, oZp = has_n ? Y.SPJ + 25 * (l + 1) : oZm;
     double out[(5 + W - 1) / W];
 #pragma unroll
     for (int q = 0; q < (5 + W - 1) / W; q++) {
         const int row = w + W * q, rr = row < 5 ? row : 0;
-        double acc = L[Y.R + 5 * l + rr];
+        double acc = LDS_RD(L, Y.R + 5 * l + rr);
 #pragma unroll
-        for (int cI = 0; cI < 5; cI++) { acc -= L[oZm + 5 * cI + rr] * dp[cI]; const double zp = L[oZp + 5 * cI + rr]; acc -= (has_n ? zp : 0.0) * dn[cI]; }
+        for (int cI = 0; cI < 5; cI++) { acc -= LDS_RD(L, oZm + 5 * cI + rr) * dp[cI]; const double zp = LDS_RD(L, oZp + 5 * cI + rr); acc -= (has_n ? zp : 0.0) * dn[cI]; }
         out[q] = acc;
     }
 #pragma unroll

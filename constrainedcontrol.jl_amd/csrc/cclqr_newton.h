@@ -8,7 +8,7 @@ namespace cclqr {
 // ---- optional in-kernel phase stamps (diagnostic build only: -DCCLQR_PROFILE; the shipped library contains none) ----
 #ifdef CCLQR_PROFILE
 enum { PF_CONTROL, PF_FORCES, PF_EVAL_BODY, PF_EVAL_JOINT, PF_EVAL_MAP, PF_SCHUR_W, PF_SCHUR_S, PF_TRI_FWD, PF_TRI_BWD, PF_BODY_SOLVE, PF_TRIAL,
-       PF_ACCEPT, PF_IO, PF_NEWTON_ITERS, PF_EVALS, PF_STEPS, PF_N };
+       PF_ACCEPT, PF_IO, PF_NEWTON_ITERS, PF_EVALS, PF_STEPS, PF_ROWS_SKIPPED, PF_N };      // (PF_ROWS_SKIPPED: evaluations of a wavefront that built no Schur rows)
 static __device__ unsigned long long g_prof[PF_N];
 struct Prof {
     unsigned long long t0, acc[PF_N];
@@ -17,6 +17,17 @@ struct Prof {
     __device__ void count(int c, int n = 1) { acc[c] += n; }
     __device__ void flush() { if ((threadIdx.x & 63) == 0) for (int i = 0; i < PF_N; i++) atomicAdd(&g_prof[i], acc[i]); }
 };
+// Host side of the counters. The two-argument cclqr_prof_read_* entry points fill exactly PF_READ_N words, the size their callers'
+// buffers have always had; counters behind that are read only through an entry point that takes the buffer's capacity.
+enum { PF_READ_N = 16 };
+static_assert(PF_READ_N == PF_ROWS_SKIPPED && PF_READ_N <= PF_N, "a new counter goes behind the words that two-argument readers receive");
+static inline int prof_read(unsigned long long* out, int cap, int reset) {
+    int n = cap < PF_N ? cap : PF_N;
+    if (!out || n < 0) return -1;
+    hipError_t e = hipMemcpyFromSymbol(out, HIP_SYMBOL(g_prof), sizeof(unsigned long long) * n);
+    if (e == hipSuccess && reset) { unsigned long long z[PF_N] = {0}; e = hipMemcpyToSymbol(HIP_SYMBOL(g_prof), z, sizeof(z)); }
+    return e == hipSuccess ? n : -1;
+}
 #define PROF_ARG , Prof& prof
 #define PROF_PASS , prof
 #define STAMP(c) prof.stamp(c)

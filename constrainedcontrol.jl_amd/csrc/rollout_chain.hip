@@ -41,12 +41,15 @@ __device__ __forceinline__ void from_next(const double* in, double* out) {
 // With JAC the Schur complement rows of the point go straight to LDS: W = G_v D^-1 only lives inside this function.
 // (The full-step trial is evaluated with JAC on the speculation that it is accepted; if it is not, the accepted point is
 // evaluated again, which overwrites these rows.)
+// rows: the lane's instance may still read the Schur rows and DINV of this point.  They are built and stored unless NO lane of the wavefront
+// says so (a vote: the rows are wavefront-wide work); the residual, the Jacobian code in front of them and the norm are the same either way.
 // KL > 1 (several lanes per link, cclqr_chain.h): t is the LINK of the lane (its sub-lane is Q.w); with Jacobians the lane evaluates the rows of its slots only
 // and builds their Schur rows, the body's share of the norm comes from the primary sub-lane alone.  KL = 1: the code of rounds 2-4, unchanged.
 template <int G, bool JAC, int KL = 1>
-__device__ __forceinline__ double chain_eval(LinkC& c, LinkS& S, int t, const Lay& Y, double* L, double alpha, bool active, double dt, const SubSel& Q PROF_ARG) {
+__device__ __forceinline__ double chain_eval(LinkC& c, LinkS& S, int t, const Lay& Y, double* L, double alpha, bool active, bool rows, double dt, const SubSel& Q PROF_ARG) {
     double part = 0.0;
     double NB[9], g[5], xq[7];
+    const bool store_dinv = JAC && __any(rows);
     LINK_FLAGS_FRESH(c);
 #pragma unroll
     for (int k = 0; k < 7; k++) xq[k] = S.z[k];
@@ -56,7 +59,7 @@ __device__ __forceinline__ double chain_eval(LinkC& c, LinkS& S, int t, const La
         for (int k = 0; k < 6; k++) { cf[k] = L[Y.C + 6 * t + k] - alpha * S.cd[k]; sv[k] = S.s[k] - alpha * S.ds[k]; cTR[k] = L[Y.D + 6 * t + k]; }
         part = ck_body_eval<JAC>(c, S.z, sv, cf, cTR, cTR + 3, dt, xq, S.d, DINV, NB);
         if (KL > 1 && !c.prim()) part = 0.0;
-        if (JAC && (KL == 1 || c.prim())) {
+        if (store_dinv && (KL == 1 || c.prim())) {
 #pragma unroll
             for (int k = 0; k < 9; k++) L[Y.DINV + 9 * t + k] = DINV[k];
         }
@@ -79,11 +82,15 @@ __device__ __forceinline__ double chain_eval(LinkC& c, LinkS& S, int t, const La
         }
         STAMP(PF_EVAL_JOINT);
         LINK_FLAGS_FRESH(c);
-        double pd[6];
-        from_prev<6>(S.d, pd);
-        // (the next column's operands are requested ahead on the three-lane shape, which has the registers: cartpole 160.0 -> 163.0 M; measured 0 / - 0.3 % on the
-        // one-lane 8- and 16-lane kernels -- tracking cfg5, Sawyer -- which therefore keep the plain form)
-        ck_schur_rows_sub<KL, (KL == 3)>(c, Q, t, active, Y, L, gs, sXT, sPB, sPA, S.d, pd);
+        if (__any(rows)) {
+            double pd[6];
+            from_prev<6>(S.d, pd);
+            // (the next column's operands are requested ahead on the three-lane shape, which has the registers: cartpole 160.0 -> 163.0 M; measured 0 / - 0.3 % on the
+            // one-lane 8- and 16-lane kernels -- tracking cfg5, Sawyer -- which therefore keep the plain form)
+            ck_schur_rows_sub<KL, (KL == 3)>(c, Q, t, active, Y, L, gs, sXT, sPB, sPA, S.d, pd);
+        } else {
+            PCOUNT(PF_ROWS_SKIPPED);
+        }
         STAMP(PF_SCHUR_S);
     } else {
         double wXT[3][3], wPB[5][3], wPA[5][3];
@@ -102,9 +109,13 @@ __device__ __forceinline__ double chain_eval(LinkC& c, LinkS& S, int t, const La
         STAMP(PF_EVAL_JOINT);
         LINK_FLAGS_FRESH(c);
         if (JAC) {
-            double pd[6];
-            from_prev<6>(S.d, pd);
-            ck_schur_rows(c, t, active, Y, L, wXT, wPB, wPA, g, S.d, pd);
+            if (__any(rows)) {
+                double pd[6];
+                from_prev<6>(S.d, pd);
+                ck_schur_rows(c, t, active, Y, L, wXT, wPB, wPA, g, S.d, pd);
+            } else {
+                PCOUNT(PF_ROWS_SKIPPED);
+            }
             STAMP(PF_SCHUR_S);
         }
     }
@@ -439,11 +450,18 @@ __global__ __launch_bounds__(64) void rollout_chain_kernel(RolloutArgs a) {
         const bool go = c.valid() && !c.dead();
         bool done = !go, failed = false;
         int its = 0;
-        double normf0 = chain_eval<G, true, KL>(c, S, tl, Y, L, 0.0, c.live() && !done, dt, Q PROF_PASS);
-        __syncthreads();
+        double normf0 = 0.0;
         LANE_INT_FRESH(plan);      // (read here, every step: not once per launch and kept in a scalar register)
         const int nchains = chain_plan_count(__builtin_amdgcn_readfirstlane(plan));
+        // ONE evaluation with Jacobians at the accepted point serves the start of the step (every instance that solves: its norm is the
+        // solve's first ||f||) and the iterations whose full-step trial was not the point accepted (need_jac, set where the step is accepted)
+        bool need_jac = !done;
         for (int iter = 1; iter <= NEWTON_MAXIT; iter++) {
+            if (__any(need_jac)) {
+                const double nf = chain_eval<G, true, KL>(c, S, tl, Y, L, 0.0, c.live() && need_jac, need_jac, dt, Q PROF_PASS);
+                if (iter == 1) normf0 = nf;
+            }
+            __syncthreads();
             if (!__any(!done)) break;
             PCOUNT(PF_NEWTON_ITERS);
             const bool active = c.live() && !done;
@@ -521,12 +539,17 @@ __global__ __launch_bounds__(64) void rollout_chain_kernel(RolloutArgs a) {
             __syncthreads();
             STAMP(PF_BODY_SOLVE);
             // line search: halve while ||f|| grows.  The first (full-step) trial also evaluates the Jacobians and the Schur blocks,
-            // speculating that it is accepted; later trials evaluate the residual only.  (Speculating the other way round once
-            // ||f|| < eps -- residual only, Jacobians afterwards if the instance goes on -- was measured: no gain.)
+            // speculating that it is accepted and the solve goes on; later trials evaluate the residual only.
+            // An instance whose ||f|| and step are both below eps already is in its last iteration if the trial's ||f|| is below eps too -- alpha nd < eps
+            // holds for every alpha <= 1 -- and then nothing reads the rows of the trial: the next step's first evaluation overwrites them.  When
+            // every instance of the wavefront that still solves is there, the trial builds none (same code for the residual: the same ||f||); one that
+            // goes on after all gets its rows from the evaluation at the top of the next iteration (jac_ok).  (A weaker predictor, ||f|| < eps alone
+            // with a residual-only trial, fires in iterations that are not the last: priced in round 3 at 0.5 % of a step, DESIGN_HISTORY.)
             double alpha = 1.0, normf1 = 0.0;
-            bool ls_done = done, jac_ok = true;
+            const bool want_rows = !done && !(normf0 < NEWTON_EPS && nd < NEWTON_EPS);
+            bool ls_done = done, jac_ok = __any(want_rows);
             {
-                const double nf = chain_eval<G, true, KL>(c, S, tl, Y, L, 1.0, active, dt, Q PROF_PASS);
+                const double nf = chain_eval<G, true, KL>(c, S, tl, Y, L, 1.0, active, want_rows, dt, Q PROF_PASS);
                 if (!ls_done) {
                     normf1 = nf;
                     if (!(normf1 > normf0)) ls_done = true;
@@ -629,7 +652,7 @@ __global__ __launch_bounds__(64) void rollout_chain_kernel(RolloutArgs a) {
                     lv += per;
                 }
             }
-            bool need_jac = false;
+            need_jac = false;
             if (!done) {
                 if (c.live()) {
                     if (KL == 1) {
@@ -654,8 +677,6 @@ __global__ __launch_bounds__(64) void rollout_chain_kernel(RolloutArgs a) {
                 need_jac = !done && !jac_ok;
             }
             STAMP(PF_ACCEPT);
-            if (__any(need_jac)) chain_eval<G, true, KL>(c, S, tl, Y, L, 0.0, c.live() && need_jac, dt, Q PROF_PASS);
-            __syncthreads();
         }
         const bool conv = done && !failed;
         if (go) {
@@ -713,9 +734,10 @@ __global__ __launch_bounds__(64) void rollout_chain_kernel(RolloutArgs a) {
 
 #ifdef CCLQR_PROFILE
 extern "C" int cclqr_prof_read_chain(unsigned long long* out, int reset) {
-    hipError_t e = hipMemcpyFromSymbol(out, HIP_SYMBOL(g_prof), sizeof(unsigned long long) * PF_N);
-    if (e == hipSuccess && reset) { unsigned long long z[PF_N] = {0}; e = hipMemcpyToSymbol(HIP_SYMBOL(g_prof), z, sizeof(z)); }
-    return e == hipSuccess ? PF_N : -1;
+    return prof_read(out, PF_READ_N, reset);
+}
+extern "C" int cclqr_prof_read_chain_n(unsigned long long* out, int cap, int reset) {      // (up to cap words: PF_ROWS_SKIPPED is word 16)
+    return prof_read(out, cap, reset);
 }
 #endif
 

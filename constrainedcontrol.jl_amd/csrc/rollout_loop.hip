@@ -242,9 +242,7 @@ __global__ __launch_bounds__(64, 2) void rollout_loop_kernel(RolloutArgs a, int 
 
 #ifdef CCLQR_PROFILE
 extern "C" int cclqr_prof_read_loop(unsigned long long* out, int reset) {
-    hipError_t e = hipMemcpyFromSymbol(out, HIP_SYMBOL(g_prof), sizeof(unsigned long long) * PF_N);
-    if (e == hipSuccess && reset) { unsigned long long z[PF_N] = {0}; e = hipMemcpyToSymbol(HIP_SYMBOL(g_prof), z, sizeof(z)); }
-    return e == hipSuccess ? PF_N : -1;
+    return prof_read(out, PF_READ_N, reset);
 }
 #endif
 

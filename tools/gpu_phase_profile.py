@@ -17,14 +17,19 @@ K = np.tile(np.load(gold)["K_first"][None], (999, 1, 1)) if n_links == 16 else r
 mh = capi.MechHandle(t); ctrl = capi.CtrlHandle(mh, [0], K=K, N=1000, zd=zd)
 names = ["control", "forces+knotjac", "eval_body", "eval_joint", "eval_map+norm", "schur_w", "schur_s", "tri_fwd", "tri_bwd", "body_solve", "trial", "accept", "io"]
 _nchild = np.bincount(np.asarray(t.parent)[np.asarray(t.parent) >= 0], minlength=t.nb)
-read = capi.lib().cclqr_prof_read if (_nchild > 1).any() else capi.lib().cclqr_prof_read_chain
-buf = (C.c_ulonglong * 16)()
+buf = (C.c_ulonglong * 32)()
+if (_nchild > 1).any():
+    read = capi.lib().cclqr_prof_read
+else:      # the chain library has a counter behind the 16 words of the two-argument read: it takes the buffer's capacity
+    read = lambda b, reset: capi.lib().cclqr_prof_read_chain_n(b, len(b), reset)
 read(buf, 1)
 t0 = time.time(); zT, _, st = capi.rollout(mh, ctrl, z0, steps); dt = time.time() - t0
-read(buf, 1)
+nread = read(buf, 1)
 v = np.array(list(buf), dtype=np.float64)
 tot = v[:13].sum()
 print("n_links %d inst %d steps %d: %.3fs %s; newton iters/step %.2f evals/step %.2f" % (n_links, ninst, steps, dt, capi.rate_or_refusal(ninst * steps, dt, st), v[13] / v[15], v[14] / v[15]))
 for i, n in enumerate(names):
     print("  %-16s %6.2f%%  %9.0f cycles/step" % (n, 100 * v[i] / tot, v[i] / v[15]))
 print("  total cycles/step (per wave) %.0f" % (tot / v[15]))
+if nread > 16:      # evaluations of a wavefront that built no Schur rows (chain kernel: the known-last full-step trial)
+    print("  evaluations without Schur rows: %.3f per wavefront-step" % (v[16] / v[15]))
