@@ -17,7 +17,7 @@ EXPORTS = ["cclqr_last_error", "cclqr_version", "cclqr_device_count", "cclqr_set
            "cclqr_ctrl_create", "cclqr_ctrl_create_lqr_batch", "cclqr_ctrl_destroy", "cclqr_linearize", "cclqr_linearize_projected", "cclqr_riccati", "cclqr_riccati_tv", "cclqr_riccati_tracking", "cclqr_rollout",
            "cclqr_rollout_dev", "cclqr_rollout_ex", "cclqr_rollout_host_ex", "cclqr_ctrl_reserve_noise", "cclqr_riccati_ex", "cclqr_riccati_tracking_ex",
            "cclqr_release_workspaces", "cclqr_rollout_geometry", "cclqr_rollout_layout_links", "cclqr_ctrl_set_feedforward", "cclqr_abi_layout", "cclqr_rollout_lanes_per_link", "cclqr_rollout_instances_per_wavefront",
-           "cclqr_plants_create", "cclqr_plants_destroy", "cclqr_rollout_plants"]
+           "cclqr_plants_create", "cclqr_plants_destroy", "cclqr_rollout_plants", "cclqr_linearize_plants", "cclqr_ctrl_create_lqr_batch_plants"]
 ABI_VERSION = 202     # include/cclqr.h CCLQR_ABI_VERSION: the structs below mirror that header (verified field by field against cclqr_abi_layout at load time)
 ROLLOUT_NO_ALLOC = 1  # cclqr_rollout_opts.flags: the call may neither allocate nor synchronise (a hipGraph capture is open on the device)
 ROLLOUT_CARRY_STATUS = 4  # ... `status` is read and written: an instance lost in an earlier launch stays frozen, the others merge this launch's result into it
@@ -247,8 +247,9 @@ class CtrlHandle:
 class BatchLqrHandle:
     """cclqr_ctrl* built by cclqr_ctrl_create_lqr_batch: one LQR per setpoint (linearsystem + dlqr + controller tables), gains device-resident"""
 
-    def __init__(self, mech, zd, ctrl_joint, Q, R, N, Fd=None, tol=1e-5, infinite_horizon=False):
-        """infinite_horizon: LQR{T,Inf} -- N = Ntemp = ceil(10/Δt) (lqr.jl:26), only Ku[1] per setpoint is kept"""
+    def __init__(self, mech, zd, ctrl_joint, Q, R, N, Fd=None, tol=1e-5, infinite_horizon=False, plants=None, first_plant=0):
+        """infinite_horizon: LQR{T,Inf} -- N = Ntemp = ceil(10/Δt) (lqr.jl:26), only Ku[1] per setpoint is kept.
+        plants: a PlantsHandle (cclqr_ctrl_create_lqr_batch_plants) -- table k is designed on the plant with global index first_plant + k"""
         nb = mech.tables.nb
         zd = f64(zd).reshape(-1, nb, 13)
         n = zd.shape[0]
@@ -259,9 +260,14 @@ class BatchLqrHandle:
         self.kbreak = np.zeros(n, dtype=np.int32)
         self.mu, self.N, self.nsp, self.n_ctrl = mu, (0 if infinite_horizon else int(N)), 1, n
         self._arrs = [zd, cj, Fd, Q, R]
+        self.plants, self.first_plant = plants, int(first_plant)      # (the plants it was designed on: kept for error messages only)
         self.ptr = C.c_void_p()
-        check(lib().cclqr_ctrl_create_lqr_batch(mech.ptr, C.c_int32(n), _d(zd), C.c_int32(mu), _i(cj), _d(Fd), _d(Q), _d(R), C.c_int32(int(N)),
-                                                C.c_int32(1 if infinite_horizon else 0), C.c_double(float(tol)), _i(self.kbreak), C.byref(self.ptr)))
+        tail = (C.c_int32(n), _d(zd), C.c_int32(mu), _i(cj), _d(Fd), _d(Q), _d(R), C.c_int32(int(N)), C.c_int32(1 if infinite_horizon else 0), C.c_double(float(tol)),
+                _i(self.kbreak), C.byref(self.ptr))
+        if plants is None:
+            check(lib().cclqr_ctrl_create_lqr_batch(mech.ptr, *tail))
+        else:
+            check(lib().cclqr_ctrl_create_lqr_batch_plants(mech.ptr, plants.ptr, C.c_int64(int(first_plant)), *tail))
 
     def close(self):
         if self.ptr:
@@ -371,8 +377,9 @@ def rollout_dev(mech, ctrl, n_inst, steps, k0, z0_ptr, lam_ptr, noise_ptr, noise
                                  vp(noise_ptr), C.c_int64(noise_stride), vp(traj_ptr), vp(zT_ptr), vp(status_ptr), C.byref(o), vp(stream)))
 
 
-def linearize(mech, zd, ctrl_joint, Fd=None):
-    """batched linearsystem: zd [nk][nb][13] -> A [nk][mx][mx], Bu, Bl, G"""
+def linearize(mech, zd, ctrl_joint, Fd=None, plants=None, first_plant=0):
+    """batched linearsystem: zd [nk][nb][13] -> A [nk][mx][mx], Bu, Bl, G.  plants: a PlantsHandle (cclqr_linearize_plants) -- knot k is linearised on the
+    plant with global index first_plant + k"""
     t = mech.tables
     zd = f64(zd).reshape(-1, t.nb, 13)
     nk = zd.shape[0]
@@ -380,7 +387,11 @@ def linearize(mech, zd, ctrl_joint, Fd=None):
     mu, mx, ml = len(cj), 12 * t.nb, 5 * t.ne
     Fd = f64(np.zeros((nk, mu)) if Fd is None else Fd).reshape(nk, mu)
     A, Bu, Bl, G = np.zeros((nk, mx, mx)), np.zeros((nk, mx, mu)), np.zeros((nk, mx, ml)), np.zeros((nk, ml, mx))
-    check(lib().cclqr_linearize(mech.ptr, C.c_int32(nk), _d(zd), C.c_int32(mu), _i(cj), _d(Fd), _d(A), _d(Bu), _d(Bl), _d(G)))
+    tail = (C.c_int32(nk), _d(zd), C.c_int32(mu), _i(cj), _d(Fd), _d(A), _d(Bu), _d(Bl), _d(G))
+    if plants is None:
+        check(lib().cclqr_linearize(mech.ptr, *tail))
+    else:
+        check(lib().cclqr_linearize_plants(mech.ptr, plants.ptr, C.c_int64(int(first_plant)), *tail))
     return A, Bu, Bl, G
 
 

@@ -223,20 +223,35 @@ __global__ void k_rows_to_link_order_kernel(double* K, long long nrows, long lon
     for (int e = threadIdx.x; e < 12 * nb; e += blockDim.x) { const int l = e / 12; p[e] = row[12 * M->perm[l] + (e - 12 * l)]; }
 }
 
-extern "C" int cclqr_ctrl_create_lqr_batch(const cclqr_mech* m, int32_t n_ctrl, const double* zd, int32_t mu, const int32_t* ctrl_joint,
-                                           const double* Fd, const double* Q, const double* R, int32_t N, int32_t infinite_horizon, double tol,
-                                           int32_t* kbreak, cclqr_ctrl** out) {
+// cclqr_linearize_plants / cclqr_ctrl_create_lqr_batch_plants: knot k of the launch must find its plant, the one with global index first_plant + k (no device work)
+static int plants_check_range(const cclqr_mech* m, const cclqr_plants* plants, int64_t first_plant, int64_t nk) {
+    if (!plants) return CCLQR_OK;
+    if (m->host.loop) return fail(CCLQR_EUNSUPPORTED, "per-instance plants are for forests of chains and branching trees (closed-loop mechanisms run their own plant)");
+    if (plants->mech != m) return fail(CCLQR_EINVAL, "the plants were created for another mechanism");
+    const int64_t lo = first_plant - plants->first_index;
+    if (nk > 0 && (lo < 0 || lo + nk > plants->n_plant))
+        return fail(CCLQR_EINVAL, "plants " + std::to_string(first_plant) + " .. " + std::to_string(first_plant + nk - 1) + " of the call are not all among the plants " +
+                                  std::to_string(plants->first_index) + " .. " + std::to_string(plants->first_index + plants->n_plant - 1));
+    return CCLQR_OK;
+}
+
+extern "C" int cclqr_ctrl_create_lqr_batch_plants(const cclqr_mech* m, const cclqr_plants* plants, int64_t first_plant, int32_t n_ctrl, const double* zd, int32_t mu,
+                                                  const int32_t* ctrl_joint, const double* Fd, const double* Q, const double* R, int32_t N, int32_t infinite_horizon,
+                                                  double tol, int32_t* kbreak, cclqr_ctrl** out) {
     const bool inf = infinite_horizon != 0;
     if (!m || !zd || !Q || !out || (mu > 0 && (!ctrl_joint || !R))) return fail(CCLQR_EINVAL, "null argument");
     { int rc = check_device(m); if (rc != CCLQR_OK) return rc; }
     if (m->host.loop) return fail(CCLQR_EUNSUPPORTED, "batched LQR construction is for tree mechanisms (closed loops: cclqr_linearize_projected)");
     if (n_ctrl < 1 || N < 2 || mu < 1 || mu > m->nb) return fail(CCLQR_EINVAL, "bad sizes");
+    { int rc = plants_check_range(m, plants, first_plant, n_ctrl); if (rc != CCLQR_OK) return rc; }
     const int nb = m->nb;
     const size_t nz = 13 * (size_t)nb, mx = 12 * (size_t)nb, ml = 5 * (size_t)nb, np = (size_t)n_ctrl;
     if (!linearize_fits_lds(m)) return fail(CCLQR_EUNSUPPORTED, "instance does not fit LDS");
     LinArgs la;
     memset(&la, 0, sizeof(la));
     la.M = m->dev; la.nk = n_ctrl; la.mu = mu;
+    la.plants = plants ? plants->dev : nullptr;
+    la.plant_off = plants ? first_plant - plants->first_index : 0;
     cclqr_ctrl* c = new cclqr_ctrl();
     memset(c, 0, sizeof(*c));
     c->nb = nb;
@@ -318,6 +333,12 @@ extern "C" int cclqr_ctrl_create_lqr_batch(const cclqr_mech* m, int32_t n_ctrl, 
     }
     *out = c;
     return CCLQR_OK;
+}
+
+extern "C" int cclqr_ctrl_create_lqr_batch(const cclqr_mech* m, int32_t n_ctrl, const double* zd, int32_t mu, const int32_t* ctrl_joint,
+                                           const double* Fd, const double* Q, const double* R, int32_t N, int32_t infinite_horizon, double tol,
+                                           int32_t* kbreak, cclqr_ctrl** out) {
+    return cclqr_ctrl_create_lqr_batch_plants(m, nullptr, 0, n_ctrl, zd, mu, ctrl_joint, Fd, Q, R, N, infinite_horizon, tol, kbreak, out);
 }
 
 extern "C" int cclqr_ctrl_destroy(cclqr_ctrl* c) {
@@ -584,6 +605,11 @@ extern "C" int cclqr_rollout(const cclqr_mech* m, const cclqr_ctrl* c, int64_t n
 
 extern "C" int cclqr_linearize(const cclqr_mech* m, int32_t nk, const double* zd, int32_t mu, const int32_t* ctrl_joint, const double* Fd,
                                double* A, double* Bu, double* Bl, double* G) {
+    return cclqr_linearize_plants(m, nullptr, 0, nk, zd, mu, ctrl_joint, Fd, A, Bu, Bl, G);
+}
+
+extern "C" int cclqr_linearize_plants(const cclqr_mech* m, const cclqr_plants* plants, int64_t first_plant, int32_t nk, const double* zd, int32_t mu,
+                                      const int32_t* ctrl_joint, const double* Fd, double* A, double* Bu, double* Bl, double* G) {
     if (!m || !zd || !A || !Bl || !G || (mu > 0 && (!ctrl_joint || !Bu))) return fail(CCLQR_EINVAL, "null argument");
     { int rc = check_device(m); if (rc != CCLQR_OK) return rc; }
     // a closed-loop mechanism has its own tables (bodies and joints in the caller's order, ml = 5 rows per joint incl. the two null rows of a
@@ -591,12 +617,15 @@ extern "C" int cclqr_linearize(const cclqr_mech* m, int32_t nk, const double* zd
     const bool loop = m->host.loop != 0;
     const int nb = m->nb, nj = loop ? m->nj : nb;
     if (nk < 0 || mu < 0 || mu > nj) return fail(CCLQR_EINVAL, "Missmatched length for constraints");
+    { int rc = plants_check_range(m, plants, first_plant, nk); if (rc != CCLQR_OK) return rc; }
     if (nk == 0) return CCLQR_OK;
     const size_t nz = 13 * (size_t)nb, mx = 12 * (size_t)nb, ml = 5 * (size_t)nj;
     if (!linearize_fits_lds(m)) return fail(CCLQR_EUNSUPPORTED, "instance does not fit LDS");
     LinArgs a;
     memset(&a, 0, sizeof(a));
     a.M = m->dev; a.nk = nk; a.mu = mu;
+    a.plants = plants ? plants->dev : nullptr;
+    a.plant_off = plants ? first_plant - plants->first_index : 0;
     for (int i = 0; i < mu; i++) {
         if (ctrl_joint[i] < 0 || ctrl_joint[i] >= nj) return fail(CCLQR_EINVAL, "controlled joint out of range");
         a.cj[i] = loop ? ctrl_joint[i] : m->link_of_joint[ctrl_joint[i]];

@@ -253,10 +253,14 @@ HD double philox_normal(unsigned key0, unsigned long long instance, int k) {
 }
 
 // ------------------------------------------------------------------ link constants -> lane registers
-HD void lane_load_consts(LaneRegs& r, const MechDev* M, int l) {
-    r.m = M->m[l];
-    for (int i = 0; i < 9; i++) r.J[i] = M->J[l][i];
-    for (int i = 0; i < 3; i++) { r.p1[i] = M->p1[l][i]; r.p2[i] = M->p2[l][i]; r.axis[i] = M->axis[l][i]; }
+// P: the records [nb] of the plant the lane's knot is evaluated on (link order), nullptr = the mechanism's own (M->rec): m, J, p1, p2 come from the link's
+// record, everything else (the topology) from the mechanism -- the scheme of cclqr_chain.h link_load_consts_rec.  ONE code path for both, so a plant table
+// that repeats the mechanism's numbers gives the same bits.
+HD void lane_load_consts(LaneRegs& r, const MechDev* M, int l, const PlantRec* P = nullptr) {
+    const PlantRec* rec = (P ? P : M->rec) + l;
+    r.m = rec->m;
+    for (int i = 0; i < 9; i++) r.J[i] = rec->J[i];
+    for (int i = 0; i < 3; i++) { r.p1[i] = rec->p1[i]; r.p2[i] = rec->p2[i]; r.axis[i] = M->axis[l][i]; }
     for (int i = 0; i < 4; i++) r.qoc[i] = M->qoc[l][i];
     for (int i = 0; i < 5; i++)
         for (int j = 0; j < 3; j++) r.sel[i][j] = M->sel[l][i][j];
@@ -434,9 +438,11 @@ HD double ph_gain_partial(int t, int G, int nb, const Lay& Y, const double* L, c
 }
 
 // F1: joint inputs -> force/torque on the owned body, per-step invariants, solution guess (SURVEY 8a-bis 'Joint input')
+// P: the plant's records as in lane_load_consts (a prismatic child joint's vertex p1 is read from the child link's record)
 template <bool TREE = false>
-HD void ph_forces(int t, int nb, const Lay& Y, double* L, LaneRegs& r, const MechDev* M, bool owner = true) {
+HD void ph_forces(int t, int nb, const Lay& Y, double* L, LaneRegs& r, const MechDev* M, bool owner = true, const PlantRec* P = nullptr) {
     if (t >= nb) return;
+    if (!P) P = M->rec;
     const double dt = M->dt;
     const double* z = L + Y.Z + 13 * t;
     double F[3] = {0, 0, 0}, tau[3] = {0, 0, 0};
@@ -458,7 +464,7 @@ HD void ph_forces(int t, int nb, const Lay& Y, double* L, LaneRegs& r, const Mec
             double f[3] = {M->axis[c][0] * uc, M->axis[c][1] * uc, M->axis[c][2] * uc};
             if (M->type[c] == 1) {
                 double fw[3], cr[3];
-                mv3(Rb, f, fw); cross3(M->p1[c], f, cr);
+                mv3(Rb, f, fw); cross3(P[c].p1, f, cr);
                 for (int i = 0; i < 3; i++) { F[i] -= fw[i]; tau[i] -= cr[i]; }
             } else for (int i = 0; i < 3; i++) tau[i] -= f[i];
         }

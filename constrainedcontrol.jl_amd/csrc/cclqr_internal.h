@@ -111,6 +111,8 @@ struct LinArgs {
     const double* Fd;        // [nk][mu]
     double *A, *Bu, *Bl, *G; // [nk][...] internal link order
     int* status;             // [nk]
+    const PlantRec* plants;  // per-knot plants (cclqr_linearize_plants): records [n_plant][nb] in link order, or nullptr = every knot on the mechanism's own plant
+    long long plant_off;     // knot k is linearised on row plant_off + k of the table (checked against [0, n_plant) on the host); chains and trees only
 };
 // the model with the multipliers exogenous at the knots a.zd, for any mechanism (linearize.hip): linearize_kernel for chains and trees; closed
 // loops are handed on to launch_linearize_loop (rollout_loop.hip, linearize_loop_kernel)

@@ -243,8 +243,10 @@ HD void body_col1(double* M, int ld, int r0, int col, const double* ft, const do
 }
 
 // L3: body t writes its rows of Bl (columns of its own joint and of its child joint), Bu and joint t its rows of G
-HD void ph_lin_rows_B(int t, int nb, const Lay& Y, const double* L, const LaneRegs& r, const MechDev* M, const int* cj, const LinOut& O) {
+// P: the records of the knot's plant (cclqr_dev.h lane_load_consts), nullptr = the mechanism's own: the vertex p1 of a controlled prismatic child joint
+HD void ph_lin_rows_B(int t, int nb, const Lay& Y, const double* L, const LaneRegs& r, const MechDev* M, const int* cj, const LinOut& O, const PlantRec* P = nullptr) {
     if (t >= nb) return;
+    if (!P) P = M->rec;
     const double dt = M->dt, dtm = dt / r.m;
     const double* Dinv = L + Y.DINV + 9 * t;
     double N[9];
@@ -280,7 +282,7 @@ HD void ph_lin_rows_B(int t, int nb, const Lay& Y, const double* L, const LaneRe
             rotmat(L + Y.Z + 13 * t + 3, Rb);
             const double* ax = M->axis[c];
             mv3(Rb, ax, Raa);
-            if (M->type[c] == 1) { double cr[3]; cross3(M->p1[c], ax, cr); for (int q = 0; q < 3; q++) { ft[q] = -Raa[q]; fr[q] = -2.0 * cr[q]; } }
+            if (M->type[c] == 1) { double cr[3]; cross3(P[c].p1, ax, cr); for (int q = 0; q < 3; q++) { ft[q] = -Raa[q]; fr[q] = -2.0 * cr[q]; } }
             else for (int q = 0; q < 3; q++) fr[q] = -2.0 * ax[q];
             hit = true;
         }

@@ -31,7 +31,11 @@ __global__ __launch_bounds__(64) void linearize_kernel(LinArgs a) {
 
     LaneRegs r;
     const int NL = newton_level_groups(G, nb), lg = t / nb, tl = t - lg * nb;   // lane groups of the level-parallel line search
-    lane_load_consts(r, M, lg < NL ? tl : 0);
+    // the knot's plant, resolved once: the mechanism's own records, or -- a wavefront-uniform branch -- the knot's row of the launch's table
+    // (rollout_chain.hip reads its instances' plants the same way).  Every lane group of the level-parallel line search loads the same knot's plant.
+    const PlantRec* plant = M->rec;
+    if (a.plants) plant = a.plants + (size_t)(a.plant_off + knot) * nb;
+    lane_load_consts(r, M, lg < NL ? tl : 0, plant);
     for (int e = t; e < nz; e += G) { int l = e / 13, c = e - 13 * l; L[Y.Z + e] = a.zd[(size_t)knot * nz + M->perm[l] * 13 + c]; }
     for (int e = t; e < 5 * nb; e += G) L[Y.LAM + e] = 0.0;
     for (int e = t; e < nb; e += G) L[Y.UJ + e] = 0.0;
@@ -39,7 +43,7 @@ __global__ __launch_bounds__(64) void linearize_kernel(LinArgs a) {
     if (t == 0)
         for (int i = 0; i < mu; i++) L[Y.UJ + a.cj[i]] += a.Fd ? a.Fd[(size_t)knot * mu + i] : 0.0;
     __syncthreads();
-    if (lg < NL) ph_forces<TREE>(tl, nb, Y, L, r, M, lg == 0);
+    if (lg < NL) ph_forces<TREE>(tl, nb, Y, L, r, M, lg == 0, plant);
     ph_knot_jac(t, nb, Y, L, r);
     __syncthreads();
     if (TREE) ph_force_map_tree(t, G, nb, Y, L, M);
@@ -58,7 +62,7 @@ __global__ __launch_bounds__(64) void linearize_kernel(LinArgs a) {
     ph_lin_joint(t, nb, Y, JB, L, r);
     __syncthreads();
     ph_lin_rows_A(t, nb, Y, JB, L, r, M, O);
-    ph_lin_rows_B(t, nb, Y, L, r, M, a.cj, O);
+    ph_lin_rows_B(t, nb, Y, L, r, M, a.cj, O, plant);
     if (t == 0 && a.status) a.status[knot] = done ? its : -its;
 }
 

@@ -3,6 +3,7 @@ meaning; the arithmetic (linearsystem, dlqr, simulate!) runs in HIP through the 
 
     LQR(mechanism, bodyids, eqcids, Q, R, horizon; xd, vd, qd, ωd, Fτd)            src/control/lqr.jl:49-66
     LQR(A, Bu, Bλ, G, Q, R, horizon, eqcids, xd, vd, qd, ωd, Fτd, Δt)              src/control/lqr.jl:17-47
+    PlantLQR(mechanism, plants, bodyids, eqcids, Q, R, horizon, zd; Fτd)           the first of these once per plant of a PlantBatch, in one call
     TrackingLQR(mechanism, storage, Fτ, eqcids, Q, R)                                src/control/lqr_tracking.jl:17-43
     simulate!(mechanism, tend | storage, controller; record)                         e.g. examples/lqr_cartpole.jl:44
     Storage{T}(steps, Nb)                                                            examples/trackingLQR_triple_cartpole.jl:50-51
@@ -49,6 +50,28 @@ def _device_mech(mechanism):
     return h
 
 
+def _body_order(bodyids, nb):
+    """state blocks follow the order of `bodyids`, the device works in mechanism body order: position in `bodyids` of every body of the mechanism"""
+    order = [int(b) - 1 for b in bodyids]
+    if sorted(order) != list(range(nb)):
+        raise ValueError("bodyids must name every body exactly once")
+    return np.argsort(order)
+
+
+def _weights_and_horizon(Q, R, horizon, Δt):
+    """the head of LQR(A, Bu, Bλ, G, Q, R, horizon, ...) (lqr.jl:18-27): Δt-scaled block-diagonal weights, the gated horizon N in steps (math.inf: LQR{T,Inf})
+    and the number of knots Ntemp the recursion runs over"""
+    Qm = _blockdiag(Q) * Δt                                 # lqr.jl:18
+    Rm = _blockdiag(R) * Δt                                 # lqr.jl:19
+    N = horizon / Δt                                        # lqr.jl:21
+    if N < math.inf:
+        N = int(math.ceil(horizon / Δt))                    # lqr.jl:23
+        Ntemp = N
+    else:
+        Ntemp = int(math.ceil(10 / Δt))                     # lqr.jl:26: 10 s as maximal horizon for Inf
+    return Qm, Rm, N, Ntemp
+
+
 class Controller:
     """abstract type owned by ConstrainedDynamics (lqr.jl:3 `<: Controller`)"""
 
@@ -93,11 +116,7 @@ class LQR(Controller):
         # lqr.jl:59-60
         assert len(bodyids) == len(Q) == len(xd) == len(vd) == len(qd) == len(ωd) == nb, "Missmatched length for bodies"
         assert len(eqcids) == len(R) == len(Fτd), "Missmatched length for constraints"
-        order = [int(b) - 1 for b in bodyids]
-        if sorted(order) != list(range(nb)):
-            raise ValueError("bodyids must name every body exactly once")
-        # state blocks follow the order of `bodyids`; the device works in mechanism body order
-        inv = np.argsort(order)
+        inv = _body_order(bodyids, nb)
         Q = [np.asarray(Q[i], dtype=np.float64) for i in inv]
         xd, vd, qd, ωd = ([a[i] for i in inv] for a in (xd, vd, qd, ωd))
         self.mechanism = mechanism
@@ -124,14 +143,7 @@ class LQR(Controller):
 
     def _finish(self, A, Bu, Bl, G, Q, R, horizon, Δt):
         """LQR(A, Bu, Bλ, G, Q, R, horizon, eqcids, xd, ..., Δt)   lqr.jl:17-47"""
-        self.Q = _blockdiag(Q) * Δt                         # lqr.jl:18
-        self.R = _blockdiag(R) * Δt                         # lqr.jl:19
-        N = horizon / Δt                                    # lqr.jl:21
-        if N < math.inf:
-            N = int(math.ceil(horizon / Δt))                # lqr.jl:23
-            Ntemp = N
-        else:
-            Ntemp = int(math.ceil(10 / Δt))                 # lqr.jl:26: 10 s as maximal horizon for Inf
+        self.Q, self.R, N, Ntemp = _weights_and_horizon(Q, R, horizon, Δt)
         if G.shape[0] == 0 and N == math.inf and not getattr(self, "projected", False):
             # lqr.jl:33 calls dlqr(A,Bu,Q,R,N) which binds N=Inf to the Δt method of util.jl:50 — a defect, not reproduced (SURVEY 8a-ter)
             raise ValueError("unconstrained infinite-horizon LQR is not reachable in the reference (lqr.jl:33)")
@@ -168,6 +180,82 @@ class LQR(Controller):
 
     def _ctrl_handle(self, dev, fric=None, noise_scale=0.0, noise_seed=None):
         return _capi.CtrlHandle(dev, self.ctrl_joints, K=self.K, N=self.N, zd=self.zd, Fd=self.Fd, fric=fric, noise_scale=noise_scale, noise_seed=noise_seed)
+
+
+class _BorrowedCtrl:
+    """what a controller that owns its device tables hands simulate: the same cclqr_ctrl*, and a close() that leaves the tables with their owner"""
+
+    def __init__(self, handle):
+        self.ptr, self.owner = handle.ptr, handle
+
+    def close(self):
+        pass
+
+
+class PlantLQR(Controller):
+    """One LQR per plant of a PlantBatch, designed in one call: for every plant k, LQR(mechanism_k, bodyids, eqcids, Q, R, horizon; xd, vd, qd, ωd, Fτd)
+    (lqr.jl:49-66) where mechanism_k is the mechanism rebuilt with plant k's masses, inertias and joint vertices -- one batched linearsystem (lqr.jl:63) and one
+    batched dlqr (lqr.jl:141-184) on the device, the gains never leaving it (cclqr_ctrl_create_lqr_batch_plants).
+
+    Q, R, horizon: as for LQR (per-body 12 x 12 and per-constraint 1 x 1 blocks in the order of bodyids / eqcids, scaled by Δt; math.inf = LQR{T,Inf}).
+    zd [n][nb][13]: the setpoint of every plant in the mechanism's body order, on that plant's own constraint manifold (joint_position_states(mech, θ,
+    plants=plants)); Fτd [n][mu]: the caller's holding inputs (default 0).  first_plant: global index of the plant zd[0] belongs to (default
+    plants.first_index).  kbreak [n], converged [n]: per plant, as LQR's.
+    simulate(mech, steps, PlantLQR, z0=, plants=, first_instance=): instance i reads table first_instance + i and runs on plant first_instance + i."""
+
+    def __init__(self, mechanism, plants, bodyids, eqcids, Q, R, horizon, zd, Fτd=None, first_plant=None, controlfunction=None, tol=1e-5):
+        if controlfunction is not None:
+            raise ValueError("PlantLQR carries no controlfunction: its gains stay on the device (one LQR per plant with a closure: build an LQR per plant)")
+        if not isinstance(mechanism, Mechanism):
+            raise TypeError("PlantLQR(mechanism, plants, bodyids, eqcids, Q, R, horizon, zd; ...)")
+        if plants.mechanism is not mechanism:
+            raise ValueError("the PlantBatch was made for another mechanism")
+        nb = len(mechanism.bodies)
+        zd = np.ascontiguousarray(zd, dtype=np.float64)
+        if zd.ndim != 3 or zd.shape[1:] != (nb, 13):
+            raise ValueError("zd must be [n][nb][13] = [n][%d][13], one setpoint per plant (got %s)" % (nb, zd.shape))
+        self.first_plant = plants.first_index if first_plant is None else int(first_plant)
+        n = zd.shape[0]
+        if n < 1:
+            raise ValueError("zd must hold at least one setpoint")
+        plants.rows_for(self.first_plant, n)      # every setpoint must find its plant
+        assert len(bodyids) == len(Q) == nb, "Missmatched length for bodies"                                              # lqr.jl:59
+        assert len(eqcids) == len(R), "Missmatched length for constraints"                                                # lqr.jl:60
+        mu = len(eqcids)
+        Fd = np.zeros((n, mu)) if Fτd is None else np.ascontiguousarray(Fτd, dtype=np.float64).reshape(-1, mu)
+        if Fd.shape[0] != n:
+            raise ValueError("Fτd must be [n][mu] = [%d][%d], one holding input per plant and controlled constraint" % (n, mu))
+        inv = _body_order(bodyids, nb)
+        self.mechanism, self.plants, self.n_plant = mechanism, plants, n
+        self.eqcids = [int(e) for e in eqcids]
+        self.ctrl_joints = [mechanism.joint_index(e) for e in self.eqcids]
+        self.controlfunction = None
+        self.zd, self.Fd = zd, Fd
+        self.Q, self.R, N, Ntemp = _weights_and_horizon([np.asarray(Q[i], dtype=np.float64) for i in inv], [np.asarray(r, dtype=np.float64) for r in R], horizon,
+                                                        mechanism.Δt)
+        self.N = 0 if N == math.inf else N
+        self.horizon_steps, self.NK = N, 12 * nb
+        dev = _device_mech(mechanism)
+        self._handle = _capi.BatchLqrHandle(dev, zd, self.ctrl_joints, self.Q, self.R, Ntemp, Fd=Fd, tol=tol, infinite_horizon=N == math.inf,
+                                            plants=plants.handle(dev), first_plant=self.first_plant)
+        self.kbreak = self._handle.kbreak
+        # LQR{T,Inf} (lqr.jl:40-42): converged when Ku[1] == Ku[2], i.e. when the recursion met its tolerance and back-filled the rest (kbreak > 1)
+        self.converged = np.ones(n, dtype=bool) if N < math.inf else ((self.kbreak > 1) | (Ntemp < 3))
+        if not self.converged.all():
+            print("[ Info: Riccati recursion did not converge.")      # lqr.jl:41
+
+    def _ctrl_handle(self, dev, fric=None, noise_scale=0.0, noise_seed=None):
+        if fric is not None or noise_scale or noise_seed is not None:
+            raise ValueError("PlantLQR carries neither joint friction nor noise: the batched constructor builds the plain LQR law")
+        if self.first_plant != 0:
+            raise ValueError("a rollout reads controller table and plant by the global instance index: a PlantLQR that is rolled out starts at plant 0 "
+                             "(this one at plant %d)" % self.first_plant)
+        if self._handle.plants.mech is not dev or not self._handle.ptr:
+            raise ValueError("the PlantLQR was designed on another device handle of the mechanism")
+        return _BorrowedCtrl(self._handle)
+
+    def close(self):
+        self._handle.close()
 
 
 class Storage:

@@ -36,7 +36,9 @@ extern "C" {
  * cclqr_ctrl_set_feedforward and cclqr_abi_layout.  A shim checks cclqr_version() == the version it was written against AND, through
  * cclqr_abi_layout(), the sizeof / offsetof of every struct it mirrors.
  * 202 (additive over 201: no struct changed): per-instance plants -- the opaque cclqr_plants with cclqr_plants_create / cclqr_plants_destroy, and the
- * launch on them, cclqr_rollout_plants. */
+ * launch on them, cclqr_rollout_plants.
+ * Still 202 (additive, no struct changed; tests/test_plants_host.py pins the number): one controller per plant -- cclqr_linearize_plants and
+ * cclqr_ctrl_create_lqr_batch_plants.  A shim that needs them looks the symbols up: a 202 library built before them lacks them. */
 #define CCLQR_ABI_VERSION 202
 
 #define CCLQR_REVOLUTE 0      /* EqualityConstraint(Revolute(a, b, axis; p1, p2, qoffset)),  examples/lqr_cartpole.jl:26 */
@@ -309,6 +311,27 @@ int cclqr_plants_destroy(cclqr_plants *p);
 int cclqr_rollout_plants(const cclqr_mech *m, const cclqr_plants *plants, const cclqr_ctrl *c, int64_t n_inst, int32_t steps, int32_t k0, const double *z0_dev,
                          double *lam_dev, const double *noise_dev, int64_t noise_stride, double *traj_dev, double *zT_dev, int32_t *status_dev,
                          const cclqr_rollout_opts *opts, void *stream);
+
+/* cclqr_linearize on per-instance plants -- linearsystem(mechanism_k, xd, vd, qd, ωd, Fτd, bodyids, eqcids) (src/control/lqr.jl:63) where mechanism_k is the
+ * `Mechanism(...)` of examples/lqr_cartpole.jl:32 rebuilt with plant k's `Box(...)` / `Revolute(...; p1, p2)` numbers (:21-26).  Knot k is linearised on the plant
+ * with GLOBAL index first_plant + k, i.e. row first_plant + k - first_index of the handle; the topology, Δt and g are the mechanism's.  zd[k] must lie on plant k's
+ * own constraint manifold, Fd[k] is the caller's holding input for plant k.  Everything else as cclqr_linearize: host pointers, the caller's body / joint order.
+ * plants == NULL: exactly cclqr_linearize.  CCLQR_EINVAL, before anything is launched, when the plants were created for another mechanism or the plants
+ * first_plant .. first_plant + nk - 1 are not all in the table; CCLQR_EUNSUPPORTED for plants on a closed-loop mechanism. */
+int cclqr_linearize_plants(const cclqr_mech *m, const cclqr_plants *plants, int64_t first_plant, int32_t nk, const double *zd, int32_t mu,
+                           const int32_t *ctrl_joint, const double *Fd, double *A, double *Bu, double *Bl, double *G);
+
+/* cclqr_ctrl_create_lqr_batch with one plant per controller table -- for every k, LQR(mechanism_k, bodyids, eqcids, Q, R, horizon; xd, vd, qd, ωd, Fτd)
+ * (src/control/lqr.jl:49-66): linearsystem at lqr.jl:63 and dlqr at lqr.jl:141-184, evaluated on the `Mechanism(...)` of examples/lqr_cartpole.jl:32 rebuilt with plant
+ * k's `Box(...)` / `Revolute(...; p1, p2)` numbers (:21-26).  Table k is designed on the plant with GLOBAL index first_plant + k (row first_plant + k - first_index of
+ * the handle).  A rollout reads the controller table AND (cclqr_rollout_plants) the plant of an instance by its global index, cclqr_rollout_opts.first_instance + i:
+ * with first_plant = 0 instance n runs on plant n under the gains designed for plant n.  (first_plant > 0 designs for a slice of a larger table; its tables are
+ * still numbered from 0.)  kbreak, infinite_horizon, the per-table zero pad and
+ * the error codes are cclqr_ctrl_create_lqr_batch's.  plants == NULL: exactly cclqr_ctrl_create_lqr_batch.  The refusals of cclqr_linearize_plants apply, before
+ * anything is launched or allocated on the device. */
+int cclqr_ctrl_create_lqr_batch_plants(const cclqr_mech *m, const cclqr_plants *plants, int64_t first_plant, int32_t n_ctrl, const double *zd, int32_t mu,
+                                       const int32_t *ctrl_joint, const double *Fd, const double *Q, const double *R, int32_t N, int32_t infinite_horizon,
+                                       double tol, int32_t *kbreak, cclqr_ctrl **out);
 
 /* cclqr_rollout (HOST pointers) with options: first_instance and newton_mode apply, the device-buffer fields must be NULL. */
 int cclqr_rollout_host_ex(const cclqr_mech *m, const cclqr_ctrl *c, int64_t n_inst, int32_t steps, int32_t k0, const double *z0,

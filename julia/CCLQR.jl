@@ -330,6 +330,30 @@ function rollout_plants_dev!(h::MechHandle, p::PlantsHandle, c::CtrlHandle, n::I
                 h.ptr, p.ptr, c.ptr, n, steps, k0, z0, lam, noise, noise_stride, traj, zT, status, o, stream))
 end
 
+"linearsystem (lqr.jl:63) of knot k on plant first_plant + k of `p` (cclqr_linearize_plants): zd is 13 x Nb x nk on the plants' own constraint manifolds, Fd is
+ mu x nk.  Returns the row-major buffers of the nk models (cmat reads one)."
+function linearsystem_plants(h::MechHandle, p::PlantsHandle, nk::Integer, zd::Array{Float64}, ctrl::Vector{Int32}, Fd::Array{Float64}; first_plant = 0)
+    nb = h.nb; mx, ml, mu = 12nb, 5nb, length(ctrl)
+    A = zeros(nk * mx * mx); Bu = zeros(nk * mx * max(mu, 1)); Bl = zeros(nk * mx * ml); G = zeros(nk * ml * mx)
+    check(ccall((:cclqr_linearize_plants, lib), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int32, Ptr{Float64}, Int32, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                h.ptr, p.ptr, first_plant, nk, zd, mu, ctrl, Fd, A, Bu, Bl, G))
+    A, Bu, Bl, G
+end
+
+"One LQR per plant, built and kept on the device (cclqr_ctrl_create_lqr_batch_plants): lqr_batch with table k designed on plant first_plant + k of `p` -- linearsystem
+ (lqr.jl:63) and dlqr (lqr.jl:141-184) on the mechanism rebuilt with that plant's numbers.  Fd (mu x n, or nothing) holds the caller's holding inputs."
+function lqr_batch_plants(h::MechHandle, p::PlantsHandle, n::Int, zd::Array{Float64}, ctrl_joint::Vector{Int32}, Q::Vector{Float64}, R::Vector{Float64}, N::Int;
+                          Fd = nothing, first_plant = 0, tol = 1e-5, infinite_horizon = false)
+    out = Ref{Ptr{Cvoid}}(C_NULL); kb = zeros(Int32, n)
+    fd = Fd === nothing ? Ptr{Float64}(C_NULL) : pointer(Fd)
+    GC.@preserve Fd check(ccall((:cclqr_ctrl_create_lqr_batch_plants, lib), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int32, Ptr{Float64}, Int32, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int32, Int32, Float64, Ptr{Int32},
+                 Ref{Ptr{Cvoid}}),
+                h.ptr, p.ptr, first_plant, Int32(n), zd, Int32(length(ctrl_joint)), ctrl_joint, fd, Q, R, Int32(N), Int32(infinite_horizon ? 1 : 0), tol, kb, out))
+    return out[], kb
+end
+
 "Size the controller handle's Philox workspace before step-per-launch rollouts are captured into a hipGraph (cclqr_ctrl_reserve_noise)."
 reserve_noise!(c::CtrlHandle, n::Integer, steps::Integer) = check(ccall((:cclqr_ctrl_reserve_noise, lib), Cint, (Ptr{Cvoid}, Int64, Int32), c.ptr, n, steps))
 
