@@ -17,7 +17,8 @@ EXPORTS = ["cclqr_last_error", "cclqr_version", "cclqr_device_count", "cclqr_set
            "cclqr_ctrl_create", "cclqr_ctrl_create_lqr_batch", "cclqr_ctrl_destroy", "cclqr_linearize", "cclqr_linearize_projected", "cclqr_riccati", "cclqr_riccati_tv", "cclqr_riccati_tracking", "cclqr_rollout",
            "cclqr_rollout_dev", "cclqr_rollout_ex", "cclqr_rollout_host_ex", "cclqr_ctrl_reserve_noise", "cclqr_riccati_ex", "cclqr_riccati_tracking_ex",
            "cclqr_release_workspaces", "cclqr_rollout_geometry", "cclqr_rollout_layout_links", "cclqr_ctrl_set_feedforward", "cclqr_abi_layout", "cclqr_rollout_lanes_per_link", "cclqr_rollout_instances_per_wavefront",
-           "cclqr_plants_create", "cclqr_plants_destroy", "cclqr_rollout_plants", "cclqr_linearize_plants", "cclqr_ctrl_create_lqr_batch_plants"]
+           "cclqr_plants_create", "cclqr_plants_destroy", "cclqr_rollout_plants", "cclqr_linearize_plants", "cclqr_ctrl_create_lqr_batch_plants",
+           "cclqr_ctrl_create_tracking_batch_plants", "cclqr_ctrl_get_gains"]
 ABI_VERSION = 202     # include/cclqr.h CCLQR_ABI_VERSION: the structs below mirror that header (verified field by field against cclqr_abi_layout at load time)
 ROLLOUT_NO_ALLOC = 1  # cclqr_rollout_opts.flags: the call may neither allocate nor synchronise (a hipGraph capture is open on the device)
 ROLLOUT_CARRY_STATUS = 4  # ... `status` is read and written: an instance lost in an earlier launch stays frozen, the others merge this launch's result into it
@@ -279,6 +280,82 @@ class BatchLqrHandle:
             self.close()
         except Exception:
             pass
+
+
+class BatchTrackingHandle:
+    """cclqr_ctrl* built by cclqr_ctrl_create_tracking_batch_plants: one TrackingLQR per plant and / or reference trajectory (linearsystem at every knot, the
+    time-varying recursion, the controller's tables), gains device-resident.
+    zd [n][N][nb][13], Fd [n][N][mu] or None: host arrays, or (on_device=True) raw device addresses read on `stream` -- n_ctrl and N must then be given.
+    plants: a PlantsHandle or None (the mechanism's own plant for every trajectory); table k is designed on the plant with global index first_plant + k.
+    fric [ne], noise_scale, noise_seed: the friction / noise law, fixed at construction.  workspace_bytes <= 0: the library's default budget."""
+
+    def __init__(self, mech, zd, ctrl_joint, Q, R, Fd=None, plants=None, first_plant=0, n_ctrl=None, N=None, on_device=False, stream=0, tol=1e-5, fric=None,
+                 noise_scale=0.0, noise_seed=None, workspace_bytes=0):
+        nb = mech.tables.nb
+        cj = i32(ctrl_joint).reshape(-1)
+        mu = len(cj)
+        if on_device:
+            if n_ctrl is None or N is None:
+                raise ValueError("device addresses carry no shape: n_ctrl and N must be given")
+            zarg, farg = C.c_void_p(int(zd)), (C.c_void_p(int(Fd)) if Fd else None)
+            self._arrs = []
+        else:
+            zd = f64(zd)
+            if zd.ndim != 4 or zd.shape[2:] != (nb, 13):
+                raise ValueError("zd must be [n][N][nb][13] = [n][N][%d][13] (got %s)" % (nb, zd.shape))
+            if n_ctrl is None:
+                n_ctrl = zd.shape[0]
+            if N is None:
+                N = zd.shape[1]
+            if zd.shape[:2] != (n_ctrl, N):
+                raise ValueError("zd does not hold n_ctrl x N = %d x %d setpoints (got %s)" % (n_ctrl, N, zd.shape))
+            Fd = None if Fd is None else f64(Fd)
+            if Fd is not None and Fd.shape != (n_ctrl, N, mu):
+                raise ValueError("Fd must be [n][N][mu] = [%d][%d][%d] (got %s)" % (n_ctrl, N, mu, Fd.shape))
+            zarg, farg = _d(zd), _d(Fd)
+            self._arrs = [zd, Fd]
+        Q, R = f64(Q).reshape(12 * nb, 12 * nb), f64(R).reshape(mu, mu)
+        fric = None if fric is None else f64(fric).reshape(mech.tables.ne)
+        self._arrs += [cj, Q, R, fric]
+        law = None
+        if fric is not None or noise_scale or noise_seed is not None:
+            law = CtrlDesc()
+            law.fric, law.noise_scale = _d(fric), float(noise_scale)
+            law.noise_philox, law.noise_seed = (0 if noise_seed is None else 1), (0 if noise_seed is None else int(noise_seed))
+        self.kbreak = np.zeros(int(n_ctrl), dtype=np.int32)
+        self.mu, self.N, self.nsp, self.nK, self.n_ctrl = mu, int(N), int(N), int(N) - 1, int(n_ctrl)
+        self.mech, self.plants, self.first_plant = mech, plants, int(first_plant)
+        self.ptr = C.c_void_p()
+        check(lib().cclqr_ctrl_create_tracking_batch_plants(mech.ptr, None if plants is None else plants.ptr, C.c_int64(int(first_plant)), C.c_int32(int(n_ctrl)),
+                                                            C.c_int32(int(N)), zarg, farg, C.c_int32(1 if on_device else 0), C.c_int32(mu), _i(cj), _d(Q), _d(R),
+                                                            C.c_double(float(tol)), None if law is None else C.byref(law), C.c_int64(int(workspace_bytes)),
+                                                            _i(self.kbreak), C.c_void_p(int(stream)) if stream else None, C.byref(self.ptr)))
+
+    def close(self):
+        if self.ptr:
+            lib().cclqr_ctrl_destroy(self.ptr)
+            self.ptr = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def ctrl_gains(mech, handle, table=0, nK=None, mu=None):
+    """cclqr_ctrl_get_gains: one table's gains [nK][mu][12 nb] of a controller handle, in the mechanism's body order.  nK, mu: the handle's own by default
+    (BatchLqrHandle keeps N: nK = N - 1, or 1 for the infinite horizon)"""
+    mu = handle.mu if mu is None else int(mu)
+    if nK is None:
+        nK = getattr(handle, "nK", None)
+        if nK is None and hasattr(handle, "desc"):
+            nK = handle.desc.nK or 1
+        if nK is None:
+            nK = handle.N - 1 if handle.N > 0 else 1
+    K = np.zeros((int(nK), mu, 12 * mech.tables.nb))
+    check(lib().cclqr_ctrl_get_gains(mech.ptr, handle.ptr, C.c_int64(int(table)), _d(K)))
+    return K
 
 
 class PlantsHandle:

@@ -235,6 +235,9 @@ static int plants_check_range(const cclqr_mech* m, const cclqr_plants* plants, i
     return CCLQR_OK;
 }
 
+// the batched constructors' RicArgs.p_rows: the kernels that assume a symmetric Pk only when Q and R are EXACTLY symmetric (cclqr_riccati's rule, run_riccati)
+static int batch_p_rows(const double* Q, int mx, const double* R, int mu) { return (ric_symmetric(Q, mx) && ric_symmetric(R, mu)) ? 0 : 1; }
+
 extern "C" int cclqr_ctrl_create_lqr_batch_plants(const cclqr_mech* m, const cclqr_plants* plants, int64_t first_plant, int32_t n_ctrl, const double* zd, int32_t mu,
                                                   const int32_t* ctrl_joint, const double* Fd, const double* Q, const double* R, int32_t N, int32_t infinite_horizon,
                                                   double tol, int32_t* kbreak, cclqr_ctrl** out) {
@@ -300,7 +303,7 @@ extern "C" int cclqr_ctrl_create_lqr_batch_plants(const cclqr_mech* m, const ccl
     // dlqr for every setpoint (lqr.jl:141-184), gains written straight into the controller's table
     RicArgs ra;
     ra.nprob = n_ctrl; ra.mx = (int)mx; ra.mu = mu; ra.ml = (int)ml; ra.N = N; ra.time_varying = 0; ra.tol = tol; ra.path = 0; ra.bf16_terms = 0; ra.keep_last = inf ? 1 : 0; ra.kpad = (long long)padi;
-    ra.p_rows = (ric_symmetric(Q, (int)mx) && ric_symmetric(R, mu)) ? 0 : 1;
+    ra.p_rows = batch_p_rows(Q, (int)mx, R, mu);
     const size_t wd = ric_total_work_doubles(ra);
     if (e == hipSuccess) e = ws_get((void**)&dQ, mx * mx * sizeof(double));
     if (e == hipSuccess) e = ws_get((void**)&dR, (size_t)(mu * mu + 1) * sizeof(double));
@@ -339,6 +342,177 @@ extern "C" int cclqr_ctrl_create_lqr_batch(const cclqr_mech* m, int32_t n_ctrl, 
                                            const double* Fd, const double* Q, const double* R, int32_t N, int32_t infinite_horizon, double tol,
                                            int32_t* kbreak, cclqr_ctrl** out) {
     return cclqr_ctrl_create_lqr_batch_plants(m, nullptr, 0, n_ctrl, zd, mu, ctrl_joint, Fd, Q, R, N, infinite_horizon, tol, kbreak, out);
+}
+
+// in-place permutation of the bodies of every setpoint row [nb][13] from the caller's body order to the kernels' link order (one workgroup per row, the row
+// staged in LDS): what build_ctrl_tables does on the host for caller-supplied setpoints, here for trajectories that may never have been on the host
+__global__ void sp_rows_to_link_order_kernel(double* zd, long long nrows, int nb, const MechDev* M) {
+    extern __shared__ double row[];
+    const long long r = blockIdx.x;
+    if (r >= nrows) return;
+    double* p = zd + r * 13 * nb;
+    for (int e = threadIdx.x; e < 13 * nb; e += blockDim.x) row[e] = p[e];
+    __syncthreads();
+    for (int e = threadIdx.x; e < 13 * nb; e += blockDim.x) { const int l = e / 13; p[e] = row[13 * M->perm[l] + (e - 13 * l)]; }
+}
+
+// TrackingLQR(mechanism_k, storage_k, Fτ_k, eqcids, Q, R) (lqr_tracking.jl:17-43) for n_ctrl plants and / or trajectories in one call: linearsystem at the knots
+// 1 .. N-1 of every trajectory (lqr_tracking.jl:88) on that trajectory's plant, the recursion of lqr_tracking.jl:73-122 per problem, the gains written into the
+// controller's tables.  The problems run in chunks that keep the models and the recursion's scratch within the workspace budget (tracking_chunk_problems).
+extern "C" int cclqr_ctrl_create_tracking_batch_plants(const cclqr_mech* m, const cclqr_plants* plants, int64_t first_plant, int32_t n_ctrl, int32_t N,
+                                                       const double* zd, const double* Fd, int32_t on_device, int32_t mu, const int32_t* ctrl_joint,
+                                                       const double* Q, const double* R, double tol, const cclqr_ctrl_desc* law, int64_t workspace_bytes,
+                                                       int32_t* kbreak, void* stream, cclqr_ctrl** out) {
+    if (!m || !zd || !Q || !R || !ctrl_joint || !out) return fail(CCLQR_EINVAL, "null argument");
+    { int rc = check_device(m); if (rc != CCLQR_OK) return rc; }
+    if (m->host.loop) return fail(CCLQR_EUNSUPPORTED, "batched TrackingLQR construction is for tree mechanisms (closed-loop mechanisms: cclqr_linearize_projected + cclqr_riccati_tv)");
+    if (n_ctrl < 1 || N < 2 || mu < 1 || mu > m->nb) return fail(CCLQR_EINVAL, "bad sizes");
+    { int rc = plants_check_range(m, plants, first_plant, n_ctrl); if (rc != CCLQR_OK) return rc; }
+    const int nb = m->nb;
+    const size_t nz = 13 * (size_t)nb, mx = 12 * (size_t)nb, ml = 5 * (size_t)nb, np = (size_t)n_ctrl, nk = (size_t)N - 1;
+    if (!linearize_fits_lds(m)) return fail(CCLQR_EUNSUPPORTED, "instance does not fit LDS");
+    LinArgs la;
+    memset(&la, 0, sizeof(la));
+    la.M = m->dev; la.mu = mu;
+    la.plants = plants ? plants->dev : nullptr;
+    la.knots_per_plant = (int)nk; la.rows_per_plant = N;
+    CtrlDev H;
+    memset(&H, 0, sizeof(H));
+    H.mu = mu; H.nK = (int)nk; H.N = N; H.nsp = N; H.n_ctrl = n_ctrl;
+    for (int i = 0; i < mu; i++) {
+        if (ctrl_joint[i] < 0 || ctrl_joint[i] >= nb) return fail(CCLQR_EINVAL, "controlled joint out of range");
+        la.cj[i] = m->link_of_joint[ctrl_joint[i]];
+        H.cj[i] = la.cj[i];
+    }
+    if (law) {       // the friction / noise law of examples/trackingLQR_triple_cartpole.jl:93-111, as build_ctrl_tables takes it
+        if (law->fric)
+            for (int j = 0; j < nb; j++) { H.fric[m->link_of_joint[j]] = law->fric[j]; if (law->fric[j] != 0.0) H.has_fric = 1; }
+        H.noise_scale = law->noise_scale;
+        H.noise_philox = law->noise_philox ? 1 : 0;
+        H.noise_key0 = (unsigned)(law->noise_seed & 0xffffffffu) ^ (unsigned)(law->noise_seed >> 32);
+    }
+    const size_t padi = n_ctrl > 1 ? gain_row_overrun(m) : 0;       // every table ends in its own zero pad (CCLQR_K_PAD)
+    const long long tab_stride = (long long)nk * mu * (long long)mx + (long long)padi;
+    H.K_stride = n_ctrl > 1 ? tab_stride : 0;
+    H.zd_stride = n_ctrl > 1 ? (long long)N * (long long)nz : 0;
+    H.Fd_stride = (n_ctrl > 1 && Fd) ? (long long)N * mu : 0;
+    // one Riccati path for the whole call, chosen from n_ctrl, and the chunks the workspace budget allows: all before anything is allocated
+    RicArgs ra;
+    ra.nprob = n_ctrl; ra.mx = (int)mx; ra.mu = mu; ra.ml = (int)ml; ra.N = N; ra.time_varying = 1; ra.tol = tol; ra.path = 0; ra.bf16_terms = 0; ra.keep_last = 0;
+    ra.kpad = (long long)padi;
+    ra.p_rows = batch_p_rows(Q, (int)mx, R, mu);
+    ra.path = ric_chosen_path(ra);
+    RicArgs r1 = ra, r2 = ra;
+    r1.nprob = 1; r2.nprob = 2;
+    const long long ric_per = (long long)(ric_total_work_doubles(r2) - ric_total_work_doubles(r1)), ric_fixed = (long long)ric_total_work_doubles(r1) - ric_per;
+    const long long per_bytes = tracking_problem_bytes((int)mx, mu, (int)ml, N, ric_per);
+    const size_t q_doubles = mx * mx, r_doubles = ((size_t)mu * mu + 1) & ~(size_t)1;
+    const long long fixed_bytes = 8 * (ric_fixed + (long long)q_doubles + (long long)r_doubles);
+    const long long budget = workspace_bytes > 0 ? (long long)workspace_bytes : CCLQR_TRACKING_WORKSPACE_BYTES;
+    const long long per_chunk = tracking_chunk_problems(n_ctrl, per_bytes, fixed_bytes, budget);
+    if (per_chunk < 1)
+        return fail(CCLQR_EINVAL, "workspace_bytes = " + std::to_string(budget) + " does not hold one problem: N = " + std::to_string(N) + " knots of this mechanism need " +
+                                  std::to_string(fixed_bytes + per_bytes) + " bytes");
+    const size_t pc = (size_t)per_chunk;
+    hipStream_t st_ = (hipStream_t)stream;
+    cclqr_ctrl* c = new cclqr_ctrl();
+    memset(c, 0, sizeof(*c));
+    c->nb = nb;
+    c->device = m->device;
+    c->host = H;
+    const size_t nK = np * (size_t)tab_stride, nsp_all = np * (size_t)N;
+    double* slab = nullptr;
+    int *dlst = nullptr, *dkb = nullptr, *dst = nullptr, *dstop = nullptr;
+    std::vector<int> lst(np * nk), kb(np), st(np);
+    const hipMemcpyKind up = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    // the setpoints go straight into the controller's table, in the caller's body order while the linearisation reads them (it permutes as it loads); they are
+    // taken to link order in place afterwards.  Host arrays are copied synchronously, device arrays on `stream`
+    hipError_t e = hipMalloc((void**)&c->zd_dev, nsp_all * nz * sizeof(double));
+    if (e == hipSuccess) e = on_device ? hipMemcpyAsync(c->zd_dev, zd, nsp_all * nz * sizeof(double), up, st_) : hipMemcpy(c->zd_dev, zd, nsp_all * nz * sizeof(double), up);
+    if (e == hipSuccess) e = hipMalloc((void**)&c->K_dev, (nK + CCLQR_K_PAD) * sizeof(double));      // (padding: see cclqr_ctrl_create)
+    if (e == hipSuccess && Fd) {
+        e = hipMalloc((void**)&c->Fd_dev, nsp_all * mu * sizeof(double));
+        if (e == hipSuccess) e = on_device ? hipMemcpyAsync(c->Fd_dev, Fd, nsp_all * mu * sizeof(double), up, st_) : hipMemcpy(c->Fd_dev, Fd, nsp_all * mu * sizeof(double), up);
+        c->Fd_len = nsp_all * mu;
+    }
+    if (e == hipSuccess) e = hipMalloc((void**)&slab, (size_t)(fixed_bytes + per_bytes * per_chunk));
+    if (e == hipSuccess) e = hipMalloc((void**)&dlst, (np * nk + 3 * np + pc) * sizeof(int));
+    if (e == hipSuccess) {
+        dkb = dlst + np * nk; dst = dkb + np; dstop = dst + np;
+        // the slab: Q | R | A | Bu | Bl | G of a chunk's knots | the recursion's workspace for a chunk
+        double* dQ = slab;
+        double* dR = dQ + q_doubles;
+        double* dA = dR + r_doubles;
+        double* dBu = dA + pc * nk * mx * mx;
+        double* dBl = dBu + pc * nk * mx * mu;
+        double* dG = dBl + pc * nk * mx * ml;
+        double* dwork = dG + pc * nk * ml * mx;
+        e = hipMemcpy(dQ, Q, mx * mx * sizeof(double), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(dR, R, (size_t)mu * mu * sizeof(double), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemsetAsync(c->K_dev, 0, (nK + CCLQR_K_PAD) * sizeof(double), st_);
+        la.A = dA; la.Bu = dBu; la.Bl = dBl; la.G = dG;
+        ra.stop = dstop; ra.A = dA; ra.Bu = dBu; ra.Bl = dBl; ra.G = dG; ra.Q = dQ; ra.R = dR; ra.work = dwork;
+        for (size_t c0 = 0; c0 < np && e == hipSuccess; c0 += pc) {
+            const size_t nc = np - c0 < pc ? np - c0 : pc;
+            // linearsystem at the knots 1 .. N-1 of the chunk's trajectories (lqr_tracking.jl:88), one launch; the models stay on the device
+            la.nk = (int)(nc * nk);
+            la.zd = c->zd_dev + c0 * (size_t)N * nz;
+            la.Fd = c->Fd_dev ? c->Fd_dev + c0 * (size_t)N * mu : nullptr;
+            la.plant_off = plants ? first_plant - plants->first_index + (long long)c0 : 0;
+            la.status = dlst + c0 * nk;
+            e = launch_linearize(la, m->shape, st_);
+            // the recursion of lqr_tracking.jl:73-122 for each of them, gains written straight into the controller's tables
+            ra.nprob = (int)nc;
+            ra.K = c->K_dev + c0 * (size_t)tab_stride; ra.kbreak = dkb + c0; ra.status = dst + c0;
+            if (e == hipSuccess) e = launch_riccati(ra, st_);
+        }
+        if (e == hipSuccess) {
+            const long long nrows = (long long)np * (long long)nk * mu;
+            e = launch_lds<false>(k_rows_to_link_order_kernel, dim3((unsigned)nrows), dim3(128), mx * sizeof(double), st_, c->K_dev, nrows, (long long)nk * mu, tab_stride, nb, m->dev);
+        }
+        if (e == hipSuccess)
+            e = launch_lds<false>(sp_rows_to_link_order_kernel, dim3((unsigned)nsp_all), dim3(64), nz * sizeof(double), st_, c->zd_dev, (long long)nsp_all, nb, m->dev);
+        if (e == hipSuccess) e = hipStreamSynchronize(st_);
+        if (e == hipSuccess) e = hipMemcpy(lst.data(), dlst, np * nk * sizeof(int), hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(kb.data(), dkb, np * sizeof(int), hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(st.data(), dst, np * sizeof(int), hipMemcpyDeviceToHost);
+    }
+    if (e != hipSuccess) (void)hipStreamSynchronize(st_);      // nothing of the call may still run on what is released below
+    if (slab) (void)hipFree(slab);
+    if (dlst) (void)hipFree(dlst);
+    c->host.K = c->K_dev; c->host.zd = c->zd_dev; c->host.Fd = c->Fd_dev;
+    ctrl_hot_build(c->host);      // the record the rollout steps read: after the tables' addresses and strides are final
+    if (e == hipSuccess) e = hipMalloc((void**)&c->dev, sizeof(CtrlDev));
+    if (e == hipSuccess) e = hipMemcpy(c->dev, &c->host, sizeof(CtrlDev), hipMemcpyHostToDevice);
+    if (e != hipSuccess) { cclqr_ctrl_destroy(c); return fail(CCLQR_EHIP, std::string("batched TrackingLQR construction: ") + hipGetErrorString(e)); }
+    for (size_t p = 0; p < np; p++) if (kbreak) kbreak[p] = kb[p];
+    for (size_t p = 0; p < np; p++) {
+        for (size_t k = 0; k < nk; k++)
+            if (lst[p * nk + k] <= 0) {
+                cclqr_ctrl_destroy(c);
+                return fail(CCLQR_ENOCONV, "Newton did not converge at the setpoint of knot " + std::to_string(k) + " of table " + std::to_string(p));
+            }
+        if (st[p] != 0) { cclqr_ctrl_destroy(c); return fail(CCLQR_ESINGULAR, "G*Bl or M is singular in table " + std::to_string(p)); }
+    }
+    *out = c;
+    return CCLQR_OK;
+}
+
+// one table's gains back on the host, in the caller's body order (the inverse of k_rows_to_link_order_kernel / build_ctrl_tables)
+extern "C" int cclqr_ctrl_get_gains(const cclqr_mech* m, const cclqr_ctrl* c, int64_t table, double* K_host) {
+    if (!m || !c || !K_host) return fail(CCLQR_EINVAL, "null argument");
+    { int rc = check_device(m); if (rc != CCLQR_OK) return rc; }
+    if (c->nb != m->nb || c->device != m->device) return fail(CCLQR_EINVAL, "the controller was created for another mechanism");
+    if (!c->K_dev || c->host.nK < 1) return fail(CCLQR_EINVAL, "the controller has no gains (open loop / PID)");
+    const int64_t ntab = c->host.n_ctrl > 1 ? c->host.n_ctrl : 1;
+    if (table < 0 || table >= ntab) return fail(CCLQR_EINVAL, "table " + std::to_string(table) + " is not among the controller's tables 0 .. " + std::to_string(ntab - 1));
+    const int nb = m->nb;
+    const size_t mx = 12 * (size_t)nb, rows = (size_t)c->host.nK * c->host.mu;
+    std::vector<double> Kl(rows * mx);
+    HIPCHK(hipMemcpy(Kl.data(), c->K_dev + (size_t)table * (size_t)c->host.K_stride, rows * mx * sizeof(double), hipMemcpyDeviceToHost));
+    for (size_t r = 0; r < rows; r++)
+        for (int l = 0; l < nb; l++) memcpy(K_host + r * mx + 12 * m->host.perm[l], &Kl[r * mx + 12 * l], 12 * sizeof(double));
+    return CCLQR_OK;
 }
 
 extern "C" int cclqr_ctrl_destroy(cclqr_ctrl* c) {

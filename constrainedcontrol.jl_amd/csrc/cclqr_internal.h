@@ -113,7 +113,19 @@ struct LinArgs {
     int* status;             // [nk]
     const PlantRec* plants;  // per-knot plants (cclqr_linearize_plants): records [n_plant][nb] in link order, or nullptr = every knot on the mechanism's own plant
     long long plant_off;     // knot k is linearised on row plant_off + k of the table (checked against [0, n_plant) on the host); chains and trees only
+    // whole trajectories per plant (cclqr_ctrl_create_tracking_batch_plants; lin_knot_rows): rows_per_plant = 0 is the map above, one knot = one setpoint row =
+    // one plant.  rows_per_plant = N > 0: the launch holds knots_per_plant = N - 1 knots of every problem -- knot q belongs to problem q / (N - 1), reads setpoint
+    // and feed-forward row problem * N + q % (N - 1) (the N-th row of a trajectory is not linearised, lqr_tracking.jl:87-88) and plant row plant_off + problem
+    int knots_per_plant, rows_per_plant;
 };
+// which problem (= plant row behind plant_off) and which setpoint / feed-forward row knot q of a linearisation launch reads
+HD void lin_knot_rows(int knot, int knots_per_plant, int rows_per_plant, int* problem, long long* row) {
+    *problem = knot; *row = knot;
+    if (rows_per_plant > 0) {
+        const int p = knot / knots_per_plant;
+        *problem = p; *row = (long long)p * rows_per_plant + (knot - p * knots_per_plant);
+    }
+}
 // the model with the multipliers exogenous at the knots a.zd, for any mechanism (linearize.hip): linearize_kernel for chains and trees; closed
 // loops are handed on to launch_linearize_loop (rollout_loop.hip, linearize_loop_kernel)
 hipError_t launch_linearize(const LinArgs& a, const RolloutShape& s, hipStream_t stream);
@@ -149,6 +161,37 @@ inline bool ric_symmetric(const double* X, int n) {
 }
 size_t ric_total_work_doubles(const RicArgs& a);
 hipError_t launch_riccati(const RicArgs& a, hipStream_t stream);
+// the RicArgs.path (1 resident, 2 tiled) launch_riccati takes for these arguments -- a call that runs its problems in several launches (chunks) asks once, with
+// the nprob of the WHOLE call, and passes the answer to every launch: a chunk's own problem count must not pick another kernel
+int ric_chosen_path(const RicArgs& a);
+
+// ---- one TrackingLQR per plant or trajectory (cclqr_ctrl_create_tracking_batch_plants): the workspace plan, pure host arithmetic
+// Default budget of the call's device workspace.  Per knot a problem holds A (mx^2), Bu (mx mu), Bl and G (mx ml each), [A'|D] (mx (mx + mu)) and the projection
+// scratch (ml^2 + ml (mx + mu)) -- triple cartpole, mx 48, mu 1, ml 20: 2304 + 48 + 960 + 960 + 2352 + 1380 doubles = 64 KB --, so its N = 1000 trajectory takes
+// 64 MB and 1024 plants would take 65 GB at once.  4 GiB (1.4 % of an MI355X's 288 GB) runs them 64 problems to a chunk; the gain table itself (393 MB) is the
+// controller's, not workspace.
+#define CCLQR_TRACKING_WORKSPACE_BYTES (4LL << 30)
+#define CCLQR_TRACKING_MAX_CHUNK 32768      // problems per launch: they are the y extent of the Riccati grids (at most 65535)
+// bytes one problem adds to a chunk: its N - 1 linear models, its share of the recursion's workspace (ric_doubles = what one more problem adds to
+// ric_total_work_doubles) and its knots' Newton statuses
+inline long long tracking_problem_bytes(int mx, int mu, int ml, int N, long long ric_doubles) {
+    const long long nk = N - 1;
+    return 8 * (nk * ((long long)mx * mx + (long long)mx * mu + 2LL * mx * ml) + ric_doubles) + 4 * ((nk + 1) & ~1LL);
+}
+// problems per chunk: as many as `budget_bytes` (<= 0: CCLQR_TRACKING_WORKSPACE_BYTES) holds next to the call's fixed_bytes, at most CCLQR_TRACKING_MAX_CHUNK, then
+// evened out over the resulting number of chunks (so that no chunk is a short tail).  0: not even one problem fits.  Chunk i of tracking_chunk_count() covers
+// the problems [i per, min(n_ctrl, (i + 1) per)).
+inline long long tracking_chunk_problems(long long n_ctrl, long long per_problem_bytes, long long fixed_bytes, long long budget_bytes) {
+    if (budget_bytes <= 0) budget_bytes = CCLQR_TRACKING_WORKSPACE_BYTES;
+    if (n_ctrl < 1 || per_problem_bytes < 1 || fixed_bytes < 0 || budget_bytes < fixed_bytes) return 0;
+    long long fit = (budget_bytes - fixed_bytes) / per_problem_bytes;
+    if (fit < 1) return 0;
+    if (fit > CCLQR_TRACKING_MAX_CHUNK) fit = CCLQR_TRACKING_MAX_CHUNK;
+    if (fit > n_ctrl) fit = n_ctrl;
+    const long long chunks = (n_ctrl + fit - 1) / fit;
+    return (n_ctrl + chunks - 1) / chunks;
+}
+inline long long tracking_chunk_count(long long n_ctrl, long long per_chunk) { return per_chunk < 1 ? 0 : (n_ctrl + per_chunk - 1) / per_chunk; }
 
 }  // namespace cclqr
 

@@ -33,15 +33,19 @@ __global__ __launch_bounds__(64) void linearize_kernel(LinArgs a) {
     const int NL = newton_level_groups(G, nb), lg = t / nb, tl = t - lg * nb;   // lane groups of the level-parallel line search
     // the knot's plant, resolved once: the mechanism's own records, or -- a wavefront-uniform branch -- the knot's row of the launch's table
     // (rollout_chain.hip reads its instances' plants the same way).  Every lane group of the level-parallel line search loads the same knot's plant.
+    // (whole trajectories per plant, rows_per_plant > 0: the knot's problem names the plant, and its setpoint row skips every trajectory's last row)
+    int problem;
+    long long row;
+    lin_knot_rows(knot, a.knots_per_plant, a.rows_per_plant, &problem, &row);
     const PlantRec* plant = M->rec;
-    if (a.plants) plant = a.plants + (size_t)(a.plant_off + knot) * nb;
+    if (a.plants) plant = a.plants + (size_t)(a.plant_off + problem) * nb;
     lane_load_consts(r, M, lg < NL ? tl : 0, plant);
-    for (int e = t; e < nz; e += G) { int l = e / 13, c = e - 13 * l; L[Y.Z + e] = a.zd[(size_t)knot * nz + M->perm[l] * 13 + c]; }
+    for (int e = t; e < nz; e += G) { int l = e / 13, c = e - 13 * l; L[Y.Z + e] = a.zd[(size_t)row * nz + M->perm[l] * 13 + c]; }
     for (int e = t; e < 5 * nb; e += G) L[Y.LAM + e] = 0.0;
     for (int e = t; e < nb; e += G) L[Y.UJ + e] = 0.0;
     __syncthreads();
     if (t == 0)
-        for (int i = 0; i < mu; i++) L[Y.UJ + a.cj[i]] += a.Fd ? a.Fd[(size_t)knot * mu + i] : 0.0;
+        for (int i = 0; i < mu; i++) L[Y.UJ + a.cj[i]] += a.Fd ? a.Fd[(size_t)row * mu + i] : 0.0;
     __syncthreads();
     if (lg < NL) ph_forces<TREE>(tl, nb, Y, L, r, M, lg == 0, plant);
     ph_knot_jac(t, nb, Y, L, r);

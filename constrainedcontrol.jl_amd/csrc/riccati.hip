@@ -1228,6 +1228,7 @@ static bool ric_use_tiled(const RicArgs& a) {
 }
 
 size_t ric_total_work_doubles(const RicArgs& a) { RicGrid g; return ric_lay_out(g, a, nullptr); }
+int ric_chosen_path(const RicArgs& a) { return ric_use_tiled(a) ? 2 : 1; }
 
 // Pkp1 = Q + Ku'RKu + Abar'(Pk Abar) is symmetric, so of its T x T tiles of 16 x 16 only the T (T + 1) / 2 with column tile >= row tile are
 // computed (and mirrored): 21 instead of 36 for the Sawyer's 84 states.  A tile's A operand is the Abar fragment of the wavefront that owns the

@@ -4,6 +4,7 @@ meaning; the arithmetic (linearsystem, dlqr, simulate!) runs in HIP through the 
     LQR(mechanism, bodyids, eqcids, Q, R, horizon; xd, vd, qd, ωd, Fτd)            src/control/lqr.jl:49-66
     LQR(A, Bu, Bλ, G, Q, R, horizon, eqcids, xd, vd, qd, ωd, Fτd, Δt)              src/control/lqr.jl:17-47
     PlantLQR(mechanism, plants, bodyids, eqcids, Q, R, horizon, zd; Fτd)           the first of these once per plant of a PlantBatch, in one call
+    PlantTrackingLQR(mechanism, plants, storage, Fτ, eqcids, Q, R; fric, noise_*)   TrackingLQR (below) once per plant / trajectory, in one call
     TrackingLQR(mechanism, storage, Fτ, eqcids, Q, R)                                src/control/lqr_tracking.jl:17-43
     simulate!(mechanism, tend | storage, controller; record)                         e.g. examples/lqr_cartpole.jl:44
     Storage{T}(steps, Nb)                                                            examples/trackingLQR_triple_cartpole.jl:50-51
@@ -253,6 +254,101 @@ class PlantLQR(Controller):
         if self._handle.plants.mech is not dev or not self._handle.ptr:
             raise ValueError("the PlantLQR was designed on another device handle of the mechanism")
         return _BorrowedCtrl(self._handle)
+
+    def gains(self, i):
+        """K[k][j] of plant i's table, [nK][mu][12 nb] in the mechanism's body order, read back from the device (cclqr_ctrl_get_gains)"""
+        return _capi.ctrl_gains(_device_mech(self.mechanism), self._handle, i)
+
+    def close(self):
+        self._handle.close()
+
+
+def _is_device_tensor(a):
+    return hasattr(a, "data_ptr") and bool(getattr(a, "is_cuda", False))
+
+
+class PlantTrackingLQR(Controller):
+    """One TrackingLQR per plant of a PlantBatch (and per reference trajectory), designed in one call: for every plant k,
+    TrackingLQR(mechanism_k, storage_k, Fτ_k, eqcids, Q, R) (lqr_tracking.jl:17-43) where mechanism_k is the mechanism rebuilt with plant k's masses, inertias and
+    joint vertices -- linearsystem at the knots 1 .. N-1 of every trajectory (lqr_tracking.jl:88) and the recursion of lqr_tracking.jl:73-122 per plant on the
+    device, the gains never leaving it (cclqr_ctrl_create_tracking_batch_plants).
+
+    storage: a batched Storage with one instance per plant, or its raw [n][N][nb][13] array (what simulate(mech, Storage(N, nb), OpenLoop(...), z0=, plants=)
+    returns), each trajectory on its own plant's constraint manifold; a torch tensor on the device is read in place.  Fτ: [N][mu] shared, or [n][N][mu].
+    plants: a PlantBatch, or None = n trajectories on the mechanism's own plant.  Q, R: per-body 12 x 12 and per-constraint 1 x 1 blocks, scaled by Δt.
+    first_plant: global index of the plant storage[0] belongs to (default plants.first_index).  fric [ne], noise_scale, noise_seed: the friction / noise law of
+    examples/trackingLQR_triple_cartpole.jl:93-111, fixed at construction.  workspace_bytes: device workspace of the call (0: the library's default).
+    kbreak [n] per plant, gains(i) reads plant i's table back.
+    simulate(mech, steps, ctl, z0=, plants=, first_instance=): instance i reads table first_instance + i and runs on plant first_instance + i."""
+
+    controlfunction = None
+
+    def __init__(self, mechanism, plants, storage, Fτ, eqcids, Q, R, first_plant=None, fric=None, noise_scale=0.0, noise_seed=None, tol=1e-5, workspace_bytes=0,
+                 controlfunction=None):
+        if controlfunction is not None:
+            raise ValueError("PlantTrackingLQR carries no controlfunction: its gains stay on the device (one TrackingLQR per plant with a closure: build a TrackingLQR per plant)")
+        if not isinstance(mechanism, Mechanism):
+            raise TypeError("PlantTrackingLQR(mechanism, plants, storage, Fτ, eqcids, Q, R; ...)")
+        if plants is not None and plants.mechanism is not mechanism:
+            raise ValueError("the PlantBatch was made for another mechanism")
+        nb, mu = len(mechanism.bodies), len(eqcids)
+        z = storage.z if isinstance(storage, Storage) else storage
+        on_dev = _is_device_tensor(z)
+        if not on_dev:
+            z = np.ascontiguousarray(z, dtype=np.float64)
+        if z.ndim != 4 or tuple(z.shape[2:]) != (nb, 13):
+            raise ValueError("storage must be [n][N][nb][13] = [n][N][%d][13], one trajectory per plant (got %s)" % (nb, tuple(z.shape)))
+        n, N = int(z.shape[0]), int(z.shape[1])
+        if n < 1 or N < 2:
+            raise ValueError("storage must hold at least one trajectory of at least two steps (got %s)" % (tuple(z.shape),))
+        self.first_plant = (0 if plants is None else plants.first_index) if first_plant is None else int(first_plant)
+        if plants is not None:
+            plants.rows_for(self.first_plant, n)      # every trajectory must find its plant
+        assert len(eqcids) == len(R), "Missmatched length for constraints"
+        assert len(Q) == nb, "Missmatched length for bodies"
+        F = Fτ
+        f_dev = _is_device_tensor(F)
+        if F is not None and not f_dev:
+            F = np.ascontiguousarray(F, dtype=np.float64)
+            if F.shape == (N, mu) or (mu == 1 and F.shape == (N,)):
+                F = np.ascontiguousarray(np.broadcast_to(F.reshape(1, N, mu), (n, N, mu)))
+        if F is not None and tuple(F.shape) != (n, N, mu):
+            raise ValueError("Fτ must be [N][mu] = [%d][%d] (shared) or [n][N][mu] = [%d][%d][%d] (got %s)" % (N, mu, n, N, mu, tuple(F.shape)))
+        if F is not None and f_dev != on_dev:
+            raise ValueError("storage and Fτ must both be host arrays or both device tensors")
+        self.mechanism, self.plants, self.n_plant = mechanism, plants, n
+        self.eqcids = [int(e) for e in eqcids]
+        self.ctrl_joints = [mechanism.joint_index(e) for e in self.eqcids]
+        self.Q = _blockdiag([np.asarray(q, dtype=np.float64) for q in Q]) * mechanism.Δt     # lqr_tracking.jl:22
+        self.R = _blockdiag([np.asarray(r, dtype=np.float64) for r in R]) * mechanism.Δt     # lqr_tracking.jl:23
+        self.zd, self.Fd, self.N, self.NK = z, F, N, 12 * nb
+        self.fric, self.noise_scale, self.noise_seed = fric, float(noise_scale), noise_seed
+        dev = _device_mech(mechanism)
+        ph = None if plants is None else plants.handle(dev)
+        kw = dict(Fd=F, plants=ph, first_plant=self.first_plant, tol=tol, fric=fric, noise_scale=noise_scale, noise_seed=noise_seed, workspace_bytes=workspace_bytes)
+        if on_dev:
+            import torch
+            if z.dtype != torch.float64 or not z.is_contiguous() or (F is not None and (F.dtype != torch.float64 or not F.is_contiguous())):
+                raise ValueError("device tensors must be contiguous float64")
+            kw.update(Fd=None if F is None else F.data_ptr(), n_ctrl=n, N=N, on_device=True, stream=torch.cuda.current_stream().cuda_stream)
+            self._handle = _capi.BatchTrackingHandle(dev, z.data_ptr(), self.ctrl_joints, self.Q, self.R, **kw)
+        else:
+            self._handle = _capi.BatchTrackingHandle(dev, z, self.ctrl_joints, self.Q, self.R, **kw)
+        self.kbreak = self._handle.kbreak
+
+    def _ctrl_handle(self, dev, fric=None, noise_scale=0.0, noise_seed=None):
+        if fric is not None or noise_scale or noise_seed is not None:
+            raise ValueError("the friction / noise law of a PlantTrackingLQR is fixed at construction (PlantTrackingLQR(..., fric=, noise_scale=, noise_seed=))")
+        if self.first_plant != 0:
+            raise ValueError("a rollout reads controller table and plant by the global instance index: a PlantTrackingLQR that is rolled out starts at plant 0 "
+                             "(this one at plant %d)" % self.first_plant)
+        if self._handle.mech is not dev or not self._handle.ptr:
+            raise ValueError("the PlantTrackingLQR was designed on another device handle of the mechanism")
+        return _BorrowedCtrl(self._handle)
+
+    def gains(self, i):
+        """K[k][j] of plant i's table, [N-1][mu][12 nb] in the mechanism's body order, read back from the device (cclqr_ctrl_get_gains)"""
+        return _capi.ctrl_gains(_device_mech(self.mechanism), self._handle, i)
 
     def close(self):
         self._handle.close()

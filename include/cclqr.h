@@ -38,7 +38,9 @@ extern "C" {
  * 202 (additive over 201: no struct changed): per-instance plants -- the opaque cclqr_plants with cclqr_plants_create / cclqr_plants_destroy, and the
  * launch on them, cclqr_rollout_plants.
  * Still 202 (additive, no struct changed; tests/test_plants_host.py pins the number): one controller per plant -- cclqr_linearize_plants and
- * cclqr_ctrl_create_lqr_batch_plants.  A shim that needs them looks the symbols up: a 202 library built before them lacks them. */
+ * cclqr_ctrl_create_lqr_batch_plants.  A shim that needs them looks the symbols up: a 202 library built before them lacks them.
+ * Still 202 (additive, no struct changed): one TrackingLQR per plant or trajectory -- cclqr_ctrl_create_tracking_batch_plants -- and the gain inspector
+ * cclqr_ctrl_get_gains; looked up the same way. */
 #define CCLQR_ABI_VERSION 202
 
 #define CCLQR_REVOLUTE 0      /* EqualityConstraint(Revolute(a, b, axis; p1, p2, qoffset)),  examples/lqr_cartpole.jl:26 */
@@ -332,6 +334,32 @@ int cclqr_linearize_plants(const cclqr_mech *m, const cclqr_plants *plants, int6
 int cclqr_ctrl_create_lqr_batch_plants(const cclqr_mech *m, const cclqr_plants *plants, int64_t first_plant, int32_t n_ctrl, const double *zd, int32_t mu,
                                        const int32_t *ctrl_joint, const double *Fd, const double *Q, const double *R, int32_t N, int32_t infinite_horizon,
                                        double tol, int32_t *kbreak, cclqr_ctrl **out);
+
+/* One TrackingLQR per plant and / or per reference trajectory, in one call -- for every k, TrackingLQR(mechanism_k, storage_k, Fτ_k, eqcids, Q, R)
+ * (src/control/lqr_tracking.jl:17-43): linearsystem at the knots 1 .. N-1 of trajectory k (lqr_tracking.jl:88) and the recursion of lqr_tracking.jl:73-122 with its own
+ * break and back-fill per problem, evaluated on the `Mechanism(...)` rebuilt with plant k's numbers as for cclqr_linearize_plants -- the question of
+ * examples/trackingLQR_triple_cartpole.jl:93-125 ("does the tracking controller still swing the perturbed plant up") asked with the controller DESIGNED for each plant.
+ * Table k is designed on the plant with GLOBAL index first_plant + k (row first_plant + k - first_index of the handle); plants == NULL: n_ctrl distinct reference
+ * trajectories on the mechanism's own plant.
+ *   zd [n_ctrl][N][nb][13] in the caller's body order, each trajectory on its own plant's constraint manifold; Fd [n_ctrl][N][mu] or NULL = 0.  on_device = 0: HOST
+ *   pointers; 1: DEVICE pointers read on `stream` (a hipStream_t) -- the traj_dev of a recorded cclqr_rollout_plants with steps = N has exactly zd's layout and can be
+ *   passed straight in.  Q [mx][mx], R [mu][mu] already Δt-scaled (lqr_tracking.jl:22-23), host pointers; kbreak [n_ctrl] (host) or NULL.
+ *   law: NULL = the plain tracking law; else ONLY fric, noise_scale, noise_philox and noise_seed are read (the friction / noise law of
+ *   examples/trackingLQR_triple_cartpole.jl:93-111, as cclqr_ctrl_create takes it).
+ *   workspace_bytes: upper bound of the call's device workspace (the per-knot models, [A'|D] and the recursion's scratch: about 64 KB per knot of a triple cartpole);
+ *   <= 0: 4 GiB.  The problems run in as many chunks as that takes, and the result does not depend on the chunking; CCLQR_EINVAL, naming the bytes one problem needs,
+ *   when not even one fits.
+ * The result is a controller of n_ctrl tables for cclqr_rollout* (instance n reads table first_instance + n): K [n_ctrl][N-1][mu][12 nb], zd [n_ctrl][N], Fd [n_ctrl][N],
+ * every table with the zero pad of cclqr_ctrl_create_lqr_batch; the gains never visit the host (cclqr_ctrl_get_gains reads a table back).  The call returns when the
+ * controller is complete.  The refusals of cclqr_linearize_plants apply before anything is launched or allocated; CCLQR_ENOCONV names the table and the knot whose
+ * Newton solve failed, CCLQR_ESINGULAR the table; tree mechanisms (CCLQR_EUNSUPPORTED for closed loops). */
+int cclqr_ctrl_create_tracking_batch_plants(const cclqr_mech *m, const cclqr_plants *plants, int64_t first_plant, int32_t n_ctrl, int32_t N, const double *zd,
+                                            const double *Fd, int32_t on_device, int32_t mu, const int32_t *ctrl_joint, const double *Q, const double *R, double tol,
+                                            const cclqr_ctrl_desc *law, int64_t workspace_bytes, int32_t *kbreak, void *stream, cclqr_ctrl **out);
+
+/* lqr.K[k][i] (src/control/lqr.jl:4, lqr_tracking.jl:4) of one table of a controller, read back from the device: K_host [nK][mu][12 nb] in the caller's body order,
+ * table in [0, n_ctrl).  For any controller that has gains, however it was built.  CCLQR_EINVAL for a table out of range or a controller without gains. */
+int cclqr_ctrl_get_gains(const cclqr_mech *m, const cclqr_ctrl *c, int64_t table, double *K_host);
 
 /* cclqr_rollout (HOST pointers) with options: first_instance and newton_mode apply, the device-buffer fields must be NULL. */
 int cclqr_rollout_host_ex(const cclqr_mech *m, const cclqr_ctrl *c, int64_t n_inst, int32_t steps, int32_t k0, const double *z0,

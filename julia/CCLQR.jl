@@ -354,6 +354,38 @@ function lqr_batch_plants(h::MechHandle, p::PlantsHandle, n::Int, zd::Array{Floa
     return out[], kb
 end
 
+"One TrackingLQR per plant and / or reference trajectory, built and kept on the device (cclqr_ctrl_create_tracking_batch_plants): table k is
+ TrackingLQR(mechanism_k, storage_k, Fτ_k, eqcids, Q, R) (lqr_tracking.jl:17-43) on plant first_plant + k of `p` (`nothing`: the mechanism's own plant for every
+ trajectory).  zd is 13 x Nb x N x n (storage_k's x, q, v, ω of every step, each trajectory on its own plant's constraint manifold), Fd mu x N x n or nothing; host arrays.
+ fric (one entry per joint) / noise_scale / noise_seed fix the friction / noise law of examples/trackingLQR_triple_cartpole.jl:93-111 on the controller.
+ workspace_bytes <= 0: the library's default budget; the problems run in chunks that stay within it.  Returns the controller handle and the break indices."
+function tracking_batch_plants(h::MechHandle, p::Union{Nothing,PlantsHandle}, n::Int, N::Int, zd::Array{Float64}, ctrl_joint::Vector{Int32}, Q::Vector{Float64},
+                               R::Vector{Float64}; Fd = nothing, first_plant = 0, tol = 1e-5, fric = nothing, noise_scale = 0.0, noise_seed = nothing,
+                               workspace_bytes = 0, stream::Ptr{Cvoid} = C_NULL)
+    out = Ref{Ptr{Cvoid}}(C_NULL); kb = zeros(Int32, n)
+    fd = Fd === nothing ? Ptr{Float64}(C_NULL) : pointer(Fd)
+    GC.@preserve Fd fric begin
+        law = CtrlDesc(0, Ptr{Int32}(C_NULL), 0, 0, Ptr{Float64}(C_NULL), 0, Ptr{Float64}(C_NULL), Ptr{Float64}(C_NULL),
+                       fric === nothing ? Ptr{Float64}(C_NULL) : pointer(fric), noise_scale,
+                       0, Ptr{Int32}(C_NULL), Ptr{Float64}(C_NULL), Ptr{Float64}(C_NULL), Ptr{Float64}(C_NULL), Ptr{Float64}(C_NULL),
+                       noise_seed === nothing ? 0 : 1, noise_seed === nothing ? UInt64(0) : UInt64(noise_seed), 0)
+        check(ccall((:cclqr_ctrl_create_tracking_batch_plants, lib), Cint,
+                    (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Int32, Int32, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Float64, Ref{CtrlDesc},
+                     Int64, Ptr{Int32}, Ptr{Cvoid}, Ref{Ptr{Cvoid}}),
+                    h.ptr, p === nothing ? C_NULL : p.ptr, first_plant, Int32(n), Int32(N), zd, fd, Int32(0), Int32(length(ctrl_joint)), ctrl_joint, Q, R, tol, law,
+                    workspace_bytes, kb, stream, out))
+    end
+    return out[], kb
+end
+
+"lqr.K[k][i] (lqr.jl:4, lqr_tracking.jl:4) of one table (0-based) of a controller, read back from the device (cclqr_ctrl_get_gains): mx x mu x nK, the caller's body order.
+ `c` is the pointer a constructor returned (CtrlHandle(...).ptr, lqr_batch, lqr_batch_plants, tracking_batch_plants)."
+function ctrl_gains(h::MechHandle, c::Ptr{Cvoid}, table::Integer, nK::Integer, mu::Integer)
+    K = zeros(12 * h.nb, mu, nK)
+    check(ccall((:cclqr_ctrl_get_gains, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Float64}), h.ptr, c, table, K))
+    K
+end
+
 "Size the controller handle's Philox workspace before step-per-launch rollouts are captured into a hipGraph (cclqr_ctrl_reserve_noise)."
 reserve_noise!(c::CtrlHandle, n::Integer, steps::Integer) = check(ccall((:cclqr_ctrl_reserve_noise, lib), Cint, (Ptr{Cvoid}, Int64, Int32), c.ptr, n, steps))
 
