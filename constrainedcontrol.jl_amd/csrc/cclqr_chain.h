@@ -28,11 +28,14 @@
 #endif
 // One double of the LDS image, read on its own.  The compiler pairs neighbouring 8-byte LDS reads into ds_read2_b64, which CDNA4 executes at half the
 // rate of two ds_read_b64 (128 against 256 bytes per clock); a volatile read through a pointer typed to the LDS address space stays a single
-// ds_read_b64 with a counted wait (volatile on a generic pointer would become a flat load).  Loads only, and only where it was measured to pay on the
-// headline kernel, phase by phase: the sweep (tri_step), the reduction level (cr_phase_a, cr_phase_b, cr_back) and the G_k operands
-// of the Schur rows (schur_col_load); ck_tri_mid, ck_tri_back and gk_t_apply gained less than the bar and keep the paired reads.  The
-// 8- and 16-lane kernels run tri_step and schur_col_load too: for them only head against parent as a whole was measured (+ 9.6 to + 11 %), not each phase.  Plain
-// indexing on the host (tests/emu).
+// ds_read_b64 with a counted wait (volatile on a generic pointer would become a flat load).  Loads only.  The phases that read through it: the sweep
+// (tri_step), the reduction level (cr_phase_a, cr_phase_b, cr_back) and the G_k operands of the Schur rows (schur_col_load), each measured to pay on
+// the headline kernel on its own; the middle solve (ck_tri_mid), the back substitution (ck_tri_back) and the chain kernel's
+// multiplier map (gk_t_apply<true>; the tree kernel's keeps the plain reads), measured together on the headline and as a whole on the 8- and 16-lane
+// kernels.  Volatile reads also keep their program order, which is what keeps the middle solve's sixty reads in front of its
+// selects (ck_tri_mid).  The 8- and 16-lane kernels run all of these but the reduction level: for them only head against parent as a whole was
+// measured, not each phase.
+// Plain indexing on the host (tests/emu).
 #if defined(__HIP_DEVICE_COMPILE__)
 #define LDS_RD(L, i) (*(const volatile __attribute__((address_space(3))) double*)(const __attribute__((address_space(3))) double*)((L) + (i)))
 #else
@@ -637,6 +640,8 @@ HD void gk_store(int j, const Lay& Y, double* L, const double (*XT)[3], const do
         }
     }
 }
+// SINGLE: the slot's 39 words through LDS_RD (the chain kernel); the tree kernel keeps the plain reads it was measured with
+template <bool SINGLE = false>
 HD void gk_t_apply(const LinkC& c, int j, const Lay& Y, const double* L, const double* y, double* own, double* par) {
     double x[3] = {0, 0, 0}, pb[3] = {0, 0, 0}, pa[3] = {0, 0, 0};
 #pragma unroll
@@ -644,8 +649,13 @@ HD void gk_t_apply(const LinkC& c, int j, const Lay& Y, const double* L, const d
         const int o = Y.GKA + GKSZ * j + gk_row(r), ob = r < 3 ? 3 : 0;
 #pragma unroll
         for (int i = 0; i < 3; i++) {
-            if (r < 3) x[i] += L[o + i] * y[r];
-            pb[i] += L[o + ob + i] * y[r]; pa[i] += L[o + ob + 3 + i] * y[r];
+            if (SINGLE) {
+                if (r < 3) x[i] += LDS_RD(L, o + i) * y[r];
+                pb[i] += LDS_RD(L, o + ob + i) * y[r]; pa[i] += LDS_RD(L, o + ob + 3 + i) * y[r];
+            } else {
+                if (r < 3) x[i] += L[o + i] * y[r];
+                pb[i] += L[o + ob + i] * y[r]; pa[i] += L[o + ob + 3 + i] * y[r];
+            }
         }
     }
 #pragma unroll
@@ -667,9 +677,11 @@ HD void ck_body_solve(const LinkC& c, const double* d, const double* cd, const d
 // the update of r_q), re-cut for latency, since one wavefront per SIMD has nothing to hide it with:
 //  * blocks are column-major, so every lane's right-hand side, target and result are five consecutive doubles;
 //  * every offset is a per-lane cursor advanced by a constant per step (no index arithmetic in the loop);
-//  * loads are issued in the order of need (S_ll, right-hand side, target, S_ql), so the pivot chain of the factorisation
-//    starts after the first 25 and hides the rest (carrying prefetched blocks across the barrier in registers instead made
-//    the register allocator spill all over the kernel);
+//  * loads are written in the order of need (S_ll, right-hand side, target, S_ql); in the headline kernel's ISA the pivot chain
+//    of the factorisation starts after the 25 reads of S_ll, the right-hand side follows the first reciprocal, and the compiler
+//    sinks the target and S_ql (30 reads) behind the back substitution.  Dealing those reads to the pivot stages instead, behind
+//    scheduling fences, was built and measured: no gain, so the compiler's placement stands (carrying
+//    prefetched blocks across the barrier in registers instead made the register allocator spill all over the kernel);
 // Plan of the chain kernel: like tri_plan, but with BALANCED fronts when the chain has an odd number of links (17: 8 + 8 steps
 // instead of 7 + 9).  Both fronts then fold into the middle link in the same (last) step; front 1 writes its contribution
 // -S_ql Z, -S_ql y to a scratch block instead of the middle link's own blocks (`merge`), and the middle solve adds it.  The
@@ -738,8 +750,8 @@ HD void lu5_factor(double* A) {
 }
 // One elimination step of this lane: tg = updated target column, zy = solution column, to be stored by the caller at *otg,
 // *oout AFTER every lane has done its loads (the caller's store sits behind this call in the wavefront's instruction stream).
-// Load order = order of need: S_ll (the LU starts as soon as it has arrived), the right-hand side, the target, and S_ql last
-// (only the final update reads it), so that most of the loads' latency hides under the pivot chain of the factorisation.
+// Load order in the source = order of need: S_ll (the LU starts as soon as it has arrived), the right-hand side, the target, and
+// S_ql last (only the final update reads it); where the compiler issues them: the comment on the solve above.
 // Returns false (and touches nothing) when the lane has no work in step i.
 HD bool tri_step(TriCur& K, int i, const double* L, double* tg, double* zy, int* otg, int* oout) {
     if (i >= K.n) return false;
@@ -772,17 +784,35 @@ HD void tri_step_store(double* L, int otg, int oout, const double* tg, const dou
     for (int r = 0; r < 5; r++) { L[otg + r] = tg[r]; L[oout + r] = zy[r]; }
 }
 // middle link: both sides have been folded in (a balanced plan: front 1's share is added from the scratch block here); one lane
-// factorises and solves
+// factorises and solves.  All sixty words are read first, unconditionally and back to back -- the middle block, the scratch block, the two
+// right-hand sides -- and the plan's `merge` selects the scratch words away afterwards: a read inside the conditional is a scalar branch
+// around every one of thirty reads, on the one lane the whole wavefront waits for.  The scratch words lie inside the instance's image
+// for every plan (tri_scratch_S: at most SJP + 25 nb, the first block of SPJ; tri_scratch_R: at most SPJ + 25 nb, the first words of R).
+// SCR = false: an instantiation whose plans never merge (one front: the 8-lane kernel) does not read the scratch block at all -- there the
+// thirty reads and selects on the waited-for lane were pure additions and cost the 8-lane configs 4 %.  Same sums either way.
+template <bool SCR = true>
 HD void ck_tri_mid(int t, const TriPlanB& B, const Lay& Y, double* L) {
     if (t != 0) return;
     const TriPlan& P = B.P;
-    double A[25], b[5];
-#pragma unroll
-    for (int i = 0; i < 5; i++) b[i] = L[Y.R + 5 * P.mid + i] + (B.merge ? L[tri_scratch_R(B, Y) + i] : 0.0);
+    double A[25], As[25], b[5], bs[5];
+    const int oS = tri_scratch_S(B, Y), oR = tri_scratch_R(B, Y);
 #pragma unroll
     for (int cI = 0; cI < 5; cI++)
 #pragma unroll
-        for (int r = 0; r < 5; r++) A[r * 5 + cI] = L[Y.SJJ + 25 * P.mid + 5 * cI + r] + (B.merge ? L[tri_scratch_S(B, Y) + 5 * cI + r] : 0.0);
+        for (int r = 0; r < 5; r++) A[r * 5 + cI] = LDS_RD(L, Y.SJJ + 25 * P.mid + 5 * cI + r);
+#pragma unroll
+    for (int cI = 0; cI < 5; cI++)
+#pragma unroll
+        for (int r = 0; r < 5; r++) As[r * 5 + cI] = SCR ? LDS_RD(L, oS + 5 * cI + r) : 0.0;
+#pragma unroll
+    for (int i = 0; i < 5; i++) b[i] = LDS_RD(L, Y.R + 5 * P.mid + i);
+#pragma unroll
+    for (int i = 0; i < 5; i++) bs[i] = SCR ? LDS_RD(L, oR + i) : 0.0;
+    const bool merge = SCR && B.merge != 0;
+#pragma unroll
+    for (int i = 0; i < 5; i++) b[i] = b[i] + (merge ? bs[i] : 0.0);
+#pragma unroll
+    for (int e = 0; e < 25; e++) A[e] = A[e] + (merge ? As[e] : 0.0);
     lu5_factor(A);
     lu5_solve(A, b);
 #pragma unroll
@@ -801,8 +831,8 @@ HD void ck_tri_back(int t, int j, const TriPlanB& B, const Lay& Y, double* L) {
     const int nbr = front ? l + B.st : l - B.st;
     double z[5], dn[5];
 #pragma unroll
-    for (int cI = 0; cI < 5; cI++) { z[cI] = L[Y.SJJ + 25 * l + 5 * cI + row]; dn[cI] = L[Y.DL + 5 * nbr + cI]; }
-    const double y = L[Y.R + 5 * l + row];
+    for (int cI = 0; cI < 5; cI++) { z[cI] = LDS_RD(L, Y.SJJ + 25 * l + 5 * cI + row); dn[cI] = LDS_RD(L, Y.DL + 5 * nbr + cI); }
+    const double y = LDS_RD(L, Y.R + 5 * l + row);
     L[Y.DL + 5 * l + row] = y - (z[0] * dn[0] + z[1] * dn[1] + z[2] * dn[2] + z[3] * dn[3] + z[4] * dn[4]);
 }
 

@@ -501,7 +501,7 @@ __global__ __launch_bounds__(64) void rollout_chain_kernel(RolloutArgs a) {
                     __syncthreads();
                 }
                 STAMP(PF_TRI_FWD);
-                if (!done) ck_tri_mid(t, PB, Y, L);
+                if (!done) ck_tri_mid<(G >= 16)>(t, PB, Y, L);      // (8 lanes: one front, no plan merges)
                 __syncthreads();
                 for (int j = 0; j < P.steps; j++) {
                     if (!done) ck_tri_back(t, j, PB, Y, L);
@@ -519,7 +519,7 @@ __global__ __launch_bounds__(64) void rollout_chain_kernel(RolloutArgs a) {
                 double own[6], par[6], cpar[6], dl[5], pdn = 0.0;
 #pragma unroll
                 for (int r = 0; r < 5; r++) dl[r] = L[Y.DL + 5 * tl + r];
-                gk_t_apply(c, tl, Y, L, dl, own, par);
+                gk_t_apply<true>(c, tl, Y, L, dl, own, par);
                 from_next<6>(par, cpar);
                 if (active) {
                     double DINV[9];
@@ -763,6 +763,10 @@ hipError_t launch_rollout_chain(const RolloutArgs& a_in, const RolloutShape& s, 
         // read must stay inside the instance's image whatever order a later re-cut of the layout puts the arrays in
         const Lay Y = make_chain_layout(s.NBP);
         if (Y.DL + 5 * (s.NBP + 1) > Y.total || Y.R + 5 * (s.NBP + 1) > Y.total) return hipErrorInvalidValue;
+        // the middle solve reads the scratch block (25 + 5 words) of every plan of the 16- and 32-lane instantiations, merging or not, and selects it away (ck_tri_mid): furthest out
+        // for a one-link chain that is the forest's last link
+        const TriPlanB B = tri_plan_balanced(s.NBP - 1, 1);
+        if (tri_scratch_S(B, Y) + 25 > Y.total || tri_scratch_R(B, Y) + 5 > Y.total) return hipErrorInvalidValue;
     }
     const bool relax = newton_mode != 0;      // (the residual-only stop exists under the plain law only: launch_chain_one)
     switch (s.NBP) {
