@@ -18,12 +18,13 @@ EXPORTS = ["cclqr_last_error", "cclqr_version", "cclqr_device_count", "cclqr_set
            "cclqr_rollout_dev", "cclqr_rollout_ex", "cclqr_rollout_host_ex", "cclqr_ctrl_reserve_noise", "cclqr_riccati_ex", "cclqr_riccati_tracking_ex",
            "cclqr_release_workspaces", "cclqr_rollout_geometry", "cclqr_rollout_layout_links", "cclqr_ctrl_set_feedforward", "cclqr_abi_layout", "cclqr_rollout_lanes_per_link", "cclqr_rollout_instances_per_wavefront",
            "cclqr_plants_create", "cclqr_plants_destroy", "cclqr_rollout_plants", "cclqr_linearize_plants", "cclqr_ctrl_create_lqr_batch_plants",
-           "cclqr_ctrl_create_tracking_batch_plants", "cclqr_ctrl_get_gains"]
+           "cclqr_ctrl_create_tracking_batch_plants", "cclqr_ctrl_get_gains", "cclqr_score_create", "cclqr_score_destroy", "cclqr_rollout_score"]
 ABI_VERSION = 202     # include/cclqr.h CCLQR_ABI_VERSION: the structs below mirror that header (verified field by field against cclqr_abi_layout at load time)
 ROLLOUT_NO_ALLOC = 1  # cclqr_rollout_opts.flags: the call may neither allocate nor synchronise (a hipGraph capture is open on the device)
 ROLLOUT_CARRY_STATUS = 4  # ... `status` is read and written: an instance lost in an earlier launch stays frozen, the others merge this launch's result into it
 ROLLOUT_PACK_WAVEFRONTS = 2  # ... every wavefront of a chain launch full, whatever the batch size (many launches sharing the device at once)
 PHILOX_INKERNEL_STEPS = 8
+SCORE_LEN = 4           # CCLQR_SCORE_LEN: Jx, Ju, peak, last_out per instance (cclqr_rollout_score)
 NEWTON_MAXIT = 100      # newtonIter of ConstrainedDynamics' newton!: |status| of an instance that hit the cap
 
 
@@ -452,6 +453,91 @@ def rollout_dev(mech, ctrl, n_inst, steps, k0, z0_ptr, lam_ptr, noise_ptr, noise
         return
     check(lib().cclqr_rollout_ex(mech.ptr, ctrl.ptr, C.c_int64(n_inst), C.c_int32(steps), C.c_int32(k0), vp(z0_ptr), vp(lam_ptr),
                                  vp(noise_ptr), C.c_int64(noise_stride), vp(traj_ptr), vp(zT_ptr), vp(status_ptr), C.byref(o), vp(stream)))
+
+
+class ScoreHandle:
+    """cclqr_score*: the device-resident weights a rollout is scored with.  Qb [nb][12][12] per-body blocks in the mechanism's body order, R [mu][mu], both already
+    Δt-scaled (lqr.jl:18-19); settle_tol: the stage cost above which an instance counts as not settled (last_out)"""
+
+    def __init__(self, mech, Qb, R, settle_tol=0.0):
+        nb = mech.tables.nb
+        Qb = f64(Qb).reshape(nb, 12, 12)
+        R = f64(R)
+        mu = int(round(np.sqrt(R.size)))
+        if mu * mu != R.size:
+            raise ValueError("R must be [mu][mu] (got %d entries)" % R.size)
+        R = R.reshape(mu, mu)
+        self.mech, self.mu, self.settle_tol = mech, mu, float(settle_tol)      # (the handle must not outlive the mechanism's)
+        self._arrs = [Qb, R]
+        self.ptr = C.c_void_p()
+        check(lib().cclqr_score_create(mech.ptr, _d(Qb), C.c_int32(mu), _d(R) if mu else None, C.c_double(self.settle_tol), C.byref(self.ptr)))
+
+    def close(self):
+        if self.ptr:
+            lib().cclqr_score_destroy(self.ptr)
+            self.ptr = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def rollout_score(mech, ctrl, score, n_inst, steps, k0, traj_ptr, score_ptr, stream=0, first_instance=0):
+    """cclqr_rollout_score on device addresses (asynchronous on `stream`): scores the slab traj [n_inst][steps][nb][13] a rollout launch has just written into
+    score [n_inst][SCORE_LEN] (read when k0 > 1, always written)"""
+    vp = lambda p: C.c_void_p(int(p)) if p else None
+    check(lib().cclqr_rollout_score(mech.ptr, ctrl.ptr, score.ptr, C.c_int64(int(n_inst)), C.c_int32(int(steps)), C.c_int32(int(k0)), C.c_int64(int(first_instance)),
+                                    vp(traj_ptr), vp(score_ptr), vp(stream)))
+
+
+def chunk_plan(steps, chunk_steps):
+    """the launches of a chunked horizon: [(k0, steps of the launch), ...] covering the steps 1 .. steps exactly once, in order"""
+    steps, chunk_steps = int(steps), int(chunk_steps)
+    if steps < 1 or chunk_steps < 1:
+        raise ValueError("need steps >= 1 and chunk_steps >= 1 (got %d, %d)" % (steps, chunk_steps))
+    return [(k0, min(chunk_steps, steps - k0 + 1)) for k0 in range(1, steps + 1, chunk_steps)]
+
+
+def default_chunk_steps(n_inst, nb, steps, slab_bytes=1 << 30):
+    """the largest chunk whose slab [n_inst][chunk][nb][13] of doubles stays under slab_bytes (at least one step)"""
+    return max(1, min(int(steps), int(slab_bytes) // max(1, int(n_inst) * int(nb) * 13 * 8)))
+
+
+def rollout_scored(mech, ctrl, score, z0, steps, chunk_steps, noise=None, first_instance=0, plants=None, newton_mode=0, newton_eps_alone=0.0, flags=0, traj_out=None):
+    """A horizon rolled out AND scored on the device without its trajectory ever existing: ceil(steps / chunk_steps) launches of cclqr_rollout_ex (plants:
+    cclqr_rollout_plants) into ONE slab of chunk_steps rows, each followed on the same stream by cclqr_rollout_score.  The state, the multipliers, the status
+    (ROLLOUT_CARRY_STATUS), the PID state and the noise column travel from launch to launch, so the result is bitwise that of one launch.
+    noise [n_inst][steps] injected samples or None.  traj_out: a numpy array [n_inst][steps][nb][13] that receives the slabs (the recorded run), or None.
+    Returns (zT, status, score [n_inst][SCORE_LEN])."""
+    import torch
+    nb, ne = mech.tables.nb, mech.tables.ne
+    z0 = f64(z0).reshape(-1, nb, 13)
+    n = z0.shape[0]
+    plan = chunk_plan(steps, chunk_steps)
+    rows = plan[0][1]
+    td = torch.device("cuda", torch.cuda.current_device())
+    z = torch.from_numpy(z0).to(td)
+    zn = torch.empty_like(z)
+    lam = torch.zeros((n, 5 * ne), dtype=torch.float64, device=td)
+    st = torch.zeros(n, dtype=torch.int32, device=td)
+    pid = torch.zeros((n, ne, 2), dtype=torch.float64, device=td)
+    sc = torch.zeros((n, SCORE_LEN), dtype=torch.float64, device=td)
+    slab = torch.empty((n, rows, nb, 13), dtype=torch.float64, device=td)
+    dnoise = None if noise is None else torch.from_numpy(f64(noise).reshape(n, steps)).to(td)
+    stream = torch.cuda.current_stream().cuda_stream
+    for k0, s in plan:
+        # the noise array is indexed by the absolute step k - 1: its base stays where it is whatever k0 is
+        rollout_dev(mech, ctrl, n, s, k0, z.data_ptr(), lam.data_ptr(), 0 if dnoise is None else dnoise.data_ptr(), steps, slab.data_ptr(), zn.data_ptr(),
+                    st.data_ptr(), stream, first_instance=first_instance, pid_state=pid.data_ptr(), newton_mode=newton_mode, newton_eps_alone=newton_eps_alone,
+                    flags=flags | ROLLOUT_CARRY_STATUS, plants=plants)
+        rollout_score(mech, ctrl, score, n, s, k0, slab.data_ptr(), sc.data_ptr(), stream, first_instance=first_instance)
+        if traj_out is not None:      # (a launch of s < rows steps fills the slab as [n][s][nb][13] from its base)
+            traj_out[:, k0 - 1:k0 - 1 + s] = slab.reshape(-1)[:n * s * nb * 13].reshape(n, s, nb, 13).cpu().numpy()
+        z, zn = zn, z
+    torch.cuda.current_stream().synchronize()
+    return z.cpu().numpy(), st.cpu().numpy(), sc.cpu().numpy()
 
 
 def linearize(mech, zd, ctrl_joint, Fd=None, plants=None, first_plant=0):

@@ -8,6 +8,8 @@
 #include "cclqr_newton.h"
 static_assert(CCLQR_NEWTON_MAXIT == NEWTON_MAXIT, "include/cclqr.h and cclqr_newton.h disagree on the Newton iteration cap");
 #include "cclqr_wscache.h"
+#include "cclqr_score.h"
+static_assert(CCLQR_SCORE_LEN == CCLQR_SCORE_LEN_, "include/cclqr.h and cclqr_score.h disagree on the length of a score");
 #include <math.h>
 #include <stdio.h>
 #include <string.h>
@@ -1131,4 +1133,59 @@ extern "C" int cclqr_riccati_tracking_ex(const cclqr_mech* m, int32_t mu, const 
     }
     if (e != hipSuccess) return fail(CCLQR_EHIP, std::string("riccati_tracking: ") + hipGetErrorString(e));
     return rc;
+}
+
+// ---- scoring a rollout on the device (score.hip).  The weights are permuted ONCE, here: traj rows stay in the caller's body order, the controller's K columns
+// and setpoints are in link order (build_ctrl_tables), so the per-body blocks go to link order with them (closed loops: perm is the identity)
+extern "C" int cclqr_score_create(const cclqr_mech* m, const double* Qb, int32_t mu, const double* R, double settle_tol, cclqr_score** out) {
+    if (!m || !Qb || !out || (mu > 0 && !R)) return fail(CCLQR_EINVAL, "null argument");
+    { int rc = check_device(m); if (rc != CCLQR_OK) return rc; }
+    if (mu < 0 || mu > m->nj) return fail(CCLQR_EINVAL, "mu = " + std::to_string(mu) + " is not a number of controlled joints of this mechanism (0 .. " + std::to_string(m->nj) + ")");
+    if (!std::isfinite(settle_tol)) return fail(CCLQR_EINVAL, "settle_tol is not finite");
+    const int nb = m->nb;
+    for (size_t e = 0; e < (size_t)nb * 144; e++)
+        if (!std::isfinite(Qb[e])) return fail(CCLQR_EINVAL, "a weight is not finite: Qb of body " + std::to_string(e / 144) + ", entry " + std::to_string(e % 144));
+    for (size_t e = 0; e < (size_t)mu * mu; e++)
+        if (!std::isfinite(R[e])) return fail(CCLQR_EINVAL, "a weight is not finite: R entry " + std::to_string(e));
+    std::vector<double> Ql((size_t)nb * 144);
+    for (int l = 0; l < nb; l++) memcpy(&Ql[(size_t)l * 144], Qb + (size_t)m->host.perm[l] * 144, 144 * sizeof(double));
+    cclqr_score* s = new cclqr_score();
+    memset(s, 0, sizeof(*s));
+    s->settle_tol = settle_tol; s->nb = nb; s->mu = mu; s->device = m->device; s->mech = m;
+    hipError_t e = hipMalloc((void**)&s->Qb_dev, Ql.size() * sizeof(double));
+    if (e == hipSuccess) e = hipMemcpy(s->Qb_dev, Ql.data(), Ql.size() * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMalloc((void**)&s->R_dev, ((size_t)mu * mu + 1) * sizeof(double));
+    if (e == hipSuccess && mu > 0) e = hipMemcpy(s->R_dev, R, (size_t)mu * mu * sizeof(double), hipMemcpyHostToDevice);
+    if (e != hipSuccess) { cclqr_score_destroy(s); return fail(CCLQR_EHIP, std::string("score weights upload: ") + hipGetErrorString(e)); }
+    *out = s;
+    return CCLQR_OK;
+}
+
+extern "C" int cclqr_score_destroy(cclqr_score* s) {
+    if (!s) return CCLQR_OK;
+    if (s->Qb_dev) (void)hipFree(s->Qb_dev);
+    if (s->R_dev) (void)hipFree(s->R_dev);
+    delete s;
+    return CCLQR_OK;
+}
+
+extern "C" int cclqr_rollout_score(const cclqr_mech* m, const cclqr_ctrl* c, const cclqr_score* s, int64_t n_inst, int32_t steps, int32_t k0, int64_t first_instance,
+                                   const double* traj, double* score, void* stream) {
+    if (!m || !c || !s) return fail(CCLQR_EINVAL, "null argument");
+    { int rc = check_device(m); if (rc != CCLQR_OK) return rc; }
+    if (s->mech != m || s->nb != m->nb || s->device != m->device) return fail(CCLQR_EINVAL, "the score weights were created for another mechanism or device");
+    if (c->nb != m->nb || c->device != m->device) return fail(CCLQR_EINVAL, "the controller was created for another mechanism or device");
+    if (steps < 1 || k0 < 1) return fail(CCLQR_EINVAL, "need steps >= 1 and k0 >= 1 (got steps = " + std::to_string(steps) + ", k0 = " + std::to_string(k0) + ")");
+    if (n_inst < 0 || first_instance < 0) return fail(CCLQR_EINVAL, "negative n_inst or first_instance");
+    if (s->mu != c->host.mu) return fail(CCLQR_EINVAL, "mu of the score weights (" + std::to_string(s->mu) + ") differs from the controller's (" + std::to_string(c->host.mu) + ")");
+    if (!c->zd_dev || c->host.nsp < 1) return fail(CCLQR_EINVAL, "the controller has no setpoint table");
+    if (c->host.n_ctrl > 1 && first_instance + n_inst > c->host.n_ctrl)
+        return fail(CCLQR_EINVAL, "first_instance + n_inst = " + std::to_string(first_instance + n_inst) + " exceeds the controller's n_ctrl = " + std::to_string(c->host.n_ctrl) + " tables");
+    if (n_inst == 0) return CCLQR_OK;
+    if (!traj || !score) return fail(CCLQR_EINVAL, "null argument");
+    ScoreArgs a;
+    a.M = m->dev; a.C = c->dev; a.Qb = s->Qb_dev; a.R = s->R_dev; a.settle_tol = s->settle_tol; a.nb = m->nb; a.mu = s->mu;
+    a.n_inst = n_inst; a.steps = steps; a.k0 = k0; a.inst0 = first_instance; a.traj = traj; a.score = score;
+    HIPCHK(launch_score(a, (hipStream_t)stream));
+    return CCLQR_OK;
 }

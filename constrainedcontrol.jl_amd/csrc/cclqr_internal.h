@@ -219,6 +219,13 @@ struct cclqr_plants {
 // past an instance's last row are zeros and never a NEIGHBOUR's gains -- which may be Inf / NaN when that neighbour's recursion diverged, and
 // 0 * NaN would poison a healthy instance's input
 #define CCLQR_K_PAD 768
+// the weights a rollout is scored with (cclqr_score_create): blocks in the controller tables' link order
+struct cclqr_score {
+    double *Qb_dev, *R_dev;    // [nb][12][12] link order, [mu][mu]
+    double settle_tol;
+    int nb, mu, device;
+    const cclqr_mech* mech;    // the mechanism whose link order the blocks were permuted to
+};
 struct cclqr_ctrl {
     cclqr::CtrlDev host;
     cclqr::CtrlDev* dev;

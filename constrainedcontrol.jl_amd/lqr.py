@@ -365,10 +365,13 @@ class Storage:
             self.z[..., 3] = 1.0
         self.status = status
         self.zT = zT
+        self.score = None          # [n_inst][4] = Jx, Ju, peak, last_out of simulate(..., score=)
 
     def instance(self, n):
-        return Storage(self.steps, self.nb, 1, self.z[n:n + 1], None if self.status is None else self.status[n:n + 1],
-                       None if self.zT is None else self.zT[n:n + 1])
+        one = Storage(self.steps, self.nb, 1, self.z[n:n + 1], None if self.status is None else self.status[n:n + 1],
+                      None if self.zT is None else self.zT[n:n + 1])
+        one.score = None if self.score is None else self.score[n:n + 1]
+        return one
 
     def _field(self, lo, hi):
         return [self.z[0, :, i, lo:hi] for i in range(self.nb)]
@@ -410,6 +413,38 @@ class TrackingLQR(Controller):
 
     def _ctrl_handle(self, dev, fric=None, noise_scale=0.0, noise_seed=None):
         return _capi.CtrlHandle(dev, self.ctrl_joints, K=self.K, N=self.N, zd=self.zd, Fd=self.Fd, fric=fric, noise_scale=noise_scale, noise_seed=noise_seed)
+
+
+class Score:
+    """What a run is ranked by: the quadratic cost the gains were designed to minimise, sum_k Δz' Q Δz + Δu' R Δu with the error Δz of lqr.jl:92-103 and the
+    feedback command Δu = -K[k] Δz, evaluated on the device from the rollout's own states (cclqr_rollout_score).
+    Score(mechanism, bodyids, eqcids, Q, R; settle_tol) takes Q and R as LQR(...) does: per-body 12 x 12 and per-constraint 1 x 1 blocks in the order of bodyids /
+    eqcids, scaled by Δt (lqr.jl:18-19).  simulate(..., score=Score) returns a Storage with .score [n_inst][4] = Jx, Ju, peak stage cost, last step whose stage
+    cost exceeded settle_tol (0: none; the instance is settled from step last_out + 1)."""
+
+    def __init__(self, mechanism, bodyids, eqcids, Q, R, settle_tol=0.0):
+        if not isinstance(mechanism, Mechanism):
+            raise TypeError("Score(mechanism, bodyids, eqcids, Q, R; settle_tol)")
+        nb = len(mechanism.bodies)
+        assert len(bodyids) == len(Q) == nb, "Missmatched length for bodies"                    # lqr.jl:59
+        assert len(eqcids) == len(R), "Missmatched length for constraints"                      # lqr.jl:60
+        if not math.isfinite(float(settle_tol)):
+            raise ValueError("settle_tol must be finite")
+        inv = _body_order(bodyids, nb)
+        Qb = [np.asarray(Q[i], dtype=np.float64) for i in inv]
+        Rb = [np.asarray(r, dtype=np.float64).reshape(1, 1) for r in R]
+        if any(q.shape != (12, 12) for q in Qb):
+            raise ValueError("every Q block must be 12 x 12")
+        self.mechanism = mechanism
+        self.eqcids = [int(e) for e in eqcids]
+        self.Q, self.R, _, _ = _weights_and_horizon(Qb, Rb, math.inf, mechanism.Δt)             # lqr.jl:18-19
+        self.Qb = np.stack([self.Q[12 * b:12 * b + 12, 12 * b:12 * b + 12] for b in range(nb)])  # the blocks, mechanism body order
+        self.settle_tol = float(settle_tol)
+        if not (np.isfinite(self.Qb).all() and np.isfinite(self.R).all()):
+            raise ValueError("the weights must be finite")
+
+    def _handle(self, dev):
+        return _capi.ScoreHandle(dev, self.Qb, self.R, self.settle_tol)
 
 
 class OpenLoop(Controller):
@@ -755,7 +790,7 @@ def _simulate_device_closure(mechanism, steps, controller, record, z0):
 
 
 def simulate(mechanism, tend_or_storage, controller, record=True, z0=None, fric=None, noise=None, noise_scale=None, noise_seed=None,
-             first_instance=0, plants=None):
+             first_instance=0, plants=None, score=None, chunk_steps=None):
     """simulate!(mechanism, tend::Real | storage::Storage, controller; record)  -> Storage
 
     z0 [n_inst][nb][13]: batch of initial states (default: the mechanism's current body states, one instance).
@@ -765,6 +800,10 @@ def simulate(mechanism, tend_or_storage, controller, record=True, z0=None, fric=
     plants: a PlantBatch -- instance i runs with the masses, inertias and joint vertices of plant first_instance + i (the controller's gains stay the
     ones it was built with: the Monte-Carlo robustness run).  z0[i] must lie on plant i's constraint manifold (joint_position_states(..., plants=)).  For the
     fused laws (LQR, TrackingLQR with friction / noise, OpenLoop, PID).
+    score: a Score -- the horizon runs in launches of chunk_steps steps (default: the largest whose slab [n_inst][chunk][nb][13] stays under 1 GiB) into one slab,
+    each scored on the device behind its launch; the returned Storage carries .score [n_inst][4] (Jx, Ju, peak, last_out).  With record=False nothing larger than
+    that slab ever exists; with record=True the slabs are also collected and the recorded trajectory is what was scored.  zT and status are bitwise those of the
+    run without score=.  For the fused laws.
     After the call the mechanism's bodies hold instance 0's final state (simulate! mutates the mechanism)."""
     if isinstance(tend_or_storage, Storage):
         steps = tend_or_storage.steps
@@ -772,6 +811,21 @@ def simulate(mechanism, tend_or_storage, controller, record=True, z0=None, fric=
         steps = int(math.ceil(tend_or_storage / mechanism.Δt))     # steps = 1:ceil(tend/Δt)
     nb = len(mechanism.bodies)
     z0 = mechanism.state()[None] if z0 is None else np.asarray(z0, dtype=np.float64).reshape(-1, nb, 13)
+    if score is None and chunk_steps is not None:
+        raise ValueError("chunk_steps is an option of score=")
+    if score is not None:
+        if not isinstance(score, Score):
+            raise TypeError("score= takes a Score(mechanism, bodyids, eqcids, Q, R)")
+        if getattr(controller, "controlfunction", None) is not None:
+            raise ValueError("score= with a custom controlfunction is not supported: the device scores the feedback command of the fused laws, a closure computes its own inputs")
+        if score.mechanism is not mechanism:
+            raise ValueError("the Score was made for another mechanism")
+        if steps < 1:
+            raise ValueError("score= needs at least one step")
+        if chunk_steps is None:
+            chunk_steps = _capi.default_chunk_steps(z0.shape[0], nb, steps)
+        if int(chunk_steps) < 1:
+            raise ValueError("chunk_steps must be at least 1")
     if plants is not None:
         if getattr(controller, "controlfunction", None) is not None:
             raise ValueError("plants= with a custom controlfunction is not supported yet: per-instance plants run under the fused laws (LQR, TrackingLQR, OpenLoop, PID)")
@@ -782,7 +836,19 @@ def simulate(mechanism, tend_or_storage, controller, record=True, z0=None, fric=
     if (noise is not None or noise_seed is not None) and noise_scale is None:
         noise_scale = 1.0
     ph = None if plants is None else plants.handle(dev)
-    if getattr(controller, "controlfunction", None) is not None:
+    scores = None
+    if score is not None:
+        ctrl = controller._ctrl_handle(dev, fric=fric, noise_scale=0.0 if noise_scale is None else noise_scale, noise_seed=noise_seed)
+        sh = None
+        try:
+            sh = score._handle(dev)
+            traj = np.zeros((z0.shape[0], steps, nb, 13)) if record else None
+            zT, status, scores = _capi.rollout_scored(dev, ctrl, sh, z0, steps, int(chunk_steps), noise=noise, first_instance=first_instance, plants=ph, traj_out=traj)
+        finally:
+            if sh is not None:
+                sh.close()
+            ctrl.close()
+    elif getattr(controller, "controlfunction", None) is not None:
         # a custom controlfunction (lqr.jl:14): the closure owns the whole law, as in the reference -- the built-in extras do not apply on top of it
         if fric is not None or noise is not None or noise_seed is not None:
             raise ValueError("fric / noise are options of the built-in laws; a custom controlfunction computes its own inputs")
@@ -799,5 +865,8 @@ def simulate(mechanism, tend_or_storage, controller, record=True, z0=None, fric=
         tend_or_storage.z = traj
         tend_or_storage.n_inst = z0.shape[0]
         tend_or_storage.status, tend_or_storage.zT = status, zT
+        tend_or_storage.score = scores
         return tend_or_storage
-    return Storage(steps, nb, z0.shape[0], traj if record else np.zeros((z0.shape[0], 0, nb, 13)), status, zT)
+    out = Storage(steps, nb, z0.shape[0], traj if record else np.zeros((z0.shape[0], 0, nb, 13)), status, zT)
+    out.score = scores
+    return out

@@ -40,7 +40,9 @@ extern "C" {
  * Still 202 (additive, no struct changed; tests/test_plants_host.py pins the number): one controller per plant -- cclqr_linearize_plants and
  * cclqr_ctrl_create_lqr_batch_plants.  A shim that needs them looks the symbols up: a 202 library built before them lacks them.
  * Still 202 (additive, no struct changed): one TrackingLQR per plant or trajectory -- cclqr_ctrl_create_tracking_batch_plants -- and the gain inspector
- * cclqr_ctrl_get_gains; looked up the same way. */
+ * cclqr_ctrl_get_gains; looked up the same way.
+ * Still 202 (additive, no struct changed): scoring a rollout on the device -- the opaque cclqr_score with cclqr_score_create / cclqr_score_destroy, and cclqr_rollout_score;
+ * looked up the same way. */
 #define CCLQR_ABI_VERSION 202
 
 #define CCLQR_REVOLUTE 0      /* EqualityConstraint(Revolute(a, b, axis; p1, p2, qoffset)),  examples/lqr_cartpole.jl:26 */
@@ -360,6 +362,31 @@ int cclqr_ctrl_create_tracking_batch_plants(const cclqr_mech *m, const cclqr_pla
 /* lqr.K[k][i] (src/control/lqr.jl:4, lqr_tracking.jl:4) of one table of a controller, read back from the device: K_host [nK][mu][12 nb] in the caller's body order,
  * table in [0, n_ctrl).  For any controller that has gains, however it was built.  CCLQR_EINVAL for a table out of range or a controller without gains. */
 int cclqr_ctrl_get_gains(const cclqr_mech *m, const cclqr_ctrl *c, int64_t table, double *K_host);
+
+/* Scoring a rollout on the device (additive, still 202, no struct changed; looked up by name like the entries above).  The reference ranks a run by the
+ * quadratic cost its gains were designed to minimise -- the weights Q, R handed to LQR(...) and scaled by Δt at src/control/lqr.jl:18-19, on the error
+ * Δz of control_lqr! (lqr.jl:92-103: per body x - xd, v - vd, vec(qd \ q), ω - ωd) and the feedback command Δu = -K[k] Δz of lqr.jl:106-111 -- but has no
+ * function that evaluates it: a user reads it off the recorded Storage (lqr_tracking.jl:32-35).  Here it is a reduction over the slab a rollout launch
+ * has just written: score[i] = { Jx = sum_k cx_k, Ju = sum_k cu_k, peak = max_k cx_k, last_out = the largest k with cx_k > settle_tol (0: none) } with
+ * cx_k = sum_b Δz_b' Qb[b] Δz_b and cu_k = Δu_k' R Δu_k; friction, noise and PID terms are plant and disturbance, not part of Δu.  A non-finite cx_k makes
+ * Jx and peak NaN and sets last_out = k.
+ * cclqr_score_create -- the weights of LQR(mechanism, bodyids, eqcids, Q, R, horizon) (lqr.jl:49-66) as a device object: Qb [nb][12][12] per-body blocks in the
+ * caller's body order, used as written (symmetric or not), R [mu][mu], both already Δt-scaled (lqr.jl:18-19); HOST pointers.  CCLQR_EINVAL for a
+ * non-finite weight or settle_tol. */
+typedef struct cclqr_score cclqr_score;   /* opaque: device-resident weights */
+#define CCLQR_SCORE_LEN 4
+int cclqr_score_create(const cclqr_mech *m, const double *Qb, int32_t mu, const double *R, double settle_tol, cclqr_score **out);
+int cclqr_score_destroy(cclqr_score *s);
+/* cclqr_rollout_score -- the cost of simulate!(mechanism, steps, controller; record = true) (examples/lqr_cartpole.jl:44) under control_lqr! (lqr.jl:89-139) /
+ * control_trackinglqr! (lqr_tracking.jl:46-71): instance i (global index first_instance + i: its controller table when the controller has several), steps
+ * k = k0 .. k0 + steps - 1 (1-based), traj_dev [n_inst][steps][nb][13] as cclqr_rollout_* wrote it (the state the law saw at step k), setpoint row
+ * min(k, nsp) - 1, gain min(k, nK) - 1 gated by k < N (N <= 0: gain 0, always).  DEVICE pointers, asynchronous on `stream`.  score_dev [n_inst][CCLQR_SCORE_LEN]
+ * is read when k0 > 1 and always written, and an instance's steps are accumulated in step order: a horizon scored chunk by chunk (the k0 continuation of
+ * cclqr_rollout_ex into one small slab) gives bitwise the score of one call.  A lost instance is scored on its frozen pose: read `status`.
+ * CCLQR_EINVAL, before anything is launched: mu differs from the controller's, the controller has no setpoint table, first_instance + n_inst > n_ctrl for a
+ * controller with several tables, steps < 1 or k0 < 1, a handle made for another mechanism or device.  Every topology cclqr_mech_create takes. */
+int cclqr_rollout_score(const cclqr_mech *m, const cclqr_ctrl *c, const cclqr_score *s, int64_t n_inst, int32_t steps, int32_t k0,
+                        int64_t first_instance, const double *traj_dev, double *score_dev, void *stream);
 
 /* cclqr_rollout (HOST pointers) with options: first_instance and newton_mode apply, the device-buffer fields must be NULL. */
 int cclqr_rollout_host_ex(const cclqr_mech *m, const cclqr_ctrl *c, int64_t n_inst, int32_t steps, int32_t k0, const double *z0,

@@ -386,6 +386,36 @@ function ctrl_gains(h::MechHandle, c::Ptr{Cvoid}, table::Integer, nK::Integer, m
     K
 end
 
+"The weights a run is ranked by, on the device (cclqr_score_create): Qb is 12 x 12 x Nb -- body b's block TRANSPOSED into Julia's column-major order, i.e.
+ Qb[:, :, b] = Q[b]' -- in the order of mech_tables, R is mu x mu transposed likewise; both already scaled by Δt (lqr.jl:18-19).  settle_tol: the stage cost under
+ which an instance counts as settled."
+mutable struct ScoreHandle
+    ptr::Ptr{Cvoid}
+    mech::MechHandle
+end
+function ScoreHandle(h::MechHandle, Qb::Array{Float64}, R::Array{Float64}, mu::Integer; settle_tol = 0.0)
+    out = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:cclqr_score_create, lib), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int32, Ptr{Float64}, Float64, Ref{Ptr{Cvoid}}), h.ptr, Qb, Int32(mu), R, settle_tol, out))
+    obj = ScoreHandle(out[], h)
+    finalizer(o -> ccall((:cclqr_score_destroy, lib), Cint, (Ptr{Cvoid},), o.ptr), obj)
+    obj
+end
+
+"Score the slab a rollout_dev! launch has just written (cclqr_rollout_score; device pointers, asynchronous on `stream`): score is 4 x n = (Jx, Ju, peak, last_out) per
+ instance, read when k0 > 1 and always written, so that a horizon rolled out chunk by chunk into one small slab (k0 continuation: carry z, lam, status with
+ ROLLOUT_CARRY_STATUS, the PID state) is scored bitwise as one launch would be:
+     for k0 in 1:chunk:steps
+         s = min(chunk, steps - k0 + 1)
+         rollout_dev!(h, c, n, s, k0, z, lam, slab, zn, status; flags = ROLLOUT_CARRY_STATUS, stream = stream)
+         rollout_score!(h, c, sc, n, s, k0, slab, score; stream = stream)
+         z, zn = zn, z
+     end"
+function rollout_score!(h::MechHandle, c::CtrlHandle, s::ScoreHandle, n::Integer, steps::Integer, k0::Integer, traj::Ptr{Float64}, score::Ptr{Float64};
+                        first_instance = 0, stream::Ptr{Cvoid} = C_NULL)
+    check(ccall((:cclqr_rollout_score, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int32, Int32, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Cvoid}),
+                h.ptr, c.ptr, s.ptr, n, steps, k0, first_instance, traj, score, stream))
+end
+
 "Size the controller handle's Philox workspace before step-per-launch rollouts are captured into a hipGraph (cclqr_ctrl_reserve_noise)."
 reserve_noise!(c::CtrlHandle, n::Integer, steps::Integer) = check(ccall((:cclqr_ctrl_reserve_noise, lib), Cint, (Ptr{Cvoid}, Int64, Int32), c.ptr, n, steps))
 
