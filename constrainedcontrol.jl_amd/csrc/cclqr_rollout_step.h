@@ -8,6 +8,21 @@
 
 namespace cclqr {
 
+// ---- hand-over of the LDS image from one phase of a step to the next, for kernels whose workgroup is ONE wavefront (WAVE_BLOCK threads).
+// Sufficient because the LDS executes one wavefront's instructions in issue order: a read issued behind a store sees the stored data whichever lane
+// stored it, and a store issued behind a read cannot overtake it.  So the hand-over is a compiler ordering point only -- a wavefront-scope fence emits
+// no instruction and no memory operation is moved across it -- where __syncthreads() also drains the LDS queue (s_waitcnt lgkmcnt(0)) before the
+// next phase may issue its first read.  Kernels with more than one wavefront per workgroup need the real barrier and never use this.
+// Nothing on the host, where builds of these headers run one lane at a time.  (An inlined function, not the builtin written in place: the two compile to
+// different schedules of the headline kernel -- 72 full drains and 9 176 instructions this way, 73 and 9 193 the other -- and this one is the one measured.)
+constexpr int WAVE_BLOCK = 64;
+__device__ __forceinline__ void wave_handover() {
+#if defined(__HIP_DEVICE_COMPILE__)
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+#endif
+}
+#define WAVE_HANDOVER() wave_handover()
+
 // dynamic per-lane data of the owned link.  The velocity part of the state is s itself: the solution (v+, w+) of one step is
 // the state's (v, w) at the next knot and the Newton start of the next step.
 struct LinkS {

@@ -236,8 +236,9 @@ hipError_t launch_philox_fill(double* out, unsigned key0, long long inst0, long 
 // KL, NL: several lanes per link (cclqr_chain.h "SEVERAL LANES PER LINK"): lane t of a group is sub-lane w = t / NL of link tl = t % NL; a mechanism of at most NL
 // links whose lane group has KL NL <= G lanes.  KL = 1 (NL = G): one lane per link, the kernels of rounds 2-4, bit for bit.
 template <int G, int NBP, int EXTRA, bool RELAX = false, int KL = 1, int NL = G>
-__global__ __launch_bounds__(64) void rollout_chain_kernel(RolloutArgs a) {
+__global__ __launch_bounds__(WAVE_BLOCK) void rollout_chain_kernel(RolloutArgs a) {
     extern __shared__ double lds[];
+    static_assert(WAVE_BLOCK == 64, "WAVE_HANDOVER orders the phases of ONE wavefront: the workgroup is exactly 64 threads");
     static_assert(KL >= 1 && KL <= 3 && KL * NL <= G && (KL > 1 || NL == G) && (KL == 1 || NL <= NBP), "lane group too small for KL lanes per link");
     const int lane = threadIdx.x, t = lane % G, grp = lane / G;
     const int w = KL > 1 ? t / NL : 0;                      // sub-lane of the lane's link
@@ -295,7 +296,7 @@ __global__ __launch_bounds__(64) void rollout_chain_kernel(RolloutArgs a) {
 #pragma unroll
         for (int i = 0; i < 5; i++) L[Y.LAM + 5 * tl + i] = warm ? a.lam[inst * 5 * nb + 5 * tl + i] : 0.0;
     }
-    __syncthreads();
+    WAVE_HANDOVER();
 
 #ifdef CCLQR_PROFILE
     Prof prof;
@@ -375,9 +376,9 @@ __global__ __launch_bounds__(64) void rollout_chain_kernel(RolloutArgs a) {
                 if (EXTRA && (C->flags & CtrlHot::FRIC) && c.has_fric()) uj = ck_friction(c, zf, za);
             }
         }
-        // ONE barrier for the staged row and the control error: they lie side by side in the image (Y.Z, Y.DZ), which nothing writes again before the
-        // barrier in front of the Newton solve -- the forces phase writes GKA / D / C only
-        __syncthreads();
+        // ONE hand-over for the staged row and the control error: they lie side by side in the image (Y.Z, Y.DZ), which nothing writes again before the
+        // hand-over in front of the Newton solve -- the forces phase writes GKA / D / C only
+        WAVE_HANDOVER();
         if (gate) {     // u_i = Fd_i - K_i . dz for the mu inputs (feedback_inputs, cclqr_rollout_step.h)
             constexpr int NE = GainRows<G, NBP>::NE;
             double unoise = 0.0;                    // noise: injected by the caller, or generated for this launch by philox_fill_kernel
@@ -442,7 +443,7 @@ __global__ __launch_bounds__(64) void rollout_chain_kernel(RolloutArgs a) {
                 for (int i = 0; i < 6; i++) L[Y.C + 6 * tl + i] = own[i] + (c.has_c() ? cpar[i] : 0.0);
             }
         }
-        __syncthreads();
+        WAVE_HANDOVER();
 
         STAMP(PF_FORCES);
         PCOUNT(PF_STEPS);
@@ -461,7 +462,7 @@ __global__ __launch_bounds__(64) void rollout_chain_kernel(RolloutArgs a) {
                 const double nf = chain_eval<G, true, KL>(c, S, tl, Y, L, 0.0, c.live() && need_jac, need_jac, dt, Q PROF_PASS);
                 if (iter == 1) normf0 = nf;
             }
-            __syncthreads();
+            WAVE_HANDOVER();
             if (!__any(!done)) break;
             PCOUNT(PF_NEWTON_ITERS);
             const bool active = c.live() && !done;
@@ -482,12 +483,12 @@ __global__ __launch_bounds__(64) void rollout_chain_kernel(RolloutArgs a) {
                     cr_phase_a<CRW>(CK, L, tc);
                     CR_FLAGS_FRESH(CK);
                     cr_store_a<CRW>(CK, L, tc);
-                    __syncthreads();
+                    WAVE_HANDOVER();
                     CR_FLAGS_FRESH(CK);
                     cr_phase_b<CRW>(CK, L, tc);
                     CR_FLAGS_FRESH(CK);
                     cr_store_b<CRW>(CK, L, tc);
-                    __syncthreads();
+                    WAVE_HANDOVER();
                 }
                 STAMP(PF_SCHUR_W);
                 const TriPlanB PB = cr ? tri_plan_balanced(cs, (cn + 1) / 2, 2) : tri_plan_balanced(cs, cn, 1, G >= 16 ? 2 : 1);
@@ -498,18 +499,18 @@ __global__ __launch_bounds__(64) void rollout_chain_kernel(RolloutArgs a) {
                     double tg[5], zy[5];
                     int otg = 0, oout = 0;
                     if (tri_step(K, i, L, tg, zy, &otg, &oout)) tri_step_store(L, otg, oout, tg, zy);
-                    __syncthreads();
+                    WAVE_HANDOVER();
                 }
                 STAMP(PF_TRI_FWD);
                 if (!done) ck_tri_mid<(G >= 16)>(t, PB, Y, L);      // (8 lanes: one front, no plan merges)
-                __syncthreads();
+                WAVE_HANDOVER();
                 for (int j = 0; j < P.steps; j++) {
                     if (!done) ck_tri_back(t, j, PB, Y, L);
-                    __syncthreads();
+                    WAVE_HANDOVER();
                 }
                 if (CR && cr) {
                     cr_back<CRW>(t, cs, cn, 1, Y, L, done);
-                    __syncthreads();
+                    WAVE_HANDOVER();
                 }
                 STAMP(PF_TRI_BWD);
             }
@@ -536,7 +537,7 @@ __global__ __launch_bounds__(64) void rollout_chain_kernel(RolloutArgs a) {
                 }
                 nd = sqrt(group_sum<G>(pdn));
             }
-            __syncthreads();
+            WAVE_HANDOVER();
             STAMP(PF_BODY_SOLVE);
             // line search: halve while ||f|| grows.  The first (full-step) trial also evaluates the Jacobians and the Schur blocks,
             // speculating that it is accepted and the solve goes on; later trials evaluate the residual only.
@@ -701,7 +702,7 @@ __global__ __launch_bounds__(64) void rollout_chain_kernel(RolloutArgs a) {
     prof.flush();
 #endif
     // ---------------- final state, multipliers, status
-    __syncthreads();
+    WAVE_HANDOVER();
     if (c.live() && (KL == 1 || c.prim())) {
         const int ub = plan >> 24;
 #pragma unroll
@@ -709,7 +710,7 @@ __global__ __launch_bounds__(64) void rollout_chain_kernel(RolloutArgs a) {
 #pragma unroll
         for (int i = 0; i < 6; i++) L[Y.Z + 13 * ub + 7 + i] = S.s[i];
     }
-    __syncthreads();
+    WAVE_HANDOVER();
     asm volatile("" : "+s"(ap));
     LINK_FLAGS_FRESH(c);
     if (c.valid()) {
@@ -751,7 +752,7 @@ static hipError_t launch_chain_one(const RolloutArgs& a, ControlLaw law, bool re
         case ControlLaw::PhiloxInKernel: kern = rollout_chain_kernel<G, NBP, 3, false, KL, NL>; break;
     }
     if (!kern) return hipErrorInvalidValue;
-    return launch_lds(kern, dim3(grid), dim3(64), lds, stream, a);
+    return launch_lds(kern, dim3(grid), dim3(WAVE_BLOCK), lds, stream, a);      // (one wavefront: what WAVE_HANDOVER rests on)
 }
 
 hipError_t launch_rollout_chain(const RolloutArgs& a_in, const RolloutShape& s, int simds, ControlLaw law, int newton_mode, hipStream_t stream) {
