@@ -20,11 +20,40 @@ using namespace cclqr;
 
 static thread_local std::string g_err;
 static int fail(int code, const std::string& msg) { g_err = msg; return code; }
-#define HIPCHK(x)                                                                                         \
-    do {                                                                                                  \
-        hipError_t e_ = (x);                                                                              \
-        if (e_ != hipSuccess) return fail(CCLQR_EHIP, std::string(#x) + ": " + hipGetErrorString(e_));   \
+// every step of an entry point is a checked call that returns on failure -- HIPTRY with the entry point's own prefix, HIPCHK with the call's text, TRY for a
+// step that has set the error itself; what the entry point holds by then is released by its scope guards (Owned, DevBlocks, WsScope)
+#define HIPTRY(prefix, x)                                                                                           \
+    do {                                                                                                            \
+        hipError_t e_ = (x);                                                                                        \
+        if (e_ != hipSuccess) return fail(CCLQR_EHIP, std::string(prefix) + ": " + hipGetErrorString(e_));         \
     } while (0)
+#define HIPCHK(x) HIPTRY(#x, x)
+#define TRY(x)                            \
+    do {                                  \
+        const int rc_ = (x);              \
+        if (rc_ != CCLQR_OK) return rc_;  \
+    } while (0)
+namespace {
+// a handle under construction: destroyed by its own cclqr_*_destroy unless the entry point hands it out
+template <class T, int (*Destroy)(T*)>
+struct Owned {
+    T* p;
+    explicit Owned(T* q) : p(q) {}
+    Owned(const Owned&) = delete;
+    ~Owned() { (void)Destroy(p); }
+    T* release() { T* q = p; p = nullptr; return q; }
+};
+// raw hipMalloc blocks of one call.  A return that has not released them first waits for the call's stream: nothing of the call may still run on what is freed
+struct DevBlocks {
+    hipStream_t stream;
+    void *a = nullptr, *b = nullptr;
+    bool released = false;
+    explicit DevBlocks(hipStream_t s) : stream(s) {}
+    DevBlocks(const DevBlocks&) = delete;
+    void release() { if (a) (void)hipFree(a); if (b) (void)hipFree(b); a = b = nullptr; released = true; }
+    ~DevBlocks() { if (!released) { (void)hipStreamSynchronize(stream); release(); } }
+};
+}  // namespace
 
 extern "C" const char* cclqr_last_error(void) { return g_err.c_str(); }
 
@@ -62,7 +91,7 @@ static hipError_t ws_get(void** p, size_t bytes) {
                              [](int d) { (void)hipSetDevice(d); });
     return rc < 0 ? hipErrorInvalidDevice : (hipError_t)rc;
 }
-struct WsScope { ~WsScope() { g_ws.used = 0; } };     // every block is free again when the entry point returns
+namespace { struct WsScope { WsMark mark{g_ws}; }; }     // the blocks the entry point took are free again when it returns
 // blocks of a thread that exits without calling this stay allocated until the process ends (thread_local destructors must not call
 // into a HIP runtime that may already be shutting down)
 extern "C" int cclqr_release_workspaces(void) {
@@ -103,39 +132,38 @@ extern "C" int cclqr_abi_layout(int32_t* out, int32_t n) {
     return CCLQR_ABI_LAYOUT_LEN;
 }
 extern "C" int cclqr_device_count(int32_t* n) {
-    int c = 0;
-    hipError_t e = hipGetDeviceCount(&c);
+    if (!n) return fail(CCLQR_EINVAL, "null argument");
+    const hipError_t e = hipGetDeviceCount(n);
     if (e != hipSuccess) { *n = 0; return fail(CCLQR_EHIP, hipGetErrorString(e)); }
-    *n = c;
     return CCLQR_OK;
 }
 extern "C" int cclqr_set_device(int32_t dev) { HIPCHK(hipSetDevice(dev)); return CCLQR_OK; }
 
 extern "C" int cclqr_mech_create(const cclqr_mech_desc* d, cclqr_mech** out) {
     if (!d || !out) return fail(CCLQR_EINVAL, "null argument");
-    cclqr_mech* m = new cclqr_mech();
+    Owned<cclqr_mech, cclqr_mech_destroy> own(new cclqr_mech());
+    cclqr_mech* m = own.p;
     std::string err;
-    int rc = build_mech_tables(d, m, err);
-    if (rc != CCLQR_OK) { delete m; return fail(rc, err); }
+    const int rc = build_mech_tables(d, m, err);
+    if (rc != CCLQR_OK) return fail(rc, err);
     // branching trees: the tables of the register-resident tree kernel (sibling lists, elimination schedule) ride behind the MechDev in the
     // same allocation (cclqr_treereg.h treereg_of)
     std::vector<char> image(m->host.tree ? treereg_offset() + sizeof(TreeRegDev) : sizeof(MechDev), 0);
     memcpy(image.data(), &m->host, sizeof(MechDev));
     if (m->host.tree && !m->host.loop) {
         TreeRegDev* R = new (image.data() + treereg_offset()) TreeRegDev;
-        if (!build_treereg_tables(m->host, *R, err)) { delete m; return fail(CCLQR_EUNSUPPORTED, err); }
+        if (!build_treereg_tables(m->host, *R, err)) return fail(CCLQR_EUNSUPPORTED, err);
     }
-    hipError_t e = hipGetDevice(&m->device);
-    if (e == hipSuccess) e = hipMalloc((void**)&m->dev, image.size());
-    if (e == hipSuccess) e = hipMemcpy(m->dev, image.data(), image.size(), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { delete m; return fail(CCLQR_EHIP, std::string("mechanism upload: ") + hipGetErrorString(e)); }
+    HIPTRY("mechanism upload", hipGetDevice(&m->device));
+    HIPTRY("mechanism upload", hipMalloc((void**)&m->dev, image.size()));
+    HIPTRY("mechanism upload", hipMemcpy(m->dev, image.data(), image.size(), hipMemcpyHostToDevice));
     // the kernels this mechanism runs on, and the SIMDs of ITS device that a small batch is spread over (spread_instances_per_wavefront): both
     // fixed here, so that no launch queries the runtime (never inside a caller's hipGraph capture)
     m->shape = rollout_shape_of(m->host, m->nb, m->nj);
     int cus = 0;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, m->device) != hipSuccess || cus <= 0) cus = 256;
     m->simds = 4 * cus;
-    *out = m;
+    *out = own.release();
     return CCLQR_OK;
 }
 
@@ -146,57 +174,67 @@ extern "C" int cclqr_mech_destroy(cclqr_mech* m) {
     return CCLQR_OK;
 }
 
-// doubles the rollout kernels' control phase fetches past the end of a gain row: they read ceil(12 NBP / G) G entries of a row (G lanes per instance,
-// the LDS image laid out for NBP >= nb links) and let the surplus meet a zero factor.  Closed-loop kernel: exact row length.
 // one knot of the mechanism's linearisation kernel (launch_linearize) within a CU's 160 KB of LDS
 static bool linearize_fits_lds(const cclqr_mech* m) { return m->shape.lin_lds <= 160 * 1024; }
 
-static size_t gain_row_overrun(const cclqr_mech* m) {
-    const RolloutShape& s = m->shape;
-    if (s.family == RolloutFamily::Loop) return 0;
-    const long long over = (long long)((12 * s.NBP + s.G - 1) / s.G) * s.G - 12LL * m->nb;
-    return over > 0 ? (size_t)((over + 1) & ~1LL) : 0;
+// the controlled joints of a call as the kernels address them: links for chains and trees, the caller's joint numbers for closed loops (their tables keep them)
+static int map_ctrl_joints(const cclqr_mech* m, int mu, const int32_t* ctrl_joint, int* cj) {
+    const bool loop = m->host.loop != 0;
+    const int nj = loop ? m->nj : m->nb;
+    for (int i = 0; i < mu; i++) {
+        if (ctrl_joint[i] < 0 || ctrl_joint[i] >= nj) return fail(CCLQR_EINVAL, "controlled joint out of range");
+        cj[i] = loop ? ctrl_joint[i] : m->link_of_joint[ctrl_joint[i]];
+    }
+    return CCLQR_OK;
 }
 
-extern "C" int cclqr_ctrl_create(const cclqr_mech* m, const cclqr_ctrl_desc* d, cclqr_ctrl** out) {
-    if (!m || !d || !out) return fail(CCLQR_EINVAL, "null argument");
-    { int rc = check_device(m); if (rc != CCLQR_OK) return rc; }
-    CtrlHostTables T;
-    std::string err;
-    int rc = build_ctrl_tables(m, d, T, err);
-    if (rc != CCLQR_OK) return fail(rc, err);
+// a controller handle under construction (ctrl_new), and its last step (ctrl_publish): the tables' addresses into the host record, the record the rollout
+// steps read built from it (after the addresses and strides are final), the whole uploaded
+typedef Owned<cclqr_ctrl, cclqr_ctrl_destroy> CtrlOwner;
+static cclqr_ctrl* ctrl_new(const cclqr_mech* m) {
     cclqr_ctrl* c = new cclqr_ctrl();
     memset(c, 0, sizeof(*c));
     c->nb = m->nb;
     c->device = m->device;
-    hipError_t e = hipMalloc((void**)&c->zd_dev, T.zd.size() * sizeof(double));
-    if (e == hipSuccess) e = hipMemcpy(c->zd_dev, T.zd.data(), T.zd.size() * sizeof(double), hipMemcpyHostToDevice);
-    if (e == hipSuccess && !T.K.empty()) {
-        // CCLQR_K_PAD zero doubles behind the last gain row: the rollout kernels fetch a row in whole strides of their lane group and let the
-        // entries past its end meet a zero factor (rollout_chain.hip, control phase) -- past the LAST row that read must stay inside the table
-        // (one table per instance: each with its own pad, see CCLQR_K_PAD)
-        const size_t ntab = T.H.n_ctrl > 1 ? (size_t)T.H.n_ctrl : 1, per = T.K.size() / ntab, padi = ntab > 1 ? gain_row_overrun(m) : 0;
-        const size_t total = ntab * (per + padi) + CCLQR_K_PAD;
-        e = hipMalloc((void**)&c->K_dev, total * sizeof(double));
-        if (e == hipSuccess) e = hipMemset(c->K_dev, 0, total * sizeof(double));
-        if (e == hipSuccess) e = padi ? hipMemcpy2D(c->K_dev, (per + padi) * sizeof(double), T.K.data(), per * sizeof(double), per * sizeof(double), ntab, hipMemcpyHostToDevice)
-                                      : hipMemcpy(c->K_dev, T.K.data(), T.K.size() * sizeof(double), hipMemcpyHostToDevice);
-        if (ntab > 1) T.H.K_stride = (long long)(per + padi);
-    }
-    if (e == hipSuccess && !T.Fd.empty()) {
-        e = hipMalloc((void**)&c->Fd_dev, T.Fd.size() * sizeof(double));
-        if (e == hipSuccess) e = hipMemcpy(c->Fd_dev, T.Fd.data(), T.Fd.size() * sizeof(double), hipMemcpyHostToDevice);
-        c->Fd_len = T.Fd.size();
-    }
-    c->host = T.H;
+    return c;
+}
+static hipError_t ctrl_publish(cclqr_ctrl* c) {
     c->host.K = c->K_dev; c->host.zd = c->zd_dev; c->host.Fd = c->Fd_dev;
     if (!c->Fd_dev) c->host.Fd_stride = 0;
     if (!c->K_dev) c->host.K_stride = 0;
-    ctrl_hot_build(c->host);      // the record the rollout steps read: after the tables' addresses and strides are final
-    if (e == hipSuccess) e = hipMalloc((void**)&c->dev, sizeof(CtrlDev));
-    if (e == hipSuccess) e = hipMemcpy(c->dev, &c->host, sizeof(CtrlDev), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { cclqr_ctrl_destroy(c); return fail(CCLQR_EHIP, std::string("controller upload: ") + hipGetErrorString(e)); }
-    *out = c;
+    ctrl_hot_build(c->host);
+    const hipError_t e = hipMalloc((void**)&c->dev, sizeof(CtrlDev));
+    return e != hipSuccess ? e : hipMemcpy(c->dev, &c->host, sizeof(CtrlDev), hipMemcpyHostToDevice);
+}
+
+extern "C" int cclqr_ctrl_create(const cclqr_mech* m, const cclqr_ctrl_desc* d, cclqr_ctrl** out) {
+    if (!m || !d || !out) return fail(CCLQR_EINVAL, "null argument");
+    TRY(check_device(m));
+    CtrlHostTables T;
+    std::string err;
+    const int rc = build_ctrl_tables(m, d, T, err);
+    if (rc != CCLQR_OK) return fail(rc, err);
+    CtrlOwner own(ctrl_new(m));
+    cclqr_ctrl* c = own.p;
+    HIPTRY("controller upload", hipMalloc((void**)&c->zd_dev, T.zd.size() * sizeof(double)));
+    HIPTRY("controller upload", hipMemcpy(c->zd_dev, T.zd.data(), T.zd.size() * sizeof(double), hipMemcpyHostToDevice));
+    if (!T.K.empty()) {      // one table, or one per instance behind its own zero pad (gain_table_layout)
+        const size_t ntab = (size_t)T.H.n_ctrl, per = T.K.size() / ntab;
+        const GainTableLayout L = gain_table_layout(m->shape, m->nb, T.H.n_ctrl, (long long)T.H.nK * T.H.mu);
+        HIPTRY("controller upload", hipMalloc((void**)&c->K_dev, L.alloc_doubles * sizeof(double)));
+        HIPTRY("controller upload", hipMemset(c->K_dev, 0, L.alloc_doubles * sizeof(double)));
+        HIPTRY("controller upload", L.pad ? hipMemcpy2D(c->K_dev, (size_t)L.stride * sizeof(double), T.K.data(), per * sizeof(double), per * sizeof(double), ntab, hipMemcpyHostToDevice)
+                                          : hipMemcpy(c->K_dev, T.K.data(), T.K.size() * sizeof(double), hipMemcpyHostToDevice));
+        if (ntab > 1) T.H.K_stride = L.K_stride;
+    }
+    if (!T.Fd.empty()) {
+        HIPTRY("controller upload", hipMalloc((void**)&c->Fd_dev, T.Fd.size() * sizeof(double)));
+        HIPTRY("controller upload", hipMemcpy(c->Fd_dev, T.Fd.data(), T.Fd.size() * sizeof(double), hipMemcpyHostToDevice));
+        c->Fd_len = T.Fd.size();
+    }
+    c->host = T.H;
+    HIPTRY("controller upload", ctrl_publish(c));
+    *out = own.release();
     return CCLQR_OK;
 }
 
@@ -225,118 +263,140 @@ __global__ void k_rows_to_link_order_kernel(double* K, long long nrows, long lon
     for (int e = threadIdx.x; e < 12 * nb; e += blockDim.x) { const int l = e / 12; p[e] = row[12 * M->perm[l] + (e - 12 * l)]; }
 }
 
-// cclqr_linearize_plants / cclqr_ctrl_create_lqr_batch_plants: knot k of the launch must find its plant, the one with global index first_plant + k (no device work)
-static int plants_check_range(const cclqr_mech* m, const cclqr_plants* plants, int64_t first_plant, int64_t nk) {
+// are the n items (`what`: knots = plants of a call, instances of a launch) first .. first + n - 1 all among the table's plants?  Item k runs on the plant with
+// global index first + k.  No device work, and no std::string unless the answer is no (cclqr_rollout_plants is on the per-step host path)
+static int plants_check_range(const cclqr_mech* m, const cclqr_plants* plants, int64_t first, int64_t n, const char* what, const char* of) {
     if (!plants) return CCLQR_OK;
-    if (m->host.loop) return fail(CCLQR_EUNSUPPORTED, "per-instance plants are for forests of chains and branching trees (closed-loop mechanisms run their own plant)");
     if (plants->mech != m) return fail(CCLQR_EINVAL, "the plants were created for another mechanism");
-    const int64_t lo = first_plant - plants->first_index;
-    if (nk > 0 && (lo < 0 || lo + nk > plants->n_plant))
-        return fail(CCLQR_EINVAL, "plants " + std::to_string(first_plant) + " .. " + std::to_string(first_plant + nk - 1) + " of the call are not all among the plants " +
+    const int64_t lo = first - plants->first_index;
+    if (n > 0 && (lo < 0 || lo + n > plants->n_plant))
+        return fail(CCLQR_EINVAL, std::string(what) + " " + std::to_string(first) + " .. " + std::to_string(first + n - 1) + " of the " + of + " are not all among the plants " +
                                   std::to_string(plants->first_index) + " .. " + std::to_string(plants->first_index + plants->n_plant - 1));
     return CCLQR_OK;
 }
 
-// the batched constructors' RicArgs.p_rows: the kernels that assume a symmetric Pk only when Q and R are EXACTLY symmetric (cclqr_riccati's rule, run_riccati)
-static int batch_p_rows(const double* Q, int mx, const double* R, int mu) { return (ric_symmetric(Q, mx) && ric_symmetric(R, mu)) ? 0 : 1; }
+// ---- linearising nk host knots into the calling thread's workspace: the one sequence behind cclqr_linearize_plants, the analytic cclqr_linearize_projected,
+// cclqr_riccati_tracking_ex and cclqr_ctrl_create_lqr_batch_plants
+struct LinWs { double *zd, *Fd, *A, *Bu, *Bl, *G; int* status; int cj[CCLQR_MAXL]; };      // cj: the controlled joints as the kernels address them
+// what such a call is refused for before anything is allocated; cj = the controlled joints as the kernels address them.  No knots: nothing else is looked at
+static int linearize_check(const cclqr_mech* m, const cclqr_plants* plants, int64_t first_plant, int nk, int mu, const int32_t* ctrl_joint, int* cj) {
+    TRY(check_device(m));
+    if (plants && m->host.loop)
+        return fail(CCLQR_EUNSUPPORTED, "per-instance plants are for forests of chains and branching trees (closed-loop mechanisms run their own plant)");
+    TRY(plants_check_range(m, plants, first_plant, nk, "plants", "call"));
+    if (nk == 0) return CCLQR_OK;
+    if (!linearize_fits_lds(m)) return fail(CCLQR_EUNSUPPORTED, "instance does not fit LDS");
+    return map_ctrl_joints(m, mu, ctrl_joint, cj);
+}
+// The checks, the blocks (inside the caller's WsScope), the upload of the knots (Fd_host null: w.Fd stays what the caller set -- a device table, or none) and
+// the launch on the null stream; the models stay on the device and w.cj keeps the mapped joints for a caller that needs them.  `prefix` words a HIP failure
+static int linearize_to_ws(const cclqr_mech* m, const cclqr_plants* plants, int64_t first_plant, int nk, const double* zd_host, const double* Fd_host, int mu,
+                           const int32_t* ctrl_joint, LinWs& w, const char* prefix) {
+    TRY(linearize_check(m, plants, first_plant, nk, mu, ctrl_joint, w.cj));
+    if (nk == 0) return CCLQR_OK;
+    LinArgs a;
+    memset(&a, 0, sizeof(a));
+    memcpy(a.cj, w.cj, sizeof(a.cj));
+    const size_t n = (size_t)nk, nz = 13 * (size_t)m->nb, mx = 12 * (size_t)m->nb, ml = 5 * (size_t)(m->host.loop ? m->nj : m->nb), mu1 = (size_t)(mu > 0 ? mu : 1);
+    HIPTRY(prefix, ws_get((void**)&w.zd, n * nz * sizeof(double)));
+    if (Fd_host && mu > 0) HIPTRY(prefix, ws_get((void**)&w.Fd, n * mu * sizeof(double)));
+    HIPTRY(prefix, ws_get((void**)&w.A, n * mx * mx * sizeof(double)));
+    HIPTRY(prefix, ws_get((void**)&w.Bu, n * mx * mu1 * sizeof(double)));
+    HIPTRY(prefix, ws_get((void**)&w.Bl, n * mx * ml * sizeof(double)));
+    HIPTRY(prefix, ws_get((void**)&w.G, n * ml * mx * sizeof(double)));
+    HIPTRY(prefix, ws_get((void**)&w.status, n * sizeof(int)));
+    HIPTRY(prefix, hipMemcpy(w.zd, zd_host, n * nz * sizeof(double), hipMemcpyHostToDevice));
+    if (Fd_host && mu > 0) HIPTRY(prefix, hipMemcpy(w.Fd, Fd_host, n * mu * sizeof(double), hipMemcpyHostToDevice));
+    a.M = m->dev; a.nk = nk; a.mu = mu;
+    a.plants = plants ? plants->dev : nullptr;
+    a.plant_off = plants ? first_plant - plants->first_index : 0;
+    a.zd = w.zd; a.Fd = w.Fd; a.A = w.A; a.Bu = w.Bu; a.Bl = w.Bl; a.G = w.G; a.status = w.status;
+    HIPTRY(prefix, launch_linearize(a, m->shape, nullptr));
+    return CCLQR_OK;
+}
+// the Newton statuses of nk linearised knots, read back: *bad = the first knot whose setpoint solve did not converge, -1 when all did (the caller words the refusal)
+static hipError_t knots_converged(const int* status_dev, size_t nk, long long* bad) {
+    std::vector<int> st(nk);
+    *bad = -1;
+    const hipError_t e = hipMemcpy(st.data(), status_dev, nk * sizeof(int), hipMemcpyDeviceToHost);
+    for (size_t k = 0; k < nk && e == hipSuccess && *bad < 0; k++)
+        if (st[k] <= 0) *bad = (long long)k;
+    return e;
+}
+static int knot_not_converged(long long k) { return fail(CCLQR_ENOCONV, "Newton did not converge at the setpoint of knot " + std::to_string(k)); }
 
 extern "C" int cclqr_ctrl_create_lqr_batch_plants(const cclqr_mech* m, const cclqr_plants* plants, int64_t first_plant, int32_t n_ctrl, const double* zd, int32_t mu,
                                                   const int32_t* ctrl_joint, const double* Fd, const double* Q, const double* R, int32_t N, int32_t infinite_horizon,
                                                   double tol, int32_t* kbreak, cclqr_ctrl** out) {
+    static const char* const what = "batched LQR construction";
     const bool inf = infinite_horizon != 0;
     if (!m || !zd || !Q || !out || (mu > 0 && (!ctrl_joint || !R))) return fail(CCLQR_EINVAL, "null argument");
-    { int rc = check_device(m); if (rc != CCLQR_OK) return rc; }
+    TRY(check_device(m));
     if (m->host.loop) return fail(CCLQR_EUNSUPPORTED, "batched LQR construction is for tree mechanisms (closed loops: cclqr_linearize_projected)");
     if (n_ctrl < 1 || N < 2 || mu < 1 || mu > m->nb) return fail(CCLQR_EINVAL, "bad sizes");
-    { int rc = plants_check_range(m, plants, first_plant, n_ctrl); if (rc != CCLQR_OK) return rc; }
     const int nb = m->nb;
     const size_t nz = 13 * (size_t)nb, mx = 12 * (size_t)nb, ml = 5 * (size_t)nb, np = (size_t)n_ctrl;
-    if (!linearize_fits_lds(m)) return fail(CCLQR_EUNSUPPORTED, "instance does not fit LDS");
-    LinArgs la;
-    memset(&la, 0, sizeof(la));
-    la.M = m->dev; la.nk = n_ctrl; la.mu = mu;
-    la.plants = plants ? plants->dev : nullptr;
-    la.plant_off = plants ? first_plant - plants->first_index : 0;
-    cclqr_ctrl* c = new cclqr_ctrl();
-    memset(c, 0, sizeof(*c));
-    c->nb = nb;
-    c->device = m->device;
+    CtrlOwner own(ctrl_new(m));
+    cclqr_ctrl* c = own.p;
     CtrlDev& H = c->host;
     // LQR{T,Inf} (lqr.jl:25-27, 40-43): the recursion runs its N = Ntemp steps, only Ku[1] is kept and the feedback is never gated
     const size_t nKtab = inf ? 1 : (size_t)(N - 1);
     H.mu = mu; H.nK = (int)nKtab; H.N = inf ? 0 : N; H.nsp = 1; H.n_ctrl = n_ctrl;
-    for (int i = 0; i < mu; i++) {
-        if (ctrl_joint[i] < 0 || ctrl_joint[i] >= nb) { delete c; return fail(CCLQR_EINVAL, "controlled joint out of range"); }
-        la.cj[i] = m->link_of_joint[ctrl_joint[i]];
-        H.cj[i] = la.cj[i];
-    }
-    const size_t padi = n_ctrl > 1 ? gain_row_overrun(m) : 0;       // every instance's table ends in its own zero pad (CCLQR_K_PAD)
-    const long long tab_stride = (long long)nKtab * mu * (long long)mx + (long long)padi;
-    H.K_stride = n_ctrl > 1 ? tab_stride : 0;
+    const GainTableLayout L = gain_table_layout(m->shape, nb, n_ctrl, (long long)nKtab * mu);      // every instance's table ends in its own zero pad
+    H.K_stride = L.K_stride;
     H.zd_stride = n_ctrl > 1 ? (long long)nz : 0;
     H.Fd_stride = (n_ctrl > 1 && Fd) ? mu : 0;
     // setpoints in link order for the rollout's control law
     std::vector<double> zl(np * nz);
     for (size_t s = 0; s < np; s++)
         for (int l = 0; l < nb; l++) memcpy(&zl[(s * nb + l) * 13], zd + (s * nb + m->host.perm[l]) * 13, 13 * sizeof(double));
-    const size_t nK = np * (size_t)tab_stride;
-    double *dzd = nullptr, *dA = nullptr, *dBu = nullptr, *dBl = nullptr, *dG = nullptr, *dQ = nullptr, *dR = nullptr, *dwork = nullptr;
-    int *dlst = nullptr, *dkb = nullptr, *dst = nullptr, *dstop = nullptr;
-    std::vector<int> lst(np), kb(np), st(np);
+    double *dQ = nullptr, *dR = nullptr, *dwork = nullptr;
+    int *dkb = nullptr, *dst = nullptr, *dstop = nullptr;
+    std::vector<int> kb(np), st(np);
     WsScope scope;
-    hipError_t e = hipMalloc((void**)&c->zd_dev, np * nz * sizeof(double));
-    if (e == hipSuccess) e = hipMemcpy(c->zd_dev, zl.data(), np * nz * sizeof(double), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMalloc((void**)&c->K_dev, (nK + CCLQR_K_PAD) * sizeof(double));      // (padding: see cclqr_ctrl_create)
-    if (e == hipSuccess && Fd) {
-        e = hipMalloc((void**)&c->Fd_dev, np * mu * sizeof(double));
-        if (e == hipSuccess) e = hipMemcpy(c->Fd_dev, Fd, np * mu * sizeof(double), hipMemcpyHostToDevice);
+    HIPTRY(what, hipMalloc((void**)&c->zd_dev, np * nz * sizeof(double)));
+    HIPTRY(what, hipMemcpy(c->zd_dev, zl.data(), np * nz * sizeof(double), hipMemcpyHostToDevice));
+    HIPTRY(what, hipMalloc((void**)&c->K_dev, L.alloc_doubles * sizeof(double)));
+    if (Fd) {
+        HIPTRY(what, hipMalloc((void**)&c->Fd_dev, np * mu * sizeof(double)));
+        HIPTRY(what, hipMemcpy(c->Fd_dev, Fd, np * mu * sizeof(double), hipMemcpyHostToDevice));
         c->Fd_len = (size_t)np * mu;
     }
-    if (e == hipSuccess) e = ws_get((void**)&dzd, np * nz * sizeof(double));
-    if (e == hipSuccess) e = ws_get((void**)&dA, np * mx * mx * sizeof(double));
-    if (e == hipSuccess) e = ws_get((void**)&dBu, np * mx * mu * sizeof(double));
-    if (e == hipSuccess) e = ws_get((void**)&dBl, np * mx * ml * sizeof(double));
-    if (e == hipSuccess) e = ws_get((void**)&dG, np * ml * mx * sizeof(double));
-    if (e == hipSuccess) e = ws_get((void**)&dlst, np * sizeof(int));
-    if (e == hipSuccess) e = hipMemcpy(dzd, zd, np * nz * sizeof(double), hipMemcpyHostToDevice);
-    // linearsystem at every setpoint (lqr.jl:63), one launch; the matrices stay on the device
-    la.zd = dzd; la.Fd = c->Fd_dev; la.A = dA; la.Bu = dBu; la.Bl = dBl; la.G = dG; la.status = dlst;
-    if (e == hipSuccess) e = launch_linearize(la, m->shape, nullptr);
+    // linearsystem at every setpoint (lqr.jl:63), one launch, reading the controller's own feed-forward table; the matrices stay on the device
+    LinWs w = {};
+    w.Fd = c->Fd_dev;
+    TRY(linearize_to_ws(m, plants, first_plant, n_ctrl, zd, nullptr, mu, ctrl_joint, w, what));
+    memcpy(H.cj, w.cj, sizeof(int) * (size_t)mu);
     // dlqr for every setpoint (lqr.jl:141-184), gains written straight into the controller's table
     RicArgs ra;
-    ra.nprob = n_ctrl; ra.mx = (int)mx; ra.mu = mu; ra.ml = (int)ml; ra.N = N; ra.time_varying = 0; ra.tol = tol; ra.path = 0; ra.bf16_terms = 0; ra.keep_last = inf ? 1 : 0; ra.kpad = (long long)padi;
-    ra.p_rows = batch_p_rows(Q, (int)mx, R, mu);
-    const size_t wd = ric_total_work_doubles(ra);
-    if (e == hipSuccess) e = ws_get((void**)&dQ, mx * mx * sizeof(double));
-    if (e == hipSuccess) e = ws_get((void**)&dR, (size_t)(mu * mu + 1) * sizeof(double));
-    if (e == hipSuccess) e = ws_get((void**)&dwork, wd * sizeof(double));
-    if (e == hipSuccess) e = ws_get((void**)&dstop, np * sizeof(int));
-    if (e == hipSuccess) e = ws_get((void**)&dkb, np * sizeof(int));
-    if (e == hipSuccess) e = ws_get((void**)&dst, np * sizeof(int));
-    if (e == hipSuccess) e = hipMemcpy(dQ, Q, mx * mx * sizeof(double), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dR, R, (size_t)mu * mu * sizeof(double), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(c->K_dev, 0, (nK + CCLQR_K_PAD) * sizeof(double));
-    ra.stop = dstop; ra.A = dA; ra.Bu = dBu; ra.Bl = dBl; ra.G = dG; ra.Q = dQ; ra.R = dR; ra.K = c->K_dev; ra.kbreak = dkb; ra.status = dst; ra.work = dwork;
-    if (e == hipSuccess) e = launch_riccati(ra, nullptr);
-    if (e == hipSuccess) {
-        const long long nrows = (long long)np * (long long)nKtab * mu;
-        e = launch_lds<false>(k_rows_to_link_order_kernel, dim3((unsigned)nrows), dim3(128), mx * sizeof(double), nullptr, c->K_dev, nrows, (long long)nKtab * mu, tab_stride, nb, m->dev);
-    }
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipMemcpy(lst.data(), dlst, np * sizeof(int), hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(kb.data(), dkb, np * sizeof(int), hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(st.data(), dst, np * sizeof(int), hipMemcpyDeviceToHost);
-    H.K = c->K_dev; H.zd = c->zd_dev; H.Fd = c->Fd_dev;
-    ctrl_hot_build(c->host);      // the record the rollout steps read: after the tables' addresses and strides are final
-    if (e == hipSuccess) e = hipMalloc((void**)&c->dev, sizeof(CtrlDev));
-    if (e == hipSuccess) e = hipMemcpy(c->dev, &c->host, sizeof(CtrlDev), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { cclqr_ctrl_destroy(c); return fail(CCLQR_EHIP, std::string("batched LQR construction: ") + hipGetErrorString(e)); }
-    for (size_t p = 0; p < np; p++) {
+    ra.nprob = n_ctrl; ra.mx = (int)mx; ra.mu = mu; ra.ml = (int)ml; ra.N = N; ra.time_varying = 0; ra.tol = tol; ra.path = 0; ra.bf16_terms = 0; ra.keep_last = inf ? 1 : 0;
+    ra.kpad = (long long)L.pad;
+    ra.p_rows = ric_p_rows(Q, (int)mx, R, mu);
+    HIPTRY(what, ws_get((void**)&dQ, mx * mx * sizeof(double)));
+    HIPTRY(what, ws_get((void**)&dR, (size_t)(mu * mu + 1) * sizeof(double)));
+    HIPTRY(what, ws_get((void**)&dwork, ric_total_work_doubles(ra) * sizeof(double)));
+    HIPTRY(what, ws_get((void**)&dstop, np * sizeof(int)));
+    HIPTRY(what, ws_get((void**)&dkb, np * sizeof(int)));
+    HIPTRY(what, ws_get((void**)&dst, np * sizeof(int)));
+    HIPTRY(what, hipMemcpy(dQ, Q, mx * mx * sizeof(double), hipMemcpyHostToDevice));
+    HIPTRY(what, hipMemcpy(dR, R, (size_t)mu * mu * sizeof(double), hipMemcpyHostToDevice));
+    HIPTRY(what, hipMemset(c->K_dev, 0, L.alloc_doubles * sizeof(double)));
+    ra.stop = dstop; ra.A = w.A; ra.Bu = w.Bu; ra.Bl = w.Bl; ra.G = w.G; ra.Q = dQ; ra.R = dR; ra.K = c->K_dev; ra.kbreak = dkb; ra.status = dst; ra.work = dwork;
+    HIPTRY(what, launch_riccati(ra, nullptr));
+    const long long nrows = (long long)np * (long long)nKtab * mu;
+    HIPTRY(what, launch_lds<false>(k_rows_to_link_order_kernel, dim3((unsigned)nrows), dim3(128), mx * sizeof(double), nullptr, c->K_dev, nrows, (long long)nKtab * mu, L.stride, nb, m->dev));
+    HIPTRY(what, hipDeviceSynchronize());
+    long long bad = -1;
+    HIPTRY(what, knots_converged(w.status, np, &bad));
+    HIPTRY(what, hipMemcpy(kb.data(), dkb, np * sizeof(int), hipMemcpyDeviceToHost));
+    HIPTRY(what, hipMemcpy(st.data(), dst, np * sizeof(int), hipMemcpyDeviceToHost));
+    HIPTRY(what, ctrl_publish(c));
+    for (size_t p = 0; p < np; p++) {      // kbreak is filled up to the problem the call is refused for
         if (kbreak) kbreak[p] = kb[p];
-        if (lst[p] <= 0) { cclqr_ctrl_destroy(c); return fail(CCLQR_ENOCONV, "Newton did not converge at setpoint " + std::to_string(p)); }
-        if (st[p] != 0) { cclqr_ctrl_destroy(c); return fail(CCLQR_ESINGULAR, "G*Bl or M is singular at setpoint " + std::to_string(p)); }
+        if ((long long)p == bad) return fail(CCLQR_ENOCONV, "Newton did not converge at setpoint " + std::to_string(p));
+        if (st[p] != 0) return fail(CCLQR_ESINGULAR, "G*Bl or M is singular at setpoint " + std::to_string(p));
     }
-    *out = c;
+    *out = own.release();
     return CCLQR_OK;
 }
 
@@ -365,27 +425,23 @@ extern "C" int cclqr_ctrl_create_tracking_batch_plants(const cclqr_mech* m, cons
                                                        const double* zd, const double* Fd, int32_t on_device, int32_t mu, const int32_t* ctrl_joint,
                                                        const double* Q, const double* R, double tol, const cclqr_ctrl_desc* law, int64_t workspace_bytes,
                                                        int32_t* kbreak, void* stream, cclqr_ctrl** out) {
+    static const char* const what = "batched TrackingLQR construction";
     if (!m || !zd || !Q || !R || !ctrl_joint || !out) return fail(CCLQR_EINVAL, "null argument");
-    { int rc = check_device(m); if (rc != CCLQR_OK) return rc; }
+    TRY(check_device(m));
     if (m->host.loop) return fail(CCLQR_EUNSUPPORTED, "batched TrackingLQR construction is for tree mechanisms (closed-loop mechanisms: cclqr_linearize_projected + cclqr_riccati_tv)");
     if (n_ctrl < 1 || N < 2 || mu < 1 || mu > m->nb) return fail(CCLQR_EINVAL, "bad sizes");
-    { int rc = plants_check_range(m, plants, first_plant, n_ctrl); if (rc != CCLQR_OK) return rc; }
     const int nb = m->nb;
     const size_t nz = 13 * (size_t)nb, mx = 12 * (size_t)nb, ml = 5 * (size_t)nb, np = (size_t)n_ctrl, nk = (size_t)N - 1;
-    if (!linearize_fits_lds(m)) return fail(CCLQR_EUNSUPPORTED, "instance does not fit LDS");
     LinArgs la;
     memset(&la, 0, sizeof(la));
     la.M = m->dev; la.mu = mu;
     la.plants = plants ? plants->dev : nullptr;
     la.knots_per_plant = (int)nk; la.rows_per_plant = N;
+    TRY(linearize_check(m, plants, first_plant, n_ctrl, mu, ctrl_joint, la.cj));
     CtrlDev H;
     memset(&H, 0, sizeof(H));
     H.mu = mu; H.nK = (int)nk; H.N = N; H.nsp = N; H.n_ctrl = n_ctrl;
-    for (int i = 0; i < mu; i++) {
-        if (ctrl_joint[i] < 0 || ctrl_joint[i] >= nb) return fail(CCLQR_EINVAL, "controlled joint out of range");
-        la.cj[i] = m->link_of_joint[ctrl_joint[i]];
-        H.cj[i] = la.cj[i];
-    }
+    memcpy(H.cj, la.cj, sizeof(int) * (size_t)mu);
     if (law) {       // the friction / noise law of examples/trackingLQR_triple_cartpole.jl:93-111, as build_ctrl_tables takes it
         if (law->fric)
             for (int j = 0; j < nb; j++) { H.fric[m->link_of_joint[j]] = law->fric[j]; if (law->fric[j] != 0.0) H.has_fric = 1; }
@@ -393,16 +449,15 @@ extern "C" int cclqr_ctrl_create_tracking_batch_plants(const cclqr_mech* m, cons
         H.noise_philox = law->noise_philox ? 1 : 0;
         H.noise_key0 = (unsigned)(law->noise_seed & 0xffffffffu) ^ (unsigned)(law->noise_seed >> 32);
     }
-    const size_t padi = n_ctrl > 1 ? gain_row_overrun(m) : 0;       // every table ends in its own zero pad (CCLQR_K_PAD)
-    const long long tab_stride = (long long)nk * mu * (long long)mx + (long long)padi;
-    H.K_stride = n_ctrl > 1 ? tab_stride : 0;
+    const GainTableLayout L = gain_table_layout(m->shape, nb, n_ctrl, (long long)nk * mu);      // every table ends in its own zero pad
+    H.K_stride = L.K_stride;
     H.zd_stride = n_ctrl > 1 ? (long long)N * (long long)nz : 0;
     H.Fd_stride = (n_ctrl > 1 && Fd) ? (long long)N * mu : 0;
     // one Riccati path for the whole call, chosen from n_ctrl, and the chunks the workspace budget allows: all before anything is allocated
     RicArgs ra;
     ra.nprob = n_ctrl; ra.mx = (int)mx; ra.mu = mu; ra.ml = (int)ml; ra.N = N; ra.time_varying = 1; ra.tol = tol; ra.path = 0; ra.bf16_terms = 0; ra.keep_last = 0;
-    ra.kpad = (long long)padi;
-    ra.p_rows = batch_p_rows(Q, (int)mx, R, mu);
+    ra.kpad = (long long)L.pad;
+    ra.p_rows = ric_p_rows(Q, (int)mx, R, mu);
     ra.path = ric_chosen_path(ra);
     RicArgs r1 = ra, r2 = ra;
     r1.nprob = 1; r2.nprob = 2;
@@ -417,93 +472,77 @@ extern "C" int cclqr_ctrl_create_tracking_batch_plants(const cclqr_mech* m, cons
                                   std::to_string(fixed_bytes + per_bytes) + " bytes");
     const size_t pc = (size_t)per_chunk;
     hipStream_t st_ = (hipStream_t)stream;
-    cclqr_ctrl* c = new cclqr_ctrl();
-    memset(c, 0, sizeof(*c));
-    c->nb = nb;
-    c->device = m->device;
+    CtrlOwner own(ctrl_new(m));      // (declared before the blocks: they are released, after a wait for the stream, before the controller's tables)
+    cclqr_ctrl* c = own.p;
     c->host = H;
-    const size_t nK = np * (size_t)tab_stride, nsp_all = np * (size_t)N;
-    double* slab = nullptr;
-    int *dlst = nullptr, *dkb = nullptr, *dst = nullptr, *dstop = nullptr;
-    std::vector<int> lst(np * nk), kb(np), st(np);
+    DevBlocks blocks(st_);           // a: the slab, b: the statuses
+    const size_t nsp_all = np * (size_t)N;
+    std::vector<int> kb(np), st(np);
     const hipMemcpyKind up = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
     // the setpoints go straight into the controller's table, in the caller's body order while the linearisation reads them (it permutes as it loads); they are
     // taken to link order in place afterwards.  Host arrays are copied synchronously, device arrays on `stream`
-    hipError_t e = hipMalloc((void**)&c->zd_dev, nsp_all * nz * sizeof(double));
-    if (e == hipSuccess) e = on_device ? hipMemcpyAsync(c->zd_dev, zd, nsp_all * nz * sizeof(double), up, st_) : hipMemcpy(c->zd_dev, zd, nsp_all * nz * sizeof(double), up);
-    if (e == hipSuccess) e = hipMalloc((void**)&c->K_dev, (nK + CCLQR_K_PAD) * sizeof(double));      // (padding: see cclqr_ctrl_create)
-    if (e == hipSuccess && Fd) {
-        e = hipMalloc((void**)&c->Fd_dev, nsp_all * mu * sizeof(double));
-        if (e == hipSuccess) e = on_device ? hipMemcpyAsync(c->Fd_dev, Fd, nsp_all * mu * sizeof(double), up, st_) : hipMemcpy(c->Fd_dev, Fd, nsp_all * mu * sizeof(double), up);
+    HIPTRY(what, hipMalloc((void**)&c->zd_dev, nsp_all * nz * sizeof(double)));
+    HIPTRY(what, on_device ? hipMemcpyAsync(c->zd_dev, zd, nsp_all * nz * sizeof(double), up, st_) : hipMemcpy(c->zd_dev, zd, nsp_all * nz * sizeof(double), up));
+    HIPTRY(what, hipMalloc((void**)&c->K_dev, L.alloc_doubles * sizeof(double)));
+    if (Fd) {
+        HIPTRY(what, hipMalloc((void**)&c->Fd_dev, nsp_all * mu * sizeof(double)));
+        HIPTRY(what, on_device ? hipMemcpyAsync(c->Fd_dev, Fd, nsp_all * mu * sizeof(double), up, st_) : hipMemcpy(c->Fd_dev, Fd, nsp_all * mu * sizeof(double), up));
         c->Fd_len = nsp_all * mu;
     }
-    if (e == hipSuccess) e = hipMalloc((void**)&slab, (size_t)(fixed_bytes + per_bytes * per_chunk));
-    if (e == hipSuccess) e = hipMalloc((void**)&dlst, (np * nk + 3 * np + pc) * sizeof(int));
-    if (e == hipSuccess) {
-        dkb = dlst + np * nk; dst = dkb + np; dstop = dst + np;
-        // the slab: Q | R | A | Bu | Bl | G of a chunk's knots | the recursion's workspace for a chunk
-        double* dQ = slab;
-        double* dR = dQ + q_doubles;
-        double* dA = dR + r_doubles;
-        double* dBu = dA + pc * nk * mx * mx;
-        double* dBl = dBu + pc * nk * mx * mu;
-        double* dG = dBl + pc * nk * mx * ml;
-        double* dwork = dG + pc * nk * ml * mx;
-        e = hipMemcpy(dQ, Q, mx * mx * sizeof(double), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(dR, R, (size_t)mu * mu * sizeof(double), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemsetAsync(c->K_dev, 0, (nK + CCLQR_K_PAD) * sizeof(double), st_);
-        la.A = dA; la.Bu = dBu; la.Bl = dBl; la.G = dG;
-        ra.stop = dstop; ra.A = dA; ra.Bu = dBu; ra.Bl = dBl; ra.G = dG; ra.Q = dQ; ra.R = dR; ra.work = dwork;
-        for (size_t c0 = 0; c0 < np && e == hipSuccess; c0 += pc) {
-            const size_t nc = np - c0 < pc ? np - c0 : pc;
-            // linearsystem at the knots 1 .. N-1 of the chunk's trajectories (lqr_tracking.jl:88), one launch; the models stay on the device
-            la.nk = (int)(nc * nk);
-            la.zd = c->zd_dev + c0 * (size_t)N * nz;
-            la.Fd = c->Fd_dev ? c->Fd_dev + c0 * (size_t)N * mu : nullptr;
-            la.plant_off = plants ? first_plant - plants->first_index + (long long)c0 : 0;
-            la.status = dlst + c0 * nk;
-            e = launch_linearize(la, m->shape, st_);
-            // the recursion of lqr_tracking.jl:73-122 for each of them, gains written straight into the controller's tables
-            ra.nprob = (int)nc;
-            ra.K = c->K_dev + c0 * (size_t)tab_stride; ra.kbreak = dkb + c0; ra.status = dst + c0;
-            if (e == hipSuccess) e = launch_riccati(ra, st_);
-        }
-        if (e == hipSuccess) {
-            const long long nrows = (long long)np * (long long)nk * mu;
-            e = launch_lds<false>(k_rows_to_link_order_kernel, dim3((unsigned)nrows), dim3(128), mx * sizeof(double), st_, c->K_dev, nrows, (long long)nk * mu, tab_stride, nb, m->dev);
-        }
-        if (e == hipSuccess)
-            e = launch_lds<false>(sp_rows_to_link_order_kernel, dim3((unsigned)nsp_all), dim3(64), nz * sizeof(double), st_, c->zd_dev, (long long)nsp_all, nb, m->dev);
-        if (e == hipSuccess) e = hipStreamSynchronize(st_);
-        if (e == hipSuccess) e = hipMemcpy(lst.data(), dlst, np * nk * sizeof(int), hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(kb.data(), dkb, np * sizeof(int), hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(st.data(), dst, np * sizeof(int), hipMemcpyDeviceToHost);
+    HIPTRY(what, hipMalloc(&blocks.a, (size_t)(fixed_bytes + per_bytes * per_chunk)));
+    HIPTRY(what, hipMalloc(&blocks.b, (np * nk + 3 * np + pc) * sizeof(int)));
+    int *dlst = (int*)blocks.b, *dkb = dlst + np * nk, *dst = dkb + np, *dstop = dst + np;
+    // the slab: Q | R | A | Bu | Bl | G of a chunk's knots | the recursion's workspace for a chunk
+    double* dQ = (double*)blocks.a;
+    double* dR = dQ + q_doubles;
+    double* dA = dR + r_doubles;
+    double* dBu = dA + pc * nk * mx * mx;
+    double* dBl = dBu + pc * nk * mx * mu;
+    double* dG = dBl + pc * nk * mx * ml;
+    double* dwork = dG + pc * nk * ml * mx;
+    HIPTRY(what, hipMemcpy(dQ, Q, mx * mx * sizeof(double), hipMemcpyHostToDevice));
+    HIPTRY(what, hipMemcpy(dR, R, (size_t)mu * mu * sizeof(double), hipMemcpyHostToDevice));
+    HIPTRY(what, hipMemsetAsync(c->K_dev, 0, L.alloc_doubles * sizeof(double), st_));
+    la.A = dA; la.Bu = dBu; la.Bl = dBl; la.G = dG;
+    ra.stop = dstop; ra.A = dA; ra.Bu = dBu; ra.Bl = dBl; ra.G = dG; ra.Q = dQ; ra.R = dR; ra.work = dwork;
+    for (size_t c0 = 0; c0 < np; c0 += pc) {
+        const size_t nc = np - c0 < pc ? np - c0 : pc;
+        // linearsystem at the knots 1 .. N-1 of the chunk's trajectories (lqr_tracking.jl:88), one launch; the models stay on the device
+        la.nk = (int)(nc * nk);
+        la.zd = c->zd_dev + c0 * (size_t)N * nz;
+        la.Fd = c->Fd_dev ? c->Fd_dev + c0 * (size_t)N * mu : nullptr;
+        la.plant_off = plants ? first_plant - plants->first_index + (long long)c0 : 0;
+        la.status = dlst + c0 * nk;
+        HIPTRY(what, launch_linearize(la, m->shape, st_));
+        // the recursion of lqr_tracking.jl:73-122 for each of them, gains written straight into the controller's tables
+        ra.nprob = (int)nc;
+        ra.K = c->K_dev + c0 * (size_t)L.stride; ra.kbreak = dkb + c0; ra.status = dst + c0;
+        HIPTRY(what, launch_riccati(ra, st_));
     }
-    if (e != hipSuccess) (void)hipStreamSynchronize(st_);      // nothing of the call may still run on what is released below
-    if (slab) (void)hipFree(slab);
-    if (dlst) (void)hipFree(dlst);
-    c->host.K = c->K_dev; c->host.zd = c->zd_dev; c->host.Fd = c->Fd_dev;
-    ctrl_hot_build(c->host);      // the record the rollout steps read: after the tables' addresses and strides are final
-    if (e == hipSuccess) e = hipMalloc((void**)&c->dev, sizeof(CtrlDev));
-    if (e == hipSuccess) e = hipMemcpy(c->dev, &c->host, sizeof(CtrlDev), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { cclqr_ctrl_destroy(c); return fail(CCLQR_EHIP, std::string("batched TrackingLQR construction: ") + hipGetErrorString(e)); }
+    const long long nrows = (long long)np * (long long)nk * mu;
+    HIPTRY(what, launch_lds<false>(k_rows_to_link_order_kernel, dim3((unsigned)nrows), dim3(128), mx * sizeof(double), st_, c->K_dev, nrows, (long long)nk * mu, L.stride, nb, m->dev));
+    HIPTRY(what, launch_lds<false>(sp_rows_to_link_order_kernel, dim3((unsigned)nsp_all), dim3(64), nz * sizeof(double), st_, c->zd_dev, (long long)nsp_all, nb, m->dev));
+    HIPTRY(what, hipStreamSynchronize(st_));
+    long long bad = -1;
+    HIPTRY(what, knots_converged(dlst, np * nk, &bad));
+    HIPTRY(what, hipMemcpy(kb.data(), dkb, np * sizeof(int), hipMemcpyDeviceToHost));
+    HIPTRY(what, hipMemcpy(st.data(), dst, np * sizeof(int), hipMemcpyDeviceToHost));
+    blocks.release();
+    HIPTRY(what, ctrl_publish(c));
     for (size_t p = 0; p < np; p++) if (kbreak) kbreak[p] = kb[p];
     for (size_t p = 0; p < np; p++) {
-        for (size_t k = 0; k < nk; k++)
-            if (lst[p * nk + k] <= 0) {
-                cclqr_ctrl_destroy(c);
-                return fail(CCLQR_ENOCONV, "Newton did not converge at the setpoint of knot " + std::to_string(k) + " of table " + std::to_string(p));
-            }
-        if (st[p] != 0) { cclqr_ctrl_destroy(c); return fail(CCLQR_ESINGULAR, "G*Bl or M is singular in table " + std::to_string(p)); }
+        if (bad >= 0 && (size_t)bad / nk == p)
+            return fail(CCLQR_ENOCONV, "Newton did not converge at the setpoint of knot " + std::to_string((size_t)bad % nk) + " of table " + std::to_string(p));
+        if (st[p] != 0) return fail(CCLQR_ESINGULAR, "G*Bl or M is singular in table " + std::to_string(p));
     }
-    *out = c;
+    *out = own.release();
     return CCLQR_OK;
 }
 
 // one table's gains back on the host, in the caller's body order (the inverse of k_rows_to_link_order_kernel / build_ctrl_tables)
 extern "C" int cclqr_ctrl_get_gains(const cclqr_mech* m, const cclqr_ctrl* c, int64_t table, double* K_host) {
     if (!m || !c || !K_host) return fail(CCLQR_EINVAL, "null argument");
-    { int rc = check_device(m); if (rc != CCLQR_OK) return rc; }
+    TRY(check_device(m));
     if (c->nb != m->nb || c->device != m->device) return fail(CCLQR_EINVAL, "the controller was created for another mechanism");
     if (!c->K_dev || c->host.nK < 1) return fail(CCLQR_EINVAL, "the controller has no gains (open loop / PID)");
     const int64_t ntab = c->host.n_ctrl > 1 ? c->host.n_ctrl : 1;
@@ -563,7 +602,7 @@ static int rollout_check_args(const cclqr_mech* m, const cclqr_ctrl* c, int64_t 
     if (!m || !c || !z0 || !zT) return fail(CCLQR_EINVAL, "null argument");
     if (n_inst < 0 || steps < 0 || k0 < 1) return fail(CCLQR_EINVAL, "bad sizes");
     if (c->nb != m->nb) return fail(CCLQR_EINVAL, "controller was built for another mechanism");
-    { int rc = check_device(m); if (rc != CCLQR_OK) return rc; }
+    TRY(check_device(m));
     if (m->shape.lds > 160 * 1024) return fail(CCLQR_EUNSUPPORTED, "instance does not fit LDS");
     const int64_t first = opts ? opts->first_instance : 0;
     if (first < 0) return fail(CCLQR_EINVAL, "negative first_instance");
@@ -610,8 +649,7 @@ static int rollout_resolve_noise(const cclqr_mech* m, const cclqr_ctrl* c, int64
             if (cap != hipStreamCaptureStatusNone)
                 return fail(CCLQR_EINVAL, "the Philox noise workspace cannot grow during stream capture: call cclqr_ctrl_reserve_noise(ctrl, n_inst, steps) "
                                           "before the capture or pass cclqr_rollout_opts.noise_ws_dev");
-            int rc = cclqr_ctrl_reserve_noise(cm, n_inst, steps);
-            if (rc != CCLQR_OK) return rc;
+            TRY(cclqr_ctrl_reserve_noise(cm, n_inst, steps));
         }
         ws = cm->noise_ws;
     }
@@ -625,17 +663,12 @@ extern "C" int cclqr_rollout_plants(const cclqr_mech* m, const cclqr_plants* pla
                                     const double* z0, double* lam, const double* noise, int64_t noise_stride, double* traj, double* zT, int32_t* status,
                                     const cclqr_rollout_opts* opts, void* stream) {
     if (m && c && n_inst == 0) return CCLQR_OK;   // empty batch
-    { int rc = rollout_check_args(m, c, n_inst, steps, k0, z0, zT, status, opts); if (rc != CCLQR_OK) return rc; }
+    TRY(rollout_check_args(m, c, n_inst, steps, k0, z0, zT, status, opts));
     const int64_t first_instance = opts ? opts->first_instance : 0;
-    if (plants) {      // every instance of the launch must find its plant: refused before anything is launched (the Philox fill included)
-        if (plants->mech != m) return fail(CCLQR_EINVAL, "the plants were created for another mechanism");
-        const int64_t lo = first_instance - plants->first_index;
-        if (lo < 0 || lo + n_inst > plants->n_plant)
-            return fail(CCLQR_EINVAL, "instances " + std::to_string(first_instance) + " .. " + std::to_string(first_instance + n_inst - 1) + " of the launch are not all among the plants " +
-                                      std::to_string(plants->first_index) + " .. " + std::to_string(plants->first_index + plants->n_plant - 1));
-    }
+    // every instance of the launch must find its plant: refused before anything is launched (the Philox fill included)
+    TRY(plants_check_range(m, plants, first_instance, n_inst, "instances", "launch"));
     bool philox_in_kernel = false;
-    { int rc = rollout_resolve_noise(m, c, n_inst, steps, k0, opts, stream, &noise, &noise_stride, &philox_in_kernel); if (rc != CCLQR_OK) return rc; }
+    TRY(rollout_resolve_noise(m, c, n_inst, steps, k0, opts, stream, &noise, &noise_stride, &philox_in_kernel));
     const CtrlDev& H = c->host;
     // the one place a controller's tables become a kernel's law
     const ControlLaw law = H.has_pid ? ControlLaw::Pid : (philox_in_kernel ? ControlLaw::PhiloxInKernel : ((H.has_fric || noise) ? ControlLaw::FricNoise : ControlLaw::Lqr));
@@ -674,7 +707,7 @@ extern "C" int cclqr_plants_create(const cclqr_mech* m, int64_t n_plant, int64_t
     if (!m || !out) return fail(CCLQR_EINVAL, "null argument");
     if (n_plant < 1 || first_index < 0) return fail(CCLQR_EINVAL, "need n_plant >= 1 and first_index >= 0");
     if (n_plant * (int64_t)(m ? m->nb : 1) >= (int64_t)1 << 31) return fail(CCLQR_EUNSUPPORTED, "a plant table holds fewer than 2^31 (plant, link) records (256 GB)");
-    { int rc = check_device(m); if (rc != CCLQR_OK) return rc; }
+    TRY(check_device(m));
     if (m->host.loop) return fail(CCLQR_EUNSUPPORTED, "per-instance plants are for forests of chains and branching trees (closed-loop mechanisms run their own plant)");
     const size_t nb = (size_t)m->nb, np = (size_t)n_plant;
     hipStream_t st = (hipStream_t)stream;
@@ -682,32 +715,29 @@ extern "C" int cclqr_plants_create(const cclqr_mech* m, int64_t n_plant, int64_t
     const size_t per[4] = {nb, 9 * nb, 3 * nb, 3 * nb};
     unsigned long long* derr = nullptr;
     WsScope scope;
-    hipError_t e = ws_get((void**)&derr, sizeof(unsigned long long));
-    if (!on_device) {
-        for (int k = 0; k < 4 && e == hipSuccess; k++) {
-            if (!src[k]) continue;
-            double* d = nullptr;
-            e = ws_get((void**)&d, np * per[k] * sizeof(double));
-            if (e == hipSuccess) e = hipMemcpyAsync(d, src[k], np * per[k] * sizeof(double), hipMemcpyHostToDevice, st);
-            src[k] = d;
-        }
+    HIPTRY("plants upload", ws_get((void**)&derr, sizeof(unsigned long long)));
+    for (int k = 0; k < 4 && !on_device; k++) {
+        if (!src[k]) continue;
+        double* d = nullptr;
+        HIPTRY("plants upload", ws_get((void**)&d, np * per[k] * sizeof(double)));
+        HIPTRY("plants upload", hipMemcpyAsync(d, src[k], np * per[k] * sizeof(double), hipMemcpyHostToDevice, st));
+        src[k] = d;
     }
-    cclqr_plants* P = new cclqr_plants();
+    Owned<cclqr_plants, cclqr_plants_destroy> own(new cclqr_plants());
+    cclqr_plants* P = own.p;
     P->dev = nullptr; P->n_plant = n_plant; P->first_index = first_index; P->mech = m; P->nb = m->nb; P->device = m->device;
     unsigned long long herr = ~0ull;
-    if (e == hipSuccess) e = hipMalloc((void**)&P->dev, np * nb * sizeof(PlantRec));
-    if (e == hipSuccess) e = hipMemcpyAsync(derr, &herr, sizeof(herr), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = launch_plants_pack(m->dev, m->nb, n_plant, src[0], src[1], src[2], src[3], P->dev, derr, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(&herr, derr, sizeof(herr), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) { cclqr_plants_destroy(P); return fail(CCLQR_EHIP, std::string("plants upload: ") + hipGetErrorString(e)); }
+    HIPTRY("plants upload", hipMalloc((void**)&P->dev, np * nb * sizeof(PlantRec)));
+    HIPTRY("plants upload", hipMemcpyAsync(derr, &herr, sizeof(herr), hipMemcpyHostToDevice, st));
+    HIPTRY("plants upload", launch_plants_pack(m->dev, m->nb, n_plant, src[0], src[1], src[2], src[3], P->dev, derr, st));
+    HIPTRY("plants upload", hipMemcpyAsync(&herr, derr, sizeof(herr), hipMemcpyDeviceToHost, st));
+    HIPTRY("plants upload", hipStreamSynchronize(st));
     if (herr != ~0ull) {
-        cclqr_plants_destroy(P);
         const unsigned long long pb = herr / 4;
         static const char* what[3] = {"a non-finite value", "mass must be positive", "inertia must be symmetric positive definite"};
         return fail(CCLQR_EINVAL, "plant " + std::to_string(pb / nb) + ", body " + std::to_string(pb % nb) + ": " + what[herr % 4 < 3 ? herr % 4 : 0]);
     }
-    *out = P;
+    *out = own.release();
     return CCLQR_OK;
 }
 
@@ -747,30 +777,26 @@ extern "C" int cclqr_rollout_host_ex(const cclqr_mech* m, const cclqr_ctrl* c, i
     if (m && c && n_inst == 0) return CCLQR_OK;   // empty batch
     if (!m || !c || !z0 || !zT) return fail(CCLQR_EINVAL, "null argument");
     if (opts && (opts->pid_state_dev || opts->noise_ws_dev)) return fail(CCLQR_EINVAL, "the host-pointer rollout takes no device buffers in its options");
-    { int rc = check_device(m); if (rc != CCLQR_OK) return rc; }
+    TRY(check_device(m));
+    if (n_inst < 0 || steps < 0 || k0 < 1) return fail(CCLQR_EINVAL, "bad sizes");      // (rollout_check_args' rule: the staging below is sized by them)
     const size_t nz = (size_t)13 * m->nb;
     double *dz0 = nullptr, *dzT = nullptr, *dtraj = nullptr, *dnoise = nullptr;
     int32_t* dst = nullptr;
-    int rc = CCLQR_OK;
     WsScope scope;
-    hipError_t e = ws_get((void**)&dz0, n_inst * nz * sizeof(double));
-    if (e == hipSuccess) e = ws_get((void**)&dzT, n_inst * nz * sizeof(double));
-    if (e == hipSuccess) e = ws_get((void**)&dst, n_inst * sizeof(int32_t));
-    if (e == hipSuccess && traj) e = ws_get((void**)&dtraj, n_inst * steps * nz * sizeof(double));
-    if (e == hipSuccess && noise) e = ws_get((void**)&dnoise, (size_t)n_inst * steps * sizeof(double));
-    if (e == hipSuccess) e = hipMemcpy(dz0, z0, n_inst * nz * sizeof(double), hipMemcpyHostToDevice);
-    if (e == hipSuccess && noise) e = hipMemcpy(dnoise, noise, (size_t)n_inst * steps * sizeof(double), hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        // noise is indexed by the absolute step k-1: shift the base so that k0 maps to column 0 of the caller's array
-        const double* nbase = dnoise ? dnoise - (k0 - 1) : nullptr;
-        rc = cclqr_rollout_ex(m, c, n_inst, steps, k0, dz0, nullptr, nbase, steps, dtraj, dzT, dst, opts, nullptr);
-        if (rc == CCLQR_OK) e = hipDeviceSynchronize();
-    }
-    if (rc == CCLQR_OK && e == hipSuccess) e = hipMemcpy(zT, dzT, n_inst * nz * sizeof(double), hipMemcpyDeviceToHost);
-    if (rc == CCLQR_OK && e == hipSuccess && traj) e = hipMemcpy(traj, dtraj, n_inst * steps * nz * sizeof(double), hipMemcpyDeviceToHost);
-    if (rc == CCLQR_OK && e == hipSuccess && status) e = hipMemcpy(status, dst, n_inst * sizeof(int32_t), hipMemcpyDeviceToHost);
-    if (rc != CCLQR_OK) return rc;
-    if (e != hipSuccess) return fail(CCLQR_EHIP, std::string("rollout: ") + hipGetErrorString(e));
+    HIPTRY("rollout", ws_get((void**)&dz0, n_inst * nz * sizeof(double)));
+    HIPTRY("rollout", ws_get((void**)&dzT, n_inst * nz * sizeof(double)));
+    HIPTRY("rollout", ws_get((void**)&dst, n_inst * sizeof(int32_t)));
+    if (traj) HIPTRY("rollout", ws_get((void**)&dtraj, n_inst * steps * nz * sizeof(double)));
+    if (noise) HIPTRY("rollout", ws_get((void**)&dnoise, (size_t)n_inst * steps * sizeof(double)));
+    HIPTRY("rollout", hipMemcpy(dz0, z0, n_inst * nz * sizeof(double), hipMemcpyHostToDevice));
+    if (noise) HIPTRY("rollout", hipMemcpy(dnoise, noise, (size_t)n_inst * steps * sizeof(double), hipMemcpyHostToDevice));
+    // noise is indexed by the absolute step k-1: shift the base so that k0 maps to column 0 of the caller's array
+    const double* nbase = dnoise ? dnoise - (k0 - 1) : nullptr;
+    TRY(cclqr_rollout_ex(m, c, n_inst, steps, k0, dz0, nullptr, nbase, steps, dtraj, dzT, dst, opts, nullptr));
+    HIPTRY("rollout", hipDeviceSynchronize());
+    HIPTRY("rollout", hipMemcpy(zT, dzT, n_inst * nz * sizeof(double), hipMemcpyDeviceToHost));
+    if (traj) HIPTRY("rollout", hipMemcpy(traj, dtraj, n_inst * steps * nz * sizeof(double), hipMemcpyDeviceToHost));
+    if (status) HIPTRY("rollout", hipMemcpy(status, dst, n_inst * sizeof(int32_t), hipMemcpyDeviceToHost));
     return CCLQR_OK;
 }
 
@@ -787,50 +813,24 @@ extern "C" int cclqr_linearize(const cclqr_mech* m, int32_t nk, const double* zd
 extern "C" int cclqr_linearize_plants(const cclqr_mech* m, const cclqr_plants* plants, int64_t first_plant, int32_t nk, const double* zd, int32_t mu,
                                       const int32_t* ctrl_joint, const double* Fd, double* A, double* Bu, double* Bl, double* G) {
     if (!m || !zd || !A || !Bl || !G || (mu > 0 && (!ctrl_joint || !Bu))) return fail(CCLQR_EINVAL, "null argument");
-    { int rc = check_device(m); if (rc != CCLQR_OK) return rc; }
+    TRY(check_device(m));
     // a closed-loop mechanism has its own tables (bodies and joints in the caller's order, ml = 5 rows per joint incl. the two null rows of a
     // FixedOrientation); its G*Bl is singular, so the recursion takes the projected pair of cclqr_linearize_projected, not these four
-    const bool loop = m->host.loop != 0;
-    const int nb = m->nb, nj = loop ? m->nj : nb;
+    const int nj = m->host.loop ? m->nj : m->nb;
+    const size_t n = (size_t)nk, mx = 12 * (size_t)m->nb, ml = 5 * (size_t)nj;
     if (nk < 0 || mu < 0 || mu > nj) return fail(CCLQR_EINVAL, "Missmatched length for constraints");
-    { int rc = plants_check_range(m, plants, first_plant, nk); if (rc != CCLQR_OK) return rc; }
-    if (nk == 0) return CCLQR_OK;
-    const size_t nz = 13 * (size_t)nb, mx = 12 * (size_t)nb, ml = 5 * (size_t)nj;
-    if (!linearize_fits_lds(m)) return fail(CCLQR_EUNSUPPORTED, "instance does not fit LDS");
-    LinArgs a;
-    memset(&a, 0, sizeof(a));
-    a.M = m->dev; a.nk = nk; a.mu = mu;
-    a.plants = plants ? plants->dev : nullptr;
-    a.plant_off = plants ? first_plant - plants->first_index : 0;
-    for (int i = 0; i < mu; i++) {
-        if (ctrl_joint[i] < 0 || ctrl_joint[i] >= nj) return fail(CCLQR_EINVAL, "controlled joint out of range");
-        a.cj[i] = loop ? ctrl_joint[i] : m->link_of_joint[ctrl_joint[i]];
-    }
-    double *dzd = nullptr, *dFd = nullptr, *dA = nullptr, *dBu = nullptr, *dBl = nullptr, *dG = nullptr;
-    int* dst = nullptr;
-    std::vector<int> st(nk);
     WsScope scope;
-    hipError_t e = ws_get((void**)&dzd, nk * nz * sizeof(double));
-    if (e == hipSuccess && Fd && mu > 0) e = ws_get((void**)&dFd, (size_t)nk * mu * sizeof(double));
-    if (e == hipSuccess) e = ws_get((void**)&dA, nk * mx * mx * sizeof(double));
-    if (e == hipSuccess) e = ws_get((void**)&dBu, (nk * mx * (size_t)(mu > 0 ? mu : 1)) * sizeof(double));
-    if (e == hipSuccess) e = ws_get((void**)&dBl, nk * mx * ml * sizeof(double));
-    if (e == hipSuccess) e = ws_get((void**)&dG, nk * ml * mx * sizeof(double));
-    if (e == hipSuccess) e = ws_get((void**)&dst, nk * sizeof(int));
-    if (e == hipSuccess) e = hipMemcpy(dzd, zd, nk * nz * sizeof(double), hipMemcpyHostToDevice);
-    if (e == hipSuccess && dFd) e = hipMemcpy(dFd, Fd, (size_t)nk * mu * sizeof(double), hipMemcpyHostToDevice);
-    a.zd = dzd; a.Fd = dFd; a.A = dA; a.Bu = dBu; a.Bl = dBl; a.G = dG; a.status = dst;
-    if (e == hipSuccess) e = launch_linearize(a, m->shape, nullptr);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipMemcpy(A, dA, nk * mx * mx * sizeof(double), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && mu > 0) e = hipMemcpy(Bu, dBu, nk * mx * mu * sizeof(double), hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(Bl, dBl, nk * mx * ml * sizeof(double), hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(G, dG, nk * ml * mx * sizeof(double), hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(st.data(), dst, nk * sizeof(int), hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return fail(CCLQR_EHIP, std::string("linearize: ") + hipGetErrorString(e));
-    for (int k = 0; k < nk; k++)
-        if (st[k] <= 0) return fail(CCLQR_ENOCONV, "Newton did not converge at the setpoint of knot " + std::to_string(k));
-    return CCLQR_OK;
+    LinWs w = {};
+    TRY(linearize_to_ws(m, plants, first_plant, nk, zd, Fd, mu, ctrl_joint, w, "linearize"));
+    if (nk == 0) return CCLQR_OK;
+    HIPTRY("linearize", hipDeviceSynchronize());
+    HIPTRY("linearize", hipMemcpy(A, w.A, n * mx * mx * sizeof(double), hipMemcpyDeviceToHost));
+    if (mu > 0) HIPTRY("linearize", hipMemcpy(Bu, w.Bu, n * mx * mu * sizeof(double), hipMemcpyDeviceToHost));
+    HIPTRY("linearize", hipMemcpy(Bl, w.Bl, n * mx * ml * sizeof(double), hipMemcpyDeviceToHost));
+    HIPTRY("linearize", hipMemcpy(G, w.G, n * ml * mx * sizeof(double), hipMemcpyDeviceToHost));
+    long long bad = -1;
+    HIPTRY("linearize", knots_converged(w.status, n, &bad));
+    return bad < 0 ? CCLQR_OK : knot_not_converged(bad);
 }
 
 // ---- projected linear model by central differences of the DEVICE step map (any topology; the only linearisation of closed loops)
@@ -867,50 +867,32 @@ __global__ void fd_quotient_kernel(const double* zT, int nk, int per, int nb, in
 }
 // The projected pair ANALYTICALLY (h <= 0): the exact Jacobians of the one-step map with the multipliers exogenous -- linearize_kernel for
 // trees, linearize_loop_kernel (cclqr_lin_loop.h) for closed loops, nothing leaves the device -- and then the multipliers eliminated by
-// project_model_kernel, whose complete pivoting stops at the numerical rank of G Bl (singular for a loop: redundant constraint rows).
+// project_model_kernel, whose complete pivoting stops at the numerical rank of G Bl (singular for a loop: redundant constraint rows).  The caller has
+// checked that both kernels fit LDS.
 static int linearize_projected_analytic(const cclqr_mech* m, int32_t nk, const double* zd, int32_t mu, const int32_t* ctrl_joint, const double* Fd,
                                         double* Ap, double* D) {
-    const int nb = m->nb, nj = m->host.loop ? m->nj : nb, mx = 12 * nb, ml = 5 * nj;
-    const size_t nz = 13 * (size_t)nb;
-    if (!linearize_fits_lds(m)) return fail(CCLQR_EUNSUPPORTED, "instance does not fit LDS");
-    if (!project_model_fits(mx, mu, ml)) return fail(CCLQR_EUNSUPPORTED, "the projection of this model does not fit LDS (use h > 0)");
-    LinArgs a;
-    memset(&a, 0, sizeof(a));
-    a.M = m->dev; a.nk = nk; a.mu = mu;
-    for (int i = 0; i < mu; i++) {
-        if (ctrl_joint[i] < 0 || ctrl_joint[i] >= nj) return fail(CCLQR_EINVAL, "controlled joint out of range");
-        a.cj[i] = m->host.loop ? ctrl_joint[i] : m->link_of_joint[ctrl_joint[i]];      // closed-loop tables keep the caller's joint order
-    }
-    const size_t mu1 = (size_t)(mu > 0 ? mu : 1);
-    double *dzd = nullptr, *dFd = nullptr, *dA = nullptr, *dBu = nullptr, *dBl = nullptr, *dG = nullptr, *dAp = nullptr, *dD = nullptr, *dres = nullptr;
-    int *dst = nullptr, *drank = nullptr;
-    std::vector<int> st(nk), rank(nk);
+    static const char* const what = "linearize_projected";
+    const int mx = 12 * m->nb, ml = 5 * (m->host.loop ? m->nj : m->nb);
+    const size_t n = (size_t)nk, mu1 = (size_t)(mu > 0 ? mu : 1);
+    double *dAp = nullptr, *dD = nullptr, *dres = nullptr;
+    int* drank = nullptr;
     std::vector<double> res(nk);
     WsScope scope;
-    hipError_t e = ws_get((void**)&dzd, nk * nz * sizeof(double));
-    if (e == hipSuccess && Fd && mu > 0) e = ws_get((void**)&dFd, (size_t)nk * mu * sizeof(double));
-    if (e == hipSuccess) e = ws_get((void**)&dA, (size_t)nk * mx * mx * sizeof(double));
-    if (e == hipSuccess) e = ws_get((void**)&dBu, (size_t)nk * mx * mu1 * sizeof(double));
-    if (e == hipSuccess) e = ws_get((void**)&dBl, (size_t)nk * mx * ml * sizeof(double));
-    if (e == hipSuccess) e = ws_get((void**)&dG, (size_t)nk * ml * mx * sizeof(double));
-    if (e == hipSuccess) e = ws_get((void**)&dAp, (size_t)nk * mx * mx * sizeof(double));
-    if (e == hipSuccess) e = ws_get((void**)&dD, (size_t)nk * mx * mu1 * sizeof(double));
-    if (e == hipSuccess) e = ws_get((void**)&dres, (size_t)nk * sizeof(double));
-    if (e == hipSuccess) e = ws_get((void**)&dst, (size_t)nk * sizeof(int));
-    if (e == hipSuccess) e = ws_get((void**)&drank, (size_t)nk * sizeof(int));
-    if (e == hipSuccess) e = hipMemcpy(dzd, zd, nk * nz * sizeof(double), hipMemcpyHostToDevice);
-    if (e == hipSuccess && dFd) e = hipMemcpy(dFd, Fd, (size_t)nk * mu * sizeof(double), hipMemcpyHostToDevice);
-    a.zd = dzd; a.Fd = dFd; a.A = dA; a.Bu = dBu; a.Bl = dBl; a.G = dG; a.status = dst;
-    if (e == hipSuccess) e = launch_linearize(a, m->shape, nullptr);
-    if (e == hipSuccess) e = launch_project_model(nk, mx, mu, ml, dA, dBu, dBl, dG, dAp, dD, dres, drank, nullptr);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipMemcpy(Ap, dAp, (size_t)nk * mx * mx * sizeof(double), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && mu > 0) e = hipMemcpy(D, dD, (size_t)nk * mx * mu * sizeof(double), hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(st.data(), dst, nk * sizeof(int), hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(res.data(), dres, nk * sizeof(double), hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return fail(CCLQR_EHIP, std::string("linearize_projected: ") + hipGetErrorString(e));
+    HIPTRY(what, ws_get((void**)&dAp, n * mx * mx * sizeof(double)));      // every block before the upload: no allocation between the two launches
+    HIPTRY(what, ws_get((void**)&dD, n * mx * mu1 * sizeof(double)));
+    HIPTRY(what, ws_get((void**)&dres, n * sizeof(double)));
+    HIPTRY(what, ws_get((void**)&drank, n * sizeof(int)));
+    LinWs w = {};
+    TRY(linearize_to_ws(m, nullptr, 0, nk, zd, Fd, mu, ctrl_joint, w, what));
+    HIPTRY(what, launch_project_model(nk, mx, mu, ml, w.A, w.Bu, w.Bl, w.G, dAp, dD, dres, drank, nullptr));
+    HIPTRY(what, hipDeviceSynchronize());
+    HIPTRY(what, hipMemcpy(Ap, dAp, n * mx * mx * sizeof(double), hipMemcpyDeviceToHost));
+    if (mu > 0) HIPTRY(what, hipMemcpy(D, dD, n * mx * mu * sizeof(double), hipMemcpyDeviceToHost));
+    long long bad = -1;
+    HIPTRY(what, knots_converged(w.status, n, &bad));
+    HIPTRY(what, hipMemcpy(res.data(), dres, n * sizeof(double), hipMemcpyDeviceToHost));
     for (int k = 0; k < nk; k++) {
-        if (st[k] <= 0) return fail(CCLQR_ENOCONV, "Newton did not converge at the setpoint of knot " + std::to_string(k));
+        if (k == bad) return knot_not_converged(k);
         if (!(res[k] < 1e-6)) return fail(CCLQR_ESINGULAR, "the constraint rows of the linear model are inconsistent at knot " + std::to_string(k) + " (G Bl rank-deficient beyond redundancy)");
     }
     return CCLQR_OK;
@@ -919,9 +901,10 @@ static int linearize_projected_analytic(const cclqr_mech* m, int32_t nk, const d
 extern "C" int cclqr_linearize_projected(const cclqr_mech* m, int32_t nk, const double* zd, int32_t mu, const int32_t* ctrl_joint, const double* Fd,
                                          double h, double* Ap, double* D) {
     if (!m || !zd || !Ap || (mu > 0 && (!ctrl_joint || !D))) return fail(CCLQR_EINVAL, "null argument");
-    { int rc = check_device(m); if (rc != CCLQR_OK) return rc; }
+    TRY(check_device(m));
     if (nk < 0 || mu < 0 || mu > m->nj) return fail(CCLQR_EINVAL, "Missmatched length for constraints");
     if (nk == 0) return CCLQR_OK;
+    static const char* const what = "linearize_projected";
     const int nb = m->nb, mx = 12 * nb;
     if (!(h > 0.0)) {
         // the analytic projection keeps [G Bl | G A | G Bu] of a knot in one CU's LDS (project_model_kernel): 175 KB for a 16-body tree, 198 KB for
@@ -968,37 +951,30 @@ extern "C" int cclqr_linearize_projected(const cclqr_mech* m, int32_t nk, const 
     cd.mu = mu; cd.ctrl_joint = ctrl_joint; cd.nK = 0; cd.N = 0; cd.K = nullptr; cd.nsp = 1; cd.zd = zdum.data(); cd.Fd = mu > 0 ? fd.data() : nullptr;
     cd.n_ctrl = (int32_t)n;
     cclqr_ctrl* c = nullptr;
-    int rc = cclqr_ctrl_create(m, &cd, &c);
-    if (rc != CCLQR_OK) return rc;
+    TRY(cclqr_ctrl_create(m, &cd, &c));
+    CtrlOwner own(c);
     double *dz0 = nullptr, *dzT = nullptr, *dAp = nullptr, *dD = nullptr;
     int32_t* dst = nullptr;
     WsScope scope;
-    hipError_t e = ws_get((void**)&dz0, n * nz * sizeof(double));
-    if (e == hipSuccess) e = ws_get((void**)&dzT, n * nz * sizeof(double));
-    if (e == hipSuccess) e = ws_get((void**)&dst, n * sizeof(int32_t));
-    if (e == hipSuccess) e = ws_get((void**)&dAp, (size_t)nk * mx * mx * sizeof(double));
-    if (e == hipSuccess) e = ws_get((void**)&dD, (size_t)nk * mx * (size_t)(mu > 0 ? mu : 1) * sizeof(double));
-    if (e == hipSuccess) e = hipMemcpy(dz0, z0.data(), n * nz * sizeof(double), hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        rc = cclqr_rollout_ex(m, c, (int64_t)n, 1, 1, dz0, nullptr, nullptr, 0, nullptr, dzT, dst, nullptr, nullptr);
-    }
-    if (rc == CCLQR_OK && e == hipSuccess) {
-        const long long work = (long long)nk * (mx + mu) * nb;
-        e = launch_lds<false>(fd_quotient_kernel, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, nullptr, dzT, nk, per, nb, mu, h, dAp, dD);
-    }
-    if (rc == CCLQR_OK && e == hipSuccess) e = hipDeviceSynchronize();
-    if (rc == CCLQR_OK && e == hipSuccess) e = hipMemcpy(st.data(), dst, n * sizeof(int32_t), hipMemcpyDeviceToHost);
-    if (rc == CCLQR_OK && e == hipSuccess) e = hipMemcpy(Ap, dAp, (size_t)nk * mx * mx * sizeof(double), hipMemcpyDeviceToHost);
-    if (rc == CCLQR_OK && e == hipSuccess && mu > 0) e = hipMemcpy(D, dD, (size_t)nk * mx * mu * sizeof(double), hipMemcpyDeviceToHost);
-    cclqr_ctrl_destroy(c);
-    if (rc != CCLQR_OK) return rc;
-    if (e != hipSuccess) return fail(CCLQR_EHIP, std::string("linearize_projected: ") + hipGetErrorString(e));
+    HIPTRY(what, ws_get((void**)&dz0, n * nz * sizeof(double)));
+    HIPTRY(what, ws_get((void**)&dzT, n * nz * sizeof(double)));
+    HIPTRY(what, ws_get((void**)&dst, n * sizeof(int32_t)));
+    HIPTRY(what, ws_get((void**)&dAp, (size_t)nk * mx * mx * sizeof(double)));
+    HIPTRY(what, ws_get((void**)&dD, (size_t)nk * mx * (size_t)(mu > 0 ? mu : 1) * sizeof(double)));
+    HIPTRY(what, hipMemcpy(dz0, z0.data(), n * nz * sizeof(double), hipMemcpyHostToDevice));
+    TRY(cclqr_rollout_ex(m, c, (int64_t)n, 1, 1, dz0, nullptr, nullptr, 0, nullptr, dzT, dst, nullptr, nullptr));
+    const long long work = (long long)nk * (mx + mu) * nb;
+    HIPTRY(what, launch_lds<false>(fd_quotient_kernel, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, nullptr, dzT, nk, per, nb, mu, h, dAp, dD));
+    HIPTRY(what, hipDeviceSynchronize());
+    HIPTRY(what, hipMemcpy(st.data(), dst, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIPTRY(what, hipMemcpy(Ap, dAp, (size_t)nk * mx * mx * sizeof(double), hipMemcpyDeviceToHost));
+    if (mu > 0) HIPTRY(what, hipMemcpy(D, dD, (size_t)nk * mx * mu * sizeof(double), hipMemcpyDeviceToHost));
     for (size_t i = 0; i < n; i++)
         if (st[i] <= 0) return fail(CCLQR_ENOCONV, "Newton did not converge at a perturbed setpoint of knot " + std::to_string(i / per));
     return CCLQR_OK;
 }
 
-// shared tail of the two dlqr entry points: run the recursion on device-resident (A,Bu,Bl,G), download K and kbreak
+// shared tail of the dlqr entry points: run the recursion on device-resident (A,Bu,Bl,G) inside the caller's WsScope, download K and kbreak
 static int run_riccati(int nprob, int mx, int mu, int ml, int N, int time_varying, double tol, const double* dA, const double* dBu,
                        const double* dBl, const double* dG, const double* Q, const double* R, double* K, int32_t* kbreak,
                        const cclqr_riccati_opts* opts) {
@@ -1012,31 +988,44 @@ static int run_riccati(int nprob, int mx, int mu, int ml, int N, int time_varyin
     a.path = opts ? opts->path : 0;
     a.bf16_terms = opts ? opts->bf16_terms : 0;
     a.keep_last = keep_last;
-    a.p_rows = (ric_symmetric(Q, mx) && (mu == 0 || ric_symmetric(R, mu))) ? 0 : 1;
+    a.p_rows = ric_p_rows(Q, mx, R, mu);
     if (a.path < 0 || a.path > 2 || a.bf16_terms < 0 || a.bf16_terms > 3) return fail(CCLQR_EINVAL, "riccati options: path in 0..2, bf16_terms in 0..3");
-    const size_t wd = ric_total_work_doubles(a);
-    hipError_t e = ws_get((void**)&dQ, (size_t)mx * mx * sizeof(double));
-    if (e == hipSuccess) e = ws_get((void**)&dR, (size_t)(mu * mu + 1) * sizeof(double));
-    if (e == hipSuccess) e = ws_get((void**)&dK, (nK + 1) * sizeof(double));
-    if (e == hipSuccess) e = ws_get((void**)&dwork, wd * sizeof(double));
-    if (e == hipSuccess) e = ws_get((void**)&dstop, nprob * sizeof(int));
-    if (e == hipSuccess) e = ws_get((void**)&dkb, nprob * sizeof(int));
-    if (e == hipSuccess) e = ws_get((void**)&dst, nprob * sizeof(int));
-    if (e == hipSuccess) e = hipMemcpy(dQ, Q, (size_t)mx * mx * sizeof(double), hipMemcpyHostToDevice);
-    if (e == hipSuccess && mu > 0) e = hipMemcpy(dR, R, (size_t)mu * mu * sizeof(double), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(dK, 0, (nK + 1) * sizeof(double));
+    HIPTRY("riccati", ws_get((void**)&dQ, (size_t)mx * mx * sizeof(double)));
+    HIPTRY("riccati", ws_get((void**)&dR, (size_t)(mu * mu + 1) * sizeof(double)));
+    HIPTRY("riccati", ws_get((void**)&dK, (nK + 1) * sizeof(double)));
+    HIPTRY("riccati", ws_get((void**)&dwork, ric_total_work_doubles(a) * sizeof(double)));
+    HIPTRY("riccati", ws_get((void**)&dstop, nprob * sizeof(int)));
+    HIPTRY("riccati", ws_get((void**)&dkb, nprob * sizeof(int)));
+    HIPTRY("riccati", ws_get((void**)&dst, nprob * sizeof(int)));
+    HIPTRY("riccati", hipMemcpy(dQ, Q, (size_t)mx * mx * sizeof(double), hipMemcpyHostToDevice));
+    if (mu > 0) HIPTRY("riccati", hipMemcpy(dR, R, (size_t)mu * mu * sizeof(double), hipMemcpyHostToDevice));
+    HIPTRY("riccati", hipMemset(dK, 0, (nK + 1) * sizeof(double)));
     a.stop = dstop;
     a.A = dA; a.Bu = dBu; a.Bl = dBl; a.G = dG; a.Q = dQ; a.R = dR; a.K = dK; a.kbreak = dkb; a.status = dst; a.work = dwork;
-    if (e == hipSuccess) e = launch_riccati(a, nullptr);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e == hipSuccess && nK) e = hipMemcpy(K, dK, nK * sizeof(double), hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(kb.data(), dkb, nprob * sizeof(int), hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(st.data(), dst, nprob * sizeof(int), hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return fail(CCLQR_EHIP, std::string("riccati: ") + hipGetErrorString(e));
+    HIPTRY("riccati", launch_riccati(a, nullptr));
+    HIPTRY("riccati", hipDeviceSynchronize());
+    if (nK) HIPTRY("riccati", hipMemcpy(K, dK, nK * sizeof(double), hipMemcpyDeviceToHost));
+    HIPTRY("riccati", hipMemcpy(kb.data(), dkb, nprob * sizeof(int), hipMemcpyDeviceToHost));
+    HIPTRY("riccati", hipMemcpy(st.data(), dst, nprob * sizeof(int), hipMemcpyDeviceToHost));
     for (int p = 0; p < nprob; p++) {
         if (kbreak) kbreak[p] = kb[p];
         if (st[p] != 0) return fail(CCLQR_ESINGULAR, "G*Bl or M is singular in problem " + std::to_string(p));
     }
+    return CCLQR_OK;
+}
+
+// `count` host models (A, Bu, Bl, G) into the calling thread's workspace for run_riccati (one per problem, or one per knot of a time-varying problem)
+struct RicModels { double *A, *Bu, *Bl, *G; };
+static int upload_models(size_t count, size_t mx, size_t mu, size_t ml, const double* A, const double* Bu, const double* Bl, const double* G, RicModels& d) {
+    static const char* const what = "riccati upload";
+    HIPTRY(what, ws_get((void**)&d.A, count * mx * mx * sizeof(double)));
+    HIPTRY(what, ws_get((void**)&d.Bu, (count * mx * mu + 1) * sizeof(double)));
+    HIPTRY(what, ws_get((void**)&d.Bl, (count * mx * ml + 1) * sizeof(double)));
+    HIPTRY(what, ws_get((void**)&d.G, (count * ml * mx + 1) * sizeof(double)));
+    HIPTRY(what, hipMemcpy(d.A, A, count * mx * mx * sizeof(double), hipMemcpyHostToDevice));
+    if (mu > 0) HIPTRY(what, hipMemcpy(d.Bu, Bu, count * mx * mu * sizeof(double), hipMemcpyHostToDevice));
+    if (ml > 0) HIPTRY(what, hipMemcpy(d.Bl, Bl, count * mx * ml * sizeof(double), hipMemcpyHostToDevice));
+    if (ml > 0) HIPTRY(what, hipMemcpy(d.G, G, count * ml * mx * sizeof(double), hipMemcpyHostToDevice));
     return CCLQR_OK;
 }
 
@@ -1050,42 +1039,20 @@ extern "C" int cclqr_riccati_ex(int32_t nprob, int32_t mx, int32_t mu, int32_t m
                                 const cclqr_riccati_opts* opts) {
     if (!A || !Q || (mu > 0 && (!Bu || !R)) || (ml > 0 && (!Bl || !G)) || !K) return fail(CCLQR_EINVAL, "null argument");
     if (nprob < 1 || mx < 1 || mu < 0 || ml < 0 || N < 1) return fail(CCLQR_EINVAL, "bad sizes");
-    double *dA = nullptr, *dBu = nullptr, *dBl = nullptr, *dG = nullptr;
-    const size_t np = nprob;
     WsScope scope;
-    hipError_t e = ws_get((void**)&dA, np * mx * mx * sizeof(double));
-    if (e == hipSuccess) e = ws_get((void**)&dBu, (np * mx * mu + 1) * sizeof(double));
-    if (e == hipSuccess) e = ws_get((void**)&dBl, (np * mx * ml + 1) * sizeof(double));
-    if (e == hipSuccess) e = ws_get((void**)&dG, (np * ml * mx + 1) * sizeof(double));
-    if (e == hipSuccess) e = hipMemcpy(dA, A, np * mx * mx * sizeof(double), hipMemcpyHostToDevice);
-    if (e == hipSuccess && mu > 0) e = hipMemcpy(dBu, Bu, np * mx * mu * sizeof(double), hipMemcpyHostToDevice);
-    if (e == hipSuccess && ml > 0) e = hipMemcpy(dBl, Bl, np * mx * ml * sizeof(double), hipMemcpyHostToDevice);
-    if (e == hipSuccess && ml > 0) e = hipMemcpy(dG, G, np * ml * mx * sizeof(double), hipMemcpyHostToDevice);
-    int rc = CCLQR_OK;
-    if (e == hipSuccess) rc = run_riccati(nprob, mx, mu, ml, N, 0, tol, dA, dBu, dBl, dG, Q, R, K, kbreak, opts);
-    if (e != hipSuccess) return fail(CCLQR_EHIP, std::string("riccati upload: ") + hipGetErrorString(e));
-    return rc;
+    RicModels d = {};
+    TRY(upload_models((size_t)nprob, mx, mu, ml, A, Bu, Bl, G, d));
+    return run_riccati(nprob, mx, mu, ml, N, 0, tol, d.A, d.Bu, d.Bl, d.G, Q, R, K, kbreak, opts);
 }
 
 extern "C" int cclqr_riccati_tv(int32_t mx, int32_t mu, int32_t ml, const double* A, const double* Bu, const double* Bl, const double* G,
                                 const double* Q, const double* R, int32_t N, double tol, double* K, int32_t* kbreak) {
     if (!A || !Q || (mu > 0 && (!Bu || !R)) || (ml > 0 && (!Bl || !G)) || !K) return fail(CCLQR_EINVAL, "null argument");
     if (mx < 1 || mu < 0 || ml < 0 || N < 2) return fail(CCLQR_EINVAL, "bad sizes");
-    double *dA = nullptr, *dBu = nullptr, *dBl = nullptr, *dG = nullptr;
-    const size_t nk = (size_t)N - 1;
     WsScope scope;
-    hipError_t e = ws_get((void**)&dA, nk * mx * mx * sizeof(double));
-    if (e == hipSuccess) e = ws_get((void**)&dBu, (nk * mx * mu + 1) * sizeof(double));
-    if (e == hipSuccess) e = ws_get((void**)&dBl, (nk * mx * ml + 1) * sizeof(double));
-    if (e == hipSuccess) e = ws_get((void**)&dG, (nk * ml * mx + 1) * sizeof(double));
-    if (e == hipSuccess) e = hipMemcpy(dA, A, nk * mx * mx * sizeof(double), hipMemcpyHostToDevice);
-    if (e == hipSuccess && mu > 0) e = hipMemcpy(dBu, Bu, nk * mx * mu * sizeof(double), hipMemcpyHostToDevice);
-    if (e == hipSuccess && ml > 0) e = hipMemcpy(dBl, Bl, nk * mx * ml * sizeof(double), hipMemcpyHostToDevice);
-    if (e == hipSuccess && ml > 0) e = hipMemcpy(dG, G, nk * ml * mx * sizeof(double), hipMemcpyHostToDevice);
-    int rc = CCLQR_OK;
-    if (e == hipSuccess) rc = run_riccati(1, mx, mu, ml, N, 1, tol, dA, dBu, dBl, dG, Q, R, K, kbreak, nullptr);
-    if (e != hipSuccess) return fail(CCLQR_EHIP, std::string("riccati upload: ") + hipGetErrorString(e));
-    return rc;
+    RicModels d = {};
+    TRY(upload_models((size_t)N - 1, mx, mu, ml, A, Bu, Bl, G, d));
+    return run_riccati(1, mx, mu, ml, N, 1, tol, d.A, d.Bu, d.Bl, d.G, Q, R, K, kbreak, nullptr);
 }
 
 extern "C" int cclqr_riccati_tracking(const cclqr_mech* m, int32_t mu, const int32_t* ctrl_joint, const double* zd, const double* Fd,
@@ -1099,47 +1066,21 @@ extern "C" int cclqr_riccati_tracking_ex(const cclqr_mech* m, int32_t mu, const 
     if (!m || !zd || !Q || !K || (mu > 0 && (!ctrl_joint || !R))) return fail(CCLQR_EINVAL, "null argument");
     if (m->host.loop) return fail(CCLQR_EUNSUPPORTED, "TrackingLQR of a closed-loop mechanism is outside this build's scope");
     if (N < 2 || mu < 0 || mu > m->nb) return fail(CCLQR_EINVAL, "bad sizes");
-    const int nb = m->nb, nk = N - 1;
-    const size_t nz = 13 * (size_t)nb, mx = 12 * (size_t)nb, ml = 5 * (size_t)nb;
-    LinArgs a;
-    memset(&a, 0, sizeof(a));
-    a.M = m->dev; a.nk = nk; a.mu = mu;
-    for (int i = 0; i < mu; i++) {
-        if (ctrl_joint[i] < 0 || ctrl_joint[i] >= nb) return fail(CCLQR_EINVAL, "controlled joint out of range");
-        a.cj[i] = m->link_of_joint[ctrl_joint[i]];
-    }
-    double *dzd = nullptr, *dFd = nullptr, *dA = nullptr, *dBu = nullptr, *dBl = nullptr, *dG = nullptr;
-    int* dst = nullptr;
-    std::vector<int> st(nk);
     // knots 1..N-1 (lqr_tracking.jl:87-88): linearise all of them in one launch, keep the matrices on the device
     WsScope scope;
-    hipError_t e = ws_get((void**)&dzd, nk * nz * sizeof(double));
-    if (e == hipSuccess && Fd && mu > 0) e = ws_get((void**)&dFd, (size_t)nk * mu * sizeof(double));
-    if (e == hipSuccess) e = ws_get((void**)&dA, nk * mx * mx * sizeof(double));
-    if (e == hipSuccess) e = ws_get((void**)&dBu, (nk * mx * (size_t)(mu > 0 ? mu : 1)) * sizeof(double));
-    if (e == hipSuccess) e = ws_get((void**)&dBl, nk * mx * ml * sizeof(double));
-    if (e == hipSuccess) e = ws_get((void**)&dG, nk * ml * mx * sizeof(double));
-    if (e == hipSuccess) e = ws_get((void**)&dst, nk * sizeof(int));
-    if (e == hipSuccess) e = hipMemcpy(dzd, zd, nk * nz * sizeof(double), hipMemcpyHostToDevice);
-    if (e == hipSuccess && dFd) e = hipMemcpy(dFd, Fd, (size_t)nk * mu * sizeof(double), hipMemcpyHostToDevice);
-    a.zd = dzd; a.Fd = dFd; a.A = dA; a.Bu = dBu; a.Bl = dBl; a.G = dG; a.status = dst;
-    if (e == hipSuccess) e = launch_linearize(a, m->shape, nullptr);
-    if (e == hipSuccess) e = hipMemcpy(st.data(), dst, nk * sizeof(int), hipMemcpyDeviceToHost);
-    int rc = CCLQR_OK;
-    if (e == hipSuccess) {
-        for (int k = 0; k < nk && rc == CCLQR_OK; k++)
-            if (st[k] <= 0) rc = fail(CCLQR_ENOCONV, "Newton did not converge at the setpoint of knot " + std::to_string(k));
-        if (rc == CCLQR_OK) rc = run_riccati(1, (int)mx, mu, (int)ml, N, 1, tol, dA, dBu, dBl, dG, Q, R, K, kbreak, opts);
-    }
-    if (e != hipSuccess) return fail(CCLQR_EHIP, std::string("riccati_tracking: ") + hipGetErrorString(e));
-    return rc;
+    LinWs w = {};
+    TRY(linearize_to_ws(m, nullptr, 0, N - 1, zd, Fd, mu, ctrl_joint, w, "riccati_tracking"));
+    long long bad = -1;
+    HIPTRY("riccati_tracking", knots_converged(w.status, (size_t)N - 1, &bad));
+    if (bad >= 0) return knot_not_converged(bad);
+    return run_riccati(1, 12 * m->nb, mu, 5 * m->nb, N, 1, tol, w.A, w.Bu, w.Bl, w.G, Q, R, K, kbreak, opts);
 }
 
 // ---- scoring a rollout on the device (score.hip).  The weights are permuted ONCE, here: traj rows stay in the caller's body order, the controller's K columns
 // and setpoints are in link order (build_ctrl_tables), so the per-body blocks go to link order with them (closed loops: perm is the identity)
 extern "C" int cclqr_score_create(const cclqr_mech* m, const double* Qb, int32_t mu, const double* R, double settle_tol, cclqr_score** out) {
     if (!m || !Qb || !out || (mu > 0 && !R)) return fail(CCLQR_EINVAL, "null argument");
-    { int rc = check_device(m); if (rc != CCLQR_OK) return rc; }
+    TRY(check_device(m));
     if (mu < 0 || mu > m->nj) return fail(CCLQR_EINVAL, "mu = " + std::to_string(mu) + " is not a number of controlled joints of this mechanism (0 .. " + std::to_string(m->nj) + ")");
     if (!std::isfinite(settle_tol)) return fail(CCLQR_EINVAL, "settle_tol is not finite");
     const int nb = m->nb;
@@ -1149,15 +1090,15 @@ extern "C" int cclqr_score_create(const cclqr_mech* m, const double* Qb, int32_t
         if (!std::isfinite(R[e])) return fail(CCLQR_EINVAL, "a weight is not finite: R entry " + std::to_string(e));
     std::vector<double> Ql((size_t)nb * 144);
     for (int l = 0; l < nb; l++) memcpy(&Ql[(size_t)l * 144], Qb + (size_t)m->host.perm[l] * 144, 144 * sizeof(double));
-    cclqr_score* s = new cclqr_score();
+    Owned<cclqr_score, cclqr_score_destroy> own(new cclqr_score());
+    cclqr_score* s = own.p;
     memset(s, 0, sizeof(*s));
     s->settle_tol = settle_tol; s->nb = nb; s->mu = mu; s->device = m->device; s->mech = m;
-    hipError_t e = hipMalloc((void**)&s->Qb_dev, Ql.size() * sizeof(double));
-    if (e == hipSuccess) e = hipMemcpy(s->Qb_dev, Ql.data(), Ql.size() * sizeof(double), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMalloc((void**)&s->R_dev, ((size_t)mu * mu + 1) * sizeof(double));
-    if (e == hipSuccess && mu > 0) e = hipMemcpy(s->R_dev, R, (size_t)mu * mu * sizeof(double), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { cclqr_score_destroy(s); return fail(CCLQR_EHIP, std::string("score weights upload: ") + hipGetErrorString(e)); }
-    *out = s;
+    HIPTRY("score weights upload", hipMalloc((void**)&s->Qb_dev, Ql.size() * sizeof(double)));
+    HIPTRY("score weights upload", hipMemcpy(s->Qb_dev, Ql.data(), Ql.size() * sizeof(double), hipMemcpyHostToDevice));
+    HIPTRY("score weights upload", hipMalloc((void**)&s->R_dev, ((size_t)mu * mu + 1) * sizeof(double)));
+    if (mu > 0) HIPTRY("score weights upload", hipMemcpy(s->R_dev, R, (size_t)mu * mu * sizeof(double), hipMemcpyHostToDevice));
+    *out = own.release();
     return CCLQR_OK;
 }
 
@@ -1172,7 +1113,7 @@ extern "C" int cclqr_score_destroy(cclqr_score* s) {
 extern "C" int cclqr_rollout_score(const cclqr_mech* m, const cclqr_ctrl* c, const cclqr_score* s, int64_t n_inst, int32_t steps, int32_t k0, int64_t first_instance,
                                    const double* traj, double* score, void* stream) {
     if (!m || !c || !s) return fail(CCLQR_EINVAL, "null argument");
-    { int rc = check_device(m); if (rc != CCLQR_OK) return rc; }
+    TRY(check_device(m));
     if (s->mech != m || s->nb != m->nb || s->device != m->device) return fail(CCLQR_EINVAL, "the score weights were created for another mechanism or device");
     if (c->nb != m->nb || c->device != m->device) return fail(CCLQR_EINVAL, "the controller was created for another mechanism or device");
     if (steps < 1 || k0 < 1) return fail(CCLQR_EINVAL, "need steps >= 1 and k0 >= 1 (got steps = " + std::to_string(steps) + ", k0 = " + std::to_string(k0) + ")");

@@ -73,6 +73,31 @@ struct RolloutShape {
     size_t lin_lds;    // dynamic LDS per workgroup (one knot) of the mechanism's linearisation kernel
 };
 
+// zero doubles behind a controller's gain table: the control phase fetches ceil(12 NBP / G) G entries of a row whatever the mechanism's own
+// 12 nb, i.e. up to 12 x 64 - 12 past the end of the LAST row when a short chain runs on a long image.  With one table per instance (n_ctrl > 1)
+// every instance's table carries its own zero pad of that overrun (gain_table_layout, CtrlDev::K_stride includes it), so that the entries
+// past an instance's last row are zeros and never a NEIGHBOUR's gains -- which may be Inf / NaN when that neighbour's recursion diverged, and
+// 0 * NaN would poison a healthy instance's input (ADVICE r4)
+#define CCLQR_K_PAD 768
+// doubles the rollout kernels' control phase fetches past the end of a gain row: they read ceil(12 NBP / G) G entries of a row (G lanes per instance,
+// the LDS image laid out for NBP >= nb links) and let the surplus meet a zero factor.  Closed-loop kernel: exact row length.
+static inline size_t gain_row_overrun(const RolloutShape& s, int nb) {
+    if (s.family == RolloutFamily::Loop) return 0;
+    const long long over = (long long)((12 * s.NBP + s.G - 1) / s.G) * s.G - 12LL * nb;
+    return over > 0 ? (size_t)((over + 1) & ~1LL) : 0;
+}
+// A controller's gain tables in device memory: n_tables tables of rows_per_table rows of 12 nb doubles.  Several tables (one per instance) lie
+// `stride` apart, each behind its own zero pad; K_stride is what CtrlDev carries (0: one shared table); alloc_doubles ends in CCLQR_K_PAD zeros.
+struct GainTableLayout { size_t pad; long long stride, K_stride; size_t alloc_doubles; };
+static inline GainTableLayout gain_table_layout(const RolloutShape& s, int nb, long long n_tables, long long rows_per_table) {
+    GainTableLayout L;
+    L.pad = n_tables > 1 ? gain_row_overrun(s, nb) : 0;
+    L.stride = rows_per_table * 12LL * nb + (long long)L.pad;
+    L.K_stride = n_tables > 1 ? L.stride : 0;
+    L.alloc_doubles = (size_t)(n_tables > 1 ? n_tables : 1) * (size_t)L.stride + CCLQR_K_PAD;
+    return L;
+}
+
 // Instances per wavefront of a launch.  A wavefront's step is latency -- a chain of dependent 5 x 5 stages -- not lanes, and a lane group without an
 // instance is not idle: it evaluates further step lengths of its neighbours' line searches (group_assist / the partner group).  So a batch that would
 // leave SIMDs without a wavefront when packed 64 / G to a wavefront is spread: the fewest instances per wavefront that still fit the batch into
@@ -150,7 +175,7 @@ struct RicArgs {
     int bf16_terms;          // 0: fp64 MFMA; 1..3: split-bf16 products with fp32 accumulation (tiled path)
     int keep_last;           // 1: K is [nprob][mu][mx], the gain of the last executed backward step (= Ku[1] after the back-fill)
     long long kpad = 0;      // doubles left free between the tables of consecutive problems in K (0: contiguous)
-    int p_rows = 0;          // 1: Q or R is not symmetric (ric_symmetric on the host arrays): the kernels that assume a symmetric Pk are not used
+    int p_rows = 0;          // 1: Q or R is not symmetric (ric_p_rows on the host arrays): the kernels that assume a symmetric Pk are not used
 };
 // is the n x n row-major host matrix exactly symmetric?
 inline bool ric_symmetric(const double* X, int n) {
@@ -159,6 +184,8 @@ inline bool ric_symmetric(const double* X, int n) {
             if (!(X[(size_t)i * n + j] == X[(size_t)j * n + i])) return false;
     return true;
 }
+// RicArgs.p_rows: the kernels that assume a symmetric Pk run only when Q and R are EXACTLY symmetric (R is not looked at when mu == 0)
+static inline int ric_p_rows(const double* Q, int mx, const double* R, int mu) { return (ric_symmetric(Q, mx) && (mu == 0 || ric_symmetric(R, mu))) ? 0 : 1; }
 size_t ric_total_work_doubles(const RicArgs& a);
 hipError_t launch_riccati(const RicArgs& a, hipStream_t stream);
 // the RicArgs.path (1 resident, 2 tiled) launch_riccati takes for these arguments -- a call that runs its problems in several launches (chunks) asks once, with
@@ -213,12 +240,6 @@ struct cclqr_plants {
     const cclqr_mech* mech;    // the mechanism whose link order and default values the records were packed with
     int nb, device;
 };
-// zero doubles behind a controller's gain table: the control phase fetches ceil(12 NBP / G) G entries of a row whatever the mechanism's own
-// 12 nb, i.e. up to 12 x 64 - 12 past the end of the LAST row when a short chain runs on a long image.  With one table per instance (n_ctrl > 1)
-// every instance's table carries its own zero pad of that overrun (capi.hip gain_row_overrun, CtrlDev::K_stride includes it), so that the entries
-// past an instance's last row are zeros and never a NEIGHBOUR's gains -- which may be Inf / NaN when that neighbour's recursion diverged, and
-// 0 * NaN would poison a healthy instance's input (ADVICE r4)
-#define CCLQR_K_PAD 768
 // the weights a rollout is scored with (cclqr_score_create): blocks in the controller tables' link order
 struct cclqr_score {
     double *Qb_dev, *R_dev;    // [nb][12][12] link order, [mu][mu]

@@ -12,6 +12,14 @@ struct WsCache {
     size_t used = 0;
     int device = -1;      // the device the cached blocks were allocated on
 };
+// The blocks an entry point takes are free again when it returns: the scope restores the `used` it found, so that an entry point which is
+// called by another one that holds blocks of its own gives back only what it took itself.
+struct WsMark {
+    WsCache& w;
+    const size_t mark;
+    explicit WsMark(WsCache& cache) : w(cache), mark(cache.used) {}
+    ~WsMark() { w.used = mark; }
+};
 // The bookkeeping of the cache with the allocator passed in, so that a CPU test can drive it (tests/emu/ws_cache_test.cpp): blocks
 // are handed out by call position; a block that is too small is replaced; when the calling thread has switched GPU since the blocks
 // were allocated (cclqr_set_device), EVERY cached block is released on its own device first -- a block of another device handed to a

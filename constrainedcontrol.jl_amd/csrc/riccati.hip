@@ -207,7 +207,7 @@ struct RicGrid {
     const double *A, *Bu, *Bl, *G, *Q, *R;
     double *AD, *W, *Abar, *P, *Ku, *KRK, *part, *TSp, *scratch, *K;
     int *stop, *kbreak, *status;
-    long long kpad;    // doubles between the gain tables of consecutive problems in K (per-instance controller tables: capi.hip gain_row_overrun)
+    long long kpad;    // doubles between the gain tables of consecutive problems in K (per-instance controller tables: cclqr_internal.h gain_row_overrun)
     int keep_last;     // 1: only the gain of the last executed backward step is kept (K [nprob][mu][mx] = Ku[1] after the back-fill of
                        // lqr.jl:179-181 = the one gain LQR{T,Inf} keeps, lqr.jl:40-43); 0: the whole table K [nprob][N-1][mu][mx]
     int bf16_terms;    // 0: fp64 MFMA (parity mode); 1..3: the two mx^3 products of a backward step on bf16 MFMA with fp32 accumulation,

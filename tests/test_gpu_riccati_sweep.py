@@ -81,7 +81,7 @@ def build_case(c, tv=False):
     Q, R = _weights(rng, c)
     pr = ref.make_problem(rng, c["mx"], c["mu"], c["ml"], nprob=c["nprob"], break_at=c["brk"], N=c["N"], tv=tv, Q=Q, R=R,
                           ref_idx=c["ref_idx"])
-    # the kernel a case runs on depends on EXACT symmetry of the weights (capi.hip ric_symmetric)
+    # the kernel a case runs on depends on EXACT symmetry of the weights (cclqr_internal.h ric_p_rows)
     assert np.array_equal(pr["Q"], pr["Q"].T) == (c["Q"] != "nonsym") and np.array_equal(pr["R"], pr["R"].T) == (c["R"] != "nonsym")
     return pr
 
@@ -184,7 +184,7 @@ def test_riccati_singular_projection_with_N1_is_not_reached(cclqr, path):
 # per-instance gain tables written by the Riccati kernels themselves (kpad = the zero pad behind every instance's table)
 
 def _gain_row_overrun(mh):
-    """capi.hip gain_row_overrun for a chain: doubles the rollout kernel's control phase reads past the end of a gain row"""
+    """cclqr_internal.h gain_row_overrun for a chain: doubles the rollout kernel's control phase reads past the end of a gain row"""
     G, _ = mh.geometry()
     over = -(-12 * mh.layout_links() // G) * G - 12 * mh.tables.nb
     return (over + 1) & ~1 if over > 0 else 0

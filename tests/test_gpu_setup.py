@@ -415,6 +415,111 @@ def test_error_codes(cclqr):
     assert e.value.code == capi.EINVAL
 
 
+def test_controlled_joint_out_of_range_is_one_refusal_everywhere(cclqr):
+    """every entry point that takes the caller's controlled joints maps them by one rule (capi.hip map_ctrl_joints): joint number nb of a two-link cartpole is
+    CCLQR_EINVAL "controlled joint out of range" in each of them (cclqr_ctrl_create states it through build_ctrl_tables: the code alone is asserted there)"""
+    capi = cclqr._capi
+    ex = cclqr.examples.cartpole_n(1)
+    t = ex["mech"].tables()
+    nb, N = t.nb, 6
+    mech = capi.MechHandle(t)
+    zd = upright_setpoint(1)
+    Q, R = np.eye(12 * nb), np.eye(1)
+    traj = np.tile(zd[None], (N, 1, 1))
+    with pytest.raises(capi.CclqrError) as e:
+        capi.CtrlHandle(mech, [nb])
+    assert e.value.code == capi.EINVAL
+    calls = {"linearize": lambda: capi.linearize(mech, zd[None], [nb]),
+             "linearize_projected": lambda: capi.linearize_projected(mech, zd[None], [nb], h=0.0),
+             "riccati_tracking": lambda: capi.riccati_tracking(mech, [nb], traj, np.zeros((N, 1)), Q, R, N),
+             "BatchLqrHandle": lambda: capi.BatchLqrHandle(mech, np.stack([zd, zd]), [nb], Q, R, N),
+             "BatchTrackingHandle": lambda: capi.BatchTrackingHandle(mech, np.stack([traj, traj]), [nb], Q, R)}
+    for name, call in calls.items():
+        with pytest.raises(capi.CclqrError) as e:
+            call()
+        assert e.value.code == capi.EINVAL and "controlled joint out of range" in str(e.value), (name, str(e.value))
+    assert capi.linearize(mech, zd[None], [nb - 1])[0].shape == (1, 12 * nb, 12 * nb)       # (the last valid joint is taken)
+
+
+def test_sizes_and_null_are_refused_before_anything_is_allocated(cclqr):
+    """cclqr_rollout (host pointers) with a negative batch is CCLQR_EINVAL "bad sizes" -- its staging buffers are sized by n_inst, so the sizes are looked at
+    first --, and cclqr_device_count(NULL) is CCLQR_EINVAL like a null argument of every other entry point"""
+    import ctypes as C
+    capi = cclqr._capi
+    ex = cclqr.examples.cartpole_n(1)
+    t = ex["mech"].tables()
+    mech = capi.MechHandle(t)
+    ctrl = capi.CtrlHandle(mech, [0])
+    L = capi.lib()
+    z0 = np.ascontiguousarray(upright_setpoint(1)[None])
+    zT = np.zeros_like(z0)
+    dp = C.POINTER(C.c_double)
+    for n_inst, steps, k0 in ((-1, 1, 1), (1, -1, 1), (1, 1, 0)):
+        rc = L.cclqr_rollout(mech.ptr, ctrl.ptr, C.c_int64(n_inst), C.c_int32(steps), C.c_int32(k0), z0.ctypes.data_as(dp), None, None, zT.ctypes.data_as(dp), None)
+        assert rc == capi.EINVAL and "bad sizes" in L.cclqr_last_error().decode(), (n_inst, steps, k0, rc)
+    assert not zT.any()
+    assert L.cclqr_device_count(None) == capi.EINVAL and "null argument" in L.cclqr_last_error().decode()
+    assert capi.device_count() >= 1
+
+
+def test_linearising_entry_points_refuse_what_does_not_fit_lds(cclqr):
+    """one knot of a 57-link chain needs 165 992 bytes of LDS in the linearisation kernel (56 links: 163 080 of the 163 840 a compute unit has; the rollout kernel
+    takes both; the boundary is pinned without a GPU by tests/test_capi_host.py): cclqr_riccati_tracking_ex refuses it as cclqr_linearize and the two batched
+    constructors do -- CCLQR_EUNSUPPORTED "instance does not fit LDS", before anything is launched"""
+    capi = cclqr._capi
+    n_links, N = 56, 3
+    t = cclqr.examples.cartpole_n(n_links)["mech"].tables()
+    nb = t.nb
+    assert nb == 57
+    mech = capi.MechHandle(t)
+    zd = upright_setpoint(n_links)
+    traj = np.tile(zd[None], (N, 1, 1))
+    Q, R = np.eye(12 * nb), np.eye(1)
+    calls = {"linearize": lambda: capi.linearize(mech, zd[None], [0]),
+             "riccati_tracking": lambda: capi.riccati_tracking(mech, [0], traj, np.zeros((N, 1)), Q, R, N),
+             "BatchLqrHandle": lambda: capi.BatchLqrHandle(mech, np.stack([zd, zd]), [0], Q, R, N),
+             "BatchTrackingHandle": lambda: capi.BatchTrackingHandle(mech, np.stack([traj, traj]), [0], Q, R)}
+    for name, call in calls.items():
+        with pytest.raises(capi.CclqrError) as e:
+            call()
+        assert e.value.code == capi.EUNSUPPORTED and "instance does not fit LDS" in str(e.value), (name, str(e.value))
+
+
+def test_a_refused_construction_gives_its_memory_back(cclqr):
+    """A batched LQR construction that is refused after everything has been allocated -- 64 four-link chains, N = 200: 64 x 199 x 48 gains = 4.9 MB of tables; one
+    setpoint row NaN, so that its Newton solve fails and the call ends CCLQR_ENOCONV at that setpoint -- releases what it allocated: 20 refused calls do not lower the
+    device's free memory by as much as one call's gain tables (the first call warms the thread's workspace cache, which is kept on purpose)."""
+    import torch
+    capi = cclqr._capi
+    ex = cclqr.examples.cartpole_n(3)
+    t = ex["mech"].tables()
+    nb, n, N, bad = t.nb, 64, 200, 37
+    assert nb == 4
+    mech = capi.MechHandle(t)
+    zd = np.tile(upright_setpoint(3)[None], (n, 1, 1))
+    zd[bad, 2, 4] = np.nan
+    Q, R = np.eye(12 * nb) * t.dt, np.eye(1) * t.dt
+    tables_bytes = n * (N - 1) * 12 * nb * 8
+
+    def refused():
+        with pytest.raises(capi.CclqrError) as e:
+            capi.BatchLqrHandle(mech, zd, [0], Q, R, N)
+        assert e.value.code == capi.ENOCONV and "setpoint %d" % bad in str(e.value), str(e.value)
+
+    refused()
+    torch.cuda.synchronize()
+    free0 = torch.cuda.mem_get_info()[0]
+    for _ in range(20):
+        refused()
+    torch.cuda.synchronize()
+    free1 = torch.cuda.mem_get_info()[0]
+    print("free memory before / after 20 refused constructions: %d / %d bytes (one call's tables: %d)" % (free0, free1, tables_bytes))
+    assert free0 - free1 < tables_bytes
+    ok = capi.BatchLqrHandle(mech, np.tile(upright_setpoint(3)[None], (n, 1, 1)), [0], Q, R, N)      # (the same call without the NaN is taken)
+    assert (ok.kbreak >= 1).all()
+    ok.close()
+
+
 def test_sawyer_config4_pipeline(cclqr, orc):
     """examples/lqr_sawyer.jl through the mirror: URDF numbers -> Mechanism -> LQR (mx = 84, mu = 7, ml = 35) -> batched simulate!"""
     import json

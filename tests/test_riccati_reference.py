@@ -143,9 +143,14 @@ def test_dispatch_mirror_matches_riccati_hip():
     assert all(ref.ric_resident_is_frag(4 * int(b), int(a)) for a, b, _, _ in frag)
     # ric_project_kernel<LDSM>
     assert "if (ml <= RIC_LDS_M && ml > 0) {" in src
-    # the host decides p_rows on exact symmetry of Q and R
-    capi = open(os.path.join(ROOT, "constrainedcontrol.jl_amd", "csrc", "capi.hip")).read()
-    assert capi.count("ric_symmetric(Q, ") == 2
+    # the host decides p_rows on exact symmetry of Q and R: the rule is stated once (cclqr_internal.h ric_p_rows) and every p_rows capi.hip hands to the
+    # kernels is assigned from it, none from a literal or from a second statement of the rule
+    csrc = os.path.join(ROOT, "constrainedcontrol.jl_amd", "csrc")
+    capi, internal = open(os.path.join(csrc, "capi.hip")).read(), open(os.path.join(csrc, "cclqr_internal.h")).read()
+    assert internal.count("ric_symmetric(Q, ") == 1 and capi.count("ric_symmetric(") == 0
+    assert "return (ric_symmetric(Q, mx) && (mu == 0 || ric_symmetric(R, mu))) ? 0 : 1;" in internal
+    assigned = re.findall(r"p_rows\s*=\s*([^;]*);", capi)
+    assert len(assigned) == 3 and all(re.fullmatch(r"ric_p_rows\(Q, (\(int\))?mx, R, mu\)", a) for a in assigned), assigned
 
 
 def _sweep_launches():
