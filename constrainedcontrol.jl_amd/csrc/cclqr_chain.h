@@ -836,6 +836,43 @@ HD void ck_tri_back(int t, int j, const TriPlanB& B, const Lay& Y, double* L) {
     L[Y.DL + 5 * l + row] = y - (z[0] * dn[0] + z[1] * dn[1] + z[2] * dn[2] + z[3] * dn[3] + z[4] * dn[4]);
 }
 
+// ---- the middle link of a TWO-FRONT sweep is solved from registers by the sweep lanes (the 16-, 32- and 64-lane kernels): ck_tri_mid_regs in
+// rollout_chain.hip, which holds the cross-lane part.  Here: what a lane does on its own around it -- the store of a sweep step that leaves the
+// middle link's update in registers, and the first back step with dl of the middle link from registers.
+// Store of a sweep step of such a kernel: in the plan's last step (`last`) the target of a working front is always the middle link, whose update
+// stays in registers -- neither the middle block nor the scratch block is read again.
+HD void tri_step_store_fold(double* L, int otg, int oout, const double* tg, const double* zy, bool last) {
+    if (!last) {
+#pragma unroll
+        for (int r = 0; r < 5; r++) L[otg + r] = tg[r];
+    }
+#pragma unroll
+    for (int r = 0; r < 5; r++) L[oout + r] = zy[r];
+}
+// The first back step (ck_tri_back with j = 0) of such a kernel, in two halves around the middle solve.  Its own operands -- row `row` of Z_l and
+// y_l of the link next to the middle one -- are what the sweep stored, so they are requested in front of the middle solve's arithmetic, by every
+// lane and unconditionally (a lane without a back step reads the middle link's words, inside the image, and drops them): they arrive under the
+// pivot chain.  dl of the middle link comes from the registers of ck_tri_mid_regs (rollout_chain.hip), not from DL[mid].  Same sum as ck_tri_back.
+// A chain WITHOUT a sweep step (one link) has no back step either, and its middle system is still in LDS: there the five z reads are pointed at the
+// lane's own column of SJJ[mid], or at R[mid] -- where its cursor's oOut still points -- and ck_tri_mid_regs takes them as its share.  So that
+// case costs no read of its own and waits for nothing but these five.
+struct TriBack0 { double z[5], y; int l; bool on; };
+HD void ck_tri_back0_load(TriBack0& Q, int t, bool done, const TriPlanB& B, const TriCur& K, const Lay& Y, const double* L) {
+    const TriPlan& P = B.P;
+    const int front = t >> 3, row = t & 7;
+    Q.on = !done && t < 16 && row < 5 && 0 < (front ? P.nB : P.nA);
+    Q.l = P.mid + (Q.on ? B.st * (1 - 2 * front) : 0);      // (front 0: the link behind the middle one, front 1: the one in front of it; no branch)
+    const int rr = row < 5 ? row : 0;
+    const bool nostep = P.steps == 0;
+    const int o = nostep ? K.oOut : Y.SJJ + 25 * Q.l + rr, d = nostep ? 1 : 5;
+#pragma unroll
+    for (int cI = 0; cI < 5; cI++) Q.z[cI] = LDS_RD(L, o + d * cI);
+    Q.y = LDS_RD(L, Y.R + 5 * Q.l + rr);
+}
+HD void ck_tri_back0_store(const TriBack0& Q, int t, const Lay& Y, double* L, const double* dn) {
+    if (Q.on) L[Y.DL + 5 * Q.l + (t & 7)] = Q.y - (Q.z[0] * dn[0] + Q.z[1] * dn[1] + Q.z[2] * dn[2] + Q.z[3] * dn[3] + Q.z[4] * dn[4]);
+}
+
 // ---- one level of odd-even (cyclic) reduction ahead of the two-front sweep.  The sweep is a chain of dependent 5x5
 // factorisations (one per step and front); eliminating every second link FIRST costs about two such steps -- all odd links at once,
 // W lanes per link -- and halves the chain that is left.  For the links x_i = cs + st i, i < n, every odd i (l = x_i, p = l - st,

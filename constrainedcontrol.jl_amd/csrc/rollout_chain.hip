@@ -37,6 +37,45 @@ __device__ __forceinline__ void from_next(const double* in, double* out) {
     for (int i = 0; i < N; i++) out[i] = wave_from_next(in[i]);
 }
 
+// ---- the middle link of a TWO-FRONT sweep, solved from registers by the sweep lanes (the 16-, 32- and 64-lane instantiations; cclqr_chain.h has the
+// one-lane solve out of LDS, ck_tri_mid, which the 8-lane kernels keep).  When the last sweep step ends, the lanes that ran it hold every word of the
+// middle system in their target registers: lane (t & 7) = c < 5 of a front column c of the updated block, lane 5 the right-hand side, and the two
+// fronts of an instance share a 16-lane DPP row.  So nothing of it goes through LDS: the two shares are merged by one row rotation (own + row_ror:8
+// of the other's -- the same bits in either operand order, and the same as ck_tri_mid's A + (merge ? As : 0.0), the + 0.0 of a plan that does not
+// merge included), lane k's column goes to every lane of the row by row_newbcast:k (30 doubles, 60 moves; no ds_bpermute / ds_swizzle, which come
+// back through lgkmcnt and would add full drains), and every lane factorises and solves redundantly, as tri_step does.  dl of the middle link is then
+// in the registers of the lanes of the first back step (ck_tri_back0_store).
+// K: the lane's cursor behind the sweep (K.n = 0 for a lane that takes no part and for a `done` instance); tg: its target registers of the last
+// step.  A front that did not run the plan's last step (the shorter one of a plan that does not merge) contributes zeros by a select: its tg is
+// stale.  A chain without a sweep step takes front 0's share from the reads of ck_tri_back0_load, behind a wavefront-uniform BRANCH: as a select
+// it would make every solve wait for those reads in front of the pivot chain.  Called by ALL lanes in wavefront-uniform control flow (a DPP
+// move reads lanes, so none of the row may be masked off); the result is garbage, and unused, outside the sweep lanes of instances that solve.
+__device__ __forceinline__ void ck_tri_mid_regs(int t, bool done, const TriPlanB& B, const TriCur& K, const Lay& Y, const double* L, const double* tg, double* dl, TriBack0& Q) {
+    const TriPlan& P = B.P;
+    ck_tri_back0_load(Q, t, done, B, K, Y, L);
+    double m[5];
+    const bool ran = K.n == P.steps;
+#pragma unroll
+    for (int r = 0; r < 5; r++) m[r] = ran ? tg[r] : 0.0;
+    if (P.steps == 0) {
+        asm volatile("");      // (keeps the branch a branch)
+        const bool f0 = (t & 8) == 0;
+#pragma unroll
+        for (int r = 0; r < 5; r++) m[r] = f0 ? Q.z[r] : 0.0;
+    }
+#pragma unroll
+    for (int r = 0; r < 5; r++) m[r] = m[r] + dpp_row_ror<8>(m[r]);      // the other front's lane of the same column
+    double A[25];
+#pragma unroll
+    for (int i = 0; i < 5; i++) {
+        A[i * 5 + 0] = dpp_f64<0x150>(m[i]); A[i * 5 + 1] = dpp_f64<0x151>(m[i]); A[i * 5 + 2] = dpp_f64<0x152>(m[i]);      // row_newbcast:k
+        A[i * 5 + 3] = dpp_f64<0x153>(m[i]); A[i * 5 + 4] = dpp_f64<0x154>(m[i]);
+        dl[i] = dpp_f64<0x155>(m[i]);
+    }
+    lu5_factor(A);
+    lu5_solve(A, dl);
+}
+
 // residual (+ Jacobians when JAC) at the point s - alpha ds with constraint forces C - alpha cd; returns the group's ||f||_2.
 // With JAC the Schur complement rows of the point go straight to LDS: W = G_v D^-1 only lives inside this function.
 // (The full-step trial is evaluated with JAC on the speculation that it is accepted; if it is not, the accepted point is
@@ -495,18 +534,49 @@ __global__ __launch_bounds__(WAVE_BLOCK) void rollout_chain_kernel(RolloutArgs a
                 const TriPlan& P = PB.P;
                 TriCur K = tri_cursor(t, PB, Y);
                 if (done) K.n = 0;
-                for (int i = 0; i < P.steps; i++) {
-                    double tg[5], zy[5];
-                    int otg = 0, oout = 0;
-                    if (tri_step(K, i, L, tg, zy, &otg, &oout)) tri_step_store(L, otg, oout, tg, zy);
+                if constexpr (G >= 16) {
+                    // two fronts: the middle link never goes through LDS.  The last sweep step leaves its update in the sweep lanes' registers, the
+                    // middle solve runs there (ck_tri_mid_regs: all lanes, no hand-over in front of it), and the first back step takes dl of the
+                    // middle link from the same registers -- two store -> load round trips fewer per Newton iteration on the dependent path
+                    double tg[5] = {0.0, 0.0, 0.0, 0.0, 0.0}, dlm[5];
+                    for (int i = 0; i < P.steps; i++) {
+                        double zy[5];
+                        int otg = 0, oout = 0;
+                        int left = P.steps - 1 - i;
+                        LANE_INT_FRESH(left);      // (a per-lane test made here: as a scalar one it has the compiler clone the whole step for the last pass)
+                        if (tri_step(K, i, L, tg, zy, &otg, &oout)) tri_step_store_fold(L, otg, oout, tg, zy, left == 0);
+                        WAVE_HANDOVER();
+                    }
+                    STAMP(PF_TRI_FWD);
+                    TriBack0 B0;
+                    ck_tri_mid_regs(t, done, PB, K, Y, L, tg, dlm, B0);
+                    ck_tri_back0_store(B0, t, Y, L, dlm);
                     WAVE_HANDOVER();
-                }
-                STAMP(PF_TRI_FWD);
-                if (!done) ck_tri_mid<(G >= 16)>(t, PB, Y, L);      // (8 lanes: one front, no plan merges)
-                WAVE_HANDOVER();
-                for (int j = 0; j < P.steps; j++) {
-                    if (!done) ck_tri_back(t, j, PB, Y, L);
+                    for (int j = 1; j < P.steps; j++) {
+                        if (!done) ck_tri_back(t, j, PB, Y, L);
+                        WAVE_HANDOVER();
+                    }
+                    // dl of the middle link for the phases behind the solve (cr_back, the body solve, the accept phase): no back step reads it from
+                    // LDS, so the five stores queue behind the back substitution, not in front of its first reads
+                    if (!done && t == 0) {
+#pragma unroll
+                        for (int i = 0; i < 5; i++) L[Y.DL + 5 * P.mid + i] = dlm[i];
+                    }
                     WAVE_HANDOVER();
+                } else {      // 8 lanes: one front, which sweeps to the chain's first link; one lane solves it out of LDS
+                    for (int i = 0; i < P.steps; i++) {
+                        double tg[5], zy[5];
+                        int otg = 0, oout = 0;
+                        if (tri_step(K, i, L, tg, zy, &otg, &oout)) tri_step_store(L, otg, oout, tg, zy);
+                        WAVE_HANDOVER();
+                    }
+                    STAMP(PF_TRI_FWD);
+                    if (!done) ck_tri_mid<false>(t, PB, Y, L);
+                    WAVE_HANDOVER();
+                    for (int j = 0; j < P.steps; j++) {
+                        if (!done) ck_tri_back(t, j, PB, Y, L);
+                        WAVE_HANDOVER();
+                    }
                 }
                 if (CR && cr) {
                     cr_back<CRW>(t, cs, cn, 1, Y, L, done);
