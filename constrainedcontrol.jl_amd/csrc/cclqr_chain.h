@@ -68,6 +68,10 @@ struct LinkC {
     HD bool has_fric() const { return (flags & FRIC) != 0; }
     static const int PRIM = 512;               // the lane is the PRIMARY one of its link's KL lanes (several lanes per link: below); always set when KL = 1
     HD bool prim() const { return (flags & PRIM) != 0; }
+    // the Schur rows split by block (ck_schur_rows_split): the lane owns no link and builds the child-side block of the link sixteen lanes below / that link has a child
+    static const int HELP = 1024, HELPC = 2048;
+    HD bool help() const { return (flags & HELP) != 0; }
+    HD bool help_c() const { return (flags & HELPC) != 0; }
     HD bool dead() const { return (flags & DEAD) != 0; }
     HD bool bad() const { return (flags & BAD) != 0; }
     HD void set_valid(bool v) { flags |= v ? (16 | ((flags & 1) << 5)) : 0; }
@@ -75,9 +79,11 @@ struct LinkC {
 #if defined(__HIP_DEVICE_COMPILE__)
 #define LINK_FLAGS_FRESH(c) asm volatile("" : "+v"((c).flags))
 #define LANE_INT_FRESH(x) asm volatile("" : "+v"(x))       // the same for any per-lane integer a predicate is formed from
+#define LANE_F64_FRESH(x) asm volatile("" : "+v"(x))       // a per-lane double the compiler is to take as it is (not as the select that formed it)
 #else
 #define LINK_FLAGS_FRESH(c) ((void)0)
 #define LANE_INT_FRESH(x) ((void)0)
+#define LANE_F64_FRESH(x) ((void)0)
 #endif
 
 // P: the records of the plant the lane's instance runs on, [nb] in link order -- the mechanism's own (M->rec) or a row of a per-instance plant table
@@ -446,6 +452,100 @@ HD void ck_schur_rows(const LinkC& c, int j, bool store, const Lay& Y, double* L
                 rr = g[r] - (c.sxb * xd + bd) - (ad - c.sxa * xa);
             }
             L[Y.R + 5 * j + r] = rr;
+        }
+    }
+}
+
+// ---- the same rows SPLIT BY BLOCK between the link's lane and the idle lane sixteen above it: the 32-lane kernels whose lane group holds at most 17
+// links (NBP 16, 17).  ck_schur_rows is bound by the LDS instructions every lane issues, whatever the lane keeps of them, and lanes 16 .. 31 keep
+// nothing.  So the one instruction stream builds TWO blocks, not three:
+//   slot 1 = s1 (wXT kx1') + wPB k1'   (+ wPA ka' on a link's lane)      link's lane j: S_jj -> SJJ[j]        helper lane 16 + l: S_lc -> SPJ[l + 1]
+//   slot 3 = wPA k3' + s3 (wXT kx3')                                     link's lane j: S_jp -> SJP[j]        lane 0 of a 17-link group: S_0c -> SPJ[1]
+// The HELPER lane 16 + l holds link l's wXT and wPB (the caller moves them there: rollout_chain.hip schur_split_take), reads G_k of link l + 1 where
+// the link's lane reads its own, and scales by - sxb of link l: schur_split_helper leaves that in the lane's c.sxb, and - 0 in c.sxa, so that
+// sxb + sxa is slot 1's scale on every lane.  Operand rows, scales, store addresses and store predicates are per-lane values; the code is one.
+// R0: the group holds 17 links, lane 16 owns the leaf and link 0 has no helper.  wPA of link 0 is identically zero (joint_eval_sparse: its parent is
+// the origin) and its S_jp does not exist, so lane 0 builds S_0c in slot 3 with wPB in wPA's place; its wPA ka' and wPA pd, + 0 today, are + 0 by a
+// select.  Every sum keeps the order of ck_schur_rows -- (s xx + bb) + aa, bjc - sxb xjc as bjc + (- sxb) xjc, ajp - sxa xjp likewise -- so the
+// blocks are the same bits (tests/emu/emu_schur_split.cpp).  wPA is the caller's array and is overwritten on that lane.  One build issues 63 operand
+// reads (15, 15, 15, 9, 9 over the columns) and 55 stores where ck_schur_rows issues 87 and 80.
+// store: the lane's link is evaluated; gstore: the same for the lane's whole instance (what a helper goes by).
+HD void schur_split_helper(LinkC& c, bool has_child, double sxb_link) {
+    c.flags |= LinkC::HELP | (has_child ? LinkC::HELPC : 0);
+    c.sxb = -sxb_link; c.sxa = -0.0;
+}
+template <bool R0>
+HD void ck_schur_rows_split(const LinkC& c, int t, bool store, bool gstore, const Lay& Y, double* L, const double (*wXT)[3], const double (*wPB)[3],
+                            double (*wPA)[3], const double* g, const double* d, const double* pd) {
+    const bool help = c.help(), root = R0 && t == 0, plain = !help && !root;
+    // joint whose G_k the child-side block reads (a lane that builds none stays inside the image: its own link's, or the helped one's); no branches
+    const int jc = t - (help ? 16 : 0) + ((c.flags >> (help ? 11 : 2)) & 1);
+    const int j1 = help ? jc : t, j3 = plain ? t - ((c.flags >> 1) & 1) : jc;
+    const int x1 = Y.GKA + GKSZ * j1, p1 = x1 + (help ? 3 : 0);      // (PA of a joint's row lies three words behind its PB)
+    const int x3 = Y.GKA + GKSZ * j3, p3 = x3 + (root ? 3 : 0);
+    const int o1 = (help ? Y.SPJ : Y.SJJ) + 25 * j1, o3 = (root ? Y.SPJ + 25 * jc : Y.SJP + 25 * t);
+    // (slot 3 is stored by lanes that store slot 1 only: the second test sits inside the first, as has_a / has_c sit inside `store` in ck_schur_rows)
+    const bool st1 = help ? (gstore && c.help_c()) : store, st3 = root ? c.has_c() : c.has_a();
+    const double s1 = c.sxb + c.sxa, s3 = root ? -c.sxb : -c.sxa;
+    // what slot 1 adds to s1 xx + bb: wPA ka' on a link's lane; + 0, which wPA ka' is today, on lane 0 of a 17-link group; - 0 (x - 0 = x for every x,
+    // - 0 included: the child-side block has no third term) on a helper
+    double z0 = help ? -0.0 : 0.0;
+    LANE_F64_FRESH(z0);      // (one select per sum: as a constant it becomes two)
+    if (R0 && root) {        // slot 3's W on lane 0 of a 17-link group, IN PLACE: no second copy of W lives
+#pragma unroll
+        for (int r = 0; r < 5; r++)
+#pragma unroll
+            for (int k = 0; k < 3; k++) wPA[r][k] = wPB[r][k];
+    }
+    const double (*wP3)[3] = wPA;
+#pragma unroll
+    for (int q = 0; q < 5; q++) {
+        const int o = gk_row(q), ob = q < 3 ? 3 : 0;   // offset of PB inside the row
+        double kx1[3], kx3[3], k1[3], ka[3], k3[3];
+#pragma unroll
+        for (int i = 0; i < 3; i++) {
+            if (q < 3) { kx1[i] = LDS_RD(L, x1 + o + i); kx3[i] = LDS_RD(L, x3 + o + i); }
+            else { kx1[i] = 0.0; kx3[i] = 0.0; }
+            k1[i] = LDS_RD(L, p1 + o + ob + i); ka[i] = LDS_RD(L, x1 + o + ob + 3 + i); k3[i] = LDS_RD(L, p3 + o + ob + i);
+        }
+        double u1[5], u3[5];
+#pragma unroll
+        for (int r = 0; r < 5; r++) {
+            const double bb = wPB[r][0] * k1[0] + wPB[r][1] * k1[1] + wPB[r][2] * k1[2];
+            const double aa = wP3[r][0] * ka[0] + wP3[r][1] * ka[1] + wP3[r][2] * ka[2];
+            const double ajp = wP3[r][0] * k3[0] + wP3[r][1] * k3[1] + wP3[r][2] * k3[2];
+            const double z = plain ? aa : z0;
+            if (r < 3 && q < 3) {
+                const double xx = wXT[r][0] * kx1[0] + wXT[r][1] * kx1[1] + wXT[r][2] * kx1[2];
+                const double xjp = wXT[r][0] * kx3[0] + wXT[r][1] * kx3[1] + wXT[r][2] * kx3[2];
+                const double u = s1 * xx + bb;
+                u1[r] = u + z; u3[r] = ajp + s3 * xjp;
+            } else { u1[r] = bb + z; u3[r] = ajp; }
+        }
+        // (unconditional in form, per-lane in address and predicate; element (r, q) of a block at 5 q + r)
+        if (st1) {
+#pragma unroll
+            for (int r = 0; r < 5; r++) L[o1 + 5 * q + r] = u1[r];
+            if (st3) {
+#pragma unroll
+                for (int r = 0; r < 5; r++) L[o3 + 5 * q + r] = u3[r];
+            }
+        }
+        SCHED_FENCE();     // (as in ck_schur_rows)
+    }
+    if (store) {
+#pragma unroll
+        for (int r = 0; r < 5; r++) {
+            const double bd = wPB[r][0] * d[3] + wPB[r][1] * d[4] + wPB[r][2] * d[5];
+            double ad = wP3[r][0] * pd[3] + wP3[r][1] * pd[4] + wP3[r][2] * pd[5];
+            if (R0) ad = root ? 0.0 : ad;
+            double rr = g[r] - bd - ad;
+            if (r < 3) {
+                const double xd = wXT[r][0] * d[0] + wXT[r][1] * d[1] + wXT[r][2] * d[2];
+                const double xa = wXT[r][0] * pd[0] + wXT[r][1] * pd[1] + wXT[r][2] * pd[2];
+                rr = g[r] - (c.sxb * xd + bd) - (ad - c.sxa * xa);
+            }
+            L[Y.R + 5 * t + r] = rr;
         }
     }
 }

@@ -76,6 +76,48 @@ __device__ __forceinline__ void ck_tri_mid_regs(int t, bool done, const TriPlanB
     lu5_solve(A, dl);
 }
 
+// ---- the cross-lane part of the Schur rows split by block (cclqr_chain.h ck_schur_rows_split; the 32-lane kernels of at most 17 links): lane 16 + l
+// of a group takes a value of lane l.  One swap of DPP rows per dword (v_permlane16_swap_b32 exchanges the odd rows of its first operand with the
+// even rows of its second): with both operands the same value, the first result is rows (0, 0, 2, 2) of it and the second rows (1, 1, 3, 3).  A
+// vector-ALU instruction: no LDS queue slot, nothing to wait for.  KEEP: lanes with `keep` (lane 16 of a 17-link group, which owns the leaf) hold on
+// to their own value, which for a lane of an odd row is the second result.  Called by ALL lanes in wavefront-uniform control flow.
+__device__ __forceinline__ auto swap_rows_b32(unsigned first, unsigned second) { return __builtin_amdgcn_permlane16_swap(first, second, false, false); }
+// N doubles at a time: the copies that the swaps consume are all made first (one 64-bit move per double), so that no swap reads a register the
+// instruction in front of it wrote (which costs two wait states each).
+template <bool KEEP, int N>
+__device__ __forceinline__ void from_row_below(double* v, bool keep) {
+    double cp[N];
+#pragma unroll
+    for (int i = 0; i < N; i++) { cp[i] = v[i]; asm volatile("" : "+v"(cp[i])); }
+#pragma unroll
+    for (int i = 0; i < N; i++) {
+        const auto a = swap_rows_b32((unsigned)__double2loint(cp[i]), (unsigned)__double2loint(v[i]));
+        const auto b = swap_rows_b32((unsigned)__double2hiint(cp[i]), (unsigned)__double2hiint(v[i]));
+        const unsigned lo = KEEP ? (keep ? a[1] : a[0]) : a[0], hi = KEEP ? (keep ? b[1] : b[0]) : b[0];
+        v[i] = __hiloint2double((int)hi, (int)lo);
+    }
+}
+// which kernels split the rows, and whether link 0 is without a helper (17 links: lane 16 owns the leaf)
+template <int G, int NBP, int KL> struct SchurSplit { static const bool ON = G == 32 && NBP <= 17 && KL == 1, R0 = NBP == 17; };
+// once per launch: the helper lanes' flags and scale (schur_split_helper).  M->childl is read at an index below 16.
+template <int NBP>
+__device__ __forceinline__ void schur_split_setup(LinkC& c, int t, const MechDev* M, int nb) {
+    const int l = t & 15;
+    const bool help = t >= 16 && !c.on();
+    double sl = c.sxb;
+    from_row_below<false, 1>(&sl, false);
+    if (help) schur_split_helper(c, l < nb && M->childl[l] >= 0, sl);
+}
+// the helper lanes take wXT and wPB of their link IN PLACE: their own are dead values (they evaluate no joint)
+template <bool R0>
+__device__ __forceinline__ void schur_split_take(const LinkC& c, int t, double (*wXT)[3], double (*wPB)[3]) {
+    const bool keep = R0 && t >= 16 && !c.help();
+#pragma unroll
+    for (int r = 0; r < 3; r++) from_row_below<R0, 3>(wXT[r], keep);
+#pragma unroll
+    for (int r = 0; r < 5; r++) from_row_below<R0, 3>(wPB[r], keep);
+}
+
 // residual (+ Jacobians when JAC) at the point s - alpha ds with constraint forces C - alpha cd; returns the group's ||f||_2.
 // With JAC the Schur complement rows of the point go straight to LDS: W = G_v D^-1 only lives inside this function.
 // (The full-step trial is evaluated with JAC on the speculation that it is accepted; if it is not, the accepted point is
@@ -84,8 +126,10 @@ __device__ __forceinline__ void ck_tri_mid_regs(int t, bool done, const TriPlanB
 // says so (a vote: the rows are wavefront-wide work); the residual, the Jacobian code in front of them and the norm are the same either way.
 // KL > 1 (several lanes per link, cclqr_chain.h): t is the LINK of the lane (its sub-lane is Q.w); with Jacobians the lane evaluates the rows of its slots only
 // and builds their Schur rows, the body's share of the norm comes from the primary sub-lane alone.  KL = 1: the code of rounds 2-4, unchanged.
-template <int G, bool JAC, int KL = 1>
-__device__ __forceinline__ double chain_eval(LinkC& c, LinkS& S, int t, const Lay& Y, double* L, double alpha, bool active, bool rows, double dt, const SubSel& Q PROF_ARG) {
+// SP: the Schur rows are split by block with the lanes sixteen above (1; 2 = in a 17-link group: SchurSplit); inst_on: the lane's instance is evaluated
+// (`active` without the lane's own link: what a helper lane stores by).
+template <int G, bool JAC, int KL = 1, int SP = 0>
+__device__ __forceinline__ double chain_eval(LinkC& c, LinkS& S, int t, const Lay& Y, double* L, double alpha, bool active, bool inst_on, bool rows, double dt, const SubSel& Q PROF_ARG) {
     double part = 0.0;
     double NB[9], g[5], xq[7];
     const bool store_dinv = JAC && __any(rows);
@@ -133,6 +177,18 @@ __device__ __forceinline__ double chain_eval(LinkC& c, LinkS& S, int t, const La
         STAMP(PF_SCHUR_S);
     } else {
         double wXT[3][3], wPB[5][3], wPA[5][3];
+        if constexpr (JAC && SP != 0) {
+            // a lane that evaluates no joint hands whatever its registers hold to the swap (schur_split_take), which overwrites it there: said here, so
+            // that the compiler does not set 24 doubles to zero for those lanes first
+#pragma unroll
+            for (int r = 0; r < 3; r++)
+#pragma unroll
+                for (int k = 0; k < 3; k++) asm volatile("" : "=v"(wXT[r][k]));
+#pragma unroll
+            for (int r = 0; r < 5; r++)
+#pragma unroll
+                for (int k = 0; k < 3; k++) asm volatile("" : "=v"(wPB[r][k]));
+        }
         if (active) {
             joint_eval_sparse<JAC>(c, pxq, pxq + 3, xq, xq + 3, pNB, NB, g, wXT, wPB, wPA);
             if (KL == 1) {
@@ -151,7 +207,12 @@ __device__ __forceinline__ double chain_eval(LinkC& c, LinkS& S, int t, const La
             if (__any(rows)) {
                 double pd[6];
                 from_prev<6>(S.d, pd);
-                ck_schur_rows(c, t, active, Y, L, wXT, wPB, wPA, g, S.d, pd);
+                if constexpr (SP != 0) {
+                    schur_split_take<SP == 2>(c, t, wXT, wPB);
+                    ck_schur_rows_split<SP == 2>(c, t, active, inst_on, Y, L, wXT, wPB, wPA, g, S.d, pd);
+                } else {
+                    ck_schur_rows(c, t, active, Y, L, wXT, wPB, wPA, g, S.d, pd);
+                }
             } else {
                 PCOUNT(PF_ROWS_SKIPPED);
             }
@@ -300,6 +361,8 @@ __global__ __launch_bounds__(WAVE_BLOCK) void rollout_chain_kernel(RolloutArgs a
     if (a.plants) plant = a.plants + ((unsigned)a.plant_off + (have ? (unsigned)inst : 0u)) * (unsigned)nb;      // (a table holds fewer than 2^31 records: cclqr_plants_create)
     link_load_consts_rec(c, M, plant, (KL > 1 && w >= KL) ? CCLQR_MAXL : tl, nb, dt);
     if (KL == 1 || w == 0) c.flags |= LinkC::PRIM;
+    constexpr int SP = SchurSplit<G, NBP, KL>::ON ? (SchurSplit<G, NBP, KL>::R0 ? 2 : 1) : 0;
+    if constexpr (SP != 0) schur_split_setup<NBP>(c, t, M, nb);
     SubSel Q;
     if (KL > 1) sub_setup<KL>(c, w < KL ? w : 0, Q);
     if (EXTRA && CT->has_fric && c.on()) { c.fric = CT->fric[tl]; if (c.fric != 0.0) c.flags |= LinkC::FRIC; }
@@ -498,7 +561,7 @@ __global__ __launch_bounds__(WAVE_BLOCK) void rollout_chain_kernel(RolloutArgs a
         bool need_jac = !done;
         for (int iter = 1; iter <= NEWTON_MAXIT; iter++) {
             if (__any(need_jac)) {
-                const double nf = chain_eval<G, true, KL>(c, S, tl, Y, L, 0.0, c.live() && need_jac, need_jac, dt, Q PROF_PASS);
+                const double nf = chain_eval<G, true, KL, SP>(c, S, tl, Y, L, 0.0, c.live() && need_jac, need_jac, need_jac, dt, Q PROF_PASS);
                 if (iter == 1) normf0 = nf;
             }
             WAVE_HANDOVER();
@@ -620,7 +683,7 @@ __global__ __launch_bounds__(WAVE_BLOCK) void rollout_chain_kernel(RolloutArgs a
             const bool want_rows = !done && !(normf0 < NEWTON_EPS && nd < NEWTON_EPS);
             bool ls_done = done, jac_ok = __any(want_rows);
             {
-                const double nf = chain_eval<G, true, KL>(c, S, tl, Y, L, 1.0, active, want_rows, dt, Q PROF_PASS);
+                const double nf = chain_eval<G, true, KL, SP>(c, S, tl, Y, L, 1.0, active, !done, want_rows, dt, Q PROF_PASS);
                 if (!ls_done) {
                     normf1 = nf;
                     if (!(normf1 > normf0)) ls_done = true;
