@@ -18,7 +18,8 @@ EXPORTS = ["cclqr_last_error", "cclqr_version", "cclqr_device_count", "cclqr_set
            "cclqr_rollout_dev", "cclqr_rollout_ex", "cclqr_rollout_host_ex", "cclqr_ctrl_reserve_noise", "cclqr_riccati_ex", "cclqr_riccati_tracking_ex",
            "cclqr_release_workspaces", "cclqr_rollout_geometry", "cclqr_rollout_layout_links", "cclqr_ctrl_set_feedforward", "cclqr_abi_layout", "cclqr_rollout_lanes_per_link", "cclqr_rollout_instances_per_wavefront",
            "cclqr_plants_create", "cclqr_plants_destroy", "cclqr_rollout_plants", "cclqr_linearize_plants", "cclqr_ctrl_create_lqr_batch_plants",
-           "cclqr_ctrl_create_tracking_batch_plants", "cclqr_ctrl_get_gains", "cclqr_score_create", "cclqr_score_destroy", "cclqr_rollout_score"]
+           "cclqr_ctrl_create_tracking_batch_plants", "cclqr_ctrl_get_gains", "cclqr_score_create", "cclqr_score_destroy", "cclqr_rollout_score",
+           "cclqr_riccati_weights", "cclqr_ctrl_create_lqr_batch_weights"]
 ABI_VERSION = 202     # include/cclqr.h CCLQR_ABI_VERSION: the structs below mirror that header (verified field by field against cclqr_abi_layout at load time)
 ROLLOUT_NO_ALLOC = 1  # cclqr_rollout_opts.flags: the call may neither allocate nor synchronise (a hipGraph capture is open on the device)
 ROLLOUT_CARRY_STATUS = 4  # ... `status` is read and written: an instance lost in an earlier launch stays frozen, the others merge this launch's result into it
@@ -249,24 +250,31 @@ class CtrlHandle:
 class BatchLqrHandle:
     """cclqr_ctrl* built by cclqr_ctrl_create_lqr_batch: one LQR per setpoint (linearsystem + dlqr + controller tables), gains device-resident"""
 
-    def __init__(self, mech, zd, ctrl_joint, Q, R, N, Fd=None, tol=1e-5, infinite_horizon=False, plants=None, first_plant=0):
+    def __init__(self, mech, zd, ctrl_joint, Q, R, N, Fd=None, tol=1e-5, infinite_horizon=False, plants=None, first_plant=0, n_weights=None):
         """infinite_horizon: LQR{T,Inf} -- N = Ntemp = ceil(10/Δt) (lqr.jl:26), only Ku[1] per setpoint is kept.
-        plants: a PlantsHandle (cclqr_ctrl_create_lqr_batch_plants) -- table k is designed on the plant with global index first_plant + k"""
+        plants: a PlantsHandle (cclqr_ctrl_create_lqr_batch_plants) -- table k is designed on the plant with global index first_plant + k.
+        n_weights: Q [n_weights][12 nb][12 nb], R [n_weights][mu][mu], one pair per table (cclqr_ctrl_create_lqr_batch_weights; the library refuses any count but
+        1 and the number of setpoints); None: one pair, through the entry points that take one"""
         nb = mech.tables.nb
         zd = f64(zd).reshape(-1, nb, 13)
         n = zd.shape[0]
         cj = i32(ctrl_joint).reshape(-1)
         mu = len(cj)
         Fd = None if Fd is None else f64(Fd).reshape(n, mu)
-        Q, R = f64(Q).reshape(12 * nb, 12 * nb), f64(R).reshape(mu, mu)
+        nw = 1 if n_weights is None else int(n_weights)
+        Q, R = f64(Q).reshape(nw, 12 * nb, 12 * nb), f64(R).reshape(nw, mu, mu)
         self.kbreak = np.zeros(n, dtype=np.int32)
         self.mu, self.N, self.nsp, self.n_ctrl = mu, (0 if infinite_horizon else int(N)), 1, n
         self._arrs = [zd, cj, Fd, Q, R]
+        self.mech = mech
         self.plants, self.first_plant = plants, int(first_plant)      # (the plants it was designed on: kept for error messages only)
         self.ptr = C.c_void_p()
-        tail = (C.c_int32(n), _d(zd), C.c_int32(mu), _i(cj), _d(Fd), _d(Q), _d(R), C.c_int32(int(N)), C.c_int32(1 if infinite_horizon else 0), C.c_double(float(tol)),
-                _i(self.kbreak), C.byref(self.ptr))
-        if plants is None:
+        head = (C.c_int32(n), _d(zd), C.c_int32(mu), _i(cj), _d(Fd))
+        last = (_d(Q), _d(R), C.c_int32(int(N)), C.c_int32(1 if infinite_horizon else 0), C.c_double(float(tol)), _i(self.kbreak), C.byref(self.ptr))
+        tail = head + last
+        if n_weights is not None:
+            check(lib().cclqr_ctrl_create_lqr_batch_weights(mech.ptr, None if plants is None else plants.ptr, C.c_int64(int(first_plant)), *head, C.c_int32(nw), *last))
+        elif plants is None:
             check(lib().cclqr_ctrl_create_lqr_batch(mech.ptr, *tail))
         else:
             check(lib().cclqr_ctrl_create_lqr_batch_plants(mech.ptr, plants.ptr, C.c_int64(int(first_plant)), *tail))
@@ -594,6 +602,35 @@ def riccati(A, Bu, Bl, G, Q, R, N, tol=1e-5, path=0, bf16_terms=0, keep_last=Fal
     check(lib().cclqr_riccati_ex(C.c_int32(nprob), C.c_int32(mx), C.c_int32(mu), C.c_int32(ml), _d(A), _d(Bu), _d(Bl), _d(G), _d(Q), _d(R),
                                  C.c_int32(N), C.c_double(tol), _d(K), _i(kb), C.byref(o)))
     return (K[0], int(kb[0])) if single else (K, kb)
+
+
+def riccati_weights(A, Bu, Bl, G, Q, R, N, tol=1e-5, path=0, bf16_terms=0, keep_last=False, K=None):
+    """batched dlqr with one pair of weights per problem (cclqr_riccati_weights): A [nprob][mx][mx], Q [n_weights][mx][mx], R [n_weights][mu][mu] with n_weights = 1
+    or nprob (the library refuses anything else) -> K [nprob][N-1][mu][mx], kbreak [nprob].  path, bf16_terms, keep_last as riccati.  K: the array to fill
+    (default: a new one)"""
+    A = f64(A)
+    mx = A.shape[-1]
+    A = A.reshape(-1, mx, mx)
+    nprob = A.shape[0]
+    Bu, Bl = f64(Bu), f64(Bl)
+    Bu = Bu.reshape(nprob, mx, Bu.shape[-1] if Bu.ndim > 1 else -1)
+    mu = Bu.shape[2]
+    Bl = Bl.reshape(nprob, mx, Bl.shape[-1] if Bl.ndim > 1 else -1)
+    ml = Bl.shape[2]
+    G = f64(G).reshape(nprob, ml, mx)
+    Q = f64(Q).reshape(-1, mx, mx)
+    nw = Q.shape[0]
+    R = f64(R).reshape(nw, mu, mu)
+    shape = (nprob, (1 if keep_last else N - 1) if N > 1 else 0, mu, mx)
+    if K is None:
+        K = np.zeros(shape)
+    if K.shape != shape or K.dtype != np.float64 or not K.flags.c_contiguous:
+        raise ValueError("K must be a contiguous float64 array of shape %s" % (shape,))
+    kb = np.zeros(nprob, dtype=np.int32)
+    o = RiccatiOpts(int(path), int(bf16_terms), 1 if keep_last else 0, 0)
+    check(lib().cclqr_riccati_weights(C.c_int32(nprob), C.c_int32(mx), C.c_int32(mu), C.c_int32(ml), _d(A), _d(Bu), _d(Bl), _d(G), C.c_int32(nw), _d(Q), _d(R),
+                                      C.c_int32(N), C.c_double(tol), _d(K), _i(kb), C.byref(o)))
+    return K, kb
 
 
 def riccati_tv(A, Bu, Bl, G, Q, R, N, tol=1e-5):

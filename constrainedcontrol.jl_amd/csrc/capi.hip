@@ -325,17 +325,24 @@ static hipError_t knots_converged(const int* status_dev, size_t nk, long long* b
 }
 static int knot_not_converged(long long k) { return fail(CCLQR_ENOCONV, "Newton did not converge at the setpoint of knot " + std::to_string(k)); }
 
-extern "C" int cclqr_ctrl_create_lqr_batch_plants(const cclqr_mech* m, const cclqr_plants* plants, int64_t first_plant, int32_t n_ctrl, const double* zd, int32_t mu,
-                                                  const int32_t* ctrl_joint, const double* Fd, const double* Q, const double* R, int32_t N, int32_t infinite_horizon,
-                                                  double tol, int32_t* kbreak, cclqr_ctrl** out) {
+// the one refusal the per-problem weights add (cclqr_riccati_weights, cclqr_ctrl_create_lqr_batch_weights): before anything is allocated or launched
+static int check_n_weights(int n_weights, int nprob, const char* of) {
+    if (n_weights == 1 || n_weights == nprob) return CCLQR_OK;
+    return fail(CCLQR_EINVAL, "n_weights = " + std::to_string(n_weights) + ": the weights are one pair shared by all (1) or one pair per " + of + " (" + std::to_string(nprob) + ")");
+}
+
+extern "C" int cclqr_ctrl_create_lqr_batch_weights(const cclqr_mech* m, const cclqr_plants* plants, int64_t first_plant, int32_t n_ctrl, const double* zd, int32_t mu,
+                                                   const int32_t* ctrl_joint, const double* Fd, int32_t n_weights, const double* Q, const double* R, int32_t N,
+                                                   int32_t infinite_horizon, double tol, int32_t* kbreak, cclqr_ctrl** out) {
     static const char* const what = "batched LQR construction";
     const bool inf = infinite_horizon != 0;
     if (!m || !zd || !Q || !out || (mu > 0 && (!ctrl_joint || !R))) return fail(CCLQR_EINVAL, "null argument");
     TRY(check_device(m));
     if (m->host.loop) return fail(CCLQR_EUNSUPPORTED, "batched LQR construction is for tree mechanisms (closed loops: cclqr_linearize_projected)");
     if (n_ctrl < 1 || N < 2 || mu < 1 || mu > m->nb) return fail(CCLQR_EINVAL, "bad sizes");
+    TRY(check_n_weights(n_weights, n_ctrl, "table"));
     const int nb = m->nb;
-    const size_t nz = 13 * (size_t)nb, mx = 12 * (size_t)nb, ml = 5 * (size_t)nb, np = (size_t)n_ctrl;
+    const size_t nz = 13 * (size_t)nb, mx = 12 * (size_t)nb, ml = 5 * (size_t)nb, np = (size_t)n_ctrl, nw = (size_t)n_weights;
     CtrlOwner own(ctrl_new(m));
     cclqr_ctrl* c = own.p;
     CtrlDev& H = c->host;
@@ -372,14 +379,15 @@ extern "C" int cclqr_ctrl_create_lqr_batch_plants(const cclqr_mech* m, const ccl
     ra.nprob = n_ctrl; ra.mx = (int)mx; ra.mu = mu; ra.ml = (int)ml; ra.N = N; ra.time_varying = 0; ra.tol = tol; ra.path = 0; ra.bf16_terms = 0; ra.keep_last = inf ? 1 : 0;
     ra.kpad = (long long)L.pad;
     ra.p_rows = ric_p_rows(Q, (int)mx, R, mu);
-    HIPTRY(what, ws_get((void**)&dQ, mx * mx * sizeof(double)));
-    HIPTRY(what, ws_get((void**)&dR, (size_t)(mu * mu + 1) * sizeof(double)));
+    ric_per_problem_weights(ra, Q, R, n_weights);      // (one pair per table: table p is designed with pair p)
+    HIPTRY(what, ws_get((void**)&dQ, nw * mx * mx * sizeof(double)));
+    HIPTRY(what, ws_get((void**)&dR, (nw * mu * mu + 1) * sizeof(double)));
     HIPTRY(what, ws_get((void**)&dwork, ric_total_work_doubles(ra) * sizeof(double)));
     HIPTRY(what, ws_get((void**)&dstop, np * sizeof(int)));
     HIPTRY(what, ws_get((void**)&dkb, np * sizeof(int)));
     HIPTRY(what, ws_get((void**)&dst, np * sizeof(int)));
-    HIPTRY(what, hipMemcpy(dQ, Q, mx * mx * sizeof(double), hipMemcpyHostToDevice));
-    HIPTRY(what, hipMemcpy(dR, R, (size_t)mu * mu * sizeof(double), hipMemcpyHostToDevice));
+    HIPTRY(what, hipMemcpy(dQ, Q, nw * mx * mx * sizeof(double), hipMemcpyHostToDevice));
+    HIPTRY(what, hipMemcpy(dR, R, nw * mu * mu * sizeof(double), hipMemcpyHostToDevice));
     HIPTRY(what, hipMemset(c->K_dev, 0, L.alloc_doubles * sizeof(double)));
     ra.stop = dstop; ra.A = w.A; ra.Bu = w.Bu; ra.Bl = w.Bl; ra.G = w.G; ra.Q = dQ; ra.R = dR; ra.K = c->K_dev; ra.kbreak = dkb; ra.status = dst; ra.work = dwork;
     HIPTRY(what, launch_riccati(ra, nullptr));
@@ -398,6 +406,12 @@ extern "C" int cclqr_ctrl_create_lqr_batch_plants(const cclqr_mech* m, const ccl
     }
     *out = own.release();
     return CCLQR_OK;
+}
+
+extern "C" int cclqr_ctrl_create_lqr_batch_plants(const cclqr_mech* m, const cclqr_plants* plants, int64_t first_plant, int32_t n_ctrl, const double* zd, int32_t mu,
+                                                  const int32_t* ctrl_joint, const double* Fd, const double* Q, const double* R, int32_t N, int32_t infinite_horizon,
+                                                  double tol, int32_t* kbreak, cclqr_ctrl** out) {
+    return cclqr_ctrl_create_lqr_batch_weights(m, plants, first_plant, n_ctrl, zd, mu, ctrl_joint, Fd, 1, Q, R, N, infinite_horizon, tol, kbreak, out);
 }
 
 extern "C" int cclqr_ctrl_create_lqr_batch(const cclqr_mech* m, int32_t n_ctrl, const double* zd, int32_t mu, const int32_t* ctrl_joint,
@@ -974,9 +988,10 @@ extern "C" int cclqr_linearize_projected(const cclqr_mech* m, int32_t nk, const 
     return CCLQR_OK;
 }
 
-// shared tail of the dlqr entry points: run the recursion on device-resident (A,Bu,Bl,G) inside the caller's WsScope, download K and kbreak
+// shared tail of the dlqr entry points: run the recursion on device-resident (A,Bu,Bl,G) inside the caller's WsScope, download K and kbreak.  Q, R: n_weights = 1
+// pair shared by the problems, or nprob pairs (the caller has checked: check_n_weights)
 static int run_riccati(int nprob, int mx, int mu, int ml, int N, int time_varying, double tol, const double* dA, const double* dBu,
-                       const double* dBl, const double* dG, const double* Q, const double* R, double* K, int32_t* kbreak,
+                       const double* dBl, const double* dG, int n_weights, const double* Q, const double* R, double* K, int32_t* kbreak,
                        const cclqr_riccati_opts* opts) {
     const int keep_last = (opts && opts->keep_last) ? 1 : 0;
     const size_t nK = (size_t)nprob * (N > 1 ? (keep_last ? 1 : N - 1) : 0) * mu * mx;
@@ -989,16 +1004,18 @@ static int run_riccati(int nprob, int mx, int mu, int ml, int N, int time_varyin
     a.bf16_terms = opts ? opts->bf16_terms : 0;
     a.keep_last = keep_last;
     a.p_rows = ric_p_rows(Q, mx, R, mu);
+    ric_per_problem_weights(a, Q, R, n_weights);
+    const size_t nw = (size_t)n_weights;
     if (a.path < 0 || a.path > 2 || a.bf16_terms < 0 || a.bf16_terms > 3) return fail(CCLQR_EINVAL, "riccati options: path in 0..2, bf16_terms in 0..3");
-    HIPTRY("riccati", ws_get((void**)&dQ, (size_t)mx * mx * sizeof(double)));
-    HIPTRY("riccati", ws_get((void**)&dR, (size_t)(mu * mu + 1) * sizeof(double)));
+    HIPTRY("riccati", ws_get((void**)&dQ, nw * mx * mx * sizeof(double)));
+    HIPTRY("riccati", ws_get((void**)&dR, (nw * mu * mu + 1) * sizeof(double)));
     HIPTRY("riccati", ws_get((void**)&dK, (nK + 1) * sizeof(double)));
     HIPTRY("riccati", ws_get((void**)&dwork, ric_total_work_doubles(a) * sizeof(double)));
     HIPTRY("riccati", ws_get((void**)&dstop, nprob * sizeof(int)));
     HIPTRY("riccati", ws_get((void**)&dkb, nprob * sizeof(int)));
     HIPTRY("riccati", ws_get((void**)&dst, nprob * sizeof(int)));
-    HIPTRY("riccati", hipMemcpy(dQ, Q, (size_t)mx * mx * sizeof(double), hipMemcpyHostToDevice));
-    if (mu > 0) HIPTRY("riccati", hipMemcpy(dR, R, (size_t)mu * mu * sizeof(double), hipMemcpyHostToDevice));
+    HIPTRY("riccati", hipMemcpy(dQ, Q, nw * mx * mx * sizeof(double), hipMemcpyHostToDevice));
+    if (mu > 0) HIPTRY("riccati", hipMemcpy(dR, R, nw * mu * mu * sizeof(double), hipMemcpyHostToDevice));
     HIPTRY("riccati", hipMemset(dK, 0, (nK + 1) * sizeof(double)));
     a.stop = dstop;
     a.A = dA; a.Bu = dBu; a.Bl = dBl; a.G = dG; a.Q = dQ; a.R = dR; a.K = dK; a.kbreak = dkb; a.status = dst; a.work = dwork;
@@ -1037,12 +1054,19 @@ extern "C" int cclqr_riccati(int32_t nprob, int32_t mx, int32_t mu, int32_t ml, 
 extern "C" int cclqr_riccati_ex(int32_t nprob, int32_t mx, int32_t mu, int32_t ml, const double* A, const double* Bu, const double* Bl,
                                 const double* G, const double* Q, const double* R, int32_t N, double tol, double* K, int32_t* kbreak,
                                 const cclqr_riccati_opts* opts) {
+    return cclqr_riccati_weights(nprob, mx, mu, ml, A, Bu, Bl, G, 1, Q, R, N, tol, K, kbreak, opts);
+}
+
+extern "C" int cclqr_riccati_weights(int32_t nprob, int32_t mx, int32_t mu, int32_t ml, const double* A, const double* Bu, const double* Bl,
+                                     const double* G, int32_t n_weights, const double* Q, const double* R, int32_t N, double tol, double* K,
+                                     int32_t* kbreak, const cclqr_riccati_opts* opts) {
     if (!A || !Q || (mu > 0 && (!Bu || !R)) || (ml > 0 && (!Bl || !G)) || !K) return fail(CCLQR_EINVAL, "null argument");
     if (nprob < 1 || mx < 1 || mu < 0 || ml < 0 || N < 1) return fail(CCLQR_EINVAL, "bad sizes");
+    TRY(check_n_weights(n_weights, nprob, "problem"));
     WsScope scope;
     RicModels d = {};
     TRY(upload_models((size_t)nprob, mx, mu, ml, A, Bu, Bl, G, d));
-    return run_riccati(nprob, mx, mu, ml, N, 0, tol, d.A, d.Bu, d.Bl, d.G, Q, R, K, kbreak, opts);
+    return run_riccati(nprob, mx, mu, ml, N, 0, tol, d.A, d.Bu, d.Bl, d.G, n_weights, Q, R, K, kbreak, opts);
 }
 
 extern "C" int cclqr_riccati_tv(int32_t mx, int32_t mu, int32_t ml, const double* A, const double* Bu, const double* Bl, const double* G,
@@ -1052,7 +1076,7 @@ extern "C" int cclqr_riccati_tv(int32_t mx, int32_t mu, int32_t ml, const double
     WsScope scope;
     RicModels d = {};
     TRY(upload_models((size_t)N - 1, mx, mu, ml, A, Bu, Bl, G, d));
-    return run_riccati(1, mx, mu, ml, N, 1, tol, d.A, d.Bu, d.Bl, d.G, Q, R, K, kbreak, nullptr);
+    return run_riccati(1, mx, mu, ml, N, 1, tol, d.A, d.Bu, d.Bl, d.G, 1, Q, R, K, kbreak, nullptr);
 }
 
 extern "C" int cclqr_riccati_tracking(const cclqr_mech* m, int32_t mu, const int32_t* ctrl_joint, const double* zd, const double* Fd,
@@ -1073,7 +1097,7 @@ extern "C" int cclqr_riccati_tracking_ex(const cclqr_mech* m, int32_t mu, const 
     long long bad = -1;
     HIPTRY("riccati_tracking", knots_converged(w.status, (size_t)N - 1, &bad));
     if (bad >= 0) return knot_not_converged(bad);
-    return run_riccati(1, 12 * m->nb, mu, 5 * m->nb, N, 1, tol, w.A, w.Bu, w.Bl, w.G, Q, R, K, kbreak, opts);
+    return run_riccati(1, 12 * m->nb, mu, 5 * m->nb, N, 1, tol, w.A, w.Bu, w.Bl, w.G, 1, Q, R, K, kbreak, opts);
 }
 
 // ---- scoring a rollout on the device (score.hip).  The weights are permuted ONCE, here: traj rows stay in the caller's body order, the controller's K columns

@@ -176,6 +176,8 @@ struct RicArgs {
     int keep_last;           // 1: K is [nprob][mu][mx], the gain of the last executed backward step (= Ku[1] after the back-fill)
     long long kpad = 0;      // doubles left free between the tables of consecutive problems in K (0: contiguous)
     int p_rows = 0;          // 1: Q or R is not symmetric (ric_p_rows on the host arrays): the kernels that assume a symmetric Pk are not used
+    long long q_stride = 0, r_stride = 0;      // doubles between the Q / R of consecutive problems: 0 = one pair shared by every problem, or mx*mx / mu*mu = one
+                                               // pair per problem (ric_per_problem_weights)
 };
 // is the n x n row-major host matrix exactly symmetric?
 inline bool ric_symmetric(const double* X, int n) {
@@ -186,6 +188,21 @@ inline bool ric_symmetric(const double* X, int n) {
 }
 // RicArgs.p_rows: the kernels that assume a symmetric Pk run only when Q and R are EXACTLY symmetric (R is not looked at when mu == 0)
 static inline int ric_p_rows(const double* Q, int mx, const double* R, int mu) { return (ric_symmetric(Q, mx) && (mu == 0 || ric_symmetric(R, mu))) ? 0 : 1; }
+// ... of a batch with one (Q, R) per problem, Q [n][mx][mx], R [n][mu][mu]: p_rows is a property of the LAUNCH (it picks the kernels), so one problem whose
+// weights are not symmetric sends the whole batch to the kernels that do not assume a symmetric Pk
+static inline int ric_p_rows_batch(const double* Q, int mx, const double* R, int mu, long long n) {
+    for (long long p = 0; p < n; p++)
+        if (ric_p_rows(Q + p * mx * mx, mx, mu == 0 ? R : R + p * mu * mu, mu)) return 1;
+    return 0;
+}
+// a call's host weights into its launch arguments: n_weights = 1 leaves the shared pair (stride 0, a.p_rows as the caller set it from that pair); n_weights =
+// a.nprob gives every problem its own pair and widens a.p_rows to the batch's
+static inline void ric_per_problem_weights(RicArgs& a, const double* Q, const double* R, int n_weights) {
+    if (n_weights <= 1) return;
+    a.q_stride = (long long)a.mx * a.mx;
+    a.r_stride = (long long)a.mu * a.mu;
+    a.p_rows = ric_p_rows_batch(Q, a.mx, R, a.mu, n_weights);
+}
 size_t ric_total_work_doubles(const RicArgs& a);
 hipError_t launch_riccati(const RicArgs& a, hipStream_t stream);
 // the RicArgs.path (1 resident, 2 tiled) launch_riccati takes for these arguments -- a call that runs its problems in several launches (chunks) asks once, with

@@ -205,6 +205,7 @@ struct RicGrid {
     int nprob, mx, mu, ml, N, nlin, na, tm, tn;
     double tol;
     const double *A, *Bu, *Bl, *G, *Q, *R;
+    long long q_stride, r_stride;      // doubles between the Q / R of consecutive problems: 0 = one pair shared by all, or mx*mx / mu*mu (RicArgs)
     double *AD, *W, *Abar, *P, *Ku, *KRK, *part, *TSp, *scratch, *K;
     int *stop, *kbreak, *status;
     long long kpad;    // doubles between the gain tables of consecutive problems in K (per-instance controller tables: cclqr_internal.h gain_row_overrun)
@@ -229,6 +230,11 @@ __device__ inline bool ric_knot_singular(const RicGrid& a, int prob, int k) {
     return ric_knot_piv(a, (size_t)prob * a.nlin + (a.nlin > 1 ? k - 1 : 0))[a.ml] != 0;
 }
 
+// Q / R of problem `prob`.  Called once per workgroup with prob = a block index: the result is wave-uniform and stays in scalar registers, and the
+// tile loops index it as they indexed the shared matrix (stride 0: the very same addresses)
+__device__ inline const double* ric_Q_of(const RicGrid& a, int prob) { return a.Q + (long long)prob * a.q_stride; }
+__device__ inline const double* ric_R_of(const RicGrid& a, int prob) { return a.R + (long long)prob * a.r_stride; }
+
 template <bool LDSM>
 __global__ __launch_bounds__(RIC_THREADS) void ric_project_kernel(RicGrid a, int lds_cols) {
     extern __shared__ double lds_M[];
@@ -239,6 +245,7 @@ __global__ __launch_bounds__(RIC_THREADS) void ric_project_kernel(RicGrid a, int
     const size_t lin = (size_t)prob * a.nlin + knot;
     const double *A = a.A + lin * mx * mx, *Bu = a.Bu + lin * mx * mu, *Bl = a.Bl + lin * mx * ml, *G = a.G + lin * ml * mx;
     double* AD = a.AD + lin * mx * na;
+    const double* Qp = ric_Q_of(a, prob);
     double* sc = a.scratch + lin * (((size_t)ml * ml + (size_t)ml * na + 3) & ~(size_t)1);
     double* GBlg = sc;
     double* X = sc + (((size_t)ml * ml + 1) & ~(size_t)1);
@@ -250,7 +257,7 @@ __global__ __launch_bounds__(RIC_THREADS) void ric_project_kernel(RicGrid a, int
     for (int i = tr; i < mx; i += RIC_THREADS / 32) {
         for (int j = tc; j < mx; j += 32) AD[(size_t)i * na + j] = A[(size_t)i * mx + j];
         for (int j = tc; j < mu; j += 32) AD[(size_t)i * na + mx + j] = Bu[(size_t)i * mu + j];
-        if (knot == 0) for (int j = tc; j < mx; j += 32) a.P[((size_t)prob * mx + i) * mx + j] = a.Q[(size_t)i * mx + j];   // Pk = Q  lqr.jl:147
+        if (knot == 0) for (int j = tc; j < mx; j += 32) a.P[((size_t)prob * mx + i) * mx + j] = Qp[(size_t)i * mx + j];   // Pk = Q  lqr.jl:147
     }
     __syncthreads();
     if (ml > 0) {
@@ -453,6 +460,7 @@ __global__ __launch_bounds__(TILE_THREADS) void ric_gain_update_kernel(RicGrid a
     double* TS = gl;
     double* S = gl + (size_t)mu * na;
     int* piv = (int*)(S + (size_t)mu * mu);
+    const double* Rp = ric_R_of(a, prob);
     if (tid == 0) sing = 0;
     for (int e = tid; e < mu * na; e += TILE_THREADS) {
         const double* tp = a.TSp + (size_t)prob * a.tm * mu * na + e;
@@ -461,7 +469,7 @@ __global__ __launch_bounds__(TILE_THREADS) void ric_gain_update_kernel(RicGrid a
         TS[e] = sacc;
     }
     __syncthreads();
-    for (int e = tid; e < mu * mu; e += TILE_THREADS) S[e] = a.R[e] + TS[(size_t)(e / mu) * na + mx + e % mu];
+    for (int e = tid; e < mu * mu; e += TILE_THREADS) S[e] = Rp[e] + TS[(size_t)(e / mu) * na + mx + e % mu];
     __syncthreads();
     for (int c = 0; c < mu; c++) {                       // LU with partial pivoting, mu <= 32
         if (tid == 0) {
@@ -497,7 +505,7 @@ __global__ __launch_bounds__(TILE_THREADS) void ric_gain_update_kernel(RicGrid a
         }
         if (lead) {
             for (int q = 0; q < mu; q++) { const double v = TS[(size_t)q * na + j]; Ku[(size_t)q * mx + j] = v; Kout[(size_t)q * mx + j] = v; }   // Ku[k][i] = Kk[i:i,:]  lqr.jl:162-164
-            for (int q = 0; q < mu; q++) { double sacc = 0.0; for (int r = 0; r < mu; r++) sacc += a.R[q * mu + r] * TS[(size_t)r * na + j]; KRK[(size_t)q * mx + j] = sacc; }
+            for (int q = 0; q < mu; q++) { double sacc = 0.0; for (int r = 0; r < mu; r++) sacc += Rp[q * mu + r] * TS[(size_t)r * na + j]; KRK[(size_t)q * mx + j] = sacc; }
         }
     }
     __syncthreads();
@@ -550,6 +558,7 @@ __global__ __launch_bounds__(TILE_THREADS) void ric_pn_kernel(RicGrid a, int k) 
     const double* W = a.W + (size_t)prob * mx * na;
     const double* Ku = a.Ku + (size_t)prob * mu * mx;
     const double* KRK = a.KRK + (size_t)prob * mu * mx;
+    const double* Qp = ric_Q_of(a, prob);
     double *KuI = kt, *KRKJ = kt + mu * 32;
     for (int e = tid; e < mu * 32; e += TILE_THREADS) {
         const int q = e >> 5, c = e & 31;
@@ -565,7 +574,7 @@ __global__ __launch_bounds__(TILE_THREADS) void ric_pn_kernel(RicGrid a, int k) 
     for (int e = tid; e < 1024; e += TILE_THREADS) {
         const int ii = e >> 5, jj = e & 31, i = i0 + ii, j = j0 + jj;
         if (i < mx && j < mx) {
-            double v = a.Q[(size_t)i * mx + j];
+            double v = Qp[(size_t)i * mx + j];
             for (int q = 0; q < mu; q++) v += KuI[q * 32 + ii] * KRKJ[q * 32 + jj];
             v += ((red[0][e] + red[1][e]) + red[2][e]) + red[3][e];
             Pn[(size_t)i * mx + j] = v;
@@ -797,9 +806,13 @@ __global__ __launch_bounds__(RIC_THREADS) void riccati_resident_kernel(RicGrid a
                             (NGT > 0 ? (size_t)RIC_WAVES * RIC_YB : 0)));
     static_assert(NGT == 0 || (MUT >= 1 && MUT <= 8), "the register-fragment form keeps Y = Abar' W_D of a row strip as 16 x 8 doubles");
     double* Kout = a.K + (size_t)prob * ((size_t)(a.keep_last ? 1 : (N > 1 ? N - 1 : 0)) * mu * mx + a.kpad);
+    const double* Qp = ric_Q_of(a, prob);      // this problem's weights: Q stays in global memory (re-read by every step's Pkp1 tiles), R is staged once
     if (tid == 0) sing = 0;
-    for (int e = tid; e < mx * mx; e += RIC_THREADS) P[e] = a.Q[e];       // Pk = Q                                  lqr.jl:147
-    for (int e = tid; e < mu * mu; e += RIC_THREADS) Rl[e] = a.R[e];
+    for (int e = tid; e < mx * mx; e += RIC_THREADS) P[e] = Qp[e];        // Pk = Q                                  lqr.jl:147
+    {
+        const double* Rp = ric_R_of(a, prob);
+        for (int e = tid; e < mu * mu; e += RIC_THREADS) Rl[e] = Rp[e];
+    }
     __syncthreads();
     const int t16m = (mx + 15) >> 4, t16n = (na + 15) >> 4;
     int col, tlo, thi;                   // this wavefront's column block of [A'|D] and its share of the row tiles (ric_wave_tiles)
@@ -1064,13 +1077,13 @@ __global__ __launch_bounds__(RIC_THREADS) void riccati_resident_kernel(RicGrid a
                     double qv[4];                     // Q of the tile's outputs, fetched BEFORE the MFMAs: its L2 round trip hides under them
                     if (BF == 0) {
 #pragma unroll
-                        for (int r = 0; r < 4; r++) { const int i = i0 + lk + 4 * r; qv[r] = a.Q[(size_t)(i < mx ? i : mx - 1) * mx + jc]; }
+                        for (int r = 0; r < 4; r++) { const int i = i0 + lk + 4 * r; qv[r] = Qp[(size_t)(i < mx ? i : mx - 1) * mx + jc]; }
                     }
                     v4d acc = {0.0, 0.0, 0.0, 0.0};
                     if (BF > 0) {                     // (measured-error mode: Q is fetched behind the tile -- the split fragments leave no registers to hold it)
                         acc = ric_tile_bf16<BF, NGF, true>(fsplit, pb, 4 * na);
 #pragma unroll
-                        for (int r = 0; r < 4; r++) { const int i = i0 + 4 * lk + r; qv[r] = a.Q[(size_t)(i < mx ? i : mx - 1) * mx + jc]; }
+                        for (int r = 0; r < 4; r++) { const int i = i0 + 4 * lk + r; qv[r] = Qp[(size_t)(i < mx ? i : mx - 1) * mx + jc]; }
                     } else {
                         // Q + Kuk'*(R*Kuk) + Abar'*(Pk*Abar) in ONE accumulation chain: Q is the initial accumulator, the rank-mu term
                         // ceil(mu / 4) more k-groups (A = Ku[q][i], B = (R Ku)[q][j])
@@ -1119,7 +1132,7 @@ __global__ __launch_bounds__(RIC_THREADS) void riccati_resident_kernel(RicGrid a
                     for (int r = 0; r < 4; r++) {
                         const int i = i0 + lk + 4 * r;
                         if (i < mx) {
-                            double v = a.Q[(size_t)i * mx + j] + acc[r];
+                            double v = Qp[(size_t)i * mx + j] + acc[r];
                             for (int q = 0; q < mu; q++) v += Ku[q * mx + i] * KRK[q * mx + j];
                             const double d = P[i * mx + j] - v;
                             nacc += d * d;
@@ -1273,7 +1286,7 @@ hipError_t launch_riccati(const RicArgs& a, hipStream_t stream) {
     (void)ric_lay_out(g, a, a.work);
     g.tol = a.tol; g.bf16_terms = a.bf16_terms; g.keep_last = a.keep_last; g.kpad = a.kpad;
     g.p_rows = a.p_rows;
-    g.A = a.A; g.Bu = a.Bu; g.Bl = a.Bl; g.G = a.G; g.Q = a.Q; g.R = a.R; g.K = a.K; g.kbreak = a.kbreak; g.status = a.status; g.stop = a.stop;
+    g.A = a.A; g.Bu = a.Bu; g.Bl = a.Bl; g.G = a.G; g.Q = a.Q; g.R = a.R; g.q_stride = a.q_stride; g.r_stride = a.r_stride; g.K = a.K; g.kbreak = a.kbreak; g.status = a.status; g.stop = a.stop;
     const size_t np = a.nprob, na = g.na, mu = a.mu, ml = a.ml;
     hipError_t e = hipMemsetAsync(a.stop, 0, np * sizeof(int), stream);
     if (e == hipSuccess) e = hipMemsetAsync(a.status, 0, np * sizeof(int), stream);

@@ -5,6 +5,7 @@ meaning; the arithmetic (linearsystem, dlqr, simulate!) runs in HIP through the 
     LQR(A, Bu, Bλ, G, Q, R, horizon, eqcids, xd, vd, qd, ωd, Fτd, Δt)              src/control/lqr.jl:17-47
     PlantLQR(mechanism, plants, bodyids, eqcids, Q, R, horizon, zd; Fτd)           the first of these once per plant of a PlantBatch, in one call
     PlantTrackingLQR(mechanism, plants, storage, Fτ, eqcids, Q, R; fric, noise_*)   TrackingLQR (below) once per plant / trajectory, in one call
+    LQRSweep(mechanism, bodyids, eqcids, Qs, Rs, horizon, zd; Fτd, plants)          the first of these once per weight candidate (Q_k, R_k), in one call
     TrackingLQR(mechanism, storage, Fτ, eqcids, Q, R)                                src/control/lqr_tracking.jl:17-43
     simulate!(mechanism, tend | storage, controller; record)                         e.g. examples/lqr_cartpole.jl:44
     Storage{T}(steps, Nb)                                                            examples/trackingLQR_triple_cartpole.jl:50-51
@@ -257,6 +258,97 @@ class PlantLQR(Controller):
 
     def gains(self, i):
         """K[k][j] of plant i's table, [nK][mu][12 nb] in the mechanism's body order, read back from the device (cclqr_ctrl_get_gains)"""
+        return _capi.ctrl_gains(_device_mech(self.mechanism), self._handle, i)
+
+    def close(self):
+        self._handle.close()
+
+
+class LQRSweep(Controller):
+    """One LQR per weight candidate, designed in one call: for every k, LQR(mechanism, bodyids, eqcids, Qs[k], Rs[k], horizon; xd, vd, qd, ωd, Fτd) (lqr.jl:49-66) --
+    one batched linearsystem (lqr.jl:63) and one batched dlqr (lqr.jl:141-184) in which problem k reads its own weights, the gains never leaving the device
+    (cclqr_ctrl_create_lqr_batch_weights).  The tuning study: simulate(mech, steps, sweep, z0=start replicated, record=False, score=Score(one Q, R)) ranks the
+    candidates under a common yardstick in one rollout launch and one score pass.
+
+    Qs: a sequence of candidates, each what LQR takes as Q (nb 12 x 12 blocks in the order of bodyids); Rs: a sequence of candidates, each mu 1 x 1 blocks in the
+    order of eqcids.  Either may hold ONE candidate, which is then shared; n = the longer length.  horizon as for LQR (math.inf = LQR{T,Inf}); every candidate
+    is scaled by Δt (lqr.jl:18-19).
+    zd [nb][13] (one setpoint for every candidate) or [n][nb][13], mechanism body order; Fτd [mu] or [n][mu] (default 0).
+    plants: a PlantBatch -- candidate k is designed on plant first_plant + k (default plants.first_index), as PlantLQR designs table k.
+    n, kbreak [n], converged [n], gains(i), close().
+    simulate(mech, steps, sweep, z0=, first_instance=): instance i runs under table first_instance + i."""
+
+    def __init__(self, mechanism, bodyids, eqcids, Qs, Rs, horizon, zd, Fτd=None, plants=None, first_plant=None, tol=1e-5, controlfunction=None):
+        if controlfunction is not None:
+            raise ValueError("LQRSweep carries no controlfunction: its gains stay on the device (one LQR per candidate with a closure: build an LQR per candidate)")
+        if not isinstance(mechanism, Mechanism):
+            raise TypeError("LQRSweep(mechanism, bodyids, eqcids, Qs, Rs, horizon, zd; ...)")
+        if plants is not None and plants.mechanism is not mechanism:
+            raise ValueError("the PlantBatch was made for another mechanism")
+        nb, mu = len(mechanism.bodies), len(eqcids)
+        Qs, Rs = list(Qs), list(Rs)
+        n = max(len(Qs), len(Rs))
+        if n < 1 or len(Qs) not in (1, n) or len(Rs) not in (1, n):
+            raise ValueError("Qs and Rs must hold one candidate (shared) or the same number of candidates each (got %d and %d)" % (len(Qs), len(Rs)))
+        assert len(bodyids) == nb, "Missmatched length for bodies"                                                        # lqr.jl:59
+        for Q in Qs:
+            assert len(Q) == nb, "Missmatched length for bodies"                                                          # lqr.jl:59
+        for R in Rs:
+            assert len(R) == mu, "Missmatched length for constraints"                                                     # lqr.jl:60
+        inv = _body_order(bodyids, nb)
+        zd = np.ascontiguousarray(zd, dtype=np.float64)
+        if zd.shape == (nb, 13):
+            zd = np.ascontiguousarray(np.broadcast_to(zd, (n, nb, 13)))
+        if zd.shape != (n, nb, 13):
+            raise ValueError("zd must be [nb][13] = [%d][13] (one setpoint for every candidate) or [n][nb][13] = [%d][%d][13] (got %s)" % (nb, n, nb, zd.shape))
+        Fd = np.zeros((n, mu)) if Fτd is None else np.ascontiguousarray(Fτd, dtype=np.float64)
+        if Fd.shape == (mu,):
+            Fd = np.ascontiguousarray(np.broadcast_to(Fd, (n, mu)))
+        if Fd.shape != (n, mu):
+            raise ValueError("Fτd must be [mu] = [%d] or [n][mu] = [%d][%d] (got %s)" % (mu, n, mu, Fd.shape))
+        self.first_plant = (0 if plants is None else plants.first_index) if first_plant is None else int(first_plant)
+        if plants is not None:
+            plants.rows_for(self.first_plant, n)      # every candidate must find its plant
+        # the head of the inner constructor (lqr.jl:18-27) per candidate: Δt scaling, the blocks permuted to the mechanism's body order, math.inf -> LQR{T,Inf}
+        Qm, Rm, N, Ntemp = [], [], None, None
+        for k in range(n):
+            Q, R = Qs[k if len(Qs) > 1 else 0], Rs[k if len(Rs) > 1 else 0]
+            Qb = [np.asarray(Q[i], dtype=np.float64) for i in inv]
+            Rb = [np.asarray(r, dtype=np.float64).reshape(1, 1) for r in R]
+            if any(q.shape != (12, 12) for q in Qb):
+                raise ValueError("every Q block must be 12 x 12 (candidate %d)" % k)
+            q, r, N, Ntemp = _weights_and_horizon(Qb, Rb, horizon, mechanism.Δt)
+            Qm.append(q)
+            Rm.append(r)
+        self.Q, self.R = np.stack(Qm), np.stack(Rm)      # [n][12 nb][12 nb], [n][mu][mu]: scaled, mechanism body order
+        self.mechanism, self.plants, self.n = mechanism, plants, n
+        self.eqcids = [int(e) for e in eqcids]
+        self.ctrl_joints = [mechanism.joint_index(e) for e in self.eqcids]
+        self.controlfunction = None
+        self.zd, self.Fd = zd, Fd
+        self.N = 0 if N == math.inf else N
+        self.horizon_steps, self.NK = N, 12 * nb
+        dev = _device_mech(mechanism)
+        self._handle = _capi.BatchLqrHandle(dev, zd, self.ctrl_joints, self.Q, self.R, Ntemp, Fd=Fd, tol=tol, infinite_horizon=N == math.inf,
+                                            plants=None if plants is None else plants.handle(dev), first_plant=self.first_plant, n_weights=n)
+        self.kbreak = self._handle.kbreak
+        # LQR{T,Inf} (lqr.jl:40-42): converged when Ku[1] == Ku[2], i.e. when the recursion met its tolerance and back-filled the rest (kbreak > 1)
+        self.converged = np.ones(n, dtype=bool) if N < math.inf else ((self.kbreak > 1) | (Ntemp < 3))
+        if not self.converged.all():
+            print("[ Info: Riccati recursion did not converge.")      # lqr.jl:41
+
+    def _ctrl_handle(self, dev, fric=None, noise_scale=0.0, noise_seed=None):
+        if fric is not None or noise_scale or noise_seed is not None:
+            raise ValueError("LQRSweep carries neither joint friction nor noise: the batched constructor builds the plain LQR law")
+        if self.first_plant != 0:
+            raise ValueError("a rollout reads controller table and plant by the global instance index: an LQRSweep that is rolled out starts at plant 0 "
+                             "(this one at plant %d)" % self.first_plant)
+        if self._handle.mech is not dev or not self._handle.ptr:
+            raise ValueError("the LQRSweep was designed on another device handle of the mechanism")
+        return _BorrowedCtrl(self._handle)
+
+    def gains(self, i):
+        """K[k][j] of candidate i's table, [nK][mu][12 nb] in the mechanism's body order, read back from the device (cclqr_ctrl_get_gains)"""
         return _capi.ctrl_gains(_device_mech(self.mechanism), self._handle, i)
 
     def close(self):

@@ -42,7 +42,9 @@ extern "C" {
  * Still 202 (additive, no struct changed): one TrackingLQR per plant or trajectory -- cclqr_ctrl_create_tracking_batch_plants -- and the gain inspector
  * cclqr_ctrl_get_gains; looked up the same way.
  * Still 202 (additive, no struct changed): scoring a rollout on the device -- the opaque cclqr_score with cclqr_score_create / cclqr_score_destroy, and cclqr_rollout_score;
- * looked up the same way. */
+ * looked up the same way.
+ * Still 202 (additive, no struct changed): one (Q, R) per problem / controller table -- cclqr_riccati_weights and cclqr_ctrl_create_lqr_batch_weights; looked up the
+ * same way.  With n_weights = 1 they ARE cclqr_riccati_ex and cclqr_ctrl_create_lqr_batch_plants (which call them). */
 #define CCLQR_ABI_VERSION 202
 
 #define CCLQR_REVOLUTE 0      /* EqualityConstraint(Revolute(a, b, axis; p1, p2, qoffset)),  examples/lqr_cartpole.jl:26 */
@@ -196,6 +198,17 @@ int cclqr_riccati_ex(int32_t nprob, int32_t mx, int32_t mu, int32_t ml, const do
 int cclqr_riccati_tracking_ex(const cclqr_mech *m, int32_t mu, const int32_t *ctrl_joint, const double *zd, const double *Fd, const double *Q,
                               const double *R, int32_t N, double tol, double *K, int32_t *kbreak, const cclqr_riccati_opts *opts);
 
+/* cclqr_riccati_ex with one pair of weights per problem -- dlqr(A_p, Bu_p, Bλ_p, G_p, Q_p, R_p, N) (src/control/lqr.jl:141-184) for every p in one launch: the tuning
+ * study that tries n_weights weightings of one model (A replicated) or of n_weights models.  Q [n_weights][mx][mx], R [n_weights][mu][mu], host pointers, used as
+ * written (the Δt scaling of lqr.jl:18-19 is the caller's).  n_weights is 1 (one pair shared by all problems: exactly cclqr_riccati_ex) or nprob; any other value
+ * is CCLQR_EINVAL before anything is allocated or launched, K untouched.  The kernels, the launch shape and the arithmetic are those of the shared-weights call --
+ * only the address problem p reads its weights from differs, so problem p's gains are bitwise those of cclqr_riccati_ex on the same nprob models with (Q_p, R_p)
+ * shared.  The kernels that assume a symmetric Pk run only when EVERY problem's Q and R are exactly symmetric.  K, kbreak, tol, opts (path, bf16_terms,
+ * keep_last) and the error codes as cclqr_riccati_ex. */
+int cclqr_riccati_weights(int32_t nprob, int32_t mx, int32_t mu, int32_t ml, const double *A, const double *Bu, const double *Bl, const double *G,
+                          int32_t n_weights, const double *Q, const double *R, int32_t N, double tol, double *K, int32_t *kbreak,
+                          const cclqr_riccati_opts *opts);
+
 /* Device workspaces of the host-pointer entry points (cclqr_linearize, cclqr_riccati*, cclqr_rollout) are cached per calling thread, on
  * the device that thread was on when they were allocated, and reused by the next call; after cclqr_set_device to another GPU the next
  * call releases them there and starts a cache on the new device.  This returns them to the driver (they are re-allocated on demand);
@@ -336,6 +349,17 @@ int cclqr_linearize_plants(const cclqr_mech *m, const cclqr_plants *plants, int6
 int cclqr_ctrl_create_lqr_batch_plants(const cclqr_mech *m, const cclqr_plants *plants, int64_t first_plant, int32_t n_ctrl, const double *zd, int32_t mu,
                                        const int32_t *ctrl_joint, const double *Fd, const double *Q, const double *R, int32_t N, int32_t infinite_horizon,
                                        double tol, int32_t *kbreak, cclqr_ctrl **out);
+
+/* cclqr_ctrl_create_lqr_batch_plants with one pair of weights per controller table -- for every k, LQR(mechanism_k, bodyids, eqcids, Q_k, R_k, horizon; ...)
+ * (src/control/lqr.jl:49-66): the last batch dimension of that constructor.  Q [n_weights][12 nb][12 nb], R [n_weights][mu][mu]: host pointers, block-diagonal in
+ * the caller's body / constraint order and already Δt-scaled (lqr.jl:18-19), used as written.  n_weights is 1 (exactly cclqr_ctrl_create_lqr_batch_plants) or n_ctrl;
+ * any other value is CCLQR_EINVAL before anything is allocated or launched.  Table k's gains are bitwise those of the shared-weights call on the same n_ctrl
+ * setpoints (and plants) with (Q_k, R_k).  kbreak, infinite_horizon, the per-table zero pad, plants == NULL, the error codes and the refusals of
+ * cclqr_linearize_plants as there.  Closed-loop mechanisms: CCLQR_EUNSUPPORTED.  A rollout reads table first_instance + i for instance i, so n_weights candidates
+ * from one start state are one launch with that state replicated; cclqr_rollout_score then ranks them under ONE set of score weights, the common yardstick. */
+int cclqr_ctrl_create_lqr_batch_weights(const cclqr_mech *m, const cclqr_plants *plants, int64_t first_plant, int32_t n_ctrl, const double *zd, int32_t mu,
+                                        const int32_t *ctrl_joint, const double *Fd, int32_t n_weights, const double *Q, const double *R, int32_t N,
+                                        int32_t infinite_horizon, double tol, int32_t *kbreak, cclqr_ctrl **out);
 
 /* One TrackingLQR per plant and / or per reference trajectory, in one call -- for every k, TrackingLQR(mechanism_k, storage_k, Fτ_k, eqcids, Q, R)
  * (src/control/lqr_tracking.jl:17-43): linearsystem at the knots 1 .. N-1 of trajectory k (lqr_tracking.jl:88) and the recursion of lqr_tracking.jl:73-122 with its own

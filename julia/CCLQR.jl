@@ -236,6 +236,21 @@ function dlqr(A, Bu, Bλ, G, Q, R, N::Integer; tol = 1e-5)
     Ku, Int(kb[])
 end
 
+"dlqr(A_p, Bu_p, Bλ_p, G_p, Q_p, R_p, N) (lqr.jl:141-184) for every p in one launch (cclqr_riccati_weights): vectors of matrices, one model per problem; Qs and Rs
+ hold ONE pair of Δt-scaled weights (shared) or one pair per problem -- any other count is refused by the library.  Returns (Ku[p][k][i], kbreak[p])."
+function dlqr_weights(As::Vector, Bus::Vector, Bλs::Vector, Gs::Vector, Qs::Vector, Rs::Vector, N::Integer; tol = 1e-5)
+    np = length(As); mx, mu, ml = size(As[1], 1), size(Bus[1], 2), size(Bλs[1], 2)
+    length(Qs) == length(Rs) || throw(AssertionError("Qs and Rs must hold the same number of weight pairs"))
+    rowmajor(Ms) = reduce(vcat, [vec(permutedims(Matrix{Float64}(M))) for M in Ms]; init = Float64[])
+    K = zeros(mx * mu * max(N - 1, 0) * np); kb = zeros(Int32, np)
+    check(ccall((:cclqr_riccati_weights, lib), Cint,
+                (Int32, Int32, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}, Int32, Float64,
+                 Ptr{Float64}, Ptr{Int32}, Ptr{Cvoid}),
+                np, mx, mu, ml, rowmajor(As), rowmajor(Bus), rowmajor(Bλs), rowmajor(Gs), Int32(length(Qs)), rowmajor(Qs), rowmajor(Rs), N, tol, K, kb, C_NULL))
+    K4 = reshape(K, mx, mu, max(N - 1, 0), np)                       # C layout [np][N-1][mu][mx]
+    [[[reshape(K4[:, i, k, p], 1, mx) for i = 1:mu] for k = 1:N-1] for p = 1:np], Int.(kb)
+end
+
 "dlqr(mechanism, xd, vd, qd, ωd, Fτd, eqcids, Q, R, N) replacement (lqr_tracking.jl:73-122): zd is 13 x Nb x N, Fd is mu x N."
 function dlqr_tracking(h::MechHandle, zd::Array{Float64,3}, Fd::Matrix{Float64}, ctrl::Vector{Int32}, Q, R, N::Integer; tol = 1e-5)
     mx, mu = 12h.nb, length(ctrl)
@@ -351,6 +366,21 @@ function lqr_batch_plants(h::MechHandle, p::PlantsHandle, n::Int, zd::Array{Floa
                 (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int32, Ptr{Float64}, Int32, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int32, Int32, Float64, Ptr{Int32},
                  Ref{Ptr{Cvoid}}),
                 h.ptr, p.ptr, first_plant, Int32(n), zd, Int32(length(ctrl_joint)), ctrl_joint, fd, Q, R, Int32(N), Int32(infinite_horizon ? 1 : 0), tol, kb, out))
+    return out[], kb
+end
+
+"One LQR per weight candidate, built and kept on the device (cclqr_ctrl_create_lqr_batch_weights): table k is LQR(mechanism, bodyids, eqcids, Q_k, R_k, horizon; ...)
+ (lqr.jl:49-66) at setpoint k (zd 13 x Nb x n), on plant first_plant + k of `p` (`nothing`: the mechanism's own plant).  Q holds n_weights row-major 12Nb x 12Nb
+ matrices one behind the other, R n_weights mu x mu ones, Δt-scaled (lqr.jl:18-19); n_weights is 1 or n, anything else is refused by the library."
+function lqr_batch_weights(h::MechHandle, p::Union{PlantsHandle,Nothing}, n::Int, zd::Array{Float64}, ctrl_joint::Vector{Int32}, n_weights::Int, Q::Vector{Float64},
+                           R::Vector{Float64}, N::Int; Fd = nothing, first_plant = 0, tol = 1e-5, infinite_horizon = false)
+    out = Ref{Ptr{Cvoid}}(C_NULL); kb = zeros(Int32, n)
+    fd = Fd === nothing ? Ptr{Float64}(C_NULL) : pointer(Fd)
+    GC.@preserve Fd check(ccall((:cclqr_ctrl_create_lqr_batch_weights, lib), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int32, Ptr{Float64}, Int32, Ptr{Int32}, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}, Int32, Int32, Float64, Ptr{Int32},
+                 Ref{Ptr{Cvoid}}),
+                h.ptr, p === nothing ? C_NULL : p.ptr, first_plant, Int32(n), zd, Int32(length(ctrl_joint)), ctrl_joint, fd, Int32(n_weights), Q, R, Int32(N),
+                Int32(infinite_horizon ? 1 : 0), tol, kb, out))
     return out[], kb
 end
 
