@@ -3,10 +3,10 @@ one-LQR-per-plant tests (cclqr_linearize_plants, cclqr_ctrl_create_lqr_batch_pla
 import ctypes as C
 import json
 import os
-import subprocess
 
 import numpy as np
 
+from build_common import host_library
 from plants_common import ROOT, TREE5, mechanism_of, random_plants
 
 N_PLANTS, HORIZON = 6, 40          # plants per case, knots N of the recursion (N - 1 = 39 recorded steps)
@@ -94,13 +94,7 @@ def oracle_gains(orc, c):
 
 def emu_lin_plants():
     """tests/emu/emu_lin_plants.cpp, compiled for the host the way plants_common.emu_plants compiles its source"""
-    d = os.path.join(ROOT, "tests", "emu")
-    so, src = os.path.join(d, "libemu_lin_plants.so"), os.path.join(d, "emu_lin_plants.cpp")
-    csrc = os.path.join(ROOT, "constrainedcontrol.jl_amd", "csrc")
-    deps = [src, os.path.join(d, "emu_rollout.cpp")] + [os.path.join(csrc, h) for h in ("cclqr_dev.h", "cclqr_lin_dev.h", "cclqr_tables.h", "cclqr_internal.h")]
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(f) for f in deps):
-        subprocess.check_call(["/opt/rocm/bin/hipcc", "-O2", "-std=c++17", "-fPIC", "-ffp-contract=off", "--offload-arch=gfx950", "-shared", "-o", so, src])
-    return C.CDLL(so)
+    return host_library("libemu_lin_plants.so", ["emu/emu_lin_plants.cpp"])
 
 
 def emu_linearize_on(lib, fn, orc, t, z, cj, Fd, records=None):

@@ -4,10 +4,10 @@ per session and never modified."""
 import ctypes as C
 import json
 import os
-import subprocess
 
 import numpy as np
 
+from build_common import host_library
 from plant_lqr_common import _rel, slider_mechanism
 from plants_common import ROOT, TREE5, mechanism_of, random_plants
 
@@ -94,13 +94,7 @@ def oracle_nominal(orc, c):
 
 def emu_tracking_plan():
     """tests/emu/emu_tracking_plan.cpp, compiled for the host the way plants_common.emu_plants compiles its source"""
-    d = os.path.join(ROOT, "tests", "emu")
-    so, src = os.path.join(d, "libemu_tracking_plan.so"), os.path.join(d, "emu_tracking_plan.cpp")
-    csrc = os.path.join(ROOT, "constrainedcontrol.jl_amd", "csrc")
-    deps = [src] + [os.path.join(csrc, h) for h in ("cclqr_dev.h", "cclqr_internal.h")]
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(f) for f in deps):
-        subprocess.check_call(["/opt/rocm/bin/hipcc", "-O2", "-std=c++17", "-fPIC", "-ffp-contract=off", "--offload-arch=gfx950", "-shared", "-o", so, src])
-    lib = C.CDLL(so)
+    lib = host_library("libemu_tracking_plan.so", ["emu/emu_tracking_plan.cpp"])
     for f in ("emu_tracking_default_budget", "emu_tracking_max_chunk", "emu_tracking_problem_bytes", "emu_tracking_chunk_problems", "emu_tracking_chunk_count"):
         getattr(lib, f).restype = C.c_longlong
     lib.emu_tracking_problem_bytes.argtypes = [C.c_int] * 4 + [C.c_longlong]

@@ -1,9 +1,10 @@
 """Shared by tests/test_plants_host.py and tests/test_gpu_plants.py: the mechanisms, plant sets and starts of the per-instance-plant tests."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
+
+from build_common import host_library
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -71,10 +72,4 @@ def patched_copy(mech, tables):
 
 def emu_plants():
     """tests/emu/emu_plants.cpp, compiled for the host the way conftest.emu compiles the other emulation sources"""
-    d = os.path.join(ROOT, "tests", "emu")
-    so, src = os.path.join(d, "libemu_plants.so"), os.path.join(d, "emu_plants.cpp")
-    csrc = os.path.join(ROOT, "constrainedcontrol.jl_amd", "csrc")
-    deps = [src] + [os.path.join(csrc, h) for h in ("cclqr_dev.h", "cclqr_chain.h", "cclqr_tables.h", "cclqr_internal.h")]
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(f) for f in deps):
-        subprocess.check_call(["/opt/rocm/bin/hipcc", "-O2", "-std=c++17", "-fPIC", "-ffp-contract=off", "--offload-arch=gfx950", "-shared", "-o", so, src])
-    return C.CDLL(so)
+    return host_library("libemu_plants.so", ["emu/emu_plants.cpp"])

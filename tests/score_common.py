@@ -1,12 +1,11 @@
 """Shared by tests/test_score_host.py and tests/test_gpu_score.py: the definition of cclqr_rollout_score restated in numpy (float64, everything in the
 caller's body order), the tolerance that goes with it, synthetic slabs and the host emulation of the kernel's row functions."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from build_common import host_library
+
 RTOL = 1e-10      # |got - ref| <= RTOL * A, A = the reference's sum with every product replaced by its magnitude
 
 
@@ -126,13 +125,7 @@ def chain_tables(cclqr, nb):
 
 def emu_score():
     """tests/emu/emu_score.cpp, compiled for the host the way plants_common.emu_plants compiles its source"""
-    d = os.path.join(ROOT, "tests", "emu")
-    so, src = os.path.join(d, "libemu_score.so"), os.path.join(d, "emu_score.cpp")
-    csrc = os.path.join(ROOT, "constrainedcontrol.jl_amd", "csrc")
-    deps = [src] + [os.path.join(csrc, h) for h in ("cclqr_dev.h", "cclqr_chain.h", "cclqr_score.h")]
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(f) for f in deps):
-        subprocess.check_call(["/opt/rocm/bin/hipcc", "-O2", "-std=c++17", "-fPIC", "-ffp-contract=off", "--offload-arch=gfx950", "-shared", "-o", so, src])
-    return C.CDLL(so)
+    return host_library("libemu_score.so", ["emu/emu_score.cpp"])
 
 
 def emu_score_run(lib, case, perm, settle_tol, k0=1, first_instance=0, init=None):

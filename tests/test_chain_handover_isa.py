@@ -3,47 +3,34 @@ workgroup of ONE wavefront, for which a barrier already lowered to a bare `s_wai
 first read.  The hand-over is a wavefront-scope fence: no instruction, the reads queue behind the stores.  What this file checks in the ISA (CPU suite: one
 gfx950 cross-compile of csrc/rollout_chain.hip, shared by the tests): the static count of full drains fell, no barrier came in, the headline kernel kept
 its registers.  The counts "before" are the parent's, measured with this toolchain; the counts "today" are recorded in DESIGN 8, round 12."""
-import os
 import re
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-KERNEL = "_ZN5cclqr20rollout_chain_kernelILi%dELi%dELi%dELb%dELi%dELi%dEEEvNS_11RolloutArgsE"
-HEADLINE = KERNEL % (32, 17, 0, 0, 1, 32)
+from build_common import HEADLINE, chain_kernel, device_asm
+
 # instantiation -> (full drains before the hand-over, full drains today)
 DRAINS = {
     HEADLINE: (81, 72),
-    KERNEL % (16, 8, 0, 0, 1, 16): (60, 54),       # Sawyer cfg4, bench.py --links 7
-    KERNEL % (8, 4, 0, 0, 3, 2): (68, 61),         # cartpole cfg2, bench.py --links 1
+    chain_kernel(16, 8, 0, 0, 1, 16): (60, 54),       # Sawyer cfg4, bench.py --links 7
+    chain_kernel(8, 4, 0, 0, 3, 2): (68, 61),         # cartpole cfg2, bench.py --links 1
 }
 
 
 @pytest.fixture(scope="module")
-def asm_lines(tmp_path_factory):
-    asm = str(tmp_path_factory.mktemp("isa") / "rollout_chain.s")
-    src = os.path.join(ROOT, "constrainedcontrol.jl_amd", "csrc", "rollout_chain.hip")
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-ffp-contract=fast", "--offload-arch=gfx950", "-S", "--cuda-device-only", "-o", asm, src],
-                          stderr=subprocess.DEVNULL)
-    return open(asm).read().splitlines()
+def asm_lines():
+    """csrc/rollout_chain.hip cross-compiled for gfx950 (build_common.device_asm: once per test process)"""
+    return device_asm("rollout_chain.hip")
 
 
-def _kernel(lines, name):
+def _kernel(asm, name):
     """(instruction lines of the kernel, the resource comments behind it)"""
-    start = [i for i, l in enumerate(lines) if l.startswith(name + ":")][0]
-    end = [i for i in range(start, len(lines)) if "s_endpgm" in lines[i]][0]
-    body = [l for l in (x.strip() for x in lines[start:end]) if l and not l.startswith((";", ".")) and not l.endswith(":")]
-    tail = []
-    for l in lines[end:]:
-        if l.startswith("_ZN5cclqr"):
-            break
-        tail.append(l)
-    return body, tail
+    k = asm.kernel(name)
+    return k.body, k.tail
 
 
-def _chain_kernels(lines):
-    return [m.group(1) for l in lines for m in [re.match(r"(_ZN5cclqr20rollout_chain_kernel\w+):", l)] if m]
+def _chain_kernels(asm):
+    return asm.kernel_names("_ZN5cclqr20rollout_chain_kernel")
 
 
 def _full_drains(body):

@@ -2,29 +2,20 @@
 csrc/rollout_chain.hip, shared by the tests of this file).  Until the fold the kernel carried THREE inlined copies of chain_eval<G, true> (residual,
 Jacobians, Schur rows: about 1.8 k instructions each): in front of the loop, as the full-step trial, and at the bottom of the loop body.  The first and
 the third did the same job and are one call now."""
-import os
-import re
-import subprocess
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADLINE = "_ZN5cclqr20rollout_chain_kernelILi32ELi17ELi0ELb0ELi1ELi32EEEvNS_11RolloutArgsE"
+from build_common import HEADLINE, device_asm
+
 
 
 @pytest.fixture(scope="module")
-def asm_lines(tmp_path_factory):
-    asm = str(tmp_path_factory.mktemp("isa") / "rollout_chain.s")
-    src = os.path.join(ROOT, "constrainedcontrol.jl_amd", "csrc", "rollout_chain.hip")
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-ffp-contract=fast", "--offload-arch=gfx950", "-S", "--cuda-device-only", "-o", asm, src],
-                          stderr=subprocess.DEVNULL)
-    return open(asm).read().splitlines()
+def asm_lines():
+    """csrc/rollout_chain.hip cross-compiled for gfx950 (build_common.device_asm: once per test process)"""
+    return device_asm("rollout_chain.hip")
 
 
-def _ops(lines, name):
-    start = [i for i, l in enumerate(lines) if l.startswith(name + ":")][0]
-    end = [i for i in range(start, len(lines)) if "s_endpgm" in lines[i]][0]
-    return [l.split()[0] for l in (x.strip() for x in lines[start:end]) if l and not l.startswith((";", ".")) and not l.endswith(":")]
+def _ops(asm, name):
+    return asm.kernel(name).ops
 
 
 def test_headline_kernel_has_two_copies_of_the_evaluation(asm_lines):
@@ -37,7 +28,7 @@ def test_headline_kernel_has_two_copies_of_the_evaluation(asm_lines):
 def test_no_flat_instruction_in_any_chain_kernel(asm_lines):
     """the single-read accessor of the solve phases (cclqr_chain.h LDS_RD) is a volatile read through a pointer typed to the LDS address space; volatile on a
     generic pointer would make every such read a flat load (address-space test + the memory pipeline).  No chain instantiation has one."""
-    names = [m.group(1) for l in asm_lines for m in [re.match(r"(_ZN5cclqr20rollout_chain_kernel\w+):", l)] if m]
+    names = asm_lines.kernel_names("_ZN5cclqr20rollout_chain_kernel")
     assert names and HEADLINE in names
     for n in names:
         flat = [o for o in _ops(asm_lines, n) if o.startswith("flat_")]

@@ -3,37 +3,30 @@ the one-lane middle solve (ck_tri_mid) are sixty DPP row broadcasts, and the fir
 checks in the ISA (CPU suite: one gfx950 cross-compile of csrc/rollout_chain.hip, shared by the tests): the broadcasts are there, the reads are gone, and the
 8-lane kernels -- one front, which keep ck_tri_mid -- are what they were.  The counts "before" are the parent's, measured with this toolchain; today's are
 recorded in DESIGN 8, round 13."""
-import os
 import re
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-KERNEL = "_ZN5cclqr20rollout_chain_kernelILi%dELi%dELi%dELb%dELi%dELi%dEEEvNS_11RolloutArgsE"
+from build_common import chain_kernel, device_asm
+
 # instantiation -> ds_read_b64 before the change
 READS_BEFORE = {
-    KERNEL % (32, 17, 0, 0, 1, 32): 511,       # the headline
-    KERNEL % (16, 8, 0, 0, 1, 16): 358,        # Sawyer cfg4, bench.py --links 7
+    chain_kernel(32, 17, 0, 0, 1, 32): 511,       # the headline
+    chain_kernel(16, 8, 0, 0, 1, 16): 358,        # Sawyer cfg4, bench.py --links 7
 }
-EIGHT_LANES = KERNEL % (8, 4, 0, 0, 3, 2)      # cartpole cfg2, bench.py --links 1
+EIGHT_LANES = chain_kernel(8, 4, 0, 0, 3, 2)      # cartpole cfg2, bench.py --links 1
 EIGHT_LANES_INSTRUCTIONS = 6600
 
 
 @pytest.fixture(scope="module")
-def asm_lines(tmp_path_factory):
-    asm = str(tmp_path_factory.mktemp("isa") / "rollout_chain.s")
-    src = os.path.join(ROOT, "constrainedcontrol.jl_amd", "csrc", "rollout_chain.hip")
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-ffp-contract=fast", "--offload-arch=gfx950", "-S", "--cuda-device-only", "-o", asm, src],
-                          stderr=subprocess.DEVNULL)
-    return open(asm).read().splitlines()
+def asm_lines():
+    """csrc/rollout_chain.hip cross-compiled for gfx950 (build_common.device_asm: once per test process)"""
+    return device_asm("rollout_chain.hip")
 
 
-def _body(lines, name):
+def _body(asm, name):
     """instruction lines of the kernel"""
-    start = [i for i, l in enumerate(lines) if l.startswith(name + ":")][0]
-    end = [i for i in range(start, len(lines)) if "s_endpgm" in lines[i]][0]
-    return [l for l in (x.strip() for x in lines[start:end]) if l and not l.startswith((";", ".")) and not l.endswith(":")]
+    return asm.kernel(name).body
 
 
 def _broadcasts(body):

@@ -4,13 +4,12 @@ most 17 links) must give the blocks of ck_schur_rows BIT FOR BIT: every sum keep
 lanes, from the same random W and G_k into LDS images poisoned with signalling NaNs; the two images must be the same words everywhere -- so a block that one
 form writes and the other does not, or a word read before it is written, shows.  CPU suite."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from build_common import host_library
+
 # (chains of the forest in link order, links the image is laid out for)
 CASES = {
     "chain17": ([17], 17),                # link 0 without a helper, the leaf on lane 16
@@ -23,11 +22,9 @@ CASES = {
 
 
 @pytest.fixture(scope="module")
-def lib(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("emu_split") / "libemu_schur_split.so")
-    subprocess.check_call(["/opt/rocm/lib/llvm/bin/clang++", "-x", "hip", "--offload-host-only", "-std=c++17", "-O2", "-fPIC", "-shared", "-ffp-contract=off",
-                           "-I/opt/rocm/include", "-o", so, os.path.join(ROOT, "tests", "emu", "emu_schur_split.cpp")], stderr=subprocess.DEVNULL)
-    return C.CDLL(so)
+def lib():
+    return host_library("libemu_schur_split.so", ["emu/emu_schur_split.cpp"], compiler="/opt/rocm/lib/llvm/bin/clang++",
+                        flags=("-x", "hip", "--offload-host-only", "-std=c++17", "-O2", "-fPIC", "-shared", "-ffp-contract=off", "-I/opt/rocm/include"))
 
 
 def _run(lib, chains, nbp, seed, zeros):

@@ -6,19 +6,16 @@ fell, the swaps are there, no ds_bpermute came in, and every kernel that keeps c
 -- is instruction for instruction what it was.  The counts and digests "before" are the parent's, measured with this toolchain; today's counts are
 recorded in DESIGN 8, round 14."""
 import hashlib
-import os
 import re
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-KERNEL = "_ZN5cclqr20rollout_chain_kernelILi%dELi%dELi%dELb%dELi%dELi%dEEEvNS_11RolloutArgsE"
-HEADLINE = KERNEL % (32, 17, 0, 0, 1, 32)
+from build_common import HEADLINE, chain_kernel, device_asm
+
 # instantiation -> (ds_read_b64, LDS store instructions, ds_bpermute_b32) before the split; two builds of the rows per kernel
 BEFORE = {
     HEADLINE: (457, 217, 67),
-    KERNEL % (32, 16, 0, 0, 1, 32): (454, 217, 67),        # bench.py --links 15: every link has a helper
+    chain_kernel(32, 16, 0, 0, 1, 32): (454, 217, 67),        # bench.py --links 15: every link has a helper
 }
 # (lanes, image links, law, relaxed stop, lanes per link, links per sub-group) -> (instructions, first 16 hex digits of the SHA-1 of the instruction
 # lines, blanks squeezed, the function number taken out of the branch labels) of the parent's kernel
@@ -37,19 +34,14 @@ UNCHANGED = {
 
 
 @pytest.fixture(scope="module")
-def asm_lines(tmp_path_factory):
-    asm = str(tmp_path_factory.mktemp("isa") / "rollout_chain.s")
-    src = os.path.join(ROOT, "constrainedcontrol.jl_amd", "csrc", "rollout_chain.hip")
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-ffp-contract=fast", "--offload-arch=gfx950", "-S", "--cuda-device-only", "-o", asm, src],
-                          stderr=subprocess.DEVNULL)
-    return open(asm).read().splitlines()
+def asm_lines():
+    """csrc/rollout_chain.hip cross-compiled for gfx950 (build_common.device_asm: once per test process)"""
+    return device_asm("rollout_chain.hip")
 
 
-def _body(lines, name):
+def _body(asm, name):
     """instruction lines of the kernel"""
-    start = [i for i, l in enumerate(lines) if l.startswith(name + ":")][0]
-    end = [i for i in range(start, len(lines)) if "s_endpgm" in lines[i]][0]
-    return [l for l in (x.strip() for x in lines[start:end]) if l and not l.startswith((";", ".")) and not l.endswith(":")]
+    return asm.kernel(name).body
 
 
 def _count(body, pattern):
@@ -80,9 +72,10 @@ def test_w_moves_by_row_swaps_not_through_the_lds_crossbar(asm_lines, name):
 
 @pytest.mark.parametrize("key", list(UNCHANGED), ids=["-".join(map(str, k)) for k in UNCHANGED])
 def test_kernels_that_keep_ck_schur_rows_are_the_parents(asm_lines, key):
-    body = _body(asm_lines, KERNEL % key)
+    kernel = asm_lines.kernel(chain_kernel(*key))
+    body = kernel.body
     assert not [l for l in body if l.split()[0].startswith("v_permlane16_swap")]
-    text = "\n".join(re.sub(r"\.LBB\d+_", ".LBB_", re.sub(r"\s+", " ", l)) for l in body)
+    text = kernel.normalised()
     n, digest = UNCHANGED[key]
     assert len(body) == n, len(body)
     assert hashlib.sha1(text.encode()).hexdigest()[:16] == digest

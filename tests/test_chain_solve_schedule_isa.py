@@ -2,32 +2,19 @@
 gfx950 cross-compile of csrc/rollout_chain.hip, shared by the tests of this file).  The solve is a chain of dependent 5 x 5 stages at one wavefront per SIMD:
 thirty reads each behind a scalar branch of its own, on the one lane the whole wavefront waits for, were 1.6 % of the headline's time.
 The sweep step's reads (tri_step) are where the compiler puts them: dealing them to the pivot stages was measured as no gain."""
-import os
 import re
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADLINE = "_ZN5cclqr20rollout_chain_kernelILi32ELi17ELi0ELb0ELi1ELi32EEEvNS_11RolloutArgsE"
+from build_common import HEADLINE, device_asm
+
 
 
 @pytest.fixture(scope="module")
-def kernel(tmp_path_factory):
+def kernel():
     """(lines of the headline kernel's body, the resource comments that follow it)"""
-    asm = str(tmp_path_factory.mktemp("isa") / "rollout_chain.s")
-    src = os.path.join(ROOT, "constrainedcontrol.jl_amd", "csrc", "rollout_chain.hip")
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-ffp-contract=fast", "--offload-arch=gfx950", "-S", "--cuda-device-only", "-o", asm, src],
-                          stderr=subprocess.DEVNULL)
-    lines = open(asm).read().splitlines()
-    start = [i for i, l in enumerate(lines) if l.startswith(HEADLINE + ":")][0]
-    end = [i for i in range(start, len(lines)) if "s_endpgm" in lines[i]][0]
-    tail = []
-    for l in lines[end:]:
-        if l.startswith("_ZN5cclqr"):
-            break
-        tail.append(l)
-    return lines[start:end], tail
+    k = device_asm("rollout_chain.hip").kernel(HEADLINE)
+    return k.raw, k.tail
 
 
 def _is_op(l):

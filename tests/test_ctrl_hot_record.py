@@ -8,27 +8,19 @@
     (tests/emu/emu_ctrl_hot.cpp keeps that indexing), on the hanging 17-body chain, a forest of two chains and the tracking law;
   * the chain plan word decodes to MechDev's chains."""
 import ctypes as C
-import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
+from build_common import device_asm, host_library
 from conftest import hanging_setpoint, long_and_short_chain_forest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "constrainedcontrol.jl_amd", "csrc")
-HIPCC = "/opt/rocm/bin/hipcc"
 FIELDS = ["mu", "nK", "N", "nsp", "K", "zd", "Fd", "K_stride", "zd_stride", "Fd_stride", "has_fric", "has_pid", "noise_on", "noise_scale", "noise_key0"]
 
 
 @pytest.fixture(scope="module")
-def hot(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("emu_hot") / "libemu_hot.so")
-    subprocess.check_call([HIPCC, "-O2", "-std=c++17", "-fPIC", "-ffp-contract=off", "--offload-arch=gfx950", "-shared", "-o", so,
-                           os.path.join(ROOT, "tests", "emu", "emu_ctrl_hot.cpp")], stderr=subprocess.DEVNULL)
-    lib = C.CDLL(so)
+def hot():
+    lib = host_library("libemu_hot.so", ["emu/emu_ctrl_hot.cpp"])
     lib.emu_ctrl_hot_rows.restype = C.c_longlong
     return lib
 
@@ -97,19 +89,14 @@ def test_chain_plan_word_decodes_to_the_chains(cclqr, orc, hot):
         assert sum(lens) == t.nb and all(((int(w) >> 8) & 0xffff) == nchains << 8 for w in words[nchains:])      # lanes past the last chain: length 0
 
 
-def test_chain_kernels_read_their_tables_through_global_loads(tmp_path):
+def test_chain_kernels_read_their_tables_through_global_loads():
     """every rollout_chain_kernel instantiation: no flat memory instruction (the address space of every table is visible to the compiler), the chains
     come out of the plan register, and the controller's record comes through scalar loads"""
-    asm = str(tmp_path / "rollout_chain.s")
-    subprocess.check_call([HIPCC, "-O3", "-std=c++17", "-ffp-contract=fast", "--offload-arch=gfx950", "-S", "--cuda-device-only", "-o", asm,
-                           os.path.join(CSRC, "rollout_chain.hip")], stderr=subprocess.DEVNULL)
-    lines = open(asm).read().splitlines()
-    starts = [i for i, l in enumerate(lines) if re.match(r"_ZN5cclqr20rollout_chain_kernelI\S+:", l)]
+    asm = device_asm("rollout_chain.hip")
+    starts = asm.kernel_names("_ZN5cclqr20rollout_chain_kernelI")
     assert len(starts) == 35, len(starts)
-    for s in starts:
-        name = lines[s].split(":")[0]
-        end = next(i for i in range(s, len(lines)) if "s_endpgm" in lines[i])
-        ops = [x.split()[0] for x in (l.strip() for l in lines[s + 1:end]) if x and not x.startswith((";", ".")) and not x.endswith(":")]
+    for name in starts:
+        ops = asm.kernel(name).ops
         flat = [o for o in ops if o.startswith(("flat_load", "flat_store", "flat_atomic"))]
         assert not flat, (name, flat[:4])
         assert any(o.startswith("v_readlane_b32") for o in ops), name                       # the chain plan

@@ -22,19 +22,17 @@ multipliers and status are bitwise equal between the packed and the spread launc
 the trajectory and the final state match the oracle within the suite's 1e-9 (fp64).  One more case runs the 17-body chain behind the LDS poison of
 tests/gpu/poison_lds.hip.  Every case is a run the kernel is expected to pass."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 import scipy.linalg as sl
 
+from build_common import host_library
 from conftest import hanging_setpoint, long_and_short_chain_forest
 
 TOL = 1e-9
 STEPS = 12
 NINST = 6
-HERE = os.path.dirname(os.path.abspath(__file__))
 SNAN = 0x7FF4000000000001
 
 # bodies, lanes per instance, links of the LDS layout
@@ -164,13 +162,11 @@ def test_forest_of_two_chains(cclqr, orc):
 
 
 @pytest.fixture(scope="module")
-def poison(tmp_path_factory):
+def poison():
     """tests/gpu/poison_lds.hip (test_gpu_lds_poison.py): fills the LDS of every compute unit with a pattern"""
     import torch
     torch.zeros(1, device="cuda")      # torch's HIP runtime first, as every other GPU test has it
-    so = str(tmp_path_factory.mktemp("poison") / "libpoison_lds.so")
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "-O2", "--offload-arch=gfx950", "-shared", "-fPIC", os.path.join(HERE, "gpu", "poison_lds.hip"), "-o", so])
-    lib = C.CDLL(so)
+    lib = host_library("libpoison_lds.so", ["gpu/poison_lds.hip"], flags=("-O2", "--offload-arch=gfx950", "-shared", "-fPIC"))
     lib.poison_lds.argtypes = [C.c_ulonglong, C.c_int, C.c_int]
 
     def run():

@@ -18,17 +18,15 @@ group without an instance).  Each case: trajectory, final state, multipliers and
 launch and carried single-step launches, and between a launch on clean LDS and one on LDS poisoned with signalling NaNs (tests/gpu/poison_lds.hip, as
 tests/test_gpu_lds_poison.py does); trajectory and final state within the suite's 1e-9 of the oracle, which runs once per problem."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 import scipy.linalg as sl
 
+from build_common import host_library
 from conftest import hanging_setpoint
 
 pytestmark = pytest.mark.gpu
-HERE = os.path.dirname(os.path.abspath(__file__))
 TOL = 1e-9
 STEPS = 24
 NINST = 6
@@ -39,12 +37,10 @@ FORESTS = [((9, 7), 16), ((9, 8), 17), ((1, 11), 16), ((16, 1), 17)]
 
 
 @pytest.fixture(scope="module")
-def poison(tmp_path_factory):
+def poison():
     import torch
     torch.zeros(1, device="cuda")      # torch's HIP runtime first (the order every other GPU test has)
-    so = str(tmp_path_factory.mktemp("poison") / "libpoison_lds.so")
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "-O2", "--offload-arch=gfx950", "-shared", "-fPIC", os.path.join(HERE, "gpu", "poison_lds.hip"), "-o", so])
-    lib = C.CDLL(so)
+    lib = host_library("libpoison_lds.so", ["gpu/poison_lds.hip"], flags=("-O2", "--offload-arch=gfx950", "-shared", "-fPIC"))
     lib.poison_lds.argtypes = [C.c_ulonglong, C.c_int, C.c_int]
 
     def run():

@@ -6,25 +6,21 @@ of signalling NaNs (tests/emu).  This is the same statement on the hardware, for
 compute unit with a pattern (a signalling NaN; 1e300, which survives a multiplication by a mask where NaN would also be caught), then the kernel
 runs; outputs must be BITWISE those of a run without poisoning."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+from build_common import host_library
 pytestmark = pytest.mark.gpu
-HERE = os.path.dirname(os.path.abspath(__file__))
 SNAN = 0x7FF4000000000001
 HUGE = int(np.array([1e300]).view(np.uint64)[0])
 
 
 @pytest.fixture(scope="module")
-def poison(tmp_path_factory):
+def poison():
     import torch
     torch.zeros(1, device="cuda")      # torch's HIP runtime first: a library loaded later binds to the runtime already in the process (the order every other GPU test has)
-    so = str(tmp_path_factory.mktemp("poison") / "libpoison_lds.so")
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "-O2", "--offload-arch=gfx950", "-shared", "-fPIC", os.path.join(HERE, "gpu", "poison_lds.hip"), "-o", so])
-    lib = C.CDLL(so)
+    lib = host_library("libpoison_lds.so", ["gpu/poison_lds.hip"], flags=("-O2", "--offload-arch=gfx950", "-shared", "-fPIC"))
     lib.poison_lds.argtypes = [C.c_ulonglong, C.c_int, C.c_int]
 
     lib.peek_lds.argtypes = [C.c_int, C.c_int, C.c_void_p]

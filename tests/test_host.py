@@ -455,32 +455,21 @@ def test_abi_layout_is_what_the_bindings_mirror(cclqr):
     assert "ABI_VERSION = %d" % capi.ABI_VERSION in jl and "cclqr_abi_layout" in jl
 
 
-def _kernel_resources(tmp_path, src_name, match):
-    import subprocess
-    asm = str(tmp_path / (src_name + ".s"))
-    src = os.path.join(ROOT, "constrainedcontrol.jl_amd", "csrc", src_name)
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-ffp-contract=fast", "--offload-arch=gfx950", "-S", "--cuda-device-only",
-                           "-o", asm, src], stderr=subprocess.DEVNULL)
-    txt = open(asm).read()
-    kernels = {}
-    for blk in txt.split("  - .agpr_count:")[1:]:
-        name = re.search(r"\.name:\s+(\S+)", blk).group(1)
-        if match not in name:
-            continue
-        g = lambda key: int(re.search(r"\." + key + r":\s+(\d+)", blk).group(1))
-        kernels[name] = dict(agpr=int(blk.split()[0]), vgpr=g("vgpr_count"), scratch=g("private_segment_fixed_size"),
-                             lds=g("group_segment_fixed_size"), sgpr_spill=g("sgpr_spill_count"), vgpr_spill=g("vgpr_spill_count"))
-    return kernels
+def _kernel_resources(src_name, match):
+    """name -> metadata resources of the kernels of csrc/<src_name> whose name contains `match` (build_common.device_asm: one compile per source)"""
+    from build_common import device_asm
+    asm = device_asm(src_name)
+    return {name: asm.kernel(name).resources for name in asm.kernel_names() if match in name}
 
 
-def test_chain_rollout_kernel_resources(tmp_path):
+def test_chain_rollout_kernel_resources():
     """the register-resident chain kernel (csrc/rollout_chain.hip), every instantiation: (lanes, layout links) in
     {(8, 4), (16, 8), (32, 16), (32, 17), (32, 32), (64, 64)} x control variant {plain LQR, + friction/noise, + PID, + friction/noise with the Philox
     sample generated in the kernel (the step-per-launch form of configs[4], round 5)}.  The plain-LQR instantiations
     -- every BASELINE config but the friction/noise law of config 5 -- must not spill a single scalar register and must not touch
     scratch memory (VERDICT r1 item 2: the kernel must not live in the regime where a spilled pointer or mask can go wrong);
     nor does the friction/noise variant; the PID variant may spill a few scalars (atan2 constants) but no vector register to scratch either."""
-    kernels = _kernel_resources(tmp_path, "rollout_chain.hip", "rollout_chain_kernel")
+    kernels = _kernel_resources("rollout_chain.hip", "rollout_chain_kernel")
     # 7 shapes (lanes, layout links, lanes per link, links per sub-lane group): since round 5 the 1- and 2-link mechanisms give a link three lanes
     # (<8, 4, 3, 2> next to <8, 4, 1, 8> for 3-4 links) x 4 control variants with the exact Newton rule + the 7 plain-law kernels of the measured-error
     # Newton mode (RELAX)
@@ -511,38 +500,32 @@ def test_chain_rollout_kernel_resources(tmp_path):
     assert shapes == {(8, 4, 3, 2), (8, 4, 1, 8), (16, 8, 1, 16), (32, 16, 1, 32), (32, 17, 1, 32), (32, 32, 1, 32), (64, 64, 1, 64)}, shapes
 
 
-def test_headline_kernel_instruction_budget(tmp_path):
+def test_headline_kernel_instruction_budget():
     """ISA-level regressions of the headline kernel rollout_chain_kernel<32, 17, 0, false> that cost time without changing a result (round 3 found
     two by reading the assembly): every DPP shift must be a lone v_mov_b32_dpp with bound_ctrl -- without it the compiler zero-initialises the
     destination first (265 extra v_mov_b32) --, and an LDS operand of a lane-conditional select must not come back as per-element EXEC-masked
     loads.  Bounds = today's counts + a margin; a failure here means: read the block that grew."""
-    import subprocess
-    asm = str(tmp_path / "rollout_chain.s")
-    src = os.path.join(ROOT, "constrainedcontrol.jl_amd", "csrc", "rollout_chain.hip")
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-ffp-contract=fast", "--offload-arch=gfx950", "-S", "--cuda-device-only", "-o", asm, src],
-                          stderr=subprocess.DEVNULL)
-    lines = open(asm).read().splitlines()
-    start = [i for i, l in enumerate(lines) if l.startswith("_ZN5cclqr20rollout_chain_kernelILi32ELi17ELi0ELb0ELi1ELi32EEEvNS_11RolloutArgsE:")][0]
-    end = [i for i in range(start, len(lines)) if "s_endpgm" in lines[i]][0]
-    ops = [l.split()[0] for l in (x.strip() for x in lines[start:end]) if l and not l.startswith((";", ".")) and not l.endswith(":")]
+    from build_common import HEADLINE, device_asm
+    kernel = device_asm("rollout_chain.hip").kernel(HEADLINE)
+    ops = kernel.ops
     count = lambda prefix: sum(o.startswith(prefix) for o in ops)
     assert len(ops) <= 10800, len(ops)                                   # 10 648 today (10 941 before the two fixes)
     assert count("v_mov_b32_e32") <= 200, count("v_mov_b32_e32")         # 152 today (417 with zero-initialised DPP destinations)
-    dpp = [x.strip() for x in lines[start:end] if "v_mov_b32_dpp" in x]
+    dpp = [x.strip() for x in kernel.raw if "v_mov_b32_dpp" in x]
     assert dpp and all("bound_ctrl" in x for x in dpp)
     assert count("s_and_saveexec_b64") + count("s_or_saveexec_b64") <= 135      # 126 today
 
 
-def test_linearize_and_riccati_kernel_resources(tmp_path):
+def test_linearize_and_riccati_kernel_resources():
     """csrc/linearize.hip and csrc/riccati.hip: no scratch memory and no vector-register spill in any kernel; the scalar spills the
     compiler makes today (to VGPR lanes, never to memory) are recorded as upper bounds so that an edit that pushes a kernel further
     into the spilling regime fails here, on the CPU, before it reaches a GPU"""
-    lin = _kernel_resources(tmp_path, "linearize.hip", "linearize_kernel")
+    lin = _kernel_resources("linearize.hip", "linearize_kernel")
     assert len(lin) == 2, sorted(lin)
     for name, k in lin.items():
         assert k["scratch"] == 0 and k["vgpr_spill"] == 0 and k["vgpr"] <= 512 and k["lds"] == 0, (name, k)
         assert k["sgpr_spill"] <= (25 if "ILb1E" in name else 8), (name, k)      # (25 / 8 since the chain masks are 64 bits wide: 64-link chains; 23 / 6 before)
-    ric = _kernel_resources(tmp_path, "riccati.hip", "ric")
+    ric = _kernel_resources("riccati.hip", "ric")
     assert len(ric) >= 24, sorted(ric)
     for name, k in ric.items():
         if "riccati_resident_kernel" in name and not re.search(r"ILi\dELi0ELi0EEEv", name):
@@ -559,11 +542,11 @@ def test_linearize_and_riccati_kernel_resources(tmp_path):
         assert k["sgpr_spill"] <= lim, (name, k)
 
 
-def test_loop_rollout_kernel_resources(tmp_path):
+def test_loop_rollout_kernel_resources():
     """the closed-loop rollout kernel (csrc/rollout_loop.hip; one instantiation per width of the register-resident rows of the dense
     system, 8 .. 64 columns) cross-compiles for gfx950 without scratch memory: the one access into the row that the register file cannot
     index -- the lane's own entry in the pivot column -- is a compare-and-select inside a uniform branch, not an indexed array"""
-    kernels = _kernel_resources(tmp_path, "rollout_loop.hip", "rollout_loop_kernel")
+    kernels = _kernel_resources("rollout_loop.hip", "rollout_loop_kernel")
     assert len(kernels) == 8, sorted(kernels)
     for name, k in kernels.items():
         # two wavefronts per SIMD (eight instances per CU instead of four): 256 registers and a small, bounded spill of the evaluation and
@@ -572,13 +555,13 @@ def test_loop_rollout_kernel_resources(tmp_path):
         assert k["scratch"] <= 384 and k["vgpr"] <= 256 and k["lds"] == 0, (name, k)
 
 
-def test_tree_rollout_kernel_resources(tmp_path):
+def test_tree_rollout_kernel_resources():
     """every instantiation of the register-resident tree kernel (csrc/rollout_treereg.hip; (lanes, layout links) x control variant + the
     measured-error Newton mode) cross-compiles for gfx950 within one wavefront's register file (512 VGPR + AGPR per lane) WITHOUT scratch
     memory -- the child / sibling lists and the schedule records are indexed by compile-time constants only (an index the compiler cannot
     resolve puts them into scratch: 128 bytes in the first cut) -- and without vector-register spills to memory; the plain-LQR and
     friction/noise instantiations spill no scalar register, the PID ones a few (atan2 constants)"""
-    kernels = _kernel_resources(tmp_path, "rollout_treereg.hip", "rollout_treereg_kernel")
+    kernels = _kernel_resources("rollout_treereg.hip", "rollout_treereg_kernel")
     assert len(kernels) == 44, sorted(kernels)          # {(16,4), (16,8), (32,8), (32,10), (32,12), (32,14), (32,16), (32,24), (32,32), (64,48), (64,64)} x 4
     for name, k in kernels.items():
         assert k["vgpr"] <= 512 and k["lds"] == 0, (name, k)      # all LDS is dynamic (one instance image per lane group)

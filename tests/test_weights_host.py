@@ -4,12 +4,12 @@ import ctypes as C
 import math
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import dlqr_reference as ref
+from build_common import host_library
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("cclqr_riccati_weights", "cclqr_ctrl_create_lqr_batch_weights")
@@ -17,13 +17,7 @@ NEW = ("cclqr_riccati_weights", "cclqr_ctrl_create_lqr_batch_weights")
 
 def emu_weights_host():
     """compiled for the host the way capi_host_common.emu_capi_host compiles its source"""
-    d = os.path.join(ROOT, "tests", "emu")
-    so, src = os.path.join(d, "libemu_weights_host.so"), os.path.join(d, "emu_weights_host.cpp")
-    csrc = os.path.join(ROOT, "constrainedcontrol.jl_amd", "csrc")
-    deps = [src] + [os.path.join(csrc, h) for h in ("cclqr_dev.h", "cclqr_internal.h")]
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(f) for f in deps):
-        subprocess.check_call(["/opt/rocm/bin/hipcc", "-O2", "-std=c++17", "-fPIC", "-ffp-contract=off", "--offload-arch=gfx950", "-shared", "-o", so, src])
-    lib = C.CDLL(so)
+    lib = host_library("libemu_weights_host.so", ["emu/emu_weights_host.cpp"])
     lib.emu_ric_p_rows_batch.restype = C.c_int
     lib.emu_ric_p_rows_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_longlong]
     lib.emu_ric_per_problem_weights.restype = None
