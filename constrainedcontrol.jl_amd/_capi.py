@@ -19,7 +19,8 @@ EXPORTS = ["cclqr_last_error", "cclqr_version", "cclqr_device_count", "cclqr_set
            "cclqr_release_workspaces", "cclqr_rollout_geometry", "cclqr_rollout_layout_links", "cclqr_ctrl_set_feedforward", "cclqr_abi_layout", "cclqr_rollout_lanes_per_link", "cclqr_rollout_instances_per_wavefront",
            "cclqr_plants_create", "cclqr_plants_destroy", "cclqr_rollout_plants", "cclqr_linearize_plants", "cclqr_ctrl_create_lqr_batch_plants",
            "cclqr_ctrl_create_tracking_batch_plants", "cclqr_ctrl_get_gains", "cclqr_score_create", "cclqr_score_destroy", "cclqr_rollout_score",
-           "cclqr_riccati_weights", "cclqr_ctrl_create_lqr_batch_weights"]
+           "cclqr_riccati_weights", "cclqr_ctrl_create_lqr_batch_weights",
+           "cclqr_riccati_value", "cclqr_ctrl_create_lqr_batch_value", "cclqr_value_create", "cclqr_value_get", "cclqr_value_destroy", "cclqr_value_eval"]
 ABI_VERSION = 202     # include/cclqr.h CCLQR_ABI_VERSION: the structs below mirror that header (verified field by field against cclqr_abi_layout at load time)
 ROLLOUT_NO_ALLOC = 1  # cclqr_rollout_opts.flags: the call may neither allocate nor synchronise (a hipGraph capture is open on the device)
 ROLLOUT_CARRY_STATUS = 4  # ... `status` is read and written: an instance lost in an earlier launch stays frozen, the others merge this launch's result into it
@@ -250,8 +251,10 @@ class CtrlHandle:
 class BatchLqrHandle:
     """cclqr_ctrl* built by cclqr_ctrl_create_lqr_batch: one LQR per setpoint (linearsystem + dlqr + controller tables), gains device-resident"""
 
-    def __init__(self, mech, zd, ctrl_joint, Q, R, N, Fd=None, tol=1e-5, infinite_horizon=False, plants=None, first_plant=0, n_weights=None):
+    def __init__(self, mech, zd, ctrl_joint, Q, R, N, Fd=None, tol=1e-5, infinite_horizon=False, plants=None, first_plant=0, n_weights=None, keep_value=False):
         """infinite_horizon: LQR{T,Inf} -- N = Ntemp = ceil(10/Δt) (lqr.jl:26), only Ku[1] per setpoint is kept.
+        keep_value: every table's cost-to-go stays on the device as self.value, a ValueHandle (cclqr_ctrl_create_lqr_batch_value); False: self.value is None and
+        nothing is allocated.
         plants: a PlantsHandle (cclqr_ctrl_create_lqr_batch_plants) -- table k is designed on the plant with global index first_plant + k.
         n_weights: Q [n_weights][12 nb][12 nb], R [n_weights][mu][mu], one pair per table (cclqr_ctrl_create_lqr_batch_weights; the library refuses any count but
         1 and the number of setpoints); None: one pair, through the entry points that take one"""
@@ -272,7 +275,13 @@ class BatchLqrHandle:
         head = (C.c_int32(n), _d(zd), C.c_int32(mu), _i(cj), _d(Fd))
         last = (_d(Q), _d(R), C.c_int32(int(N)), C.c_int32(1 if infinite_horizon else 0), C.c_double(float(tol)), _i(self.kbreak), C.byref(self.ptr))
         tail = head + last
-        if n_weights is not None:
+        self.value = None
+        if keep_value:
+            vptr = C.c_void_p()
+            check(lib().cclqr_ctrl_create_lqr_batch_value(mech.ptr, None if plants is None else plants.ptr, C.c_int64(int(first_plant)), *head, C.c_int32(nw), *last,
+                                                          C.byref(vptr)))
+            self.value = ValueHandle(mech, ptr=vptr, n_tables=n)
+        elif n_weights is not None:
             check(lib().cclqr_ctrl_create_lqr_batch_weights(mech.ptr, None if plants is None else plants.ptr, C.c_int64(int(first_plant)), *head, C.c_int32(nw), *last))
         elif plants is None:
             check(lib().cclqr_ctrl_create_lqr_batch(mech.ptr, *tail))
@@ -283,12 +292,58 @@ class BatchLqrHandle:
         if self.ptr:
             lib().cclqr_ctrl_destroy(self.ptr)
             self.ptr = C.c_void_p()
+        if getattr(self, "value", None) is not None:
+            self.value.close()
 
     def __del__(self):
         try:
             self.close()
         except Exception:
             pass
+
+
+class ValueHandle:
+    """cclqr_value*: device-resident cost-to-go tables P [n_tables][12 nb][12 nb] in the mechanism's body order, one shared by every instance or one per controller
+    table.  P: a host array (cclqr_value_create); ptr / n_tables: a handle the library has already filled (cclqr_ctrl_create_lqr_batch_value)"""
+
+    def __init__(self, mech, P=None, ptr=None, n_tables=None):
+        mx = 12 * mech.tables.nb
+        self.mech, self.mx = mech, mx      # (the handle must not outlive the mechanism's)
+        if ptr is not None:
+            self.ptr, self.n_tables = ptr, int(n_tables)
+            return
+        P = f64(P)
+        if P.ndim < 2 or P.shape[-2:] != (mx, mx):
+            raise ValueError("P must be [n_tables][12 nb][12 nb] = [..][%d][%d] (got %s)" % (mx, mx, P.shape))
+        P = np.ascontiguousarray(P.reshape(-1, mx, mx))
+        self.n_tables = P.shape[0]
+        self.ptr = C.c_void_p()
+        check(lib().cclqr_value_create(mech.ptr, C.c_int64(self.n_tables), _d(P), C.byref(self.ptr)))
+
+    def get(self, table=0):
+        """one table read back: P [12 nb][12 nb] (cclqr_value_get)"""
+        P = np.zeros((self.mx, self.mx))
+        check(lib().cclqr_value_get(self.ptr, C.c_int64(int(table)), _d(P)))
+        return P
+
+    def close(self):
+        if self.ptr:
+            lib().cclqr_value_destroy(self.ptr)
+            self.ptr = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def value_eval(mech, ctrl, value, n_inst, z_ptr, out_ptr, stream=0, first_instance=0, z_stride=None):
+    """cclqr_value_eval on device addresses (asynchronous on `stream`): out[i] = dz_i' P_t dz_i for the states at z_ptr + 8 i z_stride (z_stride in doubles; default: packed,
+    13 nb) about setpoint row 0 of controller table first_instance + i"""
+    vp = lambda p: C.c_void_p(int(p)) if p else None
+    zs = 13 * mech.tables.nb if z_stride is None else int(z_stride)
+    check(lib().cclqr_value_eval(mech.ptr, ctrl.ptr, value.ptr, C.c_int64(int(n_inst)), C.c_int64(int(first_instance)), vp(z_ptr), C.c_int64(zs), vp(out_ptr), vp(stream)))
 
 
 class BatchTrackingHandle:
@@ -631,6 +686,37 @@ def riccati_weights(A, Bu, Bl, G, Q, R, N, tol=1e-5, path=0, bf16_terms=0, keep_
     check(lib().cclqr_riccati_weights(C.c_int32(nprob), C.c_int32(mx), C.c_int32(mu), C.c_int32(ml), _d(A), _d(Bu), _d(Bl), _d(G), C.c_int32(nw), _d(Q), _d(R),
                                       C.c_int32(N), C.c_double(tol), _d(K), _i(kb), C.byref(o)))
     return K, kb
+
+
+def riccati_value(A, Bu, Bl, G, Q, R, N, tol=1e-5, path=0, bf16_terms=0, keep_last=False, time_varying=False, want_P=True):
+    """batched dlqr that also returns the cost-to-go (cclqr_riccati_value): A [nprob][mx][mx] -- with time_varying [nprob][N-1][mx][mx], the model of backward step k at
+    index k - 1 -- Q [n_weights][mx][mx], R [n_weights][mu][mu] with n_weights = 1 or nprob -> K [nprob][N-1][mu][mx], P [nprob][mx][mx], kbreak [nprob].  P[p] is the
+    Pkp1 (lqr.jl:170) of the last backward step problem p executed, Q_p when N = 1.  want_P=False passes P = NULL (P is returned as None)"""
+    A = f64(A)
+    mx = A.shape[-1]
+    per = (N - 1) if time_varying else 1
+    A = A.reshape(-1, mx, mx)
+    if A.shape[0] % per:
+        raise ValueError("time_varying: A must hold N - 1 = %d models per problem (got %d models)" % (per, A.shape[0]))
+    nmod = A.shape[0]
+    nprob = nmod // per
+    Bu, Bl = f64(Bu), f64(Bl)
+    Bu = Bu.reshape(nmod, mx, Bu.shape[-1] if Bu.ndim > 1 else -1)
+    mu = Bu.shape[2]
+    Bl = Bl.reshape(nmod, mx, Bl.shape[-1] if Bl.ndim > 1 else -1)
+    ml = Bl.shape[2]
+    G = f64(G).reshape(nmod, ml, mx)
+    Q = f64(Q).reshape(-1, mx, mx)
+    nw = Q.shape[0]
+    R = f64(R).reshape(nw, mu, mu)
+    K = np.zeros((nprob, (1 if keep_last else N - 1) if N > 1 else 0, mu, mx))
+    P = np.zeros((nprob, mx, mx)) if want_P else None
+    kb = np.zeros(nprob, dtype=np.int32)
+    o = RiccatiOpts(int(path), int(bf16_terms), 1 if keep_last else 0, 0)
+    check(lib().cclqr_riccati_value(C.c_int32(nprob), C.c_int32(mx), C.c_int32(mu), C.c_int32(ml), _d(A), _d(Bu), _d(Bl) if ml else None, _d(G) if ml else None,
+                                    C.c_int32(nw), _d(Q), _d(R), C.c_int32(int(N)), C.c_double(float(tol)), C.c_int32(1 if time_varying else 0), _d(K), _d(P), _i(kb),
+                                    C.byref(o)))
+    return K, P, kb
 
 
 def riccati_tv(A, Bu, Bl, G, Q, R, N, tol=1e-5):

@@ -10,6 +10,7 @@ static_assert(CCLQR_NEWTON_MAXIT == NEWTON_MAXIT, "include/cclqr.h and cclqr_new
 #include "cclqr_wscache.h"
 #include "cclqr_score.h"
 static_assert(CCLQR_SCORE_LEN == CCLQR_SCORE_LEN_, "include/cclqr.h and cclqr_score.h disagree on the length of a score");
+#include "cclqr_value.h"
 #include <math.h>
 #include <stdio.h>
 #include <string.h>
@@ -331,9 +332,19 @@ static int check_n_weights(int n_weights, int nprob, const char* of) {
     return fail(CCLQR_EINVAL, "n_weights = " + std::to_string(n_weights) + ": the weights are one pair shared by all (1) or one pair per " + of + " (" + std::to_string(nprob) + ")");
 }
 
-extern "C" int cclqr_ctrl_create_lqr_batch_weights(const cclqr_mech* m, const cclqr_plants* plants, int64_t first_plant, int32_t n_ctrl, const double* zd, int32_t mu,
-                                                   const int32_t* ctrl_joint, const double* Fd, int32_t n_weights, const double* Q, const double* R, int32_t N,
-                                                   int32_t infinite_horizon, double tol, int32_t* kbreak, cclqr_ctrl** out) {
+// a cost-to-go object under construction: n_tables tables of mx x mx doubles on the mechanism's device, not yet filled
+typedef Owned<cclqr_value, cclqr_value_destroy> ValueOwner;
+static cclqr_value* value_new(const cclqr_mech* m, int64_t n_tables) {
+    cclqr_value* v = new cclqr_value();
+    memset(v, 0, sizeof(*v));
+    v->n_tables = n_tables; v->nb = m->nb; v->device = m->device; v->mech = m;
+    return v;
+}
+static hipError_t value_alloc(cclqr_value* v) { return hipMalloc((void**)&v->P_dev, (size_t)v->n_tables * 144 * (size_t)v->nb * v->nb * sizeof(double)); }
+
+extern "C" int cclqr_ctrl_create_lqr_batch_value(const cclqr_mech* m, const cclqr_plants* plants, int64_t first_plant, int32_t n_ctrl, const double* zd, int32_t mu,
+                                                 const int32_t* ctrl_joint, const double* Fd, int32_t n_weights, const double* Q, const double* R, int32_t N,
+                                                 int32_t infinite_horizon, double tol, int32_t* kbreak, cclqr_ctrl** out, cclqr_value** value) {
     static const char* const what = "batched LQR construction";
     const bool inf = infinite_horizon != 0;
     if (!m || !zd || !Q || !out || (mu > 0 && (!ctrl_joint || !R))) return fail(CCLQR_EINVAL, "null argument");
@@ -346,6 +357,7 @@ extern "C" int cclqr_ctrl_create_lqr_batch_weights(const cclqr_mech* m, const cc
     CtrlOwner own(ctrl_new(m));
     cclqr_ctrl* c = own.p;
     CtrlDev& H = c->host;
+    ValueOwner vown(value ? value_new(m, n_ctrl) : nullptr);      // (value == NULL: nothing is kept, nothing allocated)
     // LQR{T,Inf} (lqr.jl:25-27, 40-43): the recursion runs its N = Ntemp steps, only Ku[1] is kept and the feedback is never gated
     const size_t nKtab = inf ? 1 : (size_t)(N - 1);
     H.mu = mu; H.nK = (int)nKtab; H.N = inf ? 0 : N; H.nsp = 1; H.n_ctrl = n_ctrl;
@@ -364,6 +376,7 @@ extern "C" int cclqr_ctrl_create_lqr_batch_weights(const cclqr_mech* m, const cc
     HIPTRY(what, hipMalloc((void**)&c->zd_dev, np * nz * sizeof(double)));
     HIPTRY(what, hipMemcpy(c->zd_dev, zl.data(), np * nz * sizeof(double), hipMemcpyHostToDevice));
     HIPTRY(what, hipMalloc((void**)&c->K_dev, L.alloc_doubles * sizeof(double)));
+    if (vown.p) HIPTRY(what, value_alloc(vown.p));
     if (Fd) {
         HIPTRY(what, hipMalloc((void**)&c->Fd_dev, np * mu * sizeof(double)));
         HIPTRY(what, hipMemcpy(c->Fd_dev, Fd, np * mu * sizeof(double), hipMemcpyHostToDevice));
@@ -390,6 +403,7 @@ extern "C" int cclqr_ctrl_create_lqr_batch_weights(const cclqr_mech* m, const cc
     HIPTRY(what, hipMemcpy(dR, R, nw * mu * mu * sizeof(double), hipMemcpyHostToDevice));
     HIPTRY(what, hipMemset(c->K_dev, 0, L.alloc_doubles * sizeof(double)));
     ra.stop = dstop; ra.A = w.A; ra.Bu = w.Bu; ra.Bl = w.Bl; ra.G = w.G; ra.Q = dQ; ra.R = dR; ra.K = c->K_dev; ra.kbreak = dkb; ra.status = dst; ra.work = dwork;
+    ra.P_out = vown.p ? vown.p->P_dev : nullptr;      // the models and Q are in the caller's body order, so is the cost-to-go: it stays as the recursion leaves it
     HIPTRY(what, launch_riccati(ra, nullptr));
     const long long nrows = (long long)np * (long long)nKtab * mu;
     HIPTRY(what, launch_lds<false>(k_rows_to_link_order_kernel, dim3((unsigned)nrows), dim3(128), mx * sizeof(double), nullptr, c->K_dev, nrows, (long long)nKtab * mu, L.stride, nb, m->dev));
@@ -405,7 +419,14 @@ extern "C" int cclqr_ctrl_create_lqr_batch_weights(const cclqr_mech* m, const cc
         if (st[p] != 0) return fail(CCLQR_ESINGULAR, "G*Bl or M is singular at setpoint " + std::to_string(p));
     }
     *out = own.release();
+    if (value) *value = vown.release();
     return CCLQR_OK;
+}
+
+extern "C" int cclqr_ctrl_create_lqr_batch_weights(const cclqr_mech* m, const cclqr_plants* plants, int64_t first_plant, int32_t n_ctrl, const double* zd, int32_t mu,
+                                                   const int32_t* ctrl_joint, const double* Fd, int32_t n_weights, const double* Q, const double* R, int32_t N,
+                                                   int32_t infinite_horizon, double tol, int32_t* kbreak, cclqr_ctrl** out) {
+    return cclqr_ctrl_create_lqr_batch_value(m, plants, first_plant, n_ctrl, zd, mu, ctrl_joint, Fd, n_weights, Q, R, N, infinite_horizon, tol, kbreak, out, nullptr);
 }
 
 extern "C" int cclqr_ctrl_create_lqr_batch_plants(const cclqr_mech* m, const cclqr_plants* plants, int64_t first_plant, int32_t n_ctrl, const double* zd, int32_t mu,
@@ -989,13 +1010,14 @@ extern "C" int cclqr_linearize_projected(const cclqr_mech* m, int32_t nk, const 
 }
 
 // shared tail of the dlqr entry points: run the recursion on device-resident (A,Bu,Bl,G) inside the caller's WsScope, download K and kbreak.  Q, R: n_weights = 1
-// pair shared by the problems, or nprob pairs (the caller has checked: check_n_weights)
+// pair shared by the problems, or nprob pairs (the caller has checked: check_n_weights).  P: host [nprob][mx][mx] for the cost-to-go (RicArgs.P_out), or null
 static int run_riccati(int nprob, int mx, int mu, int ml, int N, int time_varying, double tol, const double* dA, const double* dBu,
                        const double* dBl, const double* dG, int n_weights, const double* Q, const double* R, double* K, int32_t* kbreak,
-                       const cclqr_riccati_opts* opts) {
+                       const cclqr_riccati_opts* opts, double* P = nullptr) {
     const int keep_last = (opts && opts->keep_last) ? 1 : 0;
     const size_t nK = (size_t)nprob * (N > 1 ? (keep_last ? 1 : N - 1) : 0) * mu * mx;
-    double *dQ = nullptr, *dR = nullptr, *dK = nullptr, *dwork = nullptr;
+    const size_t nP = (size_t)nprob * mx * mx;
+    double *dQ = nullptr, *dR = nullptr, *dK = nullptr, *dwork = nullptr, *dP = nullptr;
     int *dkb = nullptr, *dst = nullptr, *dstop = nullptr;
     std::vector<int> st(nprob), kb(nprob);
     RicArgs a;
@@ -1014,14 +1036,17 @@ static int run_riccati(int nprob, int mx, int mu, int ml, int N, int time_varyin
     HIPTRY("riccati", ws_get((void**)&dstop, nprob * sizeof(int)));
     HIPTRY("riccati", ws_get((void**)&dkb, nprob * sizeof(int)));
     HIPTRY("riccati", ws_get((void**)&dst, nprob * sizeof(int)));
+    if (P) HIPTRY("riccati", ws_get((void**)&dP, nP * sizeof(double)));
     HIPTRY("riccati", hipMemcpy(dQ, Q, nw * mx * mx * sizeof(double), hipMemcpyHostToDevice));
     if (mu > 0) HIPTRY("riccati", hipMemcpy(dR, R, nw * mu * mu * sizeof(double), hipMemcpyHostToDevice));
     HIPTRY("riccati", hipMemset(dK, 0, (nK + 1) * sizeof(double)));
     a.stop = dstop;
     a.A = dA; a.Bu = dBu; a.Bl = dBl; a.G = dG; a.Q = dQ; a.R = dR; a.K = dK; a.kbreak = dkb; a.status = dst; a.work = dwork;
+    a.P_out = dP;
     HIPTRY("riccati", launch_riccati(a, nullptr));
     HIPTRY("riccati", hipDeviceSynchronize());
     if (nK) HIPTRY("riccati", hipMemcpy(K, dK, nK * sizeof(double), hipMemcpyDeviceToHost));
+    if (P) HIPTRY("riccati", hipMemcpy(P, dP, nP * sizeof(double), hipMemcpyDeviceToHost));
     HIPTRY("riccati", hipMemcpy(kb.data(), dkb, nprob * sizeof(int), hipMemcpyDeviceToHost));
     HIPTRY("riccati", hipMemcpy(st.data(), dst, nprob * sizeof(int), hipMemcpyDeviceToHost));
     for (int p = 0; p < nprob; p++) {
@@ -1057,26 +1082,28 @@ extern "C" int cclqr_riccati_ex(int32_t nprob, int32_t mx, int32_t mu, int32_t m
     return cclqr_riccati_weights(nprob, mx, mu, ml, A, Bu, Bl, G, 1, Q, R, N, tol, K, kbreak, opts);
 }
 
-extern "C" int cclqr_riccati_weights(int32_t nprob, int32_t mx, int32_t mu, int32_t ml, const double* A, const double* Bu, const double* Bl,
-                                     const double* G, int32_t n_weights, const double* Q, const double* R, int32_t N, double tol, double* K,
-                                     int32_t* kbreak, const cclqr_riccati_opts* opts) {
+extern "C" int cclqr_riccati_value(int32_t nprob, int32_t mx, int32_t mu, int32_t ml, const double* A, const double* Bu, const double* Bl, const double* G,
+                                   int32_t n_weights, const double* Q, const double* R, int32_t N, double tol, int32_t time_varying, double* K, double* P,
+                                   int32_t* kbreak, const cclqr_riccati_opts* opts) {
+    const int tv = time_varying != 0;
     if (!A || !Q || (mu > 0 && (!Bu || !R)) || (ml > 0 && (!Bl || !G)) || !K) return fail(CCLQR_EINVAL, "null argument");
-    if (nprob < 1 || mx < 1 || mu < 0 || ml < 0 || N < 1) return fail(CCLQR_EINVAL, "bad sizes");
+    if (nprob < 1 || mx < 1 || mu < 0 || ml < 0 || N < (tv ? 2 : 1)) return fail(CCLQR_EINVAL, "bad sizes");
     TRY(check_n_weights(n_weights, nprob, "problem"));
     WsScope scope;
     RicModels d = {};
-    TRY(upload_models((size_t)nprob, mx, mu, ml, A, Bu, Bl, G, d));
-    return run_riccati(nprob, mx, mu, ml, N, 0, tol, d.A, d.Bu, d.Bl, d.G, n_weights, Q, R, K, kbreak, opts);
+    TRY(upload_models((size_t)nprob * (tv ? (size_t)N - 1 : 1), mx, mu, ml, A, Bu, Bl, G, d));      // one model per problem, or per knot of every problem
+    return run_riccati(nprob, mx, mu, ml, N, tv, tol, d.A, d.Bu, d.Bl, d.G, n_weights, Q, R, K, kbreak, opts, P);
+}
+
+extern "C" int cclqr_riccati_weights(int32_t nprob, int32_t mx, int32_t mu, int32_t ml, const double* A, const double* Bu, const double* Bl,
+                                     const double* G, int32_t n_weights, const double* Q, const double* R, int32_t N, double tol, double* K,
+                                     int32_t* kbreak, const cclqr_riccati_opts* opts) {
+    return cclqr_riccati_value(nprob, mx, mu, ml, A, Bu, Bl, G, n_weights, Q, R, N, tol, 0, K, nullptr, kbreak, opts);
 }
 
 extern "C" int cclqr_riccati_tv(int32_t mx, int32_t mu, int32_t ml, const double* A, const double* Bu, const double* Bl, const double* G,
                                 const double* Q, const double* R, int32_t N, double tol, double* K, int32_t* kbreak) {
-    if (!A || !Q || (mu > 0 && (!Bu || !R)) || (ml > 0 && (!Bl || !G)) || !K) return fail(CCLQR_EINVAL, "null argument");
-    if (mx < 1 || mu < 0 || ml < 0 || N < 2) return fail(CCLQR_EINVAL, "bad sizes");
-    WsScope scope;
-    RicModels d = {};
-    TRY(upload_models((size_t)N - 1, mx, mu, ml, A, Bu, Bl, G, d));
-    return run_riccati(1, mx, mu, ml, N, 1, tol, d.A, d.Bu, d.Bl, d.G, 1, Q, R, K, kbreak, nullptr);
+    return cclqr_riccati_value(1, mx, mu, ml, A, Bu, Bl, G, 1, Q, R, N, tol, 1, K, nullptr, kbreak, nullptr);
 }
 
 extern "C" int cclqr_riccati_tracking(const cclqr_mech* m, int32_t mu, const int32_t* ctrl_joint, const double* zd, const double* Fd,
@@ -1152,5 +1179,59 @@ extern "C" int cclqr_rollout_score(const cclqr_mech* m, const cclqr_ctrl* c, con
     a.M = m->dev; a.C = c->dev; a.Qb = s->Qb_dev; a.R = s->R_dev; a.settle_tol = s->settle_tol; a.nb = m->nb; a.mu = s->mu;
     a.n_inst = n_inst; a.steps = steps; a.k0 = k0; a.inst0 = first_instance; a.traj = traj; a.score = score;
     HIPCHK(launch_score(a, (hipStream_t)stream));
+    return CCLQR_OK;
+}
+
+// ---- the cost-to-go of a controller's tables and the cost it predicts (value.hip).  P stays in the caller's body order, as the recursion holds it (the models and Q
+// are in that order); the kernel permutes the error, not the table
+extern "C" int cclqr_value_create(const cclqr_mech* m, int64_t n_tables, const double* P_host, cclqr_value** out) {
+    if (!m || !P_host || !out) return fail(CCLQR_EINVAL, "null argument");
+    TRY(check_device(m));
+    if (n_tables < 1) return fail(CCLQR_EINVAL, "n_tables = " + std::to_string(n_tables) + ": a value object holds at least one table");
+    ValueOwner own(value_new(m, n_tables));
+    HIPTRY("cost-to-go upload", value_alloc(own.p));
+    HIPTRY("cost-to-go upload", hipMemcpy(own.p->P_dev, P_host, (size_t)n_tables * 144 * (size_t)m->nb * m->nb * sizeof(double), hipMemcpyHostToDevice));
+    *out = own.release();
+    return CCLQR_OK;
+}
+
+extern "C" int cclqr_value_get(const cclqr_value* v, int64_t table, double* P_host) {
+    if (!v || !P_host) return fail(CCLQR_EINVAL, "null argument");
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess || dev != v->device) return fail(CCLQR_EINVAL, "the calling thread is not on the value object's device");
+    if (table < 0 || table >= v->n_tables) return fail(CCLQR_EINVAL, "table " + std::to_string(table) + " is not among the value object's tables 0 .. " + std::to_string(v->n_tables - 1));
+    const size_t per = 144 * (size_t)v->nb * v->nb;
+    HIPCHK(hipMemcpy(P_host, v->P_dev + (size_t)table * per, per * sizeof(double), hipMemcpyDeviceToHost));
+    return CCLQR_OK;
+}
+
+extern "C" int cclqr_value_destroy(cclqr_value* v) {
+    if (!v) return CCLQR_OK;
+    if (v->P_dev) (void)hipFree(v->P_dev);
+    delete v;
+    return CCLQR_OK;
+}
+
+extern "C" int cclqr_value_eval(const cclqr_mech* m, const cclqr_ctrl* c, const cclqr_value* v, int64_t n_inst, int64_t first_instance, const double* z_dev,
+                                int64_t z_stride, double* out_dev, void* stream) {
+    if (!m || !c || !v) return fail(CCLQR_EINVAL, "null argument");
+    TRY(check_device(m));
+    if (v->mech != m || v->nb != m->nb || v->device != m->device) return fail(CCLQR_EINVAL, "the value object was created for another mechanism or device");
+    if (c->nb != m->nb || c->device != m->device) return fail(CCLQR_EINVAL, "the controller was created for another mechanism or device");
+    if (n_inst < 0 || first_instance < 0) return fail(CCLQR_EINVAL, "negative n_inst or first_instance");
+    const int64_t ctrl_tables = c->host.n_ctrl > 1 ? c->host.n_ctrl : 1;
+    if (v->n_tables != 1 && v->n_tables != ctrl_tables)
+        return fail(CCLQR_EINVAL, "the value object holds " + std::to_string(v->n_tables) + " tables: one shared by all (1) or one per controller table (" + std::to_string(ctrl_tables) + ")");
+    if (!c->zd_dev || c->host.nsp < 1) return fail(CCLQR_EINVAL, "the controller has no setpoint table");
+    const int64_t tables = v->n_tables > 1 ? v->n_tables : ctrl_tables;
+    if (tables > 1 && first_instance + n_inst > tables)
+        return fail(CCLQR_EINVAL, "first_instance + n_inst = " + std::to_string(first_instance + n_inst) + " exceeds the " + std::to_string(tables) + " tables");
+    if (z_stride < 13 * (int64_t)m->nb) return fail(CCLQR_EINVAL, "z_stride = " + std::to_string(z_stride) + " is less than a state's 13 nb = " + std::to_string(13 * m->nb) + " doubles");
+    if (n_inst == 0) return CCLQR_OK;
+    if (!z_dev || !out_dev) return fail(CCLQR_EINVAL, "null argument");
+    ValueArgs a;
+    a.M = m->dev; a.C = c->dev; a.P = v->P_dev; a.p_stride = v->n_tables > 1 ? 144LL * m->nb * m->nb : 0; a.nb = m->nb;
+    a.n_inst = n_inst; a.inst0 = first_instance; a.z = z_dev; a.z_stride = z_stride; a.out = out_dev;
+    HIPCHK(launch_value(a, (hipStream_t)stream));
     return CCLQR_OK;
 }

@@ -178,6 +178,9 @@ struct RicArgs {
     int p_rows = 0;          // 1: Q or R is not symmetric (ric_p_rows on the host arrays): the kernels that assume a symmetric Pk are not used
     long long q_stride = 0, r_stride = 0;      // doubles between the Q / R of consecutive problems: 0 = one pair shared by every problem, or mx*mx / mu*mu = one
                                                // pair per problem (ric_per_problem_weights)
+    double* P_out = nullptr; // [nprob][mx][mx] device, or null: the cost-to-go Pkp1 of every problem's last executed backward step (lqr.jl:170; the step the break test
+                             // of lqr.jl:172 fired on, else step 1; Q when N = 1), row-major as the recursion holds it; unspecified for a problem whose status is not 0.
+                             // 16-byte aligned (the resident kernels store two doubles at a time)
 };
 // is the n x n row-major host matrix exactly symmetric?
 inline bool ric_symmetric(const double* X, int n) {
@@ -263,6 +266,13 @@ struct cclqr_score {
     double settle_tol;
     int nb, mu, device;
     const cclqr_mech* mech;    // the mechanism whose link order the blocks were permuted to
+};
+// the cost-to-go tables of a controller (cclqr_value_create, cclqr_ctrl_create_lqr_batch_value): P in the caller's body order, as the recursion holds it
+struct cclqr_value {
+    double* P_dev;             // [n_tables][12 nb][12 nb] row-major
+    int64_t n_tables;
+    int nb, device;
+    const cclqr_mech* mech;    // the mechanism whose body order the tables are in
 };
 struct cclqr_ctrl {
     cclqr::CtrlDev host;

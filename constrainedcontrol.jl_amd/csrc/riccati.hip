@@ -783,8 +783,10 @@ __device__ __forceinline__ v4d ric_tile_bf16(const RicBf16Frag<BF, NGF>& F, cons
     return r;
 }
 
-template <int MUT, int NGT, int BF = 0>
-__global__ __launch_bounds__(RIC_THREADS) void riccati_resident_kernel(RicGrid a) {
+// EMIT: the cost-to-go the loop leaves in LDS goes to P_out [nprob][mx][mx] (riccati_resident_kernel_p, RicArgs.P_out); without it the kernel is the one that has
+// always run, on the same kernel argument
+template <int MUT, int NGT, int BF, bool EMIT>
+__device__ __forceinline__ void riccati_resident_body(const RicGrid& a, double* P_out) {
     extern __shared__ double rl[];
 #ifdef CCLQR_PROFILE
     unsigned long long rt0 = __builtin_readcyclecounter();
@@ -1172,12 +1174,24 @@ __global__ __launch_bounds__(RIC_THREADS) void riccati_resident_kernel(RicGrid a
             for (int e = tid; e < mu * mx; e += RIC_THREADS) Kout[(size_t)(k2 - 1) * mu * mx + e] = Kout[(size_t)k2 * mu * mx + e];
             __syncthreads();
         }
+        // the cost-to-go that the loop left in LDS: Pk = Pkp1 of the last executed step (the step the break test fired on, lqr.jl:172, or step 1), Q when N = 1
+        if (EMIT) {      // two doubles per lane and pass: mx is a multiple of 4 (ric_resident_fits), P_out is 16-byte aligned (RicArgs)
+            typedef double v2d __attribute__((ext_vector_type(2)));
+            v2d* Po = (v2d*)(P_out + (size_t)prob * mx * mx);
+            const __attribute__((address_space(3))) v2d* P2 = (const __attribute__((address_space(3))) v2d*)P;
+            for (int e = tid; e < (mx * mx) >> 1; e += RIC_THREADS) Po[e] = P2[e];
+        }
     }
     if (tid == 0) { a.kbreak[prob] = k; a.status[prob] = status; }
 }
+template <int MUT, int NGT, int BF = 0>
+__global__ __launch_bounds__(RIC_THREADS) void riccati_resident_kernel(RicGrid a) { riccati_resident_body<MUT, NGT, BF, false>(a, nullptr); }
+// ... and with the cost-to-go emitted
+template <int MUT, int NGT, int BF = 0>
+__global__ __launch_bounds__(RIC_THREADS) void riccati_resident_kernel_p(RicGrid a, double* P_out) { riccati_resident_body<MUT, NGT, BF, true>(a, P_out); }
 
 // Ku[k2] = Ku[k2+1] below the break index (lqr.jl:179-181) and the loop variable's final value
-__global__ void ric_backfill_kernel(RicGrid a) {
+__global__ void ric_backfill_kernel(RicGrid a, double* P_out) {
     const int prob = blockIdx.x, tid = threadIdx.x;
     const int mu = a.mu, mx = a.mx, N = a.N;
     __shared__ int kb;
@@ -1190,7 +1204,15 @@ __global__ void ric_backfill_kernel(RicGrid a) {
         kb = k;
     }
     __syncthreads();
-    if (a.status[prob] != 0 || a.keep_last) return;
+    if (a.status[prob] != 0) return;
+    // the cost-to-go of the last executed step: ric_pn_kernel of step k wrote buffer (N - k) & 1, and the last step whose ric_pn_kernel ran is kbreak -- a break is
+    // detected by the NEXT step's gain kernel, which stops the problem before anything overwrites that buffer.  N = 1: no step ran, buffer 0 holds Q (ric_project_kernel)
+    if (P_out) {
+        const double* Pl = a.P + ((size_t)(kb >= 1 ? (N - kb) & 1 : 0) * a.nprob + prob) * mx * mx;
+        double* Po = P_out + (size_t)prob * mx * mx;
+        for (int e = tid; e < mx * mx; e += blockDim.x) Po[e] = Pl[e];
+    }
+    if (a.keep_last) return;
     double* Kout = a.K + (size_t)prob * ((size_t)(N > 1 ? N - 1 : 0) * mu * mx + a.kpad);
     for (int k2 = kb - 1; k2 >= 1; k2--) {
         for (int e = tid; e < mu * mx; e += blockDim.x) Kout[(size_t)(k2 - 1) * mu * mx + e] = Kout[(size_t)k2 * mu * mx + e];
@@ -1279,6 +1301,36 @@ static void ric_pp_assign(int T, int C, unsigned char* mask) {
     }
 }
 
+// The resident kernel of a launch.  PO: the forms that emit the cost-to-go (riccati_resident_kernel_p, one more kernel argument); inside the struct
+// riccati_resident_kernel<MU, NG, BF> names the instantiation of the struct's form, so that the rule below is stated once for both
+template <bool PO>
+struct RicResident {
+    typedef typename std::conditional<PO, void (*)(RicGrid, double*), void (*)(RicGrid)>::type ResKernel;
+    template <int MUT, int NGT, int BF>
+    static constexpr ResKernel form() {
+        if constexpr (PO) return cclqr::riccati_resident_kernel_p<MUT, NGT, BF>;
+        else return cclqr::riccati_resident_kernel<MUT, NGT, BF>;
+    }
+    template <int MUT, int NGT, int BF = 0>
+    static constexpr ResKernel riccati_resident_kernel = form<MUT, NGT, BF>();
+    static ResKernel pick(const RicArgs& a) {
+        // specialised (inputs, states / 4) shapes: the BASELINE mechanisms; every other shape takes the generic forms
+        static const ResKernel by_mu[RIC_MU_REG + 1] = {riccati_resident_kernel<0, 0>, riccati_resident_kernel<1, 0>, riccati_resident_kernel<2, 0>, riccati_resident_kernel<3, 0>,
+                                                        riccati_resident_kernel<4, 0>, riccati_resident_kernel<5, 0>, riccati_resident_kernel<6, 0>, riccati_resident_kernel<7, 0>};
+        ResKernel kern = by_mu[(a.mu >= 1 && a.mu <= RIC_MU_REG) ? a.mu : 0];
+        const int ng4 = a.p_rows ? -1 : a.mx >> 2;     // (the register-fragment forms compute half of a symmetric Pkp1 and mirror it)
+        if (a.mu == 1 && ng4 == 3) kern = riccati_resident_kernel<1, 3>;          // pendulum (mx 12)
+        else if (a.mu == 1 && ng4 == 6) kern = riccati_resident_kernel<1, 6>;     // cartpole, acrobot (mx 24)
+        else if (a.mu == 1 && ng4 == 12) kern = riccati_resident_kernel<1, 12>;   // triple cartpole (mx 48)
+        else if (a.mu == 7 && ng4 == 21) kern = riccati_resident_kernel<7, 21>;   // Sawyer (mx 84)
+        if (a.bf16_terms > 0) {      // ric_use_tiled has checked that the shape is one of these
+            if (a.mu == 7) kern = a.bf16_terms == 1 ? riccati_resident_kernel<7, 21, 1> : (a.bf16_terms == 2 ? riccati_resident_kernel<7, 21, 2> : riccati_resident_kernel<7, 21, 3>);
+            else kern = a.bf16_terms == 1 ? riccati_resident_kernel<1, 6, 1> : (a.bf16_terms == 2 ? riccati_resident_kernel<1, 6, 2> : riccati_resident_kernel<1, 6, 3>);
+        }
+        return kern;
+    }
+};
+
 hipError_t launch_riccati(const RicArgs& a, hipStream_t stream) {
     if (a.nprob <= 0) return hipSuccess;
     RicGrid g;
@@ -1307,21 +1359,8 @@ hipError_t launch_riccati(const RicArgs& a, hipStream_t stream) {
     if (e != hipSuccess) return e;
     if (!ric_use_tiled(a)) {
         const size_t rl = ric_resident_lds_bytes(a.mx, a.mu);
-        typedef void (*ResKernel)(RicGrid);
-        // specialised (inputs, states / 4) shapes: the BASELINE mechanisms; every other shape takes the generic forms
-        static const ResKernel by_mu[RIC_MU_REG + 1] = {riccati_resident_kernel<0, 0>, riccati_resident_kernel<1, 0>, riccati_resident_kernel<2, 0>, riccati_resident_kernel<3, 0>,
-                                                        riccati_resident_kernel<4, 0>, riccati_resident_kernel<5, 0>, riccati_resident_kernel<6, 0>, riccati_resident_kernel<7, 0>};
-        ResKernel kern = by_mu[(a.mu >= 1 && a.mu <= RIC_MU_REG) ? a.mu : 0];
-        const int ng4 = a.p_rows ? -1 : a.mx >> 2;     // (the register-fragment forms compute half of a symmetric Pkp1 and mirror it)
-        if (a.mu == 1 && ng4 == 3) kern = riccati_resident_kernel<1, 3>;          // pendulum (mx 12)
-        else if (a.mu == 1 && ng4 == 6) kern = riccati_resident_kernel<1, 6>;     // cartpole, acrobot (mx 24)
-        else if (a.mu == 1 && ng4 == 12) kern = riccati_resident_kernel<1, 12>;   // triple cartpole (mx 48)
-        else if (a.mu == 7 && ng4 == 21) kern = riccati_resident_kernel<7, 21>;   // Sawyer (mx 84)
-        if (a.bf16_terms > 0) {      // ric_use_tiled has checked that the shape is one of these
-            if (a.mu == 7) kern = a.bf16_terms == 1 ? riccati_resident_kernel<7, 21, 1> : (a.bf16_terms == 2 ? riccati_resident_kernel<7, 21, 2> : riccati_resident_kernel<7, 21, 3>);
-            else kern = a.bf16_terms == 1 ? riccati_resident_kernel<1, 6, 1> : (a.bf16_terms == 2 ? riccati_resident_kernel<1, 6, 2> : riccati_resident_kernel<1, 6, 3>);
-        }
-        return launch_lds(kern, dim3(a.nprob), dim3(RIC_THREADS), rl, stream, g);
+        return a.P_out ? launch_lds(RicResident<true>::pick(a), dim3(a.nprob), dim3(RIC_THREADS), rl, stream, g, a.P_out)
+                       : launch_lds(RicResident<false>::pick(a), dim3(a.nprob), dim3(RIC_THREADS), rl, stream, g);
     }
     const size_t lds_gain = (mu * na + mu * mu + 2 * RU * mu) * sizeof(double) + (mu + 2) * sizeof(int), lds_pn = 2 * mu * 32 * sizeof(double);
     void (*const gain_update)(RicGrid, int) = ric_gain_update_kernel;      // (one name for the limit raised here, once per call, and the launches below)
@@ -1335,7 +1374,7 @@ hipError_t launch_riccati(const RicArgs& a, hipStream_t stream) {
         if (e == hipSuccess) e = launch_lds<false>(ric_pn_kernel, dim3(g.tm * g.tm, a.nprob), dim3(TILE_THREADS), lds_pn, stream, g, k);
         if (e != hipSuccess) return e;
     }
-    return launch_lds<false>(ric_backfill_kernel, dim3(a.nprob), dim3(TILE_THREADS), 0, stream, g);
+    return launch_lds<false>(ric_backfill_kernel, dim3(a.nprob), dim3(TILE_THREADS), 0, stream, g, a.P_out);
 }
 
 #ifdef CCLQR_PROFILE

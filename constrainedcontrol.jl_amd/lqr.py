@@ -81,7 +81,10 @@ class Controller:
 class LQR(Controller):
     """LQR{T,N,NK}: K[k][i] (1 x NK rows), xd, vd, qd, ωd, eqcids, Fτd   (lqr.jl:3-15)"""
 
-    def __init__(self, mechanism, bodyids, eqcids, Q, R, horizon, xd=None, vd=None, qd=None, ωd=None, Fτd=None, controlfunction=None, **kw):
+    def __init__(self, mechanism, bodyids, eqcids, Q, R, horizon, xd=None, vd=None, qd=None, ωd=None, Fτd=None, controlfunction=None, keep_value=False, **kw):
+        """keep_value: also keep the cost-to-go .P [12 nb][12 nb] of the recursion (the Pkp1 of lqr.jl:170 at its last executed step, mechanism body order) for
+        predicted_cost; False: .P is None and nothing more is computed or allocated"""
+        self.keep_value = bool(keep_value)
         if "wd" in kw:
             ωd = kw.pop("wd")
         if "Ftd" in kw:
@@ -149,7 +152,12 @@ class LQR(Controller):
         if G.shape[0] == 0 and N == math.inf and not getattr(self, "projected", False):
             # lqr.jl:33 calls dlqr(A,Bu,Q,R,N) which binds N=Inf to the Δt method of util.jl:50 — a defect, not reproduced
             raise ValueError("unconstrained infinite-horizon LQR is not reachable in the reference (lqr.jl:33)")
-        K, kbreak = _capi.riccati(A, Bu, Bl, G, self.Q, self.R, Ntemp)   # lqr.jl:36 / :39
+        self.P = None
+        if getattr(self, "keep_value", False):      # the same recursion, its cost-to-go returned with the gains (cclqr_riccati_value)
+            K, P, kb = _capi.riccati_value(A, Bu, Bl, G, self.Q, self.R, Ntemp)
+            K, self.P, kbreak = K[0], P[0], int(kb[0])
+        else:
+            K, kbreak = _capi.riccati(A, Bu, Bl, G, self.Q, self.R, Ntemp)   # lqr.jl:36 / :39
         self.kbreak = kbreak
         self.converged = True
         if N == math.inf:
@@ -183,6 +191,22 @@ class LQR(Controller):
     def _ctrl_handle(self, dev, fric=None, noise_scale=0.0, noise_seed=None):
         return _capi.CtrlHandle(dev, self.ctrl_joints, K=self.K, N=self.N, zd=self.zd, Fd=self.Fd, fric=fric, noise_scale=noise_scale, noise_seed=noise_seed)
 
+    def _value_handle(self, dev):
+        """(ValueHandle of .P on dev, whether the caller closes it)"""
+        if self.P is None:
+            raise ValueError("the LQR was built without keep_value=True: it has no cost-to-go")
+        return _capi.ValueHandle(dev, self.P), True
+
+
+def _kept_value(controller, dev):
+    """the device-resident cost-to-go of a batched constructor (PlantLQR, LQRSweep), which stays with its owner"""
+    v = controller._handle.value
+    if v is None:
+        raise ValueError("the %s was built without keep_value=True: it has no cost-to-go" % type(controller).__name__)
+    if v.mech is not dev or not v.ptr:
+        raise ValueError("the %s was designed on another device handle of the mechanism" % type(controller).__name__)
+    return v, False
+
 
 class _BorrowedCtrl:
     """what a controller that owns its device tables hands simulate: the same cclqr_ctrl*, and a close() that leaves the tables with their owner"""
@@ -205,7 +229,9 @@ class PlantLQR(Controller):
     plants.first_index).  kbreak [n], converged [n]: per plant, as LQR's.
     simulate(mech, steps, PlantLQR, z0=, plants=, first_instance=): instance i reads table first_instance + i and runs on plant first_instance + i."""
 
-    def __init__(self, mechanism, plants, bodyids, eqcids, Q, R, horizon, zd, Fτd=None, first_plant=None, controlfunction=None, tol=1e-5):
+    def __init__(self, mechanism, plants, bodyids, eqcids, Q, R, horizon, zd, Fτd=None, first_plant=None, controlfunction=None, tol=1e-5, keep_value=False):
+        """keep_value: every plant's cost-to-go stays on the device next to its gains (cclqr_ctrl_create_lqr_batch_value; 8 (12 nb)^2 bytes per plant) for
+        predicted_cost and P(i); False: nothing is kept or allocated"""
         if controlfunction is not None:
             raise ValueError("PlantLQR carries no controlfunction: its gains stay on the device (one LQR per plant with a closure: build an LQR per plant)")
         if not isinstance(mechanism, Mechanism):
@@ -239,7 +265,7 @@ class PlantLQR(Controller):
         self.horizon_steps, self.NK = N, 12 * nb
         dev = _device_mech(mechanism)
         self._handle = _capi.BatchLqrHandle(dev, zd, self.ctrl_joints, self.Q, self.R, Ntemp, Fd=Fd, tol=tol, infinite_horizon=N == math.inf,
-                                            plants=plants.handle(dev), first_plant=self.first_plant)
+                                            plants=plants.handle(dev), first_plant=self.first_plant, keep_value=keep_value)
         self.kbreak = self._handle.kbreak
         # LQR{T,Inf} (lqr.jl:40-42): converged when Ku[1] == Ku[2], i.e. when the recursion met its tolerance and back-filled the rest (kbreak > 1)
         self.converged = np.ones(n, dtype=bool) if N < math.inf else ((self.kbreak > 1) | (Ntemp < 3))
@@ -260,6 +286,13 @@ class PlantLQR(Controller):
         """K[k][j] of plant i's table, [nK][mu][12 nb] in the mechanism's body order, read back from the device (cclqr_ctrl_get_gains)"""
         return _capi.ctrl_gains(_device_mech(self.mechanism), self._handle, i)
 
+    def P(self, i):
+        """plant i's cost-to-go [12 nb][12 nb] (lqr.jl:170 at the recursion's last executed step), mechanism body order, read back from the device (keep_value=True)"""
+        return _kept_value(self, _device_mech(self.mechanism))[0].get(i)
+
+    def _value_handle(self, dev):
+        return _kept_value(self, dev)
+
     def close(self):
         self._handle.close()
 
@@ -278,7 +311,9 @@ class LQRSweep(Controller):
     n, kbreak [n], converged [n], gains(i), close().
     simulate(mech, steps, sweep, z0=, first_instance=): instance i runs under table first_instance + i."""
 
-    def __init__(self, mechanism, bodyids, eqcids, Qs, Rs, horizon, zd, Fτd=None, plants=None, first_plant=None, tol=1e-5, controlfunction=None):
+    def __init__(self, mechanism, bodyids, eqcids, Qs, Rs, horizon, zd, Fτd=None, plants=None, first_plant=None, tol=1e-5, controlfunction=None, keep_value=False):
+        """keep_value: every candidate's cost-to-go stays on the device next to its gains (cclqr_ctrl_create_lqr_batch_value; 8 (12 nb)^2 bytes per candidate) for
+        predicted_cost and P(i); False: nothing is kept or allocated"""
         if controlfunction is not None:
             raise ValueError("LQRSweep carries no controlfunction: its gains stay on the device (one LQR per candidate with a closure: build an LQR per candidate)")
         if not isinstance(mechanism, Mechanism):
@@ -330,7 +365,8 @@ class LQRSweep(Controller):
         self.horizon_steps, self.NK = N, 12 * nb
         dev = _device_mech(mechanism)
         self._handle = _capi.BatchLqrHandle(dev, zd, self.ctrl_joints, self.Q, self.R, Ntemp, Fd=Fd, tol=tol, infinite_horizon=N == math.inf,
-                                            plants=None if plants is None else plants.handle(dev), first_plant=self.first_plant, n_weights=n)
+                                            plants=None if plants is None else plants.handle(dev), first_plant=self.first_plant, n_weights=n,
+                                            keep_value=keep_value)
         self.kbreak = self._handle.kbreak
         # LQR{T,Inf} (lqr.jl:40-42): converged when Ku[1] == Ku[2], i.e. when the recursion met its tolerance and back-filled the rest (kbreak > 1)
         self.converged = np.ones(n, dtype=bool) if N < math.inf else ((self.kbreak > 1) | (Ntemp < 3))
@@ -350,6 +386,14 @@ class LQRSweep(Controller):
     def gains(self, i):
         """K[k][j] of candidate i's table, [nK][mu][12 nb] in the mechanism's body order, read back from the device (cclqr_ctrl_get_gains)"""
         return _capi.ctrl_gains(_device_mech(self.mechanism), self._handle, i)
+
+    def P(self, i):
+        """candidate i's cost-to-go [12 nb][12 nb] (lqr.jl:170 at the recursion's last executed step), mechanism body order, read back from the device
+        (keep_value=True)"""
+        return _kept_value(self, _device_mech(self.mechanism))[0].get(i)
+
+    def _value_handle(self, dev):
+        return _kept_value(self, dev)
 
     def close(self):
         self._handle.close()
@@ -962,3 +1006,43 @@ def simulate(mechanism, tend_or_storage, controller, record=True, z0=None, fric=
     out = Storage(steps, nb, z0.shape[0], traj if record else np.zeros((z0.shape[0], 0, nb, 13)), status, zT)
     out.score = scores
     return out
+
+
+def predicted_cost(mechanism, controller, z0, first_instance=0, out=None):
+    """V_i = Δz_i' P Δz_i: the cost the controller's gains were designed to achieve from the start z0[i] -- P the cost-to-go of its recursion (lqr.jl:170), Δz_i the
+    error of lqr.jl:92-103 of z0[i] about the controller's setpoint.  The realised cost of a run, Jx + Ju of simulate(..., score=Score(Q, R)), over this is 1 inside
+    the linear regime.  controller: an LQR, PlantLQR or LQRSweep built with keep_value=True; instance i reads table first_instance + i of the batched ones.
+    z0 [n_inst][nb][13]: a numpy array -> a numpy array [n_inst]; or a float64 device tensor, read in place -> a device tensor [n_inst] (out: the tensor to fill),
+    the evaluation left running on the current stream."""
+    if not hasattr(controller, "_value_handle"):
+        raise TypeError("predicted_cost takes an LQR, PlantLQR or LQRSweep built with keep_value=True")
+    if controller.mechanism is not mechanism:
+        raise ValueError("the controller was made for another mechanism")
+    import torch
+    nb = len(mechanism.bodies)
+    dev = _device_mech(mechanism)
+    on_dev = _is_device_tensor(z0)
+    if on_dev:
+        if z0.dtype != torch.float64 or not z0.is_contiguous() or z0.numel() % (13 * nb):
+            raise ValueError("a device z0 must be a contiguous float64 tensor [n_inst][%d][13]" % nb)
+        dz = z0
+    else:
+        dz = torch.from_numpy(np.ascontiguousarray(z0, dtype=np.float64).reshape(-1, nb, 13)).to(torch.device("cuda", torch.cuda.current_device()))
+    n = dz.numel() // (13 * nb)
+    if out is None:
+        out = torch.empty(n, dtype=torch.float64, device=dz.device)
+    elif not _is_device_tensor(out) or out.dtype != torch.float64 or not out.is_contiguous() or out.numel() != n:
+        raise ValueError("out must be a contiguous float64 device tensor of %d entries" % n)
+    value, own_value = controller._value_handle(dev)
+    ctrl = None
+    try:
+        ctrl = controller._ctrl_handle(dev)
+        _capi.value_eval(dev, ctrl, value, n, dz.data_ptr(), out.data_ptr(), torch.cuda.current_stream().cuda_stream, first_instance=first_instance)
+        if not on_dev or own_value or not isinstance(ctrl, _BorrowedCtrl):
+            torch.cuda.current_stream().synchronize()      # the handles made for this call are released below
+    finally:
+        if ctrl is not None:
+            ctrl.close()
+        if own_value:
+            value.close()
+    return out if on_dev else out.cpu().numpy()

@@ -44,7 +44,10 @@ extern "C" {
  * Still 202 (additive, no struct changed): scoring a rollout on the device -- the opaque cclqr_score with cclqr_score_create / cclqr_score_destroy, and cclqr_rollout_score;
  * looked up the same way.
  * Still 202 (additive, no struct changed): one (Q, R) per problem / controller table -- cclqr_riccati_weights and cclqr_ctrl_create_lqr_batch_weights; looked up the
- * same way.  With n_weights = 1 they ARE cclqr_riccati_ex and cclqr_ctrl_create_lqr_batch_plants (which call them). */
+ * same way.  With n_weights = 1 they ARE cclqr_riccati_ex and cclqr_ctrl_create_lqr_batch_plants (which call them).
+ * Still 202 (additive, no struct changed): the cost-to-go of the recursion and the cost it predicts -- cclqr_riccati_value, cclqr_ctrl_create_lqr_batch_value, the
+ * opaque cclqr_value with cclqr_value_create / cclqr_value_get / cclqr_value_destroy, and cclqr_value_eval; looked up the same way.  With P = NULL / value = NULL the
+ * first two ARE cclqr_riccati_weights, cclqr_riccati_tv and cclqr_ctrl_create_lqr_batch_weights (which call them). */
 #define CCLQR_ABI_VERSION 202
 
 #define CCLQR_REVOLUTE 0      /* EqualityConstraint(Revolute(a, b, axis; p1, p2, qoffset)),  examples/lqr_cartpole.jl:26 */
@@ -209,6 +212,18 @@ int cclqr_riccati_weights(int32_t nprob, int32_t mx, int32_t mu, int32_t ml, con
                           int32_t n_weights, const double *Q, const double *R, int32_t N, double tol, double *K, int32_t *kbreak,
                           const cclqr_riccati_opts *opts);
 
+/* cclqr_riccati_weights that also returns the cost-to-go -- the Pkp1 of src/control/lqr.jl:170, which dlqr (lqr.jl:141-184) computes at every backward step and
+ * does not return.  P [nprob][mx][mx] (host) receives, per problem, the Pkp1 of the last backward step the problem executed: the step the break test of lqr.jl:172
+ * fired on, step 1 when it never fired, Q_p when N = 1 (no step runs).  Row-major as the recursion holds it, in the order of the models and of Q; not symmetrised
+ * when a Q or R is not symmetric.  V(dz) = dz' P dz is the cost the gains achieve on the linear model from the error dz -- the Lyapunov function of the closed loop
+ * and the terminal weight of a receding-horizon caller.  A problem that ends CCLQR_ESINGULAR leaves its P unspecified.
+ * time_varying != 0: the per-knot models of lqr_tracking.jl:73-122 as cclqr_riccati_tv takes them -- A [nprob][N-1][mx][mx], Bu, Bl, G alike, knot k at index
+ * k - 1 (N >= 2) -- and P is the Pkp1 of lqr_tracking.jl:108.  P = NULL: nothing is emitted, and K, kbreak are bitwise those of the same call with P; with
+ * time_varying = 0 that IS cclqr_riccati_weights, with time_varying != 0, nprob = 1, n_weights = 1 and opts = NULL it IS cclqr_riccati_tv. */
+int cclqr_riccati_value(int32_t nprob, int32_t mx, int32_t mu, int32_t ml, const double *A, const double *Bu, const double *Bl, const double *G,
+                        int32_t n_weights, const double *Q, const double *R, int32_t N, double tol, int32_t time_varying, double *K, double *P, int32_t *kbreak,
+                        const cclqr_riccati_opts *opts);
+
 /* Device workspaces of the host-pointer entry points (cclqr_linearize, cclqr_riccati*, cclqr_rollout) are cached per calling thread, on
  * the device that thread was on when they were allocated, and reused by the next call; after cclqr_set_device to another GPU the next
  * call releases them there and starts a cache on the new device.  This returns them to the driver (they are re-allocated on demand);
@@ -360,6 +375,33 @@ int cclqr_ctrl_create_lqr_batch_plants(const cclqr_mech *m, const cclqr_plants *
 int cclqr_ctrl_create_lqr_batch_weights(const cclqr_mech *m, const cclqr_plants *plants, int64_t first_plant, int32_t n_ctrl, const double *zd, int32_t mu,
                                         const int32_t *ctrl_joint, const double *Fd, int32_t n_weights, const double *Q, const double *R, int32_t N,
                                         int32_t infinite_horizon, double tol, int32_t *kbreak, cclqr_ctrl **out);
+
+/* The cost-to-go of a controller's tables as a device object, and the cost it predicts (additive, still 202, no struct changed; looked up by name like the entries
+ * above).  The reference's LQR(...) (src/control/lqr.jl:49-66) keeps the gains of dlqr (lqr.jl:141-184) and drops the Pkp1 of lqr.jl:170 they were derived from;
+ * a cclqr_value holds it: n_tables matrices P [12 nb][12 nb] in the caller's body order, row-major, one shared by every instance (n_tables = 1) or one per
+ * controller table. */
+typedef struct cclqr_value cclqr_value;   /* opaque: device-resident cost-to-go tables */
+/* cclqr_ctrl_create_lqr_batch_weights that also keeps every table's cost-to-go (lqr.jl:170; cclqr_riccati_value says which step's) on the device: *value receives
+ * a cclqr_value of n_ctrl tables (8 (12 nb)^2 bytes each: 8192 tables of a 7-body arm are 462 MB).  value = NULL: nothing is kept or allocated -- that IS
+ * cclqr_ctrl_create_lqr_batch_weights.  The controller's gains and kbreak are bitwise the same either way.  On an error neither handle is returned. */
+int cclqr_ctrl_create_lqr_batch_value(const cclqr_mech *m, const cclqr_plants *plants, int64_t first_plant, int32_t n_ctrl, const double *zd, int32_t mu,
+                                      const int32_t *ctrl_joint, const double *Fd, int32_t n_weights, const double *Q, const double *R, int32_t N,
+                                      int32_t infinite_horizon, double tol, int32_t *kbreak, cclqr_ctrl **out, cclqr_value **value);
+/* a cclqr_value from the caller's own matrices -- the P of cclqr_riccati_value on the models of cclqr_linearize (lqr.jl:63, 141-184), or any other quadratic form:
+ * P_host [n_tables][12 nb][12 nb], used as written (symmetric or not).  cclqr_value_get reads table `table` back; CCLQR_EINVAL for n_tables < 1 or a table out of
+ * range. */
+int cclqr_value_create(const cclqr_mech *m, int64_t n_tables, const double *P_host, cclqr_value **out);
+int cclqr_value_get(const cclqr_value *v, int64_t table, double *P_host);
+int cclqr_value_destroy(cclqr_value *v);
+/* out_dev[i] = dz_i' P_t dz_i, the cost the gains were designed to achieve from state i: dz_i is the error of control_lqr! (lqr.jl:92-103: per body x - xd, v - vd,
+ * vec(qd \ q), ω - ωd) of the state at z_dev + i * z_stride ([nb][13], caller's body order; z_stride in doubles, >= 13 nb, so a caller can point into a recorded
+ * slab at any step) about setpoint row 0 of controller table first_instance + i (table 0 when the controller has one), and t = first_instance + i when the value
+ * holds several tables, 0 otherwise.  DEVICE pointers, asynchronous on `stream`.  An instance's result is the same bits whatever n_inst, first_instance or its place
+ * in the batch; a NaN state gives NaN.  realised / predicted -- Jx + Ju of cclqr_rollout_score over this -- measures how far a start lies outside the linear regime.
+ * CCLQR_EINVAL, before anything is launched: a value or controller made for another mechanism or device, n_tables neither 1 nor the controller's table count,
+ * first_instance + n_inst beyond the tables, a controller without a setpoint table, z_stride < 13 nb.  Every topology cclqr_mech_create takes. */
+int cclqr_value_eval(const cclqr_mech *m, const cclqr_ctrl *c, const cclqr_value *v, int64_t n_inst, int64_t first_instance, const double *z_dev,
+                     int64_t z_stride, double *out_dev, void *stream);
 
 /* One TrackingLQR per plant and / or per reference trajectory, in one call -- for every k, TrackingLQR(mechanism_k, storage_k, Fτ_k, eqcids, Q, R)
  * (src/control/lqr_tracking.jl:17-43): linearsystem at the knots 1 .. N-1 of trajectory k (lqr_tracking.jl:88) and the recursion of lqr_tracking.jl:73-122 with its own

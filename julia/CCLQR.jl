@@ -446,6 +446,63 @@ function rollout_score!(h::MechHandle, c::CtrlHandle, s::ScoreHandle, n::Integer
                 h.ptr, c.ptr, s.ptr, n, steps, k0, first_instance, traj, score, stream))
 end
 
+"dlqr_weights that also returns the cost-to-go (cclqr_riccati_value): P[p] is the Pkp1 of lqr.jl:170 at the last backward step problem p executed (the step the
+ break test of lqr.jl:172 fired on, else step 1; Q_p when N = 1), mx x mx as the recursion holds it.  Returns (Ku[p][k][i], P[p], kbreak[p])."
+function dlqr_value(As::Vector, Bus::Vector, Bλs::Vector, Gs::Vector, Qs::Vector, Rs::Vector, N::Integer; tol = 1e-5)
+    np = length(As); mx, mu, ml = size(As[1], 1), size(Bus[1], 2), size(Bλs[1], 2)
+    length(Qs) == length(Rs) || throw(AssertionError("Qs and Rs must hold the same number of weight pairs"))
+    rowmajor(Ms) = reduce(vcat, [vec(permutedims(Matrix{Float64}(M))) for M in Ms]; init = Float64[])
+    K = zeros(mx * mu * max(N - 1, 0) * np); P = zeros(mx * mx * np); kb = zeros(Int32, np)
+    check(ccall((:cclqr_riccati_value, lib), Cint,
+                (Int32, Int32, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}, Int32, Float64, Int32,
+                 Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Cvoid}),
+                np, mx, mu, ml, rowmajor(As), rowmajor(Bus), rowmajor(Bλs), rowmajor(Gs), Int32(length(Qs)), rowmajor(Qs), rowmajor(Rs), N, tol, Int32(0), K, P, kb, C_NULL))
+    K4 = reshape(K, mx, mu, max(N - 1, 0), np)                       # C layout [np][N-1][mu][mx]
+    P3 = reshape(P, mx, mx, np)                                      # C layout [np][mx][mx]: row-major, so transposed here
+    [[[reshape(K4[:, i, k, p], 1, mx) for i = 1:mu] for k = 1:N-1] for p = 1:np], [permutedims(P3[:, :, p]) for p = 1:np], Int.(kb)
+end
+
+"The cost-to-go tables of a controller on the device (cclqr_value_create: P is 12Nb x 12Nb x n_tables, table t TRANSPOSED into Julia's column-major order, i.e.
+ P[:, :, t] = P_t'; or the handle lqr_batch_value returns)."
+mutable struct ValueHandle
+    ptr::Ptr{Cvoid}
+    mech::MechHandle
+end
+function value_create(h::MechHandle, P::Array{Float64,3})
+    out = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:cclqr_value_create, lib), Cint, (Ptr{Cvoid}, Int64, Ptr{Float64}, Ref{Ptr{Cvoid}}), h.ptr, size(P, 3), P, out))
+    obj = ValueHandle(out[], h)
+    finalizer(o -> ccall((:cclqr_value_destroy, lib), Cint, (Ptr{Cvoid},), o.ptr), obj)
+    obj
+end
+"table `table` (0-based) of a ValueHandle read back (cclqr_value_get), as the matrix P of lqr.jl:170"
+function value_get(v::ValueHandle, table::Integer, mx::Integer)
+    P = zeros(mx, mx)
+    check(ccall((:cclqr_value_get, lib), Cint, (Ptr{Cvoid}, Int64, Ptr{Float64}), v.ptr, table, P))
+    permutedims(P)
+end
+"lqr_batch_weights that also keeps every table's cost-to-go on the device (cclqr_ctrl_create_lqr_batch_value).  Returns (controller pointer, kbreak, ValueHandle)."
+function lqr_batch_value(h::MechHandle, p::Union{PlantsHandle,Nothing}, n::Int, zd::Array{Float64}, ctrl_joint::Vector{Int32}, n_weights::Int, Q::Vector{Float64},
+                         R::Vector{Float64}, N::Int; Fd = nothing, first_plant = 0, tol = 1e-5, infinite_horizon = false)
+    out = Ref{Ptr{Cvoid}}(C_NULL); val = Ref{Ptr{Cvoid}}(C_NULL); kb = zeros(Int32, n)
+    fd = Fd === nothing ? Ptr{Float64}(C_NULL) : pointer(Fd)
+    GC.@preserve Fd check(ccall((:cclqr_ctrl_create_lqr_batch_value, lib), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int32, Ptr{Float64}, Int32, Ptr{Int32}, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}, Int32, Int32, Float64, Ptr{Int32},
+                 Ref{Ptr{Cvoid}}, Ref{Ptr{Cvoid}}),
+                h.ptr, p === nothing ? C_NULL : p.ptr, first_plant, Int32(n), zd, Int32(length(ctrl_joint)), ctrl_joint, fd, Int32(n_weights), Q, R, Int32(N),
+                Int32(infinite_horizon ? 1 : 0), tol, kb, out, val))
+    obj = ValueHandle(val[], h)
+    finalizer(o -> ccall((:cclqr_value_destroy, lib), Cint, (Ptr{Cvoid},), o.ptr), obj)
+    return out[], kb, obj
+end
+"V_i = Δz_i' P_t Δz_i for n states on the device (cclqr_value_eval; device pointers, asynchronous on `stream`): state i at z + 8 i z_stride bytes (z_stride >= 13 Nb
+ doubles), the error of lqr.jl:92-103 about setpoint row 1 of controller table first_instance + i."
+function value_eval!(h::MechHandle, c::CtrlHandle, v::ValueHandle, n::Integer, z::Ptr{Float64}, out::Ptr{Float64}; first_instance = 0, z_stride = 13 * h.nb,
+                     stream::Ptr{Cvoid} = C_NULL)
+    check(ccall((:cclqr_value_eval, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Cvoid}),
+                h.ptr, c.ptr, v.ptr, n, first_instance, z, z_stride, out, stream))
+end
+
 "Size the controller handle's Philox workspace before step-per-launch rollouts are captured into a hipGraph (cclqr_ctrl_reserve_noise)."
 reserve_noise!(c::CtrlHandle, n::Integer, steps::Integer) = check(ccall((:cclqr_ctrl_reserve_noise, lib), Cint, (Ptr{Cvoid}, Int64, Int32), c.ptr, n, steps))
 
