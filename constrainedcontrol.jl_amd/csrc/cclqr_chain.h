@@ -456,6 +456,18 @@ HD void ck_schur_rows(const LinkC& c, int j, bool store, const Lay& Y, double* L
     }
 }
 
+// ---- will a solve read the Schur rows of this full-step trial?  Asked once the trial's ||f|| (nrm) is known, in front of the row block, by the
+// kernels that split the rows and by the tree kernel.  rows: the caller's own prediction (the instance is not done, and was not in its last
+// iteration already); nf0: ||f|| of the point the step started from; nd: the step's norm; eps: the stopping tolerance.  The rows are read in one
+// case only, the trial accepted at full step and the instance going on, so they are dead if
+//   - the trial is rejected (nrm > nf0): the line search takes a shorter step and the accepted point is evaluated again, which overwrites them;
+//   - the instance is done with this trial (nrm < eps and nd < eps, the stopping rule at alpha = 1).
+// Written with the negations of the accept sequence, so that a NaN norm builds (harmless: that instance stops).  An evaluation at an accepted
+// point passes nf0 = nd = + infinity, which leaves `rows` as it is.  tests/emu/emu_chain_rows_verdict.cpp runs the same function.
+HD bool chain_rows_verdict(bool rows, double nrm, double nf0, double nd, double eps) {
+    return rows && !(nrm > nf0) && !(nrm < eps && nd < eps);
+}
+
 // ---- the same rows SPLIT BY BLOCK between the link's lane and the idle lane sixteen above it: the 32-lane kernels whose lane group holds at most 17
 // links (NBP 16, 17).  ck_schur_rows is bound by the LDS instructions every lane issues, whatever the lane keeps of them, and lanes 16 .. 31 keep
 // nothing.  So the one instruction stream builds TWO blocks, not three:

@@ -97,6 +97,18 @@ __device__ __forceinline__ void from_row_below(double* v, bool keep) {
         v[i] = __hiloint2double((int)hi, (int)lo);
     }
 }
+// group_sum<32> with the two DPP rows of a group combined by the same swap instead of a ds_bpermute: the sum whose result a BRANCH waits for (the
+// norm in front of the row block, chain_eval) pays no LDS round trip and no drain of the LDS queue.  The two results of the swap are the sums of
+// the group's even and odd row on every lane, where group_sum adds own + other: the same two addends, in either order -- the same bits.
+__device__ __forceinline__ double group_sum_rows32(double v) {
+    v += dpp_row_ror<8>(v);
+    v += dpp_row_ror<4>(v);
+    v += dpp_row_ror<2>(v);
+    v += dpp_row_ror<1>(v);
+    const auto lo = swap_rows_b32((unsigned)__double2loint(v), (unsigned)__double2loint(v));
+    const auto hi = swap_rows_b32((unsigned)__double2hiint(v), (unsigned)__double2hiint(v));
+    return __hiloint2double((int)hi[0], (int)lo[0]) + __hiloint2double((int)hi[1], (int)lo[1]);
+}
 // which kernels split the rows, and whether link 0 is without a helper (17 links: lane 16 owns the leaf)
 template <int G, int NBP, int KL> struct SchurSplit { static const bool ON = G == 32 && NBP <= 17 && KL == 1, R0 = NBP == 17; };
 // once per launch: the helper lanes' flags and scale (schur_split_helper).  M->childl is read at an index below 16.
@@ -128,9 +140,14 @@ __device__ __forceinline__ void schur_split_take(const LinkC& c, int t, double (
 // and builds their Schur rows, the body's share of the norm comes from the primary sub-lane alone.  KL = 1: the code of rounds 2-4, unchanged.
 // SP: the Schur rows are split by block with the lanes sixteen above (1; 2 = in a 17-link group: SchurSplit); inst_on: the lane's instance is evaluated
 // (`active` without the lane's own link: what a helper lane stores by).
+// SP != 0 only: the norm is formed IN FRONT of the row block, and the lane's `rows` is narrowed by it before the vote (cclqr_chain.h chain_rows_verdict:
+// nf0, nd = ||f|| of the point the step started from and the step's norm; + infinity at an accepted point) -- a trial that is rejected, or that ends
+// its instance's solve, builds no rows unless the wavefront's other instance needs its own.  The group sum is the same on all 32 lanes of a group, so
+// the helper lanes vote as their links' lanes do.  DINV is stored before the norm exists and goes by the caller's `rows`, as jac_ok does there.
 template <int G, bool JAC, int KL = 1, int SP = 0>
-__device__ __forceinline__ double chain_eval(LinkC& c, LinkS& S, int t, const Lay& Y, double* L, double alpha, bool active, bool inst_on, bool rows, double dt, const SubSel& Q PROF_ARG) {
-    double part = 0.0;
+__device__ __forceinline__ double chain_eval(LinkC& c, LinkS& S, int t, const Lay& Y, double* L, double alpha, bool active, bool inst_on, bool rows, double nf0, double nd, double dt,
+                                             const SubSel& Q PROF_ARG) {
+    double part = 0.0, nrm = 0.0;
     double NB[9], g[5], xq[7];
     const bool store_dinv = JAC && __any(rows);
     LINK_FLAGS_FRESH(c);
@@ -203,6 +220,12 @@ __device__ __forceinline__ double chain_eval(LinkC& c, LinkS& S, int t, const La
         }
         STAMP(PF_EVAL_JOINT);
         LINK_FLAGS_FRESH(c);
+        if constexpr (JAC && SP != 0) {
+            static_assert(G == 32, "the rows are split in 32-lane groups");
+            nrm = sqrt(group_sum_rows32(part));
+            rows = chain_rows_verdict(rows, nrm, nf0, nd, NEWTON_EPS);
+            STAMP(PF_EVAL_MAP);
+        }
         if (JAC) {
             if (__any(rows)) {
                 double pd[6];
@@ -219,7 +242,7 @@ __device__ __forceinline__ double chain_eval(LinkC& c, LinkS& S, int t, const La
             STAMP(PF_SCHUR_S);
         }
     }
-    const double nrm = sqrt(group_sum<G>(part));
+    if constexpr (!(JAC && SP != 0)) nrm = sqrt(group_sum<G>(part));
     STAMP(PF_EVAL_MAP);
     PCOUNT(PF_EVALS);
     return nrm;
@@ -561,7 +584,7 @@ __global__ __launch_bounds__(WAVE_BLOCK) void rollout_chain_kernel(RolloutArgs a
         bool need_jac = !done;
         for (int iter = 1; iter <= NEWTON_MAXIT; iter++) {
             if (__any(need_jac)) {
-                const double nf = chain_eval<G, true, KL, SP>(c, S, tl, Y, L, 0.0, c.live() && need_jac, need_jac, need_jac, dt, Q PROF_PASS);
+                const double nf = chain_eval<G, true, KL, SP>(c, S, tl, Y, L, 0.0, c.live() && need_jac, need_jac, need_jac, __builtin_huge_val(), __builtin_huge_val(), dt, Q PROF_PASS);
                 if (iter == 1) normf0 = nf;
             }
             WAVE_HANDOVER();
@@ -679,11 +702,14 @@ __global__ __launch_bounds__(WAVE_BLOCK) void rollout_chain_kernel(RolloutArgs a
             // every instance of the wavefront that still solves is there, the trial builds none (same code for the residual: the same ||f||); one that
             // goes on after all gets its rows from the evaluation at the top of the next iteration (jac_ok).  (A weaker predictor, ||f|| < eps alone
             // with a residual-only trial, fires in iterations that are not the last: priced in round 3 at 0.5 % of a step, DESIGN_HISTORY.)
+            // The kernels that split the rows (SP != 0) ask again inside the trial, once its ||f|| exists (chain_eval, chain_rows_verdict): no rows either for a
+            // trial that ends its instance's solve or whose full step is rejected.  jac_ok and DINV go by the predictor here all the same: an instance
+            // that is done reads neither, and a rejected full step sets jac_ok = false below.
             double alpha = 1.0, normf1 = 0.0;
             const bool want_rows = !done && !(normf0 < NEWTON_EPS && nd < NEWTON_EPS);
             bool ls_done = done, jac_ok = __any(want_rows);
             {
-                const double nf = chain_eval<G, true, KL, SP>(c, S, tl, Y, L, 1.0, active, !done, want_rows, dt, Q PROF_PASS);
+                const double nf = chain_eval<G, true, KL, SP>(c, S, tl, Y, L, 1.0, active, !done, want_rows, normf0, nd, dt, Q PROF_PASS);
                 if (!ls_done) {
                     normf1 = nf;
                     if (!(normf1 > normf0)) ls_done = true;

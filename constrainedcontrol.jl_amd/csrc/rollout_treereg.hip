@@ -51,11 +51,15 @@ __device__ __forceinline__ void load_rec(TrRec& K, const TrRec* p) {
 }
 
 // residual (+ Jacobians when JAC) at the point s - alpha ds with constraint forces C - alpha cd; returns the group's ||f||_2.
-// With JAC the Schur complement rows of the point go straight to LDS (tr_schur_rows).
+// With JAC the Schur complement rows of the point go straight to LDS (tr_schur_rows) -- if a solve may read them: the norm is formed in front of
+// the row block and decides it (cclqr_chain.h chain_rows_verdict, as in the chain kernels that split the rows).  rows: the lane's instance is
+// evaluated; nf0, nd: ||f|| of the point the step started from and the step's norm (+ infinity at an accepted point: the rows are built).  The rows
+// are wavefront-wide work, so they are built unless NO lane says so.  DINV is stored either way, and the caller's jac_ok does not change: an
+// instance that goes on at full step has voted for its rows, one that does not never reads them.
 template <int G, bool JAC>
 __device__ __forceinline__ double tree_eval(LinkC& c, const TreeL& T, LinkS& S, int t, int pa4, int maxchild, int maxsib, const Lay& Y, double* L, double alpha,
-                                            bool active, double dt PROF_ARG) {
-    double part = 0.0;
+                                            bool active, bool rows, double nf0, double nd, double dt PROF_ARG) {
+    double part = 0.0, nrm = 0.0;
     double NB[9], g[5], xq[7];
     LINK_FLAGS_FRESH(c);
 #pragma unroll
@@ -88,14 +92,21 @@ __device__ __forceinline__ double tree_eval(LinkC& c, const TreeL& T, LinkS& S, 
     }
     STAMP(PF_EVAL_JOINT);
     LINK_FLAGS_FRESH(c);
-    if (JAC) {
-        double pd[6];
-        from_lane<6>(S.d, pd, pa4);
-        tr_schur_rows(c, T, t, active, maxchild, maxsib, Y, L, wXT, wPB, wPA, g, S.d, pd);
+    if constexpr (JAC) {
+        nrm = sqrt(group_sum<G>(part));
+        STAMP(PF_EVAL_MAP);
+        if (__any(chain_rows_verdict(rows, nrm, nf0, nd, NEWTON_EPS))) {
+            double pd[6];
+            from_lane<6>(S.d, pd, pa4);
+            tr_schur_rows(c, T, t, active, maxchild, maxsib, Y, L, wXT, wPB, wPA, g, S.d, pd);
+        } else {
+            PCOUNT(PF_ROWS_SKIPPED);
+        }
         STAMP(PF_SCHUR_S);
+    } else {
+        nrm = sqrt(group_sum<G>(part));
+        STAMP(PF_EVAL_MAP);
     }
-    const double nrm = sqrt(group_sum<G>(part));
-    STAMP(PF_EVAL_MAP);
     PCOUNT(PF_EVALS);
     return nrm;
 }
@@ -332,7 +343,7 @@ __global__ __launch_bounds__(64) void rollout_treereg_kernel(RolloutArgs a) {
         const bool go = c.valid() && !c.dead();
         bool done = !go, failed = false;
         int its = 0;
-        double normf0 = tree_eval<G, true>(c, T, S, t, pa4, maxchild, maxsib, Y, L, 0.0, c.live() && !done, dt PROF_PASS);
+        double normf0 = tree_eval<G, true>(c, T, S, t, pa4, maxchild, maxsib, Y, L, 0.0, c.live() && !done, !done, __builtin_huge_val(), __builtin_huge_val(), dt PROF_PASS);
         __syncthreads();
         const int ne_steps = R->ne_steps, nb_steps = R->nb_steps;
         for (int iter = 1; iter <= NEWTON_MAXIT; iter++) {
@@ -390,7 +401,7 @@ __global__ __launch_bounds__(64) void rollout_treereg_kernel(RolloutArgs a) {
             double alpha = 1.0, normf1 = 0.0;
             bool ls_done = done, jac_ok = true;
             {
-                const double nf = tree_eval<G, true>(c, T, S, t, pa4, maxchild, maxsib, Y, L, 1.0, active, dt PROF_PASS);
+                const double nf = tree_eval<G, true>(c, T, S, t, pa4, maxchild, maxsib, Y, L, 1.0, active, !done, normf0, nd, dt PROF_PASS);
                 if (!ls_done) {
                     normf1 = nf;
                     if (!(normf1 > normf0)) ls_done = true;
@@ -440,7 +451,7 @@ __global__ __launch_bounds__(64) void rollout_treereg_kernel(RolloutArgs a) {
                 for (int lv = 1; lv <= LINE_MAXIT; lv++) {
                     if (!__any(!ls_done)) break;
                     const double a_l = ldexp(1.0, -lv);
-                    const double nf = tree_eval<G, false>(c, T, S, t, pa4, maxchild, maxsib, Y, L, a_l, c.live() && !ls_done, dt PROF_PASS);
+                    const double nf = tree_eval<G, false>(c, T, S, t, pa4, maxchild, maxsib, Y, L, a_l, c.live() && !ls_done, false, 0.0, 0.0, dt PROF_PASS);
                     if (!ls_done) {
                         normf1 = nf; alpha = a_l; jac_ok = false;
                         if (!(nf > normf0) || lv == LINE_MAXIT) ls_done = true;
@@ -463,7 +474,7 @@ __global__ __launch_bounds__(64) void rollout_treereg_kernel(RolloutArgs a) {
                 need_jac = !done && !jac_ok;
             }
             STAMP(PF_ACCEPT);
-            if (__any(need_jac)) tree_eval<G, true>(c, T, S, t, pa4, maxchild, maxsib, Y, L, 0.0, c.live() && need_jac, dt PROF_PASS);
+            if (__any(need_jac)) tree_eval<G, true>(c, T, S, t, pa4, maxchild, maxsib, Y, L, 0.0, c.live() && need_jac, need_jac, __builtin_huge_val(), __builtin_huge_val(), dt PROF_PASS);
             __syncthreads();
         }
         const bool conv = done && !failed;
@@ -522,6 +533,9 @@ __global__ __launch_bounds__(64) void rollout_treereg_kernel(RolloutArgs a) {
 #ifdef CCLQR_PROFILE
 extern "C" int cclqr_prof_read_treereg(unsigned long long* out, int reset) {
     return prof_read(out, PF_READ_N, reset);
+}
+extern "C" int cclqr_prof_read_treereg_n(unsigned long long* out, int cap, int reset) {      // (up to cap words: PF_ROWS_SKIPPED is word 16)
+    return prof_read(out, cap, reset);
 }
 #endif
 
