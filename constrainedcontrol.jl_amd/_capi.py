@@ -20,7 +20,8 @@ EXPORTS = ["cclqr_last_error", "cclqr_version", "cclqr_device_count", "cclqr_set
            "cclqr_plants_create", "cclqr_plants_destroy", "cclqr_rollout_plants", "cclqr_linearize_plants", "cclqr_ctrl_create_lqr_batch_plants",
            "cclqr_ctrl_create_tracking_batch_plants", "cclqr_ctrl_get_gains", "cclqr_score_create", "cclqr_score_destroy", "cclqr_rollout_score",
            "cclqr_riccati_weights", "cclqr_ctrl_create_lqr_batch_weights",
-           "cclqr_riccati_value", "cclqr_ctrl_create_lqr_batch_value", "cclqr_value_create", "cclqr_value_get", "cclqr_value_destroy", "cclqr_value_eval"]
+           "cclqr_riccati_value", "cclqr_ctrl_create_lqr_batch_value", "cclqr_value_create", "cclqr_value_get", "cclqr_value_destroy", "cclqr_value_eval",
+           "cclqr_policy_value", "cclqr_value_create_policy"]
 ABI_VERSION = 202     # include/cclqr.h CCLQR_ABI_VERSION: the structs below mirror that header (verified field by field against cclqr_abi_layout at load time)
 ROLLOUT_NO_ALLOC = 1  # cclqr_rollout_opts.flags: the call may neither allocate nor synchronise (a hipGraph capture is open on the device)
 ROLLOUT_CARRY_STATUS = 4  # ... `status` is read and written: an instance lost in an earlier launch stays frozen, the others merge this launch's result into it
@@ -717,6 +718,62 @@ def riccati_value(A, Bu, Bl, G, Q, R, N, tol=1e-5, path=0, bf16_terms=0, keep_la
                                     C.c_int32(nw), _d(Q), _d(R), C.c_int32(int(N)), C.c_double(float(tol)), C.c_int32(1 if time_varying else 0), _d(K), _d(P), _i(kb),
                                     C.byref(o)))
     return K, P, kb
+
+
+def policy_value(A, Bu, Bl, G, K, Q, R, N, tol=1e-5, path=0, bf16_terms=0, want_diag=True):
+    """batched policy evaluation (cclqr_policy_value): dlqr's cost recursion (lqr.jl:147-177) with the gains given.  A [nprob][mx][mx] (or [mx][mx]), Bu, Bl, G per
+    problem; K [nK][mu][mx] (one table shared by all) or [n_gains][nK][mu][mx] with n_gains = nprob, nK = 1 (a stationary gain) or N - 1; Q [n_weights][mx][mx],
+    R [n_weights][mu][mu] with n_weights = 1 or nprob (the library refuses any other count) -> P [nprob][mx][mx], kbreak [nprob], dnorm [nprob][2] (the norm(Pk - Pkp1)
+    of the last executed step and of the step before it; NaN where no such step ran).  path: 0 auto / 1 resident / 2 tiled.  want_diag=False passes kbreak = dnorm =
+    NULL (both are returned as None)"""
+    A = f64(A)
+    mx = A.shape[-1]
+    A = A.reshape(-1, mx, mx)
+    nprob = A.shape[0]
+    Bu, Bl = f64(Bu), f64(Bl)
+    Bu = Bu.reshape(nprob, mx, Bu.shape[-1] if Bu.ndim > 1 else -1)
+    mu = Bu.shape[2]
+    Bl = Bl.reshape(nprob, mx, Bl.shape[-1] if Bl.ndim > 1 else -1)
+    ml = Bl.shape[2]
+    G = f64(G).reshape(nprob, ml, mx)
+    K = f64(K)
+    if K.ndim not in (3, 4) or K.shape[-2:] != (mu, mx):
+        raise ValueError("K must be [nK][mu][mx] or [n_gains][nK][mu][mx] with mu = %d, mx = %d (got %s)" % (mu, mx, K.shape))
+    if K.ndim == 3:
+        K = K[None]
+    n_gains, nK = K.shape[0], K.shape[1]
+    Q = f64(Q).reshape(-1, mx, mx)
+    nw = Q.shape[0]
+    R = f64(R).reshape(nw, mu, mu)
+    P = np.zeros((nprob, mx, mx))
+    kb = np.zeros(nprob, dtype=np.int32) if want_diag else None
+    dn = np.zeros((nprob, 2)) if want_diag else None
+    o = RiccatiOpts(int(path), int(bf16_terms), 0, 0)
+    check(lib().cclqr_policy_value(C.c_int32(nprob), C.c_int32(mx), C.c_int32(mu), C.c_int32(ml), _d(A), _d(Bu) if mu else None, _d(Bl) if ml else None,
+                                   _d(G) if ml else None, C.c_int32(n_gains), C.c_int32(nK), _d(K) if K.size else None, C.c_int32(nw), _d(Q), _d(R) if mu else None,
+                                   C.c_int32(int(N)), C.c_double(float(tol)), _d(P), _i(kb), _d(dn), C.byref(o)))
+    return P, kb, dn
+
+
+def value_create_policy(mech, ctrl, zd, ctrl_joint, Q, R, N, tol=1e-5, Fd=None, plants=None, first_plant=0):
+    """cclqr_value_create_policy: the policy evaluation of controller handle `ctrl` (its device-resident gains: one table, or one per model) on the models linearised at
+    zd [n_models][nb][13], setpoint k on plant first_plant + k of the PlantsHandle `plants` (None: the mechanism's own plant).  Q [n_weights][12 nb][12 nb],
+    R [n_weights][mu][mu], n_weights = 1 or n_models -> (ValueHandle of n_models tables, kbreak [n_models], dnorm [n_models][2])"""
+    nb = mech.tables.nb
+    zd = f64(zd).reshape(-1, nb, 13)
+    n = zd.shape[0]
+    cj = i32(ctrl_joint).reshape(-1)
+    mu = len(cj)
+    Fd = None if Fd is None else f64(Fd).reshape(n, mu)
+    Q = f64(Q).reshape(-1, 12 * nb, 12 * nb)
+    nw = Q.shape[0]
+    R = f64(R).reshape(nw, mu, mu)
+    kb = np.zeros(n, dtype=np.int32)
+    dn = np.zeros((n, 2))
+    vptr = C.c_void_p()
+    check(lib().cclqr_value_create_policy(mech.ptr, None if plants is None else plants.ptr, C.c_int64(int(first_plant)), C.c_int32(n), _d(zd), C.c_int32(mu), _i(cj), _d(Fd),
+                                          ctrl.ptr, C.c_int32(nw), _d(Q), _d(R), C.c_int32(int(N)), C.c_double(float(tol)), _i(kb), _d(dn), C.byref(vptr)))
+    return ValueHandle(mech, ptr=vptr, n_tables=n), kb, dn
 
 
 def riccati_tv(A, Bu, Bl, G, Q, R, N, tol=1e-5):

@@ -1235,3 +1235,134 @@ extern "C" int cclqr_value_eval(const cclqr_mech* m, const cclqr_ctrl* c, const 
     HIPCHK(launch_value(a, (hipStream_t)stream));
     return CCLQR_OK;
 }
+
+// ---- policy evaluation (policy.hip): dlqr's cost recursion (lqr.jl:147-177) with the gains given
+// rows of gain tables from the kernels' link order (a controller's device tables: padded stride between tables) to the caller's body order, packed
+// [n_tables][rows_per_table][12 nb] -- the inverse of k_rows_to_link_order_kernel, out of place: the controller's tables are not touched.  One workgroup per row
+__global__ void k_rows_to_body_order_kernel(const double* K, long long nrows, long long rows_per_table, long long table_stride, int nb, const MechDev* M, double* out) {
+    const long long r = blockIdx.x;
+    if (r >= nrows) return;
+    const double* p = K + (r / rows_per_table) * table_stride + (r % rows_per_table) * 12 * nb;
+    double* o = out + r * 12 * nb;
+    for (int e = threadIdx.x; e < 12 * nb; e += blockDim.x) { const int l = e / 12; o[12 * M->perm[l] + (e - 12 * l)] = p[e]; }
+}
+
+// shared tail of the two entry points: the recursion on device-resident models and gains (dK: tables k_stride doubles apart, 0 = one shared), inside the caller's
+// WsScope.  dP: device [nprob][mx][mx], written by the kernels.  kb, st [nprob] and dn [nprob][2] come back on the host; the caller words the refusals
+static int run_policy(int nprob, int mx, int mu, int ml, int N, double tol, const double* dA, const double* dBu, const double* dBl, const double* dG, const double* dK,
+                      long long k_stride, int nK, int n_weights, const double* Q, const double* R, int path, double* dP, std::vector<int>& kb, std::vector<int>& st,
+                      std::vector<double>& dn) {
+    static const char* const what = "policy evaluation";
+    double *dQ = nullptr, *dR = nullptr, *dwork = nullptr, *ddn = nullptr;
+    int *dkb = nullptr, *dst = nullptr, *dstop = nullptr;
+    const size_t np = (size_t)nprob, nw = (size_t)n_weights;
+    PolArgs a;
+    RicArgs& r = a.r;
+    r.nprob = nprob; r.mx = mx; r.mu = mu; r.ml = ml; r.N = N; r.time_varying = 0; r.tol = tol; r.path = path; r.bf16_terms = 0; r.keep_last = 0; r.K = nullptr;
+    if (n_weights > 1) { r.q_stride = (long long)mx * mx; r.r_stride = (long long)mu * mu; }
+    HIPTRY(what, ws_get((void**)&dQ, nw * mx * mx * sizeof(double)));
+    HIPTRY(what, ws_get((void**)&dR, (nw * mu * mu + 1) * sizeof(double)));
+    HIPTRY(what, ws_get((void**)&dwork, ric_total_work_doubles(r) * sizeof(double)));
+    HIPTRY(what, ws_get((void**)&ddn, 2 * np * sizeof(double)));
+    HIPTRY(what, ws_get((void**)&dstop, np * sizeof(int)));
+    HIPTRY(what, ws_get((void**)&dkb, np * sizeof(int)));
+    HIPTRY(what, ws_get((void**)&dst, np * sizeof(int)));
+    HIPTRY(what, hipMemcpy(dQ, Q, nw * mx * mx * sizeof(double), hipMemcpyHostToDevice));
+    if (mu > 0) HIPTRY(what, hipMemcpy(dR, R, nw * mu * mu * sizeof(double), hipMemcpyHostToDevice));
+    r.stop = dstop; r.A = dA; r.Bu = dBu; r.Bl = dBl; r.G = dG; r.Q = dQ; r.R = dR; r.kbreak = dkb; r.status = dst; r.work = dwork; r.P_out = dP;
+    a.Kin = dK; a.k_stride = k_stride; a.nK = nK; a.dnorm = ddn;
+    HIPTRY(what, launch_policy(a, nullptr));
+    HIPTRY(what, hipDeviceSynchronize());
+    kb.resize(np); st.resize(np); dn.resize(2 * np);
+    HIPTRY(what, hipMemcpy(kb.data(), dkb, np * sizeof(int), hipMemcpyDeviceToHost));
+    HIPTRY(what, hipMemcpy(st.data(), dst, np * sizeof(int), hipMemcpyDeviceToHost));
+    HIPTRY(what, hipMemcpy(dn.data(), ddn, 2 * np * sizeof(double), hipMemcpyDeviceToHost));
+    return CCLQR_OK;
+}
+// what both entry points refuse about the recursion's own sizes, before anything is allocated or launched
+static int policy_check(int nprob, int mu, int N, int nK, int n_weights, const char* of) {
+    if (N > 1 && mu > 0 && nK != 1 && nK != N - 1)
+        return fail(CCLQR_EINVAL, "nK = " + std::to_string(nK) + ": a gain table holds one row (a stationary gain) or N - 1 = " + std::to_string(N - 1) + " rows, one per backward step");
+    return check_n_weights(n_weights, nprob, of);
+}
+
+extern "C" int cclqr_policy_value(int32_t nprob, int32_t mx, int32_t mu, int32_t ml, const double* A, const double* Bu, const double* Bl, const double* G,
+                                  int32_t n_gains, int32_t nK, const double* K, int32_t n_weights, const double* Q, const double* R, int32_t N, double tol,
+                                  double* P, int32_t* kbreak, double* dnorm, const cclqr_riccati_opts* opts) {
+    if (!A || !Q || !P || (mu > 0 && (!Bu || !R)) || (ml > 0 && (!Bl || !G)) || (mu > 0 && N > 1 && !K)) return fail(CCLQR_EINVAL, "null argument");
+    if (nprob < 1 || mx < 1 || mu < 0 || ml < 0 || N < 1) return fail(CCLQR_EINVAL, "bad sizes");
+    if (n_gains != 1 && n_gains != nprob)
+        return fail(CCLQR_EINVAL, "n_gains = " + std::to_string(n_gains) + ": the gains are one table shared by all (1) or one table per problem (" + std::to_string(nprob) + ")");
+    TRY(policy_check(nprob, mu, N, nK, n_weights, "problem"));
+    const int path = opts ? opts->path : 0;
+    if (path < 0 || path > 2) return fail(CCLQR_EINVAL, "policy evaluation options: path in 0..2");
+    if (opts && opts->bf16_terms != 0) return fail(CCLQR_EINVAL, "policy evaluation runs in fp64 only (bf16_terms = 0)");
+    WsScope scope;
+    RicModels d = {};
+    TRY(upload_models((size_t)nprob, mx, mu, ml, A, Bu, Bl, G, d));
+    const size_t nKd = (mu > 0 && N > 1) ? (size_t)n_gains * nK * mu * mx : 0, nP = (size_t)nprob * mx * mx;
+    double *dK = nullptr, *dP = nullptr;
+    HIPTRY("policy evaluation", ws_get((void**)&dK, (nKd + 1) * sizeof(double)));
+    HIPTRY("policy evaluation", ws_get((void**)&dP, nP * sizeof(double)));
+    if (nKd) HIPTRY("policy evaluation", hipMemcpy(dK, K, nKd * sizeof(double), hipMemcpyHostToDevice));
+    std::vector<int> kb, st;
+    std::vector<double> dn;
+    TRY(run_policy(nprob, mx, mu, ml, N, tol, d.A, d.Bu, d.Bl, d.G, dK, n_gains > 1 ? (long long)nK * mu * mx : 0, nK, n_weights, Q, R, path, dP, kb, st, dn));
+    HIPTRY("policy evaluation", hipMemcpy(P, dP, nP * sizeof(double), hipMemcpyDeviceToHost));
+    for (int p = 0; p < nprob; p++) {      // kbreak and dnorm are filled up to the problem the call is refused for
+        if (kbreak) kbreak[p] = kb[p];
+        if (dnorm) { dnorm[2 * p] = dn[2 * (size_t)p]; dnorm[2 * p + 1] = dn[2 * (size_t)p + 1]; }
+        if (st[p] != 0) return fail(CCLQR_ESINGULAR, "G*Bl is singular in problem " + std::to_string(p));
+    }
+    return CCLQR_OK;
+}
+
+extern "C" int cclqr_value_create_policy(const cclqr_mech* m, const cclqr_plants* plants, int64_t first_plant, int32_t n_models, const double* zd, int32_t mu,
+                                         const int32_t* ctrl_joint, const double* Fd, const cclqr_ctrl* c, int32_t n_weights, const double* Q, const double* R,
+                                         int32_t N, double tol, int32_t* kbreak, double* dnorm, cclqr_value** out) {
+    static const char* const what = "policy evaluation";
+    if (!m || !zd || !c || !Q || !out || (mu > 0 && (!ctrl_joint || !R))) return fail(CCLQR_EINVAL, "null argument");
+    TRY(check_device(m));
+    if (m->host.loop) return fail(CCLQR_EUNSUPPORTED, "policy evaluation is for tree mechanisms (closed loops have no multiplier model to evaluate a gain on)");
+    if (c->nb != m->nb || c->device != m->device) return fail(CCLQR_EINVAL, "the controller was created for another mechanism or device");
+    if (n_models < 1 || N < 1 || mu < 1 || mu > m->nb) return fail(CCLQR_EINVAL, "bad sizes");
+    const CtrlDev& H = c->host;
+    if (!c->K_dev || H.nK < 1) return fail(CCLQR_EINVAL, "the controller has no gains (open loop / PID)");
+    if (H.nsp > 1) return fail(CCLQR_EUNSUPPORTED, "tracking controllers (more than one setpoint row per table) are outside policy evaluation's scope: time-invariant models only");
+    int cj[CCLQR_MAXL];
+    TRY(linearize_check(m, plants, first_plant, n_models, mu, ctrl_joint, cj));      // the refusals of cclqr_linearize_plants
+    bool same = mu == H.mu;
+    for (int i = 0; same && i < mu; i++) same = cj[i] == H.cj[i];
+    if (!same) return fail(CCLQR_EINVAL, "mu / ctrl_joint are not the controller's: its gains act on other joints");
+    const int64_t tables = H.n_ctrl > 1 ? H.n_ctrl : 1;
+    if (tables != 1 && tables != n_models)
+        return fail(CCLQR_EINVAL, "the controller holds " + std::to_string(tables) + " tables: one shared by all models (1) or one per model (" + std::to_string(n_models) + ")");
+    if (H.nK > 1 && N != H.nK + 1)
+        return fail(CCLQR_EINVAL, "the controller's tables hold " + std::to_string(H.nK) + " rows, one per backward step: N must be " + std::to_string(H.nK + 1) + " (got " + std::to_string(N) + ")");
+    TRY(policy_check(n_models, mu, N, H.nK, n_weights, "model"));
+    const int nb = m->nb, mx = 12 * nb, ml = 5 * nb;
+    ValueOwner vown(value_new(m, n_models));
+    HIPTRY(what, value_alloc(vown.p));
+    WsScope scope;
+    LinWs w = {};
+    TRY(linearize_to_ws(m, plants, first_plant, n_models, zd, Fd, mu, ctrl_joint, w, what));      // linearsystem at every setpoint, on its plant (lqr.jl:63)
+    long long bad = -1;
+    HIPTRY(what, knots_converged(w.status, (size_t)n_models, &bad));
+    if (bad >= 0) return fail(CCLQR_ENOCONV, "Newton did not converge at setpoint " + std::to_string(bad));
+    // the controller's gains into the models' body order, device to device
+    const long long rows_per_table = (long long)H.nK * mu, nrows = tables * rows_per_table;
+    double* dK = nullptr;
+    HIPTRY(what, ws_get((void**)&dK, (size_t)nrows * mx * sizeof(double)));
+    HIPTRY(what, launch_lds<false>(k_rows_to_body_order_kernel, dim3((unsigned)nrows), dim3(128), 0, nullptr, c->K_dev, nrows, rows_per_table, (long long)H.K_stride, nb,
+                                   m->dev, dK));
+    std::vector<int> kb, st;
+    std::vector<double> dn;
+    TRY(run_policy(n_models, mx, mu, ml, N, tol, w.A, w.Bu, w.Bl, w.G, dK, tables > 1 ? rows_per_table * mx : 0, H.nK, n_weights, Q, R, 0, vown.p->P_dev, kb, st, dn));
+    for (int p = 0; p < n_models; p++) {
+        if (kbreak) kbreak[p] = kb[p];
+        if (dnorm) { dnorm[2 * p] = dn[2 * (size_t)p]; dnorm[2 * p + 1] = dn[2 * (size_t)p + 1]; }
+        if (st[p] != 0) return fail(CCLQR_ESINGULAR, "G*Bl is singular in model " + std::to_string(p));
+    }
+    *out = vown.release();
+    return CCLQR_OK;
+}

@@ -212,6 +212,18 @@ hipError_t launch_riccati(const RicArgs& a, hipStream_t stream);
 // the nprob of the WHOLE call, and passes the answer to every launch: a chunk's own problem count must not pick another kernel
 int ric_chosen_path(const RicArgs& a);
 
+// Policy evaluation (policy.hip): dlqr's cost recursion (lqr.jl:147-177) with the gain GIVEN.  r: the problems as launch_riccati takes them -- nprob, mx, mu, ml, N, tol,
+// A, Bu, Bl, G (time_varying = 0), Q, R with their strides, kbreak, status, stop, work (ric_total_work_doubles(r) doubles), path, and P_out, which is REQUIRED here;
+// bf16_terms = 0; K, keep_last, kpad and p_rows are not read (no kernel here assumes a symmetric Pk).  The launch shape is ric_chosen_path(r).
+struct PolArgs {
+    RicArgs r;
+    const double* Kin;       // device: gain tables [n_gains][nK][mu][mx] in the order of the models' states; may be null when mu = 0 or N = 1
+    long long k_stride;      // doubles between the tables of consecutive problems: 0 = one table shared by all, or nK * mu * mx
+    int nK;                  // rows per table: N - 1 (row k - 1 = the gain of backward step k) or 1 (a stationary gain, used by every step)
+    double* dnorm;           // device [nprob][2]: norm(Pk - Pkp1) of the last executed step and of the step before it, NaN where no such step ran
+};
+hipError_t launch_policy(const PolArgs& a, hipStream_t stream);
+
 // ---- one TrackingLQR per plant or trajectory (cclqr_ctrl_create_tracking_batch_plants): the workspace plan, pure host arithmetic
 // Default budget of the call's device workspace.  Per knot a problem holds A (mx^2), Bu (mx mu), Bl and G (mx ml each), [A'|D] (mx (mx + mu)) and the projection
 // scratch (ml^2 + ml (mx + mu)) -- triple cartpole, mx 48, mu 1, ml 20: 2304 + 48 + 960 + 960 + 2352 + 1380 doubles = 64 KB --, so its N = 1000 trajectory takes

@@ -7,13 +7,12 @@
 // pivoting (Julia's `\` on a square matrix) followed by one-column-per-thread substitution.
 // Statement-by-statement correspondence with lqr.jl is marked with the line numbers.
 #include "cclqr_internal.h"
+#include "cclqr_riccati_dev.h"      // RicGrid, the knot flags and the MFMA tiles shared with policy.hip
 #include <math.h>
 #include <type_traits>
 
 namespace cclqr {
 
-typedef double v4d __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) double lds_double;   // explicit LDS address space: ds_read/ds_write instead of flat_*
 #define RIC_THREADS 512
 #define RIC_WAVES (RIC_THREADS / 64)
 
@@ -200,40 +199,6 @@ static __device__ unsigned long long g_rprof[RP_N];
 // Each tile is computed by four wavefronts that split the k range and are summed in a fixed order through LDS; the norm is
 // summed per tile and then over tiles in index order, so results do not depend on scheduling.  A problem that has met the
 // break criterion (lqr.jl:172) raises its `stop` flag and its later launches return at once.
-#define TILE_THREADS 256
-struct RicGrid {
-    int nprob, mx, mu, ml, N, nlin, na, tm, tn;
-    double tol;
-    const double *A, *Bu, *Bl, *G, *Q, *R;
-    long long q_stride, r_stride;      // doubles between the Q / R of consecutive problems: 0 = one pair shared by all, or mx*mx / mu*mu (RicArgs)
-    double *AD, *W, *Abar, *P, *Ku, *KRK, *part, *TSp, *scratch, *K;
-    int *stop, *kbreak, *status;
-    long long kpad;    // doubles between the gain tables of consecutive problems in K (per-instance controller tables: cclqr_internal.h gain_row_overrun)
-    int keep_last;     // 1: only the gain of the last executed backward step is kept (K [nprob][mu][mx] = Ku[1] after the back-fill of
-                       // lqr.jl:179-181 = the one gain LQR{T,Inf} keeps, lqr.jl:40-43); 0: the whole table K [nprob][N-1][mu][mx]
-    int bf16_terms;    // 0: fp64 MFMA (parity mode); 1..3: the two mx^3 products of a backward step on bf16 MFMA with fp32 accumulation,
-                       // every fp64 operand split into that many bf16 terms (measured-error mode, BASELINE configs[3]; tiled path only)
-    int p_rows;        // 1: Q or R is not symmetric, so neither is Pk: W = Pk [A'|D] reads Pk by rows (the reference's D'*Pk, lqr.jl:152-158);
-                       // 0: by columns (= rows of a symmetric Pk: the layout the MFMA A operand wants)
-    unsigned char pp_mask[8];   // resident kernel, register-fragment form: bit ct of pp_mask[w] = wavefront w computes the 16x16 tile (its own
-                                // row strip, column tile ct) of the SYMMETRIC Pkp1 and mirrors it (ric_pp_assign)
-};
-
-// per knot: the pivots of its G Bλ LU, then [ml] = 1 if G Bλ is singular (set by ric_project_kernel, read when a backward step reaches the knot)
-__device__ inline int* ric_knot_piv(const RicGrid& a, size_t lin) {
-    const size_t sc = ((size_t)a.ml * a.ml + (size_t)a.ml * a.na + 3) & ~(size_t)1;
-    return (int*)(a.scratch + (size_t)a.nprob * a.nlin * sc) + lin * (a.ml + 2);
-}
-// is G Bλ of the model of backward step k singular?  The reference factors it inside the step (lqr.jl:151, lqr_tracking.jl:89), so a knot the
-// sweep never reaches -- below the break, or any knot with N = 1 -- is no error
-__device__ inline bool ric_knot_singular(const RicGrid& a, int prob, int k) {
-    return ric_knot_piv(a, (size_t)prob * a.nlin + (a.nlin > 1 ? k - 1 : 0))[a.ml] != 0;
-}
-
-// Q / R of problem `prob`.  Called once per workgroup with prob = a block index: the result is wave-uniform and stays in scalar registers, and the
-// tile loops index it as they indexed the shared matrix (stride 0: the very same addresses)
-__device__ inline const double* ric_Q_of(const RicGrid& a, int prob) { return a.Q + (long long)prob * a.q_stride; }
-__device__ inline const double* ric_R_of(const RicGrid& a, int prob) { return a.R + (long long)prob * a.r_stride; }
 
 template <bool LDSM>
 __global__ __launch_bounds__(RIC_THREADS) void ric_project_kernel(RicGrid a, int lds_cols) {
@@ -273,51 +238,6 @@ __global__ __launch_bounds__(RIC_THREADS) void ric_project_kernel(RicGrid a, int
     }
 }
 
-// 32x32 tile of op(A)' B summed over k, split over the four wavefronts of the workgroup (wave w takes the k-groups of 4 with
-// index = w mod 4), then reduced through LDS in wave order.  la(k, h) / lb(k, h) return operand elements A[k][i0+16h+li] / B[k][j0+16h+li]
-// (already masked to 0 outside the matrix).  On return red[e], e = row*32 + col, holds the tile; all threads have synchronised.
-template <class FA, class FB>
-__device__ inline void tile_mfma_splitk(int K, FA la, FB lb, double (*red)[1024]) {
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, li = lane & 15, lk = lane >> 4;
-    v4d acc[2][2] = {{{0.0, 0.0, 0.0, 0.0}, {0.0, 0.0, 0.0, 0.0}}, {{0.0, 0.0, 0.0, 0.0}, {0.0, 0.0, 0.0, 0.0}}};
-    const int ngroups = (K + 3) >> 2;
-    // CH k-groups per wavefront and pass (4 CH loads in flight before the first MFMA): passes of 8 while they are full, then of 2
-    auto pass = [&](auto chtag, int g0) {
-        constexpr int CH = decltype(chtag)::value;
-        double av[CH][2], bv[CH][2];
-#pragma unroll
-        for (int u = 0; u < CH; u++) {
-            const int k = 4 * (g0 + 4 * u) + lk;
-            const bool kok = (g0 + 4 * u) < ngroups && k < K;
-#pragma unroll
-            for (int h = 0; h < 2; h++) { av[u][h] = kok ? la(k, h) : 0.0; bv[u][h] = kok ? lb(k, h) : 0.0; }
-        }
-#pragma unroll
-        for (int u = 0; u < CH; u++)
-#pragma unroll
-            for (int hi = 0; hi < 2; hi++)
-#pragma unroll
-                for (int hj = 0; hj < 2; hj++) acc[hi][hj] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[u][hi], bv[u][hj], acc[hi][hj], 0, 0, 0);
-    };
-    // every pass is one round trip to L2 (its loads are issued together, its MFMAs wait for them), so the tail is covered by the
-    // FEWEST passes -- a masked pass of 8 or 4 rather than a string of passes of 2 (mx = 204: 13 k-groups per wavefront = 8 + 8
-    // masked instead of 8 + 2 + 2 + 2; the masked groups cost idle MFMAs, not latency)
-    int g0 = wave;
-    for (; g0 + 4 * 7 < ngroups; g0 += 4 * 8) pass(std::integral_constant<int, 8>{}, g0);
-    while (g0 < ngroups) {
-        const int left = (ngroups - g0 + 3) >> 2;        // k-groups this wavefront still has
-        if (left > 4) { pass(std::integral_constant<int, 8>{}, g0); g0 += 4 * 8; }
-        else if (left > 2) { pass(std::integral_constant<int, 4>{}, g0); g0 += 4 * 4; }
-        else { pass(std::integral_constant<int, 2>{}, g0); g0 += 4 * 2; }
-    }
-#pragma unroll
-    for (int hi = 0; hi < 2; hi++)
-#pragma unroll
-        for (int hj = 0; hj < 2; hj++)
-#pragma unroll
-            for (int r = 0; r < 4; r++) red[wave][(16 * hi + lk + 4 * r) * 32 + 16 * hj + li] = acc[hi][hj][r];
-    __syncthreads();
-}
 
 // ---- measured-error mode (BASELINE configs[3] "dense Riccati on MFMA bf16 -> fp32 accumulate"): the same 32x32 split-k tile on
 // v_mfma_f32_16x16x16_bf16.  Every fp64 operand x is split on the fly into NS bf16 terms x ~ t0 + t1 + t2 (t0 = bf16(x),
@@ -677,31 +597,6 @@ __device__ __forceinline__ bool gain_in_registers(int j, bool owner, int mx, int
     return true;
 }
 
-// The same tile with the operands addressed by pointer and stride (no per-load lambdas and predicates) and DOUBLE-BUFFERED: the loads of
-// the next four k-groups are in flight while the MFMAs of the current four issue, so a wavefront no longer stops for a full LDS / L2
-// round trip in front of every batch of MFMAs (with two wavefronts per SIMD the partner covers part of it; the single-buffered form ran at
-// a third of the matrix core's rate).  pa / pb point at the lane's element of k-group 0 (row lk of the group, the lane's column clamped
-// into range by the caller: rows / columns past the edge compute garbage that the caller does not store); ga / gb = elements between
-// consecutive k-groups.  K must be a multiple of 4 (mx = 12 nb always is; other sizes take wave_tile16).
-template <class PA, class PB>
-__device__ inline v4d wave_tile16_db(int ngroups, PA pa, int ga, PB pb, int gb) {
-    constexpr int CH = 4;
-    v4d acc = {0.0, 0.0, 0.0, 0.0};
-    double a0[CH], b0[CH], a1[CH], b1[CH];
-#pragma unroll
-    for (int u = 0; u < CH; u++) { const bool ok = u < ngroups; a0[u] = ok ? pa[(size_t)u * ga] : 0.0; b0[u] = ok ? pb[(size_t)u * gb] : 0.0; }
-    for (int g0 = 0; g0 < ngroups; g0 += 2 * CH) {
-#pragma unroll
-        for (int u = 0; u < CH; u++) { const int g = g0 + CH + u; const bool ok = g < ngroups; a1[u] = ok ? pa[(size_t)g * ga] : 0.0; b1[u] = ok ? pb[(size_t)g * gb] : 0.0; }
-#pragma unroll
-        for (int u = 0; u < CH; u++) if (g0 + u < ngroups) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a0[u], b0[u], acc, 0, 0, 0);
-#pragma unroll
-        for (int u = 0; u < CH; u++) { const int g = g0 + 2 * CH + u; const bool ok = g < ngroups; a0[u] = ok ? pa[(size_t)g * ga] : 0.0; b0[u] = ok ? pb[(size_t)g * gb] : 0.0; }
-#pragma unroll
-        for (int u = 0; u < CH; u++) if (g0 + CH + u < ngroups) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a1[u], b1[u], acc, 0, 0, 0);
-    }
-    return acc;
-}
 
 // Tile ownership of the resident kernel.  Every wavefront works on ONE 16-column block `col` of [A' | D] for the whole sweep, so that the
 // block's MFMA fragment (A'|D)[k][col*16 + lane] -- the B operand of W = Pk [A'|D] -- stays in its registers across all backward steps of a
@@ -1224,7 +1119,7 @@ __global__ void ric_backfill_kernel(RicGrid a, double* P_out) {
 // The sizes of g from a, and the workspace of one launch_riccati walked once: g's arrays are placed one behind the other from `base` (null: nowhere);
 // returns the doubles of the whole.  launch_riccati places them in a.work, which ric_total_work_doubles has sized by the same walk.  Behind
 // g.scratch ([nprob][nlin] blocks of sc doubles) sit the per-knot pivots that ric_knot_piv finds there.
-static size_t ric_lay_out(RicGrid& g, const RicArgs& a, double* base) {
+size_t ric_lay_out(RicGrid& g, const RicArgs& a, double* base) {
     g.nprob = a.nprob; g.mx = a.mx; g.mu = a.mu; g.ml = a.ml; g.N = a.N; g.nlin = a.time_varying ? (a.N > 1 ? a.N - 1 : 1) : 1;
     g.na = a.mx + a.mu; g.tm = (a.mx + 31) / 32; g.tn = (g.na + 31) / 32;
     const size_t np = g.nprob, nlin = g.nlin, mx = g.mx, na = g.na, mu = g.mu, ml = g.ml, tm = g.tm;
@@ -1331,20 +1226,9 @@ struct RicResident {
     }
 };
 
-hipError_t launch_riccati(const RicArgs& a, hipStream_t stream) {
-    if (a.nprob <= 0) return hipSuccess;
-    RicGrid g;
-    ric_pp_assign((a.mx + 15) / 16, (a.mx + a.mu + 15) / 16, g.pp_mask);
-    (void)ric_lay_out(g, a, a.work);
-    g.tol = a.tol; g.bf16_terms = a.bf16_terms; g.keep_last = a.keep_last; g.kpad = a.kpad;
-    g.p_rows = a.p_rows;
-    g.A = a.A; g.Bu = a.Bu; g.Bl = a.Bl; g.G = a.G; g.Q = a.Q; g.R = a.R; g.q_stride = a.q_stride; g.r_stride = a.r_stride; g.K = a.K; g.kbreak = a.kbreak; g.status = a.status; g.stop = a.stop;
-    const size_t np = a.nprob, na = g.na, mu = a.mu, ml = a.ml;
-    hipError_t e = hipMemsetAsync(a.stop, 0, np * sizeof(int), stream);
-    if (e == hipSuccess) e = hipMemsetAsync(a.status, 0, np * sizeof(int), stream);
-    if (e == hipSuccess) e = hipMemsetAsync(a.kbreak, 0, np * sizeof(int), stream);
-    if (e != hipSuccess) return e;
-    // [A' | D] of every knot of every problem, in parallel
+// [A' | D] of every knot of every problem, in parallel
+hipError_t launch_ric_project(const RicGrid& g, const RicArgs& a, hipStream_t stream) {
+    const size_t na = g.na, ml = a.ml;
     size_t lds = 0; int cols = 0;
     if (ml <= RIC_LDS_M && ml > 0) {
         const size_t budget = 150 * 1024;                 // of the 160 KB per CU; the rest is static LDS
@@ -1354,8 +1238,24 @@ hipError_t launch_riccati(const RicArgs& a, hipStream_t stream) {
         cols = (int)c;
         lds = (ml * ml + ml * c) * sizeof(double);        // G Bλ for the pivoted LU + one batch of right-hand-side columns
     }
-    e = lds > 0 ? launch_lds(ric_project_kernel<true>, dim3(g.nlin, a.nprob), dim3(RIC_THREADS), lds, stream, g, cols)
-                : launch_lds<false>(ric_project_kernel<false>, dim3(g.nlin, a.nprob), dim3(RIC_THREADS), 0, stream, g, 0);
+    return lds > 0 ? launch_lds(ric_project_kernel<true>, dim3(g.nlin, a.nprob), dim3(RIC_THREADS), lds, stream, g, cols)
+                   : launch_lds<false>(ric_project_kernel<false>, dim3(g.nlin, a.nprob), dim3(RIC_THREADS), 0, stream, g, 0);
+}
+
+hipError_t launch_riccati(const RicArgs& a, hipStream_t stream) {
+    if (a.nprob <= 0) return hipSuccess;
+    RicGrid g;
+    ric_pp_assign((a.mx + 15) / 16, (a.mx + a.mu + 15) / 16, g.pp_mask);
+    (void)ric_lay_out(g, a, a.work);
+    g.tol = a.tol; g.bf16_terms = a.bf16_terms; g.keep_last = a.keep_last; g.kpad = a.kpad;
+    g.p_rows = a.p_rows;
+    g.A = a.A; g.Bu = a.Bu; g.Bl = a.Bl; g.G = a.G; g.Q = a.Q; g.R = a.R; g.q_stride = a.q_stride; g.r_stride = a.r_stride; g.K = a.K; g.kbreak = a.kbreak; g.status = a.status; g.stop = a.stop;
+    const size_t np = a.nprob, na = g.na, mu = a.mu;
+    hipError_t e = hipMemsetAsync(a.stop, 0, np * sizeof(int), stream);
+    if (e == hipSuccess) e = hipMemsetAsync(a.status, 0, np * sizeof(int), stream);
+    if (e == hipSuccess) e = hipMemsetAsync(a.kbreak, 0, np * sizeof(int), stream);
+    if (e != hipSuccess) return e;
+    e = launch_ric_project(g, a, stream);
     if (e != hipSuccess) return e;
     if (!ric_use_tiled(a)) {
         const size_t rl = ric_resident_lds_bytes(a.mx, a.mu);

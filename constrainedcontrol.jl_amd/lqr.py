@@ -399,6 +399,110 @@ class LQRSweep(Controller):
         self._handle.close()
 
 
+class PolicyValue:
+    """Policy evaluation: what the gains of `controller` cost on OTHER models than the one they were designed on, and whether that closed loop is stable there -- the
+    question a robustness study starts with (the nominal controller on plant n), answered on the linear model instead of by a nonlinear rollout per plant.  For every
+    model i -- linearsystem (lqr.jl:63) at zd[i] on plant first_plant + i -- dlqr's cost recursion (lqr.jl:147-177) runs with the gain GIVEN (in place of lqr.jl:160):
+    Abar = A - Bu K[k] - Bλ Kλ (lqr.jl:169), Pkp1 = Q + K[k]' R K[k] + Abar' Pk Abar (lqr.jl:170), break on norm(Pk - Pkp1) < tol (lqr.jl:172), all on the device
+    (cclqr_value_create_policy); the gains never leave it.
+
+    controller: an LQR, PlantLQR or LQRSweep of this mechanism -- one gain table shared by all models (LQR), or table i for model i.  Q, R, horizon: as for LQR
+    (per-body 12 x 12 and per-constraint 1 x 1 blocks in the order of bodyids / eqcids, scaled by Δt), a single pair or -- as LQRSweep takes them -- lists of
+    candidates, one per model (a list of one is shared).  A controller with a finite horizon is evaluated over that horizon (its table has one row per backward step);
+    one with horizon math.inf holds one stationary gain and is evaluated over `horizon` (math.inf: ceil(10 / Δt) steps, lqr.jl:26).
+    zd [n_models][nb][13]: every model's setpoint in the mechanism's body order, on its own plant's constraint manifold; Fτd [n_models][mu] (default 0).
+    plants: a PlantBatch or None (the mechanism's own plant for every model); first_plant: global index of the plant zd[0] belongs to (default plants.first_index).
+
+    P(i): model i's cost-to-go, read back; kbreak [n]; dnorm [n][2]: norm(Pk - Pkp1) of the last executed step and of the step before it (NaN: no such step);
+    converged = dnorm[:, 0] < tol -- a recursion that does not converge is an answer, not an error --; contraction = sqrt(dnorm[:, 0] / dnorm[:, 1]), an estimate of
+    the closed loop's spectral radius on the model (> 1: unstable there).  predicted_cost(mechanism, pv, z0) returns V_i = Δz_i' P_i Δz_i about zd[i].
+    Not a Controller: simulate(..., pv) raises TypeError."""
+
+    def __init__(self, mechanism, controller, bodyids, eqcids, Q, R, horizon, zd, plants=None, first_plant=None, Fτd=None, tol=1e-5):
+        if not isinstance(mechanism, Mechanism):
+            raise TypeError("PolicyValue(mechanism, controller, bodyids, eqcids, Q, R, horizon, zd; ...)")
+        if not isinstance(controller, (LQR, PlantLQR, LQRSweep)):
+            raise TypeError("PolicyValue evaluates the gains of an LQR, PlantLQR or LQRSweep (got %s)" % type(controller).__name__)
+        if controller.mechanism is not mechanism:
+            raise ValueError("the controller was made for another mechanism")
+        if plants is not None and plants.mechanism is not mechanism:
+            raise ValueError("the PlantBatch was made for another mechanism")
+        nb, mu = len(mechanism.bodies), len(eqcids)
+        zd = np.ascontiguousarray(zd, dtype=np.float64)
+        if zd.ndim != 3 or zd.shape[1:] != (nb, 13) or zd.shape[0] < 1:
+            raise ValueError("zd must be [n_models][nb][13] = [n][%d][13], one setpoint per model (got %s)" % (nb, zd.shape))
+        n = zd.shape[0]
+        # a single pair (Q: nb blocks of 12 x 12) or lists of candidates, one pair per model
+        single = len(Q) > 0 and np.ndim(Q[0]) == 2
+        Qs, Rs = ([Q], [R]) if single else (list(Q), list(R))
+        if len(Qs) not in (1, n) or len(Rs) not in (1, n):
+            raise ValueError("Q and R must be a single pair or lists of one pair per model, %d (got %d and %d)" % (n, len(Qs), len(Rs)))
+        assert len(bodyids) == nb, "Missmatched length for bodies"                                                        # lqr.jl:59
+        for q in Qs:
+            assert len(q) == nb, "Missmatched length for bodies"                                                          # lqr.jl:59
+        for r in Rs:
+            assert len(r) == mu, "Missmatched length for constraints"                                                     # lqr.jl:60
+        Fd = None if Fτd is None else np.ascontiguousarray(Fτd, dtype=np.float64).reshape(-1, mu)
+        if Fd is not None and Fd.shape[0] != n:
+            raise ValueError("Fτd must be [n_models][mu] = [%d][%d]" % (n, mu))
+        inv = _body_order(bodyids, nb)
+        nw = max(len(Qs), len(Rs))
+        Qm, Rm, Ntemp = [], [], None
+        for k in range(nw):
+            q, r = Qs[k if len(Qs) > 1 else 0], Rs[k if len(Rs) > 1 else 0]
+            Qb = [np.asarray(q[i], dtype=np.float64) for i in inv]
+            Rb = [np.asarray(x, dtype=np.float64).reshape(1, 1) for x in r]
+            if any(b.shape != (12, 12) for b in Qb):
+                raise ValueError("every Q block must be 12 x 12 (pair %d)" % k)
+            qm, rm, _, Ntemp = _weights_and_horizon(Qb, Rb, horizon, mechanism.Δt)
+            Qm.append(qm)
+            Rm.append(rm)
+        self.first_plant = (0 if plants is None else plants.first_index) if first_plant is None else int(first_plant)
+        if plants is not None:
+            plants.rows_for(self.first_plant, n)      # every model must find its plant
+        self.mechanism, self.controller, self.plants, self.n_models = mechanism, controller, plants, n
+        self.eqcids = [int(e) for e in eqcids]
+        self.ctrl_joints = [mechanism.joint_index(e) for e in self.eqcids]
+        self.Q, self.R = np.stack(Qm), np.stack(Rm)      # [n_weights][12 nb][12 nb], [n_weights][mu][mu]: scaled, mechanism body order
+        self.zd, self.Fd, self.N, self.tol = zd, Fd, Ntemp, float(tol)
+        dev = _device_mech(mechanism)
+        self._dev, self._setpoints = dev, None
+        ctrl = controller._ctrl_handle(dev)
+        try:
+            self._value, self.kbreak, self.dnorm = _capi.value_create_policy(dev, ctrl, zd, self.ctrl_joints, self.Q, self.R, Ntemp, tol=tol, Fd=Fd,
+                                                                             plants=None if plants is None else plants.handle(dev), first_plant=self.first_plant)
+        finally:
+            ctrl.close()
+        self.converged = self.dnorm[:, 0] < self.tol
+        with np.errstate(invalid="ignore", divide="ignore"):
+            self.contraction = np.sqrt(self.dnorm[:, 0] / self.dnorm[:, 1])
+
+    def P(self, i):
+        """model i's cost-to-go [12 nb][12 nb], mechanism body order, read back from the device (cclqr_value_get)"""
+        return self._value.get(i)
+
+    def _value_handle(self, dev):
+        if self._value.mech is not dev or not self._value.ptr:
+            raise ValueError("the PolicyValue was evaluated on another device handle of the mechanism")
+        return self._value, False
+
+    def _ctrl_handle(self, dev, **law):
+        """a setpoint-only controller of n_models tables built from zd: what predicted_cost measures model i's error about"""
+        if law:
+            raise TypeError("a PolicyValue is not a Controller: it holds costs-to-go, not a control law")
+        if dev is not self._dev:
+            raise ValueError("the PolicyValue was evaluated on another device handle of the mechanism")
+        if self._setpoints is None:
+            self._setpoints = _capi.CtrlHandle(dev, self.ctrl_joints, K=None, N=0, zd=self.zd, n_ctrl=self.n_models if self.n_models > 1 else 0)
+        return _BorrowedCtrl(self._setpoints)
+
+    def close(self):
+        if self._setpoints is not None:
+            self._setpoints.close()
+            self._setpoints = None
+        self._value.close()
+
+
 def _is_device_tensor(a):
     return hasattr(a, "data_ptr") and bool(getattr(a, "is_cuda", False))
 
@@ -941,6 +1045,8 @@ def simulate(mechanism, tend_or_storage, controller, record=True, z0=None, fric=
     that slab ever exists; with record=True the slabs are also collected and the recorded trajectory is what was scored.  zT and status are bitwise those of the
     run without score=.  For the fused laws.
     After the call the mechanism's bodies hold instance 0's final state (simulate! mutates the mechanism)."""
+    if isinstance(controller, PolicyValue):
+        raise TypeError("a PolicyValue is not a Controller: simulate rolls out the controller it evaluates (PolicyValue.controller)")
     if isinstance(tend_or_storage, Storage):
         steps = tend_or_storage.steps
     else:
@@ -1012,6 +1118,9 @@ def predicted_cost(mechanism, controller, z0, first_instance=0, out=None):
     """V_i = Δz_i' P Δz_i: the cost the controller's gains were designed to achieve from the start z0[i] -- P the cost-to-go of its recursion (lqr.jl:170), Δz_i the
     error of lqr.jl:92-103 of z0[i] about the controller's setpoint.  The realised cost of a run, Jx + Ju of simulate(..., score=Score(Q, R)), over this is 1 inside
     the linear regime.  controller: an LQR, PlantLQR or LQRSweep built with keep_value=True; instance i reads table first_instance + i of the batched ones.
+    That P is the cost on the model the gains were DESIGNED on.  For a controller that runs on another plant (simulate(mech, steps, LQR, plants=)) pass a
+    PolicyValue(mech, controller, ..., zd, plants=): V_i = Δz_i' P_i Δz_i with P_i the given gains' cost-to-go on plant i's model (lqr.jl:169-170 with the gain
+    given) and Δz_i the error about plant i's own setpoint zd[i] -- then realised / predicted tells "outside the linear regime" from "model mismatch".
     z0 [n_inst][nb][13]: a numpy array -> a numpy array [n_inst]; or a float64 device tensor, read in place -> a device tensor [n_inst] (out: the tensor to fill),
     the evaluation left running on the current stream."""
     if not hasattr(controller, "_value_handle"):

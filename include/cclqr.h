@@ -47,7 +47,9 @@ extern "C" {
  * same way.  With n_weights = 1 they ARE cclqr_riccati_ex and cclqr_ctrl_create_lqr_batch_plants (which call them).
  * Still 202 (additive, no struct changed): the cost-to-go of the recursion and the cost it predicts -- cclqr_riccati_value, cclqr_ctrl_create_lqr_batch_value, the
  * opaque cclqr_value with cclqr_value_create / cclqr_value_get / cclqr_value_destroy, and cclqr_value_eval; looked up the same way.  With P = NULL / value = NULL the
- * first two ARE cclqr_riccati_weights, cclqr_riccati_tv and cclqr_ctrl_create_lqr_batch_weights (which call them). */
+ * first two ARE cclqr_riccati_weights, cclqr_riccati_tv and cclqr_ctrl_create_lqr_batch_weights (which call them).
+ * Still 202 (additive, no struct changed): policy evaluation, a gain table's cost-to-go on another model -- cclqr_policy_value, cclqr_value_create_policy; looked up the
+ * same way.  Their result is a cost-to-go like cclqr_riccati_value's: cclqr_value_get and cclqr_value_eval take it as it stands. */
 #define CCLQR_ABI_VERSION 202
 
 #define CCLQR_REVOLUTE 0      /* EqualityConstraint(Revolute(a, b, axis; p1, p2, qoffset)),  examples/lqr_cartpole.jl:26 */
@@ -402,6 +404,44 @@ int cclqr_value_destroy(cclqr_value *v);
  * first_instance + n_inst beyond the tables, a controller without a setpoint table, z_stride < 13 nb.  Every topology cclqr_mech_create takes. */
 int cclqr_value_eval(const cclqr_mech *m, const cclqr_ctrl *c, const cclqr_value *v, int64_t n_inst, int64_t first_instance, const double *z_dev,
                      int64_t z_stride, double *out_dev, void *stream);
+
+/* Policy evaluation (additive, Still 202, no struct changed; looked up by name like the entries above): dlqr's cost recursion (src/control/lqr.jl:147-177) with the gains
+ * GIVEN instead of solved for -- what a gain table costs on a model it was NOT designed on (the nominal controller on plant n), and whether that closed loop is stable
+ * on the linear model.  Per problem p, with its model (A, Bu, Bλ, G)_p, its weights (Q, R)_p and the table K_t[k], k = 1 .. nK:
+ *     Pk = Q                                                                          lqr.jl:147
+ *     for k = N-1:-1:1                                                                lqr.jl:150
+ *         Kuk  = K_t[k] (nK == N-1)  or  K_t[1] (nK == 1: a stationary gain)          in place of lqr.jl:160: the gain is given
+ *         Kλk  = (G*Bλ) \ (G*(A - Bu*Kuk))                                            second block row of M*Kk = b, lqr.jl:154-160: independent of Pk
+ *         Abar = A - Bu*Kuk - Bλ*Kλk                                                  lqr.jl:169
+ *         Pkp1 = Q + Kuk'*R*Kuk + Abar'*Pk*Abar                                       lqr.jl:170
+ *         norm(Pk - Pkp1) < tol -> break ; Pk = Pkp1                                  lqr.jl:172-176 (Frobenius)
+ * P[p] is the last Pkp1 computed (of the step the test fired on, of step 1 when it never fired, Q when N = 1), kbreak[p] the loop index after the loop (the convention
+ * of cclqr_riccati_value), dnorm[p][0..1] the norm(Pk - Pkp1) of the last executed step and of the step before it, NaN where no such step ran.  The evaluation
+ * converged if and only if dnorm[p][0] < tol; a closed loop that is unstable on model p shows dnorm growing, and sqrt(dnorm[p][0] / dnorm[p][1]) estimates its
+ * contraction (reported, not promised).  A recursion that does not converge is NOT an error: it is the answer.  Q and R are used as written, symmetric or not.  On a
+ * table dlqr produced on the SAME model, weights and N with tol = 0 the result is the Riccati cost-to-go to rounding; on any other model it is not.
+ * cclqr_policy_value -- HOST pointers, the caller's models (the sibling of cclqr_riccati_value): A [nprob][mx][mx], Bu [nprob][mx][mu], Bl [nprob][mx][ml],
+ * G [nprob][ml][mx]; K [n_gains][nK][mu][mx] with n_gains = 1 (one table shared by all) or nprob, nK = 1 or N - 1 (K may be NULL when mu = 0 or N = 1);
+ * Q [n_weights][mx][mx], R [n_weights][mu][mu] with n_weights = 1 or nprob; P [nprob][mx][mx]; kbreak [nprob] and dnorm [nprob][2] may be NULL.  opts: only `path`
+ * is read (0 auto, 1 resident, 2 tiled, as cclqr_riccati_ex; a shape the resident kernel cannot hold runs tiled whatever it says); bf16_terms != 0 is CCLQR_EINVAL
+ * (fp64 only).  Time-invariant models only.  Any other count or size is CCLQR_EINVAL before anything is allocated or launched, with the outputs untouched; a singular
+ * G*Bλ is CCLQR_ESINGULAR, as in the Riccati. */
+int cclqr_policy_value(int32_t nprob, int32_t mx, int32_t mu, int32_t ml, const double *A, const double *Bu, const double *Bl, const double *G,
+                       int32_t n_gains, int32_t nK, const double *K, int32_t n_weights, const double *Q, const double *R, int32_t N, double tol,
+                       double *P, int32_t *kbreak, double *dnorm, const cclqr_riccati_opts *opts);
+/* cclqr_value_create_policy -- the same recursion (lqr.jl:147-177 with lqr.jl:160 given) for a CONTROLLER on a mechanism's plants (Still 202): linearsystem (lqr.jl:63)
+ * at the n_models setpoints zd [n_models][nb][13] (caller's body order, Fd [n_models][mu] or NULL = 0, HOST pointers), setpoint k on the plant with global index
+ * first_plant + k exactly as cclqr_ctrl_create_lqr_batch_plants linearises it (plants == NULL: the mechanism's own plant); the gains of controller c gathered on the
+ * device into the caller's body order -- one table shared by all models, or table k for model k; they never visit the host --; the recursion with Q [n_weights][12 nb][12 nb],
+ * R [n_weights][mu][mu] (n_weights = 1 or n_models, already Δt-scaled, HOST pointers).  *out: a cclqr_value of n_models tables in the caller's body order, for
+ * cclqr_value_eval and cclqr_value_get as it stands.  kbreak [n_models], dnorm [n_models][2]: HOST, or NULL.  The horizon: a controller with ONE gain row
+ * (LQR{T,Inf}, lqr.jl:40-43) is stationary and N is the caller's; one with nK > 1 rows requires N == nK + 1.
+ * Refused before any launch or allocation: mu / ctrl_joint that are not the controller's, a controller without gains, one made for another mechanism or device, a
+ * table count that is neither 1 nor n_models (CCLQR_EINVAL); a controller with more than one setpoint row per table (tracking) and closed-loop mechanisms
+ * (CCLQR_EUNSUPPORTED); the refusals of cclqr_linearize_plants.  During the run CCLQR_ENOCONV names the setpoint whose Newton solve failed, CCLQR_ESINGULAR the model. */
+int cclqr_value_create_policy(const cclqr_mech *m, const cclqr_plants *plants, int64_t first_plant, int32_t n_models, const double *zd, int32_t mu,
+                              const int32_t *ctrl_joint, const double *Fd, const cclqr_ctrl *c, int32_t n_weights, const double *Q, const double *R, int32_t N,
+                              double tol, int32_t *kbreak, double *dnorm, cclqr_value **out);
 
 /* One TrackingLQR per plant and / or per reference trajectory, in one call -- for every k, TrackingLQR(mechanism_k, storage_k, Fτ_k, eqcids, Q, R)
  * (src/control/lqr_tracking.jl:17-43): linearsystem at the knots 1 .. N-1 of trajectory k (lqr_tracking.jl:88) and the recursion of lqr_tracking.jl:73-122 with its own

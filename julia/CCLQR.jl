@@ -503,6 +503,45 @@ function value_eval!(h::MechHandle, c::CtrlHandle, v::ValueHandle, n::Integer, z
                 h.ptr, c.ptr, v.ptr, n, first_instance, z, z_stride, out, stream))
 end
 
+"Policy evaluation (cclqr_policy_value): dlqr's cost recursion (lqr.jl:147-177) with the gains GIVEN in place of lqr.jl:160 -- what the table Ks costs on the models
+ (As, Bus, Bλs, Gs), which need not be the model it was designed on.  Ks: one table (a Vector of N-1 or 1 gains, each mu x mx) shared by all problems, or a Vector of
+ such tables, one per problem; Qs, Rs: one pair or one per problem.  Returns (P[p], kbreak[p], dnorm[p] = (norm(Pk - Pkp1) of the last executed step, of the step before
+ it; NaN where no such step ran)).  The evaluation converged iff dnorm[p][1] < tol; a recursion that does not is the answer, not an error."
+function policy_value(As::Vector, Bus::Vector, Bλs::Vector, Gs::Vector, Ks::Vector, Qs::Vector, Rs::Vector, N::Integer; tol = 1e-5, path = 0)
+    np = length(As); mx, mu, ml = size(As[1], 1), size(Bus[1], 2), size(Bλs[1], 2)
+    length(Qs) == length(Rs) || throw(AssertionError("Qs and Rs must hold the same number of weight pairs"))
+    tables = (isempty(Ks) || Ks[1] isa AbstractMatrix) ? [Ks] : Ks
+    nK = length(tables[1])
+    rowmajor(Ms) = reduce(vcat, [vec(permutedims(Matrix{Float64}(M))) for M in Ms]; init = Float64[])
+    K = reduce(vcat, [rowmajor(t) for t in tables]; init = Float64[])
+    P = zeros(mx * mx * np); kb = zeros(Int32, np); dn = zeros(2 * np)
+    opts = Int32[path, 0, 0, 0]                                      # cclqr_riccati_opts: only `path` is read
+    check(ccall((:cclqr_policy_value, lib), Cint,
+                (Int32, Int32, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int32, Int32, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}, Int32,
+                 Float64, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}, Ptr{Int32}),
+                np, mx, mu, ml, rowmajor(As), rowmajor(Bus), rowmajor(Bλs), rowmajor(Gs), Int32(length(tables)), Int32(nK), K, Int32(length(Qs)), rowmajor(Qs), rowmajor(Rs),
+                N, tol, P, kb, dn, opts))
+    P3 = reshape(P, mx, mx, np)                                      # C layout [np][mx][mx]: row-major, so transposed here
+    [permutedims(P3[:, :, p]) for p = 1:np], Int.(kb), [(dn[2p - 1], dn[2p]) for p = 1:np]
+end
+"The policy evaluation of controller `c` on a mechanism's plants (cclqr_value_create_policy): linearsystem (lqr.jl:63) at the n setpoints zd (13 x Nb x n), setpoint k on
+ plant first_plant + k (p === nothing: the mechanism's own plant), the controller's gains gathered on the device (one table shared by all models, or table k for model
+ k), the recursion of lqr.jl:147-177 with lqr.jl:160 given.  Q, R: n_weights (1 or n) row-major pairs, Δt-scaled.  Returns (ValueHandle of n tables for value_eval! /
+ value_get, kbreak, dnorm 2 x n)."
+function value_create_policy(h::MechHandle, p::Union{PlantsHandle,Nothing}, n::Int, zd::Array{Float64}, ctrl_joint::Vector{Int32}, c::CtrlHandle, n_weights::Int,
+                             Q::Vector{Float64}, R::Vector{Float64}, N::Int; Fd = nothing, first_plant = 0, tol = 1e-5)
+    val = Ref{Ptr{Cvoid}}(C_NULL); kb = zeros(Int32, n); dn = zeros(2, n)
+    fd = Fd === nothing ? Ptr{Float64}(C_NULL) : pointer(Fd)
+    GC.@preserve Fd check(ccall((:cclqr_value_create_policy, lib), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int32, Ptr{Float64}, Int32, Ptr{Int32}, Ptr{Float64}, Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}, Int32, Float64, Ptr{Int32},
+                 Ptr{Float64}, Ref{Ptr{Cvoid}}),
+                h.ptr, p === nothing ? C_NULL : p.ptr, first_plant, Int32(n), zd, Int32(length(ctrl_joint)), ctrl_joint, fd, c.ptr, Int32(n_weights), Q, R, Int32(N), tol, kb,
+                dn, val))
+    obj = ValueHandle(val[], h)
+    finalizer(o -> ccall((:cclqr_value_destroy, lib), Cint, (Ptr{Cvoid},), o.ptr), obj)
+    return obj, kb, dn
+end
+
 "Size the controller handle's Philox workspace before step-per-launch rollouts are captured into a hipGraph (cclqr_ctrl_reserve_noise)."
 reserve_noise!(c::CtrlHandle, n::Integer, steps::Integer) = check(ccall((:cclqr_ctrl_reserve_noise, lib), Cint, (Ptr{Cvoid}, Int64, Int32), c.ptr, n, steps))
 
