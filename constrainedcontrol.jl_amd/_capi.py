@@ -21,7 +21,7 @@ EXPORTS = ["cclqr_last_error", "cclqr_version", "cclqr_device_count", "cclqr_set
            "cclqr_ctrl_create_tracking_batch_plants", "cclqr_ctrl_get_gains", "cclqr_score_create", "cclqr_score_destroy", "cclqr_rollout_score",
            "cclqr_riccati_weights", "cclqr_ctrl_create_lqr_batch_weights",
            "cclqr_riccati_value", "cclqr_ctrl_create_lqr_batch_value", "cclqr_value_create", "cclqr_value_get", "cclqr_value_destroy", "cclqr_value_eval",
-           "cclqr_policy_value", "cclqr_value_create_policy"]
+           "cclqr_policy_value", "cclqr_value_create_policy", "cclqr_policy_value_doubling", "cclqr_value_create_policy_doubling"]
 ABI_VERSION = 202     # include/cclqr.h CCLQR_ABI_VERSION: the structs below mirror that header (verified field by field against cclqr_abi_layout at load time)
 ROLLOUT_NO_ALLOC = 1  # cclqr_rollout_opts.flags: the call may neither allocate nor synchronise (a hipGraph capture is open on the device)
 ROLLOUT_CARRY_STATUS = 4  # ... `status` is read and written: an instance lost in an earlier launch stays frozen, the others merge this launch's result into it
@@ -774,6 +774,63 @@ def value_create_policy(mech, ctrl, zd, ctrl_joint, Q, R, N, tol=1e-5, Fd=None, 
     check(lib().cclqr_value_create_policy(mech.ptr, None if plants is None else plants.ptr, C.c_int64(int(first_plant)), C.c_int32(n), _d(zd), C.c_int32(mu), _i(cj), _d(Fd),
                                           ctrl.ptr, C.c_int32(nw), _d(Q), _d(R), C.c_int32(int(N)), C.c_double(float(tol)), _i(kb), _d(dn), C.byref(vptr)))
     return ValueHandle(mech, ptr=vptr, n_tables=n), kb, dn
+
+
+def policy_value_doubling(A, Bu, Bl, G, K, Q, R, N, tol=1e-5, max_levels=40, path=0, bf16_terms=0, want_diag=True):
+    """a stationary gain's cost-to-go by doubling (cclqr_policy_value_doubling; lqr.jl:169-170 with the one gain of lqr.jl:40-43).  Models and weights as for
+    policy_value; K [mu][mx] (one gain shared by all) or [n_gains][mu][mx] with n_gains = nprob.  N >= 1: N - 1 steps exactly; N = 0: level by level to convergence
+    (increment < tol, at most max_levels levels) -> P [nprob][mx][mx], levels [nprob], reason [nprob] (0 converged, 1 max_levels, 2 norm(M) > 1e50), dnorm [nprob][2],
+    gnorm [nprob][2] (the increment norms and norm(M) of the last level and of the one before; NaN where no such level ran).  want_diag=False passes NULL for the
+    four diagnostics (returned as None)"""
+    A = f64(A)
+    mx = A.shape[-1]
+    A = A.reshape(-1, mx, mx)
+    nprob = A.shape[0]
+    Bu, Bl = f64(Bu), f64(Bl)
+    Bu = Bu.reshape(nprob, mx, Bu.shape[-1] if Bu.ndim > 1 else -1)
+    mu = Bu.shape[2]
+    Bl = Bl.reshape(nprob, mx, Bl.shape[-1] if Bl.ndim > 1 else -1)
+    ml = Bl.shape[2]
+    G = f64(G).reshape(nprob, ml, mx)
+    K = f64(K)
+    if K.ndim not in (2, 3) or K.shape[-2:] != (mu, mx):
+        raise ValueError("K must be [mu][mx] or [n_gains][mu][mx] with mu = %d, mx = %d (got %s)" % (mu, mx, K.shape))
+    if K.ndim == 2:
+        K = K[None]
+    Q = f64(Q).reshape(-1, mx, mx)
+    nw = Q.shape[0]
+    R = f64(R).reshape(nw, mu, mu)
+    P = np.zeros((nprob, mx, mx))
+    lv = np.zeros(nprob, dtype=np.int32) if want_diag else None
+    rs = np.zeros(nprob, dtype=np.int32) if want_diag else None
+    dn = np.zeros((nprob, 2)) if want_diag else None
+    gn = np.zeros((nprob, 2)) if want_diag else None
+    o = RiccatiOpts(int(path), int(bf16_terms), 0, 0)
+    check(lib().cclqr_policy_value_doubling(C.c_int32(nprob), C.c_int32(mx), C.c_int32(mu), C.c_int32(ml), _d(A), _d(Bu) if mu else None, _d(Bl) if ml else None,
+                                            _d(G) if ml else None, C.c_int32(K.shape[0]), _d(K) if K.size else None, C.c_int32(nw), _d(Q), _d(R) if mu else None,
+                                            C.c_int32(int(N)), C.c_double(float(tol)), C.c_int32(int(max_levels)), _d(P), _i(lv), _i(rs), _d(dn), _d(gn), C.byref(o)))
+    return P, lv, rs, dn, gn
+
+
+def value_create_policy_doubling(mech, ctrl, zd, ctrl_joint, Q, R, N, tol=1e-5, max_levels=40, Fd=None, plants=None, first_plant=0):
+    """cclqr_value_create_policy_doubling: the doubling evaluation of controller handle `ctrl`'s stationary gain (one table, or one per model; one row each) on the models
+    linearised as for value_create_policy.  N >= 1 knots, or 0 = to convergence -> (ValueHandle of n_models tables, levels, reason, dnorm [n][2], gnorm [n][2])"""
+    nb = mech.tables.nb
+    zd = f64(zd).reshape(-1, nb, 13)
+    n = zd.shape[0]
+    cj = i32(ctrl_joint).reshape(-1)
+    mu = len(cj)
+    Fd = None if Fd is None else f64(Fd).reshape(n, mu)
+    Q = f64(Q).reshape(-1, 12 * nb, 12 * nb)
+    nw = Q.shape[0]
+    R = f64(R).reshape(nw, mu, mu)
+    lv, rs = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+    dn, gn = np.zeros((n, 2)), np.zeros((n, 2))
+    vptr = C.c_void_p()
+    check(lib().cclqr_value_create_policy_doubling(mech.ptr, None if plants is None else plants.ptr, C.c_int64(int(first_plant)), C.c_int32(n), _d(zd), C.c_int32(mu),
+                                                   _i(cj), _d(Fd), ctrl.ptr, C.c_int32(nw), _d(Q), _d(R), C.c_int32(int(N)), C.c_double(float(tol)),
+                                                   C.c_int32(int(max_levels)), _i(lv), _i(rs), _d(dn), _d(gn), C.byref(vptr)))
+    return ValueHandle(mech, ptr=vptr, n_tables=n), lv, rs, dn, gn
 
 
 def riccati_tv(A, Bu, Bl, G, Q, R, N, tol=1e-5):

@@ -1317,26 +1317,53 @@ extern "C" int cclqr_policy_value(int32_t nprob, int32_t mx, int32_t mu, int32_t
     return CCLQR_OK;
 }
 
+// what the controller entry points of the policy evaluation (stepping and doubling) refuse about the mechanism, the controller and the plants, before anything is
+// allocated or launched; bad_sizes: the caller's own test of its counts.  cj: the controlled links; *tables: the controller's gain tables (1 or n_models)
+static int policy_ctrl_check(const cclqr_mech* m, const cclqr_plants* plants, int64_t first_plant, int32_t n_models, int32_t mu, const int32_t* ctrl_joint,
+                             const cclqr_ctrl* c, bool bad_sizes, int* cj, int64_t* tables) {
+    TRY(check_device(m));
+    if (m->host.loop) return fail(CCLQR_EUNSUPPORTED, "policy evaluation is for tree mechanisms (closed loops have no multiplier model to evaluate a gain on)");
+    if (c->nb != m->nb || c->device != m->device) return fail(CCLQR_EINVAL, "the controller was created for another mechanism or device");
+    if (bad_sizes) return fail(CCLQR_EINVAL, "bad sizes");
+    const CtrlDev& H = c->host;
+    if (!c->K_dev || H.nK < 1) return fail(CCLQR_EINVAL, "the controller has no gains (open loop / PID)");
+    if (H.nsp > 1) return fail(CCLQR_EUNSUPPORTED, "tracking controllers (more than one setpoint row per table) are outside policy evaluation's scope: time-invariant models only");
+    TRY(linearize_check(m, plants, first_plant, n_models, mu, ctrl_joint, cj));      // the refusals of cclqr_linearize_plants
+    bool same = mu == H.mu;
+    for (int i = 0; same && i < mu; i++) same = cj[i] == H.cj[i];
+    if (!same) return fail(CCLQR_EINVAL, "mu / ctrl_joint are not the controller's: its gains act on other joints");
+    *tables = H.n_ctrl > 1 ? H.n_ctrl : 1;
+    if (*tables != 1 && *tables != n_models)
+        return fail(CCLQR_EINVAL, "the controller holds " + std::to_string(*tables) + " tables: one shared by all models (1) or one per model (" + std::to_string(n_models) + ")");
+    return CCLQR_OK;
+}
+// ... and the device sequence they share, inside the caller's WsScope: linearsystem at every setpoint on its plant (lqr.jl:63) into w, and the controller's gains
+// gathered into the models' body order, device to device, *dK [tables][nK][mu][12 nb], *k_stride doubles apart (0: one table)
+static int policy_models_and_gains(const cclqr_mech* m, const cclqr_plants* plants, int64_t first_plant, int32_t n_models, const double* zd, const double* Fd, int32_t mu,
+                                   const int32_t* ctrl_joint, const cclqr_ctrl* c, int64_t tables, LinWs& w, double** dK, long long* k_stride, const char* what) {
+    const CtrlDev& H = c->host;
+    const int nb = m->nb, mx = 12 * nb;
+    TRY(linearize_to_ws(m, plants, first_plant, n_models, zd, Fd, mu, ctrl_joint, w, what));
+    long long bad = -1;
+    HIPTRY(what, knots_converged(w.status, (size_t)n_models, &bad));
+    if (bad >= 0) return fail(CCLQR_ENOCONV, "Newton did not converge at setpoint " + std::to_string(bad));
+    const long long rows_per_table = (long long)H.nK * mu, nrows = tables * rows_per_table;
+    HIPTRY(what, ws_get((void**)dK, (size_t)nrows * mx * sizeof(double)));
+    HIPTRY(what, launch_lds<false>(k_rows_to_body_order_kernel, dim3((unsigned)nrows), dim3(128), 0, nullptr, c->K_dev, nrows, rows_per_table, (long long)H.K_stride, nb,
+                                   m->dev, *dK));
+    *k_stride = tables > 1 ? rows_per_table * mx : 0;
+    return CCLQR_OK;
+}
+
 extern "C" int cclqr_value_create_policy(const cclqr_mech* m, const cclqr_plants* plants, int64_t first_plant, int32_t n_models, const double* zd, int32_t mu,
                                          const int32_t* ctrl_joint, const double* Fd, const cclqr_ctrl* c, int32_t n_weights, const double* Q, const double* R,
                                          int32_t N, double tol, int32_t* kbreak, double* dnorm, cclqr_value** out) {
     static const char* const what = "policy evaluation";
     if (!m || !zd || !c || !Q || !out || (mu > 0 && (!ctrl_joint || !R))) return fail(CCLQR_EINVAL, "null argument");
-    TRY(check_device(m));
-    if (m->host.loop) return fail(CCLQR_EUNSUPPORTED, "policy evaluation is for tree mechanisms (closed loops have no multiplier model to evaluate a gain on)");
-    if (c->nb != m->nb || c->device != m->device) return fail(CCLQR_EINVAL, "the controller was created for another mechanism or device");
-    if (n_models < 1 || N < 1 || mu < 1 || mu > m->nb) return fail(CCLQR_EINVAL, "bad sizes");
-    const CtrlDev& H = c->host;
-    if (!c->K_dev || H.nK < 1) return fail(CCLQR_EINVAL, "the controller has no gains (open loop / PID)");
-    if (H.nsp > 1) return fail(CCLQR_EUNSUPPORTED, "tracking controllers (more than one setpoint row per table) are outside policy evaluation's scope: time-invariant models only");
     int cj[CCLQR_MAXL];
-    TRY(linearize_check(m, plants, first_plant, n_models, mu, ctrl_joint, cj));      // the refusals of cclqr_linearize_plants
-    bool same = mu == H.mu;
-    for (int i = 0; same && i < mu; i++) same = cj[i] == H.cj[i];
-    if (!same) return fail(CCLQR_EINVAL, "mu / ctrl_joint are not the controller's: its gains act on other joints");
-    const int64_t tables = H.n_ctrl > 1 ? H.n_ctrl : 1;
-    if (tables != 1 && tables != n_models)
-        return fail(CCLQR_EINVAL, "the controller holds " + std::to_string(tables) + " tables: one shared by all models (1) or one per model (" + std::to_string(n_models) + ")");
+    int64_t tables = 1;
+    TRY(policy_ctrl_check(m, plants, first_plant, n_models, mu, ctrl_joint, c, n_models < 1 || N < 1 || mu < 1 || mu > m->nb, cj, &tables));
+    const CtrlDev& H = c->host;
     if (H.nK > 1 && N != H.nK + 1)
         return fail(CCLQR_EINVAL, "the controller's tables hold " + std::to_string(H.nK) + " rows, one per backward step: N must be " + std::to_string(H.nK + 1) + " (got " + std::to_string(N) + ")");
     TRY(policy_check(n_models, mu, N, H.nK, n_weights, "model"));
@@ -1345,24 +1372,127 @@ extern "C" int cclqr_value_create_policy(const cclqr_mech* m, const cclqr_plants
     HIPTRY(what, value_alloc(vown.p));
     WsScope scope;
     LinWs w = {};
-    TRY(linearize_to_ws(m, plants, first_plant, n_models, zd, Fd, mu, ctrl_joint, w, what));      // linearsystem at every setpoint, on its plant (lqr.jl:63)
-    long long bad = -1;
-    HIPTRY(what, knots_converged(w.status, (size_t)n_models, &bad));
-    if (bad >= 0) return fail(CCLQR_ENOCONV, "Newton did not converge at setpoint " + std::to_string(bad));
-    // the controller's gains into the models' body order, device to device
-    const long long rows_per_table = (long long)H.nK * mu, nrows = tables * rows_per_table;
     double* dK = nullptr;
-    HIPTRY(what, ws_get((void**)&dK, (size_t)nrows * mx * sizeof(double)));
-    HIPTRY(what, launch_lds<false>(k_rows_to_body_order_kernel, dim3((unsigned)nrows), dim3(128), 0, nullptr, c->K_dev, nrows, rows_per_table, (long long)H.K_stride, nb,
-                                   m->dev, dK));
+    long long k_stride = 0;
+    TRY(policy_models_and_gains(m, plants, first_plant, n_models, zd, Fd, mu, ctrl_joint, c, tables, w, &dK, &k_stride, what));
     std::vector<int> kb, st;
     std::vector<double> dn;
-    TRY(run_policy(n_models, mx, mu, ml, N, tol, w.A, w.Bu, w.Bl, w.G, dK, tables > 1 ? rows_per_table * mx : 0, H.nK, n_weights, Q, R, 0, vown.p->P_dev, kb, st, dn));
+    TRY(run_policy(n_models, mx, mu, ml, N, tol, w.A, w.Bu, w.Bl, w.G, dK, k_stride, H.nK, n_weights, Q, R, 0, vown.p->P_dev, kb, st, dn));
     for (int p = 0; p < n_models; p++) {
         if (kbreak) kbreak[p] = kb[p];
         if (dnorm) { dnorm[2 * p] = dn[2 * (size_t)p]; dnorm[2 * p + 1] = dn[2 * (size_t)p + 1]; }
         if (st[p] != 0) return fail(CCLQR_ESINGULAR, "G*Bl is singular in model " + std::to_string(p));
     }
+    *out = vown.release();
+    return CCLQR_OK;
+}
+
+// ---- a stationary gain's cost-to-go by doubling (policy_doubling.hip): lqr.jl:169-170 with the one gain of LQR{T,Inf} (lqr.jl:40-43)
+// what both entry points refuse about the evaluation's own arguments, before anything is allocated or launched
+static int doubling_check(int nprob, int N, double tol, int max_levels, int n_weights, const cclqr_riccati_opts* opts, const char* of) {
+    if (N < 0) return fail(CCLQR_EINVAL, "N = " + std::to_string(N) + ": a horizon of N >= 1 knots, or 0 = to convergence");
+    if (N == 0 && (max_levels < 1 || max_levels > 60)) return fail(CCLQR_EINVAL, "max_levels = " + std::to_string(max_levels) + ": 1 .. 60 (2^max_levels steps)");
+    if (!(tol >= 0.0)) return fail(CCLQR_EINVAL, "tol is negative or not a number");
+    const int path = opts ? opts->path : 0;
+    if (path < 0 || path > 2) return fail(CCLQR_EINVAL, "policy evaluation options: path in 0..2");
+    if (opts && opts->bf16_terms != 0) return fail(CCLQR_EINVAL, "policy evaluation runs in fp64 only (bf16_terms = 0)");
+    return check_n_weights(n_weights, nprob, of);
+}
+// the host results of run_doubling
+struct DblOut { std::vector<int> lv, rs, st; std::vector<double> dn, gn; };
+// shared tail of the two entry points, as run_policy is: the evaluation on device-resident models and gains, inside the caller's WsScope
+static int run_doubling(int nprob, int mx, int mu, int ml, int N, double tol, int max_levels, const double* dA, const double* dBu, const double* dBl, const double* dG,
+                        const double* dK, long long k_stride, int n_weights, const double* Q, const double* R, int path, double* dP, DblOut& o) {
+    static const char* const what = "policy evaluation by doubling";
+    double *dQ = nullptr, *dR = nullptr, *dwork = nullptr, *dwork2 = nullptr, *ddn = nullptr, *dgn = nullptr;
+    int *dlv = nullptr, *drs = nullptr, *dst = nullptr, *dstop = nullptr;
+    const size_t np = (size_t)nprob, nw = (size_t)n_weights;
+    DblArgs a;
+    RicArgs& r = a.r;
+    r.nprob = nprob; r.mx = mx; r.mu = mu; r.ml = ml; r.N = N; r.time_varying = 0; r.tol = tol; r.path = path; r.bf16_terms = 0; r.keep_last = 0; r.K = nullptr;
+    if (n_weights > 1) { r.q_stride = (long long)mx * mx; r.r_stride = (long long)mu * mu; }
+    HIPTRY(what, ws_get((void**)&dQ, nw * mx * mx * sizeof(double)));
+    HIPTRY(what, ws_get((void**)&dR, (nw * mu * mu + 1) * sizeof(double)));
+    HIPTRY(what, ws_get((void**)&dwork, ric_total_work_doubles(r) * sizeof(double)));
+    HIPTRY(what, ws_get((void**)&dwork2, dbl_work_doubles(r) * sizeof(double)));
+    HIPTRY(what, ws_get((void**)&ddn, 2 * np * sizeof(double)));
+    HIPTRY(what, ws_get((void**)&dgn, 2 * np * sizeof(double)));
+    HIPTRY(what, ws_get((void**)&dstop, np * sizeof(int)));
+    HIPTRY(what, ws_get((void**)&dlv, np * sizeof(int)));
+    HIPTRY(what, ws_get((void**)&drs, np * sizeof(int)));
+    HIPTRY(what, ws_get((void**)&dst, np * sizeof(int)));
+    HIPTRY(what, hipMemcpy(dQ, Q, nw * mx * mx * sizeof(double), hipMemcpyHostToDevice));
+    if (mu > 0) HIPTRY(what, hipMemcpy(dR, R, nw * mu * mu * sizeof(double), hipMemcpyHostToDevice));
+    r.stop = dstop; r.A = dA; r.Bu = dBu; r.Bl = dBl; r.G = dG; r.Q = dQ; r.R = dR; r.kbreak = nullptr; r.status = dst; r.work = dwork; r.P_out = dP;
+    a.Kin = dK; a.k_stride = k_stride; a.max_levels = max_levels; a.work2 = dwork2; a.levels = dlv; a.reason = drs; a.dnorm = ddn; a.gnorm = dgn;
+    HIPTRY(what, launch_policy_doubling(a, nullptr));
+    HIPTRY(what, hipDeviceSynchronize());
+    o.lv.resize(np); o.rs.resize(np); o.st.resize(np); o.dn.resize(2 * np); o.gn.resize(2 * np);
+    HIPTRY(what, hipMemcpy(o.lv.data(), dlv, np * sizeof(int), hipMemcpyDeviceToHost));
+    HIPTRY(what, hipMemcpy(o.rs.data(), drs, np * sizeof(int), hipMemcpyDeviceToHost));
+    HIPTRY(what, hipMemcpy(o.st.data(), dst, np * sizeof(int), hipMemcpyDeviceToHost));
+    HIPTRY(what, hipMemcpy(o.dn.data(), ddn, 2 * np * sizeof(double), hipMemcpyDeviceToHost));
+    HIPTRY(what, hipMemcpy(o.gn.data(), dgn, 2 * np * sizeof(double), hipMemcpyDeviceToHost));
+    return CCLQR_OK;
+}
+// the diagnostics of run_doubling into the caller's arrays (each may be null), up to the problem the call is refused for
+static int doubling_report(const DblOut& o, int nprob, int32_t* levels, int32_t* reason, double* dnorm, double* gnorm, const char* of) {
+    for (int p = 0; p < nprob; p++) {
+        if (levels) levels[p] = o.lv[p];
+        if (reason) reason[p] = o.rs[p];
+        if (dnorm) { dnorm[2 * p] = o.dn[2 * (size_t)p]; dnorm[2 * p + 1] = o.dn[2 * (size_t)p + 1]; }
+        if (gnorm) { gnorm[2 * p] = o.gn[2 * (size_t)p]; gnorm[2 * p + 1] = o.gn[2 * (size_t)p + 1]; }
+        if (o.st[p] != 0) return fail(CCLQR_ESINGULAR, std::string("G*Bl is singular in ") + of + " " + std::to_string(p));
+    }
+    return CCLQR_OK;
+}
+
+extern "C" int cclqr_policy_value_doubling(int32_t nprob, int32_t mx, int32_t mu, int32_t ml, const double* A, const double* Bu, const double* Bl, const double* G,
+                                           int32_t n_gains, const double* K, int32_t n_weights, const double* Q, const double* R, int32_t N, double tol,
+                                           int32_t max_levels, double* P, int32_t* levels, int32_t* reason, double* dnorm, double* gnorm, const cclqr_riccati_opts* opts) {
+    static const char* const what = "policy evaluation by doubling";
+    if (!A || !Q || !P || (mu > 0 && (!Bu || !R || !K)) || (ml > 0 && (!Bl || !G))) return fail(CCLQR_EINVAL, "null argument");
+    if (nprob < 1 || mx < 1 || mu < 0 || ml < 0) return fail(CCLQR_EINVAL, "bad sizes");
+    if (n_gains != 1 && n_gains != nprob)
+        return fail(CCLQR_EINVAL, "n_gains = " + std::to_string(n_gains) + ": one gain shared by all (1) or one per problem (" + std::to_string(nprob) + ")");
+    TRY(doubling_check(nprob, N, tol, max_levels, n_weights, opts, "problem"));
+    WsScope scope;
+    RicModels d = {};
+    TRY(upload_models((size_t)nprob, mx, mu, ml, A, Bu, Bl, G, d));
+    const size_t nKd = (size_t)n_gains * mu * mx, nP = (size_t)nprob * mx * mx;
+    double *dK = nullptr, *dP = nullptr;
+    HIPTRY(what, ws_get((void**)&dK, (nKd + 1) * sizeof(double)));
+    HIPTRY(what, ws_get((void**)&dP, nP * sizeof(double)));
+    if (nKd) HIPTRY(what, hipMemcpy(dK, K, nKd * sizeof(double), hipMemcpyHostToDevice));
+    DblOut o;
+    TRY(run_doubling(nprob, mx, mu, ml, N, tol, max_levels, d.A, d.Bu, d.Bl, d.G, dK, n_gains > 1 ? (long long)mu * mx : 0, n_weights, Q, R, opts ? opts->path : 0, dP, o));
+    HIPTRY(what, hipMemcpy(P, dP, nP * sizeof(double), hipMemcpyDeviceToHost));
+    return doubling_report(o, nprob, levels, reason, dnorm, gnorm, "problem");
+}
+
+extern "C" int cclqr_value_create_policy_doubling(const cclqr_mech* m, const cclqr_plants* plants, int64_t first_plant, int32_t n_models, const double* zd, int32_t mu,
+                                                  const int32_t* ctrl_joint, const double* Fd, const cclqr_ctrl* c, int32_t n_weights, const double* Q, const double* R,
+                                                  int32_t N, double tol, int32_t max_levels, int32_t* levels, int32_t* reason, double* dnorm, double* gnorm,
+                                                  cclqr_value** out) {
+    static const char* const what = "policy evaluation by doubling";
+    if (!m || !zd || !c || !Q || !out || (mu > 0 && (!ctrl_joint || !R))) return fail(CCLQR_EINVAL, "null argument");
+    int cj[CCLQR_MAXL];
+    int64_t tables = 1;
+    TRY(policy_ctrl_check(m, plants, first_plant, n_models, mu, ctrl_joint, c, n_models < 1 || mu < 1 || mu > m->nb, cj, &tables));
+    if (c->host.nK != 1)
+        return fail(CCLQR_EINVAL, "the controller's tables hold " + std::to_string(c->host.nK) + " gain rows: doubling evaluates ONE stationary gain (a finite-horizon table is what cclqr_value_create_policy steps through)");
+    TRY(doubling_check(n_models, N, tol, max_levels, n_weights, nullptr, "model"));
+    const int nb = m->nb, mx = 12 * nb, ml = 5 * nb;
+    ValueOwner vown(value_new(m, n_models));
+    HIPTRY(what, value_alloc(vown.p));
+    WsScope scope;
+    LinWs w = {};
+    double* dK = nullptr;
+    long long k_stride = 0;
+    TRY(policy_models_and_gains(m, plants, first_plant, n_models, zd, Fd, mu, ctrl_joint, c, tables, w, &dK, &k_stride, what));
+    DblOut o;
+    TRY(run_doubling(n_models, mx, mu, ml, N, tol, max_levels, w.A, w.Bu, w.Bl, w.G, dK, k_stride, n_weights, Q, R, 0, vown.p->P_dev, o));
+    TRY(doubling_report(o, n_models, levels, reason, dnorm, gnorm, "model"));
     *out = vown.release();
     return CCLQR_OK;
 }

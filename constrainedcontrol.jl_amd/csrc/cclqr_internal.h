@@ -224,6 +224,21 @@ struct PolArgs {
 };
 hipError_t launch_policy(const PolArgs& a, hipStream_t stream);
 
+// A stationary gain's cost-to-go by doubling (policy_doubling.hip): S(a + b) = S(a) + M(a)' S(b) M(a) over the bits of N - 1, or level by level to convergence.
+// r: as for launch_policy, with r.N = the knots of a fixed horizon (N - 1 steps exactly; r.tol is not read) or 0 = to convergence (increment < r.tol); kbreak is not
+// written.  The launch shape is launch_policy's.
+struct DblArgs {
+    RicArgs r;
+    const double* Kin;       // device: the stationary gains [n_gains][mu][mx] in the order of the models' states; may be null when mu = 0
+    long long k_stride;      // doubles between the gains of consecutive problems: 0 = one gain shared by all, or mu * mx
+    int max_levels;          // to convergence: the last level (2^max_levels steps)
+    double* work2;           // device: dbl_work_doubles(r) doubles
+    int *levels, *reason;    // device [nprob]: doublings made; to convergence, why the last one was the last (0 converged, 1 max_levels, 2 norm(M) > 1e50)
+    double *dnorm, *gnorm;   // device [nprob][2]: the increment norms and norm(M) of the last level and of the one before, NaN where no such level ran
+};
+size_t dbl_work_doubles(const RicArgs& r);
+hipError_t launch_policy_doubling(const DblArgs& a, hipStream_t stream);
+
 // ---- one TrackingLQR per plant or trajectory (cclqr_ctrl_create_tracking_batch_plants): the workspace plan, pure host arithmetic
 // Default budget of the call's device workspace.  Per knot a problem holds A (mx^2), Bu (mx mu), Bl and G (mx ml each), [A'|D] (mx (mx + mu)) and the projection
 // scratch (ml^2 + ml (mx + mu)) -- triple cartpole, mx 48, mu 1, ml 20: 2304 + 48 + 960 + 960 + 2352 + 1380 doubles = 64 KB --, so its N = 1000 trajectory takes

@@ -503,6 +503,120 @@ class PolicyValue:
         self._value.close()
 
 
+class StationaryPolicyValue:
+    """Policy evaluation of a STATIONARY gain by doubling: what PolicyValue answers for the reference's default controller LQR{T,Inf} -- one gain (lqr.jl:40-43) -- in
+    about 2 log2 N matrix combinations instead of N - 1 backward steps.  With that gain Abar (lqr.jl:169) and Qbar = Q + K' R K (lqr.jl:170) are constant, and with
+    S(n) = sum_{i<n} (Abar^i)' Qbar Abar^i, M(n) = Abar^n the identity S(a+b) = S(a) + M(a)' S(b) M(a) gives P = S(n) + M(n)' Q M(n) for any n by square-and-multiply,
+    on the device (cclqr_value_create_policy_doubling); the gains never leave it.
+
+    controller: an LQR, PlantLQR or LQRSweep of this mechanism holding ONE gain row per table (horizon math.inf); anything else raises ValueError (a finite-horizon
+    table is what PolicyValue steps through).  Q, R, zd, plants, first_plant, Fτd: as for PolicyValue.
+    horizon: as for PolicyValue -- N - 1 steps exactly, math.inf meaning ceil(10 / Δt) knots (lqr.jl:26) --, so P(i) is PolicyValue(..., tol=0).P(i) to rounding;
+    or None: level by level to convergence, the infinite-horizon cost.  Level j doubles to 2^j steps and stops when its increment norm(S(2^j) - S(2^(j-1))) < tol
+    (reason 0), when norm(M(2^j)) > 1e50 (reason 2: the closed loop is unstable on the model) or at j == max_levels (reason 1; 1 .. 60).
+
+    P(i): model i's cost-to-go, read back; levels [n]; steps [n] = N - 1, or 2^levels; reason [n]; dnorm, gnorm [n][2]: the increment norms and norm(M) of the last
+    level and of the one before (NaN: no such level; a fixed horizon has gnorm[:, 0] = norm(M(N - 1)) only); converged = reason == 0 and diverged = reason == 2 (both
+    False for a fixed horizon, which makes no test); spectral_radius = (gnorm0 / gnorm1)^(1 / 2^(levels - 1)), an estimate, reported and not promised.
+    predicted_cost(mechanism, spv, z0) returns V_i = Δz_i' P_i Δz_i about zd[i].  Not a Controller: simulate(..., spv) raises TypeError."""
+
+    def __init__(self, mechanism, controller, bodyids, eqcids, Q, R, horizon, zd, plants=None, first_plant=None, Fτd=None, tol=1e-5, max_levels=40):
+        if not isinstance(mechanism, Mechanism):
+            raise TypeError("StationaryPolicyValue(mechanism, controller, bodyids, eqcids, Q, R, horizon, zd; ...)")
+        if not isinstance(controller, (LQR, PlantLQR, LQRSweep)):
+            raise ValueError("StationaryPolicyValue evaluates the stationary gain of an LQR, PlantLQR or LQRSweep (got %s)" % type(controller).__name__)
+        if controller.mechanism is not mechanism:
+            raise ValueError("the controller was made for another mechanism")
+        if plants is not None and plants.mechanism is not mechanism:
+            raise ValueError("the PlantBatch was made for another mechanism")
+        nb, mu = len(mechanism.bodies), len(eqcids)
+        zd = np.ascontiguousarray(zd, dtype=np.float64)
+        if zd.ndim != 3 or zd.shape[1:] != (nb, 13) or zd.shape[0] < 1:
+            raise ValueError("zd must be [n_models][nb][13] = [n][%d][13], one setpoint per model (got %s)" % (nb, zd.shape))
+        n = zd.shape[0]
+        single = len(Q) > 0 and np.ndim(Q[0]) == 2
+        Qs, Rs = ([Q], [R]) if single else (list(Q), list(R))
+        if len(Qs) not in (1, n) or len(Rs) not in (1, n):
+            raise ValueError("Q and R must be a single pair or lists of one pair per model, %d (got %d and %d)" % (n, len(Qs), len(Rs)))
+        max_levels = int(max_levels)
+        if horizon is None and not 1 <= max_levels <= 60:
+            raise ValueError("max_levels = %d: a run to convergence makes 1 .. 60 levels (2^max_levels steps)" % max_levels)
+        if not float(tol) >= 0.0:
+            raise ValueError("tol = %r is negative or not a number" % (tol,))
+        ctrl_N = int(getattr(controller, "N", 0))      # the device convention of the three controllers: 0 = LQR{T,Inf}, one gain; N > 0 = a table of N - 1 rows
+        if ctrl_N > 0 and ctrl_N - 1 != 1:
+            raise ValueError("the controller holds a table of %d gain rows: doubling evaluates ONE stationary gain (horizon math.inf); PolicyValue steps through a table" % (ctrl_N - 1))
+        assert len(bodyids) == nb, "Missmatched length for bodies"                                                        # lqr.jl:59
+        for q in Qs:
+            assert len(q) == nb, "Missmatched length for bodies"                                                          # lqr.jl:59
+        for r in Rs:
+            assert len(r) == mu, "Missmatched length for constraints"                                                     # lqr.jl:60
+        Fd = None if Fτd is None else np.ascontiguousarray(Fτd, dtype=np.float64).reshape(-1, mu)
+        if Fd is not None and Fd.shape[0] != n:
+            raise ValueError("Fτd must be [n_models][mu] = [%d][%d]" % (n, mu))
+        inv = _body_order(bodyids, nb)
+        nw = max(len(Qs), len(Rs))
+        Qm, Rm, Ntemp = [], [], 0
+        for k in range(nw):
+            q, r = Qs[k if len(Qs) > 1 else 0], Rs[k if len(Rs) > 1 else 0]
+            Qb = [np.asarray(q[i], dtype=np.float64) for i in inv]
+            Rb = [np.asarray(x, dtype=np.float64).reshape(1, 1) for x in r]
+            if any(b.shape != (12, 12) for b in Qb):
+                raise ValueError("every Q block must be 12 x 12 (pair %d)" % k)
+            qm, rm, _, nt = _weights_and_horizon(Qb, Rb, math.inf if horizon is None else horizon, mechanism.Δt)
+            Ntemp = 0 if horizon is None else nt
+            Qm.append(qm)
+            Rm.append(rm)
+        self.first_plant = (0 if plants is None else plants.first_index) if first_plant is None else int(first_plant)
+        if plants is not None:
+            plants.rows_for(self.first_plant, n)      # every model must find its plant
+        self.mechanism, self.controller, self.plants, self.n_models = mechanism, controller, plants, n
+        self.eqcids = [int(e) for e in eqcids]
+        self.ctrl_joints = [mechanism.joint_index(e) for e in self.eqcids]
+        self.Q, self.R = np.stack(Qm), np.stack(Rm)      # [n_weights][12 nb][12 nb], [n_weights][mu][mu]: scaled, mechanism body order
+        self.zd, self.Fd, self.N, self.tol, self.max_levels = zd, Fd, Ntemp, float(tol), max_levels
+        dev = _device_mech(mechanism)
+        self._dev, self._setpoints = dev, None
+        ctrl = controller._ctrl_handle(dev)
+        try:
+            self._value, self.levels, self.reason, self.dnorm, self.gnorm = _capi.value_create_policy_doubling(
+                dev, ctrl, zd, self.ctrl_joints, self.Q, self.R, Ntemp, tol=tol, max_levels=max_levels, Fd=Fd,
+                plants=None if plants is None else plants.handle(dev), first_plant=self.first_plant)
+        finally:
+            ctrl.close()
+        to_convergence = Ntemp == 0
+        self.steps = 2 ** self.levels.astype(np.int64) if to_convergence else np.full(n, Ntemp - 1, dtype=np.int64)
+        self.converged = (self.reason == 0) & to_convergence
+        self.diverged = (self.reason == 2) & to_convergence
+        with np.errstate(invalid="ignore", divide="ignore"):
+            self.spectral_radius = (self.gnorm[:, 0] / self.gnorm[:, 1]) ** (1.0 / 2.0 ** (self.levels - 1))
+
+    def P(self, i):
+        """model i's cost-to-go [12 nb][12 nb], mechanism body order, read back from the device (cclqr_value_get)"""
+        return self._value.get(i)
+
+    def _value_handle(self, dev):
+        if self._value.mech is not dev or not self._value.ptr:
+            raise ValueError("the StationaryPolicyValue was evaluated on another device handle of the mechanism")
+        return self._value, False
+
+    def _ctrl_handle(self, dev, **law):
+        """a setpoint-only controller of n_models tables built from zd: what predicted_cost measures model i's error about"""
+        if law:
+            raise TypeError("a StationaryPolicyValue is not a Controller: it holds costs-to-go, not a control law")
+        if dev is not self._dev:
+            raise ValueError("the StationaryPolicyValue was evaluated on another device handle of the mechanism")
+        if self._setpoints is None:
+            self._setpoints = _capi.CtrlHandle(dev, self.ctrl_joints, K=None, N=0, zd=self.zd, n_ctrl=self.n_models if self.n_models > 1 else 0)
+        return _BorrowedCtrl(self._setpoints)
+
+    def close(self):
+        if self._setpoints is not None:
+            self._setpoints.close()
+            self._setpoints = None
+        self._value.close()
+
+
 def _is_device_tensor(a):
     return hasattr(a, "data_ptr") and bool(getattr(a, "is_cuda", False))
 
@@ -1047,6 +1161,8 @@ def simulate(mechanism, tend_or_storage, controller, record=True, z0=None, fric=
     After the call the mechanism's bodies hold instance 0's final state (simulate! mutates the mechanism)."""
     if isinstance(controller, PolicyValue):
         raise TypeError("a PolicyValue is not a Controller: simulate rolls out the controller it evaluates (PolicyValue.controller)")
+    if isinstance(controller, StationaryPolicyValue):
+        raise TypeError("a StationaryPolicyValue is not a Controller: simulate rolls out the controller it evaluates (StationaryPolicyValue.controller)")
     if isinstance(tend_or_storage, Storage):
         steps = tend_or_storage.steps
     else:
@@ -1120,7 +1236,8 @@ def predicted_cost(mechanism, controller, z0, first_instance=0, out=None):
     the linear regime.  controller: an LQR, PlantLQR or LQRSweep built with keep_value=True; instance i reads table first_instance + i of the batched ones.
     That P is the cost on the model the gains were DESIGNED on.  For a controller that runs on another plant (simulate(mech, steps, LQR, plants=)) pass a
     PolicyValue(mech, controller, ..., zd, plants=): V_i = Δz_i' P_i Δz_i with P_i the given gains' cost-to-go on plant i's model (lqr.jl:169-170 with the gain
-    given) and Δz_i the error about plant i's own setpoint zd[i] -- then realised / predicted tells "outside the linear regime" from "model mismatch".
+    given) and Δz_i the error about plant i's own setpoint zd[i] -- then realised / predicted tells "outside the linear regime" from "model mismatch".  A
+    StationaryPolicyValue (the same cost-to-go of a stationary gain, by doubling) is taken the same way.
     z0 [n_inst][nb][13]: a numpy array -> a numpy array [n_inst]; or a float64 device tensor, read in place -> a device tensor [n_inst] (out: the tensor to fill),
     the evaluation left running on the current stream."""
     if not hasattr(controller, "_value_handle"):

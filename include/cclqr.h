@@ -49,7 +49,9 @@ extern "C" {
  * opaque cclqr_value with cclqr_value_create / cclqr_value_get / cclqr_value_destroy, and cclqr_value_eval; looked up the same way.  With P = NULL / value = NULL the
  * first two ARE cclqr_riccati_weights, cclqr_riccati_tv and cclqr_ctrl_create_lqr_batch_weights (which call them).
  * Still 202 (additive, no struct changed): policy evaluation, a gain table's cost-to-go on another model -- cclqr_policy_value, cclqr_value_create_policy; looked up the
- * same way.  Their result is a cost-to-go like cclqr_riccati_value's: cclqr_value_get and cclqr_value_eval take it as it stands. */
+ * same way.  Their result is a cost-to-go like cclqr_riccati_value's: cclqr_value_get and cclqr_value_eval take it as it stands.
+ * Still 202 (additive, no struct changed): a stationary gain's cost-to-go by doubling -- cclqr_policy_value_doubling, cclqr_value_create_policy_doubling; looked up the
+ * same way.  cclqr_policy_value and cclqr_value_create_policy are unchanged. */
 #define CCLQR_ABI_VERSION 202
 
 #define CCLQR_REVOLUTE 0      /* EqualityConstraint(Revolute(a, b, axis; p1, p2, qoffset)),  examples/lqr_cartpole.jl:26 */
@@ -442,6 +444,32 @@ int cclqr_policy_value(int32_t nprob, int32_t mx, int32_t mu, int32_t ml, const 
 int cclqr_value_create_policy(const cclqr_mech *m, const cclqr_plants *plants, int64_t first_plant, int32_t n_models, const double *zd, int32_t mu,
                               const int32_t *ctrl_joint, const double *Fd, const cclqr_ctrl *c, int32_t n_weights, const double *Q, const double *R, int32_t N,
                               double tol, int32_t *kbreak, double *dnorm, cclqr_value **out);
+
+/* Policy evaluation of a STATIONARY gain by doubling (additive, Still 202, no struct changed; looked up by name).  The reference's default controller LQR{T,Inf} keeps
+ * one gain (src/control/lqr.jl:40-43); with it the recursion above has a constant Abar = A - Bu*K - Bλ*Kλ (lqr.jl:169) and Qbar = Q + K'*R*K (lqr.jl:170), and with
+ *     S(n) = sum_{i<n} (Abar^i)' Qbar Abar^i,  M(n) = Abar^n:     S(a+b) = S(a) + M(a)' S(b) M(a),  M(a+b) = M(a) M(b),     P = S(n) + M(n)' Q M(n)
+ * gives the cost-to-go after n backward steps in at most 2 log2(n) combinations instead of n steps.  K [n_gains][mu][mx], Q and R used as written, symmetric or not.
+ *   N >= 1  fixed horizon: n = N - 1 steps exactly, square-and-multiply over the bits of n (least significant first).  P is what cclqr_policy_value returns for nK = 1,
+ *           tol = 0 and the same N, to rounding; no break test and no growth stop (tol and max_levels are not read).  levels = the doublings made, reason = 0,
+ *           dnorm = NaN, gnorm[p][0] = norm(M(n)), gnorm[p][1] = NaN
+ *   N == 0  to convergence: level j = 1, 2, .. doubles to 2^j steps; its increment norm(S(2^j) - S(2^(j-1))) comes out of the doubling.  Stop after level j, in this
+ *           order: reason 0 the increment < tol; reason 2 norm(M(2^j)) > 1e50 (one more level could overflow: the closed loop is unstable on the model); reason 1
+ *           j == max_levels (1 .. 60).  levels = j; dnorm[p][0..1] the increment norms and gnorm[p][0..1] norm(M) of the last level and of the one before, NaN where
+ *           no such level ran.  (gnorm0 / gnorm1)^(1 / 2^(levels-1)) estimates the closed loop's spectral radius (reported, not promised).  All norms Frobenius.
+ * A run that does not converge is NOT an error: reason is the answer.  Results do not depend on the batch a problem is in, nor on whether gains / weights are shared.
+ * cclqr_policy_value_doubling -- HOST pointers, laid out as for cclqr_policy_value; n_gains and n_weights = 1 or nprob; levels, reason [nprob] and dnorm, gnorm
+ * [nprob][2] may be NULL.  opts: as in cclqr_policy_value (only `path`; bf16_terms != 0 is CCLQR_EINVAL).  CCLQR_EINVAL before anything is allocated or launched, with
+ * the outputs untouched: N < 0, max_levels outside 1..60 when N == 0, tol < 0 or NaN, any other count or size.  A singular G*Bλ is CCLQR_ESINGULAR. */
+int cclqr_policy_value_doubling(int32_t nprob, int32_t mx, int32_t mu, int32_t ml, const double *A, const double *Bu, const double *Bl, const double *G,
+                                int32_t n_gains, const double *K, int32_t n_weights, const double *Q, const double *R, int32_t N, double tol, int32_t max_levels,
+                                double *P, int32_t *levels, int32_t *reason, double *dnorm, double *gnorm, const cclqr_riccati_opts *opts);
+/* cclqr_value_create_policy_doubling -- the same evaluation (lqr.jl:169-170 with the one gain of lqr.jl:40-43) for a CONTROLLER on a mechanism's plants (Still 202): the
+ * linearisation and the device-side gather of the gains are those of cclqr_value_create_policy (the gains never visit the host); *out is a cclqr_value of n_models
+ * tables for cclqr_value_eval / cclqr_value_get as it stands.  levels, reason [n_models], dnorm, gnorm [n_models][2]: HOST, or NULL.  Refused as there, and besides:
+ * a controller whose tables hold more than one gain row (a finite-horizon table is what cclqr_value_create_policy steps through) is CCLQR_EINVAL. */
+int cclqr_value_create_policy_doubling(const cclqr_mech *m, const cclqr_plants *plants, int64_t first_plant, int32_t n_models, const double *zd, int32_t mu,
+                                       const int32_t *ctrl_joint, const double *Fd, const cclqr_ctrl *c, int32_t n_weights, const double *Q, const double *R,
+                                       int32_t N, double tol, int32_t max_levels, int32_t *levels, int32_t *reason, double *dnorm, double *gnorm, cclqr_value **out);
 
 /* One TrackingLQR per plant and / or per reference trajectory, in one call -- for every k, TrackingLQR(mechanism_k, storage_k, Fτ_k, eqcids, Q, R)
  * (src/control/lqr_tracking.jl:17-43): linearsystem at the knots 1 .. N-1 of trajectory k (lqr_tracking.jl:88) and the recursion of lqr_tracking.jl:73-122 with its own

@@ -542,6 +542,40 @@ function value_create_policy(h::MechHandle, p::Union{PlantsHandle,Nothing}, n::I
     return obj, kb, dn
 end
 
+"A STATIONARY gain's cost-to-go by doubling (cclqr_policy_value_doubling): the one gain of LQR{T,Inf} (lqr.jl:40-43) makes Abar (lqr.jl:169) and Qbar = Q + K'RK
+ (lqr.jl:170) constant, and S(a+b) = S(a) + M(a)' S(b) M(a) reaches N - 1 steps in at most 2 log2 N combinations.  Ks: one gain (mu x mx) per problem, or a Vector of
+ one shared by all; N >= 1: that horizon exactly (what policy_value gives for a one-row table and tol = 0); N == 0: level by level to convergence.  Returns (P[p],
+ levels[p], reason[p] (0 converged, 1 max_levels, 2 norm(M) > 1e50), dnorm[p], gnorm[p]: the increment norms and norm(M) of the last level and the one before)."
+function policy_value_doubling(As::Vector, Bus::Vector, Bλs::Vector, Gs::Vector, Ks::Vector, Qs::Vector, Rs::Vector, N::Integer; tol = 1e-5, max_levels = 40, path = 0)
+    np = length(As); mx, mu, ml = size(As[1], 1), size(Bus[1], 2), size(Bλs[1], 2)
+    length(Qs) == length(Rs) || throw(AssertionError("Qs and Rs must hold the same number of weight pairs"))
+    rowmajor(Ms) = reduce(vcat, [vec(permutedims(Matrix{Float64}(M))) for M in Ms]; init = Float64[])
+    P = zeros(mx * mx * np); lv = zeros(Int32, np); rs = zeros(Int32, np); dn = zeros(2 * np); gn = zeros(2 * np)
+    opts = Int32[path, 0, 0, 0]                                      # cclqr_riccati_opts: only `path` is read
+    check(ccall((:cclqr_policy_value_doubling, lib), Cint,
+                (Int32, Int32, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int32, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}, Int32,
+                 Float64, Int32, Ptr{Float64}, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}),
+                np, mx, mu, ml, rowmajor(As), rowmajor(Bus), rowmajor(Bλs), rowmajor(Gs), Int32(length(Ks)), rowmajor(Ks), Int32(length(Qs)), rowmajor(Qs), rowmajor(Rs),
+                N, tol, Int32(max_levels), P, lv, rs, dn, gn, opts))
+    P3 = reshape(P, mx, mx, np)                                      # C layout [np][mx][mx]: row-major, so transposed here
+    [permutedims(P3[:, :, p]) for p = 1:np], Int.(lv), Int.(rs), [(dn[2p - 1], dn[2p]) for p = 1:np], [(gn[2p - 1], gn[2p]) for p = 1:np]
+end
+"The doubling evaluation of controller `c`'s stationary gain on a mechanism's plants (cclqr_value_create_policy_doubling): linearisation and gain gather as
+ value_create_policy, then lqr.jl:169-170 by doubling.  N >= 1 knots, or 0 = to convergence.  Returns (ValueHandle of n tables, levels, reason, dnorm 2 x n, gnorm 2 x n)."
+function value_create_policy_doubling(h::MechHandle, p::Union{PlantsHandle,Nothing}, n::Int, zd::Array{Float64}, ctrl_joint::Vector{Int32}, c::CtrlHandle, n_weights::Int,
+                                      Q::Vector{Float64}, R::Vector{Float64}, N::Int; Fd = nothing, first_plant = 0, tol = 1e-5, max_levels = 40)
+    val = Ref{Ptr{Cvoid}}(C_NULL); lv = zeros(Int32, n); rs = zeros(Int32, n); dn = zeros(2, n); gn = zeros(2, n)
+    fd = Fd === nothing ? Ptr{Float64}(C_NULL) : pointer(Fd)
+    GC.@preserve Fd check(ccall((:cclqr_value_create_policy_doubling, lib), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int32, Ptr{Float64}, Int32, Ptr{Int32}, Ptr{Float64}, Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}, Int32, Float64, Int32,
+                 Ptr{Int32}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ref{Ptr{Cvoid}}),
+                h.ptr, p === nothing ? C_NULL : p.ptr, first_plant, Int32(n), zd, Int32(length(ctrl_joint)), ctrl_joint, fd, c.ptr, Int32(n_weights), Q, R, Int32(N), tol,
+                Int32(max_levels), lv, rs, dn, gn, val))
+    obj = ValueHandle(val[], h)
+    finalizer(o -> ccall((:cclqr_value_destroy, lib), Cint, (Ptr{Cvoid},), o.ptr), obj)
+    return obj, lv, rs, dn, gn
+end
+
 "Size the controller handle's Philox workspace before step-per-launch rollouts are captured into a hipGraph (cclqr_ctrl_reserve_noise)."
 reserve_noise!(c::CtrlHandle, n::Integer, steps::Integer) = check(ccall((:cclqr_ctrl_reserve_noise, lib), Cint, (Ptr{Cvoid}, Int64, Int32), c.ptr, n, steps))
 
