@@ -21,7 +21,8 @@ EXPORTS = ["cclqr_last_error", "cclqr_version", "cclqr_device_count", "cclqr_set
            "cclqr_ctrl_create_tracking_batch_plants", "cclqr_ctrl_get_gains", "cclqr_score_create", "cclqr_score_destroy", "cclqr_rollout_score",
            "cclqr_riccati_weights", "cclqr_ctrl_create_lqr_batch_weights",
            "cclqr_riccati_value", "cclqr_ctrl_create_lqr_batch_value", "cclqr_value_create", "cclqr_value_get", "cclqr_value_destroy", "cclqr_value_eval",
-           "cclqr_policy_value", "cclqr_value_create_policy", "cclqr_policy_value_doubling", "cclqr_value_create_policy_doubling"]
+           "cclqr_policy_value", "cclqr_value_create_policy", "cclqr_policy_value_doubling", "cclqr_value_create_policy_doubling",
+           "cclqr_riccati_doubling", "cclqr_ctrl_create_lqr_batch_doubling"]
 ABI_VERSION = 202     # include/cclqr.h CCLQR_ABI_VERSION: the structs below mirror that header (verified field by field against cclqr_abi_layout at load time)
 ROLLOUT_NO_ALLOC = 1  # cclqr_rollout_opts.flags: the call may neither allocate nor synchronise (a hipGraph capture is open on the device)
 ROLLOUT_CARRY_STATUS = 4  # ... `status` is read and written: an instance lost in an earlier launch stays frozen, the others merge this launch's result into it
@@ -301,6 +302,44 @@ class BatchLqrHandle:
             self.close()
         except Exception:
             pass
+
+
+class BatchLqrDoublingHandle(BatchLqrHandle):
+    """cclqr_ctrl* built by cclqr_ctrl_create_lqr_batch_doubling: one stationary gain per setpoint by doubling the Riccati map (lqr.jl:25-27, 39-43, 141-184), gains
+    device-resident, one row per table.  N >= 2: the horizon's first gain; N = 0: to convergence.  levels, reason [n], dnorm, anorm [n][2] as the library reports them;
+    keep_value: every table's P stays on the device as self.value"""
+
+    def __init__(self, mech, zd, ctrl_joint, Q, R, N=0, Fd=None, tol=1e-5, max_levels=40, plants=None, first_plant=0, keep_value=False):
+        nb = mech.tables.nb
+        zd = f64(zd).reshape(-1, nb, 13)
+        n = zd.shape[0]
+        cj = i32(ctrl_joint).reshape(-1)
+        mu = len(cj)
+        Fd = None if Fd is None else f64(Fd).reshape(n, mu)
+        Q = f64(Q).reshape(-1, 12 * nb, 12 * nb)
+        nw = Q.shape[0]
+        R = f64(R).reshape(nw, mu, mu)
+        self.kbreak = None
+        self.levels, self.reason = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+        self.dnorm, self.anorm = np.full((n, 2), np.nan), np.full((n, 2), np.nan)
+        self.mu, self.N, self.nsp, self.n_ctrl = mu, 0, 1, n
+        self._arrs = [zd, cj, Fd, Q, R]
+        self.mech = mech
+        self.plants, self.first_plant = plants, int(first_plant)
+        self.ptr = C.c_void_p()
+        self.value = None
+        vptr = C.c_void_p()
+        check(lib().cclqr_ctrl_create_lqr_batch_doubling(mech.ptr, None if plants is None else plants.ptr, C.c_int64(int(first_plant)), C.c_int32(n), _d(zd), C.c_int32(mu),
+                                                         _i(cj), _d(Fd), C.c_int32(nw), _d(Q), _d(R), C.c_int32(int(N)), C.c_double(float(tol)),
+                                                         C.c_int32(int(max_levels)), _i(self.levels), _i(self.reason), _d(self.dnorm), _d(self.anorm),
+                                                         C.byref(self.ptr), C.byref(vptr) if keep_value else None))
+        if keep_value:
+            self.value = ValueHandle(mech, ptr=vptr, n_tables=n)
+
+
+def ctrl_create_lqr_batch_doubling(mech, zd, ctrl_joint, Q, R, N=0, Fd=None, tol=1e-5, max_levels=40, plants=None, first_plant=0, keep_value=False):
+    """cclqr_ctrl_create_lqr_batch_doubling -> BatchLqrDoublingHandle"""
+    return BatchLqrDoublingHandle(mech, zd, ctrl_joint, Q, R, N, Fd, tol, max_levels, plants, first_plant, keep_value)
 
 
 class ValueHandle:
@@ -831,6 +870,44 @@ def value_create_policy_doubling(mech, ctrl, zd, ctrl_joint, Q, R, N, tol=1e-5, 
                                                    _i(cj), _d(Fd), ctrl.ptr, C.c_int32(nw), _d(Q), _d(R), C.c_int32(int(N)), C.c_double(float(tol)),
                                                    C.c_int32(int(max_levels)), _i(lv), _i(rs), _d(dn), _d(gn), C.byref(vptr)))
     return ValueHandle(mech, ptr=vptr, n_tables=n), lv, rs, dn, gn
+
+
+def riccati_doubling(A, Bu, Bl, G, Q, R, N, tol=1e-5, max_levels=40, bf16_terms=0, want_P=True, want_diag=True, K=None, P=None):
+    """the stationary LQR gain by doubling the Riccati map (cclqr_riccati_doubling; lqr.jl:25-27, 39-43, 141-184).  Models and weights as for riccati_value (Q, R exactly
+    symmetric).  N >= 2: N - 1 steps exactly, what riccati_value(N, tol=0, keep_last=True) returns to rounding; N = 0: level by level to convergence (increment < tol,
+    at most max_levels levels) -> K [nprob][mu][mx], P [nprob][mx][mx], levels [nprob], reason [nprob] (0 converged, 1 max_levels, 2 norm(A) > 1e50 or not finite,
+    3 pivot), dnorm [nprob][2], anorm [nprob][2].  want_P=False passes P = NULL, want_diag=False NULL for the four diagnostics (returned as None); K, P: arrays to
+    write into instead of fresh ones"""
+    A = f64(A)
+    mx = A.shape[-1]
+    A = A.reshape(-1, mx, mx)
+    nprob = A.shape[0]
+    Bu, Bl = f64(Bu), f64(Bl)
+    Bu = Bu.reshape(nprob, mx, Bu.shape[-1] if Bu.ndim > 1 else -1)
+    mu = Bu.shape[2]
+    Bl = Bl.reshape(nprob, mx, Bl.shape[-1] if Bl.ndim > 1 else -1)
+    ml = Bl.shape[2]
+    G = f64(G).reshape(nprob, ml, mx)
+    Q = f64(Q).reshape(-1, mx, mx)
+    nw = Q.shape[0]
+    R = f64(R).reshape(nw, mu, mu)
+    if K is None:
+        K = np.zeros((nprob, mu, mx))
+    if K.shape != (nprob, mu, mx) or K.dtype != np.float64 or not K.flags.c_contiguous:
+        raise ValueError("K must be a contiguous float64 [nprob][mu][mx] = %s (got %s)" % ((nprob, mu, mx), K.shape))
+    if want_P and P is None:
+        P = np.zeros((nprob, mx, mx))
+    if P is not None and (P.shape != (nprob, mx, mx) or P.dtype != np.float64 or not P.flags.c_contiguous):
+        raise ValueError("P must be a contiguous float64 [nprob][mx][mx] = %s (got %s)" % ((nprob, mx, mx), P.shape))
+    lv = np.zeros(nprob, dtype=np.int32) if want_diag else None
+    rs = np.zeros(nprob, dtype=np.int32) if want_diag else None
+    dn = np.zeros((nprob, 2)) if want_diag else None
+    an = np.zeros((nprob, 2)) if want_diag else None
+    o = RiccatiOpts(0, int(bf16_terms), 1, 0)
+    check(lib().cclqr_riccati_doubling(C.c_int32(nprob), C.c_int32(mx), C.c_int32(mu), C.c_int32(ml), _d(A), _d(Bu) if mu else None, _d(Bl) if ml else None,
+                                       _d(G) if ml else None, C.c_int32(nw), _d(Q), _d(R) if mu else None, C.c_int32(int(N)), C.c_double(float(tol)),
+                                       C.c_int32(int(max_levels)), _d(K) if K.size else None, _d(P), _i(lv), _i(rs), _d(dn), _d(an), C.byref(o)))
+    return K, P, lv, rs, dn, an
 
 
 def riccati_tv(A, Bu, Bl, G, Q, R, N, tol=1e-5):

@@ -342,16 +342,36 @@ static cclqr_value* value_new(const cclqr_mech* m, int64_t n_tables) {
 }
 static hipError_t value_alloc(cclqr_value* v) { return hipMalloc((void**)&v->P_dev, (size_t)v->n_tables * 144 * (size_t)v->nb * v->nb * sizeof(double)); }
 
-extern "C" int cclqr_ctrl_create_lqr_batch_value(const cclqr_mech* m, const cclqr_plants* plants, int64_t first_plant, int32_t n_ctrl, const double* zd, int32_t mu,
-                                                 const int32_t* ctrl_joint, const double* Fd, int32_t n_weights, const double* Q, const double* R, int32_t N,
-                                                 int32_t infinite_horizon, double tol, int32_t* kbreak, cclqr_ctrl** out, cclqr_value** value) {
+// what both doubling entry points of the Riccati map refuse about their own arguments, before anything is allocated or launched (riccati_doubling.hip); the
+// n_weights pairs Q [mx][mx], R [mu][mu] have been counted by the caller (check_n_weights)
+static int riccati_doubling_check(int N, double tol, int max_levels, const cclqr_riccati_opts* opts, int mx, int mu, int n_weights, const double* Q, const double* R) {
+    if (N == 1 || N < 0) return fail(CCLQR_EINVAL, "N = " + std::to_string(N) + ": a horizon of N >= 2 knots, or 0 = to convergence");
+    if (N == 0 && (max_levels < 1 || max_levels > 60)) return fail(CCLQR_EINVAL, "max_levels = " + std::to_string(max_levels) + ": 1 .. 60 (2^max_levels steps)");
+    if (!(tol >= 0.0)) return fail(CCLQR_EINVAL, "tol is negative or not a number");
+    if (opts && opts->bf16_terms != 0) return fail(CCLQR_EINVAL, "the Riccati doubling runs in fp64 only (bf16_terms = 0)");
+    if (!riccati_doubling_fits(mx, mu)) return fail(CCLQR_EINVAL, "bad sizes: mx = " + std::to_string(mx) + ", mu = " + std::to_string(mu) + " exceed the LDS panels of the doubling kernels");
+    for (int p = 0; p < n_weights; p++)
+        if (ric_p_rows(Q + (size_t)p * mx * mx, mx, mu == 0 ? R : R + (size_t)p * mu * mu, mu))
+            return fail(CCLQR_EINVAL, "Q or R of weight pair " + std::to_string(p) + " is not symmetric: the composition of Riccati maps holds for exactly symmetric weights only");
+    return CCLQR_OK;
+}
+
+// what cclqr_ctrl_create_lqr_batch_doubling adds to the batched construction: the one gain by doubling the Riccati map (riccati_doubling.hip) in place of the
+// stepped recursion, and where its diagnostics go (host, [n_ctrl] / [n_ctrl][2], each may be null)
+struct LqrDoubling { int max_levels; int32_t *levels, *reason; double *dnorm, *anorm; };
+// The host sequence of the batched LQR constructors, one copy: checks, setpoints, linearisation on the plants, dlqr for every setpoint into the controller's table,
+// link order, publication.  dbl null: the stepped recursion (cclqr_ctrl_create_lqr_batch_value); else the doubling, with infinite_horizon = 1 and N = 0 or >= 2
+static int lqr_batch_build(const cclqr_mech* m, const cclqr_plants* plants, int64_t first_plant, int32_t n_ctrl, const double* zd, int32_t mu,
+                           const int32_t* ctrl_joint, const double* Fd, int32_t n_weights, const double* Q, const double* R, int32_t N,
+                           int32_t infinite_horizon, double tol, int32_t* kbreak, const LqrDoubling* dbl, cclqr_ctrl** out, cclqr_value** value) {
     static const char* const what = "batched LQR construction";
     const bool inf = infinite_horizon != 0;
     if (!m || !zd || !Q || !out || (mu > 0 && (!ctrl_joint || !R))) return fail(CCLQR_EINVAL, "null argument");
     TRY(check_device(m));
     if (m->host.loop) return fail(CCLQR_EUNSUPPORTED, "batched LQR construction is for tree mechanisms (closed loops: cclqr_linearize_projected)");
-    if (n_ctrl < 1 || N < 2 || mu < 1 || mu > m->nb) return fail(CCLQR_EINVAL, "bad sizes");
+    if (n_ctrl < 1 || (!dbl && N < 2) || mu < 1 || mu > m->nb) return fail(CCLQR_EINVAL, "bad sizes");
     TRY(check_n_weights(n_weights, n_ctrl, "table"));
+    if (dbl) TRY(riccati_doubling_check(N, tol, dbl->max_levels, nullptr, 12 * m->nb, mu, n_weights, Q, R));
     const int nb = m->nb;
     const size_t nz = 13 * (size_t)nb, mx = 12 * (size_t)nb, ml = 5 * (size_t)nb, np = (size_t)n_ctrl, nw = (size_t)n_weights;
     CtrlOwner own(ctrl_new(m));
@@ -404,23 +424,65 @@ extern "C" int cclqr_ctrl_create_lqr_batch_value(const cclqr_mech* m, const cclq
     HIPTRY(what, hipMemset(c->K_dev, 0, L.alloc_doubles * sizeof(double)));
     ra.stop = dstop; ra.A = w.A; ra.Bu = w.Bu; ra.Bl = w.Bl; ra.G = w.G; ra.Q = dQ; ra.R = dR; ra.K = c->K_dev; ra.kbreak = dkb; ra.status = dst; ra.work = dwork;
     ra.P_out = vown.p ? vown.p->P_dev : nullptr;      // the models and Q are in the caller's body order, so is the cost-to-go: it stays as the recursion leaves it
-    HIPTRY(what, launch_riccati(ra, nullptr));
+    RdbArgs da;
+    if (dbl) {
+        double *dwork2 = nullptr;
+        HIPTRY(what, ws_get((void**)&dwork2, rdb_work_doubles(n_ctrl, (int)mx) * sizeof(double)));
+        HIPTRY(what, ws_get((void**)&da.levels, np * sizeof(int)));
+        HIPTRY(what, ws_get((void**)&da.reason, np * sizeof(int)));
+        HIPTRY(what, ws_get((void**)&da.dnorm, 2 * np * sizeof(double)));
+        HIPTRY(what, ws_get((void**)&da.anorm, 2 * np * sizeof(double)));
+        da.r = ra; da.max_levels = dbl->max_levels; da.work2 = dwork2;
+        HIPTRY(what, launch_riccati_doubling(da, nullptr));
+    } else
+        HIPTRY(what, launch_riccati(ra, nullptr));
     const long long nrows = (long long)np * (long long)nKtab * mu;
     HIPTRY(what, launch_lds<false>(k_rows_to_link_order_kernel, dim3((unsigned)nrows), dim3(128), mx * sizeof(double), nullptr, c->K_dev, nrows, (long long)nKtab * mu, L.stride, nb, m->dev));
     HIPTRY(what, hipDeviceSynchronize());
     long long bad = -1;
     HIPTRY(what, knots_converged(w.status, np, &bad));
-    HIPTRY(what, hipMemcpy(kb.data(), dkb, np * sizeof(int), hipMemcpyDeviceToHost));
+    if (!dbl) HIPTRY(what, hipMemcpy(kb.data(), dkb, np * sizeof(int), hipMemcpyDeviceToHost));
     HIPTRY(what, hipMemcpy(st.data(), dst, np * sizeof(int), hipMemcpyDeviceToHost));
+    std::vector<int> lv, rs;
+    std::vector<double> dn, an;
+    if (dbl) {
+        lv.resize(np); rs.resize(np); dn.resize(2 * np); an.resize(2 * np);
+        HIPTRY(what, hipMemcpy(lv.data(), da.levels, np * sizeof(int), hipMemcpyDeviceToHost));
+        HIPTRY(what, hipMemcpy(rs.data(), da.reason, np * sizeof(int), hipMemcpyDeviceToHost));
+        HIPTRY(what, hipMemcpy(dn.data(), da.dnorm, 2 * np * sizeof(double), hipMemcpyDeviceToHost));
+        HIPTRY(what, hipMemcpy(an.data(), da.anorm, 2 * np * sizeof(double), hipMemcpyDeviceToHost));
+    }
     HIPTRY(what, ctrl_publish(c));
-    for (size_t p = 0; p < np; p++) {      // kbreak is filled up to the problem the call is refused for
-        if (kbreak) kbreak[p] = kb[p];
+    for (size_t p = 0; p < np; p++) {      // kbreak (the doubling's diagnostics) is filled up to the problem the call is refused for
+        if (kbreak && !dbl) kbreak[p] = kb[p];
+        if (dbl) {
+            if (dbl->levels) dbl->levels[p] = lv[p];
+            if (dbl->reason) dbl->reason[p] = rs[p];
+            if (dbl->dnorm) { dbl->dnorm[2 * p] = dn[2 * p]; dbl->dnorm[2 * p + 1] = dn[2 * p + 1]; }
+            if (dbl->anorm) { dbl->anorm[2 * p] = an[2 * p]; dbl->anorm[2 * p + 1] = an[2 * p + 1]; }
+        }
         if ((long long)p == bad) return fail(CCLQR_ENOCONV, "Newton did not converge at setpoint " + std::to_string(p));
         if (st[p] != 0) return fail(CCLQR_ESINGULAR, "G*Bl or M is singular at setpoint " + std::to_string(p));
     }
     *out = own.release();
     if (value) *value = vown.release();
     return CCLQR_OK;
+}
+
+extern "C" int cclqr_ctrl_create_lqr_batch_value(const cclqr_mech* m, const cclqr_plants* plants, int64_t first_plant, int32_t n_ctrl, const double* zd, int32_t mu,
+                                                 const int32_t* ctrl_joint, const double* Fd, int32_t n_weights, const double* Q, const double* R, int32_t N,
+                                                 int32_t infinite_horizon, double tol, int32_t* kbreak, cclqr_ctrl** out, cclqr_value** value) {
+    return lqr_batch_build(m, plants, first_plant, n_ctrl, zd, mu, ctrl_joint, Fd, n_weights, Q, R, N, infinite_horizon, tol, kbreak, nullptr, out, value);
+}
+
+// LQR{T,Inf}'s one gain (lqr.jl:25-27, 39-43) by doubling the Riccati map of lqr.jl:141-184: cclqr_ctrl_create_lqr_batch_value with infinite_horizon = 1 and the
+// doubling in place of the stepped recursion
+extern "C" int cclqr_ctrl_create_lqr_batch_doubling(const cclqr_mech* m, const cclqr_plants* plants, int64_t first_plant, int32_t n_ctrl, const double* zd, int32_t mu,
+                                                    const int32_t* ctrl_joint, const double* Fd, int32_t n_weights, const double* Q, const double* R, int32_t N,
+                                                    double tol, int32_t max_levels, int32_t* levels, int32_t* reason, double* dnorm, double* anorm,
+                                                    cclqr_ctrl** out, cclqr_value** value) {
+    const LqrDoubling dbl = {max_levels, levels, reason, dnorm, anorm};
+    return lqr_batch_build(m, plants, first_plant, n_ctrl, zd, mu, ctrl_joint, Fd, n_weights, Q, R, N, 1, tol, nullptr, &dbl, out, value);
 }
 
 extern "C" int cclqr_ctrl_create_lqr_batch_weights(const cclqr_mech* m, const cclqr_plants* plants, int64_t first_plant, int32_t n_ctrl, const double* zd, int32_t mu,
@@ -1494,5 +1556,62 @@ extern "C" int cclqr_value_create_policy_doubling(const cclqr_mech* m, const ccl
     TRY(run_doubling(n_models, mx, mu, ml, N, tol, max_levels, w.A, w.Bu, w.Bl, w.G, dK, k_stride, n_weights, Q, R, 0, vown.p->P_dev, o));
     TRY(doubling_report(o, n_models, levels, reason, dnorm, gnorm, "model"));
     *out = vown.release();
+    return CCLQR_OK;
+}
+
+// ---- the Riccati map itself by doubling (riccati_doubling.hip): Ku[1] and the last Pkp1 of lqr.jl:141-184 after N - 1 steps, or at convergence (lqr.jl:25-27, 39-43)
+extern "C" int cclqr_riccati_doubling(int32_t nprob, int32_t mx, int32_t mu, int32_t ml, const double* A, const double* Bu, const double* Bl, const double* G,
+                                      int32_t n_weights, const double* Q, const double* R, int32_t N, double tol, int32_t max_levels, double* K, double* P,
+                                      int32_t* levels, int32_t* reason, double* dnorm, double* anorm, const cclqr_riccati_opts* opts) {
+    static const char* const what = "riccati doubling";
+    if (!A || !Q || (mu > 0 && (!Bu || !R || !K)) || (ml > 0 && (!Bl || !G))) return fail(CCLQR_EINVAL, "null argument");
+    if (nprob < 1 || mx < 1 || mu < 0 || ml < 0) return fail(CCLQR_EINVAL, "bad sizes");
+    TRY(check_n_weights(n_weights, nprob, "problem"));
+    TRY(riccati_doubling_check(N, tol, max_levels, opts, mx, mu, n_weights, Q, R));
+    WsScope scope;
+    RicModels d = {};
+    TRY(upload_models((size_t)nprob, mx, mu, ml, A, Bu, Bl, G, d));
+    const size_t np = (size_t)nprob, nw = (size_t)n_weights, nK = np * mu * mx, nP = np * mx * mx;
+    double *dQ = nullptr, *dR = nullptr, *dK = nullptr, *dP = nullptr, *dwork = nullptr, *dwork2 = nullptr, *ddn = nullptr, *dan = nullptr;
+    int *dlv = nullptr, *drs = nullptr, *dst = nullptr, *dstop = nullptr;
+    RdbArgs a;
+    RicArgs& r = a.r;
+    r.nprob = nprob; r.mx = mx; r.mu = mu; r.ml = ml; r.N = N; r.time_varying = 0; r.tol = tol; r.path = 0; r.bf16_terms = 0; r.keep_last = 1;
+    if (n_weights > 1) { r.q_stride = (long long)mx * mx; r.r_stride = (long long)mu * mu; }
+    HIPTRY(what, ws_get((void**)&dQ, nw * mx * mx * sizeof(double)));
+    HIPTRY(what, ws_get((void**)&dR, (nw * mu * mu + 1) * sizeof(double)));
+    HIPTRY(what, ws_get((void**)&dK, (nK + 1) * sizeof(double)));
+    if (P) HIPTRY(what, ws_get((void**)&dP, nP * sizeof(double)));
+    HIPTRY(what, ws_get((void**)&dwork, ric_total_work_doubles(r) * sizeof(double)));
+    HIPTRY(what, ws_get((void**)&dwork2, rdb_work_doubles(nprob, mx) * sizeof(double)));
+    HIPTRY(what, ws_get((void**)&ddn, 2 * np * sizeof(double)));
+    HIPTRY(what, ws_get((void**)&dan, 2 * np * sizeof(double)));
+    HIPTRY(what, ws_get((void**)&dstop, np * sizeof(int)));
+    HIPTRY(what, ws_get((void**)&dlv, np * sizeof(int)));
+    HIPTRY(what, ws_get((void**)&drs, np * sizeof(int)));
+    HIPTRY(what, ws_get((void**)&dst, np * sizeof(int)));
+    HIPTRY(what, hipMemcpy(dQ, Q, nw * mx * mx * sizeof(double), hipMemcpyHostToDevice));
+    if (mu > 0) HIPTRY(what, hipMemcpy(dR, R, nw * mu * mu * sizeof(double), hipMemcpyHostToDevice));
+    HIPTRY(what, hipMemset(dK, 0, (nK + 1) * sizeof(double)));
+    r.stop = dstop; r.A = d.A; r.Bu = d.Bu; r.Bl = d.Bl; r.G = d.G; r.Q = dQ; r.R = dR; r.K = dK; r.kbreak = nullptr; r.status = dst; r.work = dwork; r.P_out = dP;
+    a.max_levels = max_levels; a.work2 = dwork2; a.levels = dlv; a.reason = drs; a.dnorm = ddn; a.anorm = dan;
+    HIPTRY(what, launch_riccati_doubling(a, nullptr));
+    HIPTRY(what, hipDeviceSynchronize());
+    std::vector<int> lv(np), rs(np), st(np);
+    std::vector<double> dn(2 * np), an(2 * np);
+    HIPTRY(what, hipMemcpy(lv.data(), dlv, np * sizeof(int), hipMemcpyDeviceToHost));
+    HIPTRY(what, hipMemcpy(rs.data(), drs, np * sizeof(int), hipMemcpyDeviceToHost));
+    HIPTRY(what, hipMemcpy(st.data(), dst, np * sizeof(int), hipMemcpyDeviceToHost));
+    HIPTRY(what, hipMemcpy(dn.data(), ddn, 2 * np * sizeof(double), hipMemcpyDeviceToHost));
+    HIPTRY(what, hipMemcpy(an.data(), dan, 2 * np * sizeof(double), hipMemcpyDeviceToHost));
+    if (nK) HIPTRY(what, hipMemcpy(K, dK, nK * sizeof(double), hipMemcpyDeviceToHost));
+    if (P) HIPTRY(what, hipMemcpy(P, dP, nP * sizeof(double), hipMemcpyDeviceToHost));
+    for (size_t p = 0; p < np; p++) {
+        if (levels) levels[p] = lv[p];
+        if (reason) reason[p] = rs[p];
+        if (dnorm) { dnorm[2 * p] = dn[2 * p]; dnorm[2 * p + 1] = dn[2 * p + 1]; }
+        if (anorm) { anorm[2 * p] = an[2 * p]; anorm[2 * p + 1] = an[2 * p + 1]; }
+        if (st[p] != 0) return fail(CCLQR_ESINGULAR, "G*Bl is singular in problem " + std::to_string(p));
+    }
     return CCLQR_OK;
 }

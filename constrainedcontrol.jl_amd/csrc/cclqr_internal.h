@@ -239,6 +239,46 @@ struct DblArgs {
 size_t dbl_work_doubles(const RicArgs& r);
 hipError_t launch_policy_doubling(const DblArgs& a, hipStream_t stream);
 
+// The Riccati map itself by doubling (riccati_doubling.hip): n steps of lqr.jl:151-170 in projected form are the triple (A_n, G_n, H_n) of the map
+// X -> H_n + A_n' X (I + G_n X)^-1 A_n; one step is (A', D R^-1 D', Q), and triple 1 applied after triple 2 is
+//   W = (I + G1 H2)^-1,  A = A2 W A1,  G = G2 + A2 W G1 A2',  H = H1 + A1' H2 W A1
+// r: as for launch_riccati with time_varying = 0, keep_last = 1 (K [nprob][mu][mx] + kpad, device), p_rows = 0 (Q and R symmetric: the caller has refused any other),
+// bf16_terms = 0; r.N = the knots of a fixed horizon (N >= 2: N - 1 single-step triples, no stop test; r.tol is not read) or 0 = level by level to convergence
+// (increment of H < r.tol); P_out may be null; kbreak is not written.  One launch shape for every mx >= 1.
+struct RdbArgs {
+    RicArgs r;
+    int max_levels;          // to convergence: the last level (2^max_levels triples)
+    double* work2;           // device: rdb_work_doubles(nprob, mx) doubles
+    int *levels, *reason;    // device [nprob]: doublings made; why the last one was the last (0 converged / fixed horizon, 1 max_levels, 2 norm(A) > 1e50 or a norm that
+                             // is not finite, 3 a zero or non-finite pivot of I + G1 H2)
+    double *dnorm, *anorm;   // device [nprob][2]: norm(H(2^j) - H(2^(j-1))) and norm(A(2^j)) of the last level and of the one before, NaN where no such level ran
+                             // (fixed horizon: anorm[0] = norm(A_n))
+};
+// the doubles of RdbArgs.work2: two triples, M = I + G1 H2, the solve's result [W A1 | W G1] and two product temporaries, [nprob][mx][mx] each; the per-tile sums of
+// a level's two norms; the pivots of M (ints, a double's room for two)
+static inline size_t rdb_work_doubles(long long nprob, int mx) {
+    const size_t np = (size_t)nprob, mm = (size_t)mx * mx, tm = ((size_t)mx + 31) / 32;
+    return 11 * np * mm + 4 * np * tm * tm + (np * (size_t)mx + 1) / 2 + 8;
+}
+// The schedule of a fixed horizon of n = N - 1 >= 1 single-step triples, square-and-multiply over the bits of n from the least significant: the first set bit copies
+// the doubling triple into the accumulated one, every further set bit composes them, and the doubling triple is composed with itself between bits, not after the
+// top one.  Writes the operations in order into ops (room for RDB_MAX_OPS) and returns their number; compositions = popcount(n) - 1 + bit_length(n) - 1.
+enum { RDB_COPY = 0, RDB_ACCUMULATE = 1, RDB_DOUBLE = 2, RDB_MAX_OPS = 64 };
+static inline int rdb_fixed_schedule(unsigned n, unsigned char* ops) {
+    int count = 0, top = 0;
+    bool have = false;
+    while ((n >> (top + 1)) != 0) top++;
+    for (int b = 0; n != 0 && b <= top; b++) {
+        if ((n >> b) & 1u) { ops[count++] = have ? RDB_ACCUMULATE : RDB_COPY; have = true; }
+        if (b < top) ops[count++] = RDB_DOUBLE;
+    }
+    return count;
+}
+// do the kernels hold these sizes (their LDS panels)?  The entry points refuse a size that does not fit as CCLQR_EINVAL before anything is allocated
+bool riccati_doubling_fits(int mx, int mu);
+// (a run to convergence synchronises `stream` every second level to read the stop flags)
+hipError_t launch_riccati_doubling(const RdbArgs& a, hipStream_t stream);
+
 // ---- one TrackingLQR per plant or trajectory (cclqr_ctrl_create_tracking_batch_plants): the workspace plan, pure host arithmetic
 // Default budget of the call's device workspace.  Per knot a problem holds A (mx^2), Bu (mx mu), Bl and G (mx ml each), [A'|D] (mx (mx + mu)) and the projection
 // scratch (ml^2 + ml (mx + mu)) -- triple cartpole, mx 48, mu 1, ml 20: 2304 + 48 + 960 + 960 + 2352 + 1380 doubles = 64 KB --, so its N = 1000 trajectory takes

@@ -74,6 +74,40 @@ def _weights_and_horizon(Q, R, horizon, Δt):
     return Qm, Rm, N, Ntemp
 
 
+def _pair_lists(Q, R, n, of):
+    """Q, R as PolicyValue, StationaryPolicyValue and StationaryLQR take them -- a single pair (Q: nb blocks of 12 x 12) or lists of one pair per `of` -- as two lists
+    of 1 or n candidates"""
+    single = len(Q) > 0 and np.ndim(Q[0]) == 2
+    Qs, Rs = ([Q], [R]) if single else (list(Q), list(R))
+    if len(Qs) not in (1, n) or len(Rs) not in (1, n):
+        raise ValueError("Q and R must be a single pair or lists of one pair per %s, %d (got %d and %d)" % (of, n, len(Qs), len(Rs)))
+    return Qs, Rs
+
+
+def _scaled_pairs(Qs, Rs, bodyids, nb, mu, horizon, Δt, symmetric=False):
+    """the head of the inner constructor (lqr.jl:18-27) per pair of _pair_lists: the blocks permuted to the mechanism's body order and scaled by Δt ->
+    (Q [n_weights][12 nb][12 nb], R [n_weights][mu][mu], the knots Ntemp of `horizon`).  symmetric: a Q block that is not exactly symmetric is refused"""
+    assert len(bodyids) == nb, "Missmatched length for bodies"                                                            # lqr.jl:59
+    for q in Qs:
+        assert len(q) == nb, "Missmatched length for bodies"                                                              # lqr.jl:59
+    for r in Rs:
+        assert len(r) == mu, "Missmatched length for constraints"                                                         # lqr.jl:60
+    inv = _body_order(bodyids, nb)
+    Qm, Rm, Ntemp = [], [], None
+    for k in range(max(len(Qs), len(Rs))):
+        q, r = Qs[k if len(Qs) > 1 else 0], Rs[k if len(Rs) > 1 else 0]
+        Qb = [np.asarray(q[i], dtype=np.float64) for i in inv]
+        Rb = [np.asarray(x, dtype=np.float64).reshape(1, 1) for x in r]
+        if any(b.shape != (12, 12) for b in Qb):
+            raise ValueError("every Q block must be 12 x 12 (pair %d)" % k)
+        if symmetric and any(not np.array_equal(b, b.T) for b in Qb):
+            raise ValueError("Q of pair %d is not symmetric: the composition of Riccati maps holds for exactly symmetric weights only" % k)
+        qm, rm, _, Ntemp = _weights_and_horizon(Qb, Rb, horizon, Δt)
+        Qm.append(qm)
+        Rm.append(rm)
+    return np.stack(Qm), np.stack(Rm), Ntemp
+
+
 class Controller:
     """abstract type owned by ConstrainedDynamics (lqr.jl:3 `<: Controller`)"""
 
@@ -399,6 +433,86 @@ class LQRSweep(Controller):
         self._handle.close()
 
 
+class StationaryLQR(PlantLQR):
+    """LQR{T,Inf}'s one gain (lqr.jl:25-27, 39-43) CONVERGED, by doubling the Riccati map instead of stepping it: n backward steps of dlqr (lqr.jl:141-184) in projected
+    form are the triple (A_n, G_n, H_n) of the map X -> H_n + A_n' X (I + G_n X)^-1 A_n, and two triples compose in one pivoted solve and five products, so 2^j steps
+    cost j compositions on the device (cclqr_ctrl_create_lqr_batch_doubling); gains and P never leave it.  The reference's 10 s / Δt steps leave anything longer than a
+    cartpole unconverged; a 17-body chain needs about 3500.
+
+    One gain row per table, one table per setpoint zd[i] ([n][nb][13], mechanism body order) on plant first_plant + i of `plants` (None: the mechanism's own plant).
+    Q, R: as for LQR (per-body 12 x 12 and per-constraint 1 x 1 blocks in the order of bodyids / eqcids, scaled by Δt), a single pair or -- as PolicyValue takes them --
+    lists of one pair per table; they must be exactly symmetric.  horizon: None = level by level to convergence: level j doubles to 2^j steps and stops when the
+    increment norm(H(2^j) - H(2^(j-1))) < tol (reason 0), when norm(A(2^j)) > 1e50 or a norm is not finite (reason 2: not stabilisable), on a zero pivot (reason 3), or
+    at j == max_levels (reason 1; 1 .. 60); a number = LQR{T,N}'s first gain Ku[1] (N = ceil(horizon / Δt) knots, math.inf = ceil(10 / Δt)) used as a stationary one.
+
+    gains(i) [1][mu][12 nb], P(i) (keep_value=True), levels [n], steps [n] = 2^levels or N - 1, reason [n], converged = reason == 0 of a run to convergence, dnorm and
+    anorm [n][2]: the increment norms and norm(A) of the last level and of the one before (NaN: no such level).  A table that did not converge is still written:
+    reason is the answer.  A Controller: simulate(mech, steps, ctl, z0=, plants=, score=) runs it as a PlantLQR / LQRSweep of the same tables, predicted_cost takes it
+    with keep_value=True, PolicyValue / StationaryPolicyValue evaluate its gains."""
+
+    def __init__(self, mechanism, bodyids, eqcids, Q, R, zd, horizon=None, Fτd=None, plants=None, first_plant=None, tol=1e-5, max_levels=40, keep_value=False,
+                 controlfunction=None):
+        if controlfunction is not None:
+            raise ValueError("StationaryLQR carries no controlfunction: its gains stay on the device (an LQR with a closure: build an LQR)")
+        if not isinstance(mechanism, Mechanism):
+            raise TypeError("StationaryLQR(mechanism, bodyids, eqcids, Q, R, zd; horizon, ...)")
+        if plants is not None and plants.mechanism is not mechanism:
+            raise ValueError("the PlantBatch was made for another mechanism")
+        mechanism.tables()      # (sets has_loops)
+        if mechanism.has_loops:
+            raise ValueError("StationaryLQR is for tree mechanisms: the batched constructor does not take closed loops")
+        nb, mu = len(mechanism.bodies), len(eqcids)
+        zd = np.ascontiguousarray(zd, dtype=np.float64)
+        if zd.ndim != 3 or zd.shape[1:] != (nb, 13) or zd.shape[0] < 1:
+            raise ValueError("zd must be [n][nb][13] = [n][%d][13], one setpoint per table (got %s)" % (nb, zd.shape))
+        n = zd.shape[0]
+        Qs, Rs = _pair_lists(Q, R, n, "table")
+        max_levels = int(max_levels)
+        if horizon is None and not 1 <= max_levels <= 60:
+            raise ValueError("max_levels = %d: a run to convergence makes 1 .. 60 levels (2^max_levels steps)" % max_levels)
+        if not float(tol) >= 0.0:
+            raise ValueError("tol = %r is negative or not a number" % (tol,))
+        Fd = np.zeros((n, mu)) if Fτd is None else np.ascontiguousarray(Fτd, dtype=np.float64).reshape(-1, mu)
+        if Fd.shape[0] != n:
+            raise ValueError("Fτd must be [n][mu] = [%d][%d], one holding input per table and controlled constraint" % (n, mu))
+        Qm, Rm, Ntemp = _scaled_pairs(Qs, Rs, bodyids, nb, mu, math.inf if horizon is None else horizon, mechanism.Δt, symmetric=True)
+        if horizon is None:
+            Ntemp = 0
+        if Ntemp == 1:
+            raise ValueError("horizon = %r is one knot: a gain needs at least one backward step (N >= 2)" % (horizon,))
+        self.first_plant = (0 if plants is None else plants.first_index) if first_plant is None else int(first_plant)
+        if plants is not None:
+            plants.rows_for(self.first_plant, n)      # every table must find its plant
+        self.mechanism, self.plants, self.n_plant, self.n = mechanism, plants, n, n
+        self.eqcids = [int(e) for e in eqcids]
+        self.ctrl_joints = [mechanism.joint_index(e) for e in self.eqcids]
+        self.controlfunction = None
+        self.zd, self.Fd = zd, Fd
+        self.Q, self.R = Qm, Rm      # [n_weights][12 nb][12 nb], [n_weights][mu][mu]: scaled, mechanism body order
+        self.N, self.horizon_steps, self.NK = 0, math.inf, 12 * nb      # the device convention: one gain row, never gated
+        self.tol, self.max_levels = float(tol), max_levels
+        dev = _device_mech(mechanism)
+        self._handle = _capi.ctrl_create_lqr_batch_doubling(dev, zd, self.ctrl_joints, self.Q, self.R, Ntemp, Fd=Fd, tol=tol, max_levels=max_levels,
+                                                            plants=None if plants is None else plants.handle(dev), first_plant=self.first_plant,
+                                                            keep_value=keep_value)
+        h = self._handle
+        self.levels, self.reason, self.dnorm, self.anorm, self.kbreak = h.levels, h.reason, h.dnorm, h.anorm, None
+        self.steps = 2 ** self.levels.astype(np.int64) if Ntemp == 0 else np.full(n, Ntemp - 1, dtype=np.int64)
+        self.converged = (self.reason == 0) & (Ntemp == 0)
+        if Ntemp == 0 and not self.converged.all():
+            print("[ Info: Riccati recursion did not converge.")      # lqr.jl:41
+
+    def _ctrl_handle(self, dev, fric=None, noise_scale=0.0, noise_seed=None):
+        if fric is not None or noise_scale or noise_seed is not None:
+            raise ValueError("StationaryLQR carries neither joint friction nor noise: the batched constructor builds the plain LQR law")
+        if self.first_plant != 0:
+            raise ValueError("a rollout reads controller table and plant by the global instance index: a StationaryLQR that is rolled out starts at plant 0 "
+                             "(this one at plant %d)" % self.first_plant)
+        if self._handle.mech is not dev or not self._handle.ptr:
+            raise ValueError("the StationaryLQR was designed on another device handle of the mechanism")
+        return _BorrowedCtrl(self._handle)
+
+
 class PolicyValue:
     """Policy evaluation: what the gains of `controller` cost on OTHER models than the one they were designed on, and whether that closed loop is stable there -- the
     question a robustness study starts with (the nominal controller on plant n), answered on the linear model instead of by a nonlinear rollout per plant.  For every
@@ -432,38 +546,18 @@ class PolicyValue:
         if zd.ndim != 3 or zd.shape[1:] != (nb, 13) or zd.shape[0] < 1:
             raise ValueError("zd must be [n_models][nb][13] = [n][%d][13], one setpoint per model (got %s)" % (nb, zd.shape))
         n = zd.shape[0]
-        # a single pair (Q: nb blocks of 12 x 12) or lists of candidates, one pair per model
-        single = len(Q) > 0 and np.ndim(Q[0]) == 2
-        Qs, Rs = ([Q], [R]) if single else (list(Q), list(R))
-        if len(Qs) not in (1, n) or len(Rs) not in (1, n):
-            raise ValueError("Q and R must be a single pair or lists of one pair per model, %d (got %d and %d)" % (n, len(Qs), len(Rs)))
-        assert len(bodyids) == nb, "Missmatched length for bodies"                                                        # lqr.jl:59
-        for q in Qs:
-            assert len(q) == nb, "Missmatched length for bodies"                                                          # lqr.jl:59
-        for r in Rs:
-            assert len(r) == mu, "Missmatched length for constraints"                                                     # lqr.jl:60
+        Qs, Rs = _pair_lists(Q, R, n, "model")
         Fd = None if Fτd is None else np.ascontiguousarray(Fτd, dtype=np.float64).reshape(-1, mu)
         if Fd is not None and Fd.shape[0] != n:
             raise ValueError("Fτd must be [n_models][mu] = [%d][%d]" % (n, mu))
-        inv = _body_order(bodyids, nb)
-        nw = max(len(Qs), len(Rs))
-        Qm, Rm, Ntemp = [], [], None
-        for k in range(nw):
-            q, r = Qs[k if len(Qs) > 1 else 0], Rs[k if len(Rs) > 1 else 0]
-            Qb = [np.asarray(q[i], dtype=np.float64) for i in inv]
-            Rb = [np.asarray(x, dtype=np.float64).reshape(1, 1) for x in r]
-            if any(b.shape != (12, 12) for b in Qb):
-                raise ValueError("every Q block must be 12 x 12 (pair %d)" % k)
-            qm, rm, _, Ntemp = _weights_and_horizon(Qb, Rb, horizon, mechanism.Δt)
-            Qm.append(qm)
-            Rm.append(rm)
+        Qm, Rm, Ntemp = _scaled_pairs(Qs, Rs, bodyids, nb, mu, horizon, mechanism.Δt)
         self.first_plant = (0 if plants is None else plants.first_index) if first_plant is None else int(first_plant)
         if plants is not None:
             plants.rows_for(self.first_plant, n)      # every model must find its plant
         self.mechanism, self.controller, self.plants, self.n_models = mechanism, controller, plants, n
         self.eqcids = [int(e) for e in eqcids]
         self.ctrl_joints = [mechanism.joint_index(e) for e in self.eqcids]
-        self.Q, self.R = np.stack(Qm), np.stack(Rm)      # [n_weights][12 nb][12 nb], [n_weights][mu][mu]: scaled, mechanism body order
+        self.Q, self.R = Qm, Rm      # [n_weights][12 nb][12 nb], [n_weights][mu][mu]: scaled, mechanism body order
         self.zd, self.Fd, self.N, self.tol = zd, Fd, Ntemp, float(tol)
         dev = _device_mech(mechanism)
         self._dev, self._setpoints = dev, None
@@ -534,10 +628,7 @@ class StationaryPolicyValue:
         if zd.ndim != 3 or zd.shape[1:] != (nb, 13) or zd.shape[0] < 1:
             raise ValueError("zd must be [n_models][nb][13] = [n][%d][13], one setpoint per model (got %s)" % (nb, zd.shape))
         n = zd.shape[0]
-        single = len(Q) > 0 and np.ndim(Q[0]) == 2
-        Qs, Rs = ([Q], [R]) if single else (list(Q), list(R))
-        if len(Qs) not in (1, n) or len(Rs) not in (1, n):
-            raise ValueError("Q and R must be a single pair or lists of one pair per model, %d (got %d and %d)" % (n, len(Qs), len(Rs)))
+        Qs, Rs = _pair_lists(Q, R, n, "model")
         max_levels = int(max_levels)
         if horizon is None and not 1 <= max_levels <= 60:
             raise ValueError("max_levels = %d: a run to convergence makes 1 .. 60 levels (2^max_levels steps)" % max_levels)
@@ -546,34 +637,19 @@ class StationaryPolicyValue:
         ctrl_N = int(getattr(controller, "N", 0))      # the device convention of the three controllers: 0 = LQR{T,Inf}, one gain; N > 0 = a table of N - 1 rows
         if ctrl_N > 0 and ctrl_N - 1 != 1:
             raise ValueError("the controller holds a table of %d gain rows: doubling evaluates ONE stationary gain (horizon math.inf); PolicyValue steps through a table" % (ctrl_N - 1))
-        assert len(bodyids) == nb, "Missmatched length for bodies"                                                        # lqr.jl:59
-        for q in Qs:
-            assert len(q) == nb, "Missmatched length for bodies"                                                          # lqr.jl:59
-        for r in Rs:
-            assert len(r) == mu, "Missmatched length for constraints"                                                     # lqr.jl:60
         Fd = None if Fτd is None else np.ascontiguousarray(Fτd, dtype=np.float64).reshape(-1, mu)
         if Fd is not None and Fd.shape[0] != n:
             raise ValueError("Fτd must be [n_models][mu] = [%d][%d]" % (n, mu))
-        inv = _body_order(bodyids, nb)
-        nw = max(len(Qs), len(Rs))
-        Qm, Rm, Ntemp = [], [], 0
-        for k in range(nw):
-            q, r = Qs[k if len(Qs) > 1 else 0], Rs[k if len(Rs) > 1 else 0]
-            Qb = [np.asarray(q[i], dtype=np.float64) for i in inv]
-            Rb = [np.asarray(x, dtype=np.float64).reshape(1, 1) for x in r]
-            if any(b.shape != (12, 12) for b in Qb):
-                raise ValueError("every Q block must be 12 x 12 (pair %d)" % k)
-            qm, rm, _, nt = _weights_and_horizon(Qb, Rb, math.inf if horizon is None else horizon, mechanism.Δt)
-            Ntemp = 0 if horizon is None else nt
-            Qm.append(qm)
-            Rm.append(rm)
+        Qm, Rm, Ntemp = _scaled_pairs(Qs, Rs, bodyids, nb, mu, math.inf if horizon is None else horizon, mechanism.Δt)
+        if horizon is None:
+            Ntemp = 0
         self.first_plant = (0 if plants is None else plants.first_index) if first_plant is None else int(first_plant)
         if plants is not None:
             plants.rows_for(self.first_plant, n)      # every model must find its plant
         self.mechanism, self.controller, self.plants, self.n_models = mechanism, controller, plants, n
         self.eqcids = [int(e) for e in eqcids]
         self.ctrl_joints = [mechanism.joint_index(e) for e in self.eqcids]
-        self.Q, self.R = np.stack(Qm), np.stack(Rm)      # [n_weights][12 nb][12 nb], [n_weights][mu][mu]: scaled, mechanism body order
+        self.Q, self.R = Qm, Rm      # [n_weights][12 nb][12 nb], [n_weights][mu][mu]: scaled, mechanism body order
         self.zd, self.Fd, self.N, self.tol, self.max_levels = zd, Fd, Ntemp, float(tol), max_levels
         dev = _device_mech(mechanism)
         self._dev, self._setpoints = dev, None

@@ -51,7 +51,9 @@ extern "C" {
  * Still 202 (additive, no struct changed): policy evaluation, a gain table's cost-to-go on another model -- cclqr_policy_value, cclqr_value_create_policy; looked up the
  * same way.  Their result is a cost-to-go like cclqr_riccati_value's: cclqr_value_get and cclqr_value_eval take it as it stands.
  * Still 202 (additive, no struct changed): a stationary gain's cost-to-go by doubling -- cclqr_policy_value_doubling, cclqr_value_create_policy_doubling; looked up the
- * same way.  cclqr_policy_value and cclqr_value_create_policy are unchanged. */
+ * same way.  cclqr_policy_value and cclqr_value_create_policy are unchanged.
+ * Still 202 (additive, no struct changed): the stationary LQR gain by doubling the Riccati map -- cclqr_riccati_doubling, cclqr_ctrl_create_lqr_batch_doubling; looked up
+ * the same way.  cclqr_riccati_value and cclqr_ctrl_create_lqr_batch_value are unchanged. */
 #define CCLQR_ABI_VERSION 202
 
 #define CCLQR_REVOLUTE 0      /* EqualityConstraint(Revolute(a, b, axis; p1, p2, qoffset)),  examples/lqr_cartpole.jl:26 */
@@ -470,6 +472,40 @@ int cclqr_policy_value_doubling(int32_t nprob, int32_t mx, int32_t mu, int32_t m
 int cclqr_value_create_policy_doubling(const cclqr_mech *m, const cclqr_plants *plants, int64_t first_plant, int32_t n_models, const double *zd, int32_t mu,
                                        const int32_t *ctrl_joint, const double *Fd, const cclqr_ctrl *c, int32_t n_weights, const double *Q, const double *R,
                                        int32_t N, double tol, int32_t max_levels, int32_t *levels, int32_t *reason, double *dnorm, double *gnorm, cclqr_value **out);
+
+/* The stationary LQR gain by doubling the Riccati map (additive, Still 202, no struct changed; looked up by name).  LQR{T,Inf} steps dlqr Ntemp = 10 s / Δt times and
+ * keeps Ku[1] (src/control/lqr.jl:25-27, 39-43), converged or not.  In projected form a backward step of dlqr (lqr.jl:141-184, its step lqr.jl:151-170) is
+ *     Ku = (R + D'PD)^-1 D'P A',    Pkp1 = Q + A'' P (I + G0 P)^-1 A'    with G0 = D R^-1 D'
+ * and n steps are the triple (A_n, G_n, H_n) of the map X -> H_n + A_n' X (I + G_n X)^-1 A_n, H_n = the recursion's Pk after n - 1 steps.  One step is (A', G0, Q), and
+ * triple 1 applied after triple 2 is     W = (I + G1 H2)^-1,  A = A2 W A1,  G = G2 + A2 W G1 A2',  H = H1 + A1' H2 W A1
+ * (one partially pivoted solve and five products), so n steps cost at most 2 log2(n) compositions.  The final step is taken in the recursion's own form on X = H_n.
+ * Q and R must be EXACTLY symmetric: the composition does not hold otherwise.
+ *   N >= 2  fixed horizon: n = N - 1 single-step triples, square-and-multiply over the bits of n (least significant first).  K is Ku[1] of dlqr(.., N) with tol = 0 and P
+ *           its last Pkp1: what cclqr_riccati_value(N, tol = 0, keep_last) returns, to rounding.  No stop test (tol and max_levels are not read).  levels = the
+ *           doublings made, reason = 0, dnorm = NaN, anorm[p][0] = norm(A_n), anorm[p][1] = NaN
+ *   N == 0  to convergence: level j = 1, 2, .. doubles to 2^j triples; the increment norm(H(2^j) - H(2^(j-1))) comes out of the composition.  Stop after level j, in this
+ *           order: reason 0 the increment < tol; reason 2 norm(A(2^j)) > 1e50 or a norm of the level that is not finite (the model is not stabilisable: one more level
+ *           could overflow); reason 3 an exactly zero or non-finite pivot of I + G1 H2 (the triple of the level before is kept); reason 1 j == max_levels (1 .. 60).
+ *           The result equals the fixed horizon N = 2^levels + 1.  dnorm[p][0..1] the increment norms and anorm[p][0..1] norm(A) of the last level and of the one
+ *           before, NaN where no such level ran.  All norms Frobenius.
+ * A problem that ends with reason 1, 2 or 3 is NOT an error of the call: its gain is still written, finite or not, and reason is the answer.  Results do not depend on
+ * the batch a problem is in, nor on whether the weights are shared.
+ * cclqr_riccati_doubling -- HOST pointers, laid out as for cclqr_riccati_value: K [nprob][mu][mx]; P [nprob][mx][mx] or NULL; n_weights = 1 or nprob; levels, reason
+ * [nprob] and dnorm, anorm [nprob][2] may be NULL.  opts: only bf16_terms is looked at, and bf16_terms != 0 is CCLQR_EINVAL.  CCLQR_EINVAL before anything is allocated
+ * or launched, with the outputs untouched: N == 1 or N < 0, max_levels outside 1..60 when N == 0, tol < 0 or NaN, n_weights neither 1 nor nprob, a Q or R that is not
+ * exactly symmetric, any other bad size (among them an mx or mu whose panels the kernels' LDS does not hold: mx beyond 12 800, mu * mx beyond about 9 600).  A
+ * singular G*Bλ is CCLQR_ESINGULAR. */
+int cclqr_riccati_doubling(int32_t nprob, int32_t mx, int32_t mu, int32_t ml, const double *A, const double *Bu, const double *Bl, const double *G,
+                           int32_t n_weights, const double *Q, const double *R, int32_t N, double tol, int32_t max_levels, double *K, double *P,
+                           int32_t *levels, int32_t *reason, double *dnorm, double *anorm, const cclqr_riccati_opts *opts);
+/* cclqr_ctrl_create_lqr_batch_doubling -- LQR{T,Inf} (lqr.jl:25-27, 39-43) for n_ctrl setpoints / plants / weight pairs with the gain by the doubling above (Still 202):
+ * cclqr_ctrl_create_lqr_batch_value with infinite_horizon = 1 and the doubling in place of the stepped recursion -- the same checks, the same linearisation on the
+ * plants, one gain row per table, the same link order and pad; the gains and P never visit the host.  N, tol, max_levels as above; levels, reason [n_ctrl], dnorm, anorm
+ * [n_ctrl][2]: HOST, or NULL; value NULL: no P is kept.  Refused as there (closed-loop mechanisms: CCLQR_EUNSUPPORTED) and as above; a setpoint whose Newton solve or
+ * G*Bλ fails is CCLQR_ENOCONV / CCLQR_ESINGULAR. */
+int cclqr_ctrl_create_lqr_batch_doubling(const cclqr_mech *m, const cclqr_plants *plants, int64_t first_plant, int32_t n_ctrl, const double *zd, int32_t mu,
+                                         const int32_t *ctrl_joint, const double *Fd, int32_t n_weights, const double *Q, const double *R, int32_t N, double tol,
+                                         int32_t max_levels, int32_t *levels, int32_t *reason, double *dnorm, double *anorm, cclqr_ctrl **out, cclqr_value **value);
 
 /* One TrackingLQR per plant and / or per reference trajectory, in one call -- for every k, TrackingLQR(mechanism_k, storage_k, Fτ_k, eqcids, Q, R)
  * (src/control/lqr_tracking.jl:17-43): linearsystem at the knots 1 .. N-1 of trajectory k (lqr_tracking.jl:88) and the recursion of lqr_tracking.jl:73-122 with its own

@@ -576,6 +576,41 @@ function value_create_policy_doubling(h::MechHandle, p::Union{PlantsHandle,Nothi
     return obj, lv, rs, dn, gn
 end
 
+"The stationary LQR gain by doubling the Riccati map (cclqr_riccati_doubling): n backward steps of dlqr (lqr.jl:141-184) are a triple (A_n, G_n, H_n), two triples compose
+ in one pivoted solve and five products, and the one gain LQR{T,Inf} keeps (lqr.jl:25-27, 39-43) is reached in log2 n compositions.  Qs, Rs: one exactly symmetric pair,
+ or one per problem.  N >= 2: Ku[1] and the last Pkp1 of dlqr(.., N) with tol = 0; N == 0: level by level to convergence.  Returns (K[p], P[p], levels[p], reason[p]
+ (0 converged, 1 max_levels, 2 norm(A) > 1e50 or not finite, 3 pivot), dnorm[p], anorm[p]: the increment norms and norm(A) of the last level and the one before)."
+function riccati_doubling(As::Vector, Bus::Vector, Bλs::Vector, Gs::Vector, Qs::Vector, Rs::Vector, N::Integer; tol = 1e-5, max_levels = 40)
+    np = length(As); mx, mu, ml = size(As[1], 1), size(Bus[1], 2), size(Bλs[1], 2)
+    length(Qs) == length(Rs) || throw(AssertionError("Qs and Rs must hold the same number of weight pairs"))
+    rowmajor(Ms) = reduce(vcat, [vec(permutedims(Matrix{Float64}(M))) for M in Ms]; init = Float64[])
+    K = zeros(mu * mx * np); P = zeros(mx * mx * np); lv = zeros(Int32, np); rs = zeros(Int32, np); dn = zeros(2 * np); an = zeros(2 * np)
+    opts = Int32[0, 0, 1, 0]                                         # cclqr_riccati_opts: only bf16_terms is looked at
+    check(ccall((:cclqr_riccati_doubling, lib), Cint,
+                (Int32, Int32, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}, Int32, Float64, Int32,
+                 Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}),
+                np, mx, mu, ml, rowmajor(As), rowmajor(Bus), rowmajor(Bλs), rowmajor(Gs), Int32(length(Qs)), rowmajor(Qs), rowmajor(Rs), N, tol, Int32(max_levels),
+                K, P, lv, rs, dn, an, opts))
+    K3 = reshape(K, mx, mu, np); P3 = reshape(P, mx, mx, np)         # C layouts [np][mu][mx], [np][mx][mx]: row-major, so transposed here
+    [permutedims(K3[:, :, p]) for p = 1:np], [permutedims(P3[:, :, p]) for p = 1:np], Int.(lv), Int.(rs), [(dn[2p - 1], dn[2p]) for p = 1:np],
+        [(an[2p - 1], an[2p]) for p = 1:np]
+end
+"lqr_batch_value with infinite_horizon and the gain by the doubling above (cclqr_ctrl_create_lqr_batch_doubling): one gain row per table, gains and P device-resident.
+ N >= 2 knots, or 0 = to convergence.  Returns (controller pointer, ValueHandle, levels, reason, dnorm 2 x n, anorm 2 x n)."
+function lqr_batch_doubling(h::MechHandle, p::Union{PlantsHandle,Nothing}, n::Int, zd::Array{Float64}, ctrl_joint::Vector{Int32}, n_weights::Int, Q::Vector{Float64},
+                            R::Vector{Float64}, N::Int; Fd = nothing, first_plant = 0, tol = 1e-5, max_levels = 40)
+    out = Ref{Ptr{Cvoid}}(C_NULL); val = Ref{Ptr{Cvoid}}(C_NULL); lv = zeros(Int32, n); rs = zeros(Int32, n); dn = zeros(2, n); an = zeros(2, n)
+    fd = Fd === nothing ? Ptr{Float64}(C_NULL) : pointer(Fd)
+    GC.@preserve Fd check(ccall((:cclqr_ctrl_create_lqr_batch_doubling, lib), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int32, Ptr{Float64}, Int32, Ptr{Int32}, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}, Int32, Float64, Int32,
+                 Ptr{Int32}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ref{Ptr{Cvoid}}, Ref{Ptr{Cvoid}}),
+                h.ptr, p === nothing ? C_NULL : p.ptr, first_plant, Int32(n), zd, Int32(length(ctrl_joint)), ctrl_joint, fd, Int32(n_weights), Q, R, Int32(N), tol,
+                Int32(max_levels), lv, rs, dn, an, out, val))
+    obj = ValueHandle(val[], h)
+    finalizer(o -> ccall((:cclqr_value_destroy, lib), Cint, (Ptr{Cvoid},), o.ptr), obj)
+    return out[], obj, lv, rs, dn, an
+end
+
 "Size the controller handle's Philox workspace before step-per-launch rollouts are captured into a hipGraph (cclqr_ctrl_reserve_noise)."
 reserve_noise!(c::CtrlHandle, n::Integer, steps::Integer) = check(ccall((:cclqr_ctrl_reserve_noise, lib), Cint, (Ptr{Cvoid}, Int64, Int32), c.ptr, n, steps))
 
