@@ -22,7 +22,7 @@ EXPORTS = ["cclqr_last_error", "cclqr_version", "cclqr_device_count", "cclqr_set
            "cclqr_riccati_weights", "cclqr_ctrl_create_lqr_batch_weights",
            "cclqr_riccati_value", "cclqr_ctrl_create_lqr_batch_value", "cclqr_value_create", "cclqr_value_get", "cclqr_value_destroy", "cclqr_value_eval",
            "cclqr_policy_value", "cclqr_value_create_policy", "cclqr_policy_value_doubling", "cclqr_value_create_policy_doubling",
-           "cclqr_riccati_doubling", "cclqr_ctrl_create_lqr_batch_doubling"]
+           "cclqr_riccati_doubling", "cclqr_ctrl_create_lqr_batch_doubling", "cclqr_covariance_doubling", "cclqr_value_create_covariance_doubling"]
 ABI_VERSION = 202     # include/cclqr.h CCLQR_ABI_VERSION: the structs below mirror that header (verified field by field against cclqr_abi_layout at load time)
 ROLLOUT_NO_ALLOC = 1  # cclqr_rollout_opts.flags: the call may neither allocate nor synchronise (a hipGraph capture is open on the device)
 ROLLOUT_CARRY_STATUS = 4  # ... `status` is read and written: an instance lost in an earlier launch stays frozen, the others merge this launch's result into it
@@ -870,6 +870,98 @@ def value_create_policy_doubling(mech, ctrl, zd, ctrl_joint, Q, R, N, tol=1e-5, 
                                                    _i(cj), _d(Fd), ctrl.ptr, C.c_int32(nw), _d(Q), _d(R), C.c_int32(int(N)), C.c_double(float(tol)),
                                                    C.c_int32(int(max_levels)), _i(lv), _i(rs), _d(dn), _d(gn), C.byref(vptr)))
     return ValueHandle(mech, ptr=vptr, n_tables=n), lv, rs, dn, gn
+
+
+def _noise_arrays(Wu, Sigma0, mu, mx):
+    """Wu [mu][mu] or [n][mu][mu], Sigma0 [mx][mx] or [n][mx][mx], either None -> (Wu [n_noise][mu][mu] or None, Sigma0 [n_noise][mx][mx] or None, n_noise); both
+    given: the same count"""
+    if Wu is not None:
+        Wu = f64(Wu)
+        if Wu.ndim not in (2, 3) or Wu.shape[-2:] != (mu, mu):
+            raise ValueError("Wu must be [mu][mu] or [n_noise][mu][mu] with mu = %d (got %s)" % (mu, Wu.shape))
+        Wu = np.ascontiguousarray(Wu.reshape(-1, mu, mu))
+    if Sigma0 is not None:
+        Sigma0 = f64(Sigma0)
+        if Sigma0.ndim not in (2, 3) or Sigma0.shape[-2:] != (mx, mx):
+            raise ValueError("Sigma0 must be [mx][mx] or [n_noise][mx][mx] with mx = %d (got %s)" % (mx, Sigma0.shape))
+        Sigma0 = np.ascontiguousarray(Sigma0.reshape(-1, mx, mx))
+    if Wu is not None and Sigma0 is not None and Wu.shape[0] != Sigma0.shape[0]:
+        if Wu.shape[0] == 1:
+            Wu = np.ascontiguousarray(np.repeat(Wu, Sigma0.shape[0], axis=0))
+        elif Sigma0.shape[0] == 1:
+            Sigma0 = np.ascontiguousarray(np.repeat(Sigma0, Wu.shape[0], axis=0))
+        else:
+            raise ValueError("Wu and Sigma0 hold %d and %d matrices: one shared by all, or one per problem" % (Wu.shape[0], Sigma0.shape[0]))
+    n_noise = Wu.shape[0] if Wu is not None else (Sigma0.shape[0] if Sigma0 is not None else 1)
+    return Wu, Sigma0, n_noise
+
+
+def covariance_doubling(A, Bu, Bl, G, K, Q, R, Wu, Sigma0, N, tol=1e-8, max_levels=40, path=0, bf16_terms=0, want_cost=True, want_std=True, want_diag=True):
+    """the closed-loop state covariance of a stationary gain under input noise, by doubling (cclqr_covariance_doubling; lqr.jl:169 with the one gain of lqr.jl:40-43 and
+    the noise of trackingLQR_triple_cartpole.jl:98).  Models, K, Q, R as for policy_value_doubling (Q = R = None with want_cost=False); Wu [mu][mu] or [n][mu][mu],
+    Sigma0 [mx][mx] or [n][mx][mx], either None (= 0).  N >= 1: N - 1 steps exactly from Sigma0; N = 0: the steady state (Sigma0 must be None), level by level until
+    the increment relative to w = 2^floor(log2 tr(D Wu D')) falls below tol -> Sigma [nprob][mx][mx], cost [nprob][2] (tr(Q Sigma), tr(R K Sigma K')), zstd [nprob][mx],
+    ustd [nprob][mu], levels, reason, dnorm, gnorm as there (dnorm in Sigma's units).  want_cost / want_std / want_diag = False pass NULL (returned as None)"""
+    A = f64(A)
+    mx = A.shape[-1]
+    A = A.reshape(-1, mx, mx)
+    nprob = A.shape[0]
+    Bu, Bl = f64(Bu), f64(Bl)
+    Bu = Bu.reshape(nprob, mx, Bu.shape[-1] if Bu.ndim > 1 else -1)
+    mu = Bu.shape[2]
+    Bl = Bl.reshape(nprob, mx, Bl.shape[-1] if Bl.ndim > 1 else -1)
+    ml = Bl.shape[2]
+    G = f64(G).reshape(nprob, ml, mx)
+    K = f64(K)
+    if K.ndim not in (2, 3) or K.shape[-2:] != (mu, mx):
+        raise ValueError("K must be [mu][mx] or [n_gains][mu][mx] with mu = %d, mx = %d (got %s)" % (mu, mx, K.shape))
+    if K.ndim == 2:
+        K = K[None]
+    nw = 1
+    if Q is not None:
+        Q = f64(Q).reshape(-1, mx, mx)
+        nw = Q.shape[0]
+        R = f64(R).reshape(nw, mu, mu)
+    Wu, Sigma0, n_noise = _noise_arrays(Wu, Sigma0, mu, mx)
+    S = np.zeros((nprob, mx, mx))
+    cost = np.zeros((nprob, 2)) if want_cost else None
+    zstd = np.zeros((nprob, mx)) if want_std else None
+    ustd = np.zeros((nprob, mu)) if want_std else None
+    lv = np.zeros(nprob, dtype=np.int32) if want_diag else None
+    rs = np.zeros(nprob, dtype=np.int32) if want_diag else None
+    dn = np.zeros((nprob, 2)) if want_diag else None
+    gn = np.zeros((nprob, 2)) if want_diag else None
+    o = RiccatiOpts(int(path), int(bf16_terms), 0, 0)
+    check(lib().cclqr_covariance_doubling(C.c_int32(nprob), C.c_int32(mx), C.c_int32(mu), C.c_int32(ml), _d(A), _d(Bu) if mu else None, _d(Bl) if ml else None,
+                                          _d(G) if ml else None, C.c_int32(K.shape[0]), _d(K) if K.size else None, C.c_int32(nw), _d(Q), _d(R) if mu else None,
+                                          C.c_int32(n_noise), _d(Wu), _d(Sigma0), C.c_int32(int(N)), C.c_double(float(tol)), C.c_int32(int(max_levels)), _d(S),
+                                          _d(cost), _d(zstd), _d(ustd) if mu else None, _i(lv), _i(rs), _d(dn), _d(gn), C.byref(o)))
+    return S, cost, zstd, ustd, lv, rs, dn, gn
+
+
+def value_create_covariance_doubling(mech, ctrl, zd, ctrl_joint, Q, R, Wu, Sigma0, N, tol=1e-8, max_levels=40, Fd=None, plants=None, first_plant=0):
+    """cclqr_value_create_covariance_doubling: the covariance above for controller handle `ctrl`'s stationary gain on the models linearised as for
+    value_create_policy_doubling; Q, Sigma0 in the mechanism's body order.  N >= 1 knots, or 0 = the steady state -> (ValueHandle of n_models tables holding Sigma,
+    cost [n][2], zstd [n][12 nb], ustd [n][mu], levels, reason, dnorm [n][2], gnorm [n][2])"""
+    nb = mech.tables.nb
+    zd = f64(zd).reshape(-1, nb, 13)
+    n = zd.shape[0]
+    cj = i32(ctrl_joint).reshape(-1)
+    mu = len(cj)
+    Fd = None if Fd is None else f64(Fd).reshape(n, mu)
+    Q = f64(Q).reshape(-1, 12 * nb, 12 * nb)
+    nw = Q.shape[0]
+    R = f64(R).reshape(nw, mu, mu)
+    Wu, Sigma0, n_noise = _noise_arrays(Wu, Sigma0, mu, 12 * nb)
+    cost, zstd, ustd = np.zeros((n, 2)), np.zeros((n, 12 * nb)), np.zeros((n, mu))
+    lv, rs = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+    dn, gn = np.zeros((n, 2)), np.zeros((n, 2))
+    vptr = C.c_void_p()
+    check(lib().cclqr_value_create_covariance_doubling(mech.ptr, None if plants is None else plants.ptr, C.c_int64(int(first_plant)), C.c_int32(n), _d(zd), C.c_int32(mu),
+                                                       _i(cj), _d(Fd), ctrl.ptr, C.c_int32(nw), _d(Q), _d(R), C.c_int32(n_noise), _d(Wu), _d(Sigma0), C.c_int32(int(N)),
+                                                       C.c_double(float(tol)), C.c_int32(int(max_levels)), _d(cost), _d(zstd), _d(ustd), _i(lv), _i(rs), _d(dn), _d(gn),
+                                                       C.byref(vptr)))
+    return ValueHandle(mech, ptr=vptr, n_tables=n), cost, zstd, ustd, lv, rs, dn, gn
 
 
 def riccati_doubling(A, Bu, Bl, G, Q, R, N, tol=1e-5, max_levels=40, bf16_terms=0, want_P=True, want_diag=True, K=None, P=None):

@@ -1460,42 +1460,63 @@ static int doubling_check(int nprob, int N, double tol, int max_levels, int n_we
     if (opts && opts->bf16_terms != 0) return fail(CCLQR_EINVAL, "policy evaluation runs in fp64 only (bf16_terms = 0)");
     return check_n_weights(n_weights, nprob, of);
 }
-// the host results of run_doubling
+// the host results of run_doubling and run_covariance
 struct DblOut { std::vector<int> lv, rs, st; std::vector<double> dn, gn; };
-// shared tail of the two entry points, as run_policy is: the evaluation on device-resident models and gains, inside the caller's WsScope
-static int run_doubling(int nprob, int mx, int mu, int ml, int N, double tol, int max_levels, const double* dA, const double* dBu, const double* dBl, const double* dG,
-                        const double* dK, long long k_stride, int n_weights, const double* Q, const double* R, int path, double* dP, DblOut& o) {
-    static const char* const what = "policy evaluation by doubling";
-    double *dQ = nullptr, *dR = nullptr, *dwork = nullptr, *dwork2 = nullptr, *ddn = nullptr, *dgn = nullptr;
+// what the two runs share before their launch, inside the caller's WsScope: the sizes, the models and gains, the two workspaces (work2_doubles: the launch's own
+// count, from the sizes set here) and the device diagnostics of a DblArgs; Q, R and P_out are the caller's to set
+static int doubling_args(DblArgs& a, int nprob, int mx, int mu, int ml, int N, double tol, int max_levels, const double* dA, const double* dBu, const double* dBl,
+                         const double* dG, const double* dK, long long k_stride, int path, size_t (*work2_doubles)(const RicArgs&), const char* what) {
+    double *dwork = nullptr, *dwork2 = nullptr, *ddn = nullptr, *dgn = nullptr;
     int *dlv = nullptr, *drs = nullptr, *dst = nullptr, *dstop = nullptr;
-    const size_t np = (size_t)nprob, nw = (size_t)n_weights;
-    DblArgs a;
+    const size_t np = (size_t)nprob;
     RicArgs& r = a.r;
     r.nprob = nprob; r.mx = mx; r.mu = mu; r.ml = ml; r.N = N; r.time_varying = 0; r.tol = tol; r.path = path; r.bf16_terms = 0; r.keep_last = 0; r.K = nullptr;
-    if (n_weights > 1) { r.q_stride = (long long)mx * mx; r.r_stride = (long long)mu * mu; }
-    HIPTRY(what, ws_get((void**)&dQ, nw * mx * mx * sizeof(double)));
-    HIPTRY(what, ws_get((void**)&dR, (nw * mu * mu + 1) * sizeof(double)));
     HIPTRY(what, ws_get((void**)&dwork, ric_total_work_doubles(r) * sizeof(double)));
-    HIPTRY(what, ws_get((void**)&dwork2, dbl_work_doubles(r) * sizeof(double)));
+    HIPTRY(what, ws_get((void**)&dwork2, work2_doubles(r) * sizeof(double)));
     HIPTRY(what, ws_get((void**)&ddn, 2 * np * sizeof(double)));
     HIPTRY(what, ws_get((void**)&dgn, 2 * np * sizeof(double)));
     HIPTRY(what, ws_get((void**)&dstop, np * sizeof(int)));
     HIPTRY(what, ws_get((void**)&dlv, np * sizeof(int)));
     HIPTRY(what, ws_get((void**)&drs, np * sizeof(int)));
     HIPTRY(what, ws_get((void**)&dst, np * sizeof(int)));
-    HIPTRY(what, hipMemcpy(dQ, Q, nw * mx * mx * sizeof(double), hipMemcpyHostToDevice));
-    if (mu > 0) HIPTRY(what, hipMemcpy(dR, R, nw * mu * mu * sizeof(double), hipMemcpyHostToDevice));
-    r.stop = dstop; r.A = dA; r.Bu = dBu; r.Bl = dBl; r.G = dG; r.Q = dQ; r.R = dR; r.kbreak = nullptr; r.status = dst; r.work = dwork; r.P_out = dP;
+    r.stop = dstop; r.A = dA; r.Bu = dBu; r.Bl = dBl; r.G = dG; r.kbreak = nullptr; r.status = dst; r.work = dwork;
     a.Kin = dK; a.k_stride = k_stride; a.max_levels = max_levels; a.work2 = dwork2; a.levels = dlv; a.reason = drs; a.dnorm = ddn; a.gnorm = dgn;
-    HIPTRY(what, launch_policy_doubling(a, nullptr));
+    return CCLQR_OK;
+}
+// ... and after it: the launch's diagnostics onto the host
+static int doubling_read_back(const DblArgs& a, DblOut& o, const char* what) {
+    const size_t np = (size_t)a.r.nprob;
     HIPTRY(what, hipDeviceSynchronize());
     o.lv.resize(np); o.rs.resize(np); o.st.resize(np); o.dn.resize(2 * np); o.gn.resize(2 * np);
-    HIPTRY(what, hipMemcpy(o.lv.data(), dlv, np * sizeof(int), hipMemcpyDeviceToHost));
-    HIPTRY(what, hipMemcpy(o.rs.data(), drs, np * sizeof(int), hipMemcpyDeviceToHost));
-    HIPTRY(what, hipMemcpy(o.st.data(), dst, np * sizeof(int), hipMemcpyDeviceToHost));
-    HIPTRY(what, hipMemcpy(o.dn.data(), ddn, 2 * np * sizeof(double), hipMemcpyDeviceToHost));
-    HIPTRY(what, hipMemcpy(o.gn.data(), dgn, 2 * np * sizeof(double), hipMemcpyDeviceToHost));
+    HIPTRY(what, hipMemcpy(o.lv.data(), a.levels, np * sizeof(int), hipMemcpyDeviceToHost));
+    HIPTRY(what, hipMemcpy(o.rs.data(), a.reason, np * sizeof(int), hipMemcpyDeviceToHost));
+    HIPTRY(what, hipMemcpy(o.st.data(), a.r.status, np * sizeof(int), hipMemcpyDeviceToHost));
+    HIPTRY(what, hipMemcpy(o.dn.data(), a.dnorm, 2 * np * sizeof(double), hipMemcpyDeviceToHost));
+    HIPTRY(what, hipMemcpy(o.gn.data(), a.gnorm, 2 * np * sizeof(double), hipMemcpyDeviceToHost));
     return CCLQR_OK;
+}
+// host weights [n_weights][mx][mx], [n_weights][mu][mu] onto the device, inside the caller's WsScope
+static int upload_weights(int mx, int mu, int n_weights, const double* Q, const double* R, double** dQ, double** dR, const char* what) {
+    const size_t nw = (size_t)n_weights;
+    HIPTRY(what, ws_get((void**)dQ, nw * mx * mx * sizeof(double)));
+    HIPTRY(what, ws_get((void**)dR, (nw * mu * mu + 1) * sizeof(double)));
+    HIPTRY(what, hipMemcpy(*dQ, Q, nw * mx * mx * sizeof(double), hipMemcpyHostToDevice));
+    if (mu > 0) HIPTRY(what, hipMemcpy(*dR, R, nw * mu * mu * sizeof(double), hipMemcpyHostToDevice));
+    return CCLQR_OK;
+}
+// shared tail of the two entry points, as run_policy is: the evaluation on device-resident models and gains, inside the caller's WsScope
+static int run_doubling(int nprob, int mx, int mu, int ml, int N, double tol, int max_levels, const double* dA, const double* dBu, const double* dBl, const double* dG,
+                        const double* dK, long long k_stride, int n_weights, const double* Q, const double* R, int path, double* dP, DblOut& o) {
+    static const char* const what = "policy evaluation by doubling";
+    double *dQ = nullptr, *dR = nullptr;
+    DblArgs a;
+    TRY(doubling_args(a, nprob, mx, mu, ml, N, tol, max_levels, dA, dBu, dBl, dG, dK, k_stride, path, dbl_work_doubles, what));
+    TRY(upload_weights(mx, mu, n_weights, Q, R, &dQ, &dR, what));
+    RicArgs& r = a.r;
+    if (n_weights > 1) { r.q_stride = (long long)mx * mx; r.r_stride = (long long)mu * mu; }
+    r.Q = dQ; r.R = dR; r.P_out = dP;
+    HIPTRY(what, launch_policy_doubling(a, nullptr));
+    return doubling_read_back(a, o, what);
 }
 // the diagnostics of run_doubling into the caller's arrays (each may be null), up to the problem the call is refused for
 static int doubling_report(const DblOut& o, int nprob, int32_t* levels, int32_t* reason, double* dnorm, double* gnorm, const char* of) {
@@ -1554,6 +1575,125 @@ extern "C" int cclqr_value_create_policy_doubling(const cclqr_mech* m, const ccl
     TRY(policy_models_and_gains(m, plants, first_plant, n_models, zd, Fd, mu, ctrl_joint, c, tables, w, &dK, &k_stride, what));
     DblOut o;
     TRY(run_doubling(n_models, mx, mu, ml, N, tol, max_levels, w.A, w.Bu, w.Bl, w.G, dK, k_stride, n_weights, Q, R, 0, vown.p->P_dev, o));
+    TRY(doubling_report(o, n_models, levels, reason, dnorm, gnorm, "model"));
+    *out = vown.release();
+    return CCLQR_OK;
+}
+
+// ---- closed-loop state covariance under input noise by doubling (covariance_doubling.hip): Σ⁺ = Abar Σ Abar' + D Wu D' with the one gain of LQR{T,Inf}
+// (lqr.jl:40-43, 169), the noise law of trackingLQR_triple_cartpole.jl:98
+// what both entry points refuse about the noise and the moments, after doubling_check and before anything is allocated or launched
+static int covariance_check(int nprob, int mu, int N, int n_noise, const double* Wu, const double* Sigma0, const double* Q, const double* R, const double* cost,
+                            const char* of) {
+    if (n_noise != 1 && n_noise != nprob)
+        return fail(CCLQR_EINVAL, "n_noise = " + std::to_string(n_noise) + ": Wu / Sigma0 are one shared by all (1) or one per " + of + " (" + std::to_string(nprob) + ")");
+    if (!Wu && !Sigma0) return fail(CCLQR_EINVAL, "Wu and Sigma0 are both null: there is no covariance to propagate");
+    if (Wu && mu == 0) return fail(CCLQR_EINVAL, "Wu is given with mu = 0: there is no input for the noise to enter through");
+    if (cost && (!Q || (mu > 0 && !R))) return fail(CCLQR_EINVAL, "cost is asked for without Q / R");
+    if (N == 0 && Sigma0) return fail(CCLQR_EINVAL, "N = 0 with Sigma0: a steady state does not depend on the start (pass Sigma0 = NULL)");
+    return CCLQR_OK;
+}
+// the host moments of run_covariance; each is filled only if asked for
+struct CovOut { std::vector<double> cost, zstd, ustd; };
+// shared tail of the two entry points, run_doubling's shape: the covariance on device-resident models and gains, inside the caller's WsScope.  dSigma: device
+// [nprob][mx][mx], written by the kernels.  Wu, Sigma0, Q, R: HOST, as the entry points take them
+static int run_covariance(int nprob, int mx, int mu, int ml, int N, double tol, int max_levels, const double* dA, const double* dBu, const double* dBl, const double* dG,
+                          const double* dK, long long k_stride, int n_weights, const double* Q, const double* R, int n_noise, const double* Wu, const double* Sigma0,
+                          int path, double* dSigma, bool want_cost, bool want_zstd, bool want_ustd, DblOut& o, CovOut& m) {
+    static const char* const what = "covariance by doubling";
+    const size_t np = (size_t)nprob, nn = (size_t)n_noise, mm = (size_t)mx * mx, uu = (size_t)mu * mu;
+    CovArgs c{};
+    TRY(doubling_args(c.d, nprob, mx, mu, ml, N, tol, max_levels, dA, dBu, dBl, dG, dK, k_stride, path, cov_work_doubles, what));
+    c.d.r.P_out = dSigma;
+    double *dQ = nullptr, *dR = nullptr, *dWu = nullptr, *dS0 = nullptr, *dcost = nullptr, *dz = nullptr, *du = nullptr;
+    if (want_cost) {
+        TRY(upload_weights(mx, mu, n_weights, Q, R, &dQ, &dR, what));
+        HIPTRY(what, ws_get((void**)&dcost, 2 * np * sizeof(double)));
+        c.Q = dQ; c.R = dR; c.cost = dcost;
+        if (n_weights > 1) { c.q_stride = (long long)mm; c.r_stride = (long long)uu; }
+    }
+    if (Wu) {
+        HIPTRY(what, ws_get((void**)&dWu, nn * uu * sizeof(double)));
+        HIPTRY(what, hipMemcpy(dWu, Wu, nn * uu * sizeof(double), hipMemcpyHostToDevice));
+        c.Wu = dWu; c.wu_stride = n_noise > 1 ? (long long)uu : 0;
+    }
+    if (Sigma0) {
+        HIPTRY(what, ws_get((void**)&dS0, nn * mm * sizeof(double)));
+        HIPTRY(what, hipMemcpy(dS0, Sigma0, nn * mm * sizeof(double), hipMemcpyHostToDevice));
+        c.Sigma0 = dS0; c.s0_stride = n_noise > 1 ? (long long)mm : 0;
+    }
+    if (want_zstd) { HIPTRY(what, ws_get((void**)&dz, np * mx * sizeof(double))); c.zstd = dz; }
+    if (want_ustd) { HIPTRY(what, ws_get((void**)&du, (np * mu + 1) * sizeof(double))); c.ustd = du; }
+    HIPTRY(what, launch_covariance_doubling(c, nullptr));
+    TRY(doubling_read_back(c.d, o, what));
+    if (want_cost) { m.cost.resize(2 * np); HIPTRY(what, hipMemcpy(m.cost.data(), dcost, 2 * np * sizeof(double), hipMemcpyDeviceToHost)); }
+    if (want_zstd) { m.zstd.resize(np * mx); HIPTRY(what, hipMemcpy(m.zstd.data(), dz, np * mx * sizeof(double), hipMemcpyDeviceToHost)); }
+    if (want_ustd && mu > 0) { m.ustd.resize(np * mu); HIPTRY(what, hipMemcpy(m.ustd.data(), du, np * mu * sizeof(double), hipMemcpyDeviceToHost)); }
+    return CCLQR_OK;
+}
+// the moments of run_covariance into the caller's arrays (each may be null), for the problems before the one the call is refused for (doubling_report names it)
+static void covariance_report(const DblOut& o, const CovOut& m, int nprob, int mx, int mu, double* cost, double* zstd, double* ustd) {
+    for (int p = 0; p < nprob && o.st[p] == 0; p++) {
+        if (cost) { cost[2 * p] = m.cost[2 * (size_t)p]; cost[2 * p + 1] = m.cost[2 * (size_t)p + 1]; }
+        if (zstd) memcpy(zstd + (size_t)p * mx, m.zstd.data() + (size_t)p * mx, (size_t)mx * sizeof(double));
+        if (ustd && mu > 0) memcpy(ustd + (size_t)p * mu, m.ustd.data() + (size_t)p * mu, (size_t)mu * sizeof(double));
+    }
+}
+
+extern "C" int cclqr_covariance_doubling(int32_t nprob, int32_t mx, int32_t mu, int32_t ml, const double* A, const double* Bu, const double* Bl, const double* G,
+                                         int32_t n_gains, const double* K, int32_t n_weights, const double* Q, const double* R, int32_t n_noise, const double* Wu,
+                                         const double* Sigma0, int32_t N, double tol, int32_t max_levels, double* Sigma, double* cost, double* zstd, double* ustd,
+                                         int32_t* levels, int32_t* reason, double* dnorm, double* gnorm, const cclqr_riccati_opts* opts) {
+    static const char* const what = "covariance by doubling";
+    if (!A || !Sigma || (mu > 0 && (!Bu || !K)) || (ml > 0 && (!Bl || !G))) return fail(CCLQR_EINVAL, "null argument");
+    if (nprob < 1 || mx < 1 || mu < 0 || ml < 0) return fail(CCLQR_EINVAL, "bad sizes");
+    if (n_gains != 1 && n_gains != nprob)
+        return fail(CCLQR_EINVAL, "n_gains = " + std::to_string(n_gains) + ": one gain shared by all (1) or one per problem (" + std::to_string(nprob) + ")");
+    TRY(doubling_check(nprob, N, tol, max_levels, n_weights, opts, "problem"));
+    TRY(covariance_check(nprob, mu, N, n_noise, Wu, Sigma0, Q, R, cost, "problem"));
+    WsScope scope;
+    RicModels d = {};
+    TRY(upload_models((size_t)nprob, mx, mu, ml, A, Bu, Bl, G, d));
+    const size_t nKd = (size_t)n_gains * mu * mx, nP = (size_t)nprob * mx * mx;
+    double *dK = nullptr, *dP = nullptr;
+    HIPTRY(what, ws_get((void**)&dK, (nKd + 1) * sizeof(double)));
+    HIPTRY(what, ws_get((void**)&dP, nP * sizeof(double)));
+    if (nKd) HIPTRY(what, hipMemcpy(dK, K, nKd * sizeof(double), hipMemcpyHostToDevice));
+    DblOut o;
+    CovOut mo;
+    TRY(run_covariance(nprob, mx, mu, ml, N, tol, max_levels, d.A, d.Bu, d.Bl, d.G, dK, n_gains > 1 ? (long long)mu * mx : 0, n_weights, Q, R, n_noise, Wu, Sigma0,
+                       opts ? opts->path : 0, dP, cost != nullptr, zstd != nullptr, ustd != nullptr, o, mo));
+    HIPTRY(what, hipMemcpy(Sigma, dP, nP * sizeof(double), hipMemcpyDeviceToHost));
+    covariance_report(o, mo, nprob, mx, mu, cost, zstd, ustd);
+    return doubling_report(o, nprob, levels, reason, dnorm, gnorm, "problem");
+}
+
+extern "C" int cclqr_value_create_covariance_doubling(const cclqr_mech* m, const cclqr_plants* plants, int64_t first_plant, int32_t n_models, const double* zd, int32_t mu,
+                                                      const int32_t* ctrl_joint, const double* Fd, const cclqr_ctrl* c, int32_t n_weights, const double* Q, const double* R,
+                                                      int32_t n_noise, const double* Wu, const double* Sigma0, int32_t N, double tol, int32_t max_levels, double* cost,
+                                                      double* zstd, double* ustd, int32_t* levels, int32_t* reason, double* dnorm, double* gnorm, cclqr_value** out) {
+    static const char* const what = "covariance by doubling";
+    if (!m || !zd || !c || !out || (mu > 0 && !ctrl_joint)) return fail(CCLQR_EINVAL, "null argument");
+    int cj[CCLQR_MAXL];
+    int64_t tables = 1;
+    TRY(policy_ctrl_check(m, plants, first_plant, n_models, mu, ctrl_joint, c, n_models < 1 || mu < 1 || mu > m->nb, cj, &tables));
+    if (c->host.nK != 1)
+        return fail(CCLQR_EINVAL, "the controller's tables hold " + std::to_string(c->host.nK) + " gain rows: the covariance by doubling is that of ONE stationary gain");
+    TRY(doubling_check(n_models, N, tol, max_levels, n_weights, nullptr, "model"));
+    TRY(covariance_check(n_models, mu, N, n_noise, Wu, Sigma0, Q, R, cost, "model"));
+    const int nb = m->nb, mx = 12 * nb, ml = 5 * nb;
+    ValueOwner vown(value_new(m, n_models));
+    HIPTRY(what, value_alloc(vown.p));
+    WsScope scope;
+    LinWs w = {};
+    double* dK = nullptr;
+    long long k_stride = 0;
+    TRY(policy_models_and_gains(m, plants, first_plant, n_models, zd, Fd, mu, ctrl_joint, c, tables, w, &dK, &k_stride, what));
+    DblOut o;
+    CovOut mo;
+    TRY(run_covariance(n_models, mx, mu, ml, N, tol, max_levels, w.A, w.Bu, w.Bl, w.G, dK, k_stride, n_weights, Q, R, n_noise, Wu, Sigma0, 0, vown.p->P_dev,
+                       cost != nullptr, zstd != nullptr, ustd != nullptr, o, mo));
+    covariance_report(o, mo, n_models, mx, mu, cost, zstd, ustd);
     TRY(doubling_report(o, n_models, levels, reason, dnorm, gnorm, "model"));
     *out = vown.release();
     return CCLQR_OK;

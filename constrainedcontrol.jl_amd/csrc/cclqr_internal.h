@@ -238,6 +238,28 @@ struct DblArgs {
 };
 size_t dbl_work_doubles(const RicArgs& r);
 hipError_t launch_policy_doubling(const DblArgs& a, hipStream_t stream);
+// ... and its pieces, for a caller that starts the same recursion from a pair of its own (covariance_doubling.hip): dbl_preset clears the flags and presets the
+// diagnostics; the caller's setup kernel then writes (M, S)(1) of every problem to dbl_Md / dbl_Sd, [nprob][mx][mx] each, and raises status / stop of a problem whose
+// G Bλ is singular; launch_doubling_levels runs everything after that: P_out = S(n) + M(n)' Q M(n) with r.Q the terminal matrix (N = 1: P_out = r.Q, no setup needed)
+static inline double* dbl_Md(const DblArgs& a) { return a.work2; }
+static inline double* dbl_Sd(const DblArgs& a) { return a.work2 + (size_t)a.r.nprob * a.r.mx * a.r.mx; }
+hipError_t dbl_preset(const DblArgs& a, hipStream_t stream);
+hipError_t launch_doubling_levels(const DblArgs& a, hipStream_t stream);
+
+// Closed-loop state covariance under input noise, by the same doubling (covariance_doubling.hip): with the one gain K, Δz⁺ = Abar Δz + D w, w ~ (0, Wu), so after n
+// steps from a start of covariance Σ0:  Σ_n = C(n) + M(n) Σ0 M(n)',  C(n) = sum_{i<n} Abar^i W (Abar^i)',  W = D Wu D',  M(n) = Abar^n -- the pair recursion above on
+// (Abar', W) with Σ0 as the terminal matrix.  d: as for launch_policy_doubling, except that d.r.Q / d.r.R are NOT the caller's: the launch points d.r.Q at its scaled
+// copy of Σ0 (q_stride mx^2); d.r.P_out receives Σ.  d.work2 holds cov_work_doubles(d.r) doubles.
+struct CovArgs {
+    DblArgs d;
+    const double *Wu, *Sigma0;   // device [n_noise][mu][mu], [n_noise][mx][mx]; either may be null (= 0)
+    long long wu_stride, s0_stride;   // doubles between consecutive problems' matrices: 0 = one shared by all
+    const double *Q, *R;         // device, the stage-cost weights; read only when cost is given
+    long long q_stride, r_stride;
+    double *cost, *zstd, *ustd;  // device [nprob][2], [nprob][mx], [nprob][mu], each may be null: tr(Q Σ) and tr(R K Σ K'), sqrt(diag Σ), sqrt(diag K Σ K')
+};
+size_t cov_work_doubles(const RicArgs& r);
+hipError_t launch_covariance_doubling(const CovArgs& a, hipStream_t stream);
 
 // The Riccati map itself by doubling (riccati_doubling.hip): n steps of lqr.jl:151-170 in projected form are the triple (A_n, G_n, H_n) of the map
 // X -> H_n + A_n' X (I + G_n X)^-1 A_n; one step is (A', D R^-1 D', Q), and triple 1 applied after triple 2 is

@@ -126,5 +126,7 @@ size_t ric_lay_out(RicGrid& g, const RicArgs& a, double* base);
 // [A' | D] of every knot of every problem into g.AD, the pivots and the singular flag of every knot behind g.scratch (ric_knot_piv), Pk = Q into buffer 0 of g.P:
 // ric_project_kernel, the one projection of the library.  g: laid out by ric_lay_out, with A, Bu, Bl, G, Q and q_stride set
 hipError_t launch_ric_project(const RicGrid& g, const RicArgs& a, hipStream_t stream);
+// the launch record of the doubling kernels for these arguments (policy_doubling.hip): laid out on a.work, with the models, Q, R and their strides, status and stop
+RicGrid dbl_ric_grid(const RicArgs& a);
 
 }  // namespace cclqr

@@ -347,33 +347,53 @@ size_t dbl_work_doubles(const RicArgs& r) {
     return 6 * np * mx * mx + 4 * np * tm * tm + 8;
 }
 
-hipError_t launch_policy_doubling(const DblArgs& p, hipStream_t stream) {
-    const RicArgs& a = p.r;
-    if (a.nprob <= 0) return hipSuccess;
+// the two launch records of a call, from its arguments alone (dbl_ric_grid: the Riccati record, shared with covariance_doubling.hip): the pair (Md, Sd) a setup
+// kernel writes lies at dbl_Md / dbl_Sd (cclqr_internal.h)
+RicGrid dbl_ric_grid(const RicArgs& a) {
     RicGrid g;
     memset(&g, 0, sizeof(g));
     (void)ric_lay_out(g, a, a.work);
     g.A = a.A; g.Bu = a.Bu; g.Bl = a.Bl; g.G = a.G; g.Q = a.Q; g.R = a.R; g.q_stride = a.q_stride; g.r_stride = a.r_stride;
     g.kbreak = a.kbreak; g.status = a.status; g.stop = a.stop;
-    const size_t np = a.nprob, mx = a.mx, mm = mx * mx, mu = a.mu;
-    const int tm = g.tm;
-    DblGrid d;
+    return g;
+}
+static void dbl_records(const DblArgs& p, RicGrid& g, DblGrid& d) {
+    const RicArgs& a = p.r;
+    g = dbl_ric_grid(a);
+    const size_t np = a.nprob, mm = (size_t)a.mx * a.mx;
     d.Kin = p.Kin; d.k_stride = p.k_stride; d.N = a.N; d.max_levels = p.max_levels; d.tol = a.tol;
     d.levels = p.levels; d.reason = p.reason; d.dnorm = p.dnorm; d.gnorm = p.gnorm; d.P_out = a.P_out;
     double* w = p.work2;
-    d.Md = w; d.Sd = w + np * mm; d.Ma = w + 2 * np * mm; d.Sa = w + 3 * np * mm;
-    double *T1 = w + 4 * np * mm, *T2 = w + 5 * np * mm, *partS = w + 6 * np * mm, *partM = partS + 2 * np * tm * tm;
+    d.Md = dbl_Md(p); d.Sd = dbl_Sd(p); d.Ma = w + 2 * np * mm; d.Sa = w + 3 * np * mm;
+}
+
+// before any kernel of a call: flags and diagnostics preset
+hipError_t dbl_preset(const DblArgs& p, hipStream_t stream) {
+    const RicArgs& a = p.r;
+    const size_t np = a.nprob;
     hipError_t e = hipMemsetAsync(a.stop, 0, np * sizeof(int), stream);
     if (e == hipSuccess) e = hipMemsetAsync(a.status, 0, np * sizeof(int), stream);
     if (e == hipSuccess) e = hipMemsetAsync(p.levels, 0, np * sizeof(int), stream);
     if (e == hipSuccess) e = hipMemsetAsync(p.reason, 0, np * sizeof(int), stream);
     if (e == hipSuccess) e = hipMemsetAsync(p.dnorm, 0xff, 2 * np * sizeof(double), stream);      // all bits set: a NaN, "no such level ran"
     if (e == hipSuccess) e = hipMemsetAsync(p.gnorm, 0xff, 2 * np * sizeof(double), stream);
-    if (e != hipSuccess) return e;
+    return e;
+}
+
+// everything after a setup kernel has written the pair (M, S)(1) of every problem and raised the singular flags (N = 1: no setup is needed, the terminal matrix is
+// the answer): the resident-or-tiled choice, the levels, the final sandwich with the terminal matrix a.Q and the fixed horizon's diagnostics
+hipError_t launch_doubling_levels(const DblArgs& p, hipStream_t stream) {
+    const RicArgs& a = p.r;
+    if (a.nprob <= 0) return hipSuccess;
+    RicGrid g;
+    DblGrid d;
+    dbl_records(p, g, d);
+    const size_t np = a.nprob, mx = a.mx, mm = mx * mx;
+    const int tm = g.tm;
+    double* w = p.work2;
+    double *T1 = w + 4 * np * mm, *T2 = w + 5 * np * mm, *partS = w + 6 * np * mm, *partM = partS + 2 * np * tm * tm;
+    hipError_t e = hipSuccess;
     if (a.N == 1) return launch_lds<false>(dbl_no_step_kernel, dim3(a.nprob), dim3(TILE_THREADS), 0, stream, g, d);
-    e = launch_ric_project(g, a, stream);
-    if (e == hipSuccess) e = launch_lds(dbl_setup_kernel, dim3((a.mx + DBL_RU - 1) / DBL_RU, a.nprob), dim3(TILE_THREADS), 2 * mu * mx * sizeof(double), stream, g, d);
-    if (e != hipSuccess) return e;
     // resident wherever the stepping evaluation is (launch_policy: ric_chosen_path, a wavefront's share of the tiles within its registers, two operands within the LDS)
     const int t16 = (a.mx + 15) / 16;
     if (ric_chosen_path(a) == 1 && t16 * t16 <= DBL_TILES * DBL_WAVES && dbl_resident_lds_bytes(a.mx) <= 158 * 1024)
@@ -426,6 +446,22 @@ hipError_t launch_policy_doubling(const DblArgs& p, hipStream_t stream) {
     e = sandwich(Mn, a.Q, a.q_stride, Sn, a.P_out, nullptr, 0);
     if (e == hipSuccess && !conv) e = launch_lds<false>(dbl_fixed_out_kernel, dim3(a.nprob), dim3(TILE_THREADS), 0, stream, (int)mx, top, d, Mn);
     return e;
+}
+
+hipError_t launch_policy_doubling(const DblArgs& p, hipStream_t stream) {
+    const RicArgs& a = p.r;
+    if (a.nprob <= 0) return hipSuccess;
+    hipError_t e = dbl_preset(p, stream);
+    if (e != hipSuccess) return e;
+    if (a.N != 1) {
+        RicGrid g;
+        DblGrid d;
+        dbl_records(p, g, d);
+        e = launch_ric_project(g, a, stream);
+        if (e == hipSuccess) e = launch_lds(dbl_setup_kernel, dim3((a.mx + DBL_RU - 1) / DBL_RU, a.nprob), dim3(TILE_THREADS), 2 * (size_t)a.mu * a.mx * sizeof(double), stream, g, d);
+        if (e != hipSuccess) return e;
+    }
+    return launch_doubling_levels(p, stream);
 }
 
 }  // namespace cclqr

@@ -597,6 +597,49 @@ class PolicyValue:
         self._value.close()
 
 
+def _stationary_arguments(self, name, verb, mechanism, controller, bodyids, eqcids, Q, R, horizon, zd, plants, first_plant, Fτd, tol, max_levels):
+    """what StationaryPolicyValue and StationaryCovariance share before the device is asked: the refusals, the Δt-scaled weights in the mechanism's body order and
+    the fields both keep (mechanism, controller, plants, n_models, first_plant, eqcids, ctrl_joints, Q, R, zd, Fd, N, tol, max_levels) -> (Fd, N: knots, 0 = to
+    convergence)"""
+    if not isinstance(mechanism, Mechanism):
+        raise TypeError("%s(mechanism, controller, bodyids, eqcids, Q, R, horizon, zd; ...)" % name)
+    if not isinstance(controller, (LQR, PlantLQR, LQRSweep)):
+        raise ValueError("%s %s the stationary gain of an LQR, PlantLQR or LQRSweep (got %s)" % (name, verb, type(controller).__name__))
+    if controller.mechanism is not mechanism:
+        raise ValueError("the controller was made for another mechanism")
+    if plants is not None and plants.mechanism is not mechanism:
+        raise ValueError("the PlantBatch was made for another mechanism")
+    nb, mu = len(mechanism.bodies), len(eqcids)
+    zd = np.ascontiguousarray(zd, dtype=np.float64)
+    if zd.ndim != 3 or zd.shape[1:] != (nb, 13) or zd.shape[0] < 1:
+        raise ValueError("zd must be [n_models][nb][13] = [n][%d][13], one setpoint per model (got %s)" % (nb, zd.shape))
+    n = zd.shape[0]
+    Qs, Rs = _pair_lists(Q, R, n, "model")
+    max_levels = int(max_levels)
+    if horizon is None and not 1 <= max_levels <= 60:
+        raise ValueError("max_levels = %d: a run to convergence makes 1 .. 60 levels (2^max_levels steps)" % max_levels)
+    if not float(tol) >= 0.0:
+        raise ValueError("tol = %r is negative or not a number" % (tol,))
+    ctrl_N = int(getattr(controller, "N", 0))      # the device convention of the three controllers: 0 = LQR{T,Inf}, one gain; N > 0 = a table of N - 1 rows
+    if ctrl_N > 0 and ctrl_N - 1 != 1:
+        raise ValueError("the controller holds a table of %d gain rows: doubling evaluates ONE stationary gain (horizon math.inf); PolicyValue steps through a table" % (ctrl_N - 1))
+    Fd = None if Fτd is None else np.ascontiguousarray(Fτd, dtype=np.float64).reshape(-1, mu)
+    if Fd is not None and Fd.shape[0] != n:
+        raise ValueError("Fτd must be [n_models][mu] = [%d][%d]" % (n, mu))
+    Qm, Rm, Ntemp = _scaled_pairs(Qs, Rs, bodyids, nb, mu, math.inf if horizon is None else horizon, mechanism.Δt)
+    if horizon is None:
+        Ntemp = 0
+    self.first_plant = (0 if plants is None else plants.first_index) if first_plant is None else int(first_plant)
+    if plants is not None:
+        plants.rows_for(self.first_plant, n)      # every model must find its plant
+    self.mechanism, self.controller, self.plants, self.n_models = mechanism, controller, plants, n
+    self.eqcids = [int(e) for e in eqcids]
+    self.ctrl_joints = [mechanism.joint_index(e) for e in self.eqcids]
+    self.Q, self.R = Qm, Rm      # [n_weights][12 nb][12 nb], [n_weights][mu][mu]: scaled, mechanism body order
+    self.zd, self.Fd, self.N, self.tol, self.max_levels = zd, Fd, Ntemp, float(tol), max_levels
+    return Fd, Ntemp
+
+
 class StationaryPolicyValue:
     """Policy evaluation of a STATIONARY gain by doubling: what PolicyValue answers for the reference's default controller LQR{T,Inf} -- one gain (lqr.jl:40-43) -- in
     about 2 log2 N matrix combinations instead of N - 1 backward steps.  With that gain Abar (lqr.jl:169) and Qbar = Q + K' R K (lqr.jl:170) are constant, and with
@@ -615,42 +658,9 @@ class StationaryPolicyValue:
     predicted_cost(mechanism, spv, z0) returns V_i = Δz_i' P_i Δz_i about zd[i].  Not a Controller: simulate(..., spv) raises TypeError."""
 
     def __init__(self, mechanism, controller, bodyids, eqcids, Q, R, horizon, zd, plants=None, first_plant=None, Fτd=None, tol=1e-5, max_levels=40):
-        if not isinstance(mechanism, Mechanism):
-            raise TypeError("StationaryPolicyValue(mechanism, controller, bodyids, eqcids, Q, R, horizon, zd; ...)")
-        if not isinstance(controller, (LQR, PlantLQR, LQRSweep)):
-            raise ValueError("StationaryPolicyValue evaluates the stationary gain of an LQR, PlantLQR or LQRSweep (got %s)" % type(controller).__name__)
-        if controller.mechanism is not mechanism:
-            raise ValueError("the controller was made for another mechanism")
-        if plants is not None and plants.mechanism is not mechanism:
-            raise ValueError("the PlantBatch was made for another mechanism")
-        nb, mu = len(mechanism.bodies), len(eqcids)
-        zd = np.ascontiguousarray(zd, dtype=np.float64)
-        if zd.ndim != 3 or zd.shape[1:] != (nb, 13) or zd.shape[0] < 1:
-            raise ValueError("zd must be [n_models][nb][13] = [n][%d][13], one setpoint per model (got %s)" % (nb, zd.shape))
-        n = zd.shape[0]
-        Qs, Rs = _pair_lists(Q, R, n, "model")
-        max_levels = int(max_levels)
-        if horizon is None and not 1 <= max_levels <= 60:
-            raise ValueError("max_levels = %d: a run to convergence makes 1 .. 60 levels (2^max_levels steps)" % max_levels)
-        if not float(tol) >= 0.0:
-            raise ValueError("tol = %r is negative or not a number" % (tol,))
-        ctrl_N = int(getattr(controller, "N", 0))      # the device convention of the three controllers: 0 = LQR{T,Inf}, one gain; N > 0 = a table of N - 1 rows
-        if ctrl_N > 0 and ctrl_N - 1 != 1:
-            raise ValueError("the controller holds a table of %d gain rows: doubling evaluates ONE stationary gain (horizon math.inf); PolicyValue steps through a table" % (ctrl_N - 1))
-        Fd = None if Fτd is None else np.ascontiguousarray(Fτd, dtype=np.float64).reshape(-1, mu)
-        if Fd is not None and Fd.shape[0] != n:
-            raise ValueError("Fτd must be [n_models][mu] = [%d][%d]" % (n, mu))
-        Qm, Rm, Ntemp = _scaled_pairs(Qs, Rs, bodyids, nb, mu, math.inf if horizon is None else horizon, mechanism.Δt)
-        if horizon is None:
-            Ntemp = 0
-        self.first_plant = (0 if plants is None else plants.first_index) if first_plant is None else int(first_plant)
-        if plants is not None:
-            plants.rows_for(self.first_plant, n)      # every model must find its plant
-        self.mechanism, self.controller, self.plants, self.n_models = mechanism, controller, plants, n
-        self.eqcids = [int(e) for e in eqcids]
-        self.ctrl_joints = [mechanism.joint_index(e) for e in self.eqcids]
-        self.Q, self.R = Qm, Rm      # [n_weights][12 nb][12 nb], [n_weights][mu][mu]: scaled, mechanism body order
-        self.zd, self.Fd, self.N, self.tol, self.max_levels = zd, Fd, Ntemp, float(tol), max_levels
+        Fd, Ntemp = _stationary_arguments(self, "StationaryPolicyValue", "evaluates", mechanism, controller, bodyids, eqcids, Q, R, horizon, zd, plants, first_plant, Fτd,
+                                          tol, max_levels)
+        zd, n, max_levels = self.zd, self.n_models, self.max_levels
         dev = _device_mech(mechanism)
         self._dev, self._setpoints = dev, None
         ctrl = controller._ctrl_handle(dev)
@@ -691,6 +701,77 @@ class StationaryPolicyValue:
             self._setpoints.close()
             self._setpoints = None
         self._value.close()
+
+
+class StationaryCovariance:
+    """The closed-loop state covariance of a STATIONARY gain under input noise, on the linear model of every plant: what spread of states and of actuator effort a
+    noisy rollout should show.  With the one gain of LQR{T,Inf} (lqr.jl:40-43) the closed loop is Δz⁺ = Abar Δz + D w, Abar = A' - D K (lqr.jl:169; [A' | D] the
+    projected model), w ~ (0, Wu) in input space, and after n steps from a start of covariance Σ0
+        Σ_n = C(n) + M(n) Σ0 M(n)',   C(n) = sum_{i<n} Abar^i W (Abar^i)',   W = D Wu D',   M(n) = Abar^n
+    -- the dual of StationaryPolicyValue, by the same doubling C(a+b) = C(a) + M(a) C(b) M(a)' on the device (cclqr_value_create_covariance_doubling).
+
+    controller, Q, R, zd, plants, first_plant, Fτd: as for StationaryPolicyValue.  horizon: exactly the steps a rollout of that horizon makes after its start (N - 1
+    of N knots), from Σ0; or None: the steady state, level by level until the increment relative to 2^floor(log2 tr W) falls below tol (reason 0), norm(M(2^j)) > 1e50
+    (reason 2) or j == max_levels (reason 1).
+    noise_scale=σ is shorthand for the law as the rollout applies it (simulate(..., noise_scale=σ): feedback_inputs in cclqr_rollout_step.h adds the SAME sample to
+    every controlled input, trackingLQR_triple_cartpole.jl:98): Wu = σ² ones((mu, mu)).  Wu: [mu][mu], or a list of n_models of them; not together with noise_scale.
+    Sigma0: [12 nb][12 nb] in the order of bodyids (permuted as Q is), or a list of n_models; not with horizon=None (a steady state does not depend on the start).  At
+    least one of noise_scale, Wu, Sigma0 must be given.
+
+    Sigma(i): model i's covariance, mechanism body order, read back; stage_cost [n][2] = tr(Q Σ), tr(R K Σ K'): the expected stage costs Score's Jx, Ju grow by per
+    step; state_std [n][12 nb] in the order of bodyids and input_std [n][mu]: the RMS of every state coordinate and of every controlled input; levels, steps, reason,
+    dnorm (in Σ's units), gnorm, converged, diverged, spectral_radius: as on StationaryPolicyValue.  Not a Controller and not a cost-to-go: simulate(..., cov) and
+    predicted_cost(..., cov, ...) raise TypeError."""
+
+    def __init__(self, mechanism, controller, bodyids, eqcids, Q, R, horizon, zd, noise_scale=None, Wu=None, Sigma0=None, plants=None, first_plant=None, Fτd=None,
+                 tol=1e-8, max_levels=40):
+        Fd, Ntemp = _stationary_arguments(self, "StationaryCovariance", "propagates noise through", mechanism, controller, bodyids, eqcids, Q, R, horizon, zd, plants,
+                                          first_plant, Fτd, tol, max_levels)
+        n, nb, mu = self.n_models, len(mechanism.bodies), len(self.eqcids)
+        if noise_scale is None and Wu is None and Sigma0 is None:
+            raise ValueError("none of noise_scale, Wu and Sigma0 is given: there is no covariance to propagate")
+        if noise_scale is not None and Wu is not None:
+            raise ValueError("noise_scale and Wu are both given: noise_scale IS Wu = noise_scale^2 ones((mu, mu))")
+        if Sigma0 is not None and horizon is None:
+            raise ValueError("Sigma0 with horizon=None: a steady state does not depend on the start")
+        if noise_scale is not None:
+            Wu = float(noise_scale) ** 2 * np.ones((mu, mu))
+        if Wu is not None:
+            Wu = np.ascontiguousarray(Wu, dtype=np.float64)
+            if Wu.shape not in ((mu, mu), (n, mu, mu)):
+                raise ValueError("Wu must be [mu][mu] = [%d][%d] or a list of one per model, %d (got %s)" % (mu, mu, n, Wu.shape))
+        inv = _body_order(bodyids, nb)
+        self._to_bodyids = np.concatenate([12 * inv[m] + np.arange(12) for m in range(nb)])      # mechanism-order coordinate -> its place in the order of bodyids
+        if Sigma0 is not None:
+            Sigma0 = np.ascontiguousarray(Sigma0, dtype=np.float64)
+            if Sigma0.shape not in ((12 * nb, 12 * nb), (n, 12 * nb, 12 * nb)):
+                raise ValueError("Sigma0 must be [12 nb][12 nb] = [%d][%d] or a list of one per model, %d (got %s)" % (12 * nb, 12 * nb, n, Sigma0.shape))
+            Sigma0 = np.ascontiguousarray(Sigma0[..., self._to_bodyids, :][..., :, self._to_bodyids])
+        self.Wu, self.Sigma0 = Wu, Sigma0
+        dev = _device_mech(mechanism)
+        self._dev = dev
+        ctrl = controller._ctrl_handle(dev)
+        try:
+            self._sigma, self.stage_cost, zstd, self.input_std, self.levels, self.reason, self.dnorm, self.gnorm = _capi.value_create_covariance_doubling(
+                dev, ctrl, self.zd, self.ctrl_joints, self.Q, self.R, Wu, Sigma0, Ntemp, tol=tol, max_levels=self.max_levels, Fd=Fd,
+                plants=None if plants is None else plants.handle(dev), first_plant=self.first_plant)
+        finally:
+            ctrl.close()
+        self.state_std = np.empty_like(zstd)
+        self.state_std[:, self._to_bodyids] = zstd
+        to_convergence = Ntemp == 0
+        self.steps = 2 ** self.levels.astype(np.int64) if to_convergence else np.full(n, Ntemp - 1, dtype=np.int64)
+        self.converged = (self.reason == 0) & to_convergence
+        self.diverged = (self.reason == 2) & to_convergence
+        with np.errstate(invalid="ignore", divide="ignore"):
+            self.spectral_radius = (self.gnorm[:, 0] / self.gnorm[:, 1]) ** (1.0 / 2.0 ** (self.levels - 1))
+
+    def Sigma(self, i):
+        """model i's covariance [12 nb][12 nb], mechanism body order, read back from the device (cclqr_value_get)"""
+        return self._sigma.get(i)
+
+    def close(self):
+        self._sigma.close()
 
 
 def _is_device_tensor(a):
@@ -1239,6 +1320,8 @@ def simulate(mechanism, tend_or_storage, controller, record=True, z0=None, fric=
         raise TypeError("a PolicyValue is not a Controller: simulate rolls out the controller it evaluates (PolicyValue.controller)")
     if isinstance(controller, StationaryPolicyValue):
         raise TypeError("a StationaryPolicyValue is not a Controller: simulate rolls out the controller it evaluates (StationaryPolicyValue.controller)")
+    if isinstance(controller, StationaryCovariance):
+        raise TypeError("a StationaryCovariance is not a Controller: simulate rolls out the controller it propagates noise through (StationaryCovariance.controller)")
     if isinstance(tend_or_storage, Storage):
         steps = tend_or_storage.steps
     else:

@@ -53,7 +53,9 @@ extern "C" {
  * Still 202 (additive, no struct changed): a stationary gain's cost-to-go by doubling -- cclqr_policy_value_doubling, cclqr_value_create_policy_doubling; looked up the
  * same way.  cclqr_policy_value and cclqr_value_create_policy are unchanged.
  * Still 202 (additive, no struct changed): the stationary LQR gain by doubling the Riccati map -- cclqr_riccati_doubling, cclqr_ctrl_create_lqr_batch_doubling; looked up
- * the same way.  cclqr_riccati_value and cclqr_ctrl_create_lqr_batch_value are unchanged. */
+ * the same way.  cclqr_riccati_value and cclqr_ctrl_create_lqr_batch_value are unchanged.
+ * Still 202 (additive, no struct changed): the closed-loop state covariance under input noise by doubling -- cclqr_covariance_doubling, cclqr_value_create_covariance_doubling;
+ * looked up the same way.  cclqr_policy_value_doubling and cclqr_value_create_policy_doubling are unchanged. */
 #define CCLQR_ABI_VERSION 202
 
 #define CCLQR_REVOLUTE 0      /* EqualityConstraint(Revolute(a, b, axis; p1, p2, qoffset)),  examples/lqr_cartpole.jl:26 */
@@ -472,6 +474,38 @@ int cclqr_policy_value_doubling(int32_t nprob, int32_t mx, int32_t mu, int32_t m
 int cclqr_value_create_policy_doubling(const cclqr_mech *m, const cclqr_plants *plants, int64_t first_plant, int32_t n_models, const double *zd, int32_t mu,
                                        const int32_t *ctrl_joint, const double *Fd, const cclqr_ctrl *c, int32_t n_weights, const double *Q, const double *R,
                                        int32_t N, double tol, int32_t max_levels, int32_t *levels, int32_t *reason, double *dnorm, double *gnorm, cclqr_value **out);
+
+/* Closed-loop state covariance under input noise, by doubling (additive, Still 202, no struct changed; looked up by name).  The reference's flagship example drives the
+ * cart with randn()*2 (examples/trackingLQR_triple_cartpole.jl:98); the rollout adds one such sample to every controlled input.  With the one gain of LQR{T,Inf}
+ * (src/control/lqr.jl:40-43) the closed loop on the linear model is Δz⁺ = Abar Δz + D w, Abar = A - Bu*K - Bλ*Kλ = A' - D K (lqr.jl:169-170; [A' | D] the projected
+ * model), w ~ (0, Wu) in input space, and after n steps from a start of covariance Sigma0
+ *     Σ_n = C(n) + M(n) Σ0 M(n)',  C(n) = sum_{i<n} Abar^i W (Abar^i)',  W = D Wu D',  M(n) = Abar^n:     C(a+b) = C(a) + M(a) C(b) M(a)',  M(a+b) = M(a) M(b)
+ * -- the pair recursion of cclqr_policy_value_doubling on (Abar', W) with Σ0 as the terminal matrix, run by the same kernels.  It runs on W / w and Σ0 / w with
+ * w = 2^floor(log2 tr W) per problem (exact; 1 when tr W is 0 or mu = 0): tol is RELATIVE to the noise, and 4 Wu gives exactly 4 Σ.
+ *   N >= 1  exactly N - 1 steps; no test.  levels = the doublings made, reason = 0, dnorm = NaN, gnorm[p][0] = norm(M(n)), gnorm[p][1] = NaN.  N = 1: Σ = Sigma0
+ *   N == 0  to convergence, the steady state: level j stops, in this order, on reason 0 norm(C(2^j) - C(2^(j-1))) / w < tol; reason 2 norm(M(2^j)) > 1e50; reason 1
+ *           j == max_levels (1 .. 60).  Sigma0 must be NULL.  dnorm[p][0..1] are reported in Σ's units (not divided by w), gnorm[p][0..1] as above.
+ * Moments, each written only if its pointer is not NULL: cost[p][0] = tr(Q Σ) and cost[p][1] = tr(R K Σ K'), the expected stage costs E[cx], E[cu] per step at Σ;
+ * zstd[p][i] = sqrt(max(Σ_ii, 0)); ustd[p][j] = sqrt(max((K Σ K')_jj, 0)).  Wu, Sigma0, Q, R are used as written: a matrix that is not symmetric positive
+ * semidefinite is the caller's business.  Results do not depend on the batch a problem is in, nor on whether gains / weights / noise are shared.
+ * cclqr_covariance_doubling -- HOST pointers; models, K, n_gains, n_weights, levels .. gnorm, opts as for cclqr_policy_value_doubling; Wu [n_noise][mu][mu] and Sigma0
+ * [n_noise][mx][mx] with n_noise = 1 or nprob, either NULL (= 0) but not both; Q, R may be NULL when cost is; Sigma [nprob][mx][mx], cost [nprob][2], zstd [nprob][mx],
+ * ustd [nprob][mu].  CCLQR_EINVAL before anything is allocated or launched, with the outputs untouched: what cclqr_policy_value_doubling refuses, n_noise neither 1 nor
+ * nprob, Wu and Sigma0 both NULL, cost without Q / R, Wu with mu == 0, Sigma0 with N == 0.  A singular G*Bλ is CCLQR_ESINGULAR (N = 1 reaches no model and cannot be):
+ * that problem gets no moments and its Sigma is unspecified, as P is there. */
+int cclqr_covariance_doubling(int32_t nprob, int32_t mx, int32_t mu, int32_t ml, const double *A, const double *Bu, const double *Bl, const double *G,
+                              int32_t n_gains, const double *K, int32_t n_weights, const double *Q, const double *R, int32_t n_noise, const double *Wu,
+                              const double *Sigma0, int32_t N, double tol, int32_t max_levels, double *Sigma, double *cost, double *zstd, double *ustd,
+                              int32_t *levels, int32_t *reason, double *dnorm, double *gnorm, const cclqr_riccati_opts *opts);
+/* cclqr_value_create_covariance_doubling -- the same covariance (lqr.jl:169-170 with the one gain of lqr.jl:40-43) for a CONTROLLER on a mechanism's plants (Still 202):
+ * linearisation, gain gather and refusals are those of cclqr_value_create_policy_doubling (tracking controllers and closed loops: CCLQR_EUNSUPPORTED; more than one gain
+ * row: CCLQR_EINVAL), and besides the refusals above.  Q, Sigma0, zstd and the tables of *out are in the order in which cclqr_value_create_policy_doubling takes Q and
+ * returns P.  *out is a cclqr_value of n_models tables holding Σ: cclqr_value_get reads a table back (a covariance is not a cost-to-go: cclqr_value_eval of it means
+ * nothing). */
+int cclqr_value_create_covariance_doubling(const cclqr_mech *m, const cclqr_plants *plants, int64_t first_plant, int32_t n_models, const double *zd, int32_t mu,
+                                           const int32_t *ctrl_joint, const double *Fd, const cclqr_ctrl *c, int32_t n_weights, const double *Q, const double *R,
+                                           int32_t n_noise, const double *Wu, const double *Sigma0, int32_t N, double tol, int32_t max_levels, double *cost,
+                                           double *zstd, double *ustd, int32_t *levels, int32_t *reason, double *dnorm, double *gnorm, cclqr_value **out);
 
 /* The stationary LQR gain by doubling the Riccati map (additive, Still 202, no struct changed; looked up by name).  LQR{T,Inf} steps dlqr Ntemp = 10 s / Δt times and
  * keeps Ku[1] (src/control/lqr.jl:25-27, 39-43), converged or not.  In projected form a backward step of dlqr (lqr.jl:141-184, its step lqr.jl:151-170) is

@@ -576,6 +576,53 @@ function value_create_policy_doubling(h::MechHandle, p::Union{PlantsHandle,Nothi
     return obj, lv, rs, dn, gn
 end
 
+"The closed-loop state covariance of ONE stationary gain under input noise, by doubling (cclqr_covariance_doubling): with Abar = A' - D K (lqr.jl:169) and w ~ (0, Wu)
+ on the inputs (the noise of trackingLQR_triple_cartpole.jl:98), Σ_n = C(n) + M(n) Σ0 M(n)' by the pair recursion of policy_value_doubling on (Abar', D Wu D').
+ Wus (mu x mu) and Σ0s (mx x mx): one per problem or one shared; either may be empty (= 0), not both.  N >= 1: N - 1 steps exactly; N == 0: the steady state (Σ0s
+ empty).  Returns (Σ[p], cost[p] = (tr(QΣ), tr(R KΣK')), zstd[p], ustd[p], levels[p], reason[p], dnorm[p], gnorm[p])."
+function covariance_doubling(As::Vector, Bus::Vector, Bλs::Vector, Gs::Vector, Ks::Vector, Qs::Vector, Rs::Vector, Wus::Vector, Σ0s::Vector, N::Integer;
+                             tol = 1e-8, max_levels = 40, path = 0)
+    np = length(As); mx, mu, ml = size(As[1], 1), size(Bus[1], 2), size(Bλs[1], 2)
+    length(Qs) == length(Rs) || throw(AssertionError("Qs and Rs must hold the same number of weight pairs"))
+    (isempty(Wus) || isempty(Σ0s) || length(Wus) == length(Σ0s)) || throw(AssertionError("Wus and Σ0s must hold the same number of matrices"))
+    rowmajor(Ms) = reduce(vcat, [vec(permutedims(Matrix{Float64}(M))) for M in Ms]; init = Float64[])
+    Σ = zeros(mx * mx * np); cost = zeros(2 * np); zs = zeros(mx * np); us = zeros(max(mu * np, 1))
+    lv = zeros(Int32, np); rs = zeros(Int32, np); dn = zeros(2 * np); gn = zeros(2 * np)
+    opts = Int32[path, 0, 0, 0]                                      # cclqr_riccati_opts: only `path` is read
+    wu = rowmajor(Wus); s0 = rowmajor(Σ0s)
+    GC.@preserve wu s0 check(ccall((:cclqr_covariance_doubling, lib), Cint,
+                (Int32, Int32, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int32, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}, Int32,
+                 Ptr{Float64}, Ptr{Float64}, Int32, Float64, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Int32}, Ptr{Float64},
+                 Ptr{Float64}, Ptr{Int32}),
+                np, mx, mu, ml, rowmajor(As), rowmajor(Bus), rowmajor(Bλs), rowmajor(Gs), Int32(length(Ks)), rowmajor(Ks), Int32(length(Qs)), rowmajor(Qs), rowmajor(Rs),
+                Int32(max(length(Wus), length(Σ0s))), isempty(Wus) ? Ptr{Float64}(C_NULL) : pointer(wu), isempty(Σ0s) ? Ptr{Float64}(C_NULL) : pointer(s0),
+                N, tol, Int32(max_levels), Σ, cost, zs, us, lv, rs, dn, gn, opts))
+    Σ3 = reshape(Σ, mx, mx, np)                                      # C layout [np][mx][mx]: row-major, so transposed here
+    [permutedims(Σ3[:, :, p]) for p = 1:np], [(cost[2p - 1], cost[2p]) for p = 1:np], [zs[(p - 1) * mx + 1:p * mx] for p = 1:np],
+        [us[(p - 1) * mu + 1:p * mu] for p = 1:np], Int.(lv), Int.(rs), [(dn[2p - 1], dn[2p]) for p = 1:np], [(gn[2p - 1], gn[2p]) for p = 1:np]
+end
+"The covariance above for controller `c`'s stationary gain on a mechanism's plants (cclqr_value_create_covariance_doubling): linearisation and gain gather as
+ value_create_policy_doubling.  Wu (n_noise mu x mu blocks, row-major) and Σ0 (n_noise mx x mx) flat, or nothing.  Returns (ValueHandle of n tables holding Σ, cost 2 x n,
+ zstd mx x n, ustd mu x n, levels, reason, dnorm 2 x n, gnorm 2 x n)."
+function value_create_covariance_doubling(h::MechHandle, p::Union{PlantsHandle,Nothing}, n::Int, zd::Array{Float64}, ctrl_joint::Vector{Int32}, c::CtrlHandle,
+                                          n_weights::Int, Q::Vector{Float64}, R::Vector{Float64}, n_noise::Int, Wu, Σ0, N::Int, mx::Int;
+                                          Fd = nothing, first_plant = 0, tol = 1e-8, max_levels = 40)
+    mu = length(ctrl_joint)
+    val = Ref{Ptr{Cvoid}}(C_NULL); lv = zeros(Int32, n); rs = zeros(Int32, n); dn = zeros(2, n); gn = zeros(2, n)
+    cost = zeros(2, n); zs = zeros(mx, n); us = zeros(mu, n)
+    fd = Fd === nothing ? Ptr{Float64}(C_NULL) : pointer(Fd)
+    wu = Wu === nothing ? Ptr{Float64}(C_NULL) : pointer(Wu)
+    s0 = Σ0 === nothing ? Ptr{Float64}(C_NULL) : pointer(Σ0)
+    GC.@preserve Fd Wu Σ0 check(ccall((:cclqr_value_create_covariance_doubling, lib), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int32, Ptr{Float64}, Int32, Ptr{Int32}, Ptr{Float64}, Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}, Int32, Ptr{Float64},
+                 Ptr{Float64}, Int32, Float64, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ref{Ptr{Cvoid}}),
+                h.ptr, p === nothing ? C_NULL : p.ptr, first_plant, Int32(n), zd, Int32(mu), ctrl_joint, fd, c.ptr, Int32(n_weights), Q, R, Int32(n_noise), wu, s0,
+                Int32(N), tol, Int32(max_levels), cost, zs, us, lv, rs, dn, gn, val))
+    obj = ValueHandle(val[], h)
+    finalizer(o -> ccall((:cclqr_value_destroy, lib), Cint, (Ptr{Cvoid},), o.ptr), obj)
+    return obj, cost, zs, us, lv, rs, dn, gn
+end
+
 "The stationary LQR gain by doubling the Riccati map (cclqr_riccati_doubling): n backward steps of dlqr (lqr.jl:141-184) are a triple (A_n, G_n, H_n), two triples compose
  in one pivoted solve and five products, and the one gain LQR{T,Inf} keeps (lqr.jl:25-27, 39-43) is reached in log2 n compositions.  Qs, Rs: one exactly symmetric pair,
  or one per problem.  N >= 2: Ku[1] and the last Pkp1 of dlqr(.., N) with tol = 0; N == 0: level by level to convergence.  Returns (K[p], P[p], levels[p], reason[p]
