@@ -22,7 +22,8 @@ EXPORTS = ["cclqr_last_error", "cclqr_version", "cclqr_device_count", "cclqr_set
            "cclqr_riccati_weights", "cclqr_ctrl_create_lqr_batch_weights",
            "cclqr_riccati_value", "cclqr_ctrl_create_lqr_batch_value", "cclqr_value_create", "cclqr_value_get", "cclqr_value_destroy", "cclqr_value_eval",
            "cclqr_policy_value", "cclqr_value_create_policy", "cclqr_policy_value_doubling", "cclqr_value_create_policy_doubling",
-           "cclqr_riccati_doubling", "cclqr_ctrl_create_lqr_batch_doubling", "cclqr_covariance_doubling", "cclqr_value_create_covariance_doubling"]
+           "cclqr_riccati_doubling", "cclqr_ctrl_create_lqr_batch_doubling", "cclqr_covariance_doubling", "cclqr_value_create_covariance_doubling",
+           "cclqr_covariance_tracking", "cclqr_value_create_covariance_tracking"]
 ABI_VERSION = 202     # include/cclqr.h CCLQR_ABI_VERSION: the structs below mirror that header (verified field by field against cclqr_abi_layout at load time)
 ROLLOUT_NO_ALLOC = 1  # cclqr_rollout_opts.flags: the call may neither allocate nor synchronise (a hipGraph capture is open on the device)
 ROLLOUT_CARRY_STATUS = 4  # ... `status` is read and written: an instance lost in an earlier launch stays frozen, the others merge this launch's result into it
@@ -962,6 +963,75 @@ def value_create_covariance_doubling(mech, ctrl, zd, ctrl_joint, Q, R, Wu, Sigma
                                                        C.c_double(float(tol)), C.c_int32(int(max_levels)), _d(cost), _d(zstd), _d(ustd), _i(lv), _i(rs), _d(dn), _d(gn),
                                                        C.byref(vptr)))
     return ValueHandle(mech, ptr=vptr, n_tables=n), cost, zstd, ustd, lv, rs, dn, gn
+
+
+def covariance_tracking(A, Bu, Bl, G, K, Q, R, Wu, Sigma0, N, path=0, bf16_terms=0, want_all=False, want_cost=True, want_std=True, want_total=True):
+    """the state covariance of a tracked run at every knot (cclqr_covariance_tracking; lqr_tracking.jl:63, 88, 107 under the noise of trackingLQR_triple_cartpole.jl:98):
+    Σ_{j+1} = Abar_j Σ_j Abar_j' + D_j Wu D_j', j = 0 .. N-2.  A [nprob][nlin][mx][mx], Bu [nprob][nlin][mx][mu], Bl [nprob][nlin][mx][ml], G [nprob][nlin][ml][mx] with
+    nlin = 1 or N - 1; K [mu][mx], [nK][mu][mx] or [n_gains][nK][mu][mx] with nK = 1 or N - 1; Q, R one pair or one per problem (None with want_cost = want_total = False);
+    Wu [mu][mu] or [n][mu][mu], Sigma0 [mx][mx] or [n][mx][mx], either None (= 0) -> Sigma [nprob][mx][mx] = Σ_{N-1}, Sigma_all [nprob][N][mx][mx], cost [nprob][N][2],
+    zstd [nprob][N][mx], ustd [nprob][N][mu], total [nprob][2]; want_* = False pass NULL (returned as None)"""
+    A = f64(A)
+    if A.ndim != 4 or A.shape[-1] != A.shape[-2]:
+        raise ValueError("A must be [nprob][nlin][mx][mx] (got %s)" % (A.shape,))
+    nprob, nlin, mx = A.shape[0], A.shape[1], A.shape[-1]
+    Bu, Bl = f64(Bu), f64(Bl)
+    Bu = Bu.reshape(nprob, nlin, mx, -1) if Bu.size else Bu.reshape(nprob, nlin, mx, 0)
+    mu = Bu.shape[3]
+    Bl = Bl.reshape(nprob, nlin, mx, -1) if Bl.size else Bl.reshape(nprob, nlin, mx, 0)
+    ml = Bl.shape[3]
+    G = f64(G).reshape(nprob, nlin, ml, mx)
+    K = f64(K)
+    if K.ndim not in (2, 3, 4) or K.shape[-2:] != (mu, mx):
+        raise ValueError("K must be [mu][mx], [nK][mu][mx] or [n_gains][nK][mu][mx] with mu = %d, mx = %d (got %s)" % (mu, mx, K.shape))
+    K = K.reshape((1,) * (4 - K.ndim) + K.shape)
+    nw = 1
+    if Q is not None:
+        Q = f64(Q).reshape(-1, mx, mx)
+        nw = Q.shape[0]
+        R = f64(R).reshape(nw, mu, mu)
+    Wu, Sigma0, n_noise = _noise_arrays(Wu, Sigma0, mu, mx)
+    N = int(N)
+    S = np.zeros((nprob, mx, mx))
+    Sall = np.zeros((nprob, N, mx, mx)) if want_all else None
+    cost = np.zeros((nprob, N, 2)) if want_cost else None
+    zstd = np.zeros((nprob, N, mx)) if want_std else None
+    ustd = np.zeros((nprob, N, mu)) if want_std else None
+    total = np.zeros((nprob, 2)) if want_total else None
+    o = RiccatiOpts(int(path), int(bf16_terms), 0, 0)
+    check(lib().cclqr_covariance_tracking(C.c_int32(nprob), C.c_int32(mx), C.c_int32(mu), C.c_int32(ml), C.c_int32(nlin), _d(A), _d(Bu) if mu else None,
+                                          _d(Bl) if ml else None, _d(G) if ml else None, C.c_int32(K.shape[0]), C.c_int32(K.shape[1]), _d(K) if K.size else None,
+                                          C.c_int32(nw), _d(Q), _d(R) if (mu and R is not None) else None, C.c_int32(n_noise), _d(Wu), _d(Sigma0), C.c_int32(N), _d(S),
+                                          _d(Sall), _d(cost), _d(zstd), _d(ustd) if mu else None, _d(total), C.byref(o)))
+    return S, Sall, cost, zstd, ustd, total
+
+
+def value_create_covariance_tracking(mech, ctrl, zd, n, N, ctrl_joint, Q, R, Wu, Sigma0, Fd=None, plants=None, first_plant=0, workspace_bytes=0, on_device=False,
+                                     stream=None):
+    """cclqr_value_create_covariance_tracking: the covariance above for controller handle `ctrl`'s gain rows along n trajectories zd [n][N][nb][13] (Fd [n][N][mu]),
+    linearised at the knots 0 .. N-2 on plant first_plant + k; numpy arrays, or with on_device=True device addresses read in place on `stream`.  Q, Sigma0 in the
+    mechanism's body order -> (ValueHandle of n tables holding Σ_{N-1}, cost [n][N][2], zstd [n][N][12 nb], ustd [n][N][mu], total [n][2])"""
+    nb = mech.tables.nb
+    n, N = int(n), int(N)
+    cj = i32(ctrl_joint).reshape(-1)
+    mu = len(cj)
+    if on_device:
+        zp, fp = C.c_void_p(int(zd)), (None if Fd is None else C.c_void_p(int(Fd)))
+    else:
+        zd = f64(zd).reshape(n, N, nb, 13)
+        Fd = None if Fd is None else f64(Fd).reshape(n, N, mu)
+        zp, fp = _d(zd), _d(Fd)
+    Q = f64(Q).reshape(-1, 12 * nb, 12 * nb)
+    nw = Q.shape[0]
+    R = f64(R).reshape(nw, mu, mu)
+    Wu, Sigma0, n_noise = _noise_arrays(Wu, Sigma0, mu, 12 * nb)
+    cost, zstd, ustd, total = np.zeros((n, N, 2)), np.zeros((n, N, 12 * nb)), np.zeros((n, N, mu)), np.zeros((n, 2))
+    vptr = C.c_void_p()
+    check(lib().cclqr_value_create_covariance_tracking(mech.ptr, None if plants is None else plants.ptr, C.c_int64(int(first_plant)), C.c_int32(n), C.c_int32(N), zp, fp,
+                                                       C.c_int32(1 if on_device else 0), C.c_int32(mu), _i(cj), ctrl.ptr, C.c_int32(nw), _d(Q), _d(R), C.c_int32(n_noise),
+                                                       _d(Wu), _d(Sigma0), C.c_int64(int(workspace_bytes)), _d(cost), _d(zstd), _d(ustd), _d(total),
+                                                       None if stream is None else C.c_void_p(int(stream)), C.byref(vptr)))
+    return ValueHandle(mech, ptr=vptr, n_tables=n), cost, zstd, ustd, total
 
 
 def riccati_doubling(A, Bu, Bl, G, Q, R, N, tol=1e-5, max_levels=40, bf16_terms=0, want_P=True, want_diag=True, K=None, P=None):

@@ -1699,6 +1699,251 @@ extern "C" int cclqr_value_create_covariance_doubling(const cclqr_mech* m, const
     return CCLQR_OK;
 }
 
+// ---- the state covariance of a tracked run, knot by knot (covariance_tracking.hip): Σ_{j+1} = Abar_j Σ_j Abar_j' + D_j Wu D_j' with the gain row and the model
+// of knot j (lqr_tracking.jl:63-65, 88-89, 107), the noise law of trackingLQR_triple_cartpole.jl:98
+// what the entry refuses about its counts and its noise, before anything is allocated or launched
+static int tracking_cov_check(int nprob, int mu, int N, int nlin, int n_gains, int nK, int n_weights, int n_noise, const double* Wu, const double* Sigma0, const double* Q,
+                              const double* R, bool want_cost, const cclqr_riccati_opts* opts, const char* of) {
+    if (N > 1 && nlin != 1 && nlin != N - 1)
+        return fail(CCLQR_EINVAL, "nlin = " + std::to_string(nlin) + ": one time-invariant model (1) or one per knot 0 .. N-2 (" + std::to_string(N - 1) + ")");
+    if (n_gains != 1 && n_gains != nprob)
+        return fail(CCLQR_EINVAL, "n_gains = " + std::to_string(n_gains) + ": the gains are one table shared by all (1) or one table per " + of + " (" + std::to_string(nprob) + ")");
+    if (N > 1 && mu > 0 && nK != 1 && nK != N - 1)
+        return fail(CCLQR_EINVAL, "nK = " + std::to_string(nK) + ": a gain table holds one row (a stationary gain) or N - 1 = " + std::to_string(N - 1) + " rows, one per knot 0 .. N-2");
+    if (want_cost) TRY(check_n_weights(n_weights, nprob, of));
+    if (n_noise != 1 && n_noise != nprob)
+        return fail(CCLQR_EINVAL, "n_noise = " + std::to_string(n_noise) + ": Wu / Sigma0 are one shared by all (1) or one per " + of + " (" + std::to_string(nprob) + ")");
+    if (!Wu && !Sigma0) return fail(CCLQR_EINVAL, "Wu and Sigma0 are both null: there is no covariance to propagate");
+    if (Wu && mu == 0) return fail(CCLQR_EINVAL, "Wu is given with mu = 0: there is no input for the noise to enter through");
+    if (want_cost && (!Q || (mu > 0 && !R))) return fail(CCLQR_EINVAL, "cost / total are asked for without Q / R");
+    if (nprob > 65535) return fail(CCLQR_EINVAL, "nprob = " + std::to_string(nprob) + ": at most 65535 problems per call (they are the y extent of the launch grids)");
+    const int path = opts ? opts->path : 0;
+    if (path < 0 || path > 2) return fail(CCLQR_EINVAL, "tracking covariance options: path in 0..2");
+    if (opts && opts->bf16_terms != 0) return fail(CCLQR_EINVAL, "the tracking covariance runs in fp64 only (bf16_terms = 0)");
+    return CCLQR_OK;
+}
+// what a tracking-covariance call brings back to the host
+struct CtkOut { std::vector<double> mom, total; std::vector<int> st, knot; };
+// fills d, inside the caller's WsScope, with the launch arguments of problem 0 onwards: weights, noise, records, totals and statuses of ALL nprob problems, the workspace
+// of `chunk` problems, the most one launch takes.  Q, R, Wu, Sigma0: HOST, as the entries take them (Q = null: no cost is asked for)
+static int ctk_setup(int nprob, int chunk, int mx, int mu, int ml, int N, int nlin, int nK, int n_weights, const double* Q, const double* R, int n_noise, const double* Wu,
+                     const double* Sigma0, int path, hipStream_t stream, CtkArgs& d) {
+    static const char* const what = "tracking covariance";
+    const size_t np = (size_t)nprob, nn = (size_t)n_noise, mm = (size_t)mx * mx, uu = (size_t)mu * mu, rec = (size_t)ctk_record(mx, mu);
+    CtkArgs& c = d;
+    c = CtkArgs{};
+    RicArgs& r = c.r;
+    r.nprob = chunk; r.mx = mx; r.mu = mu; r.ml = ml; r.N = N; r.time_varying = (N > 1 && nlin > 1) ? 1 : 0; r.tol = 0.0; r.path = path; r.bf16_terms = 0; r.keep_last = 0;
+    double *dQ = nullptr, *dR = nullptr, *dWu = nullptr, *dS0 = nullptr, *dwork = nullptr, *dmom = nullptr, *dtot = nullptr;
+    int *dst = nullptr, *dkn = nullptr;
+    if (Q) {
+        TRY(upload_weights(mx, mu, n_weights, Q, R, &dQ, &dR, what));
+        if (n_weights > 1) { c.q_stride = (long long)mm; c.r_stride = (long long)uu; }
+    } else {      // no cost asked for: the kernels form it against zero weights, written on the stream the kernels run on
+        HIPTRY(what, ws_get((void**)&dQ, mm * sizeof(double)));
+        HIPTRY(what, ws_get((void**)&dR, (uu + 1) * sizeof(double)));
+        HIPTRY(what, hipMemsetAsync(dQ, 0, mm * sizeof(double), stream));
+        HIPTRY(what, hipMemsetAsync(dR, 0, (uu + 1) * sizeof(double), stream));
+    }
+    if (Wu) {
+        HIPTRY(what, ws_get((void**)&dWu, nn * uu * sizeof(double)));
+        HIPTRY(what, hipMemcpy(dWu, Wu, nn * uu * sizeof(double), hipMemcpyHostToDevice));
+        c.wu_stride = n_noise > 1 ? (long long)uu : 0;
+    }
+    if (Sigma0) {
+        HIPTRY(what, ws_get((void**)&dS0, nn * mm * sizeof(double)));
+        HIPTRY(what, hipMemcpy(dS0, Sigma0, nn * mm * sizeof(double), hipMemcpyHostToDevice));
+        c.s0_stride = n_noise > 1 ? (long long)mm : 0;
+    }
+    HIPTRY(what, ws_get((void**)&dwork, ric_total_work_doubles(r) * sizeof(double)));
+    HIPTRY(what, ws_get((void**)&dmom, np * N * rec * sizeof(double)));
+    HIPTRY(what, ws_get((void**)&dtot, 2 * np * sizeof(double)));
+    HIPTRY(what, ws_get((void**)&dst, np * sizeof(int)));
+    HIPTRY(what, ws_get((void**)&dkn, np * sizeof(int)));
+    r.work = dwork; r.status = dst; r.kbreak = dkn;
+    c.nK = nK; c.Wu = dWu; c.Sigma0 = dS0; c.Q = dQ; c.R = dR; c.mom = dmom; c.total = dtot;
+    return CCLQR_OK;
+}
+// the recursion for the problems c0 .. c0 + nc - 1 on `stream`: their models (nlin per problem) lie at dA .. dG, their gains in dK (the tables of ALL problems, k_stride
+// doubles apart, 0 = one shared); dSigma [nprob][mx][mx] and dSigma_all [nprob][N][mx][mx] (or null) are the whole call's
+static hipError_t ctk_launch_chunk(const CtkArgs& d, size_t c0, size_t nc, const double* dA, const double* dBu, const double* dBl, const double* dG, const double* dK,
+                                   long long k_stride, double* dSigma, double* dSigma_all, hipStream_t stream) {
+    CtkArgs c = d;
+    const size_t mm = (size_t)c.r.mx * c.r.mx, N = (size_t)c.r.N, rec = (size_t)ctk_record(c.r.mx, c.r.mu);
+    c.r.nprob = (int)nc; c.r.A = dA; c.r.Bu = dBu; c.r.Bl = dBl; c.r.G = dG;
+    c.r.status += c0; c.r.kbreak += c0;
+    c.Kin = dK + (long long)c0 * k_stride; c.k_stride = k_stride;
+    if (c.Wu) c.Wu += (long long)c0 * c.wu_stride;
+    if (c.Sigma0) c.Sigma0 += (long long)c0 * c.s0_stride;
+    c.Q += (long long)c0 * c.q_stride; c.R += (long long)c0 * c.r_stride;
+    c.mom += c0 * N * rec; c.total += 2 * c0;
+    c.Sigma = dSigma + c0 * mm;
+    c.Sigma_all = dSigma_all ? dSigma_all + c0 * N * mm : nullptr;
+    return launch_covariance_tracking(c, stream);
+}
+static int ctk_read_back(const CtkArgs& d, int nprob, CtkOut& o) {
+    static const char* const what = "tracking covariance";
+    const size_t np = (size_t)nprob, len = np * (size_t)d.r.N * (size_t)ctk_record(d.r.mx, d.r.mu);
+    o.mom.resize(len); o.total.resize(2 * np); o.st.resize(np); o.knot.resize(np);
+    HIPTRY(what, hipMemcpy(o.mom.data(), d.mom, len * sizeof(double), hipMemcpyDeviceToHost));
+    HIPTRY(what, hipMemcpy(o.total.data(), d.total, 2 * np * sizeof(double), hipMemcpyDeviceToHost));
+    HIPTRY(what, hipMemcpy(o.st.data(), d.r.status, np * sizeof(int), hipMemcpyDeviceToHost));
+    HIPTRY(what, hipMemcpy(o.knot.data(), d.r.kbreak, np * sizeof(int), hipMemcpyDeviceToHost));
+    return CCLQR_OK;
+}
+// the per-knot records into the caller's arrays (each may be null), for the problems before the one the call is refused for, which it names with its knot
+static int tracking_cov_report(const CtkOut& o, int nprob, int mx, int mu, int N, double* cost, double* zstd, double* ustd, double* total, const char* of) {
+    const size_t rec = (size_t)ctk_record(mx, mu);
+    for (int p = 0; p < nprob; p++) {
+        if (o.st[p] != 0) return fail(CCLQR_ESINGULAR, "G*Bl is singular in " + std::string(of) + " " + std::to_string(p) + " at knot " + std::to_string(o.knot[p]));
+        for (int j = 0; j < N; j++) {
+            const double* m = o.mom.data() + ((size_t)p * N + j) * rec;
+            const size_t k = (size_t)p * N + j;
+            if (cost) { cost[2 * k] = m[0]; cost[2 * k + 1] = m[1]; }
+            if (zstd) memcpy(zstd + k * mx, m + 2, (size_t)mx * sizeof(double));
+            if (ustd && mu > 0) memcpy(ustd + k * mu, m + 2 + mx, (size_t)mu * sizeof(double));
+        }
+        if (total) { total[2 * p] = o.total[2 * (size_t)p]; total[2 * p + 1] = o.total[2 * (size_t)p + 1]; }
+    }
+    return CCLQR_OK;
+}
+
+extern "C" int cclqr_covariance_tracking(int32_t nprob, int32_t mx, int32_t mu, int32_t ml, int32_t nlin, const double* A, const double* Bu, const double* Bl, const double* G,
+                                         int32_t n_gains, int32_t nK, const double* K, int32_t n_weights, const double* Q, const double* R, int32_t n_noise, const double* Wu,
+                                         const double* Sigma0, int32_t N, double* Sigma, double* Sigma_all, double* cost, double* zstd, double* ustd, double* total,
+                                         const cclqr_riccati_opts* opts) {
+    static const char* const what = "tracking covariance";
+    if (nprob < 1 || mx < 1 || mu < 0 || ml < 0 || N < 1) return fail(CCLQR_EINVAL, "bad sizes");
+    if (N > 1 && (!A || (mu > 0 && (!Bu || !K)) || (ml > 0 && (!Bl || !G)))) return fail(CCLQR_EINVAL, "null argument");
+    const bool want_cost = cost || total;
+    TRY(tracking_cov_check(nprob, mu, N, nlin, n_gains, nK, n_weights, n_noise, Wu, Sigma0, Q, R, want_cost, opts, "problem"));
+    WsScope scope;
+    RicModels d = {};
+    if (N > 1) TRY(upload_models((size_t)nprob * nlin, mx, mu, ml, A, Bu, Bl, G, d));      // N = 1: no model is read
+    const size_t nKd = (mu > 0 && N > 1) ? (size_t)n_gains * nK * mu * mx : 0, nP = (size_t)nprob * mx * mx;
+    double *dK = nullptr, *dP = nullptr, *dAll = nullptr;
+    HIPTRY(what, ws_get((void**)&dK, (nKd + 1) * sizeof(double)));
+    HIPTRY(what, ws_get((void**)&dP, nP * sizeof(double)));
+    if (Sigma_all) HIPTRY(what, ws_get((void**)&dAll, nP * N * sizeof(double)));
+    if (nKd) HIPTRY(what, hipMemcpy(dK, K, nKd * sizeof(double), hipMemcpyHostToDevice));
+    CtkOut o;
+    CtkArgs dev;
+    TRY(ctk_setup(nprob, nprob, mx, mu, ml, N, nlin, nK, n_weights, want_cost ? Q : nullptr, R, n_noise, Wu, Sigma0, opts ? opts->path : 0, nullptr, dev));
+    HIPTRY(what, ctk_launch_chunk(dev, 0, (size_t)nprob, d.A, d.Bu, d.Bl, d.G, dK, n_gains > 1 ? (long long)nK * mu * mx : 0, dP, dAll, nullptr));
+    HIPTRY(what, hipDeviceSynchronize());
+    TRY(ctk_read_back(dev, nprob, o));
+    int bad = nprob;      // the first problem the call is refused for: the arrays are filled up to it
+    for (int p = nprob - 1; p >= 0; p--) if (o.st[p] != 0) bad = p;
+    if (Sigma && bad > 0) HIPTRY(what, hipMemcpy(Sigma, dP, (size_t)bad * mx * mx * sizeof(double), hipMemcpyDeviceToHost));
+    if (Sigma_all && bad > 0) HIPTRY(what, hipMemcpy(Sigma_all, dAll, (size_t)bad * N * mx * mx * sizeof(double), hipMemcpyDeviceToHost));
+    return tracking_cov_report(o, nprob, mx, mu, N, cost, zstd, ustd, total, "problem");
+}
+
+// the same recursion for a CONTROLLER on a mechanism's plants: linearsystem at the knots 0 .. N-2 of trajectory k on plant first_plant + k (lqr_tracking.jl:88), the
+// controller's gain rows gathered on the device, the problems in chunks within the workspace budget (tracking_cov_problem_bytes)
+extern "C" int cclqr_value_create_covariance_tracking(const cclqr_mech* m, const cclqr_plants* plants, int64_t first_plant, int32_t n_models, int32_t N, const double* zd,
+                                                      const double* Fd, int32_t on_device, int32_t mu, const int32_t* ctrl_joint, const cclqr_ctrl* c, int32_t n_weights,
+                                                      const double* Q, const double* R, int32_t n_noise, const double* Wu, const double* Sigma0, int64_t workspace_bytes,
+                                                      double* cost, double* zstd, double* ustd, double* total, void* stream, cclqr_value** out) {
+    static const char* const what = "tracking covariance";
+    if (!m || !zd || !c || !out || (mu > 0 && !ctrl_joint)) return fail(CCLQR_EINVAL, "null argument");
+    TRY(check_device(m));
+    if (m->host.loop) return fail(CCLQR_EUNSUPPORTED, "the tracking covariance is for tree mechanisms (closed loops have no multiplier model to evaluate a gain on)");
+    if (c->nb != m->nb || c->device != m->device) return fail(CCLQR_EINVAL, "the controller was created for another mechanism or device");
+    if (n_models < 1 || N < 1 || mu < 1 || mu > m->nb) return fail(CCLQR_EINVAL, "bad sizes");
+    const CtrlDev& H = c->host;
+    if (!c->K_dev || H.nK < 1) return fail(CCLQR_EINVAL, "the controller has no gains (open loop / PID)");
+    LinArgs la;
+    memset(&la, 0, sizeof(la));
+    TRY(linearize_check(m, plants, first_plant, n_models, mu, ctrl_joint, la.cj));      // the refusals of cclqr_linearize_plants
+    bool same = mu == H.mu;
+    for (int i = 0; same && i < mu; i++) same = la.cj[i] == H.cj[i];
+    if (!same) return fail(CCLQR_EINVAL, "mu / ctrl_joint are not the controller's: its gains act on other joints");
+    const int64_t tables = H.n_ctrl > 1 ? H.n_ctrl : 1;
+    if (tables != 1 && tables != n_models)
+        return fail(CCLQR_EINVAL, "the controller holds " + std::to_string(tables) + " tables: one shared by all models (1) or one per model (" + std::to_string(n_models) + ")");
+    if (N > 1 && H.nK != 1 && H.nK != N - 1)
+        return fail(CCLQR_EINVAL, "the controller's tables hold " + std::to_string(H.nK) + " gain rows: one (a stationary gain) or N - 1 = " + std::to_string(N - 1) + ", one per knot 0 .. N-2");
+    const bool want_cost = cost || total;
+    const int nb = m->nb, mx = 12 * nb, ml = 5 * nb, nlin = N > 1 ? N - 1 : 1;
+    TRY(tracking_cov_check(n_models, mu, N, nlin, (int)tables, H.nK, n_weights, n_noise, Wu, Sigma0, Q, R, want_cost, nullptr, "model"));
+    // the chunks the workspace budget allows, before anything is allocated
+    RicArgs r1;
+    r1.nprob = 1; r1.mx = mx; r1.mu = mu; r1.ml = ml; r1.N = N; r1.time_varying = nlin > 1 ? 1 : 0; r1.tol = 0.0; r1.path = 0; r1.bf16_terms = 0; r1.keep_last = 0;
+    RicArgs r2 = r1;
+    r2.nprob = 2;
+    const long long ric_per = (long long)(ric_total_work_doubles(r2) - ric_total_work_doubles(r1)), ric_fixed = (long long)ric_total_work_doubles(r1) - ric_per;
+    const long long per_bytes = tracking_cov_problem_bytes(mx, mu, ml, N, ric_per);
+    const long long fixed_bytes = tracking_cov_fixed_bytes(mx, mu, ric_fixed, want_cost ? n_weights : 1, n_noise);
+    const long long budget = workspace_bytes > 0 ? (long long)workspace_bytes : CCLQR_TRACKING_WORKSPACE_BYTES;
+    const long long per_chunk = tracking_chunk_problems(n_models, per_bytes, fixed_bytes, budget);
+    if (per_chunk < 1)
+        return fail(CCLQR_EINVAL, "workspace_bytes = " + std::to_string(budget) + " does not hold one problem: N = " + std::to_string(N) + " knots of this mechanism need " +
+                                  std::to_string(fixed_bytes + per_bytes) + " bytes");
+    const size_t np = (size_t)n_models, pc = (size_t)per_chunk, nk = (size_t)N - 1, nz = 13 * (size_t)nb, smx = (size_t)mx, sml = (size_t)ml, smu = (size_t)mu;
+    hipStream_t st_ = (hipStream_t)stream;
+    ValueOwner vown(value_new(m, n_models));
+    HIPTRY(what, value_alloc(vown.p));
+    struct StreamWait { hipStream_t s; ~StreamWait() { (void)hipStreamSynchronize(s); } };      // nothing of the call may still run on the blocks the scope below frees
+    WsScope scope;
+    StreamWait wait{st_};
+    // the trajectories: a device array is read where it lies (the linearisation permutes as it loads), a host array is copied
+    const double *dzd = zd, *dFd = Fd;
+    if (!on_device && nk > 0) {
+        double *uz = nullptr, *uf = nullptr;
+        HIPTRY(what, ws_get((void**)&uz, np * N * nz * sizeof(double)));
+        HIPTRY(what, hipMemcpy(uz, zd, np * N * nz * sizeof(double), hipMemcpyHostToDevice));
+        dzd = uz;
+        if (Fd) {
+            HIPTRY(what, ws_get((void**)&uf, np * N * smu * sizeof(double)));
+            HIPTRY(what, hipMemcpy(uf, Fd, np * N * smu * sizeof(double), hipMemcpyHostToDevice));
+            dFd = uf;
+        }
+    }
+    // the controller's gains into the models' body order, device to device: they never visit the host
+    const long long rows_per_table = (long long)H.nK * mu, nrows = tables * rows_per_table;
+    double* dK = nullptr;
+    HIPTRY(what, ws_get((void**)&dK, (size_t)nrows * smx * sizeof(double)));
+    HIPTRY(what, launch_lds<false>(k_rows_to_body_order_kernel, dim3((unsigned)nrows), dim3(128), 0, st_, c->K_dev, nrows, rows_per_table, (long long)H.K_stride, nb, m->dev, dK));
+    const long long k_stride = tables > 1 ? rows_per_table * mx : 0;
+    double *dA = nullptr, *dBu = nullptr, *dBl = nullptr, *dG = nullptr;
+    int* dlst = nullptr;
+    const size_t nkk = nk > 0 ? nk : 1;
+    HIPTRY(what, ws_get((void**)&dA, pc * nkk * smx * smx * sizeof(double)));
+    HIPTRY(what, ws_get((void**)&dBu, pc * nkk * smx * smu * sizeof(double)));
+    HIPTRY(what, ws_get((void**)&dBl, pc * nkk * smx * sml * sizeof(double)));
+    HIPTRY(what, ws_get((void**)&dG, pc * nkk * sml * smx * sizeof(double)));
+    HIPTRY(what, ws_get((void**)&dlst, (np * nkk + 1) * sizeof(int)));
+    CtkArgs dev;
+    TRY(ctk_setup(n_models, (int)pc, mx, mu, ml, N, nlin, H.nK, n_weights, want_cost ? Q : nullptr, R, n_noise, Wu, Sigma0, 0, st_, dev));
+    la.M = m->dev; la.mu = mu;
+    la.plants = plants ? plants->dev : nullptr;
+    la.knots_per_plant = (int)nk; la.rows_per_plant = N;
+    la.A = dA; la.Bu = dBu; la.Bl = dBl; la.G = dG;
+    for (size_t c0 = 0; c0 < np; c0 += pc) {
+        const size_t nc = np - c0 < pc ? np - c0 : pc;
+        if (nk > 0) {      // linearsystem at the knots 0 .. N-2 of the chunk's trajectories (lqr_tracking.jl:88), one launch; N = 1 reads no model
+            la.nk = (int)(nc * nk);
+            la.zd = dzd + c0 * (size_t)N * nz;
+            la.Fd = dFd ? dFd + c0 * (size_t)N * smu : nullptr;
+            la.plant_off = plants ? first_plant - plants->first_index + (long long)c0 : 0;
+            la.status = dlst + c0 * nk;
+            HIPTRY(what, launch_linearize(la, m->shape, st_));
+        }
+        HIPTRY(what, ctk_launch_chunk(dev, c0, nc, dA, dBu, dBl, dG, dK, k_stride, vown.p->P_dev, nullptr, st_));
+    }
+    HIPTRY(what, hipStreamSynchronize(st_));
+    long long bad = -1;
+    if (nk > 0) HIPTRY(what, knots_converged(dlst, np * nk, &bad));
+    if (bad >= 0)
+        return fail(CCLQR_ENOCONV, "Newton did not converge at the setpoint of knot " + std::to_string((size_t)bad % nk) + " of table " + std::to_string((size_t)bad / nk));
+    CtkOut o;
+    TRY(ctk_read_back(dev, n_models, o));
+    TRY(tracking_cov_report(o, n_models, mx, mu, N, cost, zstd, ustd, total, "table"));
+    *out = vown.release();
+    return CCLQR_OK;
+}
+
 // ---- the Riccati map itself by doubling (riccati_doubling.hip): Ku[1] and the last Pkp1 of lqr.jl:141-184 after N - 1 steps, or at convergence (lqr.jl:25-27, 39-43)
 extern "C" int cclqr_riccati_doubling(int32_t nprob, int32_t mx, int32_t mu, int32_t ml, const double* A, const double* Bu, const double* Bl, const double* G,
                                       int32_t n_weights, const double* Q, const double* R, int32_t N, double tol, int32_t max_levels, double* K, double* P,

@@ -261,6 +261,30 @@ struct CovArgs {
 size_t cov_work_doubles(const RicArgs& r);
 hipError_t launch_covariance_doubling(const CovArgs& a, hipStream_t stream);
 
+// The state covariance of a tracked run, knot by knot (covariance_tracking.hip): Σ_{j+1} = Abar_j Σ_j Abar_j' + D_j Wu D_j' with Abar_j = A'_j - D_j K_j
+// (lqr_tracking.jl:107), j = 0 .. N-2, and the moments of every Σ_j.  r: nprob, mx, mu, ml, N, A, Bu, Bl, G with time_varying = 1 for N - 1 models per problem (model j =
+// knot j) or 0 for one, kbreak (receives the knot of a singular G Bλ, else -1), status, work (ric_total_work_doubles(r) doubles), path (1 resident where it fits, 2
+// tiled; 0 = 1); nothing else of r is read.
+struct CtkArgs {
+    RicArgs r;
+    const double* Kin;           // device: gain tables [n_gains][nK][mu][mx] in the order of the models' states; may be null when mu = 0 or N = 1
+    long long k_stride;          // doubles between the tables of consecutive problems: 0 = one table shared by all, or nK * mu * mx
+    int nK;                      // rows per table: N - 1 (row j = the gain of knot j) or 1 (a stationary gain)
+    const double *Wu, *Sigma0;   // device [n_noise][mu][mu], [n_noise][mx][mx]; either may be null (= 0)
+    long long wu_stride, s0_stride;
+    const double *Q, *R;         // device, the stage-cost weights (zeros when the caller asks for no cost)
+    long long q_stride, r_stride;
+    double* mom;                 // device [nprob][N][2 + mx + mu]: per knot cx, cu, zstd [mx], ustd [mu]
+    double* total;               // device [nprob][2]
+    double *Sigma, *Sigma_all;   // device [nprob][mx][mx], [nprob][N][mx][mx]; each may be null
+};
+// doubles of one knot's record in CtkArgs.mom
+HD int ctk_record(int mx, int mu) { return 2 + mx + mu; }
+// the resident kernel's fit rule, and the path a launch takes (1 resident, 2 tiled) -- a property of the shape and of opts->path alone, never of the batch
+bool ctk_resident_fits(int mx, int mu);
+int ctk_chosen_path(int mx, int mu, int path);
+hipError_t launch_covariance_tracking(const CtkArgs& a, hipStream_t stream);
+
 // The Riccati map itself by doubling (riccati_doubling.hip): n steps of lqr.jl:151-170 in projected form are the triple (A_n, G_n, H_n) of the map
 // X -> H_n + A_n' X (I + G_n X)^-1 A_n; one step is (A', D R^-1 D', Q), and triple 1 applied after triple 2 is
 //   W = (I + G1 H2)^-1,  A = A2 W A1,  G = G2 + A2 W G1 A2',  H = H1 + A1' H2 W A1
@@ -328,6 +352,18 @@ inline long long tracking_chunk_problems(long long n_ctrl, long long per_problem
     return (n_ctrl + chunks - 1) / chunks;
 }
 inline long long tracking_chunk_count(long long n_ctrl, long long per_chunk) { return per_chunk < 1 ? 0 : (n_ctrl + per_chunk - 1) / per_chunk; }
+// ---- the covariance of tracked runs on a mechanism's plants (cclqr_value_create_covariance_tracking): the same plan with its own bytes per problem.  A problem adds
+// to a chunk its N - 1 linear models, its share of the recursion's workspace (ric_doubles, as above) and its knots' Newton statuses; what every problem of the CALL
+// holds whatever the chunk -- its N records of ctk_record doubles, its totals, status and knot -- is counted with it, so that the budget bounds the whole
+inline long long tracking_cov_problem_bytes(int mx, int mu, int ml, int N, long long ric_doubles) {
+    const long long nk = N - 1;
+    return 8 * (nk * ((long long)mx * mx + (long long)mx * mu + 2LL * mx * ml) + ric_doubles + (long long)N * (2 + mx + mu) + 2) + 4 * ((nk + 1) & ~1LL) + 8;
+}
+// ... and what the call holds once: the recursion's fixed workspace (ric_fixed doubles), the weights and the noise as given
+inline long long tracking_cov_fixed_bytes(int mx, int mu, long long ric_fixed, int n_weights, int n_noise) {
+    const long long mm = (long long)mx * mx, uu = (long long)mu * mu;
+    return 8 * (ric_fixed + (long long)n_weights * (mm + uu + 1) + (long long)n_noise * (mm + uu));
+}
 
 }  // namespace cclqr
 

@@ -926,6 +926,127 @@ class TrackingLQR(Controller):
         return _capi.CtrlHandle(dev, self.ctrl_joints, K=self.K, N=self.N, zd=self.zd, Fd=self.Fd, fric=fric, noise_scale=noise_scale, noise_seed=noise_seed)
 
 
+class TrackingCovariance:
+    """The state covariance of a TRACKED run under input noise, at every knot: what spread of every body and of the actuator effort a noisy tracked swing-up should
+    show, and the Jx, Ju that Score should report on average -- without Monte-Carlo rollouts.  Knots are j = 0 .. N-1, knot j being the state the law sees at step
+    j + 1 (the indexing of a recorded rollout and of Score).  With [A'_j | D_j] the projected model linearised at knot j (lqr_tracking.jl:88) and K_j the gain row of
+    knot j (lqr_tracking.jl:63-65), Abar_j = A'_j - D_j K_j (lqr_tracking.jl:107) and w ~ (0, Wu) in input space (trackingLQR_triple_cartpole.jl:98):
+        Σ_0 = Sigma0 (or 0),   Σ_{j+1} = Abar_j Σ_j Abar_j' + D_j Wu D_j',   j = 0 .. N-2
+    one sequential recursion on the device (cclqr_value_create_covariance_tracking); models and gains never leave it.  Σ is a second moment: Sigma0 = δδ' with no
+    noise is the deterministic perturbed start.
+
+    controller: a TrackingLQR or a PlantTrackingLQR of this mechanism, without a controlfunction.  Its own zd / Fd are the trajectories, device tensors included.
+    storage= ([n][N][nb][13], or a batched Storage) and Fτ= ([n][N][mu] or [N][mu]) replace them: that evaluates the NOMINAL TrackingLQR along each perturbed plant's own
+    trajectory.  plants / first_plant: trajectory k is linearised on plant first_plant + k (default: the PlantTrackingLQR's own; None = the mechanism's plant).
+    Q, R: per-body and per-constraint blocks in the order of bodyids / eqcids, Δt-scaled (lqr_tracking.jl:22-23), or lists of one pair per model -- exactly as
+    StationaryCovariance takes them.  noise_scale=σ is Wu = σ² ones((mu, mu)): the rollout adds the SAME sample to every controlled input (see StationaryCovariance).
+    Wu: [mu][mu] or one per model; Sigma0: [12 nb][12 nb] in the order of bodyids, or one per model.  At least one of noise_scale, Wu, Sigma0 must be given.
+    Friction is not in the linear model: a controller's fric is ignored here.  workspace_bytes: device workspace of the call (0: the library's default); the result
+    does not depend on it.
+
+    state_std [n][N][12 nb] in the order of bodyids and input_std [n][N][mu] (zeros at the last knot: no input acts there): the RMS deviation of every state
+    coordinate and controlled input at every knot; stage_cost [n][N][2] = tr(Q Σ_j), tr(R K_j Σ_j K_j'); expected_score [n][2] = their sums in knot order = E[Jx], E[Ju]
+    of simulate(..., steps=N, score=Score(...)); Sigma(i): Σ_{N-1} of model i, mechanism body order, read back; N, n_models.  Not a Controller and not a cost-to-go:
+    simulate(..., tc) and predicted_cost(..., tc, ...) raise TypeError."""
+
+    def __init__(self, mechanism, controller, bodyids, eqcids, Q, R, noise_scale=None, Wu=None, Sigma0=None, plants=None, first_plant=None, storage=None, Fτ=None,
+                 workspace_bytes=0):
+        if not isinstance(mechanism, Mechanism):
+            raise TypeError("TrackingCovariance(mechanism, controller, bodyids, eqcids, Q, R; ...)")
+        if not isinstance(controller, (TrackingLQR, PlantTrackingLQR)):
+            raise ValueError("TrackingCovariance propagates noise through the gain rows of a TrackingLQR or PlantTrackingLQR (got %s)" % type(controller).__name__)
+        if controller.mechanism is not mechanism:
+            raise ValueError("the controller was made for another mechanism")
+        if getattr(controller, "controlfunction", None) is not None:
+            raise ValueError("the controller carries a controlfunction: the covariance is that of the device's own tracking law (lqr_tracking.jl:63-65), not of a host closure")
+        batched = isinstance(controller, PlantTrackingLQR)
+        if plants is None and first_plant is None and batched:
+            plants, first_plant = controller.plants, controller.first_plant
+        if plants is not None and plants.mechanism is not mechanism:
+            raise ValueError("the PlantBatch was made for another mechanism")
+        nb, mu, N = len(mechanism.bodies), len(eqcids), int(controller.N)
+        if [int(e) for e in eqcids] != list(controller.eqcids):
+            raise ValueError("eqcids are not the controller's: its gains act on other constraints")
+        z = controller.zd if storage is None else (storage.z if isinstance(storage, Storage) else storage)
+        F = controller.Fd if Fτ is None else Fτ
+        on_dev = _is_device_tensor(z)
+        if not on_dev:
+            z = np.ascontiguousarray(z, dtype=np.float64)
+            if z.ndim == 3:
+                z = z[None]
+        if z.ndim != 4 or tuple(z.shape[1:]) != (N, nb, 13) or z.shape[0] < 1:
+            raise ValueError("storage must be [n][N][nb][13] = [n][%d][%d][13], one trajectory of the controller's N knots per model (got %s)" % (N, nb, tuple(z.shape)))
+        n = int(z.shape[0])
+        tables = controller.n_plant if batched else 1
+        if tables not in (1, n):
+            raise ValueError("the controller holds %d gain tables: one shared by all models, or one per model, %d" % (tables, n))
+        f_dev = _is_device_tensor(F)
+        if F is not None and not f_dev:
+            F = np.ascontiguousarray(F, dtype=np.float64)
+            if F.shape == (N, mu) or (mu == 1 and F.shape == (N,)):
+                F = np.ascontiguousarray(np.broadcast_to(F.reshape(1, N, mu), (n, N, mu)))
+        if F is not None and tuple(F.shape) != (n, N, mu):
+            raise ValueError("Fτ must be [N][mu] = [%d][%d] (shared) or [n][N][mu] = [%d][%d][%d] (got %s)" % (N, mu, n, N, mu, tuple(F.shape)))
+        if F is not None and f_dev != on_dev:
+            raise ValueError("storage and Fτ must both be host arrays or both device tensors")
+        if noise_scale is None and Wu is None and Sigma0 is None:
+            raise ValueError("none of noise_scale, Wu and Sigma0 is given: there is no covariance to propagate")
+        if noise_scale is not None and Wu is not None:
+            raise ValueError("noise_scale and Wu are both given: noise_scale IS Wu = noise_scale^2 ones((mu, mu))")
+        if noise_scale is not None:
+            Wu = float(noise_scale) ** 2 * np.ones((mu, mu))
+        if Wu is not None:
+            Wu = np.ascontiguousarray(Wu, dtype=np.float64)
+            if Wu.shape not in ((mu, mu), (n, mu, mu)):
+                raise ValueError("Wu must be [mu][mu] = [%d][%d] or a list of one per model, %d (got %s)" % (mu, mu, n, Wu.shape))
+        inv = _body_order(bodyids, nb)
+        self._to_bodyids = np.concatenate([12 * inv[m] + np.arange(12) for m in range(nb)])      # mechanism-order coordinate -> its place in the order of bodyids
+        if Sigma0 is not None:
+            Sigma0 = np.ascontiguousarray(Sigma0, dtype=np.float64)
+            if Sigma0.shape not in ((12 * nb, 12 * nb), (n, 12 * nb, 12 * nb)):
+                raise ValueError("Sigma0 must be [12 nb][12 nb] = [%d][%d] or a list of one per model, %d (got %s)" % (12 * nb, 12 * nb, n, Sigma0.shape))
+            Sigma0 = np.ascontiguousarray(Sigma0[..., self._to_bodyids, :][..., :, self._to_bodyids])
+        Qs, Rs = _pair_lists(Q, R, n, "model")
+        self.Q, self.R, _ = _scaled_pairs(Qs, Rs, bodyids, nb, mu, math.inf, mechanism.Δt)      # [n_weights][12 nb][12 nb], [n_weights][mu][mu]: scaled, mechanism body order
+        self.first_plant = (0 if plants is None else plants.first_index) if first_plant is None else int(first_plant)
+        if plants is not None:
+            plants.rows_for(self.first_plant, n)      # every model must find its plant
+        self.mechanism, self.controller, self.plants, self.n_models, self.N = mechanism, controller, plants, n, N
+        self.eqcids = [int(e) for e in eqcids]
+        self.ctrl_joints = [mechanism.joint_index(e) for e in self.eqcids]
+        self.Wu, self.Sigma0 = Wu, Sigma0
+        dev = _device_mech(mechanism)
+        self._dev = dev
+        kw = dict(Fd=F, plants=None if plants is None else plants.handle(dev), first_plant=self.first_plant, workspace_bytes=workspace_bytes)
+        zarg = z
+        if on_dev:
+            import torch
+            if z.dtype != torch.float64 or not z.is_contiguous() or (F is not None and (F.dtype != torch.float64 or not F.is_contiguous())):
+                raise ValueError("device tensors must be contiguous float64")
+            kw.update(Fd=None if F is None else F.data_ptr(), on_device=True, stream=torch.cuda.current_stream().cuda_stream)
+            zarg = z.data_ptr()
+        if batched:
+            if controller._handle.mech is not dev or not controller._handle.ptr:
+                raise ValueError("the PlantTrackingLQR was designed on another device handle of the mechanism")
+            ctrl = _BorrowedCtrl(controller._handle)
+        else:
+            ctrl = controller._ctrl_handle(dev)
+        try:
+            self._sigma, self.stage_cost, zstd, self.input_std, self.expected_score = _capi.value_create_covariance_tracking(
+                dev, ctrl, zarg, n, N, self.ctrl_joints, self.Q, self.R, Wu, Sigma0, **kw)
+        finally:
+            ctrl.close()
+        self.state_std = np.empty_like(zstd)
+        self.state_std[..., self._to_bodyids] = zstd
+
+    def Sigma(self, i):
+        """Σ_{N-1} of model i [12 nb][12 nb], mechanism body order, read back from the device (cclqr_value_get)"""
+        return self._sigma.get(i)
+
+    def close(self):
+        self._sigma.close()
+
+
 class Score:
     """What a run is ranked by: the quadratic cost the gains were designed to minimise, sum_k Δz' Q Δz + Δu' R Δu with the error Δz of lqr.jl:92-103 and the
     feedback command Δu = -K[k] Δz, evaluated on the device from the rollout's own states (cclqr_rollout_score).
@@ -1322,6 +1443,8 @@ def simulate(mechanism, tend_or_storage, controller, record=True, z0=None, fric=
         raise TypeError("a StationaryPolicyValue is not a Controller: simulate rolls out the controller it evaluates (StationaryPolicyValue.controller)")
     if isinstance(controller, StationaryCovariance):
         raise TypeError("a StationaryCovariance is not a Controller: simulate rolls out the controller it propagates noise through (StationaryCovariance.controller)")
+    if isinstance(controller, TrackingCovariance):
+        raise TypeError("a TrackingCovariance is not a Controller: simulate rolls out the controller it propagates noise through (TrackingCovariance.controller)")
     if isinstance(tend_or_storage, Storage):
         steps = tend_or_storage.steps
     else:

@@ -55,7 +55,9 @@ extern "C" {
  * Still 202 (additive, no struct changed): the stationary LQR gain by doubling the Riccati map -- cclqr_riccati_doubling, cclqr_ctrl_create_lqr_batch_doubling; looked up
  * the same way.  cclqr_riccati_value and cclqr_ctrl_create_lqr_batch_value are unchanged.
  * Still 202 (additive, no struct changed): the closed-loop state covariance under input noise by doubling -- cclqr_covariance_doubling, cclqr_value_create_covariance_doubling;
- * looked up the same way.  cclqr_policy_value_doubling and cclqr_value_create_policy_doubling are unchanged. */
+ * looked up the same way.  cclqr_policy_value_doubling and cclqr_value_create_policy_doubling are unchanged.
+ * Still 202 (additive, no struct changed): the state covariance of a TRACKED run at every knot, a model and a gain row per knot -- cclqr_covariance_tracking, cclqr_value_create_covariance_tracking;
+ * looked up the same way.  cclqr_covariance_doubling and cclqr_value_create_covariance_doubling are unchanged, their refusal of gain tables and tracking controllers included. */
 #define CCLQR_ABI_VERSION 202
 
 #define CCLQR_REVOLUTE 0      /* EqualityConstraint(Revolute(a, b, axis; p1, p2, qoffset)),  examples/lqr_cartpole.jl:26 */
@@ -506,6 +508,55 @@ int cclqr_value_create_covariance_doubling(const cclqr_mech *m, const cclqr_plan
                                            const int32_t *ctrl_joint, const double *Fd, const cclqr_ctrl *c, int32_t n_weights, const double *Q, const double *R,
                                            int32_t n_noise, const double *Wu, const double *Sigma0, int32_t N, double tol, int32_t max_levels, double *cost,
                                            double *zstd, double *ustd, int32_t *levels, int32_t *reason, double *dnorm, double *gnorm, cclqr_value **out);
+
+/* The state covariance of a TRACKED run under input noise, knot by knot (additive, Still 202, no struct changed; looked up by name).  The reference's flagship example
+ * drives the cart with randn()*2 (examples/trackingLQR_triple_cartpole.jl:98) under a TrackingLQR: the law applies gain row Ku[k] while k < N
+ * (src/control/lqr_tracking.jl:63, 65), designed on the model linearised at knot k (lqr_tracking.jl:88-89).  Knots are j = 0 .. N-1, knot j being the state the law sees
+ * at step j + 1 -- the indexing of cclqr_rollout_score and of a recorded rollout passed in as zd.  With [A'_j | D_j] the projected pair of knot j (lqr_tracking.jl:88)
+ * and K_j its gain row:
+ *     Abar_j  = A'_j - D_j K_j                       (lqr_tracking.jl:107)
+ *     Σ_0     = Sigma0 (or 0)
+ *     Σ_{j+1} = Abar_j Σ_j Abar_j' + D_j Wu D_j'     j = 0 .. N-2
+ *     cx_j = tr(Q Σ_j)                j = 0 .. N-1
+ *     cu_j = tr(R K_j Σ_j K_j')       j = 0 .. N-2,  cu_{N-1} = 0
+ *     zstd_j = sqrt(max(diag Σ_j, 0))
+ *     ustd_j = sqrt(max(diag K_j Σ_j K_j', 0)),      ustd_{N-1} = 0
+ *     total  = (sum_j cx_j, sum_j cu_j), summed in knot order = E[Jx], E[Ju] of simulate(..., steps = N, score = Score(...))
+ * Σ is a second moment: a rank-one Sigma0 = δδ' with Wu = 0 is the deterministic perturbed start.  Wu, Sigma0, Q, R are used as written: nothing assumes symmetry.
+ * N = 1: Σ = Sigma0, and no model is read.  One sequential recursion on the device, two mx^3 products per step on the fp64 matrix pipe.
+ * cclqr_covariance_tracking -- HOST pointers, caller models: A [nprob][nlin][mx][mx], Bu [nprob][nlin][mx][mu], Bl [nprob][nlin][mx][ml], G [nprob][nlin][ml][mx] with
+ * nlin = 1 (one time-invariant model) or N - 1 (model j = knot j); K [n_gains][nK][mu][mx] with n_gains = 1 or nprob and nK = 1 (a stationary gain) or N - 1 (row j = knot
+ * j); Q [n_weights][mx][mx], R [n_weights][mu][mu] with n_weights = 1 or nprob, both may be NULL when cost and total are; Wu [n_noise][mu][mu], Sigma0 [n_noise][mx][mx]
+ * with n_noise = 1 or nprob, either NULL (= 0) but not both.  Outputs, each written only if not NULL: Sigma [nprob][mx][mx] = Σ_{N-1}; Sigma_all [nprob][N][mx][mx];
+ * cost [nprob][N][2] = (cx_j, cu_j); zstd [nprob][N][mx]; ustd [nprob][N][mu]; total [nprob][2].  opts: only `path` is read (0 / 1: one workgroup per problem where the shape
+ * fits -- mx a multiple of 4 up to 96 --, 2: every step as device-wide launches, which every other shape takes anyway); bf16_terms != 0 is CCLQR_EINVAL.
+ * Results do not depend on the batch a problem is in, nor on whether gains / weights / noise are shared, nor on which outputs are asked for.
+ * CCLQR_EINVAL before anything is allocated or launched, with the outputs untouched: sizes below 1 (mu, ml below 0), nlin neither 1 nor N - 1, n_gains / n_weights / n_noise
+ * neither 1 nor nprob, nK neither 1 nor N - 1, Wu and Sigma0 both NULL, Wu with mu == 0, cost or total without Q / R, more than 65535 problems, path outside 0 .. 2.
+ * A singular G*Bλ at a knot the recursion reaches is CCLQR_ESINGULAR, naming problem and knot; the outputs are filled for the problems before it. */
+int cclqr_covariance_tracking(int32_t nprob, int32_t mx, int32_t mu, int32_t ml, int32_t nlin, const double *A, const double *Bu, const double *Bl, const double *G,
+                              int32_t n_gains, int32_t nK, const double *K, int32_t n_weights, const double *Q, const double *R, int32_t n_noise, const double *Wu,
+                              const double *Sigma0, int32_t N, double *Sigma, double *Sigma_all, double *cost, double *zstd, double *ustd, double *total,
+                              const cclqr_riccati_opts *opts);
+
+/* cclqr_value_create_covariance_tracking -- the same recursion (lqr_tracking.jl:63, 88, 107 under the noise of trackingLQR_triple_cartpole.jl:98) for a CONTROLLER on a
+ * mechanism's plants (Still 202).  zd [n_models][N][nb][13] and Fd [n_models][N][mu] (or NULL) as cclqr_ctrl_create_tracking_batch_plants takes them: host arrays
+ * (on_device = 0), or device arrays read in place on `stream` (on_device = 1) -- a recorded traj_dev passes straight in.  linearsystem runs at the knots 0 .. N-2 of
+ * trajectory k on plant first_plant + k (plants NULL: the mechanism's own); the gains of c are gathered on the device into the models' body order and never visit the
+ * host.  c holds N - 1 gain rows or one, and one table or n_models.  The problems run in chunks whose models, recursion workspace and per-knot records stay within
+ * workspace_bytes (<= 0: the library default of 4 GiB); the result does not depend on the chunking.  The budget covers what grows with the chunk and the weights and noise;
+ * NOT counted in it: the device copy of host trajectories (n_models N (13 nb + mu) doubles), the gathered gain rows of the controller's tables and the tables of *out.  Q, Sigma0, zstd and the tables of *out are in the order in which
+ * cclqr_value_create_policy takes Q and returns P.  *out is a cclqr_value of n_models tables holding Σ_{N-1}: cclqr_value_get reads a table back (a covariance is not a
+ * cost-to-go: cclqr_value_eval of it means nothing).  The per-knot moments go to the HOST arrays cost [n_models][N][2], zstd [n_models][N][12 nb], ustd [n_models][N][mu],
+ * total [n_models][2], each written only if not NULL; Q, R may be NULL when cost and total are.
+ * Refused before anything is allocated or launched, outputs and *out untouched: what cclqr_linearize_plants refuses; a controller without gains, or for another mechanism,
+ * device or set of joints; a table count other than 1 or n_models, a row count other than 1 or N - 1, the counts and the noise as for cclqr_covariance_tracking, a
+ * workspace that does not hold one problem (the message names the bytes it needs) -- CCLQR_EINVAL; closed-loop mechanisms -- CCLQR_EUNSUPPORTED.  During the run a
+ * setpoint solve that does not converge is CCLQR_ENOCONV and a singular G*Bλ CCLQR_ESINGULAR, both naming table and knot. */
+int cclqr_value_create_covariance_tracking(const cclqr_mech *m, const cclqr_plants *plants, int64_t first_plant, int32_t n_models, int32_t N, const double *zd,
+                                           const double *Fd, int32_t on_device, int32_t mu, const int32_t *ctrl_joint, const cclqr_ctrl *c, int32_t n_weights,
+                                           const double *Q, const double *R, int32_t n_noise, const double *Wu, const double *Sigma0, int64_t workspace_bytes,
+                                           double *cost, double *zstd, double *ustd, double *total, void *stream, cclqr_value **out);
 
 /* The stationary LQR gain by doubling the Riccati map (additive, Still 202, no struct changed; looked up by name).  LQR{T,Inf} steps dlqr Ntemp = 10 s / Δt times and
  * keeps Ku[1] (src/control/lqr.jl:25-27, 39-43), converged or not.  In projected form a backward step of dlqr (lqr.jl:141-184, its step lqr.jl:151-170) is

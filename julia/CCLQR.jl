@@ -623,6 +623,52 @@ function value_create_covariance_doubling(h::MechHandle, p::Union{PlantsHandle,N
     return obj, cost, zs, us, lv, rs, dn, gn
 end
 
+"The state covariance of a TRACKED run under input noise at every knot (cclqr_covariance_tracking): Σ_{j+1} = Abar_j Σ_j Abar_j' + D_j Wu D_j' with Abar_j = A'_j - D_j K_j
+ (lqr_tracking.jl:107), the model and the gain row of knot j (lqr_tracking.jl:63, 88), w ~ (0, Wu) on the inputs (trackingLQR_triple_cartpole.jl:98).  As[p], Bus[p], Bλs[p],
+ Gs[p]: vectors of nlin = 1 or N - 1 matrices per problem; Ks[p]: vectors of nK = 1 or N - 1 gain rows (one table shared: length(Ks) == 1).  Wus, Σ0s: one per problem or one
+ shared; either may be empty (= 0), not both.  Returns (Σ[p] = Σ_{N-1}, cost 2 x N x np, zstd mx x N x np, ustd mu x N x np, total 2 x np)."
+function covariance_tracking(As::Vector, Bus::Vector, Bλs::Vector, Gs::Vector, Ks::Vector, Qs::Vector, Rs::Vector, Wus::Vector, Σ0s::Vector, N::Integer; path = 0)
+    np = length(As); nlin = length(As[1])
+    mx, mu, ml = size(As[1][1], 1), size(Bus[1][1], 2), size(Bλs[1][1], 2)
+    nK = (mu == 0 || isempty(Ks)) ? 1 : length(Ks[1])                # no inputs: no gains, Ks may be empty
+    length(Qs) == length(Rs) || throw(AssertionError("Qs and Rs must hold the same number of weight pairs"))
+    (isempty(Wus) || isempty(Σ0s) || length(Wus) == length(Σ0s)) || throw(AssertionError("Wus and Σ0s must hold the same number of matrices"))
+    rowmajor(Ms) = reduce(vcat, [vec(permutedims(Matrix{Float64}(M))) for M in Ms]; init = Float64[])
+    nested(Vs) = reduce(vcat, [rowmajor(V) for V in Vs]; init = Float64[])
+    Σ = zeros(mx * mx * np); cost = zeros(2, N, np); zs = zeros(mx, N, np); us = zeros(max(mu, 1), N, np); tot = zeros(2, np)
+    opts = Int32[path, 0, 0, 0]                                      # cclqr_riccati_opts: only `path` is read
+    wu = rowmajor(Wus); s0 = rowmajor(Σ0s)
+    GC.@preserve wu s0 check(ccall((:cclqr_covariance_tracking, lib), Cint,
+                (Int32, Int32, Int32, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int32, Int32, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64},
+                 Int32, Ptr{Float64}, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}),
+                np, mx, mu, ml, nlin, nested(As), nested(Bus), nested(Bλs), nested(Gs), Int32(max(length(Ks), 1)), Int32(nK), nested(Ks), Int32(length(Qs)), rowmajor(Qs),
+                rowmajor(Rs), Int32(max(length(Wus), length(Σ0s))), isempty(Wus) ? Ptr{Float64}(C_NULL) : pointer(wu), isempty(Σ0s) ? Ptr{Float64}(C_NULL) : pointer(s0),
+                N, Σ, Ptr{Float64}(C_NULL), cost, zs, mu > 0 ? pointer(us) : Ptr{Float64}(C_NULL), tot, opts))
+    Σ3 = reshape(Σ, mx, mx, np)                                      # C layout [np][mx][mx]: row-major, so transposed here
+    [permutedims(Σ3[:, :, p]) for p = 1:np], cost, zs, us[1:mu, :, :], tot
+end
+"The covariance above for controller `c`'s gain rows along n trajectories on a mechanism's plants (cclqr_value_create_covariance_tracking): zd 13 x nb x N x n and Fd
+ mu x N x n (or nothing) host arrays, linearised at the knots 0 .. N-2 of trajectory k on plant first_plant + k.  Wu (n_noise mu x mu blocks, row-major) and Σ0 (n_noise
+ mx x mx) flat, or nothing.  Returns (ValueHandle of n tables holding Σ_{N-1}, cost 2 x N x n, zstd mx x N x n, ustd mu x N x n, total 2 x n)."
+function value_create_covariance_tracking(h::MechHandle, p::Union{PlantsHandle,Nothing}, n::Int, N::Int, zd::Array{Float64}, ctrl_joint::Vector{Int32}, c::CtrlHandle,
+                                          n_weights::Int, Q::Vector{Float64}, R::Vector{Float64}, n_noise::Int, Wu, Σ0, mx::Int;
+                                          Fd = nothing, first_plant = 0, workspace_bytes = 0)
+    mu = length(ctrl_joint)
+    val = Ref{Ptr{Cvoid}}(C_NULL)
+    cost = zeros(2, N, n); zs = zeros(mx, N, n); us = zeros(mu, N, n); tot = zeros(2, n)
+    fd = Fd === nothing ? Ptr{Float64}(C_NULL) : pointer(Fd)
+    wu = Wu === nothing ? Ptr{Float64}(C_NULL) : pointer(Wu)
+    s0 = Σ0 === nothing ? Ptr{Float64}(C_NULL) : pointer(Σ0)
+    GC.@preserve Fd Wu Σ0 check(ccall((:cclqr_value_create_covariance_tracking, lib), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Int32, Int32, Ptr{Int32}, Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}, Int32,
+                 Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Cvoid}, Ref{Ptr{Cvoid}}),
+                h.ptr, p === nothing ? C_NULL : p.ptr, first_plant, Int32(n), Int32(N), zd, fd, Int32(0), Int32(mu), ctrl_joint, c.ptr, Int32(n_weights), Q, R,
+                Int32(n_noise), wu, s0, Int64(workspace_bytes), cost, zs, us, tot, C_NULL, val))
+    obj = ValueHandle(val[], h)
+    finalizer(o -> ccall((:cclqr_value_destroy, lib), Cint, (Ptr{Cvoid},), o.ptr), obj)
+    return obj, cost, zs, us, tot
+end
+
 "The stationary LQR gain by doubling the Riccati map (cclqr_riccati_doubling): n backward steps of dlqr (lqr.jl:141-184) are a triple (A_n, G_n, H_n), two triples compose
  in one pivoted solve and five products, and the one gain LQR{T,Inf} keeps (lqr.jl:25-27, 39-43) is reached in log2 n compositions.  Qs, Rs: one exactly symmetric pair,
  or one per problem.  N >= 2: Ku[1] and the last Pkp1 of dlqr(.., N) with tol = 0; N == 0: level by level to convergence.  Returns (K[p], P[p], levels[p], reason[p]
