@@ -4,6 +4,8 @@
 // walk and the one projection onto [A' | D] (ric_project_kernel).
 #pragma once
 #include "cclqr_internal.h"
+#include <math.h>
+#include <string.h>
 #include <type_traits>
 
 namespace cclqr {
@@ -119,14 +121,164 @@ __device__ inline v4d wave_tile16_db(int ngroups, PA pa, int ga, PB pb, int gb) 
     return acc;
 }
 
-// ---- host side, defined in riccati.hip
+// =====================================================================================================================
+// The blocks every recursion over [A' | D] is built from (policy.hip, policy_doubling.hip, covariance_doubling.hip, covariance_tracking.hip,
+// riccati_doubling.hip).  Each takes its sums in ONE fixed order, and the bitwise properties the tests hold these files to -- independence of batch, sharing,
+// chunking and path, the duality of the covariance with the cost recursion -- rest on that order being written once: a new recursion calls these, it does not copy them.
+
+// ---- the register-held tile set of a resident workgroup: the 16x16 tiles of an mx x mx matrix one wavefront holds across a barrier, ceil(6 * 6 / 8) at the
+// resident limit of 96 states.  Five named values, tile t put and picked by selects, so that the tile loops stay rolled (one copy of their bodies) and nothing is
+// indexed at run time (an array indexed inside a rolled loop is placed in scratch memory)
+#define RES_TILES 5
+struct ResTiles {
+    v4d a0, a1, a2, a3, a4;
+    __device__ __forceinline__ void put(int t, v4d r) { if (t == 0) a0 = r; if (t == 1) a1 = r; if (t == 2) a2 = r; if (t == 3) a3 = r; if (t == 4) a4 = r; }
+    __device__ __forceinline__ v4d pick(int t) const { return t == 0 ? a0 : (t == 1 ? a1 : (t == 2 ? a2 : (t == 3 ? a3 : a4))); }
+};
+static_assert(sizeof(ResTiles) == RES_TILES * sizeof(v4d), "ResTiles holds RES_TILES tiles: put and pick name each of them");
+// the sizes the tile loops are written in: t16 = ceil(mx / 16), ntile = t16^2, ng = mx / 4 k-groups (mx % 4 == 0), this lane's place, nw wavefronts (wavefront
+// `wave` takes the tiles wave, wave + nw, ..).  A kernel may hand in values it re-derives as it goes (ctk_resident_kernel)
+struct ResShape { int mx, t16, ntile, ng, wave, li, lk, nw; };
+__device__ __forceinline__ ResTiles res_zero() { const v4d zero4 = {0.0, 0.0, 0.0, 0.0}; return {zero4, zero4, zero4, zero4, zero4}; }
+// C = A' B for two mx x mx LDS operands, both read along rows: this wavefront's tiles, kept in registers
+__device__ __forceinline__ ResTiles res_mul(const ResShape& s, lds_double* A, lds_double* B) {
+    ResTiles acc = res_zero();
+#pragma unroll 1
+    for (int t = 0; t < RES_TILES && s.wave + s.nw * t < s.ntile; t++) {
+        const int tile = s.wave + s.nw * t;
+        const int i0 = (tile / s.t16) << 4, j0 = (tile % s.t16) << 4;
+        const int ic = (i0 + s.li < s.mx) ? i0 + s.li : s.mx - 1, jc = (j0 + s.li < s.mx) ? j0 + s.li : s.mx - 1;
+        const v4d r = wave_tile16_db(s.ng, A + s.lk * s.mx + ic, 4 * s.mx, B + s.lk * s.mx + jc, 4 * s.mx);
+        acc.put(t, r);
+    }
+    return acc;
+}
+// f(i, j, C[i][j]) on every element this lane holds
+template <class F>
+__device__ __forceinline__ void res_each(const ResShape& s, const ResTiles& acc, F f) {
+#pragma unroll 1
+    for (int t = 0; t < RES_TILES && s.wave + s.nw * t < s.ntile; t++) {
+        const int tile = s.wave + s.nw * t;
+        const int i0 = (tile / s.t16) << 4, j = ((tile % s.t16) << 4) + s.li;
+        const v4d v = acc.pick(t);
+        if (j < s.mx) {
+#pragma unroll
+            for (int r = 0; r < 4; r++) { const int i = i0 + s.lk + 4 * r; if (i < s.mx) f(i, j, v[r]); }
+        }
+    }
+}
+
+// ---- the 32x32 masked-edge tile of a tiled launch: workgroup `tile` of tm x tm, 256 threads
+struct Tile32 {
+    int i0, j0;
+    bool iok[2], jok[2];      // are this lane's two operand columns (i0 / j0 + 16 h + li) inside the matrix
+};
+__device__ __forceinline__ Tile32 tile32_at(int tile, int tm, int mx) {
+    const int li = threadIdx.x & 15, i0 = (tile / tm) << 5, j0 = (tile % tm) << 5;
+    return {i0, j0, {i0 + li < mx, i0 + 16 + li < mx}, {j0 + li < mx, j0 + 16 + li < mx}};
+}
+// the tile of op(A) op(B) into red (tile_mfma_splitk), A and B mx x mx in global memory.  ta: op(A) = A' (A is read along rows, the lane's column contiguous),
+// else A; tb: op(B) = B', else B (read along rows)
+__device__ __forceinline__ void tile32_product(const Tile32& t, int mx, const double* A, int ta, const double* B, int tb, double (*red)[1024]) {
+    const int li = threadIdx.x & 15;
+    tile_mfma_splitk(mx,
+        [&](int kk, int h) { return t.iok[h] ? (ta ? A[(size_t)kk * mx + t.i0 + 16 * h + li] : A[(size_t)(t.i0 + 16 * h + li) * mx + kk]) : 0.0; },
+        [&](int kk, int h) { return t.jok[h] ? (tb ? B[(size_t)(t.j0 + 16 * h + li) * mx + kk] : B[(size_t)kk * mx + t.j0 + 16 * h + li]) : 0.0; }, red);
+}
+// element e of the tile: the four wavefronts' partial sums in wave order
+__device__ __forceinline__ double tile32_sum(const double (*red)[1024], int e) { return ((red[0][e] + red[1][e]) + red[2][e]) + red[3][e]; }
+// Ct = (A' B)' for the tile: the product, stored transposed with consecutive threads on consecutive i
+__device__ __forceinline__ void tile32_product_transposed(const Tile32& t, int mx, const double* A, const double* B, double* Ct, double (*red)[1024]) {
+    tile32_product(t, mx, A, 1, B, 0, red);
+    for (int e = threadIdx.x; e < 1024; e += TILE_THREADS) {
+        const int jj = e >> 5, ii = e & 31, i = t.i0 + ii, j = t.j0 + jj;
+        if (i < mx && j < mx) Ct[(size_t)j * mx + i] = tile32_sum(red, ii * 32 + jj);
+    }
+}
+
+// ---- a Frobenius norm whose sum of squares must not overflow: before the growth stop of a doubling fires the increments of an unstable closed loop reach 1e200
+// (S(2n) is about norm(M)^2 |Q|), and their squares do not exist in fp64.  Two sums, as in Blue's algorithm without its small range: an entry above 2^500 is
+// squared after scaling by 2^-600.  (An entry below 2^-511 underflows when squared: such a norm lies far below any tol and is reported as smaller than it is, down to 0.)
+struct SqSum {
+    double mid, big;
+    __device__ __forceinline__ void add(double v) {
+        if (fabs(v) > 0x1p500) { const double s = v * 0x1p-600; big += s * s; } else mid += v * v;
+    }
+    __device__ __forceinline__ double norm() const { return big > 0.0 ? sqrt(big + (mid * 0x1p-600) * 0x1p-600) * 0x1p600 : sqrt(mid); }
+};
+// the norm from a problem's per-tile sums [ntile][2], added in index order per lane and then over the lanes: the same for every launch.  Valid in the first wavefront
+__device__ inline double sq_tile_total(const double* part, int ntile) {
+    SqSum tot = {0.0, 0.0};
+    for (int t = threadIdx.x; t < ntile; t += 64) { tot.mid += part[2 * t]; tot.big += part[2 * t + 1]; }
+    for (int o = 32; o > 0; o >>= 1) { tot.mid += __shfl_xor(tot.mid, o, 64); tot.big += __shfl_xor(tot.big, o, 64); }
+    return tot.norm();
+}
+// a pair over a 256-thread workgroup: the lanes by the shuffle tree, wavefront w's sums into wsum[0 / 1][w]; then sq_wave_sum(wsum, c) is the total of component c
+// (0 mid, 1 big), the wavefronts in index order.  Ends synchronised
+__device__ __forceinline__ void sq_reduce(SqSum acc, double (*wsum)[4]) {
+    for (int s = 32; s > 0; s >>= 1) { acc.mid += __shfl_xor(acc.mid, s, 64); acc.big += __shfl_xor(acc.big, s, 64); }
+    if ((threadIdx.x & 63) == 0) { wsum[0][threadIdx.x >> 6] = acc.mid; wsum[1][threadIdx.x >> 6] = acc.big; }
+    __syncthreads();
+}
+__device__ __forceinline__ double sq_wave_sum(const double (*wsum)[4], int c) { return ((wsum[c][0] + wsum[c][1]) + wsum[c][2]) + wsum[c][3]; }
+
+// the generic product of the doubling recursions, one 32x32 tile of problem prob:  C = op(A) op(B) [+ E] [+ I]  and, where part [nprob][tm * tm][2] is given, the
+// tile's sum of squares of op(A) op(B).  E (null: no addend) may be C -- the lane that owns an element reads and writes it; A and B may not
+__device__ __forceinline__ void tile32_product_store(int mx, int tm, int prob, const double* A, int ta, const double* B, int tb, const double* E, int eye, double* Cm,
+                                                     double* part, double (*red)[1024], double (*wsum)[4]) {
+    const Tile32 t = tile32_at(blockIdx.x, tm, mx);
+    tile32_product(t, mx, A, ta, B, tb, red);
+    SqSum acc = {0.0, 0.0};
+    for (int e = threadIdx.x; e < 1024; e += TILE_THREADS) {
+        const int ii = e >> 5, jj = e & 31, i = t.i0 + ii, j = t.j0 + jj;
+        if (i < mx && j < mx) {
+            const double v = tile32_sum(red, e);
+            acc.add(v);
+            double c = E ? E[(size_t)i * mx + j] + v : v;
+            if (eye && i == j) c += 1.0;
+            Cm[(size_t)i * mx + j] = c;
+        }
+    }
+    if (!part) return;
+    sq_reduce(acc, wsum);
+    if (threadIdx.x < 2) part[2 * ((size_t)prob * (tm * tm) + blockIdx.x) + threadIdx.x] = sq_wave_sum(wsum, threadIdx.x);
+}
+
+// ---- entry (i, j) of Abar = A' - D K (= A-Bu*Kuk-Bλ*Kλk, lqr.jl:169) from a knot's [A' | D] [mx][na] and a gain K [mu][mx], and entry (r, j) of R K
+template <class PK>
+__device__ __forceinline__ double ric_abar_entry(const double* AD, int na, int mx, int mu, int i, int j, PK K) {
+    double s = AD[(size_t)i * na + j];
+    for (int c = 0; c < mu; c++) s -= AD[(size_t)i * na + mx + c] * K[c * mx + j];
+    return s;
+}
+template <class PR, class PK>
+__device__ __forceinline__ double ric_rk_entry(PR R, int mx, int mu, int r, int j, PK K) {
+    double s = 0.0;
+    for (int c = 0; c < mu; c++) s += R[r * mu + c] * K[c * mx + j];
+    return s;
+}
+
+// ---- host side
 // The sizes of g from a, and the workspace of one launch walked once: g's arrays are placed one behind the other from `base` (null: nowhere); returns the doubles
-// of the whole (= ric_total_work_doubles)
+// of the whole (= ric_total_work_doubles).  Defined in riccati.hip
 size_t ric_lay_out(RicGrid& g, const RicArgs& a, double* base);
 // [A' | D] of every knot of every problem into g.AD, the pivots and the singular flag of every knot behind g.scratch (ric_knot_piv), Pk = Q into buffer 0 of g.P:
-// ric_project_kernel, the one projection of the library.  g: laid out by ric_lay_out, with A, Bu, Bl, G, Q and q_stride set
+// ric_project_kernel, the one projection of the library (riccati.hip).  g: laid out by ric_lay_out, with A, Bu, Bl, G, Q and q_stride set
 hipError_t launch_ric_project(const RicGrid& g, const RicArgs& a, hipStream_t stream);
-// the launch record of the doubling kernels for these arguments (policy_doubling.hip): laid out on a.work, with the models, Q, R and their strides, status and stop
-RicGrid dbl_ric_grid(const RicArgs& a);
+// the launch record for these arguments: laid out on a.work, with the models, Q, R and their strides, kbreak, status and stop; everything else zero, for the caller to set
+inline RicGrid ric_grid_of(const RicArgs& a) {
+    RicGrid g;
+    memset(&g, 0, sizeof(g));
+    (void)ric_lay_out(g, a, a.work);
+    g.A = a.A; g.Bu = a.Bu; g.Bl = a.Bl; g.G = a.G; g.Q = a.Q; g.R = a.R; g.q_stride = a.q_stride; g.r_stride = a.r_stride;
+    g.kbreak = a.kbreak; g.status = a.status; g.stop = a.stop;
+    return g;
+}
+// does the resident tile set serve mx states on nw wavefronts: whole k-groups of four (wave_tile16_db) and a wavefront's share of the 16x16 tiles within ResTiles
+// (mx <= 96 on eight).  Each resident kernel adds its own LDS formula
+inline bool res_tiles_serve(int mx, int nw) {
+    const int t16 = (mx + 15) / 16;
+    return (mx & 3) == 0 && t16 * t16 <= RES_TILES * nw;
+}
 
 }  // namespace cclqr

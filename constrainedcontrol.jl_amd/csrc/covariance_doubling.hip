@@ -33,7 +33,7 @@ struct CovGrid {
 };
 
 // =====================================================================================================================
-// SETUP: Md = Abar' with Abar = A' - D K formed by the operations of dbl_setup_kernel in their order (only the store is transposed), Sd = D Wu D' / w, the
+// SETUP: Md = Abar' with Abar = A' - D K formed as dbl_setup_kernel forms it (ric_abar_entry; only the store is transposed), Sd = D Wu D' / w, the
 // terminal matrix Σ0 / w, and w.  tr W = tr(Wu D'D) costs mx mu^2: every workgroup of a problem computes it, by the same operations, so all agree on w bitwise
 __global__ __launch_bounds__(TILE_THREADS) void cov_setup_kernel(RicGrid a, CovGrid c) {
     extern __shared__ double cl[];      // K [mu][mx] | Wu [mu][mu] | D Wu of this workgroup's rows [COV_RU][mu] | the terms of tr(Wu D'D) [mu][mu]
@@ -81,9 +81,7 @@ __global__ __launch_bounds__(TILE_THREADS) void cov_setup_kernel(RicGrid a, CovG
         const int i = blockIdx.x * COV_RU + r;
         if (i >= mx) break;
         for (int j = tid; j < mx; j += TILE_THREADS) {
-            double s = AD[(size_t)i * na + j];                                        // Abar = A' - D K (= A-Bu*Kuk-Bλ*Kλk)     lqr.jl:169
-            for (int p = 0; p < mu; p++) s -= AD[(size_t)i * na + mx + p] * cl[p * mx + j];
-            Md[(size_t)j * mx + i] = s;                                               // stored as Abar'
+            Md[(size_t)j * mx + i] = ric_abar_entry(AD, na, mx, mu, i, j, cl);        // Abar = A' - D K (lqr.jl:169), stored as Abar'
             double q = 0.0;                                                           // W = D Wu D'
             for (int p = 0; p < mu; p++) q += dw[r * mu + p] * AD[(size_t)j * na + mx + p];
             Sd[(size_t)i * mx + j] = q * inv;
@@ -175,7 +173,7 @@ hipError_t launch_covariance_doubling(const CovArgs& v, hipStream_t stream) {
         c.scaled = 0;
         if (v.Sigma0) { a.Q = v.Sigma0; a.q_stride = v.s0_stride; }
     }
-    const RicGrid g = dbl_ric_grid(a);
+    const RicGrid g = ric_grid_of(a);
     if (a.N != 1) {
         if (e == hipSuccess) e = launch_ric_project(g, a, stream);
         const size_t lds = (mu * mx + 2 * mu * mu + (size_t)COV_RU * mu) * sizeof(double);

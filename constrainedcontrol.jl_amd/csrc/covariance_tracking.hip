@@ -25,7 +25,7 @@ namespace cclqr {
 
 #define CTK_THREADS 512
 #define CTK_WAVES (CTK_THREADS / 64)
-#define CTK_TILES 5      // 16x16 tiles one wavefront holds across a barrier (PolTiles of policy.hip: ceil(6 * 6 / 8) at 96 states)
+#define CTK_TILES 5      // 16x16 tiles one wavefront holds across a barrier (ResTiles of cclqr_riccati_dev.h)
 #define CTK_PRE 18       // doubles of the next knot's A' one lane holds while the products run: ceil(96 * 96 / 512)
 #define CTK_PRE_S 2      // ... and of its D and of its K: ceil(mu mx / 512) (ctk_resident_fits)
 
@@ -77,21 +77,14 @@ size_t ctk_resident_lds_bytes(int mx, int mu) {
 // THE fit rule of the resident kernel: whole k-groups of four, a wavefront's share of the tiles in its registers (mx <= 96), a lane's share of the next knot's
 // model in its registers, and the operands in one CU's LDS
 bool ctk_resident_fits(int mx, int mu) {
-    const int t16 = (mx + 15) / 16;
-    return (mx & 3) == 0 && t16 * t16 <= CTK_TILES * CTK_WAVES && mx * mx <= CTK_PRE * CTK_THREADS && mu * mx <= CTK_PRE_S * CTK_THREADS &&
-           ctk_resident_lds_bytes(mx, mu) <= 158 * 1024;
+    return res_tiles_serve(mx, CTK_WAVES) && mx * mx <= CTK_PRE * CTK_THREADS && mu * mx <= CTK_PRE_S * CTK_THREADS && ctk_resident_lds_bytes(mx, mu) <= 158 * 1024;
 }
 int ctk_chosen_path(int mx, int mu, int path) { return (path != 2 && ctk_resident_fits(mx, mu)) ? 1 : 2; }
 
 // a wave-uniform value, hidden from loop-invariant code motion
 __device__ __forceinline__ int ctk_opaque_s(int x) { asm volatile("" : "+s"(x)); return x; }
 
-struct CtkTiles {      // PolTiles of policy.hip: five named values, put and picked by selects, so that the tile loops stay rolled and nothing is indexed at run time
-    v4d a0, a1, a2, a3, a4;
-    __device__ __forceinline__ void put(int t, v4d r) { if (t == 0) a0 = r; if (t == 1) a1 = r; if (t == 2) a2 = r; if (t == 3) a3 = r; if (t == 4) a4 = r; }
-    __device__ __forceinline__ v4d pick(int t) const { return t == 0 ? a0 : (t == 1 ? a1 : (t == 2 ? a2 : (t == 3 ? a3 : a4))); }
-};
-static_assert(CTK_TILES == 5, "CtkTiles holds five tiles");
+static_assert(CTK_TILES == RES_TILES, "the resident kernel holds its tiles in ResTiles");
 
 // the sizes a knot's code is written in, derived from (mx, mu)
 struct CtkSizes {
@@ -139,7 +132,8 @@ __global__ __launch_bounds__(CTK_THREADS) void ctk_resident_kernel(RicGrid a, Ct
         // (strides, LDS bases, lane predicates, the index pairs of the unrolled walks) they do not fit the scalar registers; re-derived they are a few dozen
         // scalar operations against a step's thousands of cycles
         const CtkSizes z(ctk_opaque_s(a.mx), ctk_opaque_s(a.mu), sl);
-        const int mx = z.mx, mu = z.mu, na = z.na, mm = z.mm, ms = z.ms, t16 = z.t16, ntile = z.ntile, ng = z.ng;
+        const int mx = z.mx, mu = z.mu, na = z.na, mm = z.mm, ms = z.ms;
+        const ResShape rs = {mx, z.t16, z.ntile, z.ng, wave, li, lk, CTK_WAVES};
         lds_double *const Ab = z.Ab, *const X = z.X, *const Kl = z.Kl, *const Dl = z.Dl, *const Wl = z.Wl, *const Vl = z.Vl, *const red = z.red;
         // this lane's elements of A' / Abar: e = tid + 512 r = jj mx + i, walked by increments (no division per element)
         const int i0 = tid % mx, j0 = tid / mx, di = CTK_THREADS % mx, dj = CTK_THREADS / mx;
@@ -230,17 +224,8 @@ __global__ __launch_bounds__(CTK_THREADS) void ctk_resident_kernel(RicGrid a, Ct
                 }
             }
         }
-        const v4d zero4 = {0.0, 0.0, 0.0, 0.0};
-        CtkTiles acc = {zero4, zero4, zero4, zero4, zero4};
-        if (!last) {      // T = Abar Σ: this wavefront's tiles, kept in registers
-#pragma unroll 1
-            for (int t = 0; t < CTK_TILES && wave + CTK_WAVES * t < ntile; t++) {
-                const int tile = wave + CTK_WAVES * t;
-                const int r0 = (tile / t16) << 4, q0 = (tile % t16) << 4;
-                const int ic = (r0 + li < mx) ? r0 + li : mx - 1, jc = (q0 + li < mx) ? q0 + li : mx - 1;
-                acc.put(t, wave_tile16_db(ng, Ab + lk * mx + ic, 4 * mx, X + lk * mx + jc, 4 * mx));
-            }
-        }
+        ResTiles acc = res_zero();
+        if (!last) acc = res_mul(rs, Ab, X);      // T = Abar Σ: this wavefront's tiles, kept in registers
         __syncthreads();      // every wavefront has read Σ_j and K_j: X may take Tt, Kl may take D Wu; red and Vl are complete
         if (tid == 0) {
             double cx = 0.0, cu = 0.0;
@@ -265,44 +250,15 @@ __global__ __launch_bounds__(CTK_THREADS) void ctk_resident_kernel(RicGrid a, Ct
             for (int p = 0; p < mu; p++) s += Dl[i * mu + p] * Wl[p * mu + q];
             Kl[e] = s;
         }
-#pragma unroll 1
-        for (int t = 0; t < CTK_TILES && wave + CTK_WAVES * t < ntile; t++) {
-            const int tile = wave + CTK_WAVES * t;
-            const int r0 = (tile / t16) << 4, q = ((tile % t16) << 4) + li;
-            const v4d v = acc.pick(t);
-            if (q < mx) {
-#pragma unroll
-                for (int r = 0; r < 4; r++) { const int i = r0 + lk + 4 * r; if (i < mx) X[q * mx + i] = v[r]; }      // Tt[q][i] = T[i][q]
-            }
-        }
+        res_each(rs, acc, [&](int i, int q, double v) { X[q * mx + i] = v; });      // Tt[q][i] = T[i][q]
         __syncthreads();
-        // T Abar'
-#pragma unroll 1
-        for (int t = 0; t < CTK_TILES && wave + CTK_WAVES * t < ntile; t++) {
-            const int tile = wave + CTK_WAVES * t;
-            const int r0 = (tile / t16) << 4, q0 = (tile % t16) << 4;
-            const int ic = (r0 + li < mx) ? r0 + li : mx - 1, jc = (q0 + li < mx) ? q0 + li : mx - 1;
-            acc.put(t, wave_tile16_db(ng, X + lk * mx + ic, 4 * mx, Ab + lk * mx + jc, 4 * mx));
-        }
+        acc = res_mul(rs, X, Ab);                                                  // T Abar'
         __syncthreads();      // every wavefront has read Tt: the buffer may take Σ_{j+1}
+        res_each(rs, acc, [&](int i, int q, double v) {                             // Σ_{j+1} = Abar Σ_j Abar' + (D Wu) D'
 #pragma unroll 1
-        for (int t = 0; t < CTK_TILES && wave + CTK_WAVES * t < ntile; t++) {
-            const int tile = wave + CTK_WAVES * t;
-            const int r0 = (tile / t16) << 4, q = ((tile % t16) << 4) + li;
-            const v4d va = acc.pick(t);
-            if (q < mx) {
-#pragma unroll
-                for (int r = 0; r < 4; r++) {
-                    const int i = r0 + lk + 4 * r;
-                    if (i < mx) {
-                        double v = va[r];                                 // Σ_{j+1} = Abar Σ_j Abar' + (D Wu) D'
-#pragma unroll 1
-                        for (int p = 0; p < mu; p++) v += Kl[i * mu + p] * Dl[q * mu + p];
-                        X[i * mx + q] = v;
-                    }
-                }
-            }
-        }
+            for (int p = 0; p < mu; p++) v += Kl[i * mu + p] * Dl[q * mu + p];
+            X[i * mx + q] = v;
+        });
         __syncthreads();      // Σ_{j+1} is complete; Abar_j', D_j and D_j Wu are retired
     }
     if (status == 0 && c.Sigma) {
@@ -402,40 +358,26 @@ __global__ __launch_bounds__(TILE_THREADS) void ctk_abar_kernel(RicGrid a, CtkGr
     for (int r = 0; r < CTK_RU; r++) {
         const int i = blockIdx.x * CTK_RU + r;
         if (i >= mx) break;
-        for (int q = tid; q < mx; q += TILE_THREADS) {
-            double s = AD[(size_t)i * na + q];                                        // Abar = A' - D K (= A-Bu*Ku-Bλ*Kλ)   lqr_tracking.jl:107
-            for (int p = 0; p < mu; p++) s -= AD[(size_t)i * na + mx + p] * kl[p * mx + q];
-            AbT[(size_t)q * mx + i] = s;                                              // stored as Abar'
-        }
+        for (int q = tid; q < mx; q += TILE_THREADS) AbT[(size_t)q * mx + i] = ric_abar_entry(AD, na, mx, mu, i, q, kl);      // Abar = A' - D K (lqr_tracking.jl:107), stored as Abar'
     }
 }
 
 __global__ __launch_bounds__(TILE_THREADS) void ctk_t_kernel(RicGrid a, int j) {
     __shared__ double red[4][1024];
-    const int prob = blockIdx.y, tid = threadIdx.x, li = tid & 15;
-    const int mx = a.mx;
+    const int prob = blockIdx.y, mx = a.mx;
     if (a.status[prob] != 0 || ctk_singular(a, prob, j)) return;
-    const int i0 = (blockIdx.x / a.tm) << 5, j0 = (blockIdx.x % a.tm) << 5;
     const double* S = a.P + ((size_t)(j & 1) * a.nprob + prob) * mx * mx;
-    const double* AbT = a.Abar + (size_t)prob * mx * mx;
-    double* Tt = a.W + (size_t)prob * mx * a.na;
-    const bool iok[2] = {i0 + li < mx, i0 + 16 + li < mx}, jok[2] = {j0 + li < mx, j0 + 16 + li < mx};
-    tile_mfma_splitk(mx,
-        [&](int kk, int h) { return iok[h] ? AbT[(size_t)kk * mx + i0 + 16 * h + li] : 0.0; },
-        [&](int kk, int h) { return jok[h] ? S[(size_t)kk * mx + j0 + 16 * h + li] : 0.0; }, red);
-    for (int e = tid; e < 1024; e += TILE_THREADS) {      // Tt[q][i] = T[i][q]: consecutive threads, consecutive i
-        const int jj = e >> 5, ii = e & 31, i = i0 + ii, q = j0 + jj;
-        if (i < mx && q < mx) Tt[(size_t)q * mx + i] = ((red[0][ii * 32 + jj] + red[1][ii * 32 + jj]) + red[2][ii * 32 + jj]) + red[3][ii * 32 + jj];
-    }
+    tile32_product_transposed(tile32_at(blockIdx.x, a.tm, mx), mx, a.Abar + (size_t)prob * mx * mx, S, a.W + (size_t)prob * mx * a.na, red);      // Tt = (Abar Σ_j)'
 }
 
 __global__ __launch_bounds__(TILE_THREADS) void ctk_next_kernel(RicGrid a, CtkGrid c, int j) {
     __shared__ double red[4][1024];
     extern __shared__ double dt[];      // (D Wu) of the tile's rows [32][mu] | D of the tile's columns [32][mu]
-    const int prob = blockIdx.y, tid = threadIdx.x, li = tid & 15;
+    const int prob = blockIdx.y, tid = threadIdx.x;
     const int mx = a.mx, mu = a.mu, na = a.na;
     if (a.status[prob] != 0 || ctk_singular(a, prob, j)) return;
-    const int i0 = (blockIdx.x / a.tm) << 5, j0 = (blockIdx.x % a.tm) << 5;
+    const Tile32 t = tile32_at(blockIdx.x, a.tm, mx);
+    const int i0 = t.i0, j0 = t.j0;
     double* Sn = a.P + ((size_t)((j + 1) & 1) * a.nprob + prob) * mx * mx;
     const double* Tt = a.W + (size_t)prob * mx * na;
     const double* AbT = a.Abar + (size_t)prob * mx * mx;
@@ -450,14 +392,11 @@ __global__ __launch_bounds__(TILE_THREADS) void ctk_next_kernel(RicGrid a, CtkGr
         DWi[e] = s;
         Dj[e] = (j0 + x < mx) ? AD[(size_t)(j0 + x) * na + mx + q] : 0.0;
     }
-    const bool iok[2] = {i0 + li < mx, i0 + 16 + li < mx}, jok[2] = {j0 + li < mx, j0 + 16 + li < mx};
-    tile_mfma_splitk(mx,
-        [&](int kk, int h) { return iok[h] ? Tt[(size_t)kk * mx + i0 + 16 * h + li] : 0.0; },
-        [&](int kk, int h) { return jok[h] ? AbT[(size_t)kk * mx + j0 + 16 * h + li] : 0.0; }, red);
+    tile32_product(t, mx, Tt, 1, AbT, 0, red);      // T Abar', T read from its transpose
     for (int e = tid; e < 1024; e += TILE_THREADS) {
         const int ii = e >> 5, jj = e & 31, i = i0 + ii, q = j0 + jj;
         if (i < mx && q < mx) {
-            double v = ((red[0][e] + red[1][e]) + red[2][e]) + red[3][e];             // Σ_{j+1} = Abar Σ_j Abar' + (D Wu) D'
+            double v = tile32_sum(red, e);                                            // Σ_{j+1} = Abar Σ_j Abar' + (D Wu) D'
             for (int p = 0; p < mu; p++) v += DWi[ii * mu + p] * Dj[jj * mu + p];
             Sn[(size_t)i * mx + q] = v;
         }
@@ -467,12 +406,8 @@ __global__ __launch_bounds__(TILE_THREADS) void ctk_next_kernel(RicGrid a, CtkGr
 hipError_t launch_covariance_tracking(const CtkArgs& v, hipStream_t stream) {
     const RicArgs& a = v.r;
     if (a.nprob <= 0) return hipSuccess;
-    RicGrid g;
-    memset(&g, 0, sizeof(g));
-    (void)ric_lay_out(g, a, a.work);
-    g.A = a.A; g.Bu = a.Bu; g.Bl = a.Bl; g.G = a.G;
+    RicGrid g = ric_grid_of(a);      // (the record also carries a.R, its stride and a.stop: no tracking kernel and no projection kernel reads them)
     g.Q = g.P; g.q_stride = (long long)a.mx * a.mx;      // the projection's "Pk = Q" copies Σ_0 onto itself
-    g.kbreak = a.kbreak; g.status = a.status;
     CtkGrid c;
     memset(&c, 0, sizeof(c));
     c.Kin = v.Kin; c.k_stride = v.k_stride; c.nK = v.nK;

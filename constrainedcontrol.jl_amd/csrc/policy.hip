@@ -18,7 +18,8 @@ namespace cclqr {
 
 #define POL_THREADS 512
 #define POL_WAVES (POL_THREADS / 64)
-#define POL_TILES 5      // 16x16 tiles of an mx x mx matrix one wavefront holds in registers across a barrier: ceil(6 * 6 / 8) at the resident limit of 96 states
+#define POL_TILES 5      // 16x16 tiles of an mx x mx matrix one wavefront holds in registers across a barrier (ResTiles of cclqr_riccati_dev.h)
+static_assert(POL_TILES == RES_TILES, "the resident kernel holds its tiles in ResTiles");
 
 // what the policy kernels take besides the Riccati launch record
 struct PolGrid {
@@ -47,15 +48,6 @@ __device__ inline const double* pol_gain(const RicGrid& a, const PolGrid& q, int
 size_t pol_resident_lds_bytes(int mx, int mu) {
     return (2 * (size_t)mx * mx + 2 * (size_t)mu * mx + (size_t)mu * mu + POL_WAVES + 2) * sizeof(double);
 }
-
-// A wavefront's register-held tiles: five named values, tile t put and picked by selects, so that the tile loops stay rolled (one copy of their bodies) and
-// nothing is indexed at run time (an array indexed inside a rolled loop is placed in scratch memory)
-struct PolTiles {
-    v4d a0, a1, a2, a3, a4;
-    __device__ __forceinline__ void put(int t, v4d r) { if (t == 0) a0 = r; if (t == 1) a1 = r; if (t == 2) a2 = r; if (t == 3) a3 = r; if (t == 4) a4 = r; }
-    __device__ __forceinline__ v4d pick(int t) const { return t == 0 ? a0 : (t == 1 ? a1 : (t == 2 ? a2 : (t == 3 ? a3 : a4))); }
-};
-static_assert(POL_TILES == 5, "PolTiles holds five tiles");
 
 __global__ __launch_bounds__(POL_THREADS) void policy_resident_kernel(RicGrid a, PolGrid q, double* P_out) {
     extern __shared__ double pl[];
@@ -87,20 +79,15 @@ __global__ __launch_bounds__(POL_THREADS) void policy_resident_kernel(RicGrid a,
             __syncthreads();
             for (int e = tid; e < mu * mx; e += POL_THREADS) {
                 const int r = e / mx, j = e - r * mx;
-                double s = 0.0;
-                for (int c = 0; c < mu; c++) s += Rl[r * mu + c] * Kl[c * mx + j];
-                KR[e] = s;
+                KR[e] = ric_rk_entry(Rl, mx, mu, r, j, Kl);
             }
             for (int i = tid >> 5; i < mx; i += POL_THREADS / 32)         // Abar = A' - D Kuk (= A-Bu*Kuk-Bλ*Kλk)   lqr.jl:169
-                for (int j = tid & 31; j < mx; j += 32) {
-                    double s = AD[(size_t)i * na + j];
-                    for (int c = 0; c < mu; c++) s -= AD[(size_t)i * na + mx + c] * Kl[c * mx + j];
-                    Ab[i * mx + j] = s;
-                }
+                for (int j = tid & 31; j < mx; j += 32) Ab[i * mx + j] = ric_abar_entry(AD, na, mx, mu, i, j, Kl);
             __syncthreads();
         }
-        const v4d zero4 = {0.0, 0.0, 0.0, 0.0};
-        PolTiles acc = {zero4, zero4, zero4, zero4, zero4};
+        // The tile loops below are res_mul / res_each of cclqr_riccati_dev.h written out: on those functions this kernel compiled to the same resources and the
+        // same MFMA, LDS and memory instructions but 53 more scalar and address instructions, and 4096 problems of 24 states ran 2.7 % slower (profiles/r23)
+        ResTiles acc = res_zero();
         // V = Abar' Pk: this wavefront's tiles, kept in registers
 #pragma unroll 1
         for (int t = 0; t < POL_TILES && wave + POL_WAVES * t < ntile; t++) {      // (one copy of the tile's loop; the result goes to its register slot by selects)
@@ -225,9 +212,7 @@ __global__ __launch_bounds__(TILE_THREADS) void pol_abar_kernel(RicGrid a, PolGr
         double* KR = a.KRK + (size_t)prob * mu * mx;
         for (int e = tid; e < mu * mx; e += TILE_THREADS) {
             const int r = e / mx, j = e - r * mx;
-            double s = 0.0;
-            for (int c = 0; c < mu; c++) s += Rp[r * mu + c] * kl[c * mx + j];
-            KR[e] = s;
+            KR[e] = ric_rk_entry(Rp, mx, mu, r, j, kl);
         }
     }
     const double* AD = a.AD + (size_t)prob * mx * na;
@@ -235,41 +220,27 @@ __global__ __launch_bounds__(TILE_THREADS) void pol_abar_kernel(RicGrid a, PolGr
     for (int r = 0; r < POL_RU; r++) {
         const int i = blockIdx.x * POL_RU + r;
         if (i >= mx) break;
-        for (int j = tid; j < mx; j += TILE_THREADS) {                                // Abar = A' - D Kuk (= A-Bu*Kuk-Bλ*Kλk)   lqr.jl:169
-            double s = AD[(size_t)i * na + j];
-            for (int c = 0; c < mu; c++) s -= AD[(size_t)i * na + mx + c] * kl[c * mx + j];
-            Abar[(size_t)i * mx + j] = s;
-        }
+        for (int j = tid; j < mx; j += TILE_THREADS) Abar[(size_t)i * mx + j] = ric_abar_entry(AD, na, mx, mu, i, j, kl);      // Abar = A' - D Kuk   lqr.jl:169
     }
 }
 
 __global__ __launch_bounds__(TILE_THREADS) void pol_v_kernel(RicGrid a, int k) {
     __shared__ double red[4][1024];
-    const int prob = blockIdx.y, tid = threadIdx.x, li = tid & 15;
-    const int mx = a.mx;
+    const int prob = blockIdx.y, mx = a.mx;
     if (a.stop[prob]) return;           // pol_abar_kernel of this step has evaluated the break test
-    const int i0 = (blockIdx.x / a.tm) << 5, j0 = (blockIdx.x % a.tm) << 5;
     const double* P = a.P + ((size_t)((a.N - 1 - k) & 1) * a.nprob + prob) * mx * mx;
-    const double* Abar = a.Abar + (size_t)prob * mx * mx;
-    double* Vt = a.W + (size_t)prob * mx * a.na;
-    const bool iok[2] = {i0 + li < mx, i0 + 16 + li < mx}, jok[2] = {j0 + li < mx, j0 + 16 + li < mx};
-    tile_mfma_splitk(mx,
-        [&](int kk, int h) { return iok[h] ? Abar[(size_t)kk * mx + i0 + 16 * h + li] : 0.0; },
-        [&](int kk, int h) { return jok[h] ? P[(size_t)kk * mx + j0 + 16 * h + li] : 0.0; }, red);
-    for (int e = tid; e < 1024; e += TILE_THREADS) {      // Vt[j][i] = V[i][j]: consecutive threads, consecutive i
-        const int jj = e >> 5, ii = e & 31, i = i0 + ii, j = j0 + jj;
-        if (i < mx && j < mx) Vt[(size_t)j * mx + i] = ((red[0][ii * 32 + jj] + red[1][ii * 32 + jj]) + red[2][ii * 32 + jj]) + red[3][ii * 32 + jj];
-    }
+    tile32_product_transposed(tile32_at(blockIdx.x, a.tm, mx), mx, a.Abar + (size_t)prob * mx * mx, P, a.W + (size_t)prob * mx * a.na, red);      // Vt = (Abar' Pk)'
 }
 
 __global__ __launch_bounds__(TILE_THREADS) void pol_pn_kernel(RicGrid a, PolGrid q, int k) {
     __shared__ double red[4][1024];
     extern __shared__ double kt[];      // KuI [mu][32] | KRJ [mu][32]
     __shared__ double wsum[4];
-    const int prob = blockIdx.y, tid = threadIdx.x, lane = tid & 63, li = lane & 15;
+    const int prob = blockIdx.y, tid = threadIdx.x, lane = tid & 63;
     const int mx = a.mx, mu = a.mu;
     if (a.stop[prob]) return;
-    const int i0 = (blockIdx.x / a.tm) << 5, j0 = (blockIdx.x % a.tm) << 5;
+    const Tile32 t = tile32_at(blockIdx.x, a.tm, mx);
+    const int i0 = t.i0, j0 = t.j0;
     const double* P = a.P + ((size_t)((a.N - 1 - k) & 1) * a.nprob + prob) * mx * mx;
     double* Pn = a.P + ((size_t)((a.N - k) & 1) * a.nprob + prob) * mx * mx;
     const double* Vt = a.W + (size_t)prob * mx * a.na;
@@ -283,15 +254,12 @@ __global__ __launch_bounds__(TILE_THREADS) void pol_pn_kernel(RicGrid a, PolGrid
         KuI[e] = (i0 + x < mx) ? Kp[(size_t)c * mx + i0 + x] : 0.0;
         KRJ[e] = (j0 + x < mx) ? KR[(size_t)c * mx + j0 + x] : 0.0;
     }
-    const bool iok[2] = {i0 + li < mx, i0 + 16 + li < mx}, jok[2] = {j0 + li < mx, j0 + 16 + li < mx};
-    tile_mfma_splitk(mx,
-        [&](int kk, int h) { return iok[h] ? Vt[(size_t)kk * mx + i0 + 16 * h + li] : 0.0; },
-        [&](int kk, int h) { return jok[h] ? Abar[(size_t)kk * mx + j0 + 16 * h + li] : 0.0; }, red);
+    tile32_product(t, mx, Vt, 1, Abar, 0, red);      // V Abar, V read from its transpose
     double acc = 0.0;
     for (int e = tid; e < 1024; e += TILE_THREADS) {
         const int ii = e >> 5, jj = e & 31, i = i0 + ii, j = j0 + jj;
         if (i < mx && j < mx) {
-            double v = Qp[(size_t)i * mx + j] + (((red[0][e] + red[1][e]) + red[2][e]) + red[3][e]);      // Pkp1 = Q + Kuk'*R*Kuk + Abar'*Pk*Abar   lqr.jl:170
+            double v = Qp[(size_t)i * mx + j] + tile32_sum(red, e);      // Pkp1 = Q + Kuk'*R*Kuk + Abar'*Pk*Abar   lqr.jl:170
             for (int c = 0; c < mu; c++) v += KuI[c * 32 + ii] * KRJ[c * 32 + jj];
             Pn[(size_t)i * mx + j] = v;
             const double d = P[(size_t)i * mx + j] - v;
@@ -337,12 +305,8 @@ __global__ void pol_finish_kernel(RicGrid a, PolGrid q, double* P_out) {
 hipError_t launch_policy(const PolArgs& p, hipStream_t stream) {
     const RicArgs& a = p.r;
     if (a.nprob <= 0) return hipSuccess;
-    RicGrid g;
-    memset(&g, 0, sizeof(g));
-    (void)ric_lay_out(g, a, a.work);
+    RicGrid g = ric_grid_of(a);
     g.tol = a.tol;
-    g.A = a.A; g.Bu = a.Bu; g.Bl = a.Bl; g.G = a.G; g.Q = a.Q; g.R = a.R; g.q_stride = a.q_stride; g.r_stride = a.r_stride;
-    g.kbreak = a.kbreak; g.status = a.status; g.stop = a.stop;
     PolGrid q;
     q.Kin = p.Kin; q.k_stride = p.k_stride; q.nK = p.nK; q.dnorm = p.dnorm;
     const size_t np = a.nprob, mu = a.mu, mx = a.mx;
@@ -354,8 +318,7 @@ hipError_t launch_policy(const PolArgs& p, hipStream_t stream) {
     if (e != hipSuccess) return e;
     // resident wherever the Riccati is (ric_chosen_path: the same shapes, the same crossover), provided a wavefront's share of the tiles fits its registers -- mx <= 96;
     // the one shape beyond it the Riccati's rule lets through (100 states without inputs) runs tiled
-    const int t16 = (a.mx + 15) / 16;
-    if (ric_chosen_path(a) == 1 && t16 * t16 <= POL_TILES * POL_WAVES && pol_resident_lds_bytes(a.mx, a.mu) <= 158 * 1024)
+    if (ric_chosen_path(a) == 1 && res_tiles_serve(a.mx, POL_WAVES) && pol_resident_lds_bytes(a.mx, a.mu) <= 158 * 1024)
         return launch_lds(policy_resident_kernel, dim3(a.nprob), dim3(POL_THREADS), pol_resident_lds_bytes(a.mx, a.mu), stream, g, q, a.P_out);
     const size_t lds_abar = mu * mx * sizeof(double), lds_pn = 2 * mu * 32 * sizeof(double);
     void (*const abar)(RicGrid, PolGrid, int) = pol_abar_kernel;

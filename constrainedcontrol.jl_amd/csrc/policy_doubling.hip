@@ -20,7 +20,8 @@ namespace cclqr {
 
 #define DBL_THREADS 512
 #define DBL_WAVES (DBL_THREADS / 64)
-#define DBL_TILES 5      // 16x16 tiles of an mx x mx matrix one wavefront holds in registers across a barrier: ceil(6 * 6 / 8) at the resident limit of 96 states
+#define DBL_TILES 5      // 16x16 tiles of an mx x mx matrix one wavefront holds in registers across a barrier (ResTiles of cclqr_riccati_dev.h)
+static_assert(DBL_TILES == RES_TILES, "the resident kernel holds its tiles in ResTiles");
 #define DBL_RU 16        // rows of Abar / Qbar per workgroup of the setup kernel
 #define DBL_GROWTH 1e50  // norm(M) beyond which the next level could overflow: with norm(M) <= 1e50, S(2n) is about 1e200 |Q| and the final M' Q M stays finite
 
@@ -39,19 +40,8 @@ struct DblGrid {
 
 size_t dbl_resident_lds_bytes(int mx) { return (2 * (size_t)mx * mx + 4 * DBL_WAVES) * sizeof(double); }
 
-// A Frobenius norm whose sum of squares must not overflow: before the growth stop fires the increments of an unstable closed loop reach 1e200 (S(2n) is about
-// norm(M)^2 |Q|), and their squares do not exist in fp64.  Two sums, as in Blue's algorithm without its small range: an entry above 2^500 is squared after scaling
-// by 2^-600.  (An entry below 2^-511 underflows when squared: such a norm lies far below any tol and is reported as smaller than it is, down to 0.)
-struct DblSq {
-    double mid, big;
-    __device__ __forceinline__ void add(double v) {
-        if (fabs(v) > 0x1p500) { const double s = v * 0x1p-600; big += s * s; } else mid += v * v;
-    }
-    __device__ __forceinline__ double norm() const { return big > 0.0 ? sqrt(big + (mid * 0x1p-600) * 0x1p-600) * 0x1p600 : sqrt(mid); }
-};
-
 // =====================================================================================================================
-// SETUP, both shapes: Md = Abar = A' - D K and Sd = Qbar = Q + K' (R K), once.  Abar is formed with the operations of policy.hip, in their order: the two
+// SETUP, both shapes: Md = Abar = A' - D K and Sd = Qbar = Q + K' (R K), once.  Abar is formed by the function policy.hip forms it by (ric_abar_entry): the two
 // evaluations start from the same matrix.  The lead workgroup of a problem reads the singular flag of its G Bλ (lqr.jl:151)
 __global__ __launch_bounds__(TILE_THREADS) void dbl_setup_kernel(RicGrid a, DblGrid d) {
     extern __shared__ double kl[];      // K [mu][mx] | R K [mu][mx]
@@ -65,9 +55,7 @@ __global__ __launch_bounds__(TILE_THREADS) void dbl_setup_kernel(RicGrid a, DblG
     const double* Rp = ric_R_of(a, prob);
     for (int e = tid; e < mu * mx; e += TILE_THREADS) {
         const int r = e / mx, j = e - r * mx;
-        double s = 0.0;
-        for (int c = 0; c < mu; c++) s += Rp[r * mu + c] * kl[c * mx + j];
-        KR[e] = s;
+        KR[e] = ric_rk_entry(Rp, mx, mu, r, j, kl);
     }
     __syncthreads();
     const double* AD = a.AD + (size_t)prob * mx * na;
@@ -78,9 +66,7 @@ __global__ __launch_bounds__(TILE_THREADS) void dbl_setup_kernel(RicGrid a, DblG
         const int i = blockIdx.x * DBL_RU + r;
         if (i >= mx) break;
         for (int j = tid; j < mx; j += TILE_THREADS) {
-            double s = AD[(size_t)i * na + j];                                        // Abar = A' - D K (= A-Bu*Kuk-Bλ*Kλk)     lqr.jl:169
-            for (int c = 0; c < mu; c++) s -= AD[(size_t)i * na + mx + c] * kl[c * mx + j];
-            Md[(size_t)i * mx + j] = s;
+            Md[(size_t)i * mx + j] = ric_abar_entry(AD, na, mx, mu, i, j, kl);        // Abar = A' - D K (= A-Bu*Kuk-Bλ*Kλk)     lqr.jl:169
             double q = Qp[(size_t)i * mx + j];                                        // Qbar = Q + Kuk'*R*Kuk                    lqr.jl:170
             for (int c = 0; c < mu; c++) q += kl[c * mx + i] * KR[c * mx + j];
             Sd[(size_t)i * mx + j] = q;
@@ -107,13 +93,6 @@ __global__ void dbl_no_step_kernel(RicGrid a, DblGrid d) {
 //                           into U / V where a product needs them -- a few mx^2 reads per level against its 3 mx^3
 // U holds Md whenever a doubling starts (the doubling leaves the new Md there), so a level stages one matrix (Sd); an accumulation stages three.
 // LDS: 2 mx^2 + 32 doubles = 113 152 B at mx = 84, 147 712 B at mx = 96, of 163 840.
-struct DblTiles {
-    v4d a0, a1, a2, a3, a4;
-    __device__ __forceinline__ void put(int t, v4d r) { if (t == 0) a0 = r; if (t == 1) a1 = r; if (t == 2) a2 = r; if (t == 3) a3 = r; if (t == 4) a4 = r; }
-    __device__ __forceinline__ v4d pick(int t) const { return t == 0 ? a0 : (t == 1 ? a1 : (t == 2 ? a2 : (t == 3 ? a3 : a4))); }
-};
-static_assert(DBL_TILES == 5, "DblTiles holds five tiles");
-
 __global__ __launch_bounds__(DBL_THREADS) void dbl_resident_kernel(RicGrid a, DblGrid d) {
     extern __shared__ double dl[];
     const int prob = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = lane & 15, lk = lane >> 4;
@@ -126,39 +105,15 @@ __global__ __launch_bounds__(DBL_THREADS) void dbl_resident_kernel(RicGrid a, Db
     double* Sd = d.Sd + (size_t)prob * mm;
     double* Ma = d.Ma + (size_t)prob * mm;
     double* Sa = d.Sa + (size_t)prob * mm;
-    const int t16 = (mx + 15) >> 4, ntile = t16 * t16, ng = mx >> 2;
+    const int t16 = (mx + 15) >> 4;
+    const ResShape rs = {mx, t16, t16 * t16, mx >> 2, wave, li, lk, DBL_WAVES};
 
     auto stage = [&](lds_double* X, const double* src) { for (int e = tid; e < mm; e += DBL_THREADS) X[e] = src[e]; };
-    // C = A' B, this wavefront's tiles, kept in registers (one copy of the tile's loop; the result goes to its register slot by selects)
-    auto mul = [&](lds_double* A, lds_double* B) {
-        const v4d zero4 = {0.0, 0.0, 0.0, 0.0};
-        DblTiles acc = {zero4, zero4, zero4, zero4, zero4};
-#pragma unroll 1
-        for (int t = 0; t < DBL_TILES && wave + DBL_WAVES * t < ntile; t++) {
-            const int tile = wave + DBL_WAVES * t;
-            const int i0 = (tile / t16) << 4, j0 = (tile % t16) << 4;
-            const int ic = (i0 + li < mx) ? i0 + li : mx - 1, jc = (j0 + li < mx) ? j0 + li : mx - 1;
-            const v4d r = wave_tile16_db(ng, A + lk * mx + ic, 4 * mx, B + lk * mx + jc, 4 * mx);
-            acc.put(t, r);
-        }
-        return acc;
-    };
-    // f(i, j, C[i][j]) on every element this lane holds
-    auto each = [&](const DblTiles& acc, auto f) {
-#pragma unroll 1
-        for (int t = 0; t < DBL_TILES && wave + DBL_WAVES * t < ntile; t++) {
-            const int tile = wave + DBL_WAVES * t;
-            const int i0 = (tile / t16) << 4, j = ((tile % t16) << 4) + li;
-            const v4d v = acc.pick(t);
-            if (j < mx) {
-#pragma unroll
-                for (int r = 0; r < 4; r++) { const int i = i0 + lk + 4 * r; if (i < mx) f(i, j, v[r]); }
-            }
-        }
-    };
+    auto mul = [&](lds_double* A, lds_double* B) { return res_mul(rs, A, B); };                  // C = A' B, this wavefront's tiles
+    auto each = [&](const ResTiles& acc, auto f) { res_each(rs, acc, f); };                      // f(i, j, C[i][j]) on every element this lane holds
     // the sandwich A' B A: X = (A' B)' stored over B by the lanes that hold it, then X' A.  B's buffer is overwritten
     auto mul3 = [&](lds_double* A, lds_double* B) {
-        DblTiles acc = mul(A, B);
+        ResTiles acc = mul(A, B);
         __syncthreads();      // every wavefront has read B: the buffer may take the transposed product
         each(acc, [&](int i, int j, double v) { B[j * mx + i] = v; });
         __syncthreads();
@@ -167,8 +122,9 @@ __global__ __launch_bounds__(DBL_THREADS) void dbl_resident_kernel(RicGrid a, Db
     auto transpose_u_to_v = [&]() {
         for (int e = tid; e < mm; e += DBL_THREADS) { const int i = e / mx, k = e - i * mx; V[k * mx + i] = U[e]; }
     };
-    // two sums of squares over the workgroup: per lane, per wavefront, then over the wavefronts in index order
-    auto total2 = [&](DblSq& x, DblSq& y) {
+    // two sums of squares over the workgroup: per lane, per wavefront, then over the wavefronts in index order (the eight-wavefront, two-pair sibling of
+    // sq_reduce / sq_wave_sum of cclqr_riccati_dev.h, which serve the 256-thread kernels: a new 256-thread kernel calls those)
+    auto total2 = [&](SqSum& x, SqSum& y) {
         for (int o = 32; o > 0; o >>= 1) {
             x.mid += __shfl_xor(x.mid, o, 64); x.big += __shfl_xor(x.big, o, 64);
             y.mid += __shfl_xor(y.mid, o, 64); y.big += __shfl_xor(y.big, o, 64);
@@ -198,7 +154,7 @@ __global__ __launch_bounds__(DBL_THREADS) void dbl_resident_kernel(RicGrid a, Db
                     stage(U, Ma);
                     stage(V, Sd);
                     __syncthreads();
-                    DblTiles acc = mul3(U, V);
+                    ResTiles acc = mul3(U, V);
                     each(acc, [&](int i, int j, double v) { Sa[(size_t)i * mx + j] += v; });
                     __syncthreads();      // every wavefront has read V
                     transpose_u_to_v();
@@ -215,8 +171,8 @@ __global__ __launch_bounds__(DBL_THREADS) void dbl_resident_kernel(RicGrid a, Db
         // S(2n) = S(n) + M(n)' S(n) M(n), M(2n) = M(n) M(n); U holds Md
         stage(V, Sd);
         __syncthreads();
-        DblTiles acc = mul3(U, V);
-        DblSq inc = {0.0, 0.0}, g = {0.0, 0.0};
+        ResTiles acc = mul3(U, V);
+        SqSum inc = {0.0, 0.0}, g = {0.0, 0.0};
         each(acc, [&](int i, int j, double v) { inc.add(v); Sd[(size_t)i * mx + j] += v; });
         __syncthreads();      // every wavefront has read V
         transpose_u_to_v();
@@ -239,12 +195,12 @@ __global__ __launch_bounds__(DBL_THREADS) void dbl_resident_kernel(RicGrid a, Db
     stage(V, ric_Q_of(a, prob));
     __syncthreads();
     if (!conv) {
-        DblSq g = {0.0, 0.0}, none = {0.0, 0.0};
+        SqSum g = {0.0, 0.0}, none = {0.0, 0.0};
         for (int e = tid; e < mm; e += DBL_THREADS) g.add(U[e]);
         total2(g, none);
         gn0 = g.norm();
     }
-    DblTiles acc = mul3(U, V);
+    ResTiles acc = mul3(U, V);
     double* Po = d.P_out + (size_t)prob * mm;
     each(acc, [&](int i, int j, double v) { Po[(size_t)i * mx + j] = Sn[(size_t)i * mx + j] + v; });
     if (tid == 0) {
@@ -260,7 +216,7 @@ __global__ __launch_bounds__(DBL_THREADS) void dbl_resident_kernel(RicGrid a, Db
 // that reads them, so nothing depends on scheduling.  A problem that has stopped (its flag is raised on the device, dbl_level_kernel) is skipped by the gated launches.
 struct DblOp {
     const double *A, *B, *E;       // E null: no addend
-    double *C, *part;              // part [nprob][tm * tm][2] (DblSq), or null
+    double *C, *part;              // part [nprob][tm * tm][2] (SqSum), or null
     long long sa, sb, se, sc;      // doubles between the matrices of consecutive problems (0: one shared by all)
     int ta;                        // 1: C = A' B, 0: C = A B
     int gate;                      // 1: a stopped problem is skipped
@@ -269,40 +225,10 @@ struct DblOp {
 __global__ __launch_bounds__(TILE_THREADS) void dbl_product_kernel(int mx, int tm, const int* stop, DblOp o) {
     __shared__ double red[4][1024];
     __shared__ double wsum[2][4];
-    const int prob = blockIdx.y, tid = threadIdx.x, lane = tid & 63, li = lane & 15;
+    const int prob = blockIdx.y;
     if (o.gate && stop[prob]) return;
-    const int i0 = (blockIdx.x / tm) << 5, j0 = (blockIdx.x % tm) << 5;
-    const double* A = o.A + (long long)prob * o.sa;
-    const double* B = o.B + (long long)prob * o.sb;
-    const double* E = o.E ? o.E + (long long)prob * o.se : nullptr;
-    double* Cm = o.C + (long long)prob * o.sc;
-    const bool iok[2] = {i0 + li < mx, i0 + 16 + li < mx}, jok[2] = {j0 + li < mx, j0 + 16 + li < mx};
-    const int ta = o.ta;
-    tile_mfma_splitk(mx,
-        [&](int kk, int h) { return iok[h] ? (ta ? A[(size_t)kk * mx + i0 + 16 * h + li] : A[(size_t)(i0 + 16 * h + li) * mx + kk]) : 0.0; },
-        [&](int kk, int h) { return jok[h] ? B[(size_t)kk * mx + j0 + 16 * h + li] : 0.0; }, red);
-    DblSq acc = {0.0, 0.0};
-    for (int e = tid; e < 1024; e += TILE_THREADS) {
-        const int ii = e >> 5, jj = e & 31, i = i0 + ii, j = j0 + jj;
-        if (i < mx && j < mx) {
-            const double v = ((red[0][e] + red[1][e]) + red[2][e]) + red[3][e];
-            acc.add(v);
-            Cm[(size_t)i * mx + j] = E ? E[(size_t)i * mx + j] + v : v;
-        }
-    }
-    if (!o.part) return;
-    for (int s = 32; s > 0; s >>= 1) { acc.mid += __shfl_xor(acc.mid, s, 64); acc.big += __shfl_xor(acc.big, s, 64); }
-    if (lane == 0) { wsum[0][tid >> 6] = acc.mid; wsum[1][tid >> 6] = acc.big; }
-    __syncthreads();
-    if (tid < 2) o.part[2 * ((size_t)prob * (tm * tm) + blockIdx.x) + tid] = ((wsum[tid][0] + wsum[tid][1]) + wsum[tid][2]) + wsum[tid][3];
-}
-
-// the norm from a problem's per-tile sums, added in index order per lane and then over the lanes: the same for every launch.  Valid in the first wavefront
-__device__ inline double dbl_tile_total(const double* part, int ntile) {
-    DblSq tot = {0.0, 0.0};
-    for (int t = threadIdx.x; t < ntile; t += 64) { tot.mid += part[2 * t]; tot.big += part[2 * t + 1]; }
-    for (int o = 32; o > 0; o >>= 1) { tot.mid += __shfl_xor(tot.mid, o, 64); tot.big += __shfl_xor(tot.big, o, 64); }
-    return tot.norm();
+    tile32_product_store(mx, tm, prob, o.A + (long long)prob * o.sa, o.ta, o.B + (long long)prob * o.sb, 0, o.E ? o.E + (long long)prob * o.se : nullptr, 0,
+                         o.C + (long long)prob * o.sc, o.part, red, wsum);
 }
 
 // after level `level` of the run to convergence: the level's two norms, Md = the level's M product (T2), and the stop tests, per problem on the device
@@ -313,7 +239,7 @@ __global__ __launch_bounds__(TILE_THREADS) void dbl_level_kernel(int mx, int tm,
     double* Md = d.Md + (size_t)prob * mx * mx;
     for (int e = tid; e < mx * mx; e += TILE_THREADS) Md[e] = src[e];
     if (tid < 64) {
-        const double inc = dbl_tile_total(partS + 2 * (size_t)prob * ntile, ntile), g = dbl_tile_total(partM + 2 * (size_t)prob * ntile, ntile);
+        const double inc = sq_tile_total(partS + 2 * (size_t)prob * ntile, ntile), g = sq_tile_total(partM + 2 * (size_t)prob * ntile, ntile);
         if (tid == 0) {
             d.levels[prob] = level;
             d.dnorm[2 * prob + 1] = d.dnorm[2 * prob]; d.dnorm[2 * prob] = inc;
@@ -330,13 +256,11 @@ __global__ __launch_bounds__(TILE_THREADS) void dbl_fixed_out_kernel(int mx, int
     __shared__ double wsum[2][4];
     const int prob = blockIdx.x, tid = threadIdx.x;
     const double* M = Ma + (size_t)prob * mx * mx;
-    DblSq g = {0.0, 0.0};
+    SqSum g = {0.0, 0.0};
     for (int e = tid; e < mx * mx; e += TILE_THREADS) g.add(M[e]);
-    for (int o = 32; o > 0; o >>= 1) { g.mid += __shfl_xor(g.mid, o, 64); g.big += __shfl_xor(g.big, o, 64); }
-    if ((tid & 63) == 0) { wsum[0][tid >> 6] = g.mid; wsum[1][tid >> 6] = g.big; }
-    __syncthreads();
+    sq_reduce(g, wsum);
     if (tid == 0) {
-        g.mid = ((wsum[0][0] + wsum[0][1]) + wsum[0][2]) + wsum[0][3]; g.big = ((wsum[1][0] + wsum[1][1]) + wsum[1][2]) + wsum[1][3];
+        g.mid = sq_wave_sum(wsum, 0); g.big = sq_wave_sum(wsum, 1);
         d.levels[prob] = top; d.reason[prob] = 0; d.gnorm[2 * prob] = g.norm();
     }
 }
@@ -347,19 +271,11 @@ size_t dbl_work_doubles(const RicArgs& r) {
     return 6 * np * mx * mx + 4 * np * tm * tm + 8;
 }
 
-// the two launch records of a call, from its arguments alone (dbl_ric_grid: the Riccati record, shared with covariance_doubling.hip): the pair (Md, Sd) a setup
-// kernel writes lies at dbl_Md / dbl_Sd (cclqr_internal.h)
-RicGrid dbl_ric_grid(const RicArgs& a) {
-    RicGrid g;
-    memset(&g, 0, sizeof(g));
-    (void)ric_lay_out(g, a, a.work);
-    g.A = a.A; g.Bu = a.Bu; g.Bl = a.Bl; g.G = a.G; g.Q = a.Q; g.R = a.R; g.q_stride = a.q_stride; g.r_stride = a.r_stride;
-    g.kbreak = a.kbreak; g.status = a.status; g.stop = a.stop;
-    return g;
-}
+// the two launch records of a call, from its arguments alone (ric_grid_of: the Riccati record): the pair (Md, Sd) a setup kernel writes lies at dbl_Md / dbl_Sd
+// (cclqr_internal.h)
 static void dbl_records(const DblArgs& p, RicGrid& g, DblGrid& d) {
     const RicArgs& a = p.r;
-    g = dbl_ric_grid(a);
+    g = ric_grid_of(a);
     const size_t np = a.nprob, mm = (size_t)a.mx * a.mx;
     d.Kin = p.Kin; d.k_stride = p.k_stride; d.N = a.N; d.max_levels = p.max_levels; d.tol = a.tol;
     d.levels = p.levels; d.reason = p.reason; d.dnorm = p.dnorm; d.gnorm = p.gnorm; d.P_out = a.P_out;
@@ -395,8 +311,7 @@ hipError_t launch_doubling_levels(const DblArgs& p, hipStream_t stream) {
     hipError_t e = hipSuccess;
     if (a.N == 1) return launch_lds<false>(dbl_no_step_kernel, dim3(a.nprob), dim3(TILE_THREADS), 0, stream, g, d);
     // resident wherever the stepping evaluation is (launch_policy: ric_chosen_path, a wavefront's share of the tiles within its registers, two operands within the LDS)
-    const int t16 = (a.mx + 15) / 16;
-    if (ric_chosen_path(a) == 1 && t16 * t16 <= DBL_TILES * DBL_WAVES && dbl_resident_lds_bytes(a.mx) <= 158 * 1024)
+    if (ric_chosen_path(a) == 1 && res_tiles_serve(a.mx, DBL_WAVES) && dbl_resident_lds_bytes(a.mx) <= 158 * 1024)
         return launch_lds(dbl_resident_kernel, dim3(a.nprob), dim3(DBL_THREADS), dbl_resident_lds_bytes(a.mx), stream, g, d);
 
     const long long sm = (long long)mm;

@@ -36,15 +36,6 @@ struct RdbGrid {
     double *dnorm, *anorm;     // [nprob][2] (preset to NaN by the launch)
 };
 
-// A Frobenius norm whose sum of squares must not overflow (policy_doubling.hip DblSq: two sums, an entry above 2^500 is squared after scaling by 2^-600)
-struct RdbSq {
-    double mid, big;
-    __device__ __forceinline__ void add(double v) {
-        if (fabs(v) > 0x1p500) { const double s = v * 0x1p-600; big += s * s; } else mid += v * v;
-    }
-    __device__ __forceinline__ double norm() const { return big > 0.0 ? sqrt(big + (mid * 0x1p-600) * 0x1p-600) * 0x1p600 : sqrt(mid); }
-};
-
 // S \ B in LDS by Gaussian elimination with partial pivoting (first row of largest magnitude): S [n][n], B [n][nc], both overwritten, B with the solution.  Called by
 // every thread of the workgroup; ends synchronised.  A zero pivot is divided by: the result is not finite and says so
 __device__ inline void rdb_small_solve(double* S, double* B, int n, int nc, int* ip) {
@@ -121,13 +112,13 @@ __global__ __launch_bounds__(TILE_THREADS) void rdb_setup_kernel(RicGrid a, RdbG
 }
 
 // =====================================================================================================================
-// One generic product, launched per product over the problems (the sibling of policy_doubling.hip's dbl_product_kernel, with a transposed B and an identity addend):
+// One generic product, launched per product over the problems (tile32_product_store of cclqr_riccati_dev.h, which dbl_product_kernel of policy_doubling.hip calls too):
 //   C = op(A) op(B) [+ E] [+ I],  32x32 tiles with masked edges, and per tile the sum of squares of op(A) op(B) (the increment of H, or A itself)
 // E may be C (the lane that owns an element reads and writes it); A and B may not.  Sums are taken per tile here and over the tiles in index order by the kernel
 // that reads them, so nothing depends on scheduling or on the batch.
 struct RdbOp {
     const double *A, *B, *E;       // E null: no addend
-    double *C, *part;              // part [nprob][tm * tm][2] (RdbSq), or null
+    double *C, *part;              // part [nprob][tm * tm][2] (SqSum), or null
     long long sb, se;              // doubles between the B / E of consecutive problems (0: one shared by all); A and C lie mx * mx apart
     int ta, tb;                    // 1: the operand is read transposed
     int eye;                       // 1: + I
@@ -136,34 +127,10 @@ struct RdbOp {
 __global__ __launch_bounds__(TILE_THREADS) void rdb_product_kernel(int mx, int tm, const int* stop, RdbOp o) {
     __shared__ double red[4][1024];
     __shared__ double wsum[2][4];
-    const int prob = blockIdx.y, tid = threadIdx.x, lane = tid & 63, li = lane & 15;
+    const int prob = blockIdx.y;
     if (stop && stop[prob]) return;
-    const int i0 = (blockIdx.x / tm) << 5, j0 = (blockIdx.x % tm) << 5;
-    const double* A = o.A + (size_t)prob * mx * mx;
-    const double* B = o.B + (long long)prob * o.sb;
-    const double* E = o.E ? o.E + (long long)prob * o.se : nullptr;
-    double* Cm = o.C + (size_t)prob * mx * mx;
-    const bool iok[2] = {i0 + li < mx, i0 + 16 + li < mx}, jok[2] = {j0 + li < mx, j0 + 16 + li < mx};
-    const int ta = o.ta, tb = o.tb;
-    tile_mfma_splitk(mx,
-        [&](int kk, int h) { return iok[h] ? (ta ? A[(size_t)kk * mx + i0 + 16 * h + li] : A[(size_t)(i0 + 16 * h + li) * mx + kk]) : 0.0; },
-        [&](int kk, int h) { return jok[h] ? (tb ? B[(size_t)(j0 + 16 * h + li) * mx + kk] : B[(size_t)kk * mx + j0 + 16 * h + li]) : 0.0; }, red);
-    RdbSq acc = {0.0, 0.0};
-    for (int e = tid; e < 1024; e += TILE_THREADS) {
-        const int ii = e >> 5, jj = e & 31, i = i0 + ii, j = j0 + jj;
-        if (i < mx && j < mx) {
-            const double v = ((red[0][e] + red[1][e]) + red[2][e]) + red[3][e];
-            acc.add(v);
-            double c = E ? E[(size_t)i * mx + j] + v : v;
-            if (o.eye && i == j) c += 1.0;
-            Cm[(size_t)i * mx + j] = c;
-        }
-    }
-    if (!o.part) return;
-    for (int s = 32; s > 0; s >>= 1) { acc.mid += __shfl_xor(acc.mid, s, 64); acc.big += __shfl_xor(acc.big, s, 64); }
-    if (lane == 0) { wsum[0][tid >> 6] = acc.mid; wsum[1][tid >> 6] = acc.big; }
-    __syncthreads();
-    if (tid < 2) o.part[2 * ((size_t)prob * (tm * tm) + blockIdx.x) + tid] = ((wsum[tid][0] + wsum[tid][1]) + wsum[tid][2]) + wsum[tid][3];
+    tile32_product_store(mx, tm, prob, o.A + (size_t)prob * mx * mx, o.ta, o.B + (long long)prob * o.sb, o.tb, o.E ? o.E + (long long)prob * o.se : nullptr, o.eye,
+                         o.C + (size_t)prob * mx * mx, o.part, red, wsum);
 }
 
 // =====================================================================================================================
@@ -273,14 +240,6 @@ __global__ __launch_bounds__(RDB_THREADS) void rdb_solve_kernel(int mx, int pw, 
     }
 }
 
-// the norm from a problem's per-tile sums, added in index order per lane and then over the lanes: the same for every launch.  Valid in the first wavefront
-__device__ inline double rdb_tile_total(const double* part, int ntile) {
-    RdbSq tot = {0.0, 0.0};
-    for (int t = threadIdx.x; t < ntile; t += 64) { tot.mid += part[2 * t]; tot.big += part[2 * t + 1]; }
-    for (int o = 32; o > 0; o >>= 1) { tot.mid += __shfl_xor(tot.mid, o, 64); tot.big += __shfl_xor(tot.big, o, 64); }
-    return tot.norm();
-}
-
 // after level `level` of the run to convergence: the level's two norms, Ad = the level's A product (T), and the stop tests, per problem on the device.  A problem
 // whose pivot failed in this level has been stopped by rdb_lu_kernel (reason 3) and keeps the level before
 __global__ __launch_bounds__(TILE_THREADS) void rdb_level_kernel(int mx, int tm, int level, RdbGrid d, int* stop, const double* partH, const double* partA, const double* T) {
@@ -292,7 +251,7 @@ __global__ __launch_bounds__(TILE_THREADS) void rdb_level_kernel(int mx, int tm,
     double* Ad = d.Ad + (size_t)prob * mx * mx;
     for (int e = tid; e < mx * mx; e += TILE_THREADS) Ad[e] = src[e];
     if (tid < 64) {
-        const double inc = rdb_tile_total(partH + 2 * (size_t)prob * ntile, ntile), an = rdb_tile_total(partA + 2 * (size_t)prob * ntile, ntile);
+        const double inc = sq_tile_total(partH + 2 * (size_t)prob * ntile, ntile), an = sq_tile_total(partA + 2 * (size_t)prob * ntile, ntile);
         if (tid == 0) {
             d.levels[prob] = level;
             d.dnorm[2 * prob + 1] = d.dnorm[2 * prob]; d.dnorm[2 * prob] = inc;
@@ -310,13 +269,11 @@ __global__ __launch_bounds__(TILE_THREADS) void rdb_fixed_out_kernel(int mx, int
     __shared__ double wsum[2][4];
     const int prob = blockIdx.x, tid = threadIdx.x;
     const double* M = Aa + (size_t)prob * mx * mx;
-    RdbSq g = {0.0, 0.0};
+    SqSum g = {0.0, 0.0};
     for (int e = tid; e < mx * mx; e += TILE_THREADS) g.add(M[e]);
-    for (int o = 32; o > 0; o >>= 1) { g.mid += __shfl_xor(g.mid, o, 64); g.big += __shfl_xor(g.big, o, 64); }
-    if ((tid & 63) == 0) { wsum[0][tid >> 6] = g.mid; wsum[1][tid >> 6] = g.big; }
-    __syncthreads();
+    sq_reduce(g, wsum);
     if (tid == 0) {
-        g.mid = ((wsum[0][0] + wsum[0][1]) + wsum[0][2]) + wsum[0][3]; g.big = ((wsum[1][0] + wsum[1][1]) + wsum[1][2]) + wsum[1][3];
+        g.mid = sq_wave_sum(wsum, 0); g.big = sq_wave_sum(wsum, 1);
         d.levels[prob] = top;
         if (d.reason[prob] == 0) d.anorm[2 * prob] = g.norm();
     }
@@ -373,9 +330,7 @@ __global__ __launch_bounds__(TILE_THREADS) void rdb_gain_kernel(RicGrid a, const
         if (!want_p) return;
         for (int e = tid; e < mu * mx; e += TILE_THREADS) {      // W1 = R Ku
             const int c = e / mx, j = e - c * mx;
-            double s = 0.0;
-            for (int f = 0; f < mu; f++) s += Rp[c * mu + f] * B[f * mx + j];
-            W1[e] = s;
+            W1[e] = ric_rk_entry(Rp, mx, mu, c, j, B);
         }
         __syncthreads();
     }
@@ -383,9 +338,9 @@ __global__ __launch_bounds__(TILE_THREADS) void rdb_gain_kernel(RicGrid a, const
     const double* Qp = ric_Q_of(a, prob);
     for (int e = tid; e < mx * mx; e += TILE_THREADS) {
         const int i = e / mx, j = e - i * mx;
-        double s = AD[(size_t)i * na + j], q = Qp[e];
-        for (int c = 0; c < mu; c++) { s -= AD[(size_t)i * na + mx + c] * B[c * mx + j]; q += B[c * mx + i] * W1[c * mx + j]; }
-        Ab[e] = s;
+        Ab[e] = ric_abar_entry(AD, na, mx, mu, i, j, B);
+        double q = Qp[e];
+        for (int c = 0; c < mu; c++) q += B[c * mx + i] * W1[c * mx + j];
         Ep[e] = q;
     }
 }
@@ -401,11 +356,8 @@ hipError_t launch_riccati_doubling(const RdbArgs& p, hipStream_t stream) {
     const RicArgs& a = p.r;
     if (a.nprob <= 0) return hipSuccess;
     if (a.N == 1 || a.N < 0) return hipErrorInvalidValue;
-    RicGrid g;
-    memset(&g, 0, sizeof(g));
-    (void)ric_lay_out(g, a, a.work);
-    g.A = a.A; g.Bu = a.Bu; g.Bl = a.Bl; g.G = a.G; g.Q = a.Q; g.R = a.R; g.q_stride = a.q_stride; g.r_stride = a.r_stride;
-    g.K = a.K; g.kpad = a.kpad; g.keep_last = 1; g.kbreak = a.kbreak; g.status = a.status; g.stop = a.stop;
+    RicGrid g = ric_grid_of(a);
+    g.K = a.K; g.kpad = a.kpad; g.keep_last = 1;
     const size_t np = a.nprob, mx = a.mx, mm = mx * mx, mu = a.mu;
     const int tm = g.tm;
     const bool lm = a.mx <= RDB_LDS_MX;

@@ -88,6 +88,23 @@ def test_the_fit_rule_is_the_one_the_tests_mirror():
     assert [tc.paths_of(n) for n in tc.NAMES] == [(1, 2)] * 6 + [(2,)] * 2
 
 
+def test_the_shared_blocks_are_defined_once():
+    """across csrc/ the five-slot tile struct, the (mid, big) sum of squares and its per-tile total are each defined exactly once, and tile_mfma_splitk is called
+    from riccati.hip and from the shared header only: the order of every sum the bitwise tests rest on is written in one place"""
+    csrc = os.path.join(ROOT, "constrainedcontrol.jl_amd", "csrc")
+    code = {}
+    for f in sorted(os.listdir(csrc)):
+        if f.endswith((".hip", ".h")):
+            code[f] = "\n".join(l.split("//")[0] for l in open(os.path.join(csrc, f)).read().splitlines())      # without comments
+    count = lambda pat: {f: len(re.findall(pat, s)) for f, s in code.items() if re.search(pat, s)}
+    assert count(r"void put\(int t, v4d r\)") == {"cclqr_riccati_dev.h": 1}
+    assert count(r"struct \w+ \{\s*double mid, big;") == {"cclqr_riccati_dev.h": 1}
+    assert count(r"v \* 0x1p-600") == {"cclqr_riccati_dev.h": 1}
+    assert count(r"double \w*tile_total\(const double\* part, int ntile\)") == {"cclqr_riccati_dev.h": 1}
+    assert set(count(r"\+= part\[2 \* t\]")) == {"cclqr_riccati_dev.h"}
+    assert set(count(r"\btile_mfma_splitk\(")) == {"cclqr_riccati_dev.h", "riccati.hip"}
+
+
 def test_the_workspace_plan_is_new_arithmetic_next_to_the_tracking_one():
     hdr = open(os.path.join(ROOT, "constrainedcontrol.jl_amd", "csrc", "cclqr_internal.h")).read()
     assert "inline long long tracking_cov_problem_bytes(int mx, int mu, int ml, int N, long long ric_doubles)" in hdr
