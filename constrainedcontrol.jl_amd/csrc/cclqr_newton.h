@@ -86,8 +86,9 @@ __device__ __forceinline__ double group_sum(double v) {
     v += dpp_row_ror<2>(v);
     v += dpp_row_ror<1>(v);
     // rows 0+1 and 2+3 through the LDS crossbar (ds_bpermute).  gfx950's v_permlane16_swap does the same exchange in the vector
-    // ALU, but its two result pairs cost the 17-link instantiations 4 vector registers they do not have (VGPR spills; round 2,
-    // 6ef5c0b) for no measured gain
+    // ALU: the 32-lane chain kernels that split the Schur rows take that form for every group sum (rollout_chain.hip group_sum_rows32;
+    // rounds 17 and 23 measured the gain that round 2, 6ef5c0b, did not find).  This form stays for the kernels those rounds left
+    // alone (32-link image, tree kernel, closed loops)
     if (G == 32) v += __shfl_xor(v, 16, 64);
     if (G == 64) {
         int lo = __double2loint(v), hi = __double2hiint(v);

@@ -72,8 +72,9 @@ struct GainRows {
 };
 // adds to uj the joint input of the lane whose link number is tc (-2: none) under the record C; Kp = the lane's first entry of the step's first gain
 // row, Fp = the step's feed-forward row (null: none), dzv = the lane's NE entries of the control error.  Same products, same order of summation
-// as one input at a time.
-template <int G, int NBP, int EXTRA>
+// as one input at a time.  SUM::of: the sum over the lanes of a group (a kernel may bring its own form of group_sum<G>: same addends, same bits).
+template <int G> struct GroupSum { static __device__ __forceinline__ double of(double v) { return group_sum<G>(v); } };
+template <int G, int NBP, int EXTRA, class SUM = GroupSum<G>>
 __device__ __forceinline__ void feedback_inputs(CtrlHotK C, GlobalD Kp, GlobalD Fp, int mu, int ne, const double* dzv, double unoise, int tc, double& uj) {
     constexpr int NE = GainRows<G, NBP>::NE, CH = GainRows<G, NBP>::CH;
     if (C->K) {                                  // (uniform) LQR / TrackingLQR
@@ -92,7 +93,7 @@ __device__ __forceinline__ void feedback_inputs(CtrlHotK C, GlobalD Kp, GlobalD 
                 double part = 0.0;
 #pragma unroll
                 for (int q = 0; q < NE; q++) part += rows.kv[j][q] * dzv[q];
-                const double s = group_sum<G>(part);
+                const double s = SUM::of(part);
                 double u = rows.fd[j] - s;
                 if (EXTRA) u += unoise;
                 if (tc == cjv[j]) uj += u;

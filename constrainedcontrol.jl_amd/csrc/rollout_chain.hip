@@ -109,6 +109,31 @@ __device__ __forceinline__ double group_sum_rows32(double v) {
     const auto hi = swap_rows_b32((unsigned)__double2hiint(v), (unsigned)__double2hiint(v));
     return __hiloint2double((int)hi[0], (int)lo[0]) + __hiloint2double((int)hi[1], (int)lo[1]);
 }
+// (as the SUM of feedback_inputs, cclqr_rollout_step.h: the control law's one sum per input and step)
+struct GroupSumRows32 { static __device__ __forceinline__ double of(double v) { return group_sum_rows32(v); } };
+// ---- the two 32-lane halves of the wavefront exchange values the same way: v_permlane32_swap_b32 exchanges lanes 32-63 of its first operand with
+// lanes 0-31 of its second.  With both operands copies of one value, the first result holds the own value on lanes 0-31 and the lower half's on lanes
+// 32-63, the second result the upper half's on lanes 0-31 and the own on lanes 32-63.  Called by ALL lanes in wavefront-uniform control flow.
+__device__ __forceinline__ auto swap_halves_b32(unsigned first, unsigned second) { return __builtin_amdgcn_permlane32_swap(first, second, false, false); }
+// N doubles at a time: out[i] is the first result of v[i]'s swap on the lanes with `first`, the second on the others (v itself is left alone: a swap
+// overwrites both its operands).  The two copies that a swap consumes are made ahead of the swaps, as in from_row_below, and the second FROM THE FIRST:
+// the iterate lives in accumulation registers, and two reads of it per dword instead of a read and a 64-bit move were 76 instructions more in the
+// 17-link kernel and a second value for the allocator to park after its first pass.
+template <int N>
+__device__ __forceinline__ void halves_pick(const double* v, double* out, bool first) {
+    double ca[N], cb[N];
+#pragma unroll
+    for (int i = 0; i < N; i++) {
+        ca[i] = v[i]; asm volatile("" : "+v"(ca[i]));
+        cb[i] = ca[i]; asm volatile("" : "+v"(cb[i]));
+    }
+#pragma unroll
+    for (int i = 0; i < N; i++) {
+        const auto a = swap_halves_b32((unsigned)__double2loint(ca[i]), (unsigned)__double2loint(cb[i]));
+        const auto b = swap_halves_b32((unsigned)__double2hiint(ca[i]), (unsigned)__double2hiint(cb[i]));
+        out[i] = __hiloint2double((int)(first ? b[0] : b[1]), (int)(first ? a[0] : a[1]));
+    }
+}
 // which kernels split the rows, and whether link 0 is without a helper (17 links: lane 16 owns the leaf)
 template <int G, int NBP, int KL> struct SchurSplit { static const bool ON = G == 32 && NBP <= 17 && KL == 1, R0 = NBP == 17; };
 // once per launch: the helper lanes' flags and scale (schur_split_helper).  M->childl is read at an index below 16.
@@ -249,7 +274,8 @@ __device__ __forceinline__ double chain_eval(LinkC& c, LinkS& S, int t, const La
 }
 
 // line search of the 32-lane instantiations (cclqr_rollout_step.h TrialIn): ||f|| of the owning group at the trial points s - a ds (constraint forces C - a cd) for a = a1 and a = a2; Lc = LDS image of the instance
-template <int G, int KL = 1>
+// SP != 0 (the kernels that split the Schur rows): the two sums combine their rows by the swap (group_sum_rows32) -- the accept sequence waits for them
+template <int G, int KL = 1, int SP = 0>
 __device__ __forceinline__ void chain_eval2(LinkC& c, const TrialIn& T, const double* Lc, int t, const Lay& Y, double a1, double a2, bool active, double dt,
                                             double& n1, double& n2) {
     double part1 = 0.0, part2 = 0.0, xq1[7], xq2[7];
@@ -283,8 +309,14 @@ __device__ __forceinline__ void chain_eval2(LinkC& c, const TrialIn& T, const do
         for (int i = 0; i < 5; i++) { part1 += g1[i] * g1[i]; part2 += g2[i] * g2[i]; }
     }
     if (KL > 1 && !c.prim()) { part1 = 0.0; part2 = 0.0; }      // (several lanes per link: every lane of a link has evaluated the same residual, one counts)
-    n1 = sqrt(group_sum<G>(part1));
-    n2 = sqrt(group_sum<G>(part2));
+    if constexpr (SP != 0) {
+        static_assert(G == 32, "the rows are split in 32-lane groups");
+        n1 = sqrt(group_sum_rows32(part1));
+        n2 = sqrt(group_sum_rows32(part2));
+    } else {
+        n1 = sqrt(group_sum<G>(part1));
+        n2 = sqrt(group_sum<G>(part2));
+    }
 }
 
 // ---- line search of the 8- and 16-lane instantiations (eight / four instances per wavefront): a wavefront pays the LONGEST of its instances'
@@ -518,7 +550,7 @@ __global__ __launch_bounds__(WAVE_BLOCK) void rollout_chain_kernel(RolloutArgs a
             asm volatile("" : "+v"(tf));            // the entries' range tests are made here, every step -- not once per launch and kept as NE lane masks
 #pragma unroll
             for (int q = 0; q < NE; q++) { const int e = tf + q * G; dzv[q] = (c.valid() && e < ne) ? L[Y.DZ + e] : 0.0; }
-            feedback_inputs<G, NBP, EXTRA>(C, Kp, Fp, mu, ne, dzv, unoise, tc, uj);
+            feedback_inputs<G, NBP, EXTRA, std::conditional_t<SP != 0, GroupSumRows32, GroupSum<G>>>(C, Kp, Fp, mu, ne, dzv, unoise, tc, uj);
         }
         STAMP(PF_CONTROL);
         asm volatile("" : "+v"(grav));      // the last of the step's loads is waited for HERE, in front of the stores (behind them the wait would be for the stores too)
@@ -691,7 +723,8 @@ __global__ __launch_bounds__(WAVE_BLOCK) void rollout_chain_kernel(RolloutArgs a
                     for (int i = 0; i < 5; i++) pdn += dl[i] * dl[i];
                     if (KL > 1 && !c.prim()) pdn = 0.0;
                 }
-                nd = sqrt(group_sum<G>(pdn));
+                if constexpr (SP != 0) nd = sqrt(group_sum_rows32(pdn));      // (the trial's row verdict and the accept phase wait for it: no LDS round trip)
+                else nd = sqrt(group_sum<G>(pdn));
             }
             WAVE_HANDOVER();
             STAMP(PF_BODY_SOLVE);
@@ -719,7 +752,13 @@ __global__ __launch_bounds__(WAVE_BLOCK) void rollout_chain_kernel(RolloutArgs a
                 for (int lv = 1; lv <= LINE_MAXIT;) {
                     if (!__any(!ls_done)) break;
                     const bool mine = !ls_done;                                   // uniform over the group
-                    const bool other = __shfl_xor(mine ? 1 : 0, 32, 64) != 0;     // the wavefront's other instance is searching too
+                    bool other;                                                   // the wavefront's other instance is searching too
+                    if constexpr (SP != 0) {      // one vote, the other half's bits of it (`mine` is uniform over a half): scalar, no LDS round trip
+                        const unsigned long long searching = __ballot(mine);
+                        other = (unsigned)(grp != 0 ? searching : searching >> 32) != 0u;
+                    } else {
+                        other = __shfl_xor(mine ? 1 : 0, 32, 64) != 0;
+                    }
                     // per-instance plants: a group holds the constants of its own instance's plant only, so it evaluates no trial of the other instance --
                     // nobody helps, and a searcher advances its own two levels per pass.  Read from the kernel arguments here, not kept through the launch
                     const bool solo = ap->plants != nullptr;
@@ -730,20 +769,38 @@ __global__ __launch_bounds__(WAVE_BLOCK) void rollout_chain_kernel(RolloutArgs a
 #pragma unroll
                     for (int i = 0; i < 6; i++) { T.s[i] = S.s[i]; T.ds[i] = S.ds[i]; T.cd[i] = S.cd[i]; }
                     if (mine != other) {       // (symmetric in the two groups: a wavefront-uniform branch) one searches, one helps: hand the trial over
+                        if constexpr (SP != 0) {
+                            // by half swaps: of a swap's two results the first is the own value on the lower half and the lower half's on the upper, so a
+                            // helper of the upper half and a lane of the lower half that keeps its own (the searcher; everybody when solo) take the first
+                            const bool first = (grp != 0) == helping;
+                            halves_pick<7>(S.z, T.z, first);
+                            halves_pick<6>(S.s, T.s, first);
+                            halves_pick<6>(S.ds, T.ds, first);
+                            halves_pick<6>(S.cd, T.cd, first);
+                        } else {
 #pragma unroll
-                        for (int i = 0; i < 7; i++) { const double o = other_half(S.z[i]); T.z[i] = helping ? o : T.z[i]; }
+                            for (int i = 0; i < 7; i++) { const double o = other_half(S.z[i]); T.z[i] = helping ? o : T.z[i]; }
 #pragma unroll
-                        for (int i = 0; i < 6; i++) {
-                            const double o1 = other_half(S.s[i]), o2 = other_half(S.ds[i]), o3 = other_half(S.cd[i]);
-                            T.s[i] = helping ? o1 : T.s[i]; T.ds[i] = helping ? o2 : T.ds[i]; T.cd[i] = helping ? o3 : T.cd[i];
+                            for (int i = 0; i < 6; i++) {
+                                const double o1 = other_half(S.s[i]), o2 = other_half(S.ds[i]), o3 = other_half(S.cd[i]);
+                                T.s[i] = helping ? o1 : T.s[i]; T.ds[i] = helping ? o2 : T.ds[i]; T.cd[i] = helping ? o3 : T.cd[i];
+                            }
                         }
                     }
                     const double* Lc = helping ? lds + (1 - grp) * Y.total : L;
                     const int l0 = helping ? lv + 2 : lv;
                     double n1, n2;
-                    chain_eval2<G, KL>(c, T, Lc, tl, Y, ldexp(1.0, -l0), ldexp(1.0, -(l0 + 1)), c.on() && (mine || helping) && l0 <= LINE_MAXIT, dt, n1, n2);
+                    chain_eval2<G, KL, SP>(c, T, Lc, tl, Y, ldexp(1.0, -l0), ldexp(1.0, -(l0 + 1)), c.on() && (mine || helping) && l0 <= LINE_MAXIT, dt, n1, n2);
                     PCOUNT(PF_EVALS);
-                    const double h1 = other_half(n1), h2 = other_half(n2);
+                    double h1, h2;                                                // the other half's two norms
+                    if constexpr (SP != 0) {
+                        const double own[2] = {n1, n2};
+                        double oth[2];
+                        halves_pick<2>(own, oth, grp != 0);                       // (the lower half's value is the first result on the upper half)
+                        h1 = oth[0]; h2 = oth[1];
+                    } else {
+                        h1 = other_half(n1); h2 = other_half(n2);
+                    }
                     if (mine) {
                         const double cand[4] = {n1, n2, h1, h2};
 #pragma unroll
