@@ -27,6 +27,7 @@ EXPORTS = ["cclqr_last_error", "cclqr_version", "cclqr_device_count", "cclqr_set
 ABI_VERSION = 202     # include/cclqr.h CCLQR_ABI_VERSION: the structs below mirror that header (verified field by field against cclqr_abi_layout at load time)
 ROLLOUT_NO_ALLOC = 1  # cclqr_rollout_opts.flags: the call may neither allocate nor synchronise (a hipGraph capture is open on the device)
 ROLLOUT_CARRY_STATUS = 4  # ... `status` is read and written: an instance lost in an earlier launch stays frozen, the others merge this launch's result into it
+ROLLOUT_RUNTIME_PLAN = 16  # ... a single 16- / 17-link chain runs on the general chain kernel (plan of the solve read at run time) instead of its fixed-plan kernel: same bits
 ROLLOUT_PACK_WAVEFRONTS = 2  # ... every wavefront of a chain launch full, whatever the batch size (many launches sharing the device at once)
 PHILOX_INKERNEL_STEPS = 8
 SCORE_LEN = 4           # CCLQR_SCORE_LEN: Jx, Ju, peak, last_out per instance (cclqr_rollout_score)

@@ -707,7 +707,7 @@ static int rollout_check_args(const cclqr_mech* m, const cclqr_ctrl* c, int64_t 
     // one (integrated, last) pair per joint; never looked at for a controller without a PID law
     if (opts && c->host.has_pid && opts->pid_state_dev && opts->pid_state_len != n_inst * (int64_t)m->shape.pid_slots * 2)
         return fail(CCLQR_EINVAL, "pid_state_len must be n_inst * nb * 2 (closed loops: n_inst * joints * 2)");
-    if (opts && (opts->flags & ~(CCLQR_ROLLOUT_NO_ALLOC | CCLQR_ROLLOUT_PACK_WAVEFRONTS | CCLQR_ROLLOUT_CARRY_STATUS))) return fail(CCLQR_EINVAL, "unknown bit in cclqr_rollout_opts.flags");
+    if (opts && (opts->flags & ~(CCLQR_ROLLOUT_NO_ALLOC | CCLQR_ROLLOUT_PACK_WAVEFRONTS | CCLQR_ROLLOUT_CARRY_STATUS | CCLQR_ROLLOUT_RUNTIME_PLAN))) return fail(CCLQR_EINVAL, "unknown bit in cclqr_rollout_opts.flags");
     if (opts && (opts->flags & CCLQR_ROLLOUT_CARRY_STATUS) && !status) return fail(CCLQR_EINVAL, "CCLQR_ROLLOUT_CARRY_STATUS needs the status array (it is read and written)");
     return CCLQR_OK;
 }
@@ -787,7 +787,7 @@ extern "C" int cclqr_rollout_plants(const cclqr_mech* m, const cclqr_plants* pla
     if (newton_mode != 0 && law != ControlLaw::Lqr)
         return fail(CCLQR_EUNSUPPORTED, "newton_mode 1 exists under the plain LQR / TrackingLQR law only on chains and branching trees (closed-loop mechanisms: every law)");
     if (m->shape.family == RolloutFamily::Tree) HIPCHK(launch_rollout_treereg(a, m->shape, m->simds, law, newton_mode, (hipStream_t)stream));
-    else HIPCHK(launch_rollout_chain(a, m->shape, m->simds, law, newton_mode, (hipStream_t)stream));
+    else HIPCHK(launch_rollout_chain(a, m->shape, m->simds, law, newton_mode, opts && (opts->flags & CCLQR_ROLLOUT_RUNTIME_PLAN), (hipStream_t)stream));
     return CCLQR_OK;
 }
 

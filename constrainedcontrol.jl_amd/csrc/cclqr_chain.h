@@ -1170,6 +1170,15 @@ HD int chain_plan_pack(int nchains, int start, int len) { return (nchains << 16)
 HD int chain_plan_count(int w) { return (w >> 16) & 0xff; }
 HD int chain_plan_start(int w) { return w & 0xff; }
 HD int chain_plan_len(int w) { return (w >> 8) & 0xff; }
+// ---- the chain of a mechanism that is ONE chain from link 0 over all its NBP links (the N-link cartpole: RolloutShape::fixed_plan), as constants: what the
+// fixed-plan kernels (the kernel text of rollout_chain.hip compiled with CHAIN_PLAN_FIXED) put where rollout_chain_kernel reads the plan word.  They feed the SAME tri_plan_balanced /
+// cr_setup / tri_cursor / ck_tri_back / cr_back, and the compiler folds the plan away.  constexpr MEMBERS, not a function that returns them through references:
+// the helpers are inlined after the interprocedural passes, which compile them for what ALL their callers pass -- an argument they cannot see through at one
+// call site changes the code of every kernel of the file.
+template <int NBP>
+struct PlanFixed { static constexpr int nchains = 1, cs = 0, cn = NBP; };
+// the mechanisms PlanFixed<NBP> is instantiated for (rollout_chain.hip): the 32-lane kernels that take the reduction level
+inline bool chain_plan_is_fixed(int nb, int nchains, int start0, int len0) { return (nb == 16 || nb == 17) && nchains == 1 && start0 == 0 && len0 == nb; }
 
 // ---- which instantiation of rollout_chain_kernel a chain of nb links runs on (host side: RolloutShape, cclqr_tables.h rollout_shape_of)
 // 8 lanes per instance up to 4 links (one elimination front of 6 lanes; eight instances per wavefront: the cartpole and triple-cartpole

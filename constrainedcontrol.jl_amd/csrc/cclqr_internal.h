@@ -69,6 +69,8 @@ struct RolloutShape {
     int full;          // instances per full wavefront: 64 / G (loops: 1)
     int NCB;           // loops: column blocks of eight the instantiation holds (loop_col_blocks), else 0
     int pid_slots;     // (integrated, last) PID pairs per instance: one per joint
+    int fixed_plan;    // chains: ONE chain from link 0 over all NBP = nb links, 16 or 17 of them (the N-link cartpole): the kernels with the solve plan compiled in
+                       // (rollout_chain.hip rollout_chain_fixed_kernel, cclqr_chain.h PlanFixed); 0 = the plan is read at run time
     size_t lds;        // dynamic LDS per workgroup of the rollout kernel, `full` instances
     size_t lin_lds;    // dynamic LDS per workgroup (one knot) of the mechanism's linearisation kernel
 };
@@ -118,7 +120,10 @@ inline int spread_instances_per_wavefront(int full, int64_t n_inst, int steps, b
 hipError_t launch_philox_fill(double* out, unsigned key0, long long inst0, long long n_inst, int k0, int steps, hipStream_t stream);
 // the three rollout launchers: forests of chains (rollout_chain.hip), branching trees (rollout_treereg.hip; a.M must point at the device image
 // [MechDev | TreeRegDev], treereg_of) and closed-loop mechanisms (rollout_loop.hip: every law at run time).  s = the mechanism's shape
-hipError_t launch_rollout_chain(const RolloutArgs& a, const RolloutShape& s, int simds, ControlLaw law, int newton_mode, hipStream_t stream);
+// which kernel family launch_rollout_chain takes: the fixed-plan kernels for a shape that has them, unless the caller asked for the general kernel
+// (runtime_plan: CCLQR_ROLLOUT_RUNTIME_PLAN).  Stated here, not inside the launcher, so that the CPU suite can ask it (tests/emu/emu_chain_fixed_plan.cpp)
+inline bool chain_launch_fixed_plan(const RolloutShape& s, bool runtime_plan) { return s.family == RolloutFamily::Chain && s.fixed_plan != 0 && !runtime_plan; }
+hipError_t launch_rollout_chain(const RolloutArgs& a, const RolloutShape& s, int simds, ControlLaw law, int newton_mode, bool runtime_plan, hipStream_t stream);
 hipError_t launch_rollout_treereg(const RolloutArgs& a, const RolloutShape& s, int simds, ControlLaw law, int newton_mode, hipStream_t stream);
 hipError_t launch_rollout_loop(const RolloutArgs& a, const RolloutShape& s, int newton_mode, hipStream_t stream);
 

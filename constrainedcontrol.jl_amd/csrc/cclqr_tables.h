@@ -30,6 +30,7 @@ static inline RolloutShape rollout_shape_of(const MechDev& H, int nb, int nj) {
         s.family = RolloutFamily::Chain;
         s.G = chain_lanes_per_instance(nb); s.NBP = chain_layout_links(nb); s.KL = chain_lanes_per_link(nb); s.NL = chain_links_per_group(nb); s.pid_slots = nb;
         s.lds = chain_lds_bytes(nb); s.lin_lds = linearize_lds_bytes(nb, H.tree, H.npairs);
+        s.fixed_plan = chain_plan_is_fixed(nb, H.nchains, H.chain_start[0], H.chain_len[0]) ? 1 : 0;
     }
     s.full = 64 / s.G;
     return s;

@@ -6,6 +6,7 @@
 //
 // Replaces: ConstrainedDynamics.simulate!/newton! as driven by the reference (examples/lqr_cartpole.jl:44) with
 //           control_lqr! (src/control/lqr.jl:89-139) / control_trackinglqr! (src/control/lqr_tracking.jl:46-71).
+#ifndef CHAIN_KERNEL_TEXT       // (everything but the kernel's text: see the inclusions below)
 #include "cclqr_chain.h"
 #include "cclqr_internal.h"
 #include "cclqr_newton.h"
@@ -390,8 +391,36 @@ hipError_t launch_philox_fill(double* out, unsigned key0, long long inst0, long 
 // moves them across the line (a scalar mode flag read in the accept phase cost the 17-link instantiations 2 VGPR spills).
 // KL, NL: several lanes per link (cclqr_chain.h "SEVERAL LANES PER LINK"): lane t of a group is sub-lane w = t / NL of link tl = t % NL; a mechanism of at most NL
 // links whose lane group has KL NL <= G lanes.  KL = 1 (NL = G): one lane per link, the kernels of rounds 2-4, bit for bit.
+// ---- The kernel's text follows ONCE in this file and is compiled TWICE: the file includes itself with CHAIN_KERNEL_TEXT defined, which selects the text alone.
+// CHAIN_PLAN_FIXED 0: rollout_chain_kernel<G, NBP, EXTRA, RELAX, KL, NL> -- any forest of chains, the plan of the solve read from the plan word on every Newton
+// iteration.  CHAIN_PLAN_FIXED 1: rollout_chain_fixed_kernel<NBP, EXTRA, RELAX> (G = 32, KL = 1, NL = 32) -- the mechanisms that are ONE chain over all NBP
+// links from link 0 (NBP = 16, 17: RolloutShape::fixed_plan, the N-link cartpole), the chain a constant of the kernel (PlanFixed<NBP>, cclqr_chain.h) instead of
+// ~200 scalar selects and lane reads per iteration.  One text, the same functions on the same operands in the same order: the same bits, with the plan's selects
+// folded by the compiler.  Two inclusions and the preprocessor -- not one __device__ body with a policy parameter that both kernels call -- because the existing
+// kernels' code is pinned (tests/test_chain_*_isa.py): handing the kernel arguments to a function, or restating the lines that read the plan word, moved the
+// code of every instantiation.  With CHAIN_PLAN_FIXED 0 the text is what it was.  And in THIS file, not in a file of its own: the source-level rules
+// (tests/test_static_kernel_rules.py) and the benchmark's source fingerprint read rollout_chain.hip.
+#define CHAIN_KERNEL_TEXT
+#define CHAIN_PLAN_FIXED 0
+#include "rollout_chain.hip"
+#undef CHAIN_PLAN_FIXED
+#define CHAIN_PLAN_FIXED 1
+#include "rollout_chain.hip"
+#undef CHAIN_PLAN_FIXED
+#undef CHAIN_KERNEL_TEXT
+#else       // CHAIN_KERNEL_TEXT: the kernel's text, for the two inclusions above
+#if CHAIN_PLAN_FIXED
+template <int NBP, int EXTRA, bool RELAX = false>
+__global__ __launch_bounds__(WAVE_BLOCK) void rollout_chain_fixed_kernel(RolloutArgs a)
+#else
 template <int G, int NBP, int EXTRA, bool RELAX = false, int KL = 1, int NL = G>
-__global__ __launch_bounds__(WAVE_BLOCK) void rollout_chain_kernel(RolloutArgs a) {
+__global__ __launch_bounds__(WAVE_BLOCK) void rollout_chain_kernel(RolloutArgs a)
+#endif
+{
+#if CHAIN_PLAN_FIXED
+    constexpr int G = 32, KL = 1, NL = 32;
+    typedef PlanFixed<NBP> PLAN;
+#endif
     extern __shared__ double lds[];
     static_assert(WAVE_BLOCK == 64, "WAVE_HANDOVER orders the phases of ONE wavefront: the workgroup is exactly 64 threads");
     static_assert(KL >= 1 && KL <= 3 && KL * NL <= G && (KL > 1 || NL == G) && (KL == 1 || NL <= NBP), "lane group too small for KL lanes per link");
@@ -428,12 +457,17 @@ __global__ __launch_bounds__(WAVE_BLOCK) void rollout_chain_kernel(RolloutArgs a
     // (chain_plan_pack, cclqr_chain.h), and the Newton loop reads them with v_readlane instead of going to M->chain_start / M->chain_len (two
     // dependent memory round trips per iteration).  No scalar register holds any of it, and no new vector register: the word shares the register
     // of the lane's user body index (bits 24-29), which the launch keeps anyway.
+    // (PlanFixed: the word carries the user body index alone -- nobody reads the chains from it)
     int plan;
+#if CHAIN_PLAN_FIXED
+    plan = ut << 24;
+#else
     {
         const int nch = M->nchains;
         const int cs = M->chain_start[lane], cn = M->chain_len[lane];      // (64 lanes, CCLQR_MAXL = 64 entries: every lane's read is inside the table)
         plan = chain_plan_pack(nch, lane < nch ? cs : 0, lane < nch ? cn : 0) | (ut << 24);
     }
+#endif
 
     LinkS S;
     double pid_int = 0.0, pid_last = 0.0;
@@ -609,8 +643,12 @@ __global__ __launch_bounds__(WAVE_BLOCK) void rollout_chain_kernel(RolloutArgs a
         bool done = !go, failed = false;
         int its = 0;
         double normf0 = 0.0;
+#if CHAIN_PLAN_FIXED
+        constexpr int nchains = PLAN::nchains;
+#else
         LANE_INT_FRESH(plan);      // (read here, every step: not once per launch and kept in a scalar register)
         const int nchains = chain_plan_count(__builtin_amdgcn_readfirstlane(plan));
+#endif
         // ONE evaluation with Jacobians at the accepted point serves the start of the step (every instance that solves: its norm is the
         // solve's first ||f||) and the iterations whose full-step trial was not the point accepted (need_jac, set where the step is accepted)
         bool need_jac = !done;
@@ -625,8 +663,18 @@ __global__ __launch_bounds__(WAVE_BLOCK) void rollout_chain_kernel(RolloutArgs a
             const bool active = c.live() && !done;
             // block-tridiagonal solve along each chain, swept from both ends (cclqr_chain.h)
             for (int ci = 0; ci < nchains; ci++) {
+#if CHAIN_PLAN_FIXED
+                constexpr int cs = PLAN::cs, cn = PLAN::cn;
+                // With the plan a constant, everything the solve derives from the lane number alone (cursors, flags, offsets) is invariant over the launch, and
+                // the compiler would keep it in registers that the kernel does not have.  So the solve reads the lane number afresh every iteration, as the
+                // run-time kernel reads the plan word: `t` below is this copy (it shadows the kernel's).
+                int t_solve = t;
+                LANE_INT_FRESH(t_solve);
+                const int t = t_solve & (G - 1);      // (the same lane number; said with its range, which the functions below are compiled with: cclqr_chain.h PlanFixed)
+#else
                 const int pw = __builtin_amdgcn_readlane(plan, ci);
                 const int cs = chain_plan_start(pw), cn = chain_plan_len(pw);
+#endif
                 // long chains: every second link is eliminated first, all at once (cr_level, cclqr_chain.h), and the two-front sweep
                 // runs over the half that is left
                 constexpr int CRW = 4;
@@ -657,6 +705,9 @@ __global__ __launch_bounds__(WAVE_BLOCK) void rollout_chain_kernel(RolloutArgs a
                     // middle solve runs there (ck_tri_mid_regs: all lanes, no hand-over in front of it), and the first back step takes dl of the
                     // middle link from the same registers -- two store -> load round trips fewer per Newton iteration on the dependent path
                     double tg[5] = {0.0, 0.0, 0.0, 0.0, 0.0}, dlm[5];
+#if CHAIN_PLAN_FIXED
+#pragma unroll 1      // (a constant trip count: rolled, as the run-time kernel's loop is)
+#endif
                     for (int i = 0; i < P.steps; i++) {
                         double zy[5];
                         int otg = 0, oout = 0;
@@ -670,6 +721,9 @@ __global__ __launch_bounds__(WAVE_BLOCK) void rollout_chain_kernel(RolloutArgs a
                     ck_tri_mid_regs(t, done, PB, K, Y, L, tg, dlm, B0);
                     ck_tri_back0_store(B0, t, Y, L, dlm);
                     WAVE_HANDOVER();
+#if CHAIN_PLAN_FIXED
+#pragma unroll 1      // (a constant trip count: rolled, as the run-time kernel's loop is)
+#endif
                     for (int j = 1; j < P.steps; j++) {
                         if (!done) ck_tri_back(t, j, PB, Y, L);
                         WAVE_HANDOVER();
@@ -948,6 +1002,8 @@ __global__ __launch_bounds__(WAVE_BLOCK) void rollout_chain_kernel(RolloutArgs a
         }
     }
 }
+#endif      // CHAIN_KERNEL_TEXT
+#ifndef CHAIN_KERNEL_TEXT
 
 #ifdef CCLQR_PROFILE
 extern "C" int cclqr_prof_read_chain(unsigned long long* out, int reset) {
@@ -959,7 +1015,7 @@ extern "C" int cclqr_prof_read_chain_n(unsigned long long* out, int cap, int res
 #endif
 
 template <int G, int NBP, int KL = 1, int NL = G>
-static hipError_t launch_chain_one(const RolloutArgs& a, ControlLaw law, bool relax, unsigned grid, size_t lds, hipStream_t stream) {
+static hipError_t launch_chain_one(const RolloutArgs& a, ControlLaw law, bool relax, bool fixed, unsigned grid, size_t lds, hipStream_t stream) {
     void (*kern)(RolloutArgs) = nullptr;
     switch (law) {
         case ControlLaw::Lqr: kern = relax ? rollout_chain_kernel<G, NBP, 0, true, KL, NL> : rollout_chain_kernel<G, NBP, 0, false, KL, NL>; break;
@@ -967,11 +1023,23 @@ static hipError_t launch_chain_one(const RolloutArgs& a, ControlLaw law, bool re
         case ControlLaw::Pid: kern = rollout_chain_kernel<G, NBP, 2, false, KL, NL>; break;
         case ControlLaw::PhiloxInKernel: kern = rollout_chain_kernel<G, NBP, 3, false, KL, NL>; break;
     }
+    if constexpr (G == 32 && (NBP == 16 || NBP == 17) && KL == 1) {
+        if (fixed) {      // one full-length chain: the same kernel with the plan compiled in
+            switch (law) {
+                case ControlLaw::Lqr: kern = relax ? rollout_chain_fixed_kernel<NBP, 0, true> : rollout_chain_fixed_kernel<NBP, 0, false>; break;
+                case ControlLaw::FricNoise: kern = rollout_chain_fixed_kernel<NBP, 1, false>; break;
+                case ControlLaw::Pid: kern = rollout_chain_fixed_kernel<NBP, 2, false>; break;
+                case ControlLaw::PhiloxInKernel: kern = rollout_chain_fixed_kernel<NBP, 3, false>; break;
+            }
+        }
+    } else if (fixed) {
+        return hipErrorInvalidValue;      // (no fixed-plan kernel of this shape: rollout_shape_of never says so)
+    }
     if (!kern) return hipErrorInvalidValue;
     return launch_lds(kern, dim3(grid), dim3(WAVE_BLOCK), lds, stream, a);      // (one wavefront: what WAVE_HANDOVER rests on)
 }
 
-hipError_t launch_rollout_chain(const RolloutArgs& a_in, const RolloutShape& s, int simds, ControlLaw law, int newton_mode, hipStream_t stream) {
+hipError_t launch_rollout_chain(const RolloutArgs& a_in, const RolloutShape& s, int simds, ControlLaw law, int newton_mode, bool runtime_plan, hipStream_t stream) {
     RolloutArgs a = a_in;
     a.ipw = spread_instances_per_wavefront(s.full, a.n_inst, a.steps, a_in.ipw != 0, simds);
     const unsigned grid = (unsigned)((a.n_inst + a.ipw - 1) / a.ipw);
@@ -986,14 +1054,16 @@ hipError_t launch_rollout_chain(const RolloutArgs& a_in, const RolloutShape& s, 
         if (tri_scratch_S(B, Y) + 25 > Y.total || tri_scratch_R(B, Y) + 5 > Y.total) return hipErrorInvalidValue;
     }
     const bool relax = newton_mode != 0;      // (the residual-only stop exists under the plain law only: launch_chain_one)
+    const bool fixed = chain_launch_fixed_plan(s, runtime_plan);
     switch (s.NBP) {
-        case 4: return s.KL == 3 ? launch_chain_one<8, 4, 3, 2>(a, law, relax, grid, s.lds, stream) : launch_chain_one<8, 4>(a, law, relax, grid, s.lds, stream);
-        case 8: return launch_chain_one<16, 8>(a, law, relax, grid, s.lds, stream);
-        case 16: return launch_chain_one<32, 16>(a, law, relax, grid, s.lds, stream);
-        case 17: return launch_chain_one<32, 17>(a, law, relax, grid, s.lds, stream);
-        case 32: return launch_chain_one<32, 32>(a, law, relax, grid, s.lds, stream);
-        default: return launch_chain_one<64, 64>(a, law, relax, grid, s.lds, stream);
+        case 4: return s.KL == 3 ? launch_chain_one<8, 4, 3, 2>(a, law, relax, fixed, grid, s.lds, stream) : launch_chain_one<8, 4>(a, law, relax, fixed, grid, s.lds, stream);
+        case 8: return launch_chain_one<16, 8>(a, law, relax, fixed, grid, s.lds, stream);
+        case 16: return launch_chain_one<32, 16>(a, law, relax, fixed, grid, s.lds, stream);
+        case 17: return launch_chain_one<32, 17>(a, law, relax, fixed, grid, s.lds, stream);
+        case 32: return launch_chain_one<32, 32>(a, law, relax, fixed, grid, s.lds, stream);
+        default: return launch_chain_one<64, 64>(a, law, relax, fixed, grid, s.lds, stream);
     }
 }
 
 }  // namespace cclqr
+#endif      // !CHAIN_KERNEL_TEXT

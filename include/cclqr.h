@@ -309,11 +309,15 @@ int cclqr_rollout_dev(const cclqr_mech *m, const cclqr_ctrl *c, int64_t n_inst, 
  *                   horizon, and keeps its status; for the others this launch's result is merged in (largest Newton count so far, negative once any
  *                   step failed).  A lost instance that had ALSO failed to converge earlier reports -(CCLQR_NEWTON_MAXIT - 1), so that "lost" stays
  *                   readable from the number.  Without the flag every launch reports on its own steps only and forgets what came before;
+ *                   CCLQR_ROLLOUT_RUNTIME_PLAN: a mechanism that is ONE chain of 16 or 17 links (the N-link cartpole) runs on a kernel with the plan of its
+ *                   block-tridiagonal solve compiled in; with this flag it runs on the general kernel of forests of chains instead, which reads the plan
+ *                   at run time -- bitwise the same results, a few per cent slower.  For A/B measurements and tests; ignored by every other mechanism;
  *   newton_eps_alone  threshold of mode 1 (<= 0: 1e-10, the rule's own eps: stop on the residual alone). */
 #define CCLQR_NEWTON_MAXIT 100        /* newton!'s iteration cap */
 #define CCLQR_ROLLOUT_NO_ALLOC 1
 #define CCLQR_ROLLOUT_PACK_WAVEFRONTS 2
 #define CCLQR_ROLLOUT_CARRY_STATUS 4
+#define CCLQR_ROLLOUT_RUNTIME_PLAN 16     /* (bit 8 stays unassigned and refused: tests/test_gpu_rollout.py uses it as its unknown bit) */
 #define CCLQR_PHILOX_INKERNEL_STEPS 8
 typedef struct {
     int64_t first_instance;

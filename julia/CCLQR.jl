@@ -47,6 +47,7 @@ struct RolloutOpts         # cclqr_rollout_opts
 end
 const ROLLOUT_NO_ALLOC = Int32(1)
 const ROLLOUT_CARRY_STATUS = Int32(4)      # `status` carries an instance's status across launches: a lost instance stays frozen (step-per-launch loops)
+const ROLLOUT_RUNTIME_PLAN = Int32(16)     # a single 16- / 17-link chain runs on the general chain kernel instead of its fixed-plan kernel: same bits
 const ROLLOUT_PACK_WAVEFRONTS = Int32(2)   # every wavefront of a chain launch full whatever the batch size (many launches sharing the device at once)
 
 struct RiccatiOpts         # cclqr_riccati_opts
@@ -301,7 +302,7 @@ end
  asynchronous on `stream`.  first_instance = global index of instance 1 of this shard (noise stream and per-instance controller table),
  pid_state = device buffer n_inst x Nb x 2 carrying the PID integrators between launches (C_NULL: none), noise_ws = device workspace of
  n_inst x steps doubles for the Philox samples (C_NULL: the controller handle's own; see reserve_noise!), newton_mode 0 = exact rule,
- flags = ROLLOUT_NO_ALLOC | ROLLOUT_PACK_WAVEFRONTS | ROLLOUT_CARRY_STATUS (include/cclqr.h)."
+ flags = ROLLOUT_NO_ALLOC | ROLLOUT_PACK_WAVEFRONTS | ROLLOUT_CARRY_STATUS | ROLLOUT_RUNTIME_PLAN (include/cclqr.h)."
 function rollout_dev!(h::MechHandle, c::CtrlHandle, n::Integer, steps::Integer, k0::Integer, z0::Ptr{Float64}, lam::Ptr{Float64},
                       traj::Ptr{Float64}, zT::Ptr{Float64}, status::Ptr{Int32}; noise::Ptr{Float64} = Ptr{Float64}(C_NULL), noise_stride = 0,
                       first_instance = 0, pid_state::Ptr{Float64} = Ptr{Float64}(C_NULL), noise_ws::Ptr{Float64} = Ptr{Float64}(C_NULL),

@@ -17,6 +17,10 @@ K = np.tile(np.load(gold)["K_first"][None], (999, 1, 1)) if n_links == 16 else r
 mh = capi.MechHandle(t); ctrl = capi.CtrlHandle(mh, [0], K=K, N=1000, zd=zd)
 names = ["control", "forces+knotjac", "eval_body", "eval_joint", "eval_map+norm", "schur_w", "schur_s", "tri_fwd", "tri_bwd", "body_solve", "trial", "accept", "io"]
 _nchild = np.bincount(np.asarray(t.parent)[np.asarray(t.parent) >= 0], minlength=t.nb)
+# slot 5 (STAMP(PF_SCHUR_W)): in the CHAIN kernel the stamp stands behind the odd-even reduction level (cr_setup .. cr_store_b), so the slot is the reduction level
+# there ("cr_level"; tables from before round 24 print it as "schur_w"); W itself is built inside the evaluation and counted with eval_joint / schur_s
+if not (_nchild > 1).any():
+    names[5] = "cr_level"
 buf = (C.c_ulonglong * 32)()
 if (_nchild > 1).any():
     read = capi.lib().cclqr_prof_read

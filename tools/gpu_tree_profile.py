@@ -13,6 +13,8 @@ rng = np.random.default_rng(0)
 K = rng.normal(size=(steps + 5, 1, 12 * t.nb)) * 0.02
 mh = capi.MechHandle(t); ctrl = capi.CtrlHandle(mh, [0], K=K, N=steps + 6, zd=z0)
 zz = np.tile(z0[None], (n, 1, 1))
+# (slot 5: the tree kernel, which this tool profiles, has no stamp for it -- the row stays 0; the chain kernel stamps its odd-even reduction level there, and
+# tools/gpu_phase_profile.py prints it as "cr_level" since round 24)
 names = ["control", "forces+knotjac", "eval_body", "eval_joint", "eval_map+norm", "schur_w", "schur_s", "tri_fwd", "tri_bwd", "body_solve", "trial", "accept", "io"]
 buf = (C.c_ulonglong * 32)()
 if hasattr(capi.lib(), "cclqr_prof_read_treereg_n"):      # the counter behind the 16 words of the two-argument read: this one takes the buffer's capacity

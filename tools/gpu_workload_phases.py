@@ -23,7 +23,9 @@ elif cfg == "tracking_cfg5":
     mh = mech._cclqr_handle; ctrl = tl._ctrl_handle(mh, fric=ex["fric"], noise_scale=2.0, noise_seed=0xC0FFEE)
 else:
     raise SystemExit("unknown workload " + cfg)
-names = ["control", "forces+knotjac", "eval_body", "eval_joint", "eval_map+norm", "schur_w", "schur_s", "tri_fwd", "tri_bwd", "body_solve", "trial", "accept", "io"]
+# slot 5 (STAMP(PF_SCHUR_W)): in the CHAIN kernel the stamp stands behind the odd-even reduction level (cr_setup .. cr_store_b), so the slot is the reduction level
+# there ("cr_level"; tables from before round 24 print it as "schur_w"); W itself is built inside the evaluation and counted with eval_joint / schur_s
+names = ["control", "forces+knotjac", "eval_body", "eval_joint", "eval_map+norm", "cr_level", "schur_s", "tri_fwd", "tri_bwd", "body_solve", "trial", "accept", "io"]
 buf = (C.c_ulonglong * 16)()
 read = capi.lib().cclqr_prof_read_chain
 read(buf, 1)
