@@ -23,7 +23,7 @@ EXPORTS = ["cclqr_last_error", "cclqr_version", "cclqr_device_count", "cclqr_set
            "cclqr_riccati_value", "cclqr_ctrl_create_lqr_batch_value", "cclqr_value_create", "cclqr_value_get", "cclqr_value_destroy", "cclqr_value_eval",
            "cclqr_policy_value", "cclqr_value_create_policy", "cclqr_policy_value_doubling", "cclqr_value_create_policy_doubling",
            "cclqr_riccati_doubling", "cclqr_ctrl_create_lqr_batch_doubling", "cclqr_covariance_doubling", "cclqr_value_create_covariance_doubling",
-           "cclqr_covariance_tracking", "cclqr_value_create_covariance_tracking"]
+           "cclqr_covariance_tracking", "cclqr_value_create_covariance_tracking", "cclqr_policy_value_tracking", "cclqr_value_create_policy_tracking"]
 ABI_VERSION = 202     # include/cclqr.h CCLQR_ABI_VERSION: the structs below mirror that header (verified field by field against cclqr_abi_layout at load time)
 ROLLOUT_NO_ALLOC = 1  # cclqr_rollout_opts.flags: the call may neither allocate nor synchronise (a hipGraph capture is open on the device)
 ROLLOUT_CARRY_STATUS = 4  # ... `status` is read and written: an instance lost in an earlier launch stays frozen, the others merge this launch's result into it
@@ -1033,6 +1033,69 @@ def value_create_covariance_tracking(mech, ctrl, zd, n, N, ctrl_joint, Q, R, Wu,
                                                        _d(Wu), _d(Sigma0), C.c_int64(int(workspace_bytes)), _d(cost), _d(zstd), _d(ustd), _d(total),
                                                        None if stream is None else C.c_void_p(int(stream)), C.byref(vptr)))
     return ValueHandle(mech, ptr=vptr, n_tables=n), cost, zstd, ustd, total
+
+
+def policy_value_tracking(A, Bu, Bl, G, K, Q, R, Wu, N, path=0, bf16_terms=0, want_P=True, want_all=False, want_price=True, want_total=True):
+    """the cost-to-go of a tracked run at every knot and the price of its noise (cclqr_policy_value_tracking; lqr_tracking.jl:63, 88, 107, 108 under the noise of
+    trackingLQR_triple_cartpole.jl:98): P_{N-1} = Q, P_j = Q + K_j' R K_j + Abar_j' P_{j+1} Abar_j, price_j = tr(Wu D_j' P_{j+1} D_j).  Models, K, Q, R as
+    covariance_tracking takes them (Q, R required); Wu [mu][mu] or [n][mu][mu], or None: no price -> P [nprob][mx][mx] = P_0, P_all [nprob][N][mx][mx],
+    price [nprob][N], noise_total [nprob]; want_* = False pass NULL (returned as None), as does Wu = None for the last two"""
+    A = f64(A)
+    if A.ndim != 4 or A.shape[-1] != A.shape[-2]:
+        raise ValueError("A must be [nprob][nlin][mx][mx] (got %s)" % (A.shape,))
+    nprob, nlin, mx = A.shape[0], A.shape[1], A.shape[-1]
+    Bu, Bl = f64(Bu), f64(Bl)
+    Bu = Bu.reshape(nprob, nlin, mx, -1) if Bu.size else Bu.reshape(nprob, nlin, mx, 0)
+    mu = Bu.shape[3]
+    Bl = Bl.reshape(nprob, nlin, mx, -1) if Bl.size else Bl.reshape(nprob, nlin, mx, 0)
+    ml = Bl.shape[3]
+    G = f64(G).reshape(nprob, nlin, ml, mx)
+    K = f64(K)
+    if K.ndim not in (2, 3, 4) or K.shape[-2:] != (mu, mx):
+        raise ValueError("K must be [mu][mx], [nK][mu][mx] or [n_gains][nK][mu][mx] with mu = %d, mx = %d (got %s)" % (mu, mx, K.shape))
+    K = K.reshape((1,) * (4 - K.ndim) + K.shape)
+    Q = f64(Q).reshape(-1, mx, mx)
+    nw = Q.shape[0]
+    R = f64(R).reshape(nw, mu, mu)
+    Wu, _, n_noise = _noise_arrays(Wu, None, mu, mx)
+    N = int(N)
+    P = np.zeros((nprob, mx, mx)) if want_P else None
+    Pall = np.zeros((nprob, N, mx, mx)) if want_all else None
+    price = np.zeros((nprob, N)) if (want_price and Wu is not None) else None
+    total = np.zeros(nprob) if (want_total and Wu is not None) else None
+    o = RiccatiOpts(int(path), int(bf16_terms), 0, 0)
+    check(lib().cclqr_policy_value_tracking(C.c_int32(nprob), C.c_int32(mx), C.c_int32(mu), C.c_int32(ml), C.c_int32(nlin), _d(A), _d(Bu) if mu else None,
+                                            _d(Bl) if ml else None, _d(G) if ml else None, C.c_int32(K.shape[0]), C.c_int32(K.shape[1]), _d(K) if K.size else None,
+                                            C.c_int32(nw), _d(Q), _d(R) if mu else None, C.c_int32(n_noise), _d(Wu), C.c_int32(N), _d(P), _d(Pall), _d(price), _d(total),
+                                            C.byref(o)))
+    return P, Pall, price, total
+
+
+def value_create_policy_tracking(mech, ctrl, zd, n, N, ctrl_joint, Q, R, Wu, knot=0, Fd=None, plants=None, first_plant=0, workspace_bytes=0, on_device=False, stream=None):
+    """cclqr_value_create_policy_tracking: the cost-to-go above for controller handle `ctrl`'s gain rows along n trajectories zd [n][N][nb][13] (Fd [n][N][mu]),
+    linearised at the knots 0 .. N-2 on plant first_plant + k; numpy arrays, or with on_device=True device addresses read in place on `stream`.  Q in the mechanism's
+    body order; the recursion runs down to `knot` -> (ValueHandle of n tables holding P_knot, price [n][N], noise_total [n]); Wu = None: the last two are None"""
+    nb = mech.tables.nb
+    n, N = int(n), int(N)
+    cj = i32(ctrl_joint).reshape(-1)
+    mu = len(cj)
+    if on_device:
+        zp, fp = C.c_void_p(int(zd)), (None if Fd is None else C.c_void_p(int(Fd)))
+    else:
+        zd = f64(zd).reshape(n, N, nb, 13)
+        Fd = None if Fd is None else f64(Fd).reshape(n, N, mu)
+        zp, fp = _d(zd), _d(Fd)
+    Q = f64(Q).reshape(-1, 12 * nb, 12 * nb)
+    nw = Q.shape[0]
+    R = f64(R).reshape(nw, mu, mu)
+    Wu, _, n_noise = _noise_arrays(Wu, None, mu, 12 * nb)
+    price, total = (np.zeros((n, N)), np.zeros(n)) if Wu is not None else (None, None)
+    vptr = C.c_void_p()
+    check(lib().cclqr_value_create_policy_tracking(mech.ptr, None if plants is None else plants.ptr, C.c_int64(int(first_plant)), C.c_int32(n), C.c_int32(N), zp, fp,
+                                                   C.c_int32(1 if on_device else 0), C.c_int32(mu), _i(cj), ctrl.ptr, C.c_int32(nw), _d(Q), _d(R), C.c_int32(n_noise),
+                                                   _d(Wu), C.c_int32(int(knot)), C.c_int64(int(workspace_bytes)), _d(price), _d(total),
+                                                   None if stream is None else C.c_void_p(int(stream)), C.byref(vptr)))
+    return ValueHandle(mech, ptr=vptr, n_tables=n), price, total
 
 
 def riccati_doubling(A, Bu, Bl, G, Q, R, N, tol=1e-5, max_levels=40, bf16_terms=0, want_P=True, want_diag=True, K=None, P=None):

@@ -1839,16 +1839,21 @@ extern "C" int cclqr_covariance_tracking(int32_t nprob, int32_t mx, int32_t mu, 
     return tracking_cov_report(o, nprob, mx, mu, N, cost, zstd, ustd, total, "problem");
 }
 
-// the same recursion for a CONTROLLER on a mechanism's plants: linearsystem at the knots 0 .. N-2 of trajectory k on plant first_plant + k (lqr_tracking.jl:88), the
-// controller's gain rows gathered on the device, the problems in chunks within the workspace budget (tracking_cov_problem_bytes)
-extern "C" int cclqr_value_create_covariance_tracking(const cclqr_mech* m, const cclqr_plants* plants, int64_t first_plant, int32_t n_models, int32_t N, const double* zd,
-                                                      const double* Fd, int32_t on_device, int32_t mu, const int32_t* ctrl_joint, const cclqr_ctrl* c, int32_t n_weights,
-                                                      const double* Q, const double* R, int32_t n_noise, const double* Wu, const double* Sigma0, int64_t workspace_bytes,
-                                                      double* cost, double* zstd, double* ustd, double* total, void* stream, cclqr_value** out) {
-    static const char* const what = "tracking covariance";
+// A knot-by-knot recursion for a CONTROLLER on a mechanism's plants, the ONE host sequence of the tracking analyses (cclqr_value_create_covariance_tracking,
+// cclqr_value_create_policy_tracking): linearsystem at the knots 0 .. N-2 of trajectory k on plant first_plant + k (lqr_tracking.jl:88), the controller's gain rows
+// gathered on the device, the problems in chunks within the workspace budget.  What an analysis brings of its own:
+//   check(nlin, tables, nK)                        its refusals about counts, weights and noise, before anything is allocated or launched
+//   plan(mx, ml, ric_per, ric_fixed, &per, &fixed) the bytes one problem adds to a chunk and the bytes the call holds once (tracking_cov_ / tracking_pol_problem_bytes)
+//   setup(chunk, mx, ml, nlin, nK, stream)         its launch arguments, inside this sequence's WsScope
+//   launch(c0, nc, dA, dBu, dBl, dG, dK, k_stride, P_dev, stream)   the recursion for the problems c0 .. c0 + nc - 1 on the chunk's models
+//   report()                                       its read-back into the caller's arrays, after every knot has converged
+template <class Check, class Plan, class Setup, class Launch, class Report>
+static int tracking_value_on_plants(const char* what, const cclqr_mech* m, const cclqr_plants* plants, int64_t first_plant, int32_t n_models, int32_t N, const double* zd,
+                                    const double* Fd, int32_t on_device, int32_t mu, const int32_t* ctrl_joint, const cclqr_ctrl* c, int64_t workspace_bytes, void* stream,
+                                    cclqr_value** out, Check check, Plan plan, Setup setup, Launch launch, Report report) {
     if (!m || !zd || !c || !out || (mu > 0 && !ctrl_joint)) return fail(CCLQR_EINVAL, "null argument");
     TRY(check_device(m));
-    if (m->host.loop) return fail(CCLQR_EUNSUPPORTED, "the tracking covariance is for tree mechanisms (closed loops have no multiplier model to evaluate a gain on)");
+    if (m->host.loop) return fail(CCLQR_EUNSUPPORTED, std::string("the ") + what + " is for tree mechanisms (closed loops have no multiplier model to evaluate a gain on)");
     if (c->nb != m->nb || c->device != m->device) return fail(CCLQR_EINVAL, "the controller was created for another mechanism or device");
     if (n_models < 1 || N < 1 || mu < 1 || mu > m->nb) return fail(CCLQR_EINVAL, "bad sizes");
     const CtrlDev& H = c->host;
@@ -1864,17 +1869,16 @@ extern "C" int cclqr_value_create_covariance_tracking(const cclqr_mech* m, const
         return fail(CCLQR_EINVAL, "the controller holds " + std::to_string(tables) + " tables: one shared by all models (1) or one per model (" + std::to_string(n_models) + ")");
     if (N > 1 && H.nK != 1 && H.nK != N - 1)
         return fail(CCLQR_EINVAL, "the controller's tables hold " + std::to_string(H.nK) + " gain rows: one (a stationary gain) or N - 1 = " + std::to_string(N - 1) + ", one per knot 0 .. N-2");
-    const bool want_cost = cost || total;
     const int nb = m->nb, mx = 12 * nb, ml = 5 * nb, nlin = N > 1 ? N - 1 : 1;
-    TRY(tracking_cov_check(n_models, mu, N, nlin, (int)tables, H.nK, n_weights, n_noise, Wu, Sigma0, Q, R, want_cost, nullptr, "model"));
+    TRY(check(nlin, (int)tables, H.nK));
     // the chunks the workspace budget allows, before anything is allocated
     RicArgs r1;
     r1.nprob = 1; r1.mx = mx; r1.mu = mu; r1.ml = ml; r1.N = N; r1.time_varying = nlin > 1 ? 1 : 0; r1.tol = 0.0; r1.path = 0; r1.bf16_terms = 0; r1.keep_last = 0;
     RicArgs r2 = r1;
     r2.nprob = 2;
     const long long ric_per = (long long)(ric_total_work_doubles(r2) - ric_total_work_doubles(r1)), ric_fixed = (long long)ric_total_work_doubles(r1) - ric_per;
-    const long long per_bytes = tracking_cov_problem_bytes(mx, mu, ml, N, ric_per);
-    const long long fixed_bytes = tracking_cov_fixed_bytes(mx, mu, ric_fixed, want_cost ? n_weights : 1, n_noise);
+    long long per_bytes = 0, fixed_bytes = 0;
+    plan(mx, ml, ric_per, ric_fixed, &per_bytes, &fixed_bytes);
     const long long budget = workspace_bytes > 0 ? (long long)workspace_bytes : CCLQR_TRACKING_WORKSPACE_BYTES;
     const long long per_chunk = tracking_chunk_problems(n_models, per_bytes, fixed_bytes, budget);
     if (per_chunk < 1)
@@ -1914,8 +1918,7 @@ extern "C" int cclqr_value_create_covariance_tracking(const cclqr_mech* m, const
     HIPTRY(what, ws_get((void**)&dBl, pc * nkk * smx * sml * sizeof(double)));
     HIPTRY(what, ws_get((void**)&dG, pc * nkk * sml * smx * sizeof(double)));
     HIPTRY(what, ws_get((void**)&dlst, (np * nkk + 1) * sizeof(int)));
-    CtkArgs dev;
-    TRY(ctk_setup(n_models, (int)pc, mx, mu, ml, N, nlin, H.nK, n_weights, want_cost ? Q : nullptr, R, n_noise, Wu, Sigma0, 0, st_, dev));
+    TRY(setup((int)pc, mx, ml, nlin, H.nK, st_));
     la.M = m->dev; la.mu = mu;
     la.plants = plants ? plants->dev : nullptr;
     la.knots_per_plant = (int)nk; la.rows_per_plant = N;
@@ -1930,18 +1933,187 @@ extern "C" int cclqr_value_create_covariance_tracking(const cclqr_mech* m, const
             la.status = dlst + c0 * nk;
             HIPTRY(what, launch_linearize(la, m->shape, st_));
         }
-        HIPTRY(what, ctk_launch_chunk(dev, c0, nc, dA, dBu, dBl, dG, dK, k_stride, vown.p->P_dev, nullptr, st_));
+        HIPTRY(what, launch(c0, nc, dA, dBu, dBl, dG, dK, k_stride, vown.p->P_dev, st_));
     }
     HIPTRY(what, hipStreamSynchronize(st_));
     long long bad = -1;
     if (nk > 0) HIPTRY(what, knots_converged(dlst, np * nk, &bad));
     if (bad >= 0)
         return fail(CCLQR_ENOCONV, "Newton did not converge at the setpoint of knot " + std::to_string((size_t)bad % nk) + " of table " + std::to_string((size_t)bad / nk));
-    CtkOut o;
-    TRY(ctk_read_back(dev, n_models, o));
-    TRY(tracking_cov_report(o, n_models, mx, mu, N, cost, zstd, ustd, total, "table"));
+    TRY(report());
     *out = vown.release();
     return CCLQR_OK;
+}
+
+extern "C" int cclqr_value_create_covariance_tracking(const cclqr_mech* m, const cclqr_plants* plants, int64_t first_plant, int32_t n_models, int32_t N, const double* zd,
+                                                      const double* Fd, int32_t on_device, int32_t mu, const int32_t* ctrl_joint, const cclqr_ctrl* c, int32_t n_weights,
+                                                      const double* Q, const double* R, int32_t n_noise, const double* Wu, const double* Sigma0, int64_t workspace_bytes,
+                                                      double* cost, double* zstd, double* ustd, double* total, void* stream, cclqr_value** out) {
+    const bool want_cost = cost || total;
+    CtkArgs dev;
+    return tracking_value_on_plants(
+        "tracking covariance", m, plants, first_plant, n_models, N, zd, Fd, on_device, mu, ctrl_joint, c, workspace_bytes, stream, out,
+        [&](int nlin, int tables, int nK) { return tracking_cov_check(n_models, mu, N, nlin, tables, nK, n_weights, n_noise, Wu, Sigma0, Q, R, want_cost, nullptr, "model"); },
+        [&](int mx, int ml, long long ric_per, long long ric_fixed, long long* per, long long* fixed) {
+            *per = tracking_cov_problem_bytes(mx, mu, ml, N, ric_per);
+            *fixed = tracking_cov_fixed_bytes(mx, mu, ric_fixed, want_cost ? n_weights : 1, n_noise);
+        },
+        [&](int chunk, int mx, int ml, int nlin, int nK, hipStream_t st) {
+            return ctk_setup(n_models, chunk, mx, mu, ml, N, nlin, nK, n_weights, want_cost ? Q : nullptr, R, n_noise, Wu, Sigma0, 0, st, dev);
+        },
+        [&](size_t c0, size_t nc, const double* dA, const double* dBu, const double* dBl, const double* dG, const double* dK, long long k_stride, double* P_dev, hipStream_t st) {
+            return ctk_launch_chunk(dev, c0, nc, dA, dBu, dBl, dG, dK, k_stride, P_dev, nullptr, st);
+        },
+        [&]() {
+            CtkOut o;
+            TRY(ctk_read_back(dev, n_models, o));
+            return tracking_cov_report(o, n_models, dev.r.mx, mu, N, cost, zstd, ustd, total, "table");
+        });
+}
+
+// ---- the cost-to-go of a tracked run, knot by knot (policy_tracking.hip): P_j = Q + K_j' R K_j + Abar_j' P_{j+1} Abar_j with the gain row and the model of knot j
+// (lqr_tracking.jl:63-65, 88-89, 107-108), and the price of the noise of trackingLQR_triple_cartpole.jl:98 at every knot
+// what the entry refuses about its counts and its noise, before anything is allocated or launched: tracking_cov_check's list, and a price without a noise
+static int tracking_pol_check(int nprob, int mu, int N, int nlin, int n_gains, int nK, int n_weights, int n_noise, const double* Wu, const double* Q, const double* R,
+                              const double* price, const double* noise_total, int knot, const cclqr_riccati_opts* opts, const char* of) {
+    if (N > 1 && nlin != 1 && nlin != N - 1)
+        return fail(CCLQR_EINVAL, "nlin = " + std::to_string(nlin) + ": one time-invariant model (1) or one per knot 0 .. N-2 (" + std::to_string(N - 1) + ")");
+    if (n_gains != 1 && n_gains != nprob)
+        return fail(CCLQR_EINVAL, "n_gains = " + std::to_string(n_gains) + ": the gains are one table shared by all (1) or one table per " + of + " (" + std::to_string(nprob) + ")");
+    if (N > 1 && mu > 0 && nK != 1 && nK != N - 1)
+        return fail(CCLQR_EINVAL, "nK = " + std::to_string(nK) + ": a gain table holds one row (a stationary gain) or N - 1 = " + std::to_string(N - 1) + " rows, one per knot 0 .. N-2");
+    TRY(check_n_weights(n_weights, nprob, of));
+    if (n_noise != 1 && n_noise != nprob)
+        return fail(CCLQR_EINVAL, "n_noise = " + std::to_string(n_noise) + ": Wu is one shared by all (1) or one per " + of + " (" + std::to_string(nprob) + ")");
+    if (Wu && mu == 0) return fail(CCLQR_EINVAL, "Wu is given with mu = 0: there is no input for the noise to enter through");
+    if (!Wu && (price || noise_total)) return fail(CCLQR_EINVAL, "price / noise_total are asked for without Wu: there is no noise to price");
+    if (!Q || (mu > 0 && !R)) return fail(CCLQR_EINVAL, "the cost-to-go needs Q / R");
+    if (knot < 0 || knot > N - 1) return fail(CCLQR_EINVAL, "knot = " + std::to_string(knot) + ": the cost-to-go is that of a knot in 0 .. N-1 = " + std::to_string(N - 1));
+    if (nprob > 65535) return fail(CCLQR_EINVAL, "nprob = " + std::to_string(nprob) + ": at most 65535 problems per call (they are the y extent of the launch grids)");
+    const int path = opts ? opts->path : 0;
+    if (path < 0 || path > 2) return fail(CCLQR_EINVAL, "tracking policy value options: path in 0..2");
+    if (opts && opts->bf16_terms != 0) return fail(CCLQR_EINVAL, "the tracking policy value runs in fp64 only (bf16_terms = 0)");
+    return CCLQR_OK;
+}
+// what a tracking-policy call brings back to the host
+struct PtkOut { std::vector<double> price, total; std::vector<int> st, knot; };
+// fills d, inside the caller's WsScope, with the launch arguments of problem 0 onwards: weights, noise, prices, totals and statuses of ALL nprob problems, the workspace
+// of `chunk` problems, the most one launch takes.  Q, R, Wu: HOST, as the entries take them
+static int ptk_setup(int nprob, int chunk, int mx, int mu, int ml, int N, int nlin, int nK, int knot, int n_weights, const double* Q, const double* R, int n_noise,
+                     const double* Wu, int path, PtkArgs& d) {
+    static const char* const what = "tracking policy value";
+    const size_t np = (size_t)nprob, nn = (size_t)n_noise, uu = (size_t)mu * mu;
+    PtkArgs& c = d;
+    c = PtkArgs{};
+    RicArgs& r = c.r;
+    r.nprob = chunk; r.mx = mx; r.mu = mu; r.ml = ml; r.N = N; r.time_varying = (N > 1 && nlin > 1) ? 1 : 0; r.tol = 0.0; r.path = path; r.bf16_terms = 0; r.keep_last = 0;
+    double *dQ = nullptr, *dR = nullptr, *dWu = nullptr, *dwork = nullptr, *dprice = nullptr, *dtot = nullptr;
+    int *dst = nullptr, *dkn = nullptr;
+    TRY(upload_weights(mx, mu, n_weights, Q, R, &dQ, &dR, what));
+    if (n_weights > 1) { r.q_stride = (long long)mx * mx; r.r_stride = (long long)uu; }
+    if (Wu) {
+        HIPTRY(what, ws_get((void**)&dWu, nn * uu * sizeof(double)));
+        HIPTRY(what, hipMemcpy(dWu, Wu, nn * uu * sizeof(double), hipMemcpyHostToDevice));
+        c.wu_stride = n_noise > 1 ? (long long)uu : 0;
+        HIPTRY(what, ws_get((void**)&dprice, np * N * sizeof(double)));
+        HIPTRY(what, ws_get((void**)&dtot, np * sizeof(double)));
+    }
+    HIPTRY(what, ws_get((void**)&dwork, ric_total_work_doubles(r) * sizeof(double)));
+    HIPTRY(what, ws_get((void**)&dst, np * sizeof(int)));
+    HIPTRY(what, ws_get((void**)&dkn, np * sizeof(int)));
+    r.work = dwork; r.status = dst; r.kbreak = dkn; r.Q = dQ; r.R = dR;
+    c.nK = nK; c.knot = knot; c.Wu = dWu; c.price = dprice; c.total = dtot;
+    return CCLQR_OK;
+}
+// the recursion for the problems c0 .. c0 + nc - 1 on `stream`: their models (nlin per problem) lie at dA .. dG, their gains in dK (the tables of ALL problems, k_stride
+// doubles apart, 0 = one shared); dP [nprob][mx][mx] (or null) and dP_all [nprob][N][mx][mx] (or null) are the whole call's
+static hipError_t ptk_launch_chunk(const PtkArgs& d, size_t c0, size_t nc, const double* dA, const double* dBu, const double* dBl, const double* dG, const double* dK,
+                                   long long k_stride, double* dP, double* dP_all, hipStream_t stream) {
+    PtkArgs c = d;
+    const size_t mm = (size_t)c.r.mx * c.r.mx, N = (size_t)c.r.N;
+    c.r.nprob = (int)nc; c.r.A = dA; c.r.Bu = dBu; c.r.Bl = dBl; c.r.G = dG;
+    c.r.status += c0; c.r.kbreak += c0;
+    c.r.Q += (long long)c0 * c.r.q_stride; c.r.R += (long long)c0 * c.r.r_stride;
+    c.Kin = dK + (long long)c0 * k_stride; c.k_stride = k_stride;
+    if (c.Wu) { c.Wu += (long long)c0 * c.wu_stride; c.price += c0 * N; c.total += c0; }
+    c.P = dP ? dP + c0 * mm : nullptr;
+    c.P_all = dP_all ? dP_all + c0 * N * mm : nullptr;
+    return launch_policy_tracking(c, stream);
+}
+static int ptk_read_back(const PtkArgs& d, int nprob, PtkOut& o) {
+    static const char* const what = "tracking policy value";
+    const size_t np = (size_t)nprob, len = np * (size_t)d.r.N;
+    o.st.resize(np); o.knot.resize(np);
+    if (d.price) {
+        o.price.resize(len); o.total.resize(np);
+        HIPTRY(what, hipMemcpy(o.price.data(), d.price, len * sizeof(double), hipMemcpyDeviceToHost));
+        HIPTRY(what, hipMemcpy(o.total.data(), d.total, np * sizeof(double), hipMemcpyDeviceToHost));
+    }
+    HIPTRY(what, hipMemcpy(o.st.data(), d.r.status, np * sizeof(int), hipMemcpyDeviceToHost));
+    HIPTRY(what, hipMemcpy(o.knot.data(), d.r.kbreak, np * sizeof(int), hipMemcpyDeviceToHost));
+    return CCLQR_OK;
+}
+// the prices into the caller's arrays (each may be null), for the problems before the one the call is refused for, which it names with its knot
+static int tracking_pol_report(const PtkOut& o, int nprob, int N, double* price, double* noise_total, const char* of) {
+    for (int p = 0; p < nprob; p++) {
+        if (o.st[p] != 0) return fail(CCLQR_ESINGULAR, "G*Bl is singular in " + std::string(of) + " " + std::to_string(p) + " at knot " + std::to_string(o.knot[p]));
+        if (price) memcpy(price + (size_t)p * N, o.price.data() + (size_t)p * N, (size_t)N * sizeof(double));
+        if (noise_total) noise_total[p] = o.total[(size_t)p];
+    }
+    return CCLQR_OK;
+}
+
+extern "C" int cclqr_policy_value_tracking(int32_t nprob, int32_t mx, int32_t mu, int32_t ml, int32_t nlin, const double* A, const double* Bu, const double* Bl, const double* G,
+                                           int32_t n_gains, int32_t nK, const double* K, int32_t n_weights, const double* Q, const double* R, int32_t n_noise, const double* Wu,
+                                           int32_t N, double* P, double* P_all, double* price, double* noise_total, const cclqr_riccati_opts* opts) {
+    static const char* const what = "tracking policy value";
+    if (nprob < 1 || mx < 1 || mu < 0 || ml < 0 || N < 1) return fail(CCLQR_EINVAL, "bad sizes");
+    if (N > 1 && (!A || (mu > 0 && (!Bu || !K)) || (ml > 0 && (!Bl || !G)))) return fail(CCLQR_EINVAL, "null argument");
+    TRY(tracking_pol_check(nprob, mu, N, nlin, n_gains, nK, n_weights, n_noise, Wu, Q, R, price, noise_total, 0, opts, "problem"));
+    WsScope scope;
+    RicModels d = {};
+    if (N > 1) TRY(upload_models((size_t)nprob * nlin, mx, mu, ml, A, Bu, Bl, G, d));      // N = 1: no model is read
+    const size_t nKd = (mu > 0 && N > 1) ? (size_t)n_gains * nK * mu * mx : 0, nP = (size_t)nprob * mx * mx;
+    double *dK = nullptr, *dP = nullptr, *dAll = nullptr;
+    HIPTRY(what, ws_get((void**)&dK, (nKd + 1) * sizeof(double)));
+    HIPTRY(what, ws_get((void**)&dP, nP * sizeof(double)));
+    if (P_all) HIPTRY(what, ws_get((void**)&dAll, nP * N * sizeof(double)));
+    if (nKd) HIPTRY(what, hipMemcpy(dK, K, nKd * sizeof(double), hipMemcpyHostToDevice));
+    PtkOut o;
+    PtkArgs dev;
+    TRY(ptk_setup(nprob, nprob, mx, mu, ml, N, nlin, nK, 0, n_weights, Q, R, n_noise, Wu, opts ? opts->path : 0, dev));
+    HIPTRY(what, ptk_launch_chunk(dev, 0, (size_t)nprob, d.A, d.Bu, d.Bl, d.G, dK, n_gains > 1 ? (long long)nK * mu * mx : 0, dP, dAll, nullptr));
+    HIPTRY(what, hipDeviceSynchronize());
+    TRY(ptk_read_back(dev, nprob, o));
+    int bad = nprob;      // the first problem the call is refused for: the arrays are filled up to it
+    for (int p = nprob - 1; p >= 0; p--) if (o.st[p] != 0) bad = p;
+    if (P && bad > 0) HIPTRY(what, hipMemcpy(P, dP, (size_t)bad * mx * mx * sizeof(double), hipMemcpyDeviceToHost));
+    if (P_all && bad > 0) HIPTRY(what, hipMemcpy(P_all, dAll, (size_t)bad * N * mx * mx * sizeof(double), hipMemcpyDeviceToHost));
+    return tracking_pol_report(o, nprob, N, price, noise_total, "problem");
+}
+
+// the same recursion for a CONTROLLER on a mechanism's plants, down to `knot`: tracking_value_on_plants with the policy's plan (tracking_pol_problem_bytes)
+extern "C" int cclqr_value_create_policy_tracking(const cclqr_mech* m, const cclqr_plants* plants, int64_t first_plant, int32_t n_models, int32_t N, const double* zd,
+                                                  const double* Fd, int32_t on_device, int32_t mu, const int32_t* ctrl_joint, const cclqr_ctrl* c, int32_t n_weights,
+                                                  const double* Q, const double* R, int32_t n_noise, const double* Wu, int32_t knot, int64_t workspace_bytes, double* price,
+                                                  double* noise_total, void* stream, cclqr_value** out) {
+    PtkArgs dev;
+    return tracking_value_on_plants(
+        "tracking policy value", m, plants, first_plant, n_models, N, zd, Fd, on_device, mu, ctrl_joint, c, workspace_bytes, stream, out,
+        [&](int nlin, int tables, int nK) { return tracking_pol_check(n_models, mu, N, nlin, tables, nK, n_weights, n_noise, Wu, Q, R, price, noise_total, knot, nullptr, "model"); },
+        [&](int mx, int ml, long long ric_per, long long ric_fixed, long long* per, long long* fixed) {
+            *per = tracking_pol_problem_bytes(mx, mu, ml, N, ric_per);
+            *fixed = tracking_pol_fixed_bytes(mx, mu, ric_fixed, n_weights, Wu ? n_noise : 0);
+        },
+        [&](int chunk, int mx, int ml, int nlin, int nK, hipStream_t) { return ptk_setup(n_models, chunk, mx, mu, ml, N, nlin, nK, knot, n_weights, Q, R, n_noise, Wu, 0, dev); },
+        [&](size_t c0, size_t nc, const double* dA, const double* dBu, const double* dBl, const double* dG, const double* dK, long long k_stride, double* P_dev, hipStream_t st) {
+            return ptk_launch_chunk(dev, c0, nc, dA, dBu, dBl, dG, dK, k_stride, P_dev, nullptr, st);
+        },
+        [&]() {
+            PtkOut o;
+            TRY(ptk_read_back(dev, n_models, o));
+            return tracking_pol_report(o, n_models, N, price, noise_total, "table");
+        });
 }
 
 // ---- the Riccati map itself by doubling (riccati_doubling.hip): Ku[1] and the last Pkp1 of lqr.jl:141-184 after N - 1 steps, or at convergence (lqr.jl:25-27, 39-43)

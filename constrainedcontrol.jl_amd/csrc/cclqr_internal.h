@@ -290,6 +290,26 @@ bool ctk_resident_fits(int mx, int mu);
 int ctk_chosen_path(int mx, int mu, int path);
 hipError_t launch_covariance_tracking(const CtkArgs& a, hipStream_t stream);
 
+// The cost-to-go of a tracked run, knot by knot (policy_tracking.hip), the adjoint of the recursion above: P_{N-1} = Q, P_j = Q + K_j' R K_j + Abar_j' P_{j+1} Abar_j
+// (lqr_tracking.jl:108 with the gain given), j = N-2 .. knot, and price_j = tr(Wu D_j' P_{j+1} D_j).  r: as for launch_covariance_tracking, and Q, R with their strides
+// (the stage-cost weights, required).
+struct PtkArgs {
+    RicArgs r;
+    const double* Kin;           // device: gain tables [n_gains][nK][mu][mx] in the order of the models' states; may be null when mu = 0 or N = 1
+    long long k_stride;          // doubles between the tables of consecutive problems: 0 = one table shared by all, or nK * mu * mx
+    int nK;                      // rows per table: N - 1 (row j = the gain of knot j) or 1 (a stationary gain)
+    int knot;                    // in [0, N-1]: the recursion runs from N - 1 down to this knot
+    const double* Wu;            // device [n_noise][mu][mu], or null: no price is taken
+    long long wu_stride;
+    double *P, *P_all;           // device [nprob][mx][mx] = P_knot, [nprob][N][mx][mx] (knots below `knot` are not written); each may be null
+    double *price, *total;       // device [nprob][N] (zeros below `knot` and at N - 1), [nprob] = the prices summed from N - 2 downwards; both given with Wu, else both null
+};
+// the resident kernel's fit rule -- the shapes ctk_resident_fits serves --, and the path a launch takes (1 resident, 2 tiled): the shape and opts->path alone decide
+size_t ptk_resident_lds_bytes(int mx, int mu);
+bool ptk_resident_fits(int mx, int mu);
+int ptk_chosen_path(int mx, int mu, int path);
+hipError_t launch_policy_tracking(const PtkArgs& a, hipStream_t stream);
+
 // The Riccati map itself by doubling (riccati_doubling.hip): n steps of lqr.jl:151-170 in projected form are the triple (A_n, G_n, H_n) of the map
 // X -> H_n + A_n' X (I + G_n X)^-1 A_n; one step is (A', D R^-1 D', Q), and triple 1 applied after triple 2 is
 //   W = (I + G1 H2)^-1,  A = A2 W A1,  G = G2 + A2 W G1 A2',  H = H1 + A1' H2 W A1
@@ -368,6 +388,18 @@ inline long long tracking_cov_problem_bytes(int mx, int mu, int ml, int N, long 
 inline long long tracking_cov_fixed_bytes(int mx, int mu, long long ric_fixed, int n_weights, int n_noise) {
     const long long mm = (long long)mx * mx, uu = (long long)mu * mu;
     return 8 * (ric_fixed + (long long)n_weights * (mm + uu + 1) + (long long)n_noise * (mm + uu));
+}
+// ---- the cost-to-go of tracked runs on a mechanism's plants (cclqr_value_create_policy_tracking): the same plan again.  A problem adds to a chunk its N - 1 linear
+// models, its share of the recursion's workspace and its knots' Newton statuses; what every problem of the CALL holds whatever the chunk -- its N prices, its total,
+// status and knot -- is counted with it
+inline long long tracking_pol_problem_bytes(int mx, int mu, int ml, int N, long long ric_doubles) {
+    const long long nk = N - 1;
+    return 8 * (nk * ((long long)mx * mx + (long long)mx * mu + 2LL * mx * ml) + ric_doubles + (long long)N + 1) + 4 * ((nk + 1) & ~1LL) + 8;
+}
+// ... and what the call holds once: the recursion's fixed workspace (ric_fixed doubles), the weights and the noise as given (Wu only: there is no start covariance)
+inline long long tracking_pol_fixed_bytes(int mx, int mu, long long ric_fixed, int n_weights, int n_noise) {
+    const long long mm = (long long)mx * mx, uu = (long long)mu * mu;
+    return 8 * (ric_fixed + (long long)n_weights * (mm + uu + 1) + (long long)n_noise * uu);
 }
 
 }  // namespace cclqr

@@ -951,91 +951,14 @@ class TrackingCovariance:
 
     def __init__(self, mechanism, controller, bodyids, eqcids, Q, R, noise_scale=None, Wu=None, Sigma0=None, plants=None, first_plant=None, storage=None, Fτ=None,
                  workspace_bytes=0):
-        if not isinstance(mechanism, Mechanism):
-            raise TypeError("TrackingCovariance(mechanism, controller, bodyids, eqcids, Q, R; ...)")
-        if not isinstance(controller, (TrackingLQR, PlantTrackingLQR)):
-            raise ValueError("TrackingCovariance propagates noise through the gain rows of a TrackingLQR or PlantTrackingLQR (got %s)" % type(controller).__name__)
-        if controller.mechanism is not mechanism:
-            raise ValueError("the controller was made for another mechanism")
-        if getattr(controller, "controlfunction", None) is not None:
-            raise ValueError("the controller carries a controlfunction: the covariance is that of the device's own tracking law (lqr_tracking.jl:63-65), not of a host closure")
-        batched = isinstance(controller, PlantTrackingLQR)
-        if plants is None and first_plant is None and batched:
-            plants, first_plant = controller.plants, controller.first_plant
-        if plants is not None and plants.mechanism is not mechanism:
-            raise ValueError("the PlantBatch was made for another mechanism")
-        nb, mu, N = len(mechanism.bodies), len(eqcids), int(controller.N)
-        if [int(e) for e in eqcids] != list(controller.eqcids):
-            raise ValueError("eqcids are not the controller's: its gains act on other constraints")
-        z = controller.zd if storage is None else (storage.z if isinstance(storage, Storage) else storage)
-        F = controller.Fd if Fτ is None else Fτ
-        on_dev = _is_device_tensor(z)
-        if not on_dev:
-            z = np.ascontiguousarray(z, dtype=np.float64)
-            if z.ndim == 3:
-                z = z[None]
-        if z.ndim != 4 or tuple(z.shape[1:]) != (N, nb, 13) or z.shape[0] < 1:
-            raise ValueError("storage must be [n][N][nb][13] = [n][%d][%d][13], one trajectory of the controller's N knots per model (got %s)" % (N, nb, tuple(z.shape)))
-        n = int(z.shape[0])
-        tables = controller.n_plant if batched else 1
-        if tables not in (1, n):
-            raise ValueError("the controller holds %d gain tables: one shared by all models, or one per model, %d" % (tables, n))
-        f_dev = _is_device_tensor(F)
-        if F is not None and not f_dev:
-            F = np.ascontiguousarray(F, dtype=np.float64)
-            if F.shape == (N, mu) or (mu == 1 and F.shape == (N,)):
-                F = np.ascontiguousarray(np.broadcast_to(F.reshape(1, N, mu), (n, N, mu)))
-        if F is not None and tuple(F.shape) != (n, N, mu):
-            raise ValueError("Fτ must be [N][mu] = [%d][%d] (shared) or [n][N][mu] = [%d][%d][%d] (got %s)" % (N, mu, n, N, mu, tuple(F.shape)))
-        if F is not None and f_dev != on_dev:
-            raise ValueError("storage and Fτ must both be host arrays or both device tensors")
-        if noise_scale is None and Wu is None and Sigma0 is None:
-            raise ValueError("none of noise_scale, Wu and Sigma0 is given: there is no covariance to propagate")
-        if noise_scale is not None and Wu is not None:
-            raise ValueError("noise_scale and Wu are both given: noise_scale IS Wu = noise_scale^2 ones((mu, mu))")
-        if noise_scale is not None:
-            Wu = float(noise_scale) ** 2 * np.ones((mu, mu))
-        if Wu is not None:
-            Wu = np.ascontiguousarray(Wu, dtype=np.float64)
-            if Wu.shape not in ((mu, mu), (n, mu, mu)):
-                raise ValueError("Wu must be [mu][mu] = [%d][%d] or a list of one per model, %d (got %s)" % (mu, mu, n, Wu.shape))
-        inv = _body_order(bodyids, nb)
-        self._to_bodyids = np.concatenate([12 * inv[m] + np.arange(12) for m in range(nb)])      # mechanism-order coordinate -> its place in the order of bodyids
-        if Sigma0 is not None:
-            Sigma0 = np.ascontiguousarray(Sigma0, dtype=np.float64)
-            if Sigma0.shape not in ((12 * nb, 12 * nb), (n, 12 * nb, 12 * nb)):
-                raise ValueError("Sigma0 must be [12 nb][12 nb] = [%d][%d] or a list of one per model, %d (got %s)" % (12 * nb, 12 * nb, n, Sigma0.shape))
-            Sigma0 = np.ascontiguousarray(Sigma0[..., self._to_bodyids, :][..., :, self._to_bodyids])
-        Qs, Rs = _pair_lists(Q, R, n, "model")
-        self.Q, self.R, _ = _scaled_pairs(Qs, Rs, bodyids, nb, mu, math.inf, mechanism.Δt)      # [n_weights][12 nb][12 nb], [n_weights][mu][mu]: scaled, mechanism body order
-        self.first_plant = (0 if plants is None else plants.first_index) if first_plant is None else int(first_plant)
-        if plants is not None:
-            plants.rows_for(self.first_plant, n)      # every model must find its plant
-        self.mechanism, self.controller, self.plants, self.n_models, self.N = mechanism, controller, plants, n, N
-        self.eqcids = [int(e) for e in eqcids]
-        self.ctrl_joints = [mechanism.joint_index(e) for e in self.eqcids]
-        self.Wu, self.Sigma0 = Wu, Sigma0
-        dev = _device_mech(mechanism)
-        self._dev = dev
-        kw = dict(Fd=F, plants=None if plants is None else plants.handle(dev), first_plant=self.first_plant, workspace_bytes=workspace_bytes)
-        zarg = z
-        if on_dev:
-            import torch
-            if z.dtype != torch.float64 or not z.is_contiguous() or (F is not None and (F.dtype != torch.float64 or not F.is_contiguous())):
-                raise ValueError("device tensors must be contiguous float64")
-            kw.update(Fd=None if F is None else F.data_ptr(), on_device=True, stream=torch.cuda.current_stream().cuda_stream)
-            zarg = z.data_ptr()
-        if batched:
-            if controller._handle.mech is not dev or not controller._handle.ptr:
-                raise ValueError("the PlantTrackingLQR was designed on another device handle of the mechanism")
-            ctrl = _BorrowedCtrl(controller._handle)
-        else:
-            ctrl = controller._ctrl_handle(dev)
+        call = _tracking_arguments(self, name="TrackingCovariance", verb="propagates noise through", noun="covariance", mechanism=mechanism, controller=controller,
+                                   bodyids=bodyids, eqcids=eqcids, Q=Q, R=R, noise_scale=noise_scale, Wu=Wu, Sigma0=Sigma0,
+                                   nothing_given="none of noise_scale, Wu and Sigma0 is given: there is no covariance to propagate", plants=plants,
+                                   first_plant=first_plant, storage=storage, Fτ=Fτ, workspace_bytes=workspace_bytes)
         try:
-            self._sigma, self.stage_cost, zstd, self.input_std, self.expected_score = _capi.value_create_covariance_tracking(
-                dev, ctrl, zarg, n, N, self.ctrl_joints, self.Q, self.R, Wu, Sigma0, **kw)
+            self._sigma, self.stage_cost, zstd, self.input_std, self.expected_score = call(_capi.value_create_covariance_tracking, self.Wu, self.Sigma0)
         finally:
-            ctrl.close()
+            call.close()
         self.state_std = np.empty_like(zstd)
         self.state_std[..., self._to_bodyids] = zstd
 
@@ -1045,6 +968,170 @@ class TrackingCovariance:
 
     def close(self):
         self._sigma.close()
+
+
+class _TrackingCall:
+    """what _tracking_arguments hands back: call(entry, *noise, **more) runs a controller entry of _capi on the checked arguments -- entry(dev, ctrl, z, n, N,
+    ctrl_joints, Q, R, *noise, Fd=, plants=, first_plant=, workspace_bytes=[, on_device=, stream=], **more); close() releases the controller handle made for it"""
+
+    def __init__(self, dev, ctrl, args, kw, z):
+        self.dev, self.ctrl, self.args, self.kw, self.z = dev, ctrl, args, kw, z      # z: the trajectories [n][N][nb][13] as checked, array or device tensor
+
+    def __call__(self, entry, *noise, **more):
+        return entry(self.dev, self.ctrl, *self.args, *noise, **self.kw, **more)
+
+    def close(self):
+        self.ctrl.close()
+
+
+def _tracking_arguments(self, *, name, verb, noun, mechanism, controller, bodyids, eqcids, Q, R, noise_scale, Wu, Sigma0, nothing_given, plants, first_plant, storage,
+                        Fτ, workspace_bytes, knot=None):
+    """The argument handling TrackingCovariance and TrackingPolicyValue share, stated once: the controller (a TrackingLQR or PlantTrackingLQR of this mechanism without
+    a controlfunction), the trajectories (its own, or storage= / Fτ=; host arrays or device tensors read in place), one table or one per model, the plants, the noise
+    (noise_scale or Wu, one or one per model), a start covariance Sigma0 in the order of bodyids, the weight lists.  nothing_given: the refusal when none of
+    noise_scale, Wu, Sigma0 is given (None: that is allowed).  Sets mechanism, controller, plants, first_plant, n_models, N, eqcids, ctrl_joints, Q, R (scaled,
+    mechanism body order), Wu, Sigma0 (mechanism body order), _to_bodyids and _dev on `self`, and returns the _TrackingCall of the device entry."""
+    if not isinstance(mechanism, Mechanism):
+        raise TypeError("%s(mechanism, controller, bodyids, eqcids, Q, R; ...)" % name)
+    if not isinstance(controller, (TrackingLQR, PlantTrackingLQR)):
+        raise ValueError("%s %s the gain rows of a TrackingLQR or PlantTrackingLQR (got %s)" % (name, verb, type(controller).__name__))
+    if controller.mechanism is not mechanism:
+        raise ValueError("the controller was made for another mechanism")
+    if getattr(controller, "controlfunction", None) is not None:
+        raise ValueError("the controller carries a controlfunction: the %s is that of the device's own tracking law (lqr_tracking.jl:63-65), not of a host closure" % noun)
+    batched = isinstance(controller, PlantTrackingLQR)
+    if plants is None and first_plant is None and batched:
+        plants, first_plant = controller.plants, controller.first_plant
+    if plants is not None and plants.mechanism is not mechanism:
+        raise ValueError("the PlantBatch was made for another mechanism")
+    nb, mu, N = len(mechanism.bodies), len(eqcids), int(controller.N)
+    if [int(e) for e in eqcids] != list(controller.eqcids):
+        raise ValueError("eqcids are not the controller's: its gains act on other constraints")
+    if knot is not None and (int(knot) != knot or not 0 <= int(knot) <= N - 1):
+        raise ValueError("knot must be a knot of the controller's trajectory, 0 .. N-1 = %d (got %s)" % (N - 1, knot))
+    z = controller.zd if storage is None else (storage.z if isinstance(storage, Storage) else storage)
+    F = controller.Fd if Fτ is None else Fτ
+    on_dev = _is_device_tensor(z)
+    if not on_dev:
+        z = np.ascontiguousarray(z, dtype=np.float64)
+        if z.ndim == 3:
+            z = z[None]
+    if z.ndim != 4 or tuple(z.shape[1:]) != (N, nb, 13) or z.shape[0] < 1:
+        raise ValueError("storage must be [n][N][nb][13] = [n][%d][%d][13], one trajectory of the controller's N knots per model (got %s)" % (N, nb, tuple(z.shape)))
+    n = int(z.shape[0])
+    tables = controller.n_plant if batched else 1
+    if tables not in (1, n):
+        raise ValueError("the controller holds %d gain tables: one shared by all models, or one per model, %d" % (tables, n))
+    f_dev = _is_device_tensor(F)
+    if F is not None and not f_dev:
+        F = np.ascontiguousarray(F, dtype=np.float64)
+        if F.shape == (N, mu) or (mu == 1 and F.shape == (N,)):
+            F = np.ascontiguousarray(np.broadcast_to(F.reshape(1, N, mu), (n, N, mu)))
+    if F is not None and tuple(F.shape) != (n, N, mu):
+        raise ValueError("Fτ must be [N][mu] = [%d][%d] (shared) or [n][N][mu] = [%d][%d][%d] (got %s)" % (N, mu, n, N, mu, tuple(F.shape)))
+    if F is not None and f_dev != on_dev:
+        raise ValueError("storage and Fτ must both be host arrays or both device tensors")
+    if nothing_given is not None and noise_scale is None and Wu is None and Sigma0 is None:
+        raise ValueError(nothing_given)
+    if noise_scale is not None and Wu is not None:
+        raise ValueError("noise_scale and Wu are both given: noise_scale IS Wu = noise_scale^2 ones((mu, mu))")
+    if noise_scale is not None:
+        Wu = float(noise_scale) ** 2 * np.ones((mu, mu))
+    if Wu is not None:
+        Wu = np.ascontiguousarray(Wu, dtype=np.float64)
+        if Wu.shape not in ((mu, mu), (n, mu, mu)):
+            raise ValueError("Wu must be [mu][mu] = [%d][%d] or a list of one per model, %d (got %s)" % (mu, mu, n, Wu.shape))
+    inv = _body_order(bodyids, nb)
+    self._to_bodyids = np.concatenate([12 * inv[m] + np.arange(12) for m in range(nb)])      # mechanism-order coordinate -> its place in the order of bodyids
+    if Sigma0 is not None:
+        Sigma0 = np.ascontiguousarray(Sigma0, dtype=np.float64)
+        if Sigma0.shape not in ((12 * nb, 12 * nb), (n, 12 * nb, 12 * nb)):
+            raise ValueError("Sigma0 must be [12 nb][12 nb] = [%d][%d] or a list of one per model, %d (got %s)" % (12 * nb, 12 * nb, n, Sigma0.shape))
+        Sigma0 = np.ascontiguousarray(Sigma0[..., self._to_bodyids, :][..., :, self._to_bodyids])
+    Qs, Rs = _pair_lists(Q, R, n, "model")
+    self.Q, self.R, _ = _scaled_pairs(Qs, Rs, bodyids, nb, mu, math.inf, mechanism.Δt)      # [n_weights][12 nb][12 nb], [n_weights][mu][mu]: scaled, mechanism body order
+    self.first_plant = (0 if plants is None else plants.first_index) if first_plant is None else int(first_plant)
+    if plants is not None:
+        plants.rows_for(self.first_plant, n)      # every model must find its plant
+    self.mechanism, self.controller, self.plants, self.n_models, self.N = mechanism, controller, plants, n, N
+    self.eqcids = [int(e) for e in eqcids]
+    self.ctrl_joints = [mechanism.joint_index(e) for e in self.eqcids]
+    self.Wu, self.Sigma0 = Wu, Sigma0
+    dev = _device_mech(mechanism)
+    self._dev = dev
+    kw = dict(Fd=F, plants=None if plants is None else plants.handle(dev), first_plant=self.first_plant, workspace_bytes=workspace_bytes)
+    zarg = z
+    if on_dev:
+        import torch
+        if z.dtype != torch.float64 or not z.is_contiguous() or (F is not None and (F.dtype != torch.float64 or not F.is_contiguous())):
+            raise ValueError("device tensors must be contiguous float64")
+        kw.update(Fd=None if F is None else F.data_ptr(), on_device=True, stream=torch.cuda.current_stream().cuda_stream)
+        zarg = z.data_ptr()
+    if batched:
+        if controller._handle.mech is not dev or not controller._handle.ptr:
+            raise ValueError("the PlantTrackingLQR was designed on another device handle of the mechanism")
+        ctrl = _BorrowedCtrl(controller._handle)
+    else:
+        ctrl = controller._ctrl_handle(dev)
+    return _TrackingCall(dev, ctrl, (zarg, n, N, self.ctrl_joints, self.Q, self.R), kw, z)
+
+
+class TrackingPolicyValue:
+    """The cost-to-go of a TRACKED run at every knot, and the price of its noise: what a tracked run is expected to cost from a perturbed start, what the nominal
+    table costs along plant n's own trajectory, which knot's noise is the expensive one, and the terminal weight of a receding-horizon caller at knot j -- the
+    adjoint of TrackingCovariance.  Knots are j = 0 .. N-1 as there.  With [A'_j | D_j] the projected model linearised at knot j (lqr_tracking.jl:88), K_j the gain
+    row of knot j (lqr_tracking.jl:63-65) and Abar_j = A'_j - D_j K_j (lqr_tracking.jl:107), the Pkp1 of lqr_tracking.jl:108 with the gain given:
+        P_{N-1} = Q,   P_j = Q + K_j' R K_j + Abar_j' P_{j+1} Abar_j,   price_j = tr(Wu D_j' P_{j+1} D_j),   j = N-2 .. knot
+    one sequential recursion on the device (cclqr_value_create_policy_tracking); models and gains never leave it.  price_j is what the noise sample injected at step
+    j + 1 (trackingLQR_triple_cartpole.jl:98) adds to the expected cost of the rest of the run: with TrackingCovariance on the same arguments,
+    sum(expected_score) = tr(P_0 Sigma0) + expected_noise_cost.
+
+    controller, storage=, Fτ=, plants, first_plant, Q, R, noise_scale, Wu, workspace_bytes: exactly as TrackingCovariance takes them; without noise_scale and Wu no
+    price is taken (noise_price and expected_noise_cost are zeros).  knot in [0, N-1]: the recursion stops there.
+
+    P(i): P_knot of model i [12 nb][12 nb], mechanism body order, read back; noise_price [n][N] (zeros below knot and at N - 1); expected_noise_cost [n]: the prices
+    of the knots j >= knot, summed from N - 2 downwards; N, n_models, knot.  predicted_cost(mechanism, tpv, z) returns V_i = Δz_i' P_knot,i Δz_i about row `knot` of
+    trajectory i.  Not a Controller: simulate(..., tpv) raises TypeError."""
+
+    def __init__(self, mechanism, controller, bodyids, eqcids, Q, R, noise_scale=None, Wu=None, plants=None, first_plant=None, storage=None, Fτ=None, knot=0,
+                 workspace_bytes=0):
+        call = _tracking_arguments(self, name="TrackingPolicyValue", verb="evaluates", noun="cost-to-go", mechanism=mechanism, controller=controller, bodyids=bodyids,
+                                   eqcids=eqcids, Q=Q, R=R, noise_scale=noise_scale, Wu=Wu, Sigma0=None, nothing_given=None, plants=plants, first_plant=first_plant,
+                                   storage=storage, Fτ=Fτ, workspace_bytes=workspace_bytes, knot=knot)
+        self.knot, self._setpoints = int(knot), None
+        try:
+            self._value, price, total = call(_capi.value_create_policy_tracking, self.Wu, knot=self.knot)
+        finally:
+            call.close()
+        self.noise_price = np.zeros((self.n_models, self.N)) if price is None else price
+        self.expected_noise_cost = np.zeros(self.n_models) if total is None else total
+        row = call.z[:, self.knot]      # the setpoints predicted_cost measures the error about; a device tensor's row is copied to the host
+        self.zd = np.ascontiguousarray(row.cpu().numpy() if _is_device_tensor(row) else row, dtype=np.float64)
+
+    def P(self, i):
+        """P_knot of model i [12 nb][12 nb], mechanism body order, read back from the device (cclqr_value_get)"""
+        return self._value.get(i)
+
+    def _value_handle(self, dev):
+        if self._value.mech is not dev or not self._value.ptr:
+            raise ValueError("the TrackingPolicyValue was evaluated on another device handle of the mechanism")
+        return self._value, False
+
+    def _ctrl_handle(self, dev, **law):
+        """a setpoint-only controller of n_models tables built from row `knot` of the trajectories: what predicted_cost measures model i's error about"""
+        if law:
+            raise TypeError("a TrackingPolicyValue is not a Controller: it holds costs-to-go, not a control law")
+        if dev is not self._dev:
+            raise ValueError("the TrackingPolicyValue was evaluated on another device handle of the mechanism")
+        if self._setpoints is None:
+            self._setpoints = _capi.CtrlHandle(dev, self.ctrl_joints, K=None, N=0, zd=self.zd, n_ctrl=self.n_models if self.n_models > 1 else 0)
+        return _BorrowedCtrl(self._setpoints)
+
+    def close(self):
+        if self._setpoints is not None:
+            self._setpoints.close()
+            self._setpoints = None
+        self._value.close()
 
 
 class Score:
@@ -1445,6 +1532,8 @@ def simulate(mechanism, tend_or_storage, controller, record=True, z0=None, fric=
         raise TypeError("a StationaryCovariance is not a Controller: simulate rolls out the controller it propagates noise through (StationaryCovariance.controller)")
     if isinstance(controller, TrackingCovariance):
         raise TypeError("a TrackingCovariance is not a Controller: simulate rolls out the controller it propagates noise through (TrackingCovariance.controller)")
+    if isinstance(controller, TrackingPolicyValue):
+        raise TypeError("a TrackingPolicyValue is not a Controller: simulate rolls out the controller it evaluates (TrackingPolicyValue.controller)")
     if isinstance(tend_or_storage, Storage):
         steps = tend_or_storage.steps
     else:
@@ -1520,10 +1609,13 @@ def predicted_cost(mechanism, controller, z0, first_instance=0, out=None):
     PolicyValue(mech, controller, ..., zd, plants=): V_i = Δz_i' P_i Δz_i with P_i the given gains' cost-to-go on plant i's model (lqr.jl:169-170 with the gain
     given) and Δz_i the error about plant i's own setpoint zd[i] -- then realised / predicted tells "outside the linear regime" from "model mismatch".  A
     StationaryPolicyValue (the same cost-to-go of a stationary gain, by doubling) is taken the same way.
+    A tracking controller keeps no cost-to-go of its own: pass a TrackingPolicyValue(mech, tracking, ..., knot=) -- V_i = Δz_i' P_knot,i Δz_i with P_knot,i the tracked
+    run's cost-to-go at that knot on model i (lqr_tracking.jl:107-108 with the gain given) and Δz_i the error about row `knot` of trajectory i.
     z0 [n_inst][nb][13]: a numpy array -> a numpy array [n_inst]; or a float64 device tensor, read in place -> a device tensor [n_inst] (out: the tensor to fill),
     the evaluation left running on the current stream."""
     if not hasattr(controller, "_value_handle"):
-        raise TypeError("predicted_cost takes an LQR, PlantLQR or LQRSweep built with keep_value=True")
+        raise TypeError("predicted_cost takes an LQR, PlantLQR or LQRSweep built with keep_value=True, a PolicyValue or StationaryPolicyValue, or -- for a "
+                        "TrackingLQR or PlantTrackingLQR -- a TrackingPolicyValue of it")
     if controller.mechanism is not mechanism:
         raise ValueError("the controller was made for another mechanism")
     import torch

@@ -57,7 +57,9 @@ extern "C" {
  * Still 202 (additive, no struct changed): the closed-loop state covariance under input noise by doubling -- cclqr_covariance_doubling, cclqr_value_create_covariance_doubling;
  * looked up the same way.  cclqr_policy_value_doubling and cclqr_value_create_policy_doubling are unchanged.
  * Still 202 (additive, no struct changed): the state covariance of a TRACKED run at every knot, a model and a gain row per knot -- cclqr_covariance_tracking, cclqr_value_create_covariance_tracking;
- * looked up the same way.  cclqr_covariance_doubling and cclqr_value_create_covariance_doubling are unchanged, their refusal of gain tables and tracking controllers included. */
+ * looked up the same way.  cclqr_covariance_doubling and cclqr_value_create_covariance_doubling are unchanged, their refusal of gain tables and tracking controllers included.
+ * Still 202 (additive, no struct changed): the cost-to-go of a TRACKED run at every knot and the price of its noise, a model and a gain row per knot -- cclqr_policy_value_tracking, cclqr_value_create_policy_tracking;
+ * looked up the same way.  cclqr_policy_value, cclqr_value_create_policy and the two tracking-covariance entries are unchanged. */
 #define CCLQR_ABI_VERSION 202
 
 #define CCLQR_REVOLUTE 0      /* EqualityConstraint(Revolute(a, b, axis; p1, p2, qoffset)),  examples/lqr_cartpole.jl:26 */
@@ -561,6 +563,44 @@ int cclqr_value_create_covariance_tracking(const cclqr_mech *m, const cclqr_plan
                                            const double *Fd, int32_t on_device, int32_t mu, const int32_t *ctrl_joint, const cclqr_ctrl *c, int32_t n_weights,
                                            const double *Q, const double *R, int32_t n_noise, const double *Wu, const double *Sigma0, int64_t workspace_bytes,
                                            double *cost, double *zstd, double *ustd, double *total, void *stream, cclqr_value **out);
+
+/* The cost-to-go of a TRACKED run at every knot, and the price of its noise (additive, Still 202, no struct changed; looked up by name): the adjoint of the tracking
+ * covariance above.  With the knots, the gain rows (lqr_tracking.jl:63-65), the models (lqr_tracking.jl:88-89) and Abar_j = A'_j - D_j K_j (lqr_tracking.jl:107) as
+ * there, the recursion is the Pkp1 of lqr_tracking.jl:108 with the gain of line 98 GIVEN instead of solved for:
+ *     P_{N-1} = Q
+ *     P_j     = Q + K_j' R K_j + Abar_j' P_{j+1} Abar_j      j = N-2 .. 0
+ *     price_j = tr(Wu D_j' P_{j+1} D_j)                      j = 0 .. N-2,  price_{N-1} = 0
+ * Δz' P_j Δz is what the rest of the tracked run costs from a deviation Δz at knot j; price_j is what the noise sample w ~ (0, Wu) injected at step j + 1
+ * (examples/trackingLQR_triple_cartpole.jl:98) adds to it in expectation.  With Σ_0 and total of cclqr_covariance_tracking on the same arrays:
+ *     total[0] + total[1] = tr(P_0 Σ_0) + sum_j price_j.
+ * Q, R, Wu are used as written: nothing assumes symmetry.  N = 1: P = Q, and no model is read.  One sequential recursion on the device, two mx^3 products per step on
+ * the fp64 matrix pipe.
+ * cclqr_policy_value_tracking -- HOST pointers, caller models: A, Bu, Bl, G, nlin, K, n_gains, nK, Q, R, n_weights exactly as cclqr_covariance_tracking takes them (Q and R
+ * are required here); Wu [n_noise][mu][mu] with n_noise = 1 or nprob, or NULL: then price and noise_total must be NULL.  Outputs, each written only if not NULL:
+ * P [nprob][mx][mx] = P_0; P_all [nprob][N][mx][mx]; price [nprob][N]; noise_total [nprob] = the prices summed in the order the recursion produces them, j = N-2 down to
+ * 0.  opts: only `path` is read (0 / 1: one workgroup per problem where the shape fits -- the shapes of cclqr_covariance_tracking --, 2: every step as device-wide
+ * launches); bf16_terms != 0 is CCLQR_EINVAL.  Results do not depend on the batch a problem is in, nor on whether gains / weights / noise are shared, nor on which
+ * outputs are asked for.
+ * CCLQR_EINVAL before anything is allocated or launched, with the outputs untouched: sizes below 1 (mu, ml below 0), nlin neither 1 nor N - 1, n_gains / n_weights / n_noise
+ * neither 1 nor nprob, nK neither 1 nor N - 1, Wu with mu == 0, price or noise_total without Wu, Q / R NULL, more than 65535 problems, path outside 0 .. 2.
+ * A singular G*Bλ at a knot the recursion reaches is CCLQR_ESINGULAR, naming problem and knot; the outputs are filled for the problems before it. */
+int cclqr_policy_value_tracking(int32_t nprob, int32_t mx, int32_t mu, int32_t ml, int32_t nlin, const double *A, const double *Bu, const double *Bl, const double *G,
+                                int32_t n_gains, int32_t nK, const double *K, int32_t n_weights, const double *Q, const double *R, int32_t n_noise, const double *Wu,
+                                int32_t N, double *P, double *P_all, double *price, double *noise_total, const cclqr_riccati_opts *opts);
+
+/* cclqr_value_create_policy_tracking -- the same recursion (lqr_tracking.jl:63, 88, 107, 108 under the noise of trackingLQR_triple_cartpole.jl:98) for a CONTROLLER on a
+ * mechanism's plants (Still 202), by the host sequence of cclqr_value_create_covariance_tracking: the same trajectories zd / Fd (host, or device arrays read in place on
+ * `stream`), plants, gain gather, chunking within workspace_bytes (the prices are counted per problem, the weights and Wu once), refusals and error naming.  The
+ * recursion runs from knot N - 1 down to `knot` in [0, N-1]: *out is a cclqr_value of n_models tables holding P_knot, in the order in which cclqr_value_create_policy
+ * takes Q and returns P, for cclqr_value_get and cclqr_value_eval as they stand -- the terminal weight of a receding-horizon caller at that knot, and with knot = 0 the
+ * expected cost of the whole tracked run from a perturbed start.  price [n_models][N] (zeros below `knot` and at N - 1) and noise_total [n_models] (the prices of the
+ * knots j >= knot, summed from N - 2 downwards) are HOST arrays, each written only if not NULL; both must be NULL when Wu is.  linearsystem runs at ALL knots 0 .. N-2
+ * whatever `knot`; a singular G*Bλ below `knot` is not reached and is no error.
+ * Refused as cclqr_value_create_covariance_tracking refuses, and: Q / R NULL, price or noise_total without Wu, knot outside 0 .. N-1 -- CCLQR_EINVAL. */
+int cclqr_value_create_policy_tracking(const cclqr_mech *m, const cclqr_plants *plants, int64_t first_plant, int32_t n_models, int32_t N, const double *zd, const double *Fd,
+                                       int32_t on_device, int32_t mu, const int32_t *ctrl_joint, const cclqr_ctrl *c, int32_t n_weights, const double *Q, const double *R,
+                                       int32_t n_noise, const double *Wu, int32_t knot, int64_t workspace_bytes, double *price, double *noise_total, void *stream,
+                                       cclqr_value **out);
 
 /* The stationary LQR gain by doubling the Riccati map (additive, Still 202, no struct changed; looked up by name).  LQR{T,Inf} steps dlqr Ntemp = 10 s / Δt times and
  * keeps Ku[1] (src/control/lqr.jl:25-27, 39-43), converged or not.  In projected form a backward step of dlqr (lqr.jl:141-184, its step lqr.jl:151-170) is

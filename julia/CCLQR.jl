@@ -670,6 +670,51 @@ function value_create_covariance_tracking(h::MechHandle, p::Union{PlantsHandle,N
     return obj, cost, zs, us, tot
 end
 
+"The cost-to-go of a TRACKED run at every knot and the price of its noise (cclqr_policy_value_tracking): P_{N-1} = Q, P_j = Q + K_j' R K_j + Abar_j' P_{j+1} Abar_j
+ (lqr_tracking.jl:107-108 with the gain row of knot j given, lqr_tracking.jl:63, 88), price_j = tr(Wu D_j' P_{j+1} D_j) for w ~ (0, Wu) on the inputs
+ (trackingLQR_triple_cartpole.jl:98).  Models, gains and weights as covariance_tracking takes them; Wus: one per problem, one shared, or empty (no price).
+ Returns (P[p] = P_0, price N x np, noise_total np)."
+function policy_value_tracking(As::Vector, Bus::Vector, Bλs::Vector, Gs::Vector, Ks::Vector, Qs::Vector, Rs::Vector, Wus::Vector, N::Integer; path = 0)
+    np = length(As); nlin = length(As[1])
+    mx, mu, ml = size(As[1][1], 1), size(Bus[1][1], 2), size(Bλs[1][1], 2)
+    nK = (mu == 0 || isempty(Ks)) ? 1 : length(Ks[1])                # no inputs: no gains, Ks may be empty
+    length(Qs) == length(Rs) || throw(AssertionError("Qs and Rs must hold the same number of weight pairs"))
+    rowmajor(Ms) = reduce(vcat, [vec(permutedims(Matrix{Float64}(M))) for M in Ms]; init = Float64[])
+    nested(Vs) = reduce(vcat, [rowmajor(V) for V in Vs]; init = Float64[])
+    P = zeros(mx * mx * np); price = zeros(N, np); tot = zeros(np)
+    opts = Int32[path, 0, 0, 0]                                      # cclqr_riccati_opts: only `path` is read
+    wu = rowmajor(Wus)
+    priced = !isempty(Wus)
+    GC.@preserve wu price tot check(ccall((:cclqr_policy_value_tracking, lib), Cint,
+                (Int32, Int32, Int32, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int32, Int32, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64},
+                 Int32, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}),
+                np, mx, mu, ml, nlin, nested(As), nested(Bus), nested(Bλs), nested(Gs), Int32(max(length(Ks), 1)), Int32(nK), nested(Ks), Int32(length(Qs)), rowmajor(Qs),
+                rowmajor(Rs), Int32(max(length(Wus), 1)), priced ? pointer(wu) : Ptr{Float64}(C_NULL), N, P, Ptr{Float64}(C_NULL),
+                priced ? pointer(price) : Ptr{Float64}(C_NULL), priced ? pointer(tot) : Ptr{Float64}(C_NULL), opts))
+    P3 = reshape(P, mx, mx, np)                                      # C layout [np][mx][mx]: row-major, so transposed here
+    [permutedims(P3[:, :, p]) for p = 1:np], price, tot
+end
+"The cost-to-go above for controller `c`'s gain rows along n trajectories on a mechanism's plants, down to `knot` (0-based, cclqr_value_create_policy_tracking): zd, Fd,
+ Q, R, Wu as value_create_covariance_tracking takes them (Wu nothing: no price).  Returns (ValueHandle of n tables holding P_knot, price N x n, noise_total n)."
+function value_create_policy_tracking(h::MechHandle, p::Union{PlantsHandle,Nothing}, n::Int, N::Int, zd::Array{Float64}, ctrl_joint::Vector{Int32}, c::CtrlHandle,
+                                      n_weights::Int, Q::Vector{Float64}, R::Vector{Float64}, n_noise::Int, Wu;
+                                      Fd = nothing, first_plant = 0, knot = 0, workspace_bytes = 0)
+    mu = length(ctrl_joint)
+    val = Ref{Ptr{Cvoid}}(C_NULL)
+    price = zeros(N, n); tot = zeros(n)
+    fd = Fd === nothing ? Ptr{Float64}(C_NULL) : pointer(Fd)
+    wu = Wu === nothing ? Ptr{Float64}(C_NULL) : pointer(Wu)
+    GC.@preserve Fd Wu price tot check(ccall((:cclqr_value_create_policy_tracking, lib), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Int32, Int32, Ptr{Int32}, Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}, Int32,
+                 Ptr{Float64}, Int32, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Cvoid}, Ref{Ptr{Cvoid}}),
+                h.ptr, p === nothing ? C_NULL : p.ptr, first_plant, Int32(n), Int32(N), zd, fd, Int32(0), Int32(mu), ctrl_joint, c.ptr, Int32(n_weights), Q, R,
+                Int32(n_noise), wu, Int32(knot), Int64(workspace_bytes), Wu === nothing ? Ptr{Float64}(C_NULL) : pointer(price),
+                Wu === nothing ? Ptr{Float64}(C_NULL) : pointer(tot), C_NULL, val))
+    obj = ValueHandle(val[], h)
+    finalizer(o -> ccall((:cclqr_value_destroy, lib), Cint, (Ptr{Cvoid},), o.ptr), obj)
+    return obj, price, tot
+end
+
 "The stationary LQR gain by doubling the Riccati map (cclqr_riccati_doubling): n backward steps of dlqr (lqr.jl:141-184) are a triple (A_n, G_n, H_n), two triples compose
  in one pivoted solve and five products, and the one gain LQR{T,Inf} keeps (lqr.jl:25-27, 39-43) is reached in log2 n compositions.  Qs, Rs: one exactly symmetric pair,
  or one per problem.  N >= 2: Ku[1] and the last Pkp1 of dlqr(.., N) with tol = 0; N == 0: level by level to convergence.  Returns (K[p], P[p], levels[p], reason[p]
