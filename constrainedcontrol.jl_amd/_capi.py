@@ -23,7 +23,8 @@ EXPORTS = ["cclqr_last_error", "cclqr_version", "cclqr_device_count", "cclqr_set
            "cclqr_riccati_value", "cclqr_ctrl_create_lqr_batch_value", "cclqr_value_create", "cclqr_value_get", "cclqr_value_destroy", "cclqr_value_eval",
            "cclqr_policy_value", "cclqr_value_create_policy", "cclqr_policy_value_doubling", "cclqr_value_create_policy_doubling",
            "cclqr_riccati_doubling", "cclqr_ctrl_create_lqr_batch_doubling", "cclqr_covariance_doubling", "cclqr_value_create_covariance_doubling",
-           "cclqr_covariance_tracking", "cclqr_value_create_covariance_tracking", "cclqr_policy_value_tracking", "cclqr_value_create_policy_tracking"]
+           "cclqr_covariance_tracking", "cclqr_value_create_covariance_tracking", "cclqr_policy_value_tracking", "cclqr_value_create_policy_tracking",
+           "cclqr_rollout_ensemble_ws_bytes", "cclqr_rollout_ensemble"]
 ABI_VERSION = 202     # include/cclqr.h CCLQR_ABI_VERSION: the structs below mirror that header (verified field by field against cclqr_abi_layout at load time)
 ROLLOUT_NO_ALLOC = 1  # cclqr_rollout_opts.flags: the call may neither allocate nor synchronise (a hipGraph capture is open on the device)
 ROLLOUT_CARRY_STATUS = 4  # ... `status` is read and written: an instance lost in an earlier launch stays frozen, the others merge this launch's result into it
@@ -610,39 +611,87 @@ def default_chunk_steps(n_inst, nb, steps, slab_bytes=1 << 30):
     return max(1, min(int(steps), int(slab_bytes) // max(1, int(n_inst) * int(nb) * 13 * 8)))
 
 
-def rollout_scored(mech, ctrl, score, z0, steps, chunk_steps, noise=None, first_instance=0, plants=None, newton_mode=0, newton_eps_alone=0.0, flags=0, traj_out=None):
+ENSEMBLE_MAX_COV = 64   # listed steps of one cclqr_rollout_ensemble call
+
+
+def rollout_ensemble_ws_bytes(mech, mu, n_inst, steps, n_cov):
+    """cclqr_rollout_ensemble_ws_bytes: bytes of device workspace one cclqr_rollout_ensemble call of these sizes needs"""
+    out = C.c_size_t(0)
+    check(lib().cclqr_rollout_ensemble_ws_bytes(mech.ptr, C.c_int32(int(mu)), C.c_int64(int(n_inst)), C.c_int32(int(steps)), C.c_int32(int(n_cov)), C.byref(out)))
+    return int(out.value)
+
+
+def rollout_ensemble(mech, ctrl, n_inst, steps, k0, traj_ptr, mean_ptr, m2_ptr, ws_ptr, ws_bytes, cov_steps=(), cov_ptr=0, stream=0, first_instance=0):
+    """cclqr_rollout_ensemble on device addresses (asynchronous on `stream`): per row of the slab traj [n_inst][steps][nb][13] the mean and the centred sum of squares
+    of (Δz, Δu) across the instances into mean / m2 [steps][12 nb + mu], and for the absolute steps cov_steps (host integers within k0 .. k0 + steps - 1) the centred
+    co-moment matrices of Δz into cov [len(cov_steps)][12 nb][12 nb]"""
+    vp = lambda p: C.c_void_p(int(p)) if p else None
+    cs = i32(list(cov_steps)).reshape(-1)
+    check(lib().cclqr_rollout_ensemble(mech.ptr, ctrl.ptr, C.c_int64(int(n_inst)), C.c_int32(int(steps)), C.c_int32(int(k0)), C.c_int64(int(first_instance)),
+                                       vp(traj_ptr), vp(mean_ptr), vp(m2_ptr), C.c_int32(len(cs)), _i(cs) if len(cs) else None, vp(cov_ptr),
+                                       vp(ws_ptr), C.c_size_t(int(ws_bytes)), vp(stream)))
+
+
+def rollout_scored(mech, ctrl, score, z0, steps, chunk_steps, noise=None, first_instance=0, plants=None, newton_mode=0, newton_eps_alone=0.0, flags=0, traj_out=None,
+                   ensemble=None):
     """A horizon rolled out AND scored on the device without its trajectory ever existing: ceil(steps / chunk_steps) launches of cclqr_rollout_ex (plants:
     cclqr_rollout_plants) into ONE slab of chunk_steps rows, each followed on the same stream by cclqr_rollout_score.  The state, the multipliers, the status
     (ROLLOUT_CARRY_STATUS), the PID state and the noise column travel from launch to launch, so the result is bitwise that of one launch.
     noise [n_inst][steps] injected samples or None.  traj_out: a numpy array [n_inst][steps][nb][13] that receives the slabs (the recorded run), or None.
-    Returns (zT, status, score [n_inst][SCORE_LEN])."""
+    score: a ScoreHandle, or None = no score pass.  ensemble: None, or (mu, cov_rows) -- cclqr_rollout_ensemble runs behind every launch on the same slab, and the
+    0-based rows of the horizon in cov_rows (row j = step j + 1) get their co-moment matrix, each from the chunk that holds it.
+    Returns (zT, status, score [n_inst][SCORE_LEN] or None), with ensemble a fourth element (mean [steps][12 nb + mu], M2 the same, {row: C [12 nb][12 nb]})."""
     import torch
     nb, ne = mech.tables.nb, mech.tables.ne
     z0 = f64(z0).reshape(-1, nb, 13)
     n = z0.shape[0]
     plan = chunk_plan(steps, chunk_steps)
     rows = plan[0][1]
+    if ensemble is not None:      # (before anything touches the device)
+        mu, cov_rows = int(ensemble[0]), sorted({int(j) for j in ensemble[1]})
+        if cov_rows and (cov_rows[0] < 0 or cov_rows[-1] >= steps):
+            raise ValueError("cov_knots must lie in 0 .. steps - 1 = %d (got %s)" % (steps - 1, cov_rows))
+        cov_of = [[j + 1 for j in cov_rows if k0 <= j + 1 < k0 + s] for k0, s in plan]
+        if max(len(c) for c in cov_of) > ENSEMBLE_MAX_COV:
+            raise ValueError("more than %d cov_knots fall into one chunk: lower chunk_steps" % ENSEMBLE_MAX_COV)
     td = torch.device("cuda", torch.cuda.current_device())
     z = torch.from_numpy(z0).to(td)
     zn = torch.empty_like(z)
     lam = torch.zeros((n, 5 * ne), dtype=torch.float64, device=td)
     st = torch.zeros(n, dtype=torch.int32, device=td)
     pid = torch.zeros((n, ne, 2), dtype=torch.float64, device=td)
-    sc = torch.zeros((n, SCORE_LEN), dtype=torch.float64, device=td)
+    sc = None if score is None else torch.zeros((n, SCORE_LEN), dtype=torch.float64, device=td)
     slab = torch.empty((n, rows, nb, 13), dtype=torch.float64, device=td)
     dnoise = None if noise is None else torch.from_numpy(f64(noise).reshape(n, steps)).to(td)
     stream = torch.cuda.current_stream().cuda_stream
-    for k0, s in plan:
+    if ensemble is not None:
+        nx, mx, most = 12 * nb + mu, 12 * nb, max(1, max(len(c) for c in cov_of))
+        emean = torch.empty((steps, nx), dtype=torch.float64, device=td)
+        em2 = torch.empty((steps, nx), dtype=torch.float64, device=td)
+        ecov = torch.empty((max(1, len(cov_rows)), mx, mx), dtype=torch.float64, device=td)
+        ws_bytes = rollout_ensemble_ws_bytes(mech, mu, n, rows, most if cov_rows else 0)
+        ws = torch.empty(ws_bytes // 8 + 1, dtype=torch.float64, device=td)
+        cov_done = 0
+    for ci, (k0, s) in enumerate(plan):
         # the noise array is indexed by the absolute step k - 1: its base stays where it is whatever k0 is
         rollout_dev(mech, ctrl, n, s, k0, z.data_ptr(), lam.data_ptr(), 0 if dnoise is None else dnoise.data_ptr(), steps, slab.data_ptr(), zn.data_ptr(),
                     st.data_ptr(), stream, first_instance=first_instance, pid_state=pid.data_ptr(), newton_mode=newton_mode, newton_eps_alone=newton_eps_alone,
                     flags=flags | ROLLOUT_CARRY_STATUS, plants=plants)
-        rollout_score(mech, ctrl, score, n, s, k0, slab.data_ptr(), sc.data_ptr(), stream, first_instance=first_instance)
+        if score is not None:
+            rollout_score(mech, ctrl, score, n, s, k0, slab.data_ptr(), sc.data_ptr(), stream, first_instance=first_instance)
+        if ensemble is not None:      # (a chunk's statistics are complete: every instance of its steps is in the slab)
+            rollout_ensemble(mech, ctrl, n, s, k0, slab.data_ptr(), emean[k0 - 1:].data_ptr(), em2[k0 - 1:].data_ptr(), ws.data_ptr(), ws_bytes,
+                             cov_steps=cov_of[ci], cov_ptr=ecov[cov_done:].data_ptr() if cov_of[ci] else 0, stream=stream, first_instance=first_instance)
+            cov_done += len(cov_of[ci])
         if traj_out is not None:      # (a launch of s < rows steps fills the slab as [n][s][nb][13] from its base)
             traj_out[:, k0 - 1:k0 - 1 + s] = slab.reshape(-1)[:n * s * nb * 13].reshape(n, s, nb, 13).cpu().numpy()
         z, zn = zn, z
     torch.cuda.current_stream().synchronize()
-    return z.cpu().numpy(), st.cpu().numpy(), sc.cpu().numpy()
+    out = (z.cpu().numpy(), st.cpu().numpy(), None if sc is None else sc.cpu().numpy())
+    if ensemble is None:
+        return out
+    covs = ecov.cpu().numpy()
+    return out + ((emean.cpu().numpy(), em2.cpu().numpy(), {j: covs[q] for q, j in enumerate(cov_rows)}),)
 
 
 def linearize(mech, zd, ctrl_joint, Fd=None, plants=None, first_plant=0):

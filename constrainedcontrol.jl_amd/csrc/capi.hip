@@ -11,6 +11,7 @@ static_assert(CCLQR_NEWTON_MAXIT == NEWTON_MAXIT, "include/cclqr.h and cclqr_new
 #include "cclqr_score.h"
 static_assert(CCLQR_SCORE_LEN == CCLQR_SCORE_LEN_, "include/cclqr.h and cclqr_score.h disagree on the length of a score");
 #include "cclqr_value.h"
+#include "cclqr_ensemble.h"
 #include <math.h>
 #include <stdio.h>
 #include <string.h>
@@ -1241,6 +1242,58 @@ extern "C" int cclqr_rollout_score(const cclqr_mech* m, const cclqr_ctrl* c, con
     a.M = m->dev; a.C = c->dev; a.Qb = s->Qb_dev; a.R = s->R_dev; a.settle_tol = s->settle_tol; a.nb = m->nb; a.mu = s->mu;
     a.n_inst = n_inst; a.steps = steps; a.k0 = k0; a.inst0 = first_instance; a.traj = traj; a.score = score;
     HIPCHK(launch_score(a, (hipStream_t)stream));
+    return CCLQR_OK;
+}
+
+// ---- the statistics of a slab across its instances (ensemble.hip).  Nothing is allocated, copied or synchronised: the listed steps travel in the kernels' arguments
+// and everything between the kernels lies in the caller's workspace
+static int ensemble_sizes_ok(const cclqr_mech* m, int32_t mu, int64_t n_inst, int32_t steps, int32_t n_cov) {
+    if (mu < 0 || mu > m->nj) return fail(CCLQR_EINVAL, "mu = " + std::to_string(mu) + " is not a number of controlled joints of this mechanism (0 .. " + std::to_string(m->nj) + ")");
+    if (n_inst < 1) return fail(CCLQR_EINVAL, "n_inst = " + std::to_string(n_inst) + ": an ensemble holds at least one instance");
+    if (steps < 1) return fail(CCLQR_EINVAL, "need steps >= 1 (got " + std::to_string(steps) + ")");
+    if (n_cov < 0 || n_cov > ENS_MAX_COV) return fail(CCLQR_EINVAL, "n_cov = " + std::to_string(n_cov) + ": one call takes 0 .. " + std::to_string(ENS_MAX_COV) + " listed steps");
+    if (ens_tiles(n_inst) * steps > 0x7fffffffLL || ens_splits(n_inst) > 65535) return fail(CCLQR_EINVAL, "n_inst x steps exceeds one launch: call with fewer steps");
+    return CCLQR_OK;
+}
+extern "C" int cclqr_rollout_ensemble_ws_bytes(const cclqr_mech* m, int32_t mu, int64_t n_inst, int32_t steps, int32_t n_cov, size_t* bytes) {
+    if (!m || !bytes) return fail(CCLQR_EINVAL, "null argument");
+    TRY(ensemble_sizes_ok(m, mu, n_inst, steps, n_cov));
+    *bytes = sizeof(double) * ens_ws_doubles(m->nb, mu, n_inst, steps, n_cov);
+    return CCLQR_OK;
+}
+extern "C" int cclqr_rollout_ensemble(const cclqr_mech* m, const cclqr_ctrl* c, int64_t n_inst, int32_t steps, int32_t k0, int64_t first_instance, const double* traj,
+                                      double* mean, double* m2, int32_t n_cov, const int32_t* cov_steps, double* cov, void* ws, size_t ws_bytes, void* stream) {
+    if (!m || !c) return fail(CCLQR_EINVAL, "null argument");
+    TRY(check_device(m));
+    if (c->nb != m->nb || c->device != m->device) return fail(CCLQR_EINVAL, "the controller was created for another mechanism or device");
+    TRY(ensemble_sizes_ok(m, c->host.mu, n_inst, steps, n_cov));
+    if (k0 < 1 || first_instance < 0) return fail(CCLQR_EINVAL, "need k0 >= 1 and first_instance >= 0 (got k0 = " + std::to_string(k0) + ", first_instance = " + std::to_string(first_instance) + ")");
+    if (!c->zd_dev || c->host.nsp < 1) return fail(CCLQR_EINVAL, "the controller has no setpoint table");
+    if (c->host.n_ctrl > 1 && first_instance + n_inst > c->host.n_ctrl)
+        return fail(CCLQR_EINVAL, "first_instance + n_inst = " + std::to_string(first_instance + n_inst) + " exceeds the controller's n_ctrl = " + std::to_string(c->host.n_ctrl) + " tables");
+    if (!traj || !mean || !m2 || (n_cov > 0 && (!cov_steps || !cov))) return fail(CCLQR_EINVAL, "null argument");
+    for (int q = 0; q < n_cov; q++)
+        if (cov_steps[q] < k0 || cov_steps[q] > k0 + steps - 1)
+            return fail(CCLQR_EINVAL, "cov_steps[" + std::to_string(q) + "] = " + std::to_string(cov_steps[q]) + " lies outside the launch's steps " + std::to_string(k0) + " .. " + std::to_string(k0 + steps - 1));
+    const int nb = m->nb, mu = c->host.mu;
+    const size_t need = sizeof(double) * ens_ws_doubles(nb, mu, n_inst, steps, n_cov);
+    if (!ws) return fail(CCLQR_EINVAL, "null workspace: cclqr_rollout_ensemble_ws_bytes says how large it must be (" + std::to_string(need) + " bytes)");
+    if (ws_bytes < need) return fail(CCLQR_EINVAL, "workspace too small: " + std::to_string(ws_bytes) + " bytes given, " + std::to_string(need) + " needed (cclqr_rollout_ensemble_ws_bytes)");
+    EnsArgs a;
+    memset(&a, 0, sizeof(a));
+    a.M = m->dev; a.C = c->dev; a.nb = nb; a.mu = mu; a.n_inst = n_inst; a.steps = steps; a.k0 = k0; a.inst0 = first_instance; a.traj = traj;
+    a.part = (double*)ws;
+    a.dzrows = n_cov > 0 ? a.part + ens_ws_part_doubles(nb, mu, n_inst, steps) : nullptr;
+    a.n_cov = n_cov;
+    for (int q = 0; q < n_cov; q++) a.cov_row[q] = cov_steps[q] - k0;
+    HIPCHK(launch_ensemble(a, mean, m2, (hipStream_t)stream));
+    if (n_cov == 0) return CCLQR_OK;
+    EnsCovArgs v;
+    memset(&v, 0, sizeof(v));
+    v.mx = 12 * nb; v.tm = (v.mx + 31) / 32; v.n_inst = n_inst; v.nsplit = (int)ens_splits(n_inst); v.stride = ens_coords(nb, mu);
+    v.dzrows = a.dzrows; v.mean = mean; v.cpart = a.dzrows + ens_ws_rows_doubles(nb, n_inst, n_cov); v.cov = cov;
+    for (int q = 0; q < n_cov; q++) v.cov_row[q] = a.cov_row[q];
+    HIPCHK(launch_ensemble_cov(v, n_cov, (hipStream_t)stream));
     return CCLQR_OK;
 }
 

@@ -185,6 +185,21 @@ __device__ __forceinline__ void tile32_product(const Tile32& t, int mx, const do
         [&](int kk, int h) { return t.iok[h] ? (ta ? A[(size_t)kk * mx + t.i0 + 16 * h + li] : A[(size_t)(t.i0 + 16 * h + li) * mx + kk]) : 0.0; },
         [&](int kk, int h) { return t.jok[h] ? (tb ? B[(size_t)(t.j0 + 16 * h + li) * mx + kk] : B[(size_t)kk * mx + t.j0 + 16 * h + li]) : 0.0; }, red);
 }
+// the tile at (i0, j0) of Xc' Xc into red, Xc = the K rows of X [K][mx] (global memory) less the row vector mean [mx]: a block of a centred Gram (co-moment) matrix
+// (ensemble.hip).  The centring and the edge masking are the operand lambdas'; a K-split of a longer sum hands in its own rows
+__device__ __forceinline__ void tile32_gram_centred(int i0, int j0, int mx, int K, const double* X, const double* mean, double (*red)[1024]) {
+    const int li = threadIdx.x & 15;
+    bool iok[2], jok[2];
+    double mi[2], mj[2];
+#pragma unroll
+    for (int h = 0; h < 2; h++) {
+        iok[h] = i0 + 16 * h + li < mx; jok[h] = j0 + 16 * h + li < mx;
+        mi[h] = iok[h] ? mean[i0 + 16 * h + li] : 0.0; mj[h] = jok[h] ? mean[j0 + 16 * h + li] : 0.0;
+    }
+    tile_mfma_splitk(K,
+        [&](int kk, int h) { return iok[h] ? X[(size_t)kk * mx + i0 + 16 * h + li] - mi[h] : 0.0; },
+        [&](int kk, int h) { return jok[h] ? X[(size_t)kk * mx + j0 + 16 * h + li] - mj[h] : 0.0; }, red);
+}
 // element e of the tile: the four wavefronts' partial sums in wave order
 __device__ __forceinline__ double tile32_sum(const double (*red)[1024], int e) { return ((red[0][e] + red[1][e]) + red[2][e]) + red[3][e]; }
 // Ct = (A' B)' for the tile: the product, stored transposed with consecutive threads on consecutive i

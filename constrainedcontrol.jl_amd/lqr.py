@@ -877,6 +877,7 @@ class Storage:
         self.status = status
         self.zT = zT
         self.score = None          # [n_inst][4] = Jx, Ju, peak, last_out of simulate(..., score=)
+        self.ensemble = None       # EnsembleStats of simulate(..., ensemble=): the batch across its instances, per step
 
     def instance(self, n):
         one = Storage(self.steps, self.nb, 1, self.z[n:n + 1], None if self.status is None else self.status[n:n + 1],
@@ -1164,6 +1165,90 @@ class Score:
 
     def _handle(self, dev):
         return _capi.ScoreHandle(dev, self.Qb, self.R, self.settle_tol)
+
+
+class Ensemble:
+    """What a batch is summarised by ACROSS its instances: per step the mean and the spread of every coordinate of the error Δz of lqr.jl:92-103 and of the feedback
+    command Δu = -K[k] Δz, and at the knots named in cov_knots the full covariance of Δz, evaluated on the device from the rollout's own states
+    (cclqr_rollout_ensemble) -- the measurement TrackingCovariance / StationaryCovariance predict.  simulate(..., ensemble=Ensemble(mechanism, cov_knots=(j, ...)))
+    returns a Storage with .ensemble, an EnsembleStats; row j of it (0-based, the state the law saw at step j + 1) is knot j of TrackingCovariance."""
+
+    def __init__(self, mechanism, cov_knots=()):
+        if not isinstance(mechanism, Mechanism):
+            raise TypeError("Ensemble(mechanism, cov_knots=())")
+        knots = [int(j) for j in cov_knots]
+        if any(j < 0 for j in knots) or any(int(j) != j for j in cov_knots):
+            raise ValueError("cov_knots are 0-based knots of the run: whole numbers >= 0")
+        self.mechanism = mechanism
+        self.cov_knots = tuple(sorted(set(knots)))
+
+
+class EnsembleStats:
+    """The statistics of `count` instances at every step of a run: mean [steps][12 nb] and the centred sums of squares M2 of Δz (mechanism body order), input_mean /
+    input M2 [steps][mu] of Δu, and the centred co-moment matrices C[j] [12 nb][12 nb] of the knots that were asked for.  var / std are about the ensemble mean,
+    rms / second_moment about the setpoint: sqrt((M2 + n mean^2) / n) is what diag Σ_j of a covariance prediction with zero-mean error is compared with."""
+
+    def __init__(self, count, mean, M2, input_mean, input_M2, C=None):
+        self.count = int(count)
+        self.mean, self.M2 = np.asarray(mean, dtype=np.float64), np.asarray(M2, dtype=np.float64)
+        self.input_mean, self.input_M2 = np.asarray(input_mean, dtype=np.float64), np.asarray(input_M2, dtype=np.float64)
+        self.C = {} if C is None else {int(j): np.asarray(c, dtype=np.float64) for j, c in C.items()}
+
+    def var(self, ddof=0):
+        return self.M2 / (self.count - ddof)
+
+    def input_var(self, ddof=0):
+        return self.input_M2 / (self.count - ddof)
+
+    std = property(lambda self: np.sqrt(self.var()))
+    input_std = property(lambda self: np.sqrt(self.input_var()))
+    rms = property(lambda self: np.sqrt((self.M2 + self.count * self.mean ** 2) / self.count))
+    input_rms = property(lambda self: np.sqrt((self.input_M2 + self.count * self.input_mean ** 2) / self.count))
+
+    def _comoment(self, j):
+        if int(j) not in self.C:
+            raise KeyError("knot %d is not among the cov_knots of this run (%s)" % (int(j), sorted(self.C)))
+        return self.C[int(j)]
+
+    def cov(self, j, ddof=0):
+        """covariance of Δz at knot j about the ensemble mean, [12 nb][12 nb]"""
+        return self._comoment(j) / (self.count - ddof)
+
+    def second_moment(self, j):
+        """E[Δz Δz'] at knot j, about the setpoint: what Σ_j predicts"""
+        m = self.mean[int(j)]
+        return (self._comoment(j) + self.count * np.outer(m, m)) / self.count
+
+    def merge(self, other):
+        """the statistics of this ensemble and `other` together (the shards of dist.shard, on the host): the pairwise formula of Chan, Golub and LeVeque on
+        (count, mean, M2, C).  An empty side (count 0) leaves the other's bits.  Co-moments are kept for the knots both sides hold."""
+        if not isinstance(other, EnsembleStats):
+            raise TypeError("EnsembleStats.merge takes an EnsembleStats")
+        if other.count == 0:
+            return EnsembleStats(self.count, self.mean, self.M2, self.input_mean, self.input_M2, self.C)
+        if self.count == 0:
+            return EnsembleStats(other.count, other.mean, other.M2, other.input_mean, other.input_M2, other.C)
+        if self.mean.shape != other.mean.shape or self.input_mean.shape != other.input_mean.shape:
+            raise ValueError("the two ensembles differ in steps or coordinates")
+        na, nb = float(self.count), float(other.count)
+        n = na + nb
+
+        def both(ma, qa, mb, qb):
+            d = mb - ma
+            return ma + d * (nb / n), (qa + qb) + d * d * (na * nb / n)
+
+        mean, M2 = both(self.mean, self.M2, other.mean, other.M2)
+        imean, iM2 = both(self.input_mean, self.input_M2, other.input_mean, other.input_M2)
+        C = {}
+        for j in sorted(set(self.C) & set(other.C)):
+            d = other.mean[j] - self.mean[j]
+            C[j] = (self.C[j] + other.C[j]) + np.outer(d, d) * (na * nb / n)
+        return EnsembleStats(self.count + other.count, mean, M2, imean, iM2, C)
+
+    @staticmethod
+    def empty(steps, mx, mu, cov_knots=()):
+        """the ensemble of no instances: the identity of merge"""
+        return EnsembleStats(0, np.zeros((steps, mx)), np.zeros((steps, mx)), np.zeros((steps, mu)), np.zeros((steps, mu)), {int(j): np.zeros((mx, mx)) for j in cov_knots})
 
 
 class OpenLoop(Controller):
@@ -1509,7 +1594,7 @@ def _simulate_device_closure(mechanism, steps, controller, record, z0):
 
 
 def simulate(mechanism, tend_or_storage, controller, record=True, z0=None, fric=None, noise=None, noise_scale=None, noise_seed=None,
-             first_instance=0, plants=None, score=None, chunk_steps=None):
+             first_instance=0, plants=None, score=None, chunk_steps=None, ensemble=None):
     """simulate!(mechanism, tend::Real | storage::Storage, controller; record)  -> Storage
 
     z0 [n_inst][nb][13]: batch of initial states (default: the mechanism's current body states, one instance).
@@ -1523,6 +1608,9 @@ def simulate(mechanism, tend_or_storage, controller, record=True, z0=None, fric=
     each scored on the device behind its launch; the returned Storage carries .score [n_inst][4] (Jx, Ju, peak, last_out).  With record=False nothing larger than
     that slab ever exists; with record=True the slabs are also collected and the recorded trajectory is what was scored.  zT and status are bitwise those of the
     run without score=.  For the fused laws.
+    ensemble: an Ensemble -- the same chunk loop (with or without score=, on the same slab) with cclqr_rollout_ensemble behind every launch; the returned Storage
+    carries .ensemble, an EnsembleStats: per step the mean and the spread of every coordinate of Δz and Δu across the instances, and the covariance of Δz at the
+    Ensemble's cov_knots.  Any chunk_steps, record or not, gives the same bits.  For the fused laws.
     After the call the mechanism's bodies hold instance 0's final state (simulate! mutates the mechanism)."""
     if isinstance(controller, PolicyValue):
         raise TypeError("a PolicyValue is not a Controller: simulate rolls out the controller it evaluates (PolicyValue.controller)")
@@ -1540,8 +1628,8 @@ def simulate(mechanism, tend_or_storage, controller, record=True, z0=None, fric=
         steps = int(math.ceil(tend_or_storage / mechanism.Δt))     # steps = 1:ceil(tend/Δt)
     nb = len(mechanism.bodies)
     z0 = mechanism.state()[None] if z0 is None else np.asarray(z0, dtype=np.float64).reshape(-1, nb, 13)
-    if score is None and chunk_steps is not None:
-        raise ValueError("chunk_steps is an option of score=")
+    if score is None and ensemble is None and chunk_steps is not None:
+        raise ValueError("chunk_steps is an option of score= and ensemble=")
     if score is not None:
         if not isinstance(score, Score):
             raise TypeError("score= takes a Score(mechanism, bodyids, eqcids, Q, R)")
@@ -1551,6 +1639,18 @@ def simulate(mechanism, tend_or_storage, controller, record=True, z0=None, fric=
             raise ValueError("the Score was made for another mechanism")
         if steps < 1:
             raise ValueError("score= needs at least one step")
+    if ensemble is not None:
+        if not isinstance(ensemble, Ensemble):
+            raise TypeError("ensemble= takes an Ensemble(mechanism, cov_knots=())")
+        if getattr(controller, "controlfunction", None) is not None:
+            raise ValueError("ensemble= with a custom controlfunction is not supported: the device forms the feedback command of the fused laws, a closure computes its own inputs")
+        if ensemble.mechanism is not mechanism:
+            raise ValueError("the Ensemble was made for another mechanism")
+        if steps < 1:
+            raise ValueError("ensemble= needs at least one step")
+        if ensemble.cov_knots and ensemble.cov_knots[-1] >= steps:
+            raise ValueError("cov_knots must lie in 0 .. steps - 1 = %d (got %s)" % (steps - 1, list(ensemble.cov_knots)))
+    if score is not None or ensemble is not None:
         if chunk_steps is None:
             chunk_steps = _capi.default_chunk_steps(z0.shape[0], nb, steps)
         if int(chunk_steps) < 1:
@@ -1565,14 +1665,19 @@ def simulate(mechanism, tend_or_storage, controller, record=True, z0=None, fric=
     if (noise is not None or noise_seed is not None) and noise_scale is None:
         noise_scale = 1.0
     ph = None if plants is None else plants.handle(dev)
-    scores = None
-    if score is not None:
+    scores = stats = None
+    if score is not None or ensemble is not None:
         ctrl = controller._ctrl_handle(dev, fric=fric, noise_scale=0.0 if noise_scale is None else noise_scale, noise_seed=noise_seed)
         sh = None
         try:
-            sh = score._handle(dev)
+            sh = None if score is None else score._handle(dev)
             traj = np.zeros((z0.shape[0], steps, nb, 13)) if record else None
-            zT, status, scores = _capi.rollout_scored(dev, ctrl, sh, z0, steps, int(chunk_steps), noise=noise, first_instance=first_instance, plants=ph, traj_out=traj)
+            ens = None if ensemble is None else (ctrl.mu, ensemble.cov_knots)
+            got = _capi.rollout_scored(dev, ctrl, sh, z0, steps, int(chunk_steps), noise=noise, first_instance=first_instance, plants=ph, traj_out=traj, ensemble=ens)
+            zT, status, scores = got[:3]
+            if ensemble is not None:
+                emean, eM2, eC = got[3]
+                stats = EnsembleStats(z0.shape[0], emean[:, :12 * nb], eM2[:, :12 * nb], emean[:, 12 * nb:], eM2[:, 12 * nb:], eC)
         finally:
             if sh is not None:
                 sh.close()
@@ -1595,9 +1700,11 @@ def simulate(mechanism, tend_or_storage, controller, record=True, z0=None, fric=
         tend_or_storage.n_inst = z0.shape[0]
         tend_or_storage.status, tend_or_storage.zT = status, zT
         tend_or_storage.score = scores
+        tend_or_storage.ensemble = stats
         return tend_or_storage
     out = Storage(steps, nb, z0.shape[0], traj if record else np.zeros((z0.shape[0], 0, nb, 13)), status, zT)
     out.score = scores
+    out.ensemble = stats
     return out
 
 

@@ -16,6 +16,7 @@
  */
 #ifndef CCLQR_H
 #define CCLQR_H
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -59,7 +60,9 @@ extern "C" {
  * Still 202 (additive, no struct changed): the state covariance of a TRACKED run at every knot, a model and a gain row per knot -- cclqr_covariance_tracking, cclqr_value_create_covariance_tracking;
  * looked up the same way.  cclqr_covariance_doubling and cclqr_value_create_covariance_doubling are unchanged, their refusal of gain tables and tracking controllers included.
  * Still 202 (additive, no struct changed): the cost-to-go of a TRACKED run at every knot and the price of its noise, a model and a gain row per knot -- cclqr_policy_value_tracking, cclqr_value_create_policy_tracking;
- * looked up the same way.  cclqr_policy_value, cclqr_value_create_policy and the two tracking-covariance entries are unchanged. */
+ * looked up the same way.  cclqr_policy_value, cclqr_value_create_policy and the two tracking-covariance entries are unchanged.
+ * Still 202 (additive, no struct changed): the statistics of a slab ACROSS its instances at every step -- cclqr_rollout_ensemble_ws_bytes, cclqr_rollout_ensemble; looked up
+ * the same way.  cclqr_rollout_score is unchanged. */
 #define CCLQR_ABI_VERSION 202
 
 #define CCLQR_REVOLUTE 0      /* EqualityConstraint(Revolute(a, b, axis; p1, p2, qoffset)),  examples/lqr_cartpole.jl:26 */
@@ -686,6 +689,32 @@ int cclqr_score_destroy(cclqr_score *s);
  * controller with several tables, steps < 1 or k0 < 1, a handle made for another mechanism or device.  Every topology cclqr_mech_create takes. */
 int cclqr_rollout_score(const cclqr_mech *m, const cclqr_ctrl *c, const cclqr_score *s, int64_t n_inst, int32_t steps, int32_t k0,
                         int64_t first_instance, const double *traj_dev, double *score_dev, void *stream);
+
+/* Ensemble statistics of a rollout on the device (additive, still 202, no struct changed; looked up by name like the entries above).  cclqr_rollout_score reduces a
+ * slab along time, per instance; this reduces it ACROSS the instances, per step: what a Monte-Carlo run of the reference -- simulate! under control_lqr!
+ * (src/control/lqr.jl:89-139) / control_trackinglqr! (lqr_tracking.jl:46-71) with the `randn()` of trackingLQR_triple_cartpole.jl:98 -- is compared with the
+ * predictions of cclqr_covariance_tracking by, without its trajectory.  The indexing is that of cclqr_rollout_score: slab row r = k - k0 holds the state the law saw
+ * at the absolute step k (1-based), instance i has the global index gi = first_instance + i, and
+ *     Δz_{i,k} [12 nb] = the error of lqr.jl:92-103 about setpoint row min(k, nsp) - 1 of table gi (a one-table controller: table 0),
+ *     Δu_{i,k} [mu]    = -K[kidx] Δz_{i,k} of lqr.jl:106-111, kidx = min(k, nK) - 1 (N <= 0: 0), under the gate N <= 0 || k < N, else 0; 0 without gains,
+ *     x_{i,k}          = (Δz_{i,k}, Δu_{i,k}), 12 nb + mu coordinates.
+ * Per step the call writes  mean_dev [steps][12 nb + mu] = (1/n) sum_i x_{i,k}  and  m2_dev [steps][12 nb + mu] = sum_i (x_{i,k} - mean)^2, the CENTRED sum of squares
+ * per coordinate (variance = M2 / n; the mean square about the setpoint = (M2 + n mean^2) / n), and for each of the n_cov absolute steps listed in cov_steps (HOST
+ * array, each within k0 .. k0 + steps - 1, at most 64 per call)  cov_dev [n_cov][12 nb][12 nb] = sum_i (Δz_i - mean)(Δz_i - mean)', exactly symmetric, its diagonal
+ * equal to M2 to rounding.  Δz is in the CALLER'S body order in every output (as cclqr_value_get returns Σ), Δu in the controller's input order.  Row j (0-based) of
+ * a run from step 1 is knot j of cclqr_covariance_tracking.
+ * Nothing is formed as S2 / n - mean^2: tiles of 64 instances are reduced about their own means and merged pairwise (Chan, Golub, LeVeque), in ONE order that depends
+ * on n_inst and the mechanism only -- no floating-point atomics --, so a horizon taken chunk by chunk, or twice, gives the same bits.  All instances count: a value
+ * that is not finite makes the coordinates it enters NaN at that step, and only those; a lost instance enters with its frozen pose (read `status`).
+ * All pointers are DEVICE pointers except cov_steps; asynchronous on `stream`; nothing is allocated.  ws_dev: cclqr_rollout_ensemble_ws_bytes(m, mu, n_inst, steps,
+ * n_cov) bytes, 8-byte aligned.  CCLQR_EINVAL, before anything is launched, with the cause in cclqr_last_error: a null or short workspace, a cov_steps entry outside
+ * the launch, n_inst < 1, steps < 1 or k0 < 1, n_cov outside 0 .. 64, a controller made for another mechanism or device or without a setpoint table, first_instance +
+ * n_inst > n_ctrl for a controller with several tables.  Every topology cclqr_mech_create takes. */
+int cclqr_rollout_ensemble_ws_bytes(const cclqr_mech *m, int32_t mu, int64_t n_inst, int32_t steps, int32_t n_cov, size_t *bytes);
+int cclqr_rollout_ensemble(const cclqr_mech *m, const cclqr_ctrl *c, int64_t n_inst, int32_t steps, int32_t k0, int64_t first_instance,
+                           const double *traj_dev, double *mean_dev, double *m2_dev,
+                           int32_t n_cov, const int32_t *cov_steps /* host; absolute steps, each within k0 .. k0+steps-1 */, double *cov_dev,
+                           void *ws_dev, size_t ws_bytes, void *stream);
 
 /* cclqr_rollout (HOST pointers) with options: first_instance and newton_mode apply, the device-buffer fields must be NULL. */
 int cclqr_rollout_host_ex(const cclqr_mech *m, const cclqr_ctrl *c, int64_t n_inst, int32_t steps, int32_t k0, const double *z0,

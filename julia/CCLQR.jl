@@ -447,6 +447,26 @@ function rollout_score!(h::MechHandle, c::CtrlHandle, s::ScoreHandle, n::Integer
                 h.ptr, c.ptr, s.ptr, n, steps, k0, first_instance, traj, score, stream))
 end
 
+"Bytes of device workspace one rollout_ensemble! call of these sizes needs (cclqr_rollout_ensemble_ws_bytes)."
+function rollout_ensemble_ws_bytes(h::MechHandle, mu::Integer, n::Integer, steps::Integer, n_cov::Integer)
+    out = Ref{Csize_t}(0)
+    check(ccall((:cclqr_rollout_ensemble_ws_bytes, lib), Cint, (Ptr{Cvoid}, Int32, Int64, Int32, Int32, Ref{Csize_t}), h.ptr, mu, n, steps, n_cov, out))
+    Int(out[])
+end
+
+"The statistics of the slab a rollout_dev! launch has just written ACROSS its instances (cclqr_rollout_ensemble; device pointers except cov_steps, asynchronous on
+ `stream`): mean and m2 are (12 nb + mu) x steps -- per step the mean and the centred sum of squares of every coordinate of (Δz, Δu), Δz in the caller's body order --
+ and cov is 12 nb x 12 nb x length(cov_steps), the centred co-moment matrices of Δz at the listed absolute steps (each within k0 : k0 + steps - 1).  One fixed
+ summation order: behind every launch of the chunk loop of rollout_score!, with mean / m2 advanced by (k0 - 1) columns, the horizon's statistics are bitwise those
+ of one call."
+function rollout_ensemble!(h::MechHandle, c::CtrlHandle, n::Integer, steps::Integer, k0::Integer, traj::Ptr{Float64}, mean::Ptr{Float64}, m2::Ptr{Float64},
+                           ws::Ptr{Cvoid}, ws_bytes::Integer; cov_steps::Vector{Int32} = Int32[], cov::Ptr{Float64} = Ptr{Float64}(C_NULL), first_instance = 0,
+                           stream::Ptr{Cvoid} = C_NULL)
+    check(ccall((:cclqr_rollout_ensemble, lib), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int32, Int32, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int32, Ptr{Int32}, Ptr{Float64}, Ptr{Cvoid}, Csize_t, Ptr{Cvoid}),
+                h.ptr, c.ptr, n, steps, k0, first_instance, traj, mean, m2, length(cov_steps), cov_steps, cov, ws, ws_bytes, stream))
+end
+
 "dlqr_weights that also returns the cost-to-go (cclqr_riccati_value): P[p] is the Pkp1 of lqr.jl:170 at the last backward step problem p executed (the step the
  break test of lqr.jl:172 fired on, else step 1; Q_p when N = 1), mx x mx as the recursion holds it.  Returns (Ku[p][k][i], P[p], kbreak[p])."
 function dlqr_value(As::Vector, Bus::Vector, Bλs::Vector, Gs::Vector, Qs::Vector, Rs::Vector, N::Integer; tol = 1e-5)
