@@ -143,6 +143,118 @@ def i32(a):
     return None if a is None else np.ascontiguousarray(a, dtype=np.int32)
 
 
+# The argument marshalling every entry point below shares, each piece stated once.  _d and _i above stay the only places where an array becomes a pointer.
+
+def _panel(a):
+    """the pointer of a panel that may be empty (Bu, R, K with mu = 0; Bl, G with ml = 0) or absent: NULL then -- the library reads no panel whose extent is zero"""
+    return _d(a) if a is not None and a.size else None
+
+
+def _models(A, Bu, Bl, G, per=1, tracked=False):
+    """the projected-model arguments as contiguous float64 arrays -> ((A, Bu, Bl, G), (nprob, mx, mu, ml)).  Flat form: A [nmod][mx][mx] (or [mx][mx]) with `per`
+    models per problem (N - 1 of a time-varying problem); tracked: A [nprob][nlin][mx][mx].  mu and ml are read off Bu and Bl"""
+    A = f64(A)
+    if tracked:
+        if A.ndim != 4 or A.shape[-1] != A.shape[-2]:
+            raise ValueError("A must be [nprob][nlin][mx][mx] (got %s)" % (A.shape,))
+        lead, mx = A.shape[:2], A.shape[-1]
+        panel = lambda B: B.reshape(lead + (mx, -1)) if B.size else B.reshape(lead + (mx, 0))
+    else:
+        mx = A.shape[-1]
+        A = A.reshape(-1, mx, mx)
+        if A.shape[0] % per:
+            raise ValueError("time_varying: A must hold N - 1 = %d models per problem (got %d models)" % (per, A.shape[0]))
+        lead = A.shape[:1]
+        panel = lambda B: B.reshape(lead + (mx, B.shape[-1] if B.ndim > 1 else -1))      # (the trailing size stated: mu = 0 / ml = 0 leave nothing to infer -1 from)
+    Bu, Bl = panel(f64(Bu)), panel(f64(Bl))
+    mu, ml = Bu.shape[-1], Bl.shape[-1]
+    return (A, Bu, Bl, f64(G).reshape(lead + (ml, mx))), (lead[0] // per, mx, mu, ml)
+
+
+def _model_args(dims, models):
+    """the head of an array-level call: nprob, mx, mu, ml, A, Bu, Bl, G -- nlin before A in the tracked form, an empty panel as NULL"""
+    return tuple(C.c_int32(v) for v in dims + models[0].shape[1:-2]) + (_d(models[0]),) + tuple(_panel(M) for M in models[1:])
+
+
+def _gains(K, mu, mx, full, lowest):
+    """a gain table of any accepted rank lowest .. full as the full-rank array: full = 3, [n_gains][mu][mx] (a stationary gain), or 4, [n_gains][nK][mu][mx]"""
+    K = f64(K)
+    if not lowest <= K.ndim <= full or K.shape[-2:] != (mu, mx):
+        lead = ["[n_gains]", "[nK]"][:full - 2]
+        names = ["".join(lead[full - rank:]) + "[mu][mx]" for rank in range(lowest, full + 1)]
+        raise ValueError("K must be %s or %s with mu = %d, mx = %d (got %s)" % (", ".join(names[:-1]), names[-1], mu, mx, K.shape))
+    return K.reshape((1,) * (full - K.ndim) + K.shape)
+
+
+def _weights(Q, R, mx, mu, nw=None, optional=False):
+    """Q [n_weights][mx][mx], R [n_weights][mu][mu] -> (Q, R, n_weights): the count read off Q, or `nw` as the caller states it.  optional: Q = None (a call that
+    takes no cost) gives (None, None, 1)"""
+    if optional and Q is None:
+        return None, None, 1
+    Q = f64(Q).reshape(-1 if nw is None else nw, mx, mx)
+    nw = Q.shape[0]
+    return Q, f64(R).reshape(nw, mu, mu), nw
+
+
+def _on_plants(mech, plants, first_plant):
+    """the head of a mechanism-side call: the mechanism, the PlantsHandle (None: the mechanism's own plant) and the global index of its first plant"""
+    return mech.ptr, None if plants is None else plants.ptr, C.c_int64(int(first_plant))
+
+
+def _mech_side(mech, zd, ctrl_joint, Fd, Q, R, nw=None, traj=None, on_device=False):
+    """the mechanism-side arguments -> ((zd, ctrl_joint, Fd, Q, R) as arrays, n_weights, (zd, Fd) as the library takes them).  zd [n][nb][13], Fd [n][mu] or None; traj =
+    (n, N): trajectories zd [n][N][nb][13], Fd [n][N][mu], with on_device raw device addresses, passed as they are.  Q [n_weights][12 nb][12 nb], R [n_weights][mu][mu]"""
+    nb = mech.tables.nb
+    cj = i32(ctrl_joint).reshape(-1)
+    mu = len(cj)
+    if on_device:
+        zd, Fd, ptrs = None, None, (C.c_void_p(int(zd)), None if Fd is None else C.c_void_p(int(Fd)))
+    else:
+        zd = f64(zd).reshape(((-1,) if traj is None else traj) + (nb, 13))
+        Fd = None if Fd is None else f64(Fd).reshape(zd.shape[:-2] + (mu,))
+        ptrs = (_d(zd), _d(Fd))
+    Q, R, nw = _weights(Q, R, 12 * nb, mu, nw)
+    return (zd, cj, Fd, Q, R), nw, ptrs
+
+
+def _setpoint_args(mech, ctrl, zd, ctrl_joint, Fd, Q, R, plants, first_plant):
+    """the head the value_create_* entries on setpoints share -- mechanism, plants, first_plant, n, zd, mu, ctrl_joint, Fd, the controller, n_weights, Q, R -> (n, head)"""
+    (zd, cj, _, Q, R), nw, (zp, fp) = _mech_side(mech, zd, ctrl_joint, Fd, Q, R)
+    n = zd.shape[0]
+    return n, _on_plants(mech, plants, first_plant) + (C.c_int32(n), zp, C.c_int32(len(cj)), _i(cj), fp, ctrl.ptr, C.c_int32(nw), _d(Q), _d(R))
+
+
+def _trajectory_args(mech, ctrl, zd, n, N, ctrl_joint, Fd, Q, R, plants, first_plant, on_device):
+    """the head the value_create_* entries on trajectories share -- mechanism, plants, first_plant, n, N, zd, Fd, on_device, mu, ctrl_joint, the controller, n_weights, Q, R"""
+    (_, cj, _, Q, R), nw, (zp, fp) = _mech_side(mech, zd, ctrl_joint, Fd, Q, R, traj=(n, N), on_device=on_device)
+    return _on_plants(mech, plants, first_plant) + (C.c_int32(n), C.c_int32(N), zp, fp, C.c_int32(1 if on_device else 0), C.c_int32(len(cj)), _i(cj), ctrl.ptr,
+                                                    C.c_int32(nw), _d(Q), _d(R))
+
+
+def _diagnostics(n, want=True, fill=0.0):
+    """the four diagnostics of a doubling call -- levels, reason [n], dnorm and the second norm [n][2] --, or four None (the library then takes NULL)"""
+    if not want:
+        return None, None, None, None
+    return np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32), np.full((n, 2), fill), np.full((n, 2), fill)
+
+
+class _Handle:
+    """an object of the library behind `ptr`: destroyed once, by close() or when collected.  A subclass names the destroy symbol and keeps in _arrs the host arrays
+    its descriptor points into"""
+    _destroy = None
+
+    def close(self):
+        if self.ptr:
+            getattr(lib(), self._destroy)(self.ptr)
+            self.ptr = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def device_count():
     n = C.c_int32(0)
     check(lib().cclqr_device_count(C.byref(n)))
@@ -153,8 +265,9 @@ def set_device(dev):
     check(lib().cclqr_set_device(C.c_int32(dev)))
 
 
-class MechHandle:
+class MechHandle(_Handle):
     """cclqr_mech*: device-resident mechanism tables"""
+    _destroy = "cclqr_mech_destroy"
 
     def __init__(self, tables):
         t = tables
@@ -188,20 +301,10 @@ class MechHandle:
         check(lib().cclqr_rollout_instances_per_wavefront(self.ptr, C.c_int64(int(n_inst)), C.c_int32(int(steps)), C.c_int32(int(flags)), C.byref(v)))
         return v.value
 
-    def close(self):
-        if self.ptr:
-            lib().cclqr_mech_destroy(self.ptr)
-            self.ptr = C.c_void_p()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class CtrlHandle:
+class CtrlHandle(_Handle):
     """cclqr_ctrl*: device-resident controller tables"""
+    _destroy = "cclqr_ctrl_destroy"
 
     def __init__(self, mech, ctrl_joint, K=None, N=0, zd=None, Fd=None, fric=None, noise_scale=0.0, pid=None, noise_seed=None, n_ctrl=0):
         """n_ctrl > 1: one controller table per instance -- K [n_ctrl][nK][mu][12 nb], zd [n_ctrl][nsp][nb][13], Fd [n_ctrl][nsp][mu]"""
@@ -241,20 +344,10 @@ class CtrlHandle:
         Fd = f64(Fd).reshape(-1)
         check(lib().cclqr_ctrl_set_feedforward(self.ptr, _d(Fd), C.c_int64(Fd.size), C.c_int32(0), None))
 
-    def close(self):
-        if self.ptr:
-            lib().cclqr_ctrl_destroy(self.ptr)
-            self.ptr = C.c_void_p()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class BatchLqrHandle:
+class BatchLqrHandle(_Handle):
     """cclqr_ctrl* built by cclqr_ctrl_create_lqr_batch: one LQR per setpoint (linearsystem + dlqr + controller tables), gains device-resident"""
+    _destroy = "cclqr_ctrl_destroy"
 
     def __init__(self, mech, zd, ctrl_joint, Q, R, N, Fd=None, tol=1e-5, infinite_horizon=False, plants=None, first_plant=0, n_weights=None, keep_value=False):
         """infinite_horizon: LQR{T,Inf} -- N = Ntemp = ceil(10/Δt) (lqr.jl:26), only Ku[1] per setpoint is kept.
@@ -263,48 +356,37 @@ class BatchLqrHandle:
         plants: a PlantsHandle (cclqr_ctrl_create_lqr_batch_plants) -- table k is designed on the plant with global index first_plant + k.
         n_weights: Q [n_weights][12 nb][12 nb], R [n_weights][mu][mu], one pair per table (cclqr_ctrl_create_lqr_batch_weights; the library refuses any count but
         1 and the number of setpoints); None: one pair, through the entry points that take one"""
-        nb = mech.tables.nb
-        zd = f64(zd).reshape(-1, nb, 13)
-        n = zd.shape[0]
-        cj = i32(ctrl_joint).reshape(-1)
-        mu = len(cj)
-        Fd = None if Fd is None else f64(Fd).reshape(n, mu)
-        nw = 1 if n_weights is None else int(n_weights)
-        Q, R = f64(Q).reshape(nw, 12 * nb, 12 * nb), f64(R).reshape(nw, mu, mu)
-        self.kbreak = np.zeros(n, dtype=np.int32)
-        self.mu, self.N, self.nsp, self.n_ctrl = mu, (0 if infinite_horizon else int(N)), 1, n
-        self._arrs = [zd, cj, Fd, Q, R]
-        self.mech = mech
-        self.plants, self.first_plant = plants, int(first_plant)      # (the plants it was designed on: kept for error messages only)
-        self.ptr = C.c_void_p()
-        head = (C.c_int32(n), _d(zd), C.c_int32(mu), _i(cj), _d(Fd))
-        last = (_d(Q), _d(R), C.c_int32(int(N)), C.c_int32(1 if infinite_horizon else 0), C.c_double(float(tol)), _i(self.kbreak), C.byref(self.ptr))
-        tail = head + last
-        self.value = None
+        head, nw, weights = self._arguments(mech, zd, ctrl_joint, Fd, Q, R, 1 if n_weights is None else int(n_weights), 0 if infinite_horizon else int(N), plants,
+                                            first_plant)
+        self.kbreak = np.zeros(self.n_ctrl, dtype=np.int32)
+        last = weights + (C.c_int32(int(N)), C.c_int32(1 if infinite_horizon else 0), C.c_double(float(tol)), _i(self.kbreak), C.byref(self.ptr))
+        on = _on_plants(mech, plants, first_plant)
         if keep_value:
             vptr = C.c_void_p()
-            check(lib().cclqr_ctrl_create_lqr_batch_value(mech.ptr, None if plants is None else plants.ptr, C.c_int64(int(first_plant)), *head, C.c_int32(nw), *last,
-                                                          C.byref(vptr)))
-            self.value = ValueHandle(mech, ptr=vptr, n_tables=n)
+            check(lib().cclqr_ctrl_create_lqr_batch_value(*on, *head, C.c_int32(nw), *last, C.byref(vptr)))
+            self.value = ValueHandle(mech, ptr=vptr, n_tables=self.n_ctrl)
         elif n_weights is not None:
-            check(lib().cclqr_ctrl_create_lqr_batch_weights(mech.ptr, None if plants is None else plants.ptr, C.c_int64(int(first_plant)), *head, C.c_int32(nw), *last))
+            check(lib().cclqr_ctrl_create_lqr_batch_weights(*on, *head, C.c_int32(nw), *last))
         elif plants is None:
-            check(lib().cclqr_ctrl_create_lqr_batch(mech.ptr, *tail))
+            check(lib().cclqr_ctrl_create_lqr_batch(mech.ptr, *head, *last))
         else:
-            check(lib().cclqr_ctrl_create_lqr_batch_plants(mech.ptr, plants.ptr, C.c_int64(int(first_plant)), *tail))
+            check(lib().cclqr_ctrl_create_lqr_batch_plants(*on, *head, *last))
+
+    def _arguments(self, mech, zd, ctrl_joint, Fd, Q, R, nw, N, plants, first_plant):
+        """the fields both batched constructors keep -> (the call's arguments from the setpoint count to Fd, n_weights, the pointers of Q and R)"""
+        arrs, nw, (zp, fp) = _mech_side(mech, zd, ctrl_joint, Fd, Q, R, nw)
+        self._arrs = list(arrs)
+        n, mu = arrs[0].shape[0], len(arrs[1])
+        self.mu, self.N, self.nsp, self.n_ctrl = mu, N, 1, n
+        self.mech = mech
+        self.plants, self.first_plant = plants, int(first_plant)      # (the plants it was designed on: kept for error messages only)
+        self.ptr, self.value = C.c_void_p(), None
+        return (C.c_int32(n), zp, C.c_int32(mu), _i(arrs[1]), fp), nw, (_d(arrs[3]), _d(arrs[4]))
 
     def close(self):
-        if self.ptr:
-            lib().cclqr_ctrl_destroy(self.ptr)
-            self.ptr = C.c_void_p()
+        super().close()
         if getattr(self, "value", None) is not None:
             self.value.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class BatchLqrDoublingHandle(BatchLqrHandle):
@@ -313,31 +395,15 @@ class BatchLqrDoublingHandle(BatchLqrHandle):
     keep_value: every table's P stays on the device as self.value"""
 
     def __init__(self, mech, zd, ctrl_joint, Q, R, N=0, Fd=None, tol=1e-5, max_levels=40, plants=None, first_plant=0, keep_value=False):
-        nb = mech.tables.nb
-        zd = f64(zd).reshape(-1, nb, 13)
-        n = zd.shape[0]
-        cj = i32(ctrl_joint).reshape(-1)
-        mu = len(cj)
-        Fd = None if Fd is None else f64(Fd).reshape(n, mu)
-        Q = f64(Q).reshape(-1, 12 * nb, 12 * nb)
-        nw = Q.shape[0]
-        R = f64(R).reshape(nw, mu, mu)
+        head, nw, weights = self._arguments(mech, zd, ctrl_joint, Fd, Q, R, None, 0, plants, first_plant)
         self.kbreak = None
-        self.levels, self.reason = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
-        self.dnorm, self.anorm = np.full((n, 2), np.nan), np.full((n, 2), np.nan)
-        self.mu, self.N, self.nsp, self.n_ctrl = mu, 0, 1, n
-        self._arrs = [zd, cj, Fd, Q, R]
-        self.mech = mech
-        self.plants, self.first_plant = plants, int(first_plant)
-        self.ptr = C.c_void_p()
-        self.value = None
+        self.levels, self.reason, self.dnorm, self.anorm = _diagnostics(self.n_ctrl, fill=np.nan)
         vptr = C.c_void_p()
-        check(lib().cclqr_ctrl_create_lqr_batch_doubling(mech.ptr, None if plants is None else plants.ptr, C.c_int64(int(first_plant)), C.c_int32(n), _d(zd), C.c_int32(mu),
-                                                         _i(cj), _d(Fd), C.c_int32(nw), _d(Q), _d(R), C.c_int32(int(N)), C.c_double(float(tol)),
+        check(lib().cclqr_ctrl_create_lqr_batch_doubling(*_on_plants(mech, plants, first_plant), *head, C.c_int32(nw), *weights, C.c_int32(int(N)), C.c_double(float(tol)),
                                                          C.c_int32(int(max_levels)), _i(self.levels), _i(self.reason), _d(self.dnorm), _d(self.anorm),
                                                          C.byref(self.ptr), C.byref(vptr) if keep_value else None))
         if keep_value:
-            self.value = ValueHandle(mech, ptr=vptr, n_tables=n)
+            self.value = ValueHandle(mech, ptr=vptr, n_tables=self.n_ctrl)
 
 
 def ctrl_create_lqr_batch_doubling(mech, zd, ctrl_joint, Q, R, N=0, Fd=None, tol=1e-5, max_levels=40, plants=None, first_plant=0, keep_value=False):
@@ -345,9 +411,10 @@ def ctrl_create_lqr_batch_doubling(mech, zd, ctrl_joint, Q, R, N=0, Fd=None, tol
     return BatchLqrDoublingHandle(mech, zd, ctrl_joint, Q, R, N, Fd, tol, max_levels, plants, first_plant, keep_value)
 
 
-class ValueHandle:
+class ValueHandle(_Handle):
     """cclqr_value*: device-resident cost-to-go tables P [n_tables][12 nb][12 nb] in the mechanism's body order, one shared by every instance or one per controller
     table.  P: a host array (cclqr_value_create); ptr / n_tables: a handle the library has already filled (cclqr_ctrl_create_lqr_batch_value)"""
+    _destroy = "cclqr_value_destroy"
 
     def __init__(self, mech, P=None, ptr=None, n_tables=None):
         mx = 12 * mech.tables.nb
@@ -369,17 +436,6 @@ class ValueHandle:
         check(lib().cclqr_value_get(self.ptr, C.c_int64(int(table)), _d(P)))
         return P
 
-    def close(self):
-        if self.ptr:
-            lib().cclqr_value_destroy(self.ptr)
-            self.ptr = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def value_eval(mech, ctrl, value, n_inst, z_ptr, out_ptr, stream=0, first_instance=0, z_stride=None):
     """cclqr_value_eval on device addresses (asynchronous on `stream`): out[i] = dz_i' P_t dz_i for the states at z_ptr + 8 i z_stride (z_stride in doubles; default: packed,
@@ -389,12 +445,13 @@ def value_eval(mech, ctrl, value, n_inst, z_ptr, out_ptr, stream=0, first_instan
     check(lib().cclqr_value_eval(mech.ptr, ctrl.ptr, value.ptr, C.c_int64(int(n_inst)), C.c_int64(int(first_instance)), vp(z_ptr), C.c_int64(zs), vp(out_ptr), vp(stream)))
 
 
-class BatchTrackingHandle:
+class BatchTrackingHandle(_Handle):
     """cclqr_ctrl* built by cclqr_ctrl_create_tracking_batch_plants: one TrackingLQR per plant and / or reference trajectory (linearsystem at every knot, the
     time-varying recursion, the controller's tables), gains device-resident.
     zd [n][N][nb][13], Fd [n][N][mu] or None: host arrays, or (on_device=True) raw device addresses read on `stream` -- n_ctrl and N must then be given.
     plants: a PlantsHandle or None (the mechanism's own plant for every trajectory); table k is designed on the plant with global index first_plant + k.
     fric [ne], noise_scale, noise_seed: the friction / noise law, fixed at construction.  workspace_bytes <= 0: the library's default budget."""
+    _destroy = "cclqr_ctrl_destroy"
 
     def __init__(self, mech, zd, ctrl_joint, Q, R, Fd=None, plants=None, first_plant=0, n_ctrl=None, N=None, on_device=False, stream=0, tol=1e-5, fric=None,
                  noise_scale=0.0, noise_seed=None, workspace_bytes=0):
@@ -438,17 +495,6 @@ class BatchTrackingHandle:
                                                             C.c_double(float(tol)), None if law is None else C.byref(law), C.c_int64(int(workspace_bytes)),
                                                             _i(self.kbreak), C.c_void_p(int(stream)) if stream else None, C.byref(self.ptr)))
 
-    def close(self):
-        if self.ptr:
-            lib().cclqr_ctrl_destroy(self.ptr)
-            self.ptr = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def ctrl_gains(mech, handle, table=0, nK=None, mu=None):
     """cclqr_ctrl_get_gains: one table's gains [nK][mu][12 nb] of a controller handle, in the mechanism's body order.  nK, mu: the handle's own by default
@@ -465,10 +511,11 @@ def ctrl_gains(mech, handle, table=0, nK=None, mu=None):
     return K
 
 
-class PlantsHandle:
+class PlantsHandle(_Handle):
     """cclqr_plants*: device-resident per-instance plants of a tree mechanism.  mass [n][nb], inertia [n][nb][9], p1 / p2 [n][ne][3] in the mechanism's
     body / joint order, None = the mechanism's own value; host arrays, or (on_device=True) raw device addresses read on `stream`; n_plant must be given
     with device addresses.  first_index: global instance index of row 0."""
+    _destroy = "cclqr_plants_destroy"
 
     def __init__(self, mech, mass=None, inertia=None, p1=None, p2=None, first_index=0, n_plant=None, on_device=False, stream=0):
         nb, ne = mech.tables.nb, mech.tables.ne
@@ -490,17 +537,6 @@ class PlantsHandle:
         self.ptr = C.c_void_p()
         check(lib().cclqr_plants_create(mech.ptr, C.c_int64(self.n_plant), C.c_int64(self.first_index), args[0], args[1], args[2], args[3],
                                         C.c_int32(1 if on_device else 0), C.c_void_p(int(stream)) if stream else None, C.byref(self.ptr)))
-
-    def close(self):
-        if self.ptr:
-            lib().cclqr_plants_destroy(self.ptr)
-            self.ptr = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def _rollout_plants(mech, ctrl, plants, z0, steps, k0, noise, record, first_instance, newton_mode, newton_eps_alone, flags):
@@ -561,9 +597,10 @@ def rollout_dev(mech, ctrl, n_inst, steps, k0, z0_ptr, lam_ptr, noise_ptr, noise
                                  vp(noise_ptr), C.c_int64(noise_stride), vp(traj_ptr), vp(zT_ptr), vp(status_ptr), C.byref(o), vp(stream)))
 
 
-class ScoreHandle:
+class ScoreHandle(_Handle):
     """cclqr_score*: the device-resident weights a rollout is scored with.  Qb [nb][12][12] per-body blocks in the mechanism's body order, R [mu][mu], both already
     Δt-scaled (lqr.jl:18-19); settle_tol: the stage cost above which an instance counts as not settled (last_out)"""
+    _destroy = "cclqr_score_destroy"
 
     def __init__(self, mech, Qb, R, settle_tol=0.0):
         nb = mech.tables.nb
@@ -577,17 +614,6 @@ class ScoreHandle:
         self._arrs = [Qb, R]
         self.ptr = C.c_void_p()
         check(lib().cclqr_score_create(mech.ptr, _d(Qb), C.c_int32(mu), _d(R) if mu else None, C.c_double(self.settle_tol), C.byref(self.ptr)))
-
-    def close(self):
-        if self.ptr:
-            lib().cclqr_score_destroy(self.ptr)
-            self.ptr = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def rollout_score(mech, ctrl, score, n_inst, steps, k0, traj_ptr, score_ptr, stream=0, first_instance=0):
@@ -730,23 +756,14 @@ def riccati(A, Bu, Bl, G, Q, R, N, tol=1e-5, path=0, bf16_terms=0, keep_last=Fal
     """batched dlqr: A [nprob][mx][mx] (or [mx][mx]) -> K [nprob][N-1][mu][mx], kbreak [nprob].
     path: 0 auto / 1 resident / 2 tiled; bf16_terms: 0 = fp64 MFMA (parity), 1..3 = split-bf16 measured-error mode (cclqr_riccati_opts);
     keep_last: K [nprob][1][mu][mx] = Ku[1] only (LQR{T,Inf})"""
-    A = f64(A)
-    single = A.ndim == 2
-    mx = A.shape[-1]
-    A = A.reshape(-1, mx, mx)
-    nprob = A.shape[0]
-    Bu, Bl = f64(Bu), f64(Bl)
-    Bu = Bu.reshape(nprob, mx, Bu.shape[-1] if Bu.ndim > 1 else -1)      # (the trailing size stated: mu = 0 / ml = 0 leave nothing to infer -1 from)
-    mu = Bu.shape[2]
-    Bl = Bl.reshape(nprob, mx, Bl.shape[-1] if Bl.ndim > 1 else -1)
-    ml = Bl.shape[2]
-    G = f64(G).reshape(nprob, ml, mx)
+    single = np.ndim(A) == 2
+    models, dims = _models(A, Bu, Bl, G)
+    nprob, mx, mu, ml = dims
     Q, R = f64(Q).reshape(mx, mx), f64(R).reshape(mu, mu)
     K = np.zeros((nprob, (1 if keep_last else N - 1) if N > 1 else 0, mu, mx))
     kb = np.zeros(nprob, dtype=np.int32)
     o = RiccatiOpts(int(path), int(bf16_terms), 1 if keep_last else 0, 0)
-    check(lib().cclqr_riccati_ex(C.c_int32(nprob), C.c_int32(mx), C.c_int32(mu), C.c_int32(ml), _d(A), _d(Bu), _d(Bl), _d(G), _d(Q), _d(R),
-                                 C.c_int32(N), C.c_double(tol), _d(K), _i(kb), C.byref(o)))
+    check(lib().cclqr_riccati_ex(*_model_args(dims, models), _d(Q), _panel(R), C.c_int32(N), C.c_double(tol), _d(K), _i(kb), C.byref(o)))
     return (K[0], int(kb[0])) if single else (K, kb)
 
 
@@ -754,19 +771,9 @@ def riccati_weights(A, Bu, Bl, G, Q, R, N, tol=1e-5, path=0, bf16_terms=0, keep_
     """batched dlqr with one pair of weights per problem (cclqr_riccati_weights): A [nprob][mx][mx], Q [n_weights][mx][mx], R [n_weights][mu][mu] with n_weights = 1
     or nprob (the library refuses anything else) -> K [nprob][N-1][mu][mx], kbreak [nprob].  path, bf16_terms, keep_last as riccati.  K: the array to fill
     (default: a new one)"""
-    A = f64(A)
-    mx = A.shape[-1]
-    A = A.reshape(-1, mx, mx)
-    nprob = A.shape[0]
-    Bu, Bl = f64(Bu), f64(Bl)
-    Bu = Bu.reshape(nprob, mx, Bu.shape[-1] if Bu.ndim > 1 else -1)
-    mu = Bu.shape[2]
-    Bl = Bl.reshape(nprob, mx, Bl.shape[-1] if Bl.ndim > 1 else -1)
-    ml = Bl.shape[2]
-    G = f64(G).reshape(nprob, ml, mx)
-    Q = f64(Q).reshape(-1, mx, mx)
-    nw = Q.shape[0]
-    R = f64(R).reshape(nw, mu, mu)
+    models, dims = _models(A, Bu, Bl, G)
+    nprob, mx, mu, ml = dims
+    Q, R, nw = _weights(Q, R, mx, mu)
     shape = (nprob, (1 if keep_last else N - 1) if N > 1 else 0, mu, mx)
     if K is None:
         K = np.zeros(shape)
@@ -774,8 +781,7 @@ def riccati_weights(A, Bu, Bl, G, Q, R, N, tol=1e-5, path=0, bf16_terms=0, keep_
         raise ValueError("K must be a contiguous float64 array of shape %s" % (shape,))
     kb = np.zeros(nprob, dtype=np.int32)
     o = RiccatiOpts(int(path), int(bf16_terms), 1 if keep_last else 0, 0)
-    check(lib().cclqr_riccati_weights(C.c_int32(nprob), C.c_int32(mx), C.c_int32(mu), C.c_int32(ml), _d(A), _d(Bu), _d(Bl), _d(G), C.c_int32(nw), _d(Q), _d(R),
-                                      C.c_int32(N), C.c_double(tol), _d(K), _i(kb), C.byref(o)))
+    check(lib().cclqr_riccati_weights(*_model_args(dims, models), C.c_int32(nw), _d(Q), _panel(R), C.c_int32(N), C.c_double(tol), _d(K), _i(kb), C.byref(o)))
     return K, kb
 
 
@@ -783,30 +789,15 @@ def riccati_value(A, Bu, Bl, G, Q, R, N, tol=1e-5, path=0, bf16_terms=0, keep_la
     """batched dlqr that also returns the cost-to-go (cclqr_riccati_value): A [nprob][mx][mx] -- with time_varying [nprob][N-1][mx][mx], the model of backward step k at
     index k - 1 -- Q [n_weights][mx][mx], R [n_weights][mu][mu] with n_weights = 1 or nprob -> K [nprob][N-1][mu][mx], P [nprob][mx][mx], kbreak [nprob].  P[p] is the
     Pkp1 (lqr.jl:170) of the last backward step problem p executed, Q_p when N = 1.  want_P=False passes P = NULL (P is returned as None)"""
-    A = f64(A)
-    mx = A.shape[-1]
-    per = (N - 1) if time_varying else 1
-    A = A.reshape(-1, mx, mx)
-    if A.shape[0] % per:
-        raise ValueError("time_varying: A must hold N - 1 = %d models per problem (got %d models)" % (per, A.shape[0]))
-    nmod = A.shape[0]
-    nprob = nmod // per
-    Bu, Bl = f64(Bu), f64(Bl)
-    Bu = Bu.reshape(nmod, mx, Bu.shape[-1] if Bu.ndim > 1 else -1)
-    mu = Bu.shape[2]
-    Bl = Bl.reshape(nmod, mx, Bl.shape[-1] if Bl.ndim > 1 else -1)
-    ml = Bl.shape[2]
-    G = f64(G).reshape(nmod, ml, mx)
-    Q = f64(Q).reshape(-1, mx, mx)
-    nw = Q.shape[0]
-    R = f64(R).reshape(nw, mu, mu)
+    models, dims = _models(A, Bu, Bl, G, per=(N - 1) if time_varying else 1)
+    nprob, mx, mu, ml = dims
+    Q, R, nw = _weights(Q, R, mx, mu)
     K = np.zeros((nprob, (1 if keep_last else N - 1) if N > 1 else 0, mu, mx))
     P = np.zeros((nprob, mx, mx)) if want_P else None
     kb = np.zeros(nprob, dtype=np.int32)
     o = RiccatiOpts(int(path), int(bf16_terms), 1 if keep_last else 0, 0)
-    check(lib().cclqr_riccati_value(C.c_int32(nprob), C.c_int32(mx), C.c_int32(mu), C.c_int32(ml), _d(A), _d(Bu), _d(Bl) if ml else None, _d(G) if ml else None,
-                                    C.c_int32(nw), _d(Q), _d(R), C.c_int32(int(N)), C.c_double(float(tol)), C.c_int32(1 if time_varying else 0), _d(K), _d(P), _i(kb),
-                                    C.byref(o)))
+    check(lib().cclqr_riccati_value(*_model_args(dims, models), C.c_int32(nw), _d(Q), _panel(R), C.c_int32(int(N)), C.c_double(float(tol)),
+                                    C.c_int32(1 if time_varying else 0), _d(K), _d(P), _i(kb), C.byref(o)))
     return K, P, kb
 
 
@@ -816,31 +807,15 @@ def policy_value(A, Bu, Bl, G, K, Q, R, N, tol=1e-5, path=0, bf16_terms=0, want_
     R [n_weights][mu][mu] with n_weights = 1 or nprob (the library refuses any other count) -> P [nprob][mx][mx], kbreak [nprob], dnorm [nprob][2] (the norm(Pk - Pkp1)
     of the last executed step and of the step before it; NaN where no such step ran).  path: 0 auto / 1 resident / 2 tiled.  want_diag=False passes kbreak = dnorm =
     NULL (both are returned as None)"""
-    A = f64(A)
-    mx = A.shape[-1]
-    A = A.reshape(-1, mx, mx)
-    nprob = A.shape[0]
-    Bu, Bl = f64(Bu), f64(Bl)
-    Bu = Bu.reshape(nprob, mx, Bu.shape[-1] if Bu.ndim > 1 else -1)
-    mu = Bu.shape[2]
-    Bl = Bl.reshape(nprob, mx, Bl.shape[-1] if Bl.ndim > 1 else -1)
-    ml = Bl.shape[2]
-    G = f64(G).reshape(nprob, ml, mx)
-    K = f64(K)
-    if K.ndim not in (3, 4) or K.shape[-2:] != (mu, mx):
-        raise ValueError("K must be [nK][mu][mx] or [n_gains][nK][mu][mx] with mu = %d, mx = %d (got %s)" % (mu, mx, K.shape))
-    if K.ndim == 3:
-        K = K[None]
-    n_gains, nK = K.shape[0], K.shape[1]
-    Q = f64(Q).reshape(-1, mx, mx)
-    nw = Q.shape[0]
-    R = f64(R).reshape(nw, mu, mu)
+    models, dims = _models(A, Bu, Bl, G)
+    nprob, mx, mu, ml = dims
+    K = _gains(K, mu, mx, full=4, lowest=3)
+    Q, R, nw = _weights(Q, R, mx, mu)
     P = np.zeros((nprob, mx, mx))
     kb = np.zeros(nprob, dtype=np.int32) if want_diag else None
     dn = np.zeros((nprob, 2)) if want_diag else None
     o = RiccatiOpts(int(path), int(bf16_terms), 0, 0)
-    check(lib().cclqr_policy_value(C.c_int32(nprob), C.c_int32(mx), C.c_int32(mu), C.c_int32(ml), _d(A), _d(Bu) if mu else None, _d(Bl) if ml else None,
-                                   _d(G) if ml else None, C.c_int32(n_gains), C.c_int32(nK), _d(K) if K.size else None, C.c_int32(nw), _d(Q), _d(R) if mu else None,
+    check(lib().cclqr_policy_value(*_model_args(dims, models), C.c_int32(K.shape[0]), C.c_int32(K.shape[1]), _panel(K), C.c_int32(nw), _d(Q), _panel(R),
                                    C.c_int32(int(N)), C.c_double(float(tol)), _d(P), _i(kb), _d(dn), C.byref(o)))
     return P, kb, dn
 
@@ -849,20 +824,11 @@ def value_create_policy(mech, ctrl, zd, ctrl_joint, Q, R, N, tol=1e-5, Fd=None, 
     """cclqr_value_create_policy: the policy evaluation of controller handle `ctrl` (its device-resident gains: one table, or one per model) on the models linearised at
     zd [n_models][nb][13], setpoint k on plant first_plant + k of the PlantsHandle `plants` (None: the mechanism's own plant).  Q [n_weights][12 nb][12 nb],
     R [n_weights][mu][mu], n_weights = 1 or n_models -> (ValueHandle of n_models tables, kbreak [n_models], dnorm [n_models][2])"""
-    nb = mech.tables.nb
-    zd = f64(zd).reshape(-1, nb, 13)
-    n = zd.shape[0]
-    cj = i32(ctrl_joint).reshape(-1)
-    mu = len(cj)
-    Fd = None if Fd is None else f64(Fd).reshape(n, mu)
-    Q = f64(Q).reshape(-1, 12 * nb, 12 * nb)
-    nw = Q.shape[0]
-    R = f64(R).reshape(nw, mu, mu)
+    n, head = _setpoint_args(mech, ctrl, zd, ctrl_joint, Fd, Q, R, plants, first_plant)
     kb = np.zeros(n, dtype=np.int32)
     dn = np.zeros((n, 2))
     vptr = C.c_void_p()
-    check(lib().cclqr_value_create_policy(mech.ptr, None if plants is None else plants.ptr, C.c_int64(int(first_plant)), C.c_int32(n), _d(zd), C.c_int32(mu), _i(cj), _d(Fd),
-                                          ctrl.ptr, C.c_int32(nw), _d(Q), _d(R), C.c_int32(int(N)), C.c_double(float(tol)), _i(kb), _d(dn), C.byref(vptr)))
+    check(lib().cclqr_value_create_policy(*head, C.c_int32(int(N)), C.c_double(float(tol)), _i(kb), _d(dn), C.byref(vptr)))
     return ValueHandle(mech, ptr=vptr, n_tables=n), kb, dn
 
 
@@ -872,54 +838,26 @@ def policy_value_doubling(A, Bu, Bl, G, K, Q, R, N, tol=1e-5, max_levels=40, pat
     (increment < tol, at most max_levels levels) -> P [nprob][mx][mx], levels [nprob], reason [nprob] (0 converged, 1 max_levels, 2 norm(M) > 1e50), dnorm [nprob][2],
     gnorm [nprob][2] (the increment norms and norm(M) of the last level and of the one before; NaN where no such level ran).  want_diag=False passes NULL for the
     four diagnostics (returned as None)"""
-    A = f64(A)
-    mx = A.shape[-1]
-    A = A.reshape(-1, mx, mx)
-    nprob = A.shape[0]
-    Bu, Bl = f64(Bu), f64(Bl)
-    Bu = Bu.reshape(nprob, mx, Bu.shape[-1] if Bu.ndim > 1 else -1)
-    mu = Bu.shape[2]
-    Bl = Bl.reshape(nprob, mx, Bl.shape[-1] if Bl.ndim > 1 else -1)
-    ml = Bl.shape[2]
-    G = f64(G).reshape(nprob, ml, mx)
-    K = f64(K)
-    if K.ndim not in (2, 3) or K.shape[-2:] != (mu, mx):
-        raise ValueError("K must be [mu][mx] or [n_gains][mu][mx] with mu = %d, mx = %d (got %s)" % (mu, mx, K.shape))
-    if K.ndim == 2:
-        K = K[None]
-    Q = f64(Q).reshape(-1, mx, mx)
-    nw = Q.shape[0]
-    R = f64(R).reshape(nw, mu, mu)
+    models, dims = _models(A, Bu, Bl, G)
+    nprob, mx, mu, ml = dims
+    K = _gains(K, mu, mx, full=3, lowest=2)
+    Q, R, nw = _weights(Q, R, mx, mu)
     P = np.zeros((nprob, mx, mx))
-    lv = np.zeros(nprob, dtype=np.int32) if want_diag else None
-    rs = np.zeros(nprob, dtype=np.int32) if want_diag else None
-    dn = np.zeros((nprob, 2)) if want_diag else None
-    gn = np.zeros((nprob, 2)) if want_diag else None
+    lv, rs, dn, gn = _diagnostics(nprob, want_diag)
     o = RiccatiOpts(int(path), int(bf16_terms), 0, 0)
-    check(lib().cclqr_policy_value_doubling(C.c_int32(nprob), C.c_int32(mx), C.c_int32(mu), C.c_int32(ml), _d(A), _d(Bu) if mu else None, _d(Bl) if ml else None,
-                                            _d(G) if ml else None, C.c_int32(K.shape[0]), _d(K) if K.size else None, C.c_int32(nw), _d(Q), _d(R) if mu else None,
-                                            C.c_int32(int(N)), C.c_double(float(tol)), C.c_int32(int(max_levels)), _d(P), _i(lv), _i(rs), _d(dn), _d(gn), C.byref(o)))
+    check(lib().cclqr_policy_value_doubling(*_model_args(dims, models), C.c_int32(K.shape[0]), _panel(K), C.c_int32(nw), _d(Q), _panel(R), C.c_int32(int(N)),
+                                            C.c_double(float(tol)), C.c_int32(int(max_levels)), _d(P), _i(lv), _i(rs), _d(dn), _d(gn), C.byref(o)))
     return P, lv, rs, dn, gn
 
 
 def value_create_policy_doubling(mech, ctrl, zd, ctrl_joint, Q, R, N, tol=1e-5, max_levels=40, Fd=None, plants=None, first_plant=0):
     """cclqr_value_create_policy_doubling: the doubling evaluation of controller handle `ctrl`'s stationary gain (one table, or one per model; one row each) on the models
     linearised as for value_create_policy.  N >= 1 knots, or 0 = to convergence -> (ValueHandle of n_models tables, levels, reason, dnorm [n][2], gnorm [n][2])"""
-    nb = mech.tables.nb
-    zd = f64(zd).reshape(-1, nb, 13)
-    n = zd.shape[0]
-    cj = i32(ctrl_joint).reshape(-1)
-    mu = len(cj)
-    Fd = None if Fd is None else f64(Fd).reshape(n, mu)
-    Q = f64(Q).reshape(-1, 12 * nb, 12 * nb)
-    nw = Q.shape[0]
-    R = f64(R).reshape(nw, mu, mu)
-    lv, rs = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
-    dn, gn = np.zeros((n, 2)), np.zeros((n, 2))
+    n, head = _setpoint_args(mech, ctrl, zd, ctrl_joint, Fd, Q, R, plants, first_plant)
+    lv, rs, dn, gn = _diagnostics(n)
     vptr = C.c_void_p()
-    check(lib().cclqr_value_create_policy_doubling(mech.ptr, None if plants is None else plants.ptr, C.c_int64(int(first_plant)), C.c_int32(n), _d(zd), C.c_int32(mu),
-                                                   _i(cj), _d(Fd), ctrl.ptr, C.c_int32(nw), _d(Q), _d(R), C.c_int32(int(N)), C.c_double(float(tol)),
-                                                   C.c_int32(int(max_levels)), _i(lv), _i(rs), _d(dn), _d(gn), C.byref(vptr)))
+    check(lib().cclqr_value_create_policy_doubling(*head, C.c_int32(int(N)), C.c_double(float(tol)), C.c_int32(int(max_levels)), _i(lv), _i(rs), _d(dn), _d(gn),
+                                                   C.byref(vptr)))
     return ValueHandle(mech, ptr=vptr, n_tables=n), lv, rs, dn, gn
 
 
@@ -953,40 +891,20 @@ def covariance_doubling(A, Bu, Bl, G, K, Q, R, Wu, Sigma0, N, tol=1e-8, max_leve
     Sigma0 [mx][mx] or [n][mx][mx], either None (= 0).  N >= 1: N - 1 steps exactly from Sigma0; N = 0: the steady state (Sigma0 must be None), level by level until
     the increment relative to w = 2^floor(log2 tr(D Wu D')) falls below tol -> Sigma [nprob][mx][mx], cost [nprob][2] (tr(Q Sigma), tr(R K Sigma K')), zstd [nprob][mx],
     ustd [nprob][mu], levels, reason, dnorm, gnorm as there (dnorm in Sigma's units).  want_cost / want_std / want_diag = False pass NULL (returned as None)"""
-    A = f64(A)
-    mx = A.shape[-1]
-    A = A.reshape(-1, mx, mx)
-    nprob = A.shape[0]
-    Bu, Bl = f64(Bu), f64(Bl)
-    Bu = Bu.reshape(nprob, mx, Bu.shape[-1] if Bu.ndim > 1 else -1)
-    mu = Bu.shape[2]
-    Bl = Bl.reshape(nprob, mx, Bl.shape[-1] if Bl.ndim > 1 else -1)
-    ml = Bl.shape[2]
-    G = f64(G).reshape(nprob, ml, mx)
-    K = f64(K)
-    if K.ndim not in (2, 3) or K.shape[-2:] != (mu, mx):
-        raise ValueError("K must be [mu][mx] or [n_gains][mu][mx] with mu = %d, mx = %d (got %s)" % (mu, mx, K.shape))
-    if K.ndim == 2:
-        K = K[None]
-    nw = 1
-    if Q is not None:
-        Q = f64(Q).reshape(-1, mx, mx)
-        nw = Q.shape[0]
-        R = f64(R).reshape(nw, mu, mu)
+    models, dims = _models(A, Bu, Bl, G)
+    nprob, mx, mu, ml = dims
+    K = _gains(K, mu, mx, full=3, lowest=2)
+    Q, R, nw = _weights(Q, R, mx, mu, optional=True)
     Wu, Sigma0, n_noise = _noise_arrays(Wu, Sigma0, mu, mx)
     S = np.zeros((nprob, mx, mx))
     cost = np.zeros((nprob, 2)) if want_cost else None
     zstd = np.zeros((nprob, mx)) if want_std else None
     ustd = np.zeros((nprob, mu)) if want_std else None
-    lv = np.zeros(nprob, dtype=np.int32) if want_diag else None
-    rs = np.zeros(nprob, dtype=np.int32) if want_diag else None
-    dn = np.zeros((nprob, 2)) if want_diag else None
-    gn = np.zeros((nprob, 2)) if want_diag else None
+    lv, rs, dn, gn = _diagnostics(nprob, want_diag)
     o = RiccatiOpts(int(path), int(bf16_terms), 0, 0)
-    check(lib().cclqr_covariance_doubling(C.c_int32(nprob), C.c_int32(mx), C.c_int32(mu), C.c_int32(ml), _d(A), _d(Bu) if mu else None, _d(Bl) if ml else None,
-                                          _d(G) if ml else None, C.c_int32(K.shape[0]), _d(K) if K.size else None, C.c_int32(nw), _d(Q), _d(R) if mu else None,
-                                          C.c_int32(n_noise), _d(Wu), _d(Sigma0), C.c_int32(int(N)), C.c_double(float(tol)), C.c_int32(int(max_levels)), _d(S),
-                                          _d(cost), _d(zstd), _d(ustd) if mu else None, _i(lv), _i(rs), _d(dn), _d(gn), C.byref(o)))
+    check(lib().cclqr_covariance_doubling(*_model_args(dims, models), C.c_int32(K.shape[0]), _panel(K), C.c_int32(nw), _d(Q), _panel(R), C.c_int32(n_noise), _d(Wu),
+                                          _d(Sigma0), C.c_int32(int(N)), C.c_double(float(tol)), C.c_int32(int(max_levels)), _d(S), _d(cost), _d(zstd), _panel(ustd),
+                                          _i(lv), _i(rs), _d(dn), _d(gn), C.byref(o)))
     return S, cost, zstd, ustd, lv, rs, dn, gn
 
 
@@ -994,24 +912,14 @@ def value_create_covariance_doubling(mech, ctrl, zd, ctrl_joint, Q, R, Wu, Sigma
     """cclqr_value_create_covariance_doubling: the covariance above for controller handle `ctrl`'s stationary gain on the models linearised as for
     value_create_policy_doubling; Q, Sigma0 in the mechanism's body order.  N >= 1 knots, or 0 = the steady state -> (ValueHandle of n_models tables holding Sigma,
     cost [n][2], zstd [n][12 nb], ustd [n][mu], levels, reason, dnorm [n][2], gnorm [n][2])"""
-    nb = mech.tables.nb
-    zd = f64(zd).reshape(-1, nb, 13)
-    n = zd.shape[0]
-    cj = i32(ctrl_joint).reshape(-1)
-    mu = len(cj)
-    Fd = None if Fd is None else f64(Fd).reshape(n, mu)
-    Q = f64(Q).reshape(-1, 12 * nb, 12 * nb)
-    nw = Q.shape[0]
-    R = f64(R).reshape(nw, mu, mu)
-    Wu, Sigma0, n_noise = _noise_arrays(Wu, Sigma0, mu, 12 * nb)
-    cost, zstd, ustd = np.zeros((n, 2)), np.zeros((n, 12 * nb)), np.zeros((n, mu))
-    lv, rs = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
-    dn, gn = np.zeros((n, 2)), np.zeros((n, 2))
+    n, head = _setpoint_args(mech, ctrl, zd, ctrl_joint, Fd, Q, R, plants, first_plant)
+    mu, mx = np.size(ctrl_joint), 12 * mech.tables.nb
+    Wu, Sigma0, n_noise = _noise_arrays(Wu, Sigma0, mu, mx)
+    cost, zstd, ustd = np.zeros((n, 2)), np.zeros((n, mx)), np.zeros((n, mu))
+    lv, rs, dn, gn = _diagnostics(n)
     vptr = C.c_void_p()
-    check(lib().cclqr_value_create_covariance_doubling(mech.ptr, None if plants is None else plants.ptr, C.c_int64(int(first_plant)), C.c_int32(n), _d(zd), C.c_int32(mu),
-                                                       _i(cj), _d(Fd), ctrl.ptr, C.c_int32(nw), _d(Q), _d(R), C.c_int32(n_noise), _d(Wu), _d(Sigma0), C.c_int32(int(N)),
-                                                       C.c_double(float(tol)), C.c_int32(int(max_levels)), _d(cost), _d(zstd), _d(ustd), _i(lv), _i(rs), _d(dn), _d(gn),
-                                                       C.byref(vptr)))
+    check(lib().cclqr_value_create_covariance_doubling(*head, C.c_int32(n_noise), _d(Wu), _d(Sigma0), C.c_int32(int(N)), C.c_double(float(tol)),
+                                                       C.c_int32(int(max_levels)), _d(cost), _d(zstd), _d(ustd), _i(lv), _i(rs), _d(dn), _d(gn), C.byref(vptr)))
     return ValueHandle(mech, ptr=vptr, n_tables=n), cost, zstd, ustd, lv, rs, dn, gn
 
 
@@ -1021,25 +929,10 @@ def covariance_tracking(A, Bu, Bl, G, K, Q, R, Wu, Sigma0, N, path=0, bf16_terms
     nlin = 1 or N - 1; K [mu][mx], [nK][mu][mx] or [n_gains][nK][mu][mx] with nK = 1 or N - 1; Q, R one pair or one per problem (None with want_cost = want_total = False);
     Wu [mu][mu] or [n][mu][mu], Sigma0 [mx][mx] or [n][mx][mx], either None (= 0) -> Sigma [nprob][mx][mx] = Σ_{N-1}, Sigma_all [nprob][N][mx][mx], cost [nprob][N][2],
     zstd [nprob][N][mx], ustd [nprob][N][mu], total [nprob][2]; want_* = False pass NULL (returned as None)"""
-    A = f64(A)
-    if A.ndim != 4 or A.shape[-1] != A.shape[-2]:
-        raise ValueError("A must be [nprob][nlin][mx][mx] (got %s)" % (A.shape,))
-    nprob, nlin, mx = A.shape[0], A.shape[1], A.shape[-1]
-    Bu, Bl = f64(Bu), f64(Bl)
-    Bu = Bu.reshape(nprob, nlin, mx, -1) if Bu.size else Bu.reshape(nprob, nlin, mx, 0)
-    mu = Bu.shape[3]
-    Bl = Bl.reshape(nprob, nlin, mx, -1) if Bl.size else Bl.reshape(nprob, nlin, mx, 0)
-    ml = Bl.shape[3]
-    G = f64(G).reshape(nprob, nlin, ml, mx)
-    K = f64(K)
-    if K.ndim not in (2, 3, 4) or K.shape[-2:] != (mu, mx):
-        raise ValueError("K must be [mu][mx], [nK][mu][mx] or [n_gains][nK][mu][mx] with mu = %d, mx = %d (got %s)" % (mu, mx, K.shape))
-    K = K.reshape((1,) * (4 - K.ndim) + K.shape)
-    nw = 1
-    if Q is not None:
-        Q = f64(Q).reshape(-1, mx, mx)
-        nw = Q.shape[0]
-        R = f64(R).reshape(nw, mu, mu)
+    models, dims = _models(A, Bu, Bl, G, tracked=True)
+    nprob, mx, mu, ml = dims
+    K = _gains(K, mu, mx, full=4, lowest=2)
+    Q, R, nw = _weights(Q, R, mx, mu, optional=True)
     Wu, Sigma0, n_noise = _noise_arrays(Wu, Sigma0, mu, mx)
     N = int(N)
     S = np.zeros((nprob, mx, mx))
@@ -1049,10 +942,9 @@ def covariance_tracking(A, Bu, Bl, G, K, Q, R, Wu, Sigma0, N, path=0, bf16_terms
     ustd = np.zeros((nprob, N, mu)) if want_std else None
     total = np.zeros((nprob, 2)) if want_total else None
     o = RiccatiOpts(int(path), int(bf16_terms), 0, 0)
-    check(lib().cclqr_covariance_tracking(C.c_int32(nprob), C.c_int32(mx), C.c_int32(mu), C.c_int32(ml), C.c_int32(nlin), _d(A), _d(Bu) if mu else None,
-                                          _d(Bl) if ml else None, _d(G) if ml else None, C.c_int32(K.shape[0]), C.c_int32(K.shape[1]), _d(K) if K.size else None,
-                                          C.c_int32(nw), _d(Q), _d(R) if (mu and R is not None) else None, C.c_int32(n_noise), _d(Wu), _d(Sigma0), C.c_int32(N), _d(S),
-                                          _d(Sall), _d(cost), _d(zstd), _d(ustd) if mu else None, _d(total), C.byref(o)))
+    check(lib().cclqr_covariance_tracking(*_model_args(dims, models), C.c_int32(K.shape[0]), C.c_int32(K.shape[1]), _panel(K), C.c_int32(nw),
+                                          _d(Q), _panel(R), C.c_int32(n_noise), _d(Wu), _d(Sigma0), C.c_int32(N), _d(S), _d(Sall), _d(cost), _d(zstd), _panel(ustd),
+                                          _d(total), C.byref(o)))
     return S, Sall, cost, zstd, ustd, total
 
 
@@ -1061,26 +953,13 @@ def value_create_covariance_tracking(mech, ctrl, zd, n, N, ctrl_joint, Q, R, Wu,
     """cclqr_value_create_covariance_tracking: the covariance above for controller handle `ctrl`'s gain rows along n trajectories zd [n][N][nb][13] (Fd [n][N][mu]),
     linearised at the knots 0 .. N-2 on plant first_plant + k; numpy arrays, or with on_device=True device addresses read in place on `stream`.  Q, Sigma0 in the
     mechanism's body order -> (ValueHandle of n tables holding Σ_{N-1}, cost [n][N][2], zstd [n][N][12 nb], ustd [n][N][mu], total [n][2])"""
-    nb = mech.tables.nb
-    n, N = int(n), int(N)
-    cj = i32(ctrl_joint).reshape(-1)
-    mu = len(cj)
-    if on_device:
-        zp, fp = C.c_void_p(int(zd)), (None if Fd is None else C.c_void_p(int(Fd)))
-    else:
-        zd = f64(zd).reshape(n, N, nb, 13)
-        Fd = None if Fd is None else f64(Fd).reshape(n, N, mu)
-        zp, fp = _d(zd), _d(Fd)
-    Q = f64(Q).reshape(-1, 12 * nb, 12 * nb)
-    nw = Q.shape[0]
-    R = f64(R).reshape(nw, mu, mu)
-    Wu, Sigma0, n_noise = _noise_arrays(Wu, Sigma0, mu, 12 * nb)
-    cost, zstd, ustd, total = np.zeros((n, N, 2)), np.zeros((n, N, 12 * nb)), np.zeros((n, N, mu)), np.zeros((n, 2))
+    n, N, mu, mx = int(n), int(N), np.size(ctrl_joint), 12 * mech.tables.nb
+    head = _trajectory_args(mech, ctrl, zd, n, N, ctrl_joint, Fd, Q, R, plants, first_plant, on_device)
+    Wu, Sigma0, n_noise = _noise_arrays(Wu, Sigma0, mu, mx)
+    cost, zstd, ustd, total = np.zeros((n, N, 2)), np.zeros((n, N, mx)), np.zeros((n, N, mu)), np.zeros((n, 2))
     vptr = C.c_void_p()
-    check(lib().cclqr_value_create_covariance_tracking(mech.ptr, None if plants is None else plants.ptr, C.c_int64(int(first_plant)), C.c_int32(n), C.c_int32(N), zp, fp,
-                                                       C.c_int32(1 if on_device else 0), C.c_int32(mu), _i(cj), ctrl.ptr, C.c_int32(nw), _d(Q), _d(R), C.c_int32(n_noise),
-                                                       _d(Wu), _d(Sigma0), C.c_int64(int(workspace_bytes)), _d(cost), _d(zstd), _d(ustd), _d(total),
-                                                       None if stream is None else C.c_void_p(int(stream)), C.byref(vptr)))
+    check(lib().cclqr_value_create_covariance_tracking(*head, C.c_int32(n_noise), _d(Wu), _d(Sigma0), C.c_int64(int(workspace_bytes)), _d(cost), _d(zstd), _d(ustd),
+                                                       _d(total), None if stream is None else C.c_void_p(int(stream)), C.byref(vptr)))
     return ValueHandle(mech, ptr=vptr, n_tables=n), cost, zstd, ustd, total
 
 
@@ -1089,23 +968,10 @@ def policy_value_tracking(A, Bu, Bl, G, K, Q, R, Wu, N, path=0, bf16_terms=0, wa
     trackingLQR_triple_cartpole.jl:98): P_{N-1} = Q, P_j = Q + K_j' R K_j + Abar_j' P_{j+1} Abar_j, price_j = tr(Wu D_j' P_{j+1} D_j).  Models, K, Q, R as
     covariance_tracking takes them (Q, R required); Wu [mu][mu] or [n][mu][mu], or None: no price -> P [nprob][mx][mx] = P_0, P_all [nprob][N][mx][mx],
     price [nprob][N], noise_total [nprob]; want_* = False pass NULL (returned as None), as does Wu = None for the last two"""
-    A = f64(A)
-    if A.ndim != 4 or A.shape[-1] != A.shape[-2]:
-        raise ValueError("A must be [nprob][nlin][mx][mx] (got %s)" % (A.shape,))
-    nprob, nlin, mx = A.shape[0], A.shape[1], A.shape[-1]
-    Bu, Bl = f64(Bu), f64(Bl)
-    Bu = Bu.reshape(nprob, nlin, mx, -1) if Bu.size else Bu.reshape(nprob, nlin, mx, 0)
-    mu = Bu.shape[3]
-    Bl = Bl.reshape(nprob, nlin, mx, -1) if Bl.size else Bl.reshape(nprob, nlin, mx, 0)
-    ml = Bl.shape[3]
-    G = f64(G).reshape(nprob, nlin, ml, mx)
-    K = f64(K)
-    if K.ndim not in (2, 3, 4) or K.shape[-2:] != (mu, mx):
-        raise ValueError("K must be [mu][mx], [nK][mu][mx] or [n_gains][nK][mu][mx] with mu = %d, mx = %d (got %s)" % (mu, mx, K.shape))
-    K = K.reshape((1,) * (4 - K.ndim) + K.shape)
-    Q = f64(Q).reshape(-1, mx, mx)
-    nw = Q.shape[0]
-    R = f64(R).reshape(nw, mu, mu)
+    models, dims = _models(A, Bu, Bl, G, tracked=True)
+    nprob, mx, mu, ml = dims
+    K = _gains(K, mu, mx, full=4, lowest=2)
+    Q, R, nw = _weights(Q, R, mx, mu)
     Wu, _, n_noise = _noise_arrays(Wu, None, mu, mx)
     N = int(N)
     P = np.zeros((nprob, mx, mx)) if want_P else None
@@ -1113,10 +979,8 @@ def policy_value_tracking(A, Bu, Bl, G, K, Q, R, Wu, N, path=0, bf16_terms=0, wa
     price = np.zeros((nprob, N)) if (want_price and Wu is not None) else None
     total = np.zeros(nprob) if (want_total and Wu is not None) else None
     o = RiccatiOpts(int(path), int(bf16_terms), 0, 0)
-    check(lib().cclqr_policy_value_tracking(C.c_int32(nprob), C.c_int32(mx), C.c_int32(mu), C.c_int32(ml), C.c_int32(nlin), _d(A), _d(Bu) if mu else None,
-                                            _d(Bl) if ml else None, _d(G) if ml else None, C.c_int32(K.shape[0]), C.c_int32(K.shape[1]), _d(K) if K.size else None,
-                                            C.c_int32(nw), _d(Q), _d(R) if mu else None, C.c_int32(n_noise), _d(Wu), C.c_int32(N), _d(P), _d(Pall), _d(price), _d(total),
-                                            C.byref(o)))
+    check(lib().cclqr_policy_value_tracking(*_model_args(dims, models), C.c_int32(K.shape[0]), C.c_int32(K.shape[1]), _panel(K), C.c_int32(nw), _d(Q), _panel(R),
+                                            C.c_int32(n_noise), _d(Wu), C.c_int32(N), _d(P), _d(Pall), _d(price), _d(total), C.byref(o)))
     return P, Pall, price, total
 
 
@@ -1124,25 +988,12 @@ def value_create_policy_tracking(mech, ctrl, zd, n, N, ctrl_joint, Q, R, Wu, kno
     """cclqr_value_create_policy_tracking: the cost-to-go above for controller handle `ctrl`'s gain rows along n trajectories zd [n][N][nb][13] (Fd [n][N][mu]),
     linearised at the knots 0 .. N-2 on plant first_plant + k; numpy arrays, or with on_device=True device addresses read in place on `stream`.  Q in the mechanism's
     body order; the recursion runs down to `knot` -> (ValueHandle of n tables holding P_knot, price [n][N], noise_total [n]); Wu = None: the last two are None"""
-    nb = mech.tables.nb
     n, N = int(n), int(N)
-    cj = i32(ctrl_joint).reshape(-1)
-    mu = len(cj)
-    if on_device:
-        zp, fp = C.c_void_p(int(zd)), (None if Fd is None else C.c_void_p(int(Fd)))
-    else:
-        zd = f64(zd).reshape(n, N, nb, 13)
-        Fd = None if Fd is None else f64(Fd).reshape(n, N, mu)
-        zp, fp = _d(zd), _d(Fd)
-    Q = f64(Q).reshape(-1, 12 * nb, 12 * nb)
-    nw = Q.shape[0]
-    R = f64(R).reshape(nw, mu, mu)
-    Wu, _, n_noise = _noise_arrays(Wu, None, mu, 12 * nb)
+    head = _trajectory_args(mech, ctrl, zd, n, N, ctrl_joint, Fd, Q, R, plants, first_plant, on_device)
+    Wu, _, n_noise = _noise_arrays(Wu, None, np.size(ctrl_joint), 12 * mech.tables.nb)
     price, total = (np.zeros((n, N)), np.zeros(n)) if Wu is not None else (None, None)
     vptr = C.c_void_p()
-    check(lib().cclqr_value_create_policy_tracking(mech.ptr, None if plants is None else plants.ptr, C.c_int64(int(first_plant)), C.c_int32(n), C.c_int32(N), zp, fp,
-                                                   C.c_int32(1 if on_device else 0), C.c_int32(mu), _i(cj), ctrl.ptr, C.c_int32(nw), _d(Q), _d(R), C.c_int32(n_noise),
-                                                   _d(Wu), C.c_int32(int(knot)), C.c_int64(int(workspace_bytes)), _d(price), _d(total),
+    check(lib().cclqr_value_create_policy_tracking(*head, C.c_int32(n_noise), _d(Wu), C.c_int32(int(knot)), C.c_int64(int(workspace_bytes)), _d(price), _d(total),
                                                    None if stream is None else C.c_void_p(int(stream)), C.byref(vptr)))
     return ValueHandle(mech, ptr=vptr, n_tables=n), price, total
 
@@ -1153,19 +1004,9 @@ def riccati_doubling(A, Bu, Bl, G, Q, R, N, tol=1e-5, max_levels=40, bf16_terms=
     at most max_levels levels) -> K [nprob][mu][mx], P [nprob][mx][mx], levels [nprob], reason [nprob] (0 converged, 1 max_levels, 2 norm(A) > 1e50 or not finite,
     3 pivot), dnorm [nprob][2], anorm [nprob][2].  want_P=False passes P = NULL, want_diag=False NULL for the four diagnostics (returned as None); K, P: arrays to
     write into instead of fresh ones"""
-    A = f64(A)
-    mx = A.shape[-1]
-    A = A.reshape(-1, mx, mx)
-    nprob = A.shape[0]
-    Bu, Bl = f64(Bu), f64(Bl)
-    Bu = Bu.reshape(nprob, mx, Bu.shape[-1] if Bu.ndim > 1 else -1)
-    mu = Bu.shape[2]
-    Bl = Bl.reshape(nprob, mx, Bl.shape[-1] if Bl.ndim > 1 else -1)
-    ml = Bl.shape[2]
-    G = f64(G).reshape(nprob, ml, mx)
-    Q = f64(Q).reshape(-1, mx, mx)
-    nw = Q.shape[0]
-    R = f64(R).reshape(nw, mu, mu)
+    models, dims = _models(A, Bu, Bl, G)
+    nprob, mx, mu, ml = dims
+    Q, R, nw = _weights(Q, R, mx, mu)
     if K is None:
         K = np.zeros((nprob, mu, mx))
     if K.shape != (nprob, mu, mx) or K.dtype != np.float64 or not K.flags.c_contiguous:
@@ -1174,32 +1015,21 @@ def riccati_doubling(A, Bu, Bl, G, Q, R, N, tol=1e-5, max_levels=40, bf16_terms=
         P = np.zeros((nprob, mx, mx))
     if P is not None and (P.shape != (nprob, mx, mx) or P.dtype != np.float64 or not P.flags.c_contiguous):
         raise ValueError("P must be a contiguous float64 [nprob][mx][mx] = %s (got %s)" % ((nprob, mx, mx), P.shape))
-    lv = np.zeros(nprob, dtype=np.int32) if want_diag else None
-    rs = np.zeros(nprob, dtype=np.int32) if want_diag else None
-    dn = np.zeros((nprob, 2)) if want_diag else None
-    an = np.zeros((nprob, 2)) if want_diag else None
+    lv, rs, dn, an = _diagnostics(nprob, want_diag)
     o = RiccatiOpts(0, int(bf16_terms), 1, 0)
-    check(lib().cclqr_riccati_doubling(C.c_int32(nprob), C.c_int32(mx), C.c_int32(mu), C.c_int32(ml), _d(A), _d(Bu) if mu else None, _d(Bl) if ml else None,
-                                       _d(G) if ml else None, C.c_int32(nw), _d(Q), _d(R) if mu else None, C.c_int32(int(N)), C.c_double(float(tol)),
-                                       C.c_int32(int(max_levels)), _d(K) if K.size else None, _d(P), _i(lv), _i(rs), _d(dn), _d(an), C.byref(o)))
+    check(lib().cclqr_riccati_doubling(*_model_args(dims, models), C.c_int32(nw), _d(Q), _panel(R), C.c_int32(int(N)), C.c_double(float(tol)), C.c_int32(int(max_levels)),
+                                       _panel(K), _d(P), _i(lv), _i(rs), _d(dn), _d(an), C.byref(o)))
     return K, P, lv, rs, dn, an
 
 
 def riccati_tv(A, Bu, Bl, G, Q, R, N, tol=1e-5):
     """time-varying dlqr on caller-supplied per-knot models: A [N-1][mx][mx], Bu [N-1][mx][mu], Bl [N-1][mx][ml], G [N-1][ml][mx] -> K [N-1][mu][mx], kbreak"""
-    A = f64(A)
-    nk, mx = A.shape[0], A.shape[1]
+    models, dims = _models(A, Bu, Bl, G)
+    nk, mx, mu, ml = dims
     assert nk == N - 1
-    Bu, Bl = f64(Bu), f64(Bl)
-    Bu = Bu.reshape(nk, mx, Bu.shape[-1] if Bu.ndim > 1 else -1)
-    mu = Bu.shape[2]
-    Bl = Bl.reshape(nk, mx, Bl.shape[-1] if Bl.ndim > 1 else -1)
-    ml = Bl.shape[2]
-    G = f64(G).reshape(nk, ml, mx)
     K = np.zeros((nk, mu, mx))
     kb = np.zeros(1, dtype=np.int32)
-    check(lib().cclqr_riccati_tv(C.c_int32(mx), C.c_int32(mu), C.c_int32(ml), _d(A), _d(Bu), _d(Bl) if ml else None, _d(G) if ml else None,
-                                 _d(f64(Q)), _d(f64(R)), C.c_int32(int(N)), C.c_double(float(tol)), _d(K), _i(kb)))
+    check(lib().cclqr_riccati_tv(*_model_args(dims, models)[1:], _d(f64(Q)), _panel(f64(R)), C.c_int32(int(N)), C.c_double(float(tol)), _d(K), _i(kb)))
     return K, int(kb[0])
 
 

@@ -108,6 +108,84 @@ def _scaled_pairs(Qs, Rs, bodyids, nb, mu, horizon, Δt, symmetric=False):
     return np.stack(Qm), np.stack(Rm), Ntemp
 
 
+def _model_set(mechanism, controller, plants, zd, Q, R, zd_is="[n_models][nb][13]", of="model"):
+    """the head of the constructors that take a set of models (PolicyValue, the Stationary* classes): whose mechanism the controller and the plants are, zd as
+    [n][nb][13] (`zd_is`: how the refusal names it), Q and R as lists of 1 or n candidates (one per `of`) -> (zd, n, Qs, Rs)"""
+    if controller is not None and controller.mechanism is not mechanism:
+        raise ValueError("the controller was made for another mechanism")
+    if plants is not None and plants.mechanism is not mechanism:
+        raise ValueError("the PlantBatch was made for another mechanism")
+    nb = len(mechanism.bodies)
+    zd = np.ascontiguousarray(zd, dtype=np.float64)
+    if zd.ndim != 3 or zd.shape[1:] != (nb, 13) or zd.shape[0] < 1:
+        raise ValueError("zd must be %s = [n][%d][13], one setpoint per %s (got %s)" % (zd_is, nb, of, zd.shape))
+    n = zd.shape[0]
+    return (zd, n) + _pair_lists(Q, R, n, of)
+
+
+def _model_set_fields(self, mechanism, bodyids, eqcids, Qs, Rs, horizon, zd, plants, first_plant, Fτd, Fd_refusal="Fτd must be [n_models][mu] = [%d][%d]", hold=False,
+                      symmetric=False):
+    """... and their tail: Fτd as [n][mu] (hold: zeros when None), the Δt-scaled weights in the mechanism's body order, every model's
+    plant found; sets mechanism, plants, first_plant, eqcids, ctrl_joints, Q, R, zd, Fd on `self` -> the knots Ntemp of `horizon`"""
+    nb, mu, n = len(mechanism.bodies), len(eqcids), zd.shape[0]
+    Fd = (np.zeros((n, mu)) if hold else None) if Fτd is None else np.ascontiguousarray(Fτd, dtype=np.float64).reshape(-1, mu)
+    if Fd is not None and Fd.shape[0] != n:
+        raise ValueError(Fd_refusal % (n, mu))
+    Qm, Rm, Ntemp = _scaled_pairs(Qs, Rs, bodyids, nb, mu, horizon, mechanism.Δt, symmetric=symmetric)
+    self.first_plant = (0 if plants is None else plants.first_index) if first_plant is None else int(first_plant)
+    if plants is not None:
+        plants.rows_for(self.first_plant, n)      # every model must find its plant
+    self.mechanism, self.plants = mechanism, plants
+    self.eqcids = [int(e) for e in eqcids]
+    self.ctrl_joints = [mechanism.joint_index(e) for e in self.eqcids]
+    self.Q, self.R = Qm, Rm      # [n_weights][12 nb][12 nb], [n_weights][mu][mu]: scaled, mechanism body order
+    self.zd, self.Fd = zd, Fd
+    return Ntemp
+
+
+def _doubling_limits(horizon, max_levels, tol):
+    """what a doubling constructor refuses of max_levels and tol -> (max_levels, the horizon the knots are counted over: math.inf for horizon=None, a run to convergence)"""
+    max_levels = int(max_levels)
+    if horizon is None and not 1 <= max_levels <= 60:
+        raise ValueError("max_levels = %d: a run to convergence makes 1 .. 60 levels (2^max_levels steps)" % max_levels)
+    if not float(tol) >= 0.0:
+        raise ValueError("tol = %r is negative or not a number" % (tol,))
+    return max_levels, math.inf if horizon is None else horizon
+
+
+def _doubling_result(self, Ntemp, gnorm=None):
+    """what a doubling constructor reports next to levels and reason [n]: steps = 2^levels of a run to convergence (Ntemp = 0), else the horizon's N - 1; converged =
+    reason == 0 of such a run; with the norms gnorm [n][2] of the last two levels also diverged = reason == 2 and the spectral-radius estimate"""
+    to_convergence = Ntemp == 0
+    self.steps = 2 ** self.levels.astype(np.int64) if to_convergence else np.full(len(self.levels), Ntemp - 1, dtype=np.int64)
+    self.converged = (self.reason == 0) & to_convergence
+    if gnorm is not None:
+        self.diverged = (self.reason == 2) & to_convergence
+        with np.errstate(invalid="ignore", divide="ignore"):
+            self.spectral_radius = (gnorm[:, 0] / gnorm[:, 1]) ** (1.0 / 2.0 ** (self.levels - 1))
+
+
+def _noise_arguments(self, bodyids, nb, mu, n, noise_scale, Wu, Sigma0):
+    """the noise of the covariance and tracking classes: noise_scale or Wu ([mu][mu] or one per model), and a start covariance Sigma0 in the order of bodyids ([12 nb][12 nb]
+    or one per model) -> (Wu, Sigma0 in the mechanism's body order), either None; sets _to_bodyids on `self`"""
+    if noise_scale is not None and Wu is not None:
+        raise ValueError("noise_scale and Wu are both given: noise_scale IS Wu = noise_scale^2 ones((mu, mu))")
+    if noise_scale is not None:
+        Wu = float(noise_scale) ** 2 * np.ones((mu, mu))
+    if Wu is not None:
+        Wu = np.ascontiguousarray(Wu, dtype=np.float64)
+        if Wu.shape not in ((mu, mu), (n, mu, mu)):
+            raise ValueError("Wu must be [mu][mu] = [%d][%d] or a list of one per model, %d (got %s)" % (mu, mu, n, Wu.shape))
+    inv = _body_order(bodyids, nb)
+    self._to_bodyids = np.concatenate([12 * inv[m] + np.arange(12) for m in range(nb)])      # mechanism-order coordinate -> its place in the order of bodyids
+    if Sigma0 is not None:
+        Sigma0 = np.ascontiguousarray(Sigma0, dtype=np.float64)
+        if Sigma0.shape not in ((12 * nb, 12 * nb), (n, 12 * nb, 12 * nb)):
+            raise ValueError("Sigma0 must be [12 nb][12 nb] = [%d][%d] or a list of one per model, %d (got %s)" % (12 * nb, 12 * nb, n, Sigma0.shape))
+        Sigma0 = np.ascontiguousarray(Sigma0[..., self._to_bodyids, :][..., :, self._to_bodyids])
+    return Wu, Sigma0
+
+
 class Controller:
     """abstract type owned by ConstrainedDynamics (lqr.jl:3 `<: Controller`)"""
 
@@ -252,7 +330,50 @@ class _BorrowedCtrl:
         pass
 
 
-class PlantLQR(Controller):
+def _borrow_tables(controller, dev, fric, noise_scale, noise_seed, law_refusal=None):
+    """the _ctrl_handle of a controller whose tables stay on the device (PlantLQR, LQRSweep, StationaryLQR, PlantTrackingLQR): its own cclqr_ctrl*, borrowed -- no other
+    law than the one it was built with, table i for instance i, on the device handle it was designed on"""
+    name = type(controller).__name__
+    if fric is not None or noise_scale or noise_seed is not None:
+        raise ValueError(law_refusal or "%s carries neither joint friction nor noise: the batched constructor builds the plain LQR law" % name)
+    if controller.first_plant != 0:
+        raise ValueError("a rollout reads controller table and plant by the global instance index: %s %s that is rolled out starts at plant 0 "
+                         "(this one at plant %d)" % ("an" if name.startswith("LQR") else "a", name, controller.first_plant))
+    if controller._handle.mech is not dev or not controller._handle.ptr:
+        raise ValueError("the %s was designed on another device handle of the mechanism" % name)
+    return _BorrowedCtrl(controller._handle)
+
+
+class _BatchedLQR(Controller):
+    """what PlantLQR, LQRSweep and StationaryLQR share: one gain table per plant / candidate / setpoint behind self._handle, which never leaves the device"""
+
+    def _riccati_result(self, N, Ntemp):
+        """kbreak and converged [n] of the batched recursion, as LQR's"""
+        self.kbreak = self._handle.kbreak
+        # LQR{T,Inf} (lqr.jl:40-42): converged when Ku[1] == Ku[2], i.e. when the recursion met its tolerance and back-filled the rest (kbreak > 1)
+        self.converged = np.ones(len(self.kbreak), dtype=bool) if N < math.inf else ((self.kbreak > 1) | (Ntemp < 3))
+        if not self.converged.all():
+            print("[ Info: Riccati recursion did not converge.")      # lqr.jl:41
+
+    def _ctrl_handle(self, dev, fric=None, noise_scale=0.0, noise_seed=None):
+        return _borrow_tables(self, dev, fric, noise_scale, noise_seed)
+
+    def gains(self, i):
+        """K[k][j] of table i, [nK][mu][12 nb] in the mechanism's body order, read back from the device (cclqr_ctrl_get_gains)"""
+        return _capi.ctrl_gains(_device_mech(self.mechanism), self._handle, i)
+
+    def P(self, i):
+        """table i's cost-to-go [12 nb][12 nb] (lqr.jl:170 at the recursion's last executed step), mechanism body order, read back from the device (keep_value=True)"""
+        return _kept_value(self, _device_mech(self.mechanism))[0].get(i)
+
+    def _value_handle(self, dev):
+        return _kept_value(self, dev)
+
+    def close(self):
+        self._handle.close()
+
+
+class PlantLQR(_BatchedLQR):
     """One LQR per plant of a PlantBatch, designed in one call: for every plant k, LQR(mechanism_k, bodyids, eqcids, Q, R, horizon; xd, vd, qd, ωd, Fτd)
     (lqr.jl:49-66) where mechanism_k is the mechanism rebuilt with plant k's masses, inertias and joint vertices -- one batched linearsystem (lqr.jl:63) and one
     batched dlqr (lqr.jl:141-184) on the device, the gains never leaving it (cclqr_ctrl_create_lqr_batch_plants).
@@ -300,38 +421,10 @@ class PlantLQR(Controller):
         dev = _device_mech(mechanism)
         self._handle = _capi.BatchLqrHandle(dev, zd, self.ctrl_joints, self.Q, self.R, Ntemp, Fd=Fd, tol=tol, infinite_horizon=N == math.inf,
                                             plants=plants.handle(dev), first_plant=self.first_plant, keep_value=keep_value)
-        self.kbreak = self._handle.kbreak
-        # LQR{T,Inf} (lqr.jl:40-42): converged when Ku[1] == Ku[2], i.e. when the recursion met its tolerance and back-filled the rest (kbreak > 1)
-        self.converged = np.ones(n, dtype=bool) if N < math.inf else ((self.kbreak > 1) | (Ntemp < 3))
-        if not self.converged.all():
-            print("[ Info: Riccati recursion did not converge.")      # lqr.jl:41
-
-    def _ctrl_handle(self, dev, fric=None, noise_scale=0.0, noise_seed=None):
-        if fric is not None or noise_scale or noise_seed is not None:
-            raise ValueError("PlantLQR carries neither joint friction nor noise: the batched constructor builds the plain LQR law")
-        if self.first_plant != 0:
-            raise ValueError("a rollout reads controller table and plant by the global instance index: a PlantLQR that is rolled out starts at plant 0 "
-                             "(this one at plant %d)" % self.first_plant)
-        if self._handle.plants.mech is not dev or not self._handle.ptr:
-            raise ValueError("the PlantLQR was designed on another device handle of the mechanism")
-        return _BorrowedCtrl(self._handle)
-
-    def gains(self, i):
-        """K[k][j] of plant i's table, [nK][mu][12 nb] in the mechanism's body order, read back from the device (cclqr_ctrl_get_gains)"""
-        return _capi.ctrl_gains(_device_mech(self.mechanism), self._handle, i)
-
-    def P(self, i):
-        """plant i's cost-to-go [12 nb][12 nb] (lqr.jl:170 at the recursion's last executed step), mechanism body order, read back from the device (keep_value=True)"""
-        return _kept_value(self, _device_mech(self.mechanism))[0].get(i)
-
-    def _value_handle(self, dev):
-        return _kept_value(self, dev)
-
-    def close(self):
-        self._handle.close()
+        self._riccati_result(N, Ntemp)
 
 
-class LQRSweep(Controller):
+class LQRSweep(_BatchedLQR):
     """One LQR per weight candidate, designed in one call: for every k, LQR(mechanism, bodyids, eqcids, Qs[k], Rs[k], horizon; xd, vd, qd, ωd, Fτd) (lqr.jl:49-66) --
     one batched linearsystem (lqr.jl:63) and one batched dlqr (lqr.jl:141-184) in which problem k reads its own weights, the gains never leaving the device
     (cclqr_ctrl_create_lqr_batch_weights).  The tuning study: simulate(mech, steps, sweep, z0=start replicated, record=False, score=Score(one Q, R)) ranks the
@@ -401,36 +494,7 @@ class LQRSweep(Controller):
         self._handle = _capi.BatchLqrHandle(dev, zd, self.ctrl_joints, self.Q, self.R, Ntemp, Fd=Fd, tol=tol, infinite_horizon=N == math.inf,
                                             plants=None if plants is None else plants.handle(dev), first_plant=self.first_plant, n_weights=n,
                                             keep_value=keep_value)
-        self.kbreak = self._handle.kbreak
-        # LQR{T,Inf} (lqr.jl:40-42): converged when Ku[1] == Ku[2], i.e. when the recursion met its tolerance and back-filled the rest (kbreak > 1)
-        self.converged = np.ones(n, dtype=bool) if N < math.inf else ((self.kbreak > 1) | (Ntemp < 3))
-        if not self.converged.all():
-            print("[ Info: Riccati recursion did not converge.")      # lqr.jl:41
-
-    def _ctrl_handle(self, dev, fric=None, noise_scale=0.0, noise_seed=None):
-        if fric is not None or noise_scale or noise_seed is not None:
-            raise ValueError("LQRSweep carries neither joint friction nor noise: the batched constructor builds the plain LQR law")
-        if self.first_plant != 0:
-            raise ValueError("a rollout reads controller table and plant by the global instance index: an LQRSweep that is rolled out starts at plant 0 "
-                             "(this one at plant %d)" % self.first_plant)
-        if self._handle.mech is not dev or not self._handle.ptr:
-            raise ValueError("the LQRSweep was designed on another device handle of the mechanism")
-        return _BorrowedCtrl(self._handle)
-
-    def gains(self, i):
-        """K[k][j] of candidate i's table, [nK][mu][12 nb] in the mechanism's body order, read back from the device (cclqr_ctrl_get_gains)"""
-        return _capi.ctrl_gains(_device_mech(self.mechanism), self._handle, i)
-
-    def P(self, i):
-        """candidate i's cost-to-go [12 nb][12 nb] (lqr.jl:170 at the recursion's last executed step), mechanism body order, read back from the device
-        (keep_value=True)"""
-        return _kept_value(self, _device_mech(self.mechanism))[0].get(i)
-
-    def _value_handle(self, dev):
-        return _kept_value(self, dev)
-
-    def close(self):
-        self._handle.close()
+        self._riccati_result(N, Ntemp)
 
 
 class StationaryLQR(PlantLQR):
@@ -456,64 +520,62 @@ class StationaryLQR(PlantLQR):
             raise ValueError("StationaryLQR carries no controlfunction: its gains stay on the device (an LQR with a closure: build an LQR)")
         if not isinstance(mechanism, Mechanism):
             raise TypeError("StationaryLQR(mechanism, bodyids, eqcids, Q, R, zd; horizon, ...)")
-        if plants is not None and plants.mechanism is not mechanism:
-            raise ValueError("the PlantBatch was made for another mechanism")
         mechanism.tables()      # (sets has_loops)
         if mechanism.has_loops:
             raise ValueError("StationaryLQR is for tree mechanisms: the batched constructor does not take closed loops")
-        nb, mu = len(mechanism.bodies), len(eqcids)
-        zd = np.ascontiguousarray(zd, dtype=np.float64)
-        if zd.ndim != 3 or zd.shape[1:] != (nb, 13) or zd.shape[0] < 1:
-            raise ValueError("zd must be [n][nb][13] = [n][%d][13], one setpoint per table (got %s)" % (nb, zd.shape))
-        n = zd.shape[0]
-        Qs, Rs = _pair_lists(Q, R, n, "table")
-        max_levels = int(max_levels)
-        if horizon is None and not 1 <= max_levels <= 60:
-            raise ValueError("max_levels = %d: a run to convergence makes 1 .. 60 levels (2^max_levels steps)" % max_levels)
-        if not float(tol) >= 0.0:
-            raise ValueError("tol = %r is negative or not a number" % (tol,))
-        Fd = np.zeros((n, mu)) if Fτd is None else np.ascontiguousarray(Fτd, dtype=np.float64).reshape(-1, mu)
-        if Fd.shape[0] != n:
-            raise ValueError("Fτd must be [n][mu] = [%d][%d], one holding input per table and controlled constraint" % (n, mu))
-        Qm, Rm, Ntemp = _scaled_pairs(Qs, Rs, bodyids, nb, mu, math.inf if horizon is None else horizon, mechanism.Δt, symmetric=True)
+        zd, n, Qs, Rs = _model_set(mechanism, None, plants, zd, Q, R, zd_is="[n][nb][13]", of="table")
+        max_levels, span = _doubling_limits(horizon, max_levels, tol)
+        Ntemp = _model_set_fields(self, mechanism, bodyids, eqcids, Qs, Rs, span, zd, plants, first_plant, Fτd,
+                                  Fd_refusal="Fτd must be [n][mu] = [%d][%d], one holding input per table and controlled constraint", hold=True, symmetric=True)
         if horizon is None:
             Ntemp = 0
         if Ntemp == 1:
             raise ValueError("horizon = %r is one knot: a gain needs at least one backward step (N >= 2)" % (horizon,))
-        self.first_plant = (0 if plants is None else plants.first_index) if first_plant is None else int(first_plant)
-        if plants is not None:
-            plants.rows_for(self.first_plant, n)      # every table must find its plant
-        self.mechanism, self.plants, self.n_plant, self.n = mechanism, plants, n, n
-        self.eqcids = [int(e) for e in eqcids]
-        self.ctrl_joints = [mechanism.joint_index(e) for e in self.eqcids]
-        self.controlfunction = None
-        self.zd, self.Fd = zd, Fd
-        self.Q, self.R = Qm, Rm      # [n_weights][12 nb][12 nb], [n_weights][mu][mu]: scaled, mechanism body order
-        self.N, self.horizon_steps, self.NK = 0, math.inf, 12 * nb      # the device convention: one gain row, never gated
+        self.n_plant, self.n, self.controlfunction = n, n, None
+        self.N, self.horizon_steps, self.NK = 0, math.inf, 12 * len(mechanism.bodies)      # the device convention: one gain row, never gated
         self.tol, self.max_levels = float(tol), max_levels
         dev = _device_mech(mechanism)
-        self._handle = _capi.ctrl_create_lqr_batch_doubling(dev, zd, self.ctrl_joints, self.Q, self.R, Ntemp, Fd=Fd, tol=tol, max_levels=max_levels,
+        self._handle = _capi.ctrl_create_lqr_batch_doubling(dev, zd, self.ctrl_joints, self.Q, self.R, Ntemp, Fd=self.Fd, tol=tol, max_levels=max_levels,
                                                             plants=None if plants is None else plants.handle(dev), first_plant=self.first_plant,
                                                             keep_value=keep_value)
         h = self._handle
         self.levels, self.reason, self.dnorm, self.anorm, self.kbreak = h.levels, h.reason, h.dnorm, h.anorm, None
-        self.steps = 2 ** self.levels.astype(np.int64) if Ntemp == 0 else np.full(n, Ntemp - 1, dtype=np.int64)
-        self.converged = (self.reason == 0) & (Ntemp == 0)
+        _doubling_result(self, Ntemp)
         if Ntemp == 0 and not self.converged.all():
             print("[ Info: Riccati recursion did not converge.")      # lqr.jl:41
 
-    def _ctrl_handle(self, dev, fric=None, noise_scale=0.0, noise_seed=None):
-        if fric is not None or noise_scale or noise_seed is not None:
-            raise ValueError("StationaryLQR carries neither joint friction nor noise: the batched constructor builds the plain LQR law")
-        if self.first_plant != 0:
-            raise ValueError("a rollout reads controller table and plant by the global instance index: a StationaryLQR that is rolled out starts at plant 0 "
-                             "(this one at plant %d)" % self.first_plant)
-        if self._handle.mech is not dev or not self._handle.ptr:
-            raise ValueError("the StationaryLQR was designed on another device handle of the mechanism")
-        return _BorrowedCtrl(self._handle)
+
+class _ValueTables:
+    """what PolicyValue, StationaryPolicyValue and TrackingPolicyValue share: the device-resident costs-to-go self._value of n_models models, evaluated on the device
+    handle self._dev about the setpoints self.zd [n_models][nb][13] -- what predicted_cost reads them through"""
+
+    def P(self, i):
+        """model i's cost-to-go [12 nb][12 nb], mechanism body order, read back from the device (cclqr_value_get)"""
+        return self._value.get(i)
+
+    def _value_handle(self, dev):
+        if self._value.mech is not dev or not self._value.ptr:
+            raise ValueError("the %s was evaluated on another device handle of the mechanism" % type(self).__name__)
+        return self._value, False
+
+    def _ctrl_handle(self, dev, **law):
+        """a setpoint-only controller of n_models tables built from zd: what predicted_cost measures model i's error about"""
+        if law:
+            raise TypeError("a %s is not a Controller: it holds costs-to-go, not a control law" % type(self).__name__)
+        if dev is not self._dev:
+            raise ValueError("the %s was evaluated on another device handle of the mechanism" % type(self).__name__)
+        if self._setpoints is None:
+            self._setpoints = _capi.CtrlHandle(dev, self.ctrl_joints, K=None, N=0, zd=self.zd, n_ctrl=self.n_models if self.n_models > 1 else 0)
+        return _BorrowedCtrl(self._setpoints)
+
+    def close(self):
+        if self._setpoints is not None:
+            self._setpoints.close()
+            self._setpoints = None
+        self._value.close()
 
 
-class PolicyValue:
+class PolicyValue(_ValueTables):
     """Policy evaluation: what the gains of `controller` cost on OTHER models than the one they were designed on, and whether that closed loop is stable there -- the
     question a robustness study starts with (the nominal controller on plant n), answered on the linear model instead of by a nonlinear rollout per plant.  For every
     model i -- linearsystem (lqr.jl:63) at zd[i] on plant first_plant + i -- dlqr's cost recursion (lqr.jl:147-177) runs with the gain GIVEN (in place of lqr.jl:160):
@@ -537,64 +599,20 @@ class PolicyValue:
             raise TypeError("PolicyValue(mechanism, controller, bodyids, eqcids, Q, R, horizon, zd; ...)")
         if not isinstance(controller, (LQR, PlantLQR, LQRSweep)):
             raise TypeError("PolicyValue evaluates the gains of an LQR, PlantLQR or LQRSweep (got %s)" % type(controller).__name__)
-        if controller.mechanism is not mechanism:
-            raise ValueError("the controller was made for another mechanism")
-        if plants is not None and plants.mechanism is not mechanism:
-            raise ValueError("the PlantBatch was made for another mechanism")
-        nb, mu = len(mechanism.bodies), len(eqcids)
-        zd = np.ascontiguousarray(zd, dtype=np.float64)
-        if zd.ndim != 3 or zd.shape[1:] != (nb, 13) or zd.shape[0] < 1:
-            raise ValueError("zd must be [n_models][nb][13] = [n][%d][13], one setpoint per model (got %s)" % (nb, zd.shape))
-        n = zd.shape[0]
-        Qs, Rs = _pair_lists(Q, R, n, "model")
-        Fd = None if Fτd is None else np.ascontiguousarray(Fτd, dtype=np.float64).reshape(-1, mu)
-        if Fd is not None and Fd.shape[0] != n:
-            raise ValueError("Fτd must be [n_models][mu] = [%d][%d]" % (n, mu))
-        Qm, Rm, Ntemp = _scaled_pairs(Qs, Rs, bodyids, nb, mu, horizon, mechanism.Δt)
-        self.first_plant = (0 if plants is None else plants.first_index) if first_plant is None else int(first_plant)
-        if plants is not None:
-            plants.rows_for(self.first_plant, n)      # every model must find its plant
-        self.mechanism, self.controller, self.plants, self.n_models = mechanism, controller, plants, n
-        self.eqcids = [int(e) for e in eqcids]
-        self.ctrl_joints = [mechanism.joint_index(e) for e in self.eqcids]
-        self.Q, self.R = Qm, Rm      # [n_weights][12 nb][12 nb], [n_weights][mu][mu]: scaled, mechanism body order
-        self.zd, self.Fd, self.N, self.tol = zd, Fd, Ntemp, float(tol)
+        zd, n, Qs, Rs = _model_set(mechanism, controller, plants, zd, Q, R)
+        Ntemp = _model_set_fields(self, mechanism, bodyids, eqcids, Qs, Rs, horizon, zd, plants, first_plant, Fτd)
+        self.controller, self.n_models, self.N, self.tol = controller, n, Ntemp, float(tol)
         dev = _device_mech(mechanism)
         self._dev, self._setpoints = dev, None
         ctrl = controller._ctrl_handle(dev)
         try:
-            self._value, self.kbreak, self.dnorm = _capi.value_create_policy(dev, ctrl, zd, self.ctrl_joints, self.Q, self.R, Ntemp, tol=tol, Fd=Fd,
+            self._value, self.kbreak, self.dnorm = _capi.value_create_policy(dev, ctrl, zd, self.ctrl_joints, self.Q, self.R, Ntemp, tol=tol, Fd=self.Fd,
                                                                              plants=None if plants is None else plants.handle(dev), first_plant=self.first_plant)
         finally:
             ctrl.close()
         self.converged = self.dnorm[:, 0] < self.tol
         with np.errstate(invalid="ignore", divide="ignore"):
             self.contraction = np.sqrt(self.dnorm[:, 0] / self.dnorm[:, 1])
-
-    def P(self, i):
-        """model i's cost-to-go [12 nb][12 nb], mechanism body order, read back from the device (cclqr_value_get)"""
-        return self._value.get(i)
-
-    def _value_handle(self, dev):
-        if self._value.mech is not dev or not self._value.ptr:
-            raise ValueError("the PolicyValue was evaluated on another device handle of the mechanism")
-        return self._value, False
-
-    def _ctrl_handle(self, dev, **law):
-        """a setpoint-only controller of n_models tables built from zd: what predicted_cost measures model i's error about"""
-        if law:
-            raise TypeError("a PolicyValue is not a Controller: it holds costs-to-go, not a control law")
-        if dev is not self._dev:
-            raise ValueError("the PolicyValue was evaluated on another device handle of the mechanism")
-        if self._setpoints is None:
-            self._setpoints = _capi.CtrlHandle(dev, self.ctrl_joints, K=None, N=0, zd=self.zd, n_ctrl=self.n_models if self.n_models > 1 else 0)
-        return _BorrowedCtrl(self._setpoints)
-
-    def close(self):
-        if self._setpoints is not None:
-            self._setpoints.close()
-            self._setpoints = None
-        self._value.close()
 
 
 def _stationary_arguments(self, name, verb, mechanism, controller, bodyids, eqcids, Q, R, horizon, zd, plants, first_plant, Fτd, tol, max_levels):
@@ -605,42 +623,19 @@ def _stationary_arguments(self, name, verb, mechanism, controller, bodyids, eqci
         raise TypeError("%s(mechanism, controller, bodyids, eqcids, Q, R, horizon, zd; ...)" % name)
     if not isinstance(controller, (LQR, PlantLQR, LQRSweep)):
         raise ValueError("%s %s the stationary gain of an LQR, PlantLQR or LQRSweep (got %s)" % (name, verb, type(controller).__name__))
-    if controller.mechanism is not mechanism:
-        raise ValueError("the controller was made for another mechanism")
-    if plants is not None and plants.mechanism is not mechanism:
-        raise ValueError("the PlantBatch was made for another mechanism")
-    nb, mu = len(mechanism.bodies), len(eqcids)
-    zd = np.ascontiguousarray(zd, dtype=np.float64)
-    if zd.ndim != 3 or zd.shape[1:] != (nb, 13) or zd.shape[0] < 1:
-        raise ValueError("zd must be [n_models][nb][13] = [n][%d][13], one setpoint per model (got %s)" % (nb, zd.shape))
-    n = zd.shape[0]
-    Qs, Rs = _pair_lists(Q, R, n, "model")
-    max_levels = int(max_levels)
-    if horizon is None and not 1 <= max_levels <= 60:
-        raise ValueError("max_levels = %d: a run to convergence makes 1 .. 60 levels (2^max_levels steps)" % max_levels)
-    if not float(tol) >= 0.0:
-        raise ValueError("tol = %r is negative or not a number" % (tol,))
+    zd, n, Qs, Rs = _model_set(mechanism, controller, plants, zd, Q, R)
+    max_levels, span = _doubling_limits(horizon, max_levels, tol)
     ctrl_N = int(getattr(controller, "N", 0))      # the device convention of the three controllers: 0 = LQR{T,Inf}, one gain; N > 0 = a table of N - 1 rows
     if ctrl_N > 0 and ctrl_N - 1 != 1:
         raise ValueError("the controller holds a table of %d gain rows: doubling evaluates ONE stationary gain (horizon math.inf); PolicyValue steps through a table" % (ctrl_N - 1))
-    Fd = None if Fτd is None else np.ascontiguousarray(Fτd, dtype=np.float64).reshape(-1, mu)
-    if Fd is not None and Fd.shape[0] != n:
-        raise ValueError("Fτd must be [n_models][mu] = [%d][%d]" % (n, mu))
-    Qm, Rm, Ntemp = _scaled_pairs(Qs, Rs, bodyids, nb, mu, math.inf if horizon is None else horizon, mechanism.Δt)
+    Ntemp = _model_set_fields(self, mechanism, bodyids, eqcids, Qs, Rs, span, zd, plants, first_plant, Fτd)
     if horizon is None:
         Ntemp = 0
-    self.first_plant = (0 if plants is None else plants.first_index) if first_plant is None else int(first_plant)
-    if plants is not None:
-        plants.rows_for(self.first_plant, n)      # every model must find its plant
-    self.mechanism, self.controller, self.plants, self.n_models = mechanism, controller, plants, n
-    self.eqcids = [int(e) for e in eqcids]
-    self.ctrl_joints = [mechanism.joint_index(e) for e in self.eqcids]
-    self.Q, self.R = Qm, Rm      # [n_weights][12 nb][12 nb], [n_weights][mu][mu]: scaled, mechanism body order
-    self.zd, self.Fd, self.N, self.tol, self.max_levels = zd, Fd, Ntemp, float(tol), max_levels
-    return Fd, Ntemp
+    self.controller, self.n_models, self.N, self.tol, self.max_levels = controller, n, Ntemp, float(tol), max_levels
+    return self.Fd, Ntemp
 
 
-class StationaryPolicyValue:
+class StationaryPolicyValue(_ValueTables):
     """Policy evaluation of a STATIONARY gain by doubling: what PolicyValue answers for the reference's default controller LQR{T,Inf} -- one gain (lqr.jl:40-43) -- in
     about 2 log2 N matrix combinations instead of N - 1 backward steps.  With that gain Abar (lqr.jl:169) and Qbar = Q + K' R K (lqr.jl:170) are constant, and with
     S(n) = sum_{i<n} (Abar^i)' Qbar Abar^i, M(n) = Abar^n the identity S(a+b) = S(a) + M(a)' S(b) M(a) gives P = S(n) + M(n)' Q M(n) for any n by square-and-multiply,
@@ -660,7 +655,7 @@ class StationaryPolicyValue:
     def __init__(self, mechanism, controller, bodyids, eqcids, Q, R, horizon, zd, plants=None, first_plant=None, Fτd=None, tol=1e-5, max_levels=40):
         Fd, Ntemp = _stationary_arguments(self, "StationaryPolicyValue", "evaluates", mechanism, controller, bodyids, eqcids, Q, R, horizon, zd, plants, first_plant, Fτd,
                                           tol, max_levels)
-        zd, n, max_levels = self.zd, self.n_models, self.max_levels
+        zd, max_levels = self.zd, self.max_levels
         dev = _device_mech(mechanism)
         self._dev, self._setpoints = dev, None
         ctrl = controller._ctrl_handle(dev)
@@ -670,37 +665,7 @@ class StationaryPolicyValue:
                 plants=None if plants is None else plants.handle(dev), first_plant=self.first_plant)
         finally:
             ctrl.close()
-        to_convergence = Ntemp == 0
-        self.steps = 2 ** self.levels.astype(np.int64) if to_convergence else np.full(n, Ntemp - 1, dtype=np.int64)
-        self.converged = (self.reason == 0) & to_convergence
-        self.diverged = (self.reason == 2) & to_convergence
-        with np.errstate(invalid="ignore", divide="ignore"):
-            self.spectral_radius = (self.gnorm[:, 0] / self.gnorm[:, 1]) ** (1.0 / 2.0 ** (self.levels - 1))
-
-    def P(self, i):
-        """model i's cost-to-go [12 nb][12 nb], mechanism body order, read back from the device (cclqr_value_get)"""
-        return self._value.get(i)
-
-    def _value_handle(self, dev):
-        if self._value.mech is not dev or not self._value.ptr:
-            raise ValueError("the StationaryPolicyValue was evaluated on another device handle of the mechanism")
-        return self._value, False
-
-    def _ctrl_handle(self, dev, **law):
-        """a setpoint-only controller of n_models tables built from zd: what predicted_cost measures model i's error about"""
-        if law:
-            raise TypeError("a StationaryPolicyValue is not a Controller: it holds costs-to-go, not a control law")
-        if dev is not self._dev:
-            raise ValueError("the StationaryPolicyValue was evaluated on another device handle of the mechanism")
-        if self._setpoints is None:
-            self._setpoints = _capi.CtrlHandle(dev, self.ctrl_joints, K=None, N=0, zd=self.zd, n_ctrl=self.n_models if self.n_models > 1 else 0)
-        return _BorrowedCtrl(self._setpoints)
-
-    def close(self):
-        if self._setpoints is not None:
-            self._setpoints.close()
-            self._setpoints = None
-        self._value.close()
+        _doubling_result(self, Ntemp, self.gnorm)
 
 
 class StationaryCovariance:
@@ -730,24 +695,9 @@ class StationaryCovariance:
         n, nb, mu = self.n_models, len(mechanism.bodies), len(self.eqcids)
         if noise_scale is None and Wu is None and Sigma0 is None:
             raise ValueError("none of noise_scale, Wu and Sigma0 is given: there is no covariance to propagate")
-        if noise_scale is not None and Wu is not None:
-            raise ValueError("noise_scale and Wu are both given: noise_scale IS Wu = noise_scale^2 ones((mu, mu))")
         if Sigma0 is not None and horizon is None:
             raise ValueError("Sigma0 with horizon=None: a steady state does not depend on the start")
-        if noise_scale is not None:
-            Wu = float(noise_scale) ** 2 * np.ones((mu, mu))
-        if Wu is not None:
-            Wu = np.ascontiguousarray(Wu, dtype=np.float64)
-            if Wu.shape not in ((mu, mu), (n, mu, mu)):
-                raise ValueError("Wu must be [mu][mu] = [%d][%d] or a list of one per model, %d (got %s)" % (mu, mu, n, Wu.shape))
-        inv = _body_order(bodyids, nb)
-        self._to_bodyids = np.concatenate([12 * inv[m] + np.arange(12) for m in range(nb)])      # mechanism-order coordinate -> its place in the order of bodyids
-        if Sigma0 is not None:
-            Sigma0 = np.ascontiguousarray(Sigma0, dtype=np.float64)
-            if Sigma0.shape not in ((12 * nb, 12 * nb), (n, 12 * nb, 12 * nb)):
-                raise ValueError("Sigma0 must be [12 nb][12 nb] = [%d][%d] or a list of one per model, %d (got %s)" % (12 * nb, 12 * nb, n, Sigma0.shape))
-            Sigma0 = np.ascontiguousarray(Sigma0[..., self._to_bodyids, :][..., :, self._to_bodyids])
-        self.Wu, self.Sigma0 = Wu, Sigma0
+        self.Wu, self.Sigma0 = Wu, Sigma0 = _noise_arguments(self, bodyids, nb, mu, n, noise_scale, Wu, Sigma0)
         dev = _device_mech(mechanism)
         self._dev = dev
         ctrl = controller._ctrl_handle(dev)
@@ -759,12 +709,7 @@ class StationaryCovariance:
             ctrl.close()
         self.state_std = np.empty_like(zstd)
         self.state_std[:, self._to_bodyids] = zstd
-        to_convergence = Ntemp == 0
-        self.steps = 2 ** self.levels.astype(np.int64) if to_convergence else np.full(n, Ntemp - 1, dtype=np.int64)
-        self.converged = (self.reason == 0) & to_convergence
-        self.diverged = (self.reason == 2) & to_convergence
-        with np.errstate(invalid="ignore", divide="ignore"):
-            self.spectral_radius = (self.gnorm[:, 0] / self.gnorm[:, 1]) ** (1.0 / 2.0 ** (self.levels - 1))
+        _doubling_result(self, Ntemp, self.gnorm)
 
     def Sigma(self, i):
         """model i's covariance [12 nb][12 nb], mechanism body order, read back from the device (cclqr_value_get)"""
@@ -848,14 +793,8 @@ class PlantTrackingLQR(Controller):
         self.kbreak = self._handle.kbreak
 
     def _ctrl_handle(self, dev, fric=None, noise_scale=0.0, noise_seed=None):
-        if fric is not None or noise_scale or noise_seed is not None:
-            raise ValueError("the friction / noise law of a PlantTrackingLQR is fixed at construction (PlantTrackingLQR(..., fric=, noise_scale=, noise_seed=))")
-        if self.first_plant != 0:
-            raise ValueError("a rollout reads controller table and plant by the global instance index: a PlantTrackingLQR that is rolled out starts at plant 0 "
-                             "(this one at plant %d)" % self.first_plant)
-        if self._handle.mech is not dev or not self._handle.ptr:
-            raise ValueError("the PlantTrackingLQR was designed on another device handle of the mechanism")
-        return _BorrowedCtrl(self._handle)
+        return _borrow_tables(self, dev, fric, noise_scale, noise_seed,
+                              "the friction / noise law of a PlantTrackingLQR is fixed at construction (PlantTrackingLQR(..., fric=, noise_scale=, noise_seed=))")
 
     def gains(self, i):
         """K[k][j] of plant i's table, [N-1][mu][12 nb] in the mechanism's body order, read back from the device (cclqr_ctrl_get_gains)"""
@@ -1034,21 +973,7 @@ def _tracking_arguments(self, *, name, verb, noun, mechanism, controller, bodyid
         raise ValueError("storage and Fτ must both be host arrays or both device tensors")
     if nothing_given is not None and noise_scale is None and Wu is None and Sigma0 is None:
         raise ValueError(nothing_given)
-    if noise_scale is not None and Wu is not None:
-        raise ValueError("noise_scale and Wu are both given: noise_scale IS Wu = noise_scale^2 ones((mu, mu))")
-    if noise_scale is not None:
-        Wu = float(noise_scale) ** 2 * np.ones((mu, mu))
-    if Wu is not None:
-        Wu = np.ascontiguousarray(Wu, dtype=np.float64)
-        if Wu.shape not in ((mu, mu), (n, mu, mu)):
-            raise ValueError("Wu must be [mu][mu] = [%d][%d] or a list of one per model, %d (got %s)" % (mu, mu, n, Wu.shape))
-    inv = _body_order(bodyids, nb)
-    self._to_bodyids = np.concatenate([12 * inv[m] + np.arange(12) for m in range(nb)])      # mechanism-order coordinate -> its place in the order of bodyids
-    if Sigma0 is not None:
-        Sigma0 = np.ascontiguousarray(Sigma0, dtype=np.float64)
-        if Sigma0.shape not in ((12 * nb, 12 * nb), (n, 12 * nb, 12 * nb)):
-            raise ValueError("Sigma0 must be [12 nb][12 nb] = [%d][%d] or a list of one per model, %d (got %s)" % (12 * nb, 12 * nb, n, Sigma0.shape))
-        Sigma0 = np.ascontiguousarray(Sigma0[..., self._to_bodyids, :][..., :, self._to_bodyids])
+    Wu, Sigma0 = _noise_arguments(self, bodyids, nb, mu, n, noise_scale, Wu, Sigma0)
     Qs, Rs = _pair_lists(Q, R, n, "model")
     self.Q, self.R, _ = _scaled_pairs(Qs, Rs, bodyids, nb, mu, math.inf, mechanism.Δt)      # [n_weights][12 nb][12 nb], [n_weights][mu][mu]: scaled, mechanism body order
     self.first_plant = (0 if plants is None else plants.first_index) if first_plant is None else int(first_plant)
@@ -1077,7 +1002,7 @@ def _tracking_arguments(self, *, name, verb, noun, mechanism, controller, bodyid
     return _TrackingCall(dev, ctrl, (zarg, n, N, self.ctrl_joints, self.Q, self.R), kw, z)
 
 
-class TrackingPolicyValue:
+class TrackingPolicyValue(_ValueTables):
     """The cost-to-go of a TRACKED run at every knot, and the price of its noise: what a tracked run is expected to cost from a perturbed start, what the nominal
     table costs along plant n's own trajectory, which knot's noise is the expensive one, and the terminal weight of a receding-horizon caller at knot j -- the
     adjoint of TrackingCovariance.  Knots are j = 0 .. N-1 as there.  With [A'_j | D_j] the projected model linearised at knot j (lqr_tracking.jl:88), K_j the gain
@@ -1108,31 +1033,6 @@ class TrackingPolicyValue:
         self.expected_noise_cost = np.zeros(self.n_models) if total is None else total
         row = call.z[:, self.knot]      # the setpoints predicted_cost measures the error about; a device tensor's row is copied to the host
         self.zd = np.ascontiguousarray(row.cpu().numpy() if _is_device_tensor(row) else row, dtype=np.float64)
-
-    def P(self, i):
-        """P_knot of model i [12 nb][12 nb], mechanism body order, read back from the device (cclqr_value_get)"""
-        return self._value.get(i)
-
-    def _value_handle(self, dev):
-        if self._value.mech is not dev or not self._value.ptr:
-            raise ValueError("the TrackingPolicyValue was evaluated on another device handle of the mechanism")
-        return self._value, False
-
-    def _ctrl_handle(self, dev, **law):
-        """a setpoint-only controller of n_models tables built from row `knot` of the trajectories: what predicted_cost measures model i's error about"""
-        if law:
-            raise TypeError("a TrackingPolicyValue is not a Controller: it holds costs-to-go, not a control law")
-        if dev is not self._dev:
-            raise ValueError("the TrackingPolicyValue was evaluated on another device handle of the mechanism")
-        if self._setpoints is None:
-            self._setpoints = _capi.CtrlHandle(dev, self.ctrl_joints, K=None, N=0, zd=self.zd, n_ctrl=self.n_models if self.n_models > 1 else 0)
-        return _BorrowedCtrl(self._setpoints)
-
-    def close(self):
-        if self._setpoints is not None:
-            self._setpoints.close()
-            self._setpoints = None
-        self._value.close()
 
 
 class Score:
