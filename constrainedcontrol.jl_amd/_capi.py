@@ -24,7 +24,7 @@ EXPORTS = ["cclqr_last_error", "cclqr_version", "cclqr_device_count", "cclqr_set
            "cclqr_policy_value", "cclqr_value_create_policy", "cclqr_policy_value_doubling", "cclqr_value_create_policy_doubling",
            "cclqr_riccati_doubling", "cclqr_ctrl_create_lqr_batch_doubling", "cclqr_covariance_doubling", "cclqr_value_create_covariance_doubling",
            "cclqr_covariance_tracking", "cclqr_value_create_covariance_tracking", "cclqr_policy_value_tracking", "cclqr_value_create_policy_tracking",
-           "cclqr_rollout_ensemble_ws_bytes", "cclqr_rollout_ensemble"]
+           "cclqr_rollout_ensemble_ws_bytes", "cclqr_rollout_ensemble", "cclqr_rollout_quantiles_ws_bytes", "cclqr_rollout_quantiles"]
 ABI_VERSION = 202     # include/cclqr.h CCLQR_ABI_VERSION: the structs below mirror that header (verified field by field against cclqr_abi_layout at load time)
 ROLLOUT_NO_ALLOC = 1  # cclqr_rollout_opts.flags: the call may neither allocate nor synchronise (a hipGraph capture is open on the device)
 ROLLOUT_CARRY_STATUS = 4  # ... `status` is read and written: an instance lost in an earlier launch stays frozen, the others merge this launch's result into it
@@ -658,6 +658,38 @@ def rollout_ensemble(mech, ctrl, n_inst, steps, k0, traj_ptr, mean_ptr, m2_ptr, 
                                        vp(ws_ptr), C.c_size_t(int(ws_bytes)), vp(stream)))
 
 
+QUANTILE_MAX_INST = 16384    # CCLQR_QUANTILE_MAX_INST: instances of one cclqr_rollout_quantiles call
+QUANTILE_MAX_PROBS = 16      # CCLQR_QUANTILE_MAX_PROBS
+
+
+def quantile_probs(probs):
+    """the probabilities of a quantile request as a float64 vector: 0 .. QUANTILE_MAX_PROBS of them (none: no request), each in [0, 1]"""
+    p = f64(list(probs)).reshape(-1)
+    if len(p) > QUANTILE_MAX_PROBS:
+        raise ValueError("at most %d quantile probabilities per run (got %d)" % (QUANTILE_MAX_PROBS, len(p)))
+    if not ((p >= 0.0) & (p <= 1.0)).all():
+        raise ValueError("quantile probabilities must lie in [0, 1] (got %s)" % p.tolist())
+    return p
+
+
+def rollout_quantiles_ws_bytes(mech, mu, n_inst, steps):
+    """cclqr_rollout_quantiles_ws_bytes: (min_bytes, full_bytes) of device workspace -- one slab row, all `steps` rows"""
+    lo, full = C.c_size_t(0), C.c_size_t(0)
+    check(lib().cclqr_rollout_quantiles_ws_bytes(mech.ptr, C.c_int32(int(mu)), C.c_int64(int(n_inst)), C.c_int32(int(steps)), C.byref(lo), C.byref(full)))
+    return int(lo.value), int(full.value)
+
+
+def rollout_quantiles(mech, ctrl, n_inst, steps, k0, traj_ptr, probs, quant_ptr, finite_ptr, ws_ptr, ws_bytes, stream=0, first_instance=0):
+    """cclqr_rollout_quantiles on device addresses (asynchronous on `stream`): per row of the slab traj [n_inst][steps][nb][13] and per coordinate of (Δz, Δu) the
+    quantiles of its finite values across the instances at the probabilities `probs` (host numbers) into quant [steps][len(probs)][12 nb + mu], and their number into
+    finite [steps][12 nb + mu] (int32; 0: not wanted)"""
+    vp = lambda p: C.c_void_p(int(p)) if p else None
+    pr = f64(list(probs)).reshape(-1)
+    check(lib().cclqr_rollout_quantiles(mech.ptr, ctrl.ptr, C.c_int64(int(n_inst)), C.c_int32(int(steps)), C.c_int32(int(k0)), C.c_int64(int(first_instance)),
+                                        vp(traj_ptr), C.c_int32(len(pr)), _d(pr) if len(pr) else None, vp(quant_ptr), vp(finite_ptr),
+                                        vp(ws_ptr), C.c_size_t(int(ws_bytes)), vp(stream)))
+
+
 def rollout_scored(mech, ctrl, score, z0, steps, chunk_steps, noise=None, first_instance=0, plants=None, newton_mode=0, newton_eps_alone=0.0, flags=0, traj_out=None,
                    ensemble=None):
     """A horizon rolled out AND scored on the device without its trajectory ever existing: ceil(steps / chunk_steps) launches of cclqr_rollout_ex (plants:
@@ -665,8 +697,10 @@ def rollout_scored(mech, ctrl, score, z0, steps, chunk_steps, noise=None, first_
     (ROLLOUT_CARRY_STATUS), the PID state and the noise column travel from launch to launch, so the result is bitwise that of one launch.
     noise [n_inst][steps] injected samples or None.  traj_out: a numpy array [n_inst][steps][nb][13] that receives the slabs (the recorded run), or None.
     score: a ScoreHandle, or None = no score pass.  ensemble: None, or (mu, cov_rows) -- cclqr_rollout_ensemble runs behind every launch on the same slab, and the
-    0-based rows of the horizon in cov_rows (row j = step j + 1) get their co-moment matrix, each from the chunk that holds it.
-    Returns (zT, status, score [n_inst][SCORE_LEN] or None), with ensemble a fourth element (mean [steps][12 nb + mu], M2 the same, {row: C [12 nb][12 nb]})."""
+    0-based rows of the horizon in cov_rows (row j = step j + 1) get their co-moment matrix, each from the chunk that holds it --, or (mu, cov_rows, probs):
+    cclqr_rollout_quantiles runs behind the ensemble call on the same slab, with a workspace of as many rows as the chunk has.
+    Returns (zT, status, score [n_inst][SCORE_LEN] or None), with ensemble a fourth element (mean [steps][12 nb + mu], M2 the same, {row: C [12 nb][12 nb]}), which
+    the three-element form extends by (quant [steps][len(probs)][12 nb + mu], finite [steps][12 nb + mu])."""
     import torch
     nb, ne = mech.tables.nb, mech.tables.ne
     z0 = f64(z0).reshape(-1, nb, 13)
@@ -680,6 +714,9 @@ def rollout_scored(mech, ctrl, score, z0, steps, chunk_steps, noise=None, first_
         cov_of = [[j + 1 for j in cov_rows if k0 <= j + 1 < k0 + s] for k0, s in plan]
         if max(len(c) for c in cov_of) > ENSEMBLE_MAX_COV:
             raise ValueError("more than %d cov_knots fall into one chunk: lower chunk_steps" % ENSEMBLE_MAX_COV)
+        probs = quantile_probs(ensemble[2]) if len(ensemble) > 2 else ()
+        if len(probs) and n > QUANTILE_MAX_INST:
+            raise ValueError("quantiles are taken over at most %d instances per call (got %d)" % (QUANTILE_MAX_INST, n))
     td = torch.device("cuda", torch.cuda.current_device())
     z = torch.from_numpy(z0).to(td)
     zn = torch.empty_like(z)
@@ -698,6 +735,11 @@ def rollout_scored(mech, ctrl, score, z0, steps, chunk_steps, noise=None, first_
         ws_bytes = rollout_ensemble_ws_bytes(mech, mu, n, rows, most if cov_rows else 0)
         ws = torch.empty(ws_bytes // 8 + 1, dtype=torch.float64, device=td)
         cov_done = 0
+        if len(probs):
+            equant = torch.empty((steps, len(probs), nx), dtype=torch.float64, device=td)
+            efin = torch.empty((steps, nx), dtype=torch.int32, device=td)
+            qws_bytes = rollout_quantiles_ws_bytes(mech, mu, n, rows)[1]
+            qws = torch.empty(qws_bytes // 8 + 1, dtype=torch.float64, device=td)
     for ci, (k0, s) in enumerate(plan):
         # the noise array is indexed by the absolute step k - 1: its base stays where it is whatever k0 is
         rollout_dev(mech, ctrl, n, s, k0, z.data_ptr(), lam.data_ptr(), 0 if dnoise is None else dnoise.data_ptr(), steps, slab.data_ptr(), zn.data_ptr(),
@@ -709,6 +751,9 @@ def rollout_scored(mech, ctrl, score, z0, steps, chunk_steps, noise=None, first_
             rollout_ensemble(mech, ctrl, n, s, k0, slab.data_ptr(), emean[k0 - 1:].data_ptr(), em2[k0 - 1:].data_ptr(), ws.data_ptr(), ws_bytes,
                              cov_steps=cov_of[ci], cov_ptr=ecov[cov_done:].data_ptr() if cov_of[ci] else 0, stream=stream, first_instance=first_instance)
             cov_done += len(cov_of[ci])
+            if len(probs):
+                rollout_quantiles(mech, ctrl, n, s, k0, slab.data_ptr(), probs, equant[k0 - 1:].data_ptr(), efin[k0 - 1:].data_ptr(), qws.data_ptr(), qws_bytes,
+                                  stream=stream, first_instance=first_instance)
         if traj_out is not None:      # (a launch of s < rows steps fills the slab as [n][s][nb][13] from its base)
             traj_out[:, k0 - 1:k0 - 1 + s] = slab.reshape(-1)[:n * s * nb * 13].reshape(n, s, nb, 13).cpu().numpy()
         z, zn = zn, z
@@ -717,7 +762,10 @@ def rollout_scored(mech, ctrl, score, z0, steps, chunk_steps, noise=None, first_
     if ensemble is None:
         return out
     covs = ecov.cpu().numpy()
-    return out + ((emean.cpu().numpy(), em2.cpu().numpy(), {j: covs[q] for q, j in enumerate(cov_rows)}),)
+    stats = (emean.cpu().numpy(), em2.cpu().numpy(), {j: covs[q] for q, j in enumerate(cov_rows)})
+    if len(probs):
+        stats += (equant.cpu().numpy(), efin.cpu().numpy())
+    return out + (stats,)
 
 
 def linearize(mech, zd, ctrl_joint, Fd=None, plants=None, first_plant=0):

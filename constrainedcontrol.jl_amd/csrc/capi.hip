@@ -12,6 +12,7 @@ static_assert(CCLQR_NEWTON_MAXIT == NEWTON_MAXIT, "include/cclqr.h and cclqr_new
 static_assert(CCLQR_SCORE_LEN == CCLQR_SCORE_LEN_, "include/cclqr.h and cclqr_score.h disagree on the length of a score");
 #include "cclqr_value.h"
 #include "cclqr_ensemble.h"
+#include "cclqr_quantiles.h"
 #include <math.h>
 #include <stdio.h>
 #include <string.h>
@@ -1255,14 +1256,8 @@ static int ensemble_sizes_ok(const cclqr_mech* m, int32_t mu, int64_t n_inst, in
     if (ens_tiles(n_inst) * steps > 0x7fffffffLL || ens_splits(n_inst) > 65535) return fail(CCLQR_EINVAL, "n_inst x steps exceeds one launch: call with fewer steps");
     return CCLQR_OK;
 }
-extern "C" int cclqr_rollout_ensemble_ws_bytes(const cclqr_mech* m, int32_t mu, int64_t n_inst, int32_t steps, int32_t n_cov, size_t* bytes) {
-    if (!m || !bytes) return fail(CCLQR_EINVAL, "null argument");
-    TRY(ensemble_sizes_ok(m, mu, n_inst, steps, n_cov));
-    *bytes = sizeof(double) * ens_ws_doubles(m->nb, mu, n_inst, steps, n_cov);
-    return CCLQR_OK;
-}
-extern "C" int cclqr_rollout_ensemble(const cclqr_mech* m, const cclqr_ctrl* c, int64_t n_inst, int32_t steps, int32_t k0, int64_t first_instance, const double* traj,
-                                      double* mean, double* m2, int32_t n_cov, const int32_t* cov_steps, double* cov, void* ws, size_t ws_bytes, void* stream) {
+// the handle, size and index checks every call over a slab's instances makes, in this order (cclqr_rollout_ensemble, cclqr_rollout_quantiles)
+static int ensemble_call_ok(const cclqr_mech* m, const cclqr_ctrl* c, int64_t n_inst, int32_t steps, int32_t k0, int64_t first_instance, int32_t n_cov) {
     if (!m || !c) return fail(CCLQR_EINVAL, "null argument");
     TRY(check_device(m));
     if (c->nb != m->nb || c->device != m->device) return fail(CCLQR_EINVAL, "the controller was created for another mechanism or device");
@@ -1271,6 +1266,17 @@ extern "C" int cclqr_rollout_ensemble(const cclqr_mech* m, const cclqr_ctrl* c, 
     if (!c->zd_dev || c->host.nsp < 1) return fail(CCLQR_EINVAL, "the controller has no setpoint table");
     if (c->host.n_ctrl > 1 && first_instance + n_inst > c->host.n_ctrl)
         return fail(CCLQR_EINVAL, "first_instance + n_inst = " + std::to_string(first_instance + n_inst) + " exceeds the controller's n_ctrl = " + std::to_string(c->host.n_ctrl) + " tables");
+    return CCLQR_OK;
+}
+extern "C" int cclqr_rollout_ensemble_ws_bytes(const cclqr_mech* m, int32_t mu, int64_t n_inst, int32_t steps, int32_t n_cov, size_t* bytes) {
+    if (!m || !bytes) return fail(CCLQR_EINVAL, "null argument");
+    TRY(ensemble_sizes_ok(m, mu, n_inst, steps, n_cov));
+    *bytes = sizeof(double) * ens_ws_doubles(m->nb, mu, n_inst, steps, n_cov);
+    return CCLQR_OK;
+}
+extern "C" int cclqr_rollout_ensemble(const cclqr_mech* m, const cclqr_ctrl* c, int64_t n_inst, int32_t steps, int32_t k0, int64_t first_instance, const double* traj,
+                                      double* mean, double* m2, int32_t n_cov, const int32_t* cov_steps, double* cov, void* ws, size_t ws_bytes, void* stream) {
+    TRY(ensemble_call_ok(m, c, n_inst, steps, k0, first_instance, n_cov));
     if (!traj || !mean || !m2 || (n_cov > 0 && (!cov_steps || !cov))) return fail(CCLQR_EINVAL, "null argument");
     for (int q = 0; q < n_cov; q++)
         if (cov_steps[q] < k0 || cov_steps[q] > k0 + steps - 1)
@@ -1294,6 +1300,49 @@ extern "C" int cclqr_rollout_ensemble(const cclqr_mech* m, const cclqr_ctrl* c, 
     v.dzrows = a.dzrows; v.mean = mean; v.cpart = a.dzrows + ens_ws_rows_doubles(nb, n_inst, n_cov); v.cov = cov;
     for (int q = 0; q < n_cov; q++) v.cov_row[q] = a.cov_row[q];
     HIPCHK(launch_ensemble_cov(v, n_cov, (hipStream_t)stream));
+    return CCLQR_OK;
+}
+
+// ---- the quantiles of a slab across its instances (quantiles.hip).  Nothing is allocated, copied or synchronised: the probabilities travel in the kernels'
+// arguments, and the rows are taken in blocks of as many as the caller's workspace holds -- a row's result does not know which block it was in
+static int quantile_sizes_ok(const cclqr_mech* m, int32_t mu, int64_t n_inst, int32_t steps) {
+    TRY(ensemble_sizes_ok(m, mu, n_inst, steps, 0));
+    if (n_inst > CCLQR_QUANTILE_MAX_INST)
+        return fail(CCLQR_EUNSUPPORTED, "n_inst = " + std::to_string(n_inst) + ": one call sorts at most CCLQR_QUANTILE_MAX_INST = " + std::to_string(CCLQR_QUANTILE_MAX_INST) + " instances");
+    return CCLQR_OK;
+}
+extern "C" int cclqr_rollout_quantiles_ws_bytes(const cclqr_mech* m, int32_t mu, int64_t n_inst, int32_t steps, size_t* min_bytes, size_t* full_bytes) {
+    if (!m || !min_bytes || !full_bytes) return fail(CCLQR_EINVAL, "null argument");
+    TRY(quantile_sizes_ok(m, mu, n_inst, steps));
+    *min_bytes = sizeof(double) * qnt_row_doubles(m->nb, mu, n_inst);
+    *full_bytes = *min_bytes * (size_t)steps;
+    return CCLQR_OK;
+}
+extern "C" int cclqr_rollout_quantiles(const cclqr_mech* m, const cclqr_ctrl* c, int64_t n_inst, int32_t steps, int32_t k0, int64_t first_instance, const double* traj,
+                                       int32_t n_prob, const double* prob, double* quant, int32_t* finite, void* ws, size_t ws_bytes, void* stream) {
+    TRY(ensemble_call_ok(m, c, n_inst, steps, k0, first_instance, 0));
+    if (!traj || !prob || !quant) return fail(CCLQR_EINVAL, "null argument");
+    if (n_prob < 1 || n_prob > CCLQR_QUANTILE_MAX_PROBS)
+        return fail(CCLQR_EINVAL, "n_prob = " + std::to_string(n_prob) + ": one call takes 1 .. " + std::to_string(CCLQR_QUANTILE_MAX_PROBS) + " probabilities");
+    for (int j = 0; j < n_prob; j++)
+        if (!(prob[j] >= 0.0 && prob[j] <= 1.0)) return fail(CCLQR_EINVAL, "prob[" + std::to_string(j) + "] = " + std::to_string(prob[j]) + " is not a probability in [0, 1]");
+    const int nb = m->nb, mu = c->host.mu;
+    TRY(quantile_sizes_ok(m, mu, n_inst, steps));
+    const size_t row_bytes = sizeof(double) * qnt_row_doubles(nb, mu, n_inst);
+    if (!ws) return fail(CCLQR_EINVAL, "null workspace: cclqr_rollout_quantiles_ws_bytes says how large it must be (at least " + std::to_string(row_bytes) + " bytes)");
+    if (ws_bytes < row_bytes) return fail(CCLQR_EINVAL, "workspace too small: " + std::to_string(ws_bytes) + " bytes given, " + std::to_string(row_bytes) + " needed for one row (cclqr_rollout_quantiles_ws_bytes)");
+    if (((uintptr_t)ws & 7) != 0) return fail(CCLQR_EINVAL, "the workspace is not 8-byte aligned");
+    QntArgs a;
+    memset(&a, 0, sizeof(a));
+    a.M = m->dev; a.C = c->dev; a.nb = nb; a.mu = mu; a.n_inst = n_inst; a.n_pad = qnt_pad(n_inst); a.steps = steps; a.k0 = k0; a.inst0 = first_instance; a.traj = traj;
+    a.W = qnt_stage_window(nb, mu); a.xt = (double*)ws; a.n_prob = n_prob; a.quant = quant; a.finite = finite;
+    for (int j = 0; j < n_prob; j++) a.prob[j] = prob[j];
+    const size_t fit = ws_bytes / row_bytes;
+    const int block = (int)(fit < 65535 ? fit : 65535);      // (rows are the y extent of the select kernel's grid)
+    for (int r0 = 0; r0 < steps; r0 += block) {
+        a.row0 = r0; a.nrows = steps - r0 < block ? steps - r0 : block;
+        HIPCHK(launch_quantiles(a, (hipStream_t)stream));
+    }
     return CCLQR_OK;
 }
 

@@ -2,7 +2,8 @@
 // step the mean and the centred sum of squares of every coordinate of x = (dz, du) -- dz the error of lqr.jl:92-103 about the step's setpoint, du = -K dz the
 // feedback command of lqr.jl:105-113 under its gate -- and, at the steps the caller lists, the centred co-moment matrix of dz.  The per-row and per-tile arithmetic
 // lives here as __host__ __device__ functions so that tests/emu/emu_ensemble.cpp runs it lane by lane on the CPU (test infrastructure only).  None of them contains
-// a cross-lane operation: they are called under lane predicates (the rule of tests/test_static_kernel_rules.py).
+// a cross-lane operation: they are called under lane predicates (the rule of tests/test_static_kernel_rules.py); the two __device__ helpers ens_group_sum and
+// ens_wave_sync, which are nothing else, are marked as such below.
 //
 // The ONE summation order, a function of n_inst and of the mechanism alone (never of steps, k0, the chunk or the order workgroups finish in):
 //   tile  = ENS_TILE consecutive instances, the last tile short;
@@ -52,6 +53,23 @@ HD void ens_body_row(const double* z, const double* zd, double* dz) {
     score_body_error(z, zd, dz);
 #pragma unroll
     for (int i = 0; i < 12; i++) dz[i] = ens_canon(dz[i]);
+}
+
+// ---- the two cross-lane pieces of the front end that forms x (ens_moments_kernel; ens_stage_kernel of quantiles.hip forms the same x with them): device code only,
+// called at control flow that depends on launch arguments and controller constants alone
+template <int G>
+__device__ __forceinline__ double ens_group_sum(double v) {
+#pragma unroll
+    for (int o = 1; o < G; o <<= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// the row and x of an instance are private to ONE lane group of ONE wavefront between two workgroup barriers: what orders a lane's LDS writes before its
+// neighbours' reads is the wavefront's own instruction order; the fences keep the compiler from moving LDS accesses across the point
+__device__ __forceinline__ void ens_wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 // (mean, M2) of cnt >= 1 values x[0], x[stride], ...: two passes, the first about x[0] -- equal values give their own bits as the mean and M2 = 0 exactly

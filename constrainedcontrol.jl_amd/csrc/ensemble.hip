@@ -20,21 +20,6 @@
 namespace cclqr {
 
 template <int G>
-__device__ __forceinline__ double ens_group_sum(double v) {
-#pragma unroll
-    for (int o = 1; o < G; o <<= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// the row and x of an instance are private to ONE lane group of ONE wavefront between two workgroup barriers: what orders a lane's LDS writes before its
-// neighbours' reads is the wavefront's own instruction order; the fences keep the compiler from moving LDS accesses across the point
-__device__ __forceinline__ void ens_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-template <int G>
 __global__ __launch_bounds__(64 * ENS_WAVES) void ens_moments_kernel(EnsArgs a) {
     extern __shared__ double lds[];
     constexpr int IPW = 64 / G, P = ENS_WAVES * IPW;      // instances per wavefront and per pass

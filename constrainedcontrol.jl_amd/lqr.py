@@ -1071,24 +1071,34 @@ class Ensemble:
     """What a batch is summarised by ACROSS its instances: per step the mean and the spread of every coordinate of the error Δz of lqr.jl:92-103 and of the feedback
     command Δu = -K[k] Δz, and at the knots named in cov_knots the full covariance of Δz, evaluated on the device from the rollout's own states
     (cclqr_rollout_ensemble) -- the measurement TrackingCovariance / StationaryCovariance predict.  simulate(..., ensemble=Ensemble(mechanism, cov_knots=(j, ...)))
-    returns a Storage with .ensemble, an EnsembleStats; row j of it (0-based, the state the law saw at step j + 1) is knot j of TrackingCovariance."""
+    returns a Storage with .ensemble, an EnsembleStats; row j of it (0-based, the state the law saw at step j + 1) is knot j of TrackingCovariance.
+    quantiles=(p, ...): up to 16 probabilities in [0, 1] -- the same run also takes, per step and coordinate, the quantiles of the finite values across the instances
+    (cclqr_rollout_quantiles: 0 the minimum, 0.5 the median, 1 the maximum; at most 16384 instances), the fan chart of a run outside the Gaussian regime."""
 
-    def __init__(self, mechanism, cov_knots=()):
+    def __init__(self, mechanism, cov_knots=(), quantiles=()):
         if not isinstance(mechanism, Mechanism):
-            raise TypeError("Ensemble(mechanism, cov_knots=())")
+            raise TypeError("Ensemble(mechanism, cov_knots=(), quantiles=())")
         knots = [int(j) for j in cov_knots]
         if any(j < 0 for j in knots) or any(int(j) != j for j in cov_knots):
             raise ValueError("cov_knots are 0-based knots of the run: whole numbers >= 0")
         self.mechanism = mechanism
         self.cov_knots = tuple(sorted(set(knots)))
+        self.quantiles = tuple(float(p) for p in _capi.quantile_probs(quantiles))
 
 
 class EnsembleStats:
     """The statistics of `count` instances at every step of a run: mean [steps][12 nb] and the centred sums of squares M2 of Δz (mechanism body order), input_mean /
     input M2 [steps][mu] of Δu, and the centred co-moment matrices C[j] [12 nb][12 nb] of the knots that were asked for.  var / std are about the ensemble mean,
-    rms / second_moment about the setpoint: sqrt((M2 + n mean^2) / n) is what diag Σ_j of a covariance prediction with zero-mean error is compared with."""
+    rms / second_moment about the setpoint: sqrt((M2 + n mean^2) / n) is what diag Σ_j of a covariance prediction with zero-mean error is compared with.
+    With Ensemble(quantiles=): quantile(p) [steps][12 nb] and input_quantile(p) [steps][mu] for the probabilities that were asked for (median, min, max for 0.5, 0, 1)
+    and finite_count [steps][12 nb + mu], the number of finite values each was taken over."""
 
-    def __init__(self, count, mean, M2, input_mean, input_M2, C=None):
+    def __init__(self, count, mean, M2, input_mean, input_M2, C=None, *, probs=None, quantiles=None, finite_count=None, merged=False):
+        # probs None: no quantiles were asked for (merged: because this is a merge of shards); else quantiles [steps][len(probs)][12 nb + mu]
+        self.probs = None if probs is None else tuple(float(p) for p in probs)
+        self._quantiles = None if probs is None else np.asarray(quantiles, dtype=np.float64)
+        self.finite_count = None if probs is None else np.asarray(finite_count, dtype=np.int32)
+        self._merged = bool(merged)
         self.count = int(count)
         self.mean, self.M2 = np.asarray(mean, dtype=np.float64), np.asarray(M2, dtype=np.float64)
         self.input_mean, self.input_M2 = np.asarray(input_mean, dtype=np.float64), np.asarray(input_M2, dtype=np.float64)
@@ -1104,6 +1114,26 @@ class EnsembleStats:
     input_std = property(lambda self: np.sqrt(self.input_var()))
     rms = property(lambda self: np.sqrt((self.M2 + self.count * self.mean ** 2) / self.count))
     input_rms = property(lambda self: np.sqrt((self.input_M2 + self.count * self.input_mean ** 2) / self.count))
+
+    def _quantile_rows(self, p):
+        if self._merged:
+            raise KeyError("a merged EnsembleStats holds no quantiles: the order statistics of shards do not combine")
+        asked = () if self.probs is None else self.probs
+        if float(p) not in asked:
+            raise KeyError("quantile %r was not asked for: Ensemble(quantiles=%s)" % (p, list(asked)))
+        return self._quantiles[:, asked.index(float(p))]
+
+    def quantile(self, p):
+        """the quantile at probability p of every coordinate of Δz across the instances, [steps][12 nb]"""
+        return self._quantile_rows(p)[:, :self.mean.shape[1]]
+
+    def input_quantile(self, p):
+        """... of Δu, [steps][mu]"""
+        return self._quantile_rows(p)[:, self.mean.shape[1]:]
+
+    median = property(lambda self: self.quantile(0.5))
+    min = property(lambda self: self.quantile(0.0))
+    max = property(lambda self: self.quantile(1.0))
 
     def _comoment(self, j):
         if int(j) not in self.C:
@@ -1121,13 +1151,14 @@ class EnsembleStats:
 
     def merge(self, other):
         """the statistics of this ensemble and `other` together (the shards of dist.shard, on the host): the pairwise formula of Chan, Golub and LeVeque on
-        (count, mean, M2, C).  An empty side (count 0) leaves the other's bits.  Co-moments are kept for the knots both sides hold."""
+        (count, mean, M2, C).  An empty side (count 0) leaves the other's bits.  Co-moments are kept for the knots both sides hold.  The result holds NO quantiles:
+        the order statistics of shards do not combine."""
         if not isinstance(other, EnsembleStats):
             raise TypeError("EnsembleStats.merge takes an EnsembleStats")
         if other.count == 0:
-            return EnsembleStats(self.count, self.mean, self.M2, self.input_mean, self.input_M2, self.C)
+            return EnsembleStats(self.count, self.mean, self.M2, self.input_mean, self.input_M2, self.C, merged=True)
         if self.count == 0:
-            return EnsembleStats(other.count, other.mean, other.M2, other.input_mean, other.input_M2, other.C)
+            return EnsembleStats(other.count, other.mean, other.M2, other.input_mean, other.input_M2, other.C, merged=True)
         if self.mean.shape != other.mean.shape or self.input_mean.shape != other.input_mean.shape:
             raise ValueError("the two ensembles differ in steps or coordinates")
         na, nb = float(self.count), float(other.count)
@@ -1143,7 +1174,7 @@ class EnsembleStats:
         for j in sorted(set(self.C) & set(other.C)):
             d = other.mean[j] - self.mean[j]
             C[j] = (self.C[j] + other.C[j]) + np.outer(d, d) * (na * nb / n)
-        return EnsembleStats(self.count + other.count, mean, M2, imean, iM2, C)
+        return EnsembleStats(self.count + other.count, mean, M2, imean, iM2, C, merged=True)
 
     @staticmethod
     def empty(steps, mx, mu, cov_knots=()):
@@ -1510,7 +1541,8 @@ def simulate(mechanism, tend_or_storage, controller, record=True, z0=None, fric=
     run without score=.  For the fused laws.
     ensemble: an Ensemble -- the same chunk loop (with or without score=, on the same slab) with cclqr_rollout_ensemble behind every launch; the returned Storage
     carries .ensemble, an EnsembleStats: per step the mean and the spread of every coordinate of Δz and Δu across the instances, and the covariance of Δz at the
-    Ensemble's cov_knots.  Any chunk_steps, record or not, gives the same bits.  For the fused laws.
+    Ensemble's cov_knots -- and, with Ensemble(quantiles=), the quantiles of every coordinate at every step (at most 16384 instances).  Any chunk_steps, record or
+    not, gives the same bits.  For the fused laws.
     After the call the mechanism's bodies hold instance 0's final state (simulate! mutates the mechanism)."""
     if isinstance(controller, PolicyValue):
         raise TypeError("a PolicyValue is not a Controller: simulate rolls out the controller it evaluates (PolicyValue.controller)")
@@ -1541,7 +1573,7 @@ def simulate(mechanism, tend_or_storage, controller, record=True, z0=None, fric=
             raise ValueError("score= needs at least one step")
     if ensemble is not None:
         if not isinstance(ensemble, Ensemble):
-            raise TypeError("ensemble= takes an Ensemble(mechanism, cov_knots=())")
+            raise TypeError("ensemble= takes an Ensemble(mechanism, cov_knots=(), quantiles=())")
         if getattr(controller, "controlfunction", None) is not None:
             raise ValueError("ensemble= with a custom controlfunction is not supported: the device forms the feedback command of the fused laws, a closure computes its own inputs")
         if ensemble.mechanism is not mechanism:
@@ -1550,6 +1582,9 @@ def simulate(mechanism, tend_or_storage, controller, record=True, z0=None, fric=
             raise ValueError("ensemble= needs at least one step")
         if ensemble.cov_knots and ensemble.cov_knots[-1] >= steps:
             raise ValueError("cov_knots must lie in 0 .. steps - 1 = %d (got %s)" % (steps - 1, list(ensemble.cov_knots)))
+        if ensemble.quantiles and z0.shape[0] > _capi.QUANTILE_MAX_INST:
+            raise ValueError("quantiles= are taken over at most %d instances per run (got %d): the moments of shards merge, their order statistics do not"
+                             % (_capi.QUANTILE_MAX_INST, z0.shape[0]))
     if score is not None or ensemble is not None:
         if chunk_steps is None:
             chunk_steps = _capi.default_chunk_steps(z0.shape[0], nb, steps)
@@ -1572,12 +1607,13 @@ def simulate(mechanism, tend_or_storage, controller, record=True, z0=None, fric=
         try:
             sh = None if score is None else score._handle(dev)
             traj = np.zeros((z0.shape[0], steps, nb, 13)) if record else None
-            ens = None if ensemble is None else (ctrl.mu, ensemble.cov_knots)
+            ens = None if ensemble is None else ((ctrl.mu, ensemble.cov_knots) + ((ensemble.quantiles,) if ensemble.quantiles else ()))
             got = _capi.rollout_scored(dev, ctrl, sh, z0, steps, int(chunk_steps), noise=noise, first_instance=first_instance, plants=ph, traj_out=traj, ensemble=ens)
             zT, status, scores = got[:3]
             if ensemble is not None:
-                emean, eM2, eC = got[3]
-                stats = EnsembleStats(z0.shape[0], emean[:, :12 * nb], eM2[:, :12 * nb], emean[:, 12 * nb:], eM2[:, 12 * nb:], eC)
+                emean, eM2, eC = got[3][:3]
+                more = dict(probs=ensemble.quantiles, quantiles=got[3][3], finite_count=got[3][4]) if ensemble.quantiles else {}
+                stats = EnsembleStats(z0.shape[0], emean[:, :12 * nb], eM2[:, :12 * nb], emean[:, 12 * nb:], eM2[:, 12 * nb:], eC, **more)
         finally:
             if sh is not None:
                 sh.close()

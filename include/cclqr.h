@@ -62,7 +62,9 @@ extern "C" {
  * Still 202 (additive, no struct changed): the cost-to-go of a TRACKED run at every knot and the price of its noise, a model and a gain row per knot -- cclqr_policy_value_tracking, cclqr_value_create_policy_tracking;
  * looked up the same way.  cclqr_policy_value, cclqr_value_create_policy and the two tracking-covariance entries are unchanged.
  * Still 202 (additive, no struct changed): the statistics of a slab ACROSS its instances at every step -- cclqr_rollout_ensemble_ws_bytes, cclqr_rollout_ensemble; looked up
- * the same way.  cclqr_rollout_score is unchanged. */
+ * the same way.  cclqr_rollout_score is unchanged.
+ * Still 202 (additive, no struct changed): the quantiles of a slab ACROSS its instances at every step -- cclqr_rollout_quantiles_ws_bytes, cclqr_rollout_quantiles; looked up
+ * the same way.  cclqr_rollout_ensemble is unchanged. */
 #define CCLQR_ABI_VERSION 202
 
 #define CCLQR_REVOLUTE 0      /* EqualityConstraint(Revolute(a, b, axis; p1, p2, qoffset)),  examples/lqr_cartpole.jl:26 */
@@ -715,6 +717,32 @@ int cclqr_rollout_ensemble(const cclqr_mech *m, const cclqr_ctrl *c, int64_t n_i
                            const double *traj_dev, double *mean_dev, double *m2_dev,
                            int32_t n_cov, const int32_t *cov_steps /* host; absolute steps, each within k0 .. k0+steps-1 */, double *cov_dev,
                            void *ws_dev, size_t ws_bytes, void *stream);
+
+/* Ensemble quantiles of a rollout on the device (additive, still 202, no struct changed; looked up by name like the entries above).  cclqr_rollout_ensemble gives
+ * the second moments of a Monte-Carlo run of the reference -- simulate! (examples/lqr_cartpole.jl:44) under the `randn()` of examples/trackingLQR_triple_cartpole.jl:98
+ * --; this gives its fan chart: the median, the tails and the extremes of every coordinate at every step, without the trajectory.  Indexing and x are those of
+ * cclqr_rollout_ensemble: slab row r = k - k0, instance i has the global index gi = first_instance + i, x_{i,k} = (Δz_{i,k}, Δu_{i,k}) with 12 nb + mu coordinates,
+ * Δz in the CALLER'S body order, Δu in the controller's input order under the same gate (0 without gains); x is bit for bit the x that call reduces.
+ * For each step k and coordinate c let s_0 <= ... <= s_{cnt-1} be the FINITE values among x_{i,k,c}, i = 0 .. n_inst - 1, sorted as numbers, -0.0 before +0.0; values
+ * that are not finite are left out and counted out.  For each of the n_prob probabilities p in [0, 1] listed in prob (HOST array, at most CCLQR_QUANTILE_MAX_PROBS)
+ *     h = p (cnt - 1),  lo = floor(h),  g = h - lo,  hi = min(lo + 1, cnt - 1),  q = s_lo + g (s_hi - s_lo)
+ * in fp64 as written, each operation rounded once (no fused multiply-add); whenever g = 0 the result is the order statistic s_lo itself, bit for bit: p = 0 is the
+ * minimum, p = 1 the maximum.  cnt = 0 gives NaN.  The call writes  quant_dev [steps][n_prob][12 nb + mu]  and, unless it is NULL,  finite_dev [steps][12 nb + mu]
+ * (int32) = cnt.  All instances count: a lost instance enters with its frozen pose (read `status`).
+ * The result is a function of the multiset of values only: the same bits for any chunking of the horizon, any workspace size, a second call, and any permutation of
+ * the instances under a one-table controller.
+ * All pointers are DEVICE pointers except prob; asynchronous on `stream`; nothing is allocated, nothing synchronises.  ws_dev, 8-byte aligned: the values of the rows,
+ * transposed.  cclqr_rollout_quantiles_ws_bytes gives min_bytes (one slab row) and full_bytes (all `steps` rows); the call works through the rows in blocks of as many
+ * as ws_bytes holds, and the bits do not depend on ws_bytes.  CCLQR_EINVAL, before anything is launched, with the cause in cclqr_last_error and the outputs untouched:
+ * a null, short (ws_bytes < min_bytes) or misaligned workspace, n_prob outside 1 .. 16, a prob entry outside [0, 1] or NaN, n_inst < 1, steps < 1 or k0 < 1, and every
+ * controller and handle refusal of cclqr_rollout_ensemble.  n_inst > CCLQR_QUANTILE_MAX_INST (a coordinate's keys are sorted in one workgroup's LDS) is
+ * CCLQR_EUNSUPPORTED.  Every topology cclqr_mech_create takes. */
+#define CCLQR_QUANTILE_MAX_INST  16384
+#define CCLQR_QUANTILE_MAX_PROBS 16
+int cclqr_rollout_quantiles_ws_bytes(const cclqr_mech *m, int32_t mu, int64_t n_inst, int32_t steps, size_t *min_bytes, size_t *full_bytes);
+int cclqr_rollout_quantiles(const cclqr_mech *m, const cclqr_ctrl *c, int64_t n_inst, int32_t steps, int32_t k0, int64_t first_instance,
+                            const double *traj_dev, int32_t n_prob, const double *prob /* host */,
+                            double *quant_dev, int32_t *finite_dev, void *ws_dev, size_t ws_bytes, void *stream);
 
 /* cclqr_rollout (HOST pointers) with options: first_instance and newton_mode apply, the device-buffer fields must be NULL. */
 int cclqr_rollout_host_ex(const cclqr_mech *m, const cclqr_ctrl *c, int64_t n_inst, int32_t steps, int32_t k0, const double *z0,

@@ -467,6 +467,24 @@ function rollout_ensemble!(h::MechHandle, c::CtrlHandle, n::Integer, steps::Inte
                 h.ptr, c.ptr, n, steps, k0, first_instance, traj, mean, m2, length(cov_steps), cov_steps, cov, ws, ws_bytes, stream))
 end
 
+"(min_bytes, full_bytes) of device workspace for rollout_quantiles! (cclqr_rollout_quantiles_ws_bytes): one slab row, all `steps` rows."
+function rollout_quantiles_ws_bytes(h::MechHandle, mu::Integer, n::Integer, steps::Integer)
+    lo = Ref{Csize_t}(0); full = Ref{Csize_t}(0)
+    check(ccall((:cclqr_rollout_quantiles_ws_bytes, lib), Cint, (Ptr{Cvoid}, Int32, Int64, Int32, Ref{Csize_t}, Ref{Csize_t}), h.ptr, mu, n, steps, lo, full))
+    Int(lo[]), Int(full[])
+end
+
+"The quantiles of the slab a rollout_dev! launch has just written ACROSS its instances (cclqr_rollout_quantiles; device pointers except prob, asynchronous on
+ `stream`): quant is (12 nb + mu) x length(prob) x steps -- per step and probability the quantile of the finite values of every coordinate of (Δz, Δu), 0 the
+ minimum, 1 the maximum --, finite (12 nb + mu) x steps their number (or C_NULL).  At most 16384 instances and 16 probabilities.  A function of the multiset of
+ values alone: behind every launch of the chunk loop, with quant / finite advanced by (k0 - 1) steps, any chunking and any ws_bytes >= min_bytes give the same bits."
+function rollout_quantiles!(h::MechHandle, c::CtrlHandle, n::Integer, steps::Integer, k0::Integer, traj::Ptr{Float64}, prob::Vector{Float64}, quant::Ptr{Float64},
+                            ws::Ptr{Cvoid}, ws_bytes::Integer; finite::Ptr{Int32} = Ptr{Int32}(C_NULL), first_instance = 0, stream::Ptr{Cvoid} = C_NULL)
+    check(ccall((:cclqr_rollout_quantiles, lib), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int32, Int32, Int64, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Cvoid}, Csize_t, Ptr{Cvoid}),
+                h.ptr, c.ptr, n, steps, k0, first_instance, traj, length(prob), prob, quant, finite, ws, ws_bytes, stream))
+end
+
 "dlqr_weights that also returns the cost-to-go (cclqr_riccati_value): P[p] is the Pkp1 of lqr.jl:170 at the last backward step problem p executed (the step the
  break test of lqr.jl:172 fired on, else step 1; Q_p when N = 1), mx x mx as the recursion holds it.  Returns (Ku[p][k][i], P[p], kbreak[p])."
 function dlqr_value(As::Vector, Bus::Vector, Bλs::Vector, Gs::Vector, Qs::Vector, Rs::Vector, N::Integer; tol = 1e-5)
