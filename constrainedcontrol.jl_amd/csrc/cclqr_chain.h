@@ -1081,19 +1081,30 @@ HD void cr_store_a(const CrLane<W>& K, double* L, const double (*tA)[5]) {
             for (int r = 0; r < 5; r++) { L[K.oRhs[s] + r] = K.z[s][r]; L[K.oA[s] + r] = tA[s][r]; }
         }
 }
-template <int W>
+// ZLDS (the fixed-plan kernels): the lane's solutions are read back from where cr_store_a has just put them, K.oRhs[s], and K.z is not read: the same
+// lane stored them and its LDS operations stay in order, nothing writes those slots again before cr_back, and a slot that is not in use reads words of
+// S_ll, inside the image, for a column nobody stores.  The same bits as K.z, for 15 reads next to the phase's 40 others: with z dead at cr_store_a, and
+// no fence between a phase's arithmetic and its stores, the allocator no longer keeps the 45 doubles of a pass in accumulation registers across the
+// joins of the lane regions -- a move per dword in and, for z, a move out, all in front of a hand-over.
+template <int W, bool ZLDS = false>
 HD void cr_phase_b(const CrLane<W>& K, const double* L, double (*tB)[5]) {
     if (!(K.act() && K.has_n())) return;
-    double blk[25];
+    double blk[25], zl[CrLane<W>::NS][5];
 #pragma unroll
     for (int s = 0; s < CrLane<W>::NS; s++)
 #pragma unroll
         for (int r = 0; r < 5; r++) tB[s][r] = LDS_RD(L, K.oB[s] + r);
+    if (ZLDS) {
+#pragma unroll
+        for (int s = 0; s < CrLane<W>::NS; s++)
+#pragma unroll
+            for (int r = 0; r < 5; r++) zl[s][r] = LDS_RD(L, K.oRhs[s] + r);
+    }
 #pragma unroll
     for (int e = 0; e < 25; e++) blk[e] = LDS_RD(L, K.oNL + e);
 #pragma unroll
     for (int s = 0; s < CrLane<W>::NS; s++) {
-        const double* z = K.z[s];
+        const double* z = ZLDS ? zl[s] : K.z[s];
         const double keep = K.kind(s) != 0 ? 1.0 : 0.0;
 #pragma unroll
         for (int r = 0; r < 5; r++) tB[s][r] = keep * tB[s][r] - (blk[r] * z[0] + blk[5 + r] * z[1] + blk[10 + r] * z[2] + blk[15 + r] * z[3] + blk[20 + r] * z[4]);
@@ -1107,6 +1118,23 @@ HD void cr_store_b(const CrLane<W>& K, double* L, const double (*tB)[5]) {
 #pragma unroll
             for (int r = 0; r < 5; r++) L[K.oB[s] + r] = tB[s][r];
         }
+}
+// ---- the two passes as the fixed-plan kernels run them: every pass with columns of its OWN, no fence between a pass's arithmetic and its stores, z of
+// pass B from LDS.  (One array for both passes, as rollout_chain_kernel has it, carries pass A's columns into pass B on the lanes that sit pass B out --
+// alive over the hand-over; and as functions of this header, not as two blocks of the kernel's text: the same statements written there compile to 270
+// instructions more)  The phases stay functions of their own: a host build runs the lanes one after another and needs every lane's loads in
+// front of any lane's stores.
+template <int W>
+__device__ __forceinline__ void cr_level_a(CrLane<W>& K, double* L) {
+    double tA[CrLane<W>::NS][5];
+    cr_phase_a<W>(K, L, tA);
+    cr_store_a<W>(K, L, tA);
+}
+template <int W>
+__device__ __forceinline__ void cr_level_b(CrLane<W>& K, double* L) {
+    double tB[CrLane<W>::NS][5];
+    cr_phase_b<W, true>(K, L, tB);
+    cr_store_b<W>(K, L, tB);
 }
 // multiplier steps of the eliminated (odd) links, rows dealt to the link's W lanes
 template <int W>

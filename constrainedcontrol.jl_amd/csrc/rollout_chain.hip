@@ -51,6 +51,13 @@ __device__ __forceinline__ void from_next(const double* in, double* out) {
 // stale.  A chain without a sweep step takes front 0's share from the reads of ck_tri_back0_load, behind a wavefront-uniform BRANCH: as a select
 // it would make every solve wait for those reads in front of the pivot chain.  Called by ALL lanes in wavefront-uniform control flow (a DPP
 // move reads lanes, so none of the row may be masked off); the result is garbage, and unused, outside the sweep lanes of instances that solve.
+// B64 (the fixed-plan kernels): each broadcast is ONE 64-bit DPP move (v_mov_b64_dpp; row_newbcast is the control of this kernel that is legal on a
+// 64-bit operand) instead of one per dword -- 30 moves for 60 between the last sweep step and the pivot chain.  The same bits land in the same lanes.
+template <int CTRL>
+__device__ __forceinline__ double dpp_b64(double v) {
+    return __longlong_as_double(__builtin_amdgcn_update_dpp(0ll, __double_as_longlong(v), CTRL, 0xf, 0xf, true));
+}
+template <bool B64 = false>
 __device__ __forceinline__ void ck_tri_mid_regs(int t, bool done, const TriPlanB& B, const TriCur& K, const Lay& Y, const double* L, const double* tg, double* dl, TriBack0& Q) {
     const TriPlan& P = B.P;
     ck_tri_back0_load(Q, t, done, B, K, Y, L);
@@ -69,9 +76,15 @@ __device__ __forceinline__ void ck_tri_mid_regs(int t, bool done, const TriPlanB
     double A[25];
 #pragma unroll
     for (int i = 0; i < 5; i++) {
+        if constexpr (B64) {
+            A[i * 5 + 0] = dpp_b64<0x150>(m[i]); A[i * 5 + 1] = dpp_b64<0x151>(m[i]); A[i * 5 + 2] = dpp_b64<0x152>(m[i]);
+            A[i * 5 + 3] = dpp_b64<0x153>(m[i]); A[i * 5 + 4] = dpp_b64<0x154>(m[i]);
+            dl[i] = dpp_b64<0x155>(m[i]);
+        } else {
         A[i * 5 + 0] = dpp_f64<0x150>(m[i]); A[i * 5 + 1] = dpp_f64<0x151>(m[i]); A[i * 5 + 2] = dpp_f64<0x152>(m[i]);      // row_newbcast:k
         A[i * 5 + 3] = dpp_f64<0x153>(m[i]); A[i * 5 + 4] = dpp_f64<0x154>(m[i]);
         dl[i] = dpp_f64<0x155>(m[i]);
+        }
     }
     lu5_factor(A);
     lu5_solve(A, dl);
@@ -682,6 +695,17 @@ __global__ __launch_bounds__(WAVE_BLOCK) void rollout_chain_kernel(RolloutArgs a
                 const bool cr = CR && cn >= CR_MIN_LINKS;
                 if (CR && cr) {
                     CrLane<CRW> CK;
+#if CHAIN_PLAN_FIXED
+                    // each pass's arithmetic and stores unfenced, on columns of its own, z of pass B from LDS (cclqr_chain.h cr_level_a): nothing of a pass is
+                    // parked in accumulation registers on its way to LDS
+                    cr_setup<CRW>(CK, t, cs, cn, 1, Y, done);
+                    CR_FLAGS_FRESH(CK);
+                    cr_level_a<CRW>(CK, L);
+                    WAVE_HANDOVER();
+                    CR_FLAGS_FRESH(CK);
+                    cr_level_b<CRW>(CK, L);
+                    WAVE_HANDOVER();
+#else
                     double tc[CrLane<CRW>::NS][5];
                     cr_setup<CRW>(CK, t, cs, cn, 1, Y, done);
                     CR_FLAGS_FRESH(CK);
@@ -694,6 +718,7 @@ __global__ __launch_bounds__(WAVE_BLOCK) void rollout_chain_kernel(RolloutArgs a
                     CR_FLAGS_FRESH(CK);
                     cr_store_b<CRW>(CK, L, tc);
                     WAVE_HANDOVER();
+#endif
                 }
                 STAMP(PF_SCHUR_W);
                 const TriPlanB PB = cr ? tri_plan_balanced(cs, (cn + 1) / 2, 2) : tri_plan_balanced(cs, cn, 1, G >= 16 ? 2 : 1);
@@ -718,7 +743,11 @@ __global__ __launch_bounds__(WAVE_BLOCK) void rollout_chain_kernel(RolloutArgs a
                     }
                     STAMP(PF_TRI_FWD);
                     TriBack0 B0;
+#if CHAIN_PLAN_FIXED
+                    ck_tri_mid_regs<true>(t, done, PB, K, Y, L, tg, dlm, B0);      // (64-bit broadcasts)
+#else
                     ck_tri_mid_regs(t, done, PB, K, Y, L, tg, dlm, B0);
+#endif
                     ck_tri_back0_store(B0, t, Y, L, dlm);
                     WAVE_HANDOVER();
 #if CHAIN_PLAN_FIXED
