@@ -1411,36 +1411,133 @@ __global__ void k_rows_to_body_order_kernel(const double* K, long long nrows, lo
     for (int e = threadIdx.x; e < 12 * nb; e += blockDim.x) { const int l = e / 12; o[12 * M->perm[l] + (e - 12 * l)] = p[e]; }
 }
 
-// shared tail of the two entry points: the recursion on device-resident models and gains (dK: tables k_stride doubles apart, 0 = one shared), inside the caller's
-// WsScope.  dP: device [nprob][mx][mx], written by the kernels.  kb, st [nprob] and dn [nprob][2] come back on the host; the caller words the refusals
-static int run_policy(int nprob, int mx, int mu, int ml, int N, double tol, const double* dA, const double* dBu, const double* dBl, const double* dG, const double* dK,
-                      long long k_stride, int nK, int n_weights, const double* Q, const double* R, int path, double* dP, std::vector<int>& kb, std::vector<int>& st,
-                      std::vector<double>& dn) {
-    static const char* const what = "policy evaluation";
-    double *dQ = nullptr, *dR = nullptr, *dwork = nullptr, *ddn = nullptr;
-    int *dkb = nullptr, *dst = nullptr, *dstop = nullptr;
-    const size_t np = (size_t)nprob, nw = (size_t)n_weights;
-    PolArgs a;
-    RicArgs& r = a.r;
-    r.nprob = nprob; r.mx = mx; r.mu = mu; r.ml = ml; r.N = N; r.time_varying = 0; r.tol = tol; r.path = path; r.bf16_terms = 0; r.keep_last = 0; r.K = nullptr;
-    if (n_weights > 1) { r.q_stride = (long long)mx * mx; r.r_stride = (long long)mu * mu; }
+// ---- the host sequences the analysis entry points below share: a new analysis calls these, it does not copy them under a new name
+// the sizes of a launch record: fp64 (bf16_terms = 0), no gain output.  Callers: run_policy, doubling_args, tracking_setup, tracking_value_on_plants, cclqr_riccati_doubling
+static void ric_sizes(RicArgs& r, int nprob, int mx, int mu, int ml, int N, int time_varying, double tol, int path, int keep_last = 0) {
+    r.nprob = nprob; r.mx = mx; r.mu = mu; r.ml = ml; r.N = N; r.time_varying = time_varying; r.tol = tol; r.path = path; r.bf16_terms = 0; r.keep_last = keep_last; r.K = nullptr;
+}
+// host weights [n_weights][mx][mx], [n_weights][mu][mu] onto the device with their strides, inside the caller's WsScope.  Callers: run_policy, run_doubling,
+// run_covariance, ctk_setup, ptk_setup, cclqr_riccati_doubling
+static int upload_weights(int mx, int mu, int n_weights, const double* Q, const double* R, WeightsIn& w, const char* what) {
+    const size_t nw = (size_t)n_weights;
+    double *dQ = nullptr, *dR = nullptr;
     HIPTRY(what, ws_get((void**)&dQ, nw * mx * mx * sizeof(double)));
     HIPTRY(what, ws_get((void**)&dR, (nw * mu * mu + 1) * sizeof(double)));
+    HIPTRY(what, hipMemcpy(dQ, Q, nw * mx * mx * sizeof(double), hipMemcpyHostToDevice));
+    if (mu > 0) HIPTRY(what, hipMemcpy(dR, R, nw * mu * mu * sizeof(double), hipMemcpyHostToDevice));
+    w.Q = dQ; w.R = dR;
+    if (n_weights > 1) { w.q_stride = (long long)mx * mx; w.r_stride = (long long)mu * mu; }
+    return CCLQR_OK;
+}
+// ... as the recursion's own weights.  Callers: run_policy, run_doubling, ptk_setup, cclqr_riccati_doubling
+static void ric_weights(RicArgs& r, const WeightsIn& w) { r.Q = w.Q; r.R = w.R; r.q_stride = w.q_stride; r.r_stride = w.r_stride; }
+// host noise Wu [n_noise][mu][mu] and Sigma0 [n_noise][mx][mx] (each may be null: not given) onto the device with their strides, inside the caller's WsScope.
+// Callers: run_covariance, tracking_setup
+static int upload_noise(int mx, int mu, int n_noise, const double* Wu, const double* Sigma0, NoiseIn& n, const char* what) {
+    const size_t nn = (size_t)n_noise, mm = (size_t)mx * mx, uu = (size_t)mu * mu;
+    double *dWu = nullptr, *dS0 = nullptr;
+    if (Wu) {
+        HIPTRY(what, ws_get((void**)&dWu, nn * uu * sizeof(double)));
+        HIPTRY(what, hipMemcpy(dWu, Wu, nn * uu * sizeof(double), hipMemcpyHostToDevice));
+        n.Wu = dWu; n.wu_stride = n_noise > 1 ? (long long)uu : 0;
+    }
+    if (Sigma0) {
+        HIPTRY(what, ws_get((void**)&dS0, nn * mm * sizeof(double)));
+        HIPTRY(what, hipMemcpy(dS0, Sigma0, nn * mm * sizeof(double), hipMemcpyHostToDevice));
+        n.Sigma0 = dS0; n.s0_stride = n_noise > 1 ? (long long)mm : 0;
+    }
+    return CCLQR_OK;
+}
+// What a recursion runs on, on the device: the models, the gain tables and the [nprob][mx][mx] matrix it writes (P or Σ).  raw_upload fills it for the entries on
+// caller-supplied matrices, policy_models_and_gains for those on a mechanism's plants
+struct AnaDev { RicModels m; GainTable k; double* P; };
+// the preamble of a raw entry, inside its WsScope: models_per_problem host models of every problem (0: no model is read), n_gains host tables of `rows` rows
+// (gains_read = false: no step reads a gain, none is copied) and the matrix the kernels write.  Callers: cclqr_policy_value, cclqr_policy_value_doubling,
+// cclqr_covariance_doubling, tracking_raw_upload
+static int raw_upload(const char* what, int nprob, int mx, int mu, int ml, int models_per_problem, const double* A, const double* Bu, const double* Bl, const double* G,
+                      int n_gains, int rows, bool gains_read, const double* K, AnaDev& d) {
+    d = AnaDev{};
+    if (models_per_problem > 0) TRY(upload_models((size_t)nprob * models_per_problem, mx, mu, ml, A, Bu, Bl, G, d.m));
+    const size_t nKd = (mu > 0 && gains_read) ? (size_t)n_gains * rows * mu * mx : 0;
+    double* dK = nullptr;
+    HIPTRY(what, ws_get((void**)&dK, (nKd + 1) * sizeof(double)));
+    HIPTRY(what, ws_get((void**)&d.P, (size_t)nprob * mx * mx * sizeof(double)));
+    if (nKd) HIPTRY(what, hipMemcpy(dK, K, nKd * sizeof(double), hipMemcpyHostToDevice));
+    d.k.Kin = dK; d.k.k_stride = n_gains > 1 ? (long long)rows * mu * mx : 0; d.k.nK = rows;
+    return CCLQR_OK;
+}
+// n values from the device into v.  Callers: every read-back of the analyses (run_policy, doubling_read_back, run_covariance, ctk_ / ptk_ / tracking_read_back)
+template <class T>
+static int download(std::vector<T>& v, const T* dev, size_t n, const char* what) {
+    v.resize(n);
+    HIPTRY(what, hipMemcpy(v.data(), dev, n * sizeof(T), hipMemcpyDeviceToHost));
+    return CCLQR_OK;
+}
+// problem p's pair of a [nprob][2] diagnostic into the caller's array (may be null).  Callers: policy_report, doubling_report, covariance_report, tracking_cov_report
+static void put_pair(double* out, const std::vector<double>& v, size_t p) {
+    if (out) { out[2 * p] = v[2 * p]; out[2 * p + 1] = v[2 * p + 1]; }
+}
+// the refusal of a singular G Bλ in problem / model / table p, with its knot where the recursion names one.  Callers: policy_report, doubling_report,
+// tracking_cov_report, tracking_pol_report
+static int singular_in(const char* of, long long p, const int* knot = nullptr) {
+    return fail(CCLQR_ESINGULAR, std::string("G*Bl is singular in ") + of + " " + std::to_string(p) + (knot ? " at knot " + std::to_string(*knot) : std::string()));
+}
+// the refusals several entries word alike, before anything is allocated or launched.  n_gains: tables = whole gain tables, else single stationary gains (always per
+// problem).  Callers: cclqr_policy_value, tracking_counts_check / cclqr_policy_value_doubling, cclqr_covariance_doubling
+static int check_n_gains(int n_gains, int nprob, bool tables, const char* of) {
+    if (n_gains == 1 || n_gains == nprob) return CCLQR_OK;
+    return fail(CCLQR_EINVAL, "n_gains = " + std::to_string(n_gains) + (tables ? std::string(": the gains are one table shared by all (1) or one table per ") + of
+                                                                               : std::string(": one gain shared by all (1) or one per problem")) + " (" + std::to_string(nprob) + ")");
+}
+// n_noise: are = "Wu / Sigma0 are" or "Wu is".  Callers: covariance_check, tracking_cov_check, tracking_pol_check
+static int check_n_noise(int n_noise, int nprob, const char* are, const char* of) {
+    if (n_noise == 1 || n_noise == nprob) return CCLQR_OK;
+    return fail(CCLQR_EINVAL, "n_noise = " + std::to_string(n_noise) + ": " + are + " one shared by all (1) or one per " + of + " (" + std::to_string(nprob) + ")");
+}
+// the options of an analysis that runs in fp64 on path 0..2: what = its name, the = "the " where the sentence takes the article.  Callers: cclqr_policy_value,
+// doubling_check, tracking_launch_check
+static int check_fp64_path(const cclqr_riccati_opts* opts, const char* what, const char* the) {
+    const int path = opts ? opts->path : 0;
+    if (path < 0 || path > 2) return fail(CCLQR_EINVAL, std::string(what) + " options: path in 0..2");
+    if (opts && opts->bf16_terms != 0) return fail(CCLQR_EINVAL, std::string(the) + what + " runs in fp64 only (bf16_terms = 0)");
+    return CCLQR_OK;
+}
+
+// ---- policy evaluation's own
+// shared tail of the two entry points: the recursion on device-resident models and gains, inside the caller's WsScope; d.P is written by the kernels.  kb, st [nprob]
+// and dn [nprob][2] come back on the host
+static int run_policy(int nprob, int mx, int mu, int ml, int N, double tol, const AnaDev& d, int n_weights, const double* Q, const double* R, int path,
+                      std::vector<int>& kb, std::vector<int>& st, std::vector<double>& dn) {
+    static const char* const what = "policy evaluation";
+    double *dwork = nullptr, *ddn = nullptr;
+    int *dkb = nullptr, *dst = nullptr, *dstop = nullptr;
+    const size_t np = (size_t)nprob;
+    PolArgs a;
+    RicArgs& r = a.r;
+    WeightsIn w;
+    ric_sizes(r, nprob, mx, mu, ml, N, 0, tol, path);
+    TRY(upload_weights(mx, mu, n_weights, Q, R, w, what));
+    ric_weights(r, w);
     HIPTRY(what, ws_get((void**)&dwork, ric_total_work_doubles(r) * sizeof(double)));
     HIPTRY(what, ws_get((void**)&ddn, 2 * np * sizeof(double)));
     HIPTRY(what, ws_get((void**)&dstop, np * sizeof(int)));
     HIPTRY(what, ws_get((void**)&dkb, np * sizeof(int)));
     HIPTRY(what, ws_get((void**)&dst, np * sizeof(int)));
-    HIPTRY(what, hipMemcpy(dQ, Q, nw * mx * mx * sizeof(double), hipMemcpyHostToDevice));
-    if (mu > 0) HIPTRY(what, hipMemcpy(dR, R, nw * mu * mu * sizeof(double), hipMemcpyHostToDevice));
-    r.stop = dstop; r.A = dA; r.Bu = dBu; r.Bl = dBl; r.G = dG; r.Q = dQ; r.R = dR; r.kbreak = dkb; r.status = dst; r.work = dwork; r.P_out = dP;
-    a.Kin = dK; a.k_stride = k_stride; a.nK = nK; a.dnorm = ddn;
+    r.stop = dstop; r.A = d.m.A; r.Bu = d.m.Bu; r.Bl = d.m.Bl; r.G = d.m.G; r.kbreak = dkb; r.status = dst; r.work = dwork; r.P_out = d.P;
+    a.k = d.k; a.dnorm = ddn;
     HIPTRY(what, launch_policy(a, nullptr));
     HIPTRY(what, hipDeviceSynchronize());
-    kb.resize(np); st.resize(np); dn.resize(2 * np);
-    HIPTRY(what, hipMemcpy(kb.data(), dkb, np * sizeof(int), hipMemcpyDeviceToHost));
-    HIPTRY(what, hipMemcpy(st.data(), dst, np * sizeof(int), hipMemcpyDeviceToHost));
-    HIPTRY(what, hipMemcpy(dn.data(), ddn, 2 * np * sizeof(double), hipMemcpyDeviceToHost));
+    TRY(download(kb, dkb, np, what));
+    TRY(download(st, dst, np, what));
+    return download(dn, ddn, 2 * np, what);
+}
+// ... and its diagnostics into the caller's arrays (each may be null), up to the problem the call is refused for
+static int policy_report(const std::vector<int>& kb, const std::vector<int>& st, const std::vector<double>& dn, int nprob, int32_t* kbreak, double* dnorm, const char* of) {
+    for (int p = 0; p < nprob; p++) {
+        if (kbreak) kbreak[p] = kb[p];
+        put_pair(dnorm, dn, p);
+        if (st[p] != 0) return singular_in(of, p);
+    }
     return CCLQR_OK;
 }
 // what both entry points refuse about the recursion's own sizes, before anything is allocated or launched
@@ -1453,45 +1550,36 @@ static int policy_check(int nprob, int mu, int N, int nK, int n_weights, const c
 extern "C" int cclqr_policy_value(int32_t nprob, int32_t mx, int32_t mu, int32_t ml, const double* A, const double* Bu, const double* Bl, const double* G,
                                   int32_t n_gains, int32_t nK, const double* K, int32_t n_weights, const double* Q, const double* R, int32_t N, double tol,
                                   double* P, int32_t* kbreak, double* dnorm, const cclqr_riccati_opts* opts) {
+    static const char* const what = "policy evaluation";
     if (!A || !Q || !P || (mu > 0 && (!Bu || !R)) || (ml > 0 && (!Bl || !G)) || (mu > 0 && N > 1 && !K)) return fail(CCLQR_EINVAL, "null argument");
     if (nprob < 1 || mx < 1 || mu < 0 || ml < 0 || N < 1) return fail(CCLQR_EINVAL, "bad sizes");
-    if (n_gains != 1 && n_gains != nprob)
-        return fail(CCLQR_EINVAL, "n_gains = " + std::to_string(n_gains) + ": the gains are one table shared by all (1) or one table per problem (" + std::to_string(nprob) + ")");
+    TRY(check_n_gains(n_gains, nprob, true, "problem"));
     TRY(policy_check(nprob, mu, N, nK, n_weights, "problem"));
-    const int path = opts ? opts->path : 0;
-    if (path < 0 || path > 2) return fail(CCLQR_EINVAL, "policy evaluation options: path in 0..2");
-    if (opts && opts->bf16_terms != 0) return fail(CCLQR_EINVAL, "policy evaluation runs in fp64 only (bf16_terms = 0)");
+    TRY(check_fp64_path(opts, what, ""));
     WsScope scope;
-    RicModels d = {};
-    TRY(upload_models((size_t)nprob, mx, mu, ml, A, Bu, Bl, G, d));
-    const size_t nKd = (mu > 0 && N > 1) ? (size_t)n_gains * nK * mu * mx : 0, nP = (size_t)nprob * mx * mx;
-    double *dK = nullptr, *dP = nullptr;
-    HIPTRY("policy evaluation", ws_get((void**)&dK, (nKd + 1) * sizeof(double)));
-    HIPTRY("policy evaluation", ws_get((void**)&dP, nP * sizeof(double)));
-    if (nKd) HIPTRY("policy evaluation", hipMemcpy(dK, K, nKd * sizeof(double), hipMemcpyHostToDevice));
+    AnaDev d;
+    TRY(raw_upload(what, nprob, mx, mu, ml, 1, A, Bu, Bl, G, n_gains, nK, N > 1, K, d));
     std::vector<int> kb, st;
     std::vector<double> dn;
-    TRY(run_policy(nprob, mx, mu, ml, N, tol, d.A, d.Bu, d.Bl, d.G, dK, n_gains > 1 ? (long long)nK * mu * mx : 0, nK, n_weights, Q, R, path, dP, kb, st, dn));
-    HIPTRY("policy evaluation", hipMemcpy(P, dP, nP * sizeof(double), hipMemcpyDeviceToHost));
-    for (int p = 0; p < nprob; p++) {      // kbreak and dnorm are filled up to the problem the call is refused for
-        if (kbreak) kbreak[p] = kb[p];
-        if (dnorm) { dnorm[2 * p] = dn[2 * (size_t)p]; dnorm[2 * p + 1] = dn[2 * (size_t)p + 1]; }
-        if (st[p] != 0) return fail(CCLQR_ESINGULAR, "G*Bl is singular in problem " + std::to_string(p));
-    }
-    return CCLQR_OK;
+    TRY(run_policy(nprob, mx, mu, ml, N, tol, d, n_weights, Q, R, opts ? opts->path : 0, kb, st, dn));
+    HIPTRY(what, hipMemcpy(P, d.P, (size_t)nprob * mx * mx * sizeof(double), hipMemcpyDeviceToHost));
+    return policy_report(kb, st, dn, nprob, kbreak, dnorm, "problem");
 }
 
-// what the controller entry points of the policy evaluation (stepping and doubling) refuse about the mechanism, the controller and the plants, before anything is
-// allocated or launched; bad_sizes: the caller's own test of its counts.  cj: the controlled links; *tables: the controller's gain tables (1 or n_models)
+// what the controller entry points of every analysis refuse about the mechanism, the controller and the plants, before anything is allocated or launched; subject:
+// the analysis as the closed-loop refusal names it; bad_sizes: the caller's own test of its counts; stationary: the analysis is of time-invariant models only.  cj: the
+// controlled links; *tables: the controller's gain tables (1 or n_models).  Callers: cclqr_value_create_policy, _policy_doubling, _covariance_doubling (stationary),
+// tracking_value_on_plants
 static int policy_ctrl_check(const cclqr_mech* m, const cclqr_plants* plants, int64_t first_plant, int32_t n_models, int32_t mu, const int32_t* ctrl_joint,
-                             const cclqr_ctrl* c, bool bad_sizes, int* cj, int64_t* tables) {
+                             const cclqr_ctrl* c, const std::string& subject, bool bad_sizes, bool stationary, int* cj, int64_t* tables) {
     TRY(check_device(m));
-    if (m->host.loop) return fail(CCLQR_EUNSUPPORTED, "policy evaluation is for tree mechanisms (closed loops have no multiplier model to evaluate a gain on)");
+    if (m->host.loop) return fail(CCLQR_EUNSUPPORTED, subject + " is for tree mechanisms (closed loops have no multiplier model to evaluate a gain on)");
     if (c->nb != m->nb || c->device != m->device) return fail(CCLQR_EINVAL, "the controller was created for another mechanism or device");
     if (bad_sizes) return fail(CCLQR_EINVAL, "bad sizes");
     const CtrlDev& H = c->host;
     if (!c->K_dev || H.nK < 1) return fail(CCLQR_EINVAL, "the controller has no gains (open loop / PID)");
-    if (H.nsp > 1) return fail(CCLQR_EUNSUPPORTED, "tracking controllers (more than one setpoint row per table) are outside policy evaluation's scope: time-invariant models only");
+    if (stationary && H.nsp > 1)
+        return fail(CCLQR_EUNSUPPORTED, "tracking controllers (more than one setpoint row per table) are outside policy evaluation's scope: time-invariant models only");
     TRY(linearize_check(m, plants, first_plant, n_models, mu, ctrl_joint, cj));      // the refusals of cclqr_linearize_plants
     bool same = mu == H.mu;
     for (int i = 0; same && i < mu; i++) same = cj[i] == H.cj[i];
@@ -1501,52 +1589,53 @@ static int policy_ctrl_check(const cclqr_mech* m, const cclqr_plants* plants, in
         return fail(CCLQR_EINVAL, "the controller holds " + std::to_string(*tables) + " tables: one shared by all models (1) or one per model (" + std::to_string(n_models) + ")");
     return CCLQR_OK;
 }
-// ... and the device sequence they share, inside the caller's WsScope: linearsystem at every setpoint on its plant (lqr.jl:63) into w, and the controller's gains
-// gathered into the models' body order, device to device, *dK [tables][nK][mu][12 nb], *k_stride doubles apart (0: one table)
-static int policy_models_and_gains(const cclqr_mech* m, const cclqr_plants* plants, int64_t first_plant, int32_t n_models, const double* zd, const double* Fd, int32_t mu,
-                                   const int32_t* ctrl_joint, const cclqr_ctrl* c, int64_t tables, LinWs& w, double** dK, long long* k_stride, const char* what) {
+// the controller's gains gathered into the models' body order on `stream`, device to device (they never visit the host), inside the caller's WsScope:
+// k.Kin [tables][nK][mu][12 nb].  Callers: policy_models_and_gains, tracking_value_on_plants
+static int gather_gains(const cclqr_mech* m, const cclqr_ctrl* c, int mu, int64_t tables, hipStream_t stream, GainTable& k, const char* what) {
     const CtrlDev& H = c->host;
-    const int nb = m->nb, mx = 12 * nb;
+    const long long rows_per_table = (long long)H.nK * mu, nrows = tables * rows_per_table;
+    double* dK = nullptr;
+    HIPTRY(what, ws_get((void**)&dK, (size_t)nrows * 12 * m->nb * sizeof(double)));
+    HIPTRY(what, launch_lds<false>(k_rows_to_body_order_kernel, dim3((unsigned)nrows), dim3(128), 0, stream, c->K_dev, nrows, rows_per_table, (long long)H.K_stride, m->nb,
+                                   m->dev, dK));
+    k = GainTable{dK, tables > 1 ? rows_per_table * 12 * m->nb : 0, H.nK};
+    return CCLQR_OK;
+}
+// ... and the device sequence the stationary ones share, their counterpart of raw_upload, inside the caller's WsScope: the tables of the value v under construction
+// allocated (they are d.P), linearsystem at every setpoint on its plant (lqr.jl:63), and gather_gains.  Callers: cclqr_value_create_policy,
+// cclqr_value_create_policy_doubling, cclqr_value_create_covariance_doubling
+static int policy_models_and_gains(const cclqr_mech* m, const cclqr_plants* plants, int64_t first_plant, int32_t n_models, const double* zd, const double* Fd, int32_t mu,
+                                   const int32_t* ctrl_joint, const cclqr_ctrl* c, int64_t tables, cclqr_value* v, AnaDev& d, const char* what) {
+    LinWs w = {};
+    HIPTRY(what, value_alloc(v));
     TRY(linearize_to_ws(m, plants, first_plant, n_models, zd, Fd, mu, ctrl_joint, w, what));
     long long bad = -1;
     HIPTRY(what, knots_converged(w.status, (size_t)n_models, &bad));
     if (bad >= 0) return fail(CCLQR_ENOCONV, "Newton did not converge at setpoint " + std::to_string(bad));
-    const long long rows_per_table = (long long)H.nK * mu, nrows = tables * rows_per_table;
-    HIPTRY(what, ws_get((void**)dK, (size_t)nrows * mx * sizeof(double)));
-    HIPTRY(what, launch_lds<false>(k_rows_to_body_order_kernel, dim3((unsigned)nrows), dim3(128), 0, nullptr, c->K_dev, nrows, rows_per_table, (long long)H.K_stride, nb,
-                                   m->dev, *dK));
-    *k_stride = tables > 1 ? rows_per_table * mx : 0;
-    return CCLQR_OK;
+    d.m = RicModels{w.A, w.Bu, w.Bl, w.G};
+    d.P = v->P_dev;
+    return gather_gains(m, c, mu, tables, nullptr, d.k, what);
 }
 
 extern "C" int cclqr_value_create_policy(const cclqr_mech* m, const cclqr_plants* plants, int64_t first_plant, int32_t n_models, const double* zd, int32_t mu,
                                          const int32_t* ctrl_joint, const double* Fd, const cclqr_ctrl* c, int32_t n_weights, const double* Q, const double* R,
                                          int32_t N, double tol, int32_t* kbreak, double* dnorm, cclqr_value** out) {
-    static const char* const what = "policy evaluation";
     if (!m || !zd || !c || !Q || !out || (mu > 0 && (!ctrl_joint || !R))) return fail(CCLQR_EINVAL, "null argument");
     int cj[CCLQR_MAXL];
     int64_t tables = 1;
-    TRY(policy_ctrl_check(m, plants, first_plant, n_models, mu, ctrl_joint, c, n_models < 1 || N < 1 || mu < 1 || mu > m->nb, cj, &tables));
+    TRY(policy_ctrl_check(m, plants, first_plant, n_models, mu, ctrl_joint, c, "policy evaluation", n_models < 1 || N < 1 || mu < 1 || mu > m->nb, true, cj, &tables));
     const CtrlDev& H = c->host;
     if (H.nK > 1 && N != H.nK + 1)
         return fail(CCLQR_EINVAL, "the controller's tables hold " + std::to_string(H.nK) + " rows, one per backward step: N must be " + std::to_string(H.nK + 1) + " (got " + std::to_string(N) + ")");
     TRY(policy_check(n_models, mu, N, H.nK, n_weights, "model"));
-    const int nb = m->nb, mx = 12 * nb, ml = 5 * nb;
     ValueOwner vown(value_new(m, n_models));
-    HIPTRY(what, value_alloc(vown.p));
     WsScope scope;
-    LinWs w = {};
-    double* dK = nullptr;
-    long long k_stride = 0;
-    TRY(policy_models_and_gains(m, plants, first_plant, n_models, zd, Fd, mu, ctrl_joint, c, tables, w, &dK, &k_stride, what));
+    AnaDev d;
+    TRY(policy_models_and_gains(m, plants, first_plant, n_models, zd, Fd, mu, ctrl_joint, c, tables, vown.p, d, "policy evaluation"));
     std::vector<int> kb, st;
     std::vector<double> dn;
-    TRY(run_policy(n_models, mx, mu, ml, N, tol, w.A, w.Bu, w.Bl, w.G, dK, k_stride, H.nK, n_weights, Q, R, 0, vown.p->P_dev, kb, st, dn));
-    for (int p = 0; p < n_models; p++) {
-        if (kbreak) kbreak[p] = kb[p];
-        if (dnorm) { dnorm[2 * p] = dn[2 * (size_t)p]; dnorm[2 * p + 1] = dn[2 * (size_t)p + 1]; }
-        if (st[p] != 0) return fail(CCLQR_ESINGULAR, "G*Bl is singular in model " + std::to_string(p));
-    }
+    TRY(run_policy(n_models, 12 * m->nb, mu, 5 * m->nb, N, tol, d, n_weights, Q, R, 0, kb, st, dn));
+    TRY(policy_report(kb, st, dn, n_models, kbreak, dnorm, "model"));
     *out = vown.release();
     return CCLQR_OK;
 }
@@ -1557,22 +1646,20 @@ static int doubling_check(int nprob, int N, double tol, int max_levels, int n_we
     if (N < 0) return fail(CCLQR_EINVAL, "N = " + std::to_string(N) + ": a horizon of N >= 1 knots, or 0 = to convergence");
     if (N == 0 && (max_levels < 1 || max_levels > 60)) return fail(CCLQR_EINVAL, "max_levels = " + std::to_string(max_levels) + ": 1 .. 60 (2^max_levels steps)");
     if (!(tol >= 0.0)) return fail(CCLQR_EINVAL, "tol is negative or not a number");
-    const int path = opts ? opts->path : 0;
-    if (path < 0 || path > 2) return fail(CCLQR_EINVAL, "policy evaluation options: path in 0..2");
-    if (opts && opts->bf16_terms != 0) return fail(CCLQR_EINVAL, "policy evaluation runs in fp64 only (bf16_terms = 0)");
+    TRY(check_fp64_path(opts, "policy evaluation", ""));
     return check_n_weights(n_weights, nprob, of);
 }
 // the host results of run_doubling and run_covariance
 struct DblOut { std::vector<int> lv, rs, st; std::vector<double> dn, gn; };
 // what the two runs share before their launch, inside the caller's WsScope: the sizes, the models and gains, the two workspaces (work2_doubles: the launch's own
 // count, from the sizes set here) and the device diagnostics of a DblArgs; Q, R and P_out are the caller's to set
-static int doubling_args(DblArgs& a, int nprob, int mx, int mu, int ml, int N, double tol, int max_levels, const double* dA, const double* dBu, const double* dBl,
-                         const double* dG, const double* dK, long long k_stride, int path, size_t (*work2_doubles)(const RicArgs&), const char* what) {
+static int doubling_args(DblArgs& a, int nprob, int mx, int mu, int ml, int N, double tol, int max_levels, const AnaDev& d, int path,
+                         size_t (*work2_doubles)(const RicArgs&), const char* what) {
     double *dwork = nullptr, *dwork2 = nullptr, *ddn = nullptr, *dgn = nullptr;
     int *dlv = nullptr, *drs = nullptr, *dst = nullptr, *dstop = nullptr;
     const size_t np = (size_t)nprob;
     RicArgs& r = a.r;
-    r.nprob = nprob; r.mx = mx; r.mu = mu; r.ml = ml; r.N = N; r.time_varying = 0; r.tol = tol; r.path = path; r.bf16_terms = 0; r.keep_last = 0; r.K = nullptr;
+    ric_sizes(r, nprob, mx, mu, ml, N, 0, tol, path);
     HIPTRY(what, ws_get((void**)&dwork, ric_total_work_doubles(r) * sizeof(double)));
     HIPTRY(what, ws_get((void**)&dwork2, work2_doubles(r) * sizeof(double)));
     HIPTRY(what, ws_get((void**)&ddn, 2 * np * sizeof(double)));
@@ -1581,53 +1668,40 @@ static int doubling_args(DblArgs& a, int nprob, int mx, int mu, int ml, int N, d
     HIPTRY(what, ws_get((void**)&dlv, np * sizeof(int)));
     HIPTRY(what, ws_get((void**)&drs, np * sizeof(int)));
     HIPTRY(what, ws_get((void**)&dst, np * sizeof(int)));
-    r.stop = dstop; r.A = dA; r.Bu = dBu; r.Bl = dBl; r.G = dG; r.kbreak = nullptr; r.status = dst; r.work = dwork;
-    a.Kin = dK; a.k_stride = k_stride; a.max_levels = max_levels; a.work2 = dwork2; a.levels = dlv; a.reason = drs; a.dnorm = ddn; a.gnorm = dgn;
+    r.stop = dstop; r.A = d.m.A; r.Bu = d.m.Bu; r.Bl = d.m.Bl; r.G = d.m.G; r.kbreak = nullptr; r.status = dst; r.work = dwork; r.P_out = d.P;
+    a.k = d.k; a.max_levels = max_levels; a.work2 = dwork2; a.levels = dlv; a.reason = drs; a.dnorm = ddn; a.gnorm = dgn;
     return CCLQR_OK;
 }
-// ... and after it: the launch's diagnostics onto the host
-static int doubling_read_back(const DblArgs& a, DblOut& o, const char* what) {
-    const size_t np = (size_t)a.r.nprob;
+// ... and after it: the device is waited for and the launch's diagnostics come onto the host (gnorm: the second pair of norms, RdbArgs' anorm).  Callers:
+// run_doubling, run_covariance, cclqr_riccati_doubling
+static int doubling_read_back(size_t np, const int* levels, const int* reason, const int* status, const double* dnorm, const double* gnorm, DblOut& o, const char* what) {
     HIPTRY(what, hipDeviceSynchronize());
-    o.lv.resize(np); o.rs.resize(np); o.st.resize(np); o.dn.resize(2 * np); o.gn.resize(2 * np);
-    HIPTRY(what, hipMemcpy(o.lv.data(), a.levels, np * sizeof(int), hipMemcpyDeviceToHost));
-    HIPTRY(what, hipMemcpy(o.rs.data(), a.reason, np * sizeof(int), hipMemcpyDeviceToHost));
-    HIPTRY(what, hipMemcpy(o.st.data(), a.r.status, np * sizeof(int), hipMemcpyDeviceToHost));
-    HIPTRY(what, hipMemcpy(o.dn.data(), a.dnorm, 2 * np * sizeof(double), hipMemcpyDeviceToHost));
-    HIPTRY(what, hipMemcpy(o.gn.data(), a.gnorm, 2 * np * sizeof(double), hipMemcpyDeviceToHost));
-    return CCLQR_OK;
-}
-// host weights [n_weights][mx][mx], [n_weights][mu][mu] onto the device, inside the caller's WsScope
-static int upload_weights(int mx, int mu, int n_weights, const double* Q, const double* R, double** dQ, double** dR, const char* what) {
-    const size_t nw = (size_t)n_weights;
-    HIPTRY(what, ws_get((void**)dQ, nw * mx * mx * sizeof(double)));
-    HIPTRY(what, ws_get((void**)dR, (nw * mu * mu + 1) * sizeof(double)));
-    HIPTRY(what, hipMemcpy(*dQ, Q, nw * mx * mx * sizeof(double), hipMemcpyHostToDevice));
-    if (mu > 0) HIPTRY(what, hipMemcpy(*dR, R, nw * mu * mu * sizeof(double), hipMemcpyHostToDevice));
-    return CCLQR_OK;
+    TRY(download(o.lv, levels, np, what));
+    TRY(download(o.rs, reason, np, what));
+    TRY(download(o.st, status, np, what));
+    TRY(download(o.dn, dnorm, 2 * np, what));
+    return download(o.gn, gnorm, 2 * np, what);
 }
 // shared tail of the two entry points, as run_policy is: the evaluation on device-resident models and gains, inside the caller's WsScope
-static int run_doubling(int nprob, int mx, int mu, int ml, int N, double tol, int max_levels, const double* dA, const double* dBu, const double* dBl, const double* dG,
-                        const double* dK, long long k_stride, int n_weights, const double* Q, const double* R, int path, double* dP, DblOut& o) {
+static int run_doubling(int nprob, int mx, int mu, int ml, int N, double tol, int max_levels, const AnaDev& d, int n_weights, const double* Q, const double* R, int path,
+                        DblOut& o) {
     static const char* const what = "policy evaluation by doubling";
-    double *dQ = nullptr, *dR = nullptr;
     DblArgs a;
-    TRY(doubling_args(a, nprob, mx, mu, ml, N, tol, max_levels, dA, dBu, dBl, dG, dK, k_stride, path, dbl_work_doubles, what));
-    TRY(upload_weights(mx, mu, n_weights, Q, R, &dQ, &dR, what));
-    RicArgs& r = a.r;
-    if (n_weights > 1) { r.q_stride = (long long)mx * mx; r.r_stride = (long long)mu * mu; }
-    r.Q = dQ; r.R = dR; r.P_out = dP;
+    WeightsIn w;
+    TRY(doubling_args(a, nprob, mx, mu, ml, N, tol, max_levels, d, path, dbl_work_doubles, what));
+    TRY(upload_weights(mx, mu, n_weights, Q, R, w, what));
+    ric_weights(a.r, w);
     HIPTRY(what, launch_policy_doubling(a, nullptr));
-    return doubling_read_back(a, o, what);
+    return doubling_read_back((size_t)nprob, a.levels, a.reason, a.r.status, a.dnorm, a.gnorm, o, what);
 }
-// the diagnostics of run_doubling into the caller's arrays (each may be null), up to the problem the call is refused for
+// the diagnostics of a DblOut into the caller's arrays (each may be null), up to the problem the call is refused for.  Callers: the five doubling entry points
 static int doubling_report(const DblOut& o, int nprob, int32_t* levels, int32_t* reason, double* dnorm, double* gnorm, const char* of) {
     for (int p = 0; p < nprob; p++) {
         if (levels) levels[p] = o.lv[p];
         if (reason) reason[p] = o.rs[p];
-        if (dnorm) { dnorm[2 * p] = o.dn[2 * (size_t)p]; dnorm[2 * p + 1] = o.dn[2 * (size_t)p + 1]; }
-        if (gnorm) { gnorm[2 * p] = o.gn[2 * (size_t)p]; gnorm[2 * p + 1] = o.gn[2 * (size_t)p + 1]; }
-        if (o.st[p] != 0) return fail(CCLQR_ESINGULAR, std::string("G*Bl is singular in ") + of + " " + std::to_string(p));
+        put_pair(dnorm, o.dn, p);
+        put_pair(gnorm, o.gn, p);
+        if (o.st[p] != 0) return singular_in(of, p);
     }
     return CCLQR_OK;
 }
@@ -1638,20 +1712,14 @@ extern "C" int cclqr_policy_value_doubling(int32_t nprob, int32_t mx, int32_t mu
     static const char* const what = "policy evaluation by doubling";
     if (!A || !Q || !P || (mu > 0 && (!Bu || !R || !K)) || (ml > 0 && (!Bl || !G))) return fail(CCLQR_EINVAL, "null argument");
     if (nprob < 1 || mx < 1 || mu < 0 || ml < 0) return fail(CCLQR_EINVAL, "bad sizes");
-    if (n_gains != 1 && n_gains != nprob)
-        return fail(CCLQR_EINVAL, "n_gains = " + std::to_string(n_gains) + ": one gain shared by all (1) or one per problem (" + std::to_string(nprob) + ")");
+    TRY(check_n_gains(n_gains, nprob, false, "problem"));
     TRY(doubling_check(nprob, N, tol, max_levels, n_weights, opts, "problem"));
     WsScope scope;
-    RicModels d = {};
-    TRY(upload_models((size_t)nprob, mx, mu, ml, A, Bu, Bl, G, d));
-    const size_t nKd = (size_t)n_gains * mu * mx, nP = (size_t)nprob * mx * mx;
-    double *dK = nullptr, *dP = nullptr;
-    HIPTRY(what, ws_get((void**)&dK, (nKd + 1) * sizeof(double)));
-    HIPTRY(what, ws_get((void**)&dP, nP * sizeof(double)));
-    if (nKd) HIPTRY(what, hipMemcpy(dK, K, nKd * sizeof(double), hipMemcpyHostToDevice));
+    AnaDev d;
+    TRY(raw_upload(what, nprob, mx, mu, ml, 1, A, Bu, Bl, G, n_gains, 1, true, K, d));
     DblOut o;
-    TRY(run_doubling(nprob, mx, mu, ml, N, tol, max_levels, d.A, d.Bu, d.Bl, d.G, dK, n_gains > 1 ? (long long)mu * mx : 0, n_weights, Q, R, opts ? opts->path : 0, dP, o));
-    HIPTRY(what, hipMemcpy(P, dP, nP * sizeof(double), hipMemcpyDeviceToHost));
+    TRY(run_doubling(nprob, mx, mu, ml, N, tol, max_levels, d, n_weights, Q, R, opts ? opts->path : 0, o));
+    HIPTRY(what, hipMemcpy(P, d.P, (size_t)nprob * mx * mx * sizeof(double), hipMemcpyDeviceToHost));
     return doubling_report(o, nprob, levels, reason, dnorm, gnorm, "problem");
 }
 
@@ -1659,24 +1727,19 @@ extern "C" int cclqr_value_create_policy_doubling(const cclqr_mech* m, const ccl
                                                   const int32_t* ctrl_joint, const double* Fd, const cclqr_ctrl* c, int32_t n_weights, const double* Q, const double* R,
                                                   int32_t N, double tol, int32_t max_levels, int32_t* levels, int32_t* reason, double* dnorm, double* gnorm,
                                                   cclqr_value** out) {
-    static const char* const what = "policy evaluation by doubling";
     if (!m || !zd || !c || !Q || !out || (mu > 0 && (!ctrl_joint || !R))) return fail(CCLQR_EINVAL, "null argument");
     int cj[CCLQR_MAXL];
     int64_t tables = 1;
-    TRY(policy_ctrl_check(m, plants, first_plant, n_models, mu, ctrl_joint, c, n_models < 1 || mu < 1 || mu > m->nb, cj, &tables));
+    TRY(policy_ctrl_check(m, plants, first_plant, n_models, mu, ctrl_joint, c, "policy evaluation", n_models < 1 || mu < 1 || mu > m->nb, true, cj, &tables));
     if (c->host.nK != 1)
         return fail(CCLQR_EINVAL, "the controller's tables hold " + std::to_string(c->host.nK) + " gain rows: doubling evaluates ONE stationary gain (a finite-horizon table is what cclqr_value_create_policy steps through)");
     TRY(doubling_check(n_models, N, tol, max_levels, n_weights, nullptr, "model"));
-    const int nb = m->nb, mx = 12 * nb, ml = 5 * nb;
     ValueOwner vown(value_new(m, n_models));
-    HIPTRY(what, value_alloc(vown.p));
     WsScope scope;
-    LinWs w = {};
-    double* dK = nullptr;
-    long long k_stride = 0;
-    TRY(policy_models_and_gains(m, plants, first_plant, n_models, zd, Fd, mu, ctrl_joint, c, tables, w, &dK, &k_stride, what));
+    AnaDev d;
+    TRY(policy_models_and_gains(m, plants, first_plant, n_models, zd, Fd, mu, ctrl_joint, c, tables, vown.p, d, "policy evaluation by doubling"));
     DblOut o;
-    TRY(run_doubling(n_models, mx, mu, ml, N, tol, max_levels, w.A, w.Bu, w.Bl, w.G, dK, k_stride, n_weights, Q, R, 0, vown.p->P_dev, o));
+    TRY(run_doubling(n_models, 12 * m->nb, mu, 5 * m->nb, N, tol, max_levels, d, n_weights, Q, R, 0, o));
     TRY(doubling_report(o, n_models, levels, reason, dnorm, gnorm, "model"));
     *out = vown.release();
     return CCLQR_OK;
@@ -1687,8 +1750,7 @@ extern "C" int cclqr_value_create_policy_doubling(const cclqr_mech* m, const ccl
 // what both entry points refuse about the noise and the moments, after doubling_check and before anything is allocated or launched
 static int covariance_check(int nprob, int mu, int N, int n_noise, const double* Wu, const double* Sigma0, const double* Q, const double* R, const double* cost,
                             const char* of) {
-    if (n_noise != 1 && n_noise != nprob)
-        return fail(CCLQR_EINVAL, "n_noise = " + std::to_string(n_noise) + ": Wu / Sigma0 are one shared by all (1) or one per " + of + " (" + std::to_string(nprob) + ")");
+    TRY(check_n_noise(n_noise, nprob, "Wu / Sigma0 are", of));
     if (!Wu && !Sigma0) return fail(CCLQR_EINVAL, "Wu and Sigma0 are both null: there is no covariance to propagate");
     if (Wu && mu == 0) return fail(CCLQR_EINVAL, "Wu is given with mu = 0: there is no input for the noise to enter through");
     if (cost && (!Q || (mu > 0 && !R))) return fail(CCLQR_EINVAL, "cost is asked for without Q / R");
@@ -1697,46 +1759,32 @@ static int covariance_check(int nprob, int mu, int N, int n_noise, const double*
 }
 // the host moments of run_covariance; each is filled only if asked for
 struct CovOut { std::vector<double> cost, zstd, ustd; };
-// shared tail of the two entry points, run_doubling's shape: the covariance on device-resident models and gains, inside the caller's WsScope.  dSigma: device
-// [nprob][mx][mx], written by the kernels.  Wu, Sigma0, Q, R: HOST, as the entry points take them
-static int run_covariance(int nprob, int mx, int mu, int ml, int N, double tol, int max_levels, const double* dA, const double* dBu, const double* dBl, const double* dG,
-                          const double* dK, long long k_stride, int n_weights, const double* Q, const double* R, int n_noise, const double* Wu, const double* Sigma0,
-                          int path, double* dSigma, bool want_cost, bool want_zstd, bool want_ustd, DblOut& o, CovOut& m) {
+// shared tail of the two entry points, run_doubling's shape: the covariance on device-resident models and gains, inside the caller's WsScope; d.P receives Σ.  Wu,
+// Sigma0, Q, R: HOST, as the entry points take them
+static int run_covariance(int nprob, int mx, int mu, int ml, int N, double tol, int max_levels, const AnaDev& d, int n_weights, const double* Q, const double* R,
+                          int n_noise, const double* Wu, const double* Sigma0, int path, bool want_cost, bool want_zstd, bool want_ustd, DblOut& o, CovOut& m) {
     static const char* const what = "covariance by doubling";
-    const size_t np = (size_t)nprob, nn = (size_t)n_noise, mm = (size_t)mx * mx, uu = (size_t)mu * mu;
+    const size_t np = (size_t)nprob;
     CovArgs c{};
-    TRY(doubling_args(c.d, nprob, mx, mu, ml, N, tol, max_levels, dA, dBu, dBl, dG, dK, k_stride, path, cov_work_doubles, what));
-    c.d.r.P_out = dSigma;
-    double *dQ = nullptr, *dR = nullptr, *dWu = nullptr, *dS0 = nullptr, *dcost = nullptr, *dz = nullptr, *du = nullptr;
+    TRY(doubling_args(c.d, nprob, mx, mu, ml, N, tol, max_levels, d, path, cov_work_doubles, what));
     if (want_cost) {
-        TRY(upload_weights(mx, mu, n_weights, Q, R, &dQ, &dR, what));
-        HIPTRY(what, ws_get((void**)&dcost, 2 * np * sizeof(double)));
-        c.Q = dQ; c.R = dR; c.cost = dcost;
-        if (n_weights > 1) { c.q_stride = (long long)mm; c.r_stride = (long long)uu; }
+        TRY(upload_weights(mx, mu, n_weights, Q, R, c.w, what));
+        HIPTRY(what, ws_get((void**)&c.cost, 2 * np * sizeof(double)));
     }
-    if (Wu) {
-        HIPTRY(what, ws_get((void**)&dWu, nn * uu * sizeof(double)));
-        HIPTRY(what, hipMemcpy(dWu, Wu, nn * uu * sizeof(double), hipMemcpyHostToDevice));
-        c.Wu = dWu; c.wu_stride = n_noise > 1 ? (long long)uu : 0;
-    }
-    if (Sigma0) {
-        HIPTRY(what, ws_get((void**)&dS0, nn * mm * sizeof(double)));
-        HIPTRY(what, hipMemcpy(dS0, Sigma0, nn * mm * sizeof(double), hipMemcpyHostToDevice));
-        c.Sigma0 = dS0; c.s0_stride = n_noise > 1 ? (long long)mm : 0;
-    }
-    if (want_zstd) { HIPTRY(what, ws_get((void**)&dz, np * mx * sizeof(double))); c.zstd = dz; }
-    if (want_ustd) { HIPTRY(what, ws_get((void**)&du, (np * mu + 1) * sizeof(double))); c.ustd = du; }
+    TRY(upload_noise(mx, mu, n_noise, Wu, Sigma0, c.n, what));
+    if (want_zstd) HIPTRY(what, ws_get((void**)&c.zstd, np * mx * sizeof(double)));
+    if (want_ustd) HIPTRY(what, ws_get((void**)&c.ustd, (np * mu + 1) * sizeof(double)));
     HIPTRY(what, launch_covariance_doubling(c, nullptr));
-    TRY(doubling_read_back(c.d, o, what));
-    if (want_cost) { m.cost.resize(2 * np); HIPTRY(what, hipMemcpy(m.cost.data(), dcost, 2 * np * sizeof(double), hipMemcpyDeviceToHost)); }
-    if (want_zstd) { m.zstd.resize(np * mx); HIPTRY(what, hipMemcpy(m.zstd.data(), dz, np * mx * sizeof(double), hipMemcpyDeviceToHost)); }
-    if (want_ustd && mu > 0) { m.ustd.resize(np * mu); HIPTRY(what, hipMemcpy(m.ustd.data(), du, np * mu * sizeof(double), hipMemcpyDeviceToHost)); }
+    TRY(doubling_read_back(np, c.d.levels, c.d.reason, c.d.r.status, c.d.dnorm, c.d.gnorm, o, what));
+    if (want_cost) TRY(download(m.cost, c.cost, 2 * np, what));
+    if (want_zstd) TRY(download(m.zstd, c.zstd, np * mx, what));
+    if (want_ustd && mu > 0) TRY(download(m.ustd, c.ustd, np * mu, what));
     return CCLQR_OK;
 }
 // the moments of run_covariance into the caller's arrays (each may be null), for the problems before the one the call is refused for (doubling_report names it)
 static void covariance_report(const DblOut& o, const CovOut& m, int nprob, int mx, int mu, double* cost, double* zstd, double* ustd) {
     for (int p = 0; p < nprob && o.st[p] == 0; p++) {
-        if (cost) { cost[2 * p] = m.cost[2 * (size_t)p]; cost[2 * p + 1] = m.cost[2 * (size_t)p + 1]; }
+        put_pair(cost, m.cost, p);
         if (zstd) memcpy(zstd + (size_t)p * mx, m.zstd.data() + (size_t)p * mx, (size_t)mx * sizeof(double));
         if (ustd && mu > 0) memcpy(ustd + (size_t)p * mu, m.ustd.data() + (size_t)p * mu, (size_t)mu * sizeof(double));
     }
@@ -1749,23 +1797,17 @@ extern "C" int cclqr_covariance_doubling(int32_t nprob, int32_t mx, int32_t mu, 
     static const char* const what = "covariance by doubling";
     if (!A || !Sigma || (mu > 0 && (!Bu || !K)) || (ml > 0 && (!Bl || !G))) return fail(CCLQR_EINVAL, "null argument");
     if (nprob < 1 || mx < 1 || mu < 0 || ml < 0) return fail(CCLQR_EINVAL, "bad sizes");
-    if (n_gains != 1 && n_gains != nprob)
-        return fail(CCLQR_EINVAL, "n_gains = " + std::to_string(n_gains) + ": one gain shared by all (1) or one per problem (" + std::to_string(nprob) + ")");
+    TRY(check_n_gains(n_gains, nprob, false, "problem"));
     TRY(doubling_check(nprob, N, tol, max_levels, n_weights, opts, "problem"));
     TRY(covariance_check(nprob, mu, N, n_noise, Wu, Sigma0, Q, R, cost, "problem"));
     WsScope scope;
-    RicModels d = {};
-    TRY(upload_models((size_t)nprob, mx, mu, ml, A, Bu, Bl, G, d));
-    const size_t nKd = (size_t)n_gains * mu * mx, nP = (size_t)nprob * mx * mx;
-    double *dK = nullptr, *dP = nullptr;
-    HIPTRY(what, ws_get((void**)&dK, (nKd + 1) * sizeof(double)));
-    HIPTRY(what, ws_get((void**)&dP, nP * sizeof(double)));
-    if (nKd) HIPTRY(what, hipMemcpy(dK, K, nKd * sizeof(double), hipMemcpyHostToDevice));
+    AnaDev d;
+    TRY(raw_upload(what, nprob, mx, mu, ml, 1, A, Bu, Bl, G, n_gains, 1, true, K, d));
     DblOut o;
     CovOut mo;
-    TRY(run_covariance(nprob, mx, mu, ml, N, tol, max_levels, d.A, d.Bu, d.Bl, d.G, dK, n_gains > 1 ? (long long)mu * mx : 0, n_weights, Q, R, n_noise, Wu, Sigma0,
-                       opts ? opts->path : 0, dP, cost != nullptr, zstd != nullptr, ustd != nullptr, o, mo));
-    HIPTRY(what, hipMemcpy(Sigma, dP, nP * sizeof(double), hipMemcpyDeviceToHost));
+    TRY(run_covariance(nprob, mx, mu, ml, N, tol, max_levels, d, n_weights, Q, R, n_noise, Wu, Sigma0, opts ? opts->path : 0, cost != nullptr, zstd != nullptr,
+                       ustd != nullptr, o, mo));
+    HIPTRY(what, hipMemcpy(Sigma, d.P, (size_t)nprob * mx * mx * sizeof(double), hipMemcpyDeviceToHost));
     covariance_report(o, mo, nprob, mx, mu, cost, zstd, ustd);
     return doubling_report(o, nprob, levels, reason, dnorm, gnorm, "problem");
 }
@@ -1774,138 +1816,163 @@ extern "C" int cclqr_value_create_covariance_doubling(const cclqr_mech* m, const
                                                       const int32_t* ctrl_joint, const double* Fd, const cclqr_ctrl* c, int32_t n_weights, const double* Q, const double* R,
                                                       int32_t n_noise, const double* Wu, const double* Sigma0, int32_t N, double tol, int32_t max_levels, double* cost,
                                                       double* zstd, double* ustd, int32_t* levels, int32_t* reason, double* dnorm, double* gnorm, cclqr_value** out) {
-    static const char* const what = "covariance by doubling";
     if (!m || !zd || !c || !out || (mu > 0 && !ctrl_joint)) return fail(CCLQR_EINVAL, "null argument");
     int cj[CCLQR_MAXL];
     int64_t tables = 1;
-    TRY(policy_ctrl_check(m, plants, first_plant, n_models, mu, ctrl_joint, c, n_models < 1 || mu < 1 || mu > m->nb, cj, &tables));
+    TRY(policy_ctrl_check(m, plants, first_plant, n_models, mu, ctrl_joint, c, "policy evaluation", n_models < 1 || mu < 1 || mu > m->nb, true, cj, &tables));
     if (c->host.nK != 1)
         return fail(CCLQR_EINVAL, "the controller's tables hold " + std::to_string(c->host.nK) + " gain rows: the covariance by doubling is that of ONE stationary gain");
     TRY(doubling_check(n_models, N, tol, max_levels, n_weights, nullptr, "model"));
     TRY(covariance_check(n_models, mu, N, n_noise, Wu, Sigma0, Q, R, cost, "model"));
-    const int nb = m->nb, mx = 12 * nb, ml = 5 * nb;
+    const int mx = 12 * m->nb;
     ValueOwner vown(value_new(m, n_models));
-    HIPTRY(what, value_alloc(vown.p));
     WsScope scope;
-    LinWs w = {};
-    double* dK = nullptr;
-    long long k_stride = 0;
-    TRY(policy_models_and_gains(m, plants, first_plant, n_models, zd, Fd, mu, ctrl_joint, c, tables, w, &dK, &k_stride, what));
+    AnaDev d;
+    TRY(policy_models_and_gains(m, plants, first_plant, n_models, zd, Fd, mu, ctrl_joint, c, tables, vown.p, d, "covariance by doubling"));
     DblOut o;
     CovOut mo;
-    TRY(run_covariance(n_models, mx, mu, ml, N, tol, max_levels, w.A, w.Bu, w.Bl, w.G, dK, k_stride, n_weights, Q, R, n_noise, Wu, Sigma0, 0, vown.p->P_dev,
-                       cost != nullptr, zstd != nullptr, ustd != nullptr, o, mo));
+    TRY(run_covariance(n_models, mx, mu, 5 * m->nb, N, tol, max_levels, d, n_weights, Q, R, n_noise, Wu, Sigma0, 0, cost != nullptr, zstd != nullptr, ustd != nullptr, o, mo));
     covariance_report(o, mo, n_models, mx, mu, cost, zstd, ustd);
     TRY(doubling_report(o, n_models, levels, reason, dnorm, gnorm, "model"));
     *out = vown.release();
     return CCLQR_OK;
 }
 
-// ---- the state covariance of a tracked run, knot by knot (covariance_tracking.hip): Σ_{j+1} = Abar_j Σ_j Abar_j' + D_j Wu D_j' with the gain row and the model
-// of knot j (lqr_tracking.jl:63-65, 88-89, 107), the noise law of trackingLQR_triple_cartpole.jl:98
-// what the entry refuses about its counts and its noise, before anything is allocated or launched
-static int tracking_cov_check(int nprob, int mu, int N, int nlin, int n_gains, int nK, int n_weights, int n_noise, const double* Wu, const double* Sigma0, const double* Q,
-                              const double* R, bool want_cost, const cclqr_riccati_opts* opts, const char* of) {
+// ---- the two knot-by-knot analyses of a tracked run, one family: the state covariance (covariance_tracking.hip, Σ_{j+1} = Abar_j Σ_j Abar_j' + D_j Wu D_j') and its
+// adjoint, the cost-to-go (policy_tracking.hip, P_j = Q + K_j' R K_j + Abar_j' P_{j+1} Abar_j), each with the gain row and the model of knot j (lqr_tracking.jl:63-65,
+// 88-89, 107-108) and the noise law of trackingLQR_triple_cartpole.jl:98.  What the two do alike is done once, here, on the fields their records share (the Riccati
+// record, the gain table, the noise, status and knot); each keeps short functions for its own outputs below
+// what both refuse first about their counts, in this order.  Callers: tracking_cov_check, tracking_pol_check
+static int tracking_counts_check(int nprob, int mu, int N, int nlin, int n_gains, int nK, const char* of) {
     if (N > 1 && nlin != 1 && nlin != N - 1)
         return fail(CCLQR_EINVAL, "nlin = " + std::to_string(nlin) + ": one time-invariant model (1) or one per knot 0 .. N-2 (" + std::to_string(N - 1) + ")");
-    if (n_gains != 1 && n_gains != nprob)
-        return fail(CCLQR_EINVAL, "n_gains = " + std::to_string(n_gains) + ": the gains are one table shared by all (1) or one table per " + of + " (" + std::to_string(nprob) + ")");
+    TRY(check_n_gains(n_gains, nprob, true, of));
     if (N > 1 && mu > 0 && nK != 1 && nK != N - 1)
         return fail(CCLQR_EINVAL, "nK = " + std::to_string(nK) + ": a gain table holds one row (a stationary gain) or N - 1 = " + std::to_string(N - 1) + " rows, one per knot 0 .. N-2");
+    return CCLQR_OK;
+}
+// ... and last about the launch; what = the analysis' name.  Callers: tracking_cov_check, tracking_pol_check
+static int tracking_launch_check(int nprob, const cclqr_riccati_opts* opts, const char* what) {
+    if (nprob > 65535) return fail(CCLQR_EINVAL, "nprob = " + std::to_string(nprob) + ": at most 65535 problems per call (they are the y extent of the launch grids)");
+    return check_fp64_path(opts, what, "the ");
+}
+// what a tracking call brings back to the host: the per-knot records (moments / prices), the totals, and of every problem its status and the knot it names
+struct TrackOut { std::vector<double> rec, total; std::vector<int> st, knot; };
+// the shared part of a setup, inside the caller's WsScope: the sizes of a launch of `chunk` problems, the noise (HOST, as the entries take it), the workspace of one
+// launch, status and knot of ALL nprob problems.  Callers: ctk_setup, ptk_setup
+static int tracking_setup(RicArgs& r, NoiseIn& n, int nprob, int chunk, int mx, int mu, int ml, int N, int nlin, int n_noise, const double* Wu, const double* Sigma0, int path,
+                          const char* what) {
+    const size_t np = (size_t)nprob;
+    double* dwork = nullptr;
+    int *dst = nullptr, *dkn = nullptr;
+    ric_sizes(r, chunk, mx, mu, ml, N, (N > 1 && nlin > 1) ? 1 : 0, 0.0, path);
+    TRY(upload_noise(mx, mu, n_noise, Wu, Sigma0, n, what));
+    HIPTRY(what, ws_get((void**)&dwork, ric_total_work_doubles(r) * sizeof(double)));
+    HIPTRY(what, ws_get((void**)&dst, np * sizeof(int)));
+    HIPTRY(what, ws_get((void**)&dkn, np * sizeof(int)));
+    r.work = dwork; r.status = dst; r.kbreak = dkn;
+    return CCLQR_OK;
+}
+// the shared part of a chunk's launch record, from the call's (problem 0 onwards) to that of the problems c0 .. c0 + nc - 1: their models (nlin per problem) lie at md,
+// their gains in `tables` (the tables of ALL problems).  Callers: ctk_launch_chunk, ptk_launch_chunk
+static void tracking_chunk(RicArgs& r, GainTable& k, NoiseIn& n, size_t c0, size_t nc, const RicModels& md, const GainTable& tables) {
+    r.nprob = (int)nc; r.A = md.A; r.Bu = md.Bu; r.Bl = md.Bl; r.G = md.G;
+    r.status += c0; r.kbreak += c0;
+    k = tables; k.Kin += (long long)c0 * k.k_stride;
+    if (n.Wu) n.Wu += (long long)c0 * n.wu_stride;
+    if (n.Sigma0) n.Sigma0 += (long long)c0 * n.s0_stride;
+}
+// status and knot of every problem onto the host.  Callers: ctk_read_back, ptk_read_back
+static int tracking_read_back(const RicArgs& r, int nprob, TrackOut& o, const char* what) {
+    TRY(download(o.st, r.status, (size_t)nprob, what));
+    return download(o.knot, r.kbreak, (size_t)nprob, what);
+}
+// the body the two raw entries share around their own setup, launch and report.  First what they refuse about sizes and pointers ...
+static int tracking_raw_check(int nprob, int mx, int mu, int ml, int N, const double* A, const double* Bu, const double* Bl, const double* G, const double* K) {
+    if (nprob < 1 || mx < 1 || mu < 0 || ml < 0 || N < 1) return fail(CCLQR_EINVAL, "bad sizes");
+    if (N > 1 && (!A || (mu > 0 && (!Bu || !K)) || (ml > 0 && (!Bl || !G)))) return fail(CCLQR_EINVAL, "null argument");
+    return CCLQR_OK;
+}
+// ... then raw_upload for a horizon of N knots (N = 1: no model and no gain is read) and, if asked for, the [nprob][N][mx][mx] matrices of every knot ...
+static int tracking_raw_upload(const char* what, int nprob, int mx, int mu, int ml, int nlin, const double* A, const double* Bu, const double* Bl, const double* G, int n_gains,
+                               int nK, const double* K, int N, bool want_all, AnaDev& d, double** dAll) {
+    TRY(raw_upload(what, nprob, mx, mu, ml, N > 1 ? nlin : 0, A, Bu, Bl, G, n_gains, nK, N > 1, K, d));
+    if (want_all) HIPTRY(what, ws_get((void**)dAll, (size_t)nprob * mx * mx * N * sizeof(double)));
+    return CCLQR_OK;
+}
+// ... and after the read-back the matrices of the problems before the first one the call is refused for: the arrays are filled up to it
+static int tracking_raw_matrices(const TrackOut& o, int nprob, int mx, int N, double* out, const double* dP, double* out_all, const double* dAll, const char* what) {
+    int bad = nprob;
+    for (int p = nprob - 1; p >= 0; p--) if (o.st[p] != 0) bad = p;
+    if (out && bad > 0) HIPTRY(what, hipMemcpy(out, dP, (size_t)bad * mx * mx * sizeof(double), hipMemcpyDeviceToHost));
+    if (out_all && bad > 0) HIPTRY(what, hipMemcpy(out_all, dAll, (size_t)bad * N * mx * mx * sizeof(double), hipMemcpyDeviceToHost));
+    return CCLQR_OK;
+}
+
+// ---- the tracking covariance's own: what the entry refuses about its counts and its noise, before anything is allocated or launched
+static int tracking_cov_check(int nprob, int mu, int N, int nlin, int n_gains, int nK, int n_weights, int n_noise, const double* Wu, const double* Sigma0, const double* Q,
+                              const double* R, bool want_cost, const cclqr_riccati_opts* opts, const char* of) {
+    TRY(tracking_counts_check(nprob, mu, N, nlin, n_gains, nK, of));
     if (want_cost) TRY(check_n_weights(n_weights, nprob, of));
-    if (n_noise != 1 && n_noise != nprob)
-        return fail(CCLQR_EINVAL, "n_noise = " + std::to_string(n_noise) + ": Wu / Sigma0 are one shared by all (1) or one per " + of + " (" + std::to_string(nprob) + ")");
+    TRY(check_n_noise(n_noise, nprob, "Wu / Sigma0 are", of));
     if (!Wu && !Sigma0) return fail(CCLQR_EINVAL, "Wu and Sigma0 are both null: there is no covariance to propagate");
     if (Wu && mu == 0) return fail(CCLQR_EINVAL, "Wu is given with mu = 0: there is no input for the noise to enter through");
     if (want_cost && (!Q || (mu > 0 && !R))) return fail(CCLQR_EINVAL, "cost / total are asked for without Q / R");
-    if (nprob > 65535) return fail(CCLQR_EINVAL, "nprob = " + std::to_string(nprob) + ": at most 65535 problems per call (they are the y extent of the launch grids)");
-    const int path = opts ? opts->path : 0;
-    if (path < 0 || path > 2) return fail(CCLQR_EINVAL, "tracking covariance options: path in 0..2");
-    if (opts && opts->bf16_terms != 0) return fail(CCLQR_EINVAL, "the tracking covariance runs in fp64 only (bf16_terms = 0)");
-    return CCLQR_OK;
+    return tracking_launch_check(nprob, opts, "tracking covariance");
 }
-// what a tracking-covariance call brings back to the host
-struct CtkOut { std::vector<double> mom, total; std::vector<int> st, knot; };
-// fills d, inside the caller's WsScope, with the launch arguments of problem 0 onwards: weights, noise, records, totals and statuses of ALL nprob problems, the workspace
-// of `chunk` problems, the most one launch takes.  Q, R, Wu, Sigma0: HOST, as the entries take them (Q = null: no cost is asked for)
-static int ctk_setup(int nprob, int chunk, int mx, int mu, int ml, int N, int nlin, int nK, int n_weights, const double* Q, const double* R, int n_noise, const double* Wu,
-                     const double* Sigma0, int path, hipStream_t stream, CtkArgs& d) {
+// fills c, inside the caller's WsScope, with the launch arguments of problem 0 onwards: tracking_setup, and the weights, records and totals of ALL nprob problems.
+// Q, R: HOST (Q = null: no cost is asked for)
+static int ctk_setup(int nprob, int chunk, int mx, int mu, int ml, int N, int nlin, int n_weights, const double* Q, const double* R, int n_noise, const double* Wu,
+                     const double* Sigma0, int path, hipStream_t stream, CtkArgs& c) {
     static const char* const what = "tracking covariance";
-    const size_t np = (size_t)nprob, nn = (size_t)n_noise, mm = (size_t)mx * mx, uu = (size_t)mu * mu, rec = (size_t)ctk_record(mx, mu);
-    CtkArgs& c = d;
+    const size_t np = (size_t)nprob, mm = (size_t)mx * mx, uu = (size_t)mu * mu;
     c = CtkArgs{};
-    RicArgs& r = c.r;
-    r.nprob = chunk; r.mx = mx; r.mu = mu; r.ml = ml; r.N = N; r.time_varying = (N > 1 && nlin > 1) ? 1 : 0; r.tol = 0.0; r.path = path; r.bf16_terms = 0; r.keep_last = 0;
-    double *dQ = nullptr, *dR = nullptr, *dWu = nullptr, *dS0 = nullptr, *dwork = nullptr, *dmom = nullptr, *dtot = nullptr;
-    int *dst = nullptr, *dkn = nullptr;
     if (Q) {
-        TRY(upload_weights(mx, mu, n_weights, Q, R, &dQ, &dR, what));
-        if (n_weights > 1) { c.q_stride = (long long)mm; c.r_stride = (long long)uu; }
+        TRY(upload_weights(mx, mu, n_weights, Q, R, c.w, what));
     } else {      // no cost asked for: the kernels form it against zero weights, written on the stream the kernels run on
+        double *dQ = nullptr, *dR = nullptr;
         HIPTRY(what, ws_get((void**)&dQ, mm * sizeof(double)));
         HIPTRY(what, ws_get((void**)&dR, (uu + 1) * sizeof(double)));
         HIPTRY(what, hipMemsetAsync(dQ, 0, mm * sizeof(double), stream));
         HIPTRY(what, hipMemsetAsync(dR, 0, (uu + 1) * sizeof(double), stream));
+        c.w.Q = dQ; c.w.R = dR;
     }
-    if (Wu) {
-        HIPTRY(what, ws_get((void**)&dWu, nn * uu * sizeof(double)));
-        HIPTRY(what, hipMemcpy(dWu, Wu, nn * uu * sizeof(double), hipMemcpyHostToDevice));
-        c.wu_stride = n_noise > 1 ? (long long)uu : 0;
-    }
-    if (Sigma0) {
-        HIPTRY(what, ws_get((void**)&dS0, nn * mm * sizeof(double)));
-        HIPTRY(what, hipMemcpy(dS0, Sigma0, nn * mm * sizeof(double), hipMemcpyHostToDevice));
-        c.s0_stride = n_noise > 1 ? (long long)mm : 0;
-    }
-    HIPTRY(what, ws_get((void**)&dwork, ric_total_work_doubles(r) * sizeof(double)));
-    HIPTRY(what, ws_get((void**)&dmom, np * N * rec * sizeof(double)));
-    HIPTRY(what, ws_get((void**)&dtot, 2 * np * sizeof(double)));
-    HIPTRY(what, ws_get((void**)&dst, np * sizeof(int)));
-    HIPTRY(what, ws_get((void**)&dkn, np * sizeof(int)));
-    r.work = dwork; r.status = dst; r.kbreak = dkn;
-    c.nK = nK; c.Wu = dWu; c.Sigma0 = dS0; c.Q = dQ; c.R = dR; c.mom = dmom; c.total = dtot;
+    TRY(tracking_setup(c.r, c.n, nprob, chunk, mx, mu, ml, N, nlin, n_noise, Wu, Sigma0, path, what));
+    HIPTRY(what, ws_get((void**)&c.mom, np * N * (size_t)ctk_record(mx, mu) * sizeof(double)));
+    HIPTRY(what, ws_get((void**)&c.total, 2 * np * sizeof(double)));
     return CCLQR_OK;
 }
-// the recursion for the problems c0 .. c0 + nc - 1 on `stream`: their models (nlin per problem) lie at dA .. dG, their gains in dK (the tables of ALL problems, k_stride
-// doubles apart, 0 = one shared); dSigma [nprob][mx][mx] and dSigma_all [nprob][N][mx][mx] (or null) are the whole call's
-static hipError_t ctk_launch_chunk(const CtkArgs& d, size_t c0, size_t nc, const double* dA, const double* dBu, const double* dBl, const double* dG, const double* dK,
-                                   long long k_stride, double* dSigma, double* dSigma_all, hipStream_t stream) {
+// the recursion for the problems c0 .. c0 + nc - 1 on `stream` (tracking_chunk); dSigma [nprob][mx][mx] and dSigma_all [nprob][N][mx][mx] (or null) are the whole call's
+static hipError_t ctk_launch_chunk(const CtkArgs& d, size_t c0, size_t nc, const RicModels& md, const GainTable& tables, double* dSigma, double* dSigma_all, hipStream_t stream) {
     CtkArgs c = d;
     const size_t mm = (size_t)c.r.mx * c.r.mx, N = (size_t)c.r.N, rec = (size_t)ctk_record(c.r.mx, c.r.mu);
-    c.r.nprob = (int)nc; c.r.A = dA; c.r.Bu = dBu; c.r.Bl = dBl; c.r.G = dG;
-    c.r.status += c0; c.r.kbreak += c0;
-    c.Kin = dK + (long long)c0 * k_stride; c.k_stride = k_stride;
-    if (c.Wu) c.Wu += (long long)c0 * c.wu_stride;
-    if (c.Sigma0) c.Sigma0 += (long long)c0 * c.s0_stride;
-    c.Q += (long long)c0 * c.q_stride; c.R += (long long)c0 * c.r_stride;
+    tracking_chunk(c.r, c.k, c.n, c0, nc, md, tables);
+    c.w.Q += (long long)c0 * c.w.q_stride; c.w.R += (long long)c0 * c.w.r_stride;
     c.mom += c0 * N * rec; c.total += 2 * c0;
     c.Sigma = dSigma + c0 * mm;
     c.Sigma_all = dSigma_all ? dSigma_all + c0 * N * mm : nullptr;
     return launch_covariance_tracking(c, stream);
 }
-static int ctk_read_back(const CtkArgs& d, int nprob, CtkOut& o) {
+static int ctk_read_back(const CtkArgs& d, int nprob, TrackOut& o) {
     static const char* const what = "tracking covariance";
-    const size_t np = (size_t)nprob, len = np * (size_t)d.r.N * (size_t)ctk_record(d.r.mx, d.r.mu);
-    o.mom.resize(len); o.total.resize(2 * np); o.st.resize(np); o.knot.resize(np);
-    HIPTRY(what, hipMemcpy(o.mom.data(), d.mom, len * sizeof(double), hipMemcpyDeviceToHost));
-    HIPTRY(what, hipMemcpy(o.total.data(), d.total, 2 * np * sizeof(double), hipMemcpyDeviceToHost));
-    HIPTRY(what, hipMemcpy(o.st.data(), d.r.status, np * sizeof(int), hipMemcpyDeviceToHost));
-    HIPTRY(what, hipMemcpy(o.knot.data(), d.r.kbreak, np * sizeof(int), hipMemcpyDeviceToHost));
-    return CCLQR_OK;
+    const size_t np = (size_t)nprob;
+    TRY(download(o.rec, d.mom, np * (size_t)d.r.N * (size_t)ctk_record(d.r.mx, d.r.mu), what));
+    TRY(download(o.total, d.total, 2 * np, what));
+    return tracking_read_back(d.r, nprob, o, what);
 }
 // the per-knot records into the caller's arrays (each may be null), for the problems before the one the call is refused for, which it names with its knot
-static int tracking_cov_report(const CtkOut& o, int nprob, int mx, int mu, int N, double* cost, double* zstd, double* ustd, double* total, const char* of) {
+static int tracking_cov_report(const TrackOut& o, int nprob, int mx, int mu, int N, double* cost, double* zstd, double* ustd, double* total, const char* of) {
     const size_t rec = (size_t)ctk_record(mx, mu);
     for (int p = 0; p < nprob; p++) {
-        if (o.st[p] != 0) return fail(CCLQR_ESINGULAR, "G*Bl is singular in " + std::string(of) + " " + std::to_string(p) + " at knot " + std::to_string(o.knot[p]));
+        if (o.st[p] != 0) return singular_in(of, p, &o.knot[p]);
         for (int j = 0; j < N; j++) {
-            const double* m = o.mom.data() + ((size_t)p * N + j) * rec;
+            const double* m = o.rec.data() + ((size_t)p * N + j) * rec;
             const size_t k = (size_t)p * N + j;
             if (cost) { cost[2 * k] = m[0]; cost[2 * k + 1] = m[1]; }
             if (zstd) memcpy(zstd + k * mx, m + 2, (size_t)mx * sizeof(double));
             if (ustd && mu > 0) memcpy(ustd + k * mu, m + 2 + mx, (size_t)mu * sizeof(double));
         }
-        if (total) { total[2 * p] = o.total[2 * (size_t)p]; total[2 * p + 1] = o.total[2 * (size_t)p + 1]; }
+        put_pair(total, o.total, p);
     }
     return CCLQR_OK;
 }
@@ -1915,29 +1982,20 @@ extern "C" int cclqr_covariance_tracking(int32_t nprob, int32_t mx, int32_t mu, 
                                          const double* Sigma0, int32_t N, double* Sigma, double* Sigma_all, double* cost, double* zstd, double* ustd, double* total,
                                          const cclqr_riccati_opts* opts) {
     static const char* const what = "tracking covariance";
-    if (nprob < 1 || mx < 1 || mu < 0 || ml < 0 || N < 1) return fail(CCLQR_EINVAL, "bad sizes");
-    if (N > 1 && (!A || (mu > 0 && (!Bu || !K)) || (ml > 0 && (!Bl || !G)))) return fail(CCLQR_EINVAL, "null argument");
+    TRY(tracking_raw_check(nprob, mx, mu, ml, N, A, Bu, Bl, G, K));
     const bool want_cost = cost || total;
     TRY(tracking_cov_check(nprob, mu, N, nlin, n_gains, nK, n_weights, n_noise, Wu, Sigma0, Q, R, want_cost, opts, "problem"));
     WsScope scope;
-    RicModels d = {};
-    if (N > 1) TRY(upload_models((size_t)nprob * nlin, mx, mu, ml, A, Bu, Bl, G, d));      // N = 1: no model is read
-    const size_t nKd = (mu > 0 && N > 1) ? (size_t)n_gains * nK * mu * mx : 0, nP = (size_t)nprob * mx * mx;
-    double *dK = nullptr, *dP = nullptr, *dAll = nullptr;
-    HIPTRY(what, ws_get((void**)&dK, (nKd + 1) * sizeof(double)));
-    HIPTRY(what, ws_get((void**)&dP, nP * sizeof(double)));
-    if (Sigma_all) HIPTRY(what, ws_get((void**)&dAll, nP * N * sizeof(double)));
-    if (nKd) HIPTRY(what, hipMemcpy(dK, K, nKd * sizeof(double), hipMemcpyHostToDevice));
-    CtkOut o;
+    AnaDev d;
+    double* dAll = nullptr;
+    TRY(tracking_raw_upload(what, nprob, mx, mu, ml, nlin, A, Bu, Bl, G, n_gains, nK, K, N, Sigma_all != nullptr, d, &dAll));
+    TrackOut o;
     CtkArgs dev;
-    TRY(ctk_setup(nprob, nprob, mx, mu, ml, N, nlin, nK, n_weights, want_cost ? Q : nullptr, R, n_noise, Wu, Sigma0, opts ? opts->path : 0, nullptr, dev));
-    HIPTRY(what, ctk_launch_chunk(dev, 0, (size_t)nprob, d.A, d.Bu, d.Bl, d.G, dK, n_gains > 1 ? (long long)nK * mu * mx : 0, dP, dAll, nullptr));
+    TRY(ctk_setup(nprob, nprob, mx, mu, ml, N, nlin, n_weights, want_cost ? Q : nullptr, R, n_noise, Wu, Sigma0, opts ? opts->path : 0, nullptr, dev));
+    HIPTRY(what, ctk_launch_chunk(dev, 0, (size_t)nprob, d.m, d.k, d.P, dAll, nullptr));
     HIPTRY(what, hipDeviceSynchronize());
     TRY(ctk_read_back(dev, nprob, o));
-    int bad = nprob;      // the first problem the call is refused for: the arrays are filled up to it
-    for (int p = nprob - 1; p >= 0; p--) if (o.st[p] != 0) bad = p;
-    if (Sigma && bad > 0) HIPTRY(what, hipMemcpy(Sigma, dP, (size_t)bad * mx * mx * sizeof(double), hipMemcpyDeviceToHost));
-    if (Sigma_all && bad > 0) HIPTRY(what, hipMemcpy(Sigma_all, dAll, (size_t)bad * N * mx * mx * sizeof(double), hipMemcpyDeviceToHost));
+    TRY(tracking_raw_matrices(o, nprob, mx, N, Sigma, d.P, Sigma_all, dAll, what));
     return tracking_cov_report(o, nprob, mx, mu, N, cost, zstd, ustd, total, "problem");
 }
 
@@ -1946,36 +2004,26 @@ extern "C" int cclqr_covariance_tracking(int32_t nprob, int32_t mx, int32_t mu, 
 // gathered on the device, the problems in chunks within the workspace budget.  What an analysis brings of its own:
 //   check(nlin, tables, nK)                        its refusals about counts, weights and noise, before anything is allocated or launched
 //   plan(mx, ml, ric_per, ric_fixed, &per, &fixed) the bytes one problem adds to a chunk and the bytes the call holds once (tracking_cov_ / tracking_pol_problem_bytes)
-//   setup(chunk, mx, ml, nlin, nK, stream)         its launch arguments, inside this sequence's WsScope
-//   launch(c0, nc, dA, dBu, dBl, dG, dK, k_stride, P_dev, stream)   the recursion for the problems c0 .. c0 + nc - 1 on the chunk's models
+//   setup(chunk, mx, ml, nlin, stream)             its launch arguments, inside this sequence's WsScope
+//   launch(c0, nc, models, tables, P_dev, stream)  the recursion for the problems c0 .. c0 + nc - 1 on the chunk's models
 //   report()                                       its read-back into the caller's arrays, after every knot has converged
 template <class Check, class Plan, class Setup, class Launch, class Report>
 static int tracking_value_on_plants(const char* what, const cclqr_mech* m, const cclqr_plants* plants, int64_t first_plant, int32_t n_models, int32_t N, const double* zd,
                                     const double* Fd, int32_t on_device, int32_t mu, const int32_t* ctrl_joint, const cclqr_ctrl* c, int64_t workspace_bytes, void* stream,
                                     cclqr_value** out, Check check, Plan plan, Setup setup, Launch launch, Report report) {
     if (!m || !zd || !c || !out || (mu > 0 && !ctrl_joint)) return fail(CCLQR_EINVAL, "null argument");
-    TRY(check_device(m));
-    if (m->host.loop) return fail(CCLQR_EUNSUPPORTED, std::string("the ") + what + " is for tree mechanisms (closed loops have no multiplier model to evaluate a gain on)");
-    if (c->nb != m->nb || c->device != m->device) return fail(CCLQR_EINVAL, "the controller was created for another mechanism or device");
-    if (n_models < 1 || N < 1 || mu < 1 || mu > m->nb) return fail(CCLQR_EINVAL, "bad sizes");
-    const CtrlDev& H = c->host;
-    if (!c->K_dev || H.nK < 1) return fail(CCLQR_EINVAL, "the controller has no gains (open loop / PID)");
     LinArgs la;
     memset(&la, 0, sizeof(la));
-    TRY(linearize_check(m, plants, first_plant, n_models, mu, ctrl_joint, la.cj));      // the refusals of cclqr_linearize_plants
-    bool same = mu == H.mu;
-    for (int i = 0; same && i < mu; i++) same = la.cj[i] == H.cj[i];
-    if (!same) return fail(CCLQR_EINVAL, "mu / ctrl_joint are not the controller's: its gains act on other joints");
-    const int64_t tables = H.n_ctrl > 1 ? H.n_ctrl : 1;
-    if (tables != 1 && tables != n_models)
-        return fail(CCLQR_EINVAL, "the controller holds " + std::to_string(tables) + " tables: one shared by all models (1) or one per model (" + std::to_string(n_models) + ")");
+    int64_t tables = 1;
+    TRY(policy_ctrl_check(m, plants, first_plant, n_models, mu, ctrl_joint, c, std::string("the ") + what, n_models < 1 || N < 1 || mu < 1 || mu > m->nb, false, la.cj, &tables));
+    const CtrlDev& H = c->host;
     if (N > 1 && H.nK != 1 && H.nK != N - 1)
         return fail(CCLQR_EINVAL, "the controller's tables hold " + std::to_string(H.nK) + " gain rows: one (a stationary gain) or N - 1 = " + std::to_string(N - 1) + ", one per knot 0 .. N-2");
     const int nb = m->nb, mx = 12 * nb, ml = 5 * nb, nlin = N > 1 ? N - 1 : 1;
     TRY(check(nlin, (int)tables, H.nK));
     // the chunks the workspace budget allows, before anything is allocated
     RicArgs r1;
-    r1.nprob = 1; r1.mx = mx; r1.mu = mu; r1.ml = ml; r1.N = N; r1.time_varying = nlin > 1 ? 1 : 0; r1.tol = 0.0; r1.path = 0; r1.bf16_terms = 0; r1.keep_last = 0;
+    ric_sizes(r1, 1, mx, mu, ml, N, nlin > 1 ? 1 : 0, 0.0, 0);
     RicArgs r2 = r1;
     r2.nprob = 2;
     const long long ric_per = (long long)(ric_total_work_doubles(r2) - ric_total_work_doubles(r1)), ric_fixed = (long long)ric_total_work_doubles(r1) - ric_per;
@@ -2006,25 +2054,21 @@ static int tracking_value_on_plants(const char* what, const cclqr_mech* m, const
             dFd = uf;
         }
     }
-    // the controller's gains into the models' body order, device to device: they never visit the host
-    const long long rows_per_table = (long long)H.nK * mu, nrows = tables * rows_per_table;
-    double* dK = nullptr;
-    HIPTRY(what, ws_get((void**)&dK, (size_t)nrows * smx * sizeof(double)));
-    HIPTRY(what, launch_lds<false>(k_rows_to_body_order_kernel, dim3((unsigned)nrows), dim3(128), 0, st_, c->K_dev, nrows, rows_per_table, (long long)H.K_stride, nb, m->dev, dK));
-    const long long k_stride = tables > 1 ? rows_per_table * mx : 0;
-    double *dA = nullptr, *dBu = nullptr, *dBl = nullptr, *dG = nullptr;
+    GainTable gains;
+    TRY(gather_gains(m, c, mu, tables, st_, gains, what));
+    RicModels md = {};
     int* dlst = nullptr;
     const size_t nkk = nk > 0 ? nk : 1;
-    HIPTRY(what, ws_get((void**)&dA, pc * nkk * smx * smx * sizeof(double)));
-    HIPTRY(what, ws_get((void**)&dBu, pc * nkk * smx * smu * sizeof(double)));
-    HIPTRY(what, ws_get((void**)&dBl, pc * nkk * smx * sml * sizeof(double)));
-    HIPTRY(what, ws_get((void**)&dG, pc * nkk * sml * smx * sizeof(double)));
+    HIPTRY(what, ws_get((void**)&md.A, pc * nkk * smx * smx * sizeof(double)));
+    HIPTRY(what, ws_get((void**)&md.Bu, pc * nkk * smx * smu * sizeof(double)));
+    HIPTRY(what, ws_get((void**)&md.Bl, pc * nkk * smx * sml * sizeof(double)));
+    HIPTRY(what, ws_get((void**)&md.G, pc * nkk * sml * smx * sizeof(double)));
     HIPTRY(what, ws_get((void**)&dlst, (np * nkk + 1) * sizeof(int)));
-    TRY(setup((int)pc, mx, ml, nlin, H.nK, st_));
+    TRY(setup((int)pc, mx, ml, nlin, st_));
     la.M = m->dev; la.mu = mu;
     la.plants = plants ? plants->dev : nullptr;
     la.knots_per_plant = (int)nk; la.rows_per_plant = N;
-    la.A = dA; la.Bu = dBu; la.Bl = dBl; la.G = dG;
+    la.A = md.A; la.Bu = md.Bu; la.Bl = md.Bl; la.G = md.G;
     for (size_t c0 = 0; c0 < np; c0 += pc) {
         const size_t nc = np - c0 < pc ? np - c0 : pc;
         if (nk > 0) {      // linearsystem at the knots 0 .. N-2 of the chunk's trajectories (lqr_tracking.jl:88), one launch; N = 1 reads no model
@@ -2035,7 +2079,7 @@ static int tracking_value_on_plants(const char* what, const cclqr_mech* m, const
             la.status = dlst + c0 * nk;
             HIPTRY(what, launch_linearize(la, m->shape, st_));
         }
-        HIPTRY(what, launch(c0, nc, dA, dBu, dBl, dG, dK, k_stride, vown.p->P_dev, st_));
+        HIPTRY(what, launch(c0, nc, md, gains, vown.p->P_dev, st_));
     }
     HIPTRY(what, hipStreamSynchronize(st_));
     long long bad = -1;
@@ -2060,106 +2104,75 @@ extern "C" int cclqr_value_create_covariance_tracking(const cclqr_mech* m, const
             *per = tracking_cov_problem_bytes(mx, mu, ml, N, ric_per);
             *fixed = tracking_cov_fixed_bytes(mx, mu, ric_fixed, want_cost ? n_weights : 1, n_noise);
         },
-        [&](int chunk, int mx, int ml, int nlin, int nK, hipStream_t st) {
-            return ctk_setup(n_models, chunk, mx, mu, ml, N, nlin, nK, n_weights, want_cost ? Q : nullptr, R, n_noise, Wu, Sigma0, 0, st, dev);
+        [&](int chunk, int mx, int ml, int nlin, hipStream_t st) {
+            return ctk_setup(n_models, chunk, mx, mu, ml, N, nlin, n_weights, want_cost ? Q : nullptr, R, n_noise, Wu, Sigma0, 0, st, dev);
         },
-        [&](size_t c0, size_t nc, const double* dA, const double* dBu, const double* dBl, const double* dG, const double* dK, long long k_stride, double* P_dev, hipStream_t st) {
-            return ctk_launch_chunk(dev, c0, nc, dA, dBu, dBl, dG, dK, k_stride, P_dev, nullptr, st);
+        [&](size_t c0, size_t nc, const RicModels& md, const GainTable& gains, double* P_dev, hipStream_t st) {
+            return ctk_launch_chunk(dev, c0, nc, md, gains, P_dev, nullptr, st);
         },
         [&]() {
-            CtkOut o;
+            TrackOut o;
             TRY(ctk_read_back(dev, n_models, o));
             return tracking_cov_report(o, n_models, dev.r.mx, mu, N, cost, zstd, ustd, total, "table");
         });
 }
 
-// ---- the cost-to-go of a tracked run, knot by knot (policy_tracking.hip): P_j = Q + K_j' R K_j + Abar_j' P_{j+1} Abar_j with the gain row and the model of knot j
-// (lqr_tracking.jl:63-65, 88-89, 107-108), and the price of the noise of trackingLQR_triple_cartpole.jl:98 at every knot
-// what the entry refuses about its counts and its noise, before anything is allocated or launched: tracking_cov_check's list, and a price without a noise
+// ---- the tracking policy value's own: what the entry refuses about its counts and its noise, before anything is allocated or launched: tracking_cov_check's list, and
+// a price without a noise
 static int tracking_pol_check(int nprob, int mu, int N, int nlin, int n_gains, int nK, int n_weights, int n_noise, const double* Wu, const double* Q, const double* R,
                               const double* price, const double* noise_total, int knot, const cclqr_riccati_opts* opts, const char* of) {
-    if (N > 1 && nlin != 1 && nlin != N - 1)
-        return fail(CCLQR_EINVAL, "nlin = " + std::to_string(nlin) + ": one time-invariant model (1) or one per knot 0 .. N-2 (" + std::to_string(N - 1) + ")");
-    if (n_gains != 1 && n_gains != nprob)
-        return fail(CCLQR_EINVAL, "n_gains = " + std::to_string(n_gains) + ": the gains are one table shared by all (1) or one table per " + of + " (" + std::to_string(nprob) + ")");
-    if (N > 1 && mu > 0 && nK != 1 && nK != N - 1)
-        return fail(CCLQR_EINVAL, "nK = " + std::to_string(nK) + ": a gain table holds one row (a stationary gain) or N - 1 = " + std::to_string(N - 1) + " rows, one per knot 0 .. N-2");
+    TRY(tracking_counts_check(nprob, mu, N, nlin, n_gains, nK, of));
     TRY(check_n_weights(n_weights, nprob, of));
-    if (n_noise != 1 && n_noise != nprob)
-        return fail(CCLQR_EINVAL, "n_noise = " + std::to_string(n_noise) + ": Wu is one shared by all (1) or one per " + of + " (" + std::to_string(nprob) + ")");
+    TRY(check_n_noise(n_noise, nprob, "Wu is", of));
     if (Wu && mu == 0) return fail(CCLQR_EINVAL, "Wu is given with mu = 0: there is no input for the noise to enter through");
     if (!Wu && (price || noise_total)) return fail(CCLQR_EINVAL, "price / noise_total are asked for without Wu: there is no noise to price");
     if (!Q || (mu > 0 && !R)) return fail(CCLQR_EINVAL, "the cost-to-go needs Q / R");
     if (knot < 0 || knot > N - 1) return fail(CCLQR_EINVAL, "knot = " + std::to_string(knot) + ": the cost-to-go is that of a knot in 0 .. N-1 = " + std::to_string(N - 1));
-    if (nprob > 65535) return fail(CCLQR_EINVAL, "nprob = " + std::to_string(nprob) + ": at most 65535 problems per call (they are the y extent of the launch grids)");
-    const int path = opts ? opts->path : 0;
-    if (path < 0 || path > 2) return fail(CCLQR_EINVAL, "tracking policy value options: path in 0..2");
-    if (opts && opts->bf16_terms != 0) return fail(CCLQR_EINVAL, "the tracking policy value runs in fp64 only (bf16_terms = 0)");
-    return CCLQR_OK;
+    return tracking_launch_check(nprob, opts, "tracking policy value");
 }
-// what a tracking-policy call brings back to the host
-struct PtkOut { std::vector<double> price, total; std::vector<int> st, knot; };
-// fills d, inside the caller's WsScope, with the launch arguments of problem 0 onwards: weights, noise, prices, totals and statuses of ALL nprob problems, the workspace
-// of `chunk` problems, the most one launch takes.  Q, R, Wu: HOST, as the entries take them
-static int ptk_setup(int nprob, int chunk, int mx, int mu, int ml, int N, int nlin, int nK, int knot, int n_weights, const double* Q, const double* R, int n_noise,
-                     const double* Wu, int path, PtkArgs& d) {
+// fills c, inside the caller's WsScope, with the launch arguments of problem 0 onwards: tracking_setup, and the weights, prices and totals of ALL nprob problems.
+// Q, R: HOST, as the entries take them
+static int ptk_setup(int nprob, int chunk, int mx, int mu, int ml, int N, int nlin, int knot, int n_weights, const double* Q, const double* R, int n_noise, const double* Wu,
+                     int path, PtkArgs& c) {
     static const char* const what = "tracking policy value";
-    const size_t np = (size_t)nprob, nn = (size_t)n_noise, uu = (size_t)mu * mu;
-    PtkArgs& c = d;
+    const size_t np = (size_t)nprob;
     c = PtkArgs{};
-    RicArgs& r = c.r;
-    r.nprob = chunk; r.mx = mx; r.mu = mu; r.ml = ml; r.N = N; r.time_varying = (N > 1 && nlin > 1) ? 1 : 0; r.tol = 0.0; r.path = path; r.bf16_terms = 0; r.keep_last = 0;
-    double *dQ = nullptr, *dR = nullptr, *dWu = nullptr, *dwork = nullptr, *dprice = nullptr, *dtot = nullptr;
-    int *dst = nullptr, *dkn = nullptr;
-    TRY(upload_weights(mx, mu, n_weights, Q, R, &dQ, &dR, what));
-    if (n_weights > 1) { r.q_stride = (long long)mx * mx; r.r_stride = (long long)uu; }
+    WeightsIn w;
+    TRY(upload_weights(mx, mu, n_weights, Q, R, w, what));
+    ric_weights(c.r, w);
+    TRY(tracking_setup(c.r, c.n, nprob, chunk, mx, mu, ml, N, nlin, n_noise, Wu, nullptr, path, what));
     if (Wu) {
-        HIPTRY(what, ws_get((void**)&dWu, nn * uu * sizeof(double)));
-        HIPTRY(what, hipMemcpy(dWu, Wu, nn * uu * sizeof(double), hipMemcpyHostToDevice));
-        c.wu_stride = n_noise > 1 ? (long long)uu : 0;
-        HIPTRY(what, ws_get((void**)&dprice, np * N * sizeof(double)));
-        HIPTRY(what, ws_get((void**)&dtot, np * sizeof(double)));
+        HIPTRY(what, ws_get((void**)&c.price, np * N * sizeof(double)));
+        HIPTRY(what, ws_get((void**)&c.total, np * sizeof(double)));
     }
-    HIPTRY(what, ws_get((void**)&dwork, ric_total_work_doubles(r) * sizeof(double)));
-    HIPTRY(what, ws_get((void**)&dst, np * sizeof(int)));
-    HIPTRY(what, ws_get((void**)&dkn, np * sizeof(int)));
-    r.work = dwork; r.status = dst; r.kbreak = dkn; r.Q = dQ; r.R = dR;
-    c.nK = nK; c.knot = knot; c.Wu = dWu; c.price = dprice; c.total = dtot;
+    c.knot = knot;
     return CCLQR_OK;
 }
-// the recursion for the problems c0 .. c0 + nc - 1 on `stream`: their models (nlin per problem) lie at dA .. dG, their gains in dK (the tables of ALL problems, k_stride
-// doubles apart, 0 = one shared); dP [nprob][mx][mx] (or null) and dP_all [nprob][N][mx][mx] (or null) are the whole call's
-static hipError_t ptk_launch_chunk(const PtkArgs& d, size_t c0, size_t nc, const double* dA, const double* dBu, const double* dBl, const double* dG, const double* dK,
-                                   long long k_stride, double* dP, double* dP_all, hipStream_t stream) {
+// the recursion for the problems c0 .. c0 + nc - 1 on `stream` (tracking_chunk); dP [nprob][mx][mx] (or null) and dP_all [nprob][N][mx][mx] (or null) are the whole call's
+static hipError_t ptk_launch_chunk(const PtkArgs& d, size_t c0, size_t nc, const RicModels& md, const GainTable& tables, double* dP, double* dP_all, hipStream_t stream) {
     PtkArgs c = d;
     const size_t mm = (size_t)c.r.mx * c.r.mx, N = (size_t)c.r.N;
-    c.r.nprob = (int)nc; c.r.A = dA; c.r.Bu = dBu; c.r.Bl = dBl; c.r.G = dG;
-    c.r.status += c0; c.r.kbreak += c0;
+    tracking_chunk(c.r, c.k, c.n, c0, nc, md, tables);
     c.r.Q += (long long)c0 * c.r.q_stride; c.r.R += (long long)c0 * c.r.r_stride;
-    c.Kin = dK + (long long)c0 * k_stride; c.k_stride = k_stride;
-    if (c.Wu) { c.Wu += (long long)c0 * c.wu_stride; c.price += c0 * N; c.total += c0; }
+    if (c.n.Wu) { c.price += c0 * N; c.total += c0; }
     c.P = dP ? dP + c0 * mm : nullptr;
     c.P_all = dP_all ? dP_all + c0 * N * mm : nullptr;
     return launch_policy_tracking(c, stream);
 }
-static int ptk_read_back(const PtkArgs& d, int nprob, PtkOut& o) {
+static int ptk_read_back(const PtkArgs& d, int nprob, TrackOut& o) {
     static const char* const what = "tracking policy value";
-    const size_t np = (size_t)nprob, len = np * (size_t)d.r.N;
-    o.st.resize(np); o.knot.resize(np);
+    const size_t np = (size_t)nprob;
     if (d.price) {
-        o.price.resize(len); o.total.resize(np);
-        HIPTRY(what, hipMemcpy(o.price.data(), d.price, len * sizeof(double), hipMemcpyDeviceToHost));
-        HIPTRY(what, hipMemcpy(o.total.data(), d.total, np * sizeof(double), hipMemcpyDeviceToHost));
+        TRY(download(o.rec, d.price, np * (size_t)d.r.N, what));
+        TRY(download(o.total, d.total, np, what));
     }
-    HIPTRY(what, hipMemcpy(o.st.data(), d.r.status, np * sizeof(int), hipMemcpyDeviceToHost));
-    HIPTRY(what, hipMemcpy(o.knot.data(), d.r.kbreak, np * sizeof(int), hipMemcpyDeviceToHost));
-    return CCLQR_OK;
+    return tracking_read_back(d.r, nprob, o, what);
 }
 // the prices into the caller's arrays (each may be null), for the problems before the one the call is refused for, which it names with its knot
-static int tracking_pol_report(const PtkOut& o, int nprob, int N, double* price, double* noise_total, const char* of) {
+static int tracking_pol_report(const TrackOut& o, int nprob, int N, double* price, double* noise_total, const char* of) {
     for (int p = 0; p < nprob; p++) {
-        if (o.st[p] != 0) return fail(CCLQR_ESINGULAR, "G*Bl is singular in " + std::string(of) + " " + std::to_string(p) + " at knot " + std::to_string(o.knot[p]));
-        if (price) memcpy(price + (size_t)p * N, o.price.data() + (size_t)p * N, (size_t)N * sizeof(double));
+        if (o.st[p] != 0) return singular_in(of, p, &o.knot[p]);
+        if (price) memcpy(price + (size_t)p * N, o.rec.data() + (size_t)p * N, (size_t)N * sizeof(double));
         if (noise_total) noise_total[p] = o.total[(size_t)p];
     }
     return CCLQR_OK;
@@ -2169,28 +2182,19 @@ extern "C" int cclqr_policy_value_tracking(int32_t nprob, int32_t mx, int32_t mu
                                            int32_t n_gains, int32_t nK, const double* K, int32_t n_weights, const double* Q, const double* R, int32_t n_noise, const double* Wu,
                                            int32_t N, double* P, double* P_all, double* price, double* noise_total, const cclqr_riccati_opts* opts) {
     static const char* const what = "tracking policy value";
-    if (nprob < 1 || mx < 1 || mu < 0 || ml < 0 || N < 1) return fail(CCLQR_EINVAL, "bad sizes");
-    if (N > 1 && (!A || (mu > 0 && (!Bu || !K)) || (ml > 0 && (!Bl || !G)))) return fail(CCLQR_EINVAL, "null argument");
+    TRY(tracking_raw_check(nprob, mx, mu, ml, N, A, Bu, Bl, G, K));
     TRY(tracking_pol_check(nprob, mu, N, nlin, n_gains, nK, n_weights, n_noise, Wu, Q, R, price, noise_total, 0, opts, "problem"));
     WsScope scope;
-    RicModels d = {};
-    if (N > 1) TRY(upload_models((size_t)nprob * nlin, mx, mu, ml, A, Bu, Bl, G, d));      // N = 1: no model is read
-    const size_t nKd = (mu > 0 && N > 1) ? (size_t)n_gains * nK * mu * mx : 0, nP = (size_t)nprob * mx * mx;
-    double *dK = nullptr, *dP = nullptr, *dAll = nullptr;
-    HIPTRY(what, ws_get((void**)&dK, (nKd + 1) * sizeof(double)));
-    HIPTRY(what, ws_get((void**)&dP, nP * sizeof(double)));
-    if (P_all) HIPTRY(what, ws_get((void**)&dAll, nP * N * sizeof(double)));
-    if (nKd) HIPTRY(what, hipMemcpy(dK, K, nKd * sizeof(double), hipMemcpyHostToDevice));
-    PtkOut o;
+    AnaDev d;
+    double* dAll = nullptr;
+    TRY(tracking_raw_upload(what, nprob, mx, mu, ml, nlin, A, Bu, Bl, G, n_gains, nK, K, N, P_all != nullptr, d, &dAll));
+    TrackOut o;
     PtkArgs dev;
-    TRY(ptk_setup(nprob, nprob, mx, mu, ml, N, nlin, nK, 0, n_weights, Q, R, n_noise, Wu, opts ? opts->path : 0, dev));
-    HIPTRY(what, ptk_launch_chunk(dev, 0, (size_t)nprob, d.A, d.Bu, d.Bl, d.G, dK, n_gains > 1 ? (long long)nK * mu * mx : 0, dP, dAll, nullptr));
+    TRY(ptk_setup(nprob, nprob, mx, mu, ml, N, nlin, 0, n_weights, Q, R, n_noise, Wu, opts ? opts->path : 0, dev));
+    HIPTRY(what, ptk_launch_chunk(dev, 0, (size_t)nprob, d.m, d.k, d.P, dAll, nullptr));
     HIPTRY(what, hipDeviceSynchronize());
     TRY(ptk_read_back(dev, nprob, o));
-    int bad = nprob;      // the first problem the call is refused for: the arrays are filled up to it
-    for (int p = nprob - 1; p >= 0; p--) if (o.st[p] != 0) bad = p;
-    if (P && bad > 0) HIPTRY(what, hipMemcpy(P, dP, (size_t)bad * mx * mx * sizeof(double), hipMemcpyDeviceToHost));
-    if (P_all && bad > 0) HIPTRY(what, hipMemcpy(P_all, dAll, (size_t)bad * N * mx * mx * sizeof(double), hipMemcpyDeviceToHost));
+    TRY(tracking_raw_matrices(o, nprob, mx, N, P, d.P, P_all, dAll, what));
     return tracking_pol_report(o, nprob, N, price, noise_total, "problem");
 }
 
@@ -2207,12 +2211,12 @@ extern "C" int cclqr_value_create_policy_tracking(const cclqr_mech* m, const ccl
             *per = tracking_pol_problem_bytes(mx, mu, ml, N, ric_per);
             *fixed = tracking_pol_fixed_bytes(mx, mu, ric_fixed, n_weights, Wu ? n_noise : 0);
         },
-        [&](int chunk, int mx, int ml, int nlin, int nK, hipStream_t) { return ptk_setup(n_models, chunk, mx, mu, ml, N, nlin, nK, knot, n_weights, Q, R, n_noise, Wu, 0, dev); },
-        [&](size_t c0, size_t nc, const double* dA, const double* dBu, const double* dBl, const double* dG, const double* dK, long long k_stride, double* P_dev, hipStream_t st) {
-            return ptk_launch_chunk(dev, c0, nc, dA, dBu, dBl, dG, dK, k_stride, P_dev, nullptr, st);
+        [&](int chunk, int mx, int ml, int nlin, hipStream_t) { return ptk_setup(n_models, chunk, mx, mu, ml, N, nlin, knot, n_weights, Q, R, n_noise, Wu, 0, dev); },
+        [&](size_t c0, size_t nc, const RicModels& md, const GainTable& gains, double* P_dev, hipStream_t st) {
+            return ptk_launch_chunk(dev, c0, nc, md, gains, P_dev, nullptr, st);
         },
         [&]() {
-            PtkOut o;
+            TrackOut o;
             TRY(ptk_read_back(dev, n_models, o));
             return tracking_pol_report(o, n_models, N, price, noise_total, "table");
         });
@@ -2230,15 +2234,15 @@ extern "C" int cclqr_riccati_doubling(int32_t nprob, int32_t mx, int32_t mu, int
     WsScope scope;
     RicModels d = {};
     TRY(upload_models((size_t)nprob, mx, mu, ml, A, Bu, Bl, G, d));
-    const size_t np = (size_t)nprob, nw = (size_t)n_weights, nK = np * mu * mx, nP = np * mx * mx;
-    double *dQ = nullptr, *dR = nullptr, *dK = nullptr, *dP = nullptr, *dwork = nullptr, *dwork2 = nullptr, *ddn = nullptr, *dan = nullptr;
+    const size_t np = (size_t)nprob, nK = np * mu * mx, nP = np * mx * mx;
+    double *dK = nullptr, *dP = nullptr, *dwork = nullptr, *dwork2 = nullptr, *ddn = nullptr, *dan = nullptr;
     int *dlv = nullptr, *drs = nullptr, *dst = nullptr, *dstop = nullptr;
     RdbArgs a;
     RicArgs& r = a.r;
-    r.nprob = nprob; r.mx = mx; r.mu = mu; r.ml = ml; r.N = N; r.time_varying = 0; r.tol = tol; r.path = 0; r.bf16_terms = 0; r.keep_last = 1;
-    if (n_weights > 1) { r.q_stride = (long long)mx * mx; r.r_stride = (long long)mu * mu; }
-    HIPTRY(what, ws_get((void**)&dQ, nw * mx * mx * sizeof(double)));
-    HIPTRY(what, ws_get((void**)&dR, (nw * mu * mu + 1) * sizeof(double)));
+    WeightsIn w;
+    ric_sizes(r, nprob, mx, mu, ml, N, 0, tol, 0, 1);
+    TRY(upload_weights(mx, mu, n_weights, Q, R, w, what));
+    ric_weights(r, w);
     HIPTRY(what, ws_get((void**)&dK, (nK + 1) * sizeof(double)));
     if (P) HIPTRY(what, ws_get((void**)&dP, nP * sizeof(double)));
     HIPTRY(what, ws_get((void**)&dwork, ric_total_work_doubles(r) * sizeof(double)));
@@ -2249,28 +2253,14 @@ extern "C" int cclqr_riccati_doubling(int32_t nprob, int32_t mx, int32_t mu, int
     HIPTRY(what, ws_get((void**)&dlv, np * sizeof(int)));
     HIPTRY(what, ws_get((void**)&drs, np * sizeof(int)));
     HIPTRY(what, ws_get((void**)&dst, np * sizeof(int)));
-    HIPTRY(what, hipMemcpy(dQ, Q, nw * mx * mx * sizeof(double), hipMemcpyHostToDevice));
-    if (mu > 0) HIPTRY(what, hipMemcpy(dR, R, nw * mu * mu * sizeof(double), hipMemcpyHostToDevice));
     HIPTRY(what, hipMemset(dK, 0, (nK + 1) * sizeof(double)));
-    r.stop = dstop; r.A = d.A; r.Bu = d.Bu; r.Bl = d.Bl; r.G = d.G; r.Q = dQ; r.R = dR; r.K = dK; r.kbreak = nullptr; r.status = dst; r.work = dwork; r.P_out = dP;
+    r.stop = dstop; r.A = d.A; r.Bu = d.Bu; r.Bl = d.Bl; r.G = d.G; r.K = dK; r.kbreak = nullptr; r.status = dst; r.work = dwork; r.P_out = dP;
     a.max_levels = max_levels; a.work2 = dwork2; a.levels = dlv; a.reason = drs; a.dnorm = ddn; a.anorm = dan;
     HIPTRY(what, launch_riccati_doubling(a, nullptr));
-    HIPTRY(what, hipDeviceSynchronize());
-    std::vector<int> lv(np), rs(np), st(np);
-    std::vector<double> dn(2 * np), an(2 * np);
-    HIPTRY(what, hipMemcpy(lv.data(), dlv, np * sizeof(int), hipMemcpyDeviceToHost));
-    HIPTRY(what, hipMemcpy(rs.data(), drs, np * sizeof(int), hipMemcpyDeviceToHost));
-    HIPTRY(what, hipMemcpy(st.data(), dst, np * sizeof(int), hipMemcpyDeviceToHost));
-    HIPTRY(what, hipMemcpy(dn.data(), ddn, 2 * np * sizeof(double), hipMemcpyDeviceToHost));
-    HIPTRY(what, hipMemcpy(an.data(), dan, 2 * np * sizeof(double), hipMemcpyDeviceToHost));
+    DblOut o;
+    TRY(doubling_read_back(np, dlv, drs, dst, ddn, dan, o, what));
     if (nK) HIPTRY(what, hipMemcpy(K, dK, nK * sizeof(double), hipMemcpyDeviceToHost));
     if (P) HIPTRY(what, hipMemcpy(P, dP, nP * sizeof(double), hipMemcpyDeviceToHost));
-    for (size_t p = 0; p < np; p++) {
-        if (levels) levels[p] = lv[p];
-        if (reason) reason[p] = rs[p];
-        if (dnorm) { dnorm[2 * p] = dn[2 * p]; dnorm[2 * p + 1] = dn[2 * p + 1]; }
-        if (anorm) { anorm[2 * p] = an[2 * p]; anorm[2 * p + 1] = an[2 * p + 1]; }
-        if (st[p] != 0) return fail(CCLQR_ESINGULAR, "G*Bl is singular in problem " + std::to_string(p));
-    }
-    return CCLQR_OK;
+    return doubling_report(o, nprob, levels, reason, dnorm, anorm, "problem");
 }
+

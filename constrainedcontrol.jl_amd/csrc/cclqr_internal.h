@@ -217,14 +217,27 @@ hipError_t launch_riccati(const RicArgs& a, hipStream_t stream);
 // the nprob of the WHOLE call, and passes the answer to every launch: a chunk's own problem count must not pick another kernel
 int ric_chosen_path(const RicArgs& a);
 
+// What the analysis records below (PolArgs .. PtkArgs) share; capi.hip fills each by one function.  A batch's gain tables (raw_upload, gather_gains):
+struct GainTable {
+    const double* Kin = nullptr;   // device: tables [n_gains][nK][mu][mx] in the order of the models' states; may be null when mu = 0 or no step runs
+    long long k_stride = 0;        // doubles between the tables of consecutive problems: 0 = one table shared by all, or nK * mu * mx
+    int nK = 0;                    // rows per table: one per step / knot, or 1 (a stationary gain, used by every step); the doubling records hold 1 and do not read it
+};
+struct NoiseIn {      // ... its noise (upload_noise)
+    const double *Wu = nullptr, *Sigma0 = nullptr;   // device [n_noise][mu][mu], [n_noise][mx][mx]; either may be null (= 0)
+    long long wu_stride = 0, s0_stride = 0;          // doubles between consecutive problems' matrices: 0 = one shared by all
+};
+struct WeightsIn {    // ... its stage-cost weights (upload_weights; where they are the recursion's own, r.Q / r.R, capi.hip's ric_weights copies them into the RicArgs)
+    const double *Q = nullptr, *R = nullptr;         // device [n_weights][mx][mx], [n_weights][mu][mu]
+    long long q_stride = 0, r_stride = 0;            // 0 = one pair shared by all, or mx * mx / mu * mu
+};
+
 // Policy evaluation (policy.hip): dlqr's cost recursion (lqr.jl:147-177) with the gain GIVEN.  r: the problems as launch_riccati takes them -- nprob, mx, mu, ml, N, tol,
 // A, Bu, Bl, G (time_varying = 0), Q, R with their strides, kbreak, status, stop, work (ric_total_work_doubles(r) doubles), path, and P_out, which is REQUIRED here;
 // bf16_terms = 0; K, keep_last, kpad and p_rows are not read (no kernel here assumes a symmetric Pk).  The launch shape is ric_chosen_path(r).
 struct PolArgs {
     RicArgs r;
-    const double* Kin;       // device: gain tables [n_gains][nK][mu][mx] in the order of the models' states; may be null when mu = 0 or N = 1
-    long long k_stride;      // doubles between the tables of consecutive problems: 0 = one table shared by all, or nK * mu * mx
-    int nK;                  // rows per table: N - 1 (row k - 1 = the gain of backward step k) or 1 (a stationary gain, used by every step)
+    GainTable k;             // nK rows per table: N - 1 (row k - 1 = the gain of backward step k) or 1
     double* dnorm;           // device [nprob][2]: norm(Pk - Pkp1) of the last executed step and of the step before it, NaN where no such step ran
 };
 hipError_t launch_policy(const PolArgs& a, hipStream_t stream);
@@ -234,8 +247,7 @@ hipError_t launch_policy(const PolArgs& a, hipStream_t stream);
 // written.  The launch shape is launch_policy's.
 struct DblArgs {
     RicArgs r;
-    const double* Kin;       // device: the stationary gains [n_gains][mu][mx] in the order of the models' states; may be null when mu = 0
-    long long k_stride;      // doubles between the gains of consecutive problems: 0 = one gain shared by all, or mu * mx
+    GainTable k;             // the stationary gains [n_gains][mu][mx], one row each
     int max_levels;          // to convergence: the last level (2^max_levels steps)
     double* work2;           // device: dbl_work_doubles(r) doubles
     int *levels, *reason;    // device [nprob]: doublings made; to convergence, why the last one was the last (0 converged, 1 max_levels, 2 norm(M) > 1e50)
@@ -257,10 +269,8 @@ hipError_t launch_doubling_levels(const DblArgs& a, hipStream_t stream);
 // copy of Σ0 (q_stride mx^2); d.r.P_out receives Σ.  d.work2 holds cov_work_doubles(d.r) doubles.
 struct CovArgs {
     DblArgs d;
-    const double *Wu, *Sigma0;   // device [n_noise][mu][mu], [n_noise][mx][mx]; either may be null (= 0)
-    long long wu_stride, s0_stride;   // doubles between consecutive problems' matrices: 0 = one shared by all
-    const double *Q, *R;         // device, the stage-cost weights; read only when cost is given
-    long long q_stride, r_stride;
+    NoiseIn n;
+    WeightsIn w;                 // the stage-cost weights; read only when cost is given
     double *cost, *zstd, *ustd;  // device [nprob][2], [nprob][mx], [nprob][mu], each may be null: tr(Q Σ) and tr(R K Σ K'), sqrt(diag Σ), sqrt(diag K Σ K')
 };
 size_t cov_work_doubles(const RicArgs& r);
@@ -272,13 +282,9 @@ hipError_t launch_covariance_doubling(const CovArgs& a, hipStream_t stream);
 // tiled; 0 = 1); nothing else of r is read.
 struct CtkArgs {
     RicArgs r;
-    const double* Kin;           // device: gain tables [n_gains][nK][mu][mx] in the order of the models' states; may be null when mu = 0 or N = 1
-    long long k_stride;          // doubles between the tables of consecutive problems: 0 = one table shared by all, or nK * mu * mx
-    int nK;                      // rows per table: N - 1 (row j = the gain of knot j) or 1 (a stationary gain)
-    const double *Wu, *Sigma0;   // device [n_noise][mu][mu], [n_noise][mx][mx]; either may be null (= 0)
-    long long wu_stride, s0_stride;
-    const double *Q, *R;         // device, the stage-cost weights (zeros when the caller asks for no cost)
-    long long q_stride, r_stride;
+    GainTable k;                 // nK rows per table: N - 1 (row j = the gain of knot j) or 1
+    NoiseIn n;
+    WeightsIn w;                 // the stage-cost weights (zeros when the caller asks for no cost)
     double* mom;                 // device [nprob][N][2 + mx + mu]: per knot cx, cu, zstd [mx], ustd [mu]
     double* total;               // device [nprob][2]
     double *Sigma, *Sigma_all;   // device [nprob][mx][mx], [nprob][N][mx][mx]; each may be null
@@ -295,12 +301,9 @@ hipError_t launch_covariance_tracking(const CtkArgs& a, hipStream_t stream);
 // (the stage-cost weights, required).
 struct PtkArgs {
     RicArgs r;
-    const double* Kin;           // device: gain tables [n_gains][nK][mu][mx] in the order of the models' states; may be null when mu = 0 or N = 1
-    long long k_stride;          // doubles between the tables of consecutive problems: 0 = one table shared by all, or nK * mu * mx
-    int nK;                      // rows per table: N - 1 (row j = the gain of knot j) or 1 (a stationary gain)
+    GainTable k;                 // nK rows per table: N - 1 (row j = the gain of knot j) or 1
     int knot;                    // in [0, N-1]: the recursion runs from N - 1 down to this knot
-    const double* Wu;            // device [n_noise][mu][mu], or null: no price is taken
-    long long wu_stride;
+    NoiseIn n;                   // Wu, or null: no price is taken; there is no start covariance (Sigma0 stays null)
     double *P, *P_all;           // device [nprob][mx][mx] = P_knot, [nprob][N][mx][mx] (knots below `knot` are not written); each may be null
     double *price, *total;       // device [nprob][N] (zeros below `knot` and at N - 1), [nprob] = the prices summed from N - 2 downwards; both given with Wu, else both null
 };

@@ -163,15 +163,15 @@ hipError_t launch_covariance_doubling(const CovArgs& v, hipStream_t stream) {
     memset(&c, 0, sizeof(c));
     c.S0s = p.work2 + dbl_work_doubles(a); c.w = c.S0s + np * mm; c.stage = c.w + np; c.scaled = 1;
     a.Q = c.S0s; a.q_stride = (long long)mm; a.R = nullptr; a.r_stride = 0;      // the recursion's terminal matrix is the scaled Σ0
-    c.Kin = p.Kin; c.k_stride = p.k_stride; c.Wu = v.Wu; c.S0 = v.Sigma0; c.wu_stride = v.wu_stride; c.s0_stride = v.s0_stride;
+    c.Kin = p.k.Kin; c.k_stride = p.k.k_stride; c.Wu = v.n.Wu; c.S0 = v.n.Sigma0; c.wu_stride = v.n.wu_stride; c.s0_stride = v.n.s0_stride;
     c.Md = dbl_Md(p); c.Sd = dbl_Sd(p);
-    c.Q = v.Q; c.R = v.R; c.q_stride = v.q_stride; c.r_stride = v.r_stride;
+    c.Q = v.w.Q; c.R = v.w.R; c.q_stride = v.w.q_stride; c.r_stride = v.w.r_stride;
     c.Sigma = a.P_out; c.dnorm = p.dnorm; c.cost = v.cost; c.zstd = v.zstd; c.ustd = v.ustd;
     hipError_t e = dbl_preset(p, stream);
     if (e == hipSuccess) e = hipMemsetAsync(c.S0s, 0, np * mm * sizeof(double), stream);      // (the projection copies the terminal matrix before the setup has written it)
     if (a.N == 1) {      // no step: Σ = Σ0 as written (zeros without one) -- no model is read, nothing is scaled
         c.scaled = 0;
-        if (v.Sigma0) { a.Q = v.Sigma0; a.q_stride = v.s0_stride; }
+        if (v.n.Sigma0) { a.Q = v.n.Sigma0; a.q_stride = v.n.s0_stride; }
     }
     const RicGrid g = ric_grid_of(a);
     if (a.N != 1) {

@@ -410,9 +410,9 @@ hipError_t launch_covariance_tracking(const CtkArgs& v, hipStream_t stream) {
     g.Q = g.P; g.q_stride = (long long)a.mx * a.mx;      // the projection's "Pk = Q" copies Σ_0 onto itself
     CtkGrid c;
     memset(&c, 0, sizeof(c));
-    c.Kin = v.Kin; c.k_stride = v.k_stride; c.nK = v.nK;
-    c.Wu = a.mu > 0 ? v.Wu : nullptr; c.S0 = v.Sigma0; c.wu_stride = v.wu_stride; c.s0_stride = v.s0_stride;
-    c.Q = v.Q; c.R = v.R; c.q_stride = v.q_stride; c.r_stride = v.r_stride;
+    c.Kin = v.k.Kin; c.k_stride = v.k.k_stride; c.nK = v.k.nK;
+    c.Wu = a.mu > 0 ? v.n.Wu : nullptr; c.S0 = v.n.Sigma0; c.wu_stride = v.n.wu_stride; c.s0_stride = v.n.s0_stride;
+    c.Q = v.w.Q; c.R = v.w.R; c.q_stride = v.w.q_stride; c.r_stride = v.w.r_stride;
     c.Sigma = v.Sigma; c.Sigma_all = v.Sigma_all; c.mom = v.mom; c.total = v.total;
     hipError_t e = launch_lds<false>(ctk_init_kernel, dim3(a.nprob), dim3(TILE_THREADS), 0, stream, g, c);
     if (e == hipSuccess && a.N > 1) e = launch_ric_project(g, a, stream);      // N = 1: no model is read

@@ -308,7 +308,7 @@ hipError_t launch_policy(const PolArgs& p, hipStream_t stream) {
     RicGrid g = ric_grid_of(a);
     g.tol = a.tol;
     PolGrid q;
-    q.Kin = p.Kin; q.k_stride = p.k_stride; q.nK = p.nK; q.dnorm = p.dnorm;
+    q.Kin = p.k.Kin; q.k_stride = p.k.k_stride; q.nK = p.k.nK; q.dnorm = p.dnorm;
     const size_t np = a.nprob, mu = a.mu, mx = a.mx;
     hipError_t e = hipMemsetAsync(a.stop, 0, np * sizeof(int), stream);
     if (e == hipSuccess) e = hipMemsetAsync(a.status, 0, np * sizeof(int), stream);

@@ -277,7 +277,7 @@ static void dbl_records(const DblArgs& p, RicGrid& g, DblGrid& d) {
     const RicArgs& a = p.r;
     g = ric_grid_of(a);
     const size_t np = a.nprob, mm = (size_t)a.mx * a.mx;
-    d.Kin = p.Kin; d.k_stride = p.k_stride; d.N = a.N; d.max_levels = p.max_levels; d.tol = a.tol;
+    d.Kin = p.k.Kin; d.k_stride = p.k.k_stride; d.N = a.N; d.max_levels = p.max_levels; d.tol = a.tol;
     d.levels = p.levels; d.reason = p.reason; d.dnorm = p.dnorm; d.gnorm = p.gnorm; d.P_out = a.P_out;
     double* w = p.work2;
     d.Md = dbl_Md(p); d.Sd = dbl_Sd(p); d.Ma = w + 2 * np * mm; d.Sa = w + 3 * np * mm;

@@ -385,9 +385,9 @@ hipError_t launch_policy_tracking(const PtkArgs& v, hipStream_t stream) {
     const RicGrid g = ric_grid_of(a);      // (the record also carries a.stop: no kernel here and no projection kernel reads it)
     PtkGrid c;
     memset(&c, 0, sizeof(c));
-    c.Kin = v.Kin; c.k_stride = v.k_stride; c.nK = v.nK; c.knot = v.knot;
-    const bool priced = a.mu > 0 && v.Wu && v.price && v.total;
-    c.Wu = priced ? v.Wu : nullptr; c.wu_stride = v.wu_stride;
+    c.Kin = v.k.Kin; c.k_stride = v.k.k_stride; c.nK = v.k.nK; c.knot = v.knot;
+    const bool priced = a.mu > 0 && v.n.Wu && v.price && v.total;
+    c.Wu = priced ? v.n.Wu : nullptr; c.wu_stride = v.n.wu_stride;
     c.P = v.P; c.P_all = v.P_all;
     c.price = v.price; c.total = v.total;      // without a priced noise the init kernel still zeroes them
     hipError_t e = launch_lds<false>(ptk_init_kernel, dim3(a.nprob), dim3(TILE_THREADS), 0, stream, g, c);

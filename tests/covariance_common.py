@@ -29,6 +29,7 @@ A case takes the models, Q, R, K of pdc._models(name); Wu, one Wu per problem an
     perprob   one Wu per problem and Σ0 fixed horizons                      (not for mu = 0)
 tol of the run to convergence lies between two consecutive relative increments of problem 0, by the recipe of pdc.build_case; the builder asserts that no longdouble
 increment lies within 1e-6 relative of tol, no norm(M) within 1e-6 of 1e50, and tr W of no problem within 1e-6 relative of a power of two."""
+import ctypes as C
 import zlib
 
 import numpy as np
@@ -235,3 +236,38 @@ def check_conv(S, cost, zstd, ustd, levels, reason, dn, gn, r, what):
     err, scale, bound = float(np.abs(S - r["S"]).max()), float(np.abs(r["S"]).max()), ref.tolerance(r["e64"])
     assert err <= bound * scale, "%s: max|Σ - Σref| = %.3g relative, bound %.3g" % (what, err / scale, bound)
     check_moments(cost, zstd, ustd, r, what)
+
+
+def refusal_call(capi, pr):
+    """cclqr_covariance_doubling through ctypes on sentinel-filled outputs, for tests/test_gpu_covariance.py and tests/test_analysis_refusals_host.py.  pr: nprob, mx, mu,
+    ml and the arrays A, Bu, Bl, G, K, Q, R, Wu, Sigma0.  The call returns (rc, outputs untouched, cclqr_last_error())"""
+    L = capi.lib()
+    n, mx, mu, ml = pr["nprob"], pr["mx"], pr["mu"], pr["ml"]
+    dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+    d = lambda a: None if a is None else a.ctypes.data_as(dp)
+    A, Bu, Bl, G, K, Q, R, Wu, S0 = (np.ascontiguousarray(pr[k]) for k in ("A", "Bu", "Bl", "G", "K", "Q", "R", "Wu", "Sigma0"))
+
+    def call(n_gains=1, n_weights=1, n_noise=1, N=10, tol=1e-8, max_levels=40, path=0, bf16=0, nprob=n, A_=A, S_=True, K_=K, Bl_=Bl, Wu_=Wu, S0_=S0, Q_=Q, R_=R,
+             cost_=True, mu_=mu):
+        S = np.full((n, mx, mx), 7.5)
+        cost, zs, us = np.full((n, 2), 7.5), np.full((n, mx), 7.5), np.full((n, mu), 7.5)
+        lv, rs = np.full(n, -9, dtype=np.int32), np.full(n, -9, dtype=np.int32)
+        dn, gn = np.full((n, 2), 7.5), np.full((n, 2), 7.5)
+        o = capi.RiccatiOpts(path, bf16, 0, 0)
+        rc = L.cclqr_covariance_doubling(C.c_int32(nprob), C.c_int32(mx), C.c_int32(mu_), C.c_int32(ml), d(A_), d(Bu), d(Bl_), d(G), C.c_int32(n_gains), d(K_),
+                                         C.c_int32(n_weights), d(Q_), d(R_), C.c_int32(n_noise), d(Wu_), d(S0_), C.c_int32(N), C.c_double(tol), C.c_int32(max_levels),
+                                         d(S) if S_ else None, d(cost) if cost_ else None, d(zs), d(us), lv.ctypes.data_as(ip), rs.ctypes.data_as(ip), d(dn), d(gn),
+                                         C.byref(o))
+        untouched = bool(all((x == 7.5).all() for x in (S, cost, zs, us, dn, gn)) and (lv == -9).all() and (rs == -9).all())
+        return rc, untouched, L.cclqr_last_error().decode()
+
+    return call
+
+
+def refusal_cases():
+    """what cclqr_covariance_doubling refuses as CCLQR_EINVAL: name -> the arguments of refusal_call's call (nprob must not be 2)"""
+    return dict(N_neg=dict(N=-1), levels_0=dict(N=0, S0_=None, max_levels=0), levels_61=dict(N=0, S0_=None, max_levels=61), tol_neg=dict(tol=-1e-9),
+                tol_nan=dict(tol=float("nan")), n_gains_2=dict(n_gains=2), n_weights_2=dict(n_weights=2), n_weights_0=dict(n_weights=0), path_3=dict(path=3),
+                bf16=dict(bf16=2), nprob_0=dict(nprob=0), A_null=dict(A_=None), S_null=dict(S_=False), K_null=dict(K_=None),
+                n_noise_2=dict(n_noise=2), n_noise_0=dict(n_noise=0), no_source=dict(Wu_=None, S0_=None), cost_without_Q=dict(Q_=None),
+                cost_without_R=dict(R_=None), Wu_with_mu_0=dict(mu_=0), start_with_N_0=dict(N=0))

@@ -21,6 +21,7 @@ A case takes the models, weights and the gain Kfull[0] of a policy_value_common 
 a run to convergence lies between two consecutive longdouble increments of problem 0, and the builder asserts that no longdouble increment of any problem lies within
 1e-6 relative of tol and no norm(M) within 1e-6 relative of 1e50.  Large shapes get a tol that converges within three levels, so that the stepping reference stays
 cheap."""
+import ctypes as C
 import zlib
 
 import numpy as np
@@ -245,3 +246,34 @@ def check_conv(P, levels, reason, dn, gn, refp, what):
             else:
                 assert abs(got[j] - want[j]) <= bound * max(abs(want[j]), scale), "%s: %s[%d] = %.17g, reference %.17g, bound %.3g of max(|ref|, max|Pref| = %.3g)" % (
                     what, name, j, got[j], want[j], bound, scale)
+
+
+def refusal_call(capi, pr):
+    """cclqr_policy_value_doubling through ctypes on sentinel-filled outputs, for tests/test_gpu_policy_doubling.py and tests/test_analysis_refusals_host.py.  pr: nprob,
+    mx, mu, ml, tol and the arrays A, Bu, Bl, G, K, Q, R.  The call returns (rc, outputs untouched, cclqr_last_error())"""
+    L = capi.lib()
+    n, mx, mu, ml = pr["nprob"], pr["mx"], pr["mu"], pr["ml"]
+    dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+    d = lambda a: a.ctypes.data_as(dp)
+    A, Bu, Bl, G, K, Q, R = (np.ascontiguousarray(pr[k]) for k in ("A", "Bu", "Bl", "G", "K", "Q", "R"))
+
+    def call(n_gains=1, n_weights=1, N=10, tol=pr["tol"], max_levels=40, path=0, bf16=0, nprob=n, A_=A, P_=True, K_=K, Bl_=Bl):
+        P = np.full((n, mx, mx), 7.5)
+        lv, rs = np.full(n, -9, dtype=np.int32), np.full(n, -9, dtype=np.int32)
+        dn, gn = np.full((n, 2), 7.5), np.full((n, 2), 7.5)
+        o = capi.RiccatiOpts(path, bf16, 0, 0)
+        rc = L.cclqr_policy_value_doubling(C.c_int32(nprob), C.c_int32(mx), C.c_int32(mu), C.c_int32(ml), None if A_ is None else d(A_), d(Bu), d(Bl_), d(G),
+                                           C.c_int32(n_gains), None if K_ is None else d(K_), C.c_int32(n_weights), d(Q), d(R), C.c_int32(N), C.c_double(tol),
+                                           C.c_int32(max_levels), d(P) if P_ else None, lv.ctypes.data_as(ip), rs.ctypes.data_as(ip), d(dn), d(gn), C.byref(o))
+        untouched = bool((P == 7.5).all() and (lv == -9).all() and (rs == -9).all() and (dn == 7.5).all() and (gn == 7.5).all())
+        return rc, untouched, L.cclqr_last_error().decode()
+
+    return call
+
+
+def refusal_cases():
+    """what cclqr_policy_value_doubling refuses as CCLQR_EINVAL: name -> the arguments of refusal_call's call (nprob must not be 2)"""
+    return dict(N_neg=dict(N=-1), levels_0=dict(N=0, max_levels=0), levels_61=dict(N=0, max_levels=61), tol_neg=dict(tol=-1e-9), tol_nan=dict(tol=float("nan")),
+                tol_nan_conv=dict(N=0, tol=float("nan")), n_gains_2=dict(n_gains=2), n_gains_0=dict(n_gains=0), n_weights_2=dict(n_weights=2),
+                n_weights_0=dict(n_weights=0), path_3=dict(path=3), path_neg=dict(path=-1), bf16=dict(bf16=2), nprob_0=dict(nprob=0), A_null=dict(A_=None),
+                P_null=dict(P_=False), K_null=dict(K_=None))

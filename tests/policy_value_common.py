@@ -22,6 +22,7 @@ sums is granted.
 A case: seed crc32(name); base model dlqr_reference._model(rng, mx, mu, ml), Q = _spd, R = _spd; the gain table is the float64 dlqr of the base model at tol = 0;
 problem p is the base model with A, Bu, Bλ each perturbed by pert p N(0,1) / sqrt(mx), so problem 0 is the model the table was designed on; tol from
 choose_tol(..., "mid") on the float64 norms of every problem."""
+import ctypes as C
 import zlib
 
 import numpy as np
@@ -151,3 +152,33 @@ def check(P, kb, dn, refp, what):
             else:
                 assert abs(dn[j] - dnref[j]) <= bound * max(abs(dnref[j]), scale), "%s: dnorm[%d] = %.17g, reference %.17g, bound %.3g of max(|ref|, max|Pref| = %.3g)" % (
                     what, j, dn[j], dnref[j], bound, scale)
+
+
+def refusal_call(capi, pr):
+    """cclqr_policy_value through ctypes on sentinel-filled outputs, for tests/test_gpu_policy_value.py and tests/test_analysis_refusals_host.py.  pr: nprob, mx, mu, ml,
+    N, tol and the contiguous arrays A, Bu, Bl, G, K, Q, R.  The call returns (rc, outputs untouched, cclqr_last_error())"""
+    L = capi.lib()
+    n, mx, mu, ml, N = pr["nprob"], pr["mx"], pr["mu"], pr["ml"], pr["N"]
+    dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+    d = lambda a: a.ctypes.data_as(dp)
+    A, Bu, Bl, G, K, Q, R = (np.ascontiguousarray(pr[k]) for k in ("A", "Bu", "Bl", "G", "K", "Q", "R"))
+
+    def call(n_gains=1, nK=N - 1, n_weights=1, N_=N, path=0, bf16=0, nprob=n, A_=A, P_=True, K_=K):
+        P = np.full((n, mx, mx), 7.5)
+        kb = np.full(n, -9, dtype=np.int32)
+        dn = np.full((n, 2), 7.5)
+        o = capi.RiccatiOpts(path, bf16, 0, 0)
+        rc = L.cclqr_policy_value(C.c_int32(nprob), C.c_int32(mx), C.c_int32(mu), C.c_int32(ml), None if A_ is None else d(A_), d(Bu), d(Bl), d(G), C.c_int32(n_gains),
+                                  C.c_int32(nK), None if K_ is None else d(K_), C.c_int32(n_weights), d(Q), d(R), C.c_int32(N_), C.c_double(pr["tol"]),
+                                  d(P) if P_ else None, kb.ctypes.data_as(ip), d(dn), C.byref(o))
+        return rc, bool((P == 7.5).all() and (kb == -9).all() and (dn == 7.5).all()), L.cclqr_last_error().decode()
+
+    return call
+
+
+def refusal_cases(pr):
+    """what cclqr_policy_value refuses as CCLQR_EINVAL: name -> the arguments of refusal_call's call (nprob must not be 2)"""
+    N = pr["N"]
+    return dict(n_gains_2=dict(n_gains=2), n_gains_0=dict(n_gains=0), nK_2=dict(nK=2), nK_0=dict(nK=0), nK_N=dict(nK=N), n_weights_2=dict(n_weights=2),
+                n_weights_0=dict(n_weights=0), N_0=dict(N_=0), path_3=dict(path=3), path_neg=dict(path=-1), bf16=dict(bf16=2), nprob_0=dict(nprob=0),
+                A_null=dict(A_=None), P_null=dict(P_=False), K_null=dict(K_=None))

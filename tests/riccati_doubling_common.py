@@ -17,6 +17,7 @@ in float64, dlqr_reference._step_projected64, and the schedule above in numpy fl
 
 tol of a run to convergence lies between two consecutive longdouble increments of problem 0; the builder asserts that no longdouble increment of any problem lies
 within 1e-6 relative of it and no norm(A) within 1e-6 relative of 1e50."""
+import ctypes as C
 import zlib
 
 import numpy as np
@@ -275,3 +276,37 @@ def check_norms(got, want, bound, scale, name, what):
         else:
             assert abs(got[j] - want[j]) <= bound * max(abs(want[j]), scale), "%s: %s[%d] = %.17g, reference %.17g, bound %.3g of max(|ref|, %.3g)" % (
                 what, name, j, got[j], want[j], bound, scale)
+
+
+def refusal_call(capi, pr):
+    """cclqr_riccati_doubling through ctypes on sentinel-filled outputs, for tests/test_gpu_riccati_doubling.py and tests/test_analysis_refusals_host.py.  pr: nprob, mx,
+    mu, ml, tol and the arrays A, Bu, Bl, G, Q, R.  The call returns (rc, outputs untouched, cclqr_last_error())"""
+    L = capi.lib()
+    n, mx, mu, ml = pr["nprob"], pr["mx"], pr["mu"], pr["ml"]
+    dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+    d = lambda a: a.ctypes.data_as(dp)
+    A, Bu, Bl, G, Q, R = (np.ascontiguousarray(pr[k]) for k in ("A", "Bu", "Bl", "G", "Q", "R"))
+
+    def call(n_weights=1, N=10, tol=pr["tol"], max_levels=40, bf16=0, nprob=n, A_=A, K_=True, Bl_=Bl, Q_=Q, R_=R, mx_=mx):
+        K, P = np.full((n, mu, mx), 7.5), np.full((n, mx, mx), 7.5)
+        lv, rs = np.full(n, -9, dtype=np.int32), np.full(n, -9, dtype=np.int32)
+        dn, an = np.full((n, 2), 7.5), np.full((n, 2), 7.5)
+        o = capi.RiccatiOpts(0, bf16, 1, 0)
+        rc = L.cclqr_riccati_doubling(C.c_int32(nprob), C.c_int32(mx_), C.c_int32(mu), C.c_int32(ml), None if A_ is None else d(A_), d(Bu), d(Bl_), d(G),
+                                      C.c_int32(n_weights), d(Q_), d(R_), C.c_int32(N), C.c_double(tol), C.c_int32(max_levels), d(K) if K_ else None, d(P),
+                                      lv.ctypes.data_as(ip), rs.ctypes.data_as(ip), d(dn), d(an), C.byref(o))
+        untouched = bool((K == 7.5).all() and (P == 7.5).all() and (lv == -9).all() and (rs == -9).all() and (dn == 7.5).all() and (an == 7.5).all())
+        return rc, untouched, L.cclqr_last_error().decode()
+
+    return call
+
+
+def refusal_cases(pr):
+    """what cclqr_riccati_doubling refuses as CCLQR_EINVAL: name -> the arguments of refusal_call's call (mu >= 2: a 1 x 1 R cannot fail to be symmetric)"""
+    Qn, Rn = np.ascontiguousarray(pr["Q"]).copy(), np.ascontiguousarray(pr["R"]).copy()
+    Qn[0, 1] = np.nextafter(Qn[0, 1], np.inf)
+    Rn[1, 0] = np.nextafter(Rn[1, 0], np.inf)
+    return dict(N_1=dict(N=1), N_neg=dict(N=-1), levels_0=dict(N=0, max_levels=0), levels_61=dict(N=0, max_levels=61), tol_neg=dict(tol=-1e-9),
+                tol_nan=dict(tol=float("nan")), tol_nan_conv=dict(N=0, tol=float("nan")), n_weights_2=dict(n_weights=pr["nprob"] + 1), n_weights_0=dict(n_weights=0),
+                bf16=dict(bf16=2), nprob_0=dict(nprob=0), mx_0=dict(mx_=0), mx_huge=dict(mx_=20000), A_null=dict(A_=None), K_null=dict(K_=False),
+                Q_nonsym=dict(Q_=Qn), R_nonsym=dict(R_=Rn))

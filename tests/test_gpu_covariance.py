@@ -6,8 +6,6 @@ and the acceptance rule stated there (the CPU twin tests/test_covariance_referen
   * duality with the cost recursion on the device: tr(Q Σ) + tr(R K Σ K') = tr(P W) up to the terminal term P carries and Σ does not.
   * the unstable closed loop stops with reason 2 and a finite Σ; every refusal of both entry points returns its code with the outputs untouched;
     cclqr_policy_value_doubling returns the same bits before and after a covariance call."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
@@ -160,36 +158,14 @@ def test_policy_value_doubling_returns_the_same_bits_around_a_covariance_call(cc
 
 def test_every_refusal_code_and_untouched_outputs(cclqr):
     capi = cclqr._capi
-    L = capi.lib()
     pr = cc.build_case("pd_30")
-    n, mx, mu, ml = pr["nprob"], pr["mx"], pr["mu"], pr["ml"]
-    dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
-    d = lambda a: None if a is None else a.ctypes.data_as(dp)
-    A, Bu, Bl, G = (np.ascontiguousarray(x) for x in _models(pr))
-    K, Q, R, Wu, S0 = (np.ascontiguousarray(pr[k]) for k in ("K", "Q", "R", "Wu", "Sigma0"))
-
-    def call(n_gains=1, n_weights=1, n_noise=1, N=10, tol=1e-8, max_levels=40, path=0, bf16=0, nprob=n, A_=A, S_=True, K_=K, Bl_=Bl, Wu_=Wu, S0_=S0, Q_=Q, R_=R,
-             cost_=True, mu_=mu):
-        S = np.full((n, mx, mx), 7.5)
-        cost, zs, us = np.full((n, 2), 7.5), np.full((n, mx), 7.5), np.full((n, mu), 7.5)
-        lv, rs = np.full(n, -9, dtype=np.int32), np.full(n, -9, dtype=np.int32)
-        dn, gn = np.full((n, 2), 7.5), np.full((n, 2), 7.5)
-        o = capi.RiccatiOpts(path, bf16, 0, 0)
-        rc = L.cclqr_covariance_doubling(C.c_int32(nprob), C.c_int32(mx), C.c_int32(mu_), C.c_int32(ml), d(A_), d(Bu), d(Bl_), d(G), C.c_int32(n_gains), d(K_),
-                                         C.c_int32(n_weights), d(Q_), d(R_), C.c_int32(n_noise), d(Wu_), d(S0_), C.c_int32(N), C.c_double(tol), C.c_int32(max_levels),
-                                         d(S) if S_ else None, d(cost) if cost_ else None, d(zs), d(us), lv.ctypes.data_as(ip), rs.ctypes.data_as(ip), d(dn), d(gn),
-                                         C.byref(o))
-        return rc, bool(all((x == 7.5).all() for x in (S, cost, zs, us, dn, gn)) and (lv == -9).all() and (rs == -9).all())
-
+    Bl = np.ascontiguousarray(pr["Bl"])
+    call = cc.refusal_call(capi, pr)
     assert call()[0] == capi.OK and call(N=0, S0_=None)[0] == capi.OK and call(Wu_=None)[0] == capi.OK and call(S0_=None)[0] == capi.OK
     assert call(cost_=False, Q_=None, R_=None)[0] == capi.OK and call(N=1)[0] == capi.OK
-    refused = dict(N_neg=call(N=-1), levels_0=call(N=0, S0_=None, max_levels=0), levels_61=call(N=0, S0_=None, max_levels=61), tol_neg=call(tol=-1e-9),
-                   tol_nan=call(tol=float("nan")), n_gains_2=call(n_gains=2), n_weights_2=call(n_weights=2), n_weights_0=call(n_weights=0), path_3=call(path=3),
-                   bf16=call(bf16=2), nprob_0=call(nprob=0), A_null=call(A_=None), S_null=call(S_=False), K_null=call(K_=None),
-                   n_noise_2=call(n_noise=2), n_noise_0=call(n_noise=0), no_source=call(Wu_=None, S0_=None), cost_without_Q=call(Q_=None),
-                   cost_without_R=call(R_=None), Wu_with_mu_0=call(mu_=0), start_with_N_0=call(N=0))
-    for what, (rc, untouched) in refused.items():
-        assert rc == capi.EINVAL and untouched, (what, rc, untouched)
-    rc, _ = call(Bl_=np.zeros_like(Bl))
+    refused = {what: call(**kw) for what, kw in cc.refusal_cases().items()}
+    for what, (rc, untouched, msg) in refused.items():
+        assert rc == capi.EINVAL and untouched, (what, rc, untouched, msg)
+    rc, _, _ = call(Bl_=np.zeros_like(Bl))
     assert rc == capi.ESINGULAR and call(N=0, S0_=None, Bl_=np.zeros_like(Bl))[0] == capi.ESINGULAR
     assert call(N=1, Bl_=np.zeros_like(Bl))[0] == capi.OK      # no step reaches the model, as in the cost recursion

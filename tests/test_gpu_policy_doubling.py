@@ -6,8 +6,6 @@ references and the acceptance rule stated there (the CPU twin tests/test_policy_
     with reason 1 at the cost-to-go of 8 steps.
   * bitwise: shared against replicated gains and weights, a problem alone against inside a batch, path 1 against path 0 where 0 chooses the resident kernel.
   * every CCLQR_EINVAL leaves the outputs untouched; a singular G Bλ is CCLQR_ESINGULAR."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
@@ -106,31 +104,13 @@ def test_a_nonsymmetric_problem_keeps_a_nonsymmetric_cost_to_go_and_null_diagnos
 
 def test_every_refusal_code_and_untouched_outputs(cclqr):
     capi = cclqr._capi
-    L = capi.lib()
     pr = pdc.build_case("pd_36")
-    n, mx, mu, ml = pr["nprob"], pr["mx"], pr["mu"], pr["ml"]
-    dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
-    d = lambda a: a.ctypes.data_as(dp)
-    A, Bu, Bl, G = (np.ascontiguousarray(x) for x in _models(pr))
-    K, Q, R = np.ascontiguousarray(pr["K"]), np.ascontiguousarray(pr["Q"]), np.ascontiguousarray(pr["R"])
-
-    def call(n_gains=1, n_weights=1, N=10, tol=pr["tol"], max_levels=40, path=0, bf16=0, nprob=n, A_=A, P_=True, K_=K, Bl_=Bl):
-        P = np.full((n, mx, mx), 7.5)
-        lv, rs = np.full(n, -9, dtype=np.int32), np.full(n, -9, dtype=np.int32)
-        dn, gn = np.full((n, 2), 7.5), np.full((n, 2), 7.5)
-        o = capi.RiccatiOpts(path, bf16, 0, 0)
-        rc = L.cclqr_policy_value_doubling(C.c_int32(nprob), C.c_int32(mx), C.c_int32(mu), C.c_int32(ml), None if A_ is None else d(A_), d(Bu), d(Bl_), d(G),
-                                           C.c_int32(n_gains), None if K_ is None else d(K_), C.c_int32(n_weights), d(Q), d(R), C.c_int32(N), C.c_double(tol),
-                                           C.c_int32(max_levels), d(P) if P_ else None, lv.ctypes.data_as(ip), rs.ctypes.data_as(ip), d(dn), d(gn), C.byref(o))
-        return rc, bool((P == 7.5).all() and (lv == -9).all() and (rs == -9).all() and (dn == 7.5).all() and (gn == 7.5).all())
-
+    Bl = np.ascontiguousarray(pr["Bl"])
+    call = pdc.refusal_call(capi, pr)
     assert call()[0] == capi.OK and call(N=0)[0] == capi.OK and call(N=0, max_levels=1)[0] == capi.OK and call(N=0, max_levels=60, tol=1e300)[0] == capi.OK
     assert call(max_levels=0)[0] == capi.OK      # (max_levels is not read for a fixed horizon)
-    refused = dict(N_neg=call(N=-1), levels_0=call(N=0, max_levels=0), levels_61=call(N=0, max_levels=61), tol_neg=call(tol=-1e-9), tol_nan=call(tol=float("nan")),
-                   tol_nan_conv=call(N=0, tol=float("nan")), n_gains_2=call(n_gains=2), n_gains_0=call(n_gains=0), n_weights_2=call(n_weights=2),
-                   n_weights_0=call(n_weights=0), path_3=call(path=3), path_neg=call(path=-1), bf16=call(bf16=2), nprob_0=call(nprob=0), A_null=call(A_=None),
-                   P_null=call(P_=False), K_null=call(K_=None))
-    for what, (rc, untouched) in refused.items():
-        assert rc == capi.EINVAL and untouched, (what, rc, untouched)
+    refused = {what: call(**kw) for what, kw in pdc.refusal_cases().items()}
+    for what, (rc, untouched, msg) in refused.items():
+        assert rc == capi.EINVAL and untouched, (what, rc, untouched, msg)
     assert call(Bl_=np.zeros_like(Bl))[0] == capi.ESINGULAR and call(N=0, Bl_=np.zeros_like(Bl))[0] == capi.ESINGULAR
     assert call(N=1, Bl_=np.zeros_like(Bl))[0] == capi.OK      # no step reaches the model, as in the stepping recursion

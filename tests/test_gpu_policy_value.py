@@ -2,13 +2,11 @@
 acceptance rule stated there (the CPU twin tests/test_policy_value_reference.py shows that the cases cannot pass vacuously), and what the entry point promises besides:
 shared and per-problem gains / weights give the same bits, N = 1 returns Q, a non-symmetric problem keeps a non-symmetric P, kbreak = dnorm = NULL changes nothing,
 every CCLQR_EINVAL leaves the outputs untouched, and the Riccati's own gains fed back reproduce the Riccati's own cost-to-go, device against device."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 import dlqr_reference as ref
-from policy_value_common import CASES, build_case, check
+from policy_value_common import CASES, build_case, check, refusal_call, refusal_cases
 
 pytestmark = pytest.mark.gpu
 
@@ -70,30 +68,12 @@ def test_null_kbreak_and_dnorm_give_the_same_cost_to_go(cclqr, name, path):
 
 def test_every_einval_leaves_the_outputs_untouched(cclqr):
     capi = cclqr._capi
-    L = capi.lib()
     pr = build_case("pv_reg_mu2")
-    n, mx, mu, ml, N = pr["nprob"], pr["mx"], pr["mu"], pr["ml"], pr["N"]
-    dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
-    d = lambda a: a.ctypes.data_as(dp)
-    A, Bu, Bl, G = (np.ascontiguousarray(x) for x in _models(pr))
-    K, Q, R = np.ascontiguousarray(pr["K"]), np.ascontiguousarray(pr["Q"]), np.ascontiguousarray(pr["R"])
-
-    def call(n_gains=1, nK=N - 1, n_weights=1, N_=N, path=0, bf16=0, nprob=n, A_=A, P_=True, K_=K):
-        P = np.full((n, mx, mx), 7.5)
-        kb = np.full(n, -9, dtype=np.int32)
-        dn = np.full((n, 2), 7.5)
-        o = capi.RiccatiOpts(path, bf16, 0, 0)
-        rc = L.cclqr_policy_value(C.c_int32(nprob), C.c_int32(mx), C.c_int32(mu), C.c_int32(ml), None if A_ is None else d(A_), d(Bu), d(Bl), d(G), C.c_int32(n_gains),
-                                  C.c_int32(nK), None if K_ is None else d(K_), C.c_int32(n_weights), d(Q), d(R), C.c_int32(N_), C.c_double(pr["tol"]),
-                                  d(P) if P_ else None, kb.ctypes.data_as(ip), d(dn), C.byref(o))
-        return rc, bool((P == 7.5).all() and (kb == -9).all() and (dn == 7.5).all())
-
+    call = refusal_call(capi, pr)
     assert call()[0] == capi.OK
-    refused = dict(n_gains_2=call(n_gains=2), n_gains_0=call(n_gains=0), nK_2=call(nK=2), nK_0=call(nK=0), nK_N=call(nK=N), n_weights_2=call(n_weights=2),
-                   n_weights_0=call(n_weights=0), N_0=call(N_=0), path_3=call(path=3), path_neg=call(path=-1), bf16=call(bf16=2), nprob_0=call(nprob=0),
-                   A_null=call(A_=None), P_null=call(P_=False), K_null=call(K_=None))
-    for what, (rc, untouched) in refused.items():
-        assert rc == capi.EINVAL and untouched, (what, rc, untouched)
+    refused = {what: call(**kw) for what, kw in refusal_cases(pr).items()}
+    for what, (rc, untouched, msg) in refused.items():
+        assert rc == capi.EINVAL and untouched, (what, rc, untouched, msg)
 
 
 @pytest.mark.parametrize("name,path", [("pv_frag_1_6", 1), ("pv_frag_7_21", 1), ("pv_tiled_30", 2), ("pv_nonsym", 1)])

@@ -8,8 +8,6 @@ stated there (the CPU twin tests/test_riccati_doubling_reference.py shows that t
   * a zero pivot of I + G1 H2 (one state, q = -r / d^2) is reason 3 for that problem alone, in both modes: NaN gain and P for a fixed horizon, the triple of the
     level before kept in a run to convergence; its neighbour in the batch is untouched.
   * every CCLQR_EINVAL leaves the outputs untouched; a singular G Bλ is CCLQR_ESINGULAR."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
@@ -133,33 +131,14 @@ def test_a_zero_pivot_is_reason_three_for_that_problem_alone(cclqr):
 
 def test_every_refusal_code_and_untouched_outputs(cclqr):
     capi = cclqr._capi
-    L = capi.lib()
     pr = rdc.build_case("rd_36")
-    n, mx, mu, ml = pr["nprob"], pr["mx"], pr["mu"], pr["ml"]
-    dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
-    d = lambda a: a.ctypes.data_as(dp)
-    A, Bu, Bl, G = (np.ascontiguousarray(x) for x in _models(pr))
-    Q, R = np.ascontiguousarray(pr["Q"]), np.ascontiguousarray(pr["R"])
-    Qn, Rn = Q.copy(), R.copy()
-    Qn[0, 1] = np.nextafter(Qn[0, 1], np.inf)
-    Rn[1, 0] = np.nextafter(Rn[1, 0], np.inf)
-
-    def call(n_weights=1, N=10, tol=pr["tol"], max_levels=40, bf16=0, nprob=n, A_=A, K_=True, Bl_=Bl, Q_=Q, R_=R, mx_=mx):
-        K, P = np.full((n, mu, mx), 7.5), np.full((n, mx, mx), 7.5)
-        lv, rs = np.full(n, -9, dtype=np.int32), np.full(n, -9, dtype=np.int32)
-        dn, an = np.full((n, 2), 7.5), np.full((n, 2), 7.5)
-        o = capi.RiccatiOpts(0, bf16, 1, 0)
-        rc = L.cclqr_riccati_doubling(C.c_int32(nprob), C.c_int32(mx_), C.c_int32(mu), C.c_int32(ml), None if A_ is None else d(A_), d(Bu), d(Bl_), d(G),
-                                      C.c_int32(n_weights), d(Q_), d(R_), C.c_int32(N), C.c_double(tol), C.c_int32(max_levels), d(K) if K_ else None, d(P),
-                                      lv.ctypes.data_as(ip), rs.ctypes.data_as(ip), d(dn), d(an), C.byref(o))
-        return rc, bool((K == 7.5).all() and (P == 7.5).all() and (lv == -9).all() and (rs == -9).all() and (dn == 7.5).all() and (an == 7.5).all())
-
+    Bl = np.ascontiguousarray(pr["Bl"])
+    call = rdc.refusal_call(capi, pr)
     assert call()[0] == capi.OK and call(N=0)[0] == capi.OK and call(N=0, max_levels=1)[0] == capi.OK and call(N=0, max_levels=60, tol=1e300)[0] == capi.OK
     assert call(N=2)[0] == capi.OK and call(max_levels=0)[0] == capi.OK      # (max_levels is not read for a fixed horizon)
-    refused = dict(N_1=call(N=1), N_neg=call(N=-1), levels_0=call(N=0, max_levels=0), levels_61=call(N=0, max_levels=61), tol_neg=call(tol=-1e-9),
-                   tol_nan=call(tol=float("nan")), tol_nan_conv=call(N=0, tol=float("nan")), n_weights_2=call(n_weights=n + 1), n_weights_0=call(n_weights=0),
-                   bf16=call(bf16=2), nprob_0=call(nprob=0), mx_0=call(mx_=0), mx_huge=call(mx_=20000), A_null=call(A_=None), K_null=call(K_=False), Q_nonsym=call(Q_=Qn), R_nonsym=call(R_=Rn))
-    for what, (rc, untouched) in refused.items():
-        assert rc == capi.EINVAL and untouched, (what, rc, untouched)
-    assert call(Q_=Qn)[0] == capi.EINVAL and "not symmetric" in L.cclqr_last_error().decode()
+    cases = rdc.refusal_cases(pr)
+    refused = {what: call(**kw) for what, kw in cases.items()}
+    for what, (rc, untouched, msg) in refused.items():
+        assert rc == capi.EINVAL and untouched, (what, rc, untouched, msg)
+    assert call(**cases["Q_nonsym"])[0] == capi.EINVAL and "not symmetric" in capi.lib().cclqr_last_error().decode()
     assert call(Bl_=np.zeros_like(Bl))[0] == capi.ESINGULAR and call(N=0, Bl_=np.zeros_like(Bl))[0] == capi.ESINGULAR

@@ -4,8 +4,6 @@ references and the acceptance rule stated there (the CPU twin tests/test_trackin
   * bitwise: a problem alone against inside its batch; shared against replicated gains, weights and noise; with and without Sigma_all and the moments;
     path 0 against path 1 where the shape fits the resident kernel; N = 1 returns Sigma0.
   * every refusal returns CCLQR_EINVAL with sentinel-filled outputs untouched; a singular G Bλ at a middle knot is CCLQR_ESINGULAR and names the knot."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
@@ -70,30 +68,12 @@ def test_alone_batched_shared_replicated_and_fewer_outputs_give_the_same_bits(cc
 
 def test_every_refusal_code_and_untouched_outputs(cclqr):
     capi = cclqr._capi
-    L = capi.lib()
     pr = tc.build_case("tc_12_1_5")
-    n, mx, mu, ml, N0 = pr["nprob"], pr["mx"], pr["mu"], pr["ml"], 11
-    dp = C.POINTER(C.c_double)
-    d = lambda a: None if a is None else a.ctypes.data_as(dp)
-    A, Bu, Bl, G, K = tc.call_arrays(pr, N0, True, True)
-    Q, R, Wu, S0 = (np.ascontiguousarray(pr[k]) for k in ("Q", "R", "Wu", "Sigma0"))
-
-    def call(nlin=N0 - 1, n_gains=n, nK=N0 - 1, n_weights=1, n_noise=1, N=N0, path=0, bf16=0, nprob=n, mx_=mx, mu_=mu, A_=A, K_=K, Bl_=Bl, Wu_=Wu, S0_=S0, Q_=Q, R_=R,
-             cost_=True, total_=True):
-        S, Sall = np.full((n, mx, mx), 7.5), np.full((n, N0, mx, mx), 7.5)
-        cost, zs, us, tot = np.full((n, N0, 2), 7.5), np.full((n, N0, mx), 7.5), np.full((n, N0, mu), 7.5), np.full((n, 2), 7.5)
-        o = capi.RiccatiOpts(path, bf16, 0, 0)
-        rc = L.cclqr_covariance_tracking(C.c_int32(nprob), C.c_int32(mx_), C.c_int32(mu_), C.c_int32(ml), C.c_int32(nlin), d(A_), d(Bu), d(Bl_), d(G), C.c_int32(n_gains),
-                                         C.c_int32(nK), d(K_), C.c_int32(n_weights), d(Q_), d(R_), C.c_int32(n_noise), d(Wu_), d(S0_), C.c_int32(N), d(S), d(Sall),
-                                         d(cost) if cost_ else None, d(zs), d(us), d(tot) if total_ else None, C.byref(o))
-        return rc, bool(all((x == 7.5).all() for x in (S, Sall, cost, zs, us, tot))), L.cclqr_last_error().decode()
-
+    A, Bu, Bl, G, K = tc.call_arrays(pr, 11, True, True)
+    call = tc.refusal_call(capi, dict(pr, A=A, Bu=Bu, Bl=Bl, G=G, K=K), 11)
     assert call()[0] == capi.OK and call(Wu_=None)[0] == capi.OK and call(S0_=None)[0] == capi.OK and call(N=1)[0] == capi.OK
     assert call(cost_=False, total_=False, Q_=None, R_=None)[0] == capi.OK
-    refused = dict(nprob_0=call(nprob=0), mx_0=call(mx_=0), N_0=call(N=0), nlin_2=call(nlin=2), nlin_0=call(nlin=0), n_gains_2=call(n_gains=2), nK_2=call(nK=2),
-                   n_weights_2=call(n_weights=2), n_weights_0=call(n_weights=0), n_noise_2=call(n_noise=2), n_noise_0=call(n_noise=0), no_source=call(Wu_=None, S0_=None),
-                   Wu_with_mu_0=call(mu_=0), cost_without_Q=call(Q_=None), total_without_R=call(R_=None, cost_=False), A_null=call(A_=None), K_null=call(K_=None),
-                   Bl_null=call(Bl_=None), path_3=call(path=3), path_neg=call(path=-1), bf16=call(bf16=1), too_many=call(nprob=65536, n_gains=1))
+    refused = {what: call(**kw) for what, kw in tc.refusal_cases().items()}
     for what, (rc, untouched, msg) in refused.items():
         assert rc == capi.EINVAL and untouched, (what, rc, untouched, msg)
     # a singular G Bλ at a middle knot of problem 1: named with its knot, on both paths

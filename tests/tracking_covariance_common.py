@@ -24,6 +24,7 @@ A problem's models are dlqr_reference.make_problem(..., tv=True) (a base model w
 gains (any table would do: the gains are given); without inputs the same models from dlqr_reference._model and an empty table.  Wu, one Wu per problem and Sigma0
 are dlqr_reference._spd.  Variants: full (Wu shared, Sigma0) on all four sharings nlin x nK; nostart (Wu, no Sigma0) and perprob (one Wu per problem, Sigma0) on
 nlin = nK = N - 1; without inputs only full."""
+import ctypes as C
 import zlib
 
 import numpy as np
@@ -221,3 +222,34 @@ def check_horizon(pr, key, N, p, Sigma, Sigma_all, cost, zstd, ustd, total, what
           % (what, N, e64, bound, worst, total, want, terr / tscale if tscale else 0.0, tscale))
     assert terr <= bound * tscale, "%s: total %s, reference %s" % (what, total, want)
     assert np.array_equal(total, np.array(run)), "%s: total is not the costs summed in knot order" % what
+
+
+def refusal_call(capi, pr, N0):
+    """cclqr_covariance_tracking through ctypes on sentinel-filled outputs, for tests/test_gpu_tracking_covariance.py and tests/test_analysis_refusals_host.py.  pr: nprob,
+    mx, mu, ml, the arrays A, Bu, Bl, G [nprob][N0 - 1][...] and K [nprob][N0 - 1][mu][mx] of horizon N0 (call_arrays) and Q, R, Wu, Sigma0.  The call returns
+    (rc, outputs untouched, cclqr_last_error())"""
+    L = capi.lib()
+    n, mx, mu, ml = pr["nprob"], pr["mx"], pr["mu"], pr["ml"]
+    dp = C.POINTER(C.c_double)
+    d = lambda a: None if a is None else a.ctypes.data_as(dp)
+    A, Bu, Bl, G, K, Q, R, Wu, S0 = (np.ascontiguousarray(pr[k]) for k in ("A", "Bu", "Bl", "G", "K", "Q", "R", "Wu", "Sigma0"))
+
+    def call(nlin=N0 - 1, n_gains=n, nK=N0 - 1, n_weights=1, n_noise=1, N=N0, path=0, bf16=0, nprob=n, mx_=mx, mu_=mu, A_=A, K_=K, Bl_=Bl, Wu_=Wu, S0_=S0, Q_=Q, R_=R,
+             cost_=True, total_=True):
+        S, Sall = np.full((n, mx, mx), 7.5), np.full((n, N0, mx, mx), 7.5)
+        cost, zs, us, tot = np.full((n, N0, 2), 7.5), np.full((n, N0, mx), 7.5), np.full((n, N0, mu), 7.5), np.full((n, 2), 7.5)
+        o = capi.RiccatiOpts(path, bf16, 0, 0)
+        rc = L.cclqr_covariance_tracking(C.c_int32(nprob), C.c_int32(mx_), C.c_int32(mu_), C.c_int32(ml), C.c_int32(nlin), d(A_), d(Bu), d(Bl_), d(G), C.c_int32(n_gains),
+                                         C.c_int32(nK), d(K_), C.c_int32(n_weights), d(Q_), d(R_), C.c_int32(n_noise), d(Wu_), d(S0_), C.c_int32(N), d(S), d(Sall),
+                                         d(cost) if cost_ else None, d(zs), d(us), d(tot) if total_ else None, C.byref(o))
+        return rc, bool(all((x == 7.5).all() for x in (S, Sall, cost, zs, us, tot))), L.cclqr_last_error().decode()
+
+    return call
+
+
+def refusal_cases():
+    """what cclqr_covariance_tracking refuses as CCLQR_EINVAL: name -> the arguments of refusal_call's call (nprob must not be 2, N0 not 3)"""
+    return dict(nprob_0=dict(nprob=0), mx_0=dict(mx_=0), N_0=dict(N=0), nlin_2=dict(nlin=2), nlin_0=dict(nlin=0), n_gains_2=dict(n_gains=2), nK_2=dict(nK=2),
+                n_weights_2=dict(n_weights=2), n_weights_0=dict(n_weights=0), n_noise_2=dict(n_noise=2), n_noise_0=dict(n_noise=0), no_source=dict(Wu_=None, S0_=None),
+                Wu_with_mu_0=dict(mu_=0), cost_without_Q=dict(Q_=None), total_without_R=dict(R_=None, cost_=False), A_null=dict(A_=None), K_null=dict(K_=None),
+                Bl_null=dict(Bl_=None), path_3=dict(path=3), path_neg=dict(path=-1), bf16=dict(bf16=1), too_many=dict(nprob=65536, n_gains=1))

@@ -13,6 +13,8 @@ sharing and horizon is the largest max|P64_j - Pref_j| / max|Pref_j| over the kn
 projected pair [A' | D] (np.linalg.solve); the twins must agree with the reference to 1e-9, and the bound is dlqr_reference.tolerance(e64), the suite's own rule.
 P_j is held to the bound relative to max|Pref_j|; price_j to bound x its magnitude sum  sum |Wu| .* (|D_j|' |P_{j+1}| |D_j|)';  noise_total to bound x the sum of
 those.  The noise is the case's shared Wu (none without inputs: no price exists there)."""
+import ctypes as C
+
 import numpy as np
 
 import dlqr_reference as ref
@@ -129,3 +131,34 @@ def check_horizon(r, p, N, P, P_all, price, total, what, Q=None):
         if Q is not None:
             assert np.array_equal(P_all[N - 1], Q), "%s: P_all[N - 1] is not Q" % what
     return bound
+
+
+def refusal_call(capi, pr, N0):
+    """cclqr_policy_value_tracking through ctypes on sentinel-filled outputs, for tests/test_gpu_tracking_policy.py and tests/test_analysis_refusals_host.py.  pr: nprob,
+    mx, mu, ml, the arrays A, Bu, Bl, G [nprob][N0 - 1][...] and K [nprob][N0 - 1][mu][mx] of horizon N0 (call_arrays) and Q, R, Wu.  The call returns
+    (rc, outputs untouched, cclqr_last_error())"""
+    L = capi.lib()
+    n, mx, mu, ml = pr["nprob"], pr["mx"], pr["mu"], pr["ml"]
+    dp = C.POINTER(C.c_double)
+    d = lambda a: None if a is None else a.ctypes.data_as(dp)
+    A, Bu, Bl, G, K, Q, R, Wu = (np.ascontiguousarray(pr[k]) for k in ("A", "Bu", "Bl", "G", "K", "Q", "R", "Wu"))
+
+    def call(nlin=N0 - 1, n_gains=n, nK=N0 - 1, n_weights=1, n_noise=1, N=N0, path=0, bf16=0, nprob=n, mx_=mx, mu_=mu, A_=A, K_=K, Bl_=Bl, Wu_=Wu, Q_=Q, R_=R,
+             price_=True, total_=True):
+        P, Pall, price, tot = np.full((n, mx, mx), 7.5), np.full((n, N0, mx, mx), 7.5), np.full((n, N0), 7.5), np.full(n, 7.5)
+        o = capi.RiccatiOpts(path, bf16, 0, 0)
+        rc = L.cclqr_policy_value_tracking(C.c_int32(nprob), C.c_int32(mx_), C.c_int32(mu_), C.c_int32(ml), C.c_int32(nlin), d(A_), d(Bu), d(Bl_), d(G), C.c_int32(n_gains),
+                                           C.c_int32(nK), d(K_), C.c_int32(n_weights), d(Q_), d(R_), C.c_int32(n_noise), d(Wu_), C.c_int32(N), d(P), d(Pall),
+                                           d(price) if price_ else None, d(tot) if total_ else None, C.byref(o))
+        return rc, bool(all((x == 7.5).all() for x in (P, Pall, price, tot))), L.cclqr_last_error().decode()
+
+    return call
+
+
+def refusal_cases():
+    """what cclqr_policy_value_tracking refuses as CCLQR_EINVAL: name -> the arguments of refusal_call's call (nprob must not be 2, N0 not 3)"""
+    return dict(nprob_0=dict(nprob=0), mx_0=dict(mx_=0), N_0=dict(N=0), nlin_2=dict(nlin=2), nlin_0=dict(nlin=0), n_gains_2=dict(n_gains=2), nK_2=dict(nK=2),
+                n_weights_2=dict(n_weights=2), n_weights_0=dict(n_weights=0), n_noise_2=dict(n_noise=2), n_noise_0=dict(n_noise=0),
+                price_without_Wu=dict(Wu_=None, total_=False), total_without_Wu=dict(Wu_=None, price_=False), Wu_with_mu_0=dict(mu_=0), without_Q=dict(Q_=None),
+                without_R=dict(R_=None), A_null=dict(A_=None), K_null=dict(K_=None), Bl_null=dict(Bl_=None), path_3=dict(path=3), path_neg=dict(path=-1),
+                bf16=dict(bf16=1), too_many=dict(nprob=65536, n_gains=1))
