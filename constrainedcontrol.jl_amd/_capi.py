@@ -24,7 +24,8 @@ EXPORTS = ["cclqr_last_error", "cclqr_version", "cclqr_device_count", "cclqr_set
            "cclqr_policy_value", "cclqr_value_create_policy", "cclqr_policy_value_doubling", "cclqr_value_create_policy_doubling",
            "cclqr_riccati_doubling", "cclqr_ctrl_create_lqr_batch_doubling", "cclqr_covariance_doubling", "cclqr_value_create_covariance_doubling",
            "cclqr_covariance_tracking", "cclqr_value_create_covariance_tracking", "cclqr_policy_value_tracking", "cclqr_value_create_policy_tracking",
-           "cclqr_rollout_ensemble_ws_bytes", "cclqr_rollout_ensemble", "cclqr_rollout_quantiles_ws_bytes", "cclqr_rollout_quantiles"]
+           "cclqr_rollout_ensemble_ws_bytes", "cclqr_rollout_ensemble", "cclqr_rollout_quantiles_ws_bytes", "cclqr_rollout_quantiles",
+           "cclqr_rollout_joints", "cclqr_series_ensemble_ws_bytes", "cclqr_series_ensemble", "cclqr_series_quantiles_ws_bytes", "cclqr_series_quantiles"]
 ABI_VERSION = 202     # include/cclqr.h CCLQR_ABI_VERSION: the structs below mirror that header (verified field by field against cclqr_abi_layout at load time)
 ROLLOUT_NO_ALLOC = 1  # cclqr_rollout_opts.flags: the call may neither allocate nor synchronise (a hipGraph capture is open on the device)
 ROLLOUT_CARRY_STATUS = 4  # ... `status` is read and written: an instance lost in an earlier launch stays frozen, the others merge this launch's result into it
@@ -690,8 +691,85 @@ def rollout_quantiles(mech, ctrl, n_inst, steps, k0, traj_ptr, probs, quant_ptr,
                                         vp(ws_ptr), C.c_size_t(int(ws_bytes)), vp(stream)))
 
 
+JOINTS_RAW, JOINTS_CONTINUOUS = 0, 1      # CCLQR_JOINTS_RAW / CCLQR_JOINTS_CONTINUOUS: the mode of cclqr_rollout_joints
+SERIES_MAX_COORDS = 1024                  # CCLQR_SERIES_MAX_COORDS
+
+
+def rollout_joints(mech, n_inst, steps, k0, traj_ptr, mode, out_steps, theta_ptr, rate_ptr=0, carry_ptr=0, stream=0, first_instance=0, plants=None):
+    """cclqr_rollout_joints on device addresses (asynchronous on `stream`): the joint coordinate (and, with rate_ptr, the relative joint velocity) of every joint at
+    every row of the slab traj [n_inst][steps][nb][13] into the rows k0 - 1 .. k0 + steps - 2 of theta / rate [n_inst][out_steps][ne]; mode JOINTS_CONTINUOUS
+    carries (w_prev, turns) in carry [n_inst][ne][2] from launch to launch.  plants: a PlantsHandle -- instance i reads the vertices of plant first_instance + i"""
+    vp = lambda p: C.c_void_p(int(p)) if p else None
+    check(lib().cclqr_rollout_joints(mech.ptr, None if plants is None else plants.ptr, C.c_int64(int(n_inst)), C.c_int32(int(steps)), C.c_int32(int(k0)),
+                                     C.c_int64(int(first_instance)), vp(traj_ptr), C.c_int32(int(mode)), C.c_int64(int(out_steps)), vp(theta_ptr), vp(rate_ptr),
+                                     vp(carry_ptr), vp(stream)))
+
+
+def series_ensemble_ws_bytes(n_inst, steps, nc):
+    """cclqr_series_ensemble_ws_bytes: bytes of device workspace one cclqr_series_ensemble call of these sizes needs"""
+    out = C.c_size_t(0)
+    check(lib().cclqr_series_ensemble_ws_bytes(C.c_int64(int(n_inst)), C.c_int32(int(steps)), C.c_int32(int(nc)), C.byref(out)))
+    return int(out.value)
+
+
+def series_ensemble(n_inst, steps, nc, x_ptr, mean_ptr, m2_ptr, ws_ptr, ws_bytes, stream=0):
+    """cclqr_series_ensemble on device addresses (asynchronous on `stream`): per step the mean and the centred sum of squares of every coordinate of the series
+    x [n_inst][steps][nc] across the instances into mean / m2 [steps][nc]"""
+    vp = lambda p: C.c_void_p(int(p)) if p else None
+    check(lib().cclqr_series_ensemble(C.c_int64(int(n_inst)), C.c_int32(int(steps)), C.c_int32(int(nc)), vp(x_ptr), vp(mean_ptr), vp(m2_ptr), vp(ws_ptr),
+                                      C.c_size_t(int(ws_bytes)), vp(stream)))
+
+
+def series_quantiles_ws_bytes(n_inst, steps, nc):
+    """cclqr_series_quantiles_ws_bytes: (min_bytes, full_bytes) of device workspace -- one row of the series, all `steps` rows"""
+    lo, full = C.c_size_t(0), C.c_size_t(0)
+    check(lib().cclqr_series_quantiles_ws_bytes(C.c_int64(int(n_inst)), C.c_int32(int(steps)), C.c_int32(int(nc)), C.byref(lo), C.byref(full)))
+    return int(lo.value), int(full.value)
+
+
+def series_quantiles(n_inst, steps, nc, x_ptr, probs, quant_ptr, finite_ptr, ws_ptr, ws_bytes, stream=0):
+    """cclqr_series_quantiles on device addresses (asynchronous on `stream`): per step and coordinate of the series x [n_inst][steps][nc] the quantiles of its finite
+    values across the instances at the probabilities `probs` (host numbers) into quant [steps][len(probs)][nc], and their number into finite [steps][nc] (int32; 0:
+    not wanted)"""
+    vp = lambda p: C.c_void_p(int(p)) if p else None
+    pr = f64(list(probs)).reshape(-1)
+    check(lib().cclqr_series_quantiles(C.c_int64(int(n_inst)), C.c_int32(int(steps)), C.c_int32(int(nc)), vp(x_ptr), C.c_int32(len(pr)), _d(pr) if len(pr) else None,
+                                       vp(quant_ptr), vp(finite_ptr), vp(ws_ptr), C.c_size_t(int(ws_bytes)), vp(stream)))
+
+
+def _joint_series_results(td, stream, n, steps, ne, continuous, rates, keep, probs, jth, jrt):
+    """the statistics of the finished joint series across the instances: one cclqr_series_ensemble and, with probs, one cclqr_series_quantiles over
+    [n][steps][ne] (rates: [n][steps][2 ne] = theta, then the rate).  Returns the dict JointSeries is built from"""
+    import torch
+    nc = 2 * ne if rates else ne
+    x = torch.cat((jth, jrt), dim=2).contiguous() if rates else jth
+    mean = torch.empty((steps, nc), dtype=torch.float64, device=td)
+    m2 = torch.empty((steps, nc), dtype=torch.float64, device=td)
+    wb = series_ensemble_ws_bytes(n, steps, nc)
+    ws = torch.empty(wb // 8 + 1, dtype=torch.float64, device=td)
+    series_ensemble(n, steps, nc, x.data_ptr(), mean.data_ptr(), m2.data_ptr(), ws.data_ptr(), wb, stream)
+    out = dict(count=n, continuous=bool(continuous), mean=None, M2=None, rate_mean=None, rate_M2=None, probs=None, quantiles=None, finite_count=None, theta=None, rate=None)
+    if len(probs):
+        quant = torch.empty((steps, len(probs), nc), dtype=torch.float64, device=td)
+        fin = torch.empty((steps, nc), dtype=torch.int32, device=td)
+        qb = series_quantiles_ws_bytes(n, steps, nc)[1]
+        qws = torch.empty(qb // 8 + 1, dtype=torch.float64, device=td)
+        series_quantiles(n, steps, nc, x.data_ptr(), probs, quant.data_ptr(), fin.data_ptr(), qws.data_ptr(), qb, stream)
+    torch.cuda.current_stream().synchronize()
+    mean, m2 = mean.cpu().numpy(), m2.cpu().numpy()
+    out["mean"], out["M2"] = mean[:, :ne], m2[:, :ne]
+    if rates:
+        out["rate_mean"], out["rate_M2"] = mean[:, ne:], m2[:, ne:]
+    if len(probs):
+        out["probs"], out["quantiles"], out["finite_count"] = tuple(float(p) for p in probs), quant.cpu().numpy(), fin.cpu().numpy()
+    if keep:
+        out["theta"] = jth.cpu().numpy()
+        out["rate"] = jrt.cpu().numpy() if rates else None
+    return out
+
+
 def rollout_scored(mech, ctrl, score, z0, steps, chunk_steps, noise=None, first_instance=0, plants=None, newton_mode=0, newton_eps_alone=0.0, flags=0, traj_out=None,
-                   ensemble=None):
+                   ensemble=None, joints=None):
     """A horizon rolled out AND scored on the device without its trajectory ever existing: ceil(steps / chunk_steps) launches of cclqr_rollout_ex (plants:
     cclqr_rollout_plants) into ONE slab of chunk_steps rows, each followed on the same stream by cclqr_rollout_score.  The state, the multipliers, the status
     (ROLLOUT_CARRY_STATUS), the PID state and the noise column travel from launch to launch, so the result is bitwise that of one launch.
@@ -699,8 +777,12 @@ def rollout_scored(mech, ctrl, score, z0, steps, chunk_steps, noise=None, first_
     score: a ScoreHandle, or None = no score pass.  ensemble: None, or (mu, cov_rows) -- cclqr_rollout_ensemble runs behind every launch on the same slab, and the
     0-based rows of the horizon in cov_rows (row j = step j + 1) get their co-moment matrix, each from the chunk that holds it --, or (mu, cov_rows, probs):
     cclqr_rollout_quantiles runs behind the ensemble call on the same slab, with a workspace of as many rows as the chunk has.
+    joints: None (nothing changes, nothing is allocated), or (continuous, rates, keep, probs) -- behind every launch cclqr_rollout_joints runs on the same slab and
+    stream into whole-horizon device arrays [n_inst][steps][ne], the carry buffer travelling from chunk to chunk; after the last chunk one cclqr_series_ensemble and,
+    with probs, one cclqr_series_quantiles reduce them across the instances.
     Returns (zT, status, score [n_inst][SCORE_LEN] or None), with ensemble a fourth element (mean [steps][12 nb + mu], M2 the same, {row: C [12 nb][12 nb]}), which
-    the three-element form extends by (quant [steps][len(probs)][12 nb + mu], finite [steps][12 nb + mu])."""
+    the three-element form extends by (quant [steps][len(probs)][12 nb + mu], finite [steps][12 nb + mu]); with joints a last element, the dict of
+    _joint_series_results."""
     import torch
     nb, ne = mech.tables.nb, mech.tables.ne
     z0 = f64(z0).reshape(-1, nb, 13)
@@ -717,6 +799,13 @@ def rollout_scored(mech, ctrl, score, z0, steps, chunk_steps, noise=None, first_
         probs = quantile_probs(ensemble[2]) if len(ensemble) > 2 else ()
         if len(probs) and n > QUANTILE_MAX_INST:
             raise ValueError("quantiles are taken over at most %d instances per call (got %d)" % (QUANTILE_MAX_INST, n))
+    if joints is not None:        # (before anything touches the device)
+        jcont, jrates, jkeep = bool(joints[0]), bool(joints[1]), bool(joints[2])
+        jprobs = quantile_probs(joints[3])
+        if len(jprobs) and n > QUANTILE_MAX_INST:
+            raise ValueError("quantiles are taken over at most %d instances per call (got %d)" % (QUANTILE_MAX_INST, n))
+        if (2 * ne if jrates else ne) > SERIES_MAX_COORDS:
+            raise ValueError("a series has at most %d coordinates" % SERIES_MAX_COORDS)
     td = torch.device("cuda", torch.cuda.current_device())
     z = torch.from_numpy(z0).to(td)
     zn = torch.empty_like(z)
@@ -740,6 +829,10 @@ def rollout_scored(mech, ctrl, score, z0, steps, chunk_steps, noise=None, first_
             efin = torch.empty((steps, nx), dtype=torch.int32, device=td)
             qws_bytes = rollout_quantiles_ws_bytes(mech, mu, n, rows)[1]
             qws = torch.empty(qws_bytes // 8 + 1, dtype=torch.float64, device=td)
+    if joints is not None:
+        jth = torch.empty((n, steps, ne), dtype=torch.float64, device=td)
+        jrt = torch.empty((n, steps, ne), dtype=torch.float64, device=td) if jrates else None
+        jcarry = torch.zeros((n, ne, 2), dtype=torch.float64, device=td) if jcont else None
     for ci, (k0, s) in enumerate(plan):
         # the noise array is indexed by the absolute step k - 1: its base stays where it is whatever k0 is
         rollout_dev(mech, ctrl, n, s, k0, z.data_ptr(), lam.data_ptr(), 0 if dnoise is None else dnoise.data_ptr(), steps, slab.data_ptr(), zn.data_ptr(),
@@ -754,18 +847,22 @@ def rollout_scored(mech, ctrl, score, z0, steps, chunk_steps, noise=None, first_
             if len(probs):
                 rollout_quantiles(mech, ctrl, n, s, k0, slab.data_ptr(), probs, equant[k0 - 1:].data_ptr(), efin[k0 - 1:].data_ptr(), qws.data_ptr(), qws_bytes,
                                   stream=stream, first_instance=first_instance)
+        if joints is not None:
+            rollout_joints(mech, n, s, k0, slab.data_ptr(), JOINTS_CONTINUOUS if jcont else JOINTS_RAW, steps, jth.data_ptr(), 0 if jrt is None else jrt.data_ptr(),
+                           0 if jcarry is None else jcarry.data_ptr(), stream, first_instance=first_instance, plants=plants)
         if traj_out is not None:      # (a launch of s < rows steps fills the slab as [n][s][nb][13] from its base)
             traj_out[:, k0 - 1:k0 - 1 + s] = slab.reshape(-1)[:n * s * nb * 13].reshape(n, s, nb, 13).cpu().numpy()
         z, zn = zn, z
+    jres = () if joints is None else (_joint_series_results(td, stream, n, steps, ne, jcont, jrates, jkeep, jprobs, jth, jrt),)
     torch.cuda.current_stream().synchronize()
     out = (z.cpu().numpy(), st.cpu().numpy(), None if sc is None else sc.cpu().numpy())
     if ensemble is None:
-        return out
+        return out + jres
     covs = ecov.cpu().numpy()
     stats = (emean.cpu().numpy(), em2.cpu().numpy(), {j: covs[q] for q, j in enumerate(cov_rows)})
     if len(probs):
         stats += (equant.cpu().numpy(), efin.cpu().numpy())
-    return out + (stats,)
+    return out + (stats,) + jres
 
 
 def linearize(mech, zd, ctrl_joint, Fd=None, plants=None, first_plant=0):

@@ -13,6 +13,9 @@ static_assert(CCLQR_SCORE_LEN == CCLQR_SCORE_LEN_, "include/cclqr.h and cclqr_sc
 #include "cclqr_value.h"
 #include "cclqr_ensemble.h"
 #include "cclqr_quantiles.h"
+#include "cclqr_joints.h"
+static_assert(CCLQR_JOINTS_RAW == CCLQR_JOINTS_RAW_ && CCLQR_JOINTS_CONTINUOUS == CCLQR_JOINTS_CONTINUOUS_ && CCLQR_SERIES_MAX_COORDS == CCLQR_SERIES_MAX_COORDS_,
+              "include/cclqr.h and cclqr_joints.h disagree on the joint modes or the coordinates of a series");
 #include <math.h>
 #include <stdio.h>
 #include <string.h>
@@ -1342,6 +1345,98 @@ extern "C" int cclqr_rollout_quantiles(const cclqr_mech* m, const cclqr_ctrl* c,
     for (int r0 = 0; r0 < steps; r0 += block) {
         a.row0 = r0; a.nrows = steps - r0 < block ? steps - r0 : block;
         HIPCHK(launch_quantiles(a, (hipStream_t)stream));
+    }
+    return CCLQR_OK;
+}
+
+// ---- the joint coordinates of a slab (joints.hip).  Nothing is allocated, copied or synchronised
+extern "C" int cclqr_rollout_joints(const cclqr_mech* m, const cclqr_plants* plants, int64_t n_inst, int32_t steps, int32_t k0, int64_t first_instance, const double* traj,
+                                    int32_t mode, int64_t out_steps, double* theta, double* rate, double* carry, void* stream) {
+    if (!m) return fail(CCLQR_EINVAL, "null argument");
+    TRY(check_device(m));
+    if (n_inst < 1 || steps < 1 || k0 < 1)
+        return fail(CCLQR_EINVAL, "need n_inst >= 1, steps >= 1 and k0 >= 1 (got n_inst = " + std::to_string(n_inst) + ", steps = " + std::to_string(steps) + ", k0 = " + std::to_string(k0) + ")");
+    if (first_instance < 0) return fail(CCLQR_EINVAL, "negative first_instance");
+    if (out_steps < (int64_t)k0 + steps - 1)
+        return fail(CCLQR_EINVAL, "out_steps = " + std::to_string(out_steps) + " does not hold the steps " + std::to_string(k0) + " .. " + std::to_string((int64_t)k0 + steps - 1) + " of this launch");
+    if (mode != CCLQR_JOINTS_RAW && mode != CCLQR_JOINTS_CONTINUOUS) return fail(CCLQR_EINVAL, "mode = " + std::to_string(mode) + " is neither CCLQR_JOINTS_RAW nor CCLQR_JOINTS_CONTINUOUS");
+    if (mode == CCLQR_JOINTS_CONTINUOUS && !carry) return fail(CCLQR_EINVAL, "CCLQR_JOINTS_CONTINUOUS needs carry_dev [n_inst][ne][2]: the turn count travels in it from launch to launch");
+    if (!traj || !theta) return fail(CCLQR_EINVAL, "null traj_dev or theta_dev");
+    if (plants && (plants->nb != m->nb || plants->device != m->device)) return fail(CCLQR_EINVAL, "the plants were created for another mechanism or device");
+    if (plants && m->shape.family == RolloutFamily::Loop) return fail(CCLQR_EINVAL, "the plants were created for another mechanism: a closed-loop mechanism takes none");
+    TRY(plants_check_range(m, plants, first_instance, n_inst, "instances", "launch"));
+    JointsArgs a;
+    memset(&a, 0, sizeof(a));
+    a.M = m->dev; a.plants = plants ? plants->dev : nullptr; a.plant_off = plants ? first_instance - plants->first_index : 0;
+    a.nb = m->nb; a.ne = m->nj; a.loop = m->host.loop; a.n_inst = n_inst; a.steps = steps; a.k0 = k0; a.traj = traj; a.mode = mode; a.out_steps = out_steps;
+    a.theta = theta; a.rate = rate; a.carry = mode == CCLQR_JOINTS_CONTINUOUS ? carry : nullptr;
+    HIPCHK(launch_joints(a, (hipStream_t)stream));
+    return CCLQR_OK;
+}
+
+// ---- the statistics of any per-instance series across its instances (joints.hip in front of ens_finish_kernel / ens_select_kernel).  Nothing is allocated, copied
+// or synchronised; the refusals and the workspace block rule are those of cclqr_rollout_ensemble / cclqr_rollout_quantiles
+static int series_sizes_ok(int64_t n_inst, int32_t steps, int32_t nc) {
+    if (n_inst < 1) return fail(CCLQR_EINVAL, "n_inst = " + std::to_string(n_inst) + ": an ensemble holds at least one instance");
+    if (steps < 1) return fail(CCLQR_EINVAL, "need steps >= 1 (got " + std::to_string(steps) + ")");
+    if (nc < 1 || nc > CCLQR_SERIES_MAX_COORDS) return fail(CCLQR_EINVAL, "nc = " + std::to_string(nc) + ": a series has 1 .. CCLQR_SERIES_MAX_COORDS = " + std::to_string(CCLQR_SERIES_MAX_COORDS) + " coordinates");
+    if (ens_tiles(n_inst) * steps > 0x7fffffffLL) return fail(CCLQR_EINVAL, "n_inst x steps exceeds one launch: call with fewer steps");
+    return CCLQR_OK;
+}
+static int series_quantile_sizes_ok(int64_t n_inst, int32_t steps, int32_t nc) {
+    TRY(series_sizes_ok(n_inst, steps, nc));
+    if (n_inst > CCLQR_QUANTILE_MAX_INST)
+        return fail(CCLQR_EUNSUPPORTED, "n_inst = " + std::to_string(n_inst) + ": one call sorts at most CCLQR_QUANTILE_MAX_INST = " + std::to_string(CCLQR_QUANTILE_MAX_INST) + " instances");
+    return CCLQR_OK;
+}
+extern "C" int cclqr_series_ensemble_ws_bytes(int64_t n_inst, int32_t steps, int32_t nc, size_t* bytes) {
+    if (!bytes) return fail(CCLQR_EINVAL, "null argument");
+    TRY(series_sizes_ok(n_inst, steps, nc));
+    *bytes = sizeof(double) * ser_ws_doubles(n_inst, steps, nc);
+    return CCLQR_OK;
+}
+extern "C" int cclqr_series_ensemble(int64_t n_inst, int32_t steps, int32_t nc, const double* x, double* mean, double* m2, void* ws, size_t ws_bytes, void* stream) {
+    TRY(series_sizes_ok(n_inst, steps, nc));
+    if (!x || !mean || !m2) return fail(CCLQR_EINVAL, "null argument");
+    const size_t need = sizeof(double) * ser_ws_doubles(n_inst, steps, nc);
+    if (!ws) return fail(CCLQR_EINVAL, "null workspace: cclqr_series_ensemble_ws_bytes says how large it must be (" + std::to_string(need) + " bytes)");
+    if (ws_bytes < need) return fail(CCLQR_EINVAL, "workspace too small: " + std::to_string(ws_bytes) + " bytes given, " + std::to_string(need) + " needed (cclqr_series_ensemble_ws_bytes)");
+    if (((uintptr_t)ws & 7) != 0) return fail(CCLQR_EINVAL, "the workspace is not 8-byte aligned");
+    HIPCHK(launch_series_moments(n_inst, steps, nc, x, (double*)ws, (hipStream_t)stream));
+    HIPCHK(launch_ensemble_finish((const double*)ws, n_inst, steps, nc, mean, m2, (hipStream_t)stream));
+    return CCLQR_OK;
+}
+extern "C" int cclqr_series_quantiles_ws_bytes(int64_t n_inst, int32_t steps, int32_t nc, size_t* min_bytes, size_t* full_bytes) {
+    if (!min_bytes || !full_bytes) return fail(CCLQR_EINVAL, "null argument");
+    TRY(series_quantile_sizes_ok(n_inst, steps, nc));
+    *min_bytes = sizeof(double) * ser_row_doubles(n_inst, nc);
+    *full_bytes = *min_bytes * (size_t)steps;
+    return CCLQR_OK;
+}
+extern "C" int cclqr_series_quantiles(int64_t n_inst, int32_t steps, int32_t nc, const double* x, int32_t n_prob, const double* prob, double* quant, int32_t* finite,
+                                      void* ws, size_t ws_bytes, void* stream) {
+    TRY(series_sizes_ok(n_inst, steps, nc));
+    if (!x || !prob || !quant) return fail(CCLQR_EINVAL, "null argument");
+    if (n_prob < 1 || n_prob > CCLQR_QUANTILE_MAX_PROBS)
+        return fail(CCLQR_EINVAL, "n_prob = " + std::to_string(n_prob) + ": one call takes 1 .. " + std::to_string(CCLQR_QUANTILE_MAX_PROBS) + " probabilities");
+    for (int j = 0; j < n_prob; j++)
+        if (!(prob[j] >= 0.0 && prob[j] <= 1.0)) return fail(CCLQR_EINVAL, "prob[" + std::to_string(j) + "] = " + std::to_string(prob[j]) + " is not a probability in [0, 1]");
+    TRY(series_quantile_sizes_ok(n_inst, steps, nc));
+    const size_t row_bytes = sizeof(double) * ser_row_doubles(n_inst, nc);
+    if (!ws) return fail(CCLQR_EINVAL, "null workspace: cclqr_series_quantiles_ws_bytes says how large it must be (at least " + std::to_string(row_bytes) + " bytes)");
+    if (ws_bytes < row_bytes) return fail(CCLQR_EINVAL, "workspace too small: " + std::to_string(ws_bytes) + " bytes given, " + std::to_string(row_bytes) + " needed for one row (cclqr_series_quantiles_ws_bytes)");
+    if (((uintptr_t)ws & 7) != 0) return fail(CCLQR_EINVAL, "the workspace is not 8-byte aligned");
+    QntArgs a;      // (the select kernel counts its coordinates as 12 nb + mu: nb = 0, mu = nc)
+    memset(&a, 0, sizeof(a));
+    a.nb = 0; a.mu = nc; a.n_inst = n_inst; a.n_pad = qnt_pad(n_inst); a.steps = steps; a.k0 = 1;
+    a.xt = (double*)ws; a.n_prob = n_prob; a.quant = quant; a.finite = finite;
+    for (int j = 0; j < n_prob; j++) a.prob[j] = prob[j];
+    const size_t fit = ws_bytes / row_bytes;
+    const int block = (int)(fit < 65535 ? fit : 65535);      // (rows are the y extent of the select kernel's grid and the z extent of the stage kernel's)
+    for (int r0 = 0; r0 < steps; r0 += block) {
+        a.row0 = r0; a.nrows = steps - r0 < block ? steps - r0 : block;
+        HIPCHK(launch_series_stage(n_inst, steps, nc, x, a.row0, a.nrows, a.xt, (hipStream_t)stream));
+        HIPCHK(launch_quantile_select(a, (hipStream_t)stream));
     }
     return CCLQR_OK;
 }

@@ -115,6 +115,7 @@ HD size_t ens_ws_doubles(int nb, int mu, long long n_inst, int steps, int n_cov)
 }
 
 hipError_t launch_ensemble(const EnsArgs& a, double* mean, double* m2, hipStream_t stream);
+hipError_t launch_ensemble_finish(const double* part, long long n_inst, int steps, int nx, double* mean, double* m2, hipStream_t stream);
 hipError_t launch_ensemble_cov(const EnsCovArgs& a, int n_cov, hipStream_t stream);
 
 }  // namespace cclqr

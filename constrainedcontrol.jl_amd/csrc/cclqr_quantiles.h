@@ -108,5 +108,6 @@ HD double qnt_quantile(const unsigned long long* keys, int cnt, double p) {
 }
 
 hipError_t launch_quantiles(const QntArgs& a, hipStream_t stream);
+hipError_t launch_quantile_select(const QntArgs& a, hipStream_t stream);
 
 }  // namespace cclqr

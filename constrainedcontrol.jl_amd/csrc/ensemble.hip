@@ -185,6 +185,11 @@ __global__ __launch_bounds__(TILE_THREADS) void ens_cov_finish_kernel(EnsCovArgs
     }
 }
 
+// ens_finish_kernel over `steps` rows of partials [steps][ntiles][2][nx]: launch_ensemble's second half, and the back end of cclqr_series_ensemble (joints.hip)
+hipError_t launch_ensemble_finish(const double* part, long long n_inst, int steps, int nx, double* mean, double* m2, hipStream_t stream) {
+    return launch_lds<false>(ens_finish_kernel, dim3((unsigned)steps), dim3(TILE_THREADS), 0, stream, part, ens_tiles(n_inst), n_inst, nx, mean, m2);
+}
+
 hipError_t launch_ensemble(const EnsArgs& a, double* mean, double* m2, hipStream_t stream) {
     const int G = score_group_lanes(a.nb);
     const long long ntiles = ens_tiles(a.n_inst);
@@ -198,7 +203,7 @@ hipError_t launch_ensemble(const EnsArgs& a, double* mean, double* m2, hipStream
         default: e = launch_lds(ens_moments_kernel<64>, grid, block, lds, stream, a); break;
     }
     if (e != hipSuccess) return e;
-    return launch_lds<false>(ens_finish_kernel, dim3((unsigned)a.steps), dim3(TILE_THREADS), 0, stream, (const double*)a.part, ntiles, a.n_inst, ens_coords(a.nb, a.mu), mean, m2);
+    return launch_ensemble_finish(a.part, a.n_inst, a.steps, ens_coords(a.nb, a.mu), mean, m2, stream);
 }
 
 hipError_t launch_ensemble_cov(const EnsCovArgs& a, int n_cov, hipStream_t stream) {

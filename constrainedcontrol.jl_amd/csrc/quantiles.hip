@@ -139,8 +139,15 @@ __global__ __launch_bounds__(QNT_MAX_THREADS) void ens_select_kernel(QntArgs a, 
     }
 }
 
+// ens_select_kernel over the rows a.row0 .. of a.xt [nrows][ens_coords(a.nb, a.mu)][n_pad]: launch_quantiles' second half, and the back end of cclqr_series_quantiles
+// (joints.hip; nb = 0, mu = the series' coordinates).  Reads n_inst, n_pad, nb, mu, row0, nrows, xt, n_prob, prob, quant, finite of a
+hipError_t launch_quantile_select(const QntArgs& a, hipStream_t stream) {
+    const int n2 = qnt_pow2(a.n_inst), nx = ens_coords(a.nb, a.mu);
+    return launch_lds(ens_select_kernel, dim3((unsigned)nx, (unsigned)a.nrows), dim3((unsigned)qnt_select_threads(n2)), sizeof(unsigned long long) * (size_t)n2, stream, a, n2);
+}
+
 hipError_t launch_quantiles(const QntArgs& a, hipStream_t stream) {
-    const int G = score_group_lanes(a.nb), nx = ens_coords(a.nb, a.mu);
+    const int G = score_group_lanes(a.nb);
     const dim3 grid((unsigned)(ens_tiles(a.n_inst) * a.nrows)), block(64 * ENS_WAVES);
     const size_t lds = qnt_stage_lds_bytes(a.nb, a.mu, a.W);
     hipError_t e;
@@ -151,8 +158,7 @@ hipError_t launch_quantiles(const QntArgs& a, hipStream_t stream) {
         default: e = launch_lds(ens_stage_kernel<64>, grid, block, lds, stream, a); break;
     }
     if (e != hipSuccess) return e;
-    const int n2 = qnt_pow2(a.n_inst);
-    return launch_lds(ens_select_kernel, dim3((unsigned)nx, (unsigned)a.nrows), dim3((unsigned)qnt_select_threads(n2)), sizeof(unsigned long long) * (size_t)n2, stream, a, n2);
+    return launch_quantile_select(a, stream);
 }
 
 }  // namespace cclqr

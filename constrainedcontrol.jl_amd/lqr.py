@@ -817,6 +817,7 @@ class Storage:
         self.zT = zT
         self.score = None          # [n_inst][4] = Jx, Ju, peak, last_out of simulate(..., score=)
         self.ensemble = None       # EnsembleStats of simulate(..., ensemble=): the batch across its instances, per step
+        self.joints = None         # JointSeries of simulate(..., joints=): the run in joint coordinates, and its statistics across the instances
 
     def instance(self, n):
         one = Storage(self.steps, self.nb, 1, self.z[n:n + 1], None if self.status is None else self.status[n:n + 1],
@@ -1182,6 +1183,72 @@ class EnsembleStats:
         return EnsembleStats(0, np.zeros((steps, mx)), np.zeros((steps, mx)), np.zeros((steps, mu)), np.zeros((steps, mu)), {int(j): np.zeros((mx, mx)) for j in cov_knots})
 
 
+class Joints:
+    """A run in joint coordinates: per instance, step and joint the minimal coordinate of pid.jl:43-57 (the angle about / the offset along the joint axis, the number
+    PID regulates) and the relative joint velocity the friction law of examples/trackingLQR_triple_cartpole.jl:98-101 acts on, formed on the device from the
+    rollout's own states (cclqr_rollout_joints), and their statistics across the instances (cclqr_series_ensemble, cclqr_series_quantiles).
+    simulate(..., joints=Joints(mechanism)) returns a Storage with .joints, a JointSeries, in the order of mechanism.eqconstraints.
+    continuous: a revolute's angle is made continuous in time per instance (whole turns are counted from step 1), so that its mean, spread and median across
+    instances mean something after a pendulum has gone over the top; False: the raw angle in [-2π, 2π] that PID sees.  rates=False: no velocities.  keep=False: only
+    the statistics come back.  quantiles=(p, ...): up to 16 probabilities in [0, 1] (at most 16384 instances).  A FixedOrientation constraint has no coordinate: 0."""
+
+    def __init__(self, mechanism, continuous=True, rates=True, keep=True, quantiles=()):
+        if not isinstance(mechanism, Mechanism):
+            raise TypeError("Joints(mechanism, continuous=True, rates=True, keep=True, quantiles=())")
+        for name, v in (("continuous", continuous), ("rates", rates), ("keep", keep)):
+            if not isinstance(v, (bool, np.bool_)):
+                raise TypeError("Joints(%s=) takes True or False (got %r)" % (name, v))
+        self.mechanism = mechanism
+        self.continuous, self.rates, self.keep = bool(continuous), bool(rates), bool(keep)
+        self.quantiles = tuple(float(p) for p in _capi.quantile_probs(quantiles))
+
+
+class JointSeries:
+    """The joint coordinates of `count` instances at every step of a run, joints in the order of mechanism.eqconstraints: theta, rate [n][steps][ne] (None with
+    keep=False; rate None with rates=False), their statistics across the instances mean, M2, rate_mean, rate_M2 [steps][ne] (std about the ensemble mean), and with
+    Joints(quantiles=): quantile(p), rate_quantile(p) [steps][ne] for the probabilities that were asked for (median, min, max for 0.5, 0, 1) and finite_count
+    [steps][ne or 2 ne], the number of finite values each was taken over."""
+
+    def __init__(self, count, mean, M2, rate_mean=None, rate_M2=None, theta=None, rate=None, *, continuous=True, probs=None, quantiles=None, finite_count=None):
+        arr = lambda a: None if a is None else np.asarray(a, dtype=np.float64)
+        self.count, self.continuous = int(count), bool(continuous)
+        self.mean, self.M2, self.rate_mean, self.rate_M2, self.theta, self.rate = arr(mean), arr(M2), arr(rate_mean), arr(rate_M2), arr(theta), arr(rate)
+        self.probs = None if probs is None else tuple(float(p) for p in probs)
+        self._quantiles = None if probs is None else np.asarray(quantiles, dtype=np.float64)
+        self.finite_count = None if probs is None else np.asarray(finite_count, dtype=np.int32)
+
+    def var(self, ddof=0):
+        return self.M2 / (self.count - ddof)
+
+    def rate_var(self, ddof=0):
+        if self.rate_M2 is None:
+            raise KeyError("no rates were asked for: Joints(rates=False)")
+        return self.rate_M2 / (self.count - ddof)
+
+    std = property(lambda self: np.sqrt(self.var()))
+    rate_std = property(lambda self: np.sqrt(self.rate_var()))
+
+    def _quantile_rows(self, p):
+        asked = () if self.probs is None else self.probs
+        if float(p) not in asked:
+            raise KeyError("quantile %r was not asked for: Joints(quantiles=%s)" % (p, list(asked)))
+        return self._quantiles[:, asked.index(float(p))]
+
+    def quantile(self, p):
+        """the quantile at probability p of every joint coordinate across the instances, [steps][ne]"""
+        return self._quantile_rows(p)[:, :self.mean.shape[1]]
+
+    def rate_quantile(self, p):
+        """... of every joint rate, [steps][ne]"""
+        if self.rate_mean is None:
+            raise KeyError("no rates were asked for: Joints(rates=False)")
+        return self._quantile_rows(p)[:, self.mean.shape[1]:]
+
+    median = property(lambda self: self.quantile(0.5))
+    min = property(lambda self: self.quantile(0.0))
+    max = property(lambda self: self.quantile(1.0))
+
+
 class OpenLoop(Controller):
     """control!(mechanism, k) = setForce!(mechanism, joint, [U[k]])  — the open-loop closure of
     examples/trackingLQR_triple_cartpole.jl:46-48 as a table: U[k][i] for controlled joints eqcids."""
@@ -1525,7 +1592,7 @@ def _simulate_device_closure(mechanism, steps, controller, record, z0):
 
 
 def simulate(mechanism, tend_or_storage, controller, record=True, z0=None, fric=None, noise=None, noise_scale=None, noise_seed=None,
-             first_instance=0, plants=None, score=None, chunk_steps=None, ensemble=None):
+             first_instance=0, plants=None, score=None, chunk_steps=None, ensemble=None, joints=None):
     """simulate!(mechanism, tend::Real | storage::Storage, controller; record)  -> Storage
 
     z0 [n_inst][nb][13]: batch of initial states (default: the mechanism's current body states, one instance).
@@ -1543,6 +1610,9 @@ def simulate(mechanism, tend_or_storage, controller, record=True, z0=None, fric=
     carries .ensemble, an EnsembleStats: per step the mean and the spread of every coordinate of Δz and Δu across the instances, and the covariance of Δz at the
     Ensemble's cov_knots -- and, with Ensemble(quantiles=), the quantiles of every coordinate at every step (at most 16384 instances).  Any chunk_steps, record or
     not, gives the same bits.  For the fused laws.
+    joints: a Joints -- the same chunk loop (alone, or with score= / ensemble= on the same slab) with cclqr_rollout_joints behind every launch; the returned Storage
+    carries .joints, a JointSeries: every joint's coordinate and rate per instance and step, and their mean, spread and quantiles across the instances.  Any
+    chunk_steps, record or not, gives the same bits.  For the fused laws.
     After the call the mechanism's bodies hold instance 0's final state (simulate! mutates the mechanism)."""
     if isinstance(controller, PolicyValue):
         raise TypeError("a PolicyValue is not a Controller: simulate rolls out the controller it evaluates (PolicyValue.controller)")
@@ -1560,7 +1630,7 @@ def simulate(mechanism, tend_or_storage, controller, record=True, z0=None, fric=
         steps = int(math.ceil(tend_or_storage / mechanism.Δt))     # steps = 1:ceil(tend/Δt)
     nb = len(mechanism.bodies)
     z0 = mechanism.state()[None] if z0 is None else np.asarray(z0, dtype=np.float64).reshape(-1, nb, 13)
-    if score is None and ensemble is None and chunk_steps is not None:
+    if score is None and ensemble is None and joints is None and chunk_steps is not None:
         raise ValueError("chunk_steps is an option of score= and ensemble=")
     if score is not None:
         if not isinstance(score, Score):
@@ -1585,7 +1655,19 @@ def simulate(mechanism, tend_or_storage, controller, record=True, z0=None, fric=
         if ensemble.quantiles and z0.shape[0] > _capi.QUANTILE_MAX_INST:
             raise ValueError("quantiles= are taken over at most %d instances per run (got %d): the moments of shards merge, their order statistics do not"
                              % (_capi.QUANTILE_MAX_INST, z0.shape[0]))
-    if score is not None or ensemble is not None:
+    if joints is not None:
+        if not isinstance(joints, Joints):
+            raise TypeError("joints= takes a Joints(mechanism, continuous=True, rates=True, keep=True, quantiles=())")
+        if getattr(controller, "controlfunction", None) is not None:
+            raise ValueError("joints= with a custom controlfunction is not supported: the joint pass runs behind the launches of the fused laws")
+        if joints.mechanism is not mechanism:
+            raise ValueError("the Joints was made for another mechanism")
+        if steps < 1:
+            raise ValueError("joints= needs at least one step")
+        if joints.quantiles and z0.shape[0] > _capi.QUANTILE_MAX_INST:
+            raise ValueError("quantiles= are taken over at most %d instances per run (got %d): the moments of shards merge, their order statistics do not"
+                             % (_capi.QUANTILE_MAX_INST, z0.shape[0]))
+    if score is not None or ensemble is not None or joints is not None:
         if chunk_steps is None:
             chunk_steps = _capi.default_chunk_steps(z0.shape[0], nb, steps)
         if int(chunk_steps) < 1:
@@ -1600,16 +1682,22 @@ def simulate(mechanism, tend_or_storage, controller, record=True, z0=None, fric=
     if (noise is not None or noise_seed is not None) and noise_scale is None:
         noise_scale = 1.0
     ph = None if plants is None else plants.handle(dev)
-    scores = stats = None
-    if score is not None or ensemble is not None:
+    scores = stats = series = None
+    if score is not None or ensemble is not None or joints is not None:
         ctrl = controller._ctrl_handle(dev, fric=fric, noise_scale=0.0 if noise_scale is None else noise_scale, noise_seed=noise_seed)
         sh = None
         try:
             sh = None if score is None else score._handle(dev)
             traj = np.zeros((z0.shape[0], steps, nb, 13)) if record else None
             ens = None if ensemble is None else ((ctrl.mu, ensemble.cov_knots) + ((ensemble.quantiles,) if ensemble.quantiles else ()))
-            got = _capi.rollout_scored(dev, ctrl, sh, z0, steps, int(chunk_steps), noise=noise, first_instance=first_instance, plants=ph, traj_out=traj, ensemble=ens)
+            jnt = None if joints is None else (joints.continuous, joints.rates, joints.keep, joints.quantiles)
+            got = _capi.rollout_scored(dev, ctrl, sh, z0, steps, int(chunk_steps), noise=noise, first_instance=first_instance, plants=ph, traj_out=traj, ensemble=ens,
+                                       **({} if jnt is None else dict(joints=jnt)))
             zT, status, scores = got[:3]
+            if joints is not None:
+                j = got[-1]
+                series = JointSeries(j["count"], j["mean"], j["M2"], j["rate_mean"], j["rate_M2"], j["theta"], j["rate"], continuous=j["continuous"],
+                                     **(dict(probs=j["probs"], quantiles=j["quantiles"], finite_count=j["finite_count"]) if joints.quantiles else {}))
             if ensemble is not None:
                 emean, eM2, eC = got[3][:3]
                 more = dict(probs=ensemble.quantiles, quantiles=got[3][3], finite_count=got[3][4]) if ensemble.quantiles else {}
@@ -1637,10 +1725,12 @@ def simulate(mechanism, tend_or_storage, controller, record=True, z0=None, fric=
         tend_or_storage.status, tend_or_storage.zT = status, zT
         tend_or_storage.score = scores
         tend_or_storage.ensemble = stats
+        tend_or_storage.joints = series
         return tend_or_storage
     out = Storage(steps, nb, z0.shape[0], traj if record else np.zeros((z0.shape[0], 0, nb, 13)), status, zT)
     out.score = scores
     out.ensemble = stats
+    out.joints = series
     return out
 
 

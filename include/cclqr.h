@@ -64,7 +64,9 @@ extern "C" {
  * Still 202 (additive, no struct changed): the statistics of a slab ACROSS its instances at every step -- cclqr_rollout_ensemble_ws_bytes, cclqr_rollout_ensemble; looked up
  * the same way.  cclqr_rollout_score is unchanged.
  * Still 202 (additive, no struct changed): the quantiles of a slab ACROSS its instances at every step -- cclqr_rollout_quantiles_ws_bytes, cclqr_rollout_quantiles; looked up
- * the same way.  cclqr_rollout_ensemble is unchanged. */
+ * the same way.  cclqr_rollout_ensemble is unchanged.
+ * Still 202 (additive, no struct changed): the joint coordinates of a slab and the statistics of any per-instance series -- cclqr_rollout_joints,
+ * cclqr_series_ensemble_ws_bytes, cclqr_series_ensemble, cclqr_series_quantiles_ws_bytes, cclqr_series_quantiles; looked up the same way. */
 #define CCLQR_ABI_VERSION 202
 
 #define CCLQR_REVOLUTE 0      /* EqualityConstraint(Revolute(a, b, axis; p1, p2, qoffset)),  examples/lqr_cartpole.jl:26 */
@@ -743,6 +745,54 @@ int cclqr_rollout_quantiles_ws_bytes(const cclqr_mech *m, int32_t mu, int64_t n_
 int cclqr_rollout_quantiles(const cclqr_mech *m, const cclqr_ctrl *c, int64_t n_inst, int32_t steps, int32_t k0, int64_t first_instance,
                             const double *traj_dev, int32_t n_prob, const double *prob /* host */,
                             double *quant_dev, int32_t *finite_dev, void *ws_dev, size_t ws_bytes, void *stream);
+
+/* Joint coordinates of a rollout on the device (additive, still 202, no struct changed; looked up by name like the entries above).  The slab holds maximal
+ * coordinates; the reference's users think in joint coordinates: its minimal-coordinate LQR constructor takes xθd and vωd (src/control/lqr.jl:68-86), its PID runs on
+ * minimalCoordinates(mechanism, eqc)[1] (src/control/pid.jl:43-57), and the friction law of examples/trackingLQR_triple_cartpole.jl:98-101 acts on the relative joint
+ * velocity.  This call returns both for every joint at every row of a slab.
+ * The definition.  For joint j in the CALLER'S joint order (the index ctrl_joint uses), a = its parent body or the origin (x = 0, q = 1, velocities 0), b = its child
+ * body, poses from slab row r = k - k0 of instance i:
+ *     revolute   e = conj(q_a) q_b conj(qoff),  s = axis . vec(e),  c = e_0,  θ_raw = 2 atan2(s, c)          rate = axis . ω_b - axis . ω_a  (entries 10..12 as stored)
+ *     prismatic  θ_raw = axis . (R_a'(x_b + R_b p2 - x_a) - p1)                                              rate = axis . R_a'(v_b - v_a)
+ * exactly the coordinate the PID law of the rollout forms (pid.jl:43-57) and the relative velocity its friction law forms (trackingLQR_triple_cartpole.jl:98-101).  A
+ * CCLQR_FIXED_ORIENTATION joint has no coordinate: 0.0 for both.
+ * mode CCLQR_JOINTS_RAW: θ = θ_raw, the number PID sees.  mode CCLQR_JOINTS_CONTINUOUS, revolutes (prismatic joints as in mode 0): the principal value w in [-π, π] is
+ * 2 atan2(s, c) with (s, c) negated when c < 0, so the two quaternions of one rotation give the same w; θ_k = w_k + 2π turns_k with turns an integer, 0 at step 1;
+ * with d = w_k - w_prev, turns goes down by 1 if d > π and up by 1 if d < -π.  A w_k that is not finite gives θ_k = NaN and leaves (w_prev, turns) as they were.
+ * carry_dev [n_inst][ne][2] holds (w_prev, turns): read when k0 > 1, always written in mode 1, so a horizon taken chunk by chunk gives the bits of one call.  The rate
+ * has no state.  A value that is not finite makes the outputs it enters NaN (never Inf) and nothing else.
+ * The call writes rows k0 - 1 .. k0 + steps - 2 of each instance's out_steps rows of theta_dev [n_inst][out_steps][ne] and, unless it is NULL, rate_dev of the same
+ * shape: the absolute step, as the noise array is indexed, so the chunks of a horizon fill one series.  With a cclqr_plants handle instance i reads p1, p2 of the
+ * plant record cclqr_rollout_plants would read for the global index first_instance + i (prismatic joints of chains and trees); plants = NULL reads the mechanism's.
+ * Device pointers; asynchronous on `stream`; nothing is allocated.  CCLQR_EINVAL, before anything is launched, with the cause in cclqr_last_error and the outputs
+ * untouched: n_inst < 1, steps < 1, k0 < 1, out_steps < k0 + steps - 1, a mode outside 0 / 1, mode 1 without carry_dev, a null traj_dev or theta_dev, plants made for
+ * another mechanism or device or not covering first_instance .. first_instance + n_inst - 1.  Every topology cclqr_mech_create takes, loops included. */
+#define CCLQR_JOINTS_RAW 0
+#define CCLQR_JOINTS_CONTINUOUS 1
+int cclqr_rollout_joints(const cclqr_mech *m, const cclqr_plants *plants, int64_t n_inst, int32_t steps, int32_t k0, int64_t first_instance,
+                         const double *traj_dev, int32_t mode, int64_t out_steps,
+                         double *theta_dev /* [n_inst][out_steps][ne] */, double *rate_dev /* same shape, or NULL */,
+                         double *carry_dev /* [n_inst][ne][2]; mode 1 only, else NULL */, void *stream);
+
+/* The statistics of any per-instance series x_dev [n_inst][steps][nc] ACROSS its instances, per step (additive, still 202; looked up by name): what
+ * cclqr_rollout_ensemble / cclqr_rollout_quantiles compute, with x GIVEN instead of formed -- the joint series above (the fan chart of a swing-up in joint angles, the
+ * quantity pid.jl:43-57 regulates), or any other.  They know nothing of mechanisms.
+ * cclqr_series_ensemble: mean_dev, m2_dev [steps][nc] = the mean and the CENTRED sum of squares of every coordinate; a value that is not finite makes its coordinate
+ * NaN at that step.  Summation order: a tile is 64 consecutive instances, reduced about its own mean in two passes; the tiles are merged in tile order (Chan, Golub,
+ * LeVeque).  No atomics: a second call gives the same bits.  ws_dev: cclqr_series_ensemble_ws_bytes bytes, 8-byte aligned.
+ * cclqr_series_quantiles: quant_dev [steps][n_prob][nc] = the quantiles of the FINITE values by the formula of cclqr_rollout_quantiles above, finite_dev [steps][nc]
+ * (int32, or NULL) their number; n_inst <= CCLQR_QUANTILE_MAX_INST (else CCLQR_EUNSUPPORTED), n_prob <= CCLQR_QUANTILE_MAX_PROBS, prob a HOST array.  The workspace
+ * block rule is that call's: min_bytes holds one row, full_bytes all, and the bits do not depend on ws_bytes.
+ * Device pointers except prob; asynchronous on `stream`; nothing is allocated.  CCLQR_EINVAL, before anything is launched, with the cause in cclqr_last_error and the
+ * outputs untouched: n_inst < 1, steps < 1, nc outside 1 .. CCLQR_SERIES_MAX_COORDS, a null argument, a null, short or misaligned workspace, n_prob outside 1 .. 16, a
+ * prob entry outside [0, 1] or NaN. */
+#define CCLQR_SERIES_MAX_COORDS 1024
+int cclqr_series_ensemble_ws_bytes(int64_t n_inst, int32_t steps, int32_t nc, size_t *bytes);
+int cclqr_series_ensemble(int64_t n_inst, int32_t steps, int32_t nc, const double *x_dev, double *mean_dev, double *m2_dev,
+                          void *ws_dev, size_t ws_bytes, void *stream);
+int cclqr_series_quantiles_ws_bytes(int64_t n_inst, int32_t steps, int32_t nc, size_t *min_bytes, size_t *full_bytes);
+int cclqr_series_quantiles(int64_t n_inst, int32_t steps, int32_t nc, const double *x_dev, int32_t n_prob, const double *prob /* host */,
+                           double *quant_dev, int32_t *finite_dev, void *ws_dev, size_t ws_bytes, void *stream);
 
 /* cclqr_rollout (HOST pointers) with options: first_instance and newton_mode apply, the device-buffer fields must be NULL. */
 int cclqr_rollout_host_ex(const cclqr_mech *m, const cclqr_ctrl *c, int64_t n_inst, int32_t steps, int32_t k0, const double *z0,

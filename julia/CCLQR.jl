@@ -485,6 +485,50 @@ function rollout_quantiles!(h::MechHandle, c::CtrlHandle, n::Integer, steps::Int
                 h.ptr, c.ptr, n, steps, k0, first_instance, traj, length(prob), prob, quant, finite, ws, ws_bytes, stream))
 end
 
+const JOINTS_RAW = Int32(0)
+const JOINTS_CONTINUOUS = Int32(1)
+
+"The joint coordinates of the slab a rollout_dev! launch has just written (cclqr_rollout_joints; device pointers, asynchronous on `stream`): theta and rate are
+ ne x out_steps x n -- per instance, absolute step and joint (the caller's joint order) the minimal coordinate of pid.jl:43-57 and the relative joint velocity of
+ trackingLQR_triple_cartpole.jl:98-101; columns k0 : k0 + steps - 1 are written, so the chunks of a horizon fill one series.  mode JOINTS_CONTINUOUS makes a
+ revolute's angle continuous in time; carry (2 x ne x n: w_prev, turns) then travels from launch to launch.  p: a PlantsHandle or nothing."
+function rollout_joints!(h::MechHandle, p, n::Integer, steps::Integer, k0::Integer, traj::Ptr{Float64}, mode::Integer, out_steps::Integer, theta::Ptr{Float64};
+                         rate::Ptr{Float64} = Ptr{Float64}(C_NULL), carry::Ptr{Float64} = Ptr{Float64}(C_NULL), first_instance = 0, stream::Ptr{Cvoid} = C_NULL)
+    check(ccall((:cclqr_rollout_joints, lib), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int32, Int32, Int64, Ptr{Float64}, Int32, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Cvoid}),
+                h.ptr, p === nothing ? C_NULL : p.ptr, n, steps, k0, first_instance, traj, mode, out_steps, theta, rate, carry, stream))
+end
+
+"Bytes of device workspace one series_ensemble! call of these sizes needs (cclqr_series_ensemble_ws_bytes)."
+function series_ensemble_ws_bytes(n::Integer, steps::Integer, nc::Integer)
+    out = Ref{Csize_t}(0)
+    check(ccall((:cclqr_series_ensemble_ws_bytes, lib), Cint, (Int64, Int32, Int32, Ref{Csize_t}), n, steps, nc, out))
+    Int(out[])
+end
+
+"The mean and the centred sum of squares of every coordinate of a series x (nc x steps x n, device) ACROSS its instances, per step (cclqr_series_ensemble): mean and
+ m2 are nc x steps.  One fixed summation order, no atomics."
+function series_ensemble!(n::Integer, steps::Integer, nc::Integer, x::Ptr{Float64}, mean::Ptr{Float64}, m2::Ptr{Float64}, ws::Ptr{Cvoid}, ws_bytes::Integer;
+                          stream::Ptr{Cvoid} = C_NULL)
+    check(ccall((:cclqr_series_ensemble, lib), Cint, (Int64, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Cvoid}, Csize_t, Ptr{Cvoid}),
+                n, steps, nc, x, mean, m2, ws, ws_bytes, stream))
+end
+
+"(min_bytes, full_bytes) of device workspace for series_quantiles! (cclqr_series_quantiles_ws_bytes): one row of the series, all `steps` rows."
+function series_quantiles_ws_bytes(n::Integer, steps::Integer, nc::Integer)
+    lo = Ref{Csize_t}(0); full = Ref{Csize_t}(0)
+    check(ccall((:cclqr_series_quantiles_ws_bytes, lib), Cint, (Int64, Int32, Int32, Ref{Csize_t}, Ref{Csize_t}), n, steps, nc, lo, full))
+    Int(lo[]), Int(full[])
+end
+
+"The quantiles of every coordinate of a series x (nc x steps x n, device) ACROSS its instances, per step (cclqr_series_quantiles): quant is nc x length(prob) x
+ steps, finite nc x steps the number of finite values (or C_NULL).  At most 16384 instances and 16 probabilities."
+function series_quantiles!(n::Integer, steps::Integer, nc::Integer, x::Ptr{Float64}, prob::Vector{Float64}, quant::Ptr{Float64}, ws::Ptr{Cvoid}, ws_bytes::Integer;
+                           finite::Ptr{Int32} = Ptr{Int32}(C_NULL), stream::Ptr{Cvoid} = C_NULL)
+    check(ccall((:cclqr_series_quantiles, lib), Cint, (Int64, Int32, Int32, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Cvoid}, Csize_t, Ptr{Cvoid}),
+                n, steps, nc, x, length(prob), prob, quant, finite, ws, ws_bytes, stream))
+end
+
 "dlqr_weights that also returns the cost-to-go (cclqr_riccati_value): P[p] is the Pkp1 of lqr.jl:170 at the last backward step problem p executed (the step the
  break test of lqr.jl:172 fired on, else step 1; Q_p when N = 1), mx x mx as the recursion holds it.  Returns (Ku[p][k][i], P[p], kbreak[p])."
 function dlqr_value(As::Vector, Bus::Vector, Bλs::Vector, Gs::Vector, Qs::Vector, Rs::Vector, N::Integer; tol = 1e-5)
