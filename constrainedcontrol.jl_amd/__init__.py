@@ -9,4 +9,4 @@ from .mechanism import (Body, Box, EqualityConstraint, FixedOrientation, MechTab
 from . import examples
 from . import _capi
 from . import dist
-from .lqr import LQR, LQRSweep, PID, PlantLQR, PolicyValue, StationaryPolicyValue, StationaryCovariance, TrackingCovariance, TrackingPolicyValue, StationaryLQR, PlantTrackingLQR, Score, Ensemble, EnsembleStats, Joints, JointSeries, BatchState, Controller, OpenLoop, Storage, TrackingLQR, control_lqr, on_device, setForce, simulate, state_error, predicted_cost
+from .lqr import LQR, LQRSweep, PID, PlantLQR, PolicyValue, StationaryPolicyValue, StationaryCovariance, TrackingCovariance, TrackingPolicyValue, StationaryLQR, PlantTrackingLQR, Score, Ensemble, EnsembleStats, Joints, JointSeries, Invariants, InvariantSeries, BatchState, Controller, OpenLoop, Storage, TrackingLQR, control_lqr, on_device, setForce, simulate, state_error, predicted_cost

@@ -25,7 +25,8 @@ EXPORTS = ["cclqr_last_error", "cclqr_version", "cclqr_device_count", "cclqr_set
            "cclqr_riccati_doubling", "cclqr_ctrl_create_lqr_batch_doubling", "cclqr_covariance_doubling", "cclqr_value_create_covariance_doubling",
            "cclqr_covariance_tracking", "cclqr_value_create_covariance_tracking", "cclqr_policy_value_tracking", "cclqr_value_create_policy_tracking",
            "cclqr_rollout_ensemble_ws_bytes", "cclqr_rollout_ensemble", "cclqr_rollout_quantiles_ws_bytes", "cclqr_rollout_quantiles",
-           "cclqr_rollout_joints", "cclqr_series_ensemble_ws_bytes", "cclqr_series_ensemble", "cclqr_series_quantiles_ws_bytes", "cclqr_series_quantiles"]
+           "cclqr_rollout_joints", "cclqr_series_ensemble_ws_bytes", "cclqr_series_ensemble", "cclqr_series_quantiles_ws_bytes", "cclqr_series_quantiles",
+           "cclqr_rollout_invariants"]
 ABI_VERSION = 202     # include/cclqr.h CCLQR_ABI_VERSION: the structs below mirror that header (verified field by field against cclqr_abi_layout at load time)
 ROLLOUT_NO_ALLOC = 1  # cclqr_rollout_opts.flags: the call may neither allocate nor synchronise (a hipGraph capture is open on the device)
 ROLLOUT_CARRY_STATUS = 4  # ... `status` is read and written: an instance lost in an earlier launch stays frozen, the others merge this launch's result into it
@@ -768,8 +769,50 @@ def _joint_series_results(td, stream, n, steps, ne, continuous, rates, keep, pro
     return out
 
 
+INVARIANTS_LEN = 6            # CCLQR_INVARIANTS_LEN: T, V, E, gap, twist, quat per instance and step (cclqr_rollout_invariants)
+INVARIANTS_SUMMARY_LEN = 8    # CCLQR_INVARIANTS_SUMMARY_LEN: E_first, E_min, E_max, gap_max, gap_step, twist_max, quat_max, bad_rows per instance
+
+
+def rollout_invariants(mech, n_inst, steps, k0, traj_ptr, out_steps, inv_ptr=0, rows_ptr=0, summary_ptr=0, stream=0, first_instance=0, plants=None):
+    """cclqr_rollout_invariants on device addresses (asynchronous on `stream`): T, V, E, gap, twist, quat of every row of the slab traj [n_inst][steps][nb][13] into
+    the rows k0 - 1 .. k0 + steps - 2 of inv [n_inst][out_steps][6], the constraint rows themselves into rows [n_inst][out_steps][ne][5], and the per-instance
+    summary [n_inst][8], which is read when k0 > 1 and travels from launch to launch; any of the three may be 0.  plants: a PlantsHandle -- instance i reads the
+    masses, inertias and vertices of plant first_instance + i"""
+    vp = lambda p: C.c_void_p(int(p)) if p else None
+    check(lib().cclqr_rollout_invariants(mech.ptr, None if plants is None else plants.ptr, C.c_int64(int(n_inst)), C.c_int32(int(steps)), C.c_int32(int(k0)),
+                                         C.c_int64(int(first_instance)), vp(traj_ptr), C.c_int64(int(out_steps)), vp(inv_ptr), vp(rows_ptr), vp(summary_ptr), vp(stream)))
+
+
+def _invariant_series_results(td, stream, n, steps, ne, keep, rows, probs, inv, grows, summ):
+    """the finished invariants: the summary, the kept series, and the statistics of the series [n][steps][6] across the instances by one cclqr_series_ensemble and,
+    with probs, one cclqr_series_quantiles.  Returns the dict InvariantSeries is built from"""
+    import torch
+    nc = INVARIANTS_LEN
+    mean = torch.empty((steps, nc), dtype=torch.float64, device=td)
+    m2 = torch.empty((steps, nc), dtype=torch.float64, device=td)
+    wb = series_ensemble_ws_bytes(n, steps, nc)
+    ws = torch.empty(wb // 8 + 1, dtype=torch.float64, device=td)
+    series_ensemble(n, steps, nc, inv.data_ptr(), mean.data_ptr(), m2.data_ptr(), ws.data_ptr(), wb, stream)
+    out = dict(count=n, mean=None, M2=None, probs=None, quantiles=None, finite_count=None, series=None, g=None, summary=None)
+    if len(probs):
+        quant = torch.empty((steps, len(probs), nc), dtype=torch.float64, device=td)
+        fin = torch.empty((steps, nc), dtype=torch.int32, device=td)
+        qb = series_quantiles_ws_bytes(n, steps, nc)[1]
+        qws = torch.empty(qb // 8 + 1, dtype=torch.float64, device=td)
+        series_quantiles(n, steps, nc, inv.data_ptr(), probs, quant.data_ptr(), fin.data_ptr(), qws.data_ptr(), qb, stream)
+    torch.cuda.current_stream().synchronize()
+    out["mean"], out["M2"], out["summary"] = mean.cpu().numpy(), m2.cpu().numpy(), summ.cpu().numpy()
+    if len(probs):
+        out["probs"], out["quantiles"], out["finite_count"] = tuple(float(p) for p in probs), quant.cpu().numpy(), fin.cpu().numpy()
+    if keep:
+        out["series"] = inv.cpu().numpy()
+    if rows:
+        out["g"] = grows.cpu().numpy()
+    return out
+
+
 def rollout_scored(mech, ctrl, score, z0, steps, chunk_steps, noise=None, first_instance=0, plants=None, newton_mode=0, newton_eps_alone=0.0, flags=0, traj_out=None,
-                   ensemble=None, joints=None):
+                   ensemble=None, joints=None, invariants=None):
     """A horizon rolled out AND scored on the device without its trajectory ever existing: ceil(steps / chunk_steps) launches of cclqr_rollout_ex (plants:
     cclqr_rollout_plants) into ONE slab of chunk_steps rows, each followed on the same stream by cclqr_rollout_score.  The state, the multipliers, the status
     (ROLLOUT_CARRY_STATUS), the PID state and the noise column travel from launch to launch, so the result is bitwise that of one launch.
@@ -780,9 +823,12 @@ def rollout_scored(mech, ctrl, score, z0, steps, chunk_steps, noise=None, first_
     joints: None (nothing changes, nothing is allocated), or (continuous, rates, keep, probs) -- behind every launch cclqr_rollout_joints runs on the same slab and
     stream into whole-horizon device arrays [n_inst][steps][ne], the carry buffer travelling from chunk to chunk; after the last chunk one cclqr_series_ensemble and,
     with probs, one cclqr_series_quantiles reduce them across the instances.
+    invariants: None (nothing changes, nothing is allocated), or (keep, rows, probs) -- behind every launch cclqr_rollout_invariants runs on the same slab and stream
+    into a whole-horizon device array [n_inst][steps][6] (rows: and [n_inst][steps][ne][5]), the summary [n_inst][8] travelling from chunk to chunk; after the last
+    chunk the series is reduced across the instances as the joint series is.
     Returns (zT, status, score [n_inst][SCORE_LEN] or None), with ensemble a fourth element (mean [steps][12 nb + mu], M2 the same, {row: C [12 nb][12 nb]}), which
-    the three-element form extends by (quant [steps][len(probs)][12 nb + mu], finite [steps][12 nb + mu]); with joints a last element, the dict of
-    _joint_series_results."""
+    the three-element form extends by (quant [steps][len(probs)][12 nb + mu], finite [steps][12 nb + mu]); with joints a further element, the dict of
+    _joint_series_results, and with invariants a last one, the dict of _invariant_series_results."""
     import torch
     nb, ne = mech.tables.nb, mech.tables.ne
     z0 = f64(z0).reshape(-1, nb, 13)
@@ -806,6 +852,11 @@ def rollout_scored(mech, ctrl, score, z0, steps, chunk_steps, noise=None, first_
             raise ValueError("quantiles are taken over at most %d instances per call (got %d)" % (QUANTILE_MAX_INST, n))
         if (2 * ne if jrates else ne) > SERIES_MAX_COORDS:
             raise ValueError("a series has at most %d coordinates" % SERIES_MAX_COORDS)
+    if invariants is not None:    # (before anything touches the device)
+        ikeep, irows = bool(invariants[0]), bool(invariants[1])
+        iprobs = quantile_probs(invariants[2])
+        if len(iprobs) and n > QUANTILE_MAX_INST:
+            raise ValueError("quantiles are taken over at most %d instances per call (got %d)" % (QUANTILE_MAX_INST, n))
     td = torch.device("cuda", torch.cuda.current_device())
     z = torch.from_numpy(z0).to(td)
     zn = torch.empty_like(z)
@@ -833,6 +884,10 @@ def rollout_scored(mech, ctrl, score, z0, steps, chunk_steps, noise=None, first_
         jth = torch.empty((n, steps, ne), dtype=torch.float64, device=td)
         jrt = torch.empty((n, steps, ne), dtype=torch.float64, device=td) if jrates else None
         jcarry = torch.zeros((n, ne, 2), dtype=torch.float64, device=td) if jcont else None
+    if invariants is not None:
+        iser = torch.empty((n, steps, INVARIANTS_LEN), dtype=torch.float64, device=td)
+        igr = torch.empty((n, steps, ne, 5), dtype=torch.float64, device=td) if irows else None
+        isum = torch.zeros((n, INVARIANTS_SUMMARY_LEN), dtype=torch.float64, device=td)
     for ci, (k0, s) in enumerate(plan):
         # the noise array is indexed by the absolute step k - 1: its base stays where it is whatever k0 is
         rollout_dev(mech, ctrl, n, s, k0, z.data_ptr(), lam.data_ptr(), 0 if dnoise is None else dnoise.data_ptr(), steps, slab.data_ptr(), zn.data_ptr(),
@@ -850,10 +905,15 @@ def rollout_scored(mech, ctrl, score, z0, steps, chunk_steps, noise=None, first_
         if joints is not None:
             rollout_joints(mech, n, s, k0, slab.data_ptr(), JOINTS_CONTINUOUS if jcont else JOINTS_RAW, steps, jth.data_ptr(), 0 if jrt is None else jrt.data_ptr(),
                            0 if jcarry is None else jcarry.data_ptr(), stream, first_instance=first_instance, plants=plants)
+        if invariants is not None:
+            rollout_invariants(mech, n, s, k0, slab.data_ptr(), steps, iser.data_ptr(), 0 if igr is None else igr.data_ptr(), isum.data_ptr(), stream,
+                               first_instance=first_instance, plants=plants)
         if traj_out is not None:      # (a launch of s < rows steps fills the slab as [n][s][nb][13] from its base)
             traj_out[:, k0 - 1:k0 - 1 + s] = slab.reshape(-1)[:n * s * nb * 13].reshape(n, s, nb, 13).cpu().numpy()
         z, zn = zn, z
     jres = () if joints is None else (_joint_series_results(td, stream, n, steps, ne, jcont, jrates, jkeep, jprobs, jth, jrt),)
+    if invariants is not None:
+        jres += (_invariant_series_results(td, stream, n, steps, ne, ikeep, irows, iprobs, iser, igr, isum),)
     torch.cuda.current_stream().synchronize()
     out = (z.cpu().numpy(), st.cpu().numpy(), None if sc is None else sc.cpu().numpy())
     if ensemble is None:

@@ -16,6 +16,9 @@ static_assert(CCLQR_SCORE_LEN == CCLQR_SCORE_LEN_, "include/cclqr.h and cclqr_sc
 #include "cclqr_joints.h"
 static_assert(CCLQR_JOINTS_RAW == CCLQR_JOINTS_RAW_ && CCLQR_JOINTS_CONTINUOUS == CCLQR_JOINTS_CONTINUOUS_ && CCLQR_SERIES_MAX_COORDS == CCLQR_SERIES_MAX_COORDS_,
               "include/cclqr.h and cclqr_joints.h disagree on the joint modes or the coordinates of a series");
+#include "cclqr_invariants.h"
+static_assert(CCLQR_INVARIANTS_LEN == CCLQR_INVARIANTS_LEN_ && CCLQR_INVARIANTS_SUMMARY_LEN == CCLQR_INVARIANTS_SUMMARY_LEN_,
+              "include/cclqr.h and cclqr_invariants.h disagree on the length of a row of invariants or of a summary");
 #include <math.h>
 #include <stdio.h>
 #include <string.h>
@@ -1349,28 +1352,55 @@ extern "C" int cclqr_rollout_quantiles(const cclqr_mech* m, const cclqr_ctrl* c,
     return CCLQR_OK;
 }
 
-// ---- the joint coordinates of a slab (joints.hip).  Nothing is allocated, copied or synchronised
-extern "C" int cclqr_rollout_joints(const cclqr_mech* m, const cclqr_plants* plants, int64_t n_inst, int32_t steps, int32_t k0, int64_t first_instance, const double* traj,
-                                    int32_t mode, int64_t out_steps, double* theta, double* rate, double* carry, void* stream) {
+// ---- the passes that turn a slab into per-instance series written at the absolute step (joints.hip, invariants.hip): the ONE sequence of refusals they share.
+// slab_series_check: the device, the sizes, and -- where a series output is given -- that out_steps rows hold the steps of this launch
+static int slab_series_check(const cclqr_mech* m, int64_t n_inst, int32_t steps, int32_t k0, int64_t first_instance, int64_t out_steps, bool series) {
     if (!m) return fail(CCLQR_EINVAL, "null argument");
     TRY(check_device(m));
     if (n_inst < 1 || steps < 1 || k0 < 1)
         return fail(CCLQR_EINVAL, "need n_inst >= 1, steps >= 1 and k0 >= 1 (got n_inst = " + std::to_string(n_inst) + ", steps = " + std::to_string(steps) + ", k0 = " + std::to_string(k0) + ")");
     if (first_instance < 0) return fail(CCLQR_EINVAL, "negative first_instance");
-    if (out_steps < (int64_t)k0 + steps - 1)
+    if (series && out_steps < (int64_t)k0 + steps - 1)
         return fail(CCLQR_EINVAL, "out_steps = " + std::to_string(out_steps) + " does not hold the steps " + std::to_string(k0) + " .. " + std::to_string((int64_t)k0 + steps - 1) + " of this launch");
+    return CCLQR_OK;
+}
+// slab_plants_check: the plants are this mechanism's, on its device, and cover the launch's instances
+static int slab_plants_check(const cclqr_mech* m, const cclqr_plants* plants, int64_t first_instance, int64_t n_inst) {
+    if (plants && (plants->nb != m->nb || plants->device != m->device)) return fail(CCLQR_EINVAL, "the plants were created for another mechanism or device");
+    if (plants && m->shape.family == RolloutFamily::Loop) return fail(CCLQR_EINVAL, "the plants were created for another mechanism: a closed-loop mechanism takes none");
+    return plants_check_range(m, plants, first_instance, n_inst, "instances", "launch");
+}
+
+// ---- the joint coordinates of a slab (joints.hip).  Nothing is allocated, copied or synchronised
+extern "C" int cclqr_rollout_joints(const cclqr_mech* m, const cclqr_plants* plants, int64_t n_inst, int32_t steps, int32_t k0, int64_t first_instance, const double* traj,
+                                    int32_t mode, int64_t out_steps, double* theta, double* rate, double* carry, void* stream) {
+    TRY(slab_series_check(m, n_inst, steps, k0, first_instance, out_steps, true));
     if (mode != CCLQR_JOINTS_RAW && mode != CCLQR_JOINTS_CONTINUOUS) return fail(CCLQR_EINVAL, "mode = " + std::to_string(mode) + " is neither CCLQR_JOINTS_RAW nor CCLQR_JOINTS_CONTINUOUS");
     if (mode == CCLQR_JOINTS_CONTINUOUS && !carry) return fail(CCLQR_EINVAL, "CCLQR_JOINTS_CONTINUOUS needs carry_dev [n_inst][ne][2]: the turn count travels in it from launch to launch");
     if (!traj || !theta) return fail(CCLQR_EINVAL, "null traj_dev or theta_dev");
-    if (plants && (plants->nb != m->nb || plants->device != m->device)) return fail(CCLQR_EINVAL, "the plants were created for another mechanism or device");
-    if (plants && m->shape.family == RolloutFamily::Loop) return fail(CCLQR_EINVAL, "the plants were created for another mechanism: a closed-loop mechanism takes none");
-    TRY(plants_check_range(m, plants, first_instance, n_inst, "instances", "launch"));
+    TRY(slab_plants_check(m, plants, first_instance, n_inst));
     JointsArgs a;
     memset(&a, 0, sizeof(a));
     a.M = m->dev; a.plants = plants ? plants->dev : nullptr; a.plant_off = plants ? first_instance - plants->first_index : 0;
     a.nb = m->nb; a.ne = m->nj; a.loop = m->host.loop; a.n_inst = n_inst; a.steps = steps; a.k0 = k0; a.traj = traj; a.mode = mode; a.out_steps = out_steps;
     a.theta = theta; a.rate = rate; a.carry = mode == CCLQR_JOINTS_CONTINUOUS ? carry : nullptr;
     HIPCHK(launch_joints(a, (hipStream_t)stream));
+    return CCLQR_OK;
+}
+
+// ---- the integrator's invariants of a slab (invariants.hip).  Nothing is allocated, copied or synchronised
+extern "C" int cclqr_rollout_invariants(const cclqr_mech* m, const cclqr_plants* plants, int64_t n_inst, int32_t steps, int32_t k0, int64_t first_instance, const double* traj,
+                                        int64_t out_steps, double* inv, double* rows, double* summary, void* stream) {
+    TRY(slab_series_check(m, n_inst, steps, k0, first_instance, out_steps, inv || rows));
+    if (!traj) return fail(CCLQR_EINVAL, "null traj_dev");
+    if (!inv && !rows && !summary) return fail(CCLQR_EINVAL, "inv_dev, rows_dev and summary_dev are all NULL: the call would compute nothing");
+    TRY(slab_plants_check(m, plants, first_instance, n_inst));
+    InvArgs a;
+    memset(&a, 0, sizeof(a));
+    a.M = m->dev; a.plants = plants ? plants->dev : nullptr; a.plant_off = plants ? first_instance - plants->first_index : 0;
+    a.nb = m->nb; a.ne = m->nj; a.loop = m->host.loop; a.n_inst = n_inst; a.steps = steps; a.k0 = k0; a.traj = traj; a.out_steps = out_steps;
+    a.inv = inv; a.rows = rows; a.summary = summary;
+    HIPCHK(launch_invariants(a, (hipStream_t)stream));
     return CCLQR_OK;
 }
 

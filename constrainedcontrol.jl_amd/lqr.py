@@ -818,6 +818,7 @@ class Storage:
         self.score = None          # [n_inst][4] = Jx, Ju, peak, last_out of simulate(..., score=)
         self.ensemble = None       # EnsembleStats of simulate(..., ensemble=): the batch across its instances, per step
         self.joints = None         # JointSeries of simulate(..., joints=): the run in joint coordinates, and its statistics across the instances
+        self.invariants = None     # InvariantSeries of simulate(..., invariants=): energy, constraint gaps, quaternion norms, and a verdict per instance
 
     def instance(self, n):
         one = Storage(self.steps, self.nb, 1, self.z[n:n + 1], None if self.status is None else self.status[n:n + 1],
@@ -1249,6 +1250,86 @@ class JointSeries:
     max = property(lambda self: self.quantile(1.0))
 
 
+class Invariants:
+    """Can this run be trusted?  The integrator's own invariants of a rollout, formed on the device from the rollout's states (cclqr_rollout_invariants): per instance
+    and step the kinetic and potential energy and their sum, the largest translational and rotational constraint residual over all joints (the rows the Newton solve
+    drives to zero) and the largest | q.q - 1 | over the bodies; per instance an eight-number verdict that survives a run with no trajectory; and their statistics
+    across the instances (cclqr_series_ensemble, cclqr_series_quantiles).  simulate(..., invariants=Invariants(mechanism)) returns a Storage with .invariants, an
+    InvariantSeries.  With plants= every instance is measured on its own masses, inertias and joint vertices.
+    keep=False: only the summary and the statistics come back.  rows=True: also every constraint row, .g [n][steps][ne][5] in the order of mechanism.eqconstraints
+    (orc.constraints' layout).  quantiles=(p, ...): up to 16 probabilities in [0, 1] (at most 16384 instances)."""
+
+    def __init__(self, mechanism, keep=True, rows=False, quantiles=()):
+        if not isinstance(mechanism, Mechanism):
+            raise TypeError("Invariants(mechanism, keep=True, rows=False, quantiles=())")
+        for name, v in (("keep", keep), ("rows", rows)):
+            if not isinstance(v, (bool, np.bool_)):
+                raise TypeError("Invariants(%s=) takes True or False (got %r)" % (name, v))
+        self.mechanism = mechanism
+        self.keep, self.rows = bool(keep), bool(rows)
+        self.quantiles = tuple(float(p) for p in _capi.quantile_probs(quantiles))
+
+
+class InvariantSeries:
+    """The invariants of `count` instances at every step of a run.  Per instance and step (None with keep=False): kinetic, potential, energy, gap, twist, quat
+    [n][steps]; with rows=True g [n][steps][ne][5], the constraint rows themselves.  Per instance, always: energy_first, energy_min, energy_max, energy_drift =
+    max(energy_max - energy_first, energy_first - energy_min), gap_max, gap_step (the step, from 1, at which gap_max was first reached; 0: no finite row), twist_max,
+    quat_max, bad_rows (rows with an output that is not finite), each [n]; over rows that are not finite nothing is taken, and an instance without a finite row has
+    NaN.  Across the instances: mean, M2, std [steps][6] in the order NAMES, and with Invariants(quantiles=): quantile(p) [steps][6] for the probabilities that were
+    asked for (median, min, max for 0.5, 0, 1) and finite_count [steps][6], the number of finite values each was taken over."""
+
+    NAMES = ("kinetic", "potential", "energy", "gap", "twist", "quat")
+
+    def __init__(self, count, summary, mean, M2, series=None, g=None, *, probs=None, quantiles=None, finite_count=None):
+        arr = lambda a: None if a is None else np.asarray(a, dtype=np.float64)
+        self.count = int(count)
+        self.summary = np.asarray(summary, dtype=np.float64).reshape(self.count, _capi.INVARIANTS_SUMMARY_LEN)
+        self.mean, self.M2, self.series, self.g = arr(mean), arr(M2), arr(series), arr(g)
+        self.probs = None if probs is None else tuple(float(p) for p in probs)
+        self._quantiles = None if probs is None else np.asarray(quantiles, dtype=np.float64)
+        self.finite_count = None if probs is None else np.asarray(finite_count, dtype=np.int32)
+
+    def _column(self, i):
+        return None if self.series is None else self.series[:, :, i]
+
+    kinetic = property(lambda self: self._column(0))
+    potential = property(lambda self: self._column(1))
+    energy = property(lambda self: self._column(2))
+    gap = property(lambda self: self._column(3))
+    twist = property(lambda self: self._column(4))
+    quat = property(lambda self: self._column(5))
+
+    energy_first = property(lambda self: self.summary[:, 0])
+    energy_min = property(lambda self: self.summary[:, 1])
+    energy_max = property(lambda self: self.summary[:, 2])
+    gap_max = property(lambda self: self.summary[:, 3])
+    gap_step = property(lambda self: self.summary[:, 4].astype(np.int64))
+    twist_max = property(lambda self: self.summary[:, 5])
+    quat_max = property(lambda self: self.summary[:, 6])
+    bad_rows = property(lambda self: self.summary[:, 7].astype(np.int64))
+
+    @property
+    def energy_drift(self):
+        """max(E_max - E_1, E_1 - E_min) per instance, E_1 the energy at the first finite row"""
+        return np.maximum(self.energy_max - self.energy_first, self.energy_first - self.energy_min)
+
+    def var(self, ddof=0):
+        return self.M2 / (self.count - ddof)
+
+    std = property(lambda self: np.sqrt(self.var()))
+
+    def quantile(self, p):
+        """the quantile at probability p of each of the six invariants across the instances, [steps][6]"""
+        asked = () if self.probs is None else self.probs
+        if float(p) not in asked:
+            raise KeyError("quantile %r was not asked for: Invariants(quantiles=%s)" % (p, list(asked)))
+        return self._quantiles[:, asked.index(float(p))]
+
+    median = property(lambda self: self.quantile(0.5))
+    min = property(lambda self: self.quantile(0.0))
+    max = property(lambda self: self.quantile(1.0))
+
+
 class OpenLoop(Controller):
     """control!(mechanism, k) = setForce!(mechanism, joint, [U[k]])  — the open-loop closure of
     examples/trackingLQR_triple_cartpole.jl:46-48 as a table: U[k][i] for controlled joints eqcids."""
@@ -1592,7 +1673,7 @@ def _simulate_device_closure(mechanism, steps, controller, record, z0):
 
 
 def simulate(mechanism, tend_or_storage, controller, record=True, z0=None, fric=None, noise=None, noise_scale=None, noise_seed=None,
-             first_instance=0, plants=None, score=None, chunk_steps=None, ensemble=None, joints=None):
+             first_instance=0, plants=None, score=None, chunk_steps=None, ensemble=None, joints=None, invariants=None):
     """simulate!(mechanism, tend::Real | storage::Storage, controller; record)  -> Storage
 
     z0 [n_inst][nb][13]: batch of initial states (default: the mechanism's current body states, one instance).
@@ -1613,6 +1694,9 @@ def simulate(mechanism, tend_or_storage, controller, record=True, z0=None, fric=
     joints: a Joints -- the same chunk loop (alone, or with score= / ensemble= on the same slab) with cclqr_rollout_joints behind every launch; the returned Storage
     carries .joints, a JointSeries: every joint's coordinate and rate per instance and step, and their mean, spread and quantiles across the instances.  Any
     chunk_steps, record or not, gives the same bits.  For the fused laws.
+    invariants: an Invariants -- the same chunk loop (alone, or with score= / ensemble= / joints= on the same slab) with cclqr_rollout_invariants behind every launch;
+    the returned Storage carries .invariants, an InvariantSeries: energy, constraint gaps and quaternion norm errors per instance and step, an eight-number verdict
+    per instance that needs no trajectory, and their statistics across the instances.  Any chunk_steps, record or not, gives the same bits.  For the fused laws.
     After the call the mechanism's bodies hold instance 0's final state (simulate! mutates the mechanism)."""
     if isinstance(controller, PolicyValue):
         raise TypeError("a PolicyValue is not a Controller: simulate rolls out the controller it evaluates (PolicyValue.controller)")
@@ -1630,7 +1714,7 @@ def simulate(mechanism, tend_or_storage, controller, record=True, z0=None, fric=
         steps = int(math.ceil(tend_or_storage / mechanism.Δt))     # steps = 1:ceil(tend/Δt)
     nb = len(mechanism.bodies)
     z0 = mechanism.state()[None] if z0 is None else np.asarray(z0, dtype=np.float64).reshape(-1, nb, 13)
-    if score is None and ensemble is None and joints is None and chunk_steps is not None:
+    if score is None and ensemble is None and joints is None and invariants is None and chunk_steps is not None:
         raise ValueError("chunk_steps is an option of score= and ensemble=")
     if score is not None:
         if not isinstance(score, Score):
@@ -1667,7 +1751,19 @@ def simulate(mechanism, tend_or_storage, controller, record=True, z0=None, fric=
         if joints.quantiles and z0.shape[0] > _capi.QUANTILE_MAX_INST:
             raise ValueError("quantiles= are taken over at most %d instances per run (got %d): the moments of shards merge, their order statistics do not"
                              % (_capi.QUANTILE_MAX_INST, z0.shape[0]))
-    if score is not None or ensemble is not None or joints is not None:
+    if invariants is not None:
+        if not isinstance(invariants, Invariants):
+            raise TypeError("invariants= takes an Invariants(mechanism, keep=True, rows=False, quantiles=())")
+        if getattr(controller, "controlfunction", None) is not None:
+            raise ValueError("invariants= with a custom controlfunction is not supported: the invariants pass runs behind the launches of the fused laws")
+        if invariants.mechanism is not mechanism:
+            raise ValueError("the Invariants was made for another mechanism")
+        if steps < 1:
+            raise ValueError("invariants= needs at least one step")
+        if invariants.quantiles and z0.shape[0] > _capi.QUANTILE_MAX_INST:
+            raise ValueError("quantiles= are taken over at most %d instances per run (got %d): the moments of shards merge, their order statistics do not"
+                             % (_capi.QUANTILE_MAX_INST, z0.shape[0]))
+    if score is not None or ensemble is not None or joints is not None or invariants is not None:
         if chunk_steps is None:
             chunk_steps = _capi.default_chunk_steps(z0.shape[0], nb, steps)
         if int(chunk_steps) < 1:
@@ -1682,8 +1778,8 @@ def simulate(mechanism, tend_or_storage, controller, record=True, z0=None, fric=
     if (noise is not None or noise_seed is not None) and noise_scale is None:
         noise_scale = 1.0
     ph = None if plants is None else plants.handle(dev)
-    scores = stats = series = None
-    if score is not None or ensemble is not None or joints is not None:
+    scores = stats = series = checks = None
+    if score is not None or ensemble is not None or joints is not None or invariants is not None:
         ctrl = controller._ctrl_handle(dev, fric=fric, noise_scale=0.0 if noise_scale is None else noise_scale, noise_seed=noise_seed)
         sh = None
         try:
@@ -1692,8 +1788,13 @@ def simulate(mechanism, tend_or_storage, controller, record=True, z0=None, fric=
             ens = None if ensemble is None else ((ctrl.mu, ensemble.cov_knots) + ((ensemble.quantiles,) if ensemble.quantiles else ()))
             jnt = None if joints is None else (joints.continuous, joints.rates, joints.keep, joints.quantiles)
             got = _capi.rollout_scored(dev, ctrl, sh, z0, steps, int(chunk_steps), noise=noise, first_instance=first_instance, plants=ph, traj_out=traj, ensemble=ens,
-                                       **({} if jnt is None else dict(joints=jnt)))
+                                       **({} if jnt is None else dict(joints=jnt)),
+                                       **({} if invariants is None else dict(invariants=(invariants.keep, invariants.rows, invariants.quantiles))))
             zT, status, scores = got[:3]
+            if invariants is not None:
+                v, got = got[-1], got[:-1]
+                checks = InvariantSeries(v["count"], v["summary"], v["mean"], v["M2"], v["series"], v["g"],
+                                         **(dict(probs=v["probs"], quantiles=v["quantiles"], finite_count=v["finite_count"]) if invariants.quantiles else {}))
             if joints is not None:
                 j = got[-1]
                 series = JointSeries(j["count"], j["mean"], j["M2"], j["rate_mean"], j["rate_M2"], j["theta"], j["rate"], continuous=j["continuous"],
@@ -1726,11 +1827,13 @@ def simulate(mechanism, tend_or_storage, controller, record=True, z0=None, fric=
         tend_or_storage.score = scores
         tend_or_storage.ensemble = stats
         tend_or_storage.joints = series
+        tend_or_storage.invariants = checks
         return tend_or_storage
     out = Storage(steps, nb, z0.shape[0], traj if record else np.zeros((z0.shape[0], 0, nb, 13)), status, zT)
     out.score = scores
     out.ensemble = stats
     out.joints = series
+    out.invariants = checks
     return out
 
 

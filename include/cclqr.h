@@ -66,7 +66,8 @@ extern "C" {
  * Still 202 (additive, no struct changed): the quantiles of a slab ACROSS its instances at every step -- cclqr_rollout_quantiles_ws_bytes, cclqr_rollout_quantiles; looked up
  * the same way.  cclqr_rollout_ensemble is unchanged.
  * Still 202 (additive, no struct changed): the joint coordinates of a slab and the statistics of any per-instance series -- cclqr_rollout_joints,
- * cclqr_series_ensemble_ws_bytes, cclqr_series_ensemble, cclqr_series_quantiles_ws_bytes, cclqr_series_quantiles; looked up the same way. */
+ * cclqr_series_ensemble_ws_bytes, cclqr_series_ensemble, cclqr_series_quantiles_ws_bytes, cclqr_series_quantiles; looked up the same way.
+ * Still 202 (additive, no struct changed): the integrator's invariants of a slab -- cclqr_rollout_invariants; looked up the same way. */
 #define CCLQR_ABI_VERSION 202
 
 #define CCLQR_REVOLUTE 0      /* EqualityConstraint(Revolute(a, b, axis; p1, p2, qoffset)),  examples/lqr_cartpole.jl:26 */
@@ -773,6 +774,46 @@ int cclqr_rollout_joints(const cclqr_mech *m, const cclqr_plants *plants, int64_
                          const double *traj_dev, int32_t mode, int64_t out_steps,
                          double *theta_dev /* [n_inst][out_steps][ne] */, double *rate_dev /* same shape, or NULL */,
                          double *carry_dev /* [n_inst][ne][2]; mode 1 only, else NULL */, void *stream);
+
+/* The integrator's own invariants of a rollout on the device (additive, still 202, no struct changed; looked up by name like the entries above): can this run be
+ * trusted?  A variational integrator in maximal coordinates promises closed joints, unit quaternions and an energy that oscillates without drift (SURVEY.md,
+ * "Integrator invariants"); this call measures all three at every row of a slab, and keeps an eight-number verdict per instance for runs whose states are gone.
+ * The definition.  For instance i and slab row r (absolute step k = k0 + r, as cclqr_rollout_joints indexes) take the row's 13 entries per body AS STORED: x 0..2,
+ * q 3..6, v 7..9, ω 10..12 (body frame).  m_b, J_b, p1, p2 are the mechanism's, or -- with a cclqr_plants handle -- those of the plant record cclqr_rollout_plants
+ * would read for the global index first_instance + i.  inv_dev [i][k - 1][0..5]:
+ *     0  T      Σ_b ( ½ m_b v_b·v_b + ½ ω_b·(J_b ω_b) )
+ *     1  V      -g Σ_b m_b x_b[2]                      g: the mechanism's signed g
+ *     2  E      T + V, that one addition of outputs 0 and 1
+ *     3  gap    max |g_r| over all TRANSLATIONAL constraint rows of all joints
+ *     4  twist  max |g_r| over all ROTATIONAL rows
+ *     5  quat   max_b | q_b·q_b - 1 |
+ * g_r are the rows the rollout's Newton solve drives to zero: R(q_a)'(x_b + R(q_b) p2 - x_a) - p1 and vec(conj(q_a) q_b conj(qoff)), picked by the mechanism's row
+ * selectors (a revolute has 3 translational and 2 rotational rows, a prismatic joint 2 and 3); the origin is x = 0, q = 1.  A CCLQR_FIXED_ORIENTATION constraint of a
+ * loop mechanism contributes its rotational rows and no translational ones; rows a joint does not have count as 0.
+ * rows_dev [i][k - 1][j][0..4], optional: g of joint j in the CALLER'S joint order, five rows per joint, rows the joint does not have 0.
+ * Summation order of T and V: one term per link in the library's link order (parents first, chain by chain; loop mechanisms: the caller's body order), padded with
+ * zeros to the next of 8, 16, 32, 64 terms, added by the xor butterfly v_t += v_{t xor o}, o = 1, 2, 4, ...  Adding a zero is exact: the bits depend on the link
+ * order alone.
+ * Values that are not finite: anything not finite that enters an output makes THAT output NaN -- never Inf -- and nothing else.  The max PROPAGATES a NaN: one
+ * constraint row or quaternion that is not finite makes gap / twist / quat of that step NaN.  In rows_dev such a row is NaN.
+ * summary_dev [i][0..7], accumulated across launches: initialised when k0 == 1, read and merged when k0 > 1, always written:
+ *     0     E at the first row where it is finite (NaN until one is seen)
+ *     1, 2  min and max of E over the rows where it is finite (NaN until one is seen)
+ *     3     max of gap over the rows where it is finite (NaN until one is seen)
+ *     4     the absolute step k at which 3 was first reached (0 if there is no such row)
+ *     5, 6  max of twist, of quat over their finite rows (NaN until one is seen)
+ *     7     the number of rows with any of the six outputs not finite
+ * Min, max and "first" do not depend on how the horizon is cut: any chunk plan gives the bits of one call.  energy_drift = max(E_max - E_1, E_1 - E_min) is the host's.
+ * The call writes rows k0 - 1 .. k0 + steps - 2 of inv_dev / rows_dev only.  Device pointers; asynchronous on `stream`; nothing is allocated.  Every topology
+ * cclqr_mech_create takes, loops included; plants on chains and trees.  CCLQR_EINVAL, before anything is launched, with the cause in cclqr_last_error and the outputs
+ * untouched: n_inst < 1, steps < 1, k0 < 1, out_steps < k0 + steps - 1 when inv_dev or rows_dev is given, a null traj_dev, all three outputs NULL, plants made for
+ * another mechanism or device or not covering first_instance .. first_instance + n_inst - 1. */
+#define CCLQR_INVARIANTS_LEN 6
+#define CCLQR_INVARIANTS_SUMMARY_LEN 8
+int cclqr_rollout_invariants(const cclqr_mech *m, const cclqr_plants *plants, int64_t n_inst, int32_t steps, int32_t k0, int64_t first_instance,
+                             const double *traj_dev, int64_t out_steps,
+                             double *inv_dev /* [n_inst][out_steps][6], or NULL */, double *rows_dev /* [n_inst][out_steps][ne][5], or NULL */,
+                             double *summary_dev /* [n_inst][8], or NULL; read when k0 > 1 */, void *stream);
 
 /* The statistics of any per-instance series x_dev [n_inst][steps][nc] ACROSS its instances, per step (additive, still 202; looked up by name): what
  * cclqr_rollout_ensemble / cclqr_rollout_quantiles compute, with x GIVEN instead of formed -- the joint series above (the fan chart of a swing-up in joint angles, the

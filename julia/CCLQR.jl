@@ -499,6 +499,22 @@ function rollout_joints!(h::MechHandle, p, n::Integer, steps::Integer, k0::Integ
                 h.ptr, p === nothing ? C_NULL : p.ptr, n, steps, k0, first_instance, traj, mode, out_steps, theta, rate, carry, stream))
 end
 
+const INVARIANTS_LEN = 6
+const INVARIANTS_SUMMARY_LEN = 8
+
+"The integrator's invariants of the slab a rollout_dev! launch has just written (cclqr_rollout_invariants; device pointers, asynchronous on `stream`): inv is
+ 6 x out_steps x n -- per instance and absolute step T, V, E = T + V, the largest translational and the largest rotational constraint residual over all joints and
+ the largest |q.q - 1| over the bodies --, rows 5 x ne x out_steps x n the constraint rows themselves (the caller's joint order), summary 8 x n per instance
+ (E at the first finite row, min E, max E, max gap, its step, max twist, max quat, rows that are not finite), which is read when k0 > 1 and so travels from launch
+ to launch.  Columns k0 : k0 + steps - 1 are written; any of the three may be C_NULL, not all.  p: a PlantsHandle or nothing."
+function rollout_invariants!(h::MechHandle, p, n::Integer, steps::Integer, k0::Integer, traj::Ptr{Float64}, out_steps::Integer;
+                             inv::Ptr{Float64} = Ptr{Float64}(C_NULL), rows::Ptr{Float64} = Ptr{Float64}(C_NULL), summary::Ptr{Float64} = Ptr{Float64}(C_NULL),
+                             first_instance = 0, stream::Ptr{Cvoid} = C_NULL)
+    check(ccall((:cclqr_rollout_invariants, lib), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int32, Int32, Int64, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Cvoid}),
+                h.ptr, p === nothing ? C_NULL : p.ptr, n, steps, k0, first_instance, traj, out_steps, inv, rows, summary, stream))
+end
+
 "Bytes of device workspace one series_ensemble! call of these sizes needs (cclqr_series_ensemble_ws_bytes)."
 function series_ensemble_ws_bytes(n::Integer, steps::Integer, nc::Integer)
     out = Ref{Csize_t}(0)
